@@ -2,8 +2,14 @@
 """Headline benchmark: IQL gradient steps/sec, batch 256, 1M-transition device
 replay buffer (BASELINE.json configs[1], antmaze-medium-diverse-v2 shapes).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the headline record.  `--full` adds
+everything else the benchmark measures, each leg after the headline and never as it: the per-kernel
+breakdown and roofline, the sustained region, seeds sharing a GPU, the E-critic ensemble, the pen
+and general-step shapes, the reward-relabel kernels and the CPU baseline.  `--dump-outputs DIR`
+writes the networks the last timed step left behind as DIR/<net>.<param>.npy (float32).
 
 One step = ReplayBuffer.sample + ImplicitQLearning.train (V/Q/actor updates,
 Polyak, cosine LR) = reference iql.py:1535-1536.  Every rank trains its own seed
@@ -14,13 +20,13 @@ the all-gather of the per-rank metric record).  Rank 0 prints ONE JSON line.
 processes itself (one per GPU, RCCL), before anything touches a GPU -- the
 reference's process-per-GPU model (ensemble_sweeps/launch.sh:84-94).
 
-Timing: W untimed warm-up steps, then blocks of EXACTLY K steps -- plain kernel
+Timing: W untimed warm-up steps, then ONE block of EXACTLY K steps -- plain kernel
 launches from the library's C loop (the default; hipGraphs of --unroll steps on
 request: every graph launch costs ~5 us of device time that back-to-back kernels
 do not, and the GPU starts with the first launch instead of behind the host's
 work for a 60-node graph: 318-322 us against 322-325 us per 20-step block) --
-bracketed by barrier + synchronize on both sides.  The block is repeated until >= 0.25 s of
-timed work has accumulated; `ms_per_step` is the median block (max over ranks)
+bracketed by barrier + synchronize on both sides.  `--min-timed-s S` repeats the block until
+>= S s of timed work has accumulated; `ms_per_step` is the median block (max over ranks)
 divided by K, `value` = N * K / that block time.
 """
 import argparse
@@ -78,6 +84,15 @@ def build_trainer(ia, torch, device, seed, precision, n_critics=2, dims=None, dr
     return ia.ImplicitQLearning(
         max_action=1.0, actor=actor, actor_optimizer=ao, q_network=q, q_optimizer=qo,
         v_network=v, v_optimizer=vo, device=device, precision=precision, seed=seed, **(hyper or HYPER))
+
+
+def dump_outputs(tr, out_dir):
+    """What the timed steps hand a caller: the trained networks (fp32 masters of the actor, the
+    twin Q and V, and the Polyak target), one DIR/<net>.<param>.npy each, 1.8 MB at the headline shapes."""
+    os.makedirs(out_dir, exist_ok=True)
+    for net, mod in (("actor", tr.actor), ("qf", tr.qf), ("vf", tr.vf), ("q_target", tr.q_target)):
+        for name, t in mod.state_dict().items():
+            np.save(os.path.join(out_dir, f"{net}.{name}.npy"), t.detach().float().cpu().numpy())
 
 
 # BASELINE configs[2] (pen-human-v1, configs/offline/iql/pen/human_v1.yaml: actor_dropout 0.1, beta 3,
@@ -289,21 +304,29 @@ def main():
                          "from the library's C loop, the faster mode for one seed (66.9k against 66.1k steps/s with "
                          "graphs of 50 steps; 20-step blocks 62.6k against 61.7k as one graph); "
                          "negative: ONE graph of min(-unroll, steps) steps (the round-2 behaviour, for A/B)")
-    ap.add_argument("--min-timed-s", type=float, default=0.25,
-                    help="the K-step block is repeated until this much timed work has accumulated")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--min-timed-s", type=float, default=0.0,
+                    help="0 (the default): ONE timed block of exactly K steps; > 0: the K-step block is repeated "
+                         "until this much timed work has accumulated (timing.timed_steps_total = reps x K)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the networks they left behind (actor, twin Q, V and the "
+                         "Polyak target, float32) as DIR/<net>.<param>.npy; rank 0's trainer")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, every other figure: per-kernel breakdown and roofline, sustained "
+                         "region, the extra legs below and the CPU baseline (each can be disabled by its option)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baseline (--full only)")
     ap.add_argument("--no-sustained", action="store_true",
-                    help="skip the long comparison region (rocprofv3 --pmc passes: its 60k queued dispatches "
-                         "overrun the profiler's intercepted queue)")
+                    help="skip the long comparison region (--full only; rocprofv3 --pmc passes: its 60k queued "
+                         "dispatches overrun the profiler's intercepted queue)")
     ap.add_argument("--ensemble-q", type=int, default=4,
-                    help="extra leg (N=1 only): BASELINE configs[4], an E-critic ensemble at batch 1024 "
+                    help="extra leg (--full, N=1 only): BASELINE configs[4], an E-critic ensemble at batch 1024 "
                          "(same antmaze shapes); 0 disables.  Reported beside `value`, never as it")
     ap.add_argument("--agents-per-gpu", type=int, default=8,
-                    help="extra leg (N=1 only): aggregate steps/s of this many independent seeds sharing "
+                    help="extra leg (--full, N=1 only): aggregate steps/s of this many independent seeds sharing "
                          "the GPU -- the reference launcher's AGENTS_PER_GPU "
                          "(ensemble_sweeps/launch.sh:12); 0 disables.  `value` is always 1 seed per GPU")
-    ap.add_argument("--no-relabel", action="store_true", help="skip the reward-relabel leg (N=1 only)")
-    ap.add_argument("--no-pen", action="store_true", help="skip the config-3 (pen shapes + dropout) training leg (N=1 only)")
+    ap.add_argument("--no-relabel", action="store_true", help="skip the reward-relabel leg (--full, N=1 only)")
+    ap.add_argument("--no-pen", action="store_true",
+                    help="skip the config-3 (pen shapes + dropout) training leg (--full, N=1 only)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -341,7 +364,6 @@ def main():
 
     import iqlpref_amd as ia
     from iqlpref_amd import _lib
-    import ctypes as C
 
     seed = 1 + rank  # independent seed + dataset per rank
     data = synth_dataset(seed)
@@ -367,7 +389,8 @@ def main():
             dist.barrier()
 
     run(args.warmup)
-    run(K)  # untimed: instantiates the K-step graph the timed blocks replay
+    if unroll:
+        run(K)  # untimed: instantiates the K-step graph the timed blocks replay
     torch.cuda.synchronize()
 
     # ---- timed blocks of exactly K steps ----
@@ -394,6 +417,8 @@ def main():
         if stop.item() > 0:
             break
     reps = len(block_s)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(tr, args.dump_outputs)
     last = tr.train_steps(buf, 1, BATCH, graph_unroll=0).cpu().numpy()[0]
     if not np.isfinite(last).all():
         raise SystemExit(f"non-finite losses after the timed region: {last}")
@@ -413,60 +438,7 @@ def main():
     dev_ms_med = float(np.median(block_dev_ms))
 
     if rank == 0:
-        cfg = tr._cfg(BATCH)
-        bytes_step, flops_step = C.c_double(), C.c_double()
-        _lib.check(_lib.load().iqlhip_step_cost(C.byref(cfg), C.byref(bytes_step), C.byref(flops_step)))
         steps_per_s = world * K / dt_med
-        step_us_dev = dev_ms_med * 1e3 / K
-        # per-kernel breakdown (diagnostic pass with HIP events around every launch)
-        lib = _lib.load()
-        _lib.check(lib.iqlhip_trainer_set_timing(tr._handle, 1))
-        tr.train_steps(buf, 300, BATCH, return_losses=False, graph_unroll=0)
-        avg = (C.c_double * 3)()
-        nl = C.c_int64()
-        _lib.check(lib.iqlhip_trainer_get_timing(tr._handle, C.byref(avg), C.byref(nl)))
-        _lib.check(lib.iqlhip_trainer_set_timing(tr._handle, 0))
-        # algorithmic bytes: the gather term belongs to k_forward, every
-        # parameter / moment / target byte is moved by k_update -- the dominant kernel
-        gather_bytes = 4.0 * BATCH * (2 * S_DIM + A_DIM + 2)
-        upd_bytes = bytes_step.value - gather_bytes
-        # HIP events on the launch stream give each kernel's share of a step; the shares are
-        # scaled so that the three launches tile the measured device time per step, which is how
-        # rocprofv3 --kernel-trace attributes the timeline (dispatch to completion, back to back)
-        ev_us = [avg[k] * 1e3 for k in range(3)]
-        scale = step_us_dev / sum(ev_us) if sum(ev_us) > 0 else 1.0
-        upd_us = ev_us[2] * scale
-        traffic, traffic_src = None, None
-        tname = os.environ.get("IQL_TRAFFIC_PROFILE", f"{PROFILE_TAG}_traffic.json")
-        tpath = os.path.join(ROOT, "profiles", tname)
-        if not os.path.exists(tpath):  # (no set of this round yet: the last committed one, labelled as such)
-            tname = "r03_traffic.json"
-            tpath = os.path.join(ROOT, "profiles", tname)
-        if os.path.exists(tpath):  # PMC passes (separate rocprofv3 --pmc runs, tools/profile.sh)
-            with open(tpath) as f:
-                tj = json.load(f)
-            traffic = tj.get("k_update_bytes_per_launch")
-            traffic_src = {"file": f"profiles/{tname}", "build": tj.get("build"),
-                           "note": "PMC (2*FETCH_SIZE + WRITE_SIZE) of an earlier rocprofv3 run of this "
-                                   "command; not collected in this timed run",
-                           "matches_this_build": tj.get("build") == _lib.build_tag()}
-        live_mode = (f"hipGraphs of {unroll} steps" if unroll else "plain kernel launches from the library's C loop") + \
-            "; HIP-event shares of 300 eager steps scaled to tile the measured device time per step"
-        roof = roofline_block("k_update", upd_bytes, upd_us, live_mode, f"{PROFILE_TAG}_kernel_stats.csv",
-                              ("k_update<true, true>",), "hipGraphs of 50 steps under rocprofv3 --kernel-trace --stats "
-                              "(plain launches are paced by the tracer's per-dispatch interception)", _lib.build_tag(),
-                              extra={"traffic": traffic, "traffic_source": traffic_src,
-                                     "launch_us": upd_us, "launch_us_events_only": ev_us[2], "launches_timed": int(nl.value),
-                                     "step": {"bytes_per_step": bytes_step.value, "device_us_per_step": step_us_dev,
-                                              "achieved_gbs": bytes_step.value / (step_us_dev * 1e-6) / 1e9,
-                                              "frac": bytes_step.value / (step_us_dev * 1e-6) / 1e9 / HBM_PEAK_GBS,
-                                              "kernel_us": {"k_forward": ev_us[0] * scale, "k_backward": ev_us[1] * scale,
-                                                            "k_update": ev_us[2] * scale},
-                                              "kernel_us_events_only": {"k_forward": ev_us[0], "k_backward": ev_us[1],
-                                                                        "k_update": ev_us[2]},
-                                              "mfma_tflops": flops_step.value / (step_us_dev * 1e-6) / 1e12,
-                                              "mfma_peak_tflops": MFMA_BF16_PEAK_TFLOPS if args.precision == "bf16"
-                                              else MFMA_F32_PEAK_TFLOPS}})
         out = {
             "metric": "iql_grad_steps_per_sec", "value": steps_per_s, "unit": "steps/s",
             "n_gpus": world, "steps": K, "warmup": args.warmup,
@@ -485,112 +457,173 @@ def main():
                        "note": "each block = K steps between barrier+synchronize pairs; median block, "
                                "max over ranks; *_device = HIP events on the launch stream"},
             "build": _lib.build_tag(),
-            "roofline": roof,
         }
         if recs is not None:
             out["ranks"] = recs
-        if world == 1 and K < 5_000 and not args.no_sustained:
-            # the same path sustained over a long region, for comparison with the K-step blocks
-            n_long = 20_000 // unroll * unroll if unroll else 20_000
-            torch.cuda.synchronize()
-            t1 = time.perf_counter()
-            run(n_long)
-            torch.cuda.synchronize()
-            out["sustained"] = {"steps": n_long, "value": n_long / (time.perf_counter() - t1), "unit": "steps/s",
-                                "note": "one timed region of this many steps, same launch mode; not `value`"}
-        # (secondary legs: none of them may take the headline record down with it)
-        if world == 1 and args.agents_per_gpu > 1:
-            try:
-                out["agents_per_gpu"] = agents_leg(ia, torch, tr, buf, device, seed, args, unroll, bytes_step.value)
-            except Exception as e:
-                out["agents_per_gpu"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and args.agents_per_gpu > 1:
-            # the same aggregate through the PRODUCT entry point: train(config, seeds_per_gpu=K)
-            # (iqlpref_amd/train.py; ensemble_sweeps/launch.sh:12 AGENTS_PER_GPU), log windows of 2500 steps
-            try:
-                out["train_seeds_per_gpu"] = train_leg(ia, data, device, args)
-            except Exception as e:
-                out["train_seeds_per_gpu"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and args.ensemble_q >= 2:
-            try:
-                E_ = args.ensemble_q
-                tre = build_trainer(ia, torch, device, seed + 50, args.precision, n_critics=E_)
-                leg = step_leg(ia, torch, _lib, tre, buf, 1024, 5_000, 50, f"{PROFILE_TAG}_ens{E_}_kernel_stats.csv",
-                               ("k_update<true, false>",), f"k_update (E = {E_} critics, batch 1024)")
-                out["ensemble_q"] = dict(leg, n_critics=E_, batch=1024, transitions_per_s=1024 * leg["value"],
-                                         note="BASELINE configs[4] (E-way critic ensemble, batch 1024, antmaze "
-                                              "shapes); not `value`")
-                del tre
-            except Exception as e:
-                out["ensemble_q"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not args.no_pen:
-            try:
-                S_, A_ = PEN["dims"]
-                bufp = ia.ReplayBuffer(S_, A_, PEN["n_rows"], device)
-                bufp.load_d4rl_dataset(synth_dataset_dims(seed + 70, PEN["n_rows"], S_, A_))
-                trp = build_trainer(ia, torch, device, seed + 70, args.precision, dims=PEN["dims"],
-                                    dropout=PEN["dropout"], hyper=PEN["hyper"])
-                leg = step_leg(ia, torch, _lib, trp, bufp, BATCH, 20_000, 0, f"{PROFILE_TAG}_pen_kernel_stats.csv",
-                               ("k_update<true, true>",), "k_update (pen shapes S=45 A=24, actor dropout 0.1)")
-                out["pen_config3"] = dict(leg, batch=BATCH, buffer_rows=PEN["n_rows"],
-                                          note="BASELINE configs[2] training step (pen-human-v1 shapes and hyper-"
-                                               "parameters, Philox dropout masks); its relabel half is "
-                                               "relabel.pt_pen_config3; not `value`")
-                del trp, bufp
-            except Exception as e:
-                out["pen_config3"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not args.no_pen:
-            # a shape off the tuned step's (three hidden layers instead of two, ref:458-459 n_hidden): the general
-            # layer-wise step (csrc/iql_deep.hip), plain launches; its update kernel's share of the HBM roofline
-            # from HIP events only (no committed trace)
-            try:
-                import ctypes as C
-                trg = build_trainer(ia, torch, device, seed + 90, args.precision, n_hidden=3)
-                assert trg.step_kind(BATCH) == "general"
-                trg.train_steps(buf, 500, BATCH, return_losses=False)
-                torch.cuda.synchronize()
-                t1 = time.perf_counter()
-                trg.train_steps(buf, 5_000, BATCH, return_losses=False)
-                torch.cuda.synchronize()
-                dtg = time.perf_counter() - t1
-                evg, _ = kernel_times(_lib, trg, buf, BATCH, 200)
-                byg, flg = C.c_double(), C.c_double()
-                cfgg = trg._cfg(BATCH)
-                _lib.check(_lib.load().iqlhip_step_cost(C.byref(cfgg), C.byref(byg), C.byref(flg)))
-                gath = 4.0 * BATCH * (2 * cfgg.state_dim + cfgg.action_dim + 2)
-                out["general_step"] = {
-                    "value": 5_000 / dtg, "unit": "steps/s", "us_per_step": dtg / 5_000 * 1e6, "n_hidden": 3,
-                    "hidden_dim": 256, "batch": BATCH, "bytes_per_step": byg.value,
-                    "kernel_us_events": {"kd_forward": evg[0], "kd_backward": evg[1], "kd_update": evg[2]},
-                    "roofline": roofline_block("kd_update (three hidden layers of 256 units)", byg.value - gath, evg[2],
-                                               "plain launches; HIP events around each kernel",
-                                               f"{PROFILE_TAG}_general_kernel_stats.csv", ("kd_update<true",),
-                                               "plain launches under rocprofv3 --kernel-trace", _lib.build_tag()),
-                    "note": "the general layer-wise step on a shape the tuned three-kernel step does not take "
-                            "(coverage path); not `value`"}
-                tpg = os.path.join(ROOT, "profiles", f"{PROFILE_TAG}_general_traffic.json")
-                if os.path.exists(tpg):  # PMC bytes of a separate rocprofv3 run (tools/profile.sh)
-                    with open(tpg) as f:
-                        tjg = json.load(f)
-                    out["general_step"]["roofline"]["traffic"] = tjg.get("kd_update_bytes_per_launch")
-                    out["general_step"]["roofline"]["traffic_source"] = {
-                        "file": f"profiles/{PROFILE_TAG}_general_traffic.json", "build": tjg.get("build"),
-                        "matches_this_build": tjg.get("build") == _lib.build_tag()}
-                del trg
-            except Exception as e:
-                out["general_step"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not args.no_relabel:
-            try:
-                from tools import bench_relabel
-                out["relabel"] = bench_relabel.leg(device)
-            except Exception as e:  # the leg must never take the headline down with it
-                out["relabel"] = {"error": f"{type(e).__name__}: {e}"}
-        if not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(data)
+        if args.full:
+            full_legs(out, args, ia, torch, _lib, tr, buf, data, device, seed, world, K, unroll, run,
+                      dev_ms_med * 1e3 / K)
         print(json.dumps(out), file=json_out, flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def full_legs(out, args, ia, torch, _lib, tr, buf, data, device, seed, world, K, unroll, run, step_us_dev):
+    """--full: every figure beside the headline, added to its record `out` on rank 0 after the timed
+    steps -- the per-kernel breakdown and roofline of the headline step, then the secondary legs."""
+    import ctypes as C
+    cfg = tr._cfg(BATCH)
+    bytes_step, flops_step = C.c_double(), C.c_double()
+    _lib.check(_lib.load().iqlhip_step_cost(C.byref(cfg), C.byref(bytes_step), C.byref(flops_step)))
+    # per-kernel breakdown (diagnostic pass with HIP events around every launch)
+    lib = _lib.load()
+    _lib.check(lib.iqlhip_trainer_set_timing(tr._handle, 1))
+    tr.train_steps(buf, 300, BATCH, return_losses=False, graph_unroll=0)
+    avg = (C.c_double * 3)()
+    nl = C.c_int64()
+    _lib.check(lib.iqlhip_trainer_get_timing(tr._handle, C.byref(avg), C.byref(nl)))
+    _lib.check(lib.iqlhip_trainer_set_timing(tr._handle, 0))
+    # algorithmic bytes (SURVEY.md 8d): the gather term belongs to k_forward, every
+    # parameter / moment / target byte is moved by k_update -- the dominant kernel
+    gather_bytes = 4.0 * BATCH * (2 * S_DIM + A_DIM + 2)
+    upd_bytes = bytes_step.value - gather_bytes
+    # HIP events on the launch stream give each kernel's share of a step; the shares are
+    # scaled so that the three launches tile the measured device time per step, which is how
+    # rocprofv3 --kernel-trace attributes the timeline (dispatch to completion, back to back)
+    ev_us = [avg[k] * 1e3 for k in range(3)]
+    scale = step_us_dev / sum(ev_us) if sum(ev_us) > 0 else 1.0
+    upd_us = ev_us[2] * scale
+    traffic, traffic_src = None, None
+    tname = os.environ.get("IQL_TRAFFIC_PROFILE", f"{PROFILE_TAG}_traffic.json")
+    tpath = os.path.join(ROOT, "profiles", tname)
+    if not os.path.exists(tpath):  # (no set of this round yet: the last committed one, labelled as such)
+        tname = "r03_traffic.json"
+        tpath = os.path.join(ROOT, "profiles", tname)
+    if os.path.exists(tpath):  # PMC passes (separate rocprofv3 --pmc runs, tools/profile.sh)
+        with open(tpath) as f:
+            tj = json.load(f)
+        traffic = tj.get("k_update_bytes_per_launch")
+        traffic_src = {"file": f"profiles/{tname}", "build": tj.get("build"),
+                       "note": "PMC (2*FETCH_SIZE + WRITE_SIZE) of an earlier rocprofv3 run of this "
+                               "command; not collected in this timed run",
+                       "matches_this_build": tj.get("build") == _lib.build_tag()}
+    live_mode = (f"hipGraphs of {unroll} steps" if unroll else "plain kernel launches from the library's C loop") + \
+        "; HIP-event shares of 300 eager steps scaled to tile the measured device time per step"
+    roof = roofline_block("k_update", upd_bytes, upd_us, live_mode, f"{PROFILE_TAG}_kernel_stats.csv",
+                          ("k_update<true, true>",), "hipGraphs of 50 steps under rocprofv3 --kernel-trace --stats "
+                          "(plain launches are paced by the tracer's per-dispatch interception)", _lib.build_tag(),
+                          extra={"traffic": traffic, "traffic_source": traffic_src,
+                                 "launch_us": upd_us, "launch_us_events_only": ev_us[2], "launches_timed": int(nl.value),
+                                 "step": {"bytes_per_step": bytes_step.value, "device_us_per_step": step_us_dev,
+                                          "achieved_gbs": bytes_step.value / (step_us_dev * 1e-6) / 1e9,
+                                          "frac": bytes_step.value / (step_us_dev * 1e-6) / 1e9 / HBM_PEAK_GBS,
+                                          "kernel_us": {"k_forward": ev_us[0] * scale, "k_backward": ev_us[1] * scale,
+                                                        "k_update": ev_us[2] * scale},
+                                          "kernel_us_events_only": {"k_forward": ev_us[0], "k_backward": ev_us[1],
+                                                                    "k_update": ev_us[2]},
+                                          "mfma_tflops": flops_step.value / (step_us_dev * 1e-6) / 1e12,
+                                          "mfma_peak_tflops": MFMA_BF16_PEAK_TFLOPS if args.precision == "bf16"
+                                          else MFMA_F32_PEAK_TFLOPS}})
+    out["roofline"] = roof
+    if world == 1 and K < 5_000 and not args.no_sustained:
+        # the same path sustained over a long region, for comparison with the K-step blocks
+        n_long = 20_000 // unroll * unroll if unroll else 20_000
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        run(n_long)
+        torch.cuda.synchronize()
+        out["sustained"] = {"steps": n_long, "value": n_long / (time.perf_counter() - t1), "unit": "steps/s",
+                            "note": "one timed region of this many steps, same launch mode; not `value`"}
+    # (secondary legs: none of them may take the headline record down with it)
+    if world == 1 and args.agents_per_gpu > 1:
+        try:
+            out["agents_per_gpu"] = agents_leg(ia, torch, tr, buf, device, seed, args, unroll, bytes_step.value)
+        except Exception as e:
+            out["agents_per_gpu"] = {"error": f"{type(e).__name__}: {e}"}
+    if world == 1 and args.agents_per_gpu > 1:
+        # the same aggregate through the PRODUCT entry point: train(config, seeds_per_gpu=K)
+        # (iqlpref_amd/train.py; ensemble_sweeps/launch.sh:12 AGENTS_PER_GPU), log windows of 2500 steps
+        try:
+            out["train_seeds_per_gpu"] = train_leg(ia, data, device, args)
+        except Exception as e:
+            out["train_seeds_per_gpu"] = {"error": f"{type(e).__name__}: {e}"}
+    if world == 1 and args.ensemble_q >= 2:
+        try:
+            E_ = args.ensemble_q
+            tre = build_trainer(ia, torch, device, seed + 50, args.precision, n_critics=E_)
+            leg = step_leg(ia, torch, _lib, tre, buf, 1024, 5_000, 50, f"{PROFILE_TAG}_ens{E_}_kernel_stats.csv",
+                           ("k_update<true, false>",), f"k_update (E = {E_} critics, batch 1024)")
+            out["ensemble_q"] = dict(leg, n_critics=E_, batch=1024, transitions_per_s=1024 * leg["value"],
+                                     note="BASELINE configs[4] (E-way critic ensemble, batch 1024, antmaze "
+                                          "shapes); not `value`")
+            del tre
+        except Exception as e:
+            out["ensemble_q"] = {"error": f"{type(e).__name__}: {e}"}
+    if world == 1 and not args.no_pen:
+        try:
+            S_, A_ = PEN["dims"]
+            bufp = ia.ReplayBuffer(S_, A_, PEN["n_rows"], device)
+            bufp.load_d4rl_dataset(synth_dataset_dims(seed + 70, PEN["n_rows"], S_, A_))
+            trp = build_trainer(ia, torch, device, seed + 70, args.precision, dims=PEN["dims"],
+                                dropout=PEN["dropout"], hyper=PEN["hyper"])
+            leg = step_leg(ia, torch, _lib, trp, bufp, BATCH, 20_000, 0, f"{PROFILE_TAG}_pen_kernel_stats.csv",
+                           ("k_update<true, true>",), "k_update (pen shapes S=45 A=24, actor dropout 0.1)")
+            out["pen_config3"] = dict(leg, batch=BATCH, buffer_rows=PEN["n_rows"],
+                                      note="BASELINE configs[2] training step (pen-human-v1 shapes and hyper-"
+                                           "parameters, Philox dropout masks); its relabel half is "
+                                           "relabel.pt_pen_config3; not `value`")
+            del trp, bufp
+        except Exception as e:
+            out["pen_config3"] = {"error": f"{type(e).__name__}: {e}"}
+    if world == 1 and not args.no_pen:
+        # a shape off the tuned step's (three hidden layers instead of two, ref:458-459 n_hidden): the general
+        # layer-wise step (csrc/iql_deep.hip), plain launches; its update kernel's share of the HBM roofline
+        # from HIP events only (no committed trace)
+        try:
+            import ctypes as C
+            trg = build_trainer(ia, torch, device, seed + 90, args.precision, n_hidden=3)
+            assert trg.step_kind(BATCH) == "general"
+            trg.train_steps(buf, 500, BATCH, return_losses=False)
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            trg.train_steps(buf, 5_000, BATCH, return_losses=False)
+            torch.cuda.synchronize()
+            dtg = time.perf_counter() - t1
+            evg, _ = kernel_times(_lib, trg, buf, BATCH, 200)
+            byg, flg = C.c_double(), C.c_double()
+            cfgg = trg._cfg(BATCH)
+            _lib.check(_lib.load().iqlhip_step_cost(C.byref(cfgg), C.byref(byg), C.byref(flg)))
+            gath = 4.0 * BATCH * (2 * cfgg.state_dim + cfgg.action_dim + 2)
+            out["general_step"] = {
+                "value": 5_000 / dtg, "unit": "steps/s", "us_per_step": dtg / 5_000 * 1e6, "n_hidden": 3,
+                "hidden_dim": 256, "batch": BATCH, "bytes_per_step": byg.value,
+                "kernel_us_events": {"kd_forward": evg[0], "kd_backward": evg[1], "kd_update": evg[2]},
+                "roofline": roofline_block("kd_update (three hidden layers of 256 units)", byg.value - gath, evg[2],
+                                           "plain launches; HIP events around each kernel",
+                                           f"{PROFILE_TAG}_general_kernel_stats.csv", ("kd_update<true",),
+                                           "plain launches under rocprofv3 --kernel-trace", _lib.build_tag()),
+                "note": "the general layer-wise step on a shape the tuned three-kernel step does not take "
+                        "(coverage path); not `value`"}
+            tpg = os.path.join(ROOT, "profiles", f"{PROFILE_TAG}_general_traffic.json")
+            if os.path.exists(tpg):  # PMC bytes of a separate rocprofv3 run (tools/profile.sh)
+                with open(tpg) as f:
+                    tjg = json.load(f)
+                out["general_step"]["roofline"]["traffic"] = tjg.get("kd_update_bytes_per_launch")
+                out["general_step"]["roofline"]["traffic_source"] = {
+                    "file": f"profiles/{PROFILE_TAG}_general_traffic.json", "build": tjg.get("build"),
+                    "matches_this_build": tjg.get("build") == _lib.build_tag()}
+            del trg
+        except Exception as e:
+            out["general_step"] = {"error": f"{type(e).__name__}: {e}"}
+    if world == 1 and not args.no_relabel:
+        try:
+            from tools import bench_relabel
+            out["relabel"] = bench_relabel.leg(device)
+        except Exception as e:  # the leg must never take the headline down with it
+            out["relabel"] = {"error": f"{type(e).__name__}: {e}"}
+    if not args.no_cpu_baseline:
+        out["cpu_baseline"] = cpu_baseline(data)
 
 
 def train_leg(ia, data, device, args):

@@ -10,8 +10,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WORKER = r'''
 import os, sys, json
 sys.path.insert(0, sys.argv[1])
+import torch
 import torch.distributed as dist
 from iqlpref_amd import distributed as D
+# CPU only: the worker sees no GPU, also on a machine that has one
+torch.cuda.is_available = lambda: False
 # rank -> GPU mapping (pure part; there is no GPU here, so local_device() binds nothing)
 assert D.device_for_rank(int(os.environ["LOCAL_RANK"]), 8) == "cuda:" + os.environ["LOCAL_RANK"]
 assert D.local_device() is None
@@ -81,9 +84,12 @@ def test_rank_to_gpu_mapping():
 
 
 def test_bench_refuses_fewer_gpus_than_asked(tmp_path):
-    """bench.py --gpus 2 from plain `python` starts the ranks itself; with fewer visible GPUs it
-    exits non-zero instead of benchmarking one rank (no GPU here: 0 visible)."""
+    """bench.py --gpus N from plain `python` starts the ranks itself; with fewer visible GPUs it
+    exits non-zero instead of benchmarking fewer ranks (no GPU: --gpus 2, 0 visible; else one more
+    than are visible)."""
+    import torch
+    visible = torch.cuda.device_count()
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20",
-                        "--warmup", "5"], env=env, capture_output=True, text=True, timeout=300)
-    assert p.returncode != 0 and "only 0 GPU(s) are visible" in p.stderr and p.stdout.strip() == ""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(max(2, visible + 1)),
+                        "--steps", "20", "--warmup", "5"], env=env, capture_output=True, text=True, timeout=300)
+    assert p.returncode != 0 and f"only {visible} GPU(s) are visible" in p.stderr and p.stdout.strip() == ""

@@ -1,7 +1,7 @@
 # The same traced command several times on one box (is the tracer's pacing stable?):
 #   AB_N=6 bash tools/ab_trace.sh        optionally AB_LIB=<variant .so under iqlpref_amd/> alternates with the product build
 export TMPDIR=/tmp
-ARGS="--unroll 50 --no-cpu-baseline --no-relabel --no-pen --agents-per-gpu 0 --ensemble-q 0 --min-timed-s 0.05"
+ARGS="--full --unroll 50 --no-cpu-baseline --no-relabel --no-pen --agents-per-gpu 0 --ensemble-q 0 --min-timed-s 0.05"
 run() {
   rm -rf /tmp/tr_x
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/tr_x -- python bench.py --steps 3000 --warmup 300 $ARGS > /tmp/tr.json 2>/dev/null

@@ -29,7 +29,7 @@ for what in "$@"; do
       timeout -k 10 300 python tools/bench_relabel.py --cpu > $OUT/relabel.json 2> $OUT/relabel.err
       rc=$?; echo "relabel rc=$rc"; stop_if_killed $rc relabel; cat $OUT/relabel.json | head -120 ;;
     bench)
-      timeout -k 10 400 python bench.py > $OUT/bench.json 2> $OUT/bench.err
+      timeout -k 10 400 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
       rc=$?; echo "bench rc=$rc"; stop_if_killed $rc bench; python -c "
 import json; d=json.loads(open('$OUT/bench.json').read().strip().splitlines()[-1])
 print('value', round(d['value']), d['roofline']['step']['kernel_us'], 'frac', round(d['roofline']['frac'],3))
@@ -40,13 +40,13 @@ print('agents', d.get('agents_per_gpu',{}).get('value'), 'ensemble', d.get('ense
     waitmode)
       # host wait policy at the end of a timed block: HIP's active-wait window (us) before it blocks on the interrupt
       for round in 1 2; do for w in 0 100 10000; do
-        ROC_ACTIVE_WAIT_TIMEOUT=$w timeout -k 10 200 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-relabel --agents-per-gpu 0 --ensemble-q 0 2>/dev/null |
+        ROC_ACTIVE_WAIT_TIMEOUT=$w timeout -k 10 200 python bench.py --gpus 1 --steps 20 --warmup 5 --min-timed-s 0.25 --no-cpu-baseline --no-relabel --agents-per-gpu 0 --ensemble-q 0 2>/dev/null |
           python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('wait', $w, round(d['value']), d['ms_per_step'], d['timing']['ms_per_step_device'])" || exit 1
       done; done ;;
     unrollscan)
       # steps per hipGraph inside the driver's 20-step timed block: when does the GPU see its first packet
       for round in 1 2; do for u in 20 10 5 4 2 1; do
-        timeout -k 10 200 python bench.py --gpus 1 --steps 20 --warmup 5 --unroll $u --no-cpu-baseline --no-relabel --agents-per-gpu 0 --ensemble-q 0 2>/dev/null |
+        timeout -k 10 200 python bench.py --gpus 1 --steps 20 --warmup 5 --min-timed-s 0.25 --unroll $u --no-cpu-baseline --no-relabel --agents-per-gpu 0 --ensemble-q 0 2>/dev/null |
           python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('unroll', $u, round(d['value']), d['ms_per_step'], d['timing']['ms_per_step_device'])" || exit 1
       done; done ;;
     mlpscan)

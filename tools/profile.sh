@@ -10,7 +10,7 @@ OUT=$PWD/gpurun_out/prof_$TAG
 # (--unroll 50: the traced runs replay hipGraphs of 50 steps.  bench.py's default, plain kernel launches,
 # is paced by the tracer's per-dispatch interception -- ~6 us per launch, 18.7 us per step instead of
 # 14.9 -- and the "durations" of kernels that tile the step then measure the tool, not the kernels.)
-ARGS="--unroll 50 --no-cpu-baseline --no-relabel --no-pen --agents-per-gpu 0 --ensemble-q 0 --min-timed-s 0.05"
+ARGS="--full --unroll 50 --no-cpu-baseline --no-relabel --no-pen --agents-per-gpu 0 --ensemble-q 0 --min-timed-s 0.05"
 mkdir -p $OUT
 # which library the set was collected on (bench.py labels every profile-derived figure with it)
 python -c "from iqlpref_amd import _lib; import json; print(json.dumps({'build': _lib.build_tag(), 'tag': '$TAG'}))" > $OUT/meta.json
