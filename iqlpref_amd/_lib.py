@@ -7,7 +7,8 @@ import ctypes as C
 import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-# IQLHIP_LIB: load another build of the same library (A/B measurements of kernel variants)
+# IQLHIP_LIB: load another build of the same library (tools/ab.sh: two revisions A/B on one box;
+# tools/stamps.py: the diagnostic build)
 LIB_PATH = os.environ.get("IQLHIP_LIB") or os.path.join(HERE, "libiqlhip.so")
 
 PREC_FP32 = 0

@@ -314,8 +314,9 @@ static int n_critics(const iqlhip_trainer_config &c) { return c.n_critics > 0 ? 
 static int n_hidden(const iqlhip_trainer_config &c) { return c.n_hidden > 0 ? c.n_hidden : 2; }
 // which step runs this shape: the tuned three-kernel one or the general layer-wise one
 static bool is_deep(const iqlhip_trainer_config &c) {
-  return n_hidden(c) != 2 || (c.hidden_dim != 64 && c.hidden_dim != 128 && c.hidden_dim != 256) ||
-         getenv("IQLHIP_FORCE_GENERAL") != nullptr;  // (tests: the general step on a shape the tuned one takes)
+  // (tests: the general step on a shape the tuned one takes)
+  static const bool force_general = getenv("IQLHIP_FORCE_GENERAL") != nullptr;
+  return n_hidden(c) != 2 || (c.hidden_dim != 64 && c.hidden_dim != 128 && c.hidden_dim != 256) || force_general;
 }
 
 static int check_cfg(const iqlhip_trainer_config *c) {
@@ -470,9 +471,8 @@ static std::vector<UpdItem> flatten_table(const std::vector<UpdItem> (&per_xcd)[
 // 37.5k steps/s, E = 8 at batch 256 41.0k -> 42.4k.
 static void deal_items(const iqlhip_trainer *t, int member, int group_size, std::vector<UpdItem> (&per_xcd)[8]) {
   const int NT = t->D.ntrain;
-  static const int forced = getenv("IQLHIP_ITEM_TABLE") ? atoi(getenv("IQLHIP_ITEM_TABLE")) : -1;  // A/B: 0 / 1 forces
   const bool group = group_size > 1;
-  const bool whole = forced >= 0 ? (forced != 0 && group) : (group && group_size % 8 == 0);
+  const bool whole = group && group_size % 8 == 0;
   if (whole && NT == 4) {
     for (int n = 0; n < NT; ++n)
       for (auto &it : t->net_items[n]) per_xcd[(2 * n + member) & 7].push_back(it);
@@ -496,9 +496,8 @@ static void deal_items(const iqlhip_trainer *t, int member, int group_size, std:
   // dispatcher deals an XCD's work-groups over its CUs in order, so rows 32.. of a column land on the CUs of
   // rows 0..: those d CUs carry two work-groups, and what a CU takes in per microsecond bounds a work-group
   // (DESIGN.md section 4).  Put the d lightest items first and the next d lightest last, the heavy layer-2
-  // tiles in between: no CU gets two heavy ones.  (IQLHIP_ITEM_ORDER=0: the order of the networks.)
-  static const bool reorder = !(getenv("IQLHIP_ITEM_ORDER") && atoi(getenv("IQLHIP_ITEM_ORDER")) == 0);
-  if (!group && reorder) {
+  // tiles in between: no CU gets two heavy ones.
+  if (!group) {
     constexpr size_t CUS_PER_XCD = 32;
     auto weight = [](const UpdItem &it) { return it.layer == 1 ? 3 : (it.layer == 0 ? 2 : 1); };  // layer-2 tile / strip / layer-3 tile
     for (auto &col : per_xcd) {

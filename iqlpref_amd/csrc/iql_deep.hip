@@ -21,7 +21,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdlib>
 #include <cstring>
 #include <new>
 #include <vector>
@@ -451,7 +450,7 @@ __device__ __forceinline__ void deep_misc(const DeepDesc &D, const DeepStep &A) 
     const float sd = expf(fminf(fmaxf(p, -20.f), 2.f));
     const float g = inside ? gs * sd : 0.f;
     if (D.grads) stg(D.grads + o, g);
-    adam_apply<(BF16 && IQL_ADAM_FAST)>(p, m, v, g, A.coef, A.coef.neg_step[2]);
+    adam_apply<BF16>(p, m, v, g, A.coef, A.coef.neg_step[2]);
     stg(D.params + o, p), stg(D.exp_avg + o, m), stg(D.exp_avg_sq + o, v);
   }
 }
@@ -467,7 +466,6 @@ __global__ __launch_bounds__(256) void kd_update(const DeepDesc *__restrict__ Dp
                                                  const DeepStep A) {
   using P = Prec<BF16>;
   using T = typename P::T;
-  constexpr bool AF = BF16 && IQL_ADAM_FAST;
   const DeepDesc &D = *Dp;
   const DeepItem it = items[blockIdx.x];
   if (it.net < 0) {
@@ -557,7 +555,7 @@ __global__ __launch_bounds__(256) void kd_update(const DeepDesc *__restrict__ Dp
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         g[i] = P::round(acc[t][i]);  // parameter gradients are the bf16 results widened (autocast)
-        adam_apply<AF>(p[i], m[i], v[i], g[i], coef, neg_step);
+        adam_apply<BF16>(p[i], m[i], v[i], g[i], coef, neg_step);
         if (has_target) tg[i] = polyak(PK, tg[i], p[i]);
       }
       if (Pg) stg16(Pg + o, make_float4(g[0], g[1], g[2], g[3]));
@@ -587,7 +585,7 @@ __global__ __launch_bounds__(256) void kd_update(const DeepDesc *__restrict__ Dp
           const int64_t o = off_w + (int64_t)n * Kn + k;
           float p = ldg(Pp + o), m = ldg(Pm + o), v = ldg(Pv + o);
           if (Pg) stg(Pg + o, g);
-          adam_apply<AF>(p, m, v, g, coef, neg_step);
+          adam_apply<BF16>(p, m, v, g, coef, neg_step);
           stg(Pp + o, p), stg(Pm + o, m), stg(Pv + o, v);
           stg(wc + fidx<P>(n, k, nkw), P::from_f32(p));
           if (wt) stg(wt + fidx<P>(k, n, nkt), P::from_f32(p));
@@ -611,7 +609,7 @@ __global__ __launch_bounds__(256) void kd_update(const DeepDesc *__restrict__ Dp
         const int64_t o = off_b + n;
         float p = ldg(Pp + o), m = ldg(Pm + o), v = ldg(Pv + o);
         if (Pg) stg(Pg + o, gs);
-        adam_apply<AF>(p, m, v, gs, coef, neg_step);
+        adam_apply<BF16>(p, m, v, gs, coef, neg_step);
         stg(Pp + o, p), stg(Pm + o, m), stg(Pv + o, v);
         if (has_target) {
           const int64_t to = toff_b + n;
@@ -688,7 +686,6 @@ hipError_t deep_create(DeepTrainer **out, const iqlhip_trainer_config &cfg, int 
   D.next_off = round_up(S + A + 2, 4);
   D.opad = round_up(A, 16);
   D.nslab = B / 16;
-  const char *tq_env = getenv("IQLHIP_GENERAL_TQ");  // (A/B knob: 1 or 4; the rule sits with the item table below)
   D.deterministic = cfg.deterministic, D.has_dropout = cfg.dropout_p > 0.f, D.polyak_convex = cfg.polyak_form == 1;
   D.two_over_B = 2.0f / (float)B, D.inv_E = 1.0f / (float)E;
   D.discount = cfg.discount, D.tau = cfg.tau, D.beta = cfg.beta, D.iql_tau = cfg.iql_tau;
@@ -740,14 +737,13 @@ hipError_t deep_create(DeepTrainer **out, const iqlhip_trainer_config &cfg, int 
   add(sizeof(DeepDesc));
   // update items.  Tile width (kd_update<.., TQ>): 64 x 64 tiles where the operand panels are the traffic (batch
   // >= 1024) or the matrices are large (width >= 768) AND such tiles still make ~150 work-groups; 64 x 16 otherwise
-  // (measured with IQLHIP_GENERAL_TQ, tools/general_run.py: E = 4 / batch 1024 with three hidden layers, 216 wide
+  // (measured with tools/general_run.py: E = 4 / batch 1024 with three hidden layers, 216 wide
   // tiles: 26.4 us against 32.1; with two, 144: 25.7 against 18.6; width 1024: 43.9 against 46.5)
   {
     int wide = 0;
     for (int n = 0; n < NT; ++n)
       for (int l = 0; l < NL; ++l) wide += ((D.net[n].N[l] + 63) / 64) * ((D.net[n].K[l] + 63) / 64);
     t->tq = ((D.BP >= 1024 || D.Hp >= 768) && wide >= 150) ? 4 : 1;
-    if (tq_env) t->tq = atoi(tq_env) == 1 ? 1 : 4;
   }
   std::vector<DeepItem> items;
   for (int n = 0; n < NT; ++n)

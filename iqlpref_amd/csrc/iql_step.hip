@@ -34,8 +34,6 @@
 // both operands of dW = dZ^T X are K(batch)-contiguous 16-byte fragments, and
 // the MFMA C/D layout (4 consecutive rows per lane) stores them with 8/16-byte
 // writes.
-#include <cstdlib>
-
 #include "common.h"
 #include "iql_step.h"
 #include "step_math.h"
@@ -131,54 +129,24 @@ __device__ __forceinline__ void store4T(typename Prec<BF16>::T *dst, const float
   }
 }
 
-// IQL_WT_ACT (A/B build): the bf16 activations / deltas one kernel hands to the next leave
-// write-through (8-byte stores, lean bf16 paths only).
-#ifndef IQL_WT_ACT
-#define IQL_WT_ACT 0
-#endif
-__device__ __forceinline__ void act_store8(uint16_t *base, size_t elem, uint2 u) {
-#if IQL_WT_ACT
-  stg8_wt(base, (uint32_t)elem * 2u, u);
-#else
-  stg8(base + elem, u);
-#endif
-}
-// IQL_WT_FWD8: the forward's 8-byte hidden-activation stores (16-row work-groups) write-through -- the
-// forward's, not the backward's (IQL_WT_ACT covers both: no gain).  A/B on one box
-// (round 4, f5, three rounds): one seed 66.1k -> 67.0k steps/s, two seeds equal.
-#ifndef IQL_WT_FWD8
-#define IQL_WT_FWD8 1
-#endif
+__device__ __forceinline__ void act_store8(uint16_t *base, size_t elem, uint2 u) { stg8(base + elem, u); }
+// The forward's 8-byte hidden-activation stores (16-row work-groups) write-through -- the forward's, not
+// the backward's (both: no gain).  Round 4, f5: one seed 66.1k -> 67.0k steps/s.
 __device__ __forceinline__ void act_store8_fwd(uint16_t *base, size_t elem, uint2 u) {
-#if IQL_WT_FWD8
   stg8_wt(base, (uint32_t)elem * 2u, u);
-#else
-  act_store8(base, elem, u);
-#endif
 }
 
 // The packed bf16 C-layout registers of two row tiles m (even) and m + 1 of one feature column, stored
 // to a feature-major plane as ONE 16-byte store per lane (permlane16_swap): the lane of row group q
 // ends up with rows 16 (m + (q & 1)) + 4 (q & ~1) .. + 7 of its column.  Same bytes at the same
 // addresses as two act_store8 calls.
-// IQL_WT_ACT16: these 16-byte stores leave write-through (sc0 sc1).  A wave's store instruction covers one
-// whole 1 KiB fragment (8 full lines), so nothing is merged in L2 anyway, and what a kernel leaves dirty
-// is written back at its END, by the L2s of the few XCDs that hold it: in-kernel stamps (round 4, four
-// critics at batch 1024, plain stores) show the last forward work-group done 7.0 us after the first
-// started and the first backward work-group stamping at +12.3 us -- 7 MB of activations leaving six L2s;
-// with these stores the two are 1.6 us apart.
-// A/B on one box (round 4, d2): four critics at batch 1024 31.2k -> 35.3k steps/s, 8 seeds per launch
-// 208.7k -> 220.3k (throughput kernels), 4 seeds 156.5k -> 168.0k (k_forward<.., 2, 2>), one seed
-// unchanged (66.1k: its 16-row work-groups have no tile pairs).  -DIQL_WT_ACT16=0 builds plain stores.
-#ifndef IQL_WT_ACT16
-#define IQL_WT_ACT16 1
-#endif
+// These 16-byte stores leave write-through (sc0 sc1).  A wave's store instruction covers one whole 1 KiB
+// fragment (8 full lines), so nothing is merged in L2 anyway, and what a kernel leaves dirty is written
+// back at its END: with plain stores, in-kernel stamps (four critics at batch 1024) show the first backward
+// work-group 5.3 us after the last forward one is done; write-through, 1.6 us.  Round 4, d2: four critics
+// at batch 1024 31.2k -> 35.3k steps/s, 8 seeds per launch 208.7k -> 220.3k.
 __device__ __forceinline__ void act_store16(uint16_t *plane, size_t elem, uint4 v) {
-#if IQL_WT_ACT16
   stg16_wt(plane, (uint32_t)elem * 2u, __builtin_bit_cast(float4, v));
-#else
-  stg16(plane + elem, __builtin_bit_cast(float4, v));
-#endif
 }
 __device__ __forceinline__ void act_store16_pair(uint16_t *plane, int col, int row_m, int q, int nkb, uint2 um,
                                                  uint2 um1) {
@@ -503,8 +471,8 @@ struct FCfg {
   static_assert(HQ == 64, "one 16-column tile per wave and part");
 };
 
-template <bool BF16, int H, int MT, int PW, bool PRE>
-__global__ __launch_bounds__(256, PRE ? 1 : (MT >= 4 ? 2 : 3)) void k_forward(const TrainerDesc *__restrict__ Dp,
+template <bool BF16, int H, int MT, int PW>
+__global__ __launch_bounds__(256, 3) void k_forward(const TrainerDesc *__restrict__ Dp,
                                                  const DevArgs *__restrict__ Ap,
                                                  const DevCtr *__restrict__ Cp, const int nsl_,
                                                  const int nfwd_) {
@@ -598,12 +566,10 @@ __global__ __launch_bounds__(256, PRE ? 1 : (MT >= 4 ? 2 : 3)) void k_forward(co
 #pragma unroll
   for (int jt = 0; jt < 2; ++jt)  // clamped (used for col < out_dim)
     bias3[jt] = ldg(N.b3 + (16 * jt + r < N.out_dim ? 16 * jt + r : N.out_dim - 1));
+  // Layer 2's fragments are requested behind the layer-1 product and layer 3's behind the layer-2
+  // product, not all up front: a third fewer live registers, three work-groups per CU instead of two.
+  // Measured faster everywhere: 63.7k vs 62.5k steps/s for one seed, 164.6k vs 157.3k for a group of 8.
   uint4 w1[C::NK1][TPW], w2[PW][C::NK2], w3[PW][C::NK3][2];
-  // PRE requests the fragments of all three layers up front (the shortest chain on paper); the
-  // default requests layer 2 behind the layer-1 product and layer 3 behind the layer-2 product:
-  // a third fewer live registers, three work-groups per CU instead of two, and the other
-  // work-groups cover the wait.  Measured faster everywhere: 63.7k vs 62.5k steps/s for one seed,
-  // 164.6k vs 157.3k for a group of 8; only the just-in-time order is instantiated.
   auto load_w2 = [&]() {
 #pragma unroll
     for (int j = 0; j < PW; ++j) {
@@ -635,7 +601,6 @@ __global__ __launch_bounds__(256, PRE ? 1 : (MT >= 4 ? 2 : 3)) void k_forward(co
           w1[ks][jj] = ldg16(W1w + (size_t)(jj * nk1 + ks) * 64 * P::EPV + lane * P::EPV);
       }
     }
-    if constexpr (PRE) load_w2(), load_w3();
   }
   STAMP(0, 1);
 
@@ -681,11 +646,9 @@ __global__ __launch_bounds__(256, PRE ? 1 : (MT >= 4 ? 2 : 3)) void k_forward(co
         }
       }
     }
-    if constexpr (!PRE) {
-      __builtin_amdgcn_sched_barrier(0);
-      load_w2();
-      __builtin_amdgcn_sched_barrier(0);
-    }
+    __builtin_amdgcn_sched_barrier(0);
+    load_w2();
+    __builtin_amdgcn_sched_barrier(0);
     bool lean = false;
     if constexpr (BF16) lean = !N.dropout;  // (wave-uniform) see relu_bias_bf16x4
 #pragma unroll
@@ -706,7 +669,7 @@ __global__ __launch_bounds__(256, PRE ? 1 : (MT >= 4 ? 2 : 3)) void k_forward(co
             hrow[2 * HP] = (T)(u[m].y & 0xffff), hrow[3 * HP] = (T)(u[m].y >> 16);
           }
           T *plane = reinterpret_cast<T *>(g_hT) + (size_t)(N.train_slot * 2 + 0) * H * BP;
-          if constexpr (MT >= 2 && !IQL_WT_ACT) {  // (two row tiles = 16 contiguous bytes per lane: one store)
+          if constexpr (MT == 2) {  // (two row tiles = 16 contiguous bytes per lane: one store)
             if (mine && slab * ROWS + ROWS <= B) {
 #pragma unroll
               for (int m = 0; m < MT; m += 2) act_store16_pair(plane, col, slab * ROWS + 16 * m, q, BP / P::KM, u[m], u[m + 1]);
@@ -758,11 +721,9 @@ __global__ __launch_bounds__(256, PRE ? 1 : (MT >= 4 ? 2 : 3)) void k_forward(co
         for (int j = 0; j < PW; ++j) P::mma(a, w2[j][ks], acc[j][m]);
       }
     }
-    if constexpr (!PRE) {
-      __builtin_amdgcn_sched_barrier(0);
-      load_w3();
-      __builtin_amdgcn_sched_barrier(0);
-    }
+    __builtin_amdgcn_sched_barrier(0);
+    load_w3();
+    __builtin_amdgcn_sched_barrier(0);
     bool lean = false;
     if constexpr (BF16) lean = !N.dropout;
 #pragma unroll
@@ -781,7 +742,7 @@ __global__ __launch_bounds__(256, PRE ? 1 : (MT >= 4 ? 2 : 3)) void k_forward(co
             hrow[2 * HQP] = (T)(u[m].y & 0xffff), hrow[3 * HQP] = (T)(u[m].y >> 16);
           }
           T *plane = reinterpret_cast<T *>(g_hT) + (size_t)(N.train_slot * 2 + 1) * H * BP;
-          if constexpr (MT >= 2 && !IQL_WT_ACT) {
+          if constexpr (MT == 2) {
             if (N.train_slot >= 0 && slab * ROWS + ROWS <= B) {
 #pragma unroll
               for (int m = 0; m < MT; m += 2) act_store16_pair(plane, col, slab * ROWS + 16 * m, q, BP / P::KM, u[m], u[m + 1]);
@@ -964,12 +925,9 @@ __global__ __launch_bounds__(512, 1) void k_forward_tp(const TrainerDesc *__rest
       }
     }
   }
-  // IQL_FTP_LATE: where the 136 KB of W2 / W3 fragments enter the vector-memory queue -- 0: up front (the
-  // waves stall issuing them and reach the input barrier late); 1: behind the input barrier, ahead of the
-  // layer-1 product; 2: behind the layer-1 product (k_forward's order)
-#ifndef IQL_FTP_LATE
-#define IQL_FTP_LATE 0
-#endif
+  // the 136 KB of W2 / W3 fragments enter the vector-memory queue up front too, not behind the input
+  // barrier or the layer-1 product (k_forward's order).  (A lambda: written out in place, the same loads
+  // compile to a different register allocation.)
   auto load_w23 = [&]() {
 #pragma unroll
     for (int jj = 0; jj < TPW; ++jj) {
@@ -984,7 +942,7 @@ __global__ __launch_bounds__(512, 1) void k_forward_tp(const TrainerDesc *__rest
       for (int jt = 0; jt < 2; ++jt)
         if (jt < nt3) w3[ks][jt] = ldg16(W3w + (size_t)(jt * NK2 + ks) * 64 * P::EPV + lane * P::EPV);
   };
-  if (IQL_FTP_LATE == 0) load_w23();
+  load_w23();
   STAMP(0, 1);
 
   // ---- layer-1 input into LDS ----
@@ -1003,11 +961,6 @@ __global__ __launch_bounds__(512, 1) void k_forward_tp(const TrainerDesc *__rest
   }
   __syncthreads();
   STAMP(0, 2);
-  if (IQL_FTP_LATE == 1) {
-    __builtin_amdgcn_sched_barrier(0);
-    load_w23();
-    __builtin_amdgcn_sched_barrier(0);
-  }
 
   // DROP = false: the lean bf16 epilogues only (relu_bias_bf16x4); the instantiation with dropout
   // carries the Philox masks.  The host picks by the trainer's has_dropout; a network without dropout
@@ -1032,11 +985,6 @@ __global__ __launch_bounds__(512, 1) void k_forward_tp(const TrainerDesc *__rest
       }
     }
     STAMP(0, 6);
-    if (IQL_FTP_LATE == 2) {
-      __builtin_amdgcn_sched_barrier(0);
-      load_w23();
-      __builtin_amdgcn_sched_barrier(0);
-    }
 #pragma unroll
     for (int jj = 0; jj < TPW; ++jj) {
       const int col = 16 * (tile0 + jj) + r;
@@ -1222,7 +1170,7 @@ constexpr int FIN_LD = 64;  // LDS row stride of the finished outputs
 // phase for all H hidden units (dZ2 is the GEMM's K operand) and streams H x 64 of W2^T.
 // The parts share the stores: part p writes its 64 columns of dZ2, part 0 writes dZ3 and the
 // loss partial sums.
-// PW parts per work-group (1, 2 or 4; PW divides SPL): with the chip full anyway (seed groups) the
+// PW parts per work-group (1 or 2, dividing SPL): with the chip full anyway (seed groups) the
 // redundant loss / dZ2 phases are pure cost -- a work-group then owns PW x 64 columns of dZ1, every
 // wave PW n-tiles, and there are SPL / PW work-groups per (net, slab).  The same values either way.
 // ========================================================================
@@ -1327,7 +1275,7 @@ __device__ __forceinline__ void backward_body(const TrainerDesc *__restrict__ Dp
   }
   __builtin_amdgcn_sched_barrier(0);
   // PRE: the operands of the closing GEMM are requested here, ahead of everything; otherwise
-  // behind the dZ2 phase (fewer live registers, more work-groups per CU; A/B: IQLHIP_BWD_PRE)
+  // behind the dZ2 phase (fewer live registers, more work-groups per CU; launch_backward picks)
   uint4 w2t[PW][K::NK2];
   float h1v[PW][4];
   auto load_gemm_operands = [&]() {
@@ -1433,7 +1381,7 @@ __device__ __forceinline__ void backward_body(const TrainerDesc *__restrict__ Dp
     const bool mine = (c2 / C::HQ) / PW == part;  // the part (group) that owns this hidden unit stores its dZ2
     bool lean = false;
     if constexpr (BF16) lean = !drop_on;  // mask before the rounding (the same value), packed conversion
-    if constexpr (BF16 && !IQL_WT_ACT) {
+    if constexpr (BF16) {
       if (lean) {
         // rows 8 h .. 8 h + 7 of a hidden unit are 16 contiguous bytes of the feature-major plane: two
         // 16-byte stores per thread instead of four 8-byte ones (store instructions, not bytes, bound
@@ -1459,19 +1407,7 @@ __device__ __forceinline__ void backward_body(const TrainerDesc *__restrict__ Dp
     }
 #pragma unroll
     for (int g4 = 0; g4 < 4; ++g4) {
-      if (lean) {
-        if constexpr (BF16 && IQL_WT_ACT) {
-          float t[4];
-#pragma unroll
-          for (int i = 0; i < 4; ++i) t[i] = h2v[4 * g4 + i] > 0.f ? s[4 * g4 + i] : 0.f;
-          const uint2 u = make_uint2(pk_bf16(t[0], t[1]), pk_bf16(t[2], t[3]));
-          T *drow = dz2s + (4 * g4) * HP + c2;
-          drow[0] = (T)(u.x & 0xffff), drow[HP] = (T)(u.x >> 16);
-          drow[2 * HP] = (T)(u.y & 0xffff), drow[3 * HP] = (T)(u.y >> 16);
-          if (mine) act_store8(dst, fidx<P>(c2, slab * SLAB + 4 * g4, nkb), u);
-        }
-        continue;
-      }
+      if (lean) continue;  // (stored above)
       float outv[4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -1648,13 +1584,6 @@ __global__ __launch_bounds__(512, 1) void k_backward_tp(const TrainerDesc *__res
   const int tile0 = wave * TPW;
   uint4 w2t[TPW][K::NK2];
   float h1v[TPW][2][4];
-  // IQL_BTP_LATE: where the 128 KB of W2^T enter the vector-memory queue -- 0: up front, behind the
-  // loss inputs (the waves stall issuing them and reach the loss phase's barriers late); 1: behind the
-  // finished forward outputs; 2: behind the loss terms.  A/B on one box (round 4, e5; steps/s for four
-  // critics at batch 1024 / 8 seeds per launch): 37.6k / 224.4k, 37.8k / 226.4k, 37.7k / 226.4k.
-#ifndef IQL_BTP_LATE
-#define IQL_BTP_LATE 1
-#endif
   auto load_gemm_operands = [&]() {
 #pragma unroll
     for (int t = 0; t < TPW; ++t) {
@@ -1667,7 +1596,6 @@ __global__ __launch_bounds__(512, 1) void k_backward_tp(const TrainerDesc *__res
                          fidx<P>(16 * (tile0 + t) + r, (slab32 * 2 + m) * SLAB + 4 * q, nkb), h1v[t][m]);
     }
   };
-  if (IQL_BTP_LATE == 0) load_gemm_operands();
   STAMP(1, 1);
 
   // ---- finish the forward outputs of this slab (sum of the parts, rounding, tanh) ----
@@ -1682,11 +1610,11 @@ __global__ __launch_bounds__(512, 1) void k_backward_tp(const TrainerDesc *__res
       fin[frow * FIN_LD + col] = (col >= out_mean && col < out_mean + n_act) ? P::round(tanhf(v)) : v;
     }
   }
-  if (IQL_BTP_LATE == 1) {
-    __builtin_amdgcn_sched_barrier(0);
-    load_gemm_operands();
-    __builtin_amdgcn_sched_barrier(0);
-  }
+  // the 128 KB of W2^T enter the vector-memory queue here, behind the finished forward outputs (round 4,
+  // e5, four critics at batch 1024 / 8 seeds per launch: 37.8k / 226.4k steps/s; up front 37.6k / 224.4k)
+  __builtin_amdgcn_sched_barrier(0);
+  load_gemm_operands();
+  __builtin_amdgcn_sched_barrier(0);
   __syncthreads();
 
   // ---- per-row loss terms and d(loss)/d(out)  (ref:581-637) ----
@@ -1708,11 +1636,6 @@ __global__ __launch_bounds__(512, 1) void k_backward_tp(const TrainerDesc *__res
         if (j < out_dim) dz3[j * SLAB + lrow] = d3, lterm[j * SLAB + lrow] = lt, gstd[j * SLAB + lrow] = gs;
       }
     }
-  }
-  if (IQL_BTP_LATE == 2) {
-    __builtin_amdgcn_sched_barrier(0);
-    load_gemm_operands();
-    __builtin_amdgcn_sched_barrier(0);
   }
   __syncthreads();
   STAMP(1, 2);
@@ -1860,16 +1783,9 @@ __device__ __forceinline__ void write_adam_coef(const TrainerDesc &D, const DevA
 // boundary behind k_update costs + dirty bytes / 6 TB/s, MI355X_MICROARCH.md "boundary").  A/B on
 // one box (round 3, r4b): one seed 63.4k -> 64.9k steps/s (k_update 5.8 -> 5.4 us in the launch
 // tiling), 8 seeds per launch 171.2k -> 172.4k.  (`nt` stores, tried in round 2, are not
-// write-through: no effect.)  -DIQL_WT_STATE=0 builds the plain-store variant.
-#ifndef IQL_WT_STATE
-#define IQL_WT_STATE 1
-#endif
+// write-through: no effect.)
 __device__ __forceinline__ void state_store(const float *base, int64_t elem, float4 v) {  // uniform base, lane element
-#if IQL_WT_STATE
   stg16_wt(base, (uint32_t)elem * 4u, v);
-#else
-  stg16(base, (uint32_t)elem * 4u, v);
-#endif
 }
 
 // s += the 8 (bf16) / 4 (fp32) values of one 16-byte operand fragment, pairwise, in a fixed order
@@ -1885,27 +1801,8 @@ __device__ __forceinline__ void frag_acc(float &s, const uint4 &f) {
   }
 }
 
-// IQL_WT_ALL (A/B build): also the compute-precision copies and the layer-1 strips' state leave
-// write-through, so that k_update ends with (almost) nothing dirty in the L2s.
-#ifndef IQL_WT_ALL
-#define IQL_WT_ALL 0
-#endif
-template <bool BF16>
-__device__ __forceinline__ void copy_store4(typename Prec<BF16>::T *base, size_t elem, const float v[4]) {
-#if IQL_WT_ALL
-  using P = Prec<BF16>;
-  if constexpr (BF16) {
-    uint2 u;
-    u.x = (uint32_t)P::from_f32(v[0]) | ((uint32_t)P::from_f32(v[1]) << 16);
-    u.y = (uint32_t)P::from_f32(v[2]) | ((uint32_t)P::from_f32(v[3]) << 16);
-    stg8_wt(base, (uint32_t)elem * 2u, u);
-  } else {
-    stg16_wt(base, (uint32_t)elem * 4u, make_float4(v[0], v[1], v[2], v[3]));
-  }
-#else
-  store4T<BF16>(base + elem, v);
-#endif
-}
+// The compute-precision copies and the layer-1 strips' state use plain stores (written through as well:
+// 65.6k / 177.2k steps/s either way, round 3).
 // eight consecutive k of one row of a fragment-major copy: ONE 16-byte store in bf16 (a lane's whole
 // fragment slot), two in fp32 (elem4: the index of the second four)
 template <bool BF16>
@@ -1917,22 +1814,11 @@ __device__ __forceinline__ void copy_store8(typename Prec<BF16>::T *base, size_t
     u.y = (uint32_t)P::from_f32(v[2]) | ((uint32_t)P::from_f32(v[3]) << 16);
     u.z = (uint32_t)P::from_f32(v[4]) | ((uint32_t)P::from_f32(v[5]) << 16);
     u.w = (uint32_t)P::from_f32(v[6]) | ((uint32_t)P::from_f32(v[7]) << 16);
-#if IQL_WT_ALL
-    stg16_wt(base, (uint32_t)elem * 2u, __builtin_bit_cast(float4, u));
-#else
     stg16(base + elem, __builtin_bit_cast(float4, u));
-#endif
   } else {
-    copy_store4<BF16>(base, elem, v);
-    copy_store4<BF16>(base, elem4, v + 4);
+    store4T<BF16>(base + elem, v);
+    store4T<BF16>(base + elem4, v + 4);
   }
-}
-__device__ __forceinline__ void state_store1(float *base, int64_t elem, float v) {
-#if IQL_WT_ALL
-  stg4_wt(base, (uint32_t)elem * 4u, v);
-#else
-  stg(base + elem, v);
-#endif
 }
 
 constexpr int UKC = 8;  // batch k-steps per register chunk in the weight-gradient GEMM
@@ -1959,10 +1845,7 @@ constexpr int ULD = UTI + 4;     // LDS row stride (floats)
 constexpr int UTPR = UTI / 4;    // threads per tile row (float4 each)
 constexpr int UMAXI = 128;       // S + A <= 128 (host check)
 constexpr int UNIT = UMAXI / 16; // in-feature tiles of a layer-1 strip, at most
-#ifndef IQL_USR
-#define IQL_USR 16
-#endif
-constexpr int USR = IQL_USR;     // rows of a layer-1 strip (16 or 32)
+constexpr int USR = 16;          // rows of a layer-1 strip (32: one seed 65.7k -> 62.1k steps/s, round 3)
 constexpr int UOT = USR / 16;    // out-feature tiles of a strip
 constexpr int UPD_TILE = UTO * (UTI + 4) > USR * (UMAXI + 4) ? UTO * (UTI + 4) : USR * (UMAXI + 4);
 // (the second region: a strip's new target weights, or -- group launches -- a layer-2 tile's)
@@ -1975,7 +1858,6 @@ __device__ __forceinline__ void update_body(const TrainerDesc *__restrict__ Dp,
                                             const int blk) {
   using P = Prec<BF16>;
   using T = typename P::T;
-  constexpr bool AF = BF16 && IQL_ADAM_FAST != 0;  // (see adam_apply)
   constexpr int UWAVES = UT / 64;
   constexpr int URPP = UT / UTPR;                  // tile rows per pass
   constexpr int UNP = UTO / URPP;                  // passes
@@ -2025,7 +1907,7 @@ __device__ __forceinline__ void update_body(const TrainerDesc *__restrict__ Dp,
       const float lsc = fminf(fmaxf(ls, -20.f), 2.f);
       g = g * expf(lsc) * ((ls >= -20.f && ls <= 2.f) ? 1.f : 0.f);
       float p = ls;
-      adam_apply<AF>(p, pm, pv, g, coef, coef.neg_step[2]);
+      adam_apply<BF16>(p, pm, pv, g, coef, coef.neg_step[2]);
       stg(D.params + o, p), stg(D.exp_avg + o, pm), stg(D.exp_avg_sq + o, pv);
       if (D.grads) stg(D.grads + o, g);
     }
@@ -2247,14 +2129,14 @@ __device__ __forceinline__ void update_body(const TrainerDesc *__restrict__ Dp,
           const int ol = e / Idim, i = e - ol * Idim;
           const float g = P::round(tile[ol * TLD + i]);
           float p_ = pf[k], m_ = mf[k], v_ = vf[k];
-          adam_apply<AF>(p_, m_, v_, g, coef, neg_step);
+          adam_apply<BF16>(p_, m_, v_, g, coef, neg_step);
           tile[ol * TLD + i] = p_;
-          state_store1(g_params, fbase + e, p_), state_store1(g_m, fbase + e, m_), state_store1(g_v, fbase + e, v_);
+          stg(g_params + fbase + e, p_), stg(g_m + fbase + e, m_), stg(g_v + fbase + e, v_);
           if (g_grads) stg(g_grads + fbase + e, g);
           if (has_target) {
             const float t_ = polyak(D, tf[k], p_);
             tile2[ol * TLD + i] = t_;
-            state_store1(g_target, tbase + e, t_);
+            stg(g_target + tbase + e, t_);
           }
         }
       }
@@ -2271,7 +2153,7 @@ __device__ __forceinline__ void update_body(const TrainerDesc *__restrict__ Dp,
             const int e = 4 * e4 + j;
             const int ol = e / Idim, i = e - ol * Idim;
             g_[j] = P::round(tile[ol * TLD + i]);
-            adam_apply<AF>(p_[j], m_[j], v_[j], g_[j], coef, neg_step);
+            adam_apply<BF16>(p_[j], m_[j], v_[j], g_[j], coef, neg_step);
             tile[ol * TLD + i] = p_[j];
             if (has_target) {
               t_[j] = polyak(D, t_[j], p_[j]);
@@ -2289,7 +2171,7 @@ __device__ __forceinline__ void update_body(const TrainerDesc *__restrict__ Dp,
     if (tid < USR) {
       const int64_t e = it.off_b + o0 + tid;
       const float g = P::round(bgrad[tid]);
-      adam_apply<AF>(pb, mb, vb, g, coef, neg_step);
+      adam_apply<BF16>(pb, mb, vb, g, coef, neg_step);
       stg(g_params + e, pb), stg(g_m + e, mb), stg(g_v + e, vb);
       if (g_grads) stg(g_grads + e, g);
       if (has_target) stg(g_target + it.toff_b + o0 + tid, polyak(D, tb, pb));
@@ -2302,12 +2184,12 @@ __device__ __forceinline__ void update_body(const TrainerDesc *__restrict__ Dp,
       const int ol = e / cpr, i = (e - ol * cpr) * 4;
       const float4 p4 = *reinterpret_cast<const float4 *>(&tile[ol * TLD + i]);
       float pv4[4] = {p4.x, p4.y, p4.z, p4.w};
-      copy_store4<BF16>(wc, fidx<P>(o0 + ol, i, nkw), pv4);
+      store4T<BF16>(wc + fidx<P>(o0 + ol, i, nkw), pv4);
       if (has_target) {
         const float4 t4 = *reinterpret_cast<const float4 *>(&tile2[ol * TLD + i]);
         float tv4[4] = {i < Idim ? t4.x : 0.f, i + 1 < Idim ? t4.y : 0.f, i + 2 < Idim ? t4.z : 0.f,
                         i + 3 < Idim ? t4.w : 0.f};
-        copy_store4<BF16>(tc, fidx<P>(o0 + ol, i, nkw), tv4);
+        store4T<BF16>(tc + fidx<P>(o0 + ol, i, nkw), tv4);
       }
     }
     STAMP(2, 4);
@@ -2460,17 +2342,13 @@ __device__ __forceinline__ void update_body(const TrainerDesc *__restrict__ Dp,
     // GIF deep so that the registers stay below the 4-waves-per-SIMD budget; the other two waves,
     // which have no operands to hold, request their half of the optimiser state right away.
     // Every accumulator still sums its k-steps in ascending order: results are bit-identical.
-    #ifndef IQL_GW
-#define IQL_GW 2  // GEMM waves per tile (A/B: 1 = one wave loads every distinct fragment exactly once)
-#endif
-#ifndef IQL_GIF
-#define IQL_GIF (IQL_GW == 2 ? 4 : 3)  // k-steps in flight per GEMM wave (one more spills at the 128-register budget)
-#endif
-    constexpr int GW = IQL_GW, GNB = (UTO / 16) / GW, GNI = UTI / 16, GIF = IQL_GIF;
-    static_assert(UT == 256 && UTO == 64 && (GW == 1 || GW == 2), "the GEMM waves cover a 64-row tile");
+    // GW = 2 GEMM waves per tile (one, loading every distinct fragment exactly once: 19.7 us either way,
+    // round 3); GIF k-steps in flight per GEMM wave (one more spills at the 128-register budget)
+    constexpr int GW = 2, GNB = (UTO / 16) / GW, GNI = UTI / 16, GIF = 4;
+    static_assert(UT == 256 && UTO == 64, "the GEMM waves cover a 64-row tile");
     // (split batch: all four waves are GEMM waves -- wave pair `half` takes k-steps [half kh, ...) )
     const bool gemm_wave = ksplit || wave < GW;  // (scalar)
-    const int gw = wave & (GW - 1), half = ksplit ? wave / GW : 0;
+    const int gw = wave & 1, half = ksplit ? wave / GW : 0;
     const int kbeg = half ? kh : 0, kend = ksplit ? (half ? nk : kh) : nk;
     const bool wave_bias = do_bias && gemm_wave;
     f32x4 acc[GNB][GNI];
@@ -2481,16 +2359,10 @@ __device__ __forceinline__ void update_body(const TrainerDesc *__restrict__ Dp,
 #pragma unroll
       for (int c = 0; c < GNI; ++c) acc[b][c] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
-#ifndef IQL_G2_EARLY
-#define IQL_G2_EARLY 1
-#endif
     if (!gemm_wave) {
-#if IQL_G2_EARLY
       load_state();
-#endif
       STAMP(2, 1);
     } else {
-      static_assert(GW == 2 || IQL_GW == 1, "split batches pair the waves (GW = 2)");
       const char *xb[GNI], *zb[GNB];
 #pragma unroll
       for (int c = 0; c < GNI; ++c) xb[c] = reinterpret_cast<const char *>(Xsrc) + (size_t)(((i0 >> 4) + c) * nk) * 1024;
@@ -2548,11 +2420,6 @@ __device__ __forceinline__ void update_body(const TrainerDesc *__restrict__ Dp,
       }
     }
   }
-#if !IQL_G2_EARLY
-  if constexpr (!LAT) {
-    if (!ksplit && wave >= 2) load_state();
-  }
-#endif
   __syncthreads();
   STAMP(2, 3);
 
@@ -2578,7 +2445,7 @@ __device__ __forceinline__ void update_body(const TrainerDesc *__restrict__ Dp,
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       g[k] = P::round(g[k]);
-      adam_apply<AF>(p[k], m[k], v[k], g[k], coef, neg_step);
+      adam_apply<BF16>(p[k], m[k], v[k], g[k], coef, neg_step);
       if (has_target) tv[k] = polyak(D, tv[k], p[k]);
     }
     // the new weights replace this thread's gradients in the tile (step 4 reads them transposed)
@@ -2598,8 +2465,8 @@ __device__ __forceinline__ void update_body(const TrainerDesc *__restrict__ Dp,
       if (has_target) state_store(g_target, te, make_float4(tv[0], tv[1], tv[2], tv[3]));
       // 4 consecutive k of one row are contiguous in the fragment-major copies
       if (!copies_from_lds) {
-        copy_store4<BF16>(wc, fidx<P>(o, i, nkw), p);
-        if (has_target) copy_store4<BF16>(tc, fidx<P>(o, i, nkw), tv);
+        store4T<BF16>(wc + fidx<P>(o, i, nkw), p);
+        if (has_target) store4T<BF16>(tc + fidx<P>(o, i, nkw), tv);
       }
       if (L == 2) {  // layer 3: the [H][Opad] transposed copy k_backward reads (one unit's weights to all outputs)
         T *w3t = reinterpret_cast<T *>(it.w3t);
@@ -2617,7 +2484,7 @@ __device__ __forceinline__ void update_body(const TrainerDesc *__restrict__ Dp,
       if (ksplit) gb += bgrad2[tid];
     }
     const float g = P::round(gb);
-    adam_apply<AF>(pb, mb, vb, g, coef, neg_step);
+    adam_apply<BF16>(pb, mb, vb, g, coef, neg_step);
     stg(g_params + e, pb), stg(g_m + e, mb), stg(g_v + e, vb);
     if (g_grads) stg(g_grads + e, g);
     if (has_target) stg(g_target + it.toff_b + o0 + tid, polyak(D, tb, pb));
@@ -2662,7 +2529,7 @@ __device__ __forceinline__ void update_body(const TrainerDesc *__restrict__ Dp,
       float pv4[4];
 #pragma unroll
       for (int k = 0; k < 4; ++k) pv4[k] = tile[(o4 + k) * ULD + il];
-      copy_store4<BF16>(reinterpret_cast<T *>(it.w2ct), fidx<P>(i0 + il, o0 + o4, H / P::KM), pv4);
+      store4T<BF16>(reinterpret_cast<T *>(it.w2ct) + fidx<P>(i0 + il, o0 + o4, H / P::KM), pv4);
     }
   }
   STAMP(2, 4);
@@ -2740,17 +2607,14 @@ size_t bwd_smem_bytes(bool bf16, int H) {
 }
 // batch rows per forward work-group = 16 x this (more rows per work-group = fewer re-reads of
 // the weights; fewer work-groups): 2 for the headline batch 256 (224 work-groups at E = 2)
-// Measured (tools/group_scan.py, IQLHIP_FWD_MT / IQLHIP_FWD_PW): one seed alone is fastest with
-// 16-row work-groups (448 of them at batch 256: two per CU, whose phases interleave on each
-// SIMD), two seeds and more with 32 rows; from four seeds on with two layer-2 parts per
-// work-group (K = 8: 154.8k steps/s against 150.2k with 64 rows x one part, 139.7k with 32 x one).
+// Measured (tools/group_scan.py): one seed alone is fastest with 16-row work-groups (448 of them at
+// batch 256: two per CU, whose phases interleave on each SIMD), two seeds and more with 32 rows; from
+// four seeds on with two layer-2 parts per work-group (K = 8: 154.8k steps/s against 150.2k with
+// 64 rows x one part, 139.7k with 32 x one).
 int fwd_row_tiles(int B, int n_seeds) {
-  static const int forced = getenv("IQLHIP_FWD_MT") ? atoi(getenv("IQLHIP_FWD_MT")) : 0;  // A/B knob
-  if ((forced == 1 || forced == 2 || forced == 4) && B % (16 * forced) == 0) return forced;
   const int64_t rows = (int64_t)B * n_seeds;
-  // (round 3, on the balanced update table: 64-row work-groups -- IQLHIP_FWD_MT=4 -- gain 1.6 % for eight
-  // seeds as ONE group, 202.5k -> 205.7k steps/s, and lose for everything else: K = 4 152.9k -> 147.1k,
-  // K = 2 103.7k -> 98.6k, two sub-groups of eight on two streams 263.5k -> 255.4k: not the default)
+  // (64-row work-groups, round 3: eight seeds as ONE group 202.5k -> 205.7k steps/s, everything else
+  // slower: K = 4 152.9k -> 147.1k, K = 2 103.7k -> 98.6k, two groups of eight 263.5k -> 255.4k)
   if (rows >= 512 && B % 32 == 0) return 2;
   return 1;
 }
@@ -2758,10 +2622,7 @@ int layer2_parts(int H) { return H >= 256 ? 4 : H / 64; }
 // parts of hidden layer 2 per forward work-group: 2 in a group launch that keeps the chip full
 // anyway (layer 1 and its epilogue are then computed twice per slab instead of four times)
 int fwd_parts_per_wg(int B, int H, int n_seeds) {
-  static const int forced = getenv("IQLHIP_FWD_PW") ? atoi(getenv("IQLHIP_FWD_PW")) : 0;  // A/B knob
-  const int spl = layer2_parts(H);
-  if ((forced == 1 || forced == 2) && spl % forced == 0) return forced;
-  return ((int64_t)B * n_seeds >= 1024 && spl % 2 == 0) ? 2 : 1;
+  return ((int64_t)B * n_seeds >= 1024 && layer2_parts(H) % 2 == 0) ? 2 : 1;
 }
 
 #define DISPATCH_H(BF, HH, CALL)                 \
@@ -2778,16 +2639,12 @@ int fwd_parts_per_wg(int B, int H, int n_seeds) {
   } while (0)
 
 // Launches with many rows (seed groups, batch-1024 ensembles) take the throughput kernels
-// k_forward_tp / k_backward_tp (bf16, H = 256, batch a multiple of 64); IQLHIP_TP=0 / 1 forces the choice.
+// k_forward_tp / k_backward_tp (bf16, H = 256, batch a multiple of 64).
 bool use_tp(bool bf16, const TrainerDesc &D, int n_seeds, bool backward) {
-  static const int forced = getenv("IQLHIP_TP") ? atoi(getenv("IQLHIP_TP")) : -1;          // A/B knobs: both kernels,
-  static const int forced_b = getenv("IQLHIP_TP_BWD") ? atoi(getenv("IQLHIP_TP_BWD")) : -1;  // the backward alone
   if (!bf16 || D.H != 256 || D.B % 64 != 0) return false;
-  if (backward && forced_b >= 0) return forced_b != 0;
-  if (forced >= 0) return forced != 0;
   // The throughput kernels are one eight-wave work-group per CU, all resident at once: they win while
   // their work-groups fill a good part of the 256 CUs and lose beyond them (two rounds) and far below
-  // (nothing covers a lone work-group's latency).  Measured (round 4, tools/tp_matrix.sh and d2 / g4;
+  // (nothing covers a lone work-group's latency).  Measured (round 4, d2 / g4;
   // steps/s old kernels -> throughput forward + old backward -> both):
   //   forward work-groups = evaluations x batch / 64 x seeds, backward = trained nets x batch / 32 x seeds
   //   E = 3 / batch 256 (36 / 40) 56.4k -> 52.7k -> 47.9k     E = 4 / 256 (44 / 48) 52.7k -> 51.6k -> 46.3k
@@ -2832,19 +2689,17 @@ hipError_t launch_forward(bool bf16, const TrainerDesc &D, const TrainerDesc *dD
   const int grid = 8 * ((D.nfwd + 1 + 7) / 8) * nsl * (layer2_parts(D.H) / pw);
   const size_t sm = fwd_smem_bytes(bf16, D.H, D.k1max, mt, pw);
 #define LAUNCH_F(BF, HH, MTV, PWV)                                                                            \
-  hipLaunchKernelGGL((k_forward<BF, HH, MTV, PWV, false>), dim3(grid, n_seeds), dim3(256), sm, st, dD, a, c, nsl, D.nfwd)
+  hipLaunchKernelGGL((k_forward<BF, HH, MTV, PWV>), dim3(grid, n_seeds), dim3(256), sm, st, dD, a, c, nsl, D.nfwd)
 #define CALL(BF, HH)                                                   \
   do {                                                                 \
     if constexpr (HH >= 128) {                                         \
       if (pw == 2) {                                                   \
-        if (mt == 4) LAUNCH_F(BF, HH, 4, 2);                           \
-        else if (mt == 2) LAUNCH_F(BF, HH, 2, 2);                      \
+        if (mt == 2) LAUNCH_F(BF, HH, 2, 2);                           \
         else LAUNCH_F(BF, HH, 1, 2);                                   \
         break;                                                         \
       }                                                                \
     }                                                                  \
-    if (mt == 4) LAUNCH_F(BF, HH, 4, 1);                               \
-    else if (mt == 2) LAUNCH_F(BF, HH, 2, 1);                          \
+    if (mt == 2) LAUNCH_F(BF, HH, 2, 1);                               \
     else LAUNCH_F(BF, HH, 1, 1);                                       \
   } while (0)
   DISPATCH_H(bf16, D.H, CALL);
@@ -2854,14 +2709,11 @@ hipError_t launch_forward(bool bf16, const TrainerDesc &D, const TrainerDesc *dD
 }
 // parts of the dZ1 columns per backward work-group: 1 for one seed at batch 256 (every part repeats
 // the loss / dZ2 phase: parallelism bought with redundant work), 2 from 512 rows per launch on.
-// Measured (tools/group_scan.py, IQLHIP_BWD_PW; steps/s with 1 / 2 parts per work-group): one seed
-// 65.4k / 64.1k, two seeds 97.4k / 102.2k, four 136.2k / 144.6k, eight 177.3k / 189.5k (k_backward 10.7 ->
-// 8.0 us); all four parts in one work-group (512 work-groups of 128 registers, spilling): 148k.
+// Measured (tools/group_scan.py; steps/s with 1 / 2 parts per work-group): one seed 65.4k / 64.1k,
+// two seeds 97.4k / 102.2k, four 136.2k / 144.6k, eight 177.3k / 189.5k (k_backward 10.7 -> 8.0 us);
+// all four parts in one work-group (512 work-groups of 128 registers, spilling): 148k.
 int bwd_parts_per_wg(int B, int H, int n_seeds) {
-  static const int forced = getenv("IQLHIP_BWD_PW") ? atoi(getenv("IQLHIP_BWD_PW")) : 0;  // A/B knob
-  const int spl = layer2_parts(H);
-  if ((forced == 1 || forced == 2 || forced == 4) && spl % forced == 0) return forced;
-  return ((int64_t)B * n_seeds >= 512 && spl % 2 == 0) ? 2 : 1;
+  return ((int64_t)B * n_seeds >= 512 && layer2_parts(H) % 2 == 0) ? 2 : 1;
 }
 hipError_t launch_backward(bool bf16, const TrainerDesc &D, const TrainerDesc *dD, const DevArgs *a,
                            DevCtr *c, int n_seeds, hipStream_t st) {
@@ -2876,17 +2728,14 @@ hipError_t launch_backward(bool bf16, const TrainerDesc &D, const TrainerDesc *d
   const int pw = bwd_parts_per_wg(D.B, D.H, n_seeds);
   const int grid = 8 * ((layer2_parts(D.H) / pw * D.ntrain + 7) / 8) * (D.B / SLAB);
   const size_t sm = bwd_smem_bytes(bf16, D.H);
-  static const int forced_pre = getenv("IQLHIP_BWD_PRE") ? atoi(getenv("IQLHIP_BWD_PRE")) : -1;  // A/B knob
-  // measured: no difference for one seed (63.2k either way), K = 8 170.2k against 165.1k
-  const bool pre = forced_pre >= 0 ? forced_pre != 0 : (int64_t)D.B * n_seeds < 1024;
+  // GEMM operands up front below 1024 rows per launch, else behind the dZ2 phase (backward_body).
+  // Measured: no difference for one seed (63.2k either way), K = 8 170.2k against 165.1k
+  const bool pre = (int64_t)D.B * n_seeds < 1024;
 #define LAUNCH_B(BF, HH, PRE_, PW_)                                                                          \
   hipLaunchKernelGGL((k_backward<BF, HH, PRE_, PW_>), dim3(grid, n_seeds), dim3(256), sm, st, dD, a, c, D.B / SLAB, \
                      D.ntrain)
 #define CALL(BF, HH)                                                  \
   do {                                                                \
-    if constexpr (HH >= 256) {                                        \
-      if (pw == 4) { LAUNCH_B(BF, HH, false, 4); break; }             \
-    }                                                                 \
     if constexpr (HH >= 128) {                                        \
       if (pw == 2) { LAUNCH_B(BF, HH, false, 2); break; }             \
     }                                                                 \
@@ -2915,14 +2764,13 @@ hipError_t launch_update(bool bf16, const TrainerDesc *dD, const DevArgs *a, Dev
   // The 512-thread latency variant while a lone seed's work-groups have a CU each; the four-per-CU
   // throughput variant for groups and for a seed with more work items than CUs (E = 4 critics at batch
   // 1024: 337 items, 30.7k -> 32.0k steps/s; two critics at batch 256: 65.7k -> 63.5k).  The same bits.
-  static const int forced_lat = getenv("IQLHIP_UPD_LAT") ? atoi(getenv("IQLHIP_UPD_LAT")) : -1;  // A/B knob
   static const int cus = [] {
     int dev = 0, n = 256;
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
       n = 256;
     return n;
   }();
-  const bool lat = forced_lat >= 0 ? forced_lat != 0 : (n_seeds == 1 && n_items + 1 <= cus + 1);
+  const bool lat = n_seeds == 1 && n_items + 1 <= cus + 1;
   if (bf16 && !lat)
     hipLaunchKernelGGL((k_update<true, false>), grid, dim3(256), 0, st, dD, a, c, items, n_items);
   else if (bf16)

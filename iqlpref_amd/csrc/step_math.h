@@ -86,13 +86,10 @@ __device__ __forceinline__ float polyak(const Desc &D, float t, float p) {
   return D.polyak_convex ? (D.one_m_tau * t) + (D.tau * p) : __builtin_fmaf(D.tau, p - t, t);
 }
 
-// A/B on one box (round 3, r4m): one seed 64.1k -> 65.6k steps/s, 8 seeds per launch 175.0k -> 177.4k;
-// every parity test unchanged at its tolerance.  -DIQL_ADAM_FAST=0 builds the IEEE form everywhere.
-// FAST is the bf16 step's form only: precision = fp32 (the parity mode) keeps torch's arithmetic --
-// _single_tensor_adam's correctly rounded sqrt and two divisions, operation for operation.
-#ifndef IQL_ADAM_FAST
-#define IQL_ADAM_FAST 1
-#endif
+// FAST (round 3, r4m): one seed 64.1k -> 65.6k steps/s, 8 seeds per launch 175.0k -> 177.4k; every parity
+// test unchanged at its tolerance.  It is the bf16 step's form only (adam_apply<BF16>): precision = fp32
+// (the parity mode) keeps torch's arithmetic -- _single_tensor_adam's correctly rounded sqrt and two
+// divisions, operation for operation.
 template <bool FAST>
 __device__ __forceinline__ void adam_apply(float &p, float &m, float &v, float g, const AdamCoef &c,
                                            float neg_step) {

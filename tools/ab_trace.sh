@@ -1,5 +1,5 @@
 # The same traced command several times on one box (is the tracer's pacing stable?):
-#   AB_N=6 bash tools/ab_trace.sh        optionally AB_LIB=<variant .so under iqlpref_amd/> alternates with the product build
+#   AB_N=6 bash tools/ab_trace.sh        optionally AB_LIB=<another build's .so under iqlpref_amd/, e.g. libiqlhip_prev.so> alternates with the product build
 export TMPDIR=/tmp
 ARGS="--full --unroll 50 --no-cpu-baseline --no-relabel --no-pen --agents-per-gpu 0 --ensemble-q 0 --min-timed-s 0.05"
 run() {
@@ -15,5 +15,5 @@ PY
 for i in $(seq 1 ${AB_N:-6}); do
   unset IQLHIP_LIB
   run product
-  if [ -n "$AB_LIB" ]; then export IQLHIP_LIB=$GRAFT_REPO_ROOT/iqlpref_amd/$AB_LIB; run $AB_LIB; fi
+  if [ -n "$AB_LIB" ]; then export IQLHIP_LIB=$PWD/iqlpref_amd/$AB_LIB; run $AB_LIB; fi
 done
