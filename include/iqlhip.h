@@ -20,6 +20,7 @@
 #ifndef IQLHIP_H
 #define IQLHIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -57,9 +58,14 @@ const char *iqlhip_build_tag(void);
 /*   MLP fwd   1..8 layers, every width in [1, 1024] (beyond 256: a plain      */
 /*             one-wave-per-16-rows variant);                                  */
 /*   CVaR      1 <= n_tail <= S <= 2400;                                       */
-/*   PT        embd_dim 64, ONE GPT-2 block, num_heads a power of two <= 16,   */
-/*             inter_dim a multiple of 256 up to 1024, state_dim + action_dim  */
-/*             <= 192, query_length such that the window fits the 160 KiB LDS. */
+/*   PT        tuned (iqlhip_pt_relabel): embd_dim 64, ONE GPT-2 block,        */
+/*             num_heads a power of two <= 16, inter_dim a multiple of 256 up  */
+/*             to 1024, state_dim + action_dim <= 192, query_length such that  */
+/*             the window fits the 160 KiB LDS.  General layer-wise path       */
+/*             (iqlhip_pt_relabel_general, csrc/pt_general.hip): 1..8 blocks,  */
+/*             embd_dim a multiple of 64 up to 256, num_heads a power of two   */
+/*             with embd_dim / num_heads >= 4, inter_dim a multiple of 64 up   */
+/*             to 1024, state_dim + action_dim <= 256, query_length <= 4096.  */
 /* ------------------------------------------------------------------------ */
 
 /* ------------------------------------------------------------------------ */
@@ -333,8 +339,11 @@ int iqlhip_cvar_tail_mean(const float *preds, int32_t S, int64_t N, int32_t n_ta
 /* ------------------------------------------------------------------------ */
 /* Preference-transformer relabel  (ref:1223-1309 qlearning_dataset_pt)        */
 /* Architecture: reward_models/pref_transformer.py:170-277 (PT), ops.py:6-117.  */
-/* One GPT-2 block, embd_dim 64.  Every pointer is device fp32; "T" = stored   */
-/* transposed ([in][out]) relative to the torch / state-dict [out][in] layout. */
+/* iqlhip_pt_relabel: one GPT-2 block, embd_dim 64 (the tuned streaming      */
+/* kernel, csrc/pt.hip); iqlhip_pt_relabel_general: any depth and width of the */
+/* envelope above (layer-wise, csrc/pt_general.hip).  Every pointer is device  */
+/* fp32; "T" = stored transposed ([in][out]) relative to the torch /           */
+/* state-dict [out][in] layout.                                                */
 /* ------------------------------------------------------------------------ */
 typedef struct {
   int32_t state_dim, action_dim;
@@ -376,6 +385,56 @@ typedef struct {
 int iqlhip_pt_relabel(const iqlhip_pt_weights *w, const float *obs, const float *act, int64_t n_rows,
                       const int64_t *win_start, const int32_t *win_len, const int32_t *win_t0,
                       int64_t n_win, int32_t query_length, float *out, void *stream);
+
+/* The general path: the weights of one GPT-2 block gpt.layers.{l} (E = embd_dim, I = inter_dim),
+ * all device fp32 in the torch [out][in] layout.                                              */
+typedef struct {
+  const float *ln0_w, *ln0_b;           /* layer_norm_0 [E], [E]                        */
+  const float *qkv_w, *qkv_b;           /* attention.in_linear [3E][E], [3E]            */
+  const float *attn_out_w, *attn_out_b; /* attention.out_linear [E][E], [E]             */
+  const float *ln1_w, *ln1_b;           /* layer_norm_1 [E], [E]                        */
+  const float *mlp_in_w, *mlp_in_b;     /* mlp.in_linear [I][E], [I]                    */
+  const float *mlp_out_w, *mlp_out_b;   /* mlp.out_linear [E][I], [E]                   */
+} iqlhip_pt_block;
+
+/* A whole PT for the general path.  The embedding, stacked-LN, final-LN and value-head pointers
+ * are those of iqlhip_pt_weights, with E = embd_dim in place of 64; `blocks` is a HOST array of
+ * num_layers block structs, read during the call only.                                        */
+typedef struct {
+  int32_t state_dim, action_dim;
+  int32_t embd_dim;   /* multiple of 64, <= 256                                      */
+  int32_t num_heads;  /* power of two, embd_dim / num_heads >= 4                     */
+  int32_t inter_dim;  /* multiple of 64, <= 1024                                     */
+  int32_t num_layers; /* 1..8                                                        */
+  int32_t n_temb;     /* rows of timestep_embed (max_episode_steps + 1)              */
+  float eps;          /* LayerNorm epsilon                                           */
+  const float *state_wT, *state_b;   /* state_linear  [S][E] T, [E]                  */
+  const float *action_wT, *action_b; /* action_linear [A][E] T, [E]                  */
+  const float *temb;                 /* timestep_embed.weight [n_temb][E]            */
+  const float *sln_w, *sln_b;        /* stacked_layer_norm                           */
+  const float *lnf_w, *lnf_b;        /* gpt.layer_norm                               */
+  const float *pref_w_last;          /* LAST row of pref_linear.weight [E]           */
+  float pref_b_last;                 /* last element of pref_linear.bias             */
+  const iqlhip_pt_block *blocks;     /* host [num_layers]                            */
+} iqlhip_pt_model;
+
+/* Device workspace (bytes) that lets iqlhip_pt_relabel_general take min(n_win, chunk cap)
+ * windows of query_length in one pass; the chunk cap keeps the figure under 1 GiB.  Pure host
+ * code; the shape checks are those of iqlhip_pt_relabel_general.                              */
+int iqlhip_pt_general_workspace_bytes(const iqlhip_pt_model *m, int32_t query_length, int64_t n_win,
+                                      size_t *bytes);
+
+/* iqlhip_pt_relabel for every shape of the general envelope: the same windows, timesteps,
+ * clamping and output, computed layer by layer over chunks of windows whose token matrices live in
+ * `workspace` (device, workspace_bytes long, 16-byte aligned).  A workspace smaller than
+ * iqlhip_pt_general_workspace_bytes(m, query_length, n_win) is used in several chunks; one that
+ * holds no window is IQLHIP_ERR_INVALID.  Shapes outside the envelope return
+ * IQLHIP_ERR_UNSUPPORTED before any HIP call.  Same arithmetic (bf16 q.k logits, fp32
+ * elsewhere) as the tuned kernel.                                                              */
+int iqlhip_pt_relabel_general(const iqlhip_pt_model *m, const float *obs, const float *act, int64_t n_rows,
+                              const int64_t *win_start, const int32_t *win_len, const int32_t *win_t0,
+                              int64_t n_win, int32_t query_length, void *workspace, size_t workspace_bytes,
+                              float *out, void *stream);
 
 /* Algorithmic traffic and work of one step for this configuration
  * (SURVEY.md section 8d): bytes = 4B(2S+A+2) + 32 P_train + 8 P_q.          */

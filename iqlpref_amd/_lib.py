@@ -71,6 +71,25 @@ class PtWeights(C.Structure):
                 [("pref_b_last", C.c_float)])
 
 
+PT_MAX_LAYERS = 8  # the general PT path (iqlhip_pt_relabel_general): 1..8 GPT-2 blocks
+
+
+class PtBlock(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in (
+        "ln0_w", "ln0_b", "qkv_w", "qkv_b", "attn_out_w", "attn_out_b",
+        "ln1_w", "ln1_b", "mlp_in_w", "mlp_in_b", "mlp_out_w", "mlp_out_b")]
+
+
+class PtModel(C.Structure):
+    _fields_ = ([("state_dim", C.c_int32), ("action_dim", C.c_int32), ("embd_dim", C.c_int32),
+                 ("num_heads", C.c_int32), ("inter_dim", C.c_int32), ("num_layers", C.c_int32),
+                 ("n_temb", C.c_int32), ("eps", C.c_float)] +
+                [(n, C.c_void_p) for n in (
+                    "state_wT", "state_b", "action_wT", "action_b", "temb", "sln_w", "sln_b",
+                    "lnf_w", "lnf_b", "pref_w_last")] +
+                [("pref_b_last", C.c_float), ("blocks", C.POINTER(PtBlock))])
+
+
 # every symbol include/iqlhip.h declares: name -> (restype, argtypes)
 P = C.c_void_p
 SYMBOLS = {
@@ -115,6 +134,10 @@ SYMBOLS = {
     "iqlhip_cvar_tail_mean": (C.c_int, [P, C.c_int32, C.c_int64, C.c_int32, P, P]),
     "iqlhip_pt_relabel": (C.c_int, [C.POINTER(PtWeights), P, P, C.c_int64, P, P, P, C.c_int64, C.c_int32,
                                     P, P]),
+    "iqlhip_pt_general_workspace_bytes": (C.c_int, [C.POINTER(PtModel), C.c_int32, C.c_int64,
+                                                    C.POINTER(C.c_size_t)]),
+    "iqlhip_pt_relabel_general": (C.c_int, [C.POINTER(PtModel), P, P, C.c_int64, P, P, P, C.c_int64, C.c_int32,
+                                            P, C.c_size_t, P, P]),
     "iqlhip_step_cost": (C.c_int, [C.POINTER(TrainerConfig), C.POINTER(C.c_double),
                                    C.POINTER(C.c_double)]),
     "iqlhip_trainer_set_timing": (C.c_int, [P, C.c_int32]),

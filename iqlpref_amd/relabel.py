@@ -511,7 +511,9 @@ def load_bnn_weight_file(path):
 # --------------------------------------------------------------------------- #
 class RewardPT(nn.Module):
     """Parameter container with the state-dict keys ref:1363-1371 reads; forward =
-    ``iqlhip_pt_relabel``.  Dropout arguments are accepted and unused (eval only)."""
+    ``iqlhip_pt_relabel`` (embd_dim 64, one block) or ``iqlhip_pt_relabel_general`` (every other
+    shape of its envelope), see ``window_values``.  Dropout arguments are accepted and unused
+    (eval only)."""
 
     def __init__(self, state_dim, action_dim, max_episode_steps, embd_dim=64, pref_attn_embd_dim=64,
                  num_heads=4, attn_dropout=0.1, resid_dropout=0.1, intermediate_dim=256, num_layers=1,
@@ -576,13 +578,75 @@ class RewardPT(nn.Module):
         w.pref_b_last = float(self.pref_linear.bias[-1].item())
         return w, keep, dev
 
+    def tuned_shape(self) -> bool:
+        """True when the model fits the tuned one-block kernel (``iqlhip_pt_relabel``): embd_dim 64,
+        one block, num_heads a power of two <= 16, inter_dim 256 / 512 / 768 / 1024, S + A <= 192."""
+        nh, I = self.num_heads, self.gpt.layers[0].mlp.in_linear.out_features
+        return (self.state_linear.out_features == 64 and len(self.gpt.layers) == 1
+                and 1 <= nh <= 16 and nh & (nh - 1) == 0 and I % 256 == 0 and 256 <= I <= 1024
+                and self.state_linear.in_features + self.action_linear.in_features <= 192)
+
+    def _general_model(self):
+        f = lambda t: t.detach().to(torch.float32).contiguous()
+        keep = dict(
+            state_wT=f(self.state_linear.weight.t()), state_b=f(self.state_linear.bias),
+            action_wT=f(self.action_linear.weight.t()), action_b=f(self.action_linear.bias),
+            temb=f(self.timestep_embed.weight),
+            sln_w=f(self.stacked_layer_norm.weight), sln_b=f(self.stacked_layer_norm.bias),
+            lnf_w=f(self.gpt.layer_norm.weight), lnf_b=f(self.gpt.layer_norm.bias),
+            pref_w_last=f(self.pref_linear.weight[-1]))
+        blocks = (_lib.PtBlock * len(self.gpt.layers))()
+        held = [keep]
+        for b, blk in zip(blocks, self.gpt.layers):
+            t = dict(ln0_w=f(blk.layer_norm_0.weight), ln0_b=f(blk.layer_norm_0.bias),
+                     qkv_w=f(blk.attention.in_linear.weight), qkv_b=f(blk.attention.in_linear.bias),
+                     attn_out_w=f(blk.attention.out_linear.weight), attn_out_b=f(blk.attention.out_linear.bias),
+                     ln1_w=f(blk.layer_norm_1.weight), ln1_b=f(blk.layer_norm_1.bias),
+                     mlp_in_w=f(blk.mlp.in_linear.weight), mlp_in_b=f(blk.mlp.in_linear.bias),
+                     mlp_out_w=f(blk.mlp.out_linear.weight), mlp_out_b=f(blk.mlp.out_linear.bias))
+            for k, v in t.items():
+                setattr(b, k, v.data_ptr())
+            held.append(t)
+        m = _lib.PtModel()
+        m.state_dim = self.state_linear.in_features
+        m.action_dim = self.action_linear.in_features
+        m.embd_dim = self.state_linear.out_features
+        m.num_heads = self.num_heads
+        m.inter_dim = self.gpt.layers[0].mlp.in_linear.out_features
+        m.num_layers = len(self.gpt.layers)
+        m.n_temb = self.timestep_embed.num_embeddings
+        m.eps = self.eps
+        for k, t in keep.items():
+            setattr(m, k, t.data_ptr())
+        m.pref_b_last = float(self.pref_linear.bias[-1].item())
+        m.blocks = C.cast(blocks, C.POINTER(_lib.PtBlock))
+        held.append(blocks)
+        return m, held
+
     def window_values(self, obs: torch.Tensor, act: torch.Tensor, win_start: torch.Tensor,
                       win_len: torch.Tensor, query_length: int,
-                      win_t0: Optional[torch.Tensor] = None) -> torch.Tensor:
+                      win_t0: Optional[torch.Tensor] = None, kernel: str = "auto",
+                      workspace_windows: Optional[int] = None) -> torch.Tensor:
         """value[:, 0, -1, 0] of each (start, len) window over the device arrays obs/act; the
-        timestep of a window's k-th transition is ``win_t0 + k`` (0 + k when None)."""
+        timestep of a window's k-th transition is ``win_t0 + k`` (0 + k when None).
+
+        ``kernel``: "tuned" = the one-block kernel ``iqlhip_pt_relabel`` (embd_dim 64, one block),
+        "general" = the layer-wise path ``iqlhip_pt_relabel_general`` (any depth and width of its
+        envelope), "auto" = tuned when the shape fits it (``tuned_shape``), general otherwise.
+        ``workspace_windows``: size the general path's workspace for that many windows (it then
+        runs in chunks of that size); default: all of them, up to the library's chunk cap."""
+        if kernel not in ("auto", "tuned", "general"):
+            raise ValueError(f"kernel must be 'auto', 'tuned' or 'general', got {kernel!r}")
+        general = kernel == "general" or (kernel == "auto" and not self.tuned_shape())
+        if general and 2 * query_length > self.max_pos:
+            # the reference slices its causal mask to [:2 QL, :2 QL] of max_pos x max_pos (pref_transformer.py:60)
+            raise ValueError(f"2 * query_length = {2 * query_length} exceeds max_pos = {self.max_pos}")
         lib = _lib.load()
-        w, keep, dev = self._weights()
+        if general:
+            w, keep = self._general_model()
+            dev = _device_of(self)
+        else:
+            w, keep, dev = self._weights()
         obs = obs.to(torch.float32).contiguous()
         act = act.to(torch.float32).contiguous()
         win_start = win_start.to(torch.int64).contiguous()
@@ -593,9 +657,19 @@ class RewardPT(nn.Module):
                 raise ValueError("a window's last timestep exceeds the timestep-embedding table")
         out = torch.empty(win_start.shape[0], dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            check(lib.iqlhip_pt_relabel(C.byref(w), ptr(obs), ptr(act), obs.shape[0], ptr(win_start),
-                                        ptr(win_len), ptr(win_t0), win_start.shape[0], query_length,
-                                        ptr(out), stream_ptr()))
+            if general:
+                nbytes = C.c_size_t()
+                check(lib.iqlhip_pt_general_workspace_bytes(C.byref(w), query_length,
+                                                            workspace_windows or win_start.shape[0],
+                                                            C.byref(nbytes)))
+                ws = torch.empty((nbytes.value + 3) // 4, dtype=torch.float32, device=dev)
+                check(lib.iqlhip_pt_relabel_general(C.byref(w), ptr(obs), ptr(act), obs.shape[0], ptr(win_start),
+                                                    ptr(win_len), ptr(win_t0), win_start.shape[0], query_length,
+                                                    ptr(ws), nbytes.value, ptr(out), stream_ptr()))
+            else:
+                check(lib.iqlhip_pt_relabel(C.byref(w), ptr(obs), ptr(act), obs.shape[0], ptr(win_start),
+                                            ptr(win_len), ptr(win_t0), win_start.shape[0], query_length,
+                                            ptr(out), stream_ptr()))
         del keep
         return out
 
