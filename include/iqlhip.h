@@ -436,6 +436,19 @@ int iqlhip_pt_relabel_general(const iqlhip_pt_model *m, const float *obs, const 
                               int64_t n_win, int32_t query_length, void *workspace, size_t workspace_bytes,
                               float *out, void *stream);
 
+/* ------------------------------------------------------------------------ */
+/* numpy's legacy RandomState.randint (algorithms/custom_offline/iql.py:277-284 */
+/* samples replay indices with it), bit for bit, on the device (np_sampler.hip) */
+/* ------------------------------------------------------------------------ */
+/* numpy RandomState.randint(0, hi[k], size=(n_batches, batch)) for K legacy MT19937 states.
+ * state: device uint32 [K][625] = key[624], pos; read and advanced in place.
+ * out[k]: device int64 [n_batches][batch].  1 <= hi[k] <= 2^32, 0 <= pos <= 624.
+ * hi and out are host arrays of K entries.  Synchronises `stream` once, before the launch, to
+ * read and check the K pos words; the draw itself is asynchronous.  1 <= K <= IQLHIP_MAX_GROUP,
+ * batch >= 1, n_batches >= 0 (0 draws nothing).                                               */
+int iqlhip_np_randint(uint32_t *state, const int64_t *hi, int32_t K, int32_t batch,
+                      int64_t n_batches, int64_t *const *out, void *stream);
+
 /* Algorithmic traffic and work of one step for this configuration
  * (SURVEY.md section 8d): bytes = 4B(2S+A+2) + 32 P_train + 8 P_q.          */
 int iqlhip_step_cost(const iqlhip_trainer_config *cfg, double *bytes, double *flops);

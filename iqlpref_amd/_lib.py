@@ -138,6 +138,7 @@ SYMBOLS = {
                                                     C.POINTER(C.c_size_t)]),
     "iqlhip_pt_relabel_general": (C.c_int, [C.POINTER(PtModel), P, P, C.c_int64, P, P, P, C.c_int64, C.c_int32,
                                             P, C.c_size_t, P, P]),
+    "iqlhip_np_randint": (C.c_int, [P, P, C.c_int32, C.c_int32, C.c_int64, P, P]),
     "iqlhip_step_cost": (C.c_int, [C.POINTER(TrainerConfig), C.POINTER(C.c_double),
                                    C.POINTER(C.c_double)]),
     "iqlhip_trainer_set_timing": (C.c_int, [P, C.c_int32]),

@@ -74,6 +74,8 @@ int pt_general_tp(int ql);
 hipError_t launch_pt_general(const iqlhip_pt_model &m, const float *obs, const float *act, int64_t n_rows,
                              const int64_t *win_start, const int32_t *win_len, const int32_t *win_t0,
                              int64_t n_win, int ql, float *ws, int64_t chunk, float *out, hipStream_t st);
+hipError_t launch_np_randint(uint32_t *state, const int64_t *hi, int K, int64_t total, int64_t *const *out,
+                             hipStream_t st);
 }  // namespace iqlhip
 
 using namespace iqlhip;
@@ -1445,6 +1447,31 @@ extern "C" int iqlhip_cvar_tail_mean(const float *preds, int32_t S, int64_t N, i
   if (n_tail < 1 || n_tail > S) return fail(IQLHIP_ERR_INVALID, "n_tail must be in [1, S]");
   if (S > 2400) return fail(IQLHIP_ERR_UNSUPPORTED, "S = %d > 2400", S);
   HIP_TRY(launch_cvar(preds, S, N, n_tail, out, (hipStream_t)stream));
+  return 0;
+}
+
+// ------------------------------------------------------- numpy index stream --
+extern "C" int iqlhip_np_randint(uint32_t *state, const int64_t *hi, int32_t K, int32_t batch,
+                                 int64_t n_batches, int64_t *const *out, void *stream) {
+  if (!state || !hi || !out) return fail(IQLHIP_ERR_INVALID, "null argument");
+  if (K < 1 || K > IQLHIP_MAX_GROUP) return fail(IQLHIP_ERR_INVALID, "K = %d: 1..%d streams", K, IQLHIP_MAX_GROUP);
+  if (batch < 1) return fail(IQLHIP_ERR_INVALID, "batch = %d must be >= 1", batch);
+  if (n_batches < 0) return fail(IQLHIP_ERR_INVALID, "n_batches = %lld must be >= 0", (long long)n_batches);
+  for (int k = 0; k < K; ++k) {
+    if (hi[k] < 1 || hi[k] > (int64_t(1) << 32))
+      return fail(IQLHIP_ERR_INVALID, "hi[%d] = %lld outside 1..2^32", k, (long long)hi[k]);
+    if (!out[k]) return fail(IQLHIP_ERR_INVALID, "null out[%d]", k);
+  }
+  // pos of every state: one strided copy of the K words, then the stream is synchronised
+  hipStream_t st = (hipStream_t)stream;
+  uint32_t pos[IQLHIP_MAX_GROUP];
+  HIP_TRY(hipMemcpy2DAsync(pos, sizeof(uint32_t), state + 624, 625 * sizeof(uint32_t), sizeof(uint32_t), K,
+                           hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  for (int k = 0; k < K; ++k)
+    if (pos[k] > 624) return fail(IQLHIP_ERR_INVALID, "state %d: pos = %u outside 0..624", k, pos[k]);
+  if (n_batches == 0) return 0;
+  HIP_TRY(launch_np_randint(state, hi, K, n_batches * (int64_t)batch, out, st));
   return 0;
 }
 

@@ -11,26 +11,35 @@ Differences from ``algorithms/offline/iql.py`` and how they map onto the same ke
   (start, len, t0) = (ep + max(0, i - QL + 1), min(i + 1, QL), max(0, i + 1 - QL));
 * ``query_length == 1``: a Markovian reward MLP (reward_models/q_mlp.py) over (s, a);
 * ``ReplayBuffer.sample`` draws indices with numpy's global RNG (cref:277-284) -- reproduced
-  exactly: the indices are drawn on the host with the same call and uploaded;
+  exactly, either on the host with the same call (then uploaded) or on the device by
+  ``NumpyIndexStream`` (csrc/np_sampler.hip: numpy's legacy ``randint`` bit for bit, the advanced
+  state written back into the generator);
 * no autocast (``precision="fp32"``), Polyak update written as (1 - tau) t + tau s (cref:85-87,
   ``polyak_form=1``), checkpoint key ``actor_lr_scheduler`` and no ``total_it`` (cref:546-556);
 * ``modify_reward``: only the locomotion range scaling and antmaze's -1 (cref:145-155).
+
+``train()`` is cref:597-749 with the absent services (minari, the Orbax reward-model readers,
+wandb) injectable, and ``seeds_per_gpu`` seeds side by side on one GPU.
 
 Not built (stated): the Orbax / flax-nnx checkpoint readers ``load_PT`` / ``load_QMLP``
 (reward_models/pref_transformer.py:280-327, q_mlp.py:100-168) need orbax + jax, which are absent;
 ``RewardPT.load_flax_params`` / ``QMLP.load_flax_params`` take the parameter pytree as numpy
 arrays instead.  PT numerics stay "parity unpinned" (no runnable reference, no fixtures).
 """
+import ctypes as C
 import uuid
 import os
-from dataclasses import dataclass
-from typing import Any, Dict, Iterable, List, Optional, Sequence
+from dataclasses import asdict, dataclass
+from typing import Any, Callable, Dict, Iterable, List, Optional, Sequence
 
 import numpy as np
 import torch
 import torch.nn as nn
 
 from . import _lib
+from . import distributed as D
+from ._lib import check, ptr
+from .iql import DeterministicPolicy, GaussianPolicy, TwinQ, ValueFunction, compute_mean_std, normalize_states, set_seed
 from .iql import ImplicitQLearning as _OfflineIQL
 from .iql import ReplayBuffer as _OfflineReplayBuffer
 from .iql import mlp_forward_f32
@@ -220,6 +229,102 @@ def evaluate(env, actor: nn.Module, num_episodes: int, seed: int, device: str) -
 # --------------------------------------------------------------------------- #
 # buffer and trainer
 # --------------------------------------------------------------------------- #
+# --------------------------------------------------------------------------- #
+# numpy's legacy randint on the device (csrc/np_sampler.hip)
+# --------------------------------------------------------------------------- #
+NP_STATE_WORDS = 625  # key[624], pos
+
+
+def pack_np_state(state) -> np.ndarray:
+    """``RandomState.get_state()`` (legacy tuple) -> uint32 [625] = key[624], pos."""
+    if state[0] != "MT19937":
+        raise ValueError(f"not a legacy MT19937 state: {state[0]!r}")
+    key, pos = np.asarray(state[1]), int(state[2])
+    if key.shape != (624,) or not 0 <= pos <= 624:
+        raise ValueError(f"bad MT19937 state: key shape {key.shape}, pos {pos}")
+    out = np.empty(NP_STATE_WORDS, dtype=np.uint32)
+    out[:624], out[624] = key, pos
+    return out
+
+
+def unpack_np_state(packed: np.ndarray, like) -> tuple:
+    """uint32 [625] -> the legacy state tuple, with ``has_gauss`` / ``cached_gaussian`` of ``like``
+    (the draw does not touch them)."""
+    packed = np.asarray(packed).view(np.uint32)
+    return ("MT19937", packed[:624].copy(), int(packed[624]), int(like[3]), float(like[4]))
+
+
+class NumpyIndexStream:
+    """``np.random.randint(0, hi, size=B)`` n times, for K generators at once, on the device.
+
+    ``draw`` uploads the state of every generator (an ``np.random.RandomState``, or None for numpy's
+    global one) into a device [K][625] buffer, draws [n][B] int64 indices per generator with ONE launch
+    of ``iqlhip_np_randint`` and writes the advanced state back with ``set_state``: when ``draw``
+    returns, every generator is where the host sampler would have left it, bit for bit.
+
+    The draw runs on a stream of its own into one of two index areas used in turn; the consumer (the
+    stream current at the call) waits on an event for the indices, and the draw of call n waits only
+    for the consumer's work queued before call n - 1 (the last user of that area).  The host blocks
+    for the short draw kernel, not for the training chunk queued just before it."""
+
+    def __init__(self, device):
+        self._lib = _lib.load()
+        self._dev = _lib.require_gpu(device)
+        G = _lib.MAX_GROUP
+        self._state = torch.empty((G, NP_STATE_WORDS), dtype=torch.int32, device=self._dev)
+        self._host_in = torch.empty((G, NP_STATE_WORDS), dtype=torch.int32).pin_memory()
+        self._host_out = torch.empty((G, NP_STATE_WORDS), dtype=torch.int32).pin_memory()
+        self._stream = torch.cuda.Stream(device=self._dev)
+        self._slots: List[Optional[torch.Tensor]] = [None, None]
+        self._free: List[Optional[torch.cuda.Event]] = [None, None]  # consumer done with the area
+        self._done = torch.cuda.Event()
+        self._turn = 0
+
+    def draw(self, hi, n_batches: int, batch_size: int, generators: Optional[Sequence] = None) -> List[torch.Tensor]:
+        """Returns K int64 device tensors [n_batches, batch_size] (views of the current index area,
+        valid until the call after next).  ``hi``: one bound for all generators or one per generator."""
+        gens = [None] if generators is None else list(generators)
+        K = len(gens)
+        his = [int(hi)] * K if np.ndim(hi) == 0 else [int(h) for h in hi]
+        if not 1 <= K <= _lib.MAX_GROUP or len(his) != K:
+            raise ValueError(f"1..{_lib.MAX_GROUP} generators, one hi per generator")
+        n, B = int(n_batches), int(batch_size)
+        if n < 1 or B < 1:
+            raise ValueError("n_batches and batch_size must be >= 1")
+        before = []
+        for k, g in enumerate(gens):
+            st = (np.random if g is None else g).get_state(legacy=True)
+            self._host_in[k].numpy().view(np.uint32)[:] = pack_np_state(st)
+            before.append(st)
+        consumer = torch.cuda.current_stream(self._dev)
+        slot = self._turn & 1
+        ev = torch.cuda.Event()
+        ev.record(consumer)  # the consumer's last use of the other area is queued by now
+        self._free[slot ^ 1] = ev
+        with torch.cuda.stream(self._stream):
+            if self._free[slot] is not None:
+                self._stream.wait_event(self._free[slot])
+            area = self._slots[slot]
+            if area is None or area.shape[0] < K or area.shape[1] < n * B:
+                area = torch.empty((K, n * B), dtype=torch.int64, device=self._dev)
+                self._slots[slot] = area
+            self._state[:K].copy_(self._host_in[:K], non_blocking=True)
+            outs = (C.c_void_p * K)(*[area[k].data_ptr() for k in range(K)])
+            his_c = (C.c_int64 * K)(*his)
+            with torch.cuda.device(self._dev):
+                check(self._lib.iqlhip_np_randint(ptr(self._state), his_c, K, B, n, outs,
+                                                  C.c_void_p(self._stream.cuda_stream)))
+            self._host_out[:K].copy_(self._state[:K], non_blocking=True)
+            self._done.record(self._stream)
+        area.record_stream(consumer)
+        self._done.synchronize()
+        for k, g in enumerate(gens):
+            (np.random if g is None else g).set_state(unpack_np_state(self._host_out[k].numpy(), before[k]))
+        consumer.wait_event(self._done)
+        self._turn += 1
+        return [area[k, :n * B].view(n, B) for k in range(K)]
+
+
 class ReplayBuffer(_OfflineReplayBuffer):
     """cref:228-290: ``load_dataset`` + a sampler on numpy's GLOBAL generator -- after
     ``np.random.seed(s)`` the index stream is the reference's, draw for draw."""
@@ -227,12 +332,18 @@ class ReplayBuffer(_OfflineReplayBuffer):
     def load_dataset(self, data: Dict[str, np.ndarray]):
         self.load_d4rl_dataset(data)
 
-    def draw_indices(self, batch_size: int, n_batches: Optional[int] = None) -> np.ndarray:
-        """cref:278: ``np.random.randint(0, min(size, pointer), size=batch_size)``, once per batch."""
-        hi = min(self._size, self._pointer)
+    def index_bound(self) -> int:
+        """The ``hi`` of cref:278: indices are drawn from [0, min(size, pointer))."""
+        return min(self._size, self._pointer)
+
+    def draw_indices(self, batch_size: int, n_batches: Optional[int] = None, rng=None) -> np.ndarray:
+        """cref:278: ``np.random.randint(0, min(size, pointer), size=batch_size)``, once per batch
+        (``rng``: an ``np.random.RandomState`` to draw from instead of the global generator)."""
+        gen = np.random if rng is None else rng
+        hi = self.index_bound()
         if n_batches is None:
-            return np.random.randint(0, hi, size=batch_size)
-        return np.stack([np.random.randint(0, hi, size=batch_size) for _ in range(n_batches)])
+            return gen.randint(0, hi, size=batch_size)
+        return np.stack([gen.randint(0, hi, size=batch_size) for _ in range(n_batches)])
 
     def sample(self, batch_size: int, indices=None):
         if indices is None:
@@ -254,9 +365,20 @@ class ImplicitQLearning(_OfflineIQL):
         self.actor_lr_scheduler = self.actor_lr_schedule = actor_lr_scheduler
         self.gamma = gamma
 
-    def train_on_buffer(self, replay_buffer: ReplayBuffer, n_steps: int, batch_size: int):
-        """``n_steps`` x (sample with numpy's generator, train) in one library call."""
-        idx = torch.from_numpy(replay_buffer.draw_indices(batch_size, n_steps)).to(self._dev)
+    def train_on_buffer(self, replay_buffer: ReplayBuffer, n_steps: int, batch_size: int, *,
+                        sampler: str = "host", rng=None):
+        """``n_steps`` x (sample with numpy's generator, train) in one library call.  ``sampler``:
+        "host" draws the indices with numpy and uploads them, "device" draws the same indices with
+        ``NumpyIndexStream``; both leave the generator (``rng``, default numpy's global one) in the
+        same state.  Returns the [n_steps, 3] device loss tensor."""
+        if sampler == "host":
+            idx = torch.from_numpy(replay_buffer.draw_indices(batch_size, n_steps, rng=rng)).to(self._dev)
+        elif sampler == "device":
+            if getattr(self, "_index_stream", None) is None:
+                self._index_stream = NumpyIndexStream(self.device)
+            idx = self._index_stream.draw(replay_buffer.index_bound(), n_steps, batch_size, [rng])[0]
+        else:
+            raise ValueError("sampler must be 'host' or 'device'")
         return self.train_steps(replay_buffer, n_steps, batch_size, indices=idx)
 
     def state_dict(self) -> Dict[str, Any]:
@@ -270,3 +392,214 @@ class ImplicitQLearning(_OfflineIQL):
         sd["actor_lr_schedule"] = sd.pop("actor_lr_scheduler")
         sd.setdefault("total_it", int(sd["actor_lr_schedule"]["last_epoch"]))
         super().load_state_dict(sd)
+
+
+# --------------------------------------------------------------------------- #
+# train (cref:597-749)
+# --------------------------------------------------------------------------- #
+def _reward_model_missing(config: "TrainConfig"):
+    try:
+        import orbax.checkpoint  # noqa: F401
+    except ImportError:
+        raise ImportError(
+            f"custom_offline.train: reward_model=None would read the Orbax checkpoint {config.reward_model_path!r}, "
+            "but orbax is not installed (and iqlpref_amd has no Orbax reader); pass reward_model= a QMLP or "
+            "RewardPT holding its parameters (load_flax_params)") from None
+    raise NotImplementedError(
+        "custom_offline.train: iqlpref_amd has no Orbax checkpoint reader (load_QMLP / load_PT); pass "
+        "reward_model= a QMLP or RewardPT holding its parameters (load_flax_params)")
+
+
+def _minari():
+    try:
+        import minari
+    except ImportError:
+        raise ImportError("custom_offline.train: dataset=None loads the Minari dataset config.dataset_id, but "
+                          "minari is not installed; pass dataset= (iterable of episodes) and eval_env=") from None
+    return minari
+
+
+def _build_trainer(config: "TrainConfig", seed: int, state_dim: int, action_dim: int, max_action: float,
+                   device: str) -> "ImplicitQLearning":
+    """cref:655-689 for one seed: the nets are built right after ``torch.manual_seed(seed)`` on the
+    CPU generator (in cref's order), then moved to the device."""
+    torch.manual_seed(seed)
+    q_network = TwinQ(state_dim, action_dim).to(device)
+    v_network = ValueFunction(state_dim).to(device)
+    pol = DeterministicPolicy if config.iql_deterministic else GaussianPolicy
+    actor = pol(state_dim, action_dim, max_action, dropout=config.actor_dropout).to(device)
+    v_optimizer = torch.optim.Adam(v_network.parameters(), lr=config.vf_lr)
+    q_optimizer = torch.optim.Adam(q_network.parameters(), lr=config.qf_lr)
+    actor_optimizer = torch.optim.Adam(actor.parameters(), lr=config.actor_lr)
+    actor_lr_scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(actor_optimizer, config.update_steps)
+    return ImplicitQLearning(
+        max_action=max_action, actor=actor, actor_optimizer=actor_optimizer, actor_lr_scheduler=actor_lr_scheduler,
+        q_network=q_network, q_optimizer=q_optimizer, v_network=v_network, v_optimizer=v_optimizer,
+        iql_tau=config.iql_tau, beta=config.beta, gamma=config.gamma, tau=config.tau, device=device, seed=seed)
+
+
+def train(config: TrainConfig, dataset=None, reward_model=None, eval_env=None, *,
+          logger: Optional[Callable[[Dict[str, float], int], None]] = None,
+          normalized_score: Optional[Callable] = None, seeds_per_gpu: int = 1, sampler: str = "device",
+          device: Optional[str] = None, chunk: int = 2000):
+    """cref:597-749 on the fused HIP step.
+
+    ``dataset``: an iterable of Minari-style episodes (``observations``, ``actions``,
+    ``terminations``); None loads ``config.dataset_id`` with minari.  ``eval_env``: a gymnasium-API
+    environment (default: ``dataset.recover_environment()``).  ``reward_model``: a ``QMLP``
+    (``query_length == 1``) or ``RewardPT`` holding its parameters; the Orbax checkpoint at
+    ``reward_model_path`` cannot be read here.  ``logger(record, step)``: one call per ``wandb.log``
+    of cref (default: wandb when importable, else print).  ``normalized_score(dataset, returns)``:
+    default ``minari.get_normalized_score``; a ``ValueError`` from it keeps the raw mean return, as
+    cref's ``contextlib.suppress`` does.  ``sampler``: "device" (``NumpyIndexStream``) or "host"
+    (numpy); both give the same indices and the same final generator state.
+
+    The steps run in chunks of at most ``chunk`` that end on evaluation boundaries; the losses of a
+    chunk come back to the host once, after the next chunk has been queued.
+
+    ``seeds_per_gpu`` = K > 1: seed k is ``train_seed + rank K + k``, with its own nets (built right
+    after ``torch.manual_seed(seed)``), its own ``np.random.RandomState(seed)`` index stream (the
+    stream ``np.random.seed(seed)`` gives), its own checkpoints under ``seed_<seed>/`` and a ``seed``
+    entry in its logger records; all K share one buffer and step as one ``SeedGroup`` with the
+    indices of one K-stream draw.  Every seed is bit-identical to ``train()`` of that seed alone.
+    Returns the trainer (K = 1) or the list of K trainers."""
+    if sampler not in ("host", "device"):
+        raise ValueError("sampler must be 'host' or 'device'")
+    K = int(seeds_per_gpu)
+    if not 1 <= K <= _lib.MAX_GROUP:
+        raise ValueError(f"seeds_per_gpu must be in 1..{_lib.MAX_GROUP}")
+    if device is None:
+        device = D.local_device() or "cuda:0"
+    minari = None
+    if dataset is None:
+        minari = _minari()
+        dataset = minari.load_dataset(config.dataset_id)
+    if eval_env is None:
+        if not hasattr(dataset, "recover_environment"):
+            raise ValueError("custom_offline.train: pass eval_env= (the dataset cannot recover_environment())")
+        eval_env = dataset.recover_environment()
+    if normalized_score is None:
+        try:
+            minari = minari or _minari()
+            normalized_score = minari.get_normalized_score
+        except ImportError:
+            normalized_score = None
+    if reward_model is None:
+        _reward_model_missing(config)
+    state_dim = eval_env.observation_space.shape[0]
+    action_dim = eval_env.action_space.shape[0]
+    max_action = float(eval_env.action_space.high[0])
+
+    # ---- dataset, normalisation, buffer (cref:631-653) ----
+    qdataset = qlearning_dataset(dataset, reward_model, config.query_length)
+    if config.normalize_reward:
+        modify_reward(qdataset, config.dataset_id)
+    if config.normalize_state:
+        state_mean, state_std = compute_mean_std(qdataset["observations"], eps=1e-3)
+    else:
+        state_mean, state_std = 0, 1
+    qdataset["observations"] = normalize_states(qdataset["observations"], state_mean, state_std)
+    qdataset["next_observations"] = normalize_states(qdataset["next_observations"], state_mean, state_std)
+    from .train import _NormalizedEnv
+    eval_env = _NormalizedEnv(eval_env, state_mean, state_std, 1.0)  # cref wrap_env, reward_scale 1
+    replay_buffer = ReplayBuffer(state_dim, action_dim, config.buffer_size, device)
+    replay_buffer.load_dataset(qdataset)
+
+    seeds = [D.rank_seed(config.train_seed, K) + k for k in range(K)]
+    ckpt_dirs: List[Optional[str]] = [None] * K
+    if config.checkpoints_path is not None:
+        print(f"Checkpoints path: {config.checkpoints_path}")
+        os.makedirs(config.checkpoints_path, exist_ok=True)
+        import yaml
+        with open(os.path.join(config.checkpoints_path, "config.yaml"), "w") as f:
+            yaml.safe_dump(asdict(config), f)
+        for k in range(K):
+            ckpt_dirs[k] = config.checkpoints_path if K == 1 else os.path.join(config.checkpoints_path,
+                                                                               f"seed_{seeds[k]}")
+            os.makedirs(ckpt_dirs[k], exist_ok=True)
+
+    # ---- seeds and nets (cref:659-689) ----
+    set_seed(seeds[0])  # np, random, torch, PYTHONHASHSEED
+    gens = [None] if K == 1 else [np.random.RandomState(s) for s in seeds]  # None: numpy's global generator
+    trainers = [_build_trainer(config, s, state_dim, action_dim, max_action, device) for s in seeds]
+    group = None
+    if K > 1:
+        from .multi import SeedGroup
+        group = SeedGroup(trainers)
+    stream = NumpyIndexStream(device) if sampler == "device" else None
+
+    if logger is None:
+        try:
+            import wandb
+            wandb.init(config=asdict(config), project=config.project, group=config.group, name=config.name,
+                       id=str(uuid.uuid4()))
+            logger = (lambda d, step: wandb.log(d, step=step)) if K == 1 else \
+                (lambda d, step: wandb.log({f"seed{int(d['seed'])}/{n}": v for n, v in d.items() if n != "seed"},
+                                           step=step))
+        except ImportError:
+            logger = lambda d, step: print(f"[{step}] " + " ".join(f"{n}={v:.5g}" for n, v in d.items()))
+    tag = (lambda rec, k: rec) if K == 1 else (lambda rec, k: dict(rec, seed=seeds[k]))
+
+    best_score = [-np.inf] * K
+    best_step = [0] * K
+    norm = [None] * K  # cref's `normalized_score`: once set it stays (cref:711-718)
+    pending = None  # (first step, [K] device losses) of the chunk whose records are still to be logged
+
+    def flush():
+        nonlocal pending
+        if pending is None:
+            return
+        t0, losses = pending
+        pending = None
+        for k, arr in enumerate(l.cpu().numpy() for l in losses):
+            for i, (v, q, a) in enumerate(arr.tolist()):
+                logger(tag({"value_loss": v, "q_loss": q, "actor_loss": a}, k), t0 + i)
+
+    total, every, t = int(config.update_steps), int(config.eval_every), 0
+    while t < total:
+        nxt = min(total, t + int(chunk), (t // every + 1) * every)
+        n = nxt - t
+        if sampler == "device":
+            idx = stream.draw(replay_buffer.index_bound(), n, config.batch_size, gens)
+        else:
+            idx = [torch.from_numpy(replay_buffer.draw_indices(config.batch_size, n, rng=g)).to(trainers[0]._dev)
+                   for g in gens]
+        if group is None:
+            losses = [trainers[0].train_steps(replay_buffer, n, config.batch_size, indices=idx[0])]
+        else:
+            losses = group.train_steps(replay_buffer, n, config.batch_size, indices=idx, return_losses=True)
+        flush()
+        pending = (t, losses)
+        t = nxt
+        if t % every != 0:
+            continue
+        flush()
+        if group is not None:
+            group.synchronize()
+        step = t - 1
+        for k, trainer in enumerate(trainers):
+            log = lambda d: logger(tag(d, k), step)
+            eval_scores = evaluate(eval_env, trainer.actor, config.eval_episodes, config.eval_seed, device)
+            mean_eval = eval_scores.mean()
+            log({"evaluation_return": mean_eval})
+            if normalized_score is not None:
+                try:
+                    norm[k] = np.asarray(normalized_score(dataset, eval_scores)).mean() * 100
+                    log({"normalized_score": norm[k]})
+                except ValueError:
+                    pass
+            score = norm[k] if norm[k] is not None else mean_eval
+            if score > best_score[k]:
+                best_score[k], best_step[k] = score, step
+                if ckpt_dirs[k] is not None:
+                    torch.save(trainer.state_dict(), os.path.join(ckpt_dirs[k], "best_model.pt"))
+            log({"best_score_so_far": best_score[k]})
+            log({"best_step_so_far": best_step[k]})
+            if ckpt_dirs[k] is not None:
+                torch.save(trainer.state_dict(), os.path.join(ckpt_dirs[k], f"checkpoint_{step}.pt"))
+    flush()
+    if group is not None:
+        group.synchronize()
+        group.close()
+        return trainers
+    return trainers[0]
