@@ -1,0 +1,457 @@
+"""Sweep grids on one GPU: the runs of a W&B grid file, packed into seed groups.
+
+The reference runs its pipeline (PIPELINE.md, Phase 2) as W&B grid sweeps: a file
+``*_sweeps/sweep_*.yaml`` with ``method: grid`` and ``parameters: {name: {value | values}}`` plus a
+``config_path`` naming the base YAML, and ``launch.sh`` starts ``AGENTS_PER_GPU`` agents per GPU, one
+run each.  Here one process takes the whole grid:
+
+``expand_sweep(file)``
+    one ``TrainConfig`` per run of the grid.
+``train_runs(configs)``
+    every config trained as ``train(config)`` trains it, bit for bit, with runs of one shape stepped
+    together as one ``SeedGroup`` (iqlpref_amd.multi): the group kernels read every hyperparameter
+    (discount, tau, beta, iql_tau, dropout rate, learning rates, schedule length) from each member's
+    own descriptor, so runs that differ in any of them -- not only in the seed -- share one launch
+    sequence.
+``python -m iqlpref_amd.sweep SWEEP.yaml [--list] [--only i,j] [--runs_per_gpu K] [--field value]``
+    the command line over both.
+
+The W&B service itself (agents, the sweep server, random / bayes search) stays out.
+"""
+import argparse
+import importlib
+import itertools
+import os
+import sys
+from dataclasses import asdict, fields
+from typing import Any, Callable, Dict, List, Mapping, Optional, Sequence, Tuple, Union
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import distributed as D
+from .iql import ImplicitQLearning, TrainConfig, load_config
+
+# top-level keys of a sweep file that only name or describe it (kept as labels, otherwise ignored)
+LABEL_KEYS = ("program", "project", "name", "description", "metric", "command", "entity")
+# the fields build_dataset reads besides the environment: runs equal in all of them share one relabel
+RELABEL_FIELDS = ("reward_model_path", "query_length", "bnn_reward_model", "bnn_alpha", "bnn_n_samples",
+                  "mr_ensemble", "mr_alpha", "mr_burn_in")
+# observation / action sizes of the D4RL task families the reference's sweeps name (for --list
+# without gym; training always reads them from the environment itself)
+D4RL_DIMS = {"antmaze": (29, 8), "pen": (45, 24), "door": (39, 28), "hammer": (46, 26), "relocate": (39, 30),
+             "halfcheetah": (17, 6), "hopper": (11, 3), "walker2d": (17, 6), "kitchen": (60, 9)}
+
+
+# --------------------------------------------------------------------------- #
+# sweep files -> configs
+# --------------------------------------------------------------------------- #
+def load_sweep(spec_or_path: Union[str, os.PathLike, Mapping]) -> Dict[str, Any]:
+    """A sweep file's contents (a path is read as YAML; a mapping is taken as it is)."""
+    if isinstance(spec_or_path, Mapping):
+        return dict(spec_or_path)
+    import yaml
+    with open(spec_or_path) as f:
+        spec = yaml.safe_load(f)
+    if not isinstance(spec, dict):
+        raise ValueError(f"{spec_or_path}: a sweep file is a mapping")
+    return spec
+
+
+def sweep_axes(spec: Mapping) -> List[Tuple[str, List[Any]]]:
+    """The grid's parameters in file order: [(name, [values...])].  Only ``method: grid`` with
+    ``{value: x}`` / ``{values: [...]}`` entries; every name must be a TrainConfig field or
+    ``config_path`` (all unknown names are reported together)."""
+    method = spec.get("method")
+    if method != "grid":
+        raise ValueError(f"sweep method {method!r}: only 'grid' is supported (random / bayes search needs the "
+                         "W&B sweep service)")
+    extra = sorted(set(spec) - set(LABEL_KEYS) - {"method", "parameters"})
+    if extra:
+        raise ValueError(f"unsupported top-level sweep keys: {', '.join(extra)}")
+    params = spec.get("parameters") or {}
+    if not isinstance(params, Mapping):
+        raise ValueError("'parameters' must map names to {value: x} or {values: [...]}")
+    known = {f.name for f in fields(TrainConfig)} | {"config_path"}
+    axes, unknown = [], []
+    for name, entry in params.items():
+        if not isinstance(entry, Mapping) or len(entry) != 1 or next(iter(entry)) not in ("value", "values"):
+            got = sorted(entry) if isinstance(entry, Mapping) else type(entry).__name__
+            raise ValueError(f"parameter {name!r}: a grid entry is exactly {{value: x}} or {{values: [...]}}, "
+                             f"got {got}")
+        if "value" in entry:
+            vals = [entry["value"]]
+        else:
+            vals = entry["values"]
+            if not isinstance(vals, (list, tuple)) or not vals:
+                raise ValueError(f"parameter {name!r}: 'values' must be a non-empty list")
+            vals = list(vals)
+        if name not in known:
+            unknown.append(name)
+        axes.append((name, vals))
+    if unknown:
+        raise ValueError(f"unknown sweep parameters (neither TrainConfig fields nor config_path): {', '.join(unknown)}")
+    return axes
+
+
+def expand_sweep(spec_or_path, *, config_root: str = ".", **overrides) -> List[TrainConfig]:
+    """One TrainConfig per run of a W&B grid sweep.
+
+    Order: the cartesian product of the parameters in the order the file lists them, the LAST
+    parameter varying fastest (``a: [1, 2]``, ``b: [x, y]`` -> (1, x), (1, y), (2, x), (2, y)).
+
+    Each run loads its ``config_path`` (resolved against ``config_root``) with ``load_config``; the
+    sweep's values override the base YAML and ``overrides`` (the command line's ``--field value``)
+    override both, all coerced to the field types as load_config does.  With ``reward_model_root``
+    every run reads ``{root}_{seed}`` (TrainConfig.__post_init__, as iql_eval.py does).  Every config
+    carries ``sweep_label``: the varying parameters of its run, e.g. ``normalize_reward=3,seed=0``."""
+    spec = load_sweep(spec_or_path)
+    axes = sweep_axes(spec)
+    known = {f.name for f in fields(TrainConfig)} | {"config_path"}
+    bad = [k for k in overrides if k not in known]
+    if bad:
+        raise ValueError(f"unknown overrides (not TrainConfig fields): {', '.join(bad)}")
+    names = [n for n, _ in axes]
+    varying = [n for n, vals in axes if len(vals) > 1 and n not in overrides]
+    out = []
+    for combo in itertools.product(*[vals for _, vals in axes]):
+        run = dict(zip(names, combo))
+        label = ",".join(f"{n}={run[n]}" for n in varying)
+        run.update(overrides)
+        cp = run.pop("config_path", None)
+        path = None if cp is None else os.path.join(config_root, os.path.expanduser(str(cp)))
+        cfg = load_config(path, **run)
+        cfg.sweep_label = label  # (an attribute, not a field: config.yaml stays what train() writes)
+        out.append(cfg)
+    return out
+
+
+# --------------------------------------------------------------------------- #
+# host-side planning (no device work)
+# --------------------------------------------------------------------------- #
+def shape_key(config: TrainConfig, dims, precision: str = "bf16") -> tuple:
+    """What runs of one SeedGroup must share (iqlhip_group_create's same_shape): state / action dims,
+    batch size, policy kind, actor dropout on/off, critics, precision, device.  ``dims`` = (S, A), or
+    None when unknown (the env name stands in: runs of one env always share their dims)."""
+    dims_key = tuple(int(d) for d in dims) if dims is not None else ("env", config.env)
+    return (dims_key, int(config.batch_size), bool(config.iql_deterministic), bool(config.actor_dropout),
+            int(config.n_critics), precision, str(config.device))
+
+
+def _check_runs_per_gpu(runs_per_gpu: int) -> int:
+    k = int(runs_per_gpu)
+    if not 1 <= k <= _lib.MAX_GROUP:
+        raise ValueError(f"runs_per_gpu = {runs_per_gpu}: must be 1..{_lib.MAX_GROUP}")
+    return k
+
+
+def plan_batches(configs: Sequence[TrainConfig], dims, runs_per_gpu: int = 8,
+                 precision: str = "bf16") -> List[List[int]]:
+    """Launch batches as lists of config indices, in the order they run.  Runs of equal
+    ``shape_key`` are taken greedily in config order into batches of at most ``runs_per_gpu``; a
+    batch's position is that of its first run.  ``dims``: one (S, A) per config, or a mapping
+    env name -> (S, A) (entries may be None, see ``shape_key``)."""
+    k = _check_runs_per_gpu(runs_per_gpu)
+    open_batch: Dict[tuple, List[int]] = {}
+    batches: List[List[int]] = []
+    for i, cfg in enumerate(configs):
+        d = dims.get(cfg.env) if isinstance(dims, Mapping) else dims[i]
+        key = shape_key(cfg, d, precision)
+        b = open_batch.get(key)
+        if b is None or len(b) >= k:
+            b = open_batch[key] = []
+            batches.append(b)
+        b.append(i)
+    return batches
+
+
+def rank_share(n_configs: int, rank: int, world_size: int) -> List[int]:
+    """The configs rank ``rank`` of ``world_size`` trains: index = rank (mod world size)."""
+    return list(range(int(rank), int(n_configs), max(int(world_size), 1)))
+
+
+def check_runs(configs: Sequence[TrainConfig], runs_per_gpu: int) -> None:
+    """The checks train_runs makes before any device work."""
+    _check_runs_per_gpu(runs_per_gpu)
+    seen: Dict[str, int] = {}
+    for i, cfg in enumerate(configs):
+        if cfg.checkpoints_path is None:
+            continue
+        p = os.path.abspath(os.path.expanduser(cfg.checkpoints_path))
+        if p in seen:
+            raise ValueError(f"runs {seen[p]} and {i} share checkpoints_path {cfg.checkpoints_path!r}")
+        seen[p] = i
+
+
+def _rank_world() -> Tuple[int, int]:
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized():
+        return dist.get_rank(), dist.get_world_size()
+    return int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
+
+
+def _relabel_key(config: TrainConfig) -> tuple:
+    return (config.env, str(config.device)) + tuple(getattr(config, f) for f in RELABEL_FIELDS)
+
+
+def _next_boundary(config: TrainConfig, t: int) -> int:
+    """ref:1533-1544 as train() chunks it: the run's next log boundary, eval boundary or end."""
+    return min(int(config.max_timesteps), (t // config.log_freq + 1) * config.log_freq,
+               (t // config.eval_freq + 1) * config.eval_freq)
+
+
+# --------------------------------------------------------------------------- #
+# training
+# --------------------------------------------------------------------------- #
+def _default_logger(configs: Sequence[TrainConfig], mine: Sequence[int], run_ids: Sequence[int]):
+    """One wandb run per process, the records of run i under ``run<i>/`` (with its own step axis:
+    every launch batch starts again at step 0); without wandb the records are printed."""
+    try:
+        import wandb
+    except ImportError:
+        return lambda d, step: print(f"[run {d['run']} seed {d['seed']}] [{step}] " +
+                                     " ".join(f"{n}={v:.5g}" for n, v in d.items() if n not in ("run", "seed")))
+    first = configs[mine[0]]
+    wandb.init(config={f"run{run_ids[i]}": asdict(configs[i]) for i in mine}, project=first.project,
+               group=first.group, name=first.name)
+    for i in mine:
+        wandb.define_metric(f"run{run_ids[i]}/*", step_metric=f"run{run_ids[i]}/step")
+
+    def log(d, step):
+        r = d["run"]
+        wandb.log({f"run{r}/step": step, **{f"run{r}/{n}": v for n, v in d.items() if n not in ("run", "seed")}})
+    return log
+
+
+def _resolve_envs(configs: Sequence[TrainConfig], mine: Sequence[int], env) -> Dict[str, Any]:
+    """env name -> environment object for this rank's runs."""
+    names = list(dict.fromkeys(configs[i].env for i in mine))
+    if env is None:
+        import gym
+        return {n: gym.make(n) for n in names}
+    if isinstance(env, Mapping):
+        missing = [n for n in names if n not in env]
+        if missing:
+            raise ValueError(f"no environment given for {', '.join(missing)}")
+        return {n: env[n] for n in names}
+    if len(names) > 1:
+        raise ValueError(f"one env object given for runs of {len(names)} environments ({', '.join(names)}); "
+                         "pass env=None or a mapping env name -> env")
+    return {n: env for n in names}
+
+
+def train_runs(configs: Sequence[TrainConfig], env=None, dataset=None, *, runs_per_gpu: int = 8,
+               logger: Optional[Callable[[Dict[str, float], int], None]] = None,
+               evaluate: Union[None, Callable, Sequence[Callable]] = None, precision: str = "bf16",
+               raw_dataset=None, host_prep: bool = False, vector_env: Optional[Callable] = None,
+               group_mode: Optional[str] = None,
+               run_ids: Optional[Sequence[int]] = None) -> List[ImplicitQLearning]:
+    """Train every config exactly as ``train(config)`` would -- the same logged records (plus ``run``
+    / ``seed`` entries), evaluation calls (own actor, own seed), checkpoint files (``config.yaml`` and
+    ``checkpoint_{t}.pt`` under the run's own ``checkpoints_path``) and final parameters, target,
+    Adam moments and ``total_it``, bit for bit -- with the runs packed into seed groups.
+
+    Launch batches (``plan_batches``): runs of one shape key (dims, batch size, policy kind, dropout
+    on/off, critics, precision, device), at most ``runs_per_gpu`` (1..16) in config order; the
+    batches run one after another, each as one ``SeedGroup`` of mode ``group_mode`` (None: the
+    SeedGroup default).  Inside a batch everything else may differ: seed, reward normalisation,
+    discount, tau, beta, iql_tau, learning rates, dropout rate, max_timesteps, log / eval
+    frequencies, reward model, and the env when its dims match.  All runs of a batch start at step
+    0; every library call runs to the next log / eval / end boundary of ANY active run; a finished
+    run leaves the batch and the group is rebuilt over the others.
+
+    ``env``: one environment for runs of one env name, a mapping env name -> environment, or None
+    (one ``gym.make`` per name).  ``dataset`` / ``raw_dataset`` as in ``train()``, or a callable
+    ``config -> dict`` (called once per distinct relabel key).  The dataset is relabelled once per
+    distinct (env, reward-model fields) and one device buffer is built per distinct (relabel,
+    normalize_reward, normalize); runs equal in those share it.  ``evaluate``: one callable
+    ``(actor, step)`` or a list with one per config.  ``logger(record, step)``: default one wandb run
+    per process with keys ``run<i>/``, or print.  ``run_ids``: the names of the runs in the records
+    (default 0 .. n-1).
+
+    Under torchrun rank r trains the configs with index = r (mod world size), each at its own seed,
+    with no collectives.  Returns this rank's trainers in config order."""
+    # the module, not the function the package exports under the same name (build_dataset is looked
+    # up on it at call time: tests count its calls)
+    T = importlib.import_module(".train", __package__)
+    from .multi import SeedGroup
+
+    configs = list(configs)
+    check_runs(configs, runs_per_gpu)
+    n = len(configs)
+    run_ids = list(range(n)) if run_ids is None else [int(r) for r in run_ids]
+    if len(run_ids) != n:
+        raise ValueError("run_ids: one entry per config")
+    if isinstance(evaluate, (list, tuple)) and len(evaluate) != n:
+        raise ValueError(f"evaluate: {len(evaluate)} callables for {n} configs")
+    if group_mode not in (None, "group", "split", "streams"):
+        raise ValueError("group_mode must be None, 'group', 'split' or 'streams'")
+    rank, world = _rank_world()
+    mine = rank_share(n, rank, world)
+    if not mine:
+        return []
+    envs = _resolve_envs(configs, mine, env)
+    bound = D.local_device()  # under torchrun: this rank's GPU
+    if bound is not None:
+        for i in mine:
+            configs[i].device = bound
+    dims = {name: (e.observation_space.shape[0], e.action_space.shape[0]) for name, e in envs.items()}
+    local = plan_batches([configs[i] for i in mine], [dims[configs[i].env] for i in mine], runs_per_gpu, precision)
+    batches = [[mine[j] for j in b] for b in local]
+    if logger is None:
+        logger = _default_logger(configs, mine, run_ids)
+    pick = lambda src, cfg: src(cfg) if callable(src) else src
+    source = dataset if dataset is not None else raw_dataset
+
+    # datasets and device buffers, built when a batch first needs them and dropped after their last batch
+    rcfgs = {i: T.seed_configs(configs[i], [configs[i].seed])[0] for i in mine}
+    rkeys = {i: _relabel_key(rcfgs[i]) for i in mine}
+    bkeys = {i: (rkeys[i], configs[i].normalize_reward, bool(configs[i].normalize), configs[i].buffer_size)
+             for i in mine}
+    last_use_r, last_use_b = {}, {}
+    for bi, b in enumerate(batches):
+        for i in b:
+            last_use_r[rkeys[i]], last_use_b[bkeys[i]] = bi, bi
+    datasets: Dict[tuple, Any] = {}
+    buffers: Dict[tuple, Tuple[Any, Any, Any]] = {}
+
+    def buffer_for(i):
+        cfg = configs[i]
+        if bkeys[i] not in buffers:
+            if rkeys[i] not in datasets:
+                rc, e = rcfgs[i], envs[cfg.env]
+                src = pick(source, cfg)
+                datasets[rkeys[i]] = T.build_dataset(rc, e, src) if (rc.reward_model_path or dataset is None) else src
+            ds = datasets[rkeys[i]]
+            if host_prep:  # the numpy path rewrites its dataset in place: every preparation gets a copy
+                ds = {k: np.array(v) for k, v in ds.items()}
+            S, A = dims[cfg.env]
+            buffers[bkeys[i]] = T._prepare_replay(cfg, ds, S, A, host_prep)
+        return buffers[bkeys[i]]
+
+    trainers: Dict[int, ImplicitQLearning] = {}
+    for bi, batch in enumerate(batches):
+        state = {}
+        for i in batch:
+            cfg = configs[i]
+            buf, mean, std = buffer_for(i)
+            e = envs[cfg.env]
+            max_action = float(e.action_space.high[0])
+            if cfg.checkpoints_path is not None:
+                print(f"Checkpoints path: {cfg.checkpoints_path}")
+                os.makedirs(cfg.checkpoints_path, exist_ok=True)
+                import yaml
+                with open(os.path.join(cfg.checkpoints_path, "config.yaml"), "w") as f:
+                    yaml.safe_dump(asdict(cfg), f)
+            trainers[i] = T._build_trainer(cfg, cfg.seed, dims[cfg.env][0], dims[cfg.env][1], max_action, precision)
+            state[i] = (buf, mean, std, max_action, e)
+        _run_batch(configs, batch, trainers, state, SeedGroup, group_mode, logger, evaluate, vector_env, run_ids)
+        for key in [k for k in datasets if last_use_r[k] <= bi]:
+            del datasets[key]
+        for key in [k for k in buffers if last_use_b[k] <= bi]:
+            del buffers[key]
+    return [trainers[i] for i in mine]
+
+
+def _run_batch(configs, batch, trainers, state, SeedGroup, group_mode, logger, evaluate, vector_env, run_ids):
+    """One launch batch: all runs start at step 0 and run in lock step to the next boundary of any
+    of them; a run at its end leaves and the group is rebuilt over the rest."""
+    from .train import eval_actor
+
+    def make_group(members):
+        trs = [trainers[i] for i in members]
+        return SeedGroup(trs) if group_mode is None else SeedGroup(trs, mode=group_mode)
+
+    active = [i for i in batch if int(configs[i].max_timesteps) > 0]
+    group = make_group(active) if active else None
+    windows: Dict[int, torch.Tensor] = {}
+    tag = lambda rec, i: dict(rec, run=run_ids[i], seed=configs[i].seed)
+    t = 0
+    while active:
+        nxt = min(_next_boundary(configs[i], t) for i in active)
+        B = configs[active[0]].batch_size
+        losses = group.train_steps([state[i][0] for i in active], nxt - t, B, return_losses=True)
+        for i, l in zip(active, losses):
+            windows[i] = l if t % configs[i].log_freq == 0 else torch.cat([windows[i], l])
+        t = nxt
+        for i in active:
+            if t % configs[i].log_freq == 0:
+                mean = windows[i].mean(dim=0).tolist()
+                rec = {"value_loss": mean[0], "q_loss": mean[1], "actor_loss": mean[2]}
+                logger(tag(rec, i), trainers[i].total_it)
+        evals = [i for i in active if t % configs[i].eval_freq == 0]
+        if evals:
+            group.synchronize()
+        for i in evals:
+            cfg, trainer = configs[i], trainers[i]
+            _, mean_s, std_s, max_action, e = state[i]
+            ev = evaluate[i] if isinstance(evaluate, (list, tuple)) else evaluate
+            eval_log: Dict[str, float] = {}
+            if ev is not None:
+                scores, steps_to_goal = ev(trainer.actor, t)
+            elif vector_env is not None or (e is not None and hasattr(e, "spec")):
+                scores, steps_to_goal = eval_actor(cfg.env, trainer.actor, max_action, mean_s, std_s, cfg.device,
+                                                   cfg.n_episodes, cfg.seed, vector_env=vector_env)
+            else:
+                scores, steps_to_goal = None, []
+            if scores is not None:
+                eval_log["mean_score"] = float(np.mean(scores))
+                if "antmaze" in cfg.env.lower():
+                    eval_log["avg_steps_to_goal"] = float(np.mean(steps_to_goal)) if steps_to_goal else -1.0
+                logger(tag(eval_log, i), trainer.total_it)
+            if cfg.checkpoints_path is not None:
+                torch.save(trainer.state_dict(), os.path.join(cfg.checkpoints_path, f"checkpoint_{t - 1}.pt"))
+        left = [i for i in active if t < int(configs[i].max_timesteps)]
+        if len(left) != len(active):
+            group.synchronize()
+            group.close()
+            active = left
+            group = make_group(active) if active else None
+    if group is not None:
+        group.synchronize()
+        group.close()
+
+
+# --------------------------------------------------------------------------- #
+# command line
+# --------------------------------------------------------------------------- #
+def _list_dims(env_name: str):
+    fam = env_name.split("-")[0].lower()
+    if fam in D4RL_DIMS:
+        return D4RL_DIMS[fam]
+    return None  # unknown family: batched by env name
+
+
+def main(argv=None):
+    """python -m iqlpref_amd.sweep SWEEP.yaml [--config_root DIR] [--runs_per_gpu K] [--only 0,3,5]
+    [--list] [--field value ...]"""
+    from .train import parse_overrides
+    ap = argparse.ArgumentParser(prog="python -m iqlpref_amd.sweep", allow_abbrev=False,
+                                 description="train the runs of a W&B grid sweep file, packed into seed groups")
+    ap.add_argument("sweep", help="sweep file (method: grid)")
+    ap.add_argument("--config_root", default=".", help="directory the sweep's config_path is relative to")
+    ap.add_argument("--runs_per_gpu", type=int, default=int(os.environ.get("AGENTS_PER_GPU", "8")),
+                    help="runs stepped together as one seed group (default: $AGENTS_PER_GPU, else 8)")
+    ap.add_argument("--only", default=None, help="comma-separated run indices to train")
+    ap.add_argument("--list", action="store_true", help="print every run's index, label and launch batch; no GPU")
+    args, rest = ap.parse_known_args(argv)
+    configs = expand_sweep(args.sweep, config_root=args.config_root, **parse_overrides(rest))
+    ids = list(range(len(configs)))
+    if args.only:
+        ids = [int(s) for s in args.only.split(",") if s.strip()]
+        bad = [i for i in ids if not 0 <= i < len(configs)]
+        if bad:
+            raise SystemExit(f"--only: no run {bad} (the sweep has {len(configs)})")
+    chosen = [configs[i] for i in ids]
+    if args.list:
+        batches = plan_batches(chosen, [_list_dims(c.env) for c in chosen], args.runs_per_gpu)
+        where = {j: b for b, members in enumerate(batches) for j in members}
+        for j, i in enumerate(ids):
+            print(f"{i}\t{configs[i].sweep_label or '-'}\tbatch {where[j]}")
+        return
+    train_runs(chosen, runs_per_gpu=args.runs_per_gpu, run_ids=ids)
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])

@@ -398,8 +398,14 @@ def main(argv=None):
                     help="independent seeds trained side by side on each GPU "
                          "(ensemble_sweeps/launch.sh:12 AGENTS_PER_GPU)")
     args, rest = ap.parse_known_args(argv)
+    train(load_config(args.config_path, **parse_overrides(rest)), seeds_per_gpu=args.seeds_per_gpu)
+
+
+def parse_overrides(tokens: Sequence[str]) -> Dict[str, str]:
+    """``--field value`` / ``--field=value`` pairs of the command line -> {field: value} (strings; load_config
+    coerces them)."""
     over = {}
-    it = iter(rest)
+    it = iter(tokens)
     for tok in it:
         if tok.startswith("--"):
             k = tok[2:]
@@ -408,7 +414,7 @@ def main(argv=None):
             else:
                 v = next(it)
             over[k] = v
-    train(load_config(args.config_path, **over), seeds_per_gpu=args.seeds_per_gpu)
+    return over
 
 
 if __name__ == "__main__":
