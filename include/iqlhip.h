@@ -53,8 +53,9 @@ const char *iqlhip_build_tag(void);
 /*             for the three optimisers.  n_hidden = 2 with hidden_dim 64, 128 */
 /*             or 256 (the reference's default and every shipped YAML) runs on */
 /*             the tuned three-kernel step; every other shape on the general   */
-/*             layer-wise step (csrc/iql_deep.hip: same arithmetic, plain      */
-/*             launches only, no seed groups);                                 */
+/*             layer-wise step (csrc/iql_deep.hip: same arithmetic, graph      */
+/*             replay and seed groups of one shape as on the tuned step; no    */
+/*             CU-slice sub-groups);                                           */
 /*   MLP fwd   1..8 layers, every width in [1, 1024] (beyond 256: a plain      */
 /*             one-wave-per-16-rows variant);                                  */
 /*   CVaR      1 <= n_tail <= S <= 2400;                                       */
@@ -233,10 +234,11 @@ int iqlhip_trainer_set_lr(iqlhip_trainer *t, double lr_q, double lr_v, double lr
  *   sample (ref:211-221) -> ImplicitQLearning.train (ref:639-662).
  * idx: NULL (on-device Philox indices) or device int64[n_steps][batch].
  * dropout_keep: NULL (on-device Philox masks) or device uint8
- *   [n_steps][2][batch][hidden] (1 = keep); ignored without actor dropout.
+ *   [n_steps][n_hidden][batch][hidden] (1 = keep); ignored without actor dropout.
  * losses_out: NULL or device fp32[n_steps][3] = value_loss, q_loss, actor_loss
  *   of each step (ref:589,607,633).
- * graph_unroll: > 0 replays a captured hipGraph of that many steps per launch;
+ * graph_unroll: > 0 replays a captured hipGraph of that many steps per launch
+ *   (the general step caps it at 1024, the steps of one upload of its arguments);
  *   0: plain kernel launches, three per step, from this call's loop (one seed: the
  *   faster mode, a graph launch costs ~5 us of device time; seed groups: graphs of 50).
  * Asynchronous on `stream`, except that a call never leaves more than
@@ -247,9 +249,11 @@ int iqlhip_train_steps(iqlhip_trainer *t, const iqlhip_replay_view *view, int64_
                        int32_t graph_unroll, void *stream);
 
 /* ------------------------------------------------------------------------ */
-/* Seed groups: K independent trainers of ONE shape (dims, batch, precision,   */
-/* critics, policy kind, dropout on/off) stepped by one launch sequence -- the */
-/* three kernels of a step run with gridDim.y = K.  The seeds share nothing;   */
+/* Seed groups: K independent trainers of ONE shape (dims, hidden layers,      */
+/* batch, precision, critics, policy kind, dropout on/off) stepped by one      */
+/* launch sequence -- the three kernels of a step run once for all K members.  */
+/* All members run on the tuned step or all on the general step (a mix is      */
+/* IQLHIP_ERR_INVALID).  The seeds share nothing;                              */
 /* each one's arithmetic is bit-identical to stepping it alone.  This is the   */
 /* path's sharding unit (one (seed, dataset) run, ensemble_sweeps/launch.sh:   */
 /* 12 AGENTS_PER_GPU, :84-94) used inside one GPU.                              */
@@ -276,6 +280,11 @@ int iqlhip_group_train_steps(iqlhip_group *g, const iqlhip_replay_view *views, i
  * AGENTS_PER_GPU processes share the GPU unmanaged).  Destroy with iqlhip_stream_destroy.   */
 int iqlhip_stream_create_cu_slice(void **stream, int32_t slice, int32_t n_slices);
 int iqlhip_stream_destroy(void *stream);
+
+/* Which path ran: steps issued as plain launches (three per step; a group step counts once) and
+ * hipGraph replays issued since the handle was created.  Either pointer may be NULL.          */
+int iqlhip_trainer_launch_counts(iqlhip_trainer *t, int64_t *eager_steps, int64_t *graph_launches);
+int iqlhip_group_launch_counts(iqlhip_group *g, int64_t *eager_steps, int64_t *graph_launches);
 
 /* Per-kernel HIP-event timing of a group's launches (as iqlhip_trainer_set/get_timing). */
 int iqlhip_group_set_timing(iqlhip_group *g, int32_t enable);

@@ -25,7 +25,10 @@ hipError_t deep_create(DeepTrainer **, const iqlhip_trainer_config &, int n_hidd
                        const int64_t *offsets);
 void deep_destroy(DeepTrainer *);
 hipError_t deep_sync_weights(DeepTrainer *, hipStream_t);
-hipError_t deep_step(DeepTrainer *, const DeepStep &, hipStream_t, hipEvent_t *ev);
+const DeepDesc &deep_desc(const DeepTrainer *);
+const DeepDesc *deep_desc_dev(const DeepTrainer *);
+hipError_t deep_step(const DeepTrainer *, const DeepDesc *, const DeepArgs *, DeepCtr *, const AdamCoef *coefs, int K,
+                     hipStream_t, hipEvent_t *ev);
 hipError_t deep_infer(DeepTrainer *, int which, const float *s, const float *a, int64_t n, float *out, hipStream_t);
 int layer2_parts(int H);
 hipError_t launch_forward(bool, const TrainerDesc &, const TrainerDesc *, const DevArgs *, const DevCtr *,
@@ -257,13 +260,51 @@ struct Throttle {
   }
 };
 
+// The general step's arguments in device memory, for one trainer (K = 1) or the K members of a group:
+//   [K] DeepArgs | [K] DeepCtr | [CAP][K] AdamCoef
+// A call is cut into chunks of at most CAP steps; ahead of each, the block, the counters (= the chunk's
+// first step) and the Adam coefficients of its steps -- computed HERE in double, as the plain launches
+// always had them -- go up in ONE copy from a ring of pinned slots (a slot is reused only after the copy
+// that read it has completed: its event).
+struct DeepRing {
+  static constexpr int RING = 4;
+  static constexpr int64_t CAP = 1024;
+  int K = 0;
+  char *dev = nullptr;
+  char *host[RING] = {};
+  hipEvent_t ev[RING] = {};
+  bool used[RING] = {};
+  int head = 0;
+  size_t head_bytes() const { return (size_t)K * (sizeof(DeepArgs) + sizeof(DeepCtr)); }
+  size_t bytes(int64_t n) const { return head_bytes() + (size_t)n * K * sizeof(AdamCoef); }
+  DeepArgs *dargs() const { return reinterpret_cast<DeepArgs *>(dev); }
+  DeepCtr *dctr() const { return reinterpret_cast<DeepCtr *>(dev + (size_t)K * sizeof(DeepArgs)); }
+  AdamCoef *dcoef() const { return reinterpret_cast<AdamCoef *>(dev + head_bytes()); }
+  hipError_t init(int k) {
+    K = k;
+    hipError_t e = hipMalloc((void **)&dev, bytes(CAP));
+    return e != hipSuccess ? e : hipMemset(dev, 0, bytes(CAP));
+  }
+  void destroy() {
+    for (int k = 0; k < RING; ++k) {
+      if (ev[k]) (void)hipEventDestroy(ev[k]);
+      if (host[k]) (void)hipHostFree(host[k]);
+      ev[k] = nullptr, host[k] = nullptr;
+    }
+    if (dev) (void)hipFree(dev);
+    dev = nullptr;
+  }
+};
+
 struct iqlhip_trainer {
   iqlhip_trainer_config cfg;
   iqlhip_arenas arenas;
   // shapes outside the tuned step's (n_hidden != 2 or another width): the general layer-wise step;
-  // of the members below only cfg, the learning rates, total_it, the timing events, the throttle and
-  // batch_rows are in use then
+  // of the members below only cfg, the learning rates, total_it, the graph, the timing events, the
+  // throttle, `group` and batch_rows are in use then
   DeepTrainer *deep = nullptr;
+  DeepRing deep_ring;
+  int64_t n_eager = 0, n_graph = 0;  // steps issued as plain launches / graph replays issued (iqlhip_trainer_launch_counts)
   TrainerDesc D;
   bool bf16;
   void *ws = nullptr;
@@ -541,6 +582,11 @@ extern "C" int iqlhip_trainer_create(iqlhip_trainer **out, const iqlhip_trainer_
     const size_t rows_bytes = (size_t)cfg->batch_size * iqlhip_replay_row_stride(cfg->state_dim, cfg->action_dim) * 4;
     hipError_t e = deep_create(&t->deep, *cfg, n_hidden(*cfg), *ar, L.off);
     if (e == hipSuccess && (e = hipMalloc((void **)&t->batch_rows, rows_bytes)) != hipSuccess) deep_destroy(t->deep);
+    if (e == hipSuccess && (e = t->deep_ring.init(1)) != hipSuccess) {
+      deep_destroy(t->deep);
+      (void)hipFree(t->batch_rows);
+      t->deep_ring.destroy();
+    }
     if (e != hipSuccess) {
       delete t;
       return fail(e == hipErrorOutOfMemory ? IQLHIP_ERR_NOMEM : IQLHIP_ERR_HIP, "general step: %s", hipGetErrorString(e));
@@ -783,6 +829,7 @@ extern "C" int iqlhip_trainer_destroy(iqlhip_trainer *t) {
   if (t->deep) {
     deep_destroy(t->deep);
     (void)hipFree(t->batch_rows);
+    t->deep_ring.destroy();
   }
   if (t->ws) (void)hipFree(t->ws);
   delete t;
@@ -811,7 +858,7 @@ extern "C" int iqlhip_trainer_set_step(iqlhip_trainer *t, int64_t total_it) {
   // non-blocking stream can race the counter write below
   HIP_TRY(hipDeviceSynchronize());
   t->total_it = total_it;
-  if (t->deep) return 0;  // (the general step takes its step count with every launch)
+  if (t->deep) return 0;  // (the general step's device counter is set with the arguments of every call)
   DevCtr c;
   memset(&c, 0, sizeof(c));
   c.ctr[0] = total_it, c.ctr[1] = total_it;
@@ -900,43 +947,130 @@ static hipError_t push_args(iqlhip_trainer *t, const DevArgs &args_in, int64_t n
   return hipSuccess;
 }
 
-// The general step: three plain launches per step, the step's arguments (index / mask / loss slices,
-// Adam coefficients computed here in double) by value.  graph_unroll is ignored.
-static int run_steps_deep(iqlhip_trainer *t, const DevArgs &a, int64_t n_steps, hipStream_t st) {
-  const int64_t B = t->cfg.batch_size, H = t->cfg.hidden_dim, NH = n_hidden(t->cfg);
-  for (int64_t i = 0; i < n_steps; ++i) {
-    DeepStep s;
-    memset(&s, 0, sizeof(s));
-    s.rows = a.rows, s.n_rows = a.n_rows, s.row_stride = a.row_stride, s.idx_mode = a.idx_mode;
-    s.idx = a.idx ? a.idx + i * B : nullptr;
-    s.drop_keep = a.drop_keep ? a.drop_keep + i * NH * B * H : nullptr;
-    s.losses_out = a.losses_out ? a.losses_out + i * 3 : nullptr;
-    s.step = a.base_step + i;
-    s.coef = make_adam_coef(t->cfg.adam_beta1, t->cfg.adam_beta2, t->cfg.adam_eps, a.lr_q, a.lr_v, a.lr_a_base,
-                            t->cfg.cosine_t_max, s.step + 1);
-    HIP_TRY(deep_step(t->deep, s, st, t->timing ? t->ev : nullptr));
-    if (t->timing) {
-      HIP_TRY(hipEventRecord(t->ev[4], st));
-      HIP_TRY(hipEventSynchronize(t->ev[4]));
-      for (int k = 0; k < 3; ++k) {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, t->ev[k], t->ev[k + 1]));
-        t->t_acc[k] += ms;
+// The general step, for one trainer or the K members of a group.  Per chunk of at most DeepRing::CAP steps:
+// the arguments, the counters and the chunk's Adam coefficients go to the device (DeepRing), then the steps
+// run as hipGraphs of `graph_unroll` steps (3 graph_unroll kernel nodes, a linear chain captured on one
+// stream) and the remainder as plain launches.  Chunks are a multiple of graph_unroll steps long, so only the
+// tail of a call runs eagerly.  Everything that differs between a trainer and a group is referenced here.
+struct DeepRun {
+  iqlhip_trainer *const *tr;
+  int K;
+  DeepRing *ring;
+  const DeepDesc *ddesc;   // [K], device
+  hipGraphExec_t *gexec;
+  int *graph_unroll;
+  hipStream_t *cap_stream;
+  Throttle *throttle;
+  bool timing;
+  hipEvent_t *ev;
+  double *t_acc, *t_empty;
+  int64_t *t_n, *n_eager, *n_graph;
+};
+
+static int deep_push(const DeepRun &r, const DevArgs *a, int64_t done, int64_t n, hipStream_t st) {
+  DeepRing &R = *r.ring;
+  const int K = r.K, slot = R.head;
+  R.head = (slot + 1) % DeepRing::RING;
+  if (!R.host[slot]) {
+    HIP_TRY(hipHostMalloc((void **)&R.host[slot], R.bytes(DeepRing::CAP), hipHostMallocDefault));
+    HIP_TRY(hipEventCreateWithFlags(&R.ev[slot], hipEventDisableTiming));
+  }
+  if (R.used[slot]) HIP_TRY(hipEventSynchronize(R.ev[slot]));
+  DeepArgs *ha = reinterpret_cast<DeepArgs *>(R.host[slot]);
+  DeepCtr *hc = reinterpret_cast<DeepCtr *>(R.host[slot] + (size_t)K * sizeof(DeepArgs));
+  AdamCoef *hk = reinterpret_cast<AdamCoef *>(R.host[slot] + R.head_bytes());
+  for (int k = 0; k < K; ++k) {
+    const iqlhip_trainer_config &c = r.tr[k]->cfg;
+    const int64_t B = c.batch_size, H = c.hidden_dim, NH = n_hidden(c);
+    DeepArgs &x = ha[k];
+    memset(&x, 0, sizeof(x));
+    x.rows = a[k].rows, x.n_rows = a[k].n_rows, x.row_stride = a[k].row_stride, x.idx_mode = a[k].idx_mode;
+    x.idx = a[k].idx ? a[k].idx + done * B : nullptr;
+    x.drop_keep = a[k].drop_keep ? a[k].drop_keep + done * NH * B * H : nullptr;
+    x.losses_out = a[k].losses_out ? a[k].losses_out + done * 3 : nullptr;
+    x.base_step = a[k].base_step + done, x.n_steps = n;
+    hc[k].ctr[0] = hc[k].ctr[1] = x.base_step;
+    for (int64_t i = 0; i < n; ++i)
+      hk[i * K + k] = make_adam_coef(c.adam_beta1, c.adam_beta2, c.adam_eps, a[k].lr_q, a[k].lr_v, a[k].lr_a_base,
+                                     c.cosine_t_max, x.base_step + i + 1);
+  }
+  HIP_TRY(hipMemcpyAsync(R.dev, R.host[slot], R.bytes(n), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipEventRecord(R.ev[slot], st));
+  R.used[slot] = true;
+  return 0;
+}
+
+static int deep_run(const DeepRun &r, const DevArgs *a, int64_t n_steps, int graph_unroll, hipStream_t st) {
+  const DeepTrainer *t0 = r.tr[0]->deep;
+  const DeepArgs *dA = r.ring->dargs();
+  DeepCtr *dC = r.ring->dctr();
+  const int U = r.timing ? 0 : (int)std::min<int64_t>(std::max(graph_unroll, 0), DeepRing::CAP);
+  const int64_t cap = U > 0 ? DeepRing::CAP / U * U : DeepRing::CAP;
+  for (int64_t done = 0; done < n_steps;) {
+    const int64_t n = std::min(cap, n_steps - done);
+    if (int rc = deep_push(r, a, done, n, st)) return rc;
+    int64_t i = 0;
+    if (U > 0 && n >= U) {
+      if (!*r.gexec || *r.graph_unroll != U) {
+        if (*r.gexec) {
+          (void)hipGraphExecDestroy(*r.gexec);
+          *r.gexec = nullptr;
+        }
+        hipGraph_t g = nullptr;
+        if (!*r.cap_stream) HIP_TRY(capture_stream(r.cap_stream));
+        HIP_TRY(hipStreamBeginCapture(*r.cap_stream, hipStreamCaptureModeThreadLocal));
+        hipError_t le = hipSuccess;
+        for (int u = 0; u < U && le == hipSuccess; ++u)
+          le = deep_step(t0, r.ddesc, dA, dC, r.ring->dcoef(), r.K, *r.cap_stream, nullptr);
+        hipError_t ce = hipStreamEndCapture(*r.cap_stream, &g);
+        if ((le != hipSuccess || ce != hipSuccess) && g) (void)hipGraphDestroy(g);
+        HIP_TRY(le);
+        HIP_TRY(ce);
+        HIP_TRY(hipGraphInstantiate(r.gexec, g, nullptr, nullptr, 0));
+        (void)hipGraphDestroy(g);
+        *r.graph_unroll = U;
       }
-      float ems = 0.f;
-      HIP_TRY(hipEventElapsedTime(&ems, t->ev[3], t->ev[4]));
-      t->t_empty += ems;
-      t->t_n++;
-    } else {
-      HIP_TRY(t->throttle.queued(3, st));
+      for (; i + U <= n; i += U) {
+        HIP_TRY(hipGraphLaunch(*r.gexec, st));
+        ++*r.n_graph;
+        HIP_TRY(r.throttle->queued(3 * (int64_t)U, st));
+      }
     }
+    for (; i < n; ++i) {
+      HIP_TRY(deep_step(t0, r.ddesc, dA, dC, r.ring->dcoef(), r.K, st, r.timing ? r.ev : nullptr));
+      ++*r.n_eager;
+      if (r.timing) {  // one event pair per kernel: serialises the stream a little; diagnostic mode only
+        HIP_TRY(hipEventRecord(r.ev[4], st));
+        HIP_TRY(hipEventSynchronize(r.ev[4]));
+        for (int k = 0; k < 3; ++k) {
+          float ms = 0.f;
+          HIP_TRY(hipEventElapsedTime(&ms, r.ev[k], r.ev[k + 1]));
+          r.t_acc[k] += ms;
+        }
+        float ems = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ems, r.ev[3], r.ev[4]));
+        *r.t_empty += ems;
+        ++*r.t_n;
+      } else {
+        HIP_TRY(r.throttle->queued(3, st));
+      }
+    }
+    done += n;
   }
   return 0;
 }
 
+static int run_steps_deep(iqlhip_trainer *t, const DevArgs &a, int64_t n_steps, int graph_unroll, hipStream_t st) {
+  iqlhip_trainer *tr[1] = {t};
+  const DeepRun r = {tr, 1, &t->deep_ring, deep_desc_dev(t->deep), &t->gexec, &t->graph_unroll,
+                     &t->cap_stream, &t->throttle, t->timing, t->ev, t->t_acc, &t->t_empty, &t->t_n, &t->n_eager,
+                     &t->n_graph};
+  return deep_run(r, &a, n_steps, graph_unroll, st);
+}
+
 static int run_steps(iqlhip_trainer *t, const DevArgs &args_in, int64_t n_steps, int graph_unroll,
                      hipStream_t st) {
-  if (t->deep) return run_steps_deep(t, args_in, n_steps, st);
+  if (t->deep) return run_steps_deep(t, args_in, n_steps, graph_unroll, st);
   if (t->group) group_invalidate(t->group);  // this call rewrites the member's slot of the group's arguments
   if (!(t->D.prefetch && t->dev_args_valid && !t->timing && continues(t->dev_args, args_in))) {
     HIP_TRY(push_args(t, args_in, n_steps, st));
@@ -969,6 +1103,7 @@ static int run_steps(iqlhip_trainer *t, const DevArgs &args_in, int64_t n_steps,
       HIP_TRY(hipEventElapsedTime(&ems, t->ev[3], t->ev[4]));
       t->t_empty += ems;
       t->t_n++;
+      t->n_eager++;
     }
     return 0;
   }
@@ -992,11 +1127,13 @@ static int run_steps(iqlhip_trainer *t, const DevArgs &args_in, int64_t n_steps,
     }
     for (; done + graph_unroll <= n_steps; done += graph_unroll) {
       HIP_TRY(hipGraphLaunch(t->gexec, st));
+      t->n_graph++;
       HIP_TRY(t->throttle.queued(3 * (int64_t)graph_unroll, st));
     }
   }
   for (; done < n_steps; ++done) {
     if (int rc = enqueue_step(t, st)) return rc;
+    t->n_eager++;
     HIP_TRY(t->throttle.queued(3, st));
   }
   return 0;
@@ -1079,6 +1216,13 @@ struct iqlhip_group {
   hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   double t_acc[3] = {0, 0, 0}, t_empty = 0;
   int64_t t_n = 0;
+  int64_t n_eager = 0, n_graph = 0;  // iqlhip_group_launch_counts
+  // a group of general-step trainers (iql_deep.hip): mem = [K] DeepDesc (the update table is member 0's: one
+  // shape, one table); the arguments, counters and Adam coefficients of all members live in `deep_ring`.  The members keep their own
+  // workspaces and argument blocks, so one stepped alone between group calls needs no hand-over.
+  bool deep = false;
+  DeepRing deep_ring;
+  DeepDesc *gdeep = nullptr;
 };
 
 static void group_invalidate(iqlhip_group *g) { g->dev_args_valid = false; }
@@ -1086,7 +1230,32 @@ static void group_invalidate(iqlhip_group *g) { g->dev_args_valid = false; }
 static bool same_shape(const iqlhip_trainer_config &a, const iqlhip_trainer_config &b) {
   return a.state_dim == b.state_dim && a.action_dim == b.action_dim && a.hidden_dim == b.hidden_dim &&
          a.batch_size == b.batch_size && a.deterministic == b.deterministic && a.precision == b.precision &&
-         n_critics(a) == n_critics(b) && (a.dropout_p > 0.f) == (b.dropout_p > 0.f);  // (polyak_form: per seed)
+         n_critics(a) == n_critics(b) && (a.dropout_p > 0.f) == (b.dropout_p > 0.f) &&  // (polyak_form: per seed)
+         n_hidden(a) == n_hidden(b);
+}
+
+static int deep_group_create(iqlhip_group **out, iqlhip_trainer *const *trainers, int32_t n) {
+  iqlhip_group *g = new (std::nothrow) iqlhip_group();
+  if (!g) return fail(IQLHIP_ERR_NOMEM, "host allocation failed");
+  g->K = n, g->deep = true;
+  hipError_t e = hipDeviceSynchronize();  // members may have steps in flight on other streams
+  if (e == hipSuccess) e = hipMalloc(&g->mem, sizeof(DeepDesc) * n);
+  if (e == hipSuccess) {
+    g->gdeep = reinterpret_cast<DeepDesc *>(g->mem);
+    e = g->deep_ring.init(n);
+  }
+  for (int k = 0; k < n && e == hipSuccess; ++k)
+    e = hipMemcpy(g->gdeep + k, &deep_desc(trainers[k]->deep), sizeof(DeepDesc), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    g->deep_ring.destroy();
+    if (g->mem) (void)hipFree(g->mem);
+    delete g;
+    return fail(e == hipErrorOutOfMemory ? IQLHIP_ERR_NOMEM : IQLHIP_ERR_HIP, "general-step group: %s",
+                hipGetErrorString(e));
+  }
+  for (int k = 0; k < n; ++k) g->tr[k] = trainers[k], trainers[k]->group = g;
+  *out = g;
+  return 0;
 }
 
 extern "C" int iqlhip_group_create(iqlhip_group **out, iqlhip_trainer *const *trainers, int32_t n) {
@@ -1094,16 +1263,17 @@ extern "C" int iqlhip_group_create(iqlhip_group **out, iqlhip_trainer *const *tr
   if (n < 1 || n > IQLHIP_MAX_GROUP) return fail(IQLHIP_ERR_INVALID, "group size %d: 1..%d", n, IQLHIP_MAX_GROUP);
   for (int k = 0; k < n; ++k) {
     if (!trainers[k]) return fail(IQLHIP_ERR_INVALID, "null trainer");
-    if (trainers[k]->deep)
-      return fail(IQLHIP_ERR_UNSUPPORTED, "seed groups run on the tuned step only (n_hidden = 2, hidden_dim 64 / 128 / "
-                  "256); step trainers of other shapes one by one");
+    if ((trainers[k]->deep != nullptr) != (trainers[0]->deep != nullptr))
+      return fail(IQLHIP_ERR_INVALID, "trainer %d: a group holds trainers of the tuned step (n_hidden = 2, hidden_dim "
+                  "64 / 128 / 256) or of the general step, not both", k);
     if (trainers[k]->group) return fail(IQLHIP_ERR_INVALID, "trainer %d already belongs to a group", k);
     for (int j = 0; j < k; ++j)
       if (trainers[j] == trainers[k]) return fail(IQLHIP_ERR_INVALID, "trainer %d listed twice", k);
     if (!same_shape(trainers[0]->cfg, trainers[k]->cfg) || trainers[k]->n_items != trainers[0]->n_items)
       return fail(IQLHIP_ERR_INVALID, "trainer %d differs in shape from trainer 0 (dims, batch, precision, "
-                  "critics, policy kind and dropout on/off must match)", k);
+                  "critics, hidden layers, policy kind and dropout on/off must match)", k);
   }
+  if (trainers[0]->deep) return deep_group_create(out, trainers, n);
   iqlhip_group *g = new (std::nothrow) iqlhip_group();
   if (!g) return fail(IQLHIP_ERR_NOMEM, "host allocation failed");
   g->K = n;
@@ -1177,7 +1347,8 @@ extern "C" int iqlhip_group_create(iqlhip_group **out, iqlhip_trainer *const *tr
 extern "C" int iqlhip_group_destroy(iqlhip_group *g) {
   if (!g) return 0;
   (void)hipDeviceSynchronize();
-  for (int k = 0; k < g->K; ++k) {
+  for (int k = 0; g->deep && k < g->K; ++k) g->tr[k]->group = nullptr;
+  for (int k = 0; !g->deep && k < g->K; ++k) {
     iqlhip_trainer *t = g->tr[k];
     (void)hipMemcpy(t->own_dctr, t->dctr, sizeof(DevCtr), hipMemcpyDeviceToDevice);
     t->ddesc = t->own_ddesc, t->dargs = t->own_dargs, t->dctr = t->own_dctr, t->ditems = t->own_ditems;
@@ -1199,6 +1370,7 @@ extern "C" int iqlhip_group_destroy(iqlhip_group *g) {
     if (g->harg_ev[k]) (void)hipEventDestroy(g->harg_ev[k]);
     if (g->harg[k]) (void)hipHostFree(g->harg[k]);
   }
+  g->deep_ring.destroy();
   if (g->mem) (void)hipFree(g->mem);
   delete g;
   return 0;
@@ -1231,6 +1403,26 @@ extern "C" int iqlhip_group_train_steps(iqlhip_group *g, const iqlhip_replay_vie
   }
   if (n_steps == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
+  if (g->deep) {
+    DevArgs a[IQLHIP_MAX_GROUP];
+    for (int k = 0; k < g->K; ++k) {
+      const iqlhip_trainer *t = g->tr[k];
+      memset(&a[k], 0, sizeof(DevArgs));
+      a[k].rows = views[k].rows, a[k].n_rows = views[k].n_rows, a[k].row_stride = views[k].row_stride;
+      a[k].idx = idx ? idx[k] : nullptr;
+      a[k].idx_mode = a[k].idx ? 1 : 0;
+      a[k].drop_keep = dropout_keep ? dropout_keep[k] : nullptr;
+      a[k].losses_out = losses_out ? losses_out[k] : nullptr;
+      a[k].base_step = t->total_it;
+      a[k].lr_q = t->lr_q, a[k].lr_v = t->lr_v, a[k].lr_a_base = t->lr_a_base;
+    }
+    const DeepRun r = {g->tr, g->K, &g->deep_ring, g->gdeep, &g->gexec, &g->graph_unroll,
+                       &g->cap_stream, &g->throttle, g->timing, g->ev, g->t_acc, &g->t_empty, &g->t_n, &g->n_eager,
+                       &g->n_graph};
+    if (int rc = deep_run(r, a, n_steps, graph_unroll, st)) return rc;
+    for (int k = 0; k < g->K; ++k) g->tr[k]->total_it += n_steps;
+    return 0;
+  }
   // ---- K DevArgs through one pinned slot, one copy (skipped when the call continues the last) ----
   DevArgs want[IQLHIP_MAX_GROUP];
   bool same = g->tr[0]->D.prefetch && g->dev_args_valid && !g->timing, all_philox = true;
@@ -1292,6 +1484,7 @@ extern "C" int iqlhip_group_train_steps(iqlhip_group *g, const iqlhip_replay_vie
       HIP_TRY(hipEventElapsedTime(&ems, g->ev[3], g->ev[4]));
       g->t_empty += ems;
       g->t_n++;
+      g->n_eager++;
     }
     for (int k = 0; k < g->K; ++k) g->tr[k]->total_it += n_steps;
     return 0;
@@ -1316,11 +1509,13 @@ extern "C" int iqlhip_group_train_steps(iqlhip_group *g, const iqlhip_replay_vie
     }
     for (; done + graph_unroll <= n_steps; done += graph_unroll) {
       HIP_TRY(hipGraphLaunch(g->gexec, st));
+      g->n_graph++;
       HIP_TRY(g->throttle.queued(3 * (int64_t)graph_unroll, st));
     }
   }
   for (; done < n_steps; ++done) {
     if (int rc = group_enqueue_step(g, st)) return rc;
+    g->n_eager++;
     HIP_TRY(g->throttle.queued(3, st));
   }
   for (int k = 0; k < g->K; ++k) g->tr[k]->total_it += n_steps;
@@ -1335,6 +1530,20 @@ extern "C" int iqlhip_group_set_timing(iqlhip_group *g, int32_t enable) {
   if (g->timing)
     for (auto &e : g->ev)
       if (!e) HIP_TRY(hipEventCreate(&e));
+  return 0;
+}
+
+extern "C" int iqlhip_trainer_launch_counts(iqlhip_trainer *t, int64_t *eager_steps, int64_t *graph_launches) {
+  if (!t) return fail(IQLHIP_ERR_INVALID, "null trainer");
+  if (eager_steps) *eager_steps = t->n_eager;
+  if (graph_launches) *graph_launches = t->n_graph;
+  return 0;
+}
+
+extern "C" int iqlhip_group_launch_counts(iqlhip_group *g, int64_t *eager_steps, int64_t *graph_launches) {
+  if (!g) return fail(IQLHIP_ERR_INVALID, "null group");
+  if (eager_steps) *eager_steps = g->n_eager;
+  if (graph_launches) *graph_launches = g->n_graph;
   return 0;
 }
 

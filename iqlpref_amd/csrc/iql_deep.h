@@ -63,22 +63,46 @@ struct DeepDesc {
   DeepNet net[MAX_TRAIN];
 };
 
-// What one step needs from the host (passed by value: the general step runs as plain launches).
-struct DeepStep {
+// What a call (or a chunk of one) needs from the host: written to device memory ahead of its first
+// step and read-only for the kernels during the launches.  The same three launches with the same
+// kernel arguments then run step t, t + 1, ...: what hipGraph capture and group launches need.
+// (DeepArgs and DeepCtr fill whole 128-byte lines: the counter's line is written while a launch runs, the
+// arguments' and the coefficients' lines are only read)
+struct alignas(128) DeepArgs {
   const float *rows;  // replay view
   int64_t n_rows;
   int32_t row_stride;
   int32_t idx_mode;          // 0 philox, 1 injected, 2 identity
+  const int64_t *idx;        // [n_steps][B] when idx_mode == 1
+  const uint8_t *drop_keep;  // [n_steps][n_hidden][B][H] or null (philox masks)
+  float *losses_out;         // [n_steps][3] or null
+  int64_t base_step;         // total_it before the first of these steps
+  int64_t n_steps;
+};
+// The Adam coefficients are computed by the host in double (make_adam_coef) and travel with DeepArgs as a
+// table, a kernel argument of kd_update: those of step base_step + i of member k of K at [i * K + k].
+
+// Device-side step counter of one trainer.  The host sets it to base_step together with DeepArgs.
+struct alignas(128) DeepCtr {
+  int64_t ctr[2];  // [0] steps completed (read by kd_forward / kd_backward; advanced by kd_update's misc block)
+                   // [1] the step in flight (written by kd_backward, read by kd_update)
+};
+
+// One step as the kernels see it: the slices of DeepArgs that belong to step `step` (deep_step_of).
+struct DeepStep {
+  const float *rows;
+  int64_t n_rows;
+  int32_t row_stride;
+  int32_t idx_mode;
   const int64_t *idx;        // [B] of THIS step when idx_mode == 1
-  const uint8_t *drop_keep;  // [n_hidden][B][H] of THIS step, or null (philox masks)
+  const uint8_t *drop_keep;  // [n_hidden][B][H] of THIS step, or null
   float *losses_out;         // [3] of THIS step, or null
   int64_t step;              // total_it before this step
-  AdamCoef coef;
 };
 
 // One tile of the update kernel.
 struct DeepItem {
-  int32_t net, layer;  // net < 0: the misc block (losses, log_std)
+  int32_t net, layer;  // net < 0: the misc block (losses, log_std, the step counter)
   int32_t o0, i0;      // tile origin (out-features, in-features), 64 x 64
 };
 

@@ -1,7 +1,10 @@
 // General layer-wise IQL step for MI355X (gfx950): the shapes the tuned three-Linear step
 // (iql_step.hip) is not built for -- n_hidden = 1..6 hidden layers of any width 1..1024
 // (ref:417-449 MLP, :452-543 the networks; ref:581-662 the step).  Same arithmetic (step_math.h),
-// same arenas, same index / dropout streams; three plain launches per step:
+// same arenas, same index / dropout streams; three launches per step, for one trainer or for the K
+// members of a group (grid dimension z; y for kd_update, whose x walks the tile table).  What changes from step to
+// step sits in device memory (DeepArgs + DeepCtr + a table of host-computed Adam coefficients), so the
+// same launches with the same kernel arguments run step t, t + 1, ...: plain or replayed from a hipGraph.
 //
 //   kd_forward   (2E+3 evaluations) x B/16 slabs, four or eight waves each: the slab's 16 transitions gathered
 //                from the packed replay rows, then every Linear on MFMA -- A fragments from a
@@ -21,6 +24,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cassert>
 #include <cstring>
 #include <new>
 #include <vector>
@@ -227,15 +231,39 @@ __device__ __forceinline__ int64_t deep_row_index(const DeepDesc &D, const DeepS
   return ix < 0 ? 0 : (ix >= A.n_rows ? A.n_rows - 1 : ix);
 }
 
+// Step `step` of the call DeepArgs describes: its slices of idx[] / drop_keep[] / losses_out[].  The offset
+// is clamped to the call's steps, so a counter the host did not set can never index outside the arrays; the
+// diagnostic build (IQL_STAMPS: python -m iqlpref_amd.build --stamps) asserts on it instead of repeating the
+// last step's slices without a sign.
+__device__ __forceinline__ int64_t deep_step_off(const DeepArgs &G, int64_t step) {
+  const int64_t i = step - G.base_step, last = G.n_steps - 1;
+#ifdef IQL_STAMPS
+  assert(i >= 0 && i <= last);
+#endif
+  return i < 0 ? 0 : (i > last ? last : i);
+}
+__device__ __forceinline__ DeepStep deep_step_of(const DeepDesc &D, const DeepArgs &G, int64_t step) {
+  const int64_t i = deep_step_off(G, step);
+  DeepStep s;
+  s.rows = G.rows, s.n_rows = G.n_rows, s.row_stride = G.row_stride, s.idx_mode = G.idx_mode;
+  s.idx = G.idx ? G.idx + i * D.B : nullptr;
+  s.drop_keep = G.drop_keep ? G.drop_keep + i * (int64_t)(D.NL - 1) * D.B * D.H : nullptr;
+  s.losses_out = G.losses_out ? G.losses_out + i * 3 : nullptr;
+  s.step = step;
+  return s;
+}
+
 // ------------------------------------------------------------------------
-// kd_forward: grid (B/16, 2E+3), four waves.
+// kd_forward: grid (B/16, 2E+3, members), four or eight waves.
 // ------------------------------------------------------------------------
 template <bool BF16, int THREADS>
-__global__ __launch_bounds__(THREADS) void kd_forward(const DeepDesc *__restrict__ Dp, const DeepStep A) {
+__global__ __launch_bounds__(THREADS) void kd_forward(const DeepDesc *__restrict__ Dp, const DeepArgs *__restrict__ Gp,
+                                                      const DeepCtr *__restrict__ Cp) {
   using P = Prec<BF16>;
   using T = typename P::T;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const DeepDesc &D = *Dp;
+  const DeepDesc &D = Dp[blockIdx.z];
+  const DeepStep A = deep_step_of(D, Gp[blockIdx.z], Cp[blockIdx.z].ctr[0]);
   const DeepEval &N = D.ev[blockIdx.y];
   const int row0 = blockIdx.x * 16, q = (threadIdx.x & 63) >> 4, ldw = D.lds_w, BP = D.BP;
   T *bufA = reinterpret_cast<T *>(smem), *bufB = bufA + (size_t)16 * ldw;
@@ -313,14 +341,19 @@ __global__ __launch_bounds__(256) void kd_infer(const DeepDesc *__restrict__ Dp,
 }
 
 // ------------------------------------------------------------------------
-// kd_backward: grid (B/16, E+2), four waves (the loss terms by the first, the layer walk by all).
+// kd_backward: grid (B/16, E+2, members), four or eight waves (the loss terms by the first, the layer walk by all).
 // ------------------------------------------------------------------------
 template <bool BF16, int THREADS>
-__global__ __launch_bounds__(THREADS) void kd_backward(const DeepDesc *__restrict__ Dp, const DeepStep A) {
+__global__ __launch_bounds__(THREADS) void kd_backward(const DeepDesc *__restrict__ Dp, const DeepArgs *__restrict__ Gp,
+                                                       DeepCtr *__restrict__ Cp) {
   using P = Prec<BF16>;
   using T = typename P::T;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const DeepDesc &D = *Dp;
+  const DeepDesc &D = Dp[blockIdx.z];
+  const int64_t step = Cp[blockIdx.z].ctr[0];
+  const DeepStep A = deep_step_of(D, Gp[blockIdx.z], step);
+  // the step in flight, for kd_update (whose misc block advances ctr[0] while its tiles still run)
+  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) Cp[blockIdx.z].ctr[1] = step;
   const int net = blockIdx.y, slab = blockIdx.x, row0 = slab * 16;
   const DeepNet &N = D.net[net];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r16 = lane & 15, q = lane >> 4;
@@ -411,7 +444,9 @@ __global__ __launch_bounds__(THREADS) void kd_backward(const DeepDesc *__restric
 }
 
 // ------------------------------------------------------------------------
-// kd_update: one work-group (4 waves) per 64 x 64 tile of a weight matrix.
+// kd_update: one work-group (4 waves) per tile of a weight matrix; grid (tiles, members) -- the members of a
+// group share one shape, hence one tile table, and consecutive work-groups (consecutive tiles of one member)
+// go to consecutive XCDs: every member's tiles spread over all eight.
 // ------------------------------------------------------------------------
 // sum of n floats `stride` apart, added in index order; eight loads are in flight at a time (a rolled
 // load-add loop is one memory round trip per element: 16 slabs were 11 us of the update launch)
@@ -428,20 +463,23 @@ __device__ __forceinline__ float ordered_sum(const float *p, int stride, int n) 
 }
 
 template <bool BF16>
-__device__ __forceinline__ void deep_misc(const DeepDesc &D, const DeepStep &A) {
+__device__ __forceinline__ void deep_misc(const DeepDesc &D, const DeepArgs &G, DeepCtr *C, int64_t step, int64_t off,
+                                          const AdamCoef &coef) {
   __shared__ float lm[MAX_TRAIN];
   const int tid = threadIdx.x, nslab = D.nslab;
   if (tid < D.ntrain) {
     lm[tid] = ordered_sum(D.lossp + (size_t)tid * nslab, 1, nslab) / (float)D.B;
   }
   __syncthreads();
-  if (tid == 0 && A.losses_out) {
+  if (tid == 0 && G.losses_out) {
+    float *lo = G.losses_out + off * 3;
     float ql = 0.f;
     for (int e = 0; e < D.E; ++e) ql += lm[e];  // q_loss = sum(mse) / E (ref:606)
-    stg(A.losses_out + 0, lm[D.net_v]);
-    stg(A.losses_out + 1, ql / (float)D.E);
-    stg(A.losses_out + 2, lm[D.net_a]);
+    stg(lo + 0, lm[D.net_v]);
+    stg(lo + 1, ql / (float)D.E);
+    stg(lo + 2, lm[D.net_a]);
   }
+  if (tid == 0) C->ctr[0] = step + 1;  // the step is finished once this launch is (nothing in it reads ctr[0])
   if (!D.deterministic && tid < D.A) {  // log_std (ref:452-474): std = exp(clamp(log_std))
     const float gs = ordered_sum(D.lsp + tid, D.A, nslab);
     const int64_t o = D.off_log_std + tid;
@@ -450,7 +488,7 @@ __device__ __forceinline__ void deep_misc(const DeepDesc &D, const DeepStep &A) 
     const float sd = expf(fminf(fmaxf(p, -20.f), 2.f));
     const float g = inside ? gs * sd : 0.f;
     if (D.grads) stg(D.grads + o, g);
-    adam_apply<BF16>(p, m, v, g, A.coef, A.coef.neg_step[2]);
+    adam_apply<BF16>(p, m, v, g, coef, coef.neg_step[2]);
     stg(D.params + o, p), stg(D.exp_avg + o, m), stg(D.exp_avg_sq + o, v);
   }
 }
@@ -463,13 +501,25 @@ __device__ __forceinline__ void deep_misc(const DeepDesc &D, const DeepStep &A) 
 // against 46.6), provided such tiles still make ~150 work-groups (deep_create).
 template <bool BF16, int DEEP_TQ>
 __global__ __launch_bounds__(256) void kd_update(const DeepDesc *__restrict__ Dp, const DeepItem *__restrict__ items,
-                                                 const DeepStep A) {
+                                                 const DeepArgs *__restrict__ Gp, DeepCtr *__restrict__ Cp,
+                                                 const AdamCoef *__restrict__ coefs) {
   using P = Prec<BF16>;
   using T = typename P::T;
-  const DeepDesc &D = *Dp;
+  // (everything below hangs on the member, a launch coordinate, not on the item: the descriptor, the argument
+  // block, the counter and the tile are requested together)
+  const int member = blockIdx.y;
   const DeepItem it = items[blockIdx.x];
+  const DeepDesc &D = Dp[member];
+  const DeepArgs &G = Gp[member];
+  const int64_t step = Cp[member].ctr[1], off = deep_step_off(G, step);
+  const AdamCoef *const coefp = coefs + off * (int64_t)gridDim.y + member;
+  // (field by field: a runtime index into a private copy of the struct would put the copy into LDS)
+  AdamCoef coef;
+  coef.one_m_b1 = coefp->one_m_b1, coef.b2 = coefp->b2, coef.one_m_b2 = coefp->one_m_b2;
+  coef.neg_step[0] = coef.neg_step[1] = 0.f, coef.neg_step[2] = coefp->neg_step[2];
+  coef.bc2_sqrt = coefp->bc2_sqrt, coef.eps = coefp->eps, coef.inv_bc2_sqrt = coefp->inv_bc2_sqrt, coef.pad_ = 0.f;
   if (it.net < 0) {
-    deep_misc<BF16>(D, A);
+    deep_misc<BF16>(D, G, Cp + member, step, off, coef);
     return;
   }
   // Two orientations of the same tile.  Rows of the [out][in] tensors that start on 16-byte boundaries
@@ -527,7 +577,7 @@ __global__ __launch_bounds__(256) void kd_update(const DeepDesc *__restrict__ Dp
   // (descriptor fields the epilogue needs, read once into registers: behind its first global store the compiler
   // must assume the descriptors changed and fetched D.params, N.has_target, ... again before EVERY access -- a
   // chain of scalar-load round trips that was half of this launch)
-  const float neg_step = A.coef.neg_step[N.group];
+  const float neg_step = coefp->neg_step[N.group];
   T *const wc = reinterpret_cast<T *>(N.wc[l]), *const wt = reinterpret_cast<T *>(N.wt[l]), *const tc = reinterpret_cast<T *>(N.tc[l]);
   const int64_t off_w = N.off_w[l], toff_w = N.toff_w[l], off_b = N.off_b[l], toff_b = N.toff_b[l];
   float *const Pp = D.params, *const Pm = D.exp_avg, *const Pv = D.exp_avg_sq, *const Pt = D.target, *const Pg = D.grads;
@@ -536,7 +586,6 @@ __global__ __launch_bounds__(256) void kd_update(const DeepDesc *__restrict__ Dp
     float tau, one_m_tau;
     int polyak_convex;
   } PK = {D.tau, D.one_m_tau, D.polyak_convex};
-  const AdamCoef coef = A.coef;
   if (vec) {
     const int k0 = it.i0 + 16 * wave + 4 * q;  // (k0 + 3 < Kn whenever k0 < Kn: both are multiples of 4)
 #pragma unroll
@@ -845,43 +894,53 @@ hipError_t deep_sync_weights(DeepTrainer *t, hipStream_t st) {
   return hipGetLastError();
 }
 
-// One step: three launches; ev (optional, 4 events) brackets them for the per-kernel timing.
+const DeepDesc &deep_desc(const DeepTrainer *t) { return t->D; }
+const DeepDesc *deep_desc_dev(const DeepTrainer *t) { return t->dD; }
+
+// Four or eight waves per slab (see tile ownership above); a work-group's arithmetic does not depend on it:
+// every 16 x 16 output tile is one wave's MFMA chain over the same k-steps in the same order either way, so
+// a group launch may pick by ITS work-group count and still give every member the bits of a solo run.
 static int deep_threads(const DeepDesc &D, int n_wgs) { return D.Hp >= 256 && n_wgs <= 256 ? 512 : 256; }
 
-hipError_t deep_step(DeepTrainer *t, const DeepStep &a, hipStream_t st, hipEvent_t *ev) {
+// One step of K trainers of t's shape (their update tile table is t's): three launches; dD / dA / dC are [K]
+// arrays in device memory, coefs the [steps][K] coefficient table; ev (optional, 4 events) brackets the
+// launches for the per-kernel timing.
+hipError_t deep_step(const DeepTrainer *t, const DeepDesc *dD, const DeepArgs *dA, DeepCtr *dC, const AdamCoef *coefs,
+                     int K, hipStream_t st, hipEvent_t *ev) {
   const DeepDesc &D = t->D;
-  const dim3 gf(D.nslab, D.nfwd), gb(D.nslab, D.ntrain), gu(t->n_items);
-  const int tf = deep_threads(D, D.nslab * D.nfwd), tb = deep_threads(D, D.nslab * D.ntrain);
+  const DeepItem *items = t->ditems;
+  const dim3 gf(D.nslab, D.nfwd, K), gb(D.nslab, D.ntrain, K), gu(t->n_items, K);
+  const int tf = deep_threads(D, D.nslab * D.nfwd * K), tb = deep_threads(D, D.nslab * D.ntrain * K);
   hipError_t e;
 #define DEEP_EV(k) \
   if (ev && (e = hipEventRecord(ev[k], st)) != hipSuccess) return e;
   DEEP_EV(0);
   if (t->bf16 && tf == 512)
-    hipLaunchKernelGGL((kd_forward<true, 512>), gf, dim3(512), t->lds_bytes, st, t->dD, a);
+    hipLaunchKernelGGL((kd_forward<true, 512>), gf, dim3(512), t->lds_bytes, st, dD, dA, dC);
   else if (t->bf16)
-    hipLaunchKernelGGL((kd_forward<true, 256>), gf, dim3(256), t->lds_bytes, st, t->dD, a);
+    hipLaunchKernelGGL((kd_forward<true, 256>), gf, dim3(256), t->lds_bytes, st, dD, dA, dC);
   else if (tf == 512)
-    hipLaunchKernelGGL((kd_forward<false, 512>), gf, dim3(512), t->lds_bytes, st, t->dD, a);
+    hipLaunchKernelGGL((kd_forward<false, 512>), gf, dim3(512), t->lds_bytes, st, dD, dA, dC);
   else
-    hipLaunchKernelGGL((kd_forward<false, 256>), gf, dim3(256), t->lds_bytes, st, t->dD, a);
+    hipLaunchKernelGGL((kd_forward<false, 256>), gf, dim3(256), t->lds_bytes, st, dD, dA, dC);
   DEEP_EV(1);
   if (t->bf16 && tb == 512)
-    hipLaunchKernelGGL((kd_backward<true, 512>), gb, dim3(512), t->lds_bytes, st, t->dD, a);
+    hipLaunchKernelGGL((kd_backward<true, 512>), gb, dim3(512), t->lds_bytes, st, dD, dA, dC);
   else if (t->bf16)
-    hipLaunchKernelGGL((kd_backward<true, 256>), gb, dim3(256), t->lds_bytes, st, t->dD, a);
+    hipLaunchKernelGGL((kd_backward<true, 256>), gb, dim3(256), t->lds_bytes, st, dD, dA, dC);
   else if (tb == 512)
-    hipLaunchKernelGGL((kd_backward<false, 512>), gb, dim3(512), t->lds_bytes, st, t->dD, a);
+    hipLaunchKernelGGL((kd_backward<false, 512>), gb, dim3(512), t->lds_bytes, st, dD, dA, dC);
   else
-    hipLaunchKernelGGL((kd_backward<false, 256>), gb, dim3(256), t->lds_bytes, st, t->dD, a);
+    hipLaunchKernelGGL((kd_backward<false, 256>), gb, dim3(256), t->lds_bytes, st, dD, dA, dC);
   DEEP_EV(2);
   if (t->bf16 && t->tq == 1)
-    hipLaunchKernelGGL((kd_update<true, 1>), gu, dim3(256), 0, st, t->dD, t->ditems, a);
+    hipLaunchKernelGGL((kd_update<true, 1>), gu, dim3(256), 0, st, dD, items, dA, dC, coefs);
   else if (t->bf16)
-    hipLaunchKernelGGL((kd_update<true, 4>), gu, dim3(256), 0, st, t->dD, t->ditems, a);
+    hipLaunchKernelGGL((kd_update<true, 4>), gu, dim3(256), 0, st, dD, items, dA, dC, coefs);
   else if (t->tq == 1)
-    hipLaunchKernelGGL((kd_update<false, 1>), gu, dim3(256), 0, st, t->dD, t->ditems, a);
+    hipLaunchKernelGGL((kd_update<false, 1>), gu, dim3(256), 0, st, dD, items, dA, dC, coefs);
   else
-    hipLaunchKernelGGL((kd_update<false, 4>), gu, dim3(256), 0, st, t->dD, t->ditems, a);
+    hipLaunchKernelGGL((kd_update<false, 4>), gu, dim3(256), 0, st, dD, items, dA, dC, coefs);
   DEEP_EV(3);
 #undef DEEP_EV
   return hipGetLastError();

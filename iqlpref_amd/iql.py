@@ -72,6 +72,11 @@ class TrainConfig:
     # not in the reference: number of critics (2 = the reference's TwinQ; 3..8 = E-way critic
     # ensemble of BASELINE config 5, see EnsembleQ)
     n_critics: int = 2
+    # not in the reference's config either (its MLPs take them as constructor arguments, ref:458-459, 519,
+    # 538): width and number of the hidden layers of every network.  Anything but 2 x 64 / 128 / 256 trains
+    # on the general layer-wise step (ImplicitQLearning.step_kind)
+    hidden_dim: int = 256
+    n_hidden: int = 2
     seed: int = 0
     device: str = "cuda"
 
@@ -717,6 +722,26 @@ class ImplicitQLearning:
         self.actor_optimizer.param_groups[0]["lr"] = lr
         self._bind_optimizer_state()
 
+    def launch_counts(self):
+        """(steps issued as plain launches, hipGraph replays issued) by this trainer's own calls since its
+        device handle was created; (0, 0) before the first step."""
+        if self._handle is None:
+            return (0, 0)
+        eager, graphs = C.c_int64(), C.c_int64()
+        check(self._lib.iqlhip_trainer_launch_counts(self._handle, C.byref(eager), C.byref(graphs)))
+        return (int(eager.value), int(graphs.value))
+
+    def _check_keep(self, keep: torch.Tensor, n_steps: int, batch_size: int) -> torch.Tensor:
+        """An injected dropout mask as the kernels index it: uint8 [n_steps, n_hidden, batch, hidden]
+        (a mask built for another depth or width would be read out of bounds on the device)."""
+        want = (n_steps, self._n_hidden, batch_size, self._hidden)
+        if tuple(keep.shape) != want:
+            raise ValueError(f"dropout_keep must have shape {want} (n_steps, n_hidden, batch_size, hidden_dim), "
+                             f"got {tuple(keep.shape)}")
+        if keep.device.type != "cuda":
+            raise ValueError("dropout_keep must be a device tensor")
+        return keep.to(torch.uint8).contiguous()
+
     def _refresh_lrs(self):
         lrs = (self._handle.value, float(self.q_optimizer.param_groups[0]["lr"]),
                float(self.v_optimizer.param_groups[0]["lr"]), float(self.actor_lr_schedule.base_lrs[0]))
@@ -732,6 +757,10 @@ class ImplicitQLearning:
             raise RuntimeError("Actions shape missmatch")  # ref:627-628
         self._ensure_handle(s.shape[0])
         self._refresh_lrs()
+        if dropout_keep is not None:  # [n_hidden, batch, hidden], with or without a leading step axis of 1
+            if dropout_keep.dim() == 3:
+                dropout_keep = dropout_keep[None]
+            dropout_keep = self._check_keep(dropout_keep, 1, s.shape[0])
         losses = torch.empty(3, dtype=torch.float32, device=self._dev)
         with torch.cuda.device(self._dev):
             check(self._lib.iqlhip_train_batch(self._handle, ptr(s), ptr(a), ptr(r), ptr(s2), ptr(d),
@@ -757,7 +786,7 @@ class ImplicitQLearning:
                 raise ValueError("indices must be int64 [n_steps, batch_size]")
             indices = indices.contiguous()
         if dropout_keep is not None:
-            dropout_keep = dropout_keep.to(torch.uint8).contiguous()
+            dropout_keep = self._check_keep(dropout_keep, n_steps, batch_size)
         v = replay_buffer.view()
         unroll = self._graph_unroll if graph_unroll is None else graph_unroll
         if torch.cuda.current_device() == (self._dev.index or 0):  # (the context manager costs ~5 us a call)

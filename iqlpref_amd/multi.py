@@ -21,8 +21,14 @@ is bit-identical to running it alone.  Two execution modes:
     Measured (tools/group_streams.py, tools/group_scan.py): 2 / 4 / 8 / 16 seeds as two sub-groups
     107k / 160k / 202k / 250k steps/s against 93k / 130k / 171k / 204k as one group.  Two slices are the
     sweet spot (three do not divide the chip's 8 XCDs evenly, four leave each sub-group too few CUs).
+``mode="general"``
+    ``mode="group"`` for trainers that run on the general layer-wise step (``step_kind() ==
+    "general"``: n_hidden != 2 or a hidden_dim other than 64 / 128 / 256): ONE launch sequence for
+    up to ``MAX_GROUP`` such trainers of one shape, hipGraphs of ``graph_unroll`` steps.  Never
+    picked by default: general-step trainers default to ``"streams"``.
 """
 import ctypes as C
+import os
 from typing import List, Optional, Sequence, Union
 
 import torch
@@ -62,6 +68,28 @@ def _on_tuned_step(t: ImplicitQLearning) -> bool:
     return t._n_hidden == 2 and t._hidden in (64, 128, 256)
 
 
+GROUP_MODES = ("group", "split", "streams", "general")
+
+
+def check_group_mode(group_mode: Optional[str]) -> Optional[str]:
+    """The ``group_mode`` keyword of ``train()`` / ``sweep.train_runs()``: None (the SeedGroup default) or a
+    SeedGroup mode.  Host-only: callers validate before any device work."""
+    if group_mode is not None and group_mode not in GROUP_MODES:
+        raise ValueError(f"group_mode must be None or one of {', '.join(repr(m) for m in GROUP_MODES)} "
+                         f"(got {group_mode!r})")
+    return group_mode
+
+
+def resolve_group_mode(group_mode: Optional[str], trainers: Sequence[ImplicitQLearning], batch_size: int):
+    """The SeedGroup mode for these trainers under ``group_mode``.  "general" holds for trainers that run on
+    the general layer-wise step; asked for trainers of the tuned step (a grid may hold both kinds of batch)
+    it falls back to None, the SeedGroup default.  Every other value passes through."""
+    check_group_mode(group_mode)
+    if group_mode == "general" and not all(t.step_kind(batch_size) == "general" for t in trainers):
+        return None
+    return group_mode
+
+
 class SeedGroup:
     def __init__(self, trainers: Sequence[ImplicitQLearning], chunk: int = 2000, mode: Optional[str] = None,
                  n_streams: int = 2):
@@ -76,8 +104,13 @@ class SeedGroup:
             all(_on_tuned_step(t) for t in trainers)
         if mode is None:  # the fastest arrangement measured for the shape at hand
             mode = ("split" if len(trainers) >= 2 else "group") if one_shape else "streams"
-        if mode not in ("group", "streams", "split"):
-            raise ValueError("mode must be 'group', 'streams' or 'split'")
+        if mode not in ("group", "streams", "split", "general"):
+            raise ValueError("mode must be 'group', 'streams', 'split' or 'general'")
+        if mode == "general":
+            if len({_shape_key(t) for t in trainers}) != 1 or len(trainers) > _lib.MAX_GROUP:
+                raise ValueError(f"mode='general' needs at most {_lib.MAX_GROUP} trainers of one shape (dims, hidden, "
+                                 "n_hidden, precision, policy kind, critics, dropout on/off)")
+            self._check_general(trainers)
         if mode in ("group", "split") and not one_shape:
             raise ValueError(f"mode='group' needs at most {_lib.MAX_GROUP} trainers of one shape (dims, hidden, "
                              "precision, policy kind, critics, dropout on/off) that runs on the tuned step "
@@ -105,6 +138,21 @@ class SeedGroup:
     def __len__(self):
         return len(self.trainers)
 
+    @staticmethod
+    def _check_general(trainers, batch_size: Optional[int] = None):
+        """mode="general" is for members on the general layer-wise step.  Asked of the device handle where one
+        exists (IQLHIP_FORCE_GENERAL moves shapes over); without a handle the library's rule for the shape."""
+        def kind(t):
+            if batch_size is not None:
+                return t.step_kind(batch_size)
+            if t._handle is not None:
+                return t.step_kind(t._handle_batch)
+            return "tuned" if _on_tuned_step(t) and not os.environ.get("IQLHIP_FORCE_GENERAL") else "general"
+        tuned = [i for i, t in enumerate(trainers) if kind(t) != "general"]
+        if tuned:
+            raise ValueError(f"mode='general' is for trainers on the general layer-wise step; members {tuned} run "
+                             "on the tuned step (use mode='group' or 'split')")
+
     # -- group handle --------------------------------------------------------- #
     def _ensure_group(self, batch_size: int):
         if self._group is not None and self._group_batch == batch_size and \
@@ -113,6 +161,8 @@ class SeedGroup:
         self._drop_group()
         for t in self.trainers:
             t._ensure_handle(batch_size)
+        if self.mode == "general":
+            self._check_general(self.trainers, batch_size)
         arr = (C.c_void_p * len(self.trainers))(*[t._handle.value for t in self.trainers])
         g = C.c_void_p()
         with torch.cuda.device(self._dev):
@@ -173,7 +223,7 @@ class SeedGroup:
                 if t.dtype != torch.int64 or tuple(t.shape) != (n_steps, batch_size):
                     raise ValueError("indices must be int64 [n_steps, batch_size]")
                 idx[i] = t.contiguous()
-        keep = [None if k is None else k.to(torch.uint8).contiguous() for k in keep]
+        keep = [None if k is None else t._check_keep(k, n_steps, batch_size) for t, k in zip(self.trainers, keep)]
         losses = [torch.empty((n_steps, 3), dtype=torch.float32, device=self._dev) for _ in range(K)] \
             if return_losses else None
         views = (_lib.ReplayView * K)(*[b.view() for b in bufs])
@@ -253,8 +303,8 @@ class SeedGroup:
     def kernel_times(self, replay, batch_size: int, n_steps: int = 200):
         """Average duration (us) of the forward / backward / update launches of this group
         (mode "group"): ``n_steps`` eager steps with a HIP-event pair around every launch."""
-        if self.mode != "group":
-            raise ValueError("kernel_times needs mode='group'")
+        if self.mode not in ("group", "general"):
+            raise ValueError("kernel_times needs mode='group' or 'general'")
         self._ensure_group(batch_size)
         check(self._lib.iqlhip_group_set_timing(self._group, 1))
         try:
@@ -265,6 +315,17 @@ class SeedGroup:
             check(self._lib.iqlhip_group_set_timing(self._group, 0))
         return {"k_forward": avg[0] * 1e3, "k_backward": avg[1] * 1e3, "k_update": avg[2] * 1e3,
                 "launches": int(n.value)}
+
+    def launch_counts(self):
+        """(steps issued as plain launches, hipGraph replays issued) of this group's launch sequence since
+        its device-side group was created (modes "group" / "general"; a step of K members counts once)."""
+        if self.mode not in ("group", "general"):
+            raise ValueError("launch_counts needs mode='group' or 'general'")
+        if self._group is None:
+            return (0, 0)
+        eager, graphs = C.c_int64(), C.c_int64()
+        check(self._lib.iqlhip_group_launch_counts(self._group, C.byref(eager), C.byref(graphs)))
+        return (int(eager.value), int(graphs.value))
 
     def synchronize(self):
         for st in self._streams:

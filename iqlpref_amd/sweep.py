@@ -32,6 +32,7 @@ import torch
 from . import _lib
 from . import distributed as D
 from .iql import ImplicitQLearning, TrainConfig, load_config
+from .multi import GROUP_MODES
 
 # top-level keys of a sweep file that only name or describe it (kept as labels, otherwise ignored)
 LABEL_KEYS = ("program", "project", "name", "description", "metric", "command", "entity")
@@ -132,11 +133,12 @@ def expand_sweep(spec_or_path, *, config_root: str = ".", **overrides) -> List[T
 # --------------------------------------------------------------------------- #
 def shape_key(config: TrainConfig, dims, precision: str = "bf16") -> tuple:
     """What runs of one SeedGroup must share (iqlhip_group_create's same_shape): state / action dims,
-    batch size, policy kind, actor dropout on/off, critics, precision, device.  ``dims`` = (S, A), or
+    batch size, policy kind, actor dropout on/off, critics, precision, device, width and number of the
+    hidden layers.  ``dims`` = (S, A), or
     None when unknown (the env name stands in: runs of one env always share their dims)."""
     dims_key = tuple(int(d) for d in dims) if dims is not None else ("env", config.env)
     return (dims_key, int(config.batch_size), bool(config.iql_deterministic), bool(config.actor_dropout),
-            int(config.n_critics), precision, str(config.device))
+            int(config.n_critics), precision, str(config.device), int(config.hidden_dim), int(config.n_hidden))
 
 
 def _check_runs_per_gpu(runs_per_gpu: int) -> int:
@@ -253,9 +255,10 @@ def train_runs(configs: Sequence[TrainConfig], env=None, dataset=None, *, runs_p
     Adam moments and ``total_it``, bit for bit -- with the runs packed into seed groups.
 
     Launch batches (``plan_batches``): runs of one shape key (dims, batch size, policy kind, dropout
-    on/off, critics, precision, device), at most ``runs_per_gpu`` (1..16) in config order; the
+    on/off, critics, precision, device, hidden_dim, n_hidden), at most ``runs_per_gpu`` (1..16) in config order; the
     batches run one after another, each as one ``SeedGroup`` of mode ``group_mode`` (None: the
-    SeedGroup default).  Inside a batch everything else may differ: seed, reward normalisation,
+    SeedGroup default; "general": one launch sequence for batches whose shape runs on the general
+    layer-wise step, the default for the others).  Inside a batch everything else may differ: seed, reward normalisation,
     discount, tau, beta, iql_tau, learning rates, dropout rate, max_timesteps, log / eval
     frequencies, reward model, and the env when its dims match.  All runs of a batch start at step
     0; every library call runs to the next log / eval / end boundary of ANY active run; a finished
@@ -285,8 +288,8 @@ def train_runs(configs: Sequence[TrainConfig], env=None, dataset=None, *, runs_p
         raise ValueError("run_ids: one entry per config")
     if isinstance(evaluate, (list, tuple)) and len(evaluate) != n:
         raise ValueError(f"evaluate: {len(evaluate)} callables for {n} configs")
-    if group_mode not in (None, "group", "split", "streams"):
-        raise ValueError("group_mode must be None, 'group', 'split' or 'streams'")
+    from .multi import check_group_mode
+    check_group_mode(group_mode)
     rank, world = _rank_world()
     mine = rank_share(n, rank, world)
     if not mine:
@@ -361,7 +364,9 @@ def _run_batch(configs, batch, trainers, state, SeedGroup, group_mode, logger, e
 
     def make_group(members):
         trs = [trainers[i] for i in members]
-        return SeedGroup(trs) if group_mode is None else SeedGroup(trs, mode=group_mode)
+        from .multi import resolve_group_mode
+        mode = resolve_group_mode(group_mode, trs, configs[members[0]].batch_size)
+        return SeedGroup(trs) if mode is None else SeedGroup(trs, mode=mode)
 
     active = [i for i in batch if int(configs[i].max_timesteps) > 0]
     group = make_group(active) if active else None
@@ -416,6 +421,15 @@ def _run_batch(configs, batch, trainers, state, SeedGroup, group_mode, logger, e
 # --------------------------------------------------------------------------- #
 # command line
 # --------------------------------------------------------------------------- #
+def planned_mode(config: TrainConfig, group_mode: Optional[str]) -> str:
+    """What ``--list`` prints for a run's batch: the SeedGroup mode ``group_mode`` resolves to for this
+    shape, told from the config alone (no device; the library's own rule, without IQLHIP_FORCE_GENERAL)."""
+    tuned = int(config.n_hidden) == 2 and int(config.hidden_dim) in (64, 128, 256)
+    if group_mode is None or (group_mode == "general" and tuned):
+        return "default"
+    return group_mode
+
+
 def _list_dims(env_name: str):
     fam = env_name.split("-")[0].lower()
     if fam in D4RL_DIMS:
@@ -435,6 +449,9 @@ def main(argv=None):
                     help="runs stepped together as one seed group (default: $AGENTS_PER_GPU, else 8)")
     ap.add_argument("--only", default=None, help="comma-separated run indices to train")
     ap.add_argument("--list", action="store_true", help="print every run's index, label and launch batch; no GPU")
+    ap.add_argument("--group_mode", default=None, choices=list(GROUP_MODES),
+                    help="SeedGroup mode of every launch batch (default: the SeedGroup default; 'general': one launch "
+                         "sequence for batches on the general layer-wise step)")
     args, rest = ap.parse_known_args(argv)
     configs = expand_sweep(args.sweep, config_root=args.config_root, **parse_overrides(rest))
     ids = list(range(len(configs)))
@@ -448,9 +465,10 @@ def main(argv=None):
         batches = plan_batches(chosen, [_list_dims(c.env) for c in chosen], args.runs_per_gpu)
         where = {j: b for b, members in enumerate(batches) for j in members}
         for j, i in enumerate(ids):
-            print(f"{i}\t{configs[i].sweep_label or '-'}\tbatch {where[j]}")
+            mode = "" if args.group_mode is None else f"\tmode {planned_mode(configs[i], args.group_mode)}"
+            print(f"{i}\t{configs[i].sweep_label or '-'}\tbatch {where[j]}{mode}")
         return
-    train_runs(chosen, runs_per_gpu=args.runs_per_gpu, run_ids=ids)
+    train_runs(chosen, runs_per_gpu=args.runs_per_gpu, run_ids=ids, group_mode=args.group_mode)
 
 
 if __name__ == "__main__":

@@ -197,13 +197,14 @@ def _prepare_replay(config: TrainConfig, dataset, state_dim, action_dim, host_pr
 def _build_trainer(config: TrainConfig, seed: int, state_dim, action_dim, max_action, precision) -> ImplicitQLearning:
     """ref:1467-1520 for one seed: seeded initial weights, three Adam optimisers, the trainer."""
     set_seed(seed, None)
+    hd, nh = int(config.hidden_dim), int(config.n_hidden)
     if config.n_critics == 2:
-        q_network = TwinQ(state_dim, action_dim).to(config.device)
+        q_network = TwinQ(state_dim, action_dim, hd, nh).to(config.device)
     else:
-        q_network = EnsembleQ(state_dim, action_dim, n_critics=config.n_critics).to(config.device)
-    v_network = ValueFunction(state_dim).to(config.device)
+        q_network = EnsembleQ(state_dim, action_dim, hd, nh, n_critics=config.n_critics).to(config.device)
+    v_network = ValueFunction(state_dim, hd, nh).to(config.device)
     pol = DeterministicPolicy if config.iql_deterministic else GaussianPolicy
-    actor = pol(state_dim, action_dim, max_action, dropout=config.actor_dropout).to(config.device)
+    actor = pol(state_dim, action_dim, max_action, hd, nh, dropout=config.actor_dropout).to(config.device)
     v_optimizer = torch.optim.Adam(v_network.parameters(), lr=config.vf_lr)
     q_optimizer = torch.optim.Adam(q_network.parameters(), lr=config.qf_lr)
     actor_optimizer = torch.optim.Adam(actor.parameters(), lr=config.actor_lr)
@@ -226,7 +227,8 @@ def train(config: TrainConfig, env=None, dataset=None, *, state_dim: Optional[in
           evaluate: Optional[Callable] = None, precision: str = "bf16",
           raw_dataset=None, host_prep: bool = False, seeds_per_gpu: int = 1,
           vector_env: Optional[Callable] = None,
-          index_stream: Optional[Callable[[int, int, int], torch.Tensor]] = None):
+          index_stream: Optional[Callable[[int, int, int], torch.Tensor]] = None,
+          group_mode: Optional[str] = None):
     """ref:1393-1570.  ``dataset``: an already-built qlearning dataset (skips d4rl);
     ``raw_dataset``: an env.get_dataset()-style dict handed to the relabel functions;
     ``evaluate(actor, step) -> (scores, steps_to_goal)`` replaces eval_actor when gym is
@@ -252,7 +254,12 @@ def train(config: TrainConfig, env=None, dataset=None, *, state_dim: Optional[in
     ``index_stream(slot, first_step, n) -> int64 [n, batch_size]`` (tests): the replay rows of steps
     ``first_step .. first_step + n - 1`` of seed slot ``slot`` instead of the on-device Philox
     stream -- how a run of the reference's own ``train()`` (whose sampler draws from torch's global
-    CPU generator, ref:212-214) is replayed step for step."""
+    CPU generator, ref:212-214) is replayed step for step.
+    ``group_mode``: the ``SeedGroup`` mode of the K seeds (None: its default).  "general" -- one launch
+    sequence for seeds on the general layer-wise step -- falls back to the default for a config of the
+    tuned step (``multi.resolve_group_mode``)."""
+    from .multi import check_group_mode, resolve_group_mode
+    check_group_mode(group_mode)
     # one process per GPU: under torchrun this rank owns cuda:<LOCAL_RANK>, and everything
     # below (process group, buffer, trainer, metric all-gather) lives there
     bound = D.local_device()
@@ -309,7 +316,7 @@ def train(config: TrainConfig, env=None, dataset=None, *, state_dim: Optional[in
     group = None
     if K > 1:
         from .multi import SeedGroup
-        group = SeedGroup(trainers)
+        group = SeedGroup(trainers, mode=resolve_group_mode(group_mode, trainers, config.batch_size))
 
     if logger is None:
         try:
@@ -397,8 +404,12 @@ def main(argv=None):
     ap.add_argument("--seeds_per_gpu", type=int, default=int(os.environ.get("AGENTS_PER_GPU", "1")),
                     help="independent seeds trained side by side on each GPU "
                          "(ensemble_sweeps/launch.sh:12 AGENTS_PER_GPU)")
+    from .multi import GROUP_MODES
+    ap.add_argument("--group_mode", default=None, choices=list(GROUP_MODES),
+                    help="SeedGroup mode of the --seeds_per_gpu seeds (default: the SeedGroup default)")
     args, rest = ap.parse_known_args(argv)
-    train(load_config(args.config_path, **parse_overrides(rest)), seeds_per_gpu=args.seeds_per_gpu)
+    train(load_config(args.config_path, **parse_overrides(rest)), seeds_per_gpu=args.seeds_per_gpu,
+          group_mode=args.group_mode)
 
 
 def parse_overrides(tokens: Sequence[str]) -> Dict[str, str]:
