@@ -458,6 +458,41 @@ int iqlhip_pt_relabel_general(const iqlhip_pt_model *m, const float *obs, const 
 int iqlhip_np_randint(uint32_t *state, const int64_t *hi, int32_t K, int32_t batch,
                       int64_t n_batches, int64_t *const *out, void *stream);
 
+/* ------------------------------------------------------------------------ */
+/* Posterior relabel of algorithms/custom_offline/iql_br.py:179-253: per       */
+/* transition, n_samps draws of np.random.choice over the S posterior          */
+/* predictions on numpy's legacy generator, reduced on the device              */
+/* (posterior_choice.hip)                                                      */
+/* ------------------------------------------------------------------------ */
+#define IQLHIP_CHOICE_MEAN 0
+#define IQLHIP_CHOICE_MEDIAN 1
+
+/* Device workspace (bytes) with which iqlhip_posterior_choice runs at its full chunk size: a ring of
+ * uint16 index chunks, O(chunk) -- it does not grow with N beyond one chunk.  Pure host code; the
+ * envelope checks are those of iqlhip_posterior_choice.                                         */
+int iqlhip_posterior_choice_workspace_bytes(int32_t S, int64_t N, int32_t n_samps, size_t *bytes);
+
+/* out[c] = mean or median over j < n_samps of preds[idx[c][j]][c], where idx is
+ * RandomState.randint(0, S, size=(N, n_samps)) continued from `state` -- what N consecutive
+ * np.random.choice(preds[:, c], n_samps) calls draw (iql_br.py:179-186).
+ * state: device uint32 [625] = key[624], pos (the layout of iqlhip_np_randint); read and advanced
+ * in place; afterwards pos sits one past the word that produced the last accepted value.
+ * preds: device fp32 [S][N] row-major (the layout iqlhip_cvar_tail_mean takes).
+ * mode: IQLHIP_CHOICE_MEAN (fp32 sum / n_samps; n_samps == 1 is the single posterior draw, exact)
+ * or IQLHIP_CHOICE_MEDIAN (numpy's: the middle value, or (a + b) * 0.5f of the two middle ones).
+ * out: device fp32 [N].  idx_out: device uint16 [N][n_samps] or NULL; it receives the drawn indices
+ * (tests pin the stream with it, production passes NULL: the indices then never exist in full).
+ * workspace: device, 16-byte aligned, workspace_bytes long.  One smaller than
+ * iqlhip_posterior_choice_workspace_bytes is used in smaller chunks; one that holds no 32-row
+ * chunk is IQLHIP_ERR_INVALID.  It stays in use until the work queued on `stream` has finished.
+ * Envelope, refused with IQLHIP_ERR_INVALID before anything is launched: 2 <= S <= 2400,
+ * 1 <= n_samps <= 1024, N >= 1, pos <= 624.  Synchronises `stream` once, before the first launch,
+ * to read and check pos.  The index draw runs on an internal stream, the reductions on `stream`;
+ * when the call returns, `stream` is ordered behind both.                                        */
+int iqlhip_posterior_choice(uint32_t *state, const float *preds, int32_t S, int64_t N, int32_t n_samps,
+                            int32_t mode, float *out, uint16_t *idx_out, void *workspace,
+                            size_t workspace_bytes, void *stream);
+
 /* Algorithmic traffic and work of one step for this configuration
  * (SURVEY.md section 8d): bytes = 4B(2S+A+2) + 32 P_train + 8 P_q.          */
 int iqlhip_step_cost(const iqlhip_trainer_config *cfg, double *bytes, double *flops);

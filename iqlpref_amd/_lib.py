@@ -20,6 +20,8 @@ MLP_MAX_LAYERS = 8
 MAX_GROUP = 16
 ACT_FLAX_BASE = 8  # iqlhip_mlp_desc activation code 8 + i = entry i of reward_models/q_mlp.py:121-130
 ABI_VERSION = 6
+CHOICE_MEAN = 0
+CHOICE_MEDIAN = 1
 
 ERR_INVALID = -1
 ERR_HIP = -2
@@ -141,6 +143,8 @@ SYMBOLS = {
     "iqlhip_pt_relabel_general": (C.c_int, [C.POINTER(PtModel), P, P, C.c_int64, P, P, P, C.c_int64, C.c_int32,
                                             P, C.c_size_t, P, P]),
     "iqlhip_np_randint": (C.c_int, [P, P, C.c_int32, C.c_int32, C.c_int64, P, P]),
+    "iqlhip_posterior_choice_workspace_bytes": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_size_t)]),
+    "iqlhip_posterior_choice": (C.c_int, [P, P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, P, P, P, C.c_size_t, P]),
     "iqlhip_step_cost": (C.c_int, [C.POINTER(TrainerConfig), C.POINTER(C.c_double),
                                    C.POINTER(C.c_double)]),
     "iqlhip_trainer_set_timing": (C.c_int, [P, C.c_int32]),

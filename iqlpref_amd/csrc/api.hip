@@ -79,6 +79,11 @@ hipError_t launch_pt_general(const iqlhip_pt_model &m, const float *obs, const f
                              int64_t n_win, int ql, float *ws, int64_t chunk, float *out, hipStream_t st);
 hipError_t launch_np_randint(uint32_t *state, const int64_t *hi, int K, int64_t total, int64_t *const *out,
                              hipStream_t st);
+size_t choice_workspace_bytes(int64_t N, int n);
+int64_t choice_fit_rows(int64_t N, int n, size_t bytes);
+hipError_t launch_posterior_choice(uint32_t *state, const float *preds, int S, int64_t N, int n, int mode,
+                                   float *out, uint16_t *idx_out, uint16_t *ws, int64_t slot_rows,
+                                   hipStream_t st);
 }  // namespace iqlhip
 
 using namespace iqlhip;
@@ -1681,6 +1686,43 @@ extern "C" int iqlhip_np_randint(uint32_t *state, const int64_t *hi, int32_t K, 
     if (pos[k] > 624) return fail(IQLHIP_ERR_INVALID, "state %d: pos = %u outside 0..624", k, pos[k]);
   if (n_batches == 0) return 0;
   HIP_TRY(launch_np_randint(state, hi, K, n_batches * (int64_t)batch, out, st));
+  return 0;
+}
+
+// ------------------------------------------------------- posterior choice --
+static int choice_check(int32_t S, int64_t N, int32_t n_samps) {
+  if (S < 2 || S > 2400) return fail(IQLHIP_ERR_INVALID, "S = %d outside 2..2400", S);
+  if (n_samps < 1 || n_samps > 1024) return fail(IQLHIP_ERR_INVALID, "n_samps = %d outside 1..1024", n_samps);
+  if (N < 1) return fail(IQLHIP_ERR_INVALID, "N = %lld must be >= 1", (long long)N);
+  return 0;
+}
+
+extern "C" int iqlhip_posterior_choice_workspace_bytes(int32_t S, int64_t N, int32_t n_samps, size_t *bytes) {
+  if (!bytes) return fail(IQLHIP_ERR_INVALID, "null argument");
+  if (int rc = choice_check(S, N, n_samps)) return rc;
+  *bytes = choice_workspace_bytes(N, n_samps);
+  return 0;
+}
+
+extern "C" int iqlhip_posterior_choice(uint32_t *state, const float *preds, int32_t S, int64_t N, int32_t n_samps,
+                                       int32_t mode, float *out, uint16_t *idx_out, void *workspace,
+                                       size_t workspace_bytes, void *stream) {
+  if (!state || !preds || !out || !workspace) return fail(IQLHIP_ERR_INVALID, "null argument");
+  if (int rc = choice_check(S, N, n_samps)) return rc;
+  if (mode != IQLHIP_CHOICE_MEAN && mode != IQLHIP_CHOICE_MEDIAN)
+    return fail(IQLHIP_ERR_INVALID, "mode %d: IQLHIP_CHOICE_MEAN or IQLHIP_CHOICE_MEDIAN", mode);
+  if (reinterpret_cast<uintptr_t>(workspace) % 16) return fail(IQLHIP_ERR_INVALID, "workspace not 16-byte aligned");
+  const int64_t slot_rows = choice_fit_rows(N, n_samps, workspace_bytes);
+  if (slot_rows < 32)
+    return fail(IQLHIP_ERR_INVALID, "workspace of %zu bytes holds no chunk (the full size is %zu)", workspace_bytes,
+                choice_workspace_bytes(N, n_samps));
+  hipStream_t st = (hipStream_t)stream;
+  uint32_t pos = 0;
+  HIP_TRY(hipMemcpyAsync(&pos, state + 624, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (pos > 624) return fail(IQLHIP_ERR_INVALID, "pos = %u outside 0..624", pos);
+  HIP_TRY(launch_posterior_choice(state, preds, S, N, n_samps, mode, out, idx_out, (uint16_t *)workspace, slot_rows,
+                                  st));
   return 0;
 }
 

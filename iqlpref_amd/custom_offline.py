@@ -441,7 +441,8 @@ def _build_trainer(config: "TrainConfig", seed: int, state_dim: int, action_dim:
 def train(config: TrainConfig, dataset=None, reward_model=None, eval_env=None, *,
           logger: Optional[Callable[[Dict[str, float], int], None]] = None,
           normalized_score: Optional[Callable] = None, seeds_per_gpu: int = 1, sampler: str = "device",
-          device: Optional[str] = None, chunk: int = 2000):
+          device: Optional[str] = None, chunk: int = 2000, _relabel: Optional[Callable] = None,
+          _best_by_return: bool = False):
     """cref:597-749 on the fused HIP step.
 
     ``dataset``: an iterable of Minari-style episodes (``observations``, ``actions``,
@@ -462,7 +463,11 @@ def train(config: TrainConfig, dataset=None, reward_model=None, eval_env=None, *
     stream ``np.random.seed(seed)`` gives), its own checkpoints under ``seed_<seed>/`` and a ``seed``
     entry in its logger records; all K share one buffer and step as one ``SeedGroup`` with the
     indices of one K-stream draw.  Every seed is bit-identical to ``train()`` of that seed alone.
-    Returns the trainer (K = 1) or the list of K trainers."""
+    Returns the trainer (K = 1) or the list of K trainers.
+
+    Private, for the flavours that share this loop (``custom_offline_br.train``): ``_relabel(dataset)``
+    builds the transition dict in place of ``qlearning_dataset``; ``_best_by_return`` keeps the best
+    model by the mean evaluation return even when a normalized score is logged."""
     if sampler not in ("host", "device"):
         raise ValueError("sampler must be 'host' or 'device'")
     K = int(seeds_per_gpu)
@@ -484,14 +489,17 @@ def train(config: TrainConfig, dataset=None, reward_model=None, eval_env=None, *
             normalized_score = minari.get_normalized_score
         except ImportError:
             normalized_score = None
-    if reward_model is None:
+    if reward_model is None and _relabel is None:
         _reward_model_missing(config)
     state_dim = eval_env.observation_space.shape[0]
     action_dim = eval_env.action_space.shape[0]
     max_action = float(eval_env.action_space.high[0])
 
     # ---- dataset, normalisation, buffer (cref:631-653) ----
-    qdataset = qlearning_dataset(dataset, reward_model, config.query_length)
+    if _relabel is not None:
+        qdataset = _relabel(dataset)
+    else:
+        qdataset = qlearning_dataset(dataset, reward_model, config.query_length)
     if config.normalize_reward:
         modify_reward(qdataset, config.dataset_id)
     if config.normalize_state:
@@ -588,7 +596,7 @@ def train(config: TrainConfig, dataset=None, reward_model=None, eval_env=None, *
                     log({"normalized_score": norm[k]})
                 except ValueError:
                     pass
-            score = norm[k] if norm[k] is not None else mean_eval
+            score = norm[k] if norm[k] is not None and not _best_by_return else mean_eval
             if score > best_score[k]:
                 best_score[k], best_step[k] = score, step
                 if ckpt_dirs[k] is not None:
