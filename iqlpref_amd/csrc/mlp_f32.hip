@@ -368,6 +368,10 @@ hipError_t launch_mlp_f32(const iqlhip_mlp_desc &d, const float *x, int64_t n, i
   }
   R.w_in_out = d.w_in_out;
   M.hidden_act = d.hidden_act, M.out_act = d.out_act;
+  const int act = (d.hidden_act >= 8 || d.out_act >= 8) ? 2 : d.hidden_act;  // instantiation, see act_apply
+  const int nt_last = round_up(d.dims[d.n_layers], 16) / 16;
+  // the table variant's main-path output layer (>= 4 n-tiles) parks its raw sums in the buffer as well
+  if (act == 2 && nt_last >= 4 && d.dims[d.n_layers] > maxd) maxd = d.dims[d.n_layers];
   M.lda = round_up(maxd, 16) + 4;
   M.drop_thr = 0, M.drop_scale = 1.f, M.drop_seed = d.dropout_seed, M.drop_call = d.dropout_call;
   if (d.dropout_p > 0.f) {  // the trainer's fp32 convention (api.hip): thr = p 2^32, scale = 1 / (1 - p)
@@ -378,7 +382,6 @@ hipError_t launch_mlp_f32(const iqlhip_mlp_desc &d, const float *x, int64_t n, i
   hipLaunchKernelGGL(k_mlp_repack, dim3(64, d.n_layers), dim3(256), 0, st, R);
   // the activations [64][lda], or the partial tiles of a k-split output layer (4 waves x <= 3 n-tiles)
   size_t sm = (size_t)MROWS * M.lda * sizeof(float);
-  const int nt_last = round_up(d.dims[d.n_layers], 16) / 16;
   if (nt_last < 4 && sm < (size_t)4 * nt_last * 4 * 64 * 16) sm = (size_t)4 * nt_last * 4 * 64 * 16;
   bool wide = false;
   for (int i = 0; i <= d.n_layers; ++i) wide |= d.dims[i] > 256;
@@ -397,7 +400,6 @@ hipError_t launch_mlp_f32(const iqlhip_mlp_desc &d, const float *x, int64_t n, i
     return e;
   }
   // (set on every call: the attribute is per device, and a process may drive several)
-  const int act = (d.hidden_act >= 8 || d.out_act >= 8) ? 2 : d.hidden_act;  // instantiation, see act_apply
   auto kern = act == 0 ? k_mlp_f32<0> : act == 1 ? k_mlp_f32<1> : k_mlp_f32<2>;
   e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                           160 * 1024);

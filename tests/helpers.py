@@ -153,3 +153,129 @@ def resume_state(d):
             assert d[f"ckpt/{opt}/{i}/exp_avg"].shape == net[n].shape, (opt, i, n)
             assert float(d[f"ckpt/{opt}/{i}/step"]) == float(d["ckpt/total_it"])
     return nets, target, moments, int(d["ckpt/total_it"])
+
+
+# ---------------------------------------------------------------------------------------------
+# Envelope tests of the stand-alone relabel kernels (iqlhip_mlp_forward, iqlhip_cvar_tail_mean):
+# plain numpy references and input generators, shared by the GPU tests and the host test that
+# checks the generators themselves (tests/test_relabel_oracle.py).
+# ---------------------------------------------------------------------------------------------
+# reward_models/q_mlp.py:121-130 in table order: activation code 8 + i of iqlhip_mlp_desc is entry i
+FLAX_ACTIVATIONS = {"cos": np.cos, "tanh": np.tanh, "relu": lambda v: np.maximum(v, 0),
+                    "softplus": lambda v: np.logaddexp(v, 0), "sin": np.sin,
+                    "leaky_relu": lambda v: np.where(v >= 0, v, 0.01 * v), "swish": lambda v: v / (1 + np.exp(-v)),
+                    "none": lambda v: v}
+ACT_FLAX_BASE = 8
+
+
+def mlp_act(code, hidden):
+    """The function behind an activation code of iqlhip_mlp_desc (hidden: 0 relu, 1 tanh; output:
+    0 none, 1 tanh; 8 + i: entry i of the table, either place)."""
+    if code >= ACT_FLAX_BASE:
+        return list(FLAX_ACTIVATIONS.values())[code - ACT_FLAX_BASE]
+    if code == 1:
+        return np.tanh
+    return FLAX_ACTIVATIONS["relu"] if hidden else FLAX_ACTIVATIONS["none"]
+
+
+def mlp_weights_for(rng, dims):
+    """fp32 ([in, out] weights standard_normal / sqrt(fan_in), biases 0.1 standard_normal): O(1) activations."""
+    ws = [rng.standard_normal((dims[i], dims[i + 1])).astype(np.float32) / np.float32(np.sqrt(dims[i]))
+          for i in range(len(dims) - 1)]
+    bs = [rng.standard_normal(dims[i + 1]).astype(np.float32) * np.float32(0.1) for i in range(len(dims) - 1)]
+    return ws, bs
+
+
+def mlp_forward_ref(ws, bs, x, hidden_act=0, out_act=0, dtype=np.float64, keeps=None, scale=None):
+    """x @ W + b per layer in ``dtype`` (fp64: the reference; fp32: the yardstick of what fp32 can
+    give), ws [in, out].  keeps: one boolean mask [n, width] per hidden layer, kept values times scale."""
+    h = np.asarray(x, dtype=dtype)
+    n = len(ws)
+    for l in range(n):
+        h = (h @ ws[l].astype(dtype) + bs[l].astype(dtype)).astype(dtype)
+        h = np.asarray(mlp_act(hidden_act if l < n - 1 else out_act, l < n - 1)(h), dtype=dtype)
+        if keeps is not None and l < n - 1:
+            h = (h * keeps[l] * dtype(scale)).astype(dtype)
+    return h
+
+
+# iqlhip_cvar_tail_mean: L lanes share a column (about one per 16 rows), COLS columns per work-group;
+# beyond S = 1248 the 32-column LDS image no longer fits and a work-group takes 16 columns
+CVAR_S_MAX = 2400
+
+
+def cvar_launch_config(S):
+    """(columns per work-group, lanes per column) the launcher picks for S rows."""
+    L = 2
+    while L < 32 and L * 16 < S:
+        L *= 2
+    if L < 32:
+        return {2: 128, 4: 64, 8: 32, 16: 32}[L], L
+    return (32 if S <= 1248 else 16), 32
+
+
+CVAR_FAMILIES = ("normal", "ties", "constant", "two_half", "two_tail", "wide", "negative", "ulps",
+                 "zeros_denormals", "ascending", "descending")
+
+
+def cvar_column(rng, family, S, n_tail):
+    """One fp32 column of S finite values of a named family (row order shuffled unless it is the point)."""
+    f64 = rng.standard_normal(S)
+    if family == "normal":
+        col = f64
+    elif family == "ties":  # one decimal: many equal values
+        col = np.round(f64, 1)
+    elif family == "constant":
+        col = np.full(S, f64[0])
+    elif family in ("two_half", "two_tail"):  # exactly k copies of the smaller value
+        k = S // 2 if family == "two_half" else n_tail
+        col = np.where(rng.permutation(S) < k, -1.5, 0.75)
+    elif family in ("wide", "negative"):  # ~26 decades each side of 1: where a value-interpolated probe is worst
+        mag = np.clip(np.exp(30.0 * f64), 1e-30, 1e30)  # (strictly negative stays strictly negative in fp32)
+        col = -mag if family == "negative" else np.where(rng.uniform(size=S) < 0.5, -mag, mag)
+    elif family == "ulps":
+        # neighbouring floats 1 + k 2^-23, each repeated: from S = 32 on every value is there more
+        # than 8 times (S // 12 distinct values, at most 16), the threshold's multiplicity included
+        nd = min(16, max(1, S // 12))
+        col = 1.0 + (rng.permutation(S) % nd) * 2.0 ** -23
+    elif family == "zeros_denormals":
+        # +0, -0, fp32 denormals of both signs and normals of the smallest binades.  The column's minimum is
+        # a normal number (~ -1e-30) and in every tail: tail means stay where a rounding is relative, which
+        # is what the tests' bound models (below 2^-126 fp32 is spaced 2^-149 whatever the magnitude)
+        j = rng.integers(1, 1 << 23, S).astype(np.float64) * 2.0 ** -149
+        kind = rng.permutation(S) % 6
+        col = np.select([kind == 0, kind == 1, kind == 2, kind == 3, kind == 4],
+                        [0.0, -0.0, j, -j, f64 * 1e-30], f64 * 4e-38)
+        col[rng.integers(S)] = -(1.0 + abs(f64[0])) * 1e-30
+    elif family in ("ascending", "descending"):
+        col = np.sort(f64)
+        return (col if family == "ascending" else col[::-1]).astype(np.float32)
+    else:
+        raise KeyError(family)
+    return np.asarray(col, dtype=np.float32)
+
+
+def cvar_matrix(rng, S, N, n_tail, first=0):
+    """fp32 [S, N]: the families round-robin over the columns, starting at family ``first``."""
+    names = [CVAR_FAMILIES[(first + c) % len(CVAR_FAMILIES)] for c in range(N)]
+    return np.stack([cvar_column(rng, f, S, n_tail) for f in names], axis=1), names
+
+
+def cvar_int_matrix(rng, S, N):
+    """Integer-valued fp32 entries in [-1000, 1000] with ties: every fp32 partial sum is exact."""
+    return rng.integers(-1000, 1001, (S, N)).astype(np.float32)
+
+
+def cvar_n_tails(S):
+    from oracle import relabel_oracle as ro
+    cand = [1, 2, 8, 9, S // 20 or 1, S // 2, S - 1, S] + [ro.n_tail_of(a, S) for a in (0.5, 0.9, 0.95)]
+    return sorted({min(max(t, 1), S) for t in cand})
+
+
+def cvar_ref(preds, n_tail):
+    """(fp64 mean of the n_tail smallest per column, per-column bound for an fp32 kernel that selects
+    exactly: n_tail 2^-24 mean|tail| for the fp32 sum in any order, 2^-24 |mean| for the division)."""
+    tail = np.sort(preds.astype(np.float64), axis=0)[:n_tail]
+    want = tail.mean(axis=0)
+    tol = n_tail * 2.0 ** -24 * np.abs(tail).mean(axis=0) + 2.0 ** -24 * np.abs(want)
+    return want, tol

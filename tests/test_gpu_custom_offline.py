@@ -50,10 +50,7 @@ def test_qmlp_activations_match_numpy():
     rng = np.random.default_rng(0)
     S, A, n = 7, 3, 513
     obs, act = rng.standard_normal((n, S)).astype(np.float32), rng.uniform(-1, 1, (n, A)).astype(np.float32)
-    fns = {"cos": np.cos, "tanh": np.tanh, "relu": lambda v: np.maximum(v, 0),
-           "softplus": lambda v: np.logaddexp(v, 0), "sin": np.sin,
-           "leaky_relu": lambda v: np.where(v >= 0, v, 0.01 * v), "swish": lambda v: v / (1 + np.exp(-v)),
-           "none": lambda v: v}
+    fns = helpers.FLAX_ACTIVATIONS
     for hidden in co.ACTIVATIONS:
         final = co.ACTIVATIONS[(co.ACTIVATIONS.index(hidden) + 3) % len(co.ACTIVATIONS)]
         layers = [{"kernel": (rng.standard_normal(s) / np.sqrt(s[0])).astype(np.float32),

@@ -131,3 +131,96 @@ def test_pt_forward_self_consistency():
     am2 = np.zeros((4, QL + 3), np.float32); am2[:, 3:] = 1
     v2 = ro.pt_value_last(p, st2, ac2, ts2, am2, num_heads=4)
     np.testing.assert_allclose(v2, v, rtol=1e-5, atol=1e-5)
+
+
+# ---- the generators and references of the GPU envelope tests (tests/helpers.py): what those tests
+# ---- rely on is checked here, on the host
+CVAR_S = (2, 3, 32, 33, 64, 65, 67, 128, 129, 131, 256, 257, 1248, 1249, 1251, 2399, 2400)
+
+
+def test_cvar_launch_configurations_and_tail_sizes():
+    cfg = {S: helpers.cvar_launch_config(S) for S in CVAR_S}
+    assert [cfg[S] for S in (32, 33, 64, 65, 128, 129, 256, 257, 1248, 1249, 2400)] == \
+        [(128, 2), (64, 4), (64, 4), (32, 8), (32, 8), (32, 16), (32, 16), (32, 32), (32, 32), (16, 32), (16, 32)]
+    for S in CVAR_S:
+        tails = helpers.cvar_n_tails(S)
+        assert tails[0] == 1 and tails[-1] == S and all(1 <= t <= S for t in tails) and len(set(tails)) == len(tails)
+        assert all(ro.n_tail_of(a, S) in tails for a in (0.5, 0.9, 0.95))
+        if S >= 32:
+            assert {8, 9, S // 2, S - 1} <= set(tails)
+
+
+@pytest.mark.parametrize("S", CVAR_S)
+def test_cvar_column_families_have_their_stated_properties(S):
+    rng = np.random.default_rng(S)
+    for n_tail in helpers.cvar_n_tails(S):
+        N = 2 * len(helpers.CVAR_FAMILIES) + 1
+        preds, names = helpers.cvar_matrix(rng, S, N, n_tail, first=n_tail)
+        assert preds.dtype == np.float32 and preds.shape == (S, N) and np.isfinite(preds).all()
+        assert set(names) == set(helpers.CVAR_FAMILIES)  # round-robin: every family in every matrix
+        want, tol = helpers.cvar_ref(preds, n_tail)
+        assert np.isfinite(want).all() and np.isfinite(tol).all() and np.abs(want).max() * n_tail < 3e38
+        kth = min(n_tail, S - 1)  # the reference's own route (ref:1009-1011), in fp64
+        np.testing.assert_allclose(want, np.partition(preds.astype(np.float64), kth, axis=0)[:n_tail].mean(axis=0),
+                                   rtol=1e-12, atol=0)
+        for c, name in enumerate(names):
+            col = preds[:, c]
+            srt = np.sort(col)
+            if name == "constant":
+                assert np.unique(col).size == 1
+            elif name in ("two_half", "two_tail"):
+                k = S // 2 if name == "two_half" else n_tail
+                assert (col == col.min()).sum() == (k if 0 < k < S else S) and np.unique(col).size == (2 if 0 < k < S else 1)
+                if 0 < k < S:
+                    assert srt[k - 1] < srt[k]  # the split sits at rank k exactly
+            elif name == "ulps":
+                if S >= 32:  # (fewer rows cannot hold one value nine times)
+                    assert (col == srt[n_tail - 1]).sum() > 8
+                assert np.unique(col).size <= 16 and col.min() >= 1 and col.max() <= 1 + 15 * 2.0 ** -23
+            elif name in ("wide", "negative") and S >= 32:
+                mag = np.abs(col[col != 0].astype(np.float64))
+                assert np.log10(mag.max() / mag.min()) > 20
+                assert (col < 0).all() if name == "negative" else ((col < 0).any() and (col > 0).any())
+            elif name == "zeros_denormals" and S < 32:
+                assert col.min() <= -1e-30
+            elif name == "zeros_denormals":
+                assert col.min() <= -1e-30 and np.abs(col).max() < 1e-28
+                tiny = np.finfo(np.float32).tiny
+                assert ((col == 0) & ~np.signbit(col)).any() and ((col == 0) & np.signbit(col)).any()
+                assert ((col != 0) & (np.abs(col) < tiny)).any()
+            elif name == "ties":
+                assert S < 32 or np.unique(col).size < S
+            elif name == "ascending":
+                assert np.array_equal(col, srt)
+            elif name == "descending":
+                assert np.array_equal(col[::-1], srt)
+
+
+def test_cvar_integer_matrix_sums_exactly():
+    m = helpers.cvar_int_matrix(np.random.default_rng(0), 2400, 35)
+    assert np.array_equal(m, np.round(m)) and np.abs(m).max() <= 1000 and np.abs(m).sum(axis=0).max() < 1 << 24
+
+
+def test_mlp_reference_reproduces_the_relabel_oracle():
+    rng = np.random.default_rng(3)
+    for dims, act, code in (([37, 256, 256, 1], "relu", 0), ([13, 100, 7], "relu", 0), ([6, 8, 8, 3], "tanh", 1)):
+        ws, bs = helpers.mlp_weights_for(rng, dims)
+        x = rng.standard_normal((50, dims[0])).astype(np.float32)
+        want = ro.reward_mlp_forward([a for pair in zip(ws, bs) for a in pair], x, act)
+        np.testing.assert_allclose(helpers.mlp_forward_ref(ws, bs, x, code, 0), want, rtol=0, atol=1e-6)
+        np.testing.assert_allclose(helpers.mlp_forward_ref(ws, bs, x, code, 0, dtype=np.float32), want, rtol=0, atol=1e-6)
+    # the table codes: the functions test_qmlp_activations_match_numpy names, in table order
+    v = np.linspace(-3, 3, 13)
+    for i, name in enumerate(helpers.FLAX_ACTIVATIONS):
+        for hidden in (True, False):
+            assert np.array_equal(helpers.mlp_act(8 + i, hidden)(v), helpers.FLAX_ACTIVATIONS[name](v))
+    assert list(helpers.FLAX_ACTIVATIONS) == ["cos", "tanh", "relu", "softplus", "sin", "leaky_relu", "swish", "none"]
+    assert np.array_equal(helpers.mlp_act(0, True)(v), np.maximum(v, 0)) and np.array_equal(helpers.mlp_act(0, False)(v), v)
+    assert np.array_equal(helpers.mlp_act(1, True)(v), np.tanh(v)) and np.array_equal(helpers.mlp_act(1, False)(v), np.tanh(v))
+    # dropout masks enter as given
+    keep = [rng.uniform(size=(50, 8)) < 0.5] * 2
+    ws, bs = helpers.mlp_weights_for(rng, [6, 8, 8, 3])
+    x = rng.standard_normal((50, 6)).astype(np.float32)
+    h = np.maximum(x.astype(np.float64) @ ws[0] + bs[0], 0) * keep[0] * 2.0
+    h = np.maximum(h @ ws[1] + bs[1], 0) * keep[1] * 2.0
+    np.testing.assert_allclose(helpers.mlp_forward_ref(ws, bs, x, 0, 0, keeps=keep, scale=2.0), h @ ws[2] + bs[2], atol=1e-12)
