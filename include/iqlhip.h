@@ -47,7 +47,8 @@ const char *iqlhip_build_tag(void);
 /* Shape envelope (everything outside returns IQLHIP_ERR_UNSUPPORTED with a   */
 /* message; every YAML under the reference's configs/offline/iql/ fits):      */
 /*   trainer   ReLU hidden activations, one width for all hidden layers,       */
-/*             n_hidden 1..6, hidden_dim 1..1024, batch_size a multiple of 16, */
+/*             n_hidden 1..6, hidden_dim 1..1024, batch_size a multiple of 16  */
+/*             (a step may count fewer rows: iqlhip_train_steps_valid),        */
 /*             state_dim + action_dim <= 128, action_dim <= 32, 2..8 critics,  */
 /*             plain Adam (no weight decay / amsgrad), one (beta1, beta2, eps) */
 /*             for the three optimisers.  n_hidden = 2 with hidden_dim 64, 128 */
@@ -247,6 +248,23 @@ int iqlhip_trainer_set_lr(iqlhip_trainer *t, double lr_q, double lr_v, double lr
 int iqlhip_train_steps(iqlhip_trainer *t, const iqlhip_replay_view *view, int64_t n_steps,
                        const int64_t *idx, const uint8_t *dropout_keep, float *losses_out,
                        int32_t graph_unroll, void *stream);
+
+/* iqlhip_train_steps with a per-step count of the rows that count: n_valid is NULL (every step uses
+ * its whole batch: this IS iqlhip_train_steps, bit for bit) or a device int32[n_steps] with
+ * 1 <= n_valid[i] <= batch_size (values outside are clamped into that range on the device).
+ * Step i then forms its three losses, their gradients and the logged means over rows [0, n_valid[i])
+ * of its batch only, dividing by n_valid[i]; rows beyond it are gathered like any other (their
+ * indices must point into the buffer) and contribute nothing.  A step with n_valid[i] == batch_size
+ * equals the step without counts bit for bit.  This is the short last batch of an epoch of
+ * algorithms/custom_offline/iql_bb.py (RandomBatchSampler, drop_last=False).
+ * Supported on the tuned three-kernel step at precision fp32, plain launches and graph replay (a
+ * k_backward instantiation of its own: calls without counts run the kernels they always ran).  On
+ * the general layer-wise step, or at precision bf16, a non-NULL n_valid returns
+ * IQLHIP_ERR_UNSUPPORTED before anything is launched (the counts live on the device: the call
+ * cannot see whether they all equal batch_size); seed groups take no counts.                    */
+int iqlhip_train_steps_valid(iqlhip_trainer *t, const iqlhip_replay_view *view, int64_t n_steps,
+                             const int64_t *idx, const int32_t *n_valid, const uint8_t *dropout_keep,
+                             float *losses_out, int32_t graph_unroll, void *stream);
 
 /* ------------------------------------------------------------------------ */
 /* Seed groups: K independent trainers of ONE shape (dims, hidden layers,      */
@@ -457,6 +475,21 @@ int iqlhip_pt_relabel_general(const iqlhip_pt_model *m, const float *obs, const 
  * batch >= 1, n_batches >= 0 (0 draws nothing).                                               */
 int iqlhip_np_randint(uint32_t *state, const int64_t *hi, int32_t K, int32_t batch,
                       int64_t n_batches, int64_t *const *out, void *stream);
+
+/* ------------------------------------------------------------------------ */
+/* Block-shuffled epochs of algorithms/custom_offline/iql_bb.py:208-267        */
+/* (RandomBatchSampler: contiguous blocks of `batch` rows in ONE permuted       */
+/* order that every epoch repeats, the rows left over as a short last batch)    */
+/* ------------------------------------------------------------------------ */
+/* For steps t0 .. t0 + n_steps - 1 of that walk: with nb = n_rows / batch whole blocks and
+ * slots = ceil(n_rows / batch) steps per epoch, step t uses slot t % slots;
+ *   slot <  nb: idx[i][j] = perm[slot] * batch + j,                 n_valid[i] = batch
+ *   slot == nb: idx[i][j] = min(nb * batch + j, n_rows - 1),        n_valid[i] = n_rows % batch.
+ * perm: device int64 [nb], a permutation of 0..nb-1 (values outside are clamped into it; may be
+ * NULL when nb == 0).  idx: device int64 [n_steps][batch]; n_valid: device int32 [n_steps] -- what
+ * iqlhip_train_steps_valid takes.  One launch on `stream`, no synchronisation.                    */
+int iqlhip_block_epoch_indices(const int64_t *perm, int64_t n_rows, int32_t batch, int64_t t0,
+                               int64_t n_steps, int64_t *idx, int32_t *n_valid, void *stream);
 
 /* ------------------------------------------------------------------------ */
 /* Posterior relabel of algorithms/custom_offline/iql_br.py:179-253: per       */

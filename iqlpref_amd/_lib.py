@@ -122,6 +122,7 @@ SYMBOLS = {
     "iqlhip_trainer_get_step": (C.c_int, [P, C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     "iqlhip_trainer_set_lr": (C.c_int, [P, C.c_double, C.c_double, C.c_double]),
     "iqlhip_train_steps": (C.c_int, [P, C.POINTER(ReplayView), C.c_int64, P, P, P, C.c_int32, P]),
+    "iqlhip_train_steps_valid": (C.c_int, [P, C.POINTER(ReplayView), C.c_int64, P, P, P, P, C.c_int32, P]),
     "iqlhip_group_create": (C.c_int, [C.POINTER(P), C.POINTER(P), C.c_int32]),
     "iqlhip_group_destroy": (C.c_int, [P]),
     "iqlhip_group_train_steps": (C.c_int, [P, C.POINTER(ReplayView), C.c_int64, C.POINTER(P), C.POINTER(P),
@@ -143,6 +144,7 @@ SYMBOLS = {
     "iqlhip_pt_relabel_general": (C.c_int, [C.POINTER(PtModel), P, P, C.c_int64, P, P, P, C.c_int64, C.c_int32,
                                             P, C.c_size_t, P, P]),
     "iqlhip_np_randint": (C.c_int, [P, P, C.c_int32, C.c_int32, C.c_int64, P, P]),
+    "iqlhip_block_epoch_indices": (C.c_int, [P, C.c_int64, C.c_int32, C.c_int64, C.c_int64, P, P, P]),
     "iqlhip_posterior_choice_workspace_bytes": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_size_t)]),
     "iqlhip_posterior_choice": (C.c_int, [P, P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, P, P, P, C.c_size_t, P]),
     "iqlhip_step_cost": (C.c_int, [C.POINTER(TrainerConfig), C.POINTER(C.c_double),

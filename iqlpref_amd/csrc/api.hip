@@ -34,7 +34,7 @@ int layer2_parts(int H);
 hipError_t launch_forward(bool, const TrainerDesc &, const TrainerDesc *, const DevArgs *, const DevCtr *,
                           int n_seeds, hipStream_t);
 hipError_t launch_backward(bool, const TrainerDesc &, const TrainerDesc *, const DevArgs *, DevCtr *,
-                           int n_seeds, hipStream_t);
+                           int n_seeds, hipStream_t, bool counts = false);
 hipError_t launch_stage(bool, const TrainerDesc &, const TrainerDesc *, const DevArgs *, const DevCtr *,
                         int n_seeds, hipStream_t);
 int strip_rows();
@@ -77,6 +77,8 @@ int pt_general_tp(int ql);
 hipError_t launch_pt_general(const iqlhip_pt_model &m, const float *obs, const float *act, int64_t n_rows,
                              const int64_t *win_start, const int32_t *win_len, const int32_t *win_t0,
                              int64_t n_win, int ql, float *ws, int64_t chunk, float *out, hipStream_t st);
+hipError_t launch_block_epoch(const int64_t *perm, int64_t n_rows, int batch, int64_t t0, int64_t n_steps, int64_t *idx,
+                              int32_t *n_valid, hipStream_t st);
 hipError_t launch_np_randint(uint32_t *state, const int64_t *hi, int K, int64_t total, int64_t *const *out,
                              hipStream_t st);
 size_t choice_workspace_bytes(int64_t N, int n);
@@ -350,6 +352,8 @@ struct iqlhip_trainer {
   // hipGraph of `graph_unroll` steps
   hipGraphExec_t gexec = nullptr;
   int graph_unroll = 0;
+  bool counts = false;        // the call in flight carries valid-row counts (iqlhip_train_steps_valid)
+  bool graph_counts = false;  // ... and so did the call `gexec` was captured for
   hipStream_t cap_stream = nullptr;  // capture only (the legacy default stream cannot capture); shared, see capture_stream
   // timing
   bool timing = false;
@@ -916,7 +920,7 @@ extern "C" int iqlhip_trainer_get_timing(iqlhip_trainer *t, double avg_ms[3], in
 static int enqueue_step(iqlhip_trainer *t, hipStream_t st) {
   if (!t->D.prefetch) HIP_TRY(launch_stage(t->bf16, t->D, t->ddesc, t->dargs, t->dctr, 1, st));
   HIP_TRY(launch_forward(t->bf16, t->D, t->ddesc, t->dargs, t->dctr, 1, st));
-  HIP_TRY(launch_backward(t->bf16, t->D, t->ddesc, t->dargs, t->dctr, 1, st));
+  HIP_TRY(launch_backward(t->bf16, t->D, t->ddesc, t->dargs, t->dctr, 1, st, t->counts));
   HIP_TRY(launch_update(t->bf16, t->ddesc, t->dargs, t->dctr, t->ditems, t->n_items, 1, st));
   return 0;
 }
@@ -929,7 +933,7 @@ static int enqueue_step(iqlhip_trainer *t, hipStream_t st) {
 static bool continues(const DevArgs &a, const DevArgs &b) {
   return a.rows == b.rows && a.n_rows == b.n_rows && a.row_stride == b.row_stride &&
          a.generation == b.generation && a.idx_mode == 0 && b.idx_mode == 0 && !a.drop_keep && !b.drop_keep &&
-         !a.losses_out && !b.losses_out && a.lr_q == b.lr_q && a.lr_v == b.lr_v && a.lr_a_base == b.lr_a_base;
+         !a.losses_out && !b.losses_out && !a.n_valid && !b.n_valid && a.lr_q == b.lr_q && a.lr_v == b.lr_v && a.lr_a_base == b.lr_a_base;
 }
 
 static hipError_t push_args(iqlhip_trainer *t, const DevArgs &args_in, int64_t n_steps, hipStream_t st) {
@@ -1075,7 +1079,18 @@ static int run_steps_deep(iqlhip_trainer *t, const DevArgs &a, int64_t n_steps, 
 
 static int run_steps(iqlhip_trainer *t, const DevArgs &args_in, int64_t n_steps, int graph_unroll,
                      hipStream_t st) {
-  if (t->deep) return run_steps_deep(t, args_in, n_steps, graph_unroll, st);
+  if (t->deep) {
+    // the counts live on the device: the call cannot tell whether every one of them is the whole batch
+    if (args_in.n_valid)
+      return fail(IQLHIP_ERR_UNSUPPORTED,
+                  "per-step valid-row counts (a short batch) run on the tuned step only (n_hidden 2, hidden_dim 64 / "
+                  "128 / 256); this trainer (n_hidden %d, hidden_dim %d) runs the general layer-wise step",
+                  n_hidden(t->cfg), t->cfg.hidden_dim);
+    return run_steps_deep(t, args_in, n_steps, graph_unroll, st);
+  }
+  if (args_in.n_valid && t->bf16)
+    return fail(IQLHIP_ERR_UNSUPPORTED, "per-step valid-row counts (a short batch) are built for precision fp32 only");
+  t->counts = args_in.n_valid != nullptr;  // which k_backward the launches (and the captured graph) of this call use
   if (t->group) group_invalidate(t->group);  // this call rewrites the member's slot of the group's arguments
   if (!(t->D.prefetch && t->dev_args_valid && !t->timing && continues(t->dev_args, args_in))) {
     HIP_TRY(push_args(t, args_in, n_steps, st));
@@ -1093,7 +1108,7 @@ static int run_steps(iqlhip_trainer *t, const DevArgs &args_in, int64_t n_steps,
       HIP_TRY(hipEventRecord(t->ev[0], st));
       HIP_TRY(launch_forward(t->bf16, t->D, t->ddesc, t->dargs, t->dctr, 1, st));
       HIP_TRY(hipEventRecord(t->ev[1], st));
-      HIP_TRY(launch_backward(t->bf16, t->D, t->ddesc, t->dargs, t->dctr, 1, st));
+      HIP_TRY(launch_backward(t->bf16, t->D, t->ddesc, t->dargs, t->dctr, 1, st, t->counts));
       HIP_TRY(hipEventRecord(t->ev[2], st));
       HIP_TRY(launch_update(t->bf16, t->ddesc, t->dargs, t->dctr, t->ditems, t->n_items, 1, st));
       HIP_TRY(hipEventRecord(t->ev[3], st));
@@ -1113,7 +1128,7 @@ static int run_steps(iqlhip_trainer *t, const DevArgs &args_in, int64_t n_steps,
     return 0;
   }
   if (graph_unroll > 0 && n_steps >= graph_unroll) {
-    if (!t->gexec || t->graph_unroll != graph_unroll) {
+    if (!t->gexec || t->graph_unroll != graph_unroll || t->graph_counts != t->counts) {
       if (t->gexec) {
         (void)hipGraphExecDestroy(t->gexec);
         t->gexec = nullptr;
@@ -1128,7 +1143,7 @@ static int run_steps(iqlhip_trainer *t, const DevArgs &args_in, int64_t n_steps,
       HIP_TRY(ce);
       HIP_TRY(hipGraphInstantiate(&t->gexec, g, nullptr, nullptr, 0));
       (void)hipGraphDestroy(g);
-      t->graph_unroll = graph_unroll;
+      t->graph_unroll = graph_unroll, t->graph_counts = t->counts;
     }
     for (; done + graph_unroll <= n_steps; done += graph_unroll) {
       HIP_TRY(hipGraphLaunch(t->gexec, st));
@@ -1147,6 +1162,12 @@ static int run_steps(iqlhip_trainer *t, const DevArgs &args_in, int64_t n_steps,
 extern "C" int iqlhip_train_steps(iqlhip_trainer *t, const iqlhip_replay_view *view, int64_t n_steps,
                                   const int64_t *idx, const uint8_t *dropout_keep, float *losses_out,
                                   int32_t graph_unroll, void *stream) {
+  return iqlhip_train_steps_valid(t, view, n_steps, idx, nullptr, dropout_keep, losses_out, graph_unroll, stream);
+}
+
+extern "C" int iqlhip_train_steps_valid(iqlhip_trainer *t, const iqlhip_replay_view *view, int64_t n_steps,
+                                        const int64_t *idx, const int32_t *n_valid, const uint8_t *dropout_keep,
+                                        float *losses_out, int32_t graph_unroll, void *stream) {
   if (!t || !view || !view->rows) return fail(IQLHIP_ERR_INVALID, "null argument");
   if (n_steps < 0) return fail(IQLHIP_ERR_INVALID, "n_steps must be >= 0");
   if (view->state_dim != t->cfg.state_dim || view->action_dim != t->cfg.action_dim)
@@ -1162,7 +1183,7 @@ extern "C" int iqlhip_train_steps(iqlhip_trainer *t, const iqlhip_replay_view *v
   a.rows = view->rows, a.n_rows = view->n_rows, a.row_stride = view->row_stride;
   a.generation = view->generation;
   a.idx_mode = idx ? 1 : 0, a.idx = idx;
-  a.drop_keep = dropout_keep, a.losses_out = losses_out;
+  a.drop_keep = dropout_keep, a.losses_out = losses_out, a.n_valid = n_valid;
   a.base_step = t->total_it;
   a.lr_q = t->lr_q, a.lr_v = t->lr_v, a.lr_a_base = t->lr_a_base;
   if (int rc = run_steps(t, a, n_steps, graph_unroll, (hipStream_t)stream)) return rc;
@@ -1686,6 +1707,20 @@ extern "C" int iqlhip_np_randint(uint32_t *state, const int64_t *hi, int32_t K, 
     if (pos[k] > 624) return fail(IQLHIP_ERR_INVALID, "state %d: pos = %u outside 0..624", k, pos[k]);
   if (n_batches == 0) return 0;
   HIP_TRY(launch_np_randint(state, hi, K, n_batches * (int64_t)batch, out, st));
+  return 0;
+}
+
+// ------------------------------------------------------- block-shuffled epochs --
+extern "C" int iqlhip_block_epoch_indices(const int64_t *perm, int64_t n_rows, int32_t batch, int64_t t0,
+                                          int64_t n_steps, int64_t *idx, int32_t *n_valid, void *stream) {
+  if (!idx || !n_valid) return fail(IQLHIP_ERR_INVALID, "null argument");
+  if (batch < 1) return fail(IQLHIP_ERR_INVALID, "batch = %d must be >= 1", batch);
+  if (n_rows < 1) return fail(IQLHIP_ERR_INVALID, "n_rows = %lld must be >= 1", (long long)n_rows);
+  if (t0 < 0 || n_steps < 0)
+    return fail(IQLHIP_ERR_INVALID, "t0 = %lld and n_steps = %lld must be >= 0", (long long)t0, (long long)n_steps);
+  if (!perm && n_rows >= batch) return fail(IQLHIP_ERR_INVALID, "null perm with %lld whole blocks", (long long)(n_rows / batch));
+  if (n_steps == 0) return 0;
+  HIP_TRY(launch_block_epoch(perm, n_rows, batch, t0, n_steps, idx, n_valid, (hipStream_t)stream));
   return 0;
 }
 

@@ -98,6 +98,9 @@ struct DevArgs {
   double lr_q, lr_v, lr_a_base;
   int64_t n_steps;           // steps of this call (bounds idx[] for the batch prefetch)
   uint64_t generation;       // of the replay view (host-side bookkeeping: see push_args)
+  const int32_t *n_valid;    // [n] rows of each step's batch that count (iqlhip_train_steps_valid:
+                             // a short last batch of an epoch), or null: all B.  Last on purpose --
+                             // nothing a kernel reads on the usual path moves.
 };
 
 // Device-written counters / metrics.

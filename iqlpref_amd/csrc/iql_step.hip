@@ -1150,6 +1150,15 @@ __global__ __launch_bounds__(256) void k_infer(const TrainerDesc *__restrict__ D
 
 // (LossIn, loss_terms: step_math.h)
 
+// Rows of the batch of 0-based step `step` that count towards the losses: all B, or the count
+// iqlhip_train_steps_valid gave for that step (DevArgs::n_valid, null on every other path), clamped to
+// [1, B].  fp32 only, and in k_backward an instantiation of its own (NV) that the host picks when a call
+// carries counts: the kernels of every other call do not read the pointer at all -- read through a
+// wave-uniform branch in the common instantiation, the one extra scalar load cost the one-seed latency
+// chain 0.2-1.8 % of the headline (three alternated pairs, spread of each side 0.5-1.1 %).
+#define VALID_ROWS(nvp, A, step, B) ((nvp) ? clamp_rows(ldg((nvp) + ((step) - (A).base_step)), (B)) : (B))
+__device__ __forceinline__ int clamp_rows(int n, int B) { return n < 1 ? 1 : (n > B ? B : n); }
+
 // k_forward leaves every network output as SPL partial dot products (one per part of hidden
 // layer 2, the bias in part 0).  fin_loads requests the partials of one slab -- thread
 // (row tid / 16, lane16 = tid % 16) takes columns lane16 + 16 c of its row -- and fin_value adds
@@ -1174,9 +1183,10 @@ constexpr int FIN_LD = 64;  // LDS row stride of the finished outputs
 // redundant loss / dZ2 phases are pure cost -- a work-group then owns PW x 64 columns of dZ1, every
 // wave PW n-tiles, and there are SPL / PW work-groups per (net, slab).  The same values either way.
 // ========================================================================
-template <bool BF16, int H, bool PRE, int PW = 1>
-__device__ __forceinline__ void backward_body(const TrainerDesc *__restrict__ Dp, DevCtr *__restrict__ Cp,
-                                              const int blk, char *smem, const int nslab, const int ntrain) {
+template <bool BF16, int H, bool PRE, int PW = 1, bool NV = false>
+__device__ __forceinline__ void backward_body(const TrainerDesc *__restrict__ Dp, const DevArgs *__restrict__ Ap,
+                                              DevCtr *__restrict__ Cp, const int blk, char *smem, const int nslab,
+                                              const int ntrain) {
   using K = KCfg<BF16, H>;
   using C = FCfg<BF16, H>;
   using P = Prec<BF16>;
@@ -1202,6 +1212,7 @@ __device__ __forceinline__ void backward_body(const TrainerDesc *__restrict__ Dp
   T *const g_dz1T = reinterpret_cast<T *>(D.dz1T), *const g_dz2T = reinterpret_cast<T *>(D.dz2T);
   T *const g_dz3T = reinterpret_cast<T *>(D.dz3T);
   float *const g_lsp = D.lsp, *const g_lossp = D.lossp;
+  const int32_t *const g_nv = NV ? Ap->n_valid : nullptr;
   const bool drop_on = D.has_dropout && net == D.net_a;
   const float drop_scale = D.drop_scale;
   const bool is_gauss_actor = net == D.net_a && !D.deterministic;
@@ -1212,7 +1223,6 @@ __device__ __forceinline__ void backward_body(const TrainerDesc *__restrict__ Dp
   const int r = lane & 15, q = lane >> 4;
   constexpr int HP = K::HP;
   const int nkb = BP / P::KM;
-  const float fB = (float)B;
 
   T *dz2s = reinterpret_cast<T *>(smem);                       // [16][HP]
   float *dz3 = reinterpret_cast<float *>(dz2s + SLAB * HP);    // [32][16] d(loss)/d(out), [j][row]
@@ -1309,6 +1319,11 @@ __device__ __forceinline__ void backward_body(const TrainerDesc *__restrict__ Dp
   // ---- per-row loss terms and d(loss)/d(out)  (ref:581-637), LDS layout [j][16 rows] ----
   {
     const float *f = fin + lrow * FIN_LD;
+    // the batch means divide by the step's valid rows (a whole batch: the same B and 2 / B as ever)
+    int nv = B;
+    if constexpr (NV) nv = VALID_ROWS(g_nv, *Ap, Cp->ctr[0], B);
+    const float fB = (float)nv, two_over_B = nv == B ? D.two_over_B : 2.0f / fB;
+    const bool live = !NV || brow < nv;
     LossIn lin;
     // TwinQ.forward = min(q1, q2) of the target critics (ref:531-533, 583-584); min over all E
 #pragma unroll
@@ -1322,7 +1337,8 @@ __device__ __forceinline__ void backward_body(const TrainerDesc *__restrict__ Dp
         lin.mean = f[out_mean + (j < n_act ? j : n_act - 1)];
         lin.act = actv[h], lin.ls = lsv[h];
         float d3, lt, gs;
-        loss_terms<BF16>(D, net, lin, fB, d3, lt, gs);
+        loss_terms<BF16>(D, net, lin, fB, two_over_B, d3, lt, gs);
+        if (!live) d3 = lt = gs = 0.f;  // a row beyond the step's valid count: no loss, no gradient
         if (j < out_dim) dz3[j * SLAB + lrow] = d3, lterm[j * SLAB + lrow] = lt, gstd[j * SLAB + lrow] = gs;
       }
     }
@@ -1915,7 +1931,10 @@ __device__ __forceinline__ void update_body(const TrainerDesc *__restrict__ Dp,
       const int n = tid - 64;
       float s = 0.f;
       for (int k = 0; k < nslab; ++k) s += sred[n * nslab + k];
-      sred[nl + na + n] = s / (float)B;
+      // (counts are an fp32 feature: the bf16 kernel keeps the plain division)
+      int nv = B;
+      if constexpr (!BF16) nv = VALID_ROWS(A.n_valid, A, t1 - 1, B);
+      sred[nl + na + n] = s / (float)nv;
     }
     __syncthreads();
     if (tid == 64) {
@@ -2538,12 +2557,13 @@ __device__ __forceinline__ void update_body(const TrainerDesc *__restrict__ Dp,
 // ------------------------------------------------------------------------
 // __global__ wrappers
 // ------------------------------------------------------------------------
-template <bool BF16, int H, bool PRE, int PW>
+template <bool BF16, int H, bool PRE, int PW, bool NV = false>
 __global__ __launch_bounds__(256, PRE ? 1 : (PW > 1 ? (BF16 ? 4 : 2) : (BF16 ? 6 : 3)))
 void k_backward(const TrainerDesc *__restrict__ Dp, const DevArgs *__restrict__ Ap, DevCtr *__restrict__ Cp,
                 const int nslab, const int ntrain) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  backward_body<BF16, H, PRE, PW>(Dp + blockIdx.y, Cp + blockIdx.y, (int)blockIdx.x, smem, nslab, ntrain);
+  backward_body<BF16, H, PRE, PW, NV>(Dp + blockIdx.y, Ap + blockIdx.y, Cp + blockIdx.y, (int)blockIdx.x, smem, nslab,
+                                      ntrain);
 }
 
 template <bool BF16, bool LAT>
@@ -2716,7 +2736,8 @@ int bwd_parts_per_wg(int B, int H, int n_seeds) {
   return ((int64_t)B * n_seeds >= 512 && layer2_parts(H) % 2 == 0) ? 2 : 1;
 }
 hipError_t launch_backward(bool bf16, const TrainerDesc &D, const TrainerDesc *dD, const DevArgs *a,
-                           DevCtr *c, int n_seeds, hipStream_t st) {
+                           DevCtr *c, int n_seeds, hipStream_t st, bool counts) {
+  // counts: the call carries per-step valid-row counts (fp32, one seed: api.hip checks) -> the NV kernels
   if (use_tp(bf16, D, n_seeds, true)) {
     const int nslab32 = D.B / 32;
     const int nxn = (D.ntrain <= 4 && nslab32 % 2 == 0) ? 2 : 1;  // XCDs per trained net
@@ -2742,6 +2763,25 @@ hipError_t launch_backward(bool bf16, const TrainerDesc &D, const TrainerDesc *d
     if (pre) LAUNCH_B(BF, HH, true, 1);                               \
     else LAUNCH_B(BF, HH, false, 1);                                  \
   } while (0)
+  if (counts && !bf16) {
+#define LAUNCH_V(HH, PRE_, PW_)                                                                                      \
+  hipLaunchKernelGGL((k_backward<false, HH, PRE_, PW_, true>), dim3(grid, n_seeds), dim3(256), sm, st, dD, a, c, D.B / SLAB, \
+                     D.ntrain)
+#define CALL_V(HH)                                                    \
+  do {                                                                \
+    if constexpr (HH >= 128) {                                        \
+      if (pw == 2) { LAUNCH_V(HH, false, 2); break; }                 \
+    }                                                                 \
+    if (pre) LAUNCH_V(HH, true, 1);                                   \
+    else LAUNCH_V(HH, false, 1);                                      \
+  } while (0)
+    if (D.H == 256) CALL_V(256);
+    else if (D.H == 128) CALL_V(128);
+    else CALL_V(64);
+#undef CALL_V
+#undef LAUNCH_V
+    return hipGetLastError();
+  }
   DISPATCH_H(bf16, D.H, CALL);
 #undef CALL
 #undef LAUNCH_B

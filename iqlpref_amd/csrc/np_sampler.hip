@@ -52,4 +52,36 @@ hipError_t launch_np_randint(uint32_t *state, const int64_t *hi, int K, int64_t 
   return hipGetLastError();
 }
 
+// The epoch walk of algorithms/custom_offline/iql_bb.py:208-238 (RandomBatchSampler under a BatchSampler):
+// one permutation of the nb = N / B whole blocks, walked again every epoch of ceil(N / B) steps; the
+// rows N % B left over are one short batch at the end of each epoch.  One thread per index; the entries
+// of a short batch beyond its valid count point at the last row (they are gathered, never counted).
+__global__ __launch_bounds__(256) void k_block_epoch(const int64_t *__restrict__ perm, int64_t N, int B, int64_t t0,
+                                                      int64_t n_steps, int64_t *__restrict__ idx,
+                                                      int32_t *__restrict__ n_valid) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= n_steps * B) return;
+  const int64_t i = e / B, j = e - i * B;
+  const int64_t nb = N / B, tail = N - nb * B, slots = nb + (tail ? 1 : 0);
+  const int64_t slot = (t0 + i) % slots;
+  int64_t row;
+  if (slot < nb) {
+    const int64_t p = perm[slot];
+    row = (p < 0 ? 0 : (p >= nb ? nb - 1 : p)) * B + j;  // (a permutation of 0..nb-1 is the caller's to give)
+  } else {
+    row = nb * B + j;
+    if (row > N - 1) row = N - 1;
+  }
+  idx[e] = row;
+  if (j == 0) n_valid[i] = slot < nb ? B : (int32_t)tail;
+}
+
+hipError_t launch_block_epoch(const int64_t *perm, int64_t n_rows, int batch, int64_t t0, int64_t n_steps, int64_t *idx,
+                              int32_t *n_valid, hipStream_t st) {
+  const int64_t total = n_steps * batch;
+  hipLaunchKernelGGL(k_block_epoch, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, perm, n_rows, batch, t0,
+                     n_steps, idx, n_valid);
+  return hipGetLastError();
+}
+
 }  // namespace iqlhip

@@ -19,8 +19,9 @@ struct LossIn {
   float vv, mean, act, ls, nv, qv, rew, done;
 };
 
+// fB = the rows the batch means divide by, two_over_B = 2 / fB (D.two_over_B for a whole batch).
 template <bool BF16, class Desc>
-__device__ __forceinline__ void loss_terms(const Desc &D, int net, const LossIn &x, float fB,
+__device__ __forceinline__ void loss_terms(const Desc &D, int net, const LossIn &x, float fB, float two_over_B,
                                            float &dz3, float &lterm, float &gstd) {
   using P = Prec<BF16>;
   // Branch-free on purpose: all three variants are evaluated and one is selected.  With
@@ -63,11 +64,17 @@ __device__ __forceinline__ void loss_terms(const Desc &D, int net, const LossIn 
   const float lterm_q = diff * diff;
   // q_loss = sum_e mse(q_e, t) / E (ref:606): the division hands 1/E to each mse term, whose
   // backward is (2/B) * (q - t) * grad_out; for E = 2 and B a power of two = (q - t) / B
-  const float dz3_q = P::round((D.two_over_B * diff) * D.inv_E);
+  const float dz3_q = P::round((two_over_B * diff) * D.inv_E);
   const bool is_a = net == D.net_a, is_v = net == D.net_v;
   dz3 = is_a ? dz3_a : (is_v ? dz3_v : dz3_q);
   lterm = is_a ? lterm_a : (is_v ? lterm_v : lterm_q);
   gstd = (is_a && !det) ? gstd_g : 0.f;
+}
+
+template <bool BF16, class Desc>
+__device__ __forceinline__ void loss_terms(const Desc &D, int net, const LossIn &x, float fB,
+                                           float &dz3, float &lterm, float &gstd) {
+  loss_terms<BF16>(D, net, x, fB, D.two_over_B, dz3, lterm, gstd);
 }
 
 // Polyak update of a target weight t towards the new weight p.  Two forms, different rounding:

@@ -1,0 +1,568 @@
+"""The ``algorithms/custom_offline/iql_bb.py`` flavour of the path (config
+``configs/custom_offline/iql/bb.yaml``).  "bref:" = that file.
+
+Differences from ``custom_offline`` (``iql.py``) and how they map onto the same kernels:
+
+* batches are not drawn row by row: ``RandomBatchSampler`` (bref:208-238) draws ONE
+  ``torch.randperm(N // B)`` when it is built, and every epoch of ``ceil(N / B)`` steps walks the
+  same permutation -- batch i is the contiguous rows ``[perm[i] B, (perm[i] + 1) B)``, and the
+  ``N % B`` rows left over are one SHORT batch at the end of each epoch (``drop_last=False``).
+  ``BlockEpochSampler`` holds the permutation; ``iqlhip_block_epoch_indices`` writes the indices
+  and the valid-row count of every step on the device, and ``iqlhip_train_steps_valid`` forms the
+  batch means of a short step over its valid rows only (csrc/np_sampler.hip, csrc/iql_step.hip);
+* the Q target is ``r + attn_mask * gamma * V(s')`` (bref:473): the buffer stores
+  ``done = 1 - attn_mask``, exact for masks in {0, 1} (anything else is refused);
+* states are z-scored on all columns but the last four, eps 1e-3 (bref:145-149), in float64 on the
+  host as ``IQL_H5Dataset.__getitem__`` does, then rounded to float32 once;
+* ``act()`` clamps per dimension to ``[min_actions, max_actions]`` without scaling (bref:344-350);
+  the maximum speed is the 99th percentile of ``actions[:, 0]``, the angle range +-180;
+* the Polyak form, no autocast, the cosine actor schedule and the checkpoint keys are those of
+  ``custom_offline``.
+
+``bb_run_eval_IQL`` is the evaluation of bref:675-867: a numpy simulator of a point agent that steers
+to a goal among drifting obstacles, rewarded by the preference model over a rolling context.  It makes
+the same ``default_rng(seed)`` calls in the same order with the same float arithmetic, so that equal
+actions give equal states and returns.
+
+Not built: the Orbax reward-model reader (``load_PT``); HDF5 is read only when ``h5py`` is there.
+Seed groups, sweeps and bf16 are not offered for this flavour.
+"""
+import ctypes as C
+import os
+import uuid
+from dataclasses import asdict, dataclass
+from typing import Any, Callable, Dict, Mapping, Optional, Tuple
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import _lib
+from . import distributed as D
+from ._lib import check, ptr, stream_ptr
+from .custom_offline import ImplicitQLearning as _CustomIQL
+from .custom_offline import ReplayBuffer
+from .iql import DeterministicPolicy as _DeterministicPolicy
+from .iql import GaussianPolicy as _GaussianPolicy
+from .iql import TwinQ, ValueFunction, set_seed
+from .relabel import RewardPT
+
+DATASET_KEYS = ("states", "actions", "rewards", "n_rewards", "next_states", "attn_mask")
+
+
+@dataclass
+class TrainConfig:
+    """bref:43-81, same fields and defaults."""
+    project: str = "IQL-pref"
+    group: str = "IQL-BB"
+    name: str = "iql"
+    gamma: float = 0.99
+    tau: float = 0.005
+    beta: float = 3.0
+    iql_tau: float = 0.7
+    iql_deterministic: bool = False
+    vf_lr: float = 3e-4
+    qf_lr: float = 3e-4
+    actor_lr: float = 3e-4
+    actor_dropout: Optional[float] = None
+    dataset_id: str = "bbway1"
+    dataset_path: str = "~/iqlpref/t0012/reward_data_1/bbway1_t0012.hdf5"
+    reward_model_path: str = "~/iqlpref/t0012/pt_rewards_1/best_model.ckpt"
+    move_stats_path: str = "~/iqlpref/t0012/cache/p_stats.npy"
+    update_steps: int = int(1e6)
+    batch_size: int = 256
+    normalize_state: bool = False
+    normalize_reward: bool = False
+    eval_every: int = int(5e3)
+    eval_episodes: int = 10
+    train_seed: int = 0
+    eval_seed: int = 0
+    checkpoints_path: Optional[str] = None
+
+    def __post_init__(self):
+        self.name = f"{self.name}-{self.dataset_id}-{str(uuid.uuid4())[:8]}"
+        if self.checkpoints_path is not None:
+            self.checkpoints_path = os.path.join(self.checkpoints_path, self.name)
+
+
+def load_stats(load_file):
+    """bref:84-86."""
+    return tuple(np.load(os.path.expanduser(load_file), fix_imports=False))
+
+
+# --------------------------------------------------------------------------- #
+# dataset (bref:120-205)
+# --------------------------------------------------------------------------- #
+def _h5py():
+    try:
+        import h5py
+    except ImportError:
+        raise ImportError("custom_offline_bb: reading a dataset from an HDF5 path needs h5py, which is not "
+                          "installed; pass the arrays instead (a mapping with the keys "
+                          f"{', '.join(DATASET_KEYS)})") from None
+    return h5py
+
+
+class BBDataset:
+    """``IQL_H5Dataset`` (bref:120-205) over arrays held in memory.
+
+    ``source``: a mapping with ``states`` [N, S], ``actions`` [N, A], ``rewards``, ``n_rewards`` [N] or
+    [N, 1], ``next_states`` [N, S], ``attn_mask`` [N] or [N, 1], or the path of an HDF5 file with these
+    datasets (needs h5py).  The statistics are the reference's numpy calls on the arrays as stored:
+    the 99th percentile of ``actions[:, 0]``, and -- ``normalized_states`` -- mean and std + eps of every
+    state column but the last four, which keep mean 0 and std 1."""
+
+    def __init__(self, source, normalized_states: bool = True, normalized_rewards: bool = True,
+                 reward_adjustment: float = 0.0, eps: float = 1e-3, device: str = "cpu"):
+        if isinstance(source, (str, os.PathLike)):
+            h5py = _h5py()
+            with h5py.File(os.path.expanduser(os.fspath(source)), "r") as f:
+                source = {k: f[k][...] for k in DATASET_KEYS}
+        if not isinstance(source, Mapping):
+            raise TypeError("BBDataset takes a mapping of arrays or an HDF5 path")
+        missing = [k for k in DATASET_KEYS if k not in source]
+        if missing:
+            raise KeyError(f"BBDataset: missing arrays {missing}")
+        self._data = {k: np.asarray(source[k]) for k in DATASET_KEYS}
+        states, actions = self._data["states"], self._data["actions"]
+        if states.ndim != 2 or actions.ndim != 2 or states.shape[1] < 5:
+            raise ValueError("states must be [N, S] with S > 4 and actions [N, A]")
+        n = states.shape[0]
+        for k in DATASET_KEYS:
+            if self._data[k].shape[0] != n:
+                raise ValueError(f"BBDataset: {k} has {self._data[k].shape[0]} rows, states {n}")
+        mask = self._data["attn_mask"]
+        if not np.all((mask == 0) | (mask == 1)):
+            raise ValueError("attn_mask must hold only 0 and 1: the buffer stores done = 1 - attn_mask, and the "
+                             "target r + attn_mask * gamma * V(s') is reproduced exactly only for these")
+        self.normalized_rewards = normalized_rewards
+        self.reward_adjustment = reward_adjustment
+        self._device = device
+        self._sts_shape, self._acts_shape = states.shape, actions.shape
+        self._max_speed = np.percentile(actions[:, 0], 99)
+        self._min_speed, self._max_angle, self._min_angle = 0.0, 180.0, -180.0
+        self._state_mean = np.zeros(states.shape[1])
+        self._state_std = np.ones(states.shape[1])
+        if normalized_states:
+            self._state_mean[:-4] = states[:, :-4].mean(0)
+            self._state_std[:-4] = states[:, :-4].std(0) + eps
+
+    def __len__(self):
+        return self._sts_shape[0]
+
+    def shapes(self):
+        return self._sts_shape, self._acts_shape
+
+    def max_actions(self):
+        return torch.tensor([self._max_speed, self._max_angle], device=self._device)
+
+    def min_actions(self):
+        return torch.tensor([self._min_speed, self._min_angle], device=self._device)
+
+    def state_mean(self):
+        return self._state_mean
+
+    def state_std(self):
+        return self._state_std
+
+    def transitions(self) -> Dict[str, np.ndarray]:
+        """All N transitions as ``__getitem__`` (bref:162-187) hands them out, float32, under the keys
+        ``ReplayBuffer.load_dataset`` takes; ``terminals`` = 1 - attn_mask."""
+        d = self._data
+        f32 = lambda x: np.asarray(x).astype(np.float32)
+        rewards = d["n_rewards"] if self.normalized_rewards else d["rewards"]
+        n = len(self)
+        return {"observations": f32((d["states"] - self._state_mean) / self._state_std),
+                "actions": f32(d["actions"]),
+                "rewards": f32(rewards + self.reward_adjustment).reshape(n),
+                "next_observations": f32((d["next_states"] - self._state_mean) / self._state_std),
+                "terminals": 1.0 - f32(d["attn_mask"]).reshape(n)}
+
+
+# --------------------------------------------------------------------------- #
+# block-shuffled epochs (bref:208-267)
+# --------------------------------------------------------------------------- #
+class BlockEpochSampler:
+    """``fast_loader`` (bref:241-267): the ``n_rows // batch_size`` whole blocks in ONE permuted order,
+    drawn at construction with ``torch.randperm`` on the CPU ``generator`` (None: torch's global one, as
+    the reference) or handed in as ``perm``; then the ``n_rows % batch_size`` rows left over.  Step t of
+    training uses slot ``t % len(self)``."""
+
+    def __init__(self, n_rows: int, batch_size: int, generator: Optional[torch.Generator] = None, perm=None):
+        self.n_rows, self.batch_size = int(n_rows), int(batch_size)
+        if self.n_rows < 1 or self.batch_size < 1:
+            raise ValueError("n_rows and batch_size must be >= 1")
+        self.n_blocks = self.n_rows // self.batch_size
+        self.tail = self.n_rows - self.n_blocks * self.batch_size
+        if perm is None:
+            perm = torch.randperm(self.n_blocks, generator=generator)
+        perm = torch.as_tensor(np.asarray(perm)).to(torch.int64).cpu().reshape(-1)
+        if perm.numel() != self.n_blocks or sorted(perm.tolist()) != list(range(self.n_blocks)):
+            raise ValueError(f"perm must be a permutation of 0..{self.n_blocks - 1}")
+        self.perm = perm
+        self._dev_perm = None
+
+    def __len__(self):
+        """Steps per epoch: ceil(n_rows / batch_size)."""
+        return self.n_blocks + (1 if self.tail else 0)
+
+    def host_indices(self, t0: int, n_steps: int) -> Tuple[np.ndarray, np.ndarray]:
+        """(int64 [n_steps, batch_size], int32 [n_steps]): the rows of steps t0 .. t0 + n_steps - 1 and how
+        many of them count; the entries of a short batch beyond its count repeat the last row."""
+        B, perm = self.batch_size, self.perm.numpy()
+        idx = np.empty((n_steps, B), np.int64)
+        valid = np.empty(n_steps, np.int32)
+        j = np.arange(B, dtype=np.int64)
+        for i in range(n_steps):
+            slot = (t0 + i) % len(self)
+            if slot < self.n_blocks:
+                idx[i], valid[i] = perm[slot] * B + j, B
+            else:
+                idx[i], valid[i] = np.minimum(self.n_blocks * B + j, self.n_rows - 1), self.tail
+        return idx, valid
+
+    def device_indices(self, t0: int, n_steps: int, device) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The same two arrays written on the device by one launch of ``iqlhip_block_epoch_indices`` on
+        the current stream: nothing waits for the host."""
+        lib = _lib.load()
+        dev = _lib.require_gpu(device)
+        if self._dev_perm is None or self._dev_perm.device != dev:
+            self._dev_perm = self.perm.to(dev)
+        idx = torch.empty((n_steps, self.batch_size), dtype=torch.int64, device=dev)
+        valid = torch.empty(n_steps, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            check(lib.iqlhip_block_epoch_indices(ptr(self._dev_perm) if self.n_blocks else None, self.n_rows,
+                                                 self.batch_size, int(t0), int(n_steps), ptr(idx), ptr(valid),
+                                                 stream_ptr()))
+        return idx, valid
+
+
+# --------------------------------------------------------------------------- #
+# policies and trainer (bref:318-552)
+# --------------------------------------------------------------------------- #
+def _clamped_act(policy, action: torch.Tensor) -> np.ndarray:
+    lo = torch.as_tensor(policy.min_actions, device=action.device)
+    hi = torch.as_tensor(policy.max_actions, device=action.device)
+    return torch.clamp(action, lo, hi).cpu().data.numpy().flatten()
+
+
+class GaussianPolicy(_GaussianPolicy):
+    """bref:318-350: no action scaling; ``act`` clamps to [min_actions, max_actions] per dimension."""
+
+    def __init__(self, state_dim: int, act_dim: int, max_actions: torch.Tensor, min_actions: torch.Tensor,
+                 hidden_dim: int = 256, n_hidden: int = 2, dropout: Optional[float] = None):
+        super().__init__(state_dim, act_dim, 1.0, hidden_dim, n_hidden, dropout)
+        self.max_actions, self.min_actions = max_actions, min_actions
+
+    @torch.inference_mode()
+    def act(self, state: np.ndarray, device: str = "cpu"):
+        state = torch.tensor(state.reshape(1, -1), device=device, dtype=torch.float32)
+        dist = self(state)
+        return _clamped_act(self, dist.mean if not self.training else dist.sample())
+
+
+class DeterministicPolicy(_DeterministicPolicy):
+    """bref:353-384."""
+
+    def __init__(self, state_dim: int, act_dim: int, max_actions: torch.Tensor, min_actions: torch.Tensor,
+                 hidden_dim: int = 256, n_hidden: int = 2, dropout: Optional[float] = None):
+        super().__init__(state_dim, act_dim, 1.0, hidden_dim, n_hidden, dropout)
+        self.max_actions, self.min_actions = max_actions, min_actions
+
+    @torch.inference_mode()
+    def act(self, state: np.ndarray, device: str = "cpu"):
+        state = torch.tensor(state.reshape(1, -1), device=device, dtype=torch.float32)
+        return _clamped_act(self, self(state))
+
+
+class ImplicitQLearning(_CustomIQL):
+    """bref:416-552 on the fused step: the constructor of the reference, the arithmetic of
+    ``custom_offline.ImplicitQLearning`` (the attn_mask of bref:473 lives in the buffer as 1 - done)."""
+
+    def __init__(self, max_actions, min_actions, actor, actor_optimizer, actor_lr_scheduler, q_network, q_optimizer,
+                 v_network, v_optimizer, iql_tau: float = 0.7, beta: float = 3.0, gamma: float = 0.99,
+                 tau: float = 0.005, device: str = "cpu", *, seed: Optional[int] = None, keep_grads: bool = False):
+        super().__init__(1.0, actor, actor_optimizer, actor_lr_scheduler, q_network, q_optimizer, v_network,
+                         v_optimizer, iql_tau=iql_tau, beta=beta, gamma=gamma, tau=tau, device=device, seed=seed,
+                         keep_grads=keep_grads)
+        self.max_actions, self.min_actions = max_actions, min_actions
+
+    def train_epoch_steps(self, replay_buffer: ReplayBuffer, sampler: BlockEpochSampler, t0: int, n_steps: int, *,
+                          graph_unroll: Optional[int] = None):
+        """Steps t0 .. t0 + n_steps - 1 of the epoch walk (bref:966-970) in one library call: the indices
+        and valid-row counts come from the device generator, nothing waits for the host.  Returns the
+        [n_steps, 3] device loss tensor."""
+        if sampler.n_rows != replay_buffer.index_bound():
+            raise ValueError(f"the sampler walks {sampler.n_rows} rows, the buffer holds {replay_buffer.index_bound()}")
+        idx, valid = sampler.device_indices(t0, n_steps, self._dev)
+        return self.train_steps(replay_buffer, n_steps, sampler.batch_size, indices=idx, n_valid=valid,
+                                graph_unroll=graph_unroll)
+
+
+# --------------------------------------------------------------------------- #
+# evaluation (bref:577-867): the simulator
+# --------------------------------------------------------------------------- #
+_RAD = np.pi / 180.0
+ARENA_RADIUS = 50.0
+AGENT_RADIUS, GOAL_RADIUS = 0.3, 1.0
+STATE_TAIL = 4  # level, ai, attempt, day: the columns the normalisation leaves alone
+
+
+def _cos_deg(deg):
+    c = np.cos(deg * _RAD)
+    c = np.where(np.isclose(deg, 90), 0.0, c)
+    return np.where(np.isclose(deg, 270), 0.0, c) * 1
+
+
+def _sin_deg(deg):
+    s = np.sin(deg * _RAD)
+    s = np.where(np.isclose(deg, 360), 0.0, s)
+    return np.where(np.isclose(deg, 180), 0.0, s) * 1
+
+
+def _disc_point(radius, n, rng):
+    """Uniform in a disc: the radius draw(s) first, then the angle draw(s)."""
+    rad = radius * np.sqrt(rng.random(n))
+    ang = rng.random(n) * 2 * np.pi
+    return rad * np.cos(ang), rad * np.sin(ang)
+
+
+def _segment_hits_goal(ax, ay, bx, by, gx, gy):
+    """Does the agent (radius 0.3) moving from a to b touch the goal disc (radius 1)?  The point of the
+    segment closest to the goal is tested; all scalars."""
+    px, py, dx, dy = gx - ax, gy - ay, bx - ax, by - ay
+    with np.errstate(invalid="ignore", divide="ignore"):
+        u = np.asarray(px * dx + py * dy) / np.asarray((dx ** 2) + (dy ** 2))
+    u = np.where(np.isnan(u), 0.0, u)
+    u = np.where(u < 0, 0.0, u)
+    u = np.where(u > 1, 1.0, u)
+    cx, cy = ax + dx * u, ay + dy * u
+    d2 = ((cx - gx) ** 2) + ((cy - gy) ** 2)
+    lim = (AGENT_RADIUS + GOAL_RADIUS) ** 2
+    return bool(np.any((d2 < lim) | np.isclose(d2, lim)))
+
+
+def _observe(goal, px, py, ox, oy, oang, tail, n_near):
+    """[x, y, (x, y, heading) of the n_near nearest obstacles, goal x, y, level, ai, attempt, day]."""
+    dist = np.sqrt(((ox - px) ** 2) + ((oy - py) ** 2)) * 1
+    near = np.argpartition(dist, np.arange(n_near))[:n_near]
+    s = [px, py]
+    for k in near:
+        s += [ox[k], oy[k], oang[k]]
+    s += [goal[0], goal[1]]
+    s += [v * 1.0 for v in tail]
+    return np.asarray(s)
+
+
+def bb_run_eval_IQL(actor, num_episodes, r_model, move_stats, state_mean=0, state_std=1, max_horizon=500,
+                    n_min_obstacles=6, days=181, context_length=100, seed=4, device="cpu"):
+    """bref:675-867.  ``num_episodes`` episodes of a point agent in a disc of radius 50: 50 / 100 / 150
+    obstacles (level 9 / 10 / 11) drift along their headings by ``normal(move_stats[2], move_stats[3])``
+    per step and re-enter mirrored when they leave; the agent moves by (speed, heading) =
+    ``actor.act(normalised state)``; the episode ends when its path touches the goal or after
+    ``max_horizon`` steps.  The reward of a step is ``r_model(states, actions, timesteps, mask,
+    training=False)[0]["value"][:, 0, -1]`` over the last ``context_length`` steps; the return is their
+    sum.  Obstacles do not stop the agent (the reference computes those collisions and drops them).
+    Every draw comes from ``np.random.default_rng(seed)`` in the reference's order.  The actor is handed
+    back in train mode."""
+    actor.eval()
+    returns = []
+    rng = np.random.default_rng(seed)
+    for _ in range(num_episodes):
+        level = rng.choice([9, 10, 11])
+        n_obs = {9: 50, 10: 100}.get(int(level), 150)
+        ai = rng.choice([1, 2, 3, 4])
+        attempt = rng.choice(4)
+        day = rng.choice(days)
+        ox, oy = _disc_point(ARENA_RADIUS, n_obs, rng)
+        oang = rng.uniform(0.0, 360.0, n_obs)
+        while True:  # a start more than 1 away from obstacle 0
+            sx, sy = _disc_point(ARENA_RADIUS, None, rng)
+            if np.all(((sx - ox[0]) ** 2) + ((sy - oy[0]) ** 2) > 1):
+                break
+        px, py = float(sx), float(sy)
+        while True:  # a goal about 30 away, inside the arena
+            heading = rng.uniform(0.0, 360.0)
+            reach = rng.normal(30)
+            goal = (float(px + reach * _cos_deg(heading)), float(py + reach * _sin_deg(heading)))
+            if ((goal[0] ** 2) + (goal[1] ** 2)) <= ARENA_RADIUS ** 2:
+                break
+        tail = (level, ai, attempt, day)
+        s = _observe(goal, px, py, ox, oy, oang, tail, n_min_obstacles).reshape(1, 1, -1)
+        a = np.zeros((1, 0, 2))
+        t = np.zeros((1, 1), dtype=np.int32)
+        episode_return = 0.0
+        for _ in range(max_horizon):
+            action = actor.act((s[-1, -1] - state_mean) / state_std, device)
+            a = np.concatenate([a, action.reshape(1, 1, -1)], axis=1)[:, -context_length:, :]
+            reward, _ = r_model(s, a, t, np.ones((1, t.shape[1]), dtype=np.float32), training=False)
+            reward = reward["value"][:, 0, -1]
+            qx, qy = px, py
+            px = float(px + (action[0] * _cos_deg(action[1])))
+            py = float(py + (action[0] * _sin_deg(action[1])))
+            drift = rng.normal(move_stats[2], move_stats[3], n_obs)
+            nx, ny = ox + (drift * _cos_deg(oang)), oy + (drift * _sin_deg(oang))
+            out = np.sqrt((nx ** 2) + (ny ** 2)) > ARENA_RADIUS
+            ox, oy = np.where(out, -ox, nx), np.where(out, -oy, ny)
+            reached = _segment_hits_goal(qx, qy, px, py, goal[0], goal[1])
+            s = np.concatenate([s, _observe(goal, px, py, ox, oy, oang, tail, n_min_obstacles).reshape(1, 1, -1)],
+                               axis=1)[:, -context_length:, :]
+            t = np.concatenate([t, (t[-1][-1] + 1).reshape(1, -1)], axis=1)[:, -context_length:]
+            episode_return += reward
+            if reached:
+                break
+        returns.append(episode_return)
+    actor.train()
+    return np.asarray(returns)
+
+
+class RewardPTContext:
+    """A ``RewardPT`` behind the call shape of the reference's reward model (bref:786-793):
+    ``r(states [1, L, S], actions [1, L, A], timesteps [1, L], mask, training=False)`` ->
+    ``({"value": [1, 1, 1]}, None)``, the value of the LAST token of the context -- the one entry
+    ``bb_run_eval_IQL`` reads -- from one ``window_values`` call with the true timesteps."""
+
+    def __init__(self, model: RewardPT, context_length: int = 100):
+        if not isinstance(model, RewardPT):
+            raise TypeError("RewardPTContext wraps an iqlpref_amd RewardPT")
+        self.model, self.context_length = model, int(context_length)
+
+    def __call__(self, states, actions, timesteps, attn_mask=None, training=False):
+        dev = next(self.model.parameters()).device
+        L = states.shape[1]
+        if actions.shape[1] != L or timesteps.shape[1] != L or L > self.context_length:
+            raise ValueError("states, actions and timesteps must share one length <= context_length")
+        up = lambda x, dt: torch.as_tensor(np.ascontiguousarray(x), dtype=dt).to(dev)
+        v = self.model.window_values(up(states[0], torch.float32), up(actions[0], torch.float32),
+                                     up([0], torch.int64), up([L], torch.int32), self.context_length,
+                                     win_t0=up([int(timesteps[0, 0])], torch.int32))
+        return {"value": v.cpu().numpy().astype(np.float64).reshape(1, 1, 1)}, None
+
+
+# --------------------------------------------------------------------------- #
+# train (bref:870-1027)
+# --------------------------------------------------------------------------- #
+def _reward_model_missing(config: "TrainConfig"):
+    try:
+        import orbax.checkpoint  # noqa: F401
+    except ImportError:
+        raise ImportError(
+            f"custom_offline_bb.train: reward_model=None would read the Orbax checkpoint {config.reward_model_path!r}, "
+            "but orbax is not installed (and iqlpref_amd has no Orbax reader); pass reward_model= a callable with "
+            "the reference's call shape (RewardPTContext wraps a RewardPT)") from None
+    raise NotImplementedError(
+        "custom_offline_bb.train: iqlpref_amd has no Orbax checkpoint reader (load_PT); pass reward_model= a "
+        "callable with the reference's call shape (RewardPTContext wraps a RewardPT)")
+
+
+def _build_trainer(config: "TrainConfig", state_dim: int, action_dim: int, max_actions, min_actions,
+                   device: str) -> ImplicitQLearning:
+    """bref:923-962: nets on the CPU generator in the reference's order, then moved to the device."""
+    q_network = TwinQ(state_dim, action_dim).to(device)
+    v_network = ValueFunction(state_dim).to(device)
+    pol = DeterministicPolicy if config.iql_deterministic else GaussianPolicy
+    actor = pol(state_dim, action_dim, max_actions, min_actions, dropout=config.actor_dropout).to(device)
+    v_optimizer = torch.optim.Adam(v_network.parameters(), lr=config.vf_lr)
+    q_optimizer = torch.optim.Adam(q_network.parameters(), lr=config.qf_lr)
+    actor_optimizer = torch.optim.Adam(actor.parameters(), lr=config.actor_lr)
+    actor_lr_scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(actor_optimizer, config.update_steps)
+    return ImplicitQLearning(
+        max_actions=max_actions, min_actions=min_actions, actor=actor, actor_optimizer=actor_optimizer,
+        actor_lr_scheduler=actor_lr_scheduler, q_network=q_network, q_optimizer=q_optimizer, v_network=v_network,
+        v_optimizer=v_optimizer, iql_tau=config.iql_tau, beta=config.beta, gamma=config.gamma, tau=config.tau,
+        device=device, seed=config.train_seed)
+
+
+def train(config: TrainConfig, dataset=None, reward_model=None, move_stats=None, *,
+          logger: Optional[Callable[[Dict[str, float], int], None]] = None, perm=None,
+          device: Optional[str] = None, chunk: int = 2000):
+    """bref:870-1027 on the fused HIP step.
+
+    ``dataset``: a ``BBDataset``, a mapping of arrays or an HDF5 path (None: ``config.dataset_path``);
+    mappings and paths are wrapped with ``config.normalize_state`` / ``normalize_reward`` as bref:892-897.
+    ``reward_model``: a callable with the reference's call shape (``RewardPTContext``); the Orbax checkpoint
+    at ``reward_model_path`` cannot be read here.  ``move_stats``: the four movement statistics (None:
+    ``load_stats(config.move_stats_path)``).  ``logger(record, step)``: one call per ``wandb.log`` of bref
+    (default: wandb when importable, else print).  ``perm``: the block permutation (None: drawn with
+    ``torch.randperm`` on torch's global generator BEFORE the training seed is set, where the reference
+    builds its loader).
+
+    The steps are queued in chunks of at most ``chunk`` that end on evaluation boundaries; the indices of
+    a chunk are written on the device, and its losses come back to the host once, after the next chunk has
+    been queued.  Returns the trainer."""
+    if device is None:
+        device = D.local_device() or "cuda:0"
+    if reward_model is None:
+        _reward_model_missing(config)
+    if move_stats is None:
+        move_stats = load_stats(config.move_stats_path)
+    if dataset is None:
+        dataset = os.path.expanduser(config.dataset_path)
+    if not isinstance(dataset, BBDataset):
+        dataset = BBDataset(dataset, normalized_states=config.normalize_state,
+                            normalized_rewards=config.normalize_reward, device=device)
+    sampler = BlockEpochSampler(len(dataset), config.batch_size, perm=perm)  # bref:899-902 (before set_seed)
+    state_shape, action_shape = dataset.shapes()
+    state_dim, action_dim = state_shape[1], action_shape[1]
+    max_actions = dataset.max_actions().to(device)
+    min_actions = dataset.min_actions().to(device)
+
+    if config.checkpoints_path is not None:
+        print(f"Checkpoints path: {config.checkpoints_path}")
+        os.makedirs(config.checkpoints_path, exist_ok=True)
+        import yaml
+        with open(os.path.join(config.checkpoints_path, "config.yaml"), "w") as f:
+            yaml.safe_dump(asdict(config), f)
+
+    set_seed(config.train_seed)
+    trainer = _build_trainer(config, state_dim, action_dim, max_actions, min_actions, device)
+    replay_buffer = ReplayBuffer(state_dim, action_dim, len(dataset), device)
+    replay_buffer.load_dataset(dataset.transitions())
+
+    if logger is None:
+        try:
+            import wandb
+            wandb.init(config=asdict(config), project=config.project, group=config.group, name=config.name,
+                       id=str(uuid.uuid4()))
+            logger = lambda d, step: wandb.log(d, step=step)
+        except ImportError:
+            logger = lambda d, step: print(f"[{step}] " + " ".join(f"{n}={v:.5g}" for n, v in d.items()))
+
+    best_score, best_step = -np.inf, 0
+    pending = None  # (first step, device losses) of the chunk whose records are still to be logged
+
+    def flush():
+        nonlocal pending
+        if pending is None:
+            return
+        t0, losses = pending
+        pending = None
+        for i, (v, q, a) in enumerate(losses.cpu().numpy().tolist()):
+            logger({"value_loss": v, "q_loss": q, "actor_loss": a}, t0 + i)
+
+    total, every, t = int(config.update_steps), int(config.eval_every), 0
+    while t < total:
+        nxt = min(total, t + int(chunk), (t // every + 1) * every)
+        losses = trainer.train_epoch_steps(replay_buffer, sampler, t, nxt - t)
+        flush()
+        pending = (t, losses)
+        t = nxt
+        if t % every != 0:
+            continue
+        flush()
+        step = t - 1
+        eval_scores = bb_run_eval_IQL(actor=trainer.actor, num_episodes=config.eval_episodes, r_model=reward_model,
+                                      move_stats=move_stats, state_mean=dataset.state_mean(),
+                                      state_std=dataset.state_std(), seed=config.eval_seed + step, device=device)
+        mean_eval = eval_scores.mean()
+        logger({"evaluation_return": mean_eval}, step)
+        if mean_eval > best_score:
+            best_score, best_step = mean_eval, step
+            if config.checkpoints_path is not None:
+                torch.save(trainer.state_dict(), os.path.join(config.checkpoints_path, "best_model.pt"))
+        logger({"best_score_so_far": best_score}, step)
+        logger({"best_step_so_far": best_step}, step)
+        if config.checkpoints_path is not None:
+            torch.save(trainer.state_dict(), os.path.join(config.checkpoints_path, f"checkpoint_{step}.pt"))
+    flush()
+    return trainer

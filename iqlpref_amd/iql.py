@@ -772,11 +772,17 @@ class ImplicitQLearning:
     def train_steps(self, replay_buffer: ReplayBuffer, n_steps: int, batch_size: int, *,
                     indices: Optional[torch.Tensor] = None,
                     dropout_keep: Optional[torch.Tensor] = None,
-                    return_losses: bool = True, graph_unroll: Optional[int] = None):
+                    return_losses: bool = True, graph_unroll: Optional[int] = None,
+                    n_valid: Optional[torch.Tensor] = None):
         """ref:1533-1536 fused: ``n_steps`` x (sample + train) without host syncs.
 
         Returns a float32 device tensor [n_steps, 3] (value, q, actor loss per step)
-        when ``return_losses``; nothing is copied to the host."""
+        when ``return_losses``; nothing is copied to the host.
+
+        ``n_valid`` (int32 device tensor [n_steps], 1 <= n_valid <= batch_size): step i forms its
+        losses over the first ``n_valid[i]`` rows of its batch only and divides by that count
+        (``iqlhip_train_steps_valid``: the short last batch of an epoch of the BB flavour).  The
+        tuned step only; the general layer-wise step raises NotImplementedError."""
         self._ensure_handle(batch_size)
         self._refresh_lrs()
         losses = (torch.empty((n_steps, 3), dtype=torch.float32, device=self._dev)
@@ -789,7 +795,14 @@ class ImplicitQLearning:
             dropout_keep = self._check_keep(dropout_keep, n_steps, batch_size)
         v = replay_buffer.view()
         unroll = self._graph_unroll if graph_unroll is None else graph_unroll
-        if torch.cuda.current_device() == (self._dev.index or 0):  # (the context manager costs ~5 us a call)
+        if n_valid is not None:
+            if n_valid.dtype != torch.int32 or tuple(n_valid.shape) != (n_steps,) or n_valid.device.type != "cuda":
+                raise ValueError("n_valid must be an int32 device tensor [n_steps]")
+            n_valid = n_valid.contiguous()
+            with torch.cuda.device(self._dev):
+                check(self._lib.iqlhip_train_steps_valid(self._handle, C.byref(v), n_steps, ptr(indices), ptr(n_valid),
+                                                         ptr(dropout_keep), ptr(losses), unroll, stream_ptr()))
+        elif torch.cuda.current_device() == (self._dev.index or 0):  # (the context manager costs ~5 us a call)
             check(self._lib.iqlhip_train_steps(self._handle, C.byref(v), n_steps, ptr(indices),
                                                ptr(dropout_keep), ptr(losses), unroll, stream_ptr()))
         else:
