@@ -318,7 +318,13 @@ int iqlhip_train_batch(iqlhip_trainer *t, const float *s, const float *a, const 
  *   which = 0: q1..qE -> out[n][E]   (needs a; E = 2 for TwinQ)
  *   which = 1: v     -> out[n]
  *   which = 2: actor mean (tanh)  -> out[n][A]   (eval mode: no dropout)
- *   which = 3: q_target1..E -> out[n][E]   (needs a)                        */
+ *   which = 3: q_target1..E -> out[n][E]   (needs a)
+ * out is dense and row-major: critic e of row i is out[i * E + e].  Exactly the first n rows of out
+ * are written (a larger buffer keeps what it held beyond them) and n rows of s / a are read.  The
+ * actor runs in eval mode whatever the trainer's dropout_p and however many training steps have
+ * drawn masks: two calls on the same weights give the same bits.  which outside 0..3, n <= 0, a
+ * NULL s / out (or a NULL a where it is needed) return IQLHIP_ERR_INVALID and write nothing.
+ * Pinned over the whole shape envelope by tests/test_gpu_forward_envelope.py.                  */
 int iqlhip_forward(iqlhip_trainer *t, int32_t which, const float *s, const float *a,
                    int64_t n, float *out, void *stream);
 

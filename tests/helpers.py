@@ -279,3 +279,60 @@ def cvar_ref(preds, n_tail):
     want = tail.mean(axis=0)
     tol = n_tail * 2.0 ** -24 * np.abs(tail).mean(axis=0) + 2.0 ** -24 * np.abs(want)
     return want, tol
+
+
+# ---------------------------------------------------------------------------------------------
+# Envelope tests of the trainer's forward entry point (iqlhip_forward, tests/test_gpu_forward_envelope.py):
+# random networks under the trainer's state_dict names, a second bf16 restatement that accumulates in
+# fp64 (the yardstick of what two correct bf16 forwards may differ by) and bf16 ulps.
+# ---------------------------------------------------------------------------------------------
+def forward_nets(rng, S, A, H, n_hidden=2, n_critics=2, deterministic=False, dropout=None):
+    """(qf, vf, actor) fp32 parameter dicts under the state_dict names of TwinQ / EnsembleQ, ValueFunction
+    and the policies, from mlp_weights_for (O(1) activations), nn.Linear's [out, in] layout; every critic
+    is its own draw.  A Sequential with Dropout layers counts them in its indices (0, 3, 6 for 0, 2, 4)."""
+    def mlp(prefix, dims, step):
+        ws, bs = mlp_weights_for(rng, dims)
+        out = {}
+        for l, (w, b) in enumerate(zip(ws, bs)):
+            out[f"{prefix}{step * l}.weight"] = np.ascontiguousarray(w.T)
+            out[f"{prefix}{step * l}.bias"] = b
+        return out
+    hid = [H] * n_hidden
+    qf = {}
+    for e in range(n_critics):
+        qf.update(mlp(f"q{e + 1}.net.", [S + A] + hid + [1], 2))
+    vf = mlp("v.net.", [S] + hid + [1], 2)
+    actor = {} if deterministic else {"log_std": np.linspace(-0.5, 0.3, A).astype(np.float32)}
+    actor.update(mlp("net.net.", [S] + hid + [A], 2 if dropout is None else 3))
+    return qf, vf, actor
+
+
+def net_layers(params, prefix):
+    """([in, out] weights, biases) of the Linear layers under ``prefix``, as mlp_forward_ref takes them."""
+    keys = orc.linear_keys(params, prefix)
+    return [np.ascontiguousarray(params[w].T) for w, _ in keys], [params[b] for _, b in keys]
+
+
+def bf16_from_f64(y):
+    """fp64 -> bfloat16 in ONE nearest-even rounding (8 significant bits), returned as fp64.  (Through
+    fp32 it would be two roundings.)  Normal numbers only: nothing here comes near 2^-126."""
+    m, e = np.frexp(np.asarray(y, dtype=np.float64))
+    return np.ldexp(np.rint(m * 256.0) / 256.0, e)
+
+
+def mlp_forward_bf16_f64(x, params, prefix, out_act=None):
+    """The autocast MLP forward of oracle/iql_oracle.py:mlp_forward (eval mode) with the same operands
+    rounded to bf16, every sum in fp64 and each Linear's result rounded to bf16 once: a second correct
+    bf16 forward.  Where it and the oracle (fp32 sums) differ, a rounding tie fell the other way."""
+    h = orc.bf16(np.asarray(x, dtype=np.float32)).astype(np.float64)
+    keys = orc.linear_keys(params, prefix)
+    for l, (wk, bk) in enumerate(keys):
+        z = bf16_from_f64(h @ orc.bf16(params[wk]).astype(np.float64).T + orc.bf16(params[bk]).astype(np.float64))
+        h = np.maximum(z, 0.0) if l < len(keys) - 1 else z
+    return bf16_from_f64(np.tanh(h)) if out_act == "tanh" else h
+
+
+def bf16_ulp(x):
+    """Spacing of bfloat16 at |x|: 2^-7 of its binade."""
+    _, e = np.frexp(np.abs(np.asarray(x, dtype=np.float64)))
+    return np.ldexp(1.0, e - 1 - 7)

@@ -325,7 +325,8 @@ def test_state_dict_roundtrip_and_keys(gh):
 
 @pytest.mark.parametrize("mode", ["fp32", "bf16"])
 def test_per_op_forward_vectors(gh, mode):
-    """Module forward (fp32, outside autocast) and trainer.forward (inside) vs G1 vectors."""
+    """Module forward (fp32, outside autocast) and trainer.forward (inside) vs G1 vectors.
+    (trainer.forward over its whole envelope, both precisions: tests/test_gpu_forward_envelope.py)"""
     d = np.load(helpers.GOLDEN + "/per_op.npz")
     for tag, (S, A) in (("S17A6", (17, 6)), ("S29A8", (29, 8)), ("S45A24", (45, 24))):
         get = lambda net: {k.split("/", 2)[2]: d[k] for k in d.files if k.startswith(f"{tag}/{net}/")}
@@ -575,6 +576,7 @@ def test_general_step_seeds_checkpoint_and_forward(gh, tmp_path):
     np.testing.assert_array_equal(a, b)
     assert torch.equal(alone[0]._params, fresh._params)
     # forward passes on the live weights against the oracle on the same weights
+    # (with derived bounds and over the kernel's whole envelope: tests/test_gpu_forward_envelope.py)
     tr = alone[1]
     sdn = lambda m: {k: v.detach().cpu().numpy() for k, v in m.state_dict().items()}
     rng = np.random.default_rng(0)
