@@ -261,7 +261,8 @@ int iqlhip_train_steps(iqlhip_trainer *t, const iqlhip_replay_view *view, int64_
  * k_backward instantiation of its own: calls without counts run the kernels they always ran).  On
  * the general layer-wise step, or at precision bf16, a non-NULL n_valid returns
  * IQLHIP_ERR_UNSUPPORTED before anything is launched (the counts live on the device: the call
- * cannot see whether they all equal batch_size); seed groups take no counts.                    */
+ * cannot see whether they all equal batch_size).  Seed groups of such trainers take counts through
+ * iqlhip_group_train_steps_valid.                                                               */
 int iqlhip_train_steps_valid(iqlhip_trainer *t, const iqlhip_replay_view *view, int64_t n_steps,
                              const int64_t *idx, const int32_t *n_valid, const uint8_t *dropout_keep,
                              float *losses_out, int32_t graph_unroll, void *stream);
@@ -287,6 +288,20 @@ int iqlhip_group_destroy(iqlhip_group *g);
 int iqlhip_group_train_steps(iqlhip_group *g, const iqlhip_replay_view *views, int64_t n_steps,
                              const int64_t *const *idx, const uint8_t *const *dropout_keep,
                              float *const *losses_out, int32_t graph_unroll, void *stream);
+
+/* iqlhip_group_train_steps with per-step valid-row counts: n_valid is NULL as a whole (this IS
+ * iqlhip_group_train_steps, bit for bit) or an array of K entries, each NULL (that member uses its whole
+ * batch in every step) or a device int32[n_steps] with the meaning and the clamping of
+ * iqlhip_train_steps_valid; members may share one array.  Every member stays bit-identical to the same
+ * trainer stepped alone by iqlhip_train_steps_valid.  With any non-NULL entry the one launch of k_backward
+ * is its counted instantiation for all members; the group's captured graph is keyed on that, and a call
+ * with counts never continues the previous call (its arguments are always sent).  Plain launches and graph
+ * replay.  A non-NULL entry for a group on the general layer-wise step, or at precision bf16, returns
+ * IQLHIP_ERR_UNSUPPORTED before anything is launched.                                               */
+int iqlhip_group_train_steps_valid(iqlhip_group *g, const iqlhip_replay_view *views, int64_t n_steps,
+                                   const int64_t *const *idx, const int32_t *const *n_valid,
+                                   const uint8_t *const *dropout_keep, float *const *losses_out,
+                                   int32_t graph_unroll, void *stream);
 
 /* A HIP stream confined to one slice of the compute units: bit i of the CU mask belongs to
  * slice i % n_slices.  The mask enumerates the CUs round-robin over the 8 XCDs, so two slices
@@ -496,6 +511,16 @@ int iqlhip_np_randint(uint32_t *state, const int64_t *hi, int32_t K, int32_t bat
  * iqlhip_train_steps_valid takes.  One launch on `stream`, no synchronisation.                    */
 int iqlhip_block_epoch_indices(const int64_t *perm, int64_t n_rows, int32_t batch, int64_t t0,
                                int64_t n_steps, int64_t *idx, int32_t *n_valid, void *stream);
+
+/* The same walk for the K members of a seed group, 1 <= K <= IQLHIP_MAX_GROUP, in ONE launch: perm and idx
+ * are HOST arrays of K device pointers (read during the call only; they travel by value in the kernel's
+ * argument block), idx[k] receives what iqlhip_block_epoch_indices writes for perm[k].  All members walk
+ * the same n_rows and batch, so the short slot falls on the same step for all of them: n_valid is ONE
+ * device int32 [n_steps], what every entry of iqlhip_group_train_steps_valid's n_valid may point to.
+ * perm (or an entry of it) may be NULL only when there is no whole block.  No synchronisation.        */
+int iqlhip_block_epoch_indices_group(const int64_t *const *perm, int64_t n_rows, int32_t batch, int64_t t0,
+                                     int64_t n_steps, int64_t *const *idx, int32_t *n_valid, int32_t K,
+                                     void *stream);
 
 /* ------------------------------------------------------------------------ */
 /* Posterior relabel of algorithms/custom_offline/iql_br.py:179-253: per       */

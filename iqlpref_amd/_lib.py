@@ -127,6 +127,8 @@ SYMBOLS = {
     "iqlhip_group_destroy": (C.c_int, [P]),
     "iqlhip_group_train_steps": (C.c_int, [P, C.POINTER(ReplayView), C.c_int64, C.POINTER(P), C.POINTER(P),
                                            C.POINTER(P), C.c_int32, P]),
+    "iqlhip_group_train_steps_valid": (C.c_int, [P, C.POINTER(ReplayView), C.c_int64, C.POINTER(P), C.POINTER(P),
+                                                 C.POINTER(P), C.POINTER(P), C.c_int32, P]),
     "iqlhip_group_set_timing": (C.c_int, [P, C.c_int32]),
     "iqlhip_group_get_timing": (C.c_int, [P, C.POINTER(C.c_double * 3), C.POINTER(C.c_int64)]),
     "iqlhip_trainer_launch_counts": (C.c_int, [P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
@@ -145,6 +147,8 @@ SYMBOLS = {
                                             P, C.c_size_t, P, P]),
     "iqlhip_np_randint": (C.c_int, [P, P, C.c_int32, C.c_int32, C.c_int64, P, P]),
     "iqlhip_block_epoch_indices": (C.c_int, [P, C.c_int64, C.c_int32, C.c_int64, C.c_int64, P, P, P]),
+    "iqlhip_block_epoch_indices_group": (C.c_int, [C.POINTER(P), C.c_int64, C.c_int32, C.c_int64, C.c_int64,
+                                                   C.POINTER(P), P, C.c_int32, P]),
     "iqlhip_posterior_choice_workspace_bytes": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_size_t)]),
     "iqlhip_posterior_choice": (C.c_int, [P, P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, P, P, P, C.c_size_t, P]),
     "iqlhip_step_cost": (C.c_int, [C.POINTER(TrainerConfig), C.POINTER(C.c_double),

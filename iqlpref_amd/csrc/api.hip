@@ -79,6 +79,8 @@ hipError_t launch_pt_general(const iqlhip_pt_model &m, const float *obs, const f
                              int64_t n_win, int ql, float *ws, int64_t chunk, float *out, hipStream_t st);
 hipError_t launch_block_epoch(const int64_t *perm, int64_t n_rows, int batch, int64_t t0, int64_t n_steps, int64_t *idx,
                               int32_t *n_valid, hipStream_t st);
+hipError_t launch_block_epoch_group(const int64_t *const *perm, int64_t n_rows, int batch, int64_t t0, int64_t n_steps,
+                                    int64_t *const *idx, int32_t *n_valid, int K, hipStream_t st);
 hipError_t launch_np_randint(uint32_t *state, const int64_t *hi, int K, int64_t total, int64_t *const *out,
                              hipStream_t st);
 size_t choice_workspace_bytes(int64_t N, int n);
@@ -1233,6 +1235,7 @@ struct iqlhip_group {
   int harg_head = 0;
   hipGraphExec_t gexec = nullptr;
   int graph_unroll = 0;
+  bool graph_counts = false;  // `gexec` holds the counted k_backward (iqlhip_group_train_steps_valid)
   hipStream_t cap_stream = nullptr;
   Throttle throttle;
   DevArgs dev_args[IQLHIP_MAX_GROUP];  // what the device copies hold (see `continues`)
@@ -1402,11 +1405,11 @@ extern "C" int iqlhip_group_destroy(iqlhip_group *g) {
   return 0;
 }
 
-static int group_enqueue_step(iqlhip_group *g, hipStream_t st) {
+static int group_enqueue_step(iqlhip_group *g, hipStream_t st, bool counts) {
   iqlhip_trainer *t0 = g->tr[0];
   if (!t0->D.prefetch) HIP_TRY(launch_stage(t0->bf16, t0->D, g->gdesc, g->gargs, g->gctr, g->K, st));
   HIP_TRY(launch_forward(t0->bf16, t0->D, g->gdesc, g->gargs, g->gctr, g->K, st));
-  HIP_TRY(launch_backward(t0->bf16, t0->D, g->gdesc, g->gargs, g->gctr, g->K, st));
+  HIP_TRY(launch_backward(t0->bf16, t0->D, g->gdesc, g->gargs, g->gctr, g->K, st, counts));
   HIP_TRY(launch_update(t0->bf16, g->gdesc, g->gargs, g->gctr, g->gitems, g->n_items, g->K, st));
   return 0;
 }
@@ -1414,8 +1417,25 @@ static int group_enqueue_step(iqlhip_group *g, hipStream_t st) {
 extern "C" int iqlhip_group_train_steps(iqlhip_group *g, const iqlhip_replay_view *views, int64_t n_steps,
                                         const int64_t *const *idx, const uint8_t *const *dropout_keep,
                                         float *const *losses_out, int32_t graph_unroll, void *stream) {
+  return iqlhip_group_train_steps_valid(g, views, n_steps, idx, nullptr, dropout_keep, losses_out, graph_unroll, stream);
+}
+
+extern "C" int iqlhip_group_train_steps_valid(iqlhip_group *g, const iqlhip_replay_view *views, int64_t n_steps,
+                                              const int64_t *const *idx, const int32_t *const *n_valid,
+                                              const uint8_t *const *dropout_keep, float *const *losses_out,
+                                              int32_t graph_unroll, void *stream) {
   if (!g || !views) return fail(IQLHIP_ERR_INVALID, "null argument");
   if (n_steps < 0) return fail(IQLHIP_ERR_INVALID, "n_steps must be >= 0");
+  // any member with counts: the counted k_backward for the whole launch (a member without uses its whole batch)
+  bool counts = false;
+  for (int k = 0; n_valid && k < g->K; ++k) counts = counts || n_valid[k] != nullptr;
+  if (counts && g->deep)  // (as run_steps: the counts live on the device, the call cannot see whether they matter)
+    return fail(IQLHIP_ERR_UNSUPPORTED,
+                "per-step valid-row counts (a short batch) run on the tuned step only (n_hidden 2, hidden_dim 64 / "
+                "128 / 256); this group (n_hidden %d, hidden_dim %d) runs the general layer-wise step",
+                n_hidden(g->tr[0]->cfg), g->tr[0]->cfg.hidden_dim);
+  if (counts && g->tr[0]->bf16)
+    return fail(IQLHIP_ERR_UNSUPPORTED, "per-step valid-row counts (a short batch) are built for precision fp32 only");
   for (int k = 0; k < g->K; ++k) {
     const iqlhip_replay_view &v = views[k];
     const iqlhip_trainer_config &c = g->tr[k]->cfg;
@@ -1462,6 +1482,7 @@ extern "C" int iqlhip_group_train_steps(iqlhip_group *g, const iqlhip_replay_vie
     a.idx_mode = a.idx ? 1 : 0;
     a.drop_keep = dropout_keep ? dropout_keep[k] : nullptr;
     a.losses_out = losses_out ? losses_out[k] : nullptr;
+    a.n_valid = n_valid ? n_valid[k] : nullptr;  // (`continues` is false with counts on either side)
     a.base_step = t->total_it;
     a.lr_q = t->lr_q, a.lr_v = t->lr_v, a.lr_a_base = t->lr_a_base;
     a.n_steps = n_steps;
@@ -1495,7 +1516,7 @@ extern "C" int iqlhip_group_train_steps(iqlhip_group *g, const iqlhip_replay_vie
       HIP_TRY(hipEventRecord(g->ev[0], st));
       HIP_TRY(launch_forward(t0->bf16, t0->D, g->gdesc, g->gargs, g->gctr, g->K, st));
       HIP_TRY(hipEventRecord(g->ev[1], st));
-      HIP_TRY(launch_backward(t0->bf16, t0->D, g->gdesc, g->gargs, g->gctr, g->K, st));
+      HIP_TRY(launch_backward(t0->bf16, t0->D, g->gdesc, g->gargs, g->gctr, g->K, st, counts));
       HIP_TRY(hipEventRecord(g->ev[2], st));
       HIP_TRY(launch_update(t0->bf16, g->gdesc, g->gargs, g->gctr, g->gitems, g->n_items, g->K, st));
       HIP_TRY(hipEventRecord(g->ev[3], st));
@@ -1516,7 +1537,8 @@ extern "C" int iqlhip_group_train_steps(iqlhip_group *g, const iqlhip_replay_vie
     return 0;
   }
   if (graph_unroll > 0 && n_steps >= graph_unroll) {
-    if (!g->gexec || g->graph_unroll != graph_unroll) {
+    // (the graph holds either the counted or the plain k_backward)
+    if (!g->gexec || g->graph_unroll != graph_unroll || g->graph_counts != counts) {
       if (g->gexec) {
         (void)hipGraphExecDestroy(g->gexec);
         g->gexec = nullptr;
@@ -1525,13 +1547,13 @@ extern "C" int iqlhip_group_train_steps(iqlhip_group *g, const iqlhip_replay_vie
       if (!g->cap_stream) HIP_TRY(capture_stream(&g->cap_stream));
       HIP_TRY(hipStreamBeginCapture(g->cap_stream, hipStreamCaptureModeThreadLocal));
       int rc = 0;
-      for (int u = 0; u < graph_unroll && !rc; ++u) rc = group_enqueue_step(g, g->cap_stream);
+      for (int u = 0; u < graph_unroll && !rc; ++u) rc = group_enqueue_step(g, g->cap_stream, counts);
       hipError_t ce = hipStreamEndCapture(g->cap_stream, &gr);
       if (rc) return rc;
       HIP_TRY(ce);
       HIP_TRY(hipGraphInstantiate(&g->gexec, gr, nullptr, nullptr, 0));
       (void)hipGraphDestroy(gr);
-      g->graph_unroll = graph_unroll;
+      g->graph_unroll = graph_unroll, g->graph_counts = counts;
     }
     for (; done + graph_unroll <= n_steps; done += graph_unroll) {
       HIP_TRY(hipGraphLaunch(g->gexec, st));
@@ -1540,7 +1562,7 @@ extern "C" int iqlhip_group_train_steps(iqlhip_group *g, const iqlhip_replay_vie
     }
   }
   for (; done < n_steps; ++done) {
-    if (int rc = group_enqueue_step(g, st)) return rc;
+    if (int rc = group_enqueue_step(g, st, counts)) return rc;
     g->n_eager++;
     HIP_TRY(g->throttle.queued(3, st));
   }
@@ -1721,6 +1743,25 @@ extern "C" int iqlhip_block_epoch_indices(const int64_t *perm, int64_t n_rows, i
   if (!perm && n_rows >= batch) return fail(IQLHIP_ERR_INVALID, "null perm with %lld whole blocks", (long long)(n_rows / batch));
   if (n_steps == 0) return 0;
   HIP_TRY(launch_block_epoch(perm, n_rows, batch, t0, n_steps, idx, n_valid, (hipStream_t)stream));
+  return 0;
+}
+
+extern "C" int iqlhip_block_epoch_indices_group(const int64_t *const *perm, int64_t n_rows, int32_t batch, int64_t t0,
+                                                int64_t n_steps, int64_t *const *idx, int32_t *n_valid, int32_t K,
+                                                void *stream) {
+  if (!idx || !n_valid) return fail(IQLHIP_ERR_INVALID, "null argument");
+  if (K < 1 || K > IQLHIP_MAX_GROUP) return fail(IQLHIP_ERR_INVALID, "K = %d: 1..%d members", K, IQLHIP_MAX_GROUP);
+  if (batch < 1) return fail(IQLHIP_ERR_INVALID, "batch = %d must be >= 1", batch);
+  if (n_rows < 1) return fail(IQLHIP_ERR_INVALID, "n_rows = %lld must be >= 1", (long long)n_rows);
+  if (t0 < 0 || n_steps < 0)
+    return fail(IQLHIP_ERR_INVALID, "t0 = %lld and n_steps = %lld must be >= 0", (long long)t0, (long long)n_steps);
+  for (int k = 0; k < K; ++k) {
+    if (!idx[k]) return fail(IQLHIP_ERR_INVALID, "null idx[%d]", k);
+    if ((!perm || !perm[k]) && n_rows >= batch)
+      return fail(IQLHIP_ERR_INVALID, "null perm[%d] with %lld whole blocks", k, (long long)(n_rows / batch));
+  }
+  if (n_steps == 0) return 0;
+  HIP_TRY(launch_block_epoch_group(perm, n_rows, batch, t0, n_steps, idx, n_valid, K, (hipStream_t)stream));
   return 0;
 }
 

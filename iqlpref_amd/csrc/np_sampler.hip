@@ -76,11 +76,49 @@ __global__ __launch_bounds__(256) void k_block_epoch(const int64_t *__restrict__
   if (j == 0) n_valid[i] = slot < nb ? B : (int32_t)tail;
 }
 
+// The same walk for the K members of a seed group in ONE launch: blockIdx.y = member, its permutation and its
+// index array passed by value in the argument block (as NpDrawArgs).  All members walk the same N and B, so the
+// valid-row counts are one array, written by member 0.
+struct BlockEpochGroupArgs {
+  const int64_t *perm[IQLHIP_MAX_GROUP];
+  int64_t *idx[IQLHIP_MAX_GROUP];
+};
+
+__global__ __launch_bounds__(256) void k_block_epoch_group(BlockEpochGroupArgs a, int64_t N, int B, int64_t t0,
+                                                            int64_t n_steps, int32_t *__restrict__ n_valid) {
+  const int k = blockIdx.y;
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= n_steps * B) return;
+  const int64_t i = e / B, j = e - i * B;
+  const int64_t nb = N / B, tail = N - nb * B, slots = nb + (tail ? 1 : 0);
+  const int64_t slot = (t0 + i) % slots;
+  int64_t row;
+  if (slot < nb) {
+    const int64_t p = a.perm[k][slot];
+    row = (p < 0 ? 0 : (p >= nb ? nb - 1 : p)) * B + j;
+  } else {
+    row = nb * B + j;
+    if (row > N - 1) row = N - 1;
+  }
+  a.idx[k][e] = row;
+  if (k == 0 && j == 0) n_valid[i] = slot < nb ? B : (int32_t)tail;
+}
+
 hipError_t launch_block_epoch(const int64_t *perm, int64_t n_rows, int batch, int64_t t0, int64_t n_steps, int64_t *idx,
                               int32_t *n_valid, hipStream_t st) {
   const int64_t total = n_steps * batch;
   hipLaunchKernelGGL(k_block_epoch, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, perm, n_rows, batch, t0,
                      n_steps, idx, n_valid);
+  return hipGetLastError();
+}
+
+hipError_t launch_block_epoch_group(const int64_t *const *perm, int64_t n_rows, int batch, int64_t t0, int64_t n_steps,
+                                    int64_t *const *idx, int32_t *n_valid, int K, hipStream_t st) {
+  BlockEpochGroupArgs a = {};
+  for (int k = 0; k < K; ++k) a.perm[k] = perm ? perm[k] : nullptr, a.idx[k] = idx[k];
+  const int64_t total = n_steps * batch;
+  hipLaunchKernelGGL(k_block_epoch_group, dim3((unsigned)((total + 255) / 256), K), dim3(256), 0, st, a, n_rows, batch,
+                     t0, n_steps, n_valid);
   return hipGetLastError();
 }
 

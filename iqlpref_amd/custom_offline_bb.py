@@ -24,14 +24,20 @@ to a goal among drifting obstacles, rewarded by the preference model over a roll
 the same ``default_rng(seed)`` calls in the same order with the same float arithmetic, so that equal
 actions give equal states and returns.
 
+``train(seeds_per_gpu=K)`` steps K seeds side by side on one GPU as one ``SeedGroup``: each seed walks its
+own block permutation (``BlockEpochSamplerGroup`` writes the K index arrays and the one shared count array
+with one launch of ``iqlhip_block_epoch_indices_group``), and ``iqlhip_group_train_steps_valid`` forms the
+short step of every member over its valid rows.  Every seed is bit-identical to ``train()`` of that seed
+alone.
+
 Not built: the Orbax reward-model reader (``load_PT``); HDF5 is read only when ``h5py`` is there.
-Seed groups, sweeps and bf16 are not offered for this flavour.
+Sweeps and bf16 are not offered for this flavour.
 """
 import ctypes as C
 import os
 import uuid
 from dataclasses import asdict, dataclass
-from typing import Any, Callable, Dict, Mapping, Optional, Tuple
+from typing import Any, Callable, Dict, List, Mapping, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -235,6 +241,58 @@ class BlockEpochSampler:
                                                  self.batch_size, int(t0), int(n_steps), ptr(idx), ptr(valid),
                                                  stream_ptr()))
         return idx, valid
+
+
+class BlockEpochSamplerGroup:
+    """The samplers of the K members of a seed group: 1..``MAX_GROUP`` ``BlockEpochSampler`` of equal
+    ``n_rows`` and ``batch_size``, each with its own permutation.  All members walk epochs of the same
+    length, so the short slot falls on the same step for all of them and one count array serves the group."""
+
+    def __init__(self, samplers: Sequence[BlockEpochSampler]):
+        self.samplers = list(samplers)
+        if not 1 <= len(self.samplers) <= _lib.MAX_GROUP:
+            raise ValueError(f"a sampler group holds 1..{_lib.MAX_GROUP} samplers (got {len(self.samplers)})")
+        self.n_rows, self.batch_size = self.samplers[0].n_rows, self.samplers[0].batch_size
+        for k, sm in enumerate(self.samplers):
+            if (sm.n_rows, sm.batch_size) != (self.n_rows, self.batch_size):
+                raise ValueError(f"sampler {k} walks {sm.n_rows} rows in batches of {sm.batch_size}, sampler 0 "
+                                 f"{self.n_rows} in batches of {self.batch_size}: a group shares one epoch shape")
+        self._dev_perms = None
+
+    @classmethod
+    def draw(cls, n_rows: int, batch_size: int, n_members: int, perm=None) -> "BlockEpochSamplerGroup":
+        """``perm=None``: ``n_members`` permutations drawn in member order from torch's global generator
+        (what as many reference processes would each draw when they build their loader); else a sequence of
+        ``n_members`` permutations."""
+        K = int(n_members)
+        if perm is None:
+            return cls([BlockEpochSampler(n_rows, batch_size) for _ in range(K)])
+        perms = list(perm)
+        if len(perms) != K or any(np.ndim(p) != 1 for p in perms):
+            raise ValueError(f"perm must be a sequence of {K} block permutations, one per seed")
+        return cls([BlockEpochSampler(n_rows, batch_size, perm=p) for p in perms])
+
+    def __len__(self):
+        return len(self.samplers)
+
+    def device_indices(self, t0: int, n_steps: int, device) -> Tuple[List[torch.Tensor], torch.Tensor]:
+        """(K int64 [n_steps, batch_size] tensors, one int32 [n_steps] count tensor): what
+        ``BlockEpochSampler.device_indices`` gives for every member, from ONE launch of
+        ``iqlhip_block_epoch_indices_group`` on the current stream."""
+        lib = _lib.load()
+        dev = _lib.require_gpu(device)
+        K = len(self.samplers)
+        if self._dev_perms is None or self._dev_perms.device != dev:
+            self._dev_perms = torch.stack([sm.perm for sm in self.samplers]).to(dev)  # [K, n_blocks]
+        area = torch.empty((K, n_steps, self.batch_size), dtype=torch.int64, device=dev)
+        valid = torch.empty(n_steps, dtype=torch.int32, device=dev)
+        whole = self.samplers[0].n_blocks > 0
+        perms = (C.c_void_p * K)(*[self._dev_perms[k].data_ptr() if whole else None for k in range(K)])
+        outs = (C.c_void_p * K)(*[area[k].data_ptr() for k in range(K)])
+        with torch.cuda.device(dev):
+            check(lib.iqlhip_block_epoch_indices_group(perms, self.n_rows, self.batch_size, int(t0), int(n_steps),
+                                                       outs, ptr(valid), K, stream_ptr()))
+        return [area[k] for k in range(K)], valid
 
 
 # --------------------------------------------------------------------------- #
@@ -456,8 +514,13 @@ def _reward_model_missing(config: "TrainConfig"):
 
 
 def _build_trainer(config: "TrainConfig", state_dim: int, action_dim: int, max_actions, min_actions,
-                   device: str) -> ImplicitQLearning:
-    """bref:923-962: nets on the CPU generator in the reference's order, then moved to the device."""
+                   device: str, seed: Optional[int] = None) -> ImplicitQLearning:
+    """bref:923-962: nets on the CPU generator in the reference's order, then moved to the device.  ``seed``
+    (a member of a seed group): the nets are built right after ``torch.manual_seed(seed)``."""
+    if seed is None:
+        seed = config.train_seed
+    else:
+        torch.manual_seed(seed)
     q_network = TwinQ(state_dim, action_dim).to(device)
     v_network = ValueFunction(state_dim).to(device)
     pol = DeterministicPolicy if config.iql_deterministic else GaussianPolicy
@@ -470,11 +533,20 @@ def _build_trainer(config: "TrainConfig", state_dim: int, action_dim: int, max_a
         max_actions=max_actions, min_actions=min_actions, actor=actor, actor_optimizer=actor_optimizer,
         actor_lr_scheduler=actor_lr_scheduler, q_network=q_network, q_optimizer=q_optimizer, v_network=v_network,
         v_optimizer=v_optimizer, iql_tau=config.iql_tau, beta=config.beta, gamma=config.gamma, tau=config.tau,
-        device=device, seed=config.train_seed)
+        device=device, seed=seed)
+
+
+def group_seeds(train_seed: int, seeds_per_gpu: int) -> List[int]:
+    """The seeds of the K runs of this rank: ``rank_seed(train_seed, K) + k``."""
+    K = int(seeds_per_gpu)
+    if not 1 <= K <= _lib.MAX_GROUP:
+        raise ValueError(f"seeds_per_gpu must be in 1..{_lib.MAX_GROUP}")
+    first = D.rank_seed(train_seed, K)
+    return [first + k for k in range(K)]
 
 
 def train(config: TrainConfig, dataset=None, reward_model=None, move_stats=None, *,
-          logger: Optional[Callable[[Dict[str, float], int], None]] = None, perm=None,
+          logger: Optional[Callable[[Dict[str, float], int], None]] = None, perm=None, seeds_per_gpu: int = 1,
           device: Optional[str] = None, chunk: int = 2000):
     """bref:870-1027 on the fused HIP step.
 
@@ -489,7 +561,19 @@ def train(config: TrainConfig, dataset=None, reward_model=None, move_stats=None,
 
     The steps are queued in chunks of at most ``chunk`` that end on evaluation boundaries; the indices of
     a chunk are written on the device, and its losses come back to the host once, after the next chunk has
-    been queued.  Returns the trainer."""
+    been queued.  Returns the trainer.
+
+    ``seeds_per_gpu`` = K > 1 (the loop of ``custom_offline.train``): seed k is ``rank_seed(train_seed, K) + k``, with its own nets (built right after
+    ``torch.manual_seed(seed)``), its own block permutation (``perm``: a sequence of K permutations; None: K
+    draws in member order from torch's global generator, before any seed is set), its own evaluations
+    (``seed = eval_seed + step``, as K separate runs), best score and checkpoints under ``seed_<seed>/``, and a
+    ``seed`` entry in its logger records; all K share one buffer and step as one ``SeedGroup`` with the indices
+    of one K-way launch.  Every seed is bit-identical to ``train()`` of that seed alone with its permutation.
+    Returns the list of K trainers."""
+    K = int(seeds_per_gpu)
+    seeds = group_seeds(config.train_seed, K)
+    if K == 1:
+        seeds = [config.train_seed]  # (one seed per GPU: every rank trains train_seed, as before)
     if device is None:
         device = D.local_device() or "cuda:0"
     if reward_model is None:
@@ -501,35 +585,54 @@ def train(config: TrainConfig, dataset=None, reward_model=None, move_stats=None,
     if not isinstance(dataset, BBDataset):
         dataset = BBDataset(dataset, normalized_states=config.normalize_state,
                             normalized_rewards=config.normalize_reward, device=device)
-    sampler = BlockEpochSampler(len(dataset), config.batch_size, perm=perm)  # bref:899-902 (before set_seed)
+    # bref:899-902: the loader is built, and its permutation drawn, before set_seed
+    if K == 1:
+        sampler = BlockEpochSampler(len(dataset), config.batch_size, perm=perm)
+    else:
+        samplers = BlockEpochSamplerGroup.draw(len(dataset), config.batch_size, K, perm)
     state_shape, action_shape = dataset.shapes()
     state_dim, action_dim = state_shape[1], action_shape[1]
     max_actions = dataset.max_actions().to(device)
     min_actions = dataset.min_actions().to(device)
 
+    ckpt_dirs: List[Optional[str]] = [None] * K
     if config.checkpoints_path is not None:
         print(f"Checkpoints path: {config.checkpoints_path}")
         os.makedirs(config.checkpoints_path, exist_ok=True)
         import yaml
         with open(os.path.join(config.checkpoints_path, "config.yaml"), "w") as f:
             yaml.safe_dump(asdict(config), f)
+        for k in range(K):
+            ckpt_dirs[k] = config.checkpoints_path if K == 1 else os.path.join(config.checkpoints_path,
+                                                                               f"seed_{seeds[k]}")
+            os.makedirs(ckpt_dirs[k], exist_ok=True)
 
-    set_seed(config.train_seed)
-    trainer = _build_trainer(config, state_dim, action_dim, max_actions, min_actions, device)
+    set_seed(seeds[0])  # np, random, torch, PYTHONHASHSEED
+    trainers = [_build_trainer(config, state_dim, action_dim, max_actions, min_actions, device,
+                               seed=None if K == 1 else s) for s in seeds]
+    group = None
+    if K > 1:
+        from .multi import SeedGroup
+        group = SeedGroup(trainers)
     replay_buffer = ReplayBuffer(state_dim, action_dim, len(dataset), device)
     replay_buffer.load_dataset(dataset.transitions())
+    if K > 1 and samplers.n_rows != replay_buffer.index_bound():
+        raise ValueError(f"the samplers walk {samplers.n_rows} rows, the buffer holds {replay_buffer.index_bound()}")
 
     if logger is None:
         try:
             import wandb
             wandb.init(config=asdict(config), project=config.project, group=config.group, name=config.name,
                        id=str(uuid.uuid4()))
-            logger = lambda d, step: wandb.log(d, step=step)
+            logger = (lambda d, step: wandb.log(d, step=step)) if K == 1 else \
+                (lambda d, step: wandb.log({f"seed{int(d['seed'])}/{n}": v for n, v in d.items() if n != "seed"},
+                                           step=step))
         except ImportError:
             logger = lambda d, step: print(f"[{step}] " + " ".join(f"{n}={v:.5g}" for n, v in d.items()))
+    tag = (lambda rec, k: rec) if K == 1 else (lambda rec, k: dict(rec, seed=seeds[k]))
 
-    best_score, best_step = -np.inf, 0
-    pending = None  # (first step, device losses) of the chunk whose records are still to be logged
+    best_score, best_step = [-np.inf] * K, [0] * K
+    pending = None  # (first step, [K] device losses) of the chunk whose records are still to be logged
 
     def flush():
         nonlocal pending
@@ -537,32 +640,46 @@ def train(config: TrainConfig, dataset=None, reward_model=None, move_stats=None,
             return
         t0, losses = pending
         pending = None
-        for i, (v, q, a) in enumerate(losses.cpu().numpy().tolist()):
-            logger({"value_loss": v, "q_loss": q, "actor_loss": a}, t0 + i)
+        for k, arr in enumerate(l.cpu().numpy() for l in losses):
+            for i, (v, q, a) in enumerate(arr.tolist()):
+                logger(tag({"value_loss": v, "q_loss": q, "actor_loss": a}, k), t0 + i)
 
     total, every, t = int(config.update_steps), int(config.eval_every), 0
     while t < total:
         nxt = min(total, t + int(chunk), (t // every + 1) * every)
-        losses = trainer.train_epoch_steps(replay_buffer, sampler, t, nxt - t)
+        if group is None:
+            losses = [trainers[0].train_epoch_steps(replay_buffer, sampler, t, nxt - t)]
+        else:
+            idx, valid = samplers.device_indices(t, nxt - t, device)
+            losses = group.train_steps(replay_buffer, nxt - t, config.batch_size, indices=idx, n_valid=valid,
+                                       return_losses=True)
         flush()
         pending = (t, losses)
         t = nxt
         if t % every != 0:
             continue
         flush()
+        if group is not None:
+            group.synchronize()
         step = t - 1
-        eval_scores = bb_run_eval_IQL(actor=trainer.actor, num_episodes=config.eval_episodes, r_model=reward_model,
-                                      move_stats=move_stats, state_mean=dataset.state_mean(),
-                                      state_std=dataset.state_std(), seed=config.eval_seed + step, device=device)
-        mean_eval = eval_scores.mean()
-        logger({"evaluation_return": mean_eval}, step)
-        if mean_eval > best_score:
-            best_score, best_step = mean_eval, step
-            if config.checkpoints_path is not None:
-                torch.save(trainer.state_dict(), os.path.join(config.checkpoints_path, "best_model.pt"))
-        logger({"best_score_so_far": best_score}, step)
-        logger({"best_step_so_far": best_step}, step)
-        if config.checkpoints_path is not None:
-            torch.save(trainer.state_dict(), os.path.join(config.checkpoints_path, f"checkpoint_{step}.pt"))
+        for k, trainer in enumerate(trainers):
+            log = lambda d: logger(tag(d, k), step)
+            eval_scores = bb_run_eval_IQL(actor=trainer.actor, num_episodes=config.eval_episodes, r_model=reward_model,
+                                          move_stats=move_stats, state_mean=dataset.state_mean(),
+                                          state_std=dataset.state_std(), seed=config.eval_seed + step, device=device)
+            mean_eval = eval_scores.mean()
+            log({"evaluation_return": mean_eval})
+            if mean_eval > best_score[k]:
+                best_score[k], best_step[k] = mean_eval, step
+                if ckpt_dirs[k] is not None:
+                    torch.save(trainer.state_dict(), os.path.join(ckpt_dirs[k], "best_model.pt"))
+            log({"best_score_so_far": best_score[k]})
+            log({"best_step_so_far": best_step[k]})
+            if ckpt_dirs[k] is not None:
+                torch.save(trainer.state_dict(), os.path.join(ckpt_dirs[k], f"checkpoint_{step}.pt"))
     flush()
-    return trainer
+    if group is not None:
+        group.synchronize()
+        group.close()
+        return trainers
+    return trainers[0]

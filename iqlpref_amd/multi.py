@@ -8,7 +8,7 @@ is bit-identical to running it alone.  Two execution modes:
 
 ``mode="group"``
     ONE launch sequence steps all seeds: every kernel of the step runs with gridDim.y = K
-    (``iqlhip_group_train_steps``).  K x the work-groups per launch, one third of the kernel
+    (``iqlhip_group_train_steps``; with per-step valid-row counts ``iqlhip_group_train_steps_valid``).  K x the work-groups per launch, one third of the kernel
     boundaries per seed-step.
 ``mode="streams"``
     every trainer replays its own hipGraph on its own HIP stream; the launches interleave.
@@ -198,11 +198,16 @@ class SeedGroup:
     def train_steps(self, replay: Union[ReplayBuffer, Sequence[ReplayBuffer]], n_steps: int, batch_size: int, *,
                     indices: Optional[Sequence[Optional[torch.Tensor]]] = None,
                     dropout_keep: Optional[Sequence[Optional[torch.Tensor]]] = None,
-                    return_losses: bool = False, graph_unroll: Optional[int] = None):
+                    return_losses: bool = False, graph_unroll: Optional[int] = None,
+                    n_valid: Union[None, torch.Tensor, Sequence[Optional[torch.Tensor]]] = None):
         """``n_steps`` x (sample + train) for every seed.  ``replay`` is one buffer shared by all
         seeds (a sweep varies the seed only) or one per seed; ``indices`` / ``dropout_keep`` are
         optional per-seed lists (entries may be None) with the meaning of
-        ``ImplicitQLearning.train_steps``.  Returns a list of [n_steps, 3] loss tensors when
+        ``ImplicitQLearning.train_steps``.  ``n_valid``: the per-step valid-row counts of
+        ``ImplicitQLearning.train_steps`` -- one int32 [n_steps] device tensor shared by all seeds (the
+        short last batch of a BB epoch falls on the same step for every seed) or one entry per seed
+        (None: that seed uses its whole batch); fp32 trainers on the tuned step only, every other group
+        raises NotImplementedError before anything is launched.  Returns a list of [n_steps, 3] loss tensors when
         ``return_losses``.  Asynchronous: call ``synchronize()`` (or read the losses) before
         touching the parameters."""
         K = len(self.trainers)
@@ -213,10 +218,11 @@ class SeedGroup:
         keep = list(dropout_keep) if dropout_keep is not None else [None] * K
         if len(idx) != K or len(keep) != K:
             raise ValueError("indices / dropout_keep: one entry per trainer")
+        valid = self._check_valid(n_valid, n_steps, batch_size)
         if self.mode == "streams":
-            return self._train_streams(bufs, n_steps, batch_size, idx, keep, return_losses, graph_unroll)
+            return self._train_streams(bufs, n_steps, batch_size, idx, keep, return_losses, graph_unroll, valid)
         if self.mode == "split":
-            return self._train_split(bufs, n_steps, batch_size, idx, keep, return_losses, graph_unroll)
+            return self._train_split(bufs, n_steps, batch_size, idx, keep, return_losses, graph_unroll, valid)
         self._ensure_group(batch_size)
         for i, t in enumerate(idx):
             if t is not None:
@@ -229,20 +235,46 @@ class SeedGroup:
         views = (_lib.ReplayView * K)(*[b.view() for b in bufs])
         parr = lambda ts: (C.c_void_p * K)(*[None if t is None else t.data_ptr() for t in ts])
         any_idx, any_keep = any(t is not None for t in idx), any(t is not None for t in keep)
+        any_valid = any(t is not None for t in valid)
         for t in self.trainers:
             t._refresh_lrs()
         # (group launches: graphs of 50 steps 202-204k steps/s for 8 seeds, plain launches 198-200k)
         unroll = 50 if graph_unroll is None else graph_unroll
         with torch.cuda.device(self._dev):
-            check(self._lib.iqlhip_group_train_steps(
+            check(self._lib.iqlhip_group_train_steps_valid(
                 self._group, views, n_steps, parr(idx) if any_idx else None,
-                parr(keep) if any_keep else None, parr(losses) if losses is not None else None,
+                parr(valid) if any_valid else None, parr(keep) if any_keep else None, parr(losses) if losses is not None else None,
                 unroll, stream_ptr()))
         for t in self.trainers:
             t._after_steps(n_steps)
         return losses
 
-    def _train_streams(self, bufs, n_steps, batch_size, idx, keep, return_losses, graph_unroll):
+    def _check_valid(self, n_valid, n_steps: int, batch_size: int) -> List[Optional[torch.Tensor]]:
+        """``n_valid`` as one entry per trainer.  Checked as ``ImplicitQLearning.train_steps`` checks it; the
+        groups the counted step is not built for are refused here, before any member is stepped."""
+        K = len(self.trainers)
+        if n_valid is None:
+            return [None] * K
+        valid = [n_valid] * K if isinstance(n_valid, torch.Tensor) else list(n_valid)
+        if len(valid) != K:
+            raise ValueError("n_valid: one tensor for all trainers or one entry per trainer")
+        for i, t in enumerate(valid):
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or tuple(t.shape) != (n_steps,) or \
+                    t.device.type != "cuda":
+                raise ValueError("n_valid must be an int32 device tensor [n_steps]")
+            valid[i] = t.contiguous()
+        if all(t is None for t in valid):
+            return valid
+        if self.mode == "general" or any(t.step_kind(batch_size) == "general" for t in self.trainers):
+            raise NotImplementedError("per-step valid-row counts (a short batch) run on the tuned step only (n_hidden 2, "
+                                      "hidden_dim 64 / 128 / 256); this group runs the general layer-wise step")
+        if any(t._precision != _lib.PREC_FP32 for t in self.trainers):
+            raise NotImplementedError("per-step valid-row counts (a short batch) are built for precision fp32 only")
+        return valid
+
+    def _train_streams(self, bufs, n_steps, batch_size, idx, keep, return_losses, graph_unroll, valid):
         cur = torch.cuda.current_stream(self._dev)
         for st in self._streams:
             st.wait_stream(cur)
@@ -256,6 +288,7 @@ class SeedGroup:
                     r = tr.train_steps(buf, c, batch_size, return_losses=return_losses,
                                        indices=None if idx[k] is None else idx[k][done:done + c],
                                        dropout_keep=None if keep[k] is None else keep[k][done:done + c],
+                                       n_valid=None if valid[k] is None else valid[k][done:done + c],
                                        graph_unroll=8 if graph_unroll is None else graph_unroll)
                     if return_losses:
                         out[k].append(r)
@@ -276,7 +309,7 @@ class SeedGroup:
             warnings.warn(f"SeedGroup(mode='split'): CU-slice streams unavailable ({e}); using plain streams")
             self._streams = [torch.cuda.Stream(device=self._dev) for _ in self._children]
 
-    def _train_split(self, bufs, n_steps, batch_size, idx, keep, return_losses, graph_unroll):
+    def _train_split(self, bufs, n_steps, batch_size, idx, keep, return_losses, graph_unroll, valid):
         self._ensure_slice_streams()
         cur = torch.cuda.current_stream(self._dev)
         for st in self._streams:
@@ -289,7 +322,7 @@ class SeedGroup:
                 cut = lambda ts: [None if t is None else t[done:done + c] for t in ts[sl]]
                 with torch.cuda.stream(st):
                     r = ch.train_steps(bufs[sl], c, batch_size, indices=cut(idx), dropout_keep=cut(keep),
-                                       return_losses=return_losses, graph_unroll=graph_unroll)
+                                       return_losses=return_losses, graph_unroll=graph_unroll, n_valid=cut(valid))
                 if return_losses:
                     for k, rk in zip(range(sl.start, sl.stop), r):
                         out[k].append(rk)
