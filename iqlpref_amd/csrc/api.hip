@@ -269,6 +269,135 @@ struct Throttle {
   }
 };
 
+// How steps reach a stream, for one trainer (K = 1) or the K members of a group: what the device copies
+// of the tuned step's arguments hold, the cached hipGraph of `graph_unroll` steps, the throttle, the
+// per-kernel timing of the diagnostic mode and the launch counters.  Both step kinds issue through it.
+struct StepQueue {
+  // DevArgs travel through a small ring of pinned host slots, [K] each (a pageable source makes
+  // hipMemcpyAsync host-blocking, which serialised the streams of a SeedGroup); a slot is
+  // reused only after the copy that read it has completed (its event)
+  static constexpr int ARG_RING = 8;
+  DevArgs *harg[ARG_RING] = {};
+  hipEvent_t harg_ev[ARG_RING] = {};
+  bool harg_used[ARG_RING] = {};
+  int harg_head = 0;
+  DevArgs dev_args[IQLHIP_MAX_GROUP];  // what the device copies hold (see `continues`) ...
+  bool dev_args_valid = false;  // ... and whether the batch of step total_it is already staged for them
+  hipGraphExec_t gexec = nullptr;
+  int graph_unroll = 0;
+  bool graph_counts = false;  // `gexec` holds the counted k_backward (iqlhip_train_steps_valid)
+  hipStream_t cap_stream = nullptr;  // capture only (the legacy default stream cannot capture); shared, see capture_stream
+  Throttle throttle;
+  // per-kernel HIP-event timing (diagnostic mode, eager launches whatever graph_unroll says)
+  bool timing = false;
+  hipEvent_t ev[5] = {};
+  double t_acc[3] = {0, 0, 0};
+  double t_empty = 0;  // interval of two back-to-back event records (event overhead)
+  int64_t t_n = 0;
+  int64_t n_eager = 0, n_graph = 0;  // steps issued as plain launches / graph replays issued (iqlhip_*_launch_counts)
+
+  // K DevArgs through one pinned slot, in one copy to `dst`
+  int push(const DevArgs *want, int K, DevArgs *dst, hipStream_t st) {
+    const int slot = harg_head;
+    harg_head = (slot + 1) % ARG_RING;
+    if (!harg[slot]) {
+      HIP_TRY(hipHostMalloc((void **)&harg[slot], sizeof(DevArgs) * K, hipHostMallocDefault));
+      HIP_TRY(hipEventCreateWithFlags(&harg_ev[slot], hipEventDisableTiming));
+    }
+    if (harg_used[slot]) HIP_TRY(hipEventSynchronize(harg_ev[slot]));
+    for (int k = 0; k < K; ++k) harg[slot][k] = dev_args[k] = want[k];
+    HIP_TRY(hipMemcpyAsync(dst, harg[slot], sizeof(DevArgs) * K, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(harg_ev[slot], st));
+    harg_used[slot] = true;
+    return 0;
+  }
+  // the cached graph holds addresses (descriptors, arguments): whoever moves them drops it
+  void drop_graph() {
+    if (gexec) (void)hipGraphExecDestroy(gexec);
+    gexec = nullptr;
+  }
+  // `gexec` = U x step(cap_stream), a linear chain of kernel nodes; kept until another U or `counts` is asked for
+  template <typename Step>
+  int ensure_graph(int U, bool counts, Step step) {
+    if (gexec && graph_unroll == U && graph_counts == counts) return 0;
+    drop_graph();
+    hipGraph_t g = nullptr;
+    if (!cap_stream) HIP_TRY(capture_stream(&cap_stream));
+    HIP_TRY(hipStreamBeginCapture(cap_stream, hipStreamCaptureModeThreadLocal));
+    int rc = 0;
+    for (int u = 0; u < U && !rc; ++u) rc = step(cap_stream);
+    const hipError_t ce = hipStreamEndCapture(cap_stream, &g);
+    if ((rc || ce != hipSuccess) && g) (void)hipGraphDestroy(g);
+    if (rc) return rc;
+    HIP_TRY(ce);
+    const hipError_t ie = hipGraphInstantiate(&gexec, g, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(g);
+    HIP_TRY(ie);
+    graph_unroll = U, graph_counts = counts;
+    return 0;
+  }
+  // as many replays of the cached graph as fit into steps done .. n
+  int replay(int64_t &done, int64_t n, hipStream_t st) {
+    for (; done + graph_unroll <= n; done += graph_unroll) {
+      HIP_TRY(hipGraphLaunch(gexec, st));
+      ++n_graph;
+      HIP_TRY(throttle.queued(3 * (int64_t)graph_unroll, st));
+    }
+    return 0;
+  }
+  // one step has been issued as plain launches; under timing with ev[0..3] around its three kernels
+  // (one event pair per kernel: serialises the stream a little; diagnostic mode only)
+  int eager_issued(hipStream_t st) {
+    ++n_eager;
+    if (!timing) {
+      HIP_TRY(throttle.queued(3, st));
+      return 0;
+    }
+    HIP_TRY(hipEventRecord(ev[4], st));  // empty interval: what a record pair costs by itself
+    HIP_TRY(hipEventSynchronize(ev[4]));
+    for (int k = 0; k < 3; ++k) {
+      float ms = 0.f;
+      HIP_TRY(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
+      t_acc[k] += ms;
+    }
+    float ems = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ems, ev[3], ev[4]));
+    t_empty += ems;
+    ++t_n;
+    return 0;
+  }
+  int set_timing(bool enable) {
+    timing = enable;
+    t_acc[0] = t_acc[1] = t_acc[2] = 0, t_empty = 0, t_n = 0;
+    if (timing)
+      for (auto &e : ev)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    return 0;
+  }
+  void get_timing(double avg_ms[3], int64_t *n) const {
+    // event-pair overhead (measured on an empty interval in the same pass) is subtracted
+    for (int k = 0; k < 3; ++k) {
+      const double v = t_n ? (t_acc[k] - t_empty) / (double)t_n : 0.0;
+      avg_ms[k] = v > 0 ? v : 0.0;
+    }
+    if (n) *n = t_n;
+  }
+  void launch_counts(int64_t *eager_steps, int64_t *graph_launches) const {
+    if (eager_steps) *eager_steps = n_eager;
+    if (graph_launches) *graph_launches = n_graph;
+  }
+  void destroy() {
+    drop_graph();
+    for (int k = 0; k < ARG_RING; ++k) {
+      if (harg_ev[k]) (void)hipEventDestroy(harg_ev[k]);
+      if (harg[k]) (void)hipHostFree(harg[k]);
+    }
+    for (auto &e : ev)
+      if (e) (void)hipEventDestroy(e);
+    throttle.destroy();
+  }
+};
+
 // The general step's arguments in device memory, for one trainer (K = 1) or the K members of a group:
 //   [K] DeepArgs | [K] DeepCtr | [CAP][K] AdamCoef
 // A call is cut into chunks of at most CAP steps; ahead of each, the block, the counters (= the chunk's
@@ -309,11 +438,10 @@ struct iqlhip_trainer {
   iqlhip_trainer_config cfg;
   iqlhip_arenas arenas;
   // shapes outside the tuned step's (n_hidden != 2 or another width): the general layer-wise step;
-  // of the members below only cfg, the learning rates, total_it, the graph, the timing events, the
-  // throttle, `group` and batch_rows are in use then
+  // of the members below only cfg, the learning rates, total_it, `queue` (its graph, timing events,
+  // throttle and counters; not the DevArgs ring), `group` and batch_rows are in use then
   DeepTrainer *deep = nullptr;
   DeepRing deep_ring;
-  int64_t n_eager = 0, n_graph = 0;  // steps issued as plain launches / graph replays issued (iqlhip_trainer_launch_counts)
   TrainerDesc D;
   bool bf16;
   void *ws = nullptr;
@@ -337,32 +465,9 @@ struct iqlhip_trainer {
   struct iqlhip_group *group = nullptr;
 
   float *batch_rows = nullptr;  // [B][stride] staging for iqlhip_train_batch
-  // DevArgs travel through a small ring of pinned host slots (a pageable source makes
-  // hipMemcpyAsync host-blocking, which serialised the streams of a SeedGroup); a slot is
-  // reused only after the copy that read it has completed (its event)
-  static constexpr int ARG_RING = 8;
-  DevArgs dev_args;             // what the device copy holds ...
-  bool dev_args_valid = false;  // ... and whether the batch of step total_it is already staged for it
-  DevArgs *harg[ARG_RING] = {};
-  hipEvent_t harg_ev[ARG_RING] = {};
-  bool harg_used[ARG_RING] = {};
-  int harg_head = 0;
-
   int64_t total_it = 0;
   double lr_q, lr_v, lr_a_base;
-  Throttle throttle;
-  // hipGraph of `graph_unroll` steps
-  hipGraphExec_t gexec = nullptr;
-  int graph_unroll = 0;
-  bool counts = false;        // the call in flight carries valid-row counts (iqlhip_train_steps_valid)
-  bool graph_counts = false;  // ... and so did the call `gexec` was captured for
-  hipStream_t cap_stream = nullptr;  // capture only (the legacy default stream cannot capture); shared, see capture_stream
-  // timing
-  bool timing = false;
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  double t_acc[3] = {0, 0, 0};
-  double t_empty = 0;  // interval of two back-to-back event records (event overhead)
-  int64_t t_n = 0;
+  StepQueue queue;  // of the trainer's own calls (K = 1)
 };
 
 static_assert(MAX_CRITICS == IQLHIP_MAX_CRITICS, "iql_step.h and iqlhip.h disagree");
@@ -828,15 +933,7 @@ extern "C" int iqlhip_trainer_create(iqlhip_trainer **out, const iqlhip_trainer_
 extern "C" int iqlhip_trainer_destroy(iqlhip_trainer *t) {
   if (!t) return 0;
   if (t->group) return fail(IQLHIP_ERR_INVALID, "trainer is a member of a group: destroy the group first");
-  if (t->gexec) (void)hipGraphExecDestroy(t->gexec);
-  for (int k = 0; k < iqlhip_trainer::ARG_RING; ++k) {
-    if (t->harg_ev[k]) (void)hipEventDestroy(t->harg_ev[k]);
-    if (t->harg[k]) (void)hipHostFree(t->harg[k]);
-  }
-
-  for (auto &e : t->ev)
-    if (e) (void)hipEventDestroy(e);
-  t->throttle.destroy();
+  t->queue.destroy();
   if (t->deep) {
     deep_destroy(t->deep);
     (void)hipFree(t->batch_rows);
@@ -874,7 +971,7 @@ extern "C" int iqlhip_trainer_set_step(iqlhip_trainer *t, int64_t total_it) {
   memset(&c, 0, sizeof(c));
   c.ctr[0] = total_it, c.ctr[1] = total_it;
   HIP_TRY(hipMemcpy(t->dctr, &c, sizeof(c), hipMemcpyHostToDevice));
-  t->dev_args_valid = false;
+  t->queue.dev_args_valid = false;
   if (t->group) group_invalidate(t->group);
   return 0;
 }
@@ -897,33 +994,18 @@ extern "C" int iqlhip_trainer_set_lr(iqlhip_trainer *t, double lr_q, double lr_v
 }
 
 extern "C" int iqlhip_trainer_set_timing(iqlhip_trainer *t, int32_t enable) {
-  if (!t) return fail(IQLHIP_ERR_INVALID, "null trainer");
-  t->timing = enable != 0;
-  t->t_acc[0] = t->t_acc[1] = t->t_acc[2] = 0;
-  t->t_empty = 0;
-  t->t_n = 0;
-  if (t->timing)
-    for (auto &e : t->ev)
-      if (!e) HIP_TRY(hipEventCreate(&e));
-  return 0;
+  return t ? t->queue.set_timing(enable != 0) : fail(IQLHIP_ERR_INVALID, "null trainer");
 }
 
 extern "C" int iqlhip_trainer_get_timing(iqlhip_trainer *t, double avg_ms[3], int64_t *n) {
   if (!t) return fail(IQLHIP_ERR_INVALID, "null trainer");
-  // event-pair overhead (measured on an empty interval in the same pass) is subtracted
-  for (int k = 0; k < 3; ++k) {
-    const double v = t->t_n ? (t->t_acc[k] - t->t_empty) / (double)t->t_n : 0.0;
-    avg_ms[k] = v > 0 ? v : 0.0;
-  }
-  if (n) *n = t->t_n;
+  t->queue.get_timing(avg_ms, n);
   return 0;
 }
 
-static int enqueue_step(iqlhip_trainer *t, hipStream_t st) {
-  if (!t->D.prefetch) HIP_TRY(launch_stage(t->bf16, t->D, t->ddesc, t->dargs, t->dctr, 1, st));
-  HIP_TRY(launch_forward(t->bf16, t->D, t->ddesc, t->dargs, t->dctr, 1, st));
-  HIP_TRY(launch_backward(t->bf16, t->D, t->ddesc, t->dargs, t->dctr, 1, st, t->counts));
-  HIP_TRY(launch_update(t->bf16, t->ddesc, t->dargs, t->dctr, t->ditems, t->n_items, 1, st));
+extern "C" int iqlhip_trainer_launch_counts(iqlhip_trainer *t, int64_t *eager_steps, int64_t *graph_launches) {
+  if (!t) return fail(IQLHIP_ERR_INVALID, "null trainer");
+  t->queue.launch_counts(eager_steps, graph_launches);
   return 0;
 }
 
@@ -938,24 +1020,60 @@ static bool continues(const DevArgs &a, const DevArgs &b) {
          !a.losses_out && !b.losses_out && !a.n_valid && !b.n_valid && a.lr_q == b.lr_q && a.lr_v == b.lr_v && a.lr_a_base == b.lr_a_base;
 }
 
-static hipError_t push_args(iqlhip_trainer *t, const DevArgs &args_in, int64_t n_steps, hipStream_t st) {
-  DevArgs args = args_in;
-  args.n_steps = n_steps;
-  const int k = t->harg_head;
-  t->harg_head = (k + 1) % iqlhip_trainer::ARG_RING;
-  hipError_t e;
-  if (!t->harg[k]) {
-    if ((e = hipHostMalloc((void **)&t->harg[k], sizeof(DevArgs), hipHostMallocDefault)) != hipSuccess) return e;
-    if ((e = hipEventCreateWithFlags(&t->harg_ev[k], hipEventDisableTiming)) != hipSuccess) return e;
+// What a launch of the tuned step works on: the launch geometry of member 0 and the [K] device arrays of
+// a group, or (K = 1) a trainer's own slots -- its slot k of the group's arrays while it is a member of one.
+struct StepTarget {
+  bool bf16;
+  const TrainerDesc &D;
+  const TrainerDesc *desc;
+  DevArgs *args;
+  DevCtr *ctr;
+  const UpdItem *items;
+  int n_items, K;
+};
+
+// one step; ev (optional, 4 events) brackets the three kernels for the per-kernel timing
+static int enqueue_step(const StepTarget &x, bool counts, hipStream_t st, hipEvent_t *ev) {
+  if (!x.D.prefetch) HIP_TRY(launch_stage(x.bf16, x.D, x.desc, x.args, x.ctr, x.K, st));
+  if (ev) HIP_TRY(hipEventRecord(ev[0], st));
+  HIP_TRY(launch_forward(x.bf16, x.D, x.desc, x.args, x.ctr, x.K, st));
+  if (ev) HIP_TRY(hipEventRecord(ev[1], st));
+  HIP_TRY(launch_backward(x.bf16, x.D, x.desc, x.args, x.ctr, x.K, st, counts));
+  if (ev) HIP_TRY(hipEventRecord(ev[2], st));
+  HIP_TRY(launch_update(x.bf16, x.desc, x.args, x.ctr, x.items, x.n_items, x.K, st));
+  if (ev) HIP_TRY(hipEventRecord(ev[3], st));
+  return 0;
+}
+
+// The tuned step, for one trainer or the K members of a group: the K DevArgs go up through one pinned slot
+// in one copy (skipped when the call continues the last), then the steps run as hipGraphs of `graph_unroll`
+// steps and the remainder as plain launches.  `counts`: which k_backward the launches (and the graph) use.
+static int run_tuned(StepQueue &q, const StepTarget &x, const DevArgs *want, int64_t n_steps, int graph_unroll,
+                     bool counts, hipStream_t st) {
+  bool same = x.D.prefetch && q.dev_args_valid && !q.timing, all_philox = true;
+  for (int k = 0; k < x.K; ++k) {
+    same = same && continues(q.dev_args[k], want[k]);
+    all_philox = all_philox && want[k].idx_mode == 0;
   }
-  if (t->harg_used[k] && (e = hipEventSynchronize(t->harg_ev[k])) != hipSuccess) return e;
-  *t->harg[k] = args;
-  if ((e = hipMemcpyAsync(t->dargs, t->harg[k], sizeof(DevArgs), hipMemcpyHostToDevice, st)) != hipSuccess)
-    return e;
-  if ((e = hipEventRecord(t->harg_ev[k], st)) != hipSuccess) return e;
-  t->harg_used[k] = true;
-  t->dev_args = args;
-  return hipSuccess;
+  if (!same) {
+    if (int rc = q.push(want, x.K, x.args, st)) return rc;
+    // the first step's batch (later steps are staged by the update kernel of the step before)
+    if (x.D.prefetch) HIP_TRY(launch_stage(x.bf16, x.D, x.desc, x.args, x.ctr, x.K, st));
+  }
+  // after this call the device holds these arguments and (prefetch, on-device indices) the batch
+  // of the step that follows it
+  q.dev_args_valid = all_philox;
+  int64_t done = 0;
+  if (!q.timing && graph_unroll > 0 && n_steps >= graph_unroll) {
+    if (int rc = q.ensure_graph(graph_unroll, counts, [&](hipStream_t cs) { return enqueue_step(x, counts, cs, nullptr); }))
+      return rc;
+    if (int rc = q.replay(done, n_steps, st)) return rc;
+  }
+  for (; done < n_steps; ++done) {
+    if (int rc = enqueue_step(x, counts, st, q.timing ? q.ev : nullptr)) return rc;
+    if (int rc = q.eager_issued(st)) return rc;
+  }
+  return 0;
 }
 
 // The general step, for one trainer or the K members of a group.  Per chunk of at most DeepRing::CAP steps:
@@ -967,15 +1085,8 @@ struct DeepRun {
   iqlhip_trainer *const *tr;
   int K;
   DeepRing *ring;
-  const DeepDesc *ddesc;   // [K], device
-  hipGraphExec_t *gexec;
-  int *graph_unroll;
-  hipStream_t *cap_stream;
-  Throttle *throttle;
-  bool timing;
-  hipEvent_t *ev;
-  double *t_acc, *t_empty;
-  int64_t *t_n, *n_eager, *n_graph;
+  const DeepDesc *ddesc;  // [K], device
+  StepQueue &q;
 };
 
 static int deep_push(const DeepRun &r, const DevArgs *a, int64_t done, int64_t n, hipStream_t st) {
@@ -1012,153 +1123,80 @@ static int deep_push(const DeepRun &r, const DevArgs *a, int64_t done, int64_t n
 }
 
 static int deep_run(const DeepRun &r, const DevArgs *a, int64_t n_steps, int graph_unroll, hipStream_t st) {
-  const DeepTrainer *t0 = r.tr[0]->deep;
-  const DeepArgs *dA = r.ring->dargs();
-  DeepCtr *dC = r.ring->dctr();
-  const int U = r.timing ? 0 : (int)std::min<int64_t>(std::max(graph_unroll, 0), DeepRing::CAP);
+  StepQueue &q = r.q;
+  auto step = [&](hipStream_t s, hipEvent_t *ev) {
+    HIP_TRY(deep_step(r.tr[0]->deep, r.ddesc, r.ring->dargs(), r.ring->dctr(), r.ring->dcoef(), r.K, s, ev));
+    return 0;
+  };
+  const int U = q.timing ? 0 : (int)std::min<int64_t>(std::max(graph_unroll, 0), DeepRing::CAP);
   const int64_t cap = U > 0 ? DeepRing::CAP / U * U : DeepRing::CAP;
   for (int64_t done = 0; done < n_steps;) {
     const int64_t n = std::min(cap, n_steps - done);
     if (int rc = deep_push(r, a, done, n, st)) return rc;
     int64_t i = 0;
     if (U > 0 && n >= U) {
-      if (!*r.gexec || *r.graph_unroll != U) {
-        if (*r.gexec) {
-          (void)hipGraphExecDestroy(*r.gexec);
-          *r.gexec = nullptr;
-        }
-        hipGraph_t g = nullptr;
-        if (!*r.cap_stream) HIP_TRY(capture_stream(r.cap_stream));
-        HIP_TRY(hipStreamBeginCapture(*r.cap_stream, hipStreamCaptureModeThreadLocal));
-        hipError_t le = hipSuccess;
-        for (int u = 0; u < U && le == hipSuccess; ++u)
-          le = deep_step(t0, r.ddesc, dA, dC, r.ring->dcoef(), r.K, *r.cap_stream, nullptr);
-        hipError_t ce = hipStreamEndCapture(*r.cap_stream, &g);
-        if ((le != hipSuccess || ce != hipSuccess) && g) (void)hipGraphDestroy(g);
-        HIP_TRY(le);
-        HIP_TRY(ce);
-        HIP_TRY(hipGraphInstantiate(r.gexec, g, nullptr, nullptr, 0));
-        (void)hipGraphDestroy(g);
-        *r.graph_unroll = U;
-      }
-      for (; i + U <= n; i += U) {
-        HIP_TRY(hipGraphLaunch(*r.gexec, st));
-        ++*r.n_graph;
-        HIP_TRY(r.throttle->queued(3 * (int64_t)U, st));
-      }
+      if (int rc = q.ensure_graph(U, false, [&](hipStream_t cs) { return step(cs, nullptr); })) return rc;
+      if (int rc = q.replay(i, n, st)) return rc;
     }
     for (; i < n; ++i) {
-      HIP_TRY(deep_step(t0, r.ddesc, dA, dC, r.ring->dcoef(), r.K, st, r.timing ? r.ev : nullptr));
-      ++*r.n_eager;
-      if (r.timing) {  // one event pair per kernel: serialises the stream a little; diagnostic mode only
-        HIP_TRY(hipEventRecord(r.ev[4], st));
-        HIP_TRY(hipEventSynchronize(r.ev[4]));
-        for (int k = 0; k < 3; ++k) {
-          float ms = 0.f;
-          HIP_TRY(hipEventElapsedTime(&ms, r.ev[k], r.ev[k + 1]));
-          r.t_acc[k] += ms;
-        }
-        float ems = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ems, r.ev[3], r.ev[4]));
-        *r.t_empty += ems;
-        ++*r.t_n;
-      } else {
-        HIP_TRY(r.throttle->queued(3, st));
-      }
+      if (int rc = step(st, q.timing ? q.ev : nullptr)) return rc;
+      if (int rc = q.eager_issued(st)) return rc;
     }
     done += n;
   }
   return 0;
 }
 
-static int run_steps_deep(iqlhip_trainer *t, const DevArgs &a, int64_t n_steps, int graph_unroll, hipStream_t st) {
-  iqlhip_trainer *tr[1] = {t};
-  const DeepRun r = {tr, 1, &t->deep_ring, deep_desc_dev(t->deep), &t->gexec, &t->graph_unroll,
-                     &t->cap_stream, &t->throttle, t->timing, t->ev, t->t_acc, &t->t_empty, &t->t_n, &t->n_eager,
-                     &t->n_graph};
-  return deep_run(r, &a, n_steps, graph_unroll, st);
+// per-step valid-row counts: refused before any launch where the step is not built for them
+static int check_counts(const iqlhip_trainer *t0, bool counts, const char *who) {
+  // (the counts live on the device: the call cannot tell whether every one of them is the whole batch)
+  if (counts && t0->deep)
+    return fail(IQLHIP_ERR_UNSUPPORTED,
+                "per-step valid-row counts (a short batch) run on the tuned step only (n_hidden 2, hidden_dim 64 / "
+                "128 / 256); this %s (n_hidden %d, hidden_dim %d) runs the general layer-wise step",
+                who, n_hidden(t0->cfg), t0->cfg.hidden_dim);
+  if (counts && t0->bf16)
+    return fail(IQLHIP_ERR_UNSUPPORTED, "per-step valid-row counts (a short batch) are built for precision fp32 only");
+  return 0;
 }
 
-static int run_steps(iqlhip_trainer *t, const DevArgs &args_in, int64_t n_steps, int graph_unroll,
-                     hipStream_t st) {
-  if (t->deep) {
-    // the counts live on the device: the call cannot tell whether every one of them is the whole batch
-    if (args_in.n_valid)
-      return fail(IQLHIP_ERR_UNSUPPORTED,
-                  "per-step valid-row counts (a short batch) run on the tuned step only (n_hidden 2, hidden_dim 64 / "
-                  "128 / 256); this trainer (n_hidden %d, hidden_dim %d) runs the general layer-wise step",
-                  n_hidden(t->cfg), t->cfg.hidden_dim);
-    return run_steps_deep(t, args_in, n_steps, graph_unroll, st);
-  }
-  if (args_in.n_valid && t->bf16)
-    return fail(IQLHIP_ERR_UNSUPPORTED, "per-step valid-row counts (a short batch) are built for precision fp32 only");
-  t->counts = args_in.n_valid != nullptr;  // which k_backward the launches (and the captured graph) of this call use
-  if (t->group) group_invalidate(t->group);  // this call rewrites the member's slot of the group's arguments
-  if (!(t->D.prefetch && t->dev_args_valid && !t->timing && continues(t->dev_args, args_in))) {
-    HIP_TRY(push_args(t, args_in, n_steps, st));
-    // the first step's batch (later steps are staged by the update kernel of the step before)
-    if (t->D.prefetch) HIP_TRY(launch_stage(t->bf16, t->D, t->ddesc, t->dargs, t->dctr, 1, st));
-  }
-  // after this call the device holds these arguments and (prefetch, on-device indices) the batch
-  // of the step that follows it
-  t->dev_args_valid = args_in.idx_mode == 0;
-  int64_t done = 0;
-  if (t->timing) {
-    // one event pair per kernel: serialises the stream a little; diagnostic mode only
-    for (; done < n_steps; ++done) {
-      if (!t->D.prefetch) HIP_TRY(launch_stage(t->bf16, t->D, t->ddesc, t->dargs, t->dctr, 1, st));
-      HIP_TRY(hipEventRecord(t->ev[0], st));
-      HIP_TRY(launch_forward(t->bf16, t->D, t->ddesc, t->dargs, t->dctr, 1, st));
-      HIP_TRY(hipEventRecord(t->ev[1], st));
-      HIP_TRY(launch_backward(t->bf16, t->D, t->ddesc, t->dargs, t->dctr, 1, st, t->counts));
-      HIP_TRY(hipEventRecord(t->ev[2], st));
-      HIP_TRY(launch_update(t->bf16, t->ddesc, t->dargs, t->dctr, t->ditems, t->n_items, 1, st));
-      HIP_TRY(hipEventRecord(t->ev[3], st));
-      HIP_TRY(hipEventRecord(t->ev[4], st));  // empty interval: what a record pair costs by itself
-      HIP_TRY(hipEventSynchronize(t->ev[4]));
-      for (int k = 0; k < 3; ++k) {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, t->ev[k], t->ev[k + 1]));
-        t->t_acc[k] += ms;
-      }
-      float ems = 0.f;
-      HIP_TRY(hipEventElapsedTime(&ems, t->ev[3], t->ev[4]));
-      t->t_empty += ems;
-      t->t_n++;
-      t->n_eager++;
-    }
-    return 0;
-  }
-  if (graph_unroll > 0 && n_steps >= graph_unroll) {
-    if (!t->gexec || t->graph_unroll != graph_unroll || t->graph_counts != t->counts) {
-      if (t->gexec) {
-        (void)hipGraphExecDestroy(t->gexec);
-        t->gexec = nullptr;
-      }
-      hipGraph_t g = nullptr;
-      if (!t->cap_stream) HIP_TRY(capture_stream(&t->cap_stream));
-      HIP_TRY(hipStreamBeginCapture(t->cap_stream, hipStreamCaptureModeThreadLocal));
-      int rc = 0;
-      for (int u = 0; u < graph_unroll && !rc; ++u) rc = enqueue_step(t, t->cap_stream);
-      hipError_t ce = hipStreamEndCapture(t->cap_stream, &g);
-      if (rc) return rc;
-      HIP_TRY(ce);
-      HIP_TRY(hipGraphInstantiate(&t->gexec, g, nullptr, nullptr, 0));
-      (void)hipGraphDestroy(g);
-      t->graph_unroll = graph_unroll, t->graph_counts = t->counts;
-    }
-    for (; done + graph_unroll <= n_steps; done += graph_unroll) {
-      HIP_TRY(hipGraphLaunch(t->gexec, st));
-      t->n_graph++;
-      HIP_TRY(t->throttle.queued(3 * (int64_t)graph_unroll, st));
-    }
-  }
-  for (; done < n_steps; ++done) {
-    if (int rc = enqueue_step(t, st)) return rc;
-    t->n_eager++;
-    HIP_TRY(t->throttle.queued(3, st));
-  }
+static int check_view(const iqlhip_replay_view &v, const iqlhip_trainer_config &c) {
+  if (v.state_dim != c.state_dim || v.action_dim != c.action_dim)
+    return fail(IQLHIP_ERR_INVALID, "replay dims (%d,%d) do not match the trainer (%d,%d)", v.state_dim,
+                v.action_dim, c.state_dim, c.action_dim);
+  if (v.n_rows <= 0) return fail(IQLHIP_ERR_INVALID, "cannot sample from an empty replay buffer");
+  if (v.row_stride != iqlhip_replay_row_stride(v.state_dim, v.action_dim))
+    return fail(IQLHIP_ERR_INVALID, "row_stride %d is not the packed layout's (%d)", v.row_stride,
+                iqlhip_replay_row_stride(v.state_dim, v.action_dim));
   return 0;
+}
+
+// the arguments of n_steps steps of trainer t from where it stands
+static DevArgs make_args(const iqlhip_trainer *t, const iqlhip_replay_view &v, int64_t n_steps, const int64_t *idx,
+                         const int32_t *n_valid, const uint8_t *dropout_keep, float *losses_out) {
+  DevArgs a;
+  memset(&a, 0, sizeof(a));
+  a.rows = v.rows, a.n_rows = v.n_rows, a.row_stride = v.row_stride;
+  a.generation = v.generation;
+  a.idx_mode = idx ? 1 : 0, a.idx = idx;
+  a.drop_keep = dropout_keep, a.losses_out = losses_out;
+  a.n_valid = n_valid;  // (`continues` is false with counts on either side)
+  a.base_step = t->total_it, a.n_steps = n_steps;
+  a.lr_q = t->lr_q, a.lr_v = t->lr_v, a.lr_a_base = t->lr_a_base;
+  return a;
+}
+
+// a trainer's own call (also while it is a member of a group)
+static int run_solo(iqlhip_trainer *t, const DevArgs &a, int graph_unroll, hipStream_t st) {
+  const bool counts = a.n_valid != nullptr;
+  if (int rc = check_counts(t, counts, "trainer")) return rc;
+  if (t->deep) {
+    iqlhip_trainer *tr[1] = {t};
+    return deep_run({tr, 1, &t->deep_ring, deep_desc_dev(t->deep), t->queue}, &a, a.n_steps, graph_unroll, st);
+  }
+  if (t->group) group_invalidate(t->group);  // this call rewrites the member's slot of the group's arguments
+  const StepTarget x = {t->bf16, t->D, t->ddesc, t->dargs, t->dctr, t->ditems, t->n_items, 1};
+  return run_tuned(t->queue, x, &a, a.n_steps, graph_unroll, counts, st);
 }
 
 extern "C" int iqlhip_train_steps(iqlhip_trainer *t, const iqlhip_replay_view *view, int64_t n_steps,
@@ -1172,23 +1210,10 @@ extern "C" int iqlhip_train_steps_valid(iqlhip_trainer *t, const iqlhip_replay_v
                                         float *losses_out, int32_t graph_unroll, void *stream) {
   if (!t || !view || !view->rows) return fail(IQLHIP_ERR_INVALID, "null argument");
   if (n_steps < 0) return fail(IQLHIP_ERR_INVALID, "n_steps must be >= 0");
-  if (view->state_dim != t->cfg.state_dim || view->action_dim != t->cfg.action_dim)
-    return fail(IQLHIP_ERR_INVALID, "replay dims (%d,%d) do not match the trainer (%d,%d)", view->state_dim,
-                view->action_dim, t->cfg.state_dim, t->cfg.action_dim);
-  if (view->n_rows <= 0) return fail(IQLHIP_ERR_INVALID, "cannot sample from an empty replay buffer");
-  if (view->row_stride != iqlhip_replay_row_stride(view->state_dim, view->action_dim))
-    return fail(IQLHIP_ERR_INVALID, "row_stride %d is not the packed layout's (%d)", view->row_stride,
-                iqlhip_replay_row_stride(view->state_dim, view->action_dim));
+  if (int rc = check_view(*view, t->cfg)) return rc;
   if (n_steps == 0) return 0;
-  DevArgs a;
-  memset(&a, 0, sizeof(a));
-  a.rows = view->rows, a.n_rows = view->n_rows, a.row_stride = view->row_stride;
-  a.generation = view->generation;
-  a.idx_mode = idx ? 1 : 0, a.idx = idx;
-  a.drop_keep = dropout_keep, a.losses_out = losses_out, a.n_valid = n_valid;
-  a.base_step = t->total_it;
-  a.lr_q = t->lr_q, a.lr_v = t->lr_v, a.lr_a_base = t->lr_a_base;
-  if (int rc = run_steps(t, a, n_steps, graph_unroll, (hipStream_t)stream)) return rc;
+  const DevArgs a = make_args(t, *view, n_steps, idx, n_valid, dropout_keep, losses_out);
+  if (int rc = run_solo(t, a, graph_unroll, (hipStream_t)stream)) return rc;
   t->total_it += n_steps;
   return 0;
 }
@@ -1200,14 +1225,10 @@ extern "C" int iqlhip_train_batch(iqlhip_trainer *t, const float *s, const float
   const int S = t->cfg.state_dim, A = t->cfg.action_dim, B = t->cfg.batch_size;
   const int stride = iqlhip_replay_row_stride(S, A);
   HIP_TRY(launch_pack(t->batch_rows, stride, S, A, 0, B, s, a, r, s2, d, (hipStream_t)stream));
-  DevArgs args;
-  memset(&args, 0, sizeof(args));
-  args.rows = t->batch_rows, args.n_rows = B, args.row_stride = stride;
-  args.idx_mode = 2;
-  args.drop_keep = dropout_keep, args.losses_out = losses_out;
-  args.base_step = t->total_it;
-  args.lr_q = t->lr_q, args.lr_v = t->lr_v, args.lr_a_base = t->lr_a_base;
-  if (int rc = run_steps(t, args, 1, 0, (hipStream_t)stream)) return rc;
+  const iqlhip_replay_view rows = {t->batch_rows, B, stride, S, A, 0};
+  DevArgs args = make_args(t, rows, 1, nullptr, nullptr, dropout_keep, losses_out);
+  args.idx_mode = 2;  // the rows as they lie
+  if (int rc = run_solo(t, args, 0, (hipStream_t)stream)) return rc;
   t->total_it += 1;
   return 0;
 }
@@ -1228,24 +1249,7 @@ struct iqlhip_group {
   DevArgs *gargs = nullptr;
   DevCtr *gctr = nullptr;
   UpdItem *gitems = nullptr;
-  static constexpr int ARG_RING = 8;
-  DevArgs *harg[ARG_RING] = {};  // pinned, [K] each
-  hipEvent_t harg_ev[ARG_RING] = {};
-  bool harg_used[ARG_RING] = {};
-  int harg_head = 0;
-  hipGraphExec_t gexec = nullptr;
-  int graph_unroll = 0;
-  bool graph_counts = false;  // `gexec` holds the counted k_backward (iqlhip_group_train_steps_valid)
-  hipStream_t cap_stream = nullptr;
-  Throttle throttle;
-  DevArgs dev_args[IQLHIP_MAX_GROUP];  // what the device copies hold (see `continues`)
-  bool dev_args_valid = false;
-  // per-kernel HIP-event timing (diagnostic mode, eager launches)
-  bool timing = false;
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  double t_acc[3] = {0, 0, 0}, t_empty = 0;
-  int64_t t_n = 0;
-  int64_t n_eager = 0, n_graph = 0;  // iqlhip_group_launch_counts
+  StepQueue queue;  // of the group launches (K members per step)
   // a group of general-step trainers (iql_deep.hip): mem = [K] DeepDesc (the update table is member 0's: one
   // shape, one table); the arguments, counters and Adam coefficients of all members live in `deep_ring`.  The members keep their own
   // workspaces and argument blocks, so one stepped alone between group calls needs no hand-over.
@@ -1254,7 +1258,7 @@ struct iqlhip_group {
   DeepDesc *gdeep = nullptr;
 };
 
-static void group_invalidate(iqlhip_group *g) { g->dev_args_valid = false; }
+static void group_invalidate(iqlhip_group *g) { g->queue.dev_args_valid = false; }
 
 static bool same_shape(const iqlhip_trainer_config &a, const iqlhip_trainer_config &b) {
   return a.state_dim == b.state_dim && a.action_dim == b.action_dim && a.hidden_dim == b.hidden_dim &&
@@ -1361,11 +1365,8 @@ extern "C" int iqlhip_group_create(iqlhip_group **out, iqlhip_trainer *const *tr
     t->n_items = ni;
     // the member's DevArgs slot has moved: its next solo call must send its arguments and stage
     // its first batch again (`continues` would otherwise trust what the OLD slot held)
-    t->dev_args_valid = false;
-    if (t->gexec) {  // the member's own graph holds the old descriptor addresses
-      (void)hipGraphExecDestroy(t->gexec);
-      t->gexec = nullptr;
-    }
+    t->queue.dev_args_valid = false;
+    t->queue.drop_graph();  // the member's own graph holds the old descriptor addresses
   }
   *out = g;
   return 0;
@@ -1385,32 +1386,13 @@ extern "C" int iqlhip_group_destroy(iqlhip_group *g) {
     t->group = nullptr;
     // own_dargs holds whatever the member's last solo call OUTSIDE the group sent (all zero if
     // there was none: rows = NULL): a solo call after the group must never continue from it
-    t->dev_args_valid = false;
-    if (t->gexec) {
-      (void)hipGraphExecDestroy(t->gexec);
-      t->gexec = nullptr;
-    }
+    t->queue.dev_args_valid = false;
+    t->queue.drop_graph();
   }
-  if (g->gexec) (void)hipGraphExecDestroy(g->gexec);
-  g->throttle.destroy();
-  for (auto &e : g->ev)
-    if (e) (void)hipEventDestroy(e);
-  for (int k = 0; k < iqlhip_group::ARG_RING; ++k) {
-    if (g->harg_ev[k]) (void)hipEventDestroy(g->harg_ev[k]);
-    if (g->harg[k]) (void)hipHostFree(g->harg[k]);
-  }
+  g->queue.destroy();
   g->deep_ring.destroy();
   if (g->mem) (void)hipFree(g->mem);
   delete g;
-  return 0;
-}
-
-static int group_enqueue_step(iqlhip_group *g, hipStream_t st, bool counts) {
-  iqlhip_trainer *t0 = g->tr[0];
-  if (!t0->D.prefetch) HIP_TRY(launch_stage(t0->bf16, t0->D, g->gdesc, g->gargs, g->gctr, g->K, st));
-  HIP_TRY(launch_forward(t0->bf16, t0->D, g->gdesc, g->gargs, g->gctr, g->K, st));
-  HIP_TRY(launch_backward(t0->bf16, t0->D, g->gdesc, g->gargs, g->gctr, g->K, st, counts));
-  HIP_TRY(launch_update(t0->bf16, g->gdesc, g->gargs, g->gctr, g->gitems, g->n_items, g->K, st));
   return 0;
 }
 
@@ -1429,169 +1411,42 @@ extern "C" int iqlhip_group_train_steps_valid(iqlhip_group *g, const iqlhip_repl
   // any member with counts: the counted k_backward for the whole launch (a member without uses its whole batch)
   bool counts = false;
   for (int k = 0; n_valid && k < g->K; ++k) counts = counts || n_valid[k] != nullptr;
-  if (counts && g->deep)  // (as run_steps: the counts live on the device, the call cannot see whether they matter)
-    return fail(IQLHIP_ERR_UNSUPPORTED,
-                "per-step valid-row counts (a short batch) run on the tuned step only (n_hidden 2, hidden_dim 64 / "
-                "128 / 256); this group (n_hidden %d, hidden_dim %d) runs the general layer-wise step",
-                n_hidden(g->tr[0]->cfg), g->tr[0]->cfg.hidden_dim);
-  if (counts && g->tr[0]->bf16)
-    return fail(IQLHIP_ERR_UNSUPPORTED, "per-step valid-row counts (a short batch) are built for precision fp32 only");
+  if (int rc = check_counts(g->tr[0], counts, "group")) return rc;
   for (int k = 0; k < g->K; ++k) {
-    const iqlhip_replay_view &v = views[k];
-    const iqlhip_trainer_config &c = g->tr[k]->cfg;
-    if (!v.rows) return fail(IQLHIP_ERR_INVALID, "null replay view %d", k);
-    if (v.state_dim != c.state_dim || v.action_dim != c.action_dim)
-      return fail(IQLHIP_ERR_INVALID, "replay dims (%d,%d) do not match the trainer (%d,%d)", v.state_dim,
-                  v.action_dim, c.state_dim, c.action_dim);
-    if (v.n_rows <= 0) return fail(IQLHIP_ERR_INVALID, "cannot sample from an empty replay buffer");
-    if (v.row_stride != iqlhip_replay_row_stride(v.state_dim, v.action_dim))
-      return fail(IQLHIP_ERR_INVALID, "row_stride %d is not the packed layout's", v.row_stride);
+    if (!views[k].rows) return fail(IQLHIP_ERR_INVALID, "null replay view %d", k);
+    if (int rc = check_view(views[k], g->tr[k]->cfg)) return rc;
   }
   if (n_steps == 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
-  if (g->deep) {
-    DevArgs a[IQLHIP_MAX_GROUP];
-    for (int k = 0; k < g->K; ++k) {
-      const iqlhip_trainer *t = g->tr[k];
-      memset(&a[k], 0, sizeof(DevArgs));
-      a[k].rows = views[k].rows, a[k].n_rows = views[k].n_rows, a[k].row_stride = views[k].row_stride;
-      a[k].idx = idx ? idx[k] : nullptr;
-      a[k].idx_mode = a[k].idx ? 1 : 0;
-      a[k].drop_keep = dropout_keep ? dropout_keep[k] : nullptr;
-      a[k].losses_out = losses_out ? losses_out[k] : nullptr;
-      a[k].base_step = t->total_it;
-      a[k].lr_q = t->lr_q, a[k].lr_v = t->lr_v, a[k].lr_a_base = t->lr_a_base;
-    }
-    const DeepRun r = {g->tr, g->K, &g->deep_ring, g->gdeep, &g->gexec, &g->graph_unroll,
-                       &g->cap_stream, &g->throttle, g->timing, g->ev, g->t_acc, &g->t_empty, &g->t_n, &g->n_eager,
-                       &g->n_graph};
-    if (int rc = deep_run(r, a, n_steps, graph_unroll, st)) return rc;
-    for (int k = 0; k < g->K; ++k) g->tr[k]->total_it += n_steps;
-    return 0;
-  }
-  // ---- K DevArgs through one pinned slot, one copy (skipped when the call continues the last) ----
   DevArgs want[IQLHIP_MAX_GROUP];
-  bool same = g->tr[0]->D.prefetch && g->dev_args_valid && !g->timing, all_philox = true;
   for (int k = 0; k < g->K; ++k) {
     iqlhip_trainer *t = g->tr[k];
-    DevArgs a;
-    memset(&a, 0, sizeof(a));
-    a.rows = views[k].rows, a.n_rows = views[k].n_rows, a.row_stride = views[k].row_stride;
-    a.generation = views[k].generation;
-    a.idx = idx ? idx[k] : nullptr;
-    a.idx_mode = a.idx ? 1 : 0;
-    a.drop_keep = dropout_keep ? dropout_keep[k] : nullptr;
-    a.losses_out = losses_out ? losses_out[k] : nullptr;
-    a.n_valid = n_valid ? n_valid[k] : nullptr;  // (`continues` is false with counts on either side)
-    a.base_step = t->total_it;
-    a.lr_q = t->lr_q, a.lr_v = t->lr_v, a.lr_a_base = t->lr_a_base;
-    a.n_steps = n_steps;
-    want[k] = a;
-    same = same && continues(g->dev_args[k], a);
-    all_philox = all_philox && a.idx_mode == 0;
-    t->dev_args_valid = false;  // a member's own next call starts from scratch
+    want[k] = make_args(t, views[k], n_steps, idx ? idx[k] : nullptr, n_valid ? n_valid[k] : nullptr,
+                        dropout_keep ? dropout_keep[k] : nullptr, losses_out ? losses_out[k] : nullptr);
+    t->queue.dev_args_valid = false;  // a member's own next call starts from scratch
   }
-  if (!same) {
-    const int slot = g->harg_head;
-    g->harg_head = (slot + 1) % iqlhip_group::ARG_RING;
-    if (!g->harg[slot]) {
-      HIP_TRY(hipHostMalloc((void **)&g->harg[slot], sizeof(DevArgs) * g->K, hipHostMallocDefault));
-      HIP_TRY(hipEventCreateWithFlags(&g->harg_ev[slot], hipEventDisableTiming));
-    }
-    if (g->harg_used[slot]) HIP_TRY(hipEventSynchronize(g->harg_ev[slot]));
-    for (int k = 0; k < g->K; ++k) g->harg[slot][k] = g->dev_args[k] = want[k];
-    HIP_TRY(hipMemcpyAsync(g->gargs, g->harg[slot], sizeof(DevArgs) * g->K, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipEventRecord(g->harg_ev[slot], st));
-    g->harg_used[slot] = true;
-    if (g->tr[0]->D.prefetch)
-      HIP_TRY(launch_stage(g->tr[0]->bf16, g->tr[0]->D, g->gdesc, g->gargs, g->gctr, g->K, st));
-  }
-  g->dev_args_valid = all_philox;
-  // ---- the steps: hipGraphs of `graph_unroll` steps, the remainder eagerly ----
-  int64_t done = 0;
-  if (g->timing) {  // one event pair per kernel; diagnostic mode only
-    iqlhip_trainer *t0 = g->tr[0];
-    for (; done < n_steps; ++done) {
-      if (!t0->D.prefetch) HIP_TRY(launch_stage(t0->bf16, t0->D, g->gdesc, g->gargs, g->gctr, g->K, st));
-      HIP_TRY(hipEventRecord(g->ev[0], st));
-      HIP_TRY(launch_forward(t0->bf16, t0->D, g->gdesc, g->gargs, g->gctr, g->K, st));
-      HIP_TRY(hipEventRecord(g->ev[1], st));
-      HIP_TRY(launch_backward(t0->bf16, t0->D, g->gdesc, g->gargs, g->gctr, g->K, st, counts));
-      HIP_TRY(hipEventRecord(g->ev[2], st));
-      HIP_TRY(launch_update(t0->bf16, g->gdesc, g->gargs, g->gctr, g->gitems, g->n_items, g->K, st));
-      HIP_TRY(hipEventRecord(g->ev[3], st));
-      HIP_TRY(hipEventRecord(g->ev[4], st));
-      HIP_TRY(hipEventSynchronize(g->ev[4]));
-      for (int k = 0; k < 3; ++k) {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, g->ev[k], g->ev[k + 1]));
-        g->t_acc[k] += ms;
-      }
-      float ems = 0.f;
-      HIP_TRY(hipEventElapsedTime(&ems, g->ev[3], g->ev[4]));
-      g->t_empty += ems;
-      g->t_n++;
-      g->n_eager++;
-    }
-    for (int k = 0; k < g->K; ++k) g->tr[k]->total_it += n_steps;
-    return 0;
-  }
-  if (graph_unroll > 0 && n_steps >= graph_unroll) {
-    // (the graph holds either the counted or the plain k_backward)
-    if (!g->gexec || g->graph_unroll != graph_unroll || g->graph_counts != counts) {
-      if (g->gexec) {
-        (void)hipGraphExecDestroy(g->gexec);
-        g->gexec = nullptr;
-      }
-      hipGraph_t gr = nullptr;
-      if (!g->cap_stream) HIP_TRY(capture_stream(&g->cap_stream));
-      HIP_TRY(hipStreamBeginCapture(g->cap_stream, hipStreamCaptureModeThreadLocal));
-      int rc = 0;
-      for (int u = 0; u < graph_unroll && !rc; ++u) rc = group_enqueue_step(g, g->cap_stream, counts);
-      hipError_t ce = hipStreamEndCapture(g->cap_stream, &gr);
-      if (rc) return rc;
-      HIP_TRY(ce);
-      HIP_TRY(hipGraphInstantiate(&g->gexec, gr, nullptr, nullptr, 0));
-      (void)hipGraphDestroy(gr);
-      g->graph_unroll = graph_unroll, g->graph_counts = counts;
-    }
-    for (; done + graph_unroll <= n_steps; done += graph_unroll) {
-      HIP_TRY(hipGraphLaunch(g->gexec, st));
-      g->n_graph++;
-      HIP_TRY(g->throttle.queued(3 * (int64_t)graph_unroll, st));
-    }
-  }
-  for (; done < n_steps; ++done) {
-    if (int rc = group_enqueue_step(g, st, counts)) return rc;
-    g->n_eager++;
-    HIP_TRY(g->throttle.queued(3, st));
-  }
+  const iqlhip_trainer *t0 = g->tr[0];
+  const StepTarget x = {t0->bf16, t0->D, g->gdesc, g->gargs, g->gctr, g->gitems, g->n_items, g->K};
+  const int rc = g->deep ? deep_run({g->tr, g->K, &g->deep_ring, g->gdeep, g->queue}, want, n_steps, graph_unroll,
+                                    (hipStream_t)stream)
+                         : run_tuned(g->queue, x, want, n_steps, graph_unroll, counts, (hipStream_t)stream);
+  if (rc) return rc;
   for (int k = 0; k < g->K; ++k) g->tr[k]->total_it += n_steps;
   return 0;
 }
 
-
 extern "C" int iqlhip_group_set_timing(iqlhip_group *g, int32_t enable) {
-  if (!g) return fail(IQLHIP_ERR_INVALID, "null group");
-  g->timing = enable != 0;
-  g->t_acc[0] = g->t_acc[1] = g->t_acc[2] = 0, g->t_empty = 0, g->t_n = 0;
-  if (g->timing)
-    for (auto &e : g->ev)
-      if (!e) HIP_TRY(hipEventCreate(&e));
-  return 0;
+  return g ? g->queue.set_timing(enable != 0) : fail(IQLHIP_ERR_INVALID, "null group");
 }
 
-extern "C" int iqlhip_trainer_launch_counts(iqlhip_trainer *t, int64_t *eager_steps, int64_t *graph_launches) {
-  if (!t) return fail(IQLHIP_ERR_INVALID, "null trainer");
-  if (eager_steps) *eager_steps = t->n_eager;
-  if (graph_launches) *graph_launches = t->n_graph;
+extern "C" int iqlhip_group_get_timing(iqlhip_group *g, double avg_ms[3], int64_t *n) {
+  if (!g) return fail(IQLHIP_ERR_INVALID, "null group");
+  g->queue.get_timing(avg_ms, n);
   return 0;
 }
 
 extern "C" int iqlhip_group_launch_counts(iqlhip_group *g, int64_t *eager_steps, int64_t *graph_launches) {
   if (!g) return fail(IQLHIP_ERR_INVALID, "null group");
-  if (eager_steps) *eager_steps = g->n_eager;
-  if (graph_launches) *graph_launches = g->n_graph;
+  g->queue.launch_counts(eager_steps, graph_launches);
   return 0;
 }
 
@@ -1611,16 +1466,6 @@ extern "C" int iqlhip_stream_create_cu_slice(void **stream, int32_t slice, int32
 }
 extern "C" int iqlhip_stream_destroy(void *stream) {
   if (stream) HIP_TRY(hipStreamDestroy((hipStream_t)stream));
-  return 0;
-}
-
-extern "C" int iqlhip_group_get_timing(iqlhip_group *g, double avg_ms[3], int64_t *n) {
-  if (!g) return fail(IQLHIP_ERR_INVALID, "null group");
-  for (int k = 0; k < 3; ++k) {
-    const double v = g->t_n ? (g->t_acc[k] - g->t_empty) / (double)g->t_n : 0.0;
-    avg_ms[k] = v > 0 ? v : 0.0;
-  }
-  if (n) *n = g->t_n;
   return 0;
 }
 
@@ -1690,10 +1535,7 @@ extern "C" int iqlhip_trainer_set_debug(iqlhip_trainer *t, void *buf) {
   if (t->deep) return fail(IQLHIP_ERR_UNSUPPORTED, "no stamps in the general step");
   t->D.dbg = reinterpret_cast<unsigned long long *>(buf);
   HIP_TRY(hipMemcpy(t->ddesc, &t->D, sizeof(TrainerDesc), hipMemcpyHostToDevice));
-  if (t->gexec) {
-    (void)hipGraphExecDestroy(t->gexec);
-    t->gexec = nullptr;
-  }
+  t->queue.drop_graph();
   return 0;
 }
 
