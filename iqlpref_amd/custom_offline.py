@@ -19,7 +19,9 @@ Differences from ``algorithms/offline/iql.py`` and how they map onto the same ke
 * ``modify_reward``: only the locomotion range scaling and antmaze's -1 (cref:145-155).
 
 ``train()`` is cref:597-749 with the absent services (minari, the Orbax reward-model readers,
-wandb) injectable, and ``seeds_per_gpu`` seeds side by side on one GPU.
+wandb) injectable, and ``seeds_per_gpu`` seeds side by side on one GPU.  Its setup (``_train``) is shared
+with ``custom_offline_br``; the train / evaluate / checkpoint loop itself is ``_offline_loop.run``, which
+the BB flavour runs too.
 
 Not built (stated): the Orbax / flax-nnx checkpoint readers ``load_PT`` / ``load_QMLP``
 (reward_models/pref_transformer.py:280-327, q_mlp.py:100-168) need orbax + jax, which are absent;
@@ -29,14 +31,14 @@ arrays instead.  PT numerics stay "parity unpinned" (no runnable reference, no f
 import ctypes as C
 import uuid
 import os
-from dataclasses import asdict, dataclass
-from typing import Any, Callable, Dict, Iterable, List, Optional, Sequence
+from dataclasses import dataclass
+from typing import Any, Callable, Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _lib, _offline_loop
 from . import distributed as D
 from ._lib import check, ptr
 from .iql import DeterministicPolicy, GaussianPolicy, TwinQ, ValueFunction, compute_mean_std, normalize_states, set_seed
@@ -150,10 +152,18 @@ def load_pt_flax_params(model: RewardPT, params: Dict[str, Any]) -> RewardPT:
 # --------------------------------------------------------------------------- #
 # dataset (cref:158-225)
 # --------------------------------------------------------------------------- #
-def _episode_arrays(ep):
-    get = (lambda k: ep[k]) if isinstance(ep, dict) else (lambda k: getattr(ep, k))
-    return (np.asarray(get("observations"), np.float32), np.asarray(get("actions"), np.float32),
-            np.asarray(get("terminations")))
+def _concat_episodes(dataset: Iterable) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, List[int]]:
+    """Episodes (Minari ``EpisodeData`` or dicts) -> the per-step arrays (observations, actions, next
+    observations, terminations) of all of them end to end, and the number of steps of each."""
+    obs, act, nxt, dones = [], [], [], []
+    for ep in dataset:
+        get = ep.__getitem__ if isinstance(ep, dict) else (lambda k: getattr(ep, k))
+        o = np.asarray(get("observations"), np.float32)
+        obs.append(o[:-1]), nxt.append(o[1:])
+        act.append(np.asarray(get("actions"), np.float32))
+        dones.append(np.asarray(get("terminations")))
+    return (np.concatenate(obs), np.concatenate(act), np.concatenate(nxt), np.concatenate(dones),
+            [a.shape[0] for a in act])
 
 
 def episode_windows(lengths: Sequence[int], query_length: int):
@@ -169,16 +179,12 @@ def episode_windows(lengths: Sequence[int], query_length: int):
 def qlearning_dataset(dataset: Iterable, r_model, query_length: int = 1) -> Dict[str, np.ndarray]:
     """cref:158-225.  ``dataset`` iterates episodes (Minari ``EpisodeData`` or dicts) with
     ``observations`` [L+1, S], ``actions`` [L, A], ``terminations`` [L]."""
-    eps = [_episode_arrays(e) for e in dataset]
-    obs = np.concatenate([o[:-1] for o, _, _ in eps])
-    nxt = np.concatenate([o[1:] for o, _, _ in eps])
-    act = np.concatenate([a for _, a, _ in eps])
-    dones = np.concatenate([d for _, _, d in eps])
+    obs, act, nxt, dones, lengths = _concat_episodes(dataset)
     if query_length > 1:
         if not isinstance(r_model, RewardPT):
             raise TypeError("query_length > 1 needs an iqlpref_amd RewardPT")
         dev = next(r_model.parameters()).device
-        start, length, t0 = episode_windows([a.shape[0] for _, a, _ in eps], query_length)
+        start, length, t0 = episode_windows(lengths, query_length)
         up = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
         rewards = r_model.window_values(up(obs), up(act), up(start), up(length), query_length,
                                         win_t0=up(t0)).cpu().numpy()
@@ -226,9 +232,6 @@ def evaluate(env, actor: nn.Module, num_episodes: int, seed: int, device: str) -
     return np.asarray(episode_rewards)
 
 
-# --------------------------------------------------------------------------- #
-# buffer and trainer
-# --------------------------------------------------------------------------- #
 # --------------------------------------------------------------------------- #
 # numpy's legacy randint on the device (csrc/np_sampler.hip)
 # --------------------------------------------------------------------------- #
@@ -325,6 +328,9 @@ class NumpyIndexStream:
         return [area[k, :n * B].view(n, B) for k in range(K)]
 
 
+# --------------------------------------------------------------------------- #
+# buffer and trainer
+# --------------------------------------------------------------------------- #
 class ReplayBuffer(_OfflineReplayBuffer):
     """cref:228-290: ``load_dataset`` + a sampler on numpy's GLOBAL generator -- after
     ``np.random.seed(s)`` the index stream is the reference's, draw for draw."""
@@ -397,17 +403,17 @@ class ImplicitQLearning(_OfflineIQL):
 # --------------------------------------------------------------------------- #
 # train (cref:597-749)
 # --------------------------------------------------------------------------- #
-def _reward_model_missing(config: "TrainConfig"):
+def _reward_model_missing(where: str, config, advice: str, readers: str):
+    """``where`` got ``reward_model=None``: the reference would read an Orbax checkpoint with ``readers``,
+    which are not built here.  ``advice``: what to pass instead."""
     try:
         import orbax.checkpoint  # noqa: F401
     except ImportError:
         raise ImportError(
-            f"custom_offline.train: reward_model=None would read the Orbax checkpoint {config.reward_model_path!r}, "
-            "but orbax is not installed (and iqlpref_amd has no Orbax reader); pass reward_model= a QMLP or "
-            "RewardPT holding its parameters (load_flax_params)") from None
+            f"{where}: reward_model=None would read the Orbax checkpoint {config.reward_model_path!r}, "
+            f"but orbax is not installed (and iqlpref_amd has no Orbax reader); pass reward_model= {advice}") from None
     raise NotImplementedError(
-        "custom_offline.train: iqlpref_amd has no Orbax checkpoint reader (load_QMLP / load_PT); pass "
-        "reward_model= a QMLP or RewardPT holding its parameters (load_flax_params)")
+        f"{where}: iqlpref_amd has no Orbax checkpoint reader ({readers}); pass reward_model= {advice}")
 
 
 def _minari():
@@ -419,21 +425,24 @@ def _minari():
     return minari
 
 
-def _build_trainer(config: "TrainConfig", seed: int, state_dim: int, action_dim: int, max_action: float,
-                   device: str) -> "ImplicitQLearning":
+def _build_trainer(config, seed: int, state_dim: int, action_dim: int, limits: Sequence, device: str,
+                   policies=(GaussianPolicy, DeterministicPolicy), trainer_cls=ImplicitQLearning):
     """cref:655-689 for one seed: the nets are built right after ``torch.manual_seed(seed)`` on the
-    CPU generator (in cref's order), then moved to the device."""
+    CPU generator (in cref's order), then moved to the device.  ``limits``: the action limits that the
+    policy and the trainer take ahead of their other arguments -- ``(max_action,)`` here, ``(max_actions,
+    min_actions)`` for the BB flavour, which also hands in its own ``policies`` (Gaussian, deterministic)
+    and ``trainer_cls``."""
     torch.manual_seed(seed)
     q_network = TwinQ(state_dim, action_dim).to(device)
     v_network = ValueFunction(state_dim).to(device)
-    pol = DeterministicPolicy if config.iql_deterministic else GaussianPolicy
-    actor = pol(state_dim, action_dim, max_action, dropout=config.actor_dropout).to(device)
+    pol = policies[1] if config.iql_deterministic else policies[0]
+    actor = pol(state_dim, action_dim, *limits, dropout=config.actor_dropout).to(device)
     v_optimizer = torch.optim.Adam(v_network.parameters(), lr=config.vf_lr)
     q_optimizer = torch.optim.Adam(q_network.parameters(), lr=config.qf_lr)
     actor_optimizer = torch.optim.Adam(actor.parameters(), lr=config.actor_lr)
     actor_lr_scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(actor_optimizer, config.update_steps)
-    return ImplicitQLearning(
-        max_action=max_action, actor=actor, actor_optimizer=actor_optimizer, actor_lr_scheduler=actor_lr_scheduler,
+    return trainer_cls(
+        *limits, actor=actor, actor_optimizer=actor_optimizer, actor_lr_scheduler=actor_lr_scheduler,
         q_network=q_network, q_optimizer=q_optimizer, v_network=v_network, v_optimizer=v_optimizer,
         iql_tau=config.iql_tau, beta=config.beta, gamma=config.gamma, tau=config.tau, device=device, seed=seed)
 
@@ -441,8 +450,7 @@ def _build_trainer(config: "TrainConfig", seed: int, state_dim: int, action_dim:
 def train(config: TrainConfig, dataset=None, reward_model=None, eval_env=None, *,
           logger: Optional[Callable[[Dict[str, float], int], None]] = None,
           normalized_score: Optional[Callable] = None, seeds_per_gpu: int = 1, sampler: str = "device",
-          device: Optional[str] = None, chunk: int = 2000, _relabel: Optional[Callable] = None,
-          _best_by_return: bool = False):
+          device: Optional[str] = None, chunk: int = 2000):
     """cref:597-749 on the fused HIP step.
 
     ``dataset``: an iterable of Minari-style episodes (``observations``, ``actions``,
@@ -456,18 +464,27 @@ def train(config: TrainConfig, dataset=None, reward_model=None, eval_env=None, *
     (numpy); both give the same indices and the same final generator state.
 
     The steps run in chunks of at most ``chunk`` that end on evaluation boundaries; the losses of a
-    chunk come back to the host once, after the next chunk has been queued.
+    chunk come back to the host once, after the next chunk has been queued (``_offline_loop.run``).
 
     ``seeds_per_gpu`` = K > 1: seed k is ``train_seed + rank K + k``, with its own nets (built right
     after ``torch.manual_seed(seed)``), its own ``np.random.RandomState(seed)`` index stream (the
     stream ``np.random.seed(seed)`` gives), its own checkpoints under ``seed_<seed>/`` and a ``seed``
     entry in its logger records; all K share one buffer and step as one ``SeedGroup`` with the
     indices of one K-stream draw.  Every seed is bit-identical to ``train()`` of that seed alone.
-    Returns the trainer (K = 1) or the list of K trainers.
+    Returns the trainer (K = 1) or the list of K trainers."""
+    relabel = None
+    if reward_model is not None:
+        relabel = lambda ds: qlearning_dataset(ds, reward_model, config.query_length)
+    return _train(config, dataset, eval_env, relabel, False, logger=logger, normalized_score=normalized_score,
+                  seeds_per_gpu=seeds_per_gpu, sampler=sampler, device=device, chunk=chunk)
 
-    Private, for the flavours that share this loop (``custom_offline_br.train``): ``_relabel(dataset)``
-    builds the transition dict in place of ``qlearning_dataset``; ``_best_by_return`` keeps the best
-    model by the mean evaluation return even when a normalized score is logged."""
+
+def _train(config, dataset, eval_env, relabel: Optional[Callable], best_by_return: bool, *, logger=None,
+           normalized_score=None, seeds_per_gpu: int = 1, sampler: str = "device", device=None, chunk: int = 2000):
+    """``train()`` with the two things a flavour chooses: ``relabel(dataset)`` builds the transition dict
+    (None: there is no reward model to build it with, which is reported after the other argument checks), and
+    ``best_by_return`` keeps the best model by the mean evaluation return even when a normalized score is
+    logged (``custom_offline_br``)."""
     if sampler not in ("host", "device"):
         raise ValueError("sampler must be 'host' or 'device'")
     K = int(seeds_per_gpu)
@@ -489,17 +506,15 @@ def train(config: TrainConfig, dataset=None, reward_model=None, eval_env=None, *
             normalized_score = minari.get_normalized_score
         except ImportError:
             normalized_score = None
-    if reward_model is None and _relabel is None:
-        _reward_model_missing(config)
+    if relabel is None:
+        _reward_model_missing("custom_offline.train", config,
+                              "a QMLP or RewardPT holding its parameters (load_flax_params)", "load_QMLP / load_PT")
     state_dim = eval_env.observation_space.shape[0]
     action_dim = eval_env.action_space.shape[0]
     max_action = float(eval_env.action_space.high[0])
 
     # ---- dataset, normalisation, buffer (cref:631-653) ----
-    if _relabel is not None:
-        qdataset = _relabel(dataset)
-    else:
-        qdataset = qlearning_dataset(dataset, reward_model, config.query_length)
+    qdataset = relabel(dataset)
     if config.normalize_reward:
         modify_reward(qdataset, config.dataset_id)
     if config.normalize_state:
@@ -514,98 +529,36 @@ def train(config: TrainConfig, dataset=None, reward_model=None, eval_env=None, *
     replay_buffer.load_dataset(qdataset)
 
     seeds = [D.rank_seed(config.train_seed, K) + k for k in range(K)]
-    ckpt_dirs: List[Optional[str]] = [None] * K
-    if config.checkpoints_path is not None:
-        print(f"Checkpoints path: {config.checkpoints_path}")
-        os.makedirs(config.checkpoints_path, exist_ok=True)
-        import yaml
-        with open(os.path.join(config.checkpoints_path, "config.yaml"), "w") as f:
-            yaml.safe_dump(asdict(config), f)
-        for k in range(K):
-            ckpt_dirs[k] = config.checkpoints_path if K == 1 else os.path.join(config.checkpoints_path,
-                                                                               f"seed_{seeds[k]}")
-            os.makedirs(ckpt_dirs[k], exist_ok=True)
+    ckpt_dirs = _offline_loop.checkpoint_dirs(config, seeds)
 
     # ---- seeds and nets (cref:659-689) ----
     set_seed(seeds[0])  # np, random, torch, PYTHONHASHSEED
     gens = [None] if K == 1 else [np.random.RandomState(s) for s in seeds]  # None: numpy's global generator
-    trainers = [_build_trainer(config, s, state_dim, action_dim, max_action, device) for s in seeds]
+    trainers = [_build_trainer(config, s, state_dim, action_dim, (max_action,), device) for s in seeds]
     group = None
     if K > 1:
         from .multi import SeedGroup
         group = SeedGroup(trainers)
     stream = NumpyIndexStream(device) if sampler == "device" else None
-
     if logger is None:
-        try:
-            import wandb
-            wandb.init(config=asdict(config), project=config.project, group=config.group, name=config.name,
-                       id=str(uuid.uuid4()))
-            logger = (lambda d, step: wandb.log(d, step=step)) if K == 1 else \
-                (lambda d, step: wandb.log({f"seed{int(d['seed'])}/{n}": v for n, v in d.items() if n != "seed"},
-                                           step=step))
-        except ImportError:
-            logger = lambda d, step: print(f"[{step}] " + " ".join(f"{n}={v:.5g}" for n, v in d.items()))
-    tag = (lambda rec, k: rec) if K == 1 else (lambda rec, k: dict(rec, seed=seeds[k]))
+        logger = _offline_loop.default_logger(config, K)
 
-    best_score = [-np.inf] * K
-    best_step = [0] * K
-    norm = [None] * K  # cref's `normalized_score`: once set it stays (cref:711-718)
-    pending = None  # (first step, [K] device losses) of the chunk whose records are still to be logged
-
-    def flush():
-        nonlocal pending
-        if pending is None:
-            return
-        t0, losses = pending
-        pending = None
-        for k, arr in enumerate(l.cpu().numpy() for l in losses):
-            for i, (v, q, a) in enumerate(arr.tolist()):
-                logger(tag({"value_loss": v, "q_loss": q, "actor_loss": a}, k), t0 + i)
-
-    total, every, t = int(config.update_steps), int(config.eval_every), 0
-    while t < total:
-        nxt = min(total, t + int(chunk), (t // every + 1) * every)
-        n = nxt - t
-        if sampler == "device":
+    def steps(t, n):
+        if stream is not None:
             idx = stream.draw(replay_buffer.index_bound(), n, config.batch_size, gens)
         else:
             idx = [torch.from_numpy(replay_buffer.draw_indices(config.batch_size, n, rng=g)).to(trainers[0]._dev)
                    for g in gens]
         if group is None:
-            losses = [trainers[0].train_steps(replay_buffer, n, config.batch_size, indices=idx[0])]
-        else:
-            losses = group.train_steps(replay_buffer, n, config.batch_size, indices=idx, return_losses=True)
-        flush()
-        pending = (t, losses)
-        t = nxt
-        if t % every != 0:
-            continue
-        flush()
-        if group is not None:
-            group.synchronize()
-        step = t - 1
-        for k, trainer in enumerate(trainers):
-            log = lambda d: logger(tag(d, k), step)
-            eval_scores = evaluate(eval_env, trainer.actor, config.eval_episodes, config.eval_seed, device)
-            mean_eval = eval_scores.mean()
-            log({"evaluation_return": mean_eval})
-            if normalized_score is not None:
-                try:
-                    norm[k] = np.asarray(normalized_score(dataset, eval_scores)).mean() * 100
-                    log({"normalized_score": norm[k]})
-                except ValueError:
-                    pass
-            score = norm[k] if norm[k] is not None and not _best_by_return else mean_eval
-            if score > best_score[k]:
-                best_score[k], best_step[k] = score, step
-                if ckpt_dirs[k] is not None:
-                    torch.save(trainer.state_dict(), os.path.join(ckpt_dirs[k], "best_model.pt"))
-            log({"best_score_so_far": best_score[k]})
-            log({"best_step_so_far": best_step[k]})
-            if ckpt_dirs[k] is not None:
-                torch.save(trainer.state_dict(), os.path.join(ckpt_dirs[k], f"checkpoint_{step}.pt"))
-    flush()
+            return [trainers[0].train_steps(replay_buffer, n, config.batch_size, indices=idx[0])]
+        return group.train_steps(replay_buffer, n, config.batch_size, indices=idx, return_losses=True)
+
+    _offline_loop.run(
+        trainers, seeds, group, int(config.update_steps), int(config.eval_every), chunk, logger, ckpt_dirs, steps,
+        evaluate=lambda k, trainer, step: evaluate(eval_env, trainer.actor, config.eval_episodes, config.eval_seed,
+                                                   device),
+        normalized=None if normalized_score is None else (lambda scores: normalized_score(dataset, scores)),
+        best_by_return=best_by_return)
     if group is not None:
         group.synchronize()
         group.close()

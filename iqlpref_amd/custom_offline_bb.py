@@ -17,7 +17,8 @@ Differences from ``custom_offline`` (``iql.py``) and how they map onto the same 
 * ``act()`` clamps per dimension to ``[min_actions, max_actions]`` without scaling (bref:344-350);
   the maximum speed is the 99th percentile of ``actions[:, 0]``, the angle range +-180;
 * the Polyak form, no autocast, the cosine actor schedule and the checkpoint keys are those of
-  ``custom_offline``.
+  ``custom_offline``, whose ``_build_trainer`` builds the trainer; the train / evaluate / checkpoint loop is
+  ``_offline_loop.run``, as for the other custom flavours.
 
 ``bb_run_eval_IQL`` is the evaluation of bref:675-867: a numpy simulator of a point agent that steers
 to a goal among drifting obstacles, rewarded by the preference model over a rolling context.  It makes
@@ -36,21 +37,22 @@ Sweeps and bf16 are not offered for this flavour.
 import ctypes as C
 import os
 import uuid
-from dataclasses import asdict, dataclass
+from dataclasses import dataclass
 from typing import Any, Callable, Dict, List, Mapping, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _lib, _offline_loop
+from . import custom_offline as _co
 from . import distributed as D
 from ._lib import check, ptr, stream_ptr
 from .custom_offline import ImplicitQLearning as _CustomIQL
 from .custom_offline import ReplayBuffer
 from .iql import DeterministicPolicy as _DeterministicPolicy
 from .iql import GaussianPolicy as _GaussianPolicy
-from .iql import TwinQ, ValueFunction, set_seed
+from .iql import set_seed
 from .relabel import RewardPT
 
 DATASET_KEYS = ("states", "actions", "rewards", "n_rewards", "next_states", "attn_mask")
@@ -500,42 +502,6 @@ class RewardPTContext:
 # --------------------------------------------------------------------------- #
 # train (bref:870-1027)
 # --------------------------------------------------------------------------- #
-def _reward_model_missing(config: "TrainConfig"):
-    try:
-        import orbax.checkpoint  # noqa: F401
-    except ImportError:
-        raise ImportError(
-            f"custom_offline_bb.train: reward_model=None would read the Orbax checkpoint {config.reward_model_path!r}, "
-            "but orbax is not installed (and iqlpref_amd has no Orbax reader); pass reward_model= a callable with "
-            "the reference's call shape (RewardPTContext wraps a RewardPT)") from None
-    raise NotImplementedError(
-        "custom_offline_bb.train: iqlpref_amd has no Orbax checkpoint reader (load_PT); pass reward_model= a "
-        "callable with the reference's call shape (RewardPTContext wraps a RewardPT)")
-
-
-def _build_trainer(config: "TrainConfig", state_dim: int, action_dim: int, max_actions, min_actions,
-                   device: str, seed: Optional[int] = None) -> ImplicitQLearning:
-    """bref:923-962: nets on the CPU generator in the reference's order, then moved to the device.  ``seed``
-    (a member of a seed group): the nets are built right after ``torch.manual_seed(seed)``."""
-    if seed is None:
-        seed = config.train_seed
-    else:
-        torch.manual_seed(seed)
-    q_network = TwinQ(state_dim, action_dim).to(device)
-    v_network = ValueFunction(state_dim).to(device)
-    pol = DeterministicPolicy if config.iql_deterministic else GaussianPolicy
-    actor = pol(state_dim, action_dim, max_actions, min_actions, dropout=config.actor_dropout).to(device)
-    v_optimizer = torch.optim.Adam(v_network.parameters(), lr=config.vf_lr)
-    q_optimizer = torch.optim.Adam(q_network.parameters(), lr=config.qf_lr)
-    actor_optimizer = torch.optim.Adam(actor.parameters(), lr=config.actor_lr)
-    actor_lr_scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(actor_optimizer, config.update_steps)
-    return ImplicitQLearning(
-        max_actions=max_actions, min_actions=min_actions, actor=actor, actor_optimizer=actor_optimizer,
-        actor_lr_scheduler=actor_lr_scheduler, q_network=q_network, q_optimizer=q_optimizer, v_network=v_network,
-        v_optimizer=v_optimizer, iql_tau=config.iql_tau, beta=config.beta, gamma=config.gamma, tau=config.tau,
-        device=device, seed=seed)
-
-
 def group_seeds(train_seed: int, seeds_per_gpu: int) -> List[int]:
     """The seeds of the K runs of this rank: ``rank_seed(train_seed, K) + k``."""
     K = int(seeds_per_gpu)
@@ -563,7 +529,7 @@ def train(config: TrainConfig, dataset=None, reward_model=None, move_stats=None,
     a chunk are written on the device, and its losses come back to the host once, after the next chunk has
     been queued.  Returns the trainer.
 
-    ``seeds_per_gpu`` = K > 1 (the loop of ``custom_offline.train``): seed k is ``rank_seed(train_seed, K) + k``, with its own nets (built right after
+    ``seeds_per_gpu`` = K > 1: seed k is ``rank_seed(train_seed, K) + k``, with its own nets (built right after
     ``torch.manual_seed(seed)``), its own block permutation (``perm``: a sequence of K permutations; None: K
     draws in member order from torch's global generator, before any seed is set), its own evaluations
     (``seed = eval_seed + step``, as K separate runs), best score and checkpoints under ``seed_<seed>/``, and a
@@ -577,7 +543,8 @@ def train(config: TrainConfig, dataset=None, reward_model=None, move_stats=None,
     if device is None:
         device = D.local_device() or "cuda:0"
     if reward_model is None:
-        _reward_model_missing(config)
+        _co._reward_model_missing("custom_offline_bb.train", config, "a callable with the reference's call shape "
+                                  "(RewardPTContext wraps a RewardPT)", "load_PT")
     if move_stats is None:
         move_stats = load_stats(config.move_stats_path)
     if dataset is None:
@@ -592,24 +559,14 @@ def train(config: TrainConfig, dataset=None, reward_model=None, move_stats=None,
         samplers = BlockEpochSamplerGroup.draw(len(dataset), config.batch_size, K, perm)
     state_shape, action_shape = dataset.shapes()
     state_dim, action_dim = state_shape[1], action_shape[1]
-    max_actions = dataset.max_actions().to(device)
-    min_actions = dataset.min_actions().to(device)
+    limits = (dataset.max_actions().to(device), dataset.min_actions().to(device))
+    ckpt_dirs = _offline_loop.checkpoint_dirs(config, seeds)
 
-    ckpt_dirs: List[Optional[str]] = [None] * K
-    if config.checkpoints_path is not None:
-        print(f"Checkpoints path: {config.checkpoints_path}")
-        os.makedirs(config.checkpoints_path, exist_ok=True)
-        import yaml
-        with open(os.path.join(config.checkpoints_path, "config.yaml"), "w") as f:
-            yaml.safe_dump(asdict(config), f)
-        for k in range(K):
-            ckpt_dirs[k] = config.checkpoints_path if K == 1 else os.path.join(config.checkpoints_path,
-                                                                               f"seed_{seeds[k]}")
-            os.makedirs(ckpt_dirs[k], exist_ok=True)
-
+    # with K == 1 set_seed has just called torch.manual_seed(train_seed) and nothing has drawn since, so
+    # _build_trainer's own torch.manual_seed(seed) leaves the generator where it is
     set_seed(seeds[0])  # np, random, torch, PYTHONHASHSEED
-    trainers = [_build_trainer(config, state_dim, action_dim, max_actions, min_actions, device,
-                               seed=None if K == 1 else s) for s in seeds]
+    trainers = [_co._build_trainer(config, s, state_dim, action_dim, limits, device,
+                                   (GaussianPolicy, DeterministicPolicy), ImplicitQLearning) for s in seeds]
     group = None
     if K > 1:
         from .multi import SeedGroup
@@ -618,66 +575,22 @@ def train(config: TrainConfig, dataset=None, reward_model=None, move_stats=None,
     replay_buffer.load_dataset(dataset.transitions())
     if K > 1 and samplers.n_rows != replay_buffer.index_bound():
         raise ValueError(f"the samplers walk {samplers.n_rows} rows, the buffer holds {replay_buffer.index_bound()}")
-
     if logger is None:
-        try:
-            import wandb
-            wandb.init(config=asdict(config), project=config.project, group=config.group, name=config.name,
-                       id=str(uuid.uuid4()))
-            logger = (lambda d, step: wandb.log(d, step=step)) if K == 1 else \
-                (lambda d, step: wandb.log({f"seed{int(d['seed'])}/{n}": v for n, v in d.items() if n != "seed"},
-                                           step=step))
-        except ImportError:
-            logger = lambda d, step: print(f"[{step}] " + " ".join(f"{n}={v:.5g}" for n, v in d.items()))
-    tag = (lambda rec, k: rec) if K == 1 else (lambda rec, k: dict(rec, seed=seeds[k]))
+        logger = _offline_loop.default_logger(config, K)
 
-    best_score, best_step = [-np.inf] * K, [0] * K
-    pending = None  # (first step, [K] device losses) of the chunk whose records are still to be logged
-
-    def flush():
-        nonlocal pending
-        if pending is None:
-            return
-        t0, losses = pending
-        pending = None
-        for k, arr in enumerate(l.cpu().numpy() for l in losses):
-            for i, (v, q, a) in enumerate(arr.tolist()):
-                logger(tag({"value_loss": v, "q_loss": q, "actor_loss": a}, k), t0 + i)
-
-    total, every, t = int(config.update_steps), int(config.eval_every), 0
-    while t < total:
-        nxt = min(total, t + int(chunk), (t // every + 1) * every)
+    def steps(t, n):
         if group is None:
-            losses = [trainers[0].train_epoch_steps(replay_buffer, sampler, t, nxt - t)]
-        else:
-            idx, valid = samplers.device_indices(t, nxt - t, device)
-            losses = group.train_steps(replay_buffer, nxt - t, config.batch_size, indices=idx, n_valid=valid,
-                                       return_losses=True)
-        flush()
-        pending = (t, losses)
-        t = nxt
-        if t % every != 0:
-            continue
-        flush()
-        if group is not None:
-            group.synchronize()
-        step = t - 1
-        for k, trainer in enumerate(trainers):
-            log = lambda d: logger(tag(d, k), step)
-            eval_scores = bb_run_eval_IQL(actor=trainer.actor, num_episodes=config.eval_episodes, r_model=reward_model,
-                                          move_stats=move_stats, state_mean=dataset.state_mean(),
-                                          state_std=dataset.state_std(), seed=config.eval_seed + step, device=device)
-            mean_eval = eval_scores.mean()
-            log({"evaluation_return": mean_eval})
-            if mean_eval > best_score[k]:
-                best_score[k], best_step[k] = mean_eval, step
-                if ckpt_dirs[k] is not None:
-                    torch.save(trainer.state_dict(), os.path.join(ckpt_dirs[k], "best_model.pt"))
-            log({"best_score_so_far": best_score[k]})
-            log({"best_step_so_far": best_step[k]})
-            if ckpt_dirs[k] is not None:
-                torch.save(trainer.state_dict(), os.path.join(ckpt_dirs[k], f"checkpoint_{step}.pt"))
-    flush()
+            return [trainers[0].train_epoch_steps(replay_buffer, sampler, t, n)]
+        idx, valid = samplers.device_indices(t, n, device)
+        return group.train_steps(replay_buffer, n, config.batch_size, indices=idx, n_valid=valid, return_losses=True)
+
+    def evaluate(k, trainer, step):  # (bb_run_eval_IQL: the module's global at call time)
+        return bb_run_eval_IQL(actor=trainer.actor, num_episodes=config.eval_episodes, r_model=reward_model,
+                               move_stats=move_stats, state_mean=dataset.state_mean(),
+                               state_std=dataset.state_std(), seed=config.eval_seed + step, device=device)
+
+    _offline_loop.run(trainers, seeds, group, int(config.update_steps), int(config.eval_every), chunk, logger,
+                      ckpt_dirs, steps, evaluate)
     if group is not None:
         group.synchronize()
         group.close()

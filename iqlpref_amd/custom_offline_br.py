@@ -1,7 +1,7 @@
 """The ``algorithms/custom_offline/iql_br.py`` flavour: IQL on Minari episodes whose rewards come from a
 BNN posterior over reward networks.  "bref:" = that file; "cref:" = ``custom_offline/iql.py``.
 
-It is the custom flavour (``custom_offline.py``) with two differences:
+It is the custom flavour with two differences, which ``custom_offline._train`` takes as arguments:
 
 * the relabel (bref:179-253).  S posterior networks predict every transition, and the reward is
   ``reward_type`` 0: one posterior draw, 1: the mean and 2: the median of ``n_samples`` draws, 3: the
@@ -233,13 +233,9 @@ def qlearning_dataset(dataset: Iterable, r_model, reward_type: int, n_samples: O
     ``n_samples=None`` raise ``ValueError`` where the reference has a bare ``assert``."""
     if reward_type in (1, 2) and n_samples is None:
         raise ValueError(f"reward_type {reward_type} needs n_samples")
-    eps = [_co._episode_arrays(e) for e in dataset]
-    if any(a.shape[0] < 2 for _, a, _ in eps):
+    obs, act, nxt, dones, lengths = _co._concat_episodes(dataset)
+    if min(lengths) < 2:
         raise ValueError("an episode of one step: the reference's squeeze() leaves no row to draw from")
-    obs = np.concatenate([o[:-1] for o, _, _ in eps])
-    nxt = np.concatenate([o[1:] for o, _, _ in eps])
-    act = np.concatenate([a for _, a, _ in eps])
-    dones = np.concatenate([d for _, _, d in eps])
     obs_act = np.concatenate([obs, act], axis=-1)
     if reward_type == 3:
         if not hasattr(r_model, "map_predictions"):
@@ -263,7 +259,7 @@ def qlearning_dataset(dataset: Iterable, r_model, reward_type: int, n_samples: O
 # train (bref:625-778)
 # --------------------------------------------------------------------------- #
 def train(config: TrainConfig, dataset=None, reward_model=None, eval_env=None, **kw):
-    """bref:625-778 = ``custom_offline.train``'s loop (same keywords: ``logger``, ``normalized_score``,
+    """bref:625-778 = ``custom_offline.train`` (same keywords: ``logger``, ``normalized_score``,
     ``seeds_per_gpu``, ``sampler``, ``device``, ``chunk``) with the posterior relabel, which runs before
     ``set_seed(train_seed)`` and so consumes numpy's global generator in whatever state it is, and the
     best model chosen by the mean evaluation return.
@@ -279,4 +275,4 @@ def train(config: TrainConfig, dataset=None, reward_model=None, eval_env=None, *
     if config.reward_type == 3 and getattr(reward_model, "map_set", True) is None:
         _map_missing()
     relabel = lambda ds: qlearning_dataset(ds, reward_model, config.reward_type, config.n_samples)
-    return _co.train(config, dataset, reward_model, eval_env, _relabel=relabel, _best_by_return=True, **kw)
+    return _co._train(config, dataset, eval_env, relabel, True, **kw)

@@ -31,6 +31,7 @@ import torch
 
 from . import _lib
 from . import distributed as D
+from ._offline_loop import checkpoint_dirs
 from .iql import ImplicitQLearning, TrainConfig, load_config
 from .multi import GROUP_MODES
 
@@ -341,12 +342,7 @@ def train_runs(configs: Sequence[TrainConfig], env=None, dataset=None, *, runs_p
             buf, mean, std = buffer_for(i)
             e = envs[cfg.env]
             max_action = float(e.action_space.high[0])
-            if cfg.checkpoints_path is not None:
-                print(f"Checkpoints path: {cfg.checkpoints_path}")
-                os.makedirs(cfg.checkpoints_path, exist_ok=True)
-                import yaml
-                with open(os.path.join(cfg.checkpoints_path, "config.yaml"), "w") as f:
-                    yaml.safe_dump(asdict(cfg), f)
+            checkpoint_dirs(cfg, [cfg.seed])  # (one seed: the path itself, with its config.yaml)
             trainers[i] = T._build_trainer(cfg, cfg.seed, dims[cfg.env][0], dims[cfg.env][1], max_action, precision)
             state[i] = (buf, mean, std, max_action, e)
         _run_batch(configs, batch, trainers, state, SeedGroup, group_mode, logger, evaluate, vector_env, run_ids)

@@ -18,6 +18,7 @@ import torch
 
 from . import distributed as D
 from . import prep
+from ._offline_loop import checkpoint_dirs
 from .iql import (DeterministicPolicy, EnsembleQ, GaussianPolicy, ImplicitQLearning, ReplayBuffer, TrainConfig, TwinQ,
                   ValueFunction, compute_mean_std, normalize_states, set_seed)
 from .relabel import (load_mlp_reward_model, load_pt_reward_model, modify_reward, qlearning_dataset_bnn,
@@ -297,16 +298,7 @@ def train(config: TrainConfig, env=None, dataset=None, *, state_dim: Optional[in
     if max_action is None:
         max_action = float(env.action_space.high[0])
 
-    ckpt_dirs = [None] * K
-    if config.checkpoints_path is not None:
-        print(f"Checkpoints path: {config.checkpoints_path}")
-        os.makedirs(config.checkpoints_path, exist_ok=True)
-        import yaml
-        with open(os.path.join(config.checkpoints_path, "config.yaml"), "w") as f:
-            yaml.safe_dump(asdict(config), f)
-        for k in range(K):
-            ckpt_dirs[k] = config.checkpoints_path if K == 1 else os.path.join(config.checkpoints_path, f"seed_{seeds[k]}")
-            os.makedirs(ckpt_dirs[k], exist_ok=True)
+    ckpt_dirs = checkpoint_dirs(config, seeds)
 
     if K > 1 and config.load_model != "":
         import warnings

@@ -1,0 +1,213 @@
+"""_offline_loop: the chunked train / evaluate / checkpoint loop of the custom-offline flavours and its
+checkpoint directories, driven with fakes.  No GPU, no library load."""
+import os
+from dataclasses import dataclass
+from typing import Optional
+
+import numpy as np
+import pytest
+import torch
+
+from iqlpref_amd import _offline_loop as ol
+
+LOSS_KEYS = ("value_loss", "q_loss", "actor_loss")
+
+
+@dataclass
+class Config:
+    name: str = "fake"
+    checkpoints_path: Optional[str] = None
+
+
+class Trainer:
+    def __init__(self, k):
+        self.k, self.done, self.actor = k, 0, object()
+
+    def state_dict(self):
+        return {"w": torch.tensor([float(self.k), float(self.done)])}
+
+
+class Group:
+    def __init__(self, events):
+        self.events = events
+
+    def synchronize(self):
+        self.events.append(("sync",))
+
+
+def drive(K, returns, path=None, total=12, normalized=None, best_by_return=False):
+    """Run the loop (every=6, chunk=4) over fakes; ``returns[b]`` is the mean return of every seed at
+    boundary b.  -> (events, trainers, seeds, ckpt_dirs); events are ("steps", t, n), ("sync",),
+    ("eval", k, step) and ("log", record, step) in the order they happened."""
+    events = []
+    seeds = [40 + k for k in range(K)]
+    trainers = [Trainer(k) for k in range(K)]
+
+    def steps(t, n):
+        events.append(("steps", t, n))
+        for tr in trainers:
+            tr.done += n
+        s = torch.arange(t, t + n, dtype=torch.float32)
+        return [torch.stack([s, 10 * s + k, 100 * s + k], dim=1) for k in range(K)]
+
+    def evaluate(k, trainer, step):
+        assert trainer is trainers[k]
+        events.append(("eval", k, step))
+        r = returns[step // 6]
+        return np.array([r - 0.5, r + 0.5])
+
+    ckpt_dirs = ol.checkpoint_dirs(Config(checkpoints_path=None if path is None else str(path)), seeds)
+    ol.run(trainers, seeds, Group(events) if K > 1 else None, total, 6, 4,
+           lambda rec, step: events.append(("log", dict(rec), step)), ckpt_dirs, steps, evaluate,
+           normalized=normalized, best_by_return=best_by_return)
+    return events, trainers, seeds, ckpt_dirs
+
+
+def loss_records(K, seeds, t, n):
+    """What the flush of chunk (t, n) logs: seeds are the outer loop."""
+    out = []
+    for k in range(K):
+        for s in range(t, t + n):
+            rec = {"value_loss": float(s), "q_loss": float(10 * s + k), "actor_loss": float(100 * s + k)}
+            out.append(("log", dict(rec, seed=seeds[k]) if K > 1 else rec, s))
+    return out
+
+
+def eval_records(K, seeds, step, per_seed):
+    """The records of one boundary: ``per_seed`` is the list of (key, value) pairs every seed logs."""
+    out = [("sync",)] if K > 1 else []
+    for k in range(K):
+        out.append(("eval", k, step))
+        for key, value in per_seed:
+            out.append(("log", dict({key: value}, seed=seeds[k]) if K > 1 else {key: value}, step))
+    return out
+
+
+def pos(events, ev):
+    return events.index(ev)
+
+
+@pytest.mark.parametrize("K", [1, 3])
+def test_order_of_everything_observable(K, tmp_path):
+    events, trainers, seeds, dirs = drive(K, (2.0, 1.0), tmp_path)
+    assert [e for e in events if e[0] == "steps"] == [("steps", 0, 4), ("steps", 4, 2), ("steps", 6, 4),
+                                                      ("steps", 10, 2)]
+    # the overlap: the losses of chunk (0, 4) come back after chunk (4, 2) is queued, before the evaluation
+    first_chunk = loss_records(K, seeds, 0, 4)
+    first_eval = next(i for i, e in enumerate(events) if e[0] == "log" and "evaluation_return" in e[1])
+    for rec in first_chunk:
+        assert pos(events, ("steps", 4, 2)) < pos(events, rec) < first_eval
+    # one loss record per step and seed, with its values at its step
+    losses = [e for e in events if e[0] == "log" and "value_loss" in e[1]]
+    want = sum((loss_records(K, seeds, t, n) for t, n in ((0, 4), (4, 2), (6, 4), (10, 2))), [])
+    assert losses == want and len(losses) == 12 * K
+    assert all(("seed" in e[1]) == (K > 1) for e in events if e[0] == "log")
+    assert all(set(e[1]) - {"seed"} == set(LOSS_KEYS) for e in losses)
+    # the whole sequence: queue, flush, [flush, synchronize, evaluate] -- the best model stays that of step 5
+    at = lambda step, ret: eval_records(K, seeds, step, [("evaluation_return", ret), ("best_score_so_far", 2.0),
+                                                           ("best_step_so_far", 5)])
+    assert events == ([("steps", 0, 4), ("steps", 4, 2)] + first_chunk + loss_records(K, seeds, 4, 2) + at(5, 2.0)
+                      + [("steps", 6, 4), ("steps", 10, 2)] + loss_records(K, seeds, 6, 4)
+                      + loss_records(K, seeds, 10, 2) + at(11, 1.0))
+    if K > 1:  # synchronize comes before the first evaluation of each boundary
+        syncs = [i for i, e in enumerate(events) if e == ("sync",)]
+        assert syncs == [pos(events, ("eval", 0, 5)) - 1, pos(events, ("eval", 0, 11)) - 1]
+
+    # files: best_model.pt written once, with the state at step 5 (6 steps done)
+    files = ["best_model.pt", "checkpoint_11.pt", "checkpoint_5.pt", "config.yaml"]
+    if K == 1:
+        assert dirs == [str(tmp_path)] and sorted(os.listdir(tmp_path)) == files
+    else:
+        assert dirs == [str(tmp_path / f"seed_{s}") for s in seeds]
+        assert sorted(os.listdir(tmp_path)) == ["config.yaml"] + [f"seed_{s}" for s in seeds]
+        for d in dirs:
+            assert sorted(os.listdir(d)) == files[:3]
+    for k, d in enumerate(dirs):
+        load = lambda name: torch.load(os.path.join(d, name), weights_only=True)["w"].tolist()
+        assert load("best_model.pt") == load("checkpoint_5.pt") == [float(k), 6.0]
+        assert load("checkpoint_11.pt") == [float(k), 12.0]
+    import yaml
+    with open(tmp_path / "config.yaml") as f:
+        assert yaml.safe_load(f) == {"name": "fake", "checkpoints_path": str(tmp_path)}
+
+
+@pytest.mark.parametrize("K", [1, 3])
+def test_an_equal_score_does_not_replace_the_best(K, tmp_path):
+    events, _, seeds, dirs = drive(K, (1.0, 1.0), tmp_path)
+    best = [(e[1]["best_step_so_far"], e[2]) for e in events if e[0] == "log" and "best_step_so_far" in e[1]]
+    assert best == [(5, 5)] * K + [(5, 11)] * K
+    for k, d in enumerate(dirs):
+        assert torch.load(os.path.join(d, "best_model.pt"), weights_only=True)["w"].tolist() == [float(k), 6.0]
+
+
+def scripted(values):
+    """A ``normalized`` whose call number c returns values[c], or raises it."""
+    calls = iter(values)
+
+    def normalized(scores):
+        v = next(calls)
+        if isinstance(v, Exception):
+            raise v
+        return v
+    return normalized
+
+
+def evaluation_logs(events):
+    return [(next(iter(e[1].items())), e[2]) for e in events if e[0] == "log" and "value_loss" not in e[1]]
+
+
+def test_normalized_score_rules():
+    # no score at the first boundary (the raw return counts), 0.5 at the second
+    events, *_ = drive(1, (3.0, 1.0), normalized=scripted([ValueError("no reference score"), 0.5]))
+    assert evaluation_logs(events) == [
+        (("evaluation_return", 3.0), 5), (("best_score_so_far", 3.0), 5), (("best_step_so_far", 5), 5),
+        (("evaluation_return", 1.0), 11), (("normalized_score", 50.0), 11), (("best_score_so_far", 50.0), 11),
+        (("best_step_so_far", 11), 11)]
+    # best_by_return: the score is logged, the best model goes by the raw mean at both boundaries
+    events, *_ = drive(1, (3.0, 1.0), normalized=scripted([ValueError("no reference score"), 0.5]),
+                       best_by_return=True)
+    assert evaluation_logs(events) == [
+        (("evaluation_return", 3.0), 5), (("best_score_so_far", 3.0), 5), (("best_step_so_far", 5), 5),
+        (("evaluation_return", 1.0), 11), (("normalized_score", 50.0), 11), (("best_score_so_far", 3.0), 11),
+        (("best_step_so_far", 5), 11)]
+    # a score once obtained stays for its seed: it is not logged again, and a greater raw return does not beat it
+    events, *_ = drive(1, (1.0, 70.0), normalized=scripted([0.5, ValueError("no reference score")]))
+    assert evaluation_logs(events) == [
+        (("evaluation_return", 1.0), 5), (("normalized_score", 50.0), 5), (("best_score_so_far", 50.0), 5),
+        (("best_step_so_far", 5), 5),
+        (("evaluation_return", 70.0), 11), (("best_score_so_far", 50.0), 11), (("best_step_so_far", 5), 11)]
+
+
+def test_normalized_score_is_kept_per_seed():
+    # calls: seed 0 and 1 at step 5, then at step 11; only seed 1 ever gets a score
+    err = ValueError("no reference score")
+    events, _, seeds, _ = drive(2, (3.0, 1.0), normalized=scripted([err, 0.5, err, err]))
+    best = {s: [e[1]["best_score_so_far"] for e in events
+                if e[0] == "log" and "best_score_so_far" in e[1] and e[1]["seed"] == s] for s in seeds}
+    assert best == {seeds[0]: [3.0, 3.0], seeds[1]: [50.0, 50.0]}
+
+
+@pytest.mark.parametrize("K", [1, 3])
+def test_without_checkpoints_path_nothing_is_written(K, tmp_path, monkeypatch):
+    monkeypatch.chdir(tmp_path)
+    _, _, _, dirs = drive(K, (2.0, 1.0))
+    assert dirs == [None] * K and os.listdir(tmp_path) == []
+
+
+@pytest.mark.parametrize("K", [1, 3])
+def test_total_that_is_no_multiple_of_every(K):
+    events, _, seeds, _ = drive(K, (2.0,), total=10)
+    assert [e for e in events if e[0] == "steps"] == [("steps", 0, 4), ("steps", 4, 2), ("steps", 6, 4)]
+    assert [e[2] for e in events if e[0] == "eval"] == [5] * K  # none at step 9
+    # the last chunk's losses are flushed at the end
+    assert events[-4 * K:] == loss_records(K, seeds, 6, 4)
+    assert len([e for e in events if e[0] == "log" and "value_loss" in e[1]]) == 10 * K
+
+
+def test_tag_and_print_logger(capsys, monkeypatch):
+    import sys
+    assert ol.tag([7])({"a": 1.0}, 0) == {"a": 1.0}
+    assert ol.tag([7, 8])({"a": 1.0}, 1) == {"a": 1.0, "seed": 8}
+    monkeypatch.setitem(sys.modules, "wandb", None)  # (import wandb raises ImportError)
+    ol.default_logger(Config(), 1)({"q_loss": 0.25}, 3)
+    assert capsys.readouterr().out == "[3] q_loss=0.25\n"
