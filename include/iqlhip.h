@@ -57,6 +57,9 @@ const char *iqlhip_build_tag(void);
 /*             layer-wise step (csrc/iql_deep.hip: same arithmetic, graph      */
 /*             replay and seed groups of one shape as on the tuned step; no    */
 /*             CU-slice sub-groups);                                           */
+/*   online    iqlhip_explore_action: every trainer shape above at precision     */
+/*             fp32; iqlhip_replay_append: any ring of >= 1 rows, n <= capacity;  */
+/*             iqlhip_np_randint_growing: growth 0 or 1, bounds up to 2^32;       */
 /*   MLP fwd   1..8 layers, every width in [1, 1024] (beyond 256: a plain      */
 /*             one-wave-per-16-rows variant);                                  */
 /*   CVaR      1 <= n_tail <= S <= 2400;                                       */
@@ -496,6 +499,52 @@ int iqlhip_pt_relabel_general(const iqlhip_pt_model *m, const float *obs, const 
  * batch >= 1, n_batches >= 0 (0 draws nothing).                                               */
 int iqlhip_np_randint(uint32_t *state, const int64_t *hi, int32_t K, int32_t batch,
                       int64_t n_batches, int64_t *const *out, void *stream);
+
+/* ------------------------------------------------------------------------ */
+/* Online fine-tuning, algorithms/finetune/iql.py ("fref"): the three kernels   */
+/* around the training step of one online tick (csrc/online.hip).  The tick     */
+/* itself is a host loop (iqlpref_amd/finetune.py): act, env.step, append, one  */
+/* iqlhip_train_steps call of one step.  fref runs without autocast: fp32 only. */
+/* ------------------------------------------------------------------------ */
+/* fref:164-180 add_transition, n >= 1 transitions at once: row (pointer + i) % capacity of the ring
+ * rows[capacity][row_stride] receives transition i of the device fp32 staging arrays obs[n][S], act[n][A],
+ * rew[n], next_obs[n][S], done[n], in the layout of iqlhip_replay_pack -- padding zeros and the 16-byte
+ * aligned s' included, bit for bit what packing the same data into those rows writes.  Every other row
+ * keeps its contents.  rows on a 16-byte boundary (whole rows are written as 16-byte pieces).
+ * n > capacity, pointer outside [0, capacity), n < 1: IQLHIP_ERR_INVALID, nothing is launched.  The
+ * caller advances its pointer / size (fref:179-180) and the generation of its views.                 */
+int iqlhip_replay_append(float *rows, int32_t row_stride, int32_t state_dim, int32_t action_dim,
+                         int64_t capacity, int64_t pointer, int64_t n, const float *obs, const float *act,
+                         const float *rew, const float *next_obs, const float *done, void *stream);
+
+/* numpy's RandomState.randint(0, hi_t, batch) for t = 0 .. n_steps - 1 as ONE stream, with
+ * hi_t = min(hi0[k] + t * growth, cap[k]): the index draws of n_steps online ticks, whose buffer grows by
+ * `growth` (0 or 1) rows per tick until it is full (fref:155-156, 180).  The values, and the MT19937 key and
+ * position left behind, are those of n_steps successive host calls; a step with hi_t == 1 consumes no word
+ * and yields zeros.  growth == 0 is iqlhip_np_randint.  state, K, out[k] (device int64 [n_steps][batch]), the
+ * one synchronisation of `stream` before the launch and the pos check are as for iqlhip_np_randint; hi0 and
+ * cap are host arrays of K entries, 1 <= hi0[k] <= cap[k] <= 2^32.  IQLHIP_ERR_INVALID before any launch
+ * otherwise (the states are then untouched).  n_steps == 0 draws nothing.                            */
+int iqlhip_np_randint_growing(uint32_t *state, const int64_t *hi0, const int64_t *cap, int32_t growth,
+                              int32_t K, int32_t batch, int64_t n_steps, int64_t *const *out, void *stream);
+
+/* fref:681-693, the action the online phase proposes, for rows >= 1 states s[rows][state_dim] at once:
+ * the actor's forward on the LIVE fp32 master weights of the parameter arena (no copy is kept), then
+ *   Gaussian policy        a = mean + exp(clamp(log_std, -20, 2)) * eps            (fref:687 dist.sample())
+ *   deterministic policy   a = out + clamp(expl_noise * eps, -noise_clip, noise_clip)   (fref:689-692)
+ *   out[rows][action_dim]  = clamp(max_action * a, -max_action, max_action)        (fref:693)
+ * fref never takes the actor out of train mode for this forward (only eval_actor does, and it switches
+ * back, fref:223,240): a trainer without actor dropout (fref's default 0.0 builds no Dropout layer) runs
+ * the plain forward; one with dropout_p > 0 drops hidden units here too, as fref's actor(state) does --
+ * masks of iqlhip_mlp_forward's convention keyed by the trainer's seed with dropout_call = call.
+ * eps: device fp32 [rows][action_dim] standard normals as given (parity tests), or NULL: drawn from the
+ * trainer's Philox key, block (row, call, column / 4, stream 4), words (x, y) and (z, w) one Box-Muller
+ * pair each: u1 = (x + 1) 2^-32, u2 = y 2^-32, sqrt(-2 ln u1) (cos, sin)(2 pi u2).  `call`: a number the
+ * caller never repeats for one trainer (the tick).  Two launches on `stream`, no synchronisation.  Every
+ * trainer shape of the envelope, tuned or general step; precision bf16 is IQLHIP_ERR_UNSUPPORTED.    */
+int iqlhip_explore_action(iqlhip_trainer *t, const float *s, int64_t rows, const float *eps,
+                          float expl_noise, float noise_clip, float max_action, uint32_t call, float *out,
+                          void *stream);
 
 /* ------------------------------------------------------------------------ */
 /* Block-shuffled epochs of algorithms/custom_offline/iql_bb.py:208-267        */

@@ -146,6 +146,10 @@ SYMBOLS = {
     "iqlhip_pt_relabel_general": (C.c_int, [C.POINTER(PtModel), P, P, C.c_int64, P, P, P, C.c_int64, C.c_int32,
                                             P, C.c_size_t, P, P]),
     "iqlhip_np_randint": (C.c_int, [P, P, C.c_int32, C.c_int32, C.c_int64, P, P]),
+    "iqlhip_replay_append": (C.c_int, [P, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
+                                       P, P, P, P, P, P]),
+    "iqlhip_np_randint_growing": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.c_int32, C.c_int64, P, P]),
+    "iqlhip_explore_action": (C.c_int, [P, P, C.c_int64, P, C.c_float, C.c_float, C.c_float, C.c_uint32, P, P]),
     "iqlhip_block_epoch_indices": (C.c_int, [P, C.c_int64, C.c_int32, C.c_int64, C.c_int64, P, P, P]),
     "iqlhip_block_epoch_indices_group": (C.c_int, [C.POINTER(P), C.c_int64, C.c_int32, C.c_int64, C.c_int64,
                                                    C.POINTER(P), P, C.c_int32, P]),

@@ -81,6 +81,14 @@ hipError_t launch_block_epoch(const int64_t *perm, int64_t n_rows, int batch, in
                               int32_t *n_valid, hipStream_t st);
 hipError_t launch_block_epoch_group(const int64_t *const *perm, int64_t n_rows, int batch, int64_t t0, int64_t n_steps,
                                     int64_t *const *idx, int32_t *n_valid, int K, hipStream_t st);
+hipError_t launch_replay_append(float *rows, int stride, int S, int A, int64_t pointer, int64_t capacity, int64_t n,
+                                const float *obs, const float *act, const float *rew, const float *nxt,
+                                const float *done, hipStream_t st);
+hipError_t launch_np_randint_growing(uint32_t *state, const int64_t *hi0, const int64_t *cap, int growth, int K,
+                                     int batch, int64_t n_steps, int64_t *const *out, hipStream_t st);
+hipError_t launch_explore_epilogue(float *act, int64_t rows, int A, const float *log_std, const float *eps,
+                                   float expl_noise, float noise_clip, float max_action, uint64_t seed, uint32_t call,
+                                   hipStream_t st);
 hipError_t launch_np_randint(uint32_t *state, const int64_t *hi, int K, int64_t total, int64_t *const *out,
                              hipStream_t st);
 size_t choice_workspace_bytes(int64_t N, int n);
@@ -1571,6 +1579,90 @@ extern "C" int iqlhip_np_randint(uint32_t *state, const int64_t *hi, int32_t K, 
     if (pos[k] > 624) return fail(IQLHIP_ERR_INVALID, "state %d: pos = %u outside 0..624", k, pos[k]);
   if (n_batches == 0) return 0;
   HIP_TRY(launch_np_randint(state, hi, K, n_batches * (int64_t)batch, out, st));
+  return 0;
+}
+
+// ------------------------------------------------------- online fine-tuning --
+extern "C" int iqlhip_replay_append(float *rows, int32_t row_stride, int32_t S, int32_t A, int64_t capacity,
+                                    int64_t pointer, int64_t n, const float *obs, const float *act, const float *rew,
+                                    const float *next_obs, const float *done, void *stream) {
+  if (!rows || !obs || !act || !rew || !next_obs || !done) return fail(IQLHIP_ERR_INVALID, "null pointer");
+  if (S <= 0 || A <= 0 || row_stride < iqlhip_replay_row_stride(S, A) || (row_stride & 3))
+    return fail(IQLHIP_ERR_INVALID, "bad replay geometry S=%d A=%d stride=%d", S, A, row_stride);
+  if ((uintptr_t)rows & 15) return fail(IQLHIP_ERR_INVALID, "rows must start on a 16-byte boundary");
+  if (capacity < 1) return fail(IQLHIP_ERR_INVALID, "capacity = %lld must be >= 1", (long long)capacity);
+  if (pointer < 0 || pointer >= capacity)
+    return fail(IQLHIP_ERR_INVALID, "pointer = %lld outside 0..%lld", (long long)pointer, (long long)capacity - 1);
+  if (n < 1) return fail(IQLHIP_ERR_INVALID, "n = %lld must be >= 1", (long long)n);
+  if (n > capacity)
+    return fail(IQLHIP_ERR_INVALID, "n = %lld transitions do not fit a ring of %lld rows", (long long)n,
+                (long long)capacity);
+  HIP_TRY(launch_replay_append(rows, row_stride, S, A, pointer, capacity, n, obs, act, rew, next_obs, done,
+                               (hipStream_t)stream));
+  return 0;
+}
+
+extern "C" int iqlhip_np_randint_growing(uint32_t *state, const int64_t *hi0, const int64_t *cap, int32_t growth,
+                                         int32_t K, int32_t batch, int64_t n_steps, int64_t *const *out,
+                                         void *stream) {
+  if (!state || !hi0 || !cap || !out) return fail(IQLHIP_ERR_INVALID, "null argument");
+  if (K < 1 || K > IQLHIP_MAX_GROUP) return fail(IQLHIP_ERR_INVALID, "K = %d: 1..%d streams", K, IQLHIP_MAX_GROUP);
+  if (batch < 1) return fail(IQLHIP_ERR_INVALID, "batch = %d must be >= 1", batch);
+  if (n_steps < 0) return fail(IQLHIP_ERR_INVALID, "n_steps = %lld must be >= 0", (long long)n_steps);
+  if (growth != 0 && growth != 1) return fail(IQLHIP_ERR_INVALID, "growth = %d must be 0 or 1", growth);
+  for (int k = 0; k < K; ++k) {
+    if (hi0[k] < 1 || hi0[k] > (int64_t(1) << 32))
+      return fail(IQLHIP_ERR_INVALID, "hi0[%d] = %lld outside 1..2^32", k, (long long)hi0[k]);
+    if (cap[k] < hi0[k] || cap[k] > (int64_t(1) << 32))
+      return fail(IQLHIP_ERR_INVALID, "cap[%d] = %lld outside hi0..2^32", k, (long long)cap[k]);
+    if (!out[k]) return fail(IQLHIP_ERR_INVALID, "null out[%d]", k);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  uint32_t pos[IQLHIP_MAX_GROUP];
+  HIP_TRY(hipMemcpy2DAsync(pos, sizeof(uint32_t), state + 624, 625 * sizeof(uint32_t), sizeof(uint32_t), K,
+                           hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  for (int k = 0; k < K; ++k)
+    if (pos[k] > 624) return fail(IQLHIP_ERR_INVALID, "state %d: pos = %u outside 0..624", k, pos[k]);
+  if (n_steps == 0) return 0;
+  HIP_TRY(launch_np_randint_growing(state, hi0, cap, growth, K, batch, n_steps, out, st));
+  return 0;
+}
+
+// The actor's forward runs the stand-alone exact-fp32 MLP kernel straight on the fp32 masters of the
+// parameter arena (what every step's update writes: nothing is copied, nothing can go stale), for the
+// tuned and the general step alike; k_explore_epilogue then turns its output into the action in place.
+extern "C" int iqlhip_explore_action(iqlhip_trainer *t, const float *s, int64_t rows, const float *eps,
+                                     float expl_noise, float noise_clip, float max_action, uint32_t call,
+                                     float *out, void *stream) {
+  if (!t || !s || !out) return fail(IQLHIP_ERR_INVALID, "null argument");
+  if (rows < 1 || rows > 0xffffffffLL) return fail(IQLHIP_ERR_INVALID, "rows = %lld outside 1..2^32 - 1", (long long)rows);
+  const iqlhip_trainer_config &c = t->cfg;
+  if (c.precision != IQLHIP_PREC_FP32)
+    return fail(IQLHIP_ERR_UNSUPPORTED, "exploration actions need a precision fp32 trainer (the fine-tune flavour "
+                                        "runs without autocast)");
+  if (!(noise_clip >= 0.f) || !(max_action > 0.f) || !(expl_noise >= 0.f))
+    return fail(IQLHIP_ERR_INVALID, "expl_noise and noise_clip must be >= 0, max_action > 0");
+  const Layout L = make_layout(c);
+  const int E = n_critics(c), NL = n_hidden(c) + 1, net = E + 1;
+  iqlhip_mlp_desc d;
+  memset(&d, 0, sizeof(d));
+  d.n_layers = NL;
+  d.dims[0] = c.state_dim;
+  for (int l = 0; l < NL; ++l) {
+    d.dims[l + 1] = l == NL - 1 ? c.action_dim : c.hidden_dim;
+    d.weights[l] = t->arenas.params + L.off[(net * NL + l) * 2];
+    d.biases[l] = t->arenas.params + L.off[(net * NL + l) * 2 + 1];
+  }
+  d.w_in_out = 0, d.hidden_act = 0, d.out_act = 1;
+  // fref never leaves train mode outside eval_actor: with actor_dropout the exploring forward drops units
+  d.dropout_p = c.dropout_p > 0.f ? c.dropout_p : 0.f;
+  d.dropout_call = call, d.dropout_seed = c.seed;
+  const float *log_std = c.deterministic ? nullptr : t->arenas.params + L.off[(E + 2) * NL * 2];
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(launch_mlp_f32(d, s, rows, c.state_dim, out, c.action_dim, st));
+  HIP_TRY(launch_explore_epilogue(out, rows, c.action_dim, log_std, eps, expl_noise, noise_clip, max_action, c.seed,
+                                  call, st));
   return 0;
 }
 

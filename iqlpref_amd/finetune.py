@@ -1,0 +1,552 @@
+"""The ``algorithms/finetune/iql.py`` flavour of the path: offline pretraining, then online fine-tuning on a
+replay buffer that grows on the device.  "fref:" = that file.
+
+``offline_iterations`` steps are the chunked ``train_steps`` loop of the offline flavours, with numpy's index
+stream drawn on the device.  Each of the ``online_iterations`` ticks after them is a plain host loop around
+the same training step, with one small kernel for each thing the tick adds (csrc/online.hip):
+
+1. ``ImplicitQLearning.explore_action``: the actor's forward and the noise / scale / clamp of fref:681-693;
+2. ``env.step`` on the host;
+3. ``ReplayBuffer.add_transition``: one packed row written at the ring pointer (fref:164-180);
+4. ``train_steps(n_steps=1)`` on indices that ``GrowingIndexStream`` drew ahead for a whole chunk of ticks:
+   the bound of tick j is known in advance, ``min(size + j + 1, buffer_size)`` (fref:156, 180).
+
+What differs from ``offline/iql.py`` and how it maps onto the same kernels: no autocast (``precision="fp32"``),
+the Polyak update written as ``(1 - tau) t + tau s`` (fref:71-73, ``polyak_form=1``), ``sample`` on numpy's
+global generator over ``_size`` (fref:156), ``actor_dropout`` a float with 0.0 for none (fref:45, 314), and a
+cosine schedule that keeps stepping past ``T_max = offline_iterations`` (fref:448, 513): the rate climbs again
+as ``(1 + cos(pi t / T_max)) / 2`` does, on the host's bookkeeping and in the kernels alike.
+
+gym, d4rl and wandb are imported only when ``train()`` is not handed what they would provide.
+"""
+import ctypes as C
+import math
+import os
+import uuid
+from dataclasses import dataclass
+from typing import Callable, Dict, Optional, Sequence, Tuple, Union
+
+import numpy as np
+import torch
+
+from . import _lib, _offline_loop
+from . import distributed as D
+from ._lib import check, ptr, stream_ptr
+from .custom_offline import NP_STATE_WORDS, NumpyIndexStream, pack_np_state, unpack_np_state
+from .iql import DeterministicPolicy, GaussianPolicy, TwinQ, ValueFunction, compute_mean_std, normalize_states, set_seed
+from .iql import ImplicitQLearning as _OfflineIQL
+from .iql import ReplayBuffer as _OfflineReplayBuffer
+from .iql import _buffer_generation
+from .train import wrap_env  # noqa: F401  (fref:86-105)
+
+ENVS_WITH_GOAL = ("antmaze", "pen", "door", "hammer", "relocate")  # fref:28
+
+
+@dataclass
+class TrainConfig:
+    """fref:31-68, same fields and defaults."""
+    device: str = "cuda"
+    env: str = "antmaze-umaze-v2"
+    seed: int = 0
+    eval_seed: int = 0
+    eval_freq: int = int(5e4)
+    n_episodes: int = 100
+    offline_iterations: int = int(1e6)
+    online_iterations: int = int(1e6)
+    checkpoints_path: Optional[str] = None
+    load_model: str = ""
+    actor_dropout: float = 0.0
+    buffer_size: int = 2_000_000
+    batch_size: int = 256
+    discount: float = 0.99
+    tau: float = 0.005
+    beta: float = 3.0
+    iql_tau: float = 0.7
+    expl_noise: float = 0.03
+    noise_clip: float = 0.5
+    iql_deterministic: bool = False
+    normalize: bool = True
+    normalize_reward: bool = False
+    vf_lr: float = 3e-4
+    qf_lr: float = 3e-4
+    actor_lr: float = 3e-4
+    project: str = "CORL"
+    group: str = "IQL-D4RL"
+    name: str = "IQL"
+
+    def __post_init__(self):
+        self.name = f"{self.name}-{self.env}-{str(uuid.uuid4())[:8]}"
+        if self.checkpoints_path is not None:
+            self.checkpoints_path = os.path.join(self.checkpoints_path, self.name)
+
+
+# --------------------------------------------------------------------------- #
+# host helpers of the reference module
+# --------------------------------------------------------------------------- #
+LOCOMOTION = ("halfcheetah", "hopper", "walker2d")  # the environments whose rewards are scaled by the return range
+
+
+def is_goal_reached(reward: float, info: Dict) -> bool:
+    """fref:212-215: the environment's own ``goal_achieved`` flag where it reports one, else a positive reward."""
+    return info["goal_achieved"] if "goal_achieved" in info else reward > 0
+
+
+def modify_reward(dataset: Dict, env_name: str, max_episode_steps: int = 1000) -> Dict:
+    """fref:259-271: rescales ``dataset["rewards"]`` in place (locomotion: by ``max_episode_steps`` over the range
+    of the episode returns, taken with the project's vectorised ``relabel.return_reward_range``; antmaze: minus
+    one) and returns the ``reward_mod_dict`` that ``modify_reward_online`` takes as keywords."""
+    if any(tag in env_name for tag in LOCOMOTION):
+        from .relabel import return_reward_range
+        lo, hi, _ = return_reward_range(dataset, max_episode_steps)
+        dataset["rewards"] /= hi - lo
+        dataset["rewards"] *= max_episode_steps
+        return {"max_ret": hi, "min_ret": lo, "max_episode_steps": max_episode_steps}
+    if "antmaze" in env_name:
+        dataset["rewards"] -= 1.0
+    return {}
+
+
+def modify_reward_online(reward: float, env_name: str, **reward_mod) -> float:
+    """fref:274-280: one environment reward through what ``modify_reward`` did to the dataset's; ``reward_mod`` is
+    the dict it returned.  The division and the multiplication stay two operations, as on the dataset."""
+    if any(tag in env_name for tag in LOCOMOTION):
+        scaled = reward / (reward_mod["max_ret"] - reward_mod["min_ret"])
+        return scaled * reward_mod["max_episode_steps"]
+    return reward - 1.0 if "antmaze" in env_name else reward
+
+
+def eval_actor(env, actor, device: str, n_episodes: int, seed: int) -> Tuple[np.ndarray, np.ndarray]:
+    """fref:218-241: ``n_episodes`` sequential episodes of a gym < 0.26 environment, greedy actions from
+    ``actor.act`` (one exact-fp32 forward on the GPU per step).  Returns (episode returns, success rate);
+    the actor is handed back in train mode."""
+    env.seed(seed)
+    actor.eval()
+    episode_rewards, successes = [], []
+    try:
+        for _ in range(n_episodes):
+            state, done = env.reset(), False
+            episode_reward = 0.0
+            goal_achieved = False
+            while not done:
+                action = actor.act(np.asarray(state), device)
+                state, reward, done, env_infos = env.step(action)
+                episode_reward += reward
+                if not goal_achieved:
+                    goal_achieved = is_goal_reached(reward, env_infos)
+            successes.append(float(goal_achieved))
+            episode_rewards.append(episode_reward)
+    finally:
+        actor.train()
+    return np.asarray(episode_rewards), np.mean(successes)
+
+
+# --------------------------------------------------------------------------- #
+# replay buffer (fref:108-181)
+# --------------------------------------------------------------------------- #
+def ring_advance(pointer: int, size: int, n: int, buffer_size: int) -> Tuple[int, int]:
+    """fref:179-180, n times: (``_pointer``, ``_size``) after ``n`` transitions went into the ring."""
+    return (pointer + n) % buffer_size, min(size + n, buffer_size)
+
+
+class ReplayBuffer(_OfflineReplayBuffer):
+    """The offline buffer with a ring that takes new transitions.  All ``buffer_size`` packed rows are
+    allocated up front (the offline buffer allocates only what it loads); ``sample`` draws from ``_size`` on
+    numpy's global generator (fref:156); ``load_d4rl_dataset`` leaves ``_pointer`` at the dataset's length
+    (fref:151)."""
+
+    def __init__(self, state_dim: int, action_dim: int, buffer_size: int, device: str = "cpu"):
+        if int(buffer_size) < 1:
+            raise ValueError("buffer_size must be >= 1")
+        super().__init__(state_dim, action_dim, int(buffer_size), device)
+        W = 2 * state_dim + action_dim + 2  # one transition in the staging order s | a | r | s' | d
+        self._stage_host = torch.zeros(W, dtype=torch.float32).pin_memory()
+        self._stage_dev = torch.zeros(W, dtype=torch.float32, device=self._dev)
+        self._stage_free: Optional[torch.cuda.Event] = None
+
+    def _alloc(self, n):
+        if getattr(self, "_rows", None) is not None and self._rows.shape[0] == self._buffer_size:
+            return  # (load_device_arrays asks for its n rows: the ring is there already, zeros beyond them)
+        try:
+            super()._alloc(self._buffer_size)
+        except torch.cuda.OutOfMemoryError as e:
+            gib = self._buffer_size * self._stride * 4 / 2**30
+            raise MemoryError(f"finetune.ReplayBuffer: buffer_size = {self._buffer_size} rows of {self._stride} floats "
+                              f"({gib:.1f} GiB) do not fit on {self._dev}; pass a smaller buffer_size ({e})") from None
+
+    def view(self) -> _lib.ReplayView:
+        key = (self._rows.data_ptr(), self._size, self._generation)
+        if getattr(self, "_view_key", None) != key:
+            self._view = _lib.ReplayView(ptr(self._rows), self._size, self._stride, self._state_dim, self._action_dim,
+                                         self._generation)
+            self._view_key = key
+        return self._view
+
+    def index_bound(self) -> int:
+        """The ``hi`` of fref:156."""
+        return self._size
+
+    def sample(self, batch_size: int, indices=None):
+        if indices is None:
+            indices = torch.from_numpy(np.random.randint(0, self._size, size=batch_size)).to(self._dev)
+        return super().sample(batch_size, indices)
+
+    def append_device(self, obs: torch.Tensor, act: torch.Tensor, rew: torch.Tensor, nxt: torch.Tensor,
+                      done: torch.Tensor):
+        """``n`` transitions that already live on the device (fp32 [n, S], [n, A], [n], [n, S], [n]) in one
+        ``iqlhip_replay_append`` launch: row ``(_pointer + i) % buffer_size`` receives transition i."""
+        n, S, A = int(obs.shape[0]), self._state_dim, self._action_dim
+        f = lambda t, shape: t.to(device=self._dev, dtype=torch.float32).reshape(shape).contiguous()
+        obs, act, nxt, rew, done = f(obs, (n, S)), f(act, (n, A)), f(nxt, (n, S)), f(rew, (n,)), f(done, (n,))
+        if n > self._buffer_size:
+            raise ValueError(f"{n} transitions do not fit a replay buffer of {self._buffer_size} rows")
+        if self._pointer >= self._buffer_size:  # (a dataset that filled the buffer: fref:173 indexes past the end)
+            raise IndexError(f"index {self._pointer} is out of bounds for a replay buffer of {self._buffer_size} rows")
+        with torch.cuda.device(self._dev):
+            check(self._lib.iqlhip_replay_append(ptr(self._rows), self._stride, S, A, self._buffer_size, self._pointer, n,
+                                                 ptr(obs), ptr(act), ptr(rew), ptr(nxt), ptr(done), stream_ptr()))
+        for t in (obs, act, rew, nxt, done):
+            t.record_stream(torch.cuda.current_stream(self._dev))
+        self._pointer, self._size = ring_advance(self._pointer, self._size, n, self._buffer_size)
+        _buffer_generation[0] += 1
+        self._generation = _buffer_generation[0]  # the rows changed: no prefetched batch survives
+
+    def add_transition(self, state: np.ndarray, action: np.ndarray, reward: float, next_state: np.ndarray, done: bool):
+        """fref:164-180: one pinned staging block, one copy, one launch; nothing waits on the host except for
+        the previous call's copy out of the same block."""
+        S, A = self._state_dim, self._action_dim
+        if self._pointer >= self._buffer_size:
+            raise IndexError(f"index {self._pointer} is out of bounds for a replay buffer of {self._buffer_size} rows")
+        if self._stage_free is not None:
+            self._stage_free.synchronize()
+        h = self._stage_host.numpy()
+        h[:S] = np.asarray(state, dtype=np.float32).reshape(S)
+        h[S:S + A] = np.asarray(action, dtype=np.float32).reshape(A)
+        h[S + A] = np.float32(reward)
+        h[S + A + 1:2 * S + A + 1] = np.asarray(next_state, dtype=np.float32).reshape(S)
+        h[2 * S + A + 1] = np.float32(done)
+        d = self._stage_dev
+        with torch.cuda.device(self._dev):
+            d.copy_(self._stage_host, non_blocking=True)
+            if self._stage_free is None:
+                self._stage_free = torch.cuda.Event()
+            self._stage_free.record()
+            base, sz = d.data_ptr(), 4
+            at = lambda off: C.c_void_p(base + off * sz)
+            check(self._lib.iqlhip_replay_append(ptr(self._rows), self._stride, S, A, self._buffer_size, self._pointer, 1,
+                                                 at(0), at(S), at(S + A), at(S + A + 1), at(2 * S + A + 1), stream_ptr()))
+        self._pointer, self._size = ring_advance(self._pointer, self._size, 1, self._buffer_size)
+        _buffer_generation[0] += 1
+        self._generation = _buffer_generation[0]
+
+
+# --------------------------------------------------------------------------- #
+# numpy's index stream over a growing buffer
+# --------------------------------------------------------------------------- #
+def bound_schedule(hi0: int, cap: int, n_steps: int, growth: int = 1) -> np.ndarray:
+    """``hi_t = min(hi0 + t * growth, cap)`` for t < n_steps: the bounds ``iqlhip_np_randint_growing`` draws
+    under.  For the online ticks that follow a buffer of ``size`` rows: ``hi0 = min(size + 1, buffer_size)``."""
+    return np.minimum(int(hi0) + np.arange(int(n_steps), dtype=np.int64) * int(growth), int(cap))
+
+
+class GrowingIndexStream:
+    """``np.random.randint(0, hi_t, size=B)`` for ``n_steps`` consecutive steps with the bounds of
+    ``bound_schedule``, for K generators at once, in ONE launch of ``iqlhip_np_randint_growing``; every
+    generator (an ``np.random.RandomState``, or None for numpy's global one) is left where the host calls
+    would have left it.  Synchronous: the online tick waits for its action every step anyway."""
+
+    def __init__(self, device):
+        self._lib = _lib.load()
+        self._dev = _lib.require_gpu(device)
+        G = _lib.MAX_GROUP
+        self._state = torch.empty((G, NP_STATE_WORDS), dtype=torch.int32, device=self._dev)
+        self._host = torch.empty((G, NP_STATE_WORDS), dtype=torch.int32).pin_memory()
+
+    def draw(self, hi0, cap, n_steps: int, batch_size: int, growth: int = 1,
+             generators: Optional[Sequence] = None):
+        gens = [None] if generators is None else list(generators)
+        K = len(gens)
+        his = [int(hi0)] * K if np.ndim(hi0) == 0 else [int(h) for h in hi0]
+        caps = [int(cap)] * K if np.ndim(cap) == 0 else [int(c) for c in cap]
+        n, B = int(n_steps), int(batch_size)
+        if not 1 <= K <= _lib.MAX_GROUP or len(his) != K or len(caps) != K:
+            raise ValueError(f"1..{_lib.MAX_GROUP} generators, one hi0 and one cap per generator")
+        if n < 1 or B < 1 or growth not in (0, 1):
+            raise ValueError("n_steps and batch_size must be >= 1, growth 0 or 1")
+        if any(h < 1 for h in his) or any(c < h for c, h in zip(caps, his)):
+            raise ValueError(f"every stream needs 1 <= hi0 <= cap (got hi0 = {his}, cap = {caps})")
+        before = []
+        for k, g in enumerate(gens):
+            st = (np.random if g is None else g).get_state(legacy=True)
+            self._host[k].numpy().view(np.uint32)[:] = pack_np_state(st)
+            before.append(st)
+        area = torch.empty((K, n, B), dtype=torch.int64, device=self._dev)
+        outs = (C.c_void_p * K)(*[area[k].data_ptr() for k in range(K)])
+        with torch.cuda.device(self._dev):
+            self._state[:K].copy_(self._host[:K], non_blocking=True)
+            check(self._lib.iqlhip_np_randint_growing(ptr(self._state), (C.c_int64 * K)(*his), (C.c_int64 * K)(*caps),
+                                                      int(growth), K, B, n, outs, stream_ptr()))
+            self._host[:K].copy_(self._state[:K], non_blocking=True)
+            torch.cuda.current_stream(self._dev).synchronize()
+        for k, g in enumerate(gens):
+            (np.random if g is None else g).set_state(unpack_np_state(self._host[k].numpy(), before[k]))
+        return [area[k] for k in range(K)]
+
+
+# --------------------------------------------------------------------------- #
+# trainer (fref:423-563)
+# --------------------------------------------------------------------------- #
+def cosine_rate(base_lr: float, t: int, t_max: int, eta_min: float = 0.0) -> float:
+    """The actor's rate for its step number ``t`` (0-based) in closed form, what ``CosineAnnealingLR``'s recursion
+    follows for every t -- past ``T_max`` too, where it climbs again (period 2 ``T_max``).  The trainer's host
+    bookkeeping and the kernels' in-step rate evaluate this expression in float64."""
+    return eta_min + (base_lr - eta_min) * (1 + math.cos(math.pi * t / t_max)) / 2
+
+
+class ImplicitQLearning(_OfflineIQL):
+    """fref:423-563 on the same kernels: no autocast, convex Polyak form, ``max_steps`` the cosine ``T_max``
+    (``train()`` passes ``offline_iterations``; the online steps run past it)."""
+
+    def __init__(self, max_action, actor, actor_optimizer, q_network, q_optimizer, v_network, v_optimizer,
+                 iql_tau: float = 0.7, beta: float = 3.0, max_steps: int = 1000000, discount: float = 0.99,
+                 tau: float = 0.005, device: str = "cpu", *, seed: Optional[int] = None, keep_grads: bool = False,
+                 precision: str = "fp32"):
+        super().__init__(max_action, actor, actor_optimizer, q_network, q_optimizer, v_network, v_optimizer,
+                         iql_tau=iql_tau, beta=beta, max_steps=max_steps, discount=discount, tau=tau, device=device,
+                         precision=precision, seed=seed, keep_grads=keep_grads, polyak_form=1)
+        self._explore_calls = 0
+
+    def explore_action(self, states, eps=None, *, expl_noise: float = 0.03, noise_clip: float = 0.5,
+                       batch_size: Optional[int] = None) -> torch.Tensor:
+        """fref:681-693 for ``states`` [rows, S] (array or tensor): the actor's forward on the live weights,
+        then ``mean + std * eps`` (Gaussian) or ``out + clamp(expl_noise * eps, +-noise_clip)`` (deterministic),
+        scaled by ``max_action`` and clamped to it.  ``eps`` [rows, A]: the standard normals to use; None
+        draws them on the device from the trainer's Philox key.  Returns a float32 device tensor [rows, A]."""
+        if self._precision != _lib.PREC_FP32:
+            raise NotImplementedError("explore_action needs a precision='fp32' trainer (the fine-tune flavour runs "
+                                      "without autocast)")
+        s = torch.as_tensor(np.asarray(states) if not torch.is_tensor(states) else states)
+        s = s.to(device=self._dev, dtype=torch.float32).reshape(-1, self._state_dim).contiguous()
+        rows = s.shape[0]
+        if rows < 1:
+            raise ValueError("explore_action needs at least one state")
+        if eps is not None:
+            eps = torch.as_tensor(np.asarray(eps) if not torch.is_tensor(eps) else eps)
+            eps = eps.to(device=self._dev, dtype=torch.float32).contiguous()
+            if tuple(eps.shape) != (rows, self._action_dim):
+                raise ValueError(f"eps must have shape {(rows, self._action_dim)}, got {tuple(eps.shape)}")
+        self._ensure_handle(batch_size or self._handle_batch or 32)
+        out = torch.empty((rows, self._action_dim), dtype=torch.float32, device=self._dev)
+        with torch.cuda.device(self._dev):
+            check(self._lib.iqlhip_explore_action(self._handle, ptr(s), rows, ptr(eps), float(expl_noise),
+                                                  float(noise_clip), float(self.max_action),
+                                                  self._explore_calls & 0xFFFFFFFF, ptr(out), stream_ptr()))
+        self._explore_calls += 1
+        return out
+
+    def state_dict(self):
+        """The reference's keys and ``explore_calls``: the number that keys the next exploring call's noise and
+        dropout masks, so that a resumed run does not draw the blocks of its first ticks again."""
+        sd = super().state_dict()
+        sd["explore_calls"] = self._explore_calls
+        return sd
+
+    def load_state_dict(self, state_dict):
+        sd = dict(state_dict)
+        self._explore_calls = int(sd.pop("explore_calls", 0))  # (a checkpoint of the reference has none)
+        super().load_state_dict(sd)
+
+
+# --------------------------------------------------------------------------- #
+# train (fref:566-767)
+# --------------------------------------------------------------------------- #
+def _gym_and_d4rl():
+    try:
+        import d4rl
+        import gym
+    except ImportError:
+        raise ImportError("finetune.train: env=None / dataset=None build them with gym and d4rl, which are not "
+                          "installed; pass env=, eval_env= and dataset=") from None
+    return gym, d4rl
+
+
+def train(config: TrainConfig, env=None, eval_env=None, dataset: Optional[Dict[str, np.ndarray]] = None, *,
+          logger: Optional[Callable[[Dict[str, float], int], None]] = None,
+          normalized_score: Optional[Callable[[float], float]] = None, device: Optional[str] = None,
+          chunk: int = 2000, online_chunk: int = 256,
+          exploration_noise: Optional[Callable[[int], Union[np.ndarray, torch.Tensor]]] = None,
+          on_start: Optional[Callable] = None):
+    """fref:566-767 on the HIP path.
+
+    ``env`` / ``eval_env``: gym < 0.26 environments (``seed``, ``reset() -> obs``, ``step(a) -> (obs, r, done,
+    info)``, ``_max_episode_steps``, spaces); None builds ``gym.make(config.env)``.  ``dataset``: the d4rl
+    transition dict (None: ``d4rl.qlearning_dataset(env)``); its rewards are rescaled in place with
+    ``normalize_reward``, as fref does.  ``logger(record, step)``: one call per ``wandb.log`` of fref (default:
+    wandb when importable, else print).  ``normalized_score(score)``: default ``eval_env.get_normalized_score``.
+
+    Offline steps run in chunks of at most ``chunk`` that end on evaluation boundaries, their indices drawn
+    by ``NumpyIndexStream``.  The indices of the online ticks are drawn ``online_chunk`` ticks ahead by
+    ``GrowingIndexStream``: numpy's global generator then runs ahead of the environment by up to that many
+    draws, which only an environment that itself reads numpy's global generator could notice
+    (``online_chunk=1`` keeps fref's interleaving).  Losses come back to the host once per chunk.
+    ``exploration_noise(tick)``: the standard normals [A] of online tick ``tick`` (parity runs); None draws
+    them on the device.  ``on_start(trainer, replay_buffer)`` is called before the first step.
+    Returns the trainer."""
+    if device is None:
+        device = D.local_device() or ("cuda:0" if config.device == "cuda" else config.device)
+    if env is None or eval_env is None or dataset is None:
+        gym, d4rl = _gym_and_d4rl()
+        env = gym.make(config.env) if env is None else env
+        eval_env = gym.make(config.env) if eval_env is None else eval_env
+        if dataset is None:
+            dataset = d4rl.qlearning_dataset(env)
+    if normalized_score is None:
+        normalized_score = eval_env.get_normalized_score
+    is_env_with_goal = config.env.startswith(ENVS_WITH_GOAL)
+    max_steps = env._max_episode_steps
+    state_dim = env.observation_space.shape[0]
+    action_dim = env.action_space.shape[0]
+    n_off, n_on, B = int(config.offline_iterations), int(config.online_iterations), int(config.batch_size)
+
+    # ---- dataset, normalisation, buffer (fref:578-603) ----
+    reward_mod_dict = {}
+    if config.normalize_reward:
+        reward_mod_dict = modify_reward(dataset, config.env)
+    if config.normalize:
+        state_mean, state_std = compute_mean_std(dataset["observations"], eps=1e-3)
+    else:
+        state_mean, state_std = 0, 1
+    dataset["observations"] = normalize_states(dataset["observations"], state_mean, state_std)
+    dataset["next_observations"] = normalize_states(dataset["next_observations"], state_mean, state_std)
+    env = wrap_env(env, state_mean=state_mean, state_std=state_std)
+    eval_env = wrap_env(eval_env, state_mean=state_mean, state_std=state_std)
+    replay_buffer = ReplayBuffer(state_dim, action_dim, config.buffer_size, device)
+    replay_buffer.load_d4rl_dataset(dataset)
+    max_action = float(env.action_space.high[0])
+    ckpt_dir = _offline_loop.checkpoint_dirs(config, [config.seed])[0]
+
+    # ---- seeds and nets (fref:613-660) ----
+    seed = config.seed
+    set_seed(seed, env)
+    eval_env.seed(config.eval_seed)
+    eval_env.action_space.seed(config.eval_seed)
+    dropout = config.actor_dropout if config.actor_dropout and config.actor_dropout > 0.0 else None  # fref:314
+    q_network = TwinQ(state_dim, action_dim).to(device)
+    v_network = ValueFunction(state_dim).to(device)
+    policy = DeterministicPolicy if config.iql_deterministic else GaussianPolicy
+    actor = policy(state_dim, action_dim, max_action, dropout=dropout).to(device)
+    v_optimizer = torch.optim.Adam(v_network.parameters(), lr=config.vf_lr)
+    q_optimizer = torch.optim.Adam(q_network.parameters(), lr=config.qf_lr)
+    actor_optimizer = torch.optim.Adam(actor.parameters(), lr=config.actor_lr)
+    print("---------------------------------------")
+    print(f"Training IQL, Env: {config.env}, Seed: {seed}")
+    print("---------------------------------------")
+    trainer = ImplicitQLearning(max_action=max_action, actor=actor, actor_optimizer=actor_optimizer, q_network=q_network,
+                                q_optimizer=q_optimizer, v_network=v_network, v_optimizer=v_optimizer,
+                                discount=config.discount, tau=config.tau, device=device, beta=config.beta,
+                                iql_tau=config.iql_tau, max_steps=n_off, seed=seed)
+    if config.load_model != "":
+        trainer.load_state_dict(torch.load(config.load_model))
+    if logger is None:
+        logger = _offline_loop.default_logger(config, 1)
+    if on_start is not None:
+        on_start(trainer, replay_buffer)
+
+    train_successes, eval_successes, evaluations = [], [], []
+    pending = []  # (first t, device losses [n, 3], the online records of those steps or None)
+
+    def flush():
+        for t0, losses, extras in pending:
+            for i, (v, q, a) in enumerate(losses.cpu().numpy().tolist()):
+                t = t0 + i
+                rec = {"value_loss": v, "q_loss": q, "actor_loss": a}
+                rec["offline_iter" if t < n_off else "online_iter"] = t if t < n_off else t - n_off
+                if extras is not None:
+                    rec.update(extras[i])
+                logger(rec, t + 1)  # (step = trainer.total_it after the step, fref:734)
+        pending.clear()
+
+    def evaluate(t):
+        """fref:736-767, after step t."""
+        flush()
+        print(f"Time steps: {t + 1}")
+        eval_scores, success_rate = eval_actor(eval_env, actor, device=device, n_episodes=config.n_episodes,
+                                               seed=config.seed)
+        eval_score = eval_scores.mean()
+        eval_log = {}
+        normalized = normalized_score(eval_score)
+        if t >= n_off and is_env_with_goal:
+            eval_successes.append(success_rate)
+            eval_log["eval/regret"] = np.mean(1 - np.array(train_successes))  # (of the TRAINING episodes, as fref:751)
+            eval_log["eval/success_rate"] = success_rate
+        normalized_eval_score = normalized * 100.0
+        evaluations.append(normalized_eval_score)
+        eval_log["eval/d4rl_normalized_score"] = normalized_eval_score
+        print("---------------------------------------")
+        print(f"Evaluation over {config.n_episodes} episodes: {eval_score:.3f} , D4RL score: {normalized_eval_score:.3f}")
+        print("---------------------------------------")
+        if ckpt_dir is not None:
+            torch.save(trainer.state_dict(), os.path.join(ckpt_dir, f"checkpoint_{t}.pt"))
+        logger(eval_log, t + 1)
+
+    every = int(config.eval_freq)
+    state, done = env.reset(), False
+    episode_return, episode_step, goal_achieved = 0, 0, False
+
+    # ---- offline pretraining: the chunked loop of the offline flavours ----
+    print("Offline pretraining")
+    offline_stream = NumpyIndexStream(device) if n_off > 0 else None
+    t = 0
+    while t < n_off:
+        nxt = min(n_off, t + int(chunk), (t // every + 1) * every)
+        idx = offline_stream.draw(replay_buffer.index_bound(), nxt - t, B)[0]
+        losses = trainer.train_steps(replay_buffer, nxt - t, B, indices=idx)
+        flush()
+        pending.append((t, losses, None))
+        t = nxt
+        if t % every == 0:
+            evaluate(t - 1)
+
+    # ---- online tuning: act, step the environment, append, one gradient step ----
+    if n_on > 0:
+        print("Online tuning")
+    online_stream = GrowingIndexStream(device) if n_on > 0 else None
+    chunk_idx, chunk_t0 = None, 0
+    for t in range(n_off, n_off + n_on):
+        tick = t - n_off
+        if chunk_idx is None or tick - chunk_t0 >= chunk_idx.shape[0]:
+            flush()
+            n = min(max(1, int(online_chunk)), n_on - tick)
+            hi0 = min(replay_buffer.index_bound() + 1, int(config.buffer_size))
+            chunk_idx, chunk_t0 = online_stream.draw(hi0, int(config.buffer_size), n, B)[0], tick
+        online_log = {}
+        episode_step += 1
+        eps = None if exploration_noise is None else torch.as_tensor(np.asarray(exploration_noise(tick))).reshape(1, -1)
+        action = trainer.explore_action(np.asarray(state).reshape(1, -1), eps, expl_noise=config.expl_noise,
+                                        noise_clip=config.noise_clip, batch_size=B)
+        action = action.cpu().numpy().flatten()
+        next_state, reward, done, env_infos = env.step(action)
+        if not goal_achieved:
+            goal_achieved = is_goal_reached(reward, env_infos)
+        episode_return += reward
+        real_done = bool(done and episode_step < max_steps)  # (a timeout ends the episode but is no terminal)
+        if config.normalize_reward:
+            reward = modify_reward_online(reward, config.env, **reward_mod_dict)
+        replay_buffer.add_transition(state, action, reward, next_state, real_done)
+        state = next_state
+        if done:
+            state, done = env.reset(), False
+            if is_env_with_goal:
+                train_successes.append(goal_achieved)
+                online_log["train/regret"] = np.mean(1 - np.array(train_successes))
+                online_log["train/is_success"] = float(goal_achieved)
+            online_log["train/episode_return"] = episode_return
+            online_log["train/d4rl_normalized_episode_return"] = normalized_score(episode_return) * 100.0
+            online_log["train/episode_length"] = episode_step
+            episode_return, episode_step, goal_achieved = 0, 0, False
+        j = tick - chunk_t0
+        losses = trainer.train_steps(replay_buffer, 1, B, indices=chunk_idx[j:j + 1])
+        pending.append((t, losses, [online_log]))
+        if (t + 1) % every == 0:
+            evaluate(t)
+    flush()
+    return trainer

@@ -1,0 +1,86 @@
+#!/usr/bin/env python3
+"""Cost of one online fine-tuning tick (iqlpref_amd.finetune) with a null environment.
+
+    python tools/bench_finetune.py [--ticks 2000] [--warmup 200] [--batch 256] [--rows 100000]
+
+A tick is what ``finetune.train`` does per online step: ``explore_action`` and its copy to the host (the
+environment needs the action), ``add_transition``, one ``train_steps(n_steps=1)`` on pre-drawn indices.  The
+environment is null: the next state is a fixed array.  Prints one JSON line: microseconds per tick, its split
+into act / append / step (each timed on the host around its own call, with a device synchronisation after the
+step so that the three add up to the tick), and beside them the microseconds of a bare ``train_steps(n_steps=1)``
+call in a loop on the same trainer -- the floor the tick cannot go under.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+import iqlpref_amd as ia  # noqa: E402
+from iqlpref_amd import _lib, finetune as ft  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--ticks", type=int, default=2000)
+    ap.add_argument("--warmup", type=int, default=200)
+    ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--rows", type=int, default=100000)
+    ap.add_argument("--state-dim", type=int, default=17)
+    ap.add_argument("--action-dim", type=int, default=6)
+    args = ap.parse_args()
+    dev, S, A, B = "cuda:0", args.state_dim, args.action_dim, args.batch
+    total = args.warmup + args.ticks
+    rng = np.random.default_rng(0)
+    data = {"observations": rng.standard_normal((args.rows, S)).astype(np.float32),
+            "actions": rng.uniform(-1, 1, (args.rows, A)).astype(np.float32),
+            "rewards": rng.standard_normal(args.rows).astype(np.float32),
+            "next_observations": rng.standard_normal((args.rows, S)).astype(np.float32),
+            "terminals": (rng.uniform(size=args.rows) < 0.01).astype(np.float32)}
+    torch.manual_seed(0)
+    q, v, actor = ia.TwinQ(S, A).to(dev), ia.ValueFunction(S).to(dev), ia.GaussianPolicy(S, A, 1.0).to(dev)
+    tr = ft.ImplicitQLearning(1.0, actor, torch.optim.Adam(actor.parameters(), lr=3e-4), q,
+                              torch.optim.Adam(q.parameters(), lr=3e-4), v, torch.optim.Adam(v.parameters(), lr=3e-4),
+                              max_steps=10 ** 6, device=dev, seed=0)
+    buf = ft.ReplayBuffer(S, A, args.rows + total // 2, dev)  # (the ring fills half way through: both regimes)
+    buf.load_d4rl_dataset(data)
+    np.random.seed(0)
+    idx = ft.GrowingIndexStream(dev).draw(min(buf.index_bound() + 1, buf._buffer_size), buf._buffer_size, total, B)[0]
+    state = rng.standard_normal(S)
+    nxt = rng.standard_normal(S)
+    t_act = t_app = t_step = 0.0
+    for i in range(total):
+        if i == args.warmup:
+            torch.cuda.synchronize()
+            t_act = t_app = t_step = 0.0
+        t0 = time.perf_counter()
+        action = tr.explore_action(state.reshape(1, -1), None, batch_size=B).cpu().numpy().flatten()
+        t1 = time.perf_counter()
+        buf.add_transition(state, action, 0.5, nxt, False)
+        t2 = time.perf_counter()
+        tr.train_steps(buf, 1, B, indices=idx[i:i + 1], return_losses=False)
+        torch.cuda.synchronize()
+        t3 = time.perf_counter()
+        t_act, t_app, t_step = t_act + t1 - t0, t_app + t2 - t1, t_step + t3 - t2
+    # the floor: the same call with nothing around it (the device queue never runs dry: no sync inside)
+    floor_idx = idx[:1]
+    for _ in range(args.warmup):
+        tr.train_steps(buf, 1, B, indices=floor_idx, return_losses=False)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(args.ticks):
+        tr.train_steps(buf, 1, B, indices=floor_idx, return_losses=False)
+    torch.cuda.synchronize()
+    floor = (time.perf_counter() - t0) / args.ticks
+    us = lambda x: round(1e6 * x / args.ticks, 2)
+    print(json.dumps({"tool": "bench_finetune", "build_tag": _lib.build_tag(), "ticks": args.ticks, "batch": B,
+                      "state_dim": S, "action_dim": A, "tick_us": us(t_act + t_app + t_step), "act_us": us(t_act),
+                      "append_us": us(t_app), "step_us": us(t_step), "bare_train_step_us": round(1e6 * floor, 2)}))
+
+
+if __name__ == "__main__":
+    main()
