@@ -572,6 +572,58 @@ int iqlhip_block_epoch_indices_group(const int64_t *const *perm, int64_t n_rows,
                                      void *stream);
 
 /* ------------------------------------------------------------------------ */
+/* The BB flavour's evaluation simulator, algorithms/custom_offline/iql_bb.py   */
+/* :675-867, on the device (csrc/bb_sim.hip): the state of ONE episode lives in  */
+/* device memory, the actor's forward and one simulator step alternate on one    */
+/* stream, and the host waits for nothing between them.  The host draws the      */
+/* set-up and the whole drift table from numpy's generator and uploads them.     */
+/* ------------------------------------------------------------------------ */
+typedef struct {
+  int32_t n_obs;       /* obstacles, 1..1024 (the levels have 50 / 100 / 150)                     */
+  int32_t n_near;      /* obstacles in an observation, 1..min(n_obs, 16)                          */
+  int32_t state_dim;   /* 2 + 3 n_near + 6: agent x y, (x y heading) per obstacle, goal x y, tail */
+  int32_t action_dim;  /* 2: speed, heading in degrees                                            */
+  int32_t max_horizon; /* >= 1                                                                    */
+  int32_t actor_out_stride; /* 0: step t reads actor_out[0 .. 2) (the forward's live output row);
+                               >= 2: it reads actor_out[t * stride ..), a table of injected rows  */
+  double *state;       /* device f64 [8 + 3 n_obs]: agent x y, goal x y, level, ai, attempt, day,
+                          ox[n_obs], oy[n_obs], oang[n_obs]; uploaded per episode, advanced in place */
+  const double *drift; /* device f64 [max_horizon][n_obs]: the obstacles' drift of every step     */
+  int32_t *ctl;        /* device int32 [2]: steps taken, done flag; once done (or at max_horizon)
+                          [0] is the episode's length                                             */
+  float *obs_hist;     /* device fp32 [max_horizon + 1][state_dim]: raw observations              */
+  float *act_hist;     /* device fp32 [max_horizon][2]: clamped actions                           */
+  double *record;      /* device f64 [max_horizon + 1][state_dim]: every observation, unrounded   */
+  float *actor_in;     /* device fp32 [state_dim]: (observation - mean) / std, formed in double and
+                          rounded once: the row the next forward reads                            */
+  float *actor_out;    /* device fp32: see actor_out_stride                                       */
+  const double *state_mean, *state_std; /* device f64 [state_dim]                                 */
+  const float *min_actions, *max_actions; /* device fp32 [2]: the clamp of bref:344-350           */
+} iqlhip_bb_sim;
+
+/* Observation row 0 (record, obs_hist, actor_in) from the set-up in `state`; ctl = {0, 0}.  One launch. */
+int iqlhip_bb_sim_reset(const iqlhip_bb_sim *sim, void *stream);
+/* One simulator step, one launch: with t = ctl[0], nothing at all is written when ctl[1] is set or
+ * t == max_horizon; otherwise the action row is clamped per component in fp32 (torch.clamp) and stored as
+ * act_hist[t]; the agent moves by speed * (cos, sin)(heading) in numpy's float32 arithmetic (what the
+ * reference's scalar expressions evaluate to, see csrc/bb_sim.hip) and the obstacles by drift[t] along
+ * their headings in float64, one that leaves the disc of radius 50 re-entering at its mirrored OLD
+ * position; the goal counts as reached when the closest point of the agent's segment lies within
+ * (0.3 + 1)^2 of it (np.isclose included); observation row t + 1 and the next actor input are written,
+ * ctl[0] = t + 1 and ctl[1] = reached.  The nearest obstacles are taken in ascending distance, ties by
+ * lowest index.                                                                                      */
+int iqlhip_bb_sim_step(const iqlhip_bb_sim *sim, void *stream);
+/* n_steps >= 1 times { iqlhip_mlp_forward(actor, actor_in, 1 row) -> actor_out; iqlhip_bb_sim_step }
+ * on `stream`, no synchronisation: steps queued behind the end of the episode write nothing.  `actor`
+ * maps state_dim inputs to 2 outputs (the policy's net in eval mode: dropout_p <= 0 is the caller's
+ * to set); actor_out_stride must be 0.
+ * All three refuse, before any launch: a null pointer (IQLHIP_ERR_INVALID), n_obs outside 1..1024,
+ * n_near outside 1..min(n_obs, 16), action_dim != 2 (IQLHIP_ERR_UNSUPPORTED), state_dim !=
+ * 2 + 3 n_near + 6, max_horizon < 1, actor_out_stride 1 or negative (IQLHIP_ERR_INVALID).           */
+int iqlhip_bb_sim_rollout(const iqlhip_bb_sim *sim, const iqlhip_mlp_desc *actor, int32_t n_steps,
+                          void *stream);
+
+/* ------------------------------------------------------------------------ */
 /* Posterior relabel of algorithms/custom_offline/iql_br.py:179-253: per       */
 /* transition, n_samps draws of np.random.choice over the S posterior          */
 /* predictions on numpy's legacy generator, reduced on the device              */

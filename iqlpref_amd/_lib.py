@@ -92,6 +92,13 @@ class PtModel(C.Structure):
                 [("pref_b_last", C.c_float), ("blocks", C.POINTER(PtBlock))])
 
 
+class BbSim(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("n_obs", "n_near", "state_dim", "action_dim", "max_horizon",
+                                          "actor_out_stride")] +
+                [(n, C.c_void_p) for n in ("state", "drift", "ctl", "obs_hist", "act_hist", "record", "actor_in",
+                                           "actor_out", "state_mean", "state_std", "min_actions", "max_actions")])
+
+
 # every symbol include/iqlhip.h declares: name -> (restype, argtypes)
 P = C.c_void_p
 SYMBOLS = {
@@ -153,6 +160,9 @@ SYMBOLS = {
     "iqlhip_block_epoch_indices": (C.c_int, [P, C.c_int64, C.c_int32, C.c_int64, C.c_int64, P, P, P]),
     "iqlhip_block_epoch_indices_group": (C.c_int, [C.POINTER(P), C.c_int64, C.c_int32, C.c_int64, C.c_int64,
                                                    C.POINTER(P), P, C.c_int32, P]),
+    "iqlhip_bb_sim_reset": (C.c_int, [C.POINTER(BbSim), P]),
+    "iqlhip_bb_sim_step": (C.c_int, [C.POINTER(BbSim), P]),
+    "iqlhip_bb_sim_rollout": (C.c_int, [C.POINTER(BbSim), C.POINTER(MlpDesc), C.c_int32, P]),
     "iqlhip_posterior_choice_workspace_bytes": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_size_t)]),
     "iqlhip_posterior_choice": (C.c_int, [P, P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, P, P, P, C.c_size_t, P]),
     "iqlhip_step_cost": (C.c_int, [C.POINTER(TrainerConfig), C.POINTER(C.c_double),

@@ -91,6 +91,7 @@ hipError_t launch_explore_epilogue(float *act, int64_t rows, int A, const float 
                                    hipStream_t st);
 hipError_t launch_np_randint(uint32_t *state, const int64_t *hi, int K, int64_t total, int64_t *const *out,
                              hipStream_t st);
+hipError_t launch_bb_step(const iqlhip_bb_sim &sim, int reset, hipStream_t st);
 size_t choice_workspace_bytes(int64_t N, int n);
 int64_t choice_fit_rows(int64_t N, int n, size_t bytes);
 hipError_t launch_posterior_choice(uint32_t *state, const float *preds, int S, int64_t N, int n, int mode,
@@ -1696,6 +1697,59 @@ extern "C" int iqlhip_block_epoch_indices_group(const int64_t *const *perm, int6
   }
   if (n_steps == 0) return 0;
   HIP_TRY(launch_block_epoch_group(perm, n_rows, batch, t0, n_steps, idx, n_valid, K, (hipStream_t)stream));
+  return 0;
+}
+
+// ------------------------------------------------------- BB evaluation simulator --
+static int bb_sim_check(const iqlhip_bb_sim *s) {
+  if (!s) return fail(IQLHIP_ERR_INVALID, "null simulator");
+  if (!s->state || !s->drift || !s->ctl || !s->obs_hist || !s->act_hist || !s->record || !s->actor_in ||
+      !s->actor_out || !s->state_mean || !s->state_std || !s->min_actions || !s->max_actions)
+    return fail(IQLHIP_ERR_INVALID, "null pointer in the simulator");
+  if (s->n_obs < 1 || s->n_obs > 1024) return fail(IQLHIP_ERR_UNSUPPORTED, "n_obs = %d outside 1..1024", s->n_obs);
+  const int near_max = s->n_obs < 16 ? s->n_obs : 16;
+  if (s->n_near < 1 || s->n_near > near_max)
+    return fail(IQLHIP_ERR_UNSUPPORTED, "n_near = %d outside 1..%d", s->n_near, near_max);
+  if (s->action_dim != 2)
+    return fail(IQLHIP_ERR_UNSUPPORTED, "action_dim = %d: the simulator's action is (speed, heading)", s->action_dim);
+  if (s->state_dim != 2 + 3 * s->n_near + 6)
+    return fail(IQLHIP_ERR_INVALID, "state_dim = %d, an observation of %d obstacles has %d columns", s->state_dim,
+                s->n_near, 2 + 3 * s->n_near + 6);
+  if (s->max_horizon < 1) return fail(IQLHIP_ERR_INVALID, "max_horizon = %d must be >= 1", s->max_horizon);
+  if (s->actor_out_stride != 0 && s->actor_out_stride < s->action_dim)
+    return fail(IQLHIP_ERR_INVALID, "actor_out_stride = %d must be 0 or >= 2", s->actor_out_stride);
+  return 0;
+}
+
+extern "C" int iqlhip_bb_sim_reset(const iqlhip_bb_sim *sim, void *stream) {
+  if (int rc = bb_sim_check(sim)) return rc;
+  HIP_TRY(launch_bb_step(*sim, 1, (hipStream_t)stream));
+  return 0;
+}
+
+extern "C" int iqlhip_bb_sim_step(const iqlhip_bb_sim *sim, void *stream) {
+  if (int rc = bb_sim_check(sim)) return rc;
+  HIP_TRY(launch_bb_step(*sim, 0, (hipStream_t)stream));
+  return 0;
+}
+
+extern "C" int iqlhip_bb_sim_rollout(const iqlhip_bb_sim *sim, const iqlhip_mlp_desc *actor, int32_t n_steps,
+                                     void *stream) {
+  if (int rc = bb_sim_check(sim)) return rc;
+  if (!actor) return fail(IQLHIP_ERR_INVALID, "null actor");
+  if (n_steps < 1) return fail(IQLHIP_ERR_INVALID, "n_steps = %d must be >= 1", n_steps);
+  if (sim->actor_out_stride != 0)
+    return fail(IQLHIP_ERR_INVALID, "a rollout reads the forward's live output row: actor_out_stride must be 0");
+  if (actor->n_layers < 1 || actor->n_layers > IQLHIP_MLP_MAX_LAYERS)
+    return fail(IQLHIP_ERR_INVALID, "n_layers must be in [1, %d]", IQLHIP_MLP_MAX_LAYERS);
+  if (actor->dims[0] != sim->state_dim || actor->dims[actor->n_layers] != sim->action_dim)
+    return fail(IQLHIP_ERR_INVALID, "the actor maps %d -> %d, the simulator needs %d -> %d", actor->dims[0],
+                actor->dims[actor->n_layers], sim->state_dim, sim->action_dim);
+  for (int i = 0; i < n_steps; ++i) {
+    if (int rc = iqlhip_mlp_forward(actor, sim->actor_in, 1, sim->state_dim, sim->actor_out, sim->action_dim, stream))
+      return rc;
+    HIP_TRY(launch_bb_step(*sim, 0, (hipStream_t)stream));
+  }
   return 0;
 }
 

@@ -24,6 +24,9 @@ Differences from ``custom_offline`` (``iql.py``) and how they map onto the same 
 to a goal among drifting obstacles, rewarded by the preference model over a rolling context.  It makes
 the same ``default_rng(seed)`` calls in the same order with the same float arithmetic, so that equal
 actions give equal states and returns.
+``bb_run_eval_device`` (``train(eval_on="device")``) is the same evaluation with the step loop on the GPU
+(csrc/bb_sim.hip): the host draws the set-up and the drift table, the actor's forward and one simulator step
+alternate on one stream, and one ``window_values`` call per episode gives the rewards.
 
 ``train(seeds_per_gpu=K)`` steps K seeds side by side on one GPU as one ``SeedGroup``: each seed walks its
 own block permutation (``BlockEpochSamplerGroup`` writes the K index arrays and the one shared count array
@@ -36,6 +39,7 @@ Sweeps and bf16 are not offered for this flavour.
 """
 import ctypes as C
 import os
+import time
 import uuid
 from dataclasses import dataclass
 from typing import Any, Callable, Dict, List, Mapping, Optional, Sequence, Tuple
@@ -414,6 +418,31 @@ def _observe(goal, px, py, ox, oy, oang, tail, n_near):
     return np.asarray(s)
 
 
+def _episode_setup(rng, days):
+    """The draws that open an episode (bref:690-741), in the reference's order: level, ai, attempt, day,
+    the obstacles' disc points and headings, a start more than 1 away from obstacle 0, a goal about 30
+    away inside the arena.  Returns (n_obs, ox, oy, oang, px, py, goal, tail)."""
+    level = rng.choice([9, 10, 11])
+    n_obs = {9: 50, 10: 100}.get(int(level), 150)
+    ai = rng.choice([1, 2, 3, 4])
+    attempt = rng.choice(4)
+    day = rng.choice(days)
+    ox, oy = _disc_point(ARENA_RADIUS, n_obs, rng)
+    oang = rng.uniform(0.0, 360.0, n_obs)
+    while True:  # a start more than 1 away from obstacle 0
+        sx, sy = _disc_point(ARENA_RADIUS, None, rng)
+        if np.all(((sx - ox[0]) ** 2) + ((sy - oy[0]) ** 2) > 1):
+            break
+    px, py = float(sx), float(sy)
+    while True:  # a goal about 30 away, inside the arena
+        heading = rng.uniform(0.0, 360.0)
+        reach = rng.normal(30)
+        goal = (float(px + reach * _cos_deg(heading)), float(py + reach * _sin_deg(heading)))
+        if ((goal[0] ** 2) + (goal[1] ** 2)) <= ARENA_RADIUS ** 2:
+            break
+    return n_obs, ox, oy, oang, px, py, goal, (level, ai, attempt, day)
+
+
 def bb_run_eval_IQL(actor, num_episodes, r_model, move_stats, state_mean=0, state_std=1, max_horizon=500,
                     n_min_obstacles=6, days=181, context_length=100, seed=4, device="cpu"):
     """bref:675-867.  ``num_episodes`` episodes of a point agent in a disc of radius 50: 50 / 100 / 150
@@ -429,25 +458,7 @@ def bb_run_eval_IQL(actor, num_episodes, r_model, move_stats, state_mean=0, stat
     returns = []
     rng = np.random.default_rng(seed)
     for _ in range(num_episodes):
-        level = rng.choice([9, 10, 11])
-        n_obs = {9: 50, 10: 100}.get(int(level), 150)
-        ai = rng.choice([1, 2, 3, 4])
-        attempt = rng.choice(4)
-        day = rng.choice(days)
-        ox, oy = _disc_point(ARENA_RADIUS, n_obs, rng)
-        oang = rng.uniform(0.0, 360.0, n_obs)
-        while True:  # a start more than 1 away from obstacle 0
-            sx, sy = _disc_point(ARENA_RADIUS, None, rng)
-            if np.all(((sx - ox[0]) ** 2) + ((sy - oy[0]) ** 2) > 1):
-                break
-        px, py = float(sx), float(sy)
-        while True:  # a goal about 30 away, inside the arena
-            heading = rng.uniform(0.0, 360.0)
-            reach = rng.normal(30)
-            goal = (float(px + reach * _cos_deg(heading)), float(py + reach * _sin_deg(heading)))
-            if ((goal[0] ** 2) + (goal[1] ** 2)) <= ARENA_RADIUS ** 2:
-                break
-        tail = (level, ai, attempt, day)
+        n_obs, ox, oy, oang, px, py, goal, tail = _episode_setup(rng, days)
         s = _observe(goal, px, py, ox, oy, oang, tail, n_min_obstacles).reshape(1, 1, -1)
         a = np.zeros((1, 0, 2))
         t = np.zeros((1, 1), dtype=np.int32)
@@ -500,6 +511,206 @@ class RewardPTContext:
 
 
 # --------------------------------------------------------------------------- #
+# the same evaluation with the step loop on the device (csrc/bb_sim.hip)
+# --------------------------------------------------------------------------- #
+class DeviceEpisode:
+    """The device state of one simulated episode and the launches that advance it: ``load`` uploads a
+    set-up and its drift table, ``reset`` writes observation row 0, ``step`` is one ``iqlhip_bb_sim_step``
+    and ``rollout`` n times (actor forward, step) in one library call; ``poll`` is the one place that waits
+    for the device.  The buffers are allocated once and serve every episode of an evaluation.
+
+    ``injected``: an fp32 [max_horizon, 2] table of raw actor outputs that step t reads in place of the
+    forward's output row (tests)."""
+
+    def __init__(self, n_near: int, max_horizon: int, state_mean, state_std, min_actions, max_actions, device,
+                 n_obs_max: int = 150, injected=None):
+        self.lib = _lib.load()
+        self.dev = _lib.require_gpu(device)
+        self.n_near, self.H = int(n_near), int(max_horizon)
+        self.S, self.A = 2 + 3 * self.n_near + 2 + STATE_TAIL, 2
+        S, H, dev = self.S, self.H, self.dev
+        f64 = lambda x: torch.from_numpy(np.array(np.broadcast_to(np.asarray(x, np.float64), (S,)))).to(dev)
+        lim = lambda x: torch.as_tensor(x).detach().to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+        self.mean, self.std = f64(state_mean), f64(state_std)
+        self.lo, self.hi = lim(min_actions), lim(max_actions)
+        if self.lo.numel() != 2 or self.hi.numel() != 2:
+            raise ValueError("min_actions and max_actions hold (speed, heading)")
+        self.n_obs_max = int(n_obs_max)
+        self.state = torch.zeros(8 + 3 * self.n_obs_max, dtype=torch.float64, device=dev)
+        self.drift = torch.zeros(H * self.n_obs_max, dtype=torch.float64, device=dev)
+        self.ctl = torch.zeros(2, dtype=torch.int32, device=dev)
+        self.obs_hist = torch.zeros((H + 1, S), dtype=torch.float32, device=dev)
+        self.act_hist = torch.zeros((H, 2), dtype=torch.float32, device=dev)
+        self.record = torch.zeros((H + 1, S), dtype=torch.float64, device=dev)
+        self.actor_in = torch.zeros(S, dtype=torch.float32, device=dev)
+        self.actor_out = torch.zeros(2, dtype=torch.float32, device=dev)
+        self.injected = None
+        if injected is not None:
+            self.injected = torch.as_tensor(np.ascontiguousarray(injected, dtype=np.float32)).to(dev)
+            if self.injected.shape != (self.H, 2):
+                raise ValueError(f"injected actions must be [{self.H}, 2]")
+        self.n_obs = 0
+        self.sim = None
+
+    def _struct(self, n_obs: int) -> "_lib.BbSim":
+        b = _lib.BbSim()
+        b.n_obs, b.n_near, b.state_dim, b.action_dim, b.max_horizon = n_obs, self.n_near, self.S, self.A, self.H
+        b.actor_out_stride = 0 if self.injected is None else 2
+        out = self.actor_out if self.injected is None else self.injected
+        for name, t in (("state", self.state), ("drift", self.drift), ("ctl", self.ctl), ("obs_hist", self.obs_hist),
+                        ("act_hist", self.act_hist), ("record", self.record), ("actor_in", self.actor_in),
+                        ("actor_out", out), ("state_mean", self.mean), ("state_std", self.std),
+                        ("min_actions", self.lo), ("max_actions", self.hi)):
+            setattr(b, name, t.data_ptr())
+        return b
+
+    def load(self, ox, oy, oang, px, py, goal, tail, drift):
+        """One upload of the set-up and one of the [max_horizon, n_obs] drift table, on the current stream."""
+        n_obs = int(len(ox))
+        if n_obs > self.n_obs_max:
+            raise ValueError(f"{n_obs} obstacles, the buffers hold {self.n_obs_max}")
+        drift = np.ascontiguousarray(drift, dtype=np.float64)
+        if drift.shape != (self.H, n_obs):
+            raise ValueError(f"the drift table must be [{self.H}, {n_obs}]")
+        host = np.concatenate([[px, py, goal[0], goal[1]], [float(v) for v in tail], ox, oy, oang]).astype(np.float64)
+        self.state[:host.size].copy_(torch.from_numpy(host), non_blocking=False)
+        self.drift[:drift.size].copy_(torch.from_numpy(drift.reshape(-1)), non_blocking=False)
+        self.n_obs, self.sim = n_obs, self._struct(n_obs)
+
+    def reset(self):
+        with torch.cuda.device(self.dev):
+            check(self.lib.iqlhip_bb_sim_reset(C.byref(self.sim), stream_ptr()))
+
+    def step(self):
+        with torch.cuda.device(self.dev):
+            check(self.lib.iqlhip_bb_sim_step(C.byref(self.sim), stream_ptr()))
+
+    def rollout(self, actor_desc, n_steps: int):
+        with torch.cuda.device(self.dev):
+            check(self.lib.iqlhip_bb_sim_rollout(C.byref(self.sim), C.byref(actor_desc), int(n_steps), stream_ptr()))
+
+    def poll(self) -> Tuple[int, bool]:
+        """(steps taken, done): waits for everything queued."""
+        t, done = self.ctl.cpu().tolist()
+        return int(t), bool(done)
+
+
+def _actor_desc(actor):
+    """The ``iqlhip_mlp_desc`` of a policy's net on its live fp32 weights, eval mode (no dropout), and
+    the tensors it points into."""
+    net = getattr(actor, "net", None)
+    if not isinstance(actor, (GaussianPolicy, DeterministicPolicy)) or not hasattr(net, "linears"):
+        raise TypeError("bb_run_eval_device rolls out a custom_offline_bb GaussianPolicy or DeterministicPolicy; "
+                        "bb_run_eval_IQL takes any object with act()")
+    d = _lib.MlpDesc()
+    lin = net.linears()
+    d.n_layers = len(lin)
+    keep = []
+    for i, l in enumerate(lin):
+        w = l.weight.detach().to(torch.float32).contiguous()
+        b = l.bias.detach().to(torch.float32).contiguous()
+        keep += [w, b]
+        d.dims[i], d.dims[i + 1] = w.shape[1], w.shape[0]
+        d.weights[i], d.biases[i] = w.data_ptr(), b.data_ptr()
+    d.w_in_out, d.hidden_act, d.out_act = 0, net._hidden_act, net._out_act
+    return d, keep
+
+
+def _rewind_drift(rng, saved_state, move_stats, length: int, n_obs: int):
+    """Leave ``rng`` where ``length`` per-step draws of ``n_obs`` normals from ``saved_state`` leave it."""
+    rng.bit_generator.state = saved_state
+    if length:
+        rng.normal(move_stats[2], move_stats[3], (length, n_obs))
+
+
+def bb_run_eval_device(actor, num_episodes, r_model, move_stats, state_mean=0, state_std=1, max_horizon=500,
+                       n_min_obstacles=6, days=181, context_length=100, seed=4, device="cuda:0", chunk=64,
+                       record=None):
+    """``bb_run_eval_IQL`` with the step loop on the device: the same episodes, the same generator calls,
+    the same float arithmetic, the same float64 array of returns.
+
+    Per episode the host draws the set-up and the whole [max_horizon, n_obs] drift table from
+    ``default_rng(seed)`` and uploads them; per step it queues the actor's forward (``iqlhip_mlp_forward``
+    on the live weights, the kernel ``actor.act`` reaches) and one ``k_bb_step``, ``chunk`` steps per
+    library call, and reads the done flag once per chunk -- the only waits of the rollout.  Steps queued
+    behind the goal write nothing.  The generator is then put where the numpy loop leaves it (the saved
+    state plus ``length`` rows of drift).  All rewards of an episode come from ONE
+    ``RewardPT.window_values`` call over the device histories: window t covers steps
+    ``max(0, t + 1 - context_length) .. t`` with their true timesteps, what the numpy loop hands to
+    ``RewardPTContext`` step by step; the return is their float64 sum in step order.
+
+    ``r_model``: a ``RewardPTContext`` or a ``RewardPT`` (wrapped with ``context_length``).  ``record``: a
+    dict that receives ``record["episodes"]``, per episode ``states`` (float64 [length + 1, S], every
+    observation), ``actions`` (float32 [length, 2]), ``rewards`` (float64 [length]) and ``length``; a
+    ``record["timing"]`` dict, when present, receives the seconds spent in set-up and upload (``setup``),
+    the step loop (``steps``) and the reward call (``reward``), each closed by a device synchronisation.  The actor is handed back in train mode."""
+    if isinstance(r_model, RewardPT):
+        r_model = RewardPTContext(r_model, context_length)
+    if not isinstance(r_model, RewardPTContext):
+        raise TypeError("bb_run_eval_device takes a RewardPTContext or a RewardPT: its rewards are one window_values "
+                        "call over device histories; bb_run_eval_IQL is the path for any other callable")
+    H, cl, chunk = int(max_horizon), int(context_length), int(chunk)
+    if chunk < 1 or H < 1:
+        raise ValueError("chunk and max_horizon must be >= 1")
+    if min(H, cl) > r_model.context_length:
+        raise ValueError("states, actions and timesteps must share one length <= context_length")
+    desc, keep = _actor_desc(actor)
+    pt_dev = next(r_model.model.parameters()).device
+    actor.eval()
+    returns = []
+    rng = np.random.default_rng(seed)
+    ep = DeviceEpisode(n_min_obstacles, H, state_mean, state_std, actor.min_actions, actor.max_actions, device)
+    steps = np.arange(H)
+    starts = np.maximum(0, steps + 1 - cl)
+    win_start = torch.from_numpy(starts.astype(np.int64)).to(pt_dev)
+    win_len = torch.from_numpy((steps + 1 - starts).astype(np.int32)).to(pt_dev)
+    win_t0 = torch.from_numpy(starts.astype(np.int32)).to(pt_dev)
+    timing = record.get("timing") if isinstance(record, dict) else None
+
+    def mark(phase, t0):
+        if timing is None:
+            return t0
+        torch.cuda.synchronize(ep.dev)
+        now = time.perf_counter()
+        timing[phase] = timing.get(phase, 0.0) + (now - t0 if t0 is not None else 0.0)
+        return now
+
+    for _ in range(num_episodes):
+        t0 = mark("other", None)
+        n_obs, ox, oy, oang, px, py, goal, tail = _episode_setup(rng, days)
+        saved = rng.bit_generator.state
+        drift = rng.normal(move_stats[2], move_stats[3], (H, n_obs))
+        ep.load(ox, oy, oang, px, py, goal, tail, drift)
+        ep.reset()
+        t0 = mark("setup", t0)
+        queued, length, done = 0, 0, False
+        while queued < H and not done:
+            n = min(chunk, H - queued)
+            ep.rollout(desc, n)
+            queued += n
+            length, done = ep.poll()
+        _rewind_drift(rng, saved, move_stats, length, n_obs)
+        t0 = mark("steps", t0)
+        values = np.zeros(0)
+        if length:
+            v = r_model.model.window_values(ep.obs_hist.to(pt_dev), ep.act_hist.to(pt_dev), win_start[:length],
+                                            win_len[:length], r_model.context_length, win_t0=win_t0[:length])
+            values = v.cpu().numpy().astype(np.float64)
+        episode_return = np.zeros(1)
+        for x in values:  # (0.0 + r_0 + r_1 + ..., the order of the numpy loop)
+            episode_return = episode_return + x
+        returns.append(episode_return)
+        t0 = mark("reward", t0)
+        if isinstance(record, dict):
+            record.setdefault("episodes", []).append(
+                {"states": ep.record[:length + 1].cpu().numpy(), "actions": ep.act_hist[:length].cpu().numpy(),
+                 "rewards": values, "length": length})
+    del keep
+    actor.train()
+    return np.asarray(returns)
+
+
+# --------------------------------------------------------------------------- #
 # train (bref:870-1027)
 # --------------------------------------------------------------------------- #
 def group_seeds(train_seed: int, seeds_per_gpu: int) -> List[int]:
@@ -513,7 +724,7 @@ def group_seeds(train_seed: int, seeds_per_gpu: int) -> List[int]:
 
 def train(config: TrainConfig, dataset=None, reward_model=None, move_stats=None, *,
           logger: Optional[Callable[[Dict[str, float], int], None]] = None, perm=None, seeds_per_gpu: int = 1,
-          device: Optional[str] = None, chunk: int = 2000):
+          device: Optional[str] = None, chunk: int = 2000, eval_on: str = "host"):
     """bref:870-1027 on the fused HIP step.
 
     ``dataset``: a ``BBDataset``, a mapping of arrays or an HDF5 path (None: ``config.dataset_path``);
@@ -529,6 +740,10 @@ def train(config: TrainConfig, dataset=None, reward_model=None, move_stats=None,
     a chunk are written on the device, and its losses come back to the host once, after the next chunk has
     been queued.  Returns the trainer.
 
+    ``eval_on``: "host" evaluates with ``bb_run_eval_IQL`` (the numpy simulator, any reward callable),
+    "device" with ``bb_run_eval_device`` (the step loop on the GPU; ``reward_model`` must then be a
+    ``RewardPTContext`` or a ``RewardPT``, which is checked before the first step).
+
     ``seeds_per_gpu`` = K > 1: seed k is ``rank_seed(train_seed, K) + k``, with its own nets (built right after
     ``torch.manual_seed(seed)``), its own block permutation (``perm``: a sequence of K permutations; None: K
     draws in member order from torch's global generator, before any seed is set), its own evaluations
@@ -536,6 +751,8 @@ def train(config: TrainConfig, dataset=None, reward_model=None, move_stats=None,
     ``seed`` entry in its logger records; all K share one buffer and step as one ``SeedGroup`` with the indices
     of one K-way launch.  Every seed is bit-identical to ``train()`` of that seed alone with its permutation.
     Returns the list of K trainers."""
+    if eval_on not in ("host", "device"):
+        raise ValueError(f"eval_on must be 'host' or 'device', got {eval_on!r}")
     K = int(seeds_per_gpu)
     seeds = group_seeds(config.train_seed, K)
     if K == 1:
@@ -545,6 +762,10 @@ def train(config: TrainConfig, dataset=None, reward_model=None, move_stats=None,
     if reward_model is None:
         _co._reward_model_missing("custom_offline_bb.train", config, "a callable with the reference's call shape "
                                   "(RewardPTContext wraps a RewardPT)", "load_PT")
+    if eval_on == "device" and not isinstance(reward_model, (RewardPT, RewardPTContext)):
+        raise TypeError("train(eval_on='device') needs a RewardPTContext or a RewardPT as reward_model: the device "
+                        "rollout takes its rewards from one window_values call; eval_on='host' (bb_run_eval_IQL) "
+                        "takes any callable")
     if move_stats is None:
         move_stats = load_stats(config.move_stats_path)
     if dataset is None:
@@ -584,8 +805,9 @@ def train(config: TrainConfig, dataset=None, reward_model=None, move_stats=None,
         idx, valid = samplers.device_indices(t, n, device)
         return group.train_steps(replay_buffer, n, config.batch_size, indices=idx, n_valid=valid, return_losses=True)
 
-    def evaluate(k, trainer, step):  # (bb_run_eval_IQL: the module's global at call time)
-        return bb_run_eval_IQL(actor=trainer.actor, num_episodes=config.eval_episodes, r_model=reward_model,
+    def evaluate(k, trainer, step):  # (bb_run_eval_IQL / _device: the module's globals at call time)
+        run_eval = bb_run_eval_device if eval_on == "device" else bb_run_eval_IQL
+        return run_eval(actor=trainer.actor, num_episodes=config.eval_episodes, r_model=reward_model,
                                move_stats=move_stats, state_mean=dataset.state_mean(),
                                state_std=dataset.state_std(), seed=config.eval_seed + step, device=device)
 
