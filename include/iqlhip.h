@@ -623,6 +623,27 @@ int iqlhip_bb_sim_step(const iqlhip_bb_sim *sim, void *stream);
 int iqlhip_bb_sim_rollout(const iqlhip_bb_sim *sim, const iqlhip_mlp_desc *actor, int32_t n_steps,
                           void *stream);
 
+/* n whole episodes in ONE launch (k_bb_episodes, csrc/bb_sim.hip), one work-group per episode: what
+ * iqlhip_bb_sim_reset and then max_horizon times { forward of actors[k] on actor_in; iqlhip_bb_sim_step }
+ * leave behind for sims[k] -- ctl, record, obs_hist, act_hist, actor_in, state bit for bit, nothing past
+ * the episode's last row -- without a launch between the steps.  The forward is the arithmetic of
+ * iqlhip_mlp_forward for one row: equal input rows give equal action bits on both paths.  1 <= n <=
+ * IQLHIP_MAX_GROUP; the episodes share nothing (the members of a seed group, each with its own buffers).
+ * A sim with actor_out_stride != 0 reads row t of its injected table at step t and runs no forward;
+ * its actors[k] may be NULL.
+ * scratch: device memory the caller owns, 16-byte aligned, at least iqlhip_bb_sim_episodes_scratch_bytes
+ * long: the per-episode argument blocks and one fragment-major weight image per actor, written once per
+ * call, on `stream`; it stays in use until the work queued on `stream` has finished.  No allocation, no
+ * synchronisation.
+ * Refused before any HIP call: a null sims / actors / scratch, n out of range, what the three calls above
+ * refuse for any sims[k], a NULL actors[k] without an injected table, an actor that does not map
+ * state_dim -> 2 or has a null weight pointer, too little scratch (IQLHIP_ERR_INVALID); an actor outside
+ * the fused forward's envelope -- a width above 256, an activation code other than 0 / 1, dropout_p > 0
+ * (IQLHIP_ERR_UNSUPPORTED: iqlhip_bb_sim_rollout takes those).                                        */
+int iqlhip_bb_sim_episodes_scratch_bytes(const iqlhip_mlp_desc *const *actors, int32_t n, size_t *bytes);
+int iqlhip_bb_sim_episodes(const iqlhip_bb_sim *sims, const iqlhip_mlp_desc *const *actors, int32_t n,
+                           void *scratch, size_t scratch_bytes, void *stream);
+
 /* ------------------------------------------------------------------------ */
 /* Posterior relabel of algorithms/custom_offline/iql_br.py:179-253: per       */
 /* transition, n_samps draws of np.random.choice over the S posterior          */

@@ -163,6 +163,10 @@ SYMBOLS = {
     "iqlhip_bb_sim_reset": (C.c_int, [C.POINTER(BbSim), P]),
     "iqlhip_bb_sim_step": (C.c_int, [C.POINTER(BbSim), P]),
     "iqlhip_bb_sim_rollout": (C.c_int, [C.POINTER(BbSim), C.POINTER(MlpDesc), C.c_int32, P]),
+    "iqlhip_bb_sim_episodes_scratch_bytes": (C.c_int, [C.POINTER(C.POINTER(MlpDesc)), C.c_int32,
+                                                       C.POINTER(C.c_size_t)]),
+    "iqlhip_bb_sim_episodes": (C.c_int, [C.POINTER(BbSim), C.POINTER(C.POINTER(MlpDesc)), C.c_int32, P, C.c_size_t,
+                                         P]),
     "iqlhip_posterior_choice_workspace_bytes": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.POINTER(C.c_size_t)]),
     "iqlhip_posterior_choice": (C.c_int, [P, P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, P, P, P, C.c_size_t, P]),
     "iqlhip_step_cost": (C.c_int, [C.POINTER(TrainerConfig), C.POINTER(C.c_double),

@@ -92,6 +92,9 @@ hipError_t launch_explore_epilogue(float *act, int64_t rows, int A, const float 
 hipError_t launch_np_randint(uint32_t *state, const int64_t *hi, int K, int64_t total, int64_t *const *out,
                              hipStream_t st);
 hipError_t launch_bb_step(const iqlhip_bb_sim &sim, int reset, hipStream_t st);
+size_t bb_episodes_scratch_bytes(const iqlhip_mlp_desc *const *actors, int n);
+hipError_t launch_bb_episodes(const iqlhip_bb_sim *sims, const iqlhip_mlp_desc *const *actors, int n, void *scratch,
+                              hipStream_t st);
 size_t choice_workspace_bytes(int64_t N, int n);
 int64_t choice_fit_rows(int64_t N, int n, size_t bytes);
 hipError_t launch_posterior_choice(uint32_t *state, const float *preds, int S, int64_t N, int n, int mode,
@@ -1750,6 +1753,65 @@ extern "C" int iqlhip_bb_sim_rollout(const iqlhip_bb_sim *sim, const iqlhip_mlp_
       return rc;
     HIP_TRY(launch_bb_step(*sim, 0, (hipStream_t)stream));
   }
+  return 0;
+}
+
+// The envelope of k_bb_episodes' fused forward: that of k_mlp_f32 (widths <= 256, relu / tanh hidden layers,
+// no / tanh output, no dropout), two outputs
+static int bb_actor_check(const iqlhip_mlp_desc *a, int k) {
+  if (a->n_layers < 1 || a->n_layers > IQLHIP_MLP_MAX_LAYERS)
+    return fail(IQLHIP_ERR_INVALID, "actor %d: n_layers must be in [1, %d]", k, IQLHIP_MLP_MAX_LAYERS);
+  for (int i = 0; i <= a->n_layers; ++i) {
+    if (a->dims[i] < 1) return fail(IQLHIP_ERR_INVALID, "actor %d: layer width %d", k, a->dims[i]);
+    if (a->dims[i] > 256)
+      return fail(IQLHIP_ERR_UNSUPPORTED, "actor %d: layer width %d > 256, the fused forward's limit (the launch "
+                                          "pair of iqlhip_bb_sim_rollout takes wider actors)", k, a->dims[i]);
+  }
+  for (int i = 0; i < a->n_layers; ++i)
+    if (!a->weights[i] || !a->biases[i]) return fail(IQLHIP_ERR_INVALID, "actor %d: null weight pointer", k);
+  if (a->hidden_act < 0 || a->hidden_act > 1 || a->out_act < 0 || a->out_act > 1)
+    return fail(IQLHIP_ERR_UNSUPPORTED, "actor %d: activations %d / %d, the fused forward has relu or tanh hidden "
+                                        "layers and no or a tanh output", k, a->hidden_act, a->out_act);
+  if (a->dropout_p > 0.f)
+    return fail(IQLHIP_ERR_UNSUPPORTED, "actor %d: dropout_p > 0, the fused forward is an eval-mode forward", k);
+  return 0;
+}
+
+extern "C" int iqlhip_bb_sim_episodes_scratch_bytes(const iqlhip_mlp_desc *const *actors, int32_t n, size_t *bytes) {
+  if (!actors || !bytes) return fail(IQLHIP_ERR_INVALID, "null argument");
+  if (n < 1 || n > IQLHIP_MAX_GROUP) return fail(IQLHIP_ERR_INVALID, "n = %d: 1..%d episodes", n, IQLHIP_MAX_GROUP);
+  for (int k = 0; k < n; ++k)
+    if (actors[k])
+      if (int rc = bb_actor_check(actors[k], k)) return rc;
+  *bytes = bb_episodes_scratch_bytes(actors, n);
+  return 0;
+}
+
+extern "C" int iqlhip_bb_sim_episodes(const iqlhip_bb_sim *sims, const iqlhip_mlp_desc *const *actors, int32_t n,
+                                      void *scratch, size_t scratch_bytes, void *stream) {
+  if (!sims) return fail(IQLHIP_ERR_INVALID, "null simulators");
+  if (!actors) return fail(IQLHIP_ERR_INVALID, "null actors");
+  if (!scratch) return fail(IQLHIP_ERR_INVALID, "null scratch");
+  if (n < 1 || n > IQLHIP_MAX_GROUP) return fail(IQLHIP_ERR_INVALID, "n = %d: 1..%d episodes", n, IQLHIP_MAX_GROUP);
+  if ((uintptr_t)scratch & 15) return fail(IQLHIP_ERR_INVALID, "scratch must start on a 16-byte boundary");
+  for (int k = 0; k < n; ++k) {
+    if (int rc = bb_sim_check(sims + k)) return rc;
+    const iqlhip_mlp_desc *a = actors[k];
+    if (!a) {
+      if (sims[k].actor_out_stride == 0)
+        return fail(IQLHIP_ERR_INVALID, "episode %d: null actor and no injected table", k);
+      continue;
+    }
+    if (int rc = bb_actor_check(a, k)) return rc;
+    if (a->dims[0] != sims[k].state_dim || a->dims[a->n_layers] != sims[k].action_dim)
+      return fail(IQLHIP_ERR_INVALID, "actor %d maps %d -> %d, the simulator needs %d -> %d", k, a->dims[0],
+                  a->dims[a->n_layers], sims[k].state_dim, sims[k].action_dim);
+  }
+  const size_t need = bb_episodes_scratch_bytes(actors, n);
+  if (scratch_bytes < need)
+    return fail(IQLHIP_ERR_INVALID, "scratch of %zu bytes, %d episodes need %zu (iqlhip_bb_sim_episodes_scratch_bytes)",
+                scratch_bytes, n, need);
+  HIP_TRY(launch_bb_episodes(sims, actors, n, scratch, (hipStream_t)stream));
   return 0;
 }
 

@@ -98,16 +98,26 @@ __device__ __forceinline__ float clamp_torch(float x, float lo, float hi) {
   return x > hi ? hi : x;
 }
 
+// The LDS of one simulated step
+struct BbShared {
+  double dist[BB_MAX_OBS];
+  int sel[BB_MAX_NEAR];
+  double pos[2];
+  int reached;
+};
+
+// One simulator step of a 256-thread work-group, shared by k_bb_step (one step per launch) and k_bb_episodes (a
+// whole episode per work-group): reset != 0 writes observation row 0 (t = -1), otherwise step t.  raw(i) is
+// component i of the actor's unclamped output (read by thread 0 only); lds_in, when not null, receives the
+// next actor input as well.  sh.reached holds the goal test once the caller has passed a barrier.
 // state: [0] agent x, [1] agent y, [2] goal x, [3] goal y, [4..8) level, ai, attempt, day,
 //        [8 ..) ox[n_obs], oy[n_obs], oang[n_obs]
-__global__ __launch_bounds__(BB_THREADS) void k_bb_step(const iqlhip_bb_sim P, int reset) {
-  __shared__ double s_dist[BB_MAX_OBS];
-  __shared__ int s_sel[BB_MAX_NEAR];
-  __shared__ double s_pos[2];
-  __shared__ int s_reached;
+template <class Raw>
+__device__ __forceinline__ void bb_step_body(const iqlhip_bb_sim &P, int reset, int t, Raw raw, BbShared &sh,
+                                             float *lds_in) {
+  double *s_dist = sh.dist;
+  int *s_sel = sh.sel;
   const int tid = threadIdx.x, n_obs = P.n_obs, n_near = P.n_near, S = P.state_dim, A = P.action_dim;
-  const int t = reset ? -1 : ldg(P.ctl);
-  if (!reset && (ldg(P.ctl + 1) != 0 || t < 0 || t >= P.max_horizon)) return;  // (uniform: nothing is written)
   double *ox = P.state + 8, *oy = ox + n_obs, *oang = oy + n_obs;
   if (tid < BB_MAX_NEAR) s_sel[tid] = 0;
   if (tid == 0) {
@@ -115,9 +125,8 @@ __global__ __launch_bounds__(BB_THREADS) void k_bb_step(const iqlhip_bb_sim P, i
     double px = qx, py = qy;
     int reached = 0;
     if (!reset) {
-      const float *raw = P.actor_out + (size_t)t * P.actor_out_stride;
-      const float a0 = clamp_torch(ldg(raw), ldg(P.min_actions), ldg(P.max_actions));
-      const float a1 = clamp_torch(ldg(raw + 1), ldg(P.min_actions + 1), ldg(P.max_actions + 1));
+      const float a0 = clamp_torch(raw(0), ldg(P.min_actions), ldg(P.max_actions));
+      const float a1 = clamp_torch(raw(1), ldg(P.min_actions + 1), ldg(P.max_actions + 1));
       stg(P.act_hist + (size_t)t * A, a0);
       stg(P.act_hist + (size_t)t * A + 1, a1);
       // float(px + action[0] * _cos_deg(action[1])): float32 throughout, px rounded to float32 first
@@ -135,8 +144,8 @@ __global__ __launch_bounds__(BB_THREADS) void k_bb_step(const iqlhip_bb_sim P, i
       const double reach = 0.3 + 1.0, lim = reach * reach;  // (AGENT_RADIUS + GOAL_RADIUS) ** 2
       reached = (d2 < lim) || isclose_f64(d2, lim);
     }
-    s_pos[0] = px, s_pos[1] = py;
-    s_reached = reached;
+    sh.pos[0] = px, sh.pos[1] = py;
+    sh.reached = reached;
   }
   if (!reset) {  // the obstacles drift along their headings; one that leaves re-enters at its mirrored OLD place
     const double *drift = P.drift + (size_t)t * n_obs;
@@ -149,7 +158,7 @@ __global__ __launch_bounds__(BB_THREADS) void k_bb_step(const iqlhip_bb_sim P, i
     }
   }
   __syncthreads();
-  const double px = s_pos[0], py = s_pos[1];
+  const double px = sh.pos[0], py = sh.pos[1];
   for (int i = tid; i < n_obs; i += BB_THREADS) {  // (every thread reads back the entries it wrote itself)
     const double ex = ldg(ox + i) - px, ey = ldg(oy + i) - py;
     s_dist[i] = sqrt((ex * ex) + (ey * ey));
@@ -179,18 +188,204 @@ __global__ __launch_bounds__(BB_THREADS) void k_bb_step(const iqlhip_bb_sim P, i
     const size_t row = (size_t)(t + 1) * S + c;
     stg(P.record + row, v);
     stg(P.obs_hist + row, (float)v);
-    stg(P.actor_in + c, (float)((v - ldg(P.state_mean + c)) / ldg(P.state_std + c)));
+    const float in = (float)((v - ldg(P.state_mean + c)) / ldg(P.state_std + c));
+    stg(P.actor_in + c, in);
+    if (lds_in) lds_in[c] = in;
   }
   if (tid == 0) {
     stg(P.state, px);
     stg(P.state + 1, py);
     stg(P.ctl, t + 1);  // the episode's length once done is set
-    stg(P.ctl + 1, s_reached);
+    stg(P.ctl + 1, sh.reached);
   }
+}
+
+__global__ __launch_bounds__(BB_THREADS) void k_bb_step(const iqlhip_bb_sim P, int reset) {
+  __shared__ BbShared sh;
+  const int t = reset ? -1 : ldg(P.ctl);
+  if (!reset && (ldg(P.ctl + 1) != 0 || t < 0 || t >= P.max_horizon)) return;  // (uniform: nothing is written)
+  const float *table = P.actor_out + (size_t)(reset ? 0 : t) * P.actor_out_stride;
+  bb_step_body(P, reset, t, [table](int i) { return ldg(table + i); }, sh, nullptr);
 }
 
 hipError_t launch_bb_step(const iqlhip_bb_sim &sim, int reset, hipStream_t st) {
   hipLaunchKernelGGL(k_bb_step, dim3(1), dim3(BB_THREADS), 0, st, sim, reset);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// A whole episode per work-group: k_bb_step(reset = 1), then up to max_horizon times { the actor's forward on
+// the one-row input; the body of k_bb_step(reset = 0) }, without a launch in between.  n episodes (of n actors:
+// the members of a seed group) are n work-groups of one launch; they share nothing and wait for nothing.
+//
+// The forward restates k_mlp_f32 (mlp_f32.hip) for one row, so that equal input rows give equal action bits on
+// both paths.  What fixes the bits of an output element is the order of the operations on ITS accumulator:
+//   hidden layer   acc = 0; for ks = 0 .. nk-1, c = 0 .. 3: one mfma_f32_16x16x4f32 over the k-group
+//                  {16 ks + 4 q + c}; then + bias, then the activation;
+//   last layer     (2 outputs: fewer than 4 n-tiles, the k-split path of k_mlp_f32) four partial accumulators
+//                  over ks = w, w + 4, ... for w = 0 .. 3, summed as ((p0 + p1) + p2) + p3 -- exact zeros
+//                  included when nk < 4 --, then + bias, then the output activation.
+// Rows of an MFMA tile do not mix, so the one live row of a 16-row tile (the others stay zero) gets what row i
+// of a 64-row work-group of k_mlp_f32 gets; n-tiles do not mix either, so wave w taking tiles w, w + 4, ... is
+// a choice of speed only.  Zero K padding and zeroed padded output columns as there.  The B fragments come from
+// the fragment-major image k_mlp_repack wrote once, ahead of the launch.
+//
+// LDS: BbShared (8.3 KB) + the activation image [16][260] fp32 (16.6 KB) + 72 floats.  The obstacles stay in
+// global memory, advanced in place as k_bb_step does, so that both kernels run ONE step body.
+constexpr int BB_LDA = 260;  // >= round_up(256, 16) + 4, the row stride k_mlp_f32 uses at width 256
+
+struct BbEpisodeArgs {
+  iqlhip_bb_sim sim;
+  int32_t n_layers;  // 0: every step reads its row of the injected table, no forward
+  int32_t dims[IQLHIP_MLP_MAX_LAYERS + 1];
+  int32_t hidden_act, out_act;  // 0 relu / none, 1 tanh
+  const float *Wf[IQLHIP_MLP_MAX_LAYERS];  // fragment-major images
+  const float *b[IQLHIP_MLP_MAX_LAYERS];
+};
+
+__global__ __launch_bounds__(BB_THREADS) void k_bb_episodes(const BbEpisodeArgs *__restrict__ args) {
+  using PF = Prec<false>;
+  __shared__ BbShared sh;
+  __shared__ __attribute__((aligned(16))) float s_act[16 * BB_LDA];
+  __shared__ float s_red[4][16];
+  __shared__ float s_out[2];
+  const BbEpisodeArgs *E = args + blockIdx.x;
+  const iqlhip_bb_sim P = E->sim;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r = lane & 15, q = lane >> 4;
+  const int n_layers = E->n_layers, hidden_act = E->hidden_act, out_act = E->out_act;
+  const int S = P.state_dim, K0p = round_up(S, 16);
+  const float *so = s_out;
+  auto raw = [so](int i) { return so[i]; };
+
+  for (int e = tid; e < 16 * BB_LDA; e += BB_THREADS) s_act[e] = 0.f;  // rows 1 .. 15 stay zero for good
+  if (tid < 2) s_out[tid] = 0.f;
+  __syncthreads();
+  bb_step_body(P, 1, -1, raw, sh, s_act);
+  __syncthreads();
+
+  for (int t = 0; t < P.max_horizon; ++t) {
+    if (n_layers == 0) {
+      if (tid < 2) s_out[tid] = ldg(P.actor_out + (size_t)t * P.actor_out_stride + tid);
+      __syncthreads();
+    }
+    for (int l = 0; l < n_layers; ++l) {
+      const int K = E->dims[l], N = E->dims[l + 1];
+      const int nk = round_up(K, 16) / 16, ntile = round_up(N, 16) / 16;
+      const float *Wf = E->Wf[l], *bias = E->b[l];
+      if (l == n_layers - 1) {  // N = 2: the k-split output layer
+        f32x4 pacc = {0.f, 0.f, 0.f, 0.f};
+        for (int ks = wave; ks < nk; ks += 4) {
+          const uint4 a = *reinterpret_cast<const uint4 *>(s_act + r * BB_LDA + 16 * ks + 4 * q);
+          const uint4 b = ldg16(Wf + frag_off<PF>(0, ks, nk, lane));
+          PF::mma(a, b, pacc);
+        }
+        if (q == 0) s_red[wave][r] = pacc[0];  // row 0 of the tile
+        __syncthreads();
+        if (tid < N) {
+          float sum = s_red[0][tid];
+#pragma unroll
+          for (int w = 1; w < 4; ++w) sum += s_red[w][tid];
+          const float v = sum + ldg(bias + tid);
+          const float o = out_act == 1 ? tanhf(v) : v;
+          s_out[tid] = o;
+          stg(P.actor_out + tid, o);  // (what the launch pair leaves there)
+        }
+        __syncthreads();
+        continue;
+      }
+      int tile[4];
+      bool live[4];
+      f32x4 acc[4];
+      float bv[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        live[j] = wave + 4 * j < ntile;
+        tile[j] = live[j] ? wave + 4 * j : 0;
+        acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        bv[j] = ldg(bias + (16 * tile[j] + r < N ? 16 * tile[j] + r : N - 1));
+      }
+      if (live[0]) {  // (wave-uniform)
+        uint4 bq[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) bq[j] = ldg16(Wf + frag_off<PF>(tile[j], 0, nk, lane));
+        for (int ks = 0; ks < nk; ++ks) {
+          uint4 bn[4];  // the next k-step's fragments, in flight during this step's MFMAs
+          const int kn = ks + 1 < nk ? ks + 1 : ks;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) bn[j] = ldg16(Wf + frag_off<PF>(tile[j], kn, nk, lane));
+          const f32x4 af =
+              __builtin_bit_cast(f32x4, *reinterpret_cast<const uint4 *>(s_act + r * BB_LDA + 16 * ks + 4 * q));
+          f32x4 bf[4];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) bf[j] = __builtin_bit_cast(f32x4, bq[j]);
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              if (live[j]) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[c], bf[j][c], acc[j], 0, 0, 0);
+            }
+          }
+#pragma unroll
+          for (int j = 0; j < 4; ++j) bq[j] = bn[j];
+        }
+      }
+      __syncthreads();  // every wave has read its last A fragment: row 0 may be overwritten
+      if (q == 0) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          if (!live[j]) continue;
+          const int ncol = 16 * tile[j] + r;
+          const float v = acc[j][0] + bv[j];
+          s_act[ncol] = ncol < N ? (hidden_act == 0 ? fmaxf(v, 0.f) : tanhf(v)) : 0.f;  // zero K padding
+        }
+      }
+      __syncthreads();
+    }
+    bb_step_body(P, 0, t, raw, sh, s_act);
+    if (tid >= S && tid < K0p) s_act[tid] = 0.f;  // the input's K padding, overwritten by the hidden layers
+    __syncthreads();
+    if (sh.reached) break;  // (uniform; the next write of it lies behind a barrier of the next step)
+  }
+}
+
+size_t mlp_image_offset(const iqlhip_mlp_desc &d, int l);
+hipError_t launch_mlp_repack(const iqlhip_mlp_desc &d, float *wf, hipStream_t st);
+
+static size_t up256(size_t x) { return (x + 255) / 256 * 256; }
+
+// scratch: the n argument blocks, then one weight image per actor that is not NULL, each on a 256-byte boundary
+size_t bb_episodes_scratch_bytes(const iqlhip_mlp_desc *const *actors, int n) {
+  size_t total = up256((size_t)n * sizeof(BbEpisodeArgs));
+  for (int k = 0; k < n; ++k)
+    if (actors[k]) total += up256(mlp_image_offset(*actors[k], actors[k]->n_layers) * sizeof(float));
+  return total;
+}
+
+hipError_t launch_bb_episodes(const iqlhip_bb_sim *sims, const iqlhip_mlp_desc *const *actors, int n, void *scratch,
+                              hipStream_t st) {
+  BbEpisodeArgs host[IQLHIP_MAX_GROUP];
+  char *base = static_cast<char *>(scratch);
+  size_t off = up256((size_t)n * sizeof(BbEpisodeArgs));
+  for (int k = 0; k < n; ++k) {
+    BbEpisodeArgs &a = host[k];
+    a = BbEpisodeArgs{};
+    a.sim = sims[k];
+    const iqlhip_mlp_desc *d = actors[k];
+    if (!d) continue;
+    float *wf = reinterpret_cast<float *>(base + off);
+    off += up256(mlp_image_offset(*d, d->n_layers) * sizeof(float));
+    if (sims[k].actor_out_stride != 0) continue;  // the injected table stands in for this actor
+    if (hipError_t e = launch_mlp_repack(*d, wf, st); e != hipSuccess) return e;
+    a.n_layers = d->n_layers, a.hidden_act = d->hidden_act, a.out_act = d->out_act;
+    for (int i = 0; i <= d->n_layers; ++i) a.dims[i] = d->dims[i];
+    for (int i = 0; i < d->n_layers; ++i) a.Wf[i] = wf + mlp_image_offset(*d, i), a.b[i] = d->biases[i];
+  }
+  // (a pageable source: the copy has left `host` when the call returns)
+  hipError_t e = hipMemcpyAsync(scratch, host, (size_t)n * sizeof(BbEpisodeArgs), hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_bb_episodes, dim3(n), dim3(BB_THREADS), 0, st, static_cast<const BbEpisodeArgs *>(scratch));
   return hipGetLastError();
 }
 

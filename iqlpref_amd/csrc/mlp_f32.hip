@@ -344,6 +344,24 @@ __global__ __launch_bounds__(64) void k_mlp_wide(const MlpArgs M, const float *_
   }
 }
 
+// The fragment-major image on its own, into memory the caller owns (csrc/bb_sim.hip: k_bb_episodes reads one
+// image for a whole episode).  Layer l starts mlp_image_offset(d, l) floats into wf; l = n_layers: the total.
+size_t mlp_image_offset(const iqlhip_mlp_desc &d, int l) {
+  size_t total = 0;
+  for (int i = 0; i < l; ++i) total += (size_t)round_up(d.dims[i], 16) * round_up(d.dims[i + 1], 16);
+  return total;
+}
+
+hipError_t launch_mlp_repack(const iqlhip_mlp_desc &d, float *wf, hipStream_t st) {
+  RepackArgs R;
+  R.n_layers = d.n_layers;
+  for (int i = 0; i <= d.n_layers; ++i) R.dims[i] = d.dims[i];
+  for (int i = 0; i < d.n_layers; ++i) R.W[i] = d.weights[i], R.Wf[i] = wf + mlp_image_offset(d, i);
+  R.w_in_out = d.w_in_out;
+  hipLaunchKernelGGL(k_mlp_repack, dim3(64, d.n_layers), dim3(256), 0, st, R);
+  return hipGetLastError();
+}
+
 hipError_t launch_mlp_f32(const iqlhip_mlp_desc &d, const float *x, int64_t n, int x_stride, float *out,
                           int out_stride, hipStream_t st) {
   MlpArgs M;

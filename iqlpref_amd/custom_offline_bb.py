@@ -27,6 +27,9 @@ actions give equal states and returns.
 ``bb_run_eval_device`` (``train(eval_on="device")``) is the same evaluation with the step loop on the GPU
 (csrc/bb_sim.hip): the host draws the set-up and the drift table, the actor's forward and one simulator step
 alternate on one stream, and one ``window_values`` call per episode gives the rewards.
+``bb_run_eval_fused`` (``train(eval_on="fused")``) runs the whole step loop of an episode, the actor's forward
+included, in ONE launch (``k_bb_episodes``), and ``bb_run_eval_fused_group`` the episodes of K actors as K
+work-groups of that launch; both give the bits of ``bb_run_eval_device``.
 
 ``train(seeds_per_gpu=K)`` steps K seeds side by side on one GPU as one ``SeedGroup``: each seed walks its
 own block permutation (``BlockEpochSamplerGroup`` writes the K index arrays and the one shared count array
@@ -711,6 +714,176 @@ def bb_run_eval_device(actor, num_episodes, r_model, move_stats, state_mean=0, s
 
 
 # --------------------------------------------------------------------------- #
+# the same evaluation with one launch per episode, and K evaluations side by side (k_bb_episodes)
+# --------------------------------------------------------------------------- #
+class FusedEpisodes:
+    """K ``DeviceEpisode`` buffer sets run as the K work-groups of one ``iqlhip_bb_sim_episodes`` call.  Their
+    control words are the rows of ONE [K, 2] tensor, so that ``poll`` is one device-to-host copy; the scratch of
+    the call (argument blocks and weight images) is allocated once and grows only when an actor does."""
+
+    def __init__(self, episodes: Sequence[DeviceEpisode]):
+        self.episodes = list(episodes)
+        K = len(self.episodes)
+        if not 1 <= K <= _lib.MAX_GROUP:
+            raise ValueError(f"1..{_lib.MAX_GROUP} episodes run side by side, got {K}")
+        self.lib, self.dev = self.episodes[0].lib, self.episodes[0].dev
+        if any(ep.dev != self.dev for ep in self.episodes):
+            raise ValueError("the episodes of one launch live on one device")
+        self.ctl = torch.zeros((K, 2), dtype=torch.int32, device=self.dev)
+        for k, ep in enumerate(self.episodes):
+            ep.ctl = self.ctl[k]  # (load() builds the struct from it)
+        self.scratch = None
+
+    def run(self, actor_descs: Sequence[Optional["_lib.MlpDesc"]]):
+        """Queue every loaded episode from its reset to its end; ``actor_descs[k]`` may be None for an episode
+        with an injected table."""
+        K = len(self.episodes)
+        if len(actor_descs) != K:
+            raise ValueError(f"{K} episodes, {len(actor_descs)} actors")
+        sims = (_lib.BbSim * K)(*[ep.sim for ep in self.episodes])
+        actors = (C.POINTER(_lib.MlpDesc) * K)(*[C.pointer(d) if d is not None else C.POINTER(_lib.MlpDesc)()
+                                                 for d in actor_descs])
+        need = C.c_size_t(0)
+        check(self.lib.iqlhip_bb_sim_episodes_scratch_bytes(actors, K, C.byref(need)))
+        if self.scratch is None or self.scratch.numel() < need.value:
+            self.scratch = torch.empty(need.value, dtype=torch.uint8, device=self.dev)
+        with torch.cuda.device(self.dev):
+            check(self.lib.iqlhip_bb_sim_episodes(sims, actors, K, ptr(self.scratch), self.scratch.numel(),
+                                                  stream_ptr()))
+
+    def poll(self) -> List[Tuple[int, bool]]:
+        """[(length, done)] of the K episodes: waits for everything queued, one copy."""
+        return [(int(t), bool(d)) for t, d in self.ctl.cpu().tolist()]
+
+
+def _fused_actor_descs(actors):
+    """The descriptors of ``actors`` after the library has checked them against the fused forward's envelope
+    (widths <= 256, relu / tanh, eval mode) -- a host-side check, nothing is launched."""
+    pairs = [_actor_desc(a) for a in actors]
+    K = len(pairs)
+    arr = (C.POINTER(_lib.MlpDesc) * K)(*[C.pointer(d) for d, _ in pairs])
+    need = C.c_size_t(0)
+    check(_lib.load().iqlhip_bb_sim_episodes_scratch_bytes(arr, K, C.byref(need)))
+    return pairs
+
+
+def _fused_eval(actors, seeds, num_episodes, r_model, move_stats, state_mean, state_std, max_horizon,
+                n_min_obstacles, days, context_length, device, records, timing):
+    if isinstance(r_model, RewardPT):
+        r_model = RewardPTContext(r_model, context_length)
+    if not isinstance(r_model, RewardPTContext):
+        raise TypeError("bb_run_eval_fused takes a RewardPTContext or a RewardPT: its rewards are one window_values "
+                        "call over device histories; bb_run_eval_IQL is the path for any other callable")
+    H, cl, K = int(max_horizon), int(context_length), len(actors)
+    if H < 1:
+        raise ValueError("max_horizon must be >= 1")
+    if min(H, cl) > r_model.context_length:
+        raise ValueError("states, actions and timesteps must share one length <= context_length")
+    if len(seeds) != K:
+        raise ValueError(f"{K} actors, {len(seeds)} seeds")
+    pairs = _fused_actor_descs(actors)
+    pt_dev = next(r_model.model.parameters()).device
+    for a in actors:
+        a.eval()
+    rngs = [np.random.default_rng(s) for s in seeds]
+    eps = [DeviceEpisode(n_min_obstacles, H, state_mean, state_std, a.min_actions, a.max_actions, device)
+           for a in actors]
+    fused = FusedEpisodes(eps)
+    steps = np.arange(H)
+    starts = np.maximum(0, steps + 1 - cl)
+    win_start = torch.from_numpy(starts.astype(np.int64)).to(pt_dev)
+    win_len = torch.from_numpy((steps + 1 - starts).astype(np.int32)).to(pt_dev)
+    win_t0 = torch.from_numpy(starts.astype(np.int32)).to(pt_dev)
+    returns = [[] for _ in range(K)]
+
+    def mark(phase, t0):
+        if timing is None:
+            return t0
+        torch.cuda.synchronize(fused.dev)
+        now = time.perf_counter()
+        timing[phase] = timing.get(phase, 0.0) + (now - t0 if t0 is not None else 0.0)
+        return now
+
+    for _ in range(num_episodes):
+        t0 = mark("other", None)
+        drawn = []
+        for rng, ep in zip(rngs, eps):
+            n_obs, ox, oy, oang, px, py, goal, tail = _episode_setup(rng, days)
+            saved = rng.bit_generator.state
+            drift = rng.normal(move_stats[2], move_stats[3], (H, n_obs))
+            ep.load(ox, oy, oang, px, py, goal, tail, drift)
+            drawn.append((saved, n_obs))
+        t0 = mark("setup", t0)
+        fused.run([d for d, _ in pairs])
+        lengths = [length for length, _ in fused.poll()]
+        for rng, (saved, n_obs), length in zip(rngs, drawn, lengths):
+            _rewind_drift(rng, saved, move_stats, length, n_obs)
+        t0 = mark("steps", t0)
+        for k, (ep, length) in enumerate(zip(eps, lengths)):
+            values = np.zeros(0)
+            if length:
+                v = r_model.model.window_values(ep.obs_hist.to(pt_dev), ep.act_hist.to(pt_dev), win_start[:length],
+                                                win_len[:length], r_model.context_length, win_t0=win_t0[:length])
+                values = v.cpu().numpy().astype(np.float64)
+            episode_return = np.zeros(1)
+            for x in values:  # (0.0 + r_0 + r_1 + ..., the order of the numpy loop)
+                episode_return = episode_return + x
+            returns[k].append(episode_return)
+            if isinstance(records[k], dict):
+                records[k].setdefault("episodes", []).append(
+                    {"states": ep.record[:length + 1].cpu().numpy(), "actions": ep.act_hist[:length].cpu().numpy(),
+                     "rewards": values, "length": length})
+        t0 = mark("reward", t0)
+    del pairs
+    for a in actors:
+        a.train()
+    return [np.asarray(r) for r in returns], rngs
+
+
+def bb_run_eval_fused(actor, num_episodes, r_model, move_stats, state_mean=0, state_std=1, max_horizon=500,
+                      n_min_obstacles=6, days=181, context_length=100, seed=4, device="cuda:0", record=None):
+    """``bb_run_eval_device`` with ONE launch per episode: the contract, the arguments (but ``chunk``), the
+    ``record`` entries and the ``record["timing"]`` phases of that function, and its bits -- returns, states,
+    actions, lengths and the generator's final state.
+
+    Per episode: one set-up draw, one drift table, one upload, one ``iqlhip_bb_sim_episodes`` call (the weights
+    are repacked once, then ``k_bb_episodes`` runs reset, forwards and steps to the end of the episode in one
+    work-group), one host wait, one ``window_values`` call.  The fused forward takes actors of widths <= 256 with
+    relu or tanh hidden layers; others are refused (``NotImplementedError``) before anything is launched, and
+    ``bb_run_eval_device`` takes them."""
+    rec = record if isinstance(record, dict) else None
+    timing = rec.get("timing") if rec is not None else None
+    returns, _ = _fused_eval([actor], [seed], num_episodes, r_model, move_stats, state_mean, state_std, max_horizon,
+                             n_min_obstacles, days, context_length, device, [rec], timing)
+    return returns[0]
+
+
+def bb_run_eval_fused_group(actors, num_episodes, r_model, move_stats, state_mean=0, state_std=1, max_horizon=500,
+                            n_min_obstacles=6, days=181, context_length=100, seeds=(4,), device="cuda:0",
+                            record=None):
+    """K evaluations side by side: ``actors[k]`` on ``default_rng(seeds[k])``.  Returns the list of the K return
+    arrays, each bit-equal to ``bb_run_eval_fused`` of that member alone.
+
+    The members run in lock step over the episode index: for episode e every member draws its set-up and its
+    drift table from its own generator, ONE library call runs the K episodes as K work-groups of one launch, ONE
+    copy reads the K (length, done) pairs, every generator is rewound by its own member's length, then the K
+    reward calls run.  A member whose episode ends early leaves its generator elsewhere than the others, so the
+    later set-ups differ between members -- as in K separate evaluations.
+
+    ``record``: a dict that receives ``record["members"]``, K dicts with the ``episodes`` list of
+    ``bb_run_eval_fused``, and whose ``record["timing"]``, when present, receives the phases of all members."""
+    actors, seeds = list(actors), list(seeds)
+    rec = record if isinstance(record, dict) else None
+    members = [{} for _ in actors] if rec is not None else [None] * len(actors)
+    if rec is not None:
+        rec["members"] = members
+    timing = rec.get("timing") if rec is not None else None
+    returns, _ = _fused_eval(actors, seeds, num_episodes, r_model, move_stats, state_mean, state_std, max_horizon,
+                             n_min_obstacles, days, context_length, device, members, timing)
+    return returns
+
+
+# --------------------------------------------------------------------------- #
 # train (bref:870-1027)
 # --------------------------------------------------------------------------- #
 def group_seeds(train_seed: int, seeds_per_gpu: int) -> List[int]:
@@ -742,7 +915,11 @@ def train(config: TrainConfig, dataset=None, reward_model=None, move_stats=None,
 
     ``eval_on``: "host" evaluates with ``bb_run_eval_IQL`` (the numpy simulator, any reward callable),
     "device" with ``bb_run_eval_device`` (the step loop on the GPU; ``reward_model`` must then be a
-    ``RewardPTContext`` or a ``RewardPT``, which is checked before the first step).
+    ``RewardPTContext`` or a ``RewardPT``, which is checked before the first step), "fused" with
+    ``bb_run_eval_fused`` (one launch per episode; the same bits as "device"; the reward model as for "device",
+    actors of widths <= 256, both checked before the first step).  With ``seeds_per_gpu`` = K > 1, "fused"
+    evaluates the K members side by side (``bb_run_eval_fused_group``): the first member's evaluation of a step
+    runs the K rollouts in one launch per episode index, the others are handed their arrays.
 
     ``seeds_per_gpu`` = K > 1: seed k is ``rank_seed(train_seed, K) + k``, with its own nets (built right after
     ``torch.manual_seed(seed)``), its own block permutation (``perm``: a sequence of K permutations; None: K
@@ -751,8 +928,8 @@ def train(config: TrainConfig, dataset=None, reward_model=None, move_stats=None,
     ``seed`` entry in its logger records; all K share one buffer and step as one ``SeedGroup`` with the indices
     of one K-way launch.  Every seed is bit-identical to ``train()`` of that seed alone with its permutation.
     Returns the list of K trainers."""
-    if eval_on not in ("host", "device"):
-        raise ValueError(f"eval_on must be 'host' or 'device', got {eval_on!r}")
+    if eval_on not in ("host", "device", "fused"):
+        raise ValueError(f"eval_on must be 'host', 'device' or 'fused', got {eval_on!r}")
     K = int(seeds_per_gpu)
     seeds = group_seeds(config.train_seed, K)
     if K == 1:
@@ -762,8 +939,8 @@ def train(config: TrainConfig, dataset=None, reward_model=None, move_stats=None,
     if reward_model is None:
         _co._reward_model_missing("custom_offline_bb.train", config, "a callable with the reference's call shape "
                                   "(RewardPTContext wraps a RewardPT)", "load_PT")
-    if eval_on == "device" and not isinstance(reward_model, (RewardPT, RewardPTContext)):
-        raise TypeError("train(eval_on='device') needs a RewardPTContext or a RewardPT as reward_model: the device "
+    if eval_on in ("device", "fused") and not isinstance(reward_model, (RewardPT, RewardPTContext)):
+        raise TypeError(f"train(eval_on='{eval_on}') needs a RewardPTContext or a RewardPT as reward_model: the device "
                         "rollout takes its rewards from one window_values call; eval_on='host' (bb_run_eval_IQL) "
                         "takes any callable")
     if move_stats is None:
@@ -788,6 +965,8 @@ def train(config: TrainConfig, dataset=None, reward_model=None, move_stats=None,
     set_seed(seeds[0])  # np, random, torch, PYTHONHASHSEED
     trainers = [_co._build_trainer(config, s, state_dim, action_dim, limits, device,
                                    (GaussianPolicy, DeterministicPolicy), ImplicitQLearning) for s in seeds]
+    if eval_on == "fused":
+        _fused_actor_descs([t.actor for t in trainers])  # (the envelope, before the first step)
     group = None
     if K > 1:
         from .multi import SeedGroup
@@ -805,8 +984,20 @@ def train(config: TrainConfig, dataset=None, reward_model=None, move_stats=None,
         idx, valid = samplers.device_indices(t, n, device)
         return group.train_steps(replay_buffer, n, config.batch_size, indices=idx, n_valid=valid, return_losses=True)
 
-    def evaluate(k, trainer, step):  # (bb_run_eval_IQL / _device: the module's globals at call time)
-        run_eval = bb_run_eval_device if eval_on == "device" else bb_run_eval_IQL
+    group_eval = {"step": None, "returns": None}
+
+    def evaluate(k, trainer, step):  # (bb_run_eval_IQL / _device / _fused: the module's globals at call time)
+        if eval_on == "fused" and K > 1:
+            # the weights of no member change between the K calls of an evaluation step (the group has been
+            # synchronized and queues nothing until all have been evaluated)
+            if group_eval["step"] != step:
+                group_eval["returns"] = bb_run_eval_fused_group(
+                    actors=[t.actor for t in trainers], num_episodes=config.eval_episodes, r_model=reward_model,
+                    move_stats=move_stats, state_mean=dataset.state_mean(), state_std=dataset.state_std(),
+                    seeds=[config.eval_seed + step] * K, device=device)
+                group_eval["step"] = step
+            return group_eval["returns"][k]
+        run_eval = {"device": bb_run_eval_device, "fused": bb_run_eval_fused}.get(eval_on, bb_run_eval_IQL)
         return run_eval(actor=trainer.actor, num_episodes=config.eval_episodes, r_model=reward_model,
                                move_stats=move_stats, state_mean=dataset.state_mean(),
                                state_std=dataset.state_std(), seed=config.eval_seed + step, device=device)
