@@ -24,12 +24,12 @@ Differences from ``custom_offline`` (``iql.py``) and how they map onto the same 
 to a goal among drifting obstacles, rewarded by the preference model over a rolling context.  It makes
 the same ``default_rng(seed)`` calls in the same order with the same float arithmetic, so that equal
 actions give equal states and returns.
-``bb_run_eval_device`` (``train(eval_on="device")``) is the same evaluation with the step loop on the GPU
-(csrc/bb_sim.hip): the host draws the set-up and the drift table, the actor's forward and one simulator step
-alternate on one stream, and one ``window_values`` call per episode gives the rewards.
-``bb_run_eval_fused`` (``train(eval_on="fused")``) runs the whole step loop of an episode, the actor's forward
-included, in ONE launch (``k_bb_episodes``), and ``bb_run_eval_fused_group`` the episodes of K actors as K
-work-groups of that launch; both give the bits of ``bb_run_eval_device``.
+``_device_eval`` is the same evaluation with the step loop on the GPU (csrc/bb_sim.hip): the host draws the
+set-up and the drift table, a rollout takes the episode to its end, and one ``window_values`` call per episode
+gives the rewards.  Its rollouts: ``bb_run_eval_device`` (``train(eval_on="device")``) alternates the actor's
+forward and one simulator step on one stream; ``bb_run_eval_fused`` (``train(eval_on="fused")``) runs the whole
+step loop, the forward included, in ONE launch (``k_bb_episodes``), and ``bb_run_eval_fused_group`` the episodes
+of K actors as K work-groups of that launch, with the bits of ``bb_run_eval_device``.
 
 ``train(seeds_per_gpu=K)`` steps K seeds side by side on one GPU as one ``SeedGroup``: each seed walks its
 own block permutation (``BlockEpochSamplerGroup`` writes the K index arrays and the one shared count array
@@ -514,7 +514,7 @@ class RewardPTContext:
 
 
 # --------------------------------------------------------------------------- #
-# the same evaluation with the step loop on the device (csrc/bb_sim.hip)
+# the device state of the same evaluation and the launches that advance it (csrc/bb_sim.hip)
 # --------------------------------------------------------------------------- #
 class DeviceEpisode:
     """The device state of one simulated episode and the launches that advance it: ``load`` uploads a
@@ -626,95 +626,8 @@ def _rewind_drift(rng, saved_state, move_stats, length: int, n_obs: int):
         rng.normal(move_stats[2], move_stats[3], (length, n_obs))
 
 
-def bb_run_eval_device(actor, num_episodes, r_model, move_stats, state_mean=0, state_std=1, max_horizon=500,
-                       n_min_obstacles=6, days=181, context_length=100, seed=4, device="cuda:0", chunk=64,
-                       record=None):
-    """``bb_run_eval_IQL`` with the step loop on the device: the same episodes, the same generator calls,
-    the same float arithmetic, the same float64 array of returns.
-
-    Per episode the host draws the set-up and the whole [max_horizon, n_obs] drift table from
-    ``default_rng(seed)`` and uploads them; per step it queues the actor's forward (``iqlhip_mlp_forward``
-    on the live weights, the kernel ``actor.act`` reaches) and one ``k_bb_step``, ``chunk`` steps per
-    library call, and reads the done flag once per chunk -- the only waits of the rollout.  Steps queued
-    behind the goal write nothing.  The generator is then put where the numpy loop leaves it (the saved
-    state plus ``length`` rows of drift).  All rewards of an episode come from ONE
-    ``RewardPT.window_values`` call over the device histories: window t covers steps
-    ``max(0, t + 1 - context_length) .. t`` with their true timesteps, what the numpy loop hands to
-    ``RewardPTContext`` step by step; the return is their float64 sum in step order.
-
-    ``r_model``: a ``RewardPTContext`` or a ``RewardPT`` (wrapped with ``context_length``).  ``record``: a
-    dict that receives ``record["episodes"]``, per episode ``states`` (float64 [length + 1, S], every
-    observation), ``actions`` (float32 [length, 2]), ``rewards`` (float64 [length]) and ``length``; a
-    ``record["timing"]`` dict, when present, receives the seconds spent in set-up and upload (``setup``),
-    the step loop (``steps``) and the reward call (``reward``), each closed by a device synchronisation.  The actor is handed back in train mode."""
-    if isinstance(r_model, RewardPT):
-        r_model = RewardPTContext(r_model, context_length)
-    if not isinstance(r_model, RewardPTContext):
-        raise TypeError("bb_run_eval_device takes a RewardPTContext or a RewardPT: its rewards are one window_values "
-                        "call over device histories; bb_run_eval_IQL is the path for any other callable")
-    H, cl, chunk = int(max_horizon), int(context_length), int(chunk)
-    if chunk < 1 or H < 1:
-        raise ValueError("chunk and max_horizon must be >= 1")
-    if min(H, cl) > r_model.context_length:
-        raise ValueError("states, actions and timesteps must share one length <= context_length")
-    desc, keep = _actor_desc(actor)
-    pt_dev = next(r_model.model.parameters()).device
-    actor.eval()
-    returns = []
-    rng = np.random.default_rng(seed)
-    ep = DeviceEpisode(n_min_obstacles, H, state_mean, state_std, actor.min_actions, actor.max_actions, device)
-    steps = np.arange(H)
-    starts = np.maximum(0, steps + 1 - cl)
-    win_start = torch.from_numpy(starts.astype(np.int64)).to(pt_dev)
-    win_len = torch.from_numpy((steps + 1 - starts).astype(np.int32)).to(pt_dev)
-    win_t0 = torch.from_numpy(starts.astype(np.int32)).to(pt_dev)
-    timing = record.get("timing") if isinstance(record, dict) else None
-
-    def mark(phase, t0):
-        if timing is None:
-            return t0
-        torch.cuda.synchronize(ep.dev)
-        now = time.perf_counter()
-        timing[phase] = timing.get(phase, 0.0) + (now - t0 if t0 is not None else 0.0)
-        return now
-
-    for _ in range(num_episodes):
-        t0 = mark("other", None)
-        n_obs, ox, oy, oang, px, py, goal, tail = _episode_setup(rng, days)
-        saved = rng.bit_generator.state
-        drift = rng.normal(move_stats[2], move_stats[3], (H, n_obs))
-        ep.load(ox, oy, oang, px, py, goal, tail, drift)
-        ep.reset()
-        t0 = mark("setup", t0)
-        queued, length, done = 0, 0, False
-        while queued < H and not done:
-            n = min(chunk, H - queued)
-            ep.rollout(desc, n)
-            queued += n
-            length, done = ep.poll()
-        _rewind_drift(rng, saved, move_stats, length, n_obs)
-        t0 = mark("steps", t0)
-        values = np.zeros(0)
-        if length:
-            v = r_model.model.window_values(ep.obs_hist.to(pt_dev), ep.act_hist.to(pt_dev), win_start[:length],
-                                            win_len[:length], r_model.context_length, win_t0=win_t0[:length])
-            values = v.cpu().numpy().astype(np.float64)
-        episode_return = np.zeros(1)
-        for x in values:  # (0.0 + r_0 + r_1 + ..., the order of the numpy loop)
-            episode_return = episode_return + x
-        returns.append(episode_return)
-        t0 = mark("reward", t0)
-        if isinstance(record, dict):
-            record.setdefault("episodes", []).append(
-                {"states": ep.record[:length + 1].cpu().numpy(), "actions": ep.act_hist[:length].cpu().numpy(),
-                 "rewards": values, "length": length})
-    del keep
-    actor.train()
-    return np.asarray(returns)
-
-
 # --------------------------------------------------------------------------- #
-# the same evaluation with one launch per episode, and K evaluations side by side (k_bb_episodes)
+# K episodes as the work-groups of one launch (k_bb_episodes)
 # --------------------------------------------------------------------------- #
 class FusedEpisodes:
     """K ``DeviceEpisode`` buffer sets run as the K work-groups of one ``iqlhip_bb_sim_episodes`` call.  Their
@@ -767,12 +680,56 @@ def _fused_actor_descs(actors):
     return pairs
 
 
-def _fused_eval(actors, seeds, num_episodes, r_model, move_stats, state_mean, state_std, max_horizon,
-                n_min_obstacles, days, context_length, device, records, timing):
+# --------------------------------------------------------------------------- #
+# the device evaluations: one procedure, two rollouts
+# --------------------------------------------------------------------------- #
+def _launch_pair_rollout(eps, chunk: int):
+    """A reset launch, then ``chunk`` (forward, step) pairs per library call and one host wait per chunk, until the
+    episode is done or ``max_horizon`` steps are queued."""
+    ep, = eps
+
+    def run(descs):
+        ep.reset()
+        queued, length, done = 0, 0, False
+        while queued < ep.H and not done:
+            n = min(chunk, ep.H - queued)
+            ep.rollout(descs[0], n)
+            queued += n
+            length, done = ep.poll()
+        return [length]
+    return run
+
+
+def _fused_rollout(eps):
+    """One library call and one copy of the [K, 2] control words per episode index, whatever K is."""
+    fused = FusedEpisodes(eps)
+
+    def run(descs):
+        fused.run(descs)
+        return [length for length, _ in fused.poll()]
+    return run
+
+
+def _device_eval(caller, describe, rollout, actors, seeds, num_episodes, r_model, move_stats, state_mean, state_std,
+                 max_horizon, n_min_obstacles, days, context_length, device, records, record):
+    """``bb_run_eval_IQL`` for K actors, ``actors[k]`` on ``default_rng(seeds[k])``, in lock step over the episode
+    index with the step loop on the device; returns the K float64 [num_episodes, 1] arrays of returns.
+
+    Per episode every member draws its set-up and the whole [max_horizon, n_obs] drift table from its own generator
+    and uploads them; the rollout runs; every generator is put where the numpy loop leaves it (the saved state plus
+    ``length`` rows of drift).  All rewards of an episode come from ONE ``RewardPT.window_values`` call over the
+    device histories: window t covers steps ``max(0, t + 1 - context_length) .. t`` with their true timesteps, what
+    the numpy loop hands to ``RewardPTContext`` step by step; the return is their float64 sum in step order.
+
+    ``describe(actors)``: the K (descriptor, tensors) pairs, past the rollout's envelope check.  ``rollout(eps)``,
+    called with the K ``DeviceEpisode`` before any is loaded: the ``run(descs)`` that takes the loaded episodes from
+    their reset to their ends and returns the K lengths.  ``records[k]``: None or the dict for member k's
+    ``episodes``; ``record``: the caller's, for its ``timing`` dict."""
+    timing = record.get("timing") if isinstance(record, dict) else None
     if isinstance(r_model, RewardPT):
         r_model = RewardPTContext(r_model, context_length)
     if not isinstance(r_model, RewardPTContext):
-        raise TypeError("bb_run_eval_fused takes a RewardPTContext or a RewardPT: its rewards are one window_values "
+        raise TypeError(f"{caller} takes a RewardPTContext or a RewardPT: its rewards are one window_values "
                         "call over device histories; bb_run_eval_IQL is the path for any other callable")
     H, cl, K = int(max_horizon), int(context_length), len(actors)
     if H < 1:
@@ -781,14 +738,15 @@ def _fused_eval(actors, seeds, num_episodes, r_model, move_stats, state_mean, st
         raise ValueError("states, actions and timesteps must share one length <= context_length")
     if len(seeds) != K:
         raise ValueError(f"{K} actors, {len(seeds)} seeds")
-    pairs = _fused_actor_descs(actors)
+    pairs = describe(actors)
+    descs = [d for d, _ in pairs]
     pt_dev = next(r_model.model.parameters()).device
     for a in actors:
         a.eval()
     rngs = [np.random.default_rng(s) for s in seeds]
     eps = [DeviceEpisode(n_min_obstacles, H, state_mean, state_std, a.min_actions, a.max_actions, device)
            for a in actors]
-    fused = FusedEpisodes(eps)
+    run = rollout(eps)
     steps = np.arange(H)
     starts = np.maximum(0, steps + 1 - cl)
     win_start = torch.from_numpy(starts.astype(np.int64)).to(pt_dev)
@@ -799,7 +757,7 @@ def _fused_eval(actors, seeds, num_episodes, r_model, move_stats, state_mean, st
     def mark(phase, t0):
         if timing is None:
             return t0
-        torch.cuda.synchronize(fused.dev)
+        torch.cuda.synchronize(eps[0].dev)
         now = time.perf_counter()
         timing[phase] = timing.get(phase, 0.0) + (now - t0 if t0 is not None else 0.0)
         return now
@@ -814,8 +772,7 @@ def _fused_eval(actors, seeds, num_episodes, r_model, move_stats, state_mean, st
             ep.load(ox, oy, oang, px, py, goal, tail, drift)
             drawn.append((saved, n_obs))
         t0 = mark("setup", t0)
-        fused.run([d for d, _ in pairs])
-        lengths = [length for length, _ in fused.poll()]
+        lengths = run(descs)
         for rng, (saved, n_obs), length in zip(rngs, drawn, lengths):
             _rewind_drift(rng, saved, move_stats, length, n_obs)
         t0 = mark("steps", t0)
@@ -834,10 +791,34 @@ def _fused_eval(actors, seeds, num_episodes, r_model, move_stats, state_mean, st
                     {"states": ep.record[:length + 1].cpu().numpy(), "actions": ep.act_hist[:length].cpu().numpy(),
                      "rewards": values, "length": length})
         t0 = mark("reward", t0)
-    del pairs
     for a in actors:
         a.train()
-    return [np.asarray(r) for r in returns], rngs
+    return [np.asarray(r) for r in returns]
+
+
+def bb_run_eval_device(actor, num_episodes, r_model, move_stats, state_mean=0, state_std=1, max_horizon=500,
+                       n_min_obstacles=6, days=181, context_length=100, seed=4, device="cuda:0", chunk=64,
+                       record=None):
+    """``bb_run_eval_IQL`` with the step loop on the device: the same episodes, the same generator calls,
+    the same float arithmetic, the same float64 array of returns (``_device_eval`` is the procedure).
+
+    Per step the host queues the actor's forward (``iqlhip_mlp_forward`` on the live weights, the kernel
+    ``actor.act`` reaches) and one ``k_bb_step``, ``chunk`` steps per library call, and reads the done flag once
+    per chunk -- the only waits of the rollout.  Steps queued behind the goal write nothing.
+
+    ``r_model``: a ``RewardPTContext`` or a ``RewardPT`` (wrapped with ``context_length``).  ``record``: a
+    dict that receives ``record["episodes"]``, per episode ``states`` (float64 [length + 1, S], every
+    observation), ``actions`` (float32 [length, 2]), ``rewards`` (float64 [length]) and ``length``; a
+    ``record["timing"]`` dict, when present, receives the seconds spent in set-up and upload (``setup``),
+    the step loop (``steps``) and the reward call (``reward``), each closed by a device synchronisation.  The
+    actor is handed back in train mode."""
+    chunk = int(chunk)
+    if chunk < 1:
+        raise ValueError("chunk must be >= 1")
+    return _device_eval("bb_run_eval_device", lambda actors: [_actor_desc(a) for a in actors],
+                        lambda eps: _launch_pair_rollout(eps, chunk), [actor], [seed], num_episodes, r_model,
+                        move_stats, state_mean, state_std, max_horizon, n_min_obstacles, days, context_length,
+                        device, [record], record)[0]
 
 
 def bb_run_eval_fused(actor, num_episodes, r_model, move_stats, state_mean=0, state_std=1, max_horizon=500,
@@ -851,11 +832,9 @@ def bb_run_eval_fused(actor, num_episodes, r_model, move_stats, state_mean=0, st
     work-group), one host wait, one ``window_values`` call.  The fused forward takes actors of widths <= 256 with
     relu or tanh hidden layers; others are refused (``NotImplementedError``) before anything is launched, and
     ``bb_run_eval_device`` takes them."""
-    rec = record if isinstance(record, dict) else None
-    timing = rec.get("timing") if rec is not None else None
-    returns, _ = _fused_eval([actor], [seed], num_episodes, r_model, move_stats, state_mean, state_std, max_horizon,
-                             n_min_obstacles, days, context_length, device, [rec], timing)
-    return returns[0]
+    return _device_eval("bb_run_eval_fused", _fused_actor_descs, _fused_rollout, [actor], [seed], num_episodes,
+                        r_model, move_stats, state_mean, state_std, max_horizon, n_min_obstacles, days,
+                        context_length, device, [record], record)[0]
 
 
 def bb_run_eval_fused_group(actors, num_episodes, r_model, move_stats, state_mean=0, state_std=1, max_horizon=500,
@@ -864,23 +843,20 @@ def bb_run_eval_fused_group(actors, num_episodes, r_model, move_stats, state_mea
     """K evaluations side by side: ``actors[k]`` on ``default_rng(seeds[k])``.  Returns the list of the K return
     arrays, each bit-equal to ``bb_run_eval_fused`` of that member alone.
 
-    The members run in lock step over the episode index: for episode e every member draws its set-up and its
-    drift table from its own generator, ONE library call runs the K episodes as K work-groups of one launch, ONE
-    copy reads the K (length, done) pairs, every generator is rewound by its own member's length, then the K
-    reward calls run.  A member whose episode ends early leaves its generator elsewhere than the others, so the
-    later set-ups differ between members -- as in K separate evaluations.
+    The members run in lock step over the episode index (``_device_eval``): for episode e ONE library call runs the
+    K episodes as K work-groups of one launch, ONE copy reads the K (length, done) pairs, every generator is rewound
+    by its own member's length.  A member whose episode ends early leaves its generator elsewhere than the others,
+    so the later set-ups differ between members -- as in K separate evaluations.
 
     ``record``: a dict that receives ``record["members"]``, K dicts with the ``episodes`` list of
     ``bb_run_eval_fused``, and whose ``record["timing"]``, when present, receives the phases of all members."""
     actors, seeds = list(actors), list(seeds)
-    rec = record if isinstance(record, dict) else None
-    members = [{} for _ in actors] if rec is not None else [None] * len(actors)
-    if rec is not None:
-        rec["members"] = members
-    timing = rec.get("timing") if rec is not None else None
-    returns, _ = _fused_eval(actors, seeds, num_episodes, r_model, move_stats, state_mean, state_std, max_horizon,
-                             n_min_obstacles, days, context_length, device, members, timing)
-    return returns
+    members = [{} if isinstance(record, dict) else None for _ in actors]
+    if isinstance(record, dict):
+        record["members"] = members
+    return _device_eval("bb_run_eval_fused_group", _fused_actor_descs, _fused_rollout, actors, seeds, num_episodes,
+                        r_model, move_stats, state_mean, state_std, max_horizon, n_min_obstacles, days,
+                        context_length, device, members, record)
 
 
 # --------------------------------------------------------------------------- #
@@ -986,21 +962,19 @@ def train(config: TrainConfig, dataset=None, reward_model=None, move_stats=None,
 
     group_eval = {"step": None, "returns": None}
 
-    def evaluate(k, trainer, step):  # (bb_run_eval_IQL / _device / _fused: the module's globals at call time)
+    def evaluate(k, trainer, step):  # (the four bb_run_eval_* are the module's globals at call time)
+        kw = dict(num_episodes=config.eval_episodes, r_model=reward_model, move_stats=move_stats,
+                  state_mean=dataset.state_mean(), state_std=dataset.state_std(), device=device)
         if eval_on == "fused" and K > 1:
             # the weights of no member change between the K calls of an evaluation step (the group has been
             # synchronized and queues nothing until all have been evaluated)
             if group_eval["step"] != step:
-                group_eval["returns"] = bb_run_eval_fused_group(
-                    actors=[t.actor for t in trainers], num_episodes=config.eval_episodes, r_model=reward_model,
-                    move_stats=move_stats, state_mean=dataset.state_mean(), state_std=dataset.state_std(),
-                    seeds=[config.eval_seed + step] * K, device=device)
+                group_eval["returns"] = bb_run_eval_fused_group(actors=[t.actor for t in trainers],
+                                                                seeds=[config.eval_seed + step] * K, **kw)
                 group_eval["step"] = step
             return group_eval["returns"][k]
         run_eval = {"device": bb_run_eval_device, "fused": bb_run_eval_fused}.get(eval_on, bb_run_eval_IQL)
-        return run_eval(actor=trainer.actor, num_episodes=config.eval_episodes, r_model=reward_model,
-                               move_stats=move_stats, state_mean=dataset.state_mean(),
-                               state_std=dataset.state_std(), seed=config.eval_seed + step, device=device)
+        return run_eval(actor=trainer.actor, seed=config.eval_seed + step, **kw)
 
     _offline_loop.run(trainers, seeds, group, int(config.update_steps), int(config.eval_every), chunk, logger,
                       ckpt_dirs, steps, evaluate)

@@ -11,132 +11,29 @@ against the numpy simulator bb_run_eval_IQL and the reference's record.  -m gpu.
 5. train(eval_on="device") against train(eval_on="host").
 6. the refusals of the entry points, with nothing launched.
 
-Tolerances.
-* STATE_TOL = 1e-9 absolute on every state entry where both sides are given the same action bits (1, 2, 3):
-  positions are bounded by 50, an episode has at most 500 steps, and a step adds products whose float64
-  trig factors may differ from libm's by a couple of ulp: 500 * 50 * 4.4e-16 = 1.1e-11, two decades below.
-  The agent's own move is float32 in numpy (NEP 50 scalar promotion; csrc/bb_sim.hip restates numpy's
-  float32 sine / cosine bit for bit), so its coordinates are equal exactly, not within a rounding.
-* Margins of the inputs, computed on the CPU with the numpy simulator (a tie or a goal test decided the other
-  way would be a different trajectory, not an error of 1e-9).  Smallest gap between two consecutive
-  distances among the n_near + 1 nearest obstacles (the gap between the n_near-th and the next is one of
-  them), and smallest |d2 - 1.69| of the goal test, over all steps and episodes:
-    case 1 (fixture, seed 9):      gap 1.20e-3,  |d2 - 1.69| 8.2e+2  (the agent never comes near the goal)
-    case 2 (seed 13, n_near 1):    gap 5.27e-2,  |d2 - 1.69| 6.1e+2
-    case 2 (seed 13, n_near 6):    gap 1.92e-3,  |d2 - 1.69| 6.1e+2
-    case 3 (seed 18):              gap 2.07e-3,  |d2 - 1.69| 1.03
-  All are above 1e-6, so the committed fixture is used as it is.
-* WHOLE_STATE_TOL = 1e-4 absolute between the two whole paths (4): one fp32 rounding flip of an actor input
-  may change an action in its last bits and propagate for <= 60 steps.  Actions are compared bit for bit at
-  every step whose fp32 actor input is bit-equal on both sides.
+Tolerances.  STATE_TOL, WHOLE_STATE_TOL and the tie and goal-test margins of the seeds: tests/bb_eval_env.py.
 * RETURN_TOL: measured on the host path alone (measure_return_tolerance below: the host path twice, the
   second time with every fp32 actor input moved by one ulp), ten times the largest return difference seen,
   with a floor of 1e-5 (40 summed fp32 rewards of size O(1): 40 * 2^-23 = 5e-6).  Measured on an MI355X:
   1.4e-6 / 2.4e-6 (Gaussian policy, tuned / general PT), 7.0e-7 / 8.8e-7 (deterministic); MEASURED_RETURN_DIFF
   is the largest, RETURN_TOL = 2.4e-5.  The device path itself came out bit-equal to the host path in all four
   cases of that run (returns, states and actions).
-* Case 4 runs seed 9 (the fixture's), whose margins under the real actors, taken on the host path, are
-  gap 1.9e-3 / 1.6e-2 (Gaussian / deterministic) and |d2 - 1.69| 8.2e+2: above the 1e-3 asked of that seed.
 """
-import contextlib
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 import torch
 
 from tests import bb_env
+from tests.bb_eval_env import (DEV, GOAL_BEARING, GOAL_H, GOAL_HI, GOAL_SEED, HI, LEVEL_H, LEVEL_SEED, LO, MS,
+                               SENTINEL, WHOLE_CL, WHOLE_H, WHOLE_SEED, WHOLE_STATE_TOL, ConstantActor,
+                               _close_states, _goal_actor, _level_actions, _pt, _train, _train_args, _whole_case,
+                               bb, golden, injected, numpy_run, spied)  # (bb, golden: the module-scoped fixtures)
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-STATE_TOL = 1e-9
-WHOLE_STATE_TOL = 1e-4
 MEASURED_RETURN_DIFF = 2.4e-6  # largest |return difference| of measure_return_tolerance over its four cases
 RETURN_TOL = max(10 * MEASURED_RETURN_DIFF, 1e-5)
-MS = bb_env.MOVE_STATS
-LO, HI = np.array([0.0, -180.0], np.float32), np.array([1.5, 180.0], np.float32)
-SENTINEL = -12345.5
-
-
-@pytest.fixture(scope="module")
-def golden(golden_dir):
-    return dict(np.load(os.path.join(golden_dir, "bb_train_run.npz")))
-
-
-@pytest.fixture(scope="module")
-def bb():
-    from iqlpref_amd import custom_offline_bb
-    return custom_offline_bb
-
-
-# --------------------------------------------------------------------------- #
-# helpers: the numpy path with every observation recorded, the device path on injected actions
-# --------------------------------------------------------------------------- #
-@contextlib.contextmanager
-def spied(bb):
-    """Every observation either path forms on the host, split by episode, and the generator it draws from."""
-    seen = {"episodes": [], "rng": None}
-    real_setup, real_observe = bb._episode_setup, bb._observe
-
-    def setup(rng, days):
-        seen["rng"] = rng
-        seen["episodes"].append([])
-        return real_setup(rng, days)
-
-    def observe(*a):
-        out = real_observe(*a)
-        seen["episodes"][-1].append(out.copy())
-        return out
-
-    bb._episode_setup, bb._observe = setup, observe
-    try:
-        yield seen
-    finally:
-        bb._episode_setup, bb._observe = real_setup, real_observe
-
-
-def numpy_run(bb, actor, n_ep, horizon, seed, n_near=6, reward=bb_env.numpy_reward, **kw):
-    with spied(bb) as seen:
-        returns = bb.bb_run_eval_IQL(actor, n_ep, reward, MS, max_horizon=horizon, seed=seed,
-                                     n_min_obstacles=n_near, **kw)
-    return [np.stack(e) for e in seen["episodes"]], returns, seen["rng"].bit_generator.state
-
-
-def device_injected(bb, actions, n_ep, horizon, seed, n_near=6, mean=0, std=1, lo=LO, hi=HI, extra_steps=0,
-                    sentinel=False):
-    """The episodes of ``default_rng(seed)`` through k_bb_step with ``actions`` (consumed in order, as a
-    ReplayActor hands them out) in place of the forward's output.  All steps of an episode are queued at once."""
-    rng = np.random.default_rng(seed)
-    used, out = 0, []
-    for _ in range(n_ep):
-        n_obs, *setup = bb._episode_setup(rng, 181)
-        saved = rng.bit_generator.state
-        drift = rng.normal(MS[2], MS[3], (horizon, n_obs))
-        table = np.zeros((horizon, 2), np.float32)
-        rows = actions[used:used + horizon]
-        table[:len(rows)] = rows
-        ep = bb.DeviceEpisode(n_near, horizon, mean, std, lo, hi, DEV, injected=table)
-        if sentinel:
-            for t in (ep.record, ep.obs_hist, ep.act_hist, ep.actor_in):
-                t.fill_(SENTINEL)
-        ep.load(*setup, drift)
-        ep.reset()
-        for _ in range(horizon + extra_steps):
-            ep.step()
-        length, done = ep.poll()
-        bb._rewind_drift(rng, saved, MS, length, n_obs)
-        used += length
-        out.append({"states": ep.record.cpu().numpy(), "obs_hist": ep.obs_hist.cpu().numpy(),
-                    "act_hist": ep.act_hist.cpu().numpy(), "actor_in": ep.actor_in.cpu().numpy(), "length": length,
-                    "done": done, "n_obs": n_obs})
-    return out, rng.bit_generator.state
-
-
-def _close_states(got, want, what, tol=STATE_TOL):
-    err = np.abs(np.asarray(got) - np.asarray(want)).max()
-    print(f"{what}: max |state error| {err:.3e}")
-    assert err <= tol, what
 
 
 # --------------------------------------------------------------------------- #
@@ -147,7 +44,7 @@ def test_step_kernel_replays_the_reference_record(golden, bb):
     mean, std = golden["stats/state_mean"], golden["stats/state_std"]
     lo, hi = golden["stats/min_actions"], golden["stats/max_actions"]
     acts = golden["eval/actions"]
-    eps, _ = device_injected(bb, acts, n_ep, H, seed, mean=mean, std=std, lo=lo, hi=hi)
+    (eps, _), = injected(bb, "pair", [acts], n_ep, H, [seed], mean=mean, std=std, lo=lo, hi=hi)
     assert [e["length"] for e in eps] == [H] * n_ep and len(golden["eval/states"]) == n_ep * H  # no step left out
     want_raw, _, _ = numpy_run(bb, bb_env.ReplayActor(acts), n_ep, H, seed)
     for k, e in enumerate(eps):
@@ -164,23 +61,13 @@ def test_step_kernel_replays_the_reference_record(golden, bb):
 # --------------------------------------------------------------------------- #
 # 2. levels and envelope
 # --------------------------------------------------------------------------- #
-LEVEL_SEED, LEVEL_H = 13, 30  # its three episodes are levels 11, 10, 9
-
-
-def _level_actions():
-    r = np.random.default_rng(1000 + LEVEL_SEED)
-    a = np.stack([r.uniform(-0.2, 2.0, 90), r.uniform(-200, 200, 90)], 1).astype(np.float32)
-    a[::7, 1] = np.resize([90.0, 180.0, -180.0, 270.0, 0.0, -90.0, 360.0], len(a[::7]))
-    return a
-
-
 @pytest.mark.parametrize("n_near", [1, 6])
 def test_levels_against_the_numpy_simulator(bb, n_near):
     raw = _level_actions()
     clamped = np.clip(raw, LO, HI)
     assert (clamped != raw).any(0).all()  # both components are clamped somewhere
     want, _, want_rng = numpy_run(bb, bb_env.ReplayActor(clamped), 3, LEVEL_H, LEVEL_SEED, n_near=n_near)
-    eps, got_rng = device_injected(bb, raw, 3, LEVEL_H, LEVEL_SEED, n_near=n_near)
+    (eps, got_rng), = injected(bb, "pair", [raw], 3, LEVEL_H, [LEVEL_SEED], n_near=n_near)
     assert [e["n_obs"] for e in eps] == [150, 100, 50]
     assert [e["length"] for e in eps] == [LEVEL_H] * 3
     for k, e in enumerate(eps):
@@ -195,28 +82,14 @@ def test_levels_against_the_numpy_simulator(bb, n_near):
 # --------------------------------------------------------------------------- #
 # 3. the goal
 # --------------------------------------------------------------------------- #
-GOAL_SEED, GOAL_H = 18, 40  # the goal of its first episode lies 31.8 away at a bearing of 0.37986 degrees
-GOAL_BEARING = 0.37986065227777027
-
-
-class ConstantActor(bb_env.ReplayActor):
-    def __init__(self, action):
-        super().__init__([])
-        self.action = np.asarray(action, np.float32)
-
-    def act(self, state, device="cpu"):
-        self.states.append(np.array(state))
-        return self.action.copy()
-
-
 def test_steps_behind_the_goal_write_nothing(bb):
     action = np.array([1.0, GOAL_BEARING], np.float32)
     actor = ConstantActor(action)
     want, _, want_rng = numpy_run(bb, actor, 2, GOAL_H, GOAL_SEED)
     lengths = [len(w) - 1 for w in want]
     assert lengths[0] < GOAL_H - 5 and lengths[1] == GOAL_H  # the first episode ends at its goal, the second runs out
-    eps, got_rng = device_injected(bb, np.tile(action, (2 * GOAL_H, 1)), 2, GOAL_H, GOAL_SEED, hi=np.array([2.0, 180.0], np.float32),
-                                   extra_steps=5, sentinel=True)
+    (eps, got_rng), = injected(bb, "pair", [np.tile(action, (2 * GOAL_H, 1))], 2, GOAL_H, [GOAL_SEED], hi=GOAL_HI,
+                               extra_steps=5, sentinel=True)
     assert [e["length"] for e in eps] == lengths and [e["done"] for e in eps] == [True, False]
     assert got_rng == want_rng
     for e, w, n in zip(eps, want, lengths):
@@ -225,23 +98,10 @@ def test_steps_behind_the_goal_write_nothing(bb):
         assert (e["act_hist"][n:] == SENTINEL).all() and (e["act_hist"][:n] == action).all()
 
 
-def _pt(bb, S, horizon, seed, general=False):
-    from iqlpref_amd.relabel import RewardPT
-    torch.manual_seed(seed)
-    pt = RewardPT(S, 2, horizon, embd_dim=64, num_heads=4, intermediate_dim=256, num_layers=2 if general else 1).to(DEV)
-    assert pt.tuned_shape() != general
-    return pt
-
-
 def test_goal_episode_through_the_whole_path(bb):
     """A policy whose net puts out (1, bearing) whatever it sees: equal action bits on both paths, so equal
     lengths and states; the second episode's set-up shows that the generator was left where numpy leaves it."""
-    hi, lo = torch.tensor([2.0, 180.0]), torch.tensor([0.0, -180.0])
-    actor = bb.DeterministicPolicy(26, 2, hi.to(DEV), lo.to(DEV), hidden_dim=32).to(DEV)
-    with torch.no_grad():
-        for p in actor.parameters():
-            p.zero_()
-        actor.net.linears()[-1].bias.copy_(torch.tensor([10.0, float(np.arctanh(GOAL_BEARING))]))
+    actor = _goal_actor(bb)
     pt = _pt(bb, 26, GOAL_H, seed=3)
     with spied(bb) as host:
         want = bb.bb_run_eval_IQL(actor, 2, bb.RewardPTContext(pt, 16), MS, max_horizon=GOAL_H, context_length=16,
@@ -264,9 +124,6 @@ def test_goal_episode_through_the_whole_path(bb):
 # --------------------------------------------------------------------------- #
 # 4. whole path against the host path
 # --------------------------------------------------------------------------- #
-WHOLE_SEED, WHOLE_H, WHOLE_CL = 9, 40, 16
-
-
 class RecordingActor:
     """The host path's actor with its fp32 inputs and actions kept; ``nudge`` moves every input by one ulp."""
 
@@ -287,15 +144,6 @@ class RecordingActor:
         a = self.actor.act(x, device)
         self.actions.append(a.copy())
         return a
-
-
-def _whole_case(bb, golden, policy, general):
-    mean, std = golden["stats/state_mean"], golden["stats/state_std"]
-    hi, lo = torch.from_numpy(golden["stats/max_actions"]), torch.from_numpy(golden["stats/min_actions"])
-    torch.manual_seed(17)
-    cls = bb.GaussianPolicy if policy == "gaussian" else bb.DeterministicPolicy
-    actor = cls(26, 2, hi.to(DEV), lo.to(DEV), hidden_dim=256 if policy == "gaussian" else 40).to(DEV)
-    return actor, _pt(bb, 26, WHOLE_H, seed=5, general=general), mean, std
 
 
 def _host_run(bb, actor, pt, mean, std, nudge=False):
@@ -352,36 +200,6 @@ def test_whole_path_against_the_host_path(bb, golden, policy, general):
 # --------------------------------------------------------------------------- #
 # 5. train(eval_on="device")
 # --------------------------------------------------------------------------- #
-def _train(bb, golden, eval_on, K, tmp_path):
-    config = bb.TrainConfig(update_steps=12, eval_every=12, batch_size=bb_env.BATCH, normalize_state=True,
-                            normalize_reward=True, eval_episodes=2, train_seed=int(golden["train_seed"]), eval_seed=4,
-                            checkpoints_path=str(tmp_path / eval_on))
-    pt = _pt(bb, 26, 40, seed=5)
-    records = []
-    real = {"host": bb.bb_run_eval_IQL, "device": bb.bb_run_eval_device}
-    calls = []
-    bb.bb_run_eval_IQL = lambda **kw: (calls.append("host"), real["host"](**dict(kw, max_horizon=40)))[1]
-    bb.bb_run_eval_device = lambda **kw: (calls.append("device"), real["device"](**dict(kw, max_horizon=40)))[1]
-    torch.manual_seed(123)
-    np.random.seed(123)
-    perm = golden["perm"] if K == 1 else [golden["perm"], golden["perm"][::-1].copy()]
-    try:
-        tr = bb.train(config, {k[5:]: v for k, v in golden.items() if k.startswith("data/")},
-                      bb.RewardPTContext(pt, 100), MS, logger=lambda d, step: records.append((int(step), dict(d))),
-                      perm=perm, device=DEV, chunk=4, seeds_per_gpu=K, eval_on=eval_on)
-    finally:
-        bb.bb_run_eval_IQL, bb.bb_run_eval_device = real["host"], real["device"]
-    assert calls == [eval_on] * K
-    trainers = tr if K > 1 else [tr]
-    torch.cuda.synchronize()
-    tensors = [{n: getattr(t, n).cpu().numpy().copy() for n in ("_params", "_target", "_exp_avg", "_exp_avg_sq")}
-               for t in trainers]
-    rng = (torch.get_rng_state().numpy().tobytes(), torch.cuda.get_rng_state(DEV).numpy().tobytes(),
-           repr(np.random.get_state()))
-    assert all(t.actor.training for t in trainers)
-    return records, tensors, rng
-
-
 @pytest.mark.parametrize("K", [1, 2])
 def test_train_evaluates_on_the_device(bb, golden, tmp_path, K):
     host = _train(bb, golden, "host", K, tmp_path)
@@ -404,7 +222,7 @@ def test_train_refuses_a_plain_callable_before_the_first_step(bb, golden):
     records = []
     with pytest.raises(TypeError, match="bb_run_eval_IQL"):
         bb.train(bb.TrainConfig(update_steps=12, eval_every=12, batch_size=bb_env.BATCH),
-                 {k[5:]: v for k, v in golden.items() if k.startswith("data/")}, bb_env.numpy_reward, MS,
+                 _train_args(golden), bb_env.numpy_reward, MS,
                  logger=lambda d, step: records.append(step), perm=golden["perm"], device=DEV, eval_on="device")
     assert records == []
 

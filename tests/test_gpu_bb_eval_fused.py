@@ -11,13 +11,14 @@ path of tests/test_gpu_bb_eval_device.py, the numpy simulator and the reference'
 5. bb_run_eval_fused against bb_run_eval_device, bit for bit (the four cases of _whole_case);
 6. bb_run_eval_fused_group against the solo runs of its members, bit for bit;
 7. train(eval_on="fused"), K = 1 and K = 2, against eval_on="host" (training) and eval_on="device" (returns);
-8. the refusals, with nothing launched.
+8. the refusals, with nothing launched;
+9. the host waits of the three entry points: one per chunk, one per episode, one per episode index of a group.
 
-Tolerances: STATE_TOL = 1e-9 of tests/test_gpu_bb_eval_device.py (its derivation there) where a state is compared
+Tolerances: STATE_TOL = 1e-9 of tests/bb_eval_env.py (its derivation there) where a state is compared
 with numpy or the record (1, 3); everything else is compared bit for bit.
 
 Margins.  Cases 1 - 3 and 5 run the seeds whose tie and goal margins stand in the header of
-tests/test_gpu_bb_eval_device.py (gaps >= 1.2e-3, |d2 - 1.69| >= 1.03).  Case 4 compares the fused forward with
+tests/bb_eval_env.py (gaps >= 1.2e-3, |d2 - 1.69| >= 1.03).  Case 4 compares the fused forward with
 iqlhip_mlp_forward on the input rows the fused run itself recorded, so no decision of the simulator enters the
 comparison; its margins, taken on the CPU with the numpy simulator and an fp32 torch restatement of the four
 actors (seed 9, horizon 30, 2 episodes, the fixture's statistics; smallest gap between consecutive distances among
@@ -30,52 +31,19 @@ and of the three members of case 6 (the first three actors built under seeds 30,
 gaps 2.38e-3, 5.76e-4, 4.68e-4, |d2 - 1.69| >= 7.7e+2.  All are above 1e-6.
 """
 import ctypes as C
+import math
 
 import numpy as np
 import pytest
 import torch
 
 from tests import bb_env
-from tests import test_gpu_bb_eval_device as T
+from tests import bb_eval_env as E
 
 pytestmark = pytest.mark.gpu
-DEV, MS, LO, HI, SENTINEL, STATE_TOL = T.DEV, T.MS, T.LO, T.HI, T.SENTINEL, T.STATE_TOL
-golden, bb = T.golden, T.bb  # (the module-scoped fixtures of the launch-pair tests)
+DEV, MS, LO, HI, SENTINEL, STATE_TOL = E.DEV, E.MS, E.LO, E.HI, E.SENTINEL, E.STATE_TOL
+golden, bb = E.golden, E.bb  # (the module-scoped fixtures)
 BUFFERS = ("states", "obs_hist", "act_hist", "actor_in")
-
-
-def fused_injected(bb, tables, n_ep, horizon, seeds, n_near=6, mean=0, std=1, lo=LO, hi=HI, sentinel=False):
-    """T.device_injected through k_bb_episodes for K members side by side: member k plays ``default_rng(seeds[k])``
-    on ``tables[k]`` (consumed in order).  Returns per member (episodes, final generator state)."""
-    K = len(tables)
-    rngs = [np.random.default_rng(s) for s in seeds]
-    used, out = [0] * K, [[] for _ in range(K)]
-    for _ in range(n_ep):
-        eps, drawn = [], []
-        for k in range(K):
-            n_obs, *setup = bb._episode_setup(rngs[k], 181)
-            saved = rngs[k].bit_generator.state
-            drift = rngs[k].normal(MS[2], MS[3], (horizon, n_obs))
-            table = np.zeros((horizon, 2), np.float32)
-            rows = tables[k][used[k]:used[k] + horizon]
-            table[:len(rows)] = rows
-            eps.append(bb.DeviceEpisode(n_near, horizon, mean, std, lo, hi, DEV, injected=table))
-            drawn.append((setup, drift, saved, n_obs))
-        fused = bb.FusedEpisodes(eps)
-        for ep, (setup, drift, _, _) in zip(eps, drawn):
-            if sentinel:
-                for t in (ep.record, ep.obs_hist, ep.act_hist, ep.actor_in):
-                    t.fill_(SENTINEL)
-            ep.load(*setup, drift)
-        fused.run([None] * K)
-        for k, ((length, done), ep, (_, _, saved, n_obs)) in enumerate(zip(fused.poll(), eps, drawn)):
-            bb._rewind_drift(rngs[k], saved, MS, length, n_obs)
-            used[k] += length
-            out[k].append({"states": ep.record.cpu().numpy(), "obs_hist": ep.obs_hist.cpu().numpy(),
-                           "act_hist": ep.act_hist.cpu().numpy(), "actor_in": ep.actor_in.cpu().numpy(),
-                           "length": length, "done": done, "n_obs": n_obs, "ctl": ep.ctl.cpu().tolist(),
-                           "sim_state": ep.state.cpu().numpy()})
-    return [(out[k], rngs[k].bit_generator.state) for k in range(K)]
 
 
 def _same_bits(a, b, what):
@@ -91,13 +59,13 @@ def test_fused_kernel_replays_the_reference_record(golden, bb):
     mean, std = golden["stats/state_mean"], golden["stats/state_std"]
     lo, hi = golden["stats/min_actions"], golden["stats/max_actions"]
     acts = golden["eval/actions"]
-    (eps, _), = fused_injected(bb, [acts], n_ep, H, [seed], mean=mean, std=std, lo=lo, hi=hi)
+    (eps, _), = E.injected(bb, "fused", [acts], n_ep, H, [seed], mean=mean, std=std, lo=lo, hi=hi)
     assert [e["length"] for e in eps] == [H] * n_ep and len(golden["eval/states"]) == n_ep * H  # no step left out
-    want_raw, _, _ = T.numpy_run(bb, bb_env.ReplayActor(acts), n_ep, H, seed)
+    want_raw, _, _ = E.numpy_run(bb, bb_env.ReplayActor(acts), n_ep, H, seed)
     for k, e in enumerate(eps):
         rec = golden["eval/states"][k * H:(k + 1) * H]  # the normalised state the actor saw at every step
-        T._close_states((e["states"][:H] - mean) / std, rec, f"episode {k} against the record")
-        T._close_states(e["states"], want_raw[k], f"episode {k} against the numpy simulator")
+        E._close_states((e["states"][:H] - mean) / std, rec, f"episode {k} against the record")
+        E._close_states(e["states"], want_raw[k], f"episode {k} against the numpy simulator")
         np.testing.assert_array_equal(e["states"][:, :2], want_raw[k][:, :2])  # the agent: float32 arithmetic, exact
         np.testing.assert_array_equal(e["obs_hist"], e["states"].astype(np.float32))
         np.testing.assert_array_equal(e["act_hist"], acts[k * H:(k + 1) * H])
@@ -110,35 +78,32 @@ def test_fused_kernel_replays_the_reference_record(golden, bb):
 # --------------------------------------------------------------------------- #
 @pytest.mark.parametrize("n_near", [1, 6])
 def test_levels_bit_equal_to_the_launch_pair(bb, n_near):
-    raw = T._level_actions()
-    want, want_rng = T.device_injected(bb, raw, 3, T.LEVEL_H, T.LEVEL_SEED, n_near=n_near)
-    (got, got_rng), = fused_injected(bb, [raw], 3, T.LEVEL_H, [T.LEVEL_SEED], n_near=n_near)
+    raw = E._level_actions()
+    (want, want_rng), = E.injected(bb, "pair", [raw], 3, E.LEVEL_H, [E.LEVEL_SEED], n_near=n_near)
+    (got, got_rng), = E.injected(bb, "fused", [raw], 3, E.LEVEL_H, [E.LEVEL_SEED], n_near=n_near)
     assert [e["n_obs"] for e in got] == [150, 100, 50] and got_rng == want_rng
     for g, w in zip(got, want):
-        assert g["states"].shape == (T.LEVEL_H + 1, 2 + 3 * n_near + 6)
+        assert g["states"].shape == (E.LEVEL_H + 1, 2 + 3 * n_near + 6)
         for name in BUFFERS:
             _same_bits(g[name], w[name], f"n_near {n_near}, {g['n_obs']} obstacles: {name}")
-        assert g["ctl"] == [w["length"], int(w["done"])] == [T.LEVEL_H, 0]
+        assert g["ctl"] == [w["length"], int(w["done"])] == [E.LEVEL_H, 0]
 
 
 # --------------------------------------------------------------------------- #
 # 3. the goal
 # --------------------------------------------------------------------------- #
-GOAL_HI = np.array([2.0, 180.0], np.float32)
-
-
 def test_nothing_is_written_behind_the_goal(bb):
-    action = np.array([1.0, T.GOAL_BEARING], np.float32)
-    want, _, want_rng = T.numpy_run(bb, T.ConstantActor(action), 2, T.GOAL_H, T.GOAL_SEED)
+    action = np.array([1.0, E.GOAL_BEARING], np.float32)
+    want, _, want_rng = E.numpy_run(bb, E.ConstantActor(action), 2, E.GOAL_H, E.GOAL_SEED)
     lengths = [len(w) - 1 for w in want]
-    assert lengths[0] < T.GOAL_H - 5 and lengths[1] == T.GOAL_H  # the first ends at its goal, the second runs out
-    (eps, got_rng), = fused_injected(bb, [np.tile(action, (2 * T.GOAL_H, 1))], 2, T.GOAL_H, [T.GOAL_SEED], hi=GOAL_HI,
-                                     sentinel=True)
+    assert lengths[0] < E.GOAL_H - 5 and lengths[1] == E.GOAL_H  # the first ends at its goal, the second runs out
+    (eps, got_rng), = E.injected(bb, "fused", [np.tile(action, (2 * E.GOAL_H, 1))], 2, E.GOAL_H, [E.GOAL_SEED],
+                                 hi=E.GOAL_HI, sentinel=True)
     assert [e["length"] for e in eps] == lengths and [e["done"] for e in eps] == [True, False]
     assert [e["ctl"] for e in eps] == [[lengths[0], 1], [lengths[1], 0]]
     assert got_rng == want_rng
     for e, w, n in zip(eps, want, lengths):
-        T._close_states(e["states"][:n + 1], w, f"episode of {n} steps")
+        E._close_states(e["states"][:n + 1], w, f"episode of {n} steps")
         assert (e["states"][n + 1:] == SENTINEL).all() and (e["obs_hist"][n + 1:] == SENTINEL).all()
         assert (e["act_hist"][n:] == SENTINEL).all() and (e["act_hist"][:n] == action).all()
         np.testing.assert_array_equal(e["obs_hist"][:n + 1], e["states"][:n + 1].astype(np.float32))
@@ -170,7 +135,7 @@ def test_fused_forward_bits_are_those_of_mlp_forward(bb, golden, policy, hidden,
     mean, std = golden["stats/state_mean"], golden["stats/state_std"]
     actor = _actor(bb, golden, policy, hidden, n_hidden, act)
     assert actor.net._hidden_act == (1 if act == "tanh" else 0)
-    pt = T._pt(bb, 26, ACTOR_H, seed=5)
+    pt = E._pt(bb, 26, ACTOR_H, seed=5)
     rec = {}
     bb.bb_run_eval_fused(actor, 2, pt, MS, state_mean=mean, state_std=std, max_horizon=ACTOR_H, context_length=16,
                          seed=ACTOR_SEED, device=DEV, record=rec)
@@ -199,14 +164,14 @@ def _records_equal(got, want, what):
 @pytest.mark.parametrize("general", [False, True], ids=["tuned_pt", "general_pt"])
 @pytest.mark.parametrize("policy", ["gaussian", "deterministic"])
 def test_whole_path_bit_equal_to_the_device_path(bb, golden, policy, general):
-    actor, pt, mean, std = T._whole_case(bb, golden, policy, general)
-    kw = dict(state_mean=mean, state_std=std, max_horizon=T.WHOLE_H, context_length=T.WHOLE_CL, seed=T.WHOLE_SEED,
+    actor, pt, mean, std = E._whole_case(bb, golden, policy, general)
+    kw = dict(state_mean=mean, state_std=std, max_horizon=E.WHOLE_H, context_length=E.WHOLE_CL, seed=E.WHOLE_SEED,
               device=DEV)
     want_rec, got_rec = {}, {}
-    with T.spied(bb) as dev:
+    with E.spied(bb) as dev:
         want = bb.bb_run_eval_device(actor, 2, pt, MS, chunk=16, record=want_rec, **kw)
     actor.eval()
-    with T.spied(bb) as fus:
+    with E.spied(bb) as fus:
         got = bb.bb_run_eval_fused(actor, 2, pt, MS, record=got_rec, **kw)
     assert actor.training  # handed back in train mode, whatever it came in
     _same_bits(got, want, "returns")
@@ -214,7 +179,7 @@ def test_whole_path_bit_equal_to_the_device_path(bb, golden, policy, general):
     _records_equal(got_rec["episodes"], want_rec["episodes"], policy)
     assert fus["rng"].bit_generator.state == dev["rng"].bit_generator.state
     timed = {"timing": {}}
-    again = bb.bb_run_eval_fused(actor, 2, bb.RewardPTContext(pt, T.WHOLE_CL), MS, record=timed, **kw)
+    again = bb.bb_run_eval_fused(actor, 2, bb.RewardPTContext(pt, E.WHOLE_CL), MS, record=timed, **kw)
     _same_bits(again, got, "returns with timing")
     assert set(timed["timing"]) == {"other", "setup", "steps", "reward"}
 
@@ -241,7 +206,7 @@ def test_group_members_equal_their_solo_runs(bb, golden, generators):
     mean, std = golden["stats/state_mean"], golden["stats/state_std"]
     actors = [_actor(bb, golden, *a, seed=30 + i) for i, a in enumerate(ACTORS[:3])]
     seeds = [9, 13, 18]
-    pt = T._pt(bb, 26, ACTOR_H, seed=5)
+    pt = E._pt(bb, 26, ACTOR_H, seed=5)
     kw = dict(state_mean=mean, state_std=std, max_horizon=ACTOR_H, context_length=16, device=DEV)
     rec = {}
     got = bb.bb_run_eval_fused_group(actors, 2, pt, MS, seeds=seeds, record=rec, **kw)
@@ -265,16 +230,17 @@ def test_group_members_equal_their_solo_runs(bb, golden, generators):
 def test_group_with_members_of_different_lengths(bb):
     """One seed for all three members; member 0 walks to its goal, the others walk away from it: member 0's
     generator is rewound less far, so its second set-up is another one than theirs."""
-    tables = [np.tile(np.array([1.0, T.GOAL_BEARING + d], np.float32), (2 * T.GOAL_H, 1)) for d in (0.0, 90.0, -120.0)]
-    seeds = [T.GOAL_SEED] * 3
-    group = fused_injected(bb, tables, 2, T.GOAL_H, seeds, hi=GOAL_HI, sentinel=True)
+    tables = [np.tile(np.array([1.0, E.GOAL_BEARING + d], np.float32), (2 * E.GOAL_H, 1)) for d in (0.0, 90.0, -120.0)]
+    seeds = [E.GOAL_SEED] * 3
+    group = E.injected(bb, "fused", tables, 2, E.GOAL_H, seeds, hi=E.GOAL_HI, sentinel=True)
     lengths = [[e["length"] for e in eps] for eps, _ in group]
-    assert lengths[0][0] < T.GOAL_H - 5 and lengths[1] == lengths[2] == [T.GOAL_H] * 2
+    assert lengths[0][0] < E.GOAL_H - 5 and lengths[1] == lengths[2] == [E.GOAL_H] * 2
     assert [eps[0]["done"] for eps, _ in group] == [True, False, False]
     _same_bits(group[0][0][0]["states"][0], group[1][0][0]["states"][0], "the first set-up is shared")
     assert group[0][0][1]["states"][0].tobytes() != group[1][0][1]["states"][0].tobytes()  # the second is not
     for k in range(3):
-        (solo, solo_rng), = fused_injected(bb, tables[k:k + 1], 2, T.GOAL_H, seeds[k:k + 1], hi=GOAL_HI, sentinel=True)
+        (solo, solo_rng), = E.injected(bb, "fused", tables[k:k + 1], 2, E.GOAL_H, seeds[k:k + 1], hi=E.GOAL_HI,
+                                       sentinel=True)
         assert solo_rng == group[k][1]
         for g, w in zip(group[k][0], solo):
             for name in BUFFERS + ("sim_state",):
@@ -285,41 +251,11 @@ def test_group_with_members_of_different_lengths(bb):
 # --------------------------------------------------------------------------- #
 # 7. train(eval_on="fused")
 # --------------------------------------------------------------------------- #
-def _train_fused(bb, golden, K, tmp_path):
-    """T._train with eval_on="fused": the same tiny configuration, the evaluations cut to a horizon of 40."""
-    config = bb.TrainConfig(update_steps=12, eval_every=12, batch_size=bb_env.BATCH, normalize_state=True,
-                            normalize_reward=True, eval_episodes=2, train_seed=int(golden["train_seed"]), eval_seed=4,
-                            checkpoints_path=str(tmp_path / "fused"))
-    pt = T._pt(bb, 26, 40, seed=5)
-    records, calls = [], []
-    real = {"solo": bb.bb_run_eval_fused, "group": bb.bb_run_eval_fused_group}
-    bb.bb_run_eval_fused = lambda **kw: (calls.append("solo"), real["solo"](**dict(kw, max_horizon=40)))[1]
-    bb.bb_run_eval_fused_group = lambda **kw: (calls.append("group"), real["group"](**dict(kw, max_horizon=40)))[1]
-    torch.manual_seed(123)
-    np.random.seed(123)
-    perm = golden["perm"] if K == 1 else [golden["perm"], golden["perm"][::-1].copy()]
-    try:
-        tr = bb.train(config, {k[5:]: v for k, v in golden.items() if k.startswith("data/")},
-                      bb.RewardPTContext(pt, 100), MS, logger=lambda d, step: records.append((int(step), dict(d))),
-                      perm=perm, device=DEV, chunk=4, seeds_per_gpu=K, eval_on="fused")
-    finally:
-        bb.bb_run_eval_fused, bb.bb_run_eval_fused_group = real["solo"], real["group"]
-    assert calls == (["solo"] if K == 1 else ["group"])  # K members, ONE group rollout
-    trainers = tr if K > 1 else [tr]
-    torch.cuda.synchronize()
-    tensors = [{n: getattr(t, n).cpu().numpy().copy() for n in ("_params", "_target", "_exp_avg", "_exp_avg_sq")}
-               for t in trainers]
-    rng = (torch.get_rng_state().numpy().tobytes(), torch.cuda.get_rng_state(DEV).numpy().tobytes(),
-           repr(np.random.get_state()))
-    assert all(t.actor.training for t in trainers)
-    return records, tensors, rng
-
-
 @pytest.mark.parametrize("K", [1, 2])
 def test_train_evaluates_fused(bb, golden, tmp_path, K):
-    host = T._train(bb, golden, "host", K, tmp_path)
-    dev = T._train(bb, golden, "device", K, tmp_path)
-    fus = _train_fused(bb, golden, K, tmp_path)
+    host = E._train(bb, golden, "host", K, tmp_path)
+    dev = E._train(bb, golden, "device", K, tmp_path)
+    fus = E._train(bb, golden, "fused", K, tmp_path)
     is_loss = lambda d: "value_loss" in d
     assert [r for r in host[0] if is_loss(r[1])] == [r for r in fus[0] if is_loss(r[1])]  # bit-identical losses
     assert len([r for r in fus[0] if is_loss(r[1])]) == 12 * K
@@ -333,15 +269,11 @@ def test_train_evaluates_fused(bb, golden, tmp_path, K):
     assert len(ret(fus)) == K and ret(fus) == ret(dev)
 
 
-def _train_args(golden):
-    return {k[5:]: v for k, v in golden.items() if k.startswith("data/")}
-
-
 def test_train_refuses_before_the_first_step(bb, golden):
     records = []
     log = lambda d, step: records.append(step)
     with pytest.raises(TypeError, match="bb_run_eval_IQL"):
-        bb.train(bb.TrainConfig(update_steps=12, eval_every=12, batch_size=bb_env.BATCH), _train_args(golden),
+        bb.train(bb.TrainConfig(update_steps=12, eval_every=12, batch_size=bb_env.BATCH), E._train_args(golden),
                  bb_env.numpy_reward, MS, logger=log, perm=golden["perm"], device=DEV, eval_on="fused")
     # train() builds actors of width 256; a trainer whose actor is 512 wide (as a caller's own trainer class may
     # build it) is refused where train() checks the envelope, ahead of the first step
@@ -355,8 +287,8 @@ def test_train_refuses_before_the_first_step(bb, golden):
     bb._co._build_trainer = build
     try:
         with pytest.raises(NotImplementedError, match="512 > 256"):
-            bb.train(bb.TrainConfig(update_steps=12, eval_every=12, batch_size=bb_env.BATCH), _train_args(golden),
-                     bb.RewardPTContext(T._pt(bb, 26, 40, seed=5), 100), MS, logger=log, perm=golden["perm"],
+            bb.train(bb.TrainConfig(update_steps=12, eval_every=12, batch_size=bb_env.BATCH), E._train_args(golden),
+                     bb.RewardPTContext(E._pt(bb, 26, 40, seed=5), 100), MS, logger=log, perm=golden["perm"],
                      device=DEV, eval_on="fused")
     finally:
         bb._co._build_trainer = real
@@ -402,4 +334,37 @@ def test_entry_point_refuses_with_nothing_launched(bb):
         assert all((t == SENTINEL).all() for t in buffers) and ep.ctl.tolist() == [3, 0]
     assert (scratch == 0).all()
     with pytest.raises(TypeError, match="bb_run_eval_IQL"):
-        bb.bb_run_eval_fused(bb_env.ReplayActor([]), 1, T._pt(bb, 26, 8, seed=1), MS, max_horizon=8, device=DEV)
+        bb.bb_run_eval_fused(bb_env.ReplayActor([]), 1, E._pt(bb, 26, 8, seed=1), MS, max_horizon=8, device=DEV)
+
+
+# --------------------------------------------------------------------------- #
+# 9. host waits
+# --------------------------------------------------------------------------- #
+def test_host_waits_per_chunk_per_episode_and_per_group(bb, golden, monkeypatch):
+    """DeviceEpisode.poll and FusedEpisodes.poll are the only places that wait for a step loop: the launch pair
+    calls the first once per chunk, the fused rollout the second once per episode index, whatever K is."""
+    polls = {"pair": 0, "fused": 0}
+    for cls, name in ((bb.DeviceEpisode, "pair"), (bb.FusedEpisodes, "fused")):
+        def poll(self, real=cls.poll, name=name):
+            polls[name] += 1
+            return real(self)
+        monkeypatch.setattr(cls, "poll", poll)
+    # the goal case of test_goal_episode_through_the_whole_path: one episode ends early, one runs out
+    actor, pt = E._goal_actor(bb), E._pt(bb, 26, E.GOAL_H, seed=3)
+    kw = dict(max_horizon=E.GOAL_H, context_length=16, seed=E.GOAL_SEED, device=DEV)
+    rec = {}
+    bb.bb_run_eval_device(actor, 2, pt, MS, chunk=8, record=rec, **kw)
+    lengths = [e["length"] for e in rec["episodes"]]
+    print("lengths", lengths, "polls", polls)
+    assert lengths[0] < E.GOAL_H - 5 and lengths[1] == E.GOAL_H
+    assert polls == {"pair": sum(math.ceil(n / 8) for n in lengths), "fused": 0}
+    polls.update(pair=0)
+    bb.bb_run_eval_fused(actor, 2, pt, MS, **kw)
+    assert polls == {"pair": 0, "fused": 2}
+    # the three members of test_group_members_equal_their_solo_runs
+    actors = [_actor(bb, golden, *a, seed=30 + i) for i, a in enumerate(ACTORS[:3])]
+    polls.update(fused=0)
+    bb.bb_run_eval_fused_group(actors, 2, E._pt(bb, 26, ACTOR_H, seed=5), MS, seeds=[9, 13, 18], device=DEV,
+                               state_mean=golden["stats/state_mean"], state_std=golden["stats/state_std"],
+                               max_horizon=ACTOR_H, context_length=16)
+    assert polls == {"pair": 0, "fused": 2}  # not 6
