@@ -60,6 +60,8 @@ const char *iqlhip_build_tag(void);
 /*   online    iqlhip_explore_action: every trainer shape above at precision     */
 /*             fp32; iqlhip_replay_append: any ring of >= 1 rows, n <= capacity;  */
 /*             iqlhip_np_randint_growing: growth 0 or 1, bounds up to 2^32;       */
+/*             iqlhip_explore_action_group / iqlhip_replay_append_group: the same */
+/*             for one row of each of 1..16 trainers / rings in one launch;       */
 /*   MLP fwd   1..8 layers, every width in [1, 1024] (beyond 256: a plain      */
 /*             one-wave-per-16-rows variant);                                  */
 /*   CVaR      1 <= n_tail <= S <= 2400;                                       */
@@ -545,6 +547,33 @@ int iqlhip_np_randint_growing(uint32_t *state, const int64_t *hi0, const int64_t
 int iqlhip_explore_action(iqlhip_trainer *t, const float *s, int64_t rows, const float *eps,
                           float expl_noise, float noise_clip, float max_action, uint32_t call, float *out,
                           void *stream);
+
+/* The tick of K seeds that train side by side (finetune.train(seeds_per_gpu = K)): the act and the append
+ * of all members as ONE launch each, 1 <= K <= IQLHIP_MAX_GROUP.
+ *
+ * iqlhip_explore_action_group: row k of out[K][action_dim] is what
+ *   iqlhip_explore_action(trainers[k], s + k * s_stride, 1, eps ? eps + k * action_dim : NULL, expl_noise,
+ *                         noise_clip, max_action, calls[k], ...)
+ * writes, BIT FOR BIT, over the trainer's whole envelope (either summation order of the stand-alone MLP
+ * kernels, dropout masks, drawn or given noise): one work-group per member on the live fp32 masters, no
+ * scratch, no second launch.  trainers and calls are host arrays of K entries (read during the call only);
+ * s is device fp32 [K][s_stride], s_stride >= state_dim; eps is NULL or device fp32 [K][action_dim].  All
+ * members are precision fp32 (bf16: IQLHIP_ERR_UNSUPPORTED) on one device with equal state_dim and
+ * action_dim (else IQLHIP_ERR_INVALID); depth, width, policy kind, dropout and seed are each member's own.
+ * Nothing is launched when a check fails.  No synchronisation.
+ *
+ * iqlhip_replay_append_group: one transition into each of K rings of one geometry.  stage is device fp32
+ * [K][2 S + A + 2], transition k in the order s | a | r | s' | d; row pointer[k] % capacity[k] of
+ * rows[k][capacity[k]][row_stride] receives what iqlhip_replay_append(n = 1) writes there, padding zeros
+ * included; every other row keeps its contents.  rows, capacity and pointer are host arrays of K entries;
+ * rows[k] distinct and on 16-byte boundaries, 0 <= pointer[k] < capacity[k], else IQLHIP_ERR_INVALID
+ * before the launch.  The caller advances its pointers, sizes and generations.                       */
+int iqlhip_explore_action_group(iqlhip_trainer *const *trainers, int32_t K, const float *s, int32_t s_stride,
+                                const float *eps, float expl_noise, float noise_clip, float max_action,
+                                const uint32_t *calls, float *out, void *stream);
+int iqlhip_replay_append_group(float *const *rows, int32_t row_stride, int32_t state_dim, int32_t action_dim,
+                               const int64_t *capacity, const int64_t *pointer, int32_t K, const float *stage,
+                               void *stream);
 
 /* ------------------------------------------------------------------------ */
 /* Block-shuffled epochs of algorithms/custom_offline/iql_bb.py:208-267        */

@@ -157,6 +157,10 @@ SYMBOLS = {
                                        P, P, P, P, P, P]),
     "iqlhip_np_randint_growing": (C.c_int, [P, P, P, C.c_int32, C.c_int32, C.c_int32, C.c_int64, P, P]),
     "iqlhip_explore_action": (C.c_int, [P, P, C.c_int64, P, C.c_float, C.c_float, C.c_float, C.c_uint32, P, P]),
+    "iqlhip_explore_action_group": (C.c_int, [C.POINTER(P), C.c_int32, P, C.c_int32, P, C.c_float, C.c_float, C.c_float,
+                                              C.POINTER(C.c_uint32), P, P]),
+    "iqlhip_replay_append_group": (C.c_int, [C.POINTER(P), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int64),
+                                             C.POINTER(C.c_int64), C.c_int32, P, P]),
     "iqlhip_block_epoch_indices": (C.c_int, [P, C.c_int64, C.c_int32, C.c_int64, C.c_int64, P, P, P]),
     "iqlhip_block_epoch_indices_group": (C.c_int, [C.POINTER(P), C.c_int64, C.c_int32, C.c_int64, C.c_int64,
                                                    C.POINTER(P), P, C.c_int32, P]),

@@ -91,6 +91,11 @@ hipError_t launch_explore_epilogue(float *act, int64_t rows, int A, const float 
                                    hipStream_t st);
 hipError_t launch_np_randint(uint32_t *state, const int64_t *hi, int K, int64_t total, int64_t *const *out,
                              hipStream_t st);
+hipError_t launch_replay_append_group(float *const *rows, int stride, int S, int A, const int64_t *capacity,
+                                      const int64_t *pointer, int K, const float *stage, hipStream_t st);
+hipError_t launch_explore_group(const iqlhip_mlp_desc *actors, const float *const *log_std, int K, const float *s,
+                                int s_stride, const float *eps, float expl_noise, float noise_clip, float max_action,
+                                float *out, hipStream_t st);
 hipError_t launch_bb_step(const iqlhip_bb_sim &sim, int reset, hipStream_t st);
 size_t bb_episodes_scratch_bytes(const iqlhip_mlp_desc *const *actors, int n);
 hipError_t launch_bb_episodes(const iqlhip_bb_sim *sims, const iqlhip_mlp_desc *const *actors, int n, void *scratch,
@@ -449,6 +454,7 @@ struct DeepRing {
 struct iqlhip_trainer {
   iqlhip_trainer_config cfg;
   iqlhip_arenas arenas;
+  int device = -1;  // where the parameter arena lives
   // shapes outside the tuned step's (n_hidden != 2 or another width): the general layer-wise step;
   // of the members below only cfg, the learning rates, total_it, `queue` (its graph, timing events,
   // throttle and counters; not the DevArgs ring), `group` and batch_rows are in use then
@@ -701,6 +707,10 @@ extern "C" int iqlhip_trainer_create(iqlhip_trainer **out, const iqlhip_trainer_
   if (!t) return fail(IQLHIP_ERR_NOMEM, "host allocation failed");
   t->cfg = *cfg;
   t->arenas = *ar;
+  if (hipPointerAttribute_t at; hipPointerGetAttributes(&at, ar->params) == hipSuccess)
+    t->device = at.device;
+  else
+    (void)hipGetLastError();
   t->bf16 = cfg->precision == IQLHIP_PREC_BF16;
   t->lr_q = cfg->lr_q, t->lr_v = cfg->lr_v, t->lr_a_base = cfg->lr_actor;
   const Layout L = make_layout(*cfg);
@@ -1633,20 +1643,11 @@ extern "C" int iqlhip_np_randint_growing(uint32_t *state, const int64_t *hi0, co
   return 0;
 }
 
-// The actor's forward runs the stand-alone exact-fp32 MLP kernel straight on the fp32 masters of the
-// parameter arena (what every step's update writes: nothing is copied, nothing can go stale), for the
-// tuned and the general step alike; k_explore_epilogue then turns its output into the action in place.
-extern "C" int iqlhip_explore_action(iqlhip_trainer *t, const float *s, int64_t rows, const float *eps,
-                                     float expl_noise, float noise_clip, float max_action, uint32_t call,
-                                     float *out, void *stream) {
-  if (!t || !s || !out) return fail(IQLHIP_ERR_INVALID, "null argument");
-  if (rows < 1 || rows > 0xffffffffLL) return fail(IQLHIP_ERR_INVALID, "rows = %lld outside 1..2^32 - 1", (long long)rows);
+// The actor of a trainer as launch_mlp_f32 takes it: the fp32 masters of the parameter arena where they lie
+// (what every step's update writes: nothing is copied, nothing can go stale), for the tuned and the general
+// step alike.  log_std: NULL for a deterministic policy.
+static iqlhip_mlp_desc explore_actor(const iqlhip_trainer *t, uint32_t call, const float **log_std) {
   const iqlhip_trainer_config &c = t->cfg;
-  if (c.precision != IQLHIP_PREC_FP32)
-    return fail(IQLHIP_ERR_UNSUPPORTED, "exploration actions need a precision fp32 trainer (the fine-tune flavour "
-                                        "runs without autocast)");
-  if (!(noise_clip >= 0.f) || !(max_action > 0.f) || !(expl_noise >= 0.f))
-    return fail(IQLHIP_ERR_INVALID, "expl_noise and noise_clip must be >= 0, max_action > 0");
   const Layout L = make_layout(c);
   const int E = n_critics(c), NL = n_hidden(c) + 1, net = E + 1;
   iqlhip_mlp_desc d;
@@ -1662,11 +1663,81 @@ extern "C" int iqlhip_explore_action(iqlhip_trainer *t, const float *s, int64_t 
   // fref never leaves train mode outside eval_actor: with actor_dropout the exploring forward drops units
   d.dropout_p = c.dropout_p > 0.f ? c.dropout_p : 0.f;
   d.dropout_call = call, d.dropout_seed = c.seed;
-  const float *log_std = c.deterministic ? nullptr : t->arenas.params + L.off[(E + 2) * NL * 2];
+  *log_std = c.deterministic ? nullptr : t->arenas.params + L.off[(E + 2) * NL * 2];
+  return d;
+}
+
+// The actor's forward runs the stand-alone exact-fp32 MLP kernel straight on those masters;
+// k_explore_epilogue then turns its output into the action in place.
+extern "C" int iqlhip_explore_action(iqlhip_trainer *t, const float *s, int64_t rows, const float *eps,
+                                     float expl_noise, float noise_clip, float max_action, uint32_t call,
+                                     float *out, void *stream) {
+  if (!t || !s || !out) return fail(IQLHIP_ERR_INVALID, "null argument");
+  if (rows < 1 || rows > 0xffffffffLL) return fail(IQLHIP_ERR_INVALID, "rows = %lld outside 1..2^32 - 1", (long long)rows);
+  const iqlhip_trainer_config &c = t->cfg;
+  if (c.precision != IQLHIP_PREC_FP32)
+    return fail(IQLHIP_ERR_UNSUPPORTED, "exploration actions need a precision fp32 trainer (the fine-tune flavour "
+                                        "runs without autocast)");
+  if (!(noise_clip >= 0.f) || !(max_action > 0.f) || !(expl_noise >= 0.f))
+    return fail(IQLHIP_ERR_INVALID, "expl_noise and noise_clip must be >= 0, max_action > 0");
+  const float *log_std;
+  const iqlhip_mlp_desc d = explore_actor(t, call, &log_std);
   hipStream_t st = (hipStream_t)stream;
   HIP_TRY(launch_mlp_f32(d, s, rows, c.state_dim, out, c.action_dim, st));
   HIP_TRY(launch_explore_epilogue(out, rows, c.action_dim, log_std, eps, expl_noise, noise_clip, max_action, c.seed,
                                   call, st));
+  return 0;
+}
+
+// One state row of each of K trainers: k_explore_group, one work-group per member on the same masters.
+extern "C" int iqlhip_explore_action_group(iqlhip_trainer *const *trainers, int32_t K, const float *s,
+                                           int32_t s_stride, const float *eps, float expl_noise, float noise_clip,
+                                           float max_action, const uint32_t *calls, float *out, void *stream) {
+  if (!trainers || !s || !calls || !out) return fail(IQLHIP_ERR_INVALID, "null argument");
+  if (K < 1 || K > IQLHIP_MAX_GROUP) return fail(IQLHIP_ERR_INVALID, "K = %d: 1..%d members", K, IQLHIP_MAX_GROUP);
+  if (!(noise_clip >= 0.f) || !(max_action > 0.f) || !(expl_noise >= 0.f))
+    return fail(IQLHIP_ERR_INVALID, "expl_noise and noise_clip must be >= 0, max_action > 0");
+  for (int k = 0; k < K; ++k) {
+    if (!trainers[k]) return fail(IQLHIP_ERR_INVALID, "null trainer %d", k);
+    const iqlhip_trainer_config &c = trainers[k]->cfg, &c0 = trainers[0]->cfg;
+    if (c.precision != IQLHIP_PREC_FP32)
+      return fail(IQLHIP_ERR_UNSUPPORTED, "trainer %d: exploration actions need a precision fp32 trainer (the "
+                                          "fine-tune flavour runs without autocast)", k);
+    if (trainers[k]->device != trainers[0]->device)
+      return fail(IQLHIP_ERR_INVALID, "trainer %d lives on device %d, trainer 0 on device %d", k, trainers[k]->device,
+                  trainers[0]->device);
+    if (c.state_dim != c0.state_dim || c.action_dim != c0.action_dim)
+      return fail(IQLHIP_ERR_INVALID, "trainer %d: state_dim %d, action_dim %d differ from trainer 0's %d, %d", k,
+                  c.state_dim, c.action_dim, c0.state_dim, c0.action_dim);
+  }
+  if (s_stride < trainers[0]->cfg.state_dim)
+    return fail(IQLHIP_ERR_INVALID, "s_stride = %d below state_dim = %d", s_stride, trainers[0]->cfg.state_dim);
+  iqlhip_mlp_desc actors[IQLHIP_MAX_GROUP];
+  const float *log_std[IQLHIP_MAX_GROUP];
+  for (int k = 0; k < K; ++k) actors[k] = explore_actor(trainers[k], calls[k], &log_std[k]);
+  HIP_TRY(launch_explore_group(actors, log_std, K, s, s_stride, eps, expl_noise, noise_clip, max_action, out,
+                               (hipStream_t)stream));
+  return 0;
+}
+
+extern "C" int iqlhip_replay_append_group(float *const *rows, int32_t row_stride, int32_t S, int32_t A,
+                                          const int64_t *capacity, const int64_t *pointer, int32_t K,
+                                          const float *stage, void *stream) {
+  if (!rows || !capacity || !pointer || !stage) return fail(IQLHIP_ERR_INVALID, "null pointer");
+  if (K < 1 || K > IQLHIP_MAX_GROUP) return fail(IQLHIP_ERR_INVALID, "K = %d: 1..%d rings", K, IQLHIP_MAX_GROUP);
+  if (S <= 0 || A <= 0 || row_stride < iqlhip_replay_row_stride(S, A) || (row_stride & 3))
+    return fail(IQLHIP_ERR_INVALID, "bad replay geometry S=%d A=%d stride=%d", S, A, row_stride);
+  for (int k = 0; k < K; ++k) {
+    if (!rows[k]) return fail(IQLHIP_ERR_INVALID, "null rows[%d]", k);
+    if ((uintptr_t)rows[k] & 15) return fail(IQLHIP_ERR_INVALID, "rows[%d] must start on a 16-byte boundary", k);
+    if (capacity[k] < 1) return fail(IQLHIP_ERR_INVALID, "capacity[%d] = %lld must be >= 1", k, (long long)capacity[k]);
+    if (pointer[k] < 0 || pointer[k] >= capacity[k])
+      return fail(IQLHIP_ERR_INVALID, "pointer[%d] = %lld outside 0..%lld", k, (long long)pointer[k],
+                  (long long)capacity[k] - 1);
+    for (int j = 0; j < k; ++j)
+      if (rows[j] == rows[k]) return fail(IQLHIP_ERR_INVALID, "ring %d listed twice", k);
+  }
+  HIP_TRY(launch_replay_append_group(rows, row_stride, S, A, capacity, pointer, K, stage, (hipStream_t)stream));
   return 0;
 }
 

@@ -17,6 +17,10 @@ global generator over ``_size`` (fref:156), ``actor_dropout`` a float with 0.0 f
 cosine schedule that keeps stepping past ``T_max = offline_iterations`` (fref:448, 513): the rate climbs again
 as ``(1 + cos(pi t / T_max)) / 2`` does, on the host's bookkeeping and in the kernels alike.
 
+``train(seeds_per_gpu=K)`` runs K such seeds side by side on one GPU.  The host waits once per tick whatever K
+is, so the act (``explore_actions``), the append (``add_transitions``) and the gradient step (``SeedGroup``) of
+all members go out as one launch sequence each; member k is bit for bit the run ``config.seed = seed_k`` is alone.
+
 gym, d4rl and wandb are imported only when ``train()`` is not handed what they would provide.
 """
 import ctypes as C
@@ -239,6 +243,53 @@ class ReplayBuffer(_OfflineReplayBuffer):
         self._generation = _buffer_generation[0]
 
 
+def add_transitions(buffers: Sequence[ReplayBuffer], states, actions, rewards, next_states, dones):
+    """``buffers[k].add_transition(states[k], actions[k], rewards[k], next_states[k], dones[k])`` for K rings of
+    one geometry on one device: one pinned [K, W] staging block, one copy and ONE
+    ``iqlhip_replay_append_group`` launch; nothing waits on the host except for the previous call's copy out
+    of the same block.  Every ring is checked as ``add_transition`` checks it before anything is written."""
+    bufs = list(buffers)
+    K = len(bufs)
+    if not 1 <= K <= _lib.MAX_GROUP:
+        raise ValueError(f"add_transitions takes 1..{_lib.MAX_GROUP} replay buffers (got {K})")
+    b0 = bufs[0]
+    S, A = b0._state_dim, b0._action_dim
+    if any(len(x) != K for x in (states, actions, rewards, next_states, dones)):
+        raise ValueError(f"add_transitions: one state, action, reward, next state and done flag per buffer ({K})")
+    if len({id(b) for b in bufs}) != K:
+        raise ValueError("a replay buffer may appear only once")
+    for b in bufs:
+        if (b._state_dim, b._action_dim, b._stride, b._dev) != (S, A, b0._stride, b0._dev):
+            raise ValueError("add_transitions: all replay buffers must have one state_dim, action_dim and device")
+    for b in bufs:
+        if b._pointer >= b._buffer_size:
+            raise IndexError(f"index {b._pointer} is out of bounds for a replay buffer of {b._buffer_size} rows")
+    W = 2 * S + A + 2
+    stage = getattr(b0, "_group_stage", None)
+    if stage is None or stage[0].shape[0] != K:
+        stage = b0._group_stage = (torch.zeros((K, W), dtype=torch.float32).pin_memory(),
+                                   torch.zeros((K, W), dtype=torch.float32, device=b0._dev),
+                                   torch.cuda.Event())
+    host, dev, free = stage
+    free.synchronize()  # (an event never recorded is complete)
+    h = host.numpy()  # (five assignments whatever K is: the block is filled column-wise)
+    h[:, :S] = np.asarray(states, dtype=np.float32).reshape(K, S)
+    h[:, S:S + A] = np.asarray(actions, dtype=np.float32).reshape(K, A)
+    h[:, S + A] = np.asarray(rewards, dtype=np.float32).reshape(K)
+    h[:, S + A + 1:2 * S + A + 1] = np.asarray(next_states, dtype=np.float32).reshape(K, S)
+    h[:, 2 * S + A + 1] = np.asarray(dones, dtype=np.float32).reshape(K)
+    with torch.cuda.device(b0._dev):
+        dev.copy_(host, non_blocking=True)
+        free.record()
+        check(b0._lib.iqlhip_replay_append_group((C.c_void_p * K)(*[b._rows.data_ptr() for b in bufs]), b0._stride, S, A,
+                                                 (C.c_int64 * K)(*[b._buffer_size for b in bufs]),
+                                                 (C.c_int64 * K)(*[b._pointer for b in bufs]), K, ptr(dev), stream_ptr()))
+    for b in bufs:
+        b._pointer, b._size = ring_advance(b._pointer, b._size, 1, b._buffer_size)
+        _buffer_generation[0] += 1
+        b._generation = _buffer_generation[0]
+
+
 # --------------------------------------------------------------------------- #
 # numpy's index stream over a growing buffer
 # --------------------------------------------------------------------------- #
@@ -356,6 +407,49 @@ class ImplicitQLearning(_OfflineIQL):
         super().load_state_dict(sd)
 
 
+def explore_actions(trainers: Sequence[ImplicitQLearning], states, eps=None, *, expl_noise: float, noise_clip: float,
+                    batch_size: Optional[int] = None) -> torch.Tensor:
+    """``trainers[k].explore_action(states[k:k + 1], eps[k:k + 1])`` for K trainers (1..``_lib.MAX_GROUP``, one
+    device, one state_dim / action_dim / max_action; depth, width, policy kind, dropout and seed each member's
+    own) in ONE ``iqlhip_explore_action_group`` launch: row k of the float32 device tensor [K, A] that comes
+    back has the bits the member's own call would give.  ``states`` [K, S], ``eps`` None or [K, A].  Every
+    trainer's call number advances by one."""
+    trs = list(trainers)
+    K = len(trs)
+    if not 1 <= K <= _lib.MAX_GROUP:
+        raise ValueError(f"explore_actions takes 1..{_lib.MAX_GROUP} trainers (got {K})")
+    t0 = trs[0]
+    for t in trs:
+        if t._precision != _lib.PREC_FP32:
+            raise NotImplementedError("explore_actions needs precision='fp32' trainers (the fine-tune flavour runs "
+                                      "without autocast)")
+    for t in trs:
+        if (t._state_dim, t._action_dim, t._dev, float(t.max_action)) != \
+                (t0._state_dim, t0._action_dim, t0._dev, float(t0.max_action)):
+            raise ValueError("explore_actions: all trainers must have one state_dim, action_dim, max_action and device")
+    S, A = t0._state_dim, t0._action_dim
+    # (host arrays are rounded to float32 on the host: one copy up, no cast kernel behind it)
+    up = lambda x: x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
+    s = up(states).to(device=t0._dev, dtype=torch.float32).reshape(-1, S).contiguous()
+    if s.shape[0] != K:
+        raise ValueError(f"states must have shape {(K, S)}, got {tuple(s.shape)}")
+    if eps is not None:
+        eps = up(eps).to(device=t0._dev, dtype=torch.float32).contiguous()
+        if tuple(eps.shape) != (K, A):
+            raise ValueError(f"eps must have shape {(K, A)}, got {tuple(eps.shape)}")
+    for t in trs:
+        t._ensure_handle(batch_size or t._handle_batch or 32)
+    out = torch.empty((K, A), dtype=torch.float32, device=t0._dev)
+    with torch.cuda.device(t0._dev):
+        check(t0._lib.iqlhip_explore_action_group((C.c_void_p * K)(*[t._handle.value for t in trs]), K, ptr(s), S, ptr(eps),
+                                                  float(expl_noise), float(noise_clip), float(t0.max_action),
+                                                  (C.c_uint32 * K)(*[t._explore_calls & 0xFFFFFFFF for t in trs]),
+                                                  ptr(out), stream_ptr()))
+    for t in trs:
+        t._explore_calls += 1
+    return out
+
+
 # --------------------------------------------------------------------------- #
 # train (fref:566-767)
 # --------------------------------------------------------------------------- #
@@ -374,7 +468,7 @@ def train(config: TrainConfig, env=None, eval_env=None, dataset: Optional[Dict[s
           normalized_score: Optional[Callable[[float], float]] = None, device: Optional[str] = None,
           chunk: int = 2000, online_chunk: int = 256,
           exploration_noise: Optional[Callable[[int], Union[np.ndarray, torch.Tensor]]] = None,
-          on_start: Optional[Callable] = None):
+          on_start: Optional[Callable] = None, seeds_per_gpu: int = 1):
     """fref:566-767 on the HIP path.
 
     ``env`` / ``eval_env``: gym < 0.26 environments (``seed``, ``reset() -> obs``, ``step(a) -> (obs, r, done,
@@ -390,7 +484,23 @@ def train(config: TrainConfig, env=None, eval_env=None, dataset: Optional[Dict[s
     (``online_chunk=1`` keeps fref's interleaving).  Losses come back to the host once per chunk.
     ``exploration_noise(tick)``: the standard normals [A] of online tick ``tick`` (parity runs); None draws
     them on the device.  ``on_start(trainer, replay_buffer)`` is called before the first step.
-    Returns the trainer."""
+    Returns the trainer.
+
+    ``seeds_per_gpu`` = K > 1 (up to ``_lib.MAX_GROUP``): K runs side by side on one GPU, run k what this
+    function does alone under ``config.seed = rank_seed(config.seed, K) + k`` -- bit for bit, as long as no
+    environment reads numpy's global generator (member k draws its indices from its own
+    ``np.random.RandomState(seed_k)``).  ``env`` / ``eval_env``: sequences of K environments or a callable
+    ``k -> env``.  Every tick acts for all members in one launch (``explore_actions``), steps the K
+    environments on the host, appends in one launch (``add_transitions``) and takes one ``SeedGroup`` step.
+    Records carry a ``seed`` entry, checkpoints go under ``seed_<s>/``, ``exploration_noise(tick)`` returns
+    [K, A], ``on_start(trainers, replay_buffers)`` gets the lists, and the list of trainers is returned."""
+    K = int(seeds_per_gpu)
+    if not 1 <= K <= _lib.MAX_GROUP:
+        raise ValueError(f"seeds_per_gpu must be in 1..{_lib.MAX_GROUP}")
+    if K > 1:
+        return _train_group(config, env, eval_env, dataset, K, logger=logger, normalized_score=normalized_score,
+                            device=device, chunk=chunk, online_chunk=online_chunk,
+                            exploration_noise=exploration_noise, on_start=on_start)
     if device is None:
         device = D.local_device() or ("cuda:0" if config.device == "cuda" else config.device)
     if env is None or eval_env is None or dataset is None:
@@ -550,3 +660,207 @@ def train(config: TrainConfig, env=None, eval_env=None, dataset: Optional[Dict[s
             evaluate(t)
     flush()
     return trainer
+
+
+def _member_envs(env, K: int, what: str):
+    """``env`` / ``eval_env`` of a K-seed run as it was given: None, a callable ``k -> env``, or K environments."""
+    if env is None or callable(env):
+        return env
+    if not isinstance(env, (list, tuple)) or len(env) != K:
+        n = len(env) if isinstance(env, (list, tuple)) else 1
+        raise ValueError(f"finetune.train(seeds_per_gpu={K}): {what} must be {K} environments or a callable "
+                         f"k -> env (got {n})")
+    return list(env)
+
+
+def _train_group(config: TrainConfig, env, eval_env, dataset, K: int, *, logger, normalized_score, device, chunk,
+                 online_chunk, exploration_noise, on_start):
+    """``train`` for K > 1 seeds: the same loop with every per-run variable a list, the act, the append and the
+    gradient step of a tick one launch sequence each for all members."""
+    env, eval_env = _member_envs(env, K, "env"), _member_envs(eval_env, K, "eval_env")
+    if device is None:
+        device = D.local_device() or ("cuda:0" if config.device == "cuda" else config.device)
+    if env is None or eval_env is None or dataset is None:
+        gym, d4rl = _gym_and_d4rl()
+        env = (lambda k: gym.make(config.env)) if env is None else env
+        eval_env = (lambda k: gym.make(config.env)) if eval_env is None else eval_env
+    envs = [env(k) for k in range(K)] if callable(env) else env
+    eval_envs = [eval_env(k) for k in range(K)] if callable(eval_env) else eval_env
+    if dataset is None:
+        dataset = d4rl.qlearning_dataset(envs[0])
+    normalized = [e.get_normalized_score for e in eval_envs] if normalized_score is None else [normalized_score] * K
+    is_env_with_goal = config.env.startswith(ENVS_WITH_GOAL)
+    max_steps = envs[0]._max_episode_steps
+    state_dim = envs[0].observation_space.shape[0]
+    action_dim = envs[0].action_space.shape[0]
+    n_off, n_on, B = int(config.offline_iterations), int(config.online_iterations), int(config.batch_size)
+    ks = range(K)
+
+    # ---- dataset and normalisation once, one ring per member (fref:578-603) ----
+    reward_mod_dict = {}
+    if config.normalize_reward:
+        reward_mod_dict = modify_reward(dataset, config.env)
+    if config.normalize:
+        state_mean, state_std = compute_mean_std(dataset["observations"], eps=1e-3)
+    else:
+        state_mean, state_std = 0, 1
+    dataset["observations"] = normalize_states(dataset["observations"], state_mean, state_std)
+    dataset["next_observations"] = normalize_states(dataset["next_observations"], state_mean, state_std)
+    envs = [wrap_env(e, state_mean=state_mean, state_std=state_std) for e in envs]
+    eval_envs = [wrap_env(e, state_mean=state_mean, state_std=state_std) for e in eval_envs]
+    up = lambda name: torch.tensor(dataset[name], dtype=torch.float32, device=device)
+    arrays = [up(n) for n in ("observations", "actions", "rewards", "next_observations", "terminals")]
+    buffers = []
+    for k in ks:
+        try:
+            buffers.append(ReplayBuffer(state_dim, action_dim, config.buffer_size, device))
+            buffers[k].load_device_arrays(*arrays)
+        except MemoryError as e:
+            raise MemoryError(f"finetune.train(seeds_per_gpu={K}): the ring of member {k} of {K}: {e}") from None
+    del arrays
+    max_action = float(envs[0].action_space.high[0])
+    seeds = [D.rank_seed(config.seed, K) + k for k in ks]
+    ckpt_dirs = _offline_loop.checkpoint_dirs(config, seeds)
+    tagged = _offline_loop.tag(seeds)
+
+    # ---- seeds and nets, member by member as a run of its own sets them up (fref:613-660) ----
+    dropout = config.actor_dropout if config.actor_dropout and config.actor_dropout > 0.0 else None  # fref:314
+    policy = DeterministicPolicy if config.iql_deterministic else GaussianPolicy
+    trainers = []
+    for k, seed in enumerate(seeds):
+        set_seed(seed, envs[k])
+        eval_envs[k].seed(config.eval_seed)
+        eval_envs[k].action_space.seed(config.eval_seed)
+        q_network = TwinQ(state_dim, action_dim).to(device)
+        v_network = ValueFunction(state_dim).to(device)
+        actor = policy(state_dim, action_dim, max_action, dropout=dropout).to(device)
+        v_optimizer = torch.optim.Adam(v_network.parameters(), lr=config.vf_lr)
+        q_optimizer = torch.optim.Adam(q_network.parameters(), lr=config.qf_lr)
+        actor_optimizer = torch.optim.Adam(actor.parameters(), lr=config.actor_lr)
+        print("---------------------------------------")
+        print(f"Training IQL, Env: {config.env}, Seed: {seed}")
+        print("---------------------------------------")
+        trainers.append(ImplicitQLearning(max_action=max_action, actor=actor, actor_optimizer=actor_optimizer,
+                                          q_network=q_network, q_optimizer=q_optimizer, v_network=v_network,
+                                          v_optimizer=v_optimizer, discount=config.discount, tau=config.tau,
+                                          device=device, beta=config.beta, iql_tau=config.iql_tau, max_steps=n_off,
+                                          seed=seed))
+        if config.load_model != "":
+            trainers[k].load_state_dict(torch.load(config.load_model))
+    # what np.random.seed(seed_k) leaves numpy's global generator in, one generator per member
+    gens = [np.random.RandomState(seed) for seed in seeds]
+    from .multi import SeedGroup
+    # ONE launch sequence per step for all members (the two-stream split pays per call, and a tick is one step)
+    group = SeedGroup(trainers, mode="general" if trainers[0].step_kind(B) == "general" else "group")
+    if logger is None:
+        logger = _offline_loop.default_logger(config, K)
+    if on_start is not None:
+        on_start(trainers, buffers)
+
+    train_successes = [[] for _ in ks]
+    pending = []  # (first t, [K] device losses [n, 3], [K] lists of the online records of those steps, or None)
+
+    def flush():
+        for t0, losses, extras in pending:
+            for k, arr in enumerate(l.cpu().numpy() for l in losses):
+                for i, (v, q, a) in enumerate(arr.tolist()):
+                    t = t0 + i
+                    rec = {"value_loss": v, "q_loss": q, "actor_loss": a}
+                    rec["offline_iter" if t < n_off else "online_iter"] = t if t < n_off else t - n_off
+                    if extras is not None:
+                        rec.update(extras[k][i])
+                    logger(tagged(rec, k), t + 1)
+        pending.clear()
+
+    def evaluate(t):
+        """fref:736-767 after step t, member after member."""
+        flush()
+        group.synchronize()
+        print(f"Time steps: {t + 1}")
+        for k, seed in enumerate(seeds):
+            eval_scores, success_rate = eval_actor(eval_envs[k], trainers[k].actor, device=device,
+                                                   n_episodes=config.n_episodes, seed=seed)
+            eval_score = eval_scores.mean()
+            eval_log = {}
+            if t >= n_off and is_env_with_goal:
+                eval_log["eval/regret"] = np.mean(1 - np.array(train_successes[k]))
+                eval_log["eval/success_rate"] = success_rate
+            normalized_eval_score = normalized[k](eval_score) * 100.0
+            eval_log["eval/d4rl_normalized_score"] = normalized_eval_score
+            print("---------------------------------------")
+            print(f"Seed {seed}: evaluation over {config.n_episodes} episodes: {eval_score:.3f} , "
+                  f"D4RL score: {normalized_eval_score:.3f}")
+            print("---------------------------------------")
+            if ckpt_dirs[k] is not None:
+                torch.save(trainers[k].state_dict(), os.path.join(ckpt_dirs[k], f"checkpoint_{t}.pt"))
+            logger(tagged(eval_log, k), t + 1)
+
+    every = int(config.eval_freq)
+    states = [e.reset() for e in envs]
+    episode_return, episode_step, goal_achieved = [0] * K, [0] * K, [False] * K
+
+    # ---- offline pretraining ----
+    print("Offline pretraining")
+    offline_stream = NumpyIndexStream(device) if n_off > 0 else None
+    t = 0
+    while t < n_off:
+        nxt = min(n_off, t + int(chunk), (t // every + 1) * every)
+        idx = offline_stream.draw(buffers[0].index_bound(), nxt - t, B, gens)
+        losses = group.train_steps(buffers, nxt - t, B, indices=idx, return_losses=True)
+        flush()
+        pending.append((t, losses, None))
+        t = nxt
+        if t % every == 0:
+            evaluate(t - 1)
+
+    # ---- online tuning: one act, K environment steps, one append, one group step ----
+    if n_on > 0:
+        print("Online tuning")
+    online_stream = GrowingIndexStream(device) if n_on > 0 else None
+    chunk_idx, chunk_t0 = None, 0
+    for t in range(n_off, n_off + n_on):
+        tick = t - n_off
+        if chunk_idx is None or tick - chunk_t0 >= chunk_idx[0].shape[0]:
+            flush()
+            n = min(max(1, int(online_chunk)), n_on - tick)
+            hi0 = [min(b.index_bound() + 1, int(config.buffer_size)) for b in buffers]
+            chunk_idx, chunk_t0 = online_stream.draw(hi0, int(config.buffer_size), n, B, generators=gens), tick
+        eps = None if exploration_noise is None else \
+            torch.as_tensor(np.asarray(exploration_noise(tick))).reshape(K, action_dim)
+        actions = explore_actions(trainers, np.asarray(states).reshape(K, -1), eps, expl_noise=config.expl_noise,
+                                  noise_clip=config.noise_clip, batch_size=B).cpu().numpy()
+        online_logs, rewards, next_states, real_dones, after = [], [], [], [], []
+        for k in ks:
+            online_log = {}
+            episode_step[k] += 1
+            next_state, reward, done, env_infos = envs[k].step(actions[k])
+            if not goal_achieved[k]:
+                goal_achieved[k] = is_goal_reached(reward, env_infos)
+            episode_return[k] += reward
+            real_dones.append(bool(done and episode_step[k] < max_steps))  # (a timeout is no terminal)
+            if config.normalize_reward:
+                reward = modify_reward_online(reward, config.env, **reward_mod_dict)
+            rewards.append(reward), next_states.append(next_state)
+            if done:
+                next_state = envs[k].reset()  # (the appended s' stays the one the step returned)
+                if is_env_with_goal:
+                    train_successes[k].append(goal_achieved[k])
+                    online_log["train/regret"] = np.mean(1 - np.array(train_successes[k]))
+                    online_log["train/is_success"] = float(goal_achieved[k])
+                online_log["train/episode_return"] = episode_return[k]
+                online_log["train/d4rl_normalized_episode_return"] = normalized[k](episode_return[k]) * 100.0
+                online_log["train/episode_length"] = episode_step[k]
+                episode_return[k], episode_step[k], goal_achieved[k] = 0, 0, False
+            online_logs.append([online_log])
+            after.append(next_state)
+        add_transitions(buffers, states, actions, rewards, next_states, real_dones)
+        states = after
+        j = tick - chunk_t0
+        losses = group.train_steps(buffers, 1, B, indices=[c[j:j + 1] for c in chunk_idx], return_losses=True)
+        pending.append((t, losses, online_logs))
+        if (t + 1) % every == 0:
+            evaluate(t)
+    flush()
+    group.synchronize()
+    group.close()
+    return trainers

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Cost of one online fine-tuning tick (iqlpref_amd.finetune) with a null environment.
 
-    python tools/bench_finetune.py [--ticks 2000] [--warmup 200] [--batch 256] [--rows 100000]
+    python tools/bench_finetune.py [--ticks 2000] [--warmup 200] [--batch 256] [--rows 100000] [--seeds K]
 
 A tick is what ``finetune.train`` does per online step: ``explore_action`` and its copy to the host (the
 environment needs the action), ``add_transition``, one ``train_steps(n_steps=1)`` on pre-drawn indices.  The
@@ -9,6 +9,10 @@ environment is null: the next state is a fixed array.  Prints one JSON line: mic
 into act / append / step (each timed on the host around its own call, with a device synchronisation after the
 step so that the three add up to the tick), and beside them the microseconds of a bare ``train_steps(n_steps=1)``
 call in a loop on the same trainer -- the floor the tick cannot go under.
+
+``--seeds K`` (K > 1) times the tick of ``finetune.train(seeds_per_gpu=K)`` instead: ``explore_actions`` and its
+one copy to the host, ``add_transitions``, one ``SeedGroup.train_steps(n_steps=1)`` on K rings -- the same three
+parts, each once for all K members -- and adds ``seed_ticks_per_s`` = K / tick.
 """
 import argparse
 import json
@@ -32,7 +36,10 @@ def main():
     ap.add_argument("--rows", type=int, default=100000)
     ap.add_argument("--state-dim", type=int, default=17)
     ap.add_argument("--action-dim", type=int, default=6)
+    ap.add_argument("--seeds", type=int, default=1)
     args = ap.parse_args()
+    if args.seeds > 1:
+        return main_group(args)
     dev, S, A, B = "cuda:0", args.state_dim, args.action_dim, args.batch
     total = args.warmup + args.ticks
     rng = np.random.default_rng(0)
@@ -80,6 +87,64 @@ def main():
     print(json.dumps({"tool": "bench_finetune", "build_tag": _lib.build_tag(), "ticks": args.ticks, "batch": B,
                       "state_dim": S, "action_dim": A, "tick_us": us(t_act + t_app + t_step), "act_us": us(t_act),
                       "append_us": us(t_app), "step_us": us(t_step), "bare_train_step_us": round(1e6 * floor, 2)}))
+
+
+def main_group(args):
+    from iqlpref_amd.multi import SeedGroup
+    dev, S, A, B, K = "cuda:0", args.state_dim, args.action_dim, args.batch, args.seeds
+    total = args.warmup + args.ticks
+    rng = np.random.default_rng(0)
+    data = {"observations": rng.standard_normal((args.rows, S)).astype(np.float32),
+            "actions": rng.uniform(-1, 1, (args.rows, A)).astype(np.float32),
+            "rewards": rng.standard_normal(args.rows).astype(np.float32),
+            "next_observations": rng.standard_normal((args.rows, S)).astype(np.float32),
+            "terminals": (rng.uniform(size=args.rows) < 0.01).astype(np.float32)}
+    trs, bufs = [], []
+    for k in range(K):
+        torch.manual_seed(k)
+        q, v, actor = ia.TwinQ(S, A).to(dev), ia.ValueFunction(S).to(dev), ia.GaussianPolicy(S, A, 1.0).to(dev)
+        trs.append(ft.ImplicitQLearning(1.0, actor, torch.optim.Adam(actor.parameters(), lr=3e-4), q,
+                                        torch.optim.Adam(q.parameters(), lr=3e-4), v,
+                                        torch.optim.Adam(v.parameters(), lr=3e-4), max_steps=10 ** 6, device=dev, seed=k))
+        bufs.append(ft.ReplayBuffer(S, A, args.rows + total // 2, dev))
+        bufs[k].load_d4rl_dataset(data)
+    group = SeedGroup(trs, mode="group")  # (what finetune.train steps its members with)
+    gens = [np.random.RandomState(k) for k in range(K)]
+    cap = bufs[0]._buffer_size
+    idx = ft.GrowingIndexStream(dev).draw(min(bufs[0].index_bound() + 1, cap), cap, total, B, generators=gens)
+    states = rng.standard_normal((K, S))
+    nxt = list(rng.standard_normal((K, S)))
+    rewards, dones = [0.5] * K, [False] * K
+    t_act = t_app = t_step = 0.0
+    for i in range(total):
+        if i == args.warmup:
+            torch.cuda.synchronize()
+            t_act = t_app = t_step = 0.0
+        t0 = time.perf_counter()
+        actions = ft.explore_actions(trs, states, None, expl_noise=0.03, noise_clip=0.5, batch_size=B).cpu().numpy()
+        t1 = time.perf_counter()
+        ft.add_transitions(bufs, states, actions, rewards, nxt, dones)
+        t2 = time.perf_counter()
+        group.train_steps(bufs, 1, B, indices=[x[i:i + 1] for x in idx], return_losses=False)
+        torch.cuda.synchronize()
+        t3 = time.perf_counter()
+        t_act, t_app, t_step = t_act + t1 - t0, t_app + t2 - t1, t_step + t3 - t2
+    floor_idx = [x[:1] for x in idx]
+    for _ in range(args.warmup):
+        group.train_steps(bufs, 1, B, indices=floor_idx, return_losses=False)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(args.ticks):
+        group.train_steps(bufs, 1, B, indices=floor_idx, return_losses=False)
+    torch.cuda.synchronize()
+    floor = (time.perf_counter() - t0) / args.ticks
+    us = lambda x: round(1e6 * x / args.ticks, 2)
+    tick = (t_act + t_app + t_step) / args.ticks
+    print(json.dumps({"tool": "bench_finetune", "build_tag": _lib.build_tag(), "seeds": K, "ticks": args.ticks, "batch": B,
+                      "state_dim": S, "action_dim": A, "tick_us": us(t_act + t_app + t_step), "act_us": us(t_act),
+                      "append_us": us(t_app), "step_us": us(t_step), "bare_train_step_us": round(1e6 * floor, 2),
+                      "seed_ticks_per_s": round(K / tick, 1)}))
+    group.close()
 
 
 if __name__ == "__main__":
