@@ -47,8 +47,10 @@ const char *iqlhip_build_tag(void);
 /* Shape envelope (everything outside returns IQLHIP_ERR_UNSUPPORTED with a   */
 /* message; every YAML under the reference's configs/offline/iql/ fits):      */
 /*   trainer   ReLU hidden activations, one width for all hidden layers,       */
-/*             n_hidden 1..6, hidden_dim 1..1024, batch_size a multiple of 16  */
-/*             (a step may count fewer rows: iqlhip_train_steps_valid),        */
+/*             n_hidden 1..6, hidden_dim 1..1024, any batch_size >= 1 (the     */
+/*             kernels pad it to whole 16-row slabs and count only the real    */
+/*             rows; every array of the caller keeps batch_size rows; a step   */
+/*             may count fewer rows still: iqlhip_train_steps_valid),          */
 /*             state_dim + action_dim <= 128, action_dim <= 32, 2..8 critics,  */
 /*             plain Adam (no weight decay / amsgrad), one (beta1, beta2, eps) */
 /*             for the three optimisers.  n_hidden = 2 with hidden_dim 64, 128 */
@@ -172,7 +174,7 @@ int iqlhip_replay_sample(const iqlhip_replay_view *view, int32_t batch,
 typedef struct {
   int32_t state_dim, action_dim;
   int32_t hidden_dim;    /* 1..1024 (ref:417-449 MLP: one width for all hidden layers) */
-  int32_t batch_size;    /* multiple of 16                                        */
+  int32_t batch_size;    /* any batch_size >= 1 (padded to 16 rows inside)        */
   int32_t deterministic; /* 1: DeterministicPolicy (ref:485), 0: Gaussian (ref:452)*/
   int32_t precision;     /* IQLHIP_PREC_*                                         */
   float dropout_p;       /* actor dropout (ref:436-437); < 0 = none               */

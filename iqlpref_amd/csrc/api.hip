@@ -40,7 +40,8 @@ hipError_t launch_stage(bool, const TrainerDesc &, const TrainerDesc *, const De
 int strip_rows();
 int update_lds_floats();
 hipError_t launch_update(bool, const TrainerDesc *, const DevArgs *, DevCtr *, const UpdItem *, int,
-                         int n_seeds, hipStream_t);
+                         int n_seeds, hipStream_t, bool padded = false);
+hipError_t launch_pad_rows(const void *src, void *dst, int64_t n, int rows, int rows_padded, int row_bytes, hipStream_t);
 hipError_t launch_sync_weights(bool, const TrainerDesc *, hipStream_t);
 hipError_t prepare_step_kernels();
 
@@ -483,6 +484,11 @@ struct iqlhip_trainer {
   struct iqlhip_group *group = nullptr;
 
   float *batch_rows = nullptr;  // [B][stride] staging for iqlhip_train_batch
+  // a batch_size that is no multiple of 16 (tuned step): the kernels index idx[] and drop_keep[] with their
+  // padded row count D.B, the caller's arrays have batch_size rows a step -- copies with D.B rows a step, for
+  // one chunk of a call's steps at a time (pad_inputs); grown on demand
+  void *pad_idx = nullptr, *pad_keep = nullptr;
+  size_t pad_idx_bytes = 0, pad_keep_bytes = 0;
   int64_t total_it = 0;
   double lr_q, lr_v, lr_a_base;
   StepQueue queue;  // of the trainer's own calls (K = 1)
@@ -510,12 +516,12 @@ static int check_cfg(const iqlhip_trainer_config *c) {
   if (c->n_hidden < 0) return fail(IQLHIP_ERR_INVALID, "n_hidden must be >= 0");
   if (const char *why = nullptr; !deep_shape_ok(*c, n_hidden(*c), &why))
     return fail(IQLHIP_ERR_UNSUPPORTED, "n_hidden %d, hidden_dim %d: %s", n_hidden(*c), c->hidden_dim, why);
-  if (c->batch_size < 16 || c->batch_size % 16)
-    return fail(IQLHIP_ERR_UNSUPPORTED, "batch_size %d: must be a positive multiple of 16", c->batch_size);
+  if (c->batch_size < 1) return fail(IQLHIP_ERR_INVALID, "batch_size %d: must be >= 1", c->batch_size);
+  if (c->batch_size > (1 << 24)) return fail(IQLHIP_ERR_UNSUPPORTED, "batch_size %d: at most 2^24", c->batch_size);
   if (c->action_dim > 32) return fail(IQLHIP_ERR_UNSUPPORTED, "action_dim %d > 32", c->action_dim);
   if (c->state_dim + c->action_dim > 128) return fail(IQLHIP_ERR_UNSUPPORTED, "state_dim+action_dim > 128");
   // the misc block of k_update sums the per-slab loss partials in its LDS
-  if (!is_deep(*c) && (c->batch_size / 16) * (n_critics(*c) + 2 + (c->deterministic ? 0 : c->action_dim)) + n_critics(*c) + 2 >
+  if (!is_deep(*c) && (round_up(c->batch_size, 16) / 16) * (n_critics(*c) + 2 + (c->deterministic ? 0 : c->action_dim)) + n_critics(*c) + 2 >
       update_lds_floats())
     return fail(IQLHIP_ERR_UNSUPPORTED, "batch_size %d too large for action_dim %d", c->batch_size,
                 c->action_dim);
@@ -732,11 +738,13 @@ extern "C" int iqlhip_trainer_create(iqlhip_trainer **out, const iqlhip_trainer_
     *out = t;
     return 0;
   }
-  const int S = cfg->state_dim, A = cfg->action_dim, H = cfg->hidden_dim, B = cfg->batch_size;
+  // B: the rows every kernel works on, batch_size rounded up to whole 16-row slabs; rows [batch_size, B) are
+  // padding, gathered like the others and kept out of the losses by the counted kernels (D.NB)
+  const int S = cfg->state_dim, A = cfg->action_dim, H = cfg->hidden_dim, B = round_up(cfg->batch_size, 16);
   const int es = t->bf16 ? 2 : 4, KM = t->bf16 ? 32 : 16;
   TrainerDesc &D = t->D;
   memset(&D, 0, sizeof(D));
-  D.S = S, D.A = A, D.H = H, D.B = B, D.BP = round_up(B, 32);
+  D.S = S, D.A = A, D.H = H, D.B = B, D.BP = round_up(B, 32), D.NB = cfg->batch_size;
   const int E = n_critics(*cfg), NT = E + 2, NF = 2 * E + 3;
   D.E = E, D.ntrain = NT, D.nfwd = NF, D.net_v = E, D.net_a = E + 1;
   D.out_v = E, D.out_qt = E + 1, D.out_nv = 2 * E + 1, D.out_mean = 2 * E + 2;
@@ -962,6 +970,8 @@ extern "C" int iqlhip_trainer_destroy(iqlhip_trainer *t) {
     t->deep_ring.destroy();
   }
   if (t->ws) (void)hipFree(t->ws);
+  if (t->pad_idx) (void)hipFree(t->pad_idx);
+  if (t->pad_keep) (void)hipFree(t->pad_keep);
   delete t;
   return 0;
 }
@@ -1060,9 +1070,11 @@ static int enqueue_step(const StepTarget &x, bool counts, hipStream_t st, hipEve
   if (ev) HIP_TRY(hipEventRecord(ev[0], st));
   HIP_TRY(launch_forward(x.bf16, x.D, x.desc, x.args, x.ctr, x.K, st));
   if (ev) HIP_TRY(hipEventRecord(ev[1], st));
-  HIP_TRY(launch_backward(x.bf16, x.D, x.desc, x.args, x.ctr, x.K, st, counts));
+  // (a padded batch -- the members of a group share the shape -- takes the counted kernels in every call)
+  const bool padded = x.D.NB != x.D.B;
+  HIP_TRY(launch_backward(x.bf16, x.D, x.desc, x.args, x.ctr, x.K, st, counts || padded));
   if (ev) HIP_TRY(hipEventRecord(ev[2], st));
-  HIP_TRY(launch_update(x.bf16, x.desc, x.args, x.ctr, x.items, x.n_items, x.K, st));
+  HIP_TRY(launch_update(x.bf16, x.desc, x.args, x.ctr, x.items, x.n_items, x.K, st, padded));
   if (ev) HIP_TRY(hipEventRecord(ev[3], st));
   return 0;
 }
@@ -1193,6 +1205,43 @@ static int check_view(const iqlhip_replay_view &v, const iqlhip_trainer_config &
   return 0;
 }
 
+// A padded batch on the tuned step (batch_size no multiple of 16: D.NB < D.B).  The caller's idx[] and
+// drop_keep[] have batch_size rows a step and the kernels index D.B rows a step, so the steps of a call go
+// through copies with D.B rows a step, a chunk of at most pad_chunk() steps at a time: row r < batch_size of a
+// step is the caller's, every padding row repeats row 0 of its step (an index the caller gave: in range; a
+// mask row: never counted).  Nothing is read beyond the caller's arrays.  On-device indices and masks need
+// no copy: a padding row draws the Philox index / mask words of its own row number.
+static bool is_padded(const iqlhip_trainer *t) { return !t->deep && t->D.NB != t->D.B; }
+static int64_t pad_chunk(const iqlhip_trainer *t, bool idx, bool keep) {
+  if (!is_padded(t) || (!idx && !keep)) return INT64_MAX;
+  const size_t per_step = (idx ? (size_t)t->D.B * 8 : 0) + (keep ? (size_t)2 * t->D.B * t->D.H : 0);
+  const size_t budget = (size_t)32 << 20;
+  return budget / per_step > 0 ? (int64_t)(budget / per_step) : 1;
+}
+static int pad_grow(void **buf, size_t *have, size_t want) {
+  if (*have >= want) return 0;
+  if (*buf) HIP_TRY(hipFree(*buf));  // (waits for the device: nothing in flight reads the old copy)
+  *buf = nullptr, *have = 0;
+  if (hipMalloc(buf, want) != hipSuccess) return fail(IQLHIP_ERR_NOMEM, "hipMalloc of %zu bytes (padded batch) failed", want);
+  *have = want;
+  return 0;
+}
+static int pad_inputs(iqlhip_trainer *t, DevArgs &a, hipStream_t st) {
+  if (!is_padded(t)) return 0;
+  const int NB = t->D.NB, B = t->D.B, H = t->D.H;
+  if (a.idx_mode == 1) {
+    if (int rc = pad_grow(&t->pad_idx, &t->pad_idx_bytes, (size_t)a.n_steps * B * 8)) return rc;
+    HIP_TRY(launch_pad_rows(a.idx, t->pad_idx, a.n_steps, NB, B, 8, st));
+    a.idx = reinterpret_cast<const int64_t *>(t->pad_idx);
+  }
+  if (a.drop_keep) {
+    if (int rc = pad_grow(&t->pad_keep, &t->pad_keep_bytes, (size_t)a.n_steps * 2 * B * H)) return rc;
+    HIP_TRY(launch_pad_rows(a.drop_keep, t->pad_keep, a.n_steps * 2, NB, B, H, st));
+    a.drop_keep = reinterpret_cast<const uint8_t *>(t->pad_keep);
+  }
+  return 0;
+}
+
 // the arguments of n_steps steps of trainer t from where it stands
 static DevArgs make_args(const iqlhip_trainer *t, const iqlhip_replay_view &v, int64_t n_steps, const int64_t *idx,
                          const int32_t *n_valid, const uint8_t *dropout_keep, float *losses_out) {
@@ -1233,10 +1282,19 @@ extern "C" int iqlhip_train_steps_valid(iqlhip_trainer *t, const iqlhip_replay_v
   if (!t || !view || !view->rows) return fail(IQLHIP_ERR_INVALID, "null argument");
   if (n_steps < 0) return fail(IQLHIP_ERR_INVALID, "n_steps must be >= 0");
   if (int rc = check_view(*view, t->cfg)) return rc;
-  if (n_steps == 0) return 0;
-  const DevArgs a = make_args(t, *view, n_steps, idx, n_valid, dropout_keep, losses_out);
-  if (int rc = run_solo(t, a, graph_unroll, (hipStream_t)stream)) return rc;
-  t->total_it += n_steps;
+  // (one pass, but for a padded batch with injected indices or masks: pad_inputs)
+  const int64_t chunk = pad_chunk(t, idx != nullptr, dropout_keep != nullptr);
+  const int64_t NB = t->cfg.batch_size, keep_step = (int64_t)n_hidden(t->cfg) * NB * t->cfg.hidden_dim;
+  for (int64_t done = 0; done < n_steps;) {
+    const int64_t n = std::min(chunk, n_steps - done);
+    DevArgs a = make_args(t, *view, n, idx ? idx + done * NB : nullptr, n_valid ? n_valid + done : nullptr,
+                          dropout_keep ? dropout_keep + done * keep_step : nullptr,
+                          losses_out ? losses_out + done * 3 : nullptr);
+    if (int rc = pad_inputs(t, a, (hipStream_t)stream)) return rc;
+    if (int rc = run_solo(t, a, graph_unroll, (hipStream_t)stream)) return rc;
+    t->total_it += n;
+    done += n;
+  }
   return 0;
 }
 
@@ -1249,7 +1307,8 @@ extern "C" int iqlhip_train_batch(iqlhip_trainer *t, const float *s, const float
   HIP_TRY(launch_pack(t->batch_rows, stride, S, A, 0, B, s, a, r, s2, d, (hipStream_t)stream));
   const iqlhip_replay_view rows = {t->batch_rows, B, stride, S, A, 0};
   DevArgs args = make_args(t, rows, 1, nullptr, nullptr, dropout_keep, losses_out);
-  args.idx_mode = 2;  // the rows as they lie
+  args.idx_mode = 2;  // the rows as they lie (a padding row: clamped to the last one)
+  if (int rc = pad_inputs(t, args, (hipStream_t)stream)) return rc;
   if (int rc = run_solo(t, args, 0, (hipStream_t)stream)) return rc;
   t->total_it += 1;
   return 0;
@@ -1438,21 +1497,32 @@ extern "C" int iqlhip_group_train_steps_valid(iqlhip_group *g, const iqlhip_repl
     if (!views[k].rows) return fail(IQLHIP_ERR_INVALID, "null replay view %d", k);
     if (int rc = check_view(views[k], g->tr[k]->cfg)) return rc;
   }
-  if (n_steps == 0) return 0;
-  DevArgs want[IQLHIP_MAX_GROUP];
-  for (int k = 0; k < g->K; ++k) {
-    iqlhip_trainer *t = g->tr[k];
-    want[k] = make_args(t, views[k], n_steps, idx ? idx[k] : nullptr, n_valid ? n_valid[k] : nullptr,
-                        dropout_keep ? dropout_keep[k] : nullptr, losses_out ? losses_out[k] : nullptr);
-    t->queue.dev_args_valid = false;  // a member's own next call starts from scratch
-  }
   const iqlhip_trainer *t0 = g->tr[0];
+  // (one pass, but for a padded batch with injected indices or masks: pad_inputs, every member's own copies)
+  int64_t chunk = INT64_MAX;
+  for (int k = 0; k < g->K; ++k)
+    chunk = std::min(chunk, pad_chunk(g->tr[k], idx && idx[k], dropout_keep && dropout_keep[k]));
+  const int64_t NB = t0->cfg.batch_size, keep_step = (int64_t)n_hidden(t0->cfg) * NB * t0->cfg.hidden_dim;
   const StepTarget x = {t0->bf16, t0->D, g->gdesc, g->gargs, g->gctr, g->gitems, g->n_items, g->K};
-  const int rc = g->deep ? deep_run({g->tr, g->K, &g->deep_ring, g->gdeep, g->queue}, want, n_steps, graph_unroll,
-                                    (hipStream_t)stream)
-                         : run_tuned(g->queue, x, want, n_steps, graph_unroll, counts, (hipStream_t)stream);
-  if (rc) return rc;
-  for (int k = 0; k < g->K; ++k) g->tr[k]->total_it += n_steps;
+  for (int64_t done = 0; done < n_steps;) {
+    const int64_t n = std::min(chunk, n_steps - done);
+    DevArgs want[IQLHIP_MAX_GROUP];
+    for (int k = 0; k < g->K; ++k) {
+      iqlhip_trainer *t = g->tr[k];
+      want[k] = make_args(t, views[k], n, idx && idx[k] ? idx[k] + done * NB : nullptr,
+                          n_valid && n_valid[k] ? n_valid[k] + done : nullptr,
+                          dropout_keep && dropout_keep[k] ? dropout_keep[k] + done * keep_step : nullptr,
+                          losses_out && losses_out[k] ? losses_out[k] + done * 3 : nullptr);
+      if (int rc = pad_inputs(t, want[k], (hipStream_t)stream)) return rc;
+      t->queue.dev_args_valid = false;  // a member's own next call starts from scratch
+    }
+    const int rc = g->deep ? deep_run({g->tr, g->K, &g->deep_ring, g->gdeep, g->queue}, want, n, graph_unroll,
+                                      (hipStream_t)stream)
+                           : run_tuned(g->queue, x, want, n, graph_unroll, counts, (hipStream_t)stream);
+    if (rc) return rc;
+    for (int k = 0; k < g->K; ++k) g->tr[k]->total_it += n;
+    done += n;
+  }
   return 0;
 }
 

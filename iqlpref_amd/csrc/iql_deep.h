@@ -47,7 +47,10 @@ struct DeepDesc {
   int32_t E, ntrain, nfwd, net_v, net_a;
   int32_t out_v, out_qt, out_nv, out_mean;
   int32_t next_off, opad, nslab, lds_w;   // lds_w: elements per LDS activation row (widest layer + pad)
-  int32_t deterministic, has_dropout, polyak_convex, pad0_;
+  int32_t deterministic, has_dropout, polyak_convex;
+  int32_t NB;  // rows of the batch that count = the caller's batch_size; B = NB rounded up to whole 16-row slabs,
+               // rows [NB, B) are padding: gathered and computed like the others, masked out of the loss head.
+               // The caller's idx[] / drop_keep[] have NB rows a step.
   float two_over_B, inv_E;
   float discount, tau, beta, iql_tau, one_m_tau, drop_scale;
   uint32_t drop_thr, pad1_;
@@ -73,8 +76,8 @@ struct alignas(128) DeepArgs {
   int64_t n_rows;
   int32_t row_stride;
   int32_t idx_mode;          // 0 philox, 1 injected, 2 identity
-  const int64_t *idx;        // [n_steps][B] when idx_mode == 1
-  const uint8_t *drop_keep;  // [n_steps][n_hidden][B][H] or null (philox masks)
+  const int64_t *idx;        // [n_steps][NB] when idx_mode == 1
+  const uint8_t *drop_keep;  // [n_steps][n_hidden][NB][H] or null (philox masks)
   float *losses_out;         // [n_steps][3] or null
   int64_t base_step;         // total_it before the first of these steps
   int64_t n_steps;
@@ -94,8 +97,8 @@ struct DeepStep {
   int64_t n_rows;
   int32_t row_stride;
   int32_t idx_mode;
-  const int64_t *idx;        // [B] of THIS step when idx_mode == 1
-  const uint8_t *drop_keep;  // [n_hidden][B][H] of THIS step, or null
+  const int64_t *idx;        // [NB] of THIS step when idx_mode == 1
+  const uint8_t *drop_keep;  // [n_hidden][NB][H] of THIS step, or null
   float *losses_out;         // [3] of THIS step, or null
   int64_t step;              // total_it before this step
 };

@@ -86,9 +86,13 @@ __device__ __forceinline__ void deep_keep4(const DeepDesc &D, const DeepStep &A,
     return;
   }
   if (A.drop_keep) {
-    const uint8_t *m = A.drop_keep + ((size_t)l * D.B + (size_t)rowblk * 4) * D.H + col;
+    // (the caller's mask has NB rows: a padding row, never counted, reads the last one)
+    const uint8_t *m = A.drop_keep + (size_t)l * D.NB * D.H + col;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) keep[i] = ldg(m + (size_t)i * D.H) != 0;
+    for (int i = 0; i < 4; ++i) {
+      const int row = rowblk * 4 + i;
+      keep[i] = ldg(m + (size_t)(row < D.NB ? row : D.NB - 1) * D.H) != 0;
+    }
   } else {
     const Philox4 ph = philox4x32_10((uint32_t)(rowblk * D.H + col), (uint32_t)A.step,
                                      (uint32_t)((uint64_t)A.step >> 32), drop_stream(l), (uint32_t)D.seed,
@@ -223,7 +227,7 @@ __device__ __forceinline__ void deep_layers(const DeepDesc &D, const DeepEval &N
 __device__ __forceinline__ int64_t deep_row_index(const DeepDesc &D, const DeepStep &A, int row) {
   int64_t ix;
   if (A.idx_mode == 1)
-    ix = ldg(A.idx + row);
+    ix = ldg(A.idx + (row < D.NB ? row : 0));  // (a padding row: the step's first index, in range)
   else if (A.idx_mode == 2)
     ix = row;
   else
@@ -246,8 +250,8 @@ __device__ __forceinline__ DeepStep deep_step_of(const DeepDesc &D, const DeepAr
   const int64_t i = deep_step_off(G, step);
   DeepStep s;
   s.rows = G.rows, s.n_rows = G.n_rows, s.row_stride = G.row_stride, s.idx_mode = G.idx_mode;
-  s.idx = G.idx ? G.idx + i * D.B : nullptr;
-  s.drop_keep = G.drop_keep ? G.drop_keep + i * (int64_t)(D.NL - 1) * D.B * D.H : nullptr;
+  s.idx = G.idx ? G.idx + i * D.NB : nullptr;
+  s.drop_keep = G.drop_keep ? G.drop_keep + i * (int64_t)(D.NL - 1) * D.NB * D.H : nullptr;
   s.losses_out = G.losses_out ? G.losses_out + i * 3 : nullptr;
   s.step = step;
   return s;
@@ -366,7 +370,10 @@ __global__ __launch_bounds__(THREADS) void kd_backward(const DeepDesc *__restric
   if (wave == 0) {
     const int E = D.E, Aq = D.A, odim = N.N[L];
     const float *outs = D.outs;
-    const float fB = (float)D.B;
+    // the batch means run over the NB rows that count: the padding rows of the last slab give no loss term and
+    // no gradient
+    const int NB = D.NB;
+    const float fB = (float)NB;
     float lsum = 0.f;
     for (int nt = 0; nt < N.Npad[L] / 16; ++nt) {
       const int j = nt * 16 + r16, jc = j < Aq ? j : Aq - 1;
@@ -388,9 +395,10 @@ __global__ __launch_bounds__(THREADS) void kd_backward(const DeepDesc *__restric
         x.rew = ldg(D.rd + (size_t)b * 2), x.done = ldg(D.rd + (size_t)b * 2 + 1);
         float d3, lt, g;
         loss_terms<BF16>(D, net, x, fB, d3, lt, g);
-        dz[i] = valid ? d3 : 0.f;
-        lsum += valid ? lt : 0.f;
-        gs += valid ? g : 0.f;
+        const bool live = valid && b < NB;
+        dz[i] = live ? d3 : 0.f;
+        lsum += live ? lt : 0.f;
+        gs += live ? g : 0.f;
         dzin[(size_t)(4 * q + i) * ldw + j] = P::from_f32(dz[i]);
       }
       put4T<BF16>(reinterpret_cast<T *>(N.dzT[L]) + (size_t)j * BP + row0 + 4 * q, dz);
@@ -468,7 +476,7 @@ __device__ __forceinline__ void deep_misc(const DeepDesc &D, const DeepArgs &G, 
   __shared__ float lm[MAX_TRAIN];
   const int tid = threadIdx.x, nslab = D.nslab;
   if (tid < D.ntrain) {
-    lm[tid] = ordered_sum(D.lossp + (size_t)tid * nslab, 1, nslab) / (float)D.B;
+    lm[tid] = ordered_sum(D.lossp + (size_t)tid * nslab, 1, nslab) / (float)D.NB;
   }
   __syncthreads();
   if (tid == 0 && G.losses_out) {
@@ -726,7 +734,8 @@ hipError_t deep_create(DeepTrainer **out, const iqlhip_trainer_config &cfg, int 
   const int es = t->bf16 ? 2 : 4, KM = t->bf16 ? 32 : 16, EPV = t->bf16 ? 8 : 4;
   DeepDesc &D = t->D;
   memset(&D, 0, sizeof(D));
-  const int S = cfg.state_dim, A = cfg.action_dim, H = cfg.hidden_dim, B = cfg.batch_size;
+  // B: the rows the kernels work on (whole 16-row slabs); NB = batch_size of them count
+  const int S = cfg.state_dim, A = cfg.action_dim, H = cfg.hidden_dim, B = round_up(cfg.batch_size, 16);
   const int E = cfg.n_critics > 0 ? cfg.n_critics : 2, NT = E + 2, NF = 2 * E + 3, NL = n_hidden + 1;
   D.S = S, D.A = A, D.H = H, D.Hp = round_up(H, 32), D.B = B, D.BP = round_up(B, 32), D.NL = NL;
   D.E = E, D.ntrain = NT, D.nfwd = NF, D.net_v = E, D.net_a = E + 1;
@@ -734,9 +743,9 @@ hipError_t deep_create(DeepTrainer **out, const iqlhip_trainer_config &cfg, int 
   D.OUTW = round_up(D.out_mean + A, 4);
   D.next_off = round_up(S + A + 2, 4);
   D.opad = round_up(A, 16);
-  D.nslab = B / 16;
+  D.nslab = B / 16, D.NB = cfg.batch_size;
   D.deterministic = cfg.deterministic, D.has_dropout = cfg.dropout_p > 0.f, D.polyak_convex = cfg.polyak_form == 1;
-  D.two_over_B = 2.0f / (float)B, D.inv_E = 1.0f / (float)E;
+  D.two_over_B = 2.0f / (float)D.NB, D.inv_E = 1.0f / (float)E;
   D.discount = cfg.discount, D.tau = cfg.tau, D.beta = cfg.beta, D.iql_tau = cfg.iql_tau;
   D.one_m_tau = (float)(1.0 - (double)cfg.tau);
   if (D.has_dropout) {

@@ -58,7 +58,8 @@ struct TrainerDesc {
   float one_m_tau;       // float(1 - tau) for the convex Polyak form
   float drop_scale;      // 1/(1-p), bf16-rounded in bf16 mode (ATen _dropout_impl)
   uint32_t drop_thr;     // keep iff philox word >= thr
-  int32_t pad0_;
+  int32_t NB;            // rows of the batch that count: the caller's batch_size; B is NB rounded up to 16 and
+                         // rows [NB, B) are padding (read by the counted kernels only: k_backward NV, k_update CNT)
   uint64_t seed;
   // workspace (T = compute type)
   float *stage_rows;  // [B][stage_stride] the batch of the step about to run (k_stage / k_update)
@@ -91,7 +92,7 @@ struct DevArgs {
   int64_t n_rows;
   int32_t row_stride;
   int32_t idx_mode;          // 0 philox, 1 injected, 2 identity (explicit batch)
-  const int64_t *idx;        // [n][B] when idx_mode == 1
+  const int64_t *idx;        // [n][B] when idx_mode == 1 (a padded batch: the trainer's padded copy, api.hip)
   const uint8_t *drop_keep;  // [n][2][B][H] or null (philox masks)
   float *losses_out;         // [n][3] or null
   int64_t base_step;         // total_it of the first step of this call

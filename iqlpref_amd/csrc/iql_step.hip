@@ -34,6 +34,8 @@
 // both operands of dW = dZ^T X are K(batch)-contiguous 16-byte fragments, and
 // the MFMA C/D layout (4 consecutive rows per lane) stores them with 8/16-byte
 // writes.
+#include <algorithm>
+
 #include "common.h"
 #include "iql_step.h"
 #include "step_math.h"
@@ -439,6 +441,19 @@ __global__ __launch_bounds__(256) void k_stage(const TrainerDesc *__restrict__ D
                                                const DevCtr *__restrict__ Cp) {
   Dp += blockIdx.y, Ap += blockIdx.y, Cp += blockIdx.y;
   stage_rows16<BF16>(*Dp, *Ap, Cp->ctr[0], blockIdx.x * 16, gridDim.x * 16, threadIdx.x);
+}
+
+// A padded batch (batch_size no multiple of 16; api.hip, pad_inputs): n blocks of `rows` rows of w8 x 8 bytes
+// become n blocks of `rows_padded` rows; the padding rows of a block repeat its row 0.  Reads nothing beyond
+// src[n][rows], writes nothing beyond dst[n][rows_padded].
+__global__ __launch_bounds__(256) void k_pad_rows(const uint2 *__restrict__ src, uint2 *__restrict__ dst, int64_t n,
+                                                  int rows, int rows_padded, int w8) {
+  const int64_t total = n * rows_padded * w8;
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+    const int64_t row = e / w8, blk = row / rows_padded;
+    const int w = (int)(e - row * w8), r = (int)(row - blk * rows_padded);
+    dst[e] = src[(blk * rows + (r < rows ? r : 0)) * w8 + w];
+  }
 }
 
 __device__ __forceinline__ void write_adam_coef(const TrainerDesc &D, const DevArgs &A, int64_t t1,
@@ -1156,6 +1171,10 @@ __global__ __launch_bounds__(256) void k_infer(const TrainerDesc *__restrict__ D
 // carries counts: the kernels of every other call do not read the pointer at all -- read through a
 // wave-uniform branch in the common instantiation, the one extra scalar load cost the one-seed latency
 // chain 0.2-1.8 % of the headline (three alternated pairs, spread of each side 0.5-1.1 %).
+// A batch_size that is no multiple of 16 runs on B = batch_size rounded up to 16 rows; the count is then
+// bounded by D.NB = batch_size instead of B (rows [NB, B) are padding: they never count), and the host picks
+// the counted instantiations (k_backward NV, the bf16 k_update CNT) for every call of such a trainer.  NB is
+// read by those instantiations alone.
 #define VALID_ROWS(nvp, A, step, B) ((nvp) ? clamp_rows(ldg((nvp) + ((step) - (A).base_step)), (B)) : (B))
 __device__ __forceinline__ int clamp_rows(int n, int B) { return n < 1 ? 1 : (n > B ? B : n); }
 
@@ -1321,7 +1340,7 @@ __device__ __forceinline__ void backward_body(const TrainerDesc *__restrict__ Dp
     const float *f = fin + lrow * FIN_LD;
     // the batch means divide by the step's valid rows (a whole batch: the same B and 2 / B as ever)
     int nv = B;
-    if constexpr (NV) nv = VALID_ROWS(g_nv, *Ap, Cp->ctr[0], B);
+    if constexpr (NV) nv = VALID_ROWS(g_nv, *Ap, Cp->ctr[0], D.NB);
     const float fB = (float)nv, two_over_B = nv == B ? D.two_over_B : 2.0f / fB;
     const bool live = !NV || brow < nv;
     LossIn lin;
@@ -1867,7 +1886,7 @@ constexpr int UPD_TILE = UTO * (UTI + 4) > USR * (UMAXI + 4) ? UTO * (UTI + 4) :
 // (the second region: a strip's new target weights, or -- group launches -- a layer-2 tile's)
 constexpr int UPD_LDS = UPD_TILE + (UTO * (UTI + 4) > USR * (UMAXI + 4) ? UTO * (UTI + 4) : USR * (UMAXI + 4));  // floats (~18 KB)
 
-template <bool BF16, bool LAT, int UT>
+template <bool BF16, bool LAT, int UT, bool CNT = false>
 __device__ __forceinline__ void update_body(const TrainerDesc *__restrict__ Dp,
                                             const DevArgs *__restrict__ Ap, DevCtr *__restrict__ Cp,
                                             const UpdItem *__restrict__ items, int n_items,
@@ -1931,9 +1950,10 @@ __device__ __forceinline__ void update_body(const TrainerDesc *__restrict__ Dp,
       const int n = tid - 64;
       float s = 0.f;
       for (int k = 0; k < nslab; ++k) s += sred[n * nslab + k];
-      // (counts are an fp32 feature: the bf16 kernel keeps the plain division)
+      // (per-step counts are an fp32 feature: the bf16 kernel keeps the plain division, but for its CNT
+      // instantiation, which divides by the rows of a padded batch that count)
       int nv = B;
-      if constexpr (!BF16) nv = VALID_ROWS(A.n_valid, A, t1 - 1, B);
+      if constexpr (!BF16 || CNT) nv = VALID_ROWS(A.n_valid, A, t1 - 1, D.NB);
       sred[nl + na + n] = s / (float)nv;
     }
     __syncthreads();
@@ -2566,7 +2586,7 @@ void k_backward(const TrainerDesc *__restrict__ Dp, const DevArgs *__restrict__ 
                                       ntrain);
 }
 
-template <bool BF16, bool LAT>
+template <bool BF16, bool LAT, bool CNT = false>
 __global__ __launch_bounds__(LAT ? 512 : 256, LAT ? 2 : (BF16 ? 4 : 3)) void k_update(const TrainerDesc *__restrict__ Dp,
                                                              const DevArgs *__restrict__ Ap,
                                                              DevCtr *__restrict__ Cp,
@@ -2574,7 +2594,7 @@ __global__ __launch_bounds__(LAT ? 512 : 256, LAT ? 2 : (BF16 ? 4 : 3)) void k_u
   // group launch: blockIdx.y = seed; grid.x is padded to a multiple of 8 (so that block -> XCD
   // stays blockIdx.x & 7 for every seed), the blocks behind the misc block have nothing to do
   if ((int)blockIdx.x > n_items) return;
-  update_body<BF16, LAT, (LAT ? 512 : 256)>(Dp + blockIdx.y, Ap + blockIdx.y, Cp + blockIdx.y,
+  update_body<BF16, LAT, (LAT ? 512 : 256), CNT>(Dp + blockIdx.y, Ap + blockIdx.y, Cp + blockIdx.y,
                          items + (size_t)blockIdx.y * n_items, n_items, (int)blockIdx.x);
 }
 
@@ -2661,7 +2681,8 @@ int fwd_parts_per_wg(int B, int H, int n_seeds) {
 // Launches with many rows (seed groups, batch-1024 ensembles) take the throughput kernels
 // k_forward_tp / k_backward_tp (bf16, H = 256, batch a multiple of 64).
 bool use_tp(bool bf16, const TrainerDesc &D, int n_seeds, bool backward) {
-  if (!bf16 || D.H != 256 || D.B % 64 != 0) return false;
+  // (a padded batch, NB < B, stays on the latency kernels: k_backward_tp has no counted instantiation)
+  if (!bf16 || D.H != 256 || D.B % 64 != 0 || D.NB != D.B) return false;
   // The throughput kernels are one eight-wave work-group per CU, all resident at once: they win while
   // their work-groups fill a good part of the 256 CUs and lose beyond them (two rounds) and far below
   // (nothing covers a lone work-group's latency).  Measured (round 4, d2 / g4;
@@ -2737,7 +2758,8 @@ int bwd_parts_per_wg(int B, int H, int n_seeds) {
 }
 hipError_t launch_backward(bool bf16, const TrainerDesc &D, const TrainerDesc *dD, const DevArgs *a,
                            DevCtr *c, int n_seeds, hipStream_t st, bool counts) {
-  // counts: the call carries per-step valid-row counts (fp32, one seed: api.hip checks) -> the NV kernels
+  // counts: the call carries per-step valid-row counts (fp32: api.hip checks) or the batch is padded (either
+  // precision) -> the NV kernels
   if (use_tp(bf16, D, n_seeds, true)) {
     const int nslab32 = D.B / 32;
     const int nxn = (D.ntrain <= 4 && nslab32 % 2 == 0) ? 2 : 1;  // XCDs per trained net
@@ -2763,21 +2785,19 @@ hipError_t launch_backward(bool bf16, const TrainerDesc &D, const TrainerDesc *d
     if (pre) LAUNCH_B(BF, HH, true, 1);                               \
     else LAUNCH_B(BF, HH, false, 1);                                  \
   } while (0)
-  if (counts && !bf16) {
-#define LAUNCH_V(HH, PRE_, PW_)                                                                                      \
-  hipLaunchKernelGGL((k_backward<false, HH, PRE_, PW_, true>), dim3(grid, n_seeds), dim3(256), sm, st, dD, a, c, D.B / SLAB, \
+  if (counts) {
+#define LAUNCH_V(BF, HH, PRE_, PW_)                                                                                  \
+  hipLaunchKernelGGL((k_backward<BF, HH, PRE_, PW_, true>), dim3(grid, n_seeds), dim3(256), sm, st, dD, a, c, D.B / SLAB, \
                      D.ntrain)
-#define CALL_V(HH)                                                    \
+#define CALL_V(BF, HH)                                                \
   do {                                                                \
     if constexpr (HH >= 128) {                                        \
-      if (pw == 2) { LAUNCH_V(HH, false, 2); break; }                 \
+      if (pw == 2) { LAUNCH_V(BF, HH, false, 2); break; }             \
     }                                                                 \
-    if (pre) LAUNCH_V(HH, true, 1);                                   \
-    else LAUNCH_V(HH, false, 1);                                      \
+    if (pre) LAUNCH_V(BF, HH, true, 1);                               \
+    else LAUNCH_V(BF, HH, false, 1);                                  \
   } while (0)
-    if (D.H == 256) CALL_V(256);
-    else if (D.H == 128) CALL_V(128);
-    else CALL_V(64);
+    DISPATCH_H(bf16, D.H, CALL_V);
 #undef CALL_V
 #undef LAUNCH_V
     return hipGetLastError();
@@ -2795,10 +2815,18 @@ hipError_t launch_stage(bool bf16, const TrainerDesc &D, const TrainerDesc *dD, 
     hipLaunchKernelGGL(k_stage<false>, dim3((D.B + 15) / 16, n_seeds), dim3(256), 0, st, dD, a, c);
   return hipGetLastError();
 }
+hipError_t launch_pad_rows(const void *src, void *dst, int64_t n, int rows, int rows_padded, int row_bytes,
+                           hipStream_t st) {
+  const int64_t total = n * rows_padded * (row_bytes / 8);  // (rows are int64 indices or H mask bytes: whole 8 bytes)
+  const int grid = (int)std::min<int64_t>((total + 255) / 256, 4096);
+  hipLaunchKernelGGL(k_pad_rows, dim3(grid), dim3(256), 0, st, reinterpret_cast<const uint2 *>(src),
+                     reinterpret_cast<uint2 *>(dst), n, rows, rows_padded, row_bytes / 8);
+  return hipGetLastError();
+}
 int strip_rows() { return USR; }
 int update_lds_floats() { return UPD_LDS; }
 hipError_t launch_update(bool bf16, const TrainerDesc *dD, const DevArgs *a, DevCtr *c,
-                         const UpdItem *items, int n_items, int n_seeds, hipStream_t st) {
+                         const UpdItem *items, int n_items, int n_seeds, hipStream_t st, bool padded) {
   // n_items tiles + the misc block; a group launch pads grid.x to a multiple of 8
   const dim3 grid(n_seeds > 1 ? round_up(n_items + 1, 8) : n_items + 1, n_seeds);
   // The 512-thread latency variant while a lone seed's work-groups have a CU each; the four-per-CU
@@ -2811,7 +2839,12 @@ hipError_t launch_update(bool bf16, const TrainerDesc *dD, const DevArgs *a, Dev
     return n;
   }();
   const bool lat = n_seeds == 1 && n_items + 1 <= cus + 1;
-  if (bf16 && !lat)
+  // padded: the batch has rows that do not count (D.NB < D.B); the fp32 kernels read the count as it is
+  if (bf16 && padded && !lat)
+    hipLaunchKernelGGL((k_update<true, false, true>), grid, dim3(256), 0, st, dD, a, c, items, n_items);
+  else if (bf16 && padded)
+    hipLaunchKernelGGL((k_update<true, true, true>), grid, dim3(512), 0, st, dD, a, c, items, n_items);
+  else if (bf16 && !lat)
     hipLaunchKernelGGL((k_update<true, false>), grid, dim3(256), 0, st, dD, a, c, items, n_items);
   else if (bf16)
     hipLaunchKernelGGL((k_update<true, true>), grid, dim3(512), 0, st, dD, a, c, items, n_items);
