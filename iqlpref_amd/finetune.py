@@ -23,6 +23,7 @@ all members go out as one launch sequence each; member k is bit for bit the run 
 
 gym, d4rl and wandb are imported only when ``train()`` is not handed what they would provide.
 """
+import contextlib
 import ctypes as C
 import math
 import os
@@ -203,44 +204,56 @@ class ReplayBuffer(_OfflineReplayBuffer):
         obs, act, nxt, rew, done = f(obs, (n, S)), f(act, (n, A)), f(nxt, (n, S)), f(rew, (n,)), f(done, (n,))
         if n > self._buffer_size:
             raise ValueError(f"{n} transitions do not fit a replay buffer of {self._buffer_size} rows")
-        if self._pointer >= self._buffer_size:  # (a dataset that filled the buffer: fref:173 indexes past the end)
-            raise IndexError(f"index {self._pointer} is out of bounds for a replay buffer of {self._buffer_size} rows")
-        with torch.cuda.device(self._dev):
+        with _appending([self], n), torch.cuda.device(self._dev):
             check(self._lib.iqlhip_replay_append(ptr(self._rows), self._stride, S, A, self._buffer_size, self._pointer, n,
                                                  ptr(obs), ptr(act), ptr(rew), ptr(nxt), ptr(done), stream_ptr()))
         for t in (obs, act, rew, nxt, done):
             t.record_stream(torch.cuda.current_stream(self._dev))
-        self._pointer, self._size = ring_advance(self._pointer, self._size, n, self._buffer_size)
-        _buffer_generation[0] += 1
-        self._generation = _buffer_generation[0]  # the rows changed: no prefetched batch survives
 
     def add_transition(self, state: np.ndarray, action: np.ndarray, reward: float, next_state: np.ndarray, done: bool):
         """fref:164-180: one pinned staging block, one copy, one launch; nothing waits on the host except for
         the previous call's copy out of the same block."""
         S, A = self._state_dim, self._action_dim
-        if self._pointer >= self._buffer_size:
-            raise IndexError(f"index {self._pointer} is out of bounds for a replay buffer of {self._buffer_size} rows")
-        if self._stage_free is not None:
-            self._stage_free.synchronize()
-        h = self._stage_host.numpy()
-        h[:S] = np.asarray(state, dtype=np.float32).reshape(S)
-        h[S:S + A] = np.asarray(action, dtype=np.float32).reshape(A)
-        h[S + A] = np.float32(reward)
-        h[S + A + 1:2 * S + A + 1] = np.asarray(next_state, dtype=np.float32).reshape(S)
-        h[2 * S + A + 1] = np.float32(done)
-        d = self._stage_dev
-        with torch.cuda.device(self._dev):
-            d.copy_(self._stage_host, non_blocking=True)
-            if self._stage_free is None:
-                self._stage_free = torch.cuda.Event()
-            self._stage_free.record()
-            base, sz = d.data_ptr(), 4
-            at = lambda off: C.c_void_p(base + off * sz)
-            check(self._lib.iqlhip_replay_append(ptr(self._rows), self._stride, S, A, self._buffer_size, self._pointer, 1,
-                                                 at(0), at(S), at(S + A), at(S + A + 1), at(2 * S + A + 1), stream_ptr()))
-        self._pointer, self._size = ring_advance(self._pointer, self._size, 1, self._buffer_size)
+        with _appending([self], 1):
+            if self._stage_free is not None:
+                self._stage_free.synchronize()
+            _stage(self._stage_host.numpy()[None], S, A, state, action, reward, next_state, done)
+            d = self._stage_dev
+            with torch.cuda.device(self._dev):
+                d.copy_(self._stage_host, non_blocking=True)
+                if self._stage_free is None:
+                    self._stage_free = torch.cuda.Event()
+                self._stage_free.record()
+                base, sz = d.data_ptr(), 4
+                at = lambda off: C.c_void_p(base + off * sz)
+                check(self._lib.iqlhip_replay_append(ptr(self._rows), self._stride, S, A, self._buffer_size, self._pointer,
+                                                     1, at(0), at(S), at(S + A), at(S + A + 1), at(2 * S + A + 1),
+                                                     stream_ptr()))
+
+
+def _stage(h: np.ndarray, S: int, A: int, states, actions, rewards, next_states, dones):
+    """K transitions into the [K, W] staging block ``h`` in the order s | a | r | s' | d (five assignments
+    whatever K is: the block is filled column-wise)."""
+    K = h.shape[0]
+    h[:, :S] = np.asarray(states, dtype=np.float32).reshape(K, S)
+    h[:, S:S + A] = np.asarray(actions, dtype=np.float32).reshape(K, A)
+    h[:, S + A] = np.asarray(rewards, dtype=np.float32).reshape(K)
+    h[:, S + A + 1:2 * S + A + 1] = np.asarray(next_states, dtype=np.float32).reshape(K, S)
+    h[:, 2 * S + A + 1] = np.asarray(dones, dtype=np.float32).reshape(K)
+
+
+@contextlib.contextmanager
+def _appending(bufs: Sequence[ReplayBuffer], n: int):
+    """Around the launch that writes ``n`` rows at every ring's pointer: all rings are checked before anything is
+    written, and pointer, size and generation advance only when the body raised nothing."""
+    for b in bufs:
+        if b._pointer >= b._buffer_size:  # (a dataset that filled the buffer: fref:173 indexes past the end)
+            raise IndexError(f"index {b._pointer} is out of bounds for a replay buffer of {b._buffer_size} rows")
+    yield
+    for b in bufs:
+        b._pointer, b._size = ring_advance(b._pointer, b._size, n, b._buffer_size)
         _buffer_generation[0] += 1
-        self._generation = _buffer_generation[0]
+        b._generation = _buffer_generation[0]  # the rows changed: no prefetched batch survives
 
 
 def add_transitions(buffers: Sequence[ReplayBuffer], states, actions, rewards, next_states, dones):
@@ -261,33 +274,22 @@ def add_transitions(buffers: Sequence[ReplayBuffer], states, actions, rewards, n
     for b in bufs:
         if (b._state_dim, b._action_dim, b._stride, b._dev) != (S, A, b0._stride, b0._dev):
             raise ValueError("add_transitions: all replay buffers must have one state_dim, action_dim and device")
-    for b in bufs:
-        if b._pointer >= b._buffer_size:
-            raise IndexError(f"index {b._pointer} is out of bounds for a replay buffer of {b._buffer_size} rows")
-    W = 2 * S + A + 2
-    stage = getattr(b0, "_group_stage", None)
-    if stage is None or stage[0].shape[0] != K:
-        stage = b0._group_stage = (torch.zeros((K, W), dtype=torch.float32).pin_memory(),
-                                   torch.zeros((K, W), dtype=torch.float32, device=b0._dev),
-                                   torch.cuda.Event())
-    host, dev, free = stage
-    free.synchronize()  # (an event never recorded is complete)
-    h = host.numpy()  # (five assignments whatever K is: the block is filled column-wise)
-    h[:, :S] = np.asarray(states, dtype=np.float32).reshape(K, S)
-    h[:, S:S + A] = np.asarray(actions, dtype=np.float32).reshape(K, A)
-    h[:, S + A] = np.asarray(rewards, dtype=np.float32).reshape(K)
-    h[:, S + A + 1:2 * S + A + 1] = np.asarray(next_states, dtype=np.float32).reshape(K, S)
-    h[:, 2 * S + A + 1] = np.asarray(dones, dtype=np.float32).reshape(K)
-    with torch.cuda.device(b0._dev):
-        dev.copy_(host, non_blocking=True)
-        free.record()
-        check(b0._lib.iqlhip_replay_append_group((C.c_void_p * K)(*[b._rows.data_ptr() for b in bufs]), b0._stride, S, A,
-                                                 (C.c_int64 * K)(*[b._buffer_size for b in bufs]),
-                                                 (C.c_int64 * K)(*[b._pointer for b in bufs]), K, ptr(dev), stream_ptr()))
-    for b in bufs:
-        b._pointer, b._size = ring_advance(b._pointer, b._size, 1, b._buffer_size)
-        _buffer_generation[0] += 1
-        b._generation = _buffer_generation[0]
+    with _appending(bufs, 1):
+        stage = getattr(b0, "_group_stage", None)
+        if stage is None or stage[0].shape[0] != K:
+            stage = b0._group_stage = (torch.zeros((K, 2 * S + A + 2), dtype=torch.float32).pin_memory(),
+                                       torch.zeros((K, 2 * S + A + 2), dtype=torch.float32, device=b0._dev),
+                                       torch.cuda.Event())
+        host, dev, free = stage
+        free.synchronize()  # (an event never recorded is complete)
+        _stage(host.numpy(), S, A, states, actions, rewards, next_states, dones)
+        with torch.cuda.device(b0._dev):
+            dev.copy_(host, non_blocking=True)
+            free.record()
+            check(b0._lib.iqlhip_replay_append_group((C.c_void_p * K)(*[b._rows.data_ptr() for b in bufs]), b0._stride, S,
+                                                     A, (C.c_int64 * K)(*[b._buffer_size for b in bufs]),
+                                                     (C.c_int64 * K)(*[b._pointer for b in bufs]), K, ptr(dev),
+                                                     stream_ptr()))
 
 
 # --------------------------------------------------------------------------- #
@@ -353,6 +355,21 @@ def cosine_rate(base_lr: float, t: int, t_max: int, eta_min: float = 0.0) -> flo
     return eta_min + (base_lr - eta_min) * (1 + math.cos(math.pi * t / t_max)) / 2
 
 
+def _act_args(dev, S: int, A: int, states, eps, rows: Optional[int] = None):
+    """``states`` [rows, S] and ``eps`` [rows, A] | None (arrays or tensors) as contiguous float32 tensors on
+    ``dev``; ``rows`` None takes as many as ``states`` has, at least one."""
+    # (host arrays are rounded to float32 on the host: one copy up, no cast kernel behind it)
+    up = lambda x: x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
+    s = up(states).to(device=dev, dtype=torch.float32).reshape(-1, S).contiguous()
+    if s.shape[0] < 1 or rows not in (None, s.shape[0]):
+        raise ValueError(f"states must have shape (rows, {S}) with rows {rows or '>= 1'}, got {tuple(s.shape)}")
+    if eps is not None:
+        eps = up(eps).to(device=dev, dtype=torch.float32).contiguous()
+        if tuple(eps.shape) != (s.shape[0], A):
+            raise ValueError(f"eps must have shape {(s.shape[0], A)} (rows, A), got {tuple(eps.shape)}")
+    return s, eps
+
+
 class ImplicitQLearning(_OfflineIQL):
     """fref:423-563 on the same kernels: no autocast, convex Polyak form, ``max_steps`` the cosine ``T_max``
     (``train()`` passes ``offline_iterations``; the online steps run past it)."""
@@ -375,16 +392,8 @@ class ImplicitQLearning(_OfflineIQL):
         if self._precision != _lib.PREC_FP32:
             raise NotImplementedError("explore_action needs a precision='fp32' trainer (the fine-tune flavour runs "
                                       "without autocast)")
-        s = torch.as_tensor(np.asarray(states) if not torch.is_tensor(states) else states)
-        s = s.to(device=self._dev, dtype=torch.float32).reshape(-1, self._state_dim).contiguous()
+        s, eps = _act_args(self._dev, self._state_dim, self._action_dim, states, eps)
         rows = s.shape[0]
-        if rows < 1:
-            raise ValueError("explore_action needs at least one state")
-        if eps is not None:
-            eps = torch.as_tensor(np.asarray(eps) if not torch.is_tensor(eps) else eps)
-            eps = eps.to(device=self._dev, dtype=torch.float32).contiguous()
-            if tuple(eps.shape) != (rows, self._action_dim):
-                raise ValueError(f"eps must have shape {(rows, self._action_dim)}, got {tuple(eps.shape)}")
         self._ensure_handle(batch_size or self._handle_batch or 32)
         out = torch.empty((rows, self._action_dim), dtype=torch.float32, device=self._dev)
         with torch.cuda.device(self._dev):
@@ -428,15 +437,7 @@ def explore_actions(trainers: Sequence[ImplicitQLearning], states, eps=None, *, 
                 (t0._state_dim, t0._action_dim, t0._dev, float(t0.max_action)):
             raise ValueError("explore_actions: all trainers must have one state_dim, action_dim, max_action and device")
     S, A = t0._state_dim, t0._action_dim
-    # (host arrays are rounded to float32 on the host: one copy up, no cast kernel behind it)
-    up = lambda x: x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
-    s = up(states).to(device=t0._dev, dtype=torch.float32).reshape(-1, S).contiguous()
-    if s.shape[0] != K:
-        raise ValueError(f"states must have shape {(K, S)}, got {tuple(s.shape)}")
-    if eps is not None:
-        eps = up(eps).to(device=t0._dev, dtype=torch.float32).contiguous()
-        if tuple(eps.shape) != (K, A):
-            raise ValueError(f"eps must have shape {(K, A)}, got {tuple(eps.shape)}")
+    s, eps = _act_args(t0._dev, S, A, states, eps, rows=K)
     for t in trs:
         t._ensure_handle(batch_size or t._handle_batch or 32)
     out = torch.empty((K, A), dtype=torch.float32, device=t0._dev)
@@ -461,6 +462,20 @@ def _gym_and_d4rl():
         raise ImportError("finetune.train: env=None / dataset=None build them with gym and d4rl, which are not "
                           "installed; pass env=, eval_env= and dataset=") from None
     return gym, d4rl
+
+
+def _member_envs(env, K: int, what: str):
+    """``env`` / ``eval_env`` as it was given -- for one seed the environment itself, for K > 1 a callable
+    ``k -> env`` or K environments -- as a callable ``k -> env``; None stays None."""
+    if env is None or (K > 1 and callable(env)):
+        return env
+    if K == 1:
+        return lambda k: env
+    if not isinstance(env, (list, tuple)) or len(env) != K:
+        n = len(env) if isinstance(env, (list, tuple)) else 1
+        raise ValueError(f"finetune.train(seeds_per_gpu={K}): {what} must be {K} environments or a callable "
+                         f"k -> env (got {n})")
+    return list(env).__getitem__
 
 
 def train(config: TrainConfig, env=None, eval_env=None, dataset: Optional[Dict[str, np.ndarray]] = None, *,
@@ -490,193 +505,14 @@ def train(config: TrainConfig, env=None, eval_env=None, dataset: Optional[Dict[s
     function does alone under ``config.seed = rank_seed(config.seed, K) + k`` -- bit for bit, as long as no
     environment reads numpy's global generator (member k draws its indices from its own
     ``np.random.RandomState(seed_k)``).  ``env`` / ``eval_env``: sequences of K environments or a callable
-    ``k -> env``.  Every tick acts for all members in one launch (``explore_actions``), steps the K
-    environments on the host, appends in one launch (``add_transitions``) and takes one ``SeedGroup`` step.
-    Records carry a ``seed`` entry, checkpoints go under ``seed_<s>/``, ``exploration_noise(tick)`` returns
-    [K, A], ``on_start(trainers, replay_buffers)`` gets the lists, and the list of trainers is returned."""
+    ``k -> env``.  The loop is the same one over K members; only what a tick launches differs: it acts for all
+    members in one launch (``explore_actions``), steps the K environments on the host, appends in one launch
+    (``add_transitions``) and takes one ``SeedGroup`` step, where one seed calls its trainer's and its ring's
+    own methods.  Records carry a ``seed`` entry, checkpoints go under ``seed_<s>/``, ``exploration_noise(tick)``
+    returns [K, A], ``on_start(trainers, replay_buffers)`` gets the lists, and the list of trainers is returned."""
     K = int(seeds_per_gpu)
     if not 1 <= K <= _lib.MAX_GROUP:
         raise ValueError(f"seeds_per_gpu must be in 1..{_lib.MAX_GROUP}")
-    if K > 1:
-        return _train_group(config, env, eval_env, dataset, K, logger=logger, normalized_score=normalized_score,
-                            device=device, chunk=chunk, online_chunk=online_chunk,
-                            exploration_noise=exploration_noise, on_start=on_start)
-    if device is None:
-        device = D.local_device() or ("cuda:0" if config.device == "cuda" else config.device)
-    if env is None or eval_env is None or dataset is None:
-        gym, d4rl = _gym_and_d4rl()
-        env = gym.make(config.env) if env is None else env
-        eval_env = gym.make(config.env) if eval_env is None else eval_env
-        if dataset is None:
-            dataset = d4rl.qlearning_dataset(env)
-    if normalized_score is None:
-        normalized_score = eval_env.get_normalized_score
-    is_env_with_goal = config.env.startswith(ENVS_WITH_GOAL)
-    max_steps = env._max_episode_steps
-    state_dim = env.observation_space.shape[0]
-    action_dim = env.action_space.shape[0]
-    n_off, n_on, B = int(config.offline_iterations), int(config.online_iterations), int(config.batch_size)
-
-    # ---- dataset, normalisation, buffer (fref:578-603) ----
-    reward_mod_dict = {}
-    if config.normalize_reward:
-        reward_mod_dict = modify_reward(dataset, config.env)
-    if config.normalize:
-        state_mean, state_std = compute_mean_std(dataset["observations"], eps=1e-3)
-    else:
-        state_mean, state_std = 0, 1
-    dataset["observations"] = normalize_states(dataset["observations"], state_mean, state_std)
-    dataset["next_observations"] = normalize_states(dataset["next_observations"], state_mean, state_std)
-    env = wrap_env(env, state_mean=state_mean, state_std=state_std)
-    eval_env = wrap_env(eval_env, state_mean=state_mean, state_std=state_std)
-    replay_buffer = ReplayBuffer(state_dim, action_dim, config.buffer_size, device)
-    replay_buffer.load_d4rl_dataset(dataset)
-    max_action = float(env.action_space.high[0])
-    ckpt_dir = _offline_loop.checkpoint_dirs(config, [config.seed])[0]
-
-    # ---- seeds and nets (fref:613-660) ----
-    seed = config.seed
-    set_seed(seed, env)
-    eval_env.seed(config.eval_seed)
-    eval_env.action_space.seed(config.eval_seed)
-    dropout = config.actor_dropout if config.actor_dropout and config.actor_dropout > 0.0 else None  # fref:314
-    q_network = TwinQ(state_dim, action_dim).to(device)
-    v_network = ValueFunction(state_dim).to(device)
-    policy = DeterministicPolicy if config.iql_deterministic else GaussianPolicy
-    actor = policy(state_dim, action_dim, max_action, dropout=dropout).to(device)
-    v_optimizer = torch.optim.Adam(v_network.parameters(), lr=config.vf_lr)
-    q_optimizer = torch.optim.Adam(q_network.parameters(), lr=config.qf_lr)
-    actor_optimizer = torch.optim.Adam(actor.parameters(), lr=config.actor_lr)
-    print("---------------------------------------")
-    print(f"Training IQL, Env: {config.env}, Seed: {seed}")
-    print("---------------------------------------")
-    trainer = ImplicitQLearning(max_action=max_action, actor=actor, actor_optimizer=actor_optimizer, q_network=q_network,
-                                q_optimizer=q_optimizer, v_network=v_network, v_optimizer=v_optimizer,
-                                discount=config.discount, tau=config.tau, device=device, beta=config.beta,
-                                iql_tau=config.iql_tau, max_steps=n_off, seed=seed)
-    if config.load_model != "":
-        trainer.load_state_dict(torch.load(config.load_model))
-    if logger is None:
-        logger = _offline_loop.default_logger(config, 1)
-    if on_start is not None:
-        on_start(trainer, replay_buffer)
-
-    train_successes, eval_successes, evaluations = [], [], []
-    pending = []  # (first t, device losses [n, 3], the online records of those steps or None)
-
-    def flush():
-        for t0, losses, extras in pending:
-            for i, (v, q, a) in enumerate(losses.cpu().numpy().tolist()):
-                t = t0 + i
-                rec = {"value_loss": v, "q_loss": q, "actor_loss": a}
-                rec["offline_iter" if t < n_off else "online_iter"] = t if t < n_off else t - n_off
-                if extras is not None:
-                    rec.update(extras[i])
-                logger(rec, t + 1)  # (step = trainer.total_it after the step, fref:734)
-        pending.clear()
-
-    def evaluate(t):
-        """fref:736-767, after step t."""
-        flush()
-        print(f"Time steps: {t + 1}")
-        eval_scores, success_rate = eval_actor(eval_env, actor, device=device, n_episodes=config.n_episodes,
-                                               seed=config.seed)
-        eval_score = eval_scores.mean()
-        eval_log = {}
-        normalized = normalized_score(eval_score)
-        if t >= n_off and is_env_with_goal:
-            eval_successes.append(success_rate)
-            eval_log["eval/regret"] = np.mean(1 - np.array(train_successes))  # (of the TRAINING episodes, as fref:751)
-            eval_log["eval/success_rate"] = success_rate
-        normalized_eval_score = normalized * 100.0
-        evaluations.append(normalized_eval_score)
-        eval_log["eval/d4rl_normalized_score"] = normalized_eval_score
-        print("---------------------------------------")
-        print(f"Evaluation over {config.n_episodes} episodes: {eval_score:.3f} , D4RL score: {normalized_eval_score:.3f}")
-        print("---------------------------------------")
-        if ckpt_dir is not None:
-            torch.save(trainer.state_dict(), os.path.join(ckpt_dir, f"checkpoint_{t}.pt"))
-        logger(eval_log, t + 1)
-
-    every = int(config.eval_freq)
-    state, done = env.reset(), False
-    episode_return, episode_step, goal_achieved = 0, 0, False
-
-    # ---- offline pretraining: the chunked loop of the offline flavours ----
-    print("Offline pretraining")
-    offline_stream = NumpyIndexStream(device) if n_off > 0 else None
-    t = 0
-    while t < n_off:
-        nxt = min(n_off, t + int(chunk), (t // every + 1) * every)
-        idx = offline_stream.draw(replay_buffer.index_bound(), nxt - t, B)[0]
-        losses = trainer.train_steps(replay_buffer, nxt - t, B, indices=idx)
-        flush()
-        pending.append((t, losses, None))
-        t = nxt
-        if t % every == 0:
-            evaluate(t - 1)
-
-    # ---- online tuning: act, step the environment, append, one gradient step ----
-    if n_on > 0:
-        print("Online tuning")
-    online_stream = GrowingIndexStream(device) if n_on > 0 else None
-    chunk_idx, chunk_t0 = None, 0
-    for t in range(n_off, n_off + n_on):
-        tick = t - n_off
-        if chunk_idx is None or tick - chunk_t0 >= chunk_idx.shape[0]:
-            flush()
-            n = min(max(1, int(online_chunk)), n_on - tick)
-            hi0 = min(replay_buffer.index_bound() + 1, int(config.buffer_size))
-            chunk_idx, chunk_t0 = online_stream.draw(hi0, int(config.buffer_size), n, B)[0], tick
-        online_log = {}
-        episode_step += 1
-        eps = None if exploration_noise is None else torch.as_tensor(np.asarray(exploration_noise(tick))).reshape(1, -1)
-        action = trainer.explore_action(np.asarray(state).reshape(1, -1), eps, expl_noise=config.expl_noise,
-                                        noise_clip=config.noise_clip, batch_size=B)
-        action = action.cpu().numpy().flatten()
-        next_state, reward, done, env_infos = env.step(action)
-        if not goal_achieved:
-            goal_achieved = is_goal_reached(reward, env_infos)
-        episode_return += reward
-        real_done = bool(done and episode_step < max_steps)  # (a timeout ends the episode but is no terminal)
-        if config.normalize_reward:
-            reward = modify_reward_online(reward, config.env, **reward_mod_dict)
-        replay_buffer.add_transition(state, action, reward, next_state, real_done)
-        state = next_state
-        if done:
-            state, done = env.reset(), False
-            if is_env_with_goal:
-                train_successes.append(goal_achieved)
-                online_log["train/regret"] = np.mean(1 - np.array(train_successes))
-                online_log["train/is_success"] = float(goal_achieved)
-            online_log["train/episode_return"] = episode_return
-            online_log["train/d4rl_normalized_episode_return"] = normalized_score(episode_return) * 100.0
-            online_log["train/episode_length"] = episode_step
-            episode_return, episode_step, goal_achieved = 0, 0, False
-        j = tick - chunk_t0
-        losses = trainer.train_steps(replay_buffer, 1, B, indices=chunk_idx[j:j + 1])
-        pending.append((t, losses, [online_log]))
-        if (t + 1) % every == 0:
-            evaluate(t)
-    flush()
-    return trainer
-
-
-def _member_envs(env, K: int, what: str):
-    """``env`` / ``eval_env`` of a K-seed run as it was given: None, a callable ``k -> env``, or K environments."""
-    if env is None or callable(env):
-        return env
-    if not isinstance(env, (list, tuple)) or len(env) != K:
-        n = len(env) if isinstance(env, (list, tuple)) else 1
-        raise ValueError(f"finetune.train(seeds_per_gpu={K}): {what} must be {K} environments or a callable "
-                         f"k -> env (got {n})")
-    return list(env)
-
-
-def _train_group(config: TrainConfig, env, eval_env, dataset, K: int, *, logger, normalized_score, device, chunk,
-                 online_chunk, exploration_noise, on_start):
-    """``train`` for K > 1 seeds: the same loop with every per-run variable a list, the act, the append and the
-    gradient step of a tick one launch sequence each for all members."""
     env, eval_env = _member_envs(env, K, "env"), _member_envs(eval_env, K, "eval_env")
     if device is None:
         device = D.local_device() or ("cuda:0" if config.device == "cuda" else config.device)
@@ -684,8 +520,8 @@ def _train_group(config: TrainConfig, env, eval_env, dataset, K: int, *, logger,
         gym, d4rl = _gym_and_d4rl()
         env = (lambda k: gym.make(config.env)) if env is None else env
         eval_env = (lambda k: gym.make(config.env)) if eval_env is None else eval_env
-    envs = [env(k) for k in range(K)] if callable(env) else env
-    eval_envs = [eval_env(k) for k in range(K)] if callable(eval_env) else eval_env
+    ks = range(K)
+    envs, eval_envs = [env(k) for k in ks], [eval_env(k) for k in ks]
     if dataset is None:
         dataset = d4rl.qlearning_dataset(envs[0])
     normalized = [e.get_normalized_score for e in eval_envs] if normalized_score is None else [normalized_score] * K
@@ -694,7 +530,6 @@ def _train_group(config: TrainConfig, env, eval_env, dataset, K: int, *, logger,
     state_dim = envs[0].observation_space.shape[0]
     action_dim = envs[0].action_space.shape[0]
     n_off, n_on, B = int(config.offline_iterations), int(config.online_iterations), int(config.batch_size)
-    ks = range(K)
 
     # ---- dataset and normalisation once, one ring per member (fref:578-603) ----
     reward_mod_dict = {}
@@ -708,6 +543,10 @@ def _train_group(config: TrainConfig, env, eval_env, dataset, K: int, *, logger,
     dataset["next_observations"] = normalize_states(dataset["next_observations"], state_mean, state_std)
     envs = [wrap_env(e, state_mean=state_mean, state_std=state_std) for e in envs]
     eval_envs = [wrap_env(e, state_mean=state_mean, state_std=state_std) for e in eval_envs]
+    # one seed keeps config.seed as it is (under torchrun too: no rank offset)
+    seeds = [config.seed] if K == 1 else [D.rank_seed(config.seed, K) + k for k in ks]
+    ckpt_dirs = _offline_loop.checkpoint_dirs(config, seeds)
+    tagged = _offline_loop.tag(seeds)
     up = lambda name: torch.tensor(dataset[name], dtype=torch.float32, device=device)
     arrays = [up(n) for n in ("observations", "actions", "rewards", "next_observations", "terminals")]
     buffers = []
@@ -716,12 +555,11 @@ def _train_group(config: TrainConfig, env, eval_env, dataset, K: int, *, logger,
             buffers.append(ReplayBuffer(state_dim, action_dim, config.buffer_size, device))
             buffers[k].load_device_arrays(*arrays)
         except MemoryError as e:
+            if K == 1:
+                raise
             raise MemoryError(f"finetune.train(seeds_per_gpu={K}): the ring of member {k} of {K}: {e}") from None
     del arrays
     max_action = float(envs[0].action_space.high[0])
-    seeds = [D.rank_seed(config.seed, K) + k for k in ks]
-    ckpt_dirs = _offline_loop.checkpoint_dirs(config, seeds)
-    tagged = _offline_loop.tag(seeds)
 
     # ---- seeds and nets, member by member as a run of its own sets them up (fref:613-660) ----
     dropout = config.actor_dropout if config.actor_dropout and config.actor_dropout > 0.0 else None  # fref:314
@@ -747,15 +585,28 @@ def _train_group(config: TrainConfig, env, eval_env, dataset, K: int, *, logger,
                                           seed=seed))
         if config.load_model != "":
             trainers[k].load_state_dict(torch.load(config.load_model))
-    # what np.random.seed(seed_k) leaves numpy's global generator in, one generator per member
-    gens = [np.random.RandomState(seed) for seed in seeds]
-    from .multi import SeedGroup
-    # ONE launch sequence per step for all members (the two-stream split pays per call, and a tick is one step)
-    group = SeedGroup(trainers, mode="general" if trainers[0].step_kind(B) == "general" else "group")
     if logger is None:
         logger = _offline_loop.default_logger(config, K)
     if on_start is not None:
-        on_start(trainers, buffers)
+        on_start(*((trainers[0], buffers[0]) if K == 1 else (trainers, buffers)))
+
+    # ---- what a tick launches: one seed stays on its trainer's and its ring's own calls (the group kernels
+    # cost more per member), K > 1 send each part out once for all members ----
+    act_kw = dict(expl_noise=config.expl_noise, noise_clip=config.noise_clip, batch_size=B)
+    if K == 1:
+        gens, group = None, None  # (numpy's global generator, as set_seed left it)
+        act = lambda states, eps: trainers[0].explore_action(states, eps, **act_kw).cpu().numpy()
+        append = lambda s, a, r, s2, d: buffers[0].add_transition(s[0], a[0], r[0], s2[0], d[0])
+        step = lambda n, indices: [trainers[0].train_steps(buffers[0], n, B, indices=indices[0])]
+    else:
+        # what np.random.seed(seed_k) leaves numpy's global generator in, one generator per member
+        gens = [np.random.RandomState(seed) for seed in seeds]
+        from .multi import SeedGroup
+        # ONE launch sequence per step for all members (the two-stream split pays per call, and a tick is one step)
+        group = SeedGroup(trainers, mode="general" if trainers[0].step_kind(B) == "general" else "group")
+        act = lambda states, eps: explore_actions(trainers, states, eps, **act_kw).cpu().numpy()
+        append = lambda *transitions: add_transitions(buffers, *transitions)
+        step = lambda n, indices: group.train_steps(buffers, n, B, indices=indices, return_losses=True)
 
     train_successes = [[] for _ in ks]
     pending = []  # (first t, [K] device losses [n, 3], [K] lists of the online records of those steps, or None)
@@ -769,13 +620,14 @@ def _train_group(config: TrainConfig, env, eval_env, dataset, K: int, *, logger,
                     rec["offline_iter" if t < n_off else "online_iter"] = t if t < n_off else t - n_off
                     if extras is not None:
                         rec.update(extras[k][i])
-                    logger(tagged(rec, k), t + 1)
+                    logger(tagged(rec, k), t + 1)  # (step = trainer.total_it after the step, fref:734)
         pending.clear()
 
     def evaluate(t):
         """fref:736-767 after step t, member after member."""
         flush()
-        group.synchronize()
+        if group is not None:
+            group.synchronize()
         print(f"Time steps: {t + 1}")
         for k, seed in enumerate(seeds):
             eval_scores, success_rate = eval_actor(eval_envs[k], trainers[k].actor, device=device,
@@ -783,13 +635,14 @@ def _train_group(config: TrainConfig, env, eval_env, dataset, K: int, *, logger,
             eval_score = eval_scores.mean()
             eval_log = {}
             if t >= n_off and is_env_with_goal:
+                # (of the TRAINING episodes, as fref:751)
                 eval_log["eval/regret"] = np.mean(1 - np.array(train_successes[k]))
                 eval_log["eval/success_rate"] = success_rate
             normalized_eval_score = normalized[k](eval_score) * 100.0
             eval_log["eval/d4rl_normalized_score"] = normalized_eval_score
             print("---------------------------------------")
-            print(f"Seed {seed}: evaluation over {config.n_episodes} episodes: {eval_score:.3f} , "
-                  f"D4RL score: {normalized_eval_score:.3f}")
+            print(f"{'Evaluation' if K == 1 else f'Seed {seed}: evaluation'} over {config.n_episodes} episodes: "
+                  f"{eval_score:.3f} , D4RL score: {normalized_eval_score:.3f}")
             print("---------------------------------------")
             if ckpt_dirs[k] is not None:
                 torch.save(trainers[k].state_dict(), os.path.join(ckpt_dirs[k], f"checkpoint_{t}.pt"))
@@ -799,21 +652,20 @@ def _train_group(config: TrainConfig, env, eval_env, dataset, K: int, *, logger,
     states = [e.reset() for e in envs]
     episode_return, episode_step, goal_achieved = [0] * K, [0] * K, [False] * K
 
-    # ---- offline pretraining ----
+    # ---- offline pretraining: the chunked loop of the offline flavours ----
     print("Offline pretraining")
     offline_stream = NumpyIndexStream(device) if n_off > 0 else None
     t = 0
     while t < n_off:
         nxt = min(n_off, t + int(chunk), (t // every + 1) * every)
-        idx = offline_stream.draw(buffers[0].index_bound(), nxt - t, B, gens)
-        losses = group.train_steps(buffers, nxt - t, B, indices=idx, return_losses=True)
+        losses = step(nxt - t, offline_stream.draw(buffers[0].index_bound(), nxt - t, B, gens))
         flush()
         pending.append((t, losses, None))
         t = nxt
         if t % every == 0:
             evaluate(t - 1)
 
-    # ---- online tuning: one act, K environment steps, one append, one group step ----
+    # ---- online tuning: act, step the environments, append, one gradient step ----
     if n_on > 0:
         print("Online tuning")
     online_stream = GrowingIndexStream(device) if n_on > 0 else None
@@ -827,8 +679,7 @@ def _train_group(config: TrainConfig, env, eval_env, dataset, K: int, *, logger,
             chunk_idx, chunk_t0 = online_stream.draw(hi0, int(config.buffer_size), n, B, generators=gens), tick
         eps = None if exploration_noise is None else \
             torch.as_tensor(np.asarray(exploration_noise(tick))).reshape(K, action_dim)
-        actions = explore_actions(trainers, np.asarray(states).reshape(K, -1), eps, expl_noise=config.expl_noise,
-                                  noise_clip=config.noise_clip, batch_size=B).cpu().numpy()
+        actions = act(np.asarray(states).reshape(K, -1), eps)
         online_logs, rewards, next_states, real_dones, after = [], [], [], [], []
         for k in ks:
             online_log = {}
@@ -853,14 +704,14 @@ def _train_group(config: TrainConfig, env, eval_env, dataset, K: int, *, logger,
                 episode_return[k], episode_step[k], goal_achieved[k] = 0, 0, False
             online_logs.append([online_log])
             after.append(next_state)
-        add_transitions(buffers, states, actions, rewards, next_states, real_dones)
+        append(states, actions, rewards, next_states, real_dones)
         states = after
         j = tick - chunk_t0
-        losses = group.train_steps(buffers, 1, B, indices=[c[j:j + 1] for c in chunk_idx], return_losses=True)
-        pending.append((t, losses, online_logs))
+        pending.append((t, step(1, [c[j:j + 1] for c in chunk_idx]), online_logs))
         if (t + 1) % every == 0:
             evaluate(t)
     flush()
-    group.synchronize()
-    group.close()
-    return trainers
+    if group is not None:
+        group.synchronize()
+        group.close()
+    return trainers[0] if K == 1 else trainers

@@ -4,7 +4,9 @@
    over both summation orders of the stand-alone MLP kernels, both policies, dropout, drawn and given noise;
 2. iqlhip_replay_append_group: K rings byte for byte what add_transition leaves in twin rings;
 3. refusals change nothing;
-4. finetune.train(seeds_per_gpu=3) is three runs of finetune.train, member for member.
+4. finetune.train(seeds_per_gpu=3) is three runs of finetune.train, member for member;
+5. the one loop of finetune.train launches the solo calls for one seed and the grouped ones for K > 1, and hands
+   the caller of one seed what it always got.
 """
 import ctypes as C
 import os
@@ -361,3 +363,84 @@ def test_train_three_seeds_equals_three_runs(name, det, tmp_path, monkeypatch):
         assert m["ckpts"] == want and [f for f in solo["ckpts"] if f.endswith(".pt")] == want, who
     # the members are runs of their own: they differ from one another
     assert not torch.equal(group[0]["rows"], group[1]["rows"])
+
+
+# --------------------------------------------------------------------------- #
+# one loop: what one seed and what a group call in it, and what the caller of one seed is handed
+# --------------------------------------------------------------------------- #
+def _small_run(ft, name, K, tmp_path, **hooks):
+    """A run of one offline chunk (4 steps), three online index chunks of 5 / 5 / 2 ticks, evaluations after
+    steps 7 and 15, and a ring that wraps (40 + 12 > 48).  Returns (config, envs, what train returned, records)."""
+    config = ft.TrainConfig(device=DEV, env=name, seed=40, eval_seed=3, eval_freq=8, n_episodes=1, offline_iterations=4,
+                            online_iterations=12, checkpoints_path=str(tmp_path / f"K{K}"), buffer_size=48, batch_size=32)
+    envs = [fe.RecordingEnv(fe.FinetuneEnv(name)) for _ in range(K)]
+    eval_envs = [fe.RecordingEnv(fe.FinetuneEnv(name)) for _ in range(K)]
+    records = []
+    solo = K == 1
+    got = ft.train(config, envs[0] if solo else envs, eval_envs[0] if solo else eval_envs, fe.make_dataset(name, 40, 17),
+                   device=DEV, logger=lambda d, step: records.append((int(step), dict(d))), online_chunk=5,
+                   seeds_per_gpu=K, **hooks)
+    torch.cuda.synchronize()
+    return config, envs, got, records
+
+
+@pytest.mark.parametrize("name", ["antmaze-finetune-v0", "cheetah-finetune-v0"], ids=["goal", "plain"])
+def test_one_seed_takes_the_solo_calls_and_a_group_the_grouped_ones(name, tmp_path, monkeypatch):
+    ft = _ft()
+    from iqlpref_amd import multi
+    calls = {}
+
+    def spy(owner, attr, key):
+        real = getattr(owner, attr)
+        calls[key] = 0
+
+        def counted(*args, **kw):
+            calls[key] += 1
+            return real(*args, **kw)
+        monkeypatch.setattr(owner, attr, counted)
+
+    spy(ft, "explore_actions", "explore_actions")
+    spy(ft, "add_transitions", "add_transitions")
+    spy(ft.ImplicitQLearning, "explore_action", "explore_action")
+    spy(ft.ReplayBuffer, "add_transition", "add_transition")
+    spy(ft.ImplicitQLearning, "train_steps", "train_steps")
+    spy(multi.SeedGroup, "__init__", "SeedGroup")
+    spy(multi.SeedGroup, "train_steps", "SeedGroup.train_steps")
+
+    _small_run(ft, name, 1, tmp_path)
+    solo = dict(calls)
+    assert solo["explore_action"] == 12 and solo["add_transition"] == 12
+    assert solo["train_steps"] == 1 + 12  # one offline chunk, one call per tick
+    assert solo["explore_actions"] == 0 and solo["add_transitions"] == 0
+    assert solo["SeedGroup"] == 0 and solo["SeedGroup.train_steps"] == 0
+
+    for key in calls:
+        calls[key] = 0
+    _small_run(ft, name, 3, tmp_path)
+    assert calls["explore_action"] == 0 and calls["add_transition"] == 0
+    assert calls["explore_actions"] == 12 and calls["add_transitions"] == 12
+    assert calls["SeedGroup"] == 1 and calls["SeedGroup.train_steps"] == 1 + 12
+
+
+@pytest.mark.parametrize("name", ["antmaze-finetune-v0", "cheetah-finetune-v0"], ids=["goal", "plain"])
+def test_one_seed_keeps_its_call_shapes(name, tmp_path, monkeypatch):
+    ft = _ft()
+    real_rank_seed = ft.D.rank_seed
+    monkeypatch.setattr(ft.D, "rank_seed", lambda seed, *a, **kw: real_rank_seed(seed, *a, **kw) + 1000)
+    want = ["checkpoint_15.pt", "checkpoint_7.pt"]
+    box = {}
+    config, envs, got, records = _small_run(ft, name, 1, tmp_path, on_start=lambda tr, buf: box.update(tr=tr, buf=buf))
+    assert envs[0].seeds[0] == config.seed  # no rank_seed for one seed
+    assert isinstance(box["tr"], ft.ImplicitQLearning) and isinstance(box["buf"], ft.ReplayBuffer)
+    assert got is box["tr"]
+    assert records and not any("seed" in d for _, d in records)
+    assert sorted(f for f in os.listdir(config.checkpoints_path) if f.endswith(".pt")) == want
+
+    config, envs, got, records = _small_run(ft, name, 2, tmp_path, on_start=lambda tr, buf: box.update(tr=tr, buf=buf))
+    assert isinstance(got, list) and got == box["tr"] and len(box["buf"]) == 2
+    for k in range(2):
+        s = config.seed + 1000 + k
+        assert envs[k].seeds[0] == s
+        assert sorted(os.listdir(os.path.join(config.checkpoints_path, f"seed_{s}"))) == want
+    assert {d["seed"] for _, d in records} == {config.seed + 1000, config.seed + 1001}
+    assert not [f for f in os.listdir(config.checkpoints_path) if f.endswith(".pt")]

@@ -12,7 +12,7 @@ call in a loop on the same trainer -- the floor the tick cannot go under.
 
 ``--seeds K`` (K > 1) times the tick of ``finetune.train(seeds_per_gpu=K)`` instead: ``explore_actions`` and its
 one copy to the host, ``add_transitions``, one ``SeedGroup.train_steps(n_steps=1)`` on K rings -- the same three
-parts, each once for all K members -- and adds ``seed_ticks_per_s`` = K / tick.
+parts, each once for all K members.  ``seed_ticks_per_s`` = K / tick.
 """
 import argparse
 import json
@@ -38,59 +38,6 @@ def main():
     ap.add_argument("--action-dim", type=int, default=6)
     ap.add_argument("--seeds", type=int, default=1)
     args = ap.parse_args()
-    if args.seeds > 1:
-        return main_group(args)
-    dev, S, A, B = "cuda:0", args.state_dim, args.action_dim, args.batch
-    total = args.warmup + args.ticks
-    rng = np.random.default_rng(0)
-    data = {"observations": rng.standard_normal((args.rows, S)).astype(np.float32),
-            "actions": rng.uniform(-1, 1, (args.rows, A)).astype(np.float32),
-            "rewards": rng.standard_normal(args.rows).astype(np.float32),
-            "next_observations": rng.standard_normal((args.rows, S)).astype(np.float32),
-            "terminals": (rng.uniform(size=args.rows) < 0.01).astype(np.float32)}
-    torch.manual_seed(0)
-    q, v, actor = ia.TwinQ(S, A).to(dev), ia.ValueFunction(S).to(dev), ia.GaussianPolicy(S, A, 1.0).to(dev)
-    tr = ft.ImplicitQLearning(1.0, actor, torch.optim.Adam(actor.parameters(), lr=3e-4), q,
-                              torch.optim.Adam(q.parameters(), lr=3e-4), v, torch.optim.Adam(v.parameters(), lr=3e-4),
-                              max_steps=10 ** 6, device=dev, seed=0)
-    buf = ft.ReplayBuffer(S, A, args.rows + total // 2, dev)  # (the ring fills half way through: both regimes)
-    buf.load_d4rl_dataset(data)
-    np.random.seed(0)
-    idx = ft.GrowingIndexStream(dev).draw(min(buf.index_bound() + 1, buf._buffer_size), buf._buffer_size, total, B)[0]
-    state = rng.standard_normal(S)
-    nxt = rng.standard_normal(S)
-    t_act = t_app = t_step = 0.0
-    for i in range(total):
-        if i == args.warmup:
-            torch.cuda.synchronize()
-            t_act = t_app = t_step = 0.0
-        t0 = time.perf_counter()
-        action = tr.explore_action(state.reshape(1, -1), None, batch_size=B).cpu().numpy().flatten()
-        t1 = time.perf_counter()
-        buf.add_transition(state, action, 0.5, nxt, False)
-        t2 = time.perf_counter()
-        tr.train_steps(buf, 1, B, indices=idx[i:i + 1], return_losses=False)
-        torch.cuda.synchronize()
-        t3 = time.perf_counter()
-        t_act, t_app, t_step = t_act + t1 - t0, t_app + t2 - t1, t_step + t3 - t2
-    # the floor: the same call with nothing around it (the device queue never runs dry: no sync inside)
-    floor_idx = idx[:1]
-    for _ in range(args.warmup):
-        tr.train_steps(buf, 1, B, indices=floor_idx, return_losses=False)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(args.ticks):
-        tr.train_steps(buf, 1, B, indices=floor_idx, return_losses=False)
-    torch.cuda.synchronize()
-    floor = (time.perf_counter() - t0) / args.ticks
-    us = lambda x: round(1e6 * x / args.ticks, 2)
-    print(json.dumps({"tool": "bench_finetune", "build_tag": _lib.build_tag(), "ticks": args.ticks, "batch": B,
-                      "state_dim": S, "action_dim": A, "tick_us": us(t_act + t_app + t_step), "act_us": us(t_act),
-                      "append_us": us(t_app), "step_us": us(t_step), "bare_train_step_us": round(1e6 * floor, 2)}))
-
-
-def main_group(args):
-    from iqlpref_amd.multi import SeedGroup
     dev, S, A, B, K = "cuda:0", args.state_dim, args.action_dim, args.batch, args.seeds
     total = args.warmup + args.ticks
     rng = np.random.default_rng(0)
@@ -106,10 +53,23 @@ def main_group(args):
         trs.append(ft.ImplicitQLearning(1.0, actor, torch.optim.Adam(actor.parameters(), lr=3e-4), q,
                                         torch.optim.Adam(q.parameters(), lr=3e-4), v,
                                         torch.optim.Adam(v.parameters(), lr=3e-4), max_steps=10 ** 6, device=dev, seed=k))
-        bufs.append(ft.ReplayBuffer(S, A, args.rows + total // 2, dev))
+        bufs.append(ft.ReplayBuffer(S, A, args.rows + total // 2, dev))  # (the ring fills half way through: both regimes)
         bufs[k].load_d4rl_dataset(data)
-    group = SeedGroup(trs, mode="group")  # (what finetune.train steps its members with)
-    gens = [np.random.RandomState(k) for k in range(K)]
+    # the three calls of a tick, as finetune.train picks them: one seed on its own entry points, K > 1 grouped
+    if K == 1:
+        np.random.seed(0)
+        gens, group = None, None
+        act = lambda states: trs[0].explore_action(states, None, batch_size=B).cpu().numpy()
+        append = lambda s, a, r, s2, d: bufs[0].add_transition(s[0], a[0], r[0], s2[0], d[0])
+        step = lambda indices: trs[0].train_steps(bufs[0], 1, B, indices=indices[0], return_losses=False)
+    else:
+        from iqlpref_amd.multi import SeedGroup
+        gens = [np.random.RandomState(k) for k in range(K)]
+        group = SeedGroup(trs, mode="group")  # (what finetune.train steps its members with)
+        act = lambda states: ft.explore_actions(trs, states, None, expl_noise=0.03, noise_clip=0.5,
+                                                batch_size=B).cpu().numpy()
+        append = lambda *transitions: ft.add_transitions(bufs, *transitions)
+        step = lambda indices: group.train_steps(bufs, 1, B, indices=indices, return_losses=False)
     cap = bufs[0]._buffer_size
     idx = ft.GrowingIndexStream(dev).draw(min(bufs[0].index_bound() + 1, cap), cap, total, B, generators=gens)
     states = rng.standard_normal((K, S))
@@ -121,21 +81,22 @@ def main_group(args):
             torch.cuda.synchronize()
             t_act = t_app = t_step = 0.0
         t0 = time.perf_counter()
-        actions = ft.explore_actions(trs, states, None, expl_noise=0.03, noise_clip=0.5, batch_size=B).cpu().numpy()
+        actions = act(states)
         t1 = time.perf_counter()
-        ft.add_transitions(bufs, states, actions, rewards, nxt, dones)
+        append(states, actions, rewards, nxt, dones)
         t2 = time.perf_counter()
-        group.train_steps(bufs, 1, B, indices=[x[i:i + 1] for x in idx], return_losses=False)
+        step([x[i:i + 1] for x in idx])
         torch.cuda.synchronize()
         t3 = time.perf_counter()
         t_act, t_app, t_step = t_act + t1 - t0, t_app + t2 - t1, t_step + t3 - t2
+    # the floor: the same call with nothing around it (the device queue never runs dry: no sync inside)
     floor_idx = [x[:1] for x in idx]
     for _ in range(args.warmup):
-        group.train_steps(bufs, 1, B, indices=floor_idx, return_losses=False)
+        step(floor_idx)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.ticks):
-        group.train_steps(bufs, 1, B, indices=floor_idx, return_losses=False)
+        step(floor_idx)
     torch.cuda.synchronize()
     floor = (time.perf_counter() - t0) / args.ticks
     us = lambda x: round(1e6 * x / args.ticks, 2)
@@ -144,7 +105,8 @@ def main_group(args):
                       "state_dim": S, "action_dim": A, "tick_us": us(t_act + t_app + t_step), "act_us": us(t_act),
                       "append_us": us(t_app), "step_us": us(t_step), "bare_train_step_us": round(1e6 * floor, 2),
                       "seed_ticks_per_s": round(K / tick, 1)}))
-    group.close()
+    if group is not None:
+        group.close()
 
 
 if __name__ == "__main__":
