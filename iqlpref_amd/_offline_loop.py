@@ -3,12 +3,14 @@
 directories, the default logger and the ``seed`` tag of K > 1 records.
 
 ``run`` knows no trainer class, buffer or sampler: a flavour hands in how a chunk of steps is queued and how
-one seed is evaluated.  Nothing here touches the GPU or loads the library.
+one seed is evaluated.  Its members are the K seeds of one config (one step count and evaluation period for all)
+or the runs of a sweep's launch batch (``custom_offline.train_runs``: one of each per member, and a hook that
+rebuilds the group when a member leaves).  Nothing here touches the GPU or loads the library.
 """
 import os
 import uuid
 from dataclasses import asdict
-from typing import Callable, Dict, List, Optional, Sequence
+from typing import Callable, Dict, List, Optional, Sequence, Union
 
 import numpy as np
 import torch
@@ -54,57 +56,76 @@ def tag(seeds: Sequence[int]) -> Callable[[Dict[str, float], int], Dict[str, flo
     return lambda rec, k: dict(rec, seed=seeds[k])
 
 
-def run(trainers: Sequence, seeds: Sequence[int], group, total: int, every: int, chunk: int, logger: Logger,
-        ckpt_dirs: Sequence[Optional[str]], steps: Callable[[int, int], List[torch.Tensor]],
-        evaluate: Callable[[int, object, int], np.ndarray], normalized: Optional[Callable] = None,
-        best_by_return: bool = False) -> None:
+def run(trainers: Sequence, seeds: Sequence[int], group, total: Union[int, Sequence[int]],
+        every: Union[int, Sequence[int]], chunk: int, logger: Logger, ckpt_dirs: Sequence[Optional[str]],
+        steps: Callable[[int, int], List[torch.Tensor]], evaluate: Callable[[int, object, int], np.ndarray],
+        normalized: Union[None, Callable, Sequence[Optional[Callable]]] = None, best_by_return: bool = False, *,
+        regroup: Optional[Callable[[List[int]], object]] = None,
+        tagged: Optional[Callable[[Dict[str, float], int], Dict[str, float]]] = None) -> None:
     """``total`` steps in chunks of at most ``chunk`` that end on the evaluation boundaries (every ``every``
     steps); the losses of a chunk come back to the host once, after the next chunk has been queued.
 
-    ``steps(t, n)`` queues steps t .. t + n - 1 and returns the K loss tensors [n, 3]; ``group`` (a
-    ``SeedGroup`` or None) is synchronized before an evaluation.  ``evaluate(k, trainer, step)`` gives the
-    returns of seed k.  ``normalized(returns)``: the normalized scores, logged x 100; a ``ValueError`` from
-    it keeps what the seed had (at first the raw mean return), and a value once obtained stays.  The best
-    model is the one of the strictly greatest normalized score, or mean return without one or with
-    ``best_by_return``.  One ``logger(record, step)`` call per step and seed for the losses, then per
-    evaluation record."""
+    ``steps(t, n)`` queues steps t .. t + n - 1 and returns the loss tensors [n, 3] of the active members in
+    member order; ``group`` (a ``SeedGroup`` or None) is synchronized before an evaluation.
+    ``evaluate(k, trainer, step)`` gives the returns of member k.  ``normalized(returns)``: the normalized
+    scores, logged x 100 (one callable, or one per member); a ``ValueError`` from it keeps what the member had
+    (at first the raw mean return), and a value once obtained stays.  The best model is the one of the
+    strictly greatest normalized score, or mean return without one or with ``best_by_return``.  One
+    ``logger(record, step)`` call per step and member for the losses, then per evaluation record;
+    ``tagged(record, k)`` makes the record the logger gets (default: ``tag(seeds)``).
+
+    ``total`` / ``every`` may be one entry per member (a sweep's runs): all members start at step 0, a chunk
+    ends on the next evaluation boundary or end of ANY active member, and a member whose ``total`` is reached
+    leaves after its evaluation.  ``regroup(active)`` is then called with the member indices that go on; it
+    returns the group (or None) that ``steps`` drives from there.  With scalars every member is active to the
+    end and ``regroup`` is never called."""
     K = len(trainers)
-    tagged = tag(seeds)
+    totals = [int(total)] * K if np.ndim(total) == 0 else [int(x) for x in total]
+    everys = [int(every)] * K if np.ndim(every) == 0 else [int(x) for x in every]
+    norms = list(normalized) if isinstance(normalized, (list, tuple)) else [normalized] * K
+    if not len(totals) == len(everys) == len(norms) == K:
+        raise ValueError("total / every / normalized: one entry per member")
+    if tagged is None:
+        tagged = tag(seeds)
     best_score, best_step = [-np.inf] * K, [0] * K
     norm = [None] * K
-    pending = None  # (first step, [K] device losses) of the chunk whose records are still to be logged
+    pending = None  # (first step, members, their device losses) of the chunk whose records are still to be logged
 
     def flush():
         nonlocal pending
         if pending is None:
             return
-        t0, losses = pending
+        t0, members, losses = pending
         pending = None
-        for k, arr in enumerate(l.cpu().numpy() for l in losses):
+        for k, arr in zip(members, (l.cpu().numpy() for l in losses)):
             for i, (v, q, a) in enumerate(arr.tolist()):
                 logger(tagged({"value_loss": v, "q_loss": q, "actor_loss": a}, k), t0 + i)
 
+    active = [k for k in range(K) if totals[k] > 0]
+    if len(active) != K and active and regroup is not None:
+        group = regroup(list(active))
     t = 0
-    while t < total:
-        nxt = min(total, t + int(chunk), (t // every + 1) * every)
+    while active:
+        nxt = min(t + int(chunk), *[min(totals[k], (t // everys[k] + 1) * everys[k]) for k in active])
         losses = steps(t, nxt - t)
         flush()
-        pending = (t, losses)
+        pending = (t, list(active), losses)
         t = nxt
-        if t % every != 0:
-            continue
-        flush()
-        if group is not None:
-            group.synchronize()
+        due = [k for k in active if t % everys[k] == 0]
+        if due:
+            flush()
+            if group is not None:
+                group.synchronize()
         step = t - 1
-        for k, trainer in enumerate(trainers):
+        for k in due:
+            trainer = trainers[k]
             log = lambda d: logger(tagged(d, k), step)
             eval_scores = evaluate(k, trainer, step)
             mean_eval = eval_scores.mean()
             log({"evaluation_return": mean_eval})
-            if normalized is not None:
+            if norms[k] is not None:
                 try:
-                    norm[k] = np.asarray(normalized(eval_scores)).mean() * 100
+                    norm[k] = np.asarray(norms[k](eval_scores)).mean() * 100
                     log({"normalized_score": norm[k]})
                 except ValueError:
                     pass
@@ -117,4 +138,9 @@ def run(trainers: Sequence, seeds: Sequence[int], group, total: int, every: int,
             log({"best_step_so_far": best_step[k]})
             if ckpt_dirs[k] is not None:
                 torch.save(trainer.state_dict(), os.path.join(ckpt_dirs[k], f"checkpoint_{step}.pt"))
+        left = [k for k in active if t < totals[k]]
+        if len(left) != len(active):
+            active = left
+            if active and regroup is not None:
+                group = regroup(list(active))
     flush()

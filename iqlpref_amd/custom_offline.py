@@ -23,16 +23,27 @@ wandb) injectable, and ``seeds_per_gpu`` seeds side by side on one GPU.  Its set
 with ``custom_offline_br``; the train / evaluate / checkpoint loop itself is ``_offline_loop.run``, which
 the BB flavour runs too.
 
+``train_runs()`` trains a list of configs -- the runs of a pen sweep grid, which differ in the reward
+model and not in the seed -- each exactly as ``train()`` would train it alone, packed into seed groups:
+one relabel per distinct reward model, one device buffer per distinct preparation, one K-stream index draw
+and one group step per library call (``iqlpref_amd.sweep`` is the command line over it).
+
+Reward models travel as plain ``.npz`` files (``save_reward_params`` / ``load_reward_model``): the flax
+parameter tree as numpy arrays plus the constructor arguments, written on a machine that has jax.  A
+``reward_model_path`` that ends in ``.npz``, or has such a file beside it (``best_model.ckpt.npz``), is
+read from there when no model is handed in.
+
 Not built (stated): the Orbax / flax-nnx checkpoint readers ``load_PT`` / ``load_QMLP``
 (reward_models/pref_transformer.py:280-327, q_mlp.py:100-168) need orbax + jax, which are absent;
-``RewardPT.load_flax_params`` / ``QMLP.load_flax_params`` take the parameter pytree as numpy
-arrays instead.  PT numerics stay "parity unpinned" (no runnable reference, no fixtures).
+``load_pt_flax_params`` / ``QMLP.load_flax_params`` take the parameter pytree as numpy
+arrays instead, and the ``.npz`` interchange above carries it between machines.  PT numerics stay "parity unpinned" (no runnable reference, no fixtures).
 """
 import ctypes as C
+import json
 import uuid
 import os
-from dataclasses import dataclass
-from typing import Any, Callable, Dict, Iterable, List, Optional, Sequence, Tuple
+from dataclasses import dataclass, fields
+from typing import Any, Callable, Dict, Iterable, List, Mapping, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -44,7 +55,7 @@ from ._lib import check, ptr
 from .iql import DeterministicPolicy, GaussianPolicy, TwinQ, ValueFunction, compute_mean_std, normalize_states, set_seed
 from .iql import ImplicitQLearning as _OfflineIQL
 from .iql import ReplayBuffer as _OfflineReplayBuffer
-from .iql import mlp_forward_f32
+from .iql import _coerce, mlp_forward_f32
 from .relabel import RewardPT
 
 ACTIVATIONS = ("cos", "tanh", "relu", "softplus", "sin", "leaky_relu", "swish", "none")  # q_mlp.py:121-130
@@ -83,6 +94,25 @@ class TrainConfig:
         self.name = f"{self.name}-{self.dataset_id}-{str(uuid.uuid4())[:8]}"
         if self.checkpoints_path is not None:
             self.checkpoints_path = os.path.join(self.checkpoints_path, self.name)
+
+
+def load_config(config_path: Optional[str] = None, **overrides) -> TrainConfig:
+    """The pyrallis ``--config_path`` behaviour (cref:597) with ``iql.load_config``'s rules: YAML keys =
+    field names, unknown keys raise, values are coerced to the field's declared type; ``overrides`` beat
+    the file."""
+    import yaml
+    raw: Dict[str, Any] = {}
+    if config_path:
+        with open(config_path) as f:
+            raw.update(yaml.safe_load(f) or {})
+    raw.update(overrides)
+    known = {f.name: f for f in fields(TrainConfig)}
+    kwargs = {}
+    for k, v in raw.items():
+        if k not in known:
+            raise ValueError(f"unknown custom_offline.TrainConfig field {k!r}")
+        kwargs[k] = _coerce(v, known[k].type)
+    return TrainConfig(**kwargs)
 
 
 # --------------------------------------------------------------------------- #
@@ -147,6 +177,91 @@ def load_pt_flax_params(model: RewardPT, params: Dict[str, Any]) -> RewardPT:
     if bad or missing.unexpected_keys:
         raise KeyError(f"flax parameter tree does not match: missing {bad}, unexpected {missing.unexpected_keys}")
     return model
+
+
+# --------------------------------------------------------------------------- #
+# reward models as .npz files (the interchange that stands in for the Orbax readers)
+# --------------------------------------------------------------------------- #
+REWARD_KINDS = ("qmlp", "pt")
+_META = "__meta__"
+
+
+def _flatten_params(node, prefix: str, out: Dict[str, np.ndarray]):
+    items = node.items() if isinstance(node, Mapping) else enumerate(node)
+    for k, v in items:
+        name = f"{prefix}/{k}" if prefix else str(k)
+        if "/" in str(k) or name == _META:
+            raise ValueError(f"parameter key {k!r} cannot be stored")
+        if isinstance(v, (Mapping, list, tuple)):
+            _flatten_params(v, name, out)
+        else:
+            out[name] = np.asarray(v)
+
+
+def save_reward_params(path, kind: str, params, **ctor) -> str:
+    """Write a reward model as one ``.npz`` file that ``load_reward_model`` reads.
+
+    ``kind``: "qmlp" (``params``: the layers ``QMLP.load_flax_params`` takes, [{"kernel", "bias"}, ...]) or
+    "pt" (``params``: the flax-nnx tree ``load_pt_flax_params`` takes).  The arrays go in under ``/``-joined
+    keys (``0/kernel``, ``gpt/layers/0/attention/in_linear/kernel``); the one entry ``__meta__`` is a JSON
+    string {"kind": ..., "ctor": {...}} with the constructor arguments besides the dims (qmlp:
+    ``hidden_dims``, ``activations``, ``activation_final``; pt: ``max_episode_steps``, ``embd_dim``, ...).
+    The file is written at ``path`` exactly (no suffix is appended).  Returns the path."""
+    if kind not in REWARD_KINDS:
+        raise ValueError(f"kind must be among {REWARD_KINDS}")
+    arrays: Dict[str, np.ndarray] = {}
+    _flatten_params(params, "", arrays)
+    if not arrays:
+        raise ValueError("no parameters to write")
+    meta = json.dumps({"kind": kind, "ctor": ctor})
+    path = os.fspath(path)
+    with open(path, "wb") as f:
+        np.savez(f, **{_META: np.asarray(meta)}, **arrays)
+    return path
+
+
+def _read_reward_file(path) -> Tuple[Dict[str, Any], Dict[str, Any]]:
+    """(meta, parameter tree) of a ``save_reward_params`` file."""
+    with np.load(os.fspath(path), allow_pickle=False) as z:
+        if _META not in z.files:
+            raise ValueError(f"{path}: no {_META} entry (not written by save_reward_params)")
+        meta = json.loads(str(z[_META]))
+        tree: Dict[str, Any] = {}
+        for name in z.files:
+            if name == _META:
+                continue
+            node = tree
+            *parents, leaf = name.split("/")
+            for part in parents:
+                node = node.setdefault(part, {})
+            node[leaf] = z[name]
+    if meta.get("kind") not in REWARD_KINDS:
+        raise ValueError(f"{path}: kind {meta.get('kind')!r} is not among {REWARD_KINDS}")
+    return meta, tree
+
+
+def load_reward_model(path, state_dim: int, action_dim: int, device):
+    """The ``QMLP`` or ``RewardPT`` of a ``save_reward_params`` file, on ``device``."""
+    meta, tree = _read_reward_file(path)
+    ctor = dict(meta.get("ctor") or {})
+    if meta["kind"] == "qmlp":
+        layers = [tree[k] for k in sorted(tree, key=int)]
+        ctor.setdefault("hidden_dims", [int(l["kernel"].shape[1]) for l in layers[:-1]])
+        ctor["hidden_dims"] = tuple(int(h) for h in ctor["hidden_dims"])
+        return QMLP(state_dim, action_dim, **ctor).load_flax_params(layers).to(device)
+    if "max_episode_steps" not in ctor:
+        ctor["max_episode_steps"] = int(tree["timestep_embed"]["embedding"].shape[0]) - 1
+    return load_pt_flax_params(RewardPT(state_dim, action_dim, **ctor), tree).to(device)
+
+
+def reward_model_file(reward_model_path: str) -> Optional[str]:
+    """The ``.npz`` file a ``reward_model_path`` is read from when no model is handed in: the path itself
+    when it ends in ``.npz``, else ``<path>.npz`` when that exists (``best_model.ckpt`` ->
+    ``best_model.ckpt.npz``), else None."""
+    p = os.path.expanduser(str(reward_model_path))
+    if p.endswith(".npz"):
+        return p
+    return p + ".npz" if os.path.isfile(p + ".npz") else None
 
 
 # --------------------------------------------------------------------------- #
@@ -406,14 +521,16 @@ class ImplicitQLearning(_OfflineIQL):
 def _reward_model_missing(where: str, config, advice: str, readers: str):
     """``where`` got ``reward_model=None``: the reference would read an Orbax checkpoint with ``readers``,
     which are not built here.  ``advice``: what to pass instead."""
+    npz = (f", or export the parameters with custom_offline.save_reward_params to "
+           f"{os.path.expanduser(str(config.reward_model_path))}.npz (INTEGRATION.md)")
     try:
         import orbax.checkpoint  # noqa: F401
     except ImportError:
         raise ImportError(
             f"{where}: reward_model=None would read the Orbax checkpoint {config.reward_model_path!r}, "
-            f"but orbax is not installed (and iqlpref_amd has no Orbax reader); pass reward_model= {advice}") from None
+            f"but orbax is not installed (and iqlpref_amd has no Orbax reader); pass reward_model= {advice}{npz}") from None
     raise NotImplementedError(
-        f"{where}: iqlpref_amd has no Orbax checkpoint reader ({readers}); pass reward_model= {advice}")
+        f"{where}: iqlpref_amd has no Orbax checkpoint reader ({readers}); pass reward_model= {advice}{npz}")
 
 
 def _minari():
@@ -447,6 +564,24 @@ def _build_trainer(config, seed: int, state_dim: int, action_dim: int, limits: S
         iql_tau=config.iql_tau, beta=config.beta, gamma=config.gamma, tau=config.tau, device=device, seed=seed)
 
 
+def _prepare(config, qdataset: Dict[str, np.ndarray], eval_env, state_dim: int, action_dim: int, device):
+    """cref:631-653: the relabelled transitions (rewritten in place) -> the device buffer and the evaluation
+    environment that normalises its observations with the same mean / std."""
+    if config.normalize_reward:
+        modify_reward(qdataset, config.dataset_id)
+    if config.normalize_state:
+        state_mean, state_std = compute_mean_std(qdataset["observations"], eps=1e-3)
+    else:
+        state_mean, state_std = 0, 1
+    qdataset["observations"] = normalize_states(qdataset["observations"], state_mean, state_std)
+    qdataset["next_observations"] = normalize_states(qdataset["next_observations"], state_mean, state_std)
+    from .train import _NormalizedEnv
+    eval_env = _NormalizedEnv(eval_env, state_mean, state_std, 1.0)  # cref wrap_env, reward_scale 1
+    replay_buffer = ReplayBuffer(state_dim, action_dim, config.buffer_size, device)
+    replay_buffer.load_dataset(qdataset)
+    return replay_buffer, eval_env
+
+
 def train(config: TrainConfig, dataset=None, reward_model=None, eval_env=None, *,
           logger: Optional[Callable[[Dict[str, float], int], None]] = None,
           normalized_score: Optional[Callable] = None, seeds_per_gpu: int = 1, sampler: str = "device",
@@ -457,7 +592,8 @@ def train(config: TrainConfig, dataset=None, reward_model=None, eval_env=None, *
     ``terminations``); None loads ``config.dataset_id`` with minari.  ``eval_env``: a gymnasium-API
     environment (default: ``dataset.recover_environment()``).  ``reward_model``: a ``QMLP``
     (``query_length == 1``) or ``RewardPT`` holding its parameters; the Orbax checkpoint at
-    ``reward_model_path`` cannot be read here.  ``logger(record, step)``: one call per ``wandb.log``
+    ``reward_model_path`` cannot be read here; with None the model is read from the ``.npz`` file
+    ``reward_model_file(config.reward_model_path)`` names (``save_reward_params``).  ``logger(record, step)``: one call per ``wandb.log``
     of cref (default: wandb when importable, else print).  ``normalized_score(dataset, returns)``:
     default ``minari.get_normalized_score``; a ``ValueError`` from it keeps the raw mean return, as
     cref's ``contextlib.suppress`` does.  ``sampler``: "device" (``NumpyIndexStream``) or "host"
@@ -476,14 +612,17 @@ def train(config: TrainConfig, dataset=None, reward_model=None, eval_env=None, *
     if reward_model is not None:
         relabel = lambda ds: qlearning_dataset(ds, reward_model, config.query_length)
     return _train(config, dataset, eval_env, relabel, False, logger=logger, normalized_score=normalized_score,
-                  seeds_per_gpu=seeds_per_gpu, sampler=sampler, device=device, chunk=chunk)
+                  seeds_per_gpu=seeds_per_gpu, sampler=sampler, device=device, chunk=chunk,
+                  model_file=None if reward_model is not None else reward_model_file(config.reward_model_path))
 
 
 def _train(config, dataset, eval_env, relabel: Optional[Callable], best_by_return: bool, *, logger=None,
-           normalized_score=None, seeds_per_gpu: int = 1, sampler: str = "device", device=None, chunk: int = 2000):
+           normalized_score=None, seeds_per_gpu: int = 1, sampler: str = "device", device=None, chunk: int = 2000,
+           model_file: Optional[str] = None):
     """``train()`` with the two things a flavour chooses: ``relabel(dataset)`` builds the transition dict
-    (None: there is no reward model to build it with, which is reported after the other argument checks), and
-    ``best_by_return`` keeps the best model by the mean evaluation return even when a normalized score is
+    (None: there is no reward model to build it with, which is reported after the other argument checks --
+    unless ``model_file`` names a ``save_reward_params`` file, read once the dims and the device are known),
+    and ``best_by_return`` keeps the best model by the mean evaluation return even when a normalized score is
     logged (``custom_offline_br``)."""
     if sampler not in ("host", "device"):
         raise ValueError("sampler must be 'host' or 'device'")
@@ -506,27 +645,17 @@ def _train(config, dataset, eval_env, relabel: Optional[Callable], best_by_retur
             normalized_score = minari.get_normalized_score
         except ImportError:
             normalized_score = None
-    if relabel is None:
+    if relabel is None and model_file is None:
         _reward_model_missing("custom_offline.train", config,
                               "a QMLP or RewardPT holding its parameters (load_flax_params)", "load_QMLP / load_PT")
     state_dim = eval_env.observation_space.shape[0]
     action_dim = eval_env.action_space.shape[0]
     max_action = float(eval_env.action_space.high[0])
+    if relabel is None:
+        file_model = load_reward_model(model_file, state_dim, action_dim, device)
+        relabel = lambda ds: qlearning_dataset(ds, file_model, config.query_length)
 
-    # ---- dataset, normalisation, buffer (cref:631-653) ----
-    qdataset = relabel(dataset)
-    if config.normalize_reward:
-        modify_reward(qdataset, config.dataset_id)
-    if config.normalize_state:
-        state_mean, state_std = compute_mean_std(qdataset["observations"], eps=1e-3)
-    else:
-        state_mean, state_std = 0, 1
-    qdataset["observations"] = normalize_states(qdataset["observations"], state_mean, state_std)
-    qdataset["next_observations"] = normalize_states(qdataset["next_observations"], state_mean, state_std)
-    from .train import _NormalizedEnv
-    eval_env = _NormalizedEnv(eval_env, state_mean, state_std, 1.0)  # cref wrap_env, reward_scale 1
-    replay_buffer = ReplayBuffer(state_dim, action_dim, config.buffer_size, device)
-    replay_buffer.load_dataset(qdataset)
+    replay_buffer, eval_env = _prepare(config, relabel(dataset), eval_env, state_dim, action_dim, device)
 
     seeds = [D.rank_seed(config.train_seed, K) + k for k in range(K)]
     ckpt_dirs = _offline_loop.checkpoint_dirs(config, seeds)
@@ -564,3 +693,263 @@ def _train(config, dataset, eval_env, relabel: Optional[Callable], best_by_retur
         group.close()
         return trainers
     return trainers[0]
+
+
+# --------------------------------------------------------------------------- #
+# sweep grids: runs of different configs as seed groups
+# --------------------------------------------------------------------------- #
+def shape_key(config: TrainConfig, dims, device: str = "cuda") -> tuple:
+    """What the runs of one launch batch must share: state / action dims, batch size, policy kind, actor
+    dropout on/off and the device (the nets of this flavour are always 2 x 256, fp32, two critics).
+    ``dims`` = (S, A), or None when unknown (the dataset id stands in)."""
+    dims_key = tuple(int(d) for d in dims) if dims is not None else ("dataset", config.dataset_id)
+    return (dims_key, int(config.batch_size), bool(config.iql_deterministic), bool(config.actor_dropout), str(device))
+
+
+def plan_batches(configs: Sequence[TrainConfig], dims: Sequence, runs_per_gpu: int = 8,
+                 device: str = "cuda") -> List[List[int]]:
+    """``sweep.plan_batches`` with this flavour's ``shape_key``: launch batches as lists of config indices,
+    filled greedily in config order.  ``dims``: one (S, A) or None per config."""
+    from .sweep import plan_batches as plan
+    return plan(configs, list(dims), runs_per_gpu, key=lambda cfg, d: shape_key(cfg, d, device))
+
+
+def _relabel_key(config: TrainConfig) -> tuple:
+    return (config.dataset_id, config.reward_model_path, int(config.query_length))
+
+
+def _buffer_key(config: TrainConfig) -> tuple:
+    return (_relabel_key(config), bool(config.normalize_reward), bool(config.normalize_state), int(config.buffer_size))
+
+
+def _model_sources(configs: Sequence[TrainConfig], reward_models) -> Dict[tuple, Any]:
+    """Relabel key -> where the run's reward model comes from: the model itself (found in the mapping under
+    the path as written or expanded), ("file", path) for a ``save_reward_params`` file, or ("call",) for a
+    callable ``reward_models``.  No device work; raises for the paths that have no model and for a
+    ``query_length > 1`` whose model is known not to be a ``RewardPT``."""
+    sources: Dict[tuple, Any] = {}
+    missing, not_pt = [], []
+    for cfg in configs:
+        key = _relabel_key(cfg)
+        if key in sources:
+            continue
+        path = str(cfg.reward_model_path)
+        src, kind = None, None
+        if callable(reward_models) and not isinstance(reward_models, Mapping):
+            src = ("call",)
+        else:
+            for name in (path, os.path.expanduser(path)):
+                if reward_models is not None and name in reward_models:
+                    src = reward_models[name]
+                    kind = "pt" if isinstance(src, RewardPT) else "other"
+                    break
+            if src is None:
+                f = reward_model_file(path)
+                if f is not None and os.path.isfile(f):
+                    src, kind = ("file", f), _read_reward_file(f)[0]["kind"]
+        if src is None:
+            if path not in missing:
+                missing.append(path)
+            continue
+        if int(cfg.query_length) > 1 and kind not in (None, "pt"):
+            not_pt.append(path)
+        sources[key] = src
+    if missing:
+        raise ValueError(
+            "custom_offline.train_runs: no reward model for reward_model_path " + ", ".join(repr(m) for m in missing) +
+            "; hand them in with reward_models= (a mapping path -> QMLP | RewardPT, or a callable config -> model) or "
+            "export each with custom_offline.save_reward_params to <path>.npz (iqlpref_amd has no Orbax reader)")
+    if not_pt:
+        raise TypeError("query_length > 1 needs an iqlpref_amd RewardPT; not one: " + ", ".join(repr(m) for m in not_pt))
+    return sources
+
+
+def train_runs(configs: Sequence[TrainConfig], dataset=None, reward_models=None, eval_env=None, *,
+               runs_per_gpu: int = 8, logger: Optional[Callable[[Dict[str, float], int], None]] = None,
+               normalized_score: Optional[Callable] = None, sampler: str = "device", chunk: int = 2000,
+               run_ids: Optional[Sequence[int]] = None) -> List[ImplicitQLearning]:
+    """Train every config exactly as ``train(config, ...)`` would train it alone -- the same logged records
+    (each with a ``run`` entry besides), evaluations (own actor, ``eval_seed``, ``eval_episodes``, the
+    best-model rule of ``_offline_loop.run``), files under the run's own ``checkpoints_path``
+    (``config.yaml``, ``checkpoint_{step}.pt``, ``best_model.pt``) and final parameters, target, Adam
+    moments and actor learning rate, bit for bit -- with the runs packed into seed groups.
+
+    Launch batches (``plan_batches``): runs of one ``shape_key`` (dims, ``batch_size``,
+    ``iql_deterministic``, actor dropout on/off, device), at most ``runs_per_gpu`` (1..16) in config order,
+    one batch after another.  Inside a batch everything else may differ: the reward model, the dataset when
+    its dims match, ``train_seed`` / ``eval_seed`` / ``eval_episodes``, ``gamma``, ``tau``, ``beta``,
+    ``iql_tau``, the learning rates, the dropout rate, ``normalize_reward`` / ``normalize_state``,
+    ``update_steps`` and ``eval_every``.  All runs of a batch start at step 0; every library call runs to
+    the next chunk, evaluation or end boundary of ANY active run; a finished run leaves and the group is
+    rebuilt over the rest.  A batch of one run steps its trainer directly, with no ``SeedGroup``.
+
+    Shared work: the dataset is relabelled once per distinct (``dataset_id``, ``reward_model_path``,
+    ``query_length``), and one device buffer -- with its state mean / std and its normalising evaluation
+    environment -- is built per distinct (that key, ``normalize_reward``, ``normalize_state``,
+    ``buffer_size``); both are dropped after the last batch that uses them.  Per run: nets built right after
+    ``torch.manual_seed(train_seed)``, an ``np.random.RandomState(train_seed)`` index stream of its own
+    (two runs of one seed draw the same indices, as they would alone) below the bound of its own buffer.
+
+    ``dataset``: one re-iterable of episodes for every run, a mapping ``dataset_id -> iterable``, or None
+    (one ``minari.load_dataset`` per distinct id).  ``eval_env``: one environment, a mapping
+    ``dataset_id -> env``, or None (``recover_environment()``).  ``reward_models``: a mapping
+    ``reward_model_path -> QMLP | RewardPT`` (paths matched as the config writes them and after
+    ``expanduser``) or a callable ``config -> model`` (called once per distinct relabel); a path that has no
+    entry, and every path with None, is read from its ``.npz`` file (``reward_model_file``).
+    ``logger(record, step)``: default one wandb run per process with keys ``run<r>/``, or print.
+    ``run_ids``: the names of the runs in the records (default 0 .. n-1).
+
+    Before any device work: ``runs_per_gpu`` in range, no two runs with one ``checkpoints_path``, a reward
+    model for every run (the error names the paths without), a ``RewardPT`` where ``query_length > 1``.
+
+    numpy's global generator is no part of this function's contract: ``train()`` alone draws its indices
+    from it (and leaves it advanced); ``train_runs`` draws the same numbers from per-run generators and
+    neither seeds nor reads the global one.
+
+    Under torchrun rank r trains the configs with index = r (mod world size), with no collectives.
+    Returns this rank's trainers in config order."""
+    from . import sweep as SW
+    configs = list(configs)
+    SW.check_runs(configs, runs_per_gpu)
+    if sampler not in ("host", "device"):
+        raise ValueError("sampler must be 'host' or 'device'")
+    n = len(configs)
+    run_ids = list(range(n)) if run_ids is None else [int(r) for r in run_ids]
+    if len(run_ids) != n:
+        raise ValueError("run_ids: one entry per config")
+    sources = _model_sources(configs, reward_models)
+    rank, world = SW._rank_world()
+    mine = SW.rank_share(n, rank, world)
+    if not mine:
+        return []
+    device = D.local_device() or "cuda:0"
+
+    # ---- datasets and environments of this rank's runs ----
+    ids = list(dict.fromkeys(configs[i].dataset_id for i in mine))
+    minari = None
+    if dataset is None:
+        minari = _minari()
+        datasets = {d: minari.load_dataset(d) for d in ids}
+    elif isinstance(dataset, Mapping):
+        lacking = [d for d in ids if d not in dataset]
+        if lacking:
+            raise ValueError(f"no dataset given for {', '.join(lacking)}")
+        datasets = {d: dataset[d] for d in ids}
+    else:
+        datasets = {d: dataset for d in ids}
+    if isinstance(eval_env, Mapping):
+        lacking = [d for d in ids if d not in eval_env]
+        if lacking:
+            raise ValueError(f"no eval_env given for {', '.join(lacking)}")
+        envs = {d: eval_env[d] for d in ids}
+    elif eval_env is not None:
+        envs = {d: eval_env for d in ids}
+    else:
+        envs = {}
+        for d in ids:
+            if not hasattr(datasets[d], "recover_environment"):
+                raise ValueError(f"custom_offline.train_runs: pass eval_env= (the dataset of {d} cannot "
+                                 "recover_environment())")
+            envs[d] = datasets[d].recover_environment()
+    if normalized_score is None:
+        try:
+            minari = minari or _minari()
+            normalized_score = minari.get_normalized_score
+        except ImportError:
+            normalized_score = None
+    dims = {d: (envs[d].observation_space.shape[0], envs[d].action_space.shape[0]) for d in ids}
+    local = plan_batches([configs[i] for i in mine], [dims[configs[i].dataset_id] for i in mine], runs_per_gpu, device)
+    batches = [[mine[j] for j in b] for b in local]
+    if logger is None:
+        logger = SW._default_logger(configs, mine, run_ids)
+
+    # ---- relabelled datasets and device buffers: built when a batch first needs them, dropped after their last ----
+    rkeys = {i: _relabel_key(configs[i]) for i in mine}
+    bkeys = {i: _buffer_key(configs[i]) for i in mine}
+    last_use_r, last_use_b = {}, {}
+    for bi, b in enumerate(batches):
+        for i in b:
+            last_use_r[rkeys[i]], last_use_b[bkeys[i]] = bi, bi
+    relabelled: Dict[tuple, Dict[str, np.ndarray]] = {}
+    buffers: Dict[tuple, Tuple[ReplayBuffer, Any]] = {}
+
+    def buffer_for(i):
+        cfg = configs[i]
+        if bkeys[i] not in buffers:
+            S, A = dims[cfg.dataset_id]
+            if rkeys[i] not in relabelled:
+                src = sources[rkeys[i]]
+                if isinstance(src, tuple) and src[0] == "call":
+                    model = reward_models(cfg)
+                elif isinstance(src, tuple) and src[0] == "file":
+                    model = load_reward_model(src[1], S, A, device)
+                else:
+                    model = src
+                relabelled[rkeys[i]] = qlearning_dataset(datasets[cfg.dataset_id], model, cfg.query_length)
+            # (_prepare rewrites its dict, and the rewards in place: every preparation gets its own)
+            qd = dict(relabelled[rkeys[i]])
+            qd["rewards"] = qd["rewards"].copy()
+            buffers[bkeys[i]] = _prepare(cfg, qd, envs[cfg.dataset_id], S, A, device)
+        return buffers[bkeys[i]]
+
+    stream = NumpyIndexStream(device) if sampler == "device" else None
+    trainers: Dict[int, ImplicitQLearning] = {}
+    for bi, batch in enumerate(batches):
+        prepared = [buffer_for(i) for i in batch]
+        ckpt_dirs = [_offline_loop.checkpoint_dirs(configs[i], [configs[i].train_seed])[0] for i in batch]
+        for i in batch:
+            cfg, e = configs[i], envs[configs[i].dataset_id]
+            S, A = dims[cfg.dataset_id]
+            trainers[i] = _build_trainer(cfg, cfg.train_seed, S, A, (float(e.action_space.high[0]),), device)
+        _run_batch([configs[i] for i in batch], [trainers[i] for i in batch], [p[0] for p in prepared],
+                   [p[1] for p in prepared], [run_ids[i] for i in batch], ckpt_dirs, stream, logger, chunk, device,
+                   [None if normalized_score is None else
+                    (lambda scores, ds=datasets[configs[i].dataset_id]: normalized_score(ds, scores)) for i in batch])
+        del prepared
+        for key in [k for k in relabelled if last_use_r[k] <= bi]:
+            del relabelled[key]
+        for key in [k for k in buffers if last_use_b[k] <= bi]:
+            del buffers[key]
+    return [trainers[i] for i in mine]
+
+
+def _run_batch(configs, trainers, bufs, envs, ids, ckpt_dirs, stream, logger, chunk, device, normalized):
+    """One launch batch through ``_offline_loop.run``: member k has its own buffer, bound, generator, step
+    count and evaluation period; the group is rebuilt when a member leaves, and one member alone steps its
+    trainer directly."""
+    from .multi import SeedGroup
+    B = int(configs[0].batch_size)
+    gens = [np.random.RandomState(cfg.train_seed) for cfg in configs]
+    now = {"active": list(range(len(trainers))), "group": None}
+
+    def regroup(active):
+        if now["group"] is not None:
+            now["group"].synchronize()
+            now["group"].close()
+        now["active"] = list(active)
+        now["group"] = SeedGroup([trainers[k] for k in active]) if len(active) > 1 else None
+        return now["group"]
+
+    def steps(t, n):
+        act = now["active"]
+        if stream is not None:
+            idx = stream.draw([bufs[k].index_bound() for k in act], n, B, [gens[k] for k in act])
+        else:
+            idx = [torch.from_numpy(bufs[k].draw_indices(B, n, rng=gens[k])).to(trainers[k]._dev) for k in act]
+        if now["group"] is None:
+            return [trainers[act[0]].train_steps(bufs[act[0]], n, B, indices=idx[0])]
+        return now["group"].train_steps([bufs[k] for k in act], n, B, indices=idx, return_losses=True)
+
+    try:
+        _offline_loop.run(
+            trainers, [cfg.train_seed for cfg in configs], regroup(now["active"]),
+            [int(cfg.update_steps) for cfg in configs], [int(cfg.eval_every) for cfg in configs], chunk, logger,
+            ckpt_dirs, steps,
+            evaluate=lambda k, trainer, step: evaluate(envs[k], trainer.actor, configs[k].eval_episodes,
+                                                       configs[k].eval_seed, device),
+            normalized=normalized, regroup=regroup, tagged=lambda rec, k: dict(rec, run=ids[k]))
+    finally:
+        if now["group"] is not None:
+            now["group"].synchronize()
+            now["group"].close()
+    torch.cuda.current_stream(trainers[0]._dev).synchronize()

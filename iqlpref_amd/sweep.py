@@ -16,6 +16,13 @@ run each.  Here one process takes the whole grid:
 ``python -m iqlpref_amd.sweep SWEEP.yaml [--list] [--only i,j] [--runs_per_gpu K] [--field value]``
     the command line over both.
 
+Two flavours of sweep file.  A file whose ``program`` ends in ``custom_offline/iql.py`` (the six pen sweeps,
+``mr_sweeps/sweep_pen_*_pref.yaml`` and ``pt_sweeps/sweep_pen_*_pt.yaml``) is a custom-flavour sweep: its
+names are those of ``custom_offline.TrainConfig``, ``expand_sweep`` builds configs of that class through
+``custom_offline.load_config``, and the command line trains them with ``custom_offline.train_runs`` (runs
+that differ in the reward model, not the seed, as one seed group).  Every other ``program`` value, and none,
+is an offline sweep as before.
+
 The W&B service itself (agents, the sweep server, random / bayes search) stays out.
 """
 import argparse
@@ -29,7 +36,7 @@ from typing import Any, Callable, Dict, List, Mapping, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, custom_offline
 from . import distributed as D
 from ._offline_loop import checkpoint_dirs
 from .iql import ImplicitQLearning, TrainConfig, load_config
@@ -40,6 +47,8 @@ LABEL_KEYS = ("program", "project", "name", "description", "metric", "command", 
 # the fields build_dataset reads besides the environment: runs equal in all of them share one relabel
 RELABEL_FIELDS = ("reward_model_path", "query_length", "bnn_reward_model", "bnn_alpha", "bnn_n_samples",
                   "mr_ensemble", "mr_alpha", "mr_burn_in")
+# a sweep file whose ``program`` ends in this runs the Minari custom-offline flavour (custom_offline.py)
+CUSTOM_PROGRAM = "custom_offline/iql.py"
 # observation / action sizes of the D4RL task families the reference's sweeps name (for --list
 # without gym; training always reads them from the environment itself)
 D4RL_DIMS = {"antmaze": (29, 8), "pen": (45, 24), "door": (39, 28), "hammer": (46, 26), "relocate": (39, 30),
@@ -61,10 +70,22 @@ def load_sweep(spec_or_path: Union[str, os.PathLike, Mapping]) -> Dict[str, Any]
     return spec
 
 
+def is_custom_sweep(spec: Mapping) -> bool:
+    """Whether the sweep file runs ``algorithms/custom_offline/iql.py`` (told from its ``program`` key)."""
+    return str(spec.get("program") or "").endswith(CUSTOM_PROGRAM)
+
+
+def _flavour(spec: Mapping):
+    """(TrainConfig class, load_config) of the flavour the sweep file runs."""
+    if is_custom_sweep(spec):
+        return custom_offline.TrainConfig, custom_offline.load_config
+    return TrainConfig, load_config
+
+
 def sweep_axes(spec: Mapping) -> List[Tuple[str, List[Any]]]:
     """The grid's parameters in file order: [(name, [values...])].  Only ``method: grid`` with
-    ``{value: x}`` / ``{values: [...]}`` entries; every name must be a TrainConfig field or
-    ``config_path`` (all unknown names are reported together)."""
+    ``{value: x}`` / ``{values: [...]}`` entries; every name must be a field of the flavour's TrainConfig
+    (``is_custom_sweep``) or ``config_path`` (all unknown names are reported together)."""
     method = spec.get("method")
     if method != "grid":
         raise ValueError(f"sweep method {method!r}: only 'grid' is supported (random / bayes search needs the "
@@ -75,7 +96,7 @@ def sweep_axes(spec: Mapping) -> List[Tuple[str, List[Any]]]:
     params = spec.get("parameters") or {}
     if not isinstance(params, Mapping):
         raise ValueError("'parameters' must map names to {value: x} or {values: [...]}")
-    known = {f.name for f in fields(TrainConfig)} | {"config_path"}
+    known = {f.name for f in fields(_flavour(spec)[0])} | {"config_path"}
     axes, unknown = [], []
     for name, entry in params.items():
         if not isinstance(entry, Mapping) or len(entry) != 1 or next(iter(entry)) not in ("value", "values"):
@@ -98,7 +119,8 @@ def sweep_axes(spec: Mapping) -> List[Tuple[str, List[Any]]]:
 
 
 def expand_sweep(spec_or_path, *, config_root: str = ".", **overrides) -> List[TrainConfig]:
-    """One TrainConfig per run of a W&B grid sweep.
+    """One TrainConfig per run of a W&B grid sweep (``custom_offline.TrainConfig`` for a custom-flavour
+    file, ``is_custom_sweep``).
 
     Order: the cartesian product of the parameters in the order the file lists them, the LAST
     parameter varying fastest (``a: [1, 2]``, ``b: [x, y]`` -> (1, x), (1, y), (2, x), (2, y)).
@@ -110,7 +132,8 @@ def expand_sweep(spec_or_path, *, config_root: str = ".", **overrides) -> List[T
     carries ``sweep_label``: the varying parameters of its run, e.g. ``normalize_reward=3,seed=0``."""
     spec = load_sweep(spec_or_path)
     axes = sweep_axes(spec)
-    known = {f.name for f in fields(TrainConfig)} | {"config_path"}
+    config_cls, load = _flavour(spec)
+    known = {f.name for f in fields(config_cls)} | {"config_path"}
     bad = [k for k in overrides if k not in known]
     if bad:
         raise ValueError(f"unknown overrides (not TrainConfig fields): {', '.join(bad)}")
@@ -123,7 +146,7 @@ def expand_sweep(spec_or_path, *, config_root: str = ".", **overrides) -> List[T
         run.update(overrides)
         cp = run.pop("config_path", None)
         path = None if cp is None else os.path.join(config_root, os.path.expanduser(str(cp)))
-        cfg = load_config(path, **run)
+        cfg = load(path, **run)
         cfg.sweep_label = label  # (an attribute, not a field: config.yaml stays what train() writes)
         out.append(cfg)
     return out
@@ -149,21 +172,24 @@ def _check_runs_per_gpu(runs_per_gpu: int) -> int:
     return k
 
 
-def plan_batches(configs: Sequence[TrainConfig], dims, runs_per_gpu: int = 8,
-                 precision: str = "bf16") -> List[List[int]]:
+def plan_batches(configs: Sequence, dims, runs_per_gpu: int = 8, precision: str = "bf16", *,
+                 key: Optional[Callable[[Any, Any], tuple]] = None) -> List[List[int]]:
     """Launch batches as lists of config indices, in the order they run.  Runs of equal
     ``shape_key`` are taken greedily in config order into batches of at most ``runs_per_gpu``; a
     batch's position is that of its first run.  ``dims``: one (S, A) per config, or a mapping
-    env name -> (S, A) (entries may be None, see ``shape_key``)."""
+    env name -> (S, A) (entries may be None, see ``shape_key``).  ``key(config, dims)``: the shape key
+    of another flavour's configs (default: ``shape_key`` at ``precision``)."""
     k = _check_runs_per_gpu(runs_per_gpu)
+    if key is None:
+        key = lambda cfg, d: shape_key(cfg, d, precision)
     open_batch: Dict[tuple, List[int]] = {}
     batches: List[List[int]] = []
     for i, cfg in enumerate(configs):
         d = dims.get(cfg.env) if isinstance(dims, Mapping) else dims[i]
-        key = shape_key(cfg, d, precision)
-        b = open_batch.get(key)
+        shape = key(cfg, d)
+        b = open_batch.get(shape)
         if b is None or len(b) >= k:
-            b = open_batch[key] = []
+            b = open_batch[shape] = []
             batches.append(b)
         b.append(i)
     return batches
@@ -174,7 +200,7 @@ def rank_share(n_configs: int, rank: int, world_size: int) -> List[int]:
     return list(range(int(rank), int(n_configs), max(int(world_size), 1)))
 
 
-def check_runs(configs: Sequence[TrainConfig], runs_per_gpu: int) -> None:
+def check_runs(configs: Sequence, runs_per_gpu: int) -> None:
     """The checks train_runs makes before any device work."""
     _check_runs_per_gpu(runs_per_gpu)
     seen: Dict[str, int] = {}
@@ -207,14 +233,17 @@ def _next_boundary(config: TrainConfig, t: int) -> int:
 # --------------------------------------------------------------------------- #
 # training
 # --------------------------------------------------------------------------- #
-def _default_logger(configs: Sequence[TrainConfig], mine: Sequence[int], run_ids: Sequence[int]):
+def _default_logger(configs: Sequence, mine: Sequence[int], run_ids: Sequence[int]):
     """One wandb run per process, the records of run i under ``run<i>/`` (with its own step axis:
-    every launch batch starts again at step 0); without wandb the records are printed."""
+    every launch batch starts again at step 0); without wandb the records are printed.  (The records of the
+    custom flavour carry ``run`` and no ``seed``.)"""
     try:
         import wandb
     except ImportError:
-        return lambda d, step: print(f"[run {d['run']} seed {d['seed']}] [{step}] " +
-                                     " ".join(f"{n}={v:.5g}" for n, v in d.items() if n not in ("run", "seed")))
+        def show(d, step):
+            who = f"run {d['run']}" + (f" seed {d['seed']}" if "seed" in d else "")
+            print(f"[{who}] [{step}] " + " ".join(f"{n}={v:.5g}" for n, v in d.items() if n not in ("run", "seed")))
+        return show
     first = configs[mine[0]]
     wandb.init(config={f"run{run_ids[i]}": asdict(configs[i]) for i in mine}, project=first.project,
                group=first.group, name=first.name)
@@ -433,6 +462,14 @@ def _list_dims(env_name: str):
     return None  # unknown family: batched by env name
 
 
+def _list_dims_custom(dataset_id: str):
+    """Dims of a Minari dataset id from the D4RL family inside it (``D4RL/pen/human-v2`` -> pen)."""
+    for part in str(dataset_id).lower().replace("-", "/").split("/"):
+        if part in D4RL_DIMS:
+            return D4RL_DIMS[part]
+    return None  # unknown family: batched by dataset id
+
+
 def main(argv=None):
     """python -m iqlpref_amd.sweep SWEEP.yaml [--config_root DIR] [--runs_per_gpu K] [--only 0,3,5]
     [--list] [--field value ...]"""
@@ -449,6 +486,11 @@ def main(argv=None):
                     help="SeedGroup mode of every launch batch (default: the SeedGroup default; 'general': one launch "
                          "sequence for batches on the general layer-wise step)")
     args, rest = ap.parse_known_args(argv)
+    custom = is_custom_sweep(load_sweep(args.sweep))
+    if custom and args.group_mode is not None:
+        raise SystemExit(f"--group_mode: {args.sweep} is a custom-flavour sweep (program: ...{CUSTOM_PROGRAM}), whose "
+                         "launch batches always run the SeedGroup default (fp32, 2 x 256 nets: there is no general "
+                         "step to choose); drop the option")
     configs = expand_sweep(args.sweep, config_root=args.config_root, **parse_overrides(rest))
     ids = list(range(len(configs)))
     if args.only:
@@ -457,6 +499,16 @@ def main(argv=None):
         if bad:
             raise SystemExit(f"--only: no run {bad} (the sweep has {len(configs)})")
     chosen = [configs[i] for i in ids]
+    if custom:
+        if args.list:
+            batches = custom_offline.plan_batches(chosen, [_list_dims_custom(c.dataset_id) for c in chosen],
+                                                  args.runs_per_gpu)
+            where = {j: b for b, members in enumerate(batches) for j in members}
+            for j, i in enumerate(ids):
+                print(f"{i}\t{configs[i].sweep_label or '-'}\tbatch {where[j]}")
+            return
+        custom_offline.train_runs(chosen, runs_per_gpu=args.runs_per_gpu, run_ids=ids)
+        return
     if args.list:
         batches = plan_batches(chosen, [_list_dims(c.env) for c in chosen], args.runs_per_gpu)
         where = {j: b for b, members in enumerate(batches) for j in members}
