@@ -15,12 +15,18 @@ from typing import Callable, Dict, List, Optional, Sequence, Union
 import numpy as np
 import torch
 
+from . import _resume
+
 Logger = Callable[[Dict[str, float], int], None]
 
 
-def checkpoint_dirs(config, seeds: Sequence[int]) -> List[Optional[str]]:
+def checkpoint_dirs(config, seeds: Sequence[int], resume: bool = False) -> List[Optional[str]]:
     """The checkpoint directory of every seed (None each without ``config.checkpoints_path``): the path
-    itself for one seed, ``seed_<seed>/`` under it for several.  Makes them and writes ``config.yaml``."""
+    itself for one seed, ``seed_<seed>/`` under it for several.  Makes them and writes ``config.yaml``.
+    ``resume``: first ``_resume.check_config`` -- ValueError without a ``checkpoints_path``, or when the
+    ``config.yaml`` already there was written for another config (paths aside)."""
+    if resume:
+        _resume.check_config(config)
     if config.checkpoints_path is None:
         return [None] * len(seeds)
     print(f"Checkpoints path: {config.checkpoints_path}")
@@ -61,7 +67,9 @@ def run(trainers: Sequence, seeds: Sequence[int], group, total: Union[int, Seque
         steps: Callable[[int, int], List[torch.Tensor]], evaluate: Callable[[int, object, int], np.ndarray],
         normalized: Union[None, Callable, Sequence[Optional[Callable]]] = None, best_by_return: bool = False, *,
         regroup: Optional[Callable[[List[int]], object]] = None,
-        tagged: Optional[Callable[[Dict[str, float], int], Dict[str, float]]] = None) -> None:
+        tagged: Optional[Callable[[Dict[str, float], int], Dict[str, float]]] = None,
+        resume: bool = False, sampler_state: Optional[Callable[[int], object]] = None,
+        set_sampler_state: Optional[Callable[[int, object], None]] = None) -> None:
     """``total`` steps in chunks of at most ``chunk`` that end on the evaluation boundaries (every ``every``
     steps); the losses of a chunk come back to the host once, after the next chunk has been queued.
 
@@ -78,7 +86,22 @@ def run(trainers: Sequence, seeds: Sequence[int], group, total: Union[int, Seque
     ends on the next evaluation boundary or end of ANY active member, and a member whose ``total`` is reached
     leaves after its evaluation.  ``regroup(active)`` is then called with the member indices that go on; it
     returns the group (or None) that ``steps`` drives from there.  With scalars every member is active to the
-    end and ``regroup`` is never called."""
+    end and ``regroup`` is never called.
+
+    ``resume`` (every entry of ``ckpt_dirs`` must be a directory, else ValueError): at the end of every
+    boundary at which a member evaluated or left -- after the evaluations, records and ``checkpoint_{step}.pt``
+    files of all due members -- every member active in the chunk, due or not, writes one file of a resume
+    generation (``_resume``) at the common step: its ``trainer.resume_state()``, ``sampler_state(k)`` (what
+    its index sampler needs to stand where it stands now; ``steps`` draws exactly the steps it queues, so
+    nothing is drawn ahead of the boundary), its best score and step, its kept normalized score and whether
+    it has finished.  No loss record is pending then.  And the loop starts from the newest complete
+    generation (``_resume.latest``) instead of step 0: every member is restored with
+    ``trainer.load_resume_state`` and ``set_sampler_state(k, state)``, files of later, incomplete
+    generations are removed, finished members are neither trained nor evaluated again, and ``regroup`` is
+    handed the members that go on.  Without any generation the run starts at step 0; members that
+    hold generations of different steps and none in common were not interrupted together: ValueError, and their
+    files stay (``_resume.restore``).  Without ``resume``
+    nothing of this happens and no such file is written."""
     K = len(trainers)
     totals = [int(total)] * K if np.ndim(total) == 0 else [int(x) for x in total]
     everys = [int(every)] * K if np.ndim(every) == 0 else [int(x) for x in every]
@@ -101,10 +124,30 @@ def run(trainers: Sequence, seeds: Sequence[int], group, total: Union[int, Seque
             for i, (v, q, a) in enumerate(arr.tolist()):
                 logger(tagged({"value_loss": v, "q_loss": q, "actor_loss": a}, k), t0 + i)
 
-    active = [k for k in range(K) if totals[k] > 0]
+    t = 0
+    finished = set()
+    kept: Dict[int, int] = {}  # member -> step of the generation file it holds
+    if resume:
+        t, payloads = _resume.restore(ckpt_dirs, kept, [k for k in range(K) if totals[k] > 0])
+        for k, p in payloads.items():
+            trainers[k].load_resume_state(p["trainer"])
+            if set_sampler_state is not None:
+                set_sampler_state(k, p["sampler"])
+            best_score[k], best_step[k], norm[k] = p["loop"]["best_score"], p["loop"]["best_step"], p["loop"]["norm"]
+            if p["finished"]:
+                finished.add(k)
+
+    def commit(members):
+        flush()
+        payloads = {k: {"finished": t >= totals[k], "trainer": trainers[k].resume_state(),
+                        "sampler": None if sampler_state is None else sampler_state(k),
+                        "loop": {"best_score": float(best_score[k]), "best_step": int(best_step[k]),
+                                 "norm": None if norm[k] is None else float(norm[k])}} for k in members}
+        _resume.commit(ckpt_dirs, t, payloads, kept)
+
+    active = [k for k in range(K) if t < totals[k] and k not in finished]
     if len(active) != K and active and regroup is not None:
         group = regroup(list(active))
-    t = 0
     while active:
         nxt = min(t + int(chunk), *[min(totals[k], (t // everys[k] + 1) * everys[k]) for k in active])
         losses = steps(t, nxt - t)
@@ -139,6 +182,10 @@ def run(trainers: Sequence, seeds: Sequence[int], group, total: Union[int, Seque
             if ckpt_dirs[k] is not None:
                 torch.save(trainer.state_dict(), os.path.join(ckpt_dirs[k], f"checkpoint_{step}.pt"))
         left = [k for k in active if t < totals[k]]
+        if resume and (due or len(left) != len(active)):
+            if not due and group is not None:
+                group.synchronize()
+            commit(active)
         if len(left) != len(active):
             active = left
             if active and regroup is not None:

@@ -49,7 +49,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib, _offline_loop
+from . import _lib, _offline_loop, _resume
 from . import distributed as D
 from ._lib import check, ptr
 from .iql import DeterministicPolicy, GaussianPolicy, TwinQ, ValueFunction, compute_mean_std, normalize_states, set_seed
@@ -372,6 +372,23 @@ def unpack_np_state(packed: np.ndarray, like) -> tuple:
     return ("MT19937", packed[:624].copy(), int(packed[624]), int(like[3]), float(like[4]))
 
 
+def generator_state(gen=None) -> Dict[str, Any]:
+    """The state of an ``np.random.RandomState`` (None: numpy's global generator) as a resume generation
+    stores it: the MT19937 key as an int64 tensor, the position and the cached gaussian."""
+    st = (np.random if gen is None else gen).get_state(legacy=True)
+    if st[0] != "MT19937":
+        raise ValueError(f"not a legacy MT19937 state: {st[0]!r}")
+    return {"key": torch.from_numpy(np.asarray(st[1]).astype(np.int64)), "pos": int(st[2]), "has_gauss": int(st[3]),
+            "cached_gaussian": float(st[4])}
+
+
+def set_generator_state(gen, state: Mapping[str, Any]) -> None:
+    """Put a generator (None: numpy's global one) where ``generator_state`` found it."""
+    (np.random if gen is None else gen).set_state(
+        ("MT19937", state["key"].numpy().astype(np.uint32), int(state["pos"]), int(state["has_gauss"]),
+         float(state["cached_gaussian"])))
+
+
 class NumpyIndexStream:
     """``np.random.randint(0, hi, size=B)`` n times, for K generators at once, on the device.
 
@@ -585,7 +602,7 @@ def _prepare(config, qdataset: Dict[str, np.ndarray], eval_env, state_dim: int, 
 def train(config: TrainConfig, dataset=None, reward_model=None, eval_env=None, *,
           logger: Optional[Callable[[Dict[str, float], int], None]] = None,
           normalized_score: Optional[Callable] = None, seeds_per_gpu: int = 1, sampler: str = "device",
-          device: Optional[str] = None, chunk: int = 2000):
+          device: Optional[str] = None, chunk: int = 2000, resume: bool = False):
     """cref:597-749 on the fused HIP step.
 
     ``dataset``: an iterable of Minari-style episodes (``observations``, ``actions``,
@@ -607,18 +624,31 @@ def train(config: TrainConfig, dataset=None, reward_model=None, eval_env=None, *
     stream ``np.random.seed(seed)`` gives), its own checkpoints under ``seed_<seed>/`` and a ``seed``
     entry in its logger records; all K share one buffer and step as one ``SeedGroup`` with the
     indices of one K-stream draw.  Every seed is bit-identical to ``train()`` of that seed alone.
-    Returns the trainer (K = 1) or the list of K trainers."""
+    Returns the trainer (K = 1) or the list of K trainers.
+
+    ``resume`` (needs ``checkpoints_path``, and the ``config.yaml`` there, if any, must have been written for
+    the same config, paths aside; ValueError otherwise): at the end of every evaluation boundary every seed
+    writes ``resume_{t}.pt`` into its checkpoint directory -- its trainer's ``resume_state()`` (with the target
+    critics and the dropout counters), the state of its numpy generator (which stands exactly after the
+    draws of step t: a chunk draws the steps it queues and ends on the boundary) and its best score / step and
+    kept normalized score -- and the run starts from the newest complete generation instead of step 0
+    (``_offline_loop.run``).  A run killed at any moment and started again with the same arguments logs the
+    records and writes the files of the uninterrupted run from there on and returns the same trainers, bit for
+    bit; the generators end where the uninterrupted run's end.  The dataset, the reward model and the
+    evaluation environment must be the same again; an environment that keeps state of its own from one
+    evaluation to the next is outside the contract.  ``custom_offline_br`` and ``custom_offline_bb`` do not
+    resume (their relabel draws and block permutations come from global generators ahead of the loop)."""
     relabel = None
     if reward_model is not None:
         relabel = lambda ds: qlearning_dataset(ds, reward_model, config.query_length)
     return _train(config, dataset, eval_env, relabel, False, logger=logger, normalized_score=normalized_score,
-                  seeds_per_gpu=seeds_per_gpu, sampler=sampler, device=device, chunk=chunk,
+                  seeds_per_gpu=seeds_per_gpu, sampler=sampler, device=device, chunk=chunk, resume=resume,
                   model_file=None if reward_model is not None else reward_model_file(config.reward_model_path))
 
 
 def _train(config, dataset, eval_env, relabel: Optional[Callable], best_by_return: bool, *, logger=None,
            normalized_score=None, seeds_per_gpu: int = 1, sampler: str = "device", device=None, chunk: int = 2000,
-           model_file: Optional[str] = None):
+           model_file: Optional[str] = None, resume: bool = False):
     """``train()`` with the two things a flavour chooses: ``relabel(dataset)`` builds the transition dict
     (None: there is no reward model to build it with, which is reported after the other argument checks --
     unless ``model_file`` names a ``save_reward_params`` file, read once the dims and the device are known),
@@ -629,6 +659,8 @@ def _train(config, dataset, eval_env, relabel: Optional[Callable], best_by_retur
     K = int(seeds_per_gpu)
     if not 1 <= K <= _lib.MAX_GROUP:
         raise ValueError(f"seeds_per_gpu must be in 1..{_lib.MAX_GROUP}")
+    if resume:
+        _resume.check_config(config)
     if device is None:
         device = D.local_device() or "cuda:0"
     minari = None
@@ -658,7 +690,7 @@ def _train(config, dataset, eval_env, relabel: Optional[Callable], best_by_retur
     replay_buffer, eval_env = _prepare(config, relabel(dataset), eval_env, state_dim, action_dim, device)
 
     seeds = [D.rank_seed(config.train_seed, K) + k for k in range(K)]
-    ckpt_dirs = _offline_loop.checkpoint_dirs(config, seeds)
+    ckpt_dirs = _offline_loop.checkpoint_dirs(config, seeds, resume=resume)
 
     # ---- seeds and nets (cref:659-689) ----
     set_seed(seeds[0])  # np, random, torch, PYTHONHASHSEED
@@ -687,7 +719,8 @@ def _train(config, dataset, eval_env, relabel: Optional[Callable], best_by_retur
         evaluate=lambda k, trainer, step: evaluate(eval_env, trainer.actor, config.eval_episodes, config.eval_seed,
                                                    device),
         normalized=None if normalized_score is None else (lambda scores: normalized_score(dataset, scores)),
-        best_by_return=best_by_return)
+        best_by_return=best_by_return, resume=resume, sampler_state=lambda k: generator_state(gens[k]),
+        set_sampler_state=lambda k, st: set_generator_state(gens[k], st))
     if group is not None:
         group.synchronize()
         group.close()
@@ -767,7 +800,7 @@ def _model_sources(configs: Sequence[TrainConfig], reward_models) -> Dict[tuple,
 def train_runs(configs: Sequence[TrainConfig], dataset=None, reward_models=None, eval_env=None, *,
                runs_per_gpu: int = 8, logger: Optional[Callable[[Dict[str, float], int], None]] = None,
                normalized_score: Optional[Callable] = None, sampler: str = "device", chunk: int = 2000,
-               run_ids: Optional[Sequence[int]] = None) -> List[ImplicitQLearning]:
+               run_ids: Optional[Sequence[int]] = None, resume: bool = False) -> List[ImplicitQLearning]:
     """Train every config exactly as ``train(config, ...)`` would train it alone -- the same logged records
     (each with a ``run`` entry besides), evaluations (own actor, ``eval_seed``, ``eval_episodes``, the
     best-model rule of ``_offline_loop.run``), files under the run's own ``checkpoints_path``
@@ -806,11 +839,22 @@ def train_runs(configs: Sequence[TrainConfig], dataset=None, reward_models=None,
     from it (and leaves it advanced); ``train_runs`` draws the same numbers from per-run generators and
     neither seeds nor reads the global one.
 
+    ``resume`` (a ``checkpoints_path`` for every config, and the ``config.yaml`` there, if any, written for the
+    same config, paths aside; ValueError otherwise, before any device work): as in ``train()``, per launch
+    batch (``_offline_loop.run``).  At the end of every boundary at which a run of the batch evaluated or
+    ended, every run active in it, due or not, writes ``resume_{t}.pt`` at the common step (trainer
+    ``resume_state()``, the state of its own generator, best score / step, kept normalized score, whether it
+    has ended); a batch starts from its newest complete generation with the ended runs left out (their
+    trainers loaded from their final state) and the others regrouped.  Each rank resumes its own runs.
+
     Under torchrun rank r trains the configs with index = r (mod world size), with no collectives.
     Returns this rank's trainers in config order."""
     from . import sweep as SW
     configs = list(configs)
     SW.check_runs(configs, runs_per_gpu)
+    if resume:
+        for cfg in configs:
+            _resume.check_config(cfg)
     if sampler not in ("host", "device"):
         raise ValueError("sampler must be 'host' or 'device'")
     n = len(configs)
@@ -896,7 +940,7 @@ def train_runs(configs: Sequence[TrainConfig], dataset=None, reward_models=None,
     trainers: Dict[int, ImplicitQLearning] = {}
     for bi, batch in enumerate(batches):
         prepared = [buffer_for(i) for i in batch]
-        ckpt_dirs = [_offline_loop.checkpoint_dirs(configs[i], [configs[i].train_seed])[0] for i in batch]
+        ckpt_dirs = [_offline_loop.checkpoint_dirs(configs[i], [configs[i].train_seed], resume=resume)[0] for i in batch]
         for i in batch:
             cfg, e = configs[i], envs[configs[i].dataset_id]
             S, A = dims[cfg.dataset_id]
@@ -904,7 +948,8 @@ def train_runs(configs: Sequence[TrainConfig], dataset=None, reward_models=None,
         _run_batch([configs[i] for i in batch], [trainers[i] for i in batch], [p[0] for p in prepared],
                    [p[1] for p in prepared], [run_ids[i] for i in batch], ckpt_dirs, stream, logger, chunk, device,
                    [None if normalized_score is None else
-                    (lambda scores, ds=datasets[configs[i].dataset_id]: normalized_score(ds, scores)) for i in batch])
+                    (lambda scores, ds=datasets[configs[i].dataset_id]: normalized_score(ds, scores)) for i in batch],
+                   resume)
         del prepared
         for key in [k for k in relabelled if last_use_r[k] <= bi]:
             del relabelled[key]
@@ -913,7 +958,8 @@ def train_runs(configs: Sequence[TrainConfig], dataset=None, reward_models=None,
     return [trainers[i] for i in mine]
 
 
-def _run_batch(configs, trainers, bufs, envs, ids, ckpt_dirs, stream, logger, chunk, device, normalized):
+def _run_batch(configs, trainers, bufs, envs, ids, ckpt_dirs, stream, logger, chunk, device, normalized,
+               resume=False):
     """One launch batch through ``_offline_loop.run``: member k has its own buffer, bound, generator, step
     count and evaluation period; the group is rebuilt when a member leaves, and one member alone steps its
     trainer directly."""
@@ -947,7 +993,9 @@ def _run_batch(configs, trainers, bufs, envs, ids, ckpt_dirs, stream, logger, ch
             ckpt_dirs, steps,
             evaluate=lambda k, trainer, step: evaluate(envs[k], trainer.actor, configs[k].eval_episodes,
                                                        configs[k].eval_seed, device),
-            normalized=normalized, regroup=regroup, tagged=lambda rec, k: dict(rec, run=ids[k]))
+            normalized=normalized, regroup=regroup, tagged=lambda rec, k: dict(rec, run=ids[k]), resume=resume,
+            sampler_state=lambda k: generator_state(gens[k]),
+            set_sampler_state=lambda k, st: set_generator_state(gens[k], st))
     finally:
         if now["group"] is not None:
             now["group"].synchronize()

@@ -883,7 +883,8 @@ def train(config: TrainConfig, dataset=None, reward_model=None, move_stats=None,
     ``load_stats(config.move_stats_path)``).  ``logger(record, step)``: one call per ``wandb.log`` of bref
     (default: wandb when importable, else print).  ``perm``: the block permutation (None: drawn with
     ``torch.randperm`` on torch's global generator BEFORE the training seed is set, where the reference
-    builds its loader).
+    builds its loader).  There is no ``resume`` for this flavour for that reason: the permutations of a second
+    start would be others (``_offline_loop.run(resume=...)`` is not passed).
 
     The steps are queued in chunks of at most ``chunk`` that end on evaluation boundaries; the indices of
     a chunk are written on the device, and its losses come back to the host once, after the next chunk has

@@ -266,7 +266,13 @@ def train(config: TrainConfig, dataset=None, reward_model=None, eval_env=None, *
 
     ``reward_model``: a ``PosteriorRewardNet``; None reads ``config.saved_dir`` with
     ``PosteriorRewardNet.from_saved_dir``.  ``reward_type`` 3 needs its MAP weights (no ``find_map``
-    here: ``NotImplementedError`` without them)."""
+    here: ``NotImplementedError`` without them).
+
+    No ``resume``: the relabel above draws from numpy's global generator before the run is seeded, so a second
+    start would not relabel as the first did (``custom_offline.train(resume=True)`` is the flavour that resumes)."""
+    if kw.get("resume"):
+        raise NotImplementedError("custom_offline_br.train does not resume: its posterior relabel draws from numpy's "
+                                  "global generator before the run is seeded")
     if reward_model is None:
         if config.reward_type == 3:
             _map_missing()

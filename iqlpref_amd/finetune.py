@@ -509,7 +509,10 @@ def train(config: TrainConfig, env=None, eval_env=None, dataset: Optional[Dict[s
     members in one launch (``explore_actions``), steps the K environments on the host, appends in one launch
     (``add_transitions``) and takes one ``SeedGroup`` step, where one seed calls its trainer's and its ring's
     own methods.  Records carry a ``seed`` entry, checkpoints go under ``seed_<s>/``, ``exploration_noise(tick)``
-    returns [K, A], ``on_start(trainers, replay_buffers)`` gets the lists, and the list of trainers is returned."""
+    returns [K, A], ``on_start(trainers, replay_buffers)`` gets the lists, and the list of trainers is returned.
+
+    There is no ``resume`` here (``train`` / ``sweep.train_runs`` / ``custom_offline`` have one): the replay ring
+    grows on the device, and going on bit for bit would need a snapshot of it and of the index stream drawn ahead."""
     K = int(seeds_per_gpu)
     if not 1 <= K <= _lib.MAX_GROUP:
         raise ValueError(f"seeds_per_gpu must be in 1..{_lib.MAX_GROUP}")

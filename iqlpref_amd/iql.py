@@ -321,8 +321,8 @@ class MLP(nn.Module):
         self._dropout = dropout
         # key of this module's stand-alone dropout masks: the torch seed in force when the module was
         # BUILT (train(seeds_per_gpu=K) builds the K actors after K successive set_seed calls: each
-        # keeps its own run's seed, as it would running alone).  The per-module call counter is
-        # neither checkpointed nor reset: a resumed run draws its masks from call 0 again.
+        # keeps its own run's seed, as it would running alone).  The per-module call counter is no part of
+        # state_dict() (the reference's keys); ImplicitQLearning.resume_state() carries both.
         self._drop_seed = torch.initial_seed() & 0xFFFFFFFFFFFFFFFF
 
     def linears(self) -> List[nn.Linear]:
@@ -860,6 +860,63 @@ class ImplicitQLearning:
             with torch.cuda.device(self._dev):
                 check(self._lib.iqlhip_trainer_set_step(self._handle, self.total_it))
         self.sync_weights()
+
+    # -- exact resumption ---------------------------------------------------- #
+    def _dropout_modules(self) -> Dict[str, MLP]:
+        """Every MLP of this trainer that has dropout, by name (their stand-alone forwards count calls)."""
+        out = {}
+        for name, net in (("qf", self.qf), ("vf", self.vf), ("actor", self.actor)):
+            for sub, m in net.named_modules():
+                if isinstance(m, MLP) and m._dropout is not None:
+                    out[f"{name}.{sub}" if sub else name] = m
+        return out
+
+    def resume_state(self) -> Dict[str, Any]:
+        """Everything the next ``train_steps`` call and the next stand-alone forward depend on: with it a
+        freshly built trainer of the same config goes on as this one would, bit for bit.
+
+        ``state_dict``  ``state_dict()`` as it is (the reference's keys; parameters, Adam moments, schedule);
+        ``q_target``    the target critics -- ``state_dict()`` leaves them out and ``load_state_dict`` starts
+                        them as a copy of ``qf`` (ref:679), which is right only at step 0;
+        ``total_it``    the step count (``state_dict()`` of the custom flavour has none): Adam's bias
+                        correction, the cosine schedule and the Philox index / mask streams are keyed by it;
+        ``seed``        the Philox key of those streams;
+        ``dropout``     ``[_drop_seed, _drop_calls]`` of every module with dropout: the key and the call
+                        counter of its stand-alone train-mode masks.
+        The batch the library stages ahead and its cached graphs are rebuilt from these.  The tensors are
+        copies: later steps do not change them."""
+        sd = self.state_dict()  # (synchronizes the device)
+        own = lambda v: v.detach().clone() if isinstance(v, torch.Tensor) else v
+        deep = lambda v: {k: deep(x) for k, x in v.items()} if isinstance(v, dict) else \
+            [deep(x) for x in v] if isinstance(v, (list, tuple)) else own(v)
+        return {"state_dict": deep(sd),
+                "q_target": {k: own(v) for k, v in self.q_target.state_dict().items()},
+                "total_it": int(self.total_it), "seed": int(self._seed),
+                "dropout": {name: [int(m._drop_seed), int(getattr(m, "_drop_calls", 0))]
+                            for name, m in self._dropout_modules().items()}}
+
+    def load_resume_state(self, state: Dict[str, Any]):
+        """Take over a ``resume_state()``: ``load_state_dict``, then the target critics, the step count (in
+        the library through ``iqlhip_trainer_set_step``), the Philox key and the dropout counters.  Works on
+        a freshly built trainer before it joins a ``SeedGroup`` as well as on one that has stepped."""
+        self.load_state_dict(state["state_dict"])
+        if int(state["seed"]) != self._seed:  # the descriptor holds the key: the handle is built anew
+            self._destroy_handle()
+            self._seed = int(state["seed"])
+        self.q_target.load_state_dict(state["q_target"])  # copies into the views of the target arena
+        if int(state["total_it"]) != self.total_it:
+            self.total_it = int(state["total_it"])
+            self._after_steps(0)  # schedule, learning rate and Adam step counters at this step
+            if self._handle is not None:
+                with torch.cuda.device(self._dev):
+                    check(self._lib.iqlhip_trainer_set_step(self._handle, self.total_it))
+        mods = self._dropout_modules()
+        if set(mods) != set(state["dropout"]):
+            raise ValueError(f"resume state has dropout modules {sorted(state['dropout'])}, the trainer "
+                             f"{sorted(mods)}")
+        for name, m in mods.items():
+            m._drop_seed, m._drop_calls = int(state["dropout"][name][0]), int(state["dropout"][name][1])
+        self.sync_weights()  # the compute-precision copies of the target
 
     # -- forward passes at the trainer's precision (tests, diagnostics) ------ #
     def forward(self, which: str, states: torch.Tensor, actions: Optional[torch.Tensor] = None):

@@ -13,8 +13,9 @@ run each.  Here one process takes the whole grid:
     (discount, tau, beta, iql_tau, dropout rate, learning rates, schedule length) from each member's
     own descriptor, so runs that differ in any of them -- not only in the seed -- share one launch
     sequence.
-``python -m iqlpref_amd.sweep SWEEP.yaml [--list] [--only i,j] [--runs_per_gpu K] [--field value]``
-    the command line over both.
+``python -m iqlpref_amd.sweep SWEEP.yaml [--list] [--only i,j] [--runs_per_gpu K] [--resume] [--field value]``
+    the command line over both.  ``--resume``: every run goes on from its last evaluation boundary, bit for
+    bit (``train_runs(resume=True)``); with ``--list`` it prints ``done`` / ``at step t`` / ``new`` per run.
 
 Two flavours of sweep file.  A file whose ``program`` ends in ``custom_offline/iql.py`` (the six pen sweeps,
 ``mr_sweeps/sweep_pen_*_pref.yaml`` and ``pt_sweeps/sweep_pen_*_pt.yaml``) is a custom-flavour sweep: its
@@ -36,7 +37,7 @@ from typing import Any, Callable, Dict, List, Mapping, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _lib, custom_offline
+from . import _lib, _resume, custom_offline
 from . import distributed as D
 from ._offline_loop import checkpoint_dirs
 from .iql import ImplicitQLearning, TrainConfig, load_config
@@ -278,7 +279,7 @@ def train_runs(configs: Sequence[TrainConfig], env=None, dataset=None, *, runs_p
                evaluate: Union[None, Callable, Sequence[Callable]] = None, precision: str = "bf16",
                raw_dataset=None, host_prep: bool = False, vector_env: Optional[Callable] = None,
                group_mode: Optional[str] = None,
-               run_ids: Optional[Sequence[int]] = None) -> List[ImplicitQLearning]:
+               run_ids: Optional[Sequence[int]] = None, resume: bool = False) -> List[ImplicitQLearning]:
     """Train every config exactly as ``train(config)`` would -- the same logged records (plus ``run``
     / ``seed`` entries), evaluation calls (own actor, own seed), checkpoint files (``config.yaml`` and
     ``checkpoint_{t}.pt`` under the run's own ``checkpoints_path``) and final parameters, target,
@@ -303,8 +304,20 @@ def train_runs(configs: Sequence[TrainConfig], env=None, dataset=None, *, runs_p
     per process with keys ``run<i>/``, or print.  ``run_ids``: the names of the runs in the records
     (default 0 .. n-1).
 
+    ``resume`` (every config needs a ``checkpoints_path``, and the ``config.yaml`` there, if any, must have
+    been written for the same config, paths aside; ValueError otherwise, before any device work): as in
+    ``train()``, per launch batch.  At the end of every boundary at which a run of the batch evaluated or
+    ended, every run active in it -- due or not -- writes ``resume_{t}.pt`` (trainer ``resume_state()``, its
+    partly filled loss window, whether it has ended) at the batch's common step t under its own
+    ``checkpoints_path``; the files of the generation before go once all are written, the file of an ended
+    run stays.  A batch starts from its newest complete generation: ended runs are neither trained nor
+    evaluated again (their trainers are loaded from their final state), the others go on as one regrouped
+    batch, bit for bit the uninterrupted run.  A batch without a generation starts at step 0.  The step is
+    one that all unfinished runs of the batch have: resume with the configs and ``runs_per_gpu`` of the first
+    start -- runs that hold generations with no step in common are refused (ValueError) and keep their files.
+
     Under torchrun rank r trains the configs with index = r (mod world size), each at its own seed,
-    with no collectives.  Returns this rank's trainers in config order."""
+    with no collectives (each rank resumes its own runs).  Returns this rank's trainers in config order."""
     # the module, not the function the package exports under the same name (build_dataset is looked
     # up on it at call time: tests count its calls)
     T = importlib.import_module(".train", __package__)
@@ -312,6 +325,9 @@ def train_runs(configs: Sequence[TrainConfig], env=None, dataset=None, *, runs_p
 
     configs = list(configs)
     check_runs(configs, runs_per_gpu)
+    if resume:
+        for cfg in configs:
+            _resume.check_config(cfg)
     n = len(configs)
     run_ids = list(range(n)) if run_ids is None else [int(r) for r in run_ids]
     if len(run_ids) != n:
@@ -371,10 +387,11 @@ def train_runs(configs: Sequence[TrainConfig], env=None, dataset=None, *, runs_p
             buf, mean, std = buffer_for(i)
             e = envs[cfg.env]
             max_action = float(e.action_space.high[0])
-            checkpoint_dirs(cfg, [cfg.seed])  # (one seed: the path itself, with its config.yaml)
+            checkpoint_dirs(cfg, [cfg.seed], resume=resume)  # (one seed: the path itself, with its config.yaml)
             trainers[i] = T._build_trainer(cfg, cfg.seed, dims[cfg.env][0], dims[cfg.env][1], max_action, precision)
             state[i] = (buf, mean, std, max_action, e)
-        _run_batch(configs, batch, trainers, state, SeedGroup, group_mode, logger, evaluate, vector_env, run_ids)
+        _run_batch(configs, batch, trainers, state, SeedGroup, group_mode, logger, evaluate, vector_env, run_ids,
+                   resume)
         for key in [k for k in datasets if last_use_r[k] <= bi]:
             del datasets[key]
         for key in [k for k in buffers if last_use_b[k] <= bi]:
@@ -382,9 +399,11 @@ def train_runs(configs: Sequence[TrainConfig], env=None, dataset=None, *, runs_p
     return [trainers[i] for i in mine]
 
 
-def _run_batch(configs, batch, trainers, state, SeedGroup, group_mode, logger, evaluate, vector_env, run_ids):
-    """One launch batch: all runs start at step 0 and run in lock step to the next boundary of any
-    of them; a run at its end leaves and the group is rebuilt over the rest."""
+def _run_batch(configs, batch, trainers, state, SeedGroup, group_mode, logger, evaluate, vector_env, run_ids,
+               resume=False):
+    """One launch batch: all runs start at step 0 (``resume``: at the batch's newest complete resume
+    generation) and run in lock step to the next boundary of any of them; a run at its end leaves and the
+    group is rebuilt over the rest."""
     from .train import eval_actor
 
     def make_group(members):
@@ -393,11 +412,31 @@ def _run_batch(configs, batch, trainers, state, SeedGroup, group_mode, logger, e
         mode = resolve_group_mode(group_mode, trs, configs[members[0]].batch_size)
         return SeedGroup(trs) if mode is None else SeedGroup(trs, mode=mode)
 
-    active = [i for i in batch if int(configs[i].max_timesteps) > 0]
-    group = make_group(active) if active else None
     windows: Dict[int, torch.Tensor] = {}
-    tag = lambda rec, i: dict(rec, run=run_ids[i], seed=configs[i].seed)
     t = 0
+    ended = set()
+    members = [i for i in batch if int(configs[i].max_timesteps) > 0]
+    dirs = [configs[i].checkpoints_path for i in members]
+    kept: Dict[int, int] = {}  # position in members -> step of the generation file the run holds
+    if resume:  # (before the trainers join a group)
+        t, payloads = _resume.restore(dirs, kept)
+        for j, p in payloads.items():
+            i = members[j]
+            trainers[i].load_resume_state(p["trainer"])
+            if p["loop"]["window"] is not None:
+                windows[i] = p["loop"]["window"].to(configs[i].device)
+            if p["finished"]:
+                ended.add(i)
+
+    def commit(runs):
+        payloads = {members.index(i): {
+            "finished": t >= int(configs[i].max_timesteps), "trainer": trainers[i].resume_state(), "sampler": None,
+            "loop": {"window": None if t % configs[i].log_freq == 0 else windows[i].cpu()}} for i in runs}
+        _resume.commit(dirs, t, payloads, kept)
+
+    active = [i for i in members if i not in ended and t < int(configs[i].max_timesteps)]
+    group = make_group(active) if active else None
+    tag = lambda rec, i: dict(rec, run=run_ids[i], seed=configs[i].seed)
     while active:
         nxt = min(_next_boundary(configs[i], t) for i in active)
         B = configs[active[0]].batch_size
@@ -433,6 +472,10 @@ def _run_batch(configs, batch, trainers, state, SeedGroup, group_mode, logger, e
             if cfg.checkpoints_path is not None:
                 torch.save(trainer.state_dict(), os.path.join(cfg.checkpoints_path, f"checkpoint_{t - 1}.pt"))
         left = [i for i in active if t < int(configs[i].max_timesteps)]
+        if resume and (evals or len(left) != len(active)):
+            if not evals:
+                group.synchronize()
+            commit(active)
         if len(left) != len(active):
             group.synchronize()
             group.close()
@@ -472,7 +515,7 @@ def _list_dims_custom(dataset_id: str):
 
 def main(argv=None):
     """python -m iqlpref_amd.sweep SWEEP.yaml [--config_root DIR] [--runs_per_gpu K] [--only 0,3,5]
-    [--list] [--field value ...]"""
+    [--list] [--resume] [--field value ...]"""
     from .train import parse_overrides
     ap = argparse.ArgumentParser(prog="python -m iqlpref_amd.sweep", allow_abbrev=False,
                                  description="train the runs of a W&B grid sweep file, packed into seed groups")
@@ -482,6 +525,10 @@ def main(argv=None):
                     help="runs stepped together as one seed group (default: $AGENTS_PER_GPU, else 8)")
     ap.add_argument("--only", default=None, help="comma-separated run indices to train")
     ap.add_argument("--list", action="store_true", help="print every run's index, label and launch batch; no GPU")
+    ap.add_argument("--resume", action="store_true",
+                    help="go on from the last evaluation boundary of an earlier start of each run under its "
+                         "checkpoints_path (found by its config.yaml), bit for bit, and write resume generations; "
+                         "with --list: print done / at step t / new per run")
     ap.add_argument("--group_mode", default=None, choices=list(GROUP_MODES),
                     help="SeedGroup mode of every launch batch (default: the SeedGroup default; 'general': one launch "
                          "sequence for batches on the general layer-wise step)")
@@ -499,24 +546,29 @@ def main(argv=None):
         if bad:
             raise SystemExit(f"--only: no run {bad} (the sweep has {len(configs)})")
     chosen = [configs[i] for i in ids]
+    if args.resume:  # (expanding the file gave every run a fresh random name and directory)
+        taken = set()
+        for cfg in chosen:
+            _resume.adopt_run_dir(cfg, taken=taken)
+    progress = (lambda i: "\t" + _resume.run_status(configs[i])) if args.resume else (lambda i: "")
     if custom:
         if args.list:
             batches = custom_offline.plan_batches(chosen, [_list_dims_custom(c.dataset_id) for c in chosen],
                                                   args.runs_per_gpu)
             where = {j: b for b, members in enumerate(batches) for j in members}
             for j, i in enumerate(ids):
-                print(f"{i}\t{configs[i].sweep_label or '-'}\tbatch {where[j]}")
+                print(f"{i}\t{configs[i].sweep_label or '-'}\tbatch {where[j]}{progress(i)}")
             return
-        custom_offline.train_runs(chosen, runs_per_gpu=args.runs_per_gpu, run_ids=ids)
+        custom_offline.train_runs(chosen, runs_per_gpu=args.runs_per_gpu, run_ids=ids, resume=args.resume)
         return
     if args.list:
         batches = plan_batches(chosen, [_list_dims(c.env) for c in chosen], args.runs_per_gpu)
         where = {j: b for b, members in enumerate(batches) for j in members}
         for j, i in enumerate(ids):
             mode = "" if args.group_mode is None else f"\tmode {planned_mode(configs[i], args.group_mode)}"
-            print(f"{i}\t{configs[i].sweep_label or '-'}\tbatch {where[j]}{mode}")
+            print(f"{i}\t{configs[i].sweep_label or '-'}\tbatch {where[j]}{mode}{progress(i)}")
         return
-    train_runs(chosen, runs_per_gpu=args.runs_per_gpu, run_ids=ids, group_mode=args.group_mode)
+    train_runs(chosen, runs_per_gpu=args.runs_per_gpu, run_ids=ids, group_mode=args.group_mode, resume=args.resume)
 
 
 if __name__ == "__main__":

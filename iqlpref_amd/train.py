@@ -16,6 +16,7 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from . import _resume
 from . import distributed as D
 from . import prep
 from ._offline_loop import checkpoint_dirs
@@ -229,7 +230,7 @@ def train(config: TrainConfig, env=None, dataset=None, *, state_dim: Optional[in
           raw_dataset=None, host_prep: bool = False, seeds_per_gpu: int = 1,
           vector_env: Optional[Callable] = None,
           index_stream: Optional[Callable[[int, int, int], torch.Tensor]] = None,
-          group_mode: Optional[str] = None):
+          group_mode: Optional[str] = None, resume: bool = False):
     """ref:1393-1570.  ``dataset``: an already-built qlearning dataset (skips d4rl);
     ``raw_dataset``: an env.get_dataset()-style dict handed to the relabel functions;
     ``evaluate(actor, step) -> (scores, steps_to_goal)`` replaces eval_actor when gym is
@@ -258,7 +259,21 @@ def train(config: TrainConfig, env=None, dataset=None, *, state_dim: Optional[in
     CPU generator, ref:212-214) is replayed step for step.
     ``group_mode``: the ``SeedGroup`` mode of the K seeds (None: its default).  "general" -- one launch
     sequence for seeds on the general layer-wise step -- falls back to the default for a config of the
-    tuned step (``multi.resolve_group_mode``)."""
+    tuned step (``multi.resolve_group_mode``).
+
+    ``resume`` (needs ``checkpoints_path``, else ValueError; ValueError too when the ``config.yaml`` there was
+    written for a config that differs in anything but paths): at the end of every evaluation boundary -- after
+    the evaluations, records, ``checkpoint_{t}.pt`` files and the metric exchange -- every seed writes one file
+    ``resume_{t}.pt`` of a resume generation into its checkpoint directory (``_resume``): its trainer's
+    ``resume_state()`` (parameters, Adam moments, schedule, TARGET critics, step count, dropout counters), its
+    partly filled loss window and its last window record; the generation before is removed once all K files
+    exist.  The index and mask streams need nothing: they are Philox streams keyed by seed and step.  And the
+    run starts from the newest complete generation instead of step 0 (from step 0 when there is none, whatever
+    ``load_model`` says otherwise): a run killed at any moment and started again with the same config logs
+    the records and writes the files the uninterrupted run would from there on, and returns the same trainers,
+    bit for bit (``steps_per_sec`` aside).  A finished run is neither trained nor evaluated again.  Under
+    torchrun every rank resumes its own seeds, all from the newest generation that every rank has.
+    ``index_stream`` must be a function of its arguments alone."""
     from .multi import check_group_mode, resolve_group_mode
     check_group_mode(group_mode)
     # one process per GPU: under torchrun this rank owns cuda:<LOCAL_RANK>, and everything
@@ -298,17 +313,44 @@ def train(config: TrainConfig, env=None, dataset=None, *, state_dim: Optional[in
     if max_action is None:
         max_action = float(env.action_space.high[0])
 
-    ckpt_dirs = checkpoint_dirs(config, seeds)
+    ckpt_dirs = checkpoint_dirs(config, seeds, resume=resume)
 
     if K > 1 and config.load_model != "":
         import warnings
         warnings.warn(f"seeds_per_gpu={K} with load_model set: all {K} seeds start from the SAME checkpoint "
                       f"({config.load_model}) and differ only in their sample streams", stacklevel=2)
     trainers = [_build_trainer(config, seeds[k], state_dim, action_dim, max_action, precision) for k in range(K)]
+    total = int(config.max_timesteps)
+    t = 0
+    windows: List[Optional[torch.Tensor]] = [None] * K
+    last: List[Dict[str, float]] = [{} for _ in range(K)]
+    kept: Dict[int, int] = {}  # seed slot -> step of the generation file it holds
+    many_ranks = D.dist.is_initialized() and D.dist.get_world_size() > 1
+    if resume:  # (before the trainers join a group)
+        common = None
+        if many_ranks:  # the newest generation that every rank has (-1: some rank has none)
+            found = _resume.latest(ckpt_dirs)
+            mine = -1 if found is None else found[0]
+            common = int(min(r["total_it"] for r in D.gather_metrics({"total_it": mine}, device=config.device)))
+        t, payloads = _resume.restore(ckpt_dirs, kept, at_most=common)
+        if many_ranks and any(int(r["total_it"]) != t for r in D.gather_metrics({"total_it": t}, device=config.device)):
+            raise ValueError("resume=True: the ranks have no resume generation in common")
+        for k, p in payloads.items():
+            trainers[k].load_resume_state(p["trainer"])
+            w = p["loop"]["window"]
+            windows[k] = None if w is None else w.to(config.device)
+            last[k] = dict(p["loop"]["last"])
     group = None
     if K > 1:
         from .multi import SeedGroup
         group = SeedGroup(trainers, mode=resolve_group_mode(group_mode, trainers, config.batch_size))
+
+    def commit():
+        """One resume generation at step t: every seed's file, then the generation before goes."""
+        payloads = {k: {"finished": t >= total, "trainer": trainers[k].resume_state(), "sampler": None,
+                        "loop": {"window": None if t % config.log_freq == 0 or windows[k] is None
+                                 else windows[k].cpu(), "last": dict(last[k])}} for k in range(K)}
+        _resume.commit(ckpt_dirs, t, payloads, kept, keep_previous=many_ranks)
 
     if logger is None:
         try:
@@ -323,11 +365,7 @@ def train(config: TrainConfig, env=None, dataset=None, *, state_dim: Optional[in
             logger = lambda d, step: print(f"[{step}] " + " ".join(f"{n}={v:.5g}" for n, v in d.items()))
     tag = (lambda rec, k: rec) if K == 1 else (lambda rec, k: dict(rec, seed=seeds[k]))
 
-    total = int(config.max_timesteps)
-    t = 0
     t_window = time.perf_counter()
-    windows: List[Optional[torch.Tensor]] = [None] * K
-    last: List[Dict[str, float]] = [{} for _ in range(K)]
     while t < total:
         # run to the next logging / evaluation boundary in one library call (ref:1533-1544)
         nxt = min(total, (t // config.log_freq + 1) * config.log_freq,
@@ -380,6 +418,12 @@ def train(config: TrainConfig, env=None, dataset=None, *, state_dim: Optional[in
             recs = D.gather_metric_records(records, device=config.device)
             if rank == 0 and len(recs) > 1:
                 logger(D.summarize(recs), trainers[0].total_it)
+            if resume:
+                commit()
+    if resume and kept.get(0) != t:  # (max_timesteps is no multiple of eval_freq: the final state, finished)
+        if group is not None:
+            group.synchronize()
+        commit()
     if group is not None:
         group.synchronize()
         group.close()
@@ -399,9 +443,15 @@ def main(argv=None):
     from .multi import GROUP_MODES
     ap.add_argument("--group_mode", default=None, choices=list(GROUP_MODES),
                     help="SeedGroup mode of the --seeds_per_gpu seeds (default: the SeedGroup default)")
+    ap.add_argument("--resume", action="store_true",
+                    help="go on from the last evaluation boundary of an earlier start of this config under "
+                         "--checkpoints_path (found by its config.yaml), bit for bit; write resume generations")
     args, rest = ap.parse_known_args(argv)
-    train(load_config(args.config_path, **parse_overrides(rest)), seeds_per_gpu=args.seeds_per_gpu,
-          group_mode=args.group_mode)
+    config = load_config(args.config_path, **parse_overrides(rest))
+    if args.resume:  # (a fresh start gave the config a fresh random name and directory; this rank's seeds only)
+        first = config.seed + int(os.environ.get("RANK", "0")) * args.seeds_per_gpu
+        _resume.adopt_run_dir(config, seeds=range(first, first + args.seeds_per_gpu))
+    train(config, seeds_per_gpu=args.seeds_per_gpu, group_mode=args.group_mode, resume=args.resume)
 
 
 def parse_overrides(tokens: Sequence[str]) -> Dict[str, str]:
