@@ -404,7 +404,7 @@ typedef struct {
   int32_t state_dim, action_dim;
   int32_t embd_dim;   /* must be 64                                             */
   int32_t num_heads;  /* power of two <= 16                                     */
-  int32_t inter_dim;  /* GPT2MLP width, multiple of 64, <= 1024                 */
+  int32_t inter_dim;  /* GPT2MLP width, multiple of 256, <= 1024                */
   int32_t num_layers; /* must be 1                                              */
   int32_t n_temb;     /* rows of timestep_embed (max_episode_steps + 1)         */
   float eps;          /* LayerNorm epsilon                                      */

@@ -227,29 +227,46 @@ def pt_windows(obs_all, act_all, ep_steps, query_length, correct_window_offsets=
 #   gpt.layers.{l}.mlp.in_linear.{weight,bias}  gpt.layers.{l}.mlp.out_linear.{weight,bias}
 #   gpt.layer_norm.{weight,bias}  pref_linear.{weight,bias}
 # --------------------------------------------------------------------------- #
-def _ln(x, w, b, eps):
-    mu = x.mean(-1, keepdims=True, dtype=F32)
-    var = ((x - mu) ** 2).mean(-1, keepdims=True, dtype=F32)
-    return ((x - mu) / np.sqrt(var + F32(eps)) * w + b).astype(F32)
+def _ln(x, w, b, eps, dtype=F32):
+    mu = x.mean(-1, keepdims=True, dtype=dtype)
+    var = ((x - mu) ** 2).mean(-1, keepdims=True, dtype=dtype)
+    return ((x - mu) / np.sqrt(var + dtype(eps)) * w + b).astype(dtype)
 
 
-def _lin(x, p, name):
-    return (x @ p[name + ".weight"].T + p[name + ".bias"]).astype(F32)
+def _lin(x, p, name, dtype=F32):
+    return (x @ p[name + ".weight"].T + p[name + ".bias"]).astype(dtype)
 
 
-def pt_value_last(p, states, actions, timesteps, attn_mask, num_heads=4, eps=1e-5, all_positions=False):
+def _bf16_as(x, dtype):
+    """x rounded to bfloat16 (nearest-even), returned in ``dtype``.  float32: iql_oracle.bf16.  float64:
+    ONE rounding from the float64 value (through float32 it would be two); normal numbers only."""
+    if dtype == F32:
+        return bf16(x)
+    m, e = np.frexp(np.asarray(x, dtype=np.float64))
+    return np.ldexp(np.rint(m * 256.0) / 256.0, e)
+
+
+def pt_value_last(p, states, actions, timesteps, attn_mask, num_heads=4, eps=1e-5, all_positions=False,
+                  dtype=np.float32):
     """value[:, 0, -1, 0] of PT.__call__ (pref_transformer.py:210-277), eval mode.
 
-    states [B,QL,S], actions [B,QL,A], timesteps [B,QL] int, attn_mask [B,QL]."""
+    states [B,QL,S], actions [B,QL,A], timesteps [B,QL] int, attn_mask [B,QL].
+    ``dtype``: np.float32 is the restatement as the reference computes it.  np.float64 is the
+    high-precision yardstick of the GPU envelope tests: every linear, LayerNorm, softmax and sum in
+    float64, the three bf16 rounding points of ops.py:74-79 (q and k, the q.k sum, the scaled logit)
+    where they are."""
+    dtype = np.dtype(dtype).type
+    if dtype is not F32:
+        p = {k: np.asarray(v, dtype=dtype) for k, v in p.items()}
     B, QL = states.shape[:2]
     E = p["state_linear.weight"].shape[0]
     temb = p["timestep_embed.weight"][timesteps]  # [B,QL,E]
-    es = _lin(states.astype(F32), p, "state_linear") + temb
-    ea = _lin(actions.astype(F32), p, "action_linear") + temb
+    es = _lin(states.astype(dtype), p, "state_linear", dtype) + temb
+    ea = _lin(actions.astype(dtype), p, "action_linear", dtype) + temb
     x = np.stack([es, ea], axis=2).reshape(B, 2 * QL, E)  # s0,a0,s1,a1,... (:221-225)
-    x = _ln(x, p["stacked_layer_norm.weight"], p["stacked_layer_norm.bias"], eps)
-    m2 = np.stack([attn_mask, attn_mask], axis=2).reshape(B, 2 * QL).astype(F32)
-    add_mask = ((F32(1.0) - m2) * F32(-10000.0))[:, None, None, :]  # ops.py:6-11
+    x = _ln(x, p["stacked_layer_norm.weight"], p["stacked_layer_norm.bias"], eps, dtype)
+    m2 = np.stack([attn_mask, attn_mask], axis=2).reshape(B, 2 * QL).astype(dtype)
+    add_mask = ((dtype(1.0) - m2) * dtype(-10000.0))[:, None, None, :]  # ops.py:6-11
     T = 2 * QL
     causal = np.tril(np.ones((T, T), dtype=bool))[None, None]
     hd = E // num_heads
@@ -259,28 +276,28 @@ def pt_value_last(p, states, actions, timesteps, attn_mask, num_heads=4, eps=1e-
     for l in range(n_layers):
         pre = f"gpt.layers.{l}."
         res = x
-        h = _ln(x, p[pre + "layer_norm_0.weight"], p[pre + "layer_norm_0.bias"], eps)
-        qkv = _lin(h, p, pre + "attention.in_linear")
+        h = _ln(x, p[pre + "layer_norm_0.weight"], p[pre + "layer_norm_0.bias"], eps, dtype)
+        qkv = _lin(h, p, pre + "attention.in_linear", dtype)
         q, k, v = np.split(qkv, 3, axis=2)
         sh = lambda t: t.reshape(B, T, num_heads, hd).transpose(0, 2, 1, 3)
         q, k, v = sh(q), sh(k), sh(v)
         # ops.py:74-76: query/key cast to bf16; the product is a bf16 tensor
-        w = bf16((bf16(q) @ bf16(k).transpose(0, 1, 3, 2)).astype(F32))
-        w = bf16(w / F32(float(hd) ** 0.5))
-        w = np.where(causal, w, bf16(np.asarray(-1e4, dtype=F32)))
-        w = w.astype(F32) + add_mask
+        w = _bf16_as((_bf16_as(q, dtype) @ _bf16_as(k, dtype).transpose(0, 1, 3, 2)).astype(dtype), dtype)
+        w = _bf16_as(w / dtype(float(hd) ** 0.5), dtype)
+        w = np.where(causal, w, _bf16_as(np.asarray(-1e4, dtype=dtype), dtype))
+        w = w.astype(dtype) + add_mask
         w = w - w.max(-1, keepdims=True)
-        pw = np.exp(w).astype(F32)
-        pw = (pw / pw.sum(-1, keepdims=True, dtype=F32)).astype(F32)
-        o = (pw @ v).astype(F32).transpose(0, 2, 1, 3).reshape(B, T, E)
-        x = _lin(o, p, pre + "attention.out_linear") + res
+        pw = np.exp(w).astype(dtype)
+        pw = (pw / pw.sum(-1, keepdims=True, dtype=dtype)).astype(dtype)
+        o = (pw @ v).astype(dtype).transpose(0, 2, 1, 3).reshape(B, T, E)
+        x = _lin(o, p, pre + "attention.out_linear", dtype) + res
         res = x
-        h = _ln(x, p[pre + "layer_norm_1.weight"], p[pre + "layer_norm_1.bias"], eps)
-        h = np.maximum(_lin(h, p, pre + "mlp.in_linear"), 0).astype(F32)
-        x = _lin(h, p, pre + "mlp.out_linear") + res
-    x = _ln(x, p["gpt.layer_norm.weight"], p["gpt.layer_norm.bias"], eps)
+        h = _ln(x, p[pre + "layer_norm_1.weight"], p[pre + "layer_norm_1.bias"], eps, dtype)
+        h = np.maximum(_lin(h, p, pre + "mlp.in_linear", dtype), 0).astype(dtype)
+        x = _lin(h, p, pre + "mlp.out_linear", dtype) + res
+    x = _ln(x, p["gpt.layer_norm.weight"], p["gpt.layer_norm.bias"], eps, dtype)
     hidden = x.reshape(B, QL, 2, E)[:, :, 1]  # action tokens (:241-242)
-    out = _lin(hidden, p, "pref_linear")
+    out = _lin(hidden, p, "pref_linear", dtype)
     if all_positions:
         return out[:, :, -1]  # value at every timestep of the window (custom_offline/iql.py:176-192)
     return out[:, -1, -1]  # value = last output column, last timestep

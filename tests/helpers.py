@@ -336,3 +336,179 @@ def bf16_ulp(x):
     """Spacing of bfloat16 at |x|: 2^-7 of its binade."""
     _, e = np.frexp(np.abs(np.asarray(x, dtype=np.float64)))
     return np.ldexp(1.0, e - 1 - 7)
+
+
+# ---------------------------------------------------------------------------------------------
+# Preference-transformer relabel (tests/test_gpu_relabel.py, test_gpu_pt_general.py,
+# test_gpu_pt_envelope.py): windows, their oracle values, the two bounds, and the cases of the
+# envelope tests with their inputs -- numpy only, so that tests/test_relabel_oracle.py can show on
+# the host that the reference alone stays inside the bounds.
+# ---------------------------------------------------------------------------------------------
+PT_TOL = 5e-3            # absorbs bf16 rounding flips of a q.k logit
+PT_TIGHT_MEDIAN = 1e-5   # on short windows: a wrong tile or head split errs by the size of the values
+
+
+def oracle_windows(p, obs, act, starts, lens, t0, QL, heads, dtype=np.float32, trim=False):
+    """pt_value_last of right-aligned windows (start, len, t0), batched.  dtype=np.float64: the
+    high-precision mode of the oracle, returned as float64.  trim=True (the long cases: the cost of a
+    forward grows with the square of its padded length): the windows go in order of length and a
+    batch is padded to ITS longest window instead of to QL -- a pad key weighs exp(-1e4 - max) = 0
+    exactly, so the number of pads moves a value by the order of a float sum of zeros at most
+    (tests/test_relabel_oracle.py holds the float64 mode to 1e-12 on this)."""
+    from oracle import relabel_oracle as ro
+    n, S, A = len(lens), obs.shape[1], act.shape[1]
+    order = np.argsort(lens, kind="stable") if trim else np.arange(n)
+    out = np.empty(n, dtype)
+    for b in range(0, n, 32 if trim else 64):
+        idx = order[b:b + (32 if trim else 64)]
+        pad = int(max(lens[i] for i in idx)) if trim else QL
+        sts = np.zeros((len(idx), pad, S), np.float32); acs = np.zeros((len(idx), pad, A), np.float32)
+        ts = np.zeros((len(idx), pad), np.int64); am = np.zeros((len(idx), pad), np.float32)
+        for r, i in enumerate(idx):
+            s0, l0 = int(starts[i]), int(lens[i])
+            sts[r, pad - l0:] = obs[s0:s0 + l0]; acs[r, pad - l0:] = act[s0:s0 + l0]
+            ts[r, pad - l0:] = (0 if t0 is None else int(t0[i])) + np.arange(l0); am[r, pad - l0:] = 1
+        out[idx] = ro.pt_value_last(p, sts, acs, ts, am, num_heads=heads, dtype=dtype)
+    return out
+
+
+def oracle_prefixes(p, obs, act, start, n, t0, heads, dtype=np.float32):
+    """ONE forward over the n transitions from row ``start`` (timesteps t0 ..), values at every
+    position: because attention is causal, entry l - 1 is the value of the window (start, l, t0)
+    (include/iqlhip.h; the pads of the shorter window weigh exactly 0)."""
+    from oracle import relabel_oracle as ro
+    ts = (t0 + np.arange(n))[None]
+    return ro.pt_value_last(p, obs[None, start:start + n], act[None, start:start + n], ts,
+                            np.ones((1, n), np.float32), num_heads=heads, all_positions=True, dtype=dtype)[0]
+
+
+def random_windows(rng, n_rows, max_ep, QL, n_extra, lengths=None):
+    """Every length 1..QL once (or each of ``lengths``), then random ones, then windows sharing rows
+    with earlier ones."""
+    first = np.arange(1, QL + 1) if lengths is None else np.asarray(lengths)
+    lens = np.concatenate([first, rng.integers(1, QL + 1, n_extra)]).astype(np.int32)
+    starts = np.array([rng.integers(0, n_rows - l + 1) for l in lens], np.int64)
+    t0 = np.array([rng.integers(0, max_ep + 2 - l) for l in lens], np.int32)
+    # the same rows again under other lengths / timesteps
+    k = min(16, len(lens))
+    lens2 = rng.integers(1, QL + 1, k).astype(np.int32)
+    starts2 = np.minimum(starts[:k], n_rows - lens2)
+    t02 = np.array([rng.integers(0, max_ep + 2 - l) for l in lens2], np.int32)
+    return (np.concatenate([lens, lens2]), np.concatenate([starts, starts2]), np.concatenate([t0, t02]))
+
+
+def check_close(got, want, short=None):
+    """Loose bound everywhere; the tight median bound on all windows, or on `short` (a mask)."""
+    d = np.abs(got.astype(np.float64) - want)
+    assert np.isfinite(got).all()
+    np.testing.assert_allclose(got, want, rtol=PT_TOL, atol=PT_TOL)
+    sel = d if short is None else d[short]
+    assert np.median(sel) <= PT_TIGHT_MEDIAN, (float(d.max()), float(np.median(sel)))
+    return float(d.max()), float(np.median(d))
+
+
+# The envelope cases, every one as (L, E, heads, I, S, A, QL).  Tuned kernel (k_pt_relabel: one block,
+# embd 64): nks = 16-deep k-steps of the embedding GEMM, walked in chunks of KCH = 3; nmt = 16-token
+# tiles per kind, 2 nmt jobs on 8 waves; nkq = k-steps per K half of the MLP out projection.
+PT_TUNED_CASES = [
+    (1, 64, 1, 256, 1, 1, 1),        # smallest: one token pair, one job
+    (1, 64, 4, 256, 49, 3, 6),       # first second chunk, state: nks_s = 4 = one chunk + a partial one
+    (1, 64, 4, 256, 3, 49, 6),       # the same on the side prepare_query uses
+    (1, 64, 2, 1024, 96, 96, 20),    # whole chunks, S + A = 192, no padding column, LDS > 80 KiB
+    (1, 64, 8, 768, 191, 1, 12),     # twelve k-steps, the last padded by one input; nkq = 24
+    (1, 64, 16, 1024, 29, 8, 20),    # widest MLP (nkq = 32), most heads (head_dim 4)
+    (1, 64, 4, 256, 5, 3, 129),      # three job rounds: nmt = 9
+    (1, 64, 1, 512, 5, 3, 300),      # many job rounds: nmt = 19
+]
+PT_TUNED_WIDEST = PT_TUNED_CASES[3]
+# General path (k_lin, k_attn, k_last_rows, k_value_head): head_dim HD = E / heads over HDL lanes,
+# DPL = HD / HDL features per lane, G = 64 / HDL key groups; tp = row pitch of a window, 32-row tiles.
+PT_GENERAL_CASES = [
+    (2, 256, 1, 64, 5, 3, 9),        # HD 256: HDL 64, DPL 4, G 1
+    (2, 128, 1, 128, 5, 3, 9),       # HD 128: 64, 2, 1
+    (2, 256, 2, 256, 5, 3, 9),       # HD 128: 64, 2, 1
+    (2, 192, 1, 192, 5, 3, 9),       # HD 192: 64, 3, 1
+    (2, 192, 2, 192, 5, 3, 9),       # HD 96: 32, 3, 2
+    (2, 192, 4, 192, 5, 3, 9),       # HD 48: 16, 3, 4
+    (2, 192, 16, 192, 5, 3, 9),      # HD 12: 4, 3, 16
+    (2, 192, 32, 192, 5, 3, 9),      # HD 6: 2, 3, 32
+    (2, 64, 8, 64, 5, 3, 9),         # HD 8: 8, 1, 8
+    (2, 128, 32, 128, 5, 3, 9),      # HD 4: 4, 1, 16
+    (2, 256, 64, 1024, 5, 3, 9),     # HD 4, most heads, widest MLP
+    (2, 64, 4, 64, 255, 1, 6),       # widest input, the split at the state end
+    (2, 64, 4, 64, 1, 255, 6),       # widest input, the split at the action end
+    (1, 128, 4, 256, 128, 128, 6),   # widest input, even
+    (2, 64, 4, 64, 5, 3, 1),         # one transition: tp = 32, two real tokens
+    (2, 64, 4, 64, 5, 3, 16),        # full tile: 2 QL = 32 rows exactly
+    (2, 64, 4, 64, 5, 3, 17),        # one past the tile: tp = 64, short windows skip tile 2
+]
+# Long windows of the general path: prefixes of ONE stretch of rows (oracle_prefixes).
+PT_GENERAL_LONG = (2, 64, 4, 64, 5, 3, 1024)
+PT_GENERAL_TOP = (2, 64, 1, 64, 5, 3, 4096)
+# Seeds: the shape itself unless a case is listed here.  (A listed case did not pass the float32 vs
+# float64 check of tests/test_relabel_oracle.py with its own seed: a bf16 flip of a logit that weighs.)
+PT_CASE_SEEDS = {}
+
+
+def pt_case_id(case):
+    return "L%d-E%d-h%d-I%d-S%d-A%d-QL%d" % case
+
+
+def pt_case_rng(case):
+    return np.random.default_rng(PT_CASE_SEEDS.get(case, list(case)))
+
+
+def pt_case_lengths(QL, rng):
+    """Every length 1..QL up to 129; beyond, about 120 of them: both neighbours of every multiple of
+    16 (a token tile) up to 64, of every multiple of 64 (a job round of the tuned kernel: 8 jobs of
+    16 tokens of one kind), the ends, and random ones."""
+    if QL <= 129:
+        return None
+    edges = {1, 2, QL - 1, QL}
+    for m in list(range(16, 65, 16)) + list(range(64, QL, 64)):
+        edges |= {m - 1, m, m + 1}
+    edges = {l for l in edges if 1 <= l <= QL}
+    rest = np.setdiff1d(np.arange(1, QL + 1), sorted(edges))
+    return np.sort(np.concatenate([sorted(edges), rng.choice(rest, 118 - len(edges), replace=False)]))
+
+
+def pt_case_inputs(case):
+    """(p, obs, act, lens, starts, t0, max_ep) of one envelope case: seeded random weights
+    (oracle.relabel_oracle.make_pt_params), a few hundred dataset rows, every length 1..QL once plus 16
+    random windows plus 16 that share rows with earlier ones (random_windows)."""
+    from oracle import relabel_oracle as ro
+    L, E, heads, I, S, A, QL = case
+    rng = pt_case_rng(case)
+    max_ep = max(150, QL + 20)
+    p = ro.make_pt_params(rng, S, A, max_ep, embd=E, pref=8, inter=I, layers=L)
+    n_rows = max(300, QL + 200)
+    obs = rng.standard_normal((n_rows, S)).astype(np.float32)
+    act = rng.uniform(-1, 1, (n_rows, A)).astype(np.float32)
+    lens, starts, t0 = random_windows(rng, n_rows, max_ep, QL, 16, lengths=pt_case_lengths(QL, rng))
+    return p, obs, act, lens, starts, t0, max_ep
+
+
+def pt_prefix_inputs(case, n, lengths, n_random):
+    """(p, obs, act, start, t0, lens, max_ep) of a long case: the windows are the prefixes ``lengths``,
+    and ``n_random`` more, of the n transitions from row ``start``, first timestep t0."""
+    from oracle import relabel_oracle as ro
+    L, E, heads, I, S, A, QL = case
+    rng = pt_case_rng(case)
+    max_ep = QL + 50
+    p = ro.make_pt_params(rng, S, A, max_ep, embd=E, pref=8, inter=I, layers=L)
+    n_rows = n + 64
+    obs = rng.standard_normal((n_rows, S)).astype(np.float32)
+    act = rng.uniform(-1, 1, (n_rows, A)).astype(np.float32)
+    start, t0 = int(rng.integers(1, n_rows - n)), int(rng.integers(1, max_ep + 2 - n))
+    lens = np.concatenate([lengths, rng.integers(1, n + 1, n_random)]).astype(np.int32)
+    return p, obs, act, start, t0, lens, max_ep
+
+
+def pt_clamp_windows(starts, lens, t0, n_rows, n_temb, QL):
+    """The rule of include/iqlhip.h as both load_window functions implement it: the length into
+    [1, min(QL, n_rows, n_temb)], then the start into [0, n_rows - len] and the first timestep into
+    [0, n_temb - len]."""
+    lens = np.maximum(np.minimum(np.asarray(lens, np.int64), min(QL, n_rows, n_temb)), 1)
+    starts = np.clip(np.asarray(starts, np.int64), 0, n_rows - lens)
+    t0 = np.clip(np.asarray(t0, np.int64), 0, n_temb - lens)
+    return starts.astype(np.int64), lens.astype(np.int32), t0.astype(np.int32)

@@ -14,11 +14,10 @@ import torch
 from oracle import relabel_oracle as ro
 from tests.test_relabel_oracle import g5_dataset
 from tests import helpers
+from tests.helpers import PT_TOL as TOL, check_close, oracle_windows, random_windows
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-TOL = 5e-3
-TIGHT_MEDIAN = 1e-5
 
 
 class FakeEnv:
@@ -39,45 +38,6 @@ def make_model(p, S, A, max_ep, heads, max_pos=64):
     missing = m.load_state_dict({k: torch.from_numpy(v) for k, v in p.items()}, strict=False)
     assert all(k.endswith("causal_bias") for k in missing.missing_keys) and not missing.unexpected_keys
     return m.to(DEV)
-
-
-def oracle_windows(p, obs, act, starts, lens, t0, QL, heads):
-    """pt_value_last of right-aligned windows (start, len, t0), batched."""
-    n, S, A = len(lens), obs.shape[1], act.shape[1]
-    sts = np.zeros((n, QL, S), np.float32); acs = np.zeros((n, QL, A), np.float32)
-    ts = np.zeros((n, QL), np.int64); am = np.zeros((n, QL), np.float32)
-    for i, (s0, l0) in enumerate(zip(starts, lens)):
-        s0, l0 = int(s0), int(l0)
-        sts[i, QL - l0:] = obs[s0:s0 + l0]; acs[i, QL - l0:] = act[s0:s0 + l0]
-        ts[i, QL - l0:] = (0 if t0 is None else int(t0[i])) + np.arange(l0); am[i, QL - l0:] = 1
-    out = np.empty(n, np.float32)
-    for b in range(0, n, 64):
-        out[b:b + 64] = ro.pt_value_last(p, sts[b:b + 64], acs[b:b + 64], ts[b:b + 64], am[b:b + 64],
-                                         num_heads=heads)
-    return out
-
-
-def random_windows(rng, n_rows, max_ep, QL, n_extra):
-    """Every length 1..QL once, then random ones, then windows sharing rows with earlier ones."""
-    lens = np.concatenate([np.arange(1, QL + 1), rng.integers(1, QL + 1, n_extra)]).astype(np.int32)
-    starts = np.array([rng.integers(0, n_rows - l + 1) for l in lens], np.int64)
-    t0 = np.array([rng.integers(0, max_ep + 2 - l) for l in lens], np.int32)
-    # the same rows again under other lengths / timesteps
-    k = min(16, len(lens))
-    lens2 = rng.integers(1, QL + 1, k).astype(np.int32)
-    starts2 = np.minimum(starts[:k], n_rows - lens2)
-    t02 = np.array([rng.integers(0, max_ep + 2 - l) for l in lens2], np.int32)
-    return (np.concatenate([lens, lens2]), np.concatenate([starts, starts2]), np.concatenate([t0, t02]))
-
-
-def check_close(got, want, short=None):
-    """Loose bound everywhere; the tight median bound on all windows, or on `short` (a mask)."""
-    d = np.abs(got.astype(np.float64) - want)
-    assert np.isfinite(got).all()
-    np.testing.assert_allclose(got, want, rtol=TOL, atol=TOL)
-    sel = d if short is None else d[short]
-    assert np.median(sel) <= TIGHT_MEDIAN, (float(d.max()), float(np.median(sel)))
-    return float(d.max()), float(np.median(d))
 
 
 @pytest.mark.parametrize("L,E,heads,I,S,A,QL", [

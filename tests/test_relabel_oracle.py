@@ -224,3 +224,85 @@ def test_mlp_reference_reproduces_the_relabel_oracle():
     h = np.maximum(x.astype(np.float64) @ ws[0] + bs[0], 0) * keep[0] * 2.0
     h = np.maximum(h @ ws[1] + bs[1], 0) * keep[1] * 2.0
     np.testing.assert_allclose(helpers.mlp_forward_ref(ws, bs, x, 0, 0, keeps=keep, scale=2.0), h @ ws[2] + bs[2], atol=1e-12)
+
+
+# ---- the preference-transformer envelope cases (tests/helpers.py, tests/test_gpu_pt_envelope.py): the
+# ---- float64 mode of pt_value_last is the yardstick there.  Here: the float32 restatement and the
+# ---- float64 one agree inside the bounds those tests apply, so a kernel that misses them is wrong
+def test_pt_float64_mode_keeps_the_bf16_rounding_points():
+    rng = np.random.default_rng(2)
+    S, A, QL = 5, 3, 6
+    p = ro.make_pt_params(rng, S, A, 20, embd=16, pref=8, inter=32, layers=2)
+    st = rng.standard_normal((4, QL, S)).astype(np.float32)
+    ac = rng.standard_normal((4, QL, A)).astype(np.float32)
+    ts, am = np.tile(np.arange(QL), (4, 1)), np.ones((4, QL), np.float32)
+    v32 = ro.pt_value_last(p, st, ac, ts, am, num_heads=4)
+    assert v32.dtype == np.float32
+    np.testing.assert_array_equal(v32, ro.pt_value_last(p, st, ac, ts, am, num_heads=4, dtype=np.float32))
+    v64 = ro.pt_value_last(p, st, ac, ts, am, num_heads=4, dtype=np.float64)
+    assert v64.dtype == np.float64 and not np.array_equal(v64, v32.astype(np.float64))
+    np.testing.assert_allclose(v32, v64, rtol=0, atol=1e-5)
+    # one rounding from float64, ties to even, 8 significant bits
+    x = np.array([1.0 + 2.0 ** -8, 1.0 + 3 * 2.0 ** -8, 1.0 + 2.0 ** -8 + 2.0 ** -40, -3.14159, 0.0, 1e-3])
+    r = ro._bf16_as(x, np.float64)
+    np.testing.assert_array_equal(r[:3], [1.0, 1.0 + 2.0 ** -6, 1.0 + 2.0 ** -7])
+    np.testing.assert_array_equal(r, ro._bf16_as(r, np.float64))
+    np.testing.assert_array_equal(r.astype(np.float32), ro.bf16(r.astype(np.float32)))
+    assert np.all(np.abs(r - x) <= helpers.bf16_ulp(x) / 2)
+
+
+def test_pt_oracle_windows_trimmed_to_their_batch():
+    """The long cases pad a batch to its longest window, not to query_length: the same value."""
+    case = (2, 64, 4, 64, 5, 3, 17)
+    p, obs, act, lens, starts, t0, _ = helpers.pt_case_inputs(case)
+    full = helpers.oracle_windows(p, obs, act, starts, lens, t0, 17, 4, dtype=np.float64)
+    np.testing.assert_allclose(helpers.oracle_windows(p, obs, act, starts, lens, t0, 17, 4, dtype=np.float64, trim=True),
+                               full, rtol=0, atol=1e-12)
+    np.testing.assert_allclose(helpers.oracle_windows(p, obs, act, starts, lens, t0, 40, 4, dtype=np.float64),
+                               full, rtol=0, atol=1e-12)
+    # and a prefix of one longer forward is the window of that length
+    pre = helpers.oracle_prefixes(p, obs, act, 7, 17, 3, 4, dtype=np.float64)
+    ln = np.arange(1, 18, dtype=np.int32)
+    np.testing.assert_allclose(pre, helpers.oracle_windows(p, obs, act, np.full(17, 7), ln, np.full(17, 3), 17, 4,
+                                                           dtype=np.float64), rtol=0, atol=1e-12)
+
+
+@pytest.mark.parametrize("case", helpers.PT_TUNED_CASES + helpers.PT_GENERAL_CASES, ids=helpers.pt_case_id)
+def test_pt_envelope_case_float32_vs_float64(case):
+    """Worst over the cases and both timestep modes: max |d| 6.7e-4 (the widest tuned shape, win_t0 None),
+    median <= 5.6e-7.  Every case passes with its own shape as the seed (helpers.PT_CASE_SEEDS is empty)."""
+    L, E, heads, I, S, A, QL = case
+    p, obs, act, lens, starts, t0, _ = helpers.pt_case_inputs(case)
+    assert lens.min() == 1 and lens.max() == QL and len(lens) <= 161
+    assert (starts >= 0).all() and (starts + lens <= len(obs)).all() and (t0 + lens <= len(p["timestep_embed.weight"])).all()
+    trim = QL > 64
+    for tt in (t0,) if trim else (t0, None):  # (the long cases once: their forwards take seconds)
+        f32 = helpers.oracle_windows(p, obs, act, starts, lens, tt, QL, heads, trim=trim)
+        f64 = helpers.oracle_windows(p, obs, act, starts, lens, tt, QL, heads, dtype=np.float64, trim=trim)
+        mx, med = helpers.check_close(f32, f64, short=lens <= 8)
+        print(f"{helpers.pt_case_id(case)}: float32 vs float64 max |d| {mx:.3g}, median {med:.3g}")
+
+
+@pytest.mark.parametrize("case,n", [(helpers.PT_GENERAL_LONG, 1024), (helpers.PT_GENERAL_TOP, 4096)],
+                         ids=["long", "top"])
+def test_pt_envelope_long_case_float32_vs_float64(case, n):
+    """Every prefix of the one forward.  QL 1024: max |d| 2.1e-4, median 8.6e-7; QL 4096: 1.1e-3 /
+    7.9e-7 (the float64 forward over 4096 transitions: 9.5 s on one core of the development host)."""
+    heads = case[2]
+    p, obs, act, start, t0, lens, _ = helpers.pt_prefix_inputs(case, n, [1, 2, n // 2, n - 1, n], 0)
+    f32 = helpers.oracle_prefixes(p, obs, act, start, n, t0, heads)
+    f64 = helpers.oracle_prefixes(p, obs, act, start, n, t0, heads, dtype=np.float64)
+    mx, med = helpers.check_close(f32, f64, short=np.arange(1, n + 1) <= 8)
+    print(f"{helpers.pt_case_id(case)} ({n}): float32 vs float64 max |d| {mx:.3g}, median {med:.3g}")
+
+
+def test_pt_clamp_rule_passes_valid_windows_through():
+    rng = np.random.default_rng(0)
+    lens, starts, t0 = helpers.random_windows(rng, 60, 40, 8, 16)
+    s2, l2, t2 = helpers.pt_clamp_windows(starts, lens, t0, 60, 41, 8)
+    assert np.array_equal(s2, starts) and np.array_equal(l2, lens) and np.array_equal(t2, t0)
+    s2, l2, t2 = helpers.pt_clamp_windows([-4, 58, 160, 5, 5, 5, 5, 5], [5, 5, 3, 0, -3, 13, 4, 3],
+                                          [0, 0, 0, 0, 0, 0, -1, 40], 60, 41, 8)
+    assert s2.tolist() == [0, 55, 57, 5, 5, 5, 5, 5] and l2.tolist() == [5, 5, 3, 1, 1, 8, 4, 3]
+    assert t2.tolist() == [0, 0, 0, 0, 0, 0, 0, 38]
+    assert [a.tolist() for a in helpers.pt_clamp_windows([0], [8], [2], 3, 41, 8)] == [[0], [3], [2]]
