@@ -1,6 +1,8 @@
-"""The chunked train / evaluate / checkpoint loop of the custom-offline flavours (``custom_offline``,
-``custom_offline_br``, ``custom_offline_bb``), once, and the setup every ``train()`` shares: the checkpoint
-directories, the default logger and the ``seed`` tag of K > 1 records.
+"""The chunked train / evaluate / checkpoint loop of the custom-offline flavours (``custom_offline.train`` and
+``train_runs``, ``custom_offline_br``, ``custom_offline_bb``), once, and the setup every ``train()`` shares: the
+checkpoint directories, the default logger and the ``seed`` tag of K > 1 records.  The offline flavour (``train``,
+``sweep.train_runs``) takes that setup from here and runs ``_window_loop``: window means instead of every step's
+losses, a metric exchange instead of a best model.
 
 ``run`` knows no trainer class, buffer or sampler: a flavour hands in how a chunk of steps is queued and how
 one seed is evaluated.  Its members are the K seeds of one config (one step count and evaluation period for all)

@@ -35,13 +35,12 @@ from dataclasses import asdict, fields
 from typing import Any, Callable, Dict, List, Mapping, Optional, Sequence, Tuple, Union
 
 import numpy as np
-import torch
 
-from . import _lib, _resume, custom_offline
+from . import _lib, _resume, _window_loop, custom_offline
 from . import distributed as D
 from ._offline_loop import checkpoint_dirs
 from .iql import ImplicitQLearning, TrainConfig, load_config
-from .multi import GROUP_MODES
+from .multi import GROUP_MODES, SeedGroup, check_group_mode, resolve_group_mode
 
 # top-level keys of a sweep file that only name or describe it (kept as labels, otherwise ignored)
 LABEL_KEYS = ("program", "project", "name", "description", "metric", "command", "entity")
@@ -225,12 +224,6 @@ def _relabel_key(config: TrainConfig) -> tuple:
     return (config.env, str(config.device)) + tuple(getattr(config, f) for f in RELABEL_FIELDS)
 
 
-def _next_boundary(config: TrainConfig, t: int) -> int:
-    """ref:1533-1544 as train() chunks it: the run's next log boundary, eval boundary or end."""
-    return min(int(config.max_timesteps), (t // config.log_freq + 1) * config.log_freq,
-               (t // config.eval_freq + 1) * config.eval_freq)
-
-
 # --------------------------------------------------------------------------- #
 # training
 # --------------------------------------------------------------------------- #
@@ -321,7 +314,6 @@ def train_runs(configs: Sequence[TrainConfig], env=None, dataset=None, *, runs_p
     # the module, not the function the package exports under the same name (build_dataset is looked
     # up on it at call time: tests count its calls)
     T = importlib.import_module(".train", __package__)
-    from .multi import SeedGroup
 
     configs = list(configs)
     check_runs(configs, runs_per_gpu)
@@ -334,7 +326,6 @@ def train_runs(configs: Sequence[TrainConfig], env=None, dataset=None, *, runs_p
         raise ValueError("run_ids: one entry per config")
     if isinstance(evaluate, (list, tuple)) and len(evaluate) != n:
         raise ValueError(f"evaluate: {len(evaluate)} callables for {n} configs")
-    from .multi import check_group_mode
     check_group_mode(group_mode)
     rank, world = _rank_world()
     mine = rank_share(n, rank, world)
@@ -381,109 +372,43 @@ def train_runs(configs: Sequence[TrainConfig], env=None, dataset=None, *, runs_p
 
     trainers: Dict[int, ImplicitQLearning] = {}
     for bi, batch in enumerate(batches):
-        state = {}
+        bufs, evals = {}, {}
         for i in batch:
             cfg = configs[i]
-            buf, mean, std = buffer_for(i)
+            bufs[i], mean, std = buffer_for(i)
             e = envs[cfg.env]
             max_action = float(e.action_space.high[0])
             checkpoint_dirs(cfg, [cfg.seed], resume=resume)  # (one seed: the path itself, with its config.yaml)
             trainers[i] = T._build_trainer(cfg, cfg.seed, dims[cfg.env][0], dims[cfg.env][1], max_action, precision)
-            state[i] = (buf, mean, std, max_action, e)
-        _run_batch(configs, batch, trainers, state, SeedGroup, group_mode, logger, evaluate, vector_env, run_ids,
-                   resume)
+            evals[i] = (cfg, e, max_action, mean, std, cfg.seed)
+        # one launch batch: its runs go in lock step to the next boundary of any of them, and at its end a run
+        # leaves and the group is rebuilt over the rest.  The loop's member j is run members[j]
+        members = [i for i in batch if int(configs[i].max_timesteps) > 0]
+        cfgs, trs = [configs[i] for i in members], [trainers[i] for i in members]
+        dirs = [c.checkpoints_path for c in cfgs]
+
+        def make_group(active):
+            group_trs = [trs[j] for j in active]
+            mode = resolve_group_mode(group_mode, group_trs, cfgs[active[0]].batch_size)
+            return SeedGroup(group_trs) if mode is None else SeedGroup(group_trs, mode=mode)
+
+        def steps(group, active, t, n):
+            return group.train_steps([bufs[members[j]] for j in active], n, cfgs[active[0]].batch_size,
+                                     return_losses=True)
+
+        _window_loop.run(
+            _window_loop.restore(trs, dirs) if resume else _window_loop.State(len(members)), trs,
+            [c.seed for c in cfgs], [c.max_timesteps for c in cfgs], [c.log_freq for c in cfgs],
+            [c.eval_freq for c in cfgs], logger, dirs, make_group, steps,
+            T.member_evaluator([evaluate[i] for i in members] if isinstance(evaluate, (list, tuple)) else evaluate,
+                               vector_env, [evals[i] for i in members]),
+            lambda rec, j: dict(rec, run=run_ids[members[j]], seed=cfgs[j].seed),
+            goal_env=["antmaze" in c.env.lower() for c in cfgs], resume=resume)
         for key in [k for k in datasets if last_use_r[k] <= bi]:
             del datasets[key]
         for key in [k for k in buffers if last_use_b[k] <= bi]:
             del buffers[key]
     return [trainers[i] for i in mine]
-
-
-def _run_batch(configs, batch, trainers, state, SeedGroup, group_mode, logger, evaluate, vector_env, run_ids,
-               resume=False):
-    """One launch batch: all runs start at step 0 (``resume``: at the batch's newest complete resume
-    generation) and run in lock step to the next boundary of any of them; a run at its end leaves and the
-    group is rebuilt over the rest."""
-    from .train import eval_actor
-
-    def make_group(members):
-        trs = [trainers[i] for i in members]
-        from .multi import resolve_group_mode
-        mode = resolve_group_mode(group_mode, trs, configs[members[0]].batch_size)
-        return SeedGroup(trs) if mode is None else SeedGroup(trs, mode=mode)
-
-    windows: Dict[int, torch.Tensor] = {}
-    t = 0
-    ended = set()
-    members = [i for i in batch if int(configs[i].max_timesteps) > 0]
-    dirs = [configs[i].checkpoints_path for i in members]
-    kept: Dict[int, int] = {}  # position in members -> step of the generation file the run holds
-    if resume:  # (before the trainers join a group)
-        t, payloads = _resume.restore(dirs, kept)
-        for j, p in payloads.items():
-            i = members[j]
-            trainers[i].load_resume_state(p["trainer"])
-            if p["loop"]["window"] is not None:
-                windows[i] = p["loop"]["window"].to(configs[i].device)
-            if p["finished"]:
-                ended.add(i)
-
-    def commit(runs):
-        payloads = {members.index(i): {
-            "finished": t >= int(configs[i].max_timesteps), "trainer": trainers[i].resume_state(), "sampler": None,
-            "loop": {"window": None if t % configs[i].log_freq == 0 else windows[i].cpu()}} for i in runs}
-        _resume.commit(dirs, t, payloads, kept)
-
-    active = [i for i in members if i not in ended and t < int(configs[i].max_timesteps)]
-    group = make_group(active) if active else None
-    tag = lambda rec, i: dict(rec, run=run_ids[i], seed=configs[i].seed)
-    while active:
-        nxt = min(_next_boundary(configs[i], t) for i in active)
-        B = configs[active[0]].batch_size
-        losses = group.train_steps([state[i][0] for i in active], nxt - t, B, return_losses=True)
-        for i, l in zip(active, losses):
-            windows[i] = l if t % configs[i].log_freq == 0 else torch.cat([windows[i], l])
-        t = nxt
-        for i in active:
-            if t % configs[i].log_freq == 0:
-                mean = windows[i].mean(dim=0).tolist()
-                rec = {"value_loss": mean[0], "q_loss": mean[1], "actor_loss": mean[2]}
-                logger(tag(rec, i), trainers[i].total_it)
-        evals = [i for i in active if t % configs[i].eval_freq == 0]
-        if evals:
-            group.synchronize()
-        for i in evals:
-            cfg, trainer = configs[i], trainers[i]
-            _, mean_s, std_s, max_action, e = state[i]
-            ev = evaluate[i] if isinstance(evaluate, (list, tuple)) else evaluate
-            eval_log: Dict[str, float] = {}
-            if ev is not None:
-                scores, steps_to_goal = ev(trainer.actor, t)
-            elif vector_env is not None or (e is not None and hasattr(e, "spec")):
-                scores, steps_to_goal = eval_actor(cfg.env, trainer.actor, max_action, mean_s, std_s, cfg.device,
-                                                   cfg.n_episodes, cfg.seed, vector_env=vector_env)
-            else:
-                scores, steps_to_goal = None, []
-            if scores is not None:
-                eval_log["mean_score"] = float(np.mean(scores))
-                if "antmaze" in cfg.env.lower():
-                    eval_log["avg_steps_to_goal"] = float(np.mean(steps_to_goal)) if steps_to_goal else -1.0
-                logger(tag(eval_log, i), trainer.total_it)
-            if cfg.checkpoints_path is not None:
-                torch.save(trainer.state_dict(), os.path.join(cfg.checkpoints_path, f"checkpoint_{t - 1}.pt"))
-        left = [i for i in active if t < int(configs[i].max_timesteps)]
-        if resume and (evals or len(left) != len(active)):
-            if not evals:
-                group.synchronize()
-            commit(active)
-        if len(left) != len(active):
-            group.synchronize()
-            group.close()
-            active = left
-            group = make_group(active) if active else None
-    if group is not None:
-        group.synchronize()
-        group.close()
 
 
 # --------------------------------------------------------------------------- #

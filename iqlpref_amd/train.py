@@ -8,7 +8,6 @@ step, ref:589,607,633).  gym / d4rl / wandb are optional: pass ``env`` and
 when it is importable.
 """
 import os
-import time
 from dataclasses import asdict
 from pathlib import Path
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
@@ -16,10 +15,10 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _resume
+from . import _resume, _window_loop
 from . import distributed as D
 from . import prep
-from ._offline_loop import checkpoint_dirs
+from ._offline_loop import checkpoint_dirs, tag
 from .iql import (DeterministicPolicy, EnsembleQ, GaussianPolicy, ImplicitQLearning, ReplayBuffer, TrainConfig, TwinQ,
                   ValueFunction, compute_mean_std, normalize_states, set_seed)
 from .relabel import (load_mlp_reward_model, load_pt_reward_model, modify_reward, qlearning_dataset_bnn,
@@ -132,6 +131,23 @@ def eval_actor(env_name: str, actor, max_action: float, state_mean, state_std, d
         envs.close()
         actor.train()  # ref:340: the reference always hands the actor back in train mode
     return np.asarray(ledger.scores[:n_episodes]), ledger.steps_to_goal
+
+
+def member_evaluator(evaluate, vector_env, members: Sequence[tuple]) -> Callable:
+    """The ``evaluate(k, trainer, t) -> (scores, steps_to_goal)`` that ``_window_loop.run`` takes.  ``members``: one
+    ``(config, env, max_action, state_mean, state_std, seed)`` each.  ``evaluate``: the user's ``(actor, step)``,
+    one per member, or None: then ``eval_actor`` on ``config.env`` at the member's seed when there is a
+    ``vector_env`` or an ``env`` with a ``.spec``, else no evaluation, ``(None, [])``."""
+    def run(k, trainer, t):
+        config, env, max_action, state_mean, state_std, seed = members[k]
+        ev = evaluate[k] if isinstance(evaluate, (list, tuple)) else evaluate
+        if ev is not None:
+            return ev(trainer.actor, t)
+        if vector_env is not None or (env is not None and hasattr(env, "spec")):
+            return eval_actor(config.env, trainer.actor, max_action, state_mean, state_std, config.device,
+                              config.n_episodes, seed, vector_env=vector_env)
+        return None, []
+    return run
 
 
 def build_dataset(config: TrainConfig, env, dataset=None) -> Dict[str, np.ndarray]:
@@ -320,37 +336,22 @@ def train(config: TrainConfig, env=None, dataset=None, *, state_dim: Optional[in
         warnings.warn(f"seeds_per_gpu={K} with load_model set: all {K} seeds start from the SAME checkpoint "
                       f"({config.load_model}) and differ only in their sample streams", stacklevel=2)
     trainers = [_build_trainer(config, seeds[k], state_dim, action_dim, max_action, precision) for k in range(K)]
-    total = int(config.max_timesteps)
-    t = 0
-    windows: List[Optional[torch.Tensor]] = [None] * K
-    last: List[Dict[str, float]] = [{} for _ in range(K)]
-    kept: Dict[int, int] = {}  # seed slot -> step of the generation file it holds
     many_ranks = D.dist.is_initialized() and D.dist.get_world_size() > 1
+    state = _window_loop.State(K)
     if resume:  # (before the trainers join a group)
         common = None
         if many_ranks:  # the newest generation that every rank has (-1: some rank has none)
             found = _resume.latest(ckpt_dirs)
             mine = -1 if found is None else found[0]
             common = int(min(r["total_it"] for r in D.gather_metrics({"total_it": mine}, device=config.device)))
-        t, payloads = _resume.restore(ckpt_dirs, kept, at_most=common)
-        if many_ranks and any(int(r["total_it"]) != t for r in D.gather_metrics({"total_it": t}, device=config.device)):
+        state = _window_loop.restore(trainers, ckpt_dirs, at_most=common)
+        if many_ranks and any(int(r["total_it"]) != state.t
+                              for r in D.gather_metrics({"total_it": state.t}, device=config.device)):
             raise ValueError("resume=True: the ranks have no resume generation in common")
-        for k, p in payloads.items():
-            trainers[k].load_resume_state(p["trainer"])
-            w = p["loop"]["window"]
-            windows[k] = None if w is None else w.to(config.device)
-            last[k] = dict(p["loop"]["last"])
-    group = None
-    if K > 1:
-        from .multi import SeedGroup
-        group = SeedGroup(trainers, mode=resolve_group_mode(group_mode, trainers, config.batch_size))
 
-    def commit():
-        """One resume generation at step t: every seed's file, then the generation before goes."""
-        payloads = {k: {"finished": t >= total, "trainer": trainers[k].resume_state(), "sampler": None,
-                        "loop": {"window": None if t % config.log_freq == 0 or windows[k] is None
-                                 else windows[k].cpu(), "last": dict(last[k])}} for k in range(K)}
-        _resume.commit(ckpt_dirs, t, payloads, kept, keep_previous=many_ranks)
+    def make_group(active):  # (always all K seeds: they end together)
+        from .multi import SeedGroup
+        return None if K == 1 else SeedGroup(trainers, mode=resolve_group_mode(group_mode, trainers, config.batch_size))
 
     if logger is None:
         try:
@@ -363,72 +364,26 @@ def train(config: TrainConfig, env=None, dataset=None, *, state_dim: Optional[in
                                                     for n, v in d.items() if n != "seed"}, step=step)
         except ImportError:
             logger = lambda d, step: print(f"[{step}] " + " ".join(f"{n}={v:.5g}" for n, v in d.items()))
-    tag = (lambda rec, k: rec) if K == 1 else (lambda rec, k: dict(rec, seed=seeds[k]))
 
-    t_window = time.perf_counter()
-    while t < total:
-        # run to the next logging / evaluation boundary in one library call (ref:1533-1544)
-        nxt = min(total, (t // config.log_freq + 1) * config.log_freq,
-                  (t // config.eval_freq + 1) * config.eval_freq)
-        idx = None
-        if index_stream is not None:
-            idx = [index_stream(k, t, nxt - t).to(device=config.device, dtype=torch.int64) for k in range(K)]
+    def steps(group, active, t, n):  # one library call for steps t .. t + n - 1 of all K seeds (ref:1533-1544)
+        idx = None if index_stream is None else [index_stream(k, t, n).to(device=config.device, dtype=torch.int64)
+                                                 for k in range(K)]
         if group is None:
-            losses = [trainers[0].train_steps(buffers[0], nxt - t, config.batch_size,
-                                              indices=None if idx is None else idx[0])]
-        else:
-            losses = group.train_steps(buffers, nxt - t, config.batch_size, return_losses=True, indices=idx)
-        for k in range(K):
-            windows[k] = losses[k] if t % config.log_freq == 0 else torch.cat([windows[k], losses[k]])
-        t = nxt
-        if t % config.log_freq == 0:
-            means = [w.mean(dim=0).tolist() for w in windows]  # the only host syncs of the window
-            now = time.perf_counter()
-            for k, mean in enumerate(means):
-                rec = {"value_loss": mean[0], "q_loss": mean[1], "actor_loss": mean[2]}
-                logger(tag(dict(rec), k), trainers[k].total_it)
-                last[k] = dict(rec, steps_per_sec=windows[k].shape[0] / max(now - t_window, 1e-9))
-            t_window = now
-        if t % config.eval_freq == 0:
-            if group is not None:
-                group.synchronize()
-            records = []
-            for k, trainer in enumerate(trainers):
-                eval_log: Dict[str, float] = {}
-                actor = trainer.actor
-                if evaluate is not None:
-                    scores, steps_to_goal = evaluate(actor, t)
-                elif vector_env is not None or (env is not None and hasattr(env, "spec")):
-                    # the evaluation seed of a run is the run's own seed (ref:1547-1556)
-                    scores, steps_to_goal = eval_actor(config.env, actor, max_action, stats[k][0], stats[k][1],
-                                                       config.device, config.n_episodes, seeds[k],
-                                                       vector_env=vector_env)
-                else:
-                    scores, steps_to_goal = None, []
-                if scores is not None:
-                    eval_log["mean_score"] = float(np.mean(scores))
-                    if "antmaze" in config.env.lower():
-                        eval_log["avg_steps_to_goal"] = float(np.mean(steps_to_goal)) if steps_to_goal else -1.0
-                    logger(tag(dict(eval_log), k), trainer.total_it)
-                if ckpt_dirs[k] is not None:
-                    torch.save(trainer.state_dict(), os.path.join(ckpt_dirs[k], f"checkpoint_{t - 1}.pt"))
-                records.append(dict(last[k] if t >= config.log_freq else {}, seed=seeds[k],
-                                    total_it=trainer.total_it, **eval_log))
-            # end-of-eval metric exchange across the per-GPU seeds (the path's only collective)
-            recs = D.gather_metric_records(records, device=config.device)
-            if rank == 0 and len(recs) > 1:
-                logger(D.summarize(recs), trainers[0].total_it)
-            if resume:
-                commit()
-    if resume and kept.get(0) != t:  # (max_timesteps is no multiple of eval_freq: the final state, finished)
-        if group is not None:
-            group.synchronize()
-        commit()
-    if group is not None:
-        group.synchronize()
-        group.close()
-        return trainers
-    return trainers[0]
+            return [trainers[0].train_steps(buffers[0], n, config.batch_size, indices=None if idx is None else idx[0])]
+        return group.train_steps(buffers, n, config.batch_size, return_losses=True, indices=idx)
+
+    def exchange(records):  # end-of-eval metrics across the per-GPU seeds (the path's only collective)
+        recs = D.gather_metric_records(records, device=config.device)
+        if rank == 0 and len(recs) > 1:
+            logger(D.summarize(recs), trainers[0].total_it)
+
+    # the evaluation seed of a run is the run's own seed (ref:1547-1556)
+    evaluator = member_evaluator(evaluate, vector_env,
+                                 [(config, env, max_action, *stats[k], seeds[k]) for k in range(K)])
+    _window_loop.run(state, trainers, seeds, config.max_timesteps, config.log_freq, config.eval_freq, logger, ckpt_dirs,
+                     make_group, steps, evaluator, tag(seeds), goal_env="antmaze" in config.env.lower(),
+                     exchange=exchange, resume=resume, keep_previous=many_ranks)
+    return trainers if K > 1 else trainers[0]
 
 
 def main(argv=None):

@@ -160,21 +160,31 @@ def cut_and_resume(tmp_path, data, tamper=None, **kw):
 
 
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
-@pytest.mark.parametrize("shape", ["one_seed", "three_seeds", "general_step"])
+@pytest.mark.parametrize("shape", ["one_seed", "three_seeds", "general_step", "end_off_the_eval_grid"])
 def test_offline_train_resumed_is_the_uninterrupted_run(tmp_path, shape, precision):
-    kw = {"one_seed": {}, "three_seeds": {"seeds_per_gpu": 3}, "general_step": {"n_hidden": 3, "hidden_dim": 40}}[shape]
+    """``end_off_the_eval_grid``: 34 steps, no multiple of ``eval_freq``: the run still ends with a generation at
+    its last step, written when its seeds leave the loop, and that generation says finished."""
+    from iqlpref_amd import _resume
+    kw = {"one_seed": {}, "three_seeds": {"seeds_per_gpu": 3}, "general_step": {"n_hidden": 3, "hidden_dim": 40},
+          "end_off_the_eval_grid": {"max_timesteps": 34}}[shape]
     data = synth(300)
     whole_cfg, whole, cfg, first, second = cut_and_resume(tmp_path, data, precision=precision, **kw)
     K = kw.get("seeds_per_gpu", 1)
+    total = cfg.max_timesteps
+    assert total == kw.get("max_timesteps", 40)
     trainers = second[0] if K > 1 else [second[0]]
     assert trainers[0].step_kind(16) == ("general" if shape == "general_step" else "tuned")
-    assert all(t.total_it == 40 for t in trainers)
+    assert all(t.total_it == total for t in trainers)
     # the resumed part starts behind step 10: its first record is the window that ends at step 12
-    assert second[1][0][0] == 12 and [t for t, _ in second[2]] == [t for t in (20, 30, 40) for _ in range(K)]
+    evaluated = [t for t in range(cfg.eval_freq, total + 1, cfg.eval_freq) if t >= 20]  # (cut in the one at 20)
+    assert second[1][0][0] == 12 and [t for t, _ in second[2]] == [t for t in evaluated for _ in range(K)]
     assert upto(first[1], 10) + second[1] == whole[1]
     assert first[2][:K] + second[2] == whole[2]  # what the evaluations saw: the dropout call counter went on
     same_trees(cfg.checkpoints_path, whole_cfg.checkpoints_path, shape)
     same_trainers(second[0], whole[0], shape)
+    seed_dirs = [os.path.join(cfg.checkpoints_path, f"seed_{3 + k}") for k in range(K)]
+    for d in [cfg.checkpoints_path] if K == 1 else seed_dirs:
+        assert _resume.steps_in(d) == [total] and _resume.status(d) == "done"  # one generation, at the last step
     # a finished run started again trains and evaluates nothing and returns the same trainers
     third = offline_run(cfg, data, precision=precision, **({"seeds_per_gpu": K} if K > 1 else {}))
     assert third[1] == [] and third[2] == []
