@@ -4,10 +4,11 @@ checkpoint directories, the default logger and the ``seed`` tag of K > 1 records
 ``sweep.train_runs``) takes that setup from here and runs ``_window_loop``: window means instead of every step's
 losses, a metric exchange instead of a best model.
 
-``run`` knows no trainer class, buffer or sampler: a flavour hands in how a chunk of steps is queued and how
-one seed is evaluated.  Its members are the K seeds of one config (one step count and evaluation period for all)
-or the runs of a sweep's launch batch (``custom_offline.train_runs``: one of each per member, and a hook that
-rebuilds the group when a member leaves).  Nothing here touches the GPU or loads the library.
+``run`` knows no trainer class, buffer or sampler: a flavour hands in how a group is built, how a chunk of steps
+is queued and how one seed is evaluated.  Its members are the K seeds of one config (one step count and
+evaluation period for all) or the runs of a sweep's launch batch (``custom_offline.train_runs``: one of each per
+member).  ``Members`` is the group lifecycle of both loops: built over the members that start, rebuilt when one
+leaves, closed at the end.  Nothing here touches the GPU or loads the library.
 """
 import os
 import uuid
@@ -20,6 +21,7 @@ import torch
 from . import _resume
 
 Logger = Callable[[Dict[str, float], int], None]
+PerMember = Union[int, Sequence[int]]  # one value for all members of a loop, or one per member
 
 
 def checkpoint_dirs(config, seeds: Sequence[int], resume: bool = False) -> List[Optional[str]]:
@@ -44,17 +46,19 @@ def checkpoint_dirs(config, seeds: Sequence[int], resume: bool = False) -> List[
     return dirs
 
 
-def default_logger(config, K: int) -> Logger:
-    """wandb when importable (one run; with K > 1 the records of seed s go under ``seed<s>/``), else print."""
+def default_logger(config, K: int, run_id: bool = True) -> Logger:
+    """wandb when importable (one run, under a fresh uuid with ``run_id``; with K > 1 the records of seed s go
+    under ``seed<s>/``, one without a ``seed`` under its own names), else print."""
     try:
         import wandb
         wandb.init(config=asdict(config), project=config.project, group=config.group, name=config.name,
-                   id=str(uuid.uuid4()))
+                   **({"id": str(uuid.uuid4())} if run_id else {}))
     except ImportError:
         return lambda d, step: print(f"[{step}] " + " ".join(f"{n}={v:.5g}" for n, v in d.items()))
     if K == 1:
         return lambda d, step: wandb.log(d, step=step)
-    return lambda d, step: wandb.log({f"seed{int(d['seed'])}/{n}": v for n, v in d.items() if n != "seed"}, step=step)
+    return lambda d, step: wandb.log({(f"seed{int(d['seed'])}/{n}" if "seed" in d else n): v
+                                      for n, v in d.items() if n != "seed"}, step=step)
 
 
 def tag(seeds: Sequence[int]) -> Callable[[Dict[str, float], int], Dict[str, float]]:
@@ -64,19 +68,63 @@ def tag(seeds: Sequence[int]) -> Callable[[Dict[str, float], int], Dict[str, flo
     return lambda rec, k: dict(rec, seed=seeds[k])
 
 
-def run(trainers: Sequence, seeds: Sequence[int], group, total: Union[int, Sequence[int]],
-        every: Union[int, Sequence[int]], chunk: int, logger: Logger, ckpt_dirs: Sequence[Optional[str]],
-        steps: Callable[[int, int], List[torch.Tensor]], evaluate: Callable[[int, object, int], np.ndarray],
+def spread(x, K: int) -> List[int]:
+    """One int per member: ``x`` for all K of them, or its entries."""
+    return [int(x)] * K if np.ndim(x) == 0 else [int(v) for v in x]
+
+
+class Members:
+    """The members a loop still trains (``active``) and what steps them together: ``group``, from
+    ``make_group(active)`` -- None where there is nothing to synchronize or close, and for no member nothing is
+    built.  As a context manager it dissolves the group at the end: synchronized and closed on a normal exit,
+    only closed on an exception (``iqlhip_group_destroy`` waits for the device itself, and a ``synchronize``
+    that fails must not mask the first error)."""
+
+    def __init__(self, make_group: Callable[[List[int]], object], active: Sequence[int]):
+        self._make, self.active = make_group, list(active)
+        self.group = make_group(list(active)) if self.active else None
+
+    def synchronize(self) -> None:
+        if self.group is not None:
+            self.group.synchronize()
+
+    def commit_due(self, due: Sequence[int], left: Sequence[int]) -> bool:
+        """Whether this boundary ends with a resume generation: a member evaluated or left.  If so the members
+        can be read when this returns (no evaluation has synchronized them: it is done here)."""
+        gone = len(left) != len(self.active)
+        if gone and not due:
+            self.synchronize()
+        return bool(due) or gone
+
+    def keep(self, left: Sequence[int]) -> None:
+        """``left`` are the members that go on: if one has left, the group is synchronized, closed and rebuilt."""
+        if len(left) != len(self.active):
+            self.__exit__()
+            self.active = list(left)
+            self.group = self._make(list(left)) if self.active else None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type=None, exc=None, tb=None):
+        group, self.group = self.group, None
+        if group is not None:
+            if exc_type is None:
+                group.synchronize()
+            group.close()
+
+
+def run(trainers: Sequence, seeds: Sequence[int], make_group: Callable, total: PerMember, every: PerMember,
+        chunk: int, logger: Logger, ckpt_dirs: Sequence[Optional[str]], steps: Callable, evaluate: Callable,
         normalized: Union[None, Callable, Sequence[Optional[Callable]]] = None, best_by_return: bool = False, *,
-        regroup: Optional[Callable[[List[int]], object]] = None,
-        tagged: Optional[Callable[[Dict[str, float], int], Dict[str, float]]] = None,
-        resume: bool = False, sampler_state: Optional[Callable[[int], object]] = None,
-        set_sampler_state: Optional[Callable[[int, object], None]] = None) -> None:
+        tagged: Optional[Callable] = None, resume: bool = False, sampler_state: Optional[Callable] = None,
+        set_sampler_state: Optional[Callable] = None) -> None:
     """``total`` steps in chunks of at most ``chunk`` that end on the evaluation boundaries (every ``every``
     steps); the losses of a chunk come back to the host once, after the next chunk has been queued.
 
-    ``steps(t, n)`` queues steps t .. t + n - 1 and returns the loss tensors [n, 3] of the active members in
-    member order; ``group`` (a ``SeedGroup`` or None) is synchronized before an evaluation.
+    ``make_group(active)`` builds what steps the members that start together (``multi.stepper``; None: nothing to
+    synchronize or close); ``steps(group, active, t, n)`` queues steps t .. t + n - 1 and returns the loss tensors
+    [n, 3] of the active members in member order; the group is synchronized before an evaluation (``Members``).
     ``evaluate(k, trainer, step)`` gives the returns of member k.  ``normalized(returns)``: the normalized
     scores, logged x 100 (one callable, or one per member); a ``ValueError`` from it keeps what the member had
     (at first the raw mean return), and a value once obtained stays.  The best model is the one of the
@@ -86,9 +134,8 @@ def run(trainers: Sequence, seeds: Sequence[int], group, total: Union[int, Seque
 
     ``total`` / ``every`` may be one entry per member (a sweep's runs): all members start at step 0, a chunk
     ends on the next evaluation boundary or end of ANY active member, and a member whose ``total`` is reached
-    leaves after its evaluation.  ``regroup(active)`` is then called with the member indices that go on; it
-    returns the group (or None) that ``steps`` drives from there.  With scalars every member is active to the
-    end and ``regroup`` is never called.
+    leaves after its evaluation: the group is synchronized and closed, and ``make_group`` is called with the
+    member indices that go on (for none, nothing is built).  With scalars every member is active to the end.
 
     ``resume`` (every entry of ``ckpt_dirs`` must be a directory, else ValueError): at the end of every
     boundary at which a member evaluated or left -- after the evaluations, records and ``checkpoint_{step}.pt``
@@ -99,14 +146,13 @@ def run(trainers: Sequence, seeds: Sequence[int], group, total: Union[int, Seque
     it has finished.  No loss record is pending then.  And the loop starts from the newest complete
     generation (``_resume.latest``) instead of step 0: every member is restored with
     ``trainer.load_resume_state`` and ``set_sampler_state(k, state)``, files of later, incomplete
-    generations are removed, finished members are neither trained nor evaluated again, and ``regroup`` is
-    handed the members that go on.  Without any generation the run starts at step 0; members that
-    hold generations of different steps and none in common were not interrupted together: ValueError, and their
-    files stay (``_resume.restore``).  Without ``resume``
-    nothing of this happens and no such file is written."""
+    generations are removed, finished members are neither trained nor evaluated again, and ``make_group`` is
+    first called after the restore, with the members that go on.  Without any generation the run starts at step
+    0; members that hold generations of different steps and none in common were not interrupted together:
+    ValueError, and their files stay (``_resume.restore``).  Without ``resume`` nothing of this happens and no
+    such file is written."""
     K = len(trainers)
-    totals = [int(total)] * K if np.ndim(total) == 0 else [int(x) for x in total]
-    everys = [int(every)] * K if np.ndim(every) == 0 else [int(x) for x in every]
+    totals, everys = spread(total, K), spread(every, K)
     norms = list(normalized) if isinstance(normalized, (list, tuple)) else [normalized] * K
     if not len(totals) == len(everys) == len(norms) == K:
         raise ValueError("total / every / normalized: one entry per member")
@@ -147,49 +193,42 @@ def run(trainers: Sequence, seeds: Sequence[int], group, total: Union[int, Seque
                                  "norm": None if norm[k] is None else float(norm[k])}} for k in members}
         _resume.commit(ckpt_dirs, t, payloads, kept)
 
-    active = [k for k in range(K) if t < totals[k] and k not in finished]
-    if len(active) != K and active and regroup is not None:
-        group = regroup(list(active))
-    while active:
-        nxt = min(t + int(chunk), *[min(totals[k], (t // everys[k] + 1) * everys[k]) for k in active])
-        losses = steps(t, nxt - t)
-        flush()
-        pending = (t, list(active), losses)
-        t = nxt
-        due = [k for k in active if t % everys[k] == 0]
-        if due:
+    with Members(make_group, [k for k in range(K) if t < totals[k] and k not in finished]) as live:
+        while live.active:
+            active = live.active
+            nxt = min(t + int(chunk), *[min(totals[k], (t // everys[k] + 1) * everys[k]) for k in active])
+            losses = steps(live.group, list(active), t, nxt - t)
             flush()
-            if group is not None:
-                group.synchronize()
-        step = t - 1
-        for k in due:
-            trainer = trainers[k]
-            log = lambda d: logger(tagged(d, k), step)
-            eval_scores = evaluate(k, trainer, step)
-            mean_eval = eval_scores.mean()
-            log({"evaluation_return": mean_eval})
-            if norms[k] is not None:
-                try:
-                    norm[k] = np.asarray(norms[k](eval_scores)).mean() * 100
-                    log({"normalized_score": norm[k]})
-                except ValueError:
-                    pass
-            score = norm[k] if norm[k] is not None and not best_by_return else mean_eval
-            if score > best_score[k]:
-                best_score[k], best_step[k] = score, step
+            pending = (t, list(active), losses)
+            t = nxt
+            due = [k for k in active if t % everys[k] == 0]
+            if due:
+                flush()
+                live.synchronize()
+            step = t - 1
+            for k in due:
+                trainer = trainers[k]
+                log = lambda d: logger(tagged(d, k), step)
+                eval_scores = evaluate(k, trainer, step)
+                mean_eval = eval_scores.mean()
+                log({"evaluation_return": mean_eval})
+                if norms[k] is not None:
+                    try:
+                        norm[k] = np.asarray(norms[k](eval_scores)).mean() * 100
+                        log({"normalized_score": norm[k]})
+                    except ValueError:
+                        pass
+                score = norm[k] if norm[k] is not None and not best_by_return else mean_eval
+                if score > best_score[k]:
+                    best_score[k], best_step[k] = score, step
+                    if ckpt_dirs[k] is not None:
+                        torch.save(trainer.state_dict(), os.path.join(ckpt_dirs[k], "best_model.pt"))
+                log({"best_score_so_far": best_score[k]})
+                log({"best_step_so_far": best_step[k]})
                 if ckpt_dirs[k] is not None:
-                    torch.save(trainer.state_dict(), os.path.join(ckpt_dirs[k], "best_model.pt"))
-            log({"best_score_so_far": best_score[k]})
-            log({"best_step_so_far": best_step[k]})
-            if ckpt_dirs[k] is not None:
-                torch.save(trainer.state_dict(), os.path.join(ckpt_dirs[k], f"checkpoint_{step}.pt"))
-        left = [k for k in active if t < totals[k]]
-        if resume and (due or len(left) != len(active)):
-            if not due and group is not None:
-                group.synchronize()
-            commit(active)
-        if len(left) != len(active):
-            active = left
-            if active and regroup is not None:
-                group = regroup(list(active))
+                    torch.save(trainer.state_dict(), os.path.join(ckpt_dirs[k], f"checkpoint_{step}.pt"))
+            left = [k for k in active if t < totals[k]]
+            if resume and live.commit_due(due, left):
+                commit(active)
+            live.keep(left)
     flush()

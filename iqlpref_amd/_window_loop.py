@@ -12,8 +12,7 @@ import numpy as np
 import torch
 
 from . import _resume
-
-PerMember = Union[int, Sequence[int]]
+from ._offline_loop import Members, PerMember, spread
 
 
 def next_boundary(t: int, total: int, log_every: int, eval_every: int) -> int:
@@ -65,57 +64,50 @@ def run(state: State, trainers: Sequence, seeds: Sequence[int], total: PerMember
       generation t (``_resume.commit`` with ``keep_previous``), after a synchronize if no evaluation made one.
       So every run ends with a generation at its last step that says ``finished``;
     * a member at its end leaves: the group is synchronized and closed, and ``make_group`` is called with the
-      members that go on (for none, nothing is built)."""
+      members that go on (for none, nothing is built).  An exception closes the group without a synchronize
+      (``_offline_loop.Members``)."""
     K = len(trainers)
-    spread = lambda x: [int(x)] * K if np.ndim(x) == 0 else [int(v) for v in x]
-    totals, logs, evals, goal = spread(total), spread(log_every), spread(eval_every), spread(goal_env)
+    totals, logs, evals, goal = spread(total, K), spread(log_every, K), spread(eval_every, K), spread(goal_env, K)
     if not len(totals) == len(logs) == len(evals) == len(goal) == K:
         raise ValueError("total / log_every / eval_every / goal_env: one entry per member")
     windows, last = state.windows, state.last
-    active = [k for k in range(K) if state.t < totals[k]]
-    group = make_group(list(active)) if active else None
     t_window = [time.perf_counter()] * K
-    while active:
-        t0 = state.t
-        t = state.t = min(next_boundary(t0, totals[k], logs[k], evals[k]) for k in active)
-        for k, l in zip(active, steps(group, list(active), t0, t - t0)):
-            windows[k] = l if t0 % logs[k] == 0 else torch.cat([windows[k].to(l.device), l])
-        logged = [k for k in active if t % logs[k] == 0]
-        means = [windows[k].mean(dim=0).tolist() for k in logged]  # the only host syncs of the window
-        now = time.perf_counter()
-        for k, mean in zip(logged, means):
-            rec = {"value_loss": mean[0], "q_loss": mean[1], "actor_loss": mean[2]}
-            logger(tagged(dict(rec), k), trainers[k].total_it)
-            last[k] = dict(rec, steps_per_sec=windows[k].shape[0] / max(now - t_window[k], 1e-9))
-            t_window[k] = now
-        due = [k for k in active if t % evals[k] == 0]
-        if due and group is not None:
-            group.synchronize()
-        records = []
-        for k in due:
-            trainer, eval_log = trainers[k], {}
-            scores, steps_to_goal = evaluate(k, trainer, t)
-            if scores is not None:
-                eval_log["mean_score"] = float(np.mean(scores))
-                if goal[k]:
-                    eval_log["avg_steps_to_goal"] = float(np.mean(steps_to_goal)) if steps_to_goal else -1.0
-                logger(tagged(dict(eval_log), k), trainer.total_it)
-            if ckpt_dirs[k] is not None:
-                torch.save(trainer.state_dict(), os.path.join(ckpt_dirs[k], f"checkpoint_{t - 1}.pt"))
-            records.append(dict(last[k] if t >= logs[k] else {}, seed=seeds[k], total_it=trainer.total_it, **eval_log))
-        if due and exchange is not None:
-            exchange(records)
-        left = [k for k in active if t < totals[k]]
-        if resume and (due or len(left) != len(active)):
-            if not due and group is not None:
-                group.synchronize()
-            payloads = {k: {"finished": t >= totals[k], "trainer": trainers[k].resume_state(), "sampler": None,
-                            "loop": {"window": None if t % logs[k] == 0 or windows[k] is None else windows[k].cpu(),
-                                     "last": dict(last[k])}} for k in active}
-            _resume.commit(ckpt_dirs, t, payloads, state.kept, keep_previous=keep_previous)
-        if len(left) != len(active):
-            if group is not None:
-                group.synchronize()
-                group.close()
-            active = left
-            group = make_group(list(active)) if active else None
+    with Members(make_group, [k for k in range(K) if state.t < totals[k]]) as live:
+        while live.active:
+            active, t0 = live.active, state.t
+            t = state.t = min(next_boundary(t0, totals[k], logs[k], evals[k]) for k in active)
+            for k, l in zip(active, steps(live.group, list(active), t0, t - t0)):
+                windows[k] = l if t0 % logs[k] == 0 else torch.cat([windows[k].to(l.device), l])
+            logged = [k for k in active if t % logs[k] == 0]
+            means = [windows[k].mean(dim=0).tolist() for k in logged]  # the only host syncs of the window
+            now = time.perf_counter()
+            for k, mean in zip(logged, means):
+                rec = {"value_loss": mean[0], "q_loss": mean[1], "actor_loss": mean[2]}
+                logger(tagged(dict(rec), k), trainers[k].total_it)
+                last[k] = dict(rec, steps_per_sec=windows[k].shape[0] / max(now - t_window[k], 1e-9))
+                t_window[k] = now
+            due = [k for k in active if t % evals[k] == 0]
+            if due:
+                live.synchronize()
+            records = []
+            for k in due:
+                trainer, eval_log = trainers[k], {}
+                scores, steps_to_goal = evaluate(k, trainer, t)
+                if scores is not None:
+                    eval_log["mean_score"] = float(np.mean(scores))
+                    if goal[k]:
+                        eval_log["avg_steps_to_goal"] = float(np.mean(steps_to_goal)) if steps_to_goal else -1.0
+                    logger(tagged(dict(eval_log), k), trainer.total_it)
+                if ckpt_dirs[k] is not None:
+                    torch.save(trainer.state_dict(), os.path.join(ckpt_dirs[k], f"checkpoint_{t - 1}.pt"))
+                records.append(dict(last[k] if t >= logs[k] else {}, seed=seeds[k], total_it=trainer.total_it,
+                                    **eval_log))
+            if due and exchange is not None:
+                exchange(records)
+            left = [k for k in active if t < totals[k]]
+            if resume and live.commit_due(due, left):
+                payloads = {k: {"finished": t >= totals[k], "trainer": trainers[k].resume_state(), "sampler": None,
+                                "loop": {"window": None if t % logs[k] == 0 or windows[k] is None else windows[k].cpu(),
+                                         "last": dict(last[k])}} for k in active}
+                _resume.commit(ckpt_dirs, t, payloads, state.kept, keep_previous=keep_previous)
+            live.keep(left)

@@ -56,6 +56,7 @@ from .iql import DeterministicPolicy, GaussianPolicy, TwinQ, ValueFunction, comp
 from .iql import ImplicitQLearning as _OfflineIQL
 from .iql import ReplayBuffer as _OfflineReplayBuffer
 from .iql import _coerce, mlp_forward_f32
+from .multi import stepper
 from .relabel import RewardPT
 
 ACTIVATIONS = ("cos", "tanh", "relu", "softplus", "sin", "leaky_relu", "swish", "none")  # q_mlp.py:121-130
@@ -559,6 +560,14 @@ def _minari():
     return minari
 
 
+def _minari_score(minari=None):
+    """``minari.get_normalized_score`` (of the module, where a caller has imported it), or None without minari."""
+    try:
+        return (minari or _minari()).get_normalized_score
+    except ImportError:
+        return None
+
+
 def _build_trainer(config, seed: int, state_dim: int, action_dim: int, limits: Sequence, device: str,
                    policies=(GaussianPolicy, DeterministicPolicy), trainer_cls=ImplicitQLearning):
     """cref:655-689 for one seed: the nets are built right after ``torch.manual_seed(seed)`` on the
@@ -597,6 +606,18 @@ def _prepare(config, qdataset: Dict[str, np.ndarray], eval_env, state_dim: int, 
     replay_buffer = ReplayBuffer(state_dim, action_dim, config.buffer_size, device)
     replay_buffer.load_dataset(qdataset)
     return replay_buffer, eval_env
+
+
+def _steps(stream, trainers, bufs, gens, B: int):
+    """The ``steps(group, active, t, n)`` of ``_offline_loop.run``: member k steps on indices below the bound of
+    ``bufs[k]`` from ``gens[k]``, drawn in ONE ``NumpyIndexStream`` launch for all, or on the host (``stream`` None)."""
+    def steps(group, act, t, n):
+        if stream is not None:
+            idx = stream.draw([bufs[k].index_bound() for k in act], n, B, [gens[k] for k in act])
+        else:
+            idx = [torch.from_numpy(bufs[k].draw_indices(B, n, rng=gens[k])).to(trainers[k]._dev) for k in act]
+        return group.train_steps([bufs[k] for k in act], n, B, indices=idx, return_losses=True)
+    return steps
 
 
 def train(config: TrainConfig, dataset=None, reward_model=None, eval_env=None, *,
@@ -672,11 +693,7 @@ def _train(config, dataset, eval_env, relabel: Optional[Callable], best_by_retur
             raise ValueError("custom_offline.train: pass eval_env= (the dataset cannot recover_environment())")
         eval_env = dataset.recover_environment()
     if normalized_score is None:
-        try:
-            minari = minari or _minari()
-            normalized_score = minari.get_normalized_score
-        except ImportError:
-            normalized_score = None
+        normalized_score = _minari_score(minari)
     if relabel is None and model_file is None:
         _reward_model_missing("custom_offline.train", config,
                               "a QMLP or RewardPT holding its parameters (load_flax_params)", "load_QMLP / load_PT")
@@ -696,36 +713,19 @@ def _train(config, dataset, eval_env, relabel: Optional[Callable], best_by_retur
     set_seed(seeds[0])  # np, random, torch, PYTHONHASHSEED
     gens = [None] if K == 1 else [np.random.RandomState(s) for s in seeds]  # None: numpy's global generator
     trainers = [_build_trainer(config, s, state_dim, action_dim, (max_action,), device) for s in seeds]
-    group = None
-    if K > 1:
-        from .multi import SeedGroup
-        group = SeedGroup(trainers)
     stream = NumpyIndexStream(device) if sampler == "device" else None
     if logger is None:
         logger = _offline_loop.default_logger(config, K)
 
-    def steps(t, n):
-        if stream is not None:
-            idx = stream.draw(replay_buffer.index_bound(), n, config.batch_size, gens)
-        else:
-            idx = [torch.from_numpy(replay_buffer.draw_indices(config.batch_size, n, rng=g)).to(trainers[0]._dev)
-                   for g in gens]
-        if group is None:
-            return [trainers[0].train_steps(replay_buffer, n, config.batch_size, indices=idx[0])]
-        return group.train_steps(replay_buffer, n, config.batch_size, indices=idx, return_losses=True)
-
     _offline_loop.run(
-        trainers, seeds, group, int(config.update_steps), int(config.eval_every), chunk, logger, ckpt_dirs, steps,
+        trainers, seeds, lambda active: stepper(trainers), int(config.update_steps), int(config.eval_every), chunk,
+        logger, ckpt_dirs, _steps(stream, trainers, [replay_buffer] * K, gens, config.batch_size),
         evaluate=lambda k, trainer, step: evaluate(eval_env, trainer.actor, config.eval_episodes, config.eval_seed,
                                                    device),
         normalized=None if normalized_score is None else (lambda scores: normalized_score(dataset, scores)),
         best_by_return=best_by_return, resume=resume, sampler_state=lambda k: generator_state(gens[k]),
         set_sampler_state=lambda k, st: set_generator_state(gens[k], st))
-    if group is not None:
-        group.synchronize()
-        group.close()
-        return trainers
-    return trainers[0]
+    return trainers if K > 1 else trainers[0]
 
 
 # --------------------------------------------------------------------------- #
@@ -797,6 +797,16 @@ def _model_sources(configs: Sequence[TrainConfig], reward_models) -> Dict[tuple,
     return sources
 
 
+def _per_id(given, ids: Sequence[str], what: str) -> Dict[str, Any]:
+    """``given`` -- one object for every dataset id, or a mapping id -> object -- as a dict over ``ids``."""
+    if not isinstance(given, Mapping):
+        return {d: given for d in ids}
+    lacking = [d for d in ids if d not in given]
+    if lacking:
+        raise ValueError(f"no {what} given for {', '.join(lacking)}")
+    return {d: given[d] for d in ids}
+
+
 def train_runs(configs: Sequence[TrainConfig], dataset=None, reward_models=None, eval_env=None, *,
                runs_per_gpu: int = 8, logger: Optional[Callable[[Dict[str, float], int], None]] = None,
                normalized_score: Optional[Callable] = None, sampler: str = "device", chunk: int = 2000,
@@ -845,25 +855,16 @@ def train_runs(configs: Sequence[TrainConfig], dataset=None, reward_models=None,
     ended, every run active in it, due or not, writes ``resume_{t}.pt`` at the common step (trainer
     ``resume_state()``, the state of its own generator, best score / step, kept normalized score, whether it
     has ended); a batch starts from its newest complete generation with the ended runs left out (their
-    trainers loaded from their final state) and the others regrouped.  Each rank resumes its own runs.
+    trainers loaded from their final state) and the group built over the others.  Each rank resumes its own runs.
 
     Under torchrun rank r trains the configs with index = r (mod world size), with no collectives.
     Returns this rank's trainers in config order."""
     from . import sweep as SW
     configs = list(configs)
-    SW.check_runs(configs, runs_per_gpu)
-    if resume:
-        for cfg in configs:
-            _resume.check_config(cfg)
+    run_ids, mine = SW.start_runs(configs, runs_per_gpu, run_ids, resume)
     if sampler not in ("host", "device"):
         raise ValueError("sampler must be 'host' or 'device'")
-    n = len(configs)
-    run_ids = list(range(n)) if run_ids is None else [int(r) for r in run_ids]
-    if len(run_ids) != n:
-        raise ValueError("run_ids: one entry per config")
     sources = _model_sources(configs, reward_models)
-    rank, world = SW._rank_world()
-    mine = SW.rank_share(n, rank, world)
     if not mine:
         return []
     device = D.local_device() or "cuda:0"
@@ -874,20 +875,10 @@ def train_runs(configs: Sequence[TrainConfig], dataset=None, reward_models=None,
     if dataset is None:
         minari = _minari()
         datasets = {d: minari.load_dataset(d) for d in ids}
-    elif isinstance(dataset, Mapping):
-        lacking = [d for d in ids if d not in dataset]
-        if lacking:
-            raise ValueError(f"no dataset given for {', '.join(lacking)}")
-        datasets = {d: dataset[d] for d in ids}
     else:
-        datasets = {d: dataset for d in ids}
-    if isinstance(eval_env, Mapping):
-        lacking = [d for d in ids if d not in eval_env]
-        if lacking:
-            raise ValueError(f"no eval_env given for {', '.join(lacking)}")
-        envs = {d: eval_env[d] for d in ids}
-    elif eval_env is not None:
-        envs = {d: eval_env for d in ids}
+        datasets = _per_id(dataset, ids, "dataset")
+    if eval_env is not None:
+        envs = _per_id(eval_env, ids, "eval_env")
     else:
         envs = {}
         for d in ids:
@@ -896,11 +887,7 @@ def train_runs(configs: Sequence[TrainConfig], dataset=None, reward_models=None,
                                  "recover_environment())")
             envs[d] = datasets[d].recover_environment()
     if normalized_score is None:
-        try:
-            minari = minari or _minari()
-            normalized_score = minari.get_normalized_score
-        except ImportError:
-            normalized_score = None
+        normalized_score = _minari_score(minari)
     dims = {d: (envs[d].observation_space.shape[0], envs[d].action_space.shape[0]) for d in ids}
     local = plan_batches([configs[i] for i in mine], [dims[configs[i].dataset_id] for i in mine], runs_per_gpu, device)
     batches = [[mine[j] for j in b] for b in local]
@@ -908,96 +895,48 @@ def train_runs(configs: Sequence[TrainConfig], dataset=None, reward_models=None,
         logger = SW._default_logger(configs, mine, run_ids)
 
     # ---- relabelled datasets and device buffers: built when a batch first needs them, dropped after their last ----
-    rkeys = {i: _relabel_key(configs[i]) for i in mine}
-    bkeys = {i: _buffer_key(configs[i]) for i in mine}
-    last_use_r, last_use_b = {}, {}
-    for bi, b in enumerate(batches):
-        for i in b:
-            last_use_r[rkeys[i]], last_use_b[bkeys[i]] = bi, bi
-    relabelled: Dict[tuple, Dict[str, np.ndarray]] = {}
-    buffers: Dict[tuple, Tuple[ReplayBuffer, Any]] = {}
+    relabelled = SW.BatchCache(batches, lambda i: _relabel_key(configs[i]))
+    buffers = SW.BatchCache(batches, lambda i: _buffer_key(configs[i]))
 
-    def buffer_for(i):
+    def relabel(i):
+        cfg, src = configs[i], sources[relabelled.key_of[i]]
+        if isinstance(src, tuple) and src[0] == "call":
+            src = reward_models(cfg)
+        elif isinstance(src, tuple) and src[0] == "file":
+            src = load_reward_model(src[1], *dims[cfg.dataset_id], device)
+        return qlearning_dataset(datasets[cfg.dataset_id], src, cfg.query_length)
+
+    def prepare(i):
         cfg = configs[i]
-        if bkeys[i] not in buffers:
-            S, A = dims[cfg.dataset_id]
-            if rkeys[i] not in relabelled:
-                src = sources[rkeys[i]]
-                if isinstance(src, tuple) and src[0] == "call":
-                    model = reward_models(cfg)
-                elif isinstance(src, tuple) and src[0] == "file":
-                    model = load_reward_model(src[1], S, A, device)
-                else:
-                    model = src
-                relabelled[rkeys[i]] = qlearning_dataset(datasets[cfg.dataset_id], model, cfg.query_length)
-            # (_prepare rewrites its dict, and the rewards in place: every preparation gets its own)
-            qd = dict(relabelled[rkeys[i]])
-            qd["rewards"] = qd["rewards"].copy()
-            buffers[bkeys[i]] = _prepare(cfg, qd, envs[cfg.dataset_id], S, A, device)
-        return buffers[bkeys[i]]
+        # (_prepare rewrites its dict, and the rewards in place: every preparation gets its own)
+        qd = dict(relabelled.get(i, lambda: relabel(i)))
+        qd["rewards"] = qd["rewards"].copy()
+        return _prepare(cfg, qd, envs[cfg.dataset_id], *dims[cfg.dataset_id], device)
 
     stream = NumpyIndexStream(device) if sampler == "device" else None
     trainers: Dict[int, ImplicitQLearning] = {}
     for bi, batch in enumerate(batches):
-        prepared = [buffer_for(i) for i in batch]
-        ckpt_dirs = [_offline_loop.checkpoint_dirs(configs[i], [configs[i].train_seed], resume=resume)[0] for i in batch]
-        for i in batch:
-            cfg, e = configs[i], envs[configs[i].dataset_id]
-            S, A = dims[cfg.dataset_id]
-            trainers[i] = _build_trainer(cfg, cfg.train_seed, S, A, (float(e.action_space.high[0]),), device)
-        _run_batch([configs[i] for i in batch], [trainers[i] for i in batch], [p[0] for p in prepared],
-                   [p[1] for p in prepared], [run_ids[i] for i in batch], ckpt_dirs, stream, logger, chunk, device,
-                   [None if normalized_score is None else
-                    (lambda scores, ds=datasets[configs[i].dataset_id]: normalized_score(ds, scores)) for i in batch],
-                   resume)
-        del prepared
-        for key in [k for k in relabelled if last_use_r[k] <= bi]:
-            del relabelled[key]
-        for key in [k for k in buffers if last_use_b[k] <= bi]:
-            del buffers[key]
-    return [trainers[i] for i in mine]
-
-
-def _run_batch(configs, trainers, bufs, envs, ids, ckpt_dirs, stream, logger, chunk, device, normalized,
-               resume=False):
-    """One launch batch through ``_offline_loop.run``: member k has its own buffer, bound, generator, step
-    count and evaluation period; the group is rebuilt when a member leaves, and one member alone steps its
-    trainer directly."""
-    from .multi import SeedGroup
-    B = int(configs[0].batch_size)
-    gens = [np.random.RandomState(cfg.train_seed) for cfg in configs]
-    now = {"active": list(range(len(trainers))), "group": None}
-
-    def regroup(active):
-        if now["group"] is not None:
-            now["group"].synchronize()
-            now["group"].close()
-        now["active"] = list(active)
-        now["group"] = SeedGroup([trainers[k] for k in active]) if len(active) > 1 else None
-        return now["group"]
-
-    def steps(t, n):
-        act = now["active"]
-        if stream is not None:
-            idx = stream.draw([bufs[k].index_bound() for k in act], n, B, [gens[k] for k in act])
-        else:
-            idx = [torch.from_numpy(bufs[k].draw_indices(B, n, rng=gens[k])).to(trainers[k]._dev) for k in act]
-        if now["group"] is None:
-            return [trainers[act[0]].train_steps(bufs[act[0]], n, B, indices=idx[0])]
-        return now["group"].train_steps([bufs[k] for k in act], n, B, indices=idx, return_losses=True)
-
-    try:
+        cfgs = [configs[i] for i in batch]
+        bufs, batch_envs = zip(*[buffers.get(i, lambda: prepare(i)) for i in batch])
+        ckpt_dirs = [_offline_loop.checkpoint_dirs(cfg, [cfg.train_seed], resume=resume)[0] for cfg in cfgs]
+        for i, cfg in zip(batch, cfgs):
+            high = float(envs[cfg.dataset_id].action_space.high[0])
+            trainers[i] = _build_trainer(cfg, cfg.train_seed, *dims[cfg.dataset_id], (high,), device)
+        trs = [trainers[i] for i in batch]
+        gens = [np.random.RandomState(cfg.train_seed) for cfg in cfgs]
+        # member k has its own buffer, bound, generator, step count and evaluation period (one alone: a ``Solo``)
         _offline_loop.run(
-            trainers, [cfg.train_seed for cfg in configs], regroup(now["active"]),
-            [int(cfg.update_steps) for cfg in configs], [int(cfg.eval_every) for cfg in configs], chunk, logger,
-            ckpt_dirs, steps,
-            evaluate=lambda k, trainer, step: evaluate(envs[k], trainer.actor, configs[k].eval_episodes,
-                                                       configs[k].eval_seed, device),
-            normalized=normalized, regroup=regroup, tagged=lambda rec, k: dict(rec, run=ids[k]), resume=resume,
+            trs, [cfg.train_seed for cfg in cfgs], lambda act: stepper([trs[k] for k in act]),
+            [int(cfg.update_steps) for cfg in cfgs], [int(cfg.eval_every) for cfg in cfgs], chunk, logger, ckpt_dirs,
+            _steps(stream, trs, bufs, gens, int(cfgs[0].batch_size)),
+            evaluate=lambda k, trainer, step: evaluate(batch_envs[k], trainer.actor, cfgs[k].eval_episodes,
+                                                       cfgs[k].eval_seed, device),
+            normalized=[None if normalized_score is None else
+                        (lambda scores, ds=datasets[cfg.dataset_id]: normalized_score(ds, scores)) for cfg in cfgs],
+            tagged=lambda rec, k: dict(rec, run=run_ids[batch[k]]), resume=resume,
             sampler_state=lambda k: generator_state(gens[k]),
             set_sampler_state=lambda k, st: set_generator_state(gens[k], st))
-    finally:
-        if now["group"] is not None:
-            now["group"].synchronize()
-            now["group"].close()
-    torch.cuda.current_stream(trainers[0]._dev).synchronize()
+        del bufs, batch_envs
+        relabelled.batch_done(bi)
+        buffers.batch_done(bi)
+    return [trainers[i] for i in mine]

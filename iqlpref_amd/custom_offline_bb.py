@@ -60,6 +60,7 @@ from .custom_offline import ReplayBuffer
 from .iql import DeterministicPolicy as _DeterministicPolicy
 from .iql import GaussianPolicy as _GaussianPolicy
 from .iql import set_seed
+from .multi import stepper
 from .relabel import RewardPT
 
 DATASET_KEYS = ("states", "actions", "rewards", "n_rewards", "next_states", "attn_mask")
@@ -287,10 +288,13 @@ class BlockEpochSamplerGroup:
     def device_indices(self, t0: int, n_steps: int, device) -> Tuple[List[torch.Tensor], torch.Tensor]:
         """(K int64 [n_steps, batch_size] tensors, one int32 [n_steps] count tensor): what
         ``BlockEpochSampler.device_indices`` gives for every member, from ONE launch of
-        ``iqlhip_block_epoch_indices_group`` on the current stream."""
+        ``iqlhip_block_epoch_indices_group`` on the current stream (one member: from its own launch)."""
         lib = _lib.load()
         dev = _lib.require_gpu(device)
         K = len(self.samplers)
+        if K == 1:  # (the one-sampler launch)
+            idx, valid = self.samplers[0].device_indices(t0, n_steps, device)
+            return [idx], valid
         if self._dev_perms is None or self._dev_perms.device != dev:
             self._dev_perms = torch.stack([sm.perm for sm in self.samplers]).to(dev)  # [K, n_blocks]
         area = torch.empty((K, n_steps, self.batch_size), dtype=torch.int64, device=dev)
@@ -927,11 +931,9 @@ def train(config: TrainConfig, dataset=None, reward_model=None, move_stats=None,
     if not isinstance(dataset, BBDataset):
         dataset = BBDataset(dataset, normalized_states=config.normalize_state,
                             normalized_rewards=config.normalize_reward, device=device)
-    # bref:899-902: the loader is built, and its permutation drawn, before set_seed
-    if K == 1:
-        sampler = BlockEpochSampler(len(dataset), config.batch_size, perm=perm)
-    else:
-        samplers = BlockEpochSamplerGroup.draw(len(dataset), config.batch_size, K, perm)
+    # bref:899-902: the loader is built, and its permutation drawn, before set_seed (one seed takes one ``perm``)
+    samplers = BlockEpochSamplerGroup.draw(len(dataset), config.batch_size, K,
+                                           [perm] if K == 1 and perm is not None else perm)
     state_shape, action_shape = dataset.shapes()
     state_dim, action_dim = state_shape[1], action_shape[1]
     limits = (dataset.max_actions().to(device), dataset.min_actions().to(device))
@@ -944,20 +946,14 @@ def train(config: TrainConfig, dataset=None, reward_model=None, move_stats=None,
                                    (GaussianPolicy, DeterministicPolicy), ImplicitQLearning) for s in seeds]
     if eval_on == "fused":
         _fused_actor_descs([t.actor for t in trainers])  # (the envelope, before the first step)
-    group = None
-    if K > 1:
-        from .multi import SeedGroup
-        group = SeedGroup(trainers)
     replay_buffer = ReplayBuffer(state_dim, action_dim, len(dataset), device)
     replay_buffer.load_dataset(dataset.transitions())
-    if K > 1 and samplers.n_rows != replay_buffer.index_bound():
+    if samplers.n_rows != replay_buffer.index_bound():
         raise ValueError(f"the samplers walk {samplers.n_rows} rows, the buffer holds {replay_buffer.index_bound()}")
     if logger is None:
         logger = _offline_loop.default_logger(config, K)
 
-    def steps(t, n):
-        if group is None:
-            return [trainers[0].train_epoch_steps(replay_buffer, sampler, t, n)]
+    def steps(group, active, t, n):  # (always all K seeds: they end together)
         idx, valid = samplers.device_indices(t, n, device)
         return group.train_steps(replay_buffer, n, config.batch_size, indices=idx, n_valid=valid, return_losses=True)
 
@@ -977,10 +973,6 @@ def train(config: TrainConfig, dataset=None, reward_model=None, move_stats=None,
         run_eval = {"device": bb_run_eval_device, "fused": bb_run_eval_fused}.get(eval_on, bb_run_eval_IQL)
         return run_eval(actor=trainer.actor, seed=config.eval_seed + step, **kw)
 
-    _offline_loop.run(trainers, seeds, group, int(config.update_steps), int(config.eval_every), chunk, logger,
-                      ckpt_dirs, steps, evaluate)
-    if group is not None:
-        group.synchronize()
-        group.close()
-        return trainers
-    return trainers[0]
+    _offline_loop.run(trainers, seeds, lambda active: stepper(trainers), int(config.update_steps),
+                      int(config.eval_every), chunk, logger, ckpt_dirs, steps, evaluate)
+    return trainers if K > 1 else trainers[0]

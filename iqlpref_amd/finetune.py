@@ -42,6 +42,7 @@ from .iql import DeterministicPolicy, GaussianPolicy, TwinQ, ValueFunction, comp
 from .iql import ImplicitQLearning as _OfflineIQL
 from .iql import ReplayBuffer as _OfflineReplayBuffer
 from .iql import _buffer_generation
+from .multi import stepper
 from .train import wrap_env  # noqa: F401  (fref:86-105)
 
 ENVS_WITH_GOAL = ("antmaze", "pen", "door", "hammer", "relocate")  # fref:28
@@ -597,19 +598,18 @@ def train(config: TrainConfig, env=None, eval_env=None, dataset: Optional[Dict[s
     # cost more per member), K > 1 send each part out once for all members ----
     act_kw = dict(expl_noise=config.expl_noise, noise_clip=config.noise_clip, batch_size=B)
     if K == 1:
-        gens, group = None, None  # (numpy's global generator, as set_seed left it)
+        gens, mode = None, None  # (numpy's global generator, as set_seed left it)
         act = lambda states, eps: trainers[0].explore_action(states, eps, **act_kw).cpu().numpy()
         append = lambda s, a, r, s2, d: buffers[0].add_transition(s[0], a[0], r[0], s2[0], d[0])
-        step = lambda n, indices: [trainers[0].train_steps(buffers[0], n, B, indices=indices[0])]
     else:
         # what np.random.seed(seed_k) leaves numpy's global generator in, one generator per member
         gens = [np.random.RandomState(seed) for seed in seeds]
-        from .multi import SeedGroup
         # ONE launch sequence per step for all members (the two-stream split pays per call, and a tick is one step)
-        group = SeedGroup(trainers, mode="general" if trainers[0].step_kind(B) == "general" else "group")
+        mode = "general" if trainers[0].step_kind(B) == "general" else "group"
         act = lambda states, eps: explore_actions(trainers, states, eps, **act_kw).cpu().numpy()
         append = lambda *transitions: add_transitions(buffers, *transitions)
-        step = lambda n, indices: group.train_steps(buffers, n, B, indices=indices, return_losses=True)
+    group = stepper(trainers, mode=mode)
+    step = lambda n, indices: group.train_steps(buffers, n, B, indices=indices, return_losses=True)
 
     train_successes = [[] for _ in ks]
     pending = []  # (first t, [K] device losses [n, 3], [K] lists of the online records of those steps, or None)
@@ -629,8 +629,7 @@ def train(config: TrainConfig, env=None, eval_env=None, dataset: Optional[Dict[s
     def evaluate(t):
         """fref:736-767 after step t, member after member."""
         flush()
-        if group is not None:
-            group.synchronize()
+        group.synchronize()
         print(f"Time steps: {t + 1}")
         for k, seed in enumerate(seeds):
             eval_scores, success_rate = eval_actor(eval_envs[k], trainers[k].actor, device=device,
@@ -714,7 +713,6 @@ def train(config: TrainConfig, env=None, eval_env=None, dataset: Optional[Dict[s
         if (t + 1) % every == 0:
             evaluate(t)
     flush()
-    if group is not None:
-        group.synchronize()
-        group.close()
+    group.synchronize()
+    group.close()
     return trainers[0] if K == 1 else trainers

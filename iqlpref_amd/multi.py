@@ -90,6 +90,21 @@ def resolve_group_mode(group_mode: Optional[str], trainers: Sequence[ImplicitQLe
     return group_mode
 
 
+def _per_member(K: int, replay, indices, dropout_keep, n_valid):
+    """The arguments of ``train_steps`` as one entry per trainer each: (buffers, indices, dropout_keep, n_valid)."""
+    bufs = list(replay) if isinstance(replay, (list, tuple)) else [replay] * K
+    if len(bufs) != K:
+        raise ValueError("one replay buffer per trainer (or a single shared one)")
+    idx = list(indices) if indices is not None else [None] * K
+    keep = list(dropout_keep) if dropout_keep is not None else [None] * K
+    if len(idx) != K or len(keep) != K:
+        raise ValueError("indices / dropout_keep: one entry per trainer")
+    valid = [n_valid] * K if n_valid is None or isinstance(n_valid, torch.Tensor) else list(n_valid)
+    if len(valid) != K:
+        raise ValueError("n_valid: one tensor for all trainers or one entry per trainer")
+    return bufs, idx, keep, valid
+
+
 class SeedGroup:
     def __init__(self, trainers: Sequence[ImplicitQLearning], chunk: int = 2000, mode: Optional[str] = None,
                  n_streams: int = 2):
@@ -211,14 +226,8 @@ class SeedGroup:
         ``return_losses``.  Asynchronous: call ``synchronize()`` (or read the losses) before
         touching the parameters."""
         K = len(self.trainers)
-        bufs = list(replay) if isinstance(replay, (list, tuple)) else [replay] * K
-        if len(bufs) != K:
-            raise ValueError("one replay buffer per trainer (or a single shared one)")
-        idx = list(indices) if indices is not None else [None] * K
-        keep = list(dropout_keep) if dropout_keep is not None else [None] * K
-        if len(idx) != K or len(keep) != K:
-            raise ValueError("indices / dropout_keep: one entry per trainer")
-        valid = self._check_valid(n_valid, n_steps, batch_size)
+        bufs, idx, keep, valid = _per_member(K, replay, indices, dropout_keep, n_valid)
+        valid = self._check_valid(valid, n_steps, batch_size)
         if self.mode == "streams":
             return self._train_streams(bufs, n_steps, batch_size, idx, keep, return_losses, graph_unroll, valid)
         if self.mode == "split":
@@ -249,15 +258,9 @@ class SeedGroup:
             t._after_steps(n_steps)
         return losses
 
-    def _check_valid(self, n_valid, n_steps: int, batch_size: int) -> List[Optional[torch.Tensor]]:
-        """``n_valid`` as one entry per trainer.  Checked as ``ImplicitQLearning.train_steps`` checks it; the
+    def _check_valid(self, valid, n_steps: int, batch_size: int) -> List[Optional[torch.Tensor]]:
+        """``n_valid``, one entry per trainer, checked as ``ImplicitQLearning.train_steps`` checks it; the
         groups the counted step is not built for are refused here, before any member is stepped."""
-        K = len(self.trainers)
-        if n_valid is None:
-            return [None] * K
-        valid = [n_valid] * K if isinstance(n_valid, torch.Tensor) else list(n_valid)
-        if len(valid) != K:
-            raise ValueError("n_valid: one tensor for all trainers or one entry per trainer")
         for i, t in enumerate(valid):
             if t is None:
                 continue
@@ -295,9 +298,7 @@ class SeedGroup:
             done += c
         for st in self._streams:
             cur.wait_stream(st)
-        if return_losses:
-            return [torch.cat(o) for o in out]
-        return None
+        return [torch.cat(o) for o in out] if return_losses else None
 
     def _ensure_slice_streams(self):
         if self._streams:
@@ -329,9 +330,7 @@ class SeedGroup:
             done += c
         for st in self._streams:
             cur.wait_stream(st)
-        if return_losses:
-            return [torch.cat(o) for o in out]
-        return None
+        return [torch.cat(o) for o in out] if return_losses else None
 
     def kernel_times(self, replay, batch_size: int, n_steps: int = 200):
         """Average duration (us) of the forward / backward / update launches of this group
@@ -364,3 +363,36 @@ class SeedGroup:
         for st in self._streams:
             st.synchronize()
         torch.cuda.current_stream(self._dev).synchronize()
+
+
+class Solo:
+    """ONE trainer behind the part of ``SeedGroup``'s surface the training loops use, so that a loop drives one
+    seed and K seeds with the same calls.  Nothing is added on the device: no group is created, the trainer
+    is never owned, there is no stream of its own, and ``train_steps`` is one ``trainer.train_steps`` call with
+    ``SeedGroup.train_steps``' argument conventions and ValueErrors (every per-member list holds one entry;
+    ``graph_unroll`` None leaves the unroll to the trainer) that returns ``[losses]`` or None."""
+    mode = "solo"
+
+    def __init__(self, trainer: ImplicitQLearning):
+        self.trainers: List[ImplicitQLearning] = [trainer]
+
+    def __len__(self):
+        return 1
+
+    def train_steps(self, replay, n_steps: int, batch_size: int, *, indices=None, dropout_keep=None,
+                    return_losses: bool = False, graph_unroll: Optional[int] = None, n_valid=None):
+        (buf,), (idx,), (keep,), (valid,) = _per_member(1, replay, indices, dropout_keep, n_valid)
+        losses = self.trainers[0].train_steps(buf, n_steps, batch_size, indices=idx, dropout_keep=keep,
+                                              return_losses=return_losses, graph_unroll=graph_unroll, n_valid=valid)
+        return [losses] if return_losses else None
+
+    def synchronize(self):
+        torch.cuda.current_stream(self.trainers[0]._dev).synchronize()
+
+    def close(self):
+        pass
+
+
+def stepper(trainers: Sequence[ImplicitQLearning], mode: Optional[str] = None, **kw) -> Union[Solo, SeedGroup]:
+    """What steps these trainers together: ``Solo`` for one, ``SeedGroup(trainers, mode=mode, **kw)`` for more."""
+    return Solo(trainers[0]) if len(trainers) == 1 else SeedGroup(trainers, mode=mode, **kw)

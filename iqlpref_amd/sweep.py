@@ -220,6 +220,43 @@ def _rank_world() -> Tuple[int, int]:
     return int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
 
 
+def start_runs(configs: Sequence, runs_per_gpu: int, run_ids: Optional[Sequence[int]],
+               resume: bool) -> Tuple[List[int], List[int]]:
+    """What both ``train_runs`` do first, ahead of any device work: ``check_runs``, under ``resume`` every config's
+    ``_resume.check_config``, the runs' names (default 0 .. n-1).  -> (run_ids, this rank's config indices)."""
+    check_runs(configs, runs_per_gpu)
+    if resume:
+        for cfg in configs:
+            _resume.check_config(cfg)
+    n = len(configs)
+    run_ids = list(range(n)) if run_ids is None else [int(r) for r in run_ids]
+    if len(run_ids) != n:
+        raise ValueError("run_ids: one entry per config")
+    return run_ids, rank_share(n, *_rank_world())
+
+
+class BatchCache:
+    """key -> value, built on first need and dropped after the last launch batch whose runs use the key.
+    ``batches``: lists of run indices in the order they run; ``key(i)``: the key of run i (kept as ``key_of[i]``)."""
+
+    def __init__(self, batches: Sequence[Sequence[int]], key: Callable[[int], Any]):
+        self.key_of, self._values = {i: key(i) for b in batches for i in b}, {}
+        self._last_use = {self.key_of[i]: bi for bi, b in enumerate(batches) for i in b}
+
+    def __contains__(self, key) -> bool:
+        return key in self._values
+
+    def get(self, i: int, build: Callable[[], Any]):
+        """The value of run i's key; ``build()`` makes it if no earlier run has."""
+        if self.key_of[i] not in self._values:
+            self._values[self.key_of[i]] = build()
+        return self._values[self.key_of[i]]
+
+    def batch_done(self, bi: int) -> None:
+        for key in [k for k in self._values if self._last_use[k] <= bi]:
+            del self._values[key]
+
+
 def _relabel_key(config: TrainConfig) -> tuple:
     return (config.env, str(config.device)) + tuple(getattr(config, f) for f in RELABEL_FIELDS)
 
@@ -316,19 +353,10 @@ def train_runs(configs: Sequence[TrainConfig], env=None, dataset=None, *, runs_p
     T = importlib.import_module(".train", __package__)
 
     configs = list(configs)
-    check_runs(configs, runs_per_gpu)
-    if resume:
-        for cfg in configs:
-            _resume.check_config(cfg)
-    n = len(configs)
-    run_ids = list(range(n)) if run_ids is None else [int(r) for r in run_ids]
-    if len(run_ids) != n:
-        raise ValueError("run_ids: one entry per config")
-    if isinstance(evaluate, (list, tuple)) and len(evaluate) != n:
-        raise ValueError(f"evaluate: {len(evaluate)} callables for {n} configs")
+    run_ids, mine = start_runs(configs, runs_per_gpu, run_ids, resume)
+    if isinstance(evaluate, (list, tuple)) and len(evaluate) != len(configs):
+        raise ValueError(f"evaluate: {len(evaluate)} callables for {len(configs)} configs")
     check_group_mode(group_mode)
-    rank, world = _rank_world()
-    mine = rank_share(n, rank, world)
     if not mine:
         return []
     envs = _resolve_envs(configs, mine, env)
@@ -346,36 +374,26 @@ def train_runs(configs: Sequence[TrainConfig], env=None, dataset=None, *, runs_p
 
     # datasets and device buffers, built when a batch first needs them and dropped after their last batch
     rcfgs = {i: T.seed_configs(configs[i], [configs[i].seed])[0] for i in mine}
-    rkeys = {i: _relabel_key(rcfgs[i]) for i in mine}
-    bkeys = {i: (rkeys[i], configs[i].normalize_reward, bool(configs[i].normalize), configs[i].buffer_size)
-             for i in mine}
-    last_use_r, last_use_b = {}, {}
-    for bi, b in enumerate(batches):
-        for i in b:
-            last_use_r[rkeys[i]], last_use_b[bkeys[i]] = bi, bi
-    datasets: Dict[tuple, Any] = {}
-    buffers: Dict[tuple, Tuple[Any, Any, Any]] = {}
+    datasets = BatchCache(batches, lambda i: _relabel_key(rcfgs[i]))
+    buffers = BatchCache(batches, lambda i: (datasets.key_of[i], configs[i].normalize_reward,
+                                             bool(configs[i].normalize), configs[i].buffer_size))
 
-    def buffer_for(i):
-        cfg = configs[i]
-        if bkeys[i] not in buffers:
-            if rkeys[i] not in datasets:
-                rc, e = rcfgs[i], envs[cfg.env]
-                src = pick(source, cfg)
-                datasets[rkeys[i]] = T.build_dataset(rc, e, src) if (rc.reward_model_path or dataset is None) else src
-            ds = datasets[rkeys[i]]
-            if host_prep:  # the numpy path rewrites its dataset in place: every preparation gets a copy
-                ds = {k: np.array(v) for k, v in ds.items()}
-            S, A = dims[cfg.env]
-            buffers[bkeys[i]] = T._prepare_replay(cfg, ds, S, A, host_prep)
-        return buffers[bkeys[i]]
+    def relabel(i):
+        rc, src = rcfgs[i], pick(source, configs[i])
+        return T.build_dataset(rc, envs[rc.env], src) if (rc.reward_model_path or dataset is None) else src
+
+    def prepare(i):
+        ds = datasets.get(i, lambda: relabel(i))
+        if host_prep:  # the numpy path rewrites its dataset in place: every preparation gets a copy
+            ds = {k: np.array(v) for k, v in ds.items()}
+        return T._prepare_replay(configs[i], ds, *dims[configs[i].env], host_prep)
 
     trainers: Dict[int, ImplicitQLearning] = {}
     for bi, batch in enumerate(batches):
         bufs, evals = {}, {}
         for i in batch:
             cfg = configs[i]
-            bufs[i], mean, std = buffer_for(i)
+            bufs[i], mean, std = buffers.get(i, lambda: prepare(i))
             e = envs[cfg.env]
             max_action = float(e.action_space.high[0])
             checkpoint_dirs(cfg, [cfg.seed], resume=resume)  # (one seed: the path itself, with its config.yaml)
@@ -389,8 +407,7 @@ def train_runs(configs: Sequence[TrainConfig], env=None, dataset=None, *, runs_p
 
         def make_group(active):
             group_trs = [trs[j] for j in active]
-            mode = resolve_group_mode(group_mode, group_trs, cfgs[active[0]].batch_size)
-            return SeedGroup(group_trs) if mode is None else SeedGroup(group_trs, mode=mode)
+            return SeedGroup(group_trs, mode=resolve_group_mode(group_mode, group_trs, cfgs[active[0]].batch_size))
 
         def steps(group, active, t, n):
             return group.train_steps([bufs[members[j]] for j in active], n, cfgs[active[0]].batch_size,
@@ -404,10 +421,8 @@ def train_runs(configs: Sequence[TrainConfig], env=None, dataset=None, *, runs_p
                                vector_env, [evals[i] for i in members]),
             lambda rec, j: dict(rec, run=run_ids[members[j]], seed=cfgs[j].seed),
             goal_env=["antmaze" in c.env.lower() for c in cfgs], resume=resume)
-        for key in [k for k in datasets if last_use_r[k] <= bi]:
-            del datasets[key]
-        for key in [k for k in buffers if last_use_b[k] <= bi]:
-            del buffers[key]
+        datasets.batch_done(bi)
+        buffers.batch_done(bi)
     return [trainers[i] for i in mine]
 
 

@@ -8,7 +8,6 @@ step, ref:589,607,633).  gym / d4rl / wandb are optional: pass ``env`` and
 when it is importable.
 """
 import os
-from dataclasses import asdict
 from pathlib import Path
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
@@ -18,7 +17,7 @@ import torch
 from . import _resume, _window_loop
 from . import distributed as D
 from . import prep
-from ._offline_loop import checkpoint_dirs, tag
+from ._offline_loop import checkpoint_dirs, default_logger, tag
 from .iql import (DeterministicPolicy, EnsembleQ, GaussianPolicy, ImplicitQLearning, ReplayBuffer, TrainConfig, TwinQ,
                   ValueFunction, compute_mean_std, normalize_states, set_seed)
 from .relabel import (load_mlp_reward_model, load_pt_reward_model, modify_reward, qlearning_dataset_bnn,
@@ -290,7 +289,7 @@ def train(config: TrainConfig, env=None, dataset=None, *, state_dim: Optional[in
     bit for bit (``steps_per_sec`` aside).  A finished run is neither trained nor evaluated again.  Under
     torchrun every rank resumes its own seeds, all from the newest generation that every rank has.
     ``index_stream`` must be a function of its arguments alone."""
-    from .multi import check_group_mode, resolve_group_mode
+    from .multi import check_group_mode, resolve_group_mode, stepper
     check_group_mode(group_mode)
     # one process per GPU: under torchrun this rank owns cuda:<LOCAL_RANK>, and everything
     # below (process group, buffer, trainer, metric all-gather) lives there
@@ -350,26 +349,14 @@ def train(config: TrainConfig, env=None, dataset=None, *, state_dim: Optional[in
             raise ValueError("resume=True: the ranks have no resume generation in common")
 
     def make_group(active):  # (always all K seeds: they end together)
-        from .multi import SeedGroup
-        return None if K == 1 else SeedGroup(trainers, mode=resolve_group_mode(group_mode, trainers, config.batch_size))
+        return stepper(trainers, mode=None if K == 1 else resolve_group_mode(group_mode, trainers, config.batch_size))
 
-    if logger is None:
-        try:
-            import wandb
-            wandb.init(config=asdict(config), project=config.project, group=config.group, name=config.name)
-            if K == 1:
-                logger = lambda d, step: wandb.log(d, step=step)
-            else:  # one process, K runs: the records of seed s go under "seed<s>/"
-                logger = lambda d, step: wandb.log({(f"seed{int(d['seed'])}/{n}" if "seed" in d else n): v
-                                                    for n, v in d.items() if n != "seed"}, step=step)
-        except ImportError:
-            logger = lambda d, step: print(f"[{step}] " + " ".join(f"{n}={v:.5g}" for n, v in d.items()))
+    if logger is None:  # (one process, K runs: the records of seed s go under "seed<s>/")
+        logger = default_logger(config, K, run_id=False)
 
     def steps(group, active, t, n):  # one library call for steps t .. t + n - 1 of all K seeds (ref:1533-1544)
         idx = None if index_stream is None else [index_stream(k, t, n).to(device=config.device, dtype=torch.int64)
                                                  for k in range(K)]
-        if group is None:
-            return [trainers[0].train_steps(buffers[0], n, config.batch_size, indices=None if idx is None else idx[0])]
         return group.train_steps(buffers, n, config.batch_size, return_losses=True, indices=idx)
 
     def exchange(records):  # end-of-eval metrics across the per-GPU seeds (the path's only collective)

@@ -222,42 +222,45 @@ def test_main_list(root, capsys, monkeypatch):
     assert sw._list_dims_custom("D4RL/pen/human-v2") == (45, 24) and sw._list_dims_custom("mujoco/ant/x-v0") is None
 
 
-def _loop(totals, everys, chunk, regroup=True):
-    """_offline_loop.run over stand-in trainers: what was stepped, logged, evaluated and regrouped."""
+def _loop(totals, everys, chunk):
+    """_offline_loop.run over stand-in trainers: what was stepped, logged and evaluated, and the members of every
+    group that was built."""
     from iqlpref_amd import _offline_loop
     K = len(totals) if isinstance(totals, list) else 2
-    calls, active = [], [list(range(K))]
+    calls = []
 
-    def steps(t, n):
-        calls.append(("steps", t, n, tuple(active[0])))
-        return [torch.full((n, 3), float(k)) + torch.arange(t, t + n, dtype=torch.float32)[:, None] for k in active[0]]
+    def steps(group, active, t, n):
+        assert group is None
+        calls.append(("steps", t, n, tuple(active)))
+        return [torch.full((n, 3), float(k)) + torch.arange(t, t + n, dtype=torch.float32)[:, None] for k in active]
 
-    def hook(left):
-        calls.append(("regroup", tuple(left)))
-        active[0] = list(left)
+    def make_group(active):
+        calls.append(("make_group", tuple(active)))
         return None
 
     records = []
-    _offline_loop.run([object()] * K, list(range(K)), None, totals, everys, chunk, lambda d, s: records.append((d, s)),
-                      [None] * K, steps, lambda k, tr, step: calls.append(("eval", k, step)) or np.asarray([1.0 * k]),
-                      regroup=hook if regroup else None, tagged=lambda rec, k: dict(rec, run=k))
+    _offline_loop.run([object()] * K, list(range(K)), make_group, totals, everys, chunk,
+                      lambda d, s: records.append((d, s)), [None] * K, steps,
+                      lambda k, tr, step: calls.append(("eval", k, step)) or np.asarray([1.0 * k]),
+                      tagged=lambda rec, k: dict(rec, run=k))
     return calls, records
 
 
 def test_loop_per_member_totals_and_periods():
     calls, records = _loop([6, 4], [3, 2], 100)
-    assert calls == [("steps", 0, 2, (0, 1)), ("eval", 1, 1), ("steps", 2, 1, (0, 1)), ("eval", 0, 2),
-                     ("steps", 3, 1, (0, 1)), ("eval", 1, 3), ("regroup", (0,)), ("steps", 4, 2, (0,)), ("eval", 0, 5)]
+    assert calls == [("make_group", (0, 1)), ("steps", 0, 2, (0, 1)), ("eval", 1, 1), ("steps", 2, 1, (0, 1)),
+                     ("eval", 0, 2), ("steps", 3, 1, (0, 1)), ("eval", 1, 3), ("make_group", (0,)),
+                     ("steps", 4, 2, (0,)), ("eval", 0, 5)]
     for k, total in ((0, 6), (1, 4)):
         mine = [(d, s) for d, s in records if d["run"] == k and "value_loss" in d]
         assert [s for _, s in mine] == list(range(total))
         assert [d["value_loss"] for d, _ in mine] == [float(k + s) for s in range(total)]
     # the chunk bounds a call as well; a member of no steps never enters
     calls, _ = _loop([5, 0], [10, 10], 2)
-    assert calls == [("regroup", (0,)), ("steps", 0, 2, (0,)), ("steps", 2, 2, (0,)), ("steps", 4, 1, (0,))]
-    # scalars: every member to the end, no regroup
-    calls, records = _loop(4, 2, 100, regroup=False)
-    assert calls == [("steps", 0, 2, (0, 1)), ("eval", 0, 1), ("eval", 1, 1), ("steps", 2, 2, (0, 1)), ("eval", 0, 3),
+    assert calls == [("make_group", (0,)), ("steps", 0, 2, (0,)), ("steps", 2, 2, (0,)), ("steps", 4, 1, (0,))]
+    # scalars: every member to the end, one group for all of it
+    calls, records = _loop(4, 2, 100)
+    assert calls == [("make_group", (0, 1)), ("steps", 0, 2, (0, 1)), ("eval", 0, 1), ("eval", 1, 1), ("steps", 2, 2, (0, 1)), ("eval", 0, 3),
                      ("eval", 1, 3)]
     assert len(records) == 2 * 4 + 2 * 2 * 3
 

@@ -78,3 +78,40 @@ def test_sweep_list_prints_the_mode_per_batch(tmp_path, capsys, monkeypatch):
     assert all(len(ln.split("\t")) == 3 for ln in capsys.readouterr().out.strip().splitlines())
     with pytest.raises(SystemExit):
         sw.main([str(path), "--list", "--group_mode", "fastest"])
+
+
+def test_solo_forwards_to_its_one_trainer_and_stepper_picks(monkeypatch):
+    import torch
+    from iqlpref_amd import multi
+    calls = []
+
+    class Trainer:
+        def train_steps(self, *args, **kw):
+            calls.append((args, kw))
+            return "losses" if kw["return_losses"] else None
+
+    tr, buf, idx, keep, valid = Trainer(), object(), object(), object(), torch.zeros(5, dtype=torch.int32)
+    solo = multi.Solo(tr)
+    assert solo.trainers == [tr] and len(solo) == 1 and solo.mode == "solo" and solo.close() is None
+    # every argument unchanged, in one call; a list of one losses back
+    assert solo.train_steps([buf], 5, 32, indices=[idx], dropout_keep=[keep], return_losses=True, graph_unroll=7,
+                            n_valid=[valid]) == ["losses"]
+    assert solo.train_steps(buf, 5, 32, n_valid=valid) is None
+    want = [((buf, 5, 32), dict(indices=idx, dropout_keep=keep, return_losses=True, graph_unroll=7, n_valid=valid)),
+            ((buf, 5, 32), dict(indices=None, dropout_keep=None, return_losses=False, graph_unroll=None, n_valid=valid))]
+    assert len(calls) == 2 and all(got[0] == exp[0] and list(got[1]) == list(exp[1]) and
+                                   all(got[1][n] is exp[1][n] for n in exp[1]) for got, exp in zip(calls, want))
+    # lists of another length: SeedGroup.train_steps' errors, and no call
+    for kw, words in ((dict(indices=[idx, idx]), "indices / dropout_keep"), (dict(dropout_keep=[]), "indices / dropout_keep"),
+                      (dict(n_valid=[valid, valid]), "n_valid: one tensor")):
+        with pytest.raises(ValueError, match=words):
+            solo.train_steps(buf, 5, 32, **kw)
+    with pytest.raises(ValueError, match="one replay buffer per trainer"):
+        solo.train_steps([buf, buf], 5, 32)
+    assert len(calls) == 2
+    # stepper: Solo for one trainer, SeedGroup with the mode and keywords for several (no library load)
+    monkeypatch.setattr(multi, "SeedGroup", lambda trainers, **kw: ("group", trainers, kw))
+    one = multi.stepper([tr], mode="group")
+    assert isinstance(one, multi.Solo) and one.trainers == [tr]
+    assert multi.stepper([tr, tr], mode="general", chunk=9) == ("group", [tr, tr], {"mode": "general", "chunk": 9})
+    assert multi.stepper([tr, tr]) == ("group", [tr, tr], {"mode": None})

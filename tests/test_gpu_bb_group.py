@@ -248,6 +248,20 @@ def test_group_index_generator_equals_host_sampler(bb, n_rows, t0, K):
         assert torch.equal(lone_idx, idx[k]) and torch.equal(lone_valid, valid)
 
 
+def test_a_sampler_group_of_one_is_its_sampler(bb):
+    """37 rows in batches of 8 (4 blocks and 5 rows left over), steps 3 .. 11: the short slot twice, the epoch
+    wrap, and the one-sampler launch behind the group's return shape."""
+    sampler = bb.BlockEpochSampler(37, 8, generator=torch.Generator().manual_seed(37))
+    idx, valid = bb.BlockEpochSamplerGroup([sampler]).device_indices(3, 9, DEV)
+    lone_idx, lone_valid = sampler.device_indices(3, 9, DEV)
+    want_idx, want_valid = sampler.host_indices(3, 9)
+    assert isinstance(idx, list) and len(idx) == 1 and want_valid.tolist() == [8, 5, 8, 8, 8, 8, 5, 8, 8]
+    assert torch.equal(idx[0], lone_idx) and torch.equal(valid, lone_valid)
+    assert idx[0].dtype == torch.int64 and valid.dtype == torch.int32
+    np.testing.assert_array_equal(idx[0].cpu().numpy(), want_idx)
+    np.testing.assert_array_equal(valid.cpu().numpy(), want_valid)
+
+
 def _train(bb, golden, tmp_path, **kw):
     records = []
     seeds = []

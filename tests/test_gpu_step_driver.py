@@ -1,8 +1,8 @@
 """The host driver of the training step (csrc/api.hip: StepQueue, run_tuned, deep_run): one road from
 ``train_steps`` to the stream for a lone trainer and for the K members of a group, on the tuned and on the
 general step.  What the other files do not pin: the timed diagnostic mode changes no bit, a group of one is
-a trainer, and one handle taken through every branch of the driver in one sequence.  Everything is compared
-bit for bit against plain launches from the same seeds.  -m gpu."""
+a trainer, one handle taken through every branch of the driver in one sequence, and a ``multi.Solo`` stepper is
+its trainer.  Everything is compared bit for bit against plain launches from the same seeds.  -m gpu."""
 import ctypes as C
 import functools
 import math
@@ -14,6 +14,7 @@ from tests import helpers
 
 pytestmark = pytest.mark.gpu
 STATE = ("_params", "_target", "_exp_avg", "_exp_avg_sq")
+DEV = "cuda:0"
 TUNED, GENERAL = "traj_antmaze", "traj_deep3_w96"
 
 
@@ -147,3 +148,62 @@ def test_one_handle_through_every_branch_of_the_driver(gh, kind):
     if kind == "group":
         assert not torch.equal(got[0]._params, got[1]._params)
         h.close(), plain.close()
+
+
+# ---- 4. a Solo stepper is its trainer -------------------------------------------------------------------------- #
+def _small_trainer(seed, S=11, A=3, H=64):
+    import iqlpref_amd as ia
+    torch.manual_seed(seed)
+    q, v, actor = (ia.TwinQ(S, A, hidden_dim=H).to(DEV), ia.ValueFunction(S, hidden_dim=H).to(DEV),
+                   ia.GaussianPolicy(S, A, 1.0, hidden_dim=H).to(DEV))
+    adam = lambda mod: torch.optim.Adam(mod.parameters(), lr=3e-4)
+    return ia.ImplicitQLearning(1.0, actor, adam(actor), q, adam(q), v, adam(v), max_steps=1000, device=DEV,
+                                precision="fp32", seed=seed)
+
+
+def _tensors(x, prefix=""):
+    if isinstance(x, dict):
+        for k, v in x.items():
+            yield from _tensors(v, f"{prefix}/{k}")
+    elif isinstance(x, (list, tuple)):
+        for i, v in enumerate(x):
+            yield from _tensors(v, f"{prefix}/{i}")
+    elif isinstance(x, torch.Tensor):
+        yield prefix, x
+
+
+@pytest.mark.parametrize("short_last", [False, True])
+def test_a_solo_stepper_is_its_trainer(gh, short_last):
+    """40 steps on explicit indices, once by ``trainer.train_steps`` and once through ``stepper([trainer])``: the
+    same losses, state and launch counts, and the trainer joins no group.  ``short_last``: per-step valid-row
+    counts, the last step 13 rows of 32."""
+    import numpy as np
+    import iqlpref_amd as ia
+    from iqlpref_amd import multi
+    S, A, B, N, steps = 11, 3, 32, 500, 40
+    rng = np.random.default_rng(17)
+    buf = ia.ReplayBuffer(S, A, N, DEV)
+    buf.load_d4rl_dataset({"observations": rng.standard_normal((N, S)).astype(np.float32),
+                           "actions": rng.uniform(-1, 1, (N, A)).astype(np.float32),
+                           "rewards": rng.standard_normal(N).astype(np.float32),
+                           "next_observations": rng.standard_normal((N, S)).astype(np.float32),
+                           "terminals": (rng.uniform(size=N) < 0.1).astype(np.float32)})
+    idx = torch.from_numpy(rng.integers(0, N, (steps, B))).to(DEV)
+    valid = torch.tensor([B] * (steps - 1) + [13], dtype=torch.int32, device=DEV) if short_last else None
+    lone, member = _small_trainer(5), _small_trainer(5)
+    assert lone.step_kind(B) == "tuned"
+    want = lone.train_steps(buf, steps, B, indices=idx, n_valid=valid)
+    solo = multi.stepper([member])
+    assert isinstance(solo, multi.Solo) and solo.trainers == [member]
+    got = solo.train_steps([buf], steps, B, indices=[idx], n_valid=valid, return_losses=True)
+    solo.synchronize()
+    assert len(got) == 1 and torch.equal(got[0], want) and torch.isfinite(want).all()
+    a, b = dict(_tensors(member.state_dict())), dict(_tensors(lone.state_dict()))
+    assert a.keys() == b.keys() and len(a) > 20
+    for name in b:
+        assert torch.equal(a[name], b[name]), name
+    _same_state([lone], [member])
+    assert member.launch_counts() == lone.launch_counts() != (0, 0)
+    assert member._group_owner is None
+    solo.close()
+    assert member.total_it == lone.total_it == steps

@@ -27,6 +27,10 @@ class Trainer:
         return {"w": torch.tensor([float(self.k), float(self.done)])}
 
 
+class Failure(Exception):
+    pass
+
+
 class Group:
     def __init__(self, events):
         self.events = events
@@ -34,16 +38,27 @@ class Group:
     def synchronize(self):
         self.events.append(("sync",))
 
+    def close(self):
+        self.events.append(("close",))
 
-def drive(K, returns, path=None, total=12, normalized=None, best_by_return=False):
+
+def drive(K, returns, path=None, total=12, normalized=None, best_by_return=False, fail_at=None):
     """Run the loop (every=6, chunk=4) over fakes; ``returns[b]`` is the mean return of every seed at
-    boundary b.  -> (events, trainers, seeds, ckpt_dirs); events are ("steps", t, n), ("sync",),
-    ("eval", k, step) and ("log", record, step) in the order they happened."""
+    boundary b.  -> (events, trainers, seeds, ckpt_dirs); events are ("group", active) of every ``make_group``
+    call (which gives None for K = 1), ("steps", t, n), ("sync",), ("close",), ("eval", k, step) and
+    ("log", record, step) in the order they happened.  ``fail_at``: the evaluation at that step raises."""
     events = []
     seeds = [40 + k for k in range(K)]
     trainers = [Trainer(k) for k in range(K)]
+    group = []
 
-    def steps(t, n):
+    def make_group(active):
+        events.append(("group", active))
+        group[:] = [Group(events) if K > 1 else None]
+        return group[0]
+
+    def steps(got, active, t, n):
+        assert got is group[0] and active == list(range(K))
         events.append(("steps", t, n))
         for tr in trainers:
             tr.done += n
@@ -52,12 +67,15 @@ def drive(K, returns, path=None, total=12, normalized=None, best_by_return=False
 
     def evaluate(k, trainer, step):
         assert trainer is trainers[k]
+        if step == fail_at:
+            events.append(("raise",))
+            raise Failure(events)
         events.append(("eval", k, step))
         r = returns[step // 6]
         return np.array([r - 0.5, r + 0.5])
 
     ckpt_dirs = ol.checkpoint_dirs(Config(checkpoints_path=None if path is None else str(path)), seeds)
-    ol.run(trainers, seeds, Group(events) if K > 1 else None, total, 6, 4,
+    ol.run(trainers, seeds, make_group, total, 6, 4,
            lambda rec, step: events.append(("log", dict(rec), step)), ckpt_dirs, steps, evaluate,
            normalized=normalized, best_by_return=best_by_return)
     return events, trainers, seeds, ckpt_dirs
@@ -106,12 +124,16 @@ def test_order_of_everything_observable(K, tmp_path):
     # the whole sequence: queue, flush, [flush, synchronize, evaluate] -- the best model stays that of step 5
     at = lambda step, ret: eval_records(K, seeds, step, [("evaluation_return", ret), ("best_score_so_far", 2.0),
                                                            ("best_step_so_far", 5)])
-    assert events == ([("steps", 0, 4), ("steps", 4, 2)] + first_chunk + loss_records(K, seeds, 4, 2) + at(5, 2.0)
+    everyone = list(range(K))
+    assert events == ([("group", everyone), ("steps", 0, 4), ("steps", 4, 2)] + first_chunk + loss_records(K, seeds, 4, 2) + at(5, 2.0)
                       + [("steps", 6, 4), ("steps", 10, 2)] + loss_records(K, seeds, 6, 4)
-                      + loss_records(K, seeds, 10, 2) + at(11, 1.0))
+                      + loss_records(K, seeds, 10, 2) + at(11, 1.0)
+                      + ([("sync",), ("close",)] if K > 1 else []))  # all end: the group is dissolved, none built
     if K > 1:  # synchronize comes before the first evaluation of each boundary
         syncs = [i for i, e in enumerate(events) if e == ("sync",)]
-        assert syncs == [pos(events, ("eval", 0, 5)) - 1, pos(events, ("eval", 0, 11)) - 1]
+        assert syncs[:2] == [pos(events, ("eval", 0, 5)) - 1, pos(events, ("eval", 0, 11)) - 1]
+    else:  # None as the group: nothing is synchronized or closed
+        assert not [e for e in events if e[0] in ("sync", "close")]
 
     # files: best_model.pt written once, with the state at step 5 (6 steps done)
     files = ["best_model.pt", "checkpoint_11.pt", "checkpoint_5.pt", "config.yaml"]
@@ -129,6 +151,53 @@ def test_order_of_everything_observable(K, tmp_path):
     import yaml
     with open(tmp_path / "config.yaml") as f:
         assert yaml.safe_load(f) == {"name": "fake", "checkpoints_path": str(tmp_path)}
+
+
+@pytest.mark.parametrize("K", [1, 3])
+def test_an_exception_closes_the_group_once_without_a_synchronize(K):
+    with pytest.raises(Failure) as err:
+        drive(K, (2.0, 1.0), fail_at=11)
+    events = err.value.args[0]  # what had happened when evaluate raised, and what the loop did on its way out:
+    assert events[events.index(("raise",)) + 1:] == ([("close",)] if K > 1 else [])  # no synchronize, no log
+    assert events.count(("close",)) == (1 if K > 1 else 0)
+    assert [e for e in events if e[0] == "group"] == [("group", list(range(K)))]
+
+
+def test_members_lifecycle_and_spread():
+    calls = []
+
+    class G:
+        def __init__(self, active):
+            self.active = tuple(active)
+
+        def synchronize(self):
+            calls.append(("sync", self.active))
+
+        def close(self):
+            calls.append(("close", self.active))
+
+    def make(active):
+        calls.append(("group", active))
+        return G(active)
+
+    with ol.Members(make, [0, 1, 2]) as live:
+        live.keep([0, 1, 2])  # nobody left: nothing happens
+        assert not live.commit_due([], [0, 1, 2]) and live.commit_due([1], [0, 1, 2]) and calls == [("group", [0, 1, 2])]
+        assert live.commit_due([], [0, 2]) and calls[-1] == ("sync", (0, 1, 2))  # no evaluation synchronized
+        live.keep([0, 2])
+        assert live.active == [0, 2] and live.group.active == (0, 2)
+        live.keep([])
+        assert live.active == [] and live.group is None
+    assert calls == [("group", [0, 1, 2]), ("sync", (0, 1, 2)), ("sync", (0, 1, 2)), ("close", (0, 1, 2)),
+                     ("group", [0, 2]), ("sync", (0, 2)), ("close", (0, 2))]  # nothing built for nobody
+    del calls[:]
+    with ol.Members(make, [4]):
+        pass
+    assert calls == [("group", [4]), ("sync", (4,)), ("close", (4,))]
+    with ol.Members(lambda active: None, [0]) as live:  # None: nothing to synchronize or close
+        live.synchronize()
+    assert ol.Members(make, []).group is None and calls[-1] == ("close", (4,))
+    assert ol.spread(3, 2) == [3, 3] and ol.spread([1, 2.0], 2) == [1, 2] and ol.spread(True, 1) == [1]
 
 
 @pytest.mark.parametrize("K", [1, 3])

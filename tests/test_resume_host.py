@@ -55,16 +55,16 @@ class World:
         self.K, self.totals, self.everys = K, totals, everys
         self.trainers = [Trainer(k) for k in range(K)]
         self.draws = [0] * K
-        self.records, self.evals, self.regroups = [], [], []
-        self.active = list(range(K))
+        self.records, self.evals, self.regroups = [], [], []  # regroups: the members of every make_group call
         self.seeds = [40 + k for k in range(K)]
         self.dirs = [os.path.join(str(path), f"run{k}") for k in range(K)]
         for d in self.dirs:
             os.makedirs(d, exist_ok=True)
 
-    def steps(self, t, n):
+    def steps(self, group, active, t, n):
+        assert group is None and active == self.regroups[-1]
         out = []
-        for k in self.active:
+        for k in active:
             tr, rows = self.trainers[k], []
             assert tr.done == t, "a member is stepped from the common step"
             for _ in range(n):
@@ -75,9 +75,8 @@ class World:
             out.append(torch.tensor(rows, dtype=torch.float64))
         return out
 
-    def regroup(self, active):
+    def make_group(self, active):
         self.regroups.append(list(active))
-        self.active = list(active)
         return None
 
     def run(self, resume, stop_at=None, chunk=4):
@@ -88,9 +87,9 @@ class World:
             self.evals.append((k, step))
             return np.array([trainer.acc - step, trainer.acc + k])
 
-        ol.run(self.trainers, self.seeds, None, self.totals, self.everys, chunk,
+        ol.run(self.trainers, self.seeds, self.make_group, self.totals, self.everys, chunk,
                lambda rec, step: self.records.append((dict(rec), step)), self.dirs, self.steps, evaluate,
-               normalized=lambda scores: scores / 8.0, regroup=self.regroup, resume=resume,
+               normalized=lambda scores: scores / 8.0, resume=resume,
                sampler_state=lambda k: {"draws": self.draws[k]},
                set_sampler_state=lambda k, st: self.draws.__setitem__(k, st["draws"]))
         return self
@@ -143,7 +142,7 @@ def test_interrupt_at_a_boundary(tmp_path):
     assert [_resume.steps_in(d) for d in first.dirs] == [[6], [6], [6]]
     second = World(3, tmp_path / "cut", TOTALS, EVERYS).run(True)
     check_resumed(first, second, whole, 6)
-    assert second.evals[0] == (0, 11) and second.regroups == whole.regroups == [[1, 2], [1]]
+    assert second.evals[0] == (0, 11) and second.regroups == whole.regroups == [[0, 1, 2], [1, 2], [1]]
     # what the finished run leaves: every member's final file, marked finished, at its own last step
     assert [_resume.steps_in(d) for d in second.dirs] == [[12], [24], [18]]
     assert [_resume.status(d) for d in second.dirs] == ["done"] * 3

@@ -138,6 +138,40 @@ def test_duplicate_checkpoints_path_and_bad_runs_per_gpu_raise_before_device_wor
         sw.train_runs([_cfg(), _cfg()], env=object(), dataset={}, evaluate=[lambda a, t: None])
 
 
+def test_start_runs_checks_in_order_and_deals_the_configs(tmp_path, monkeypatch):
+    monkeypatch.setenv("RANK", "1")
+    monkeypatch.setenv("WORLD_SIZE", "2")
+    cfgs = [_cfg(seed=s) for s in range(5)]
+    assert sw.start_runs(cfgs, 8, None, False) == ([0, 1, 2, 3, 4], [1, 3])
+    assert sw.start_runs(cfgs, 8, ["7", 8, 9, 10, 11], False) == ([7, 8, 9, 10, 11], [1, 3])
+    with pytest.raises(ValueError, match="run_ids"):
+        sw.start_runs(cfgs, 8, [0, 1], False)
+    with pytest.raises(ValueError, match="runs_per_gpu"):  # ahead of the run_ids check
+        sw.start_runs(cfgs, 0, [0, 1], False)
+    with pytest.raises(ValueError, match="checkpoints_path"):  # resume: every config needs a directory
+        sw.start_runs(cfgs, 8, [0, 1], True)
+
+
+def test_batch_cache_builds_on_first_need_and_drops_after_the_last_batch():
+    batches = [[0, 1], [2], [3, 4]]
+    keys = {0: "a", 1: "b", 2: "a", 3: "c", 4: "b"}  # a: batches 0-1, b: 0-2, c: 2
+    cache, built = sw.BatchCache(batches, keys.__getitem__), []
+    assert cache.key_of == keys
+
+    def get(i):
+        return cache.get(i, lambda: built.append(keys[i]) or [keys[i]])
+
+    held = []
+    for bi, batch in enumerate(batches):
+        values = [get(i) for i in batch]
+        assert [v[0] for v in values] == [keys[i] for i in batch]
+        assert get(batch[0]) is values[0]  # the same object for every run of the key
+        cache.batch_done(bi)
+        held.append([k for k in "abc" if k in cache])
+    assert built == ["a", "b", "c"]  # each once, in the order first needed
+    assert held == [["a", "b"], ["b"], []]  # gone right after the last batch that uses it
+
+
 def test_one_env_object_for_two_env_names_raises():
     cfgs = [_cfg(env="antmaze-medium-play-v2"), _cfg(env="antmaze-large-play-v2")]
     with pytest.raises(ValueError, match="environments"):

@@ -68,7 +68,7 @@ def drive(settings, path=None, *, grouped=True, resume=False, scores=True, cut_a
     """One start of the loop over ``len(settings)`` fake members; ``settings``: (total, log_every, eval_every)
     each.  -> (events, trainers, ckpt_dirs, state).  ``grouped`` False: the factory gives None (one seed)."""
     K = len(settings)
-    events = []
+    events, cut = [], Cut()
     trainers = [Trainer(k, events) for k in range(K)]
     dirs = [None if path is None else str(path / f"m{k}") for k in range(K)]
     for d in dirs:
@@ -89,7 +89,8 @@ def drive(settings, path=None, *, grouped=True, resume=False, scores=True, cut_a
     def evaluate(k, trainer, t):
         assert trainer is trainers[k] and trainer.total_it == t
         if t == cut_at:
-            raise Cut
+            events.append(("raise", k, t))
+            raise cut
         events.append(("eval", k, t))
         return (scores_at(k, t), [] if t == 6 else [t, t + 2]) if scores else (None, [])
 
@@ -101,8 +102,8 @@ def drive(settings, path=None, *, grouped=True, resume=False, scores=True, cut_a
                lambda rec, k: dict(rec, who=k), goal_env=goal_env,
                exchange=lambda records: events.append(("exchange", strip(records))), resume=resume,
                keep_previous=keep_previous)
-    except Cut:
-        assert cut_at is not None
+    except Cut as e:  # (the loop hands on what evaluate raised)
+        assert cut_at is not None and e is cut
     return events, trainers, dirs, state
 
 
@@ -269,6 +270,13 @@ def test_at_most_picks_the_older_generation(tmp_path):
     assert again[0] == ("group", [0, 1]) and again[1:] == whole[whole.index(("steps", 12, 2, [0, 1])):]
     assert state.t == 14 and [tr.total_it for tr in trainers] == [14, 14]
     assert [_resume.steps_in(d) for d in dirs] == [[12, 14]] * 2
+
+
+@pytest.mark.parametrize("grouped", [True, False])
+def test_an_exception_closes_the_group_once_without_a_synchronize(grouped):
+    events, *_ = drive(OWN, grouped=grouped, cut_at=10)  # member 0 left at 8: the second group is the open one
+    assert events[events.index(("raise", 2, 10)) + 1:] == ([("close", (1, 2))] if grouped else [])
+    assert [e for e in events if e[0] == "close"] == ([("close", (0, 1, 2)), ("close", (1, 2))] if grouped else [])
 
 
 # --------------------------------------------------------------------------- #
