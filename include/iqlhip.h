@@ -381,6 +381,32 @@ typedef struct {
 int iqlhip_mlp_forward(const iqlhip_mlp_desc *d, const float *x, int64_t n, int32_t x_stride,
                        float *out, int32_t out_stride, void *stream);
 
+/* A frozen set of M MLPs of one shape, for one launch over rows of their own (the post-hoc
+ * checkpoint evaluation, iqlpref_amd/posthoc.py: M checkpoints x R environments per lock step).
+ *
+ * iqlhip_mlp_set_create writes every member's fragment-major weight images and biases into ONE device
+ * allocation of the current device that the set owns, and waits for `stream`: the set is a snapshot,
+ * the source tensors may change or go afterwards.  All members share n_layers, dims, the activation
+ * codes and w_in_out (else IQLHIP_ERR_INVALID); every width is <= 256 and dropout_p <= 0 (an eval-mode
+ * forward), else IQLHIP_ERR_UNSUPPORTED: iqlhip_mlp_forward takes those.  M outside
+ * 1..IQLHIP_MLP_SET_MAX, a null pointer anywhere, n_layers or an activation code outside
+ * iqlhip_mlp_forward's range: IQLHIP_ERR_INVALID.  Every refusal happens before any HIP call and
+ * leaves *out as it was.
+ *
+ * iqlhip_mlp_set_forward is one launch: no allocation, no host wait, no repack.
+ *   out[(m R + r) out_stride + c] = MLP_m(x[(m R + r) x_stride + 0 .. dims[0]))[c],  m < M, r < R
+ * with the bits iqlhip_mlp_forward(descs[m], that row, 1, ...) writes (both run the same row-tile
+ * body).  Exactly M R rows and dims[n_layers] columns are written.  R < 1, a null pointer or a stride
+ * below the width: IQLHIP_ERR_INVALID, nothing is launched; so is a call while another device than the
+ * set's (the one current at create) is current.
+ * Pinned by tests/test_gpu_posthoc.py.                                                            */
+typedef struct iqlhip_mlp_set iqlhip_mlp_set;
+#define IQLHIP_MLP_SET_MAX 1024
+int iqlhip_mlp_set_create(const iqlhip_mlp_desc *const *descs, int32_t M, iqlhip_mlp_set **out, void *stream);
+int iqlhip_mlp_set_destroy(iqlhip_mlp_set *set);
+int iqlhip_mlp_set_forward(const iqlhip_mlp_set *set, const float *x, int32_t R, int32_t x_stride,
+                           float *out, int32_t out_stride, void *stream);
+
 /* ------------------------------------------------------------------------ */
 /* Ensemble CVaR  (ref:1003-1011 BNN, ref:1185-1187 MR snapshots)             */
 /*   out[c] = mean of the n_tail smallest of preds[0..S)[c],  c < N           */

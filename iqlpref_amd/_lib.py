@@ -18,6 +18,8 @@ MAX_HIDDEN = 6
 N_TENSORS = 2 * (MAX_HIDDEN + 1) * (MAX_CRITICS + 2) + 1
 MLP_MAX_LAYERS = 8
 MAX_GROUP = 16
+MLP_SET_MAX = 1024  # IQLHIP_MLP_SET_MAX
+MLP_SET_MAX_WIDTH = 256  # wider members: iqlhip_mlp_set_create is ERR_UNSUPPORTED
 ACT_FLAX_BASE = 8  # iqlhip_mlp_desc activation code 8 + i = entry i of reward_models/q_mlp.py:121-130
 ABI_VERSION = 6
 CHOICE_MEAN = 0
@@ -145,6 +147,9 @@ SYMBOLS = {
     "iqlhip_train_batch": (C.c_int, [P, P, P, P, P, P, P, P, P]),
     "iqlhip_forward": (C.c_int, [P, C.c_int32, P, P, C.c_int64, P, P]),
     "iqlhip_mlp_forward": (C.c_int, [C.POINTER(MlpDesc), P, C.c_int64, C.c_int32, P, C.c_int32, P]),
+    "iqlhip_mlp_set_create": (C.c_int, [C.POINTER(C.POINTER(MlpDesc)), C.c_int32, C.POINTER(P), P]),
+    "iqlhip_mlp_set_destroy": (C.c_int, [P]),
+    "iqlhip_mlp_set_forward": (C.c_int, [P, P, C.c_int32, C.c_int32, P, C.c_int32, P]),
     "iqlhip_cvar_tail_mean": (C.c_int, [P, C.c_int32, C.c_int64, C.c_int32, P, P]),
     "iqlhip_pt_relabel": (C.c_int, [C.POINTER(PtWeights), P, P, C.c_int64, P, P, P, C.c_int64, C.c_int32,
                                     P, P]),

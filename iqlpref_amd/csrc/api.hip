@@ -56,6 +56,11 @@ hipError_t launch_sample(const iqlhip_replay_view &v, int batch, const int64_t *
                          int64_t *idx_out, hipStream_t st);
 hipError_t launch_mlp_f32(const iqlhip_mlp_desc &d, const float *x, int64_t n, int x_stride, float *out,
                           int out_stride, hipStream_t st);
+hipError_t mlp_set_create(const iqlhip_mlp_desc *const *descs, int M, iqlhip_mlp_set **out, hipStream_t st);
+hipError_t mlp_set_destroy(iqlhip_mlp_set *s);
+void mlp_set_shape(const iqlhip_mlp_set *s, int *M, int *in, int *out, int *device);
+hipError_t launch_mlp_set(const iqlhip_mlp_set *s, const float *x, int R, int x_stride, float *out, int out_stride,
+                          hipStream_t st);
 hipError_t launch_cvar(const float *preds, int S, int64_t N, int n_tail, float *out, hipStream_t st);
 hipError_t launch_keep_steps(const uint8_t *term, const uint8_t *tmo, int64_t n, int64_t M, int toe,
                              uint8_t *keep, int64_t *ep_steps, hipStream_t st);
@@ -1618,6 +1623,60 @@ extern "C" int iqlhip_mlp_forward(const iqlhip_mlp_desc *d, const float *x, int6
   if (!(d->dropout_p < 1.0f)) return fail(IQLHIP_ERR_INVALID, "dropout_p must be < 1");
   if (d->dropout_p > 0.f && n > 0xffffffffLL) return fail(IQLHIP_ERR_UNSUPPORTED, "dropout: n must fit 32 bits");
   HIP_TRY(launch_mlp_f32(*d, x, n, x_stride, out, out_stride, (hipStream_t)stream));
+  return 0;
+}
+
+extern "C" int iqlhip_mlp_set_create(const iqlhip_mlp_desc *const *descs, int32_t M, iqlhip_mlp_set **out,
+                                     void *stream) {
+  if (!descs || !out) return fail(IQLHIP_ERR_INVALID, "null argument");
+  if (M < 1 || M > IQLHIP_MLP_SET_MAX)
+    return fail(IQLHIP_ERR_INVALID, "M = %d outside [1, %d]", M, IQLHIP_MLP_SET_MAX);
+  for (int m = 0; m < M; ++m)
+    if (!descs[m]) return fail(IQLHIP_ERR_INVALID, "member %d: null descriptor", m);
+  const iqlhip_mlp_desc &d0 = *descs[0];
+  if (d0.n_layers < 1 || d0.n_layers > IQLHIP_MLP_MAX_LAYERS)
+    return fail(IQLHIP_ERR_INVALID, "n_layers must be in [1, %d]", IQLHIP_MLP_MAX_LAYERS);
+  for (int i = 0; i <= d0.n_layers; ++i) {
+    if (d0.dims[i] <= 0) return fail(IQLHIP_ERR_INVALID, "layer width %d", d0.dims[i]);
+    if (d0.dims[i] > 256)
+      return fail(IQLHIP_ERR_UNSUPPORTED, "layer width %d > 256: iqlhip_mlp_forward takes it", d0.dims[i]);
+  }
+  for (int a : {d0.hidden_act, d0.out_act})
+    if (a < 0 || (a > 1 && a < 8) || a > 15) return fail(IQLHIP_ERR_INVALID, "activation code %d", a);
+  for (int m = 0; m < M; ++m) {
+    const iqlhip_mlp_desc &d = *descs[m];
+    bool same = d.n_layers == d0.n_layers && d.w_in_out == d0.w_in_out && d.hidden_act == d0.hidden_act &&
+                d.out_act == d0.out_act;
+    for (int i = 0; same && i <= d0.n_layers; ++i) same = d.dims[i] == d0.dims[i];
+    if (!same) return fail(IQLHIP_ERR_INVALID, "member %d differs from member 0 in shape, activation or layout", m);
+    for (int i = 0; i < d.n_layers; ++i)
+      if (!d.weights[i] || !d.biases[i]) return fail(IQLHIP_ERR_INVALID, "member %d: null weight pointer", m);
+    if (d.dropout_p > 0.f)
+      return fail(IQLHIP_ERR_UNSUPPORTED, "member %d: dropout_p > 0 (the set is an eval-mode forward)", m);
+  }
+  iqlhip_mlp_set *s = nullptr;
+  HIP_TRY(mlp_set_create(descs, M, &s, (hipStream_t)stream));
+  *out = s;
+  return 0;
+}
+
+extern "C" int iqlhip_mlp_set_destroy(iqlhip_mlp_set *set) {
+  if (!set) return fail(IQLHIP_ERR_INVALID, "null set");
+  HIP_TRY(mlp_set_destroy(set));
+  return 0;
+}
+
+extern "C" int iqlhip_mlp_set_forward(const iqlhip_mlp_set *set, const float *x, int32_t R, int32_t x_stride,
+                                      float *out, int32_t out_stride, void *stream) {
+  if (!set || !x || !out) return fail(IQLHIP_ERR_INVALID, "null argument");
+  if (R < 1) return fail(IQLHIP_ERR_INVALID, "R = %d must be positive", R);
+  int M, in, width, device, current;
+  mlp_set_shape(set, &M, &in, &width, &device);
+  if (x_stride < in || out_stride < width) return fail(IQLHIP_ERR_INVALID, "stride smaller than the row width");
+  HIP_TRY(hipGetDevice(&current));  // (no launch, no wait: the set's images live on one device)
+  if (current != device)
+    return fail(IQLHIP_ERR_INVALID, "the set lives on device %d, the current device is %d", device, current);
+  HIP_TRY(launch_mlp_set(set, x, R, x_stride, out, out_stride, (hipStream_t)stream));
   return 0;
 }
 

@@ -14,6 +14,13 @@
 //                 share every B fragment; A fragments are shared by the wave's four n-tiles),
 //                 then written back in place behind a barrier.  Per 16-deep k-step a wave issues
 //                 4 LDS reads, 4 fragment loads (the next step's, prefetched) and 64 MFMAs.
+//
+// iqlhip_mlp_set (the post-hoc checkpoint evaluation: M actors x R rows per environment step): the M
+// members' images are written ONCE at create, a fixed stride apart in one allocation, and
+//   k_mlp_set     grid (row tile, member) runs the same 64-row body (mlp_row_tile) on member m's image,
+//                 with the tile's empty 16-row M tiles left out: one launch per step, no repack.
+#include <new>
+
 #include "../../include/iqlhip.h"
 #include "common.h"
 
@@ -95,22 +102,26 @@ __device__ __forceinline__ float out_apply(float v, int kind) {  // output layer
   return kind >= 8 ? act_flax(v, kind - 8) : (kind == 1 ? tanhf(v) : v);
 }
 
-template <int ACT>
-__global__ __launch_bounds__(256, 2) void k_mlp_f32(const MlpArgs M, const float *__restrict__ x, int64_t n,
-                                                    int x_stride, float *__restrict__ out, int out_stride) {
+// One 64-row tile through every layer: the body of k_mlp_f32 and of k_mlp_set.  Rows row0 .. row0 + 64 of
+// x[n] -> out[n]; the weight images and biases are M.Wf[l] + wofs and M.b[l] + wofs (k_mlp_set: member m's
+// copy lies m strides behind member 0's).  MT: how many of the tile's four 16-row M tiles are computed.
+// Every (n-tile, M tile) pair has accumulators of its own, so an M tile left out changes nothing in the
+// others; the rows of one that is left out must lie at or beyond n.  buf: [16 MT][lda] floats of LDS.
+template <int ACT, int MT>
+__device__ __forceinline__ void mlp_row_tile(const MlpArgs M, const size_t wofs, const float *__restrict__ x,
+                                             const int64_t n, const int64_t row0, const int x_stride,
+                                             float *__restrict__ out, const int out_stride, float *buf) {
   using P = Prec<false>;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float *buf = reinterpret_cast<float *>(smem);  // [MROWS][lda]
+  constexpr int TROWS = 16 * MT;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 15, q = lane >> 4;
-  const int64_t row0 = (int64_t)blockIdx.x * MROWS;
   const int lda = M.lda;
 
   // input rows, zero padded to a multiple of 16 columns
   {
     const int K0 = M.dims[0], K0p = round_up(K0, 16);
-    for (int e = tid; e < MROWS * K0p; e += 256) {
+    for (int e = tid; e < TROWS * K0p; e += 256) {
       const int rr = e / K0p, c = e - rr * K0p;
       float v = 0.f;
       if (row0 + rr < n && c < K0) v = ldg(x + (size_t)(row0 + rr) * x_stride + c);
@@ -122,30 +133,30 @@ __global__ __launch_bounds__(256, 2) void k_mlp_f32(const MlpArgs M, const float
   for (int l = 0; l < M.n_layers; ++l) {
     const int K = M.dims[l], N = M.dims[l + 1];
     const int nk = round_up(K, 16) / 16, ntile = round_up(N, 16) / 16;
-    const float *Wf = M.Wf[l];
-    const float *bias = M.b[l];
+    const float *Wf = M.Wf[l] + wofs;
+    const float *bias = M.b[l] + wofs;
     const bool last = l == M.n_layers - 1;
     if (last && ntile < 4) {
       // ---- narrow output layer (N < 64, e.g. the reward head N = 1): with n-tiles over waves
       // only `ntile` waves would work through all of K; instead the four waves split the k-steps,
       // every wave accumulates all n-tiles for its share, and the partial tiles meet in LDS ----
-      f32x4 pacc[3][4];
+      f32x4 pacc[3][MT];
 #pragma unroll
       for (int t = 0; t < 3; ++t)
 #pragma unroll
-        for (int m = 0; m < 4; ++m) pacc[t][m] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int m = 0; m < MT; ++m) pacc[t][m] = f32x4{0.f, 0.f, 0.f, 0.f};
       for (int ks = wave; ks < nk; ks += 4) {
-        uint4 a[4], bq[3];
+        uint4 a[MT], bq[3];
 #pragma unroll
         for (int t = 0; t < 3; ++t) bq[t] = ldg16(Wf + frag_off<P>(t < ntile ? t : 0, ks, nk, lane));
 #pragma unroll
-        for (int m = 0; m < 4; ++m)
+        for (int m = 0; m < MT; ++m)
           a[m] = *reinterpret_cast<const uint4 *>(buf + (16 * m + r) * lda + 16 * ks + 4 * q);
 #pragma unroll
         for (int t = 0; t < 3; ++t) {
           if (t < ntile) {
 #pragma unroll
-            for (int m = 0; m < 4; ++m) P::mma(a[m], bq[t], pacc[t][m]);
+            for (int m = 0; m < MT; ++m) P::mma(a[m], bq[t], pacc[t][m]);
           }
         }
       }
@@ -155,10 +166,11 @@ __global__ __launch_bounds__(256, 2) void k_mlp_f32(const MlpArgs M, const float
       for (int t = 0; t < 3; ++t)
         if (t < ntile)
 #pragma unroll
-          for (int m = 0; m < 4; ++m) red[((wave * ntile + t) * 4 + m) * 64 + lane] = pacc[t][m];
+          for (int m = 0; m < MT; ++m) red[((wave * ntile + t) * 4 + m) * 64 + lane] = pacc[t][m];
       __syncthreads();
       for (int e = tid; e < ntile * 4 * 64; e += 256) {
         const int ln = e & 63, m = (e >> 6) & 3, t = e >> 8;
+        if (MT < 4 && m >= MT) continue;
         f32x4 sum = red[((0 * ntile + t) * 4 + m) * 64 + ln];
 #pragma unroll
         for (int w = 1; w < 4; ++w) sum += red[((w * ntile + t) * 4 + m) * 64 + ln];
@@ -184,11 +196,11 @@ __global__ __launch_bounds__(256, 2) void k_mlp_f32(const MlpArgs M, const float
       live[t] = wave + 4 * t < ntile;
       tile[t] = live[t] ? wave + 4 * t : 0;
     }
-    f32x4 acc[MAXT][4];
+    f32x4 acc[MAXT][MT];
 #pragma unroll
     for (int t = 0; t < MAXT; ++t)
 #pragma unroll
-      for (int m = 0; m < 4; ++m) acc[t][m] = f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int m = 0; m < MT; ++m) acc[t][m] = f32x4{0.f, 0.f, 0.f, 0.f};
     float bv[MAXT];
 #pragma unroll
     for (int t = 0; t < MAXT; ++t) bv[t] = ldg(bias + (16 * tile[t] + r < N ? 16 * tile[t] + r : N - 1));
@@ -201,16 +213,16 @@ __global__ __launch_bounds__(256, 2) void k_mlp_f32(const MlpArgs M, const float
         const int kn = ks + 1 < nk ? ks + 1 : ks;
 #pragma unroll
         for (int t = 0; t < MAXT; ++t) bn[t] = ldg16(Wf + frag_off<P>(tile[t], kn, nk, lane));
-        uint4 a[4];
+        uint4 a[MT];
 #pragma unroll
-        for (int m = 0; m < 4; ++m)
+        for (int m = 0; m < MT; ++m)
           a[m] = *reinterpret_cast<const uint4 *>(buf + (16 * m + r) * lda + 16 * ks + 4 * q);
         // component-major issue order: the four MFMAs of one (n-tile, M-tile) pair accumulate into
         // the same registers (40-cycle dependent latency vs 32-cycle issue); between two of them the
         // wave issues the other 15 pairs
-        float4 af[4], bf[MAXT];
+        float4 af[MT], bf[MAXT];
 #pragma unroll
-        for (int m = 0; m < 4; ++m) af[m] = __builtin_bit_cast(float4, a[m]);
+        for (int m = 0; m < MT; ++m) af[m] = __builtin_bit_cast(float4, a[m]);
 #pragma unroll
         for (int t = 0; t < MAXT; ++t) bf[t] = __builtin_bit_cast(float4, bq[t]);
 #pragma unroll
@@ -219,7 +231,7 @@ __global__ __launch_bounds__(256, 2) void k_mlp_f32(const MlpArgs M, const float
           for (int t = 0; t < MAXT; ++t) {
             if (live[t]) {
 #pragma unroll
-              for (int m = 0; m < 4; ++m)
+              for (int m = 0; m < MT; ++m)
                 acc[t][m] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[m][c], bf[t][c], acc[t][m], 0, 0, 0);
             }
           }
@@ -234,7 +246,7 @@ __global__ __launch_bounds__(256, 2) void k_mlp_f32(const MlpArgs M, const float
       if (!live[t]) continue;
       const int ncol = 16 * tile[t] + r;
 #pragma unroll
-      for (int m = 0; m < 4; ++m) {
+      for (int m = 0; m < MT; ++m) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int rr = 16 * m + 4 * q + i;
@@ -253,7 +265,7 @@ __global__ __launch_bounds__(256, 2) void k_mlp_f32(const MlpArgs M, const float
     if constexpr (ACT == 2) {
       const int Np = 16 * ntile;
 #pragma unroll 1
-      for (int e = tid; e < MROWS * Np; e += 256) {
+      for (int e = tid; e < TROWS * Np; e += 256) {
         const int rr = e / Np, c = e - rr * Np;
         const float v = buf[rr * lda + c];
         if (!last) {
@@ -269,7 +281,7 @@ __global__ __launch_bounds__(256, 2) void k_mlp_f32(const MlpArgs M, const float
       // (row, 4 consecutive units); a rolled pass over LDS, the 64-fold unrolled epilogues stay lean
       const int Nq = 4 * ntile;
 #pragma unroll 1
-      for (int e = tid; e < MROWS * Nq; e += 256) {
+      for (int e = tid; e < TROWS * Nq; e += 256) {
         const int rr = e / Nq, cq = e - rr * Nq;
         const uint64_t R = (uint64_t)(row0 + rr);
         const Philox4 ph = philox4x32_10((uint32_t)R, M.drop_call, (uint32_t)cq | ((uint32_t)l << 16),
@@ -284,6 +296,40 @@ __global__ __launch_bounds__(256, 2) void k_mlp_f32(const MlpArgs M, const float
       __syncthreads();
     }
   }
+}
+
+
+template <int ACT>
+__global__ __launch_bounds__(256, 2) void k_mlp_f32(const MlpArgs M, const float *__restrict__ x, int64_t n,
+                                                    int x_stride, float *__restrict__ out, int out_stride) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  mlp_row_tile<ACT, 4>(M, 0, x, n, (int64_t)blockIdx.x * MROWS, x_stride, out, out_stride,
+                       reinterpret_cast<float *>(smem));  // [MROWS][lda]
+}
+
+// A frozen set of MLPs of one shape (iqlhip_mlp_set): block (tile, m) takes rows 64 tile .. of member m's R
+// rows through member m's weights.  The members' images and biases lie `stride` floats apart in one
+// allocation, so S.A describes member 0 and the block adds m strides: no table.  A tile's M tiles that
+// hold no row (R = 1: three of four) are not computed.
+struct MlpSetArgs {
+  MlpArgs A;
+  int64_t stride;  // floats between two members
+  int32_t R;
+};
+
+template <int ACT>
+__global__ __launch_bounds__(256, 2) void k_mlp_set(const MlpSetArgs S, const float *__restrict__ x, int x_stride,
+                                                    float *__restrict__ out, int out_stride) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float *buf = reinterpret_cast<float *>(smem);
+  const size_t m = blockIdx.y, wofs = m * (size_t)S.stride;
+  const int64_t row0 = (int64_t)blockIdx.x * MROWS, n = S.R;
+  x += m * (size_t)S.R * x_stride, out += m * (size_t)S.R * out_stride;
+  const int mt = n - row0 >= MROWS ? 4 : (int)(n - row0 + 15) / 16;  // block-uniform
+  if (mt == 1) mlp_row_tile<ACT, 1>(S.A, wofs, x, n, row0, x_stride, out, out_stride, buf);
+  else if (mt == 2) mlp_row_tile<ACT, 2>(S.A, wofs, x, n, row0, x_stride, out, out_stride, buf);
+  else if (mt == 3) mlp_row_tile<ACT, 3>(S.A, wofs, x, n, row0, x_stride, out, out_stride, buf);
+  else mlp_row_tile<ACT, 4>(S.A, wofs, x, n, row0, x_stride, out, out_stride, buf);
 }
 
 // Widths beyond 256 (up to 1024; ref:417-449 accepts any hidden_dim): one wave per 16 rows, the
@@ -362,31 +408,18 @@ hipError_t launch_mlp_repack(const iqlhip_mlp_desc &d, float *wf, hipStream_t st
   return hipGetLastError();
 }
 
-hipError_t launch_mlp_f32(const iqlhip_mlp_desc &d, const float *x, int64_t n, int x_stride, float *out,
-                          int out_stride, hipStream_t st) {
-  MlpArgs M;
-  RepackArgs R;
-  M.n_layers = R.n_layers = d.n_layers;
-  int maxd = 0;
-  size_t total = 0, off[IQLHIP_MLP_MAX_LAYERS];
+// What k_mlp_f32 / k_mlp_set need to know of a shape: everything of MlpArgs but the weight and bias
+// pointers, the kernel instantiation (see act_apply) and the dynamic LDS bytes.  maxd: the widest layer
+// that passes through the LDS buffer.
+static void mlp_geometry(const iqlhip_mlp_desc &d, MlpArgs &M, int &act, size_t &sm, int &maxd) {
+  M.n_layers = d.n_layers;
+  maxd = 0;
   for (int i = 0; i <= d.n_layers; ++i) {
-    M.dims[i] = R.dims[i] = d.dims[i];
-    if (i < d.n_layers && d.dims[i] > maxd) maxd = d.dims[i];  // widths that pass through the LDS buffer
+    M.dims[i] = d.dims[i];
+    if (i < d.n_layers && d.dims[i] > maxd) maxd = d.dims[i];
   }
-  for (int i = 0; i < d.n_layers; ++i) {
-    off[i] = total;
-    total += (size_t)round_up(d.dims[i], 16) * round_up(d.dims[i + 1], 16);
-  }
-  float *wf = nullptr;  // stream-ordered scratch for the fragment-major images (<= 8 x 256 KB)
-  hipError_t e = hipMallocAsync((void **)&wf, total * sizeof(float), st);
-  if (e != hipSuccess) return e;
-  for (int i = 0; i < d.n_layers; ++i) {
-    R.W[i] = d.weights[i], R.Wf[i] = wf + off[i];
-    M.Wf[i] = wf + off[i], M.b[i] = d.biases[i];
-  }
-  R.w_in_out = d.w_in_out;
   M.hidden_act = d.hidden_act, M.out_act = d.out_act;
-  const int act = (d.hidden_act >= 8 || d.out_act >= 8) ? 2 : d.hidden_act;  // instantiation, see act_apply
+  act = (d.hidden_act >= 8 || d.out_act >= 8) ? 2 : d.hidden_act;
   const int nt_last = round_up(d.dims[d.n_layers], 16) / 16;
   // the table variant's main-path output layer (>= 4 n-tiles) parks its raw sums in the buffer as well
   if (act == 2 && nt_last >= 4 && d.dims[d.n_layers] > maxd) maxd = d.dims[d.n_layers];
@@ -397,10 +430,27 @@ hipError_t launch_mlp_f32(const iqlhip_mlp_desc &d, const float *x, int64_t n, i
     M.drop_thr = thr >= 4294967295.0 ? 0xffffffffu : (thr < 1.0 ? 1u : (uint32_t)thr);
     M.drop_scale = 1.0f / (float)(1.0 - (double)d.dropout_p);
   }
-  hipLaunchKernelGGL(k_mlp_repack, dim3(64, d.n_layers), dim3(256), 0, st, R);
   // the activations [64][lda], or the partial tiles of a k-split output layer (4 waves x <= 3 n-tiles)
-  size_t sm = (size_t)MROWS * M.lda * sizeof(float);
+  sm = (size_t)MROWS * M.lda * sizeof(float);
   if (nt_last < 4 && sm < (size_t)4 * nt_last * 4 * 64 * 16) sm = (size_t)4 * nt_last * 4 * 64 * 16;
+}
+
+hipError_t launch_mlp_f32(const iqlhip_mlp_desc &d, const float *x, int64_t n, int x_stride, float *out,
+                          int out_stride, hipStream_t st) {
+  MlpArgs M;
+  int act, maxd;
+  size_t sm;
+  mlp_geometry(d, M, act, sm, maxd);
+  const size_t total = mlp_image_offset(d, d.n_layers);
+  float *wf = nullptr;  // stream-ordered scratch for the fragment-major images (<= 8 x 256 KB)
+  hipError_t e = hipMallocAsync((void **)&wf, total * sizeof(float), st);
+  if (e != hipSuccess) return e;
+  for (int i = 0; i < d.n_layers; ++i) M.Wf[i] = wf + mlp_image_offset(d, i), M.b[i] = d.biases[i];
+  e = launch_mlp_repack(d, wf, st);
+  if (e != hipSuccess) {
+    (void)hipFreeAsync(wf, st);
+    return e;
+  }
   bool wide = false;
   for (int i = 0; i <= d.n_layers; ++i) wide |= d.dims[i] > 256;
   if (wide) {
@@ -428,6 +478,99 @@ hipError_t launch_mlp_f32(const iqlhip_mlp_desc &d, const float *x, int64_t n, i
   }
   (void)hipFreeAsync(wf, st);
   return e;
+}
+
+}  // namespace iqlhip
+
+// ---- iqlhip_mlp_set: M MLPs of one shape, repacked once into one allocation ----
+// Member m's block starts m * stride floats into `mem`: the fragment-major images of its layers as
+// launch_mlp_repack lays them out, then every layer's bias padded to 16 floats.
+struct iqlhip_mlp_set {
+  iqlhip::MlpSetArgs S;  // S.A: member 0's pointers
+  int act;               // kernel instantiation
+  size_t sm;             // dynamic LDS bytes
+  int M;
+  int device;  // the allocation's, and the one the kernel attribute was set on
+  float *mem;
+};
+
+namespace iqlhip {
+
+struct BiasArgs {
+  int32_t n_layers;
+  int32_t dims[IQLHIP_MLP_MAX_LAYERS + 1];
+  const float *src[IQLHIP_MLP_MAX_LAYERS];
+  float *dst[IQLHIP_MLP_MAX_LAYERS];
+};
+
+__global__ void k_mlp_set_bias(const BiasArgs B) {
+  const int l = blockIdx.x;
+  if (l >= B.n_layers) return;
+  const int N = B.dims[l + 1], Np = round_up(N, 16);
+  for (int c = threadIdx.x; c < Np; c += blockDim.x) B.dst[l][c] = c < N ? B.src[l][c] : 0.f;
+}
+
+// The caller (api.hip) has checked the members: one shape, every width <= 256, no dropout, no null pointer.
+hipError_t mlp_set_create(const iqlhip_mlp_desc *const *descs, int M, iqlhip_mlp_set **out, hipStream_t st) {
+  const iqlhip_mlp_desc &d0 = *descs[0];
+  const int L = d0.n_layers;
+  const size_t image = mlp_image_offset(d0, L);
+  size_t boff[IQLHIP_MLP_MAX_LAYERS], floats = image;
+  for (int l = 0; l < L; ++l) boff[l] = floats, floats += round_up(d0.dims[l + 1], 16);
+  const size_t stride = (floats + 63) / 64 * 64;  // members on 256-byte boundaries
+  iqlhip_mlp_set *s = new (std::nothrow) iqlhip_mlp_set;
+  if (!s) return hipErrorOutOfMemory;
+  int maxd;
+  mlp_geometry(d0, s->S.A, s->act, s->sm, maxd);
+  s->S.stride = (int64_t)stride, s->S.R = 0, s->M = M, s->mem = nullptr;
+  hipError_t e = hipGetDevice(&s->device);
+  if (e == hipSuccess) e = hipMalloc((void **)&s->mem, stride * (size_t)M * sizeof(float));
+  for (int m = 0; m < M && e == hipSuccess; ++m) {
+    float *base = s->mem + (size_t)m * stride;
+    e = launch_mlp_repack(*descs[m], base, st);
+    if (e != hipSuccess) break;
+    BiasArgs B;
+    B.n_layers = L;
+    for (int l = 0; l <= L; ++l) B.dims[l] = d0.dims[l];
+    for (int l = 0; l < L; ++l) B.src[l] = descs[m]->biases[l], B.dst[l] = base + boff[l];
+    hipLaunchKernelGGL(k_mlp_set_bias, dim3(L), dim3(256), 0, st, B);
+    e = hipGetLastError();
+  }
+  for (int l = 0; l < L; ++l) s->S.A.Wf[l] = s->mem + mlp_image_offset(d0, l), s->S.A.b[l] = s->mem + boff[l];
+  if (e == hipSuccess) {  // once, here: the forward is one launch and nothing else
+    auto kern = s->act == 0 ? k_mlp_set<0> : s->act == 1 ? k_mlp_set<1> : k_mlp_set<2>;
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            160 * 1024);
+  }
+  // a snapshot: the sources have been read when this returns
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) {
+    if (s->mem) (void)hipFree(s->mem);
+    delete s;
+    return e;
+  }
+  *out = s;
+  return hipSuccess;
+}
+
+hipError_t mlp_set_destroy(iqlhip_mlp_set *s) {
+  const hipError_t e = hipFree(s->mem);  // (waits for the work that still reads it)
+  delete s;
+  return e;
+}
+
+void mlp_set_shape(const iqlhip_mlp_set *s, int *M, int *in, int *out, int *device) {
+  *device = s->device, *M = s->M, *in = s->S.A.dims[0], *out = s->S.A.dims[s->S.A.n_layers];
+}
+
+hipError_t launch_mlp_set(const iqlhip_mlp_set *s, const float *x, int R, int x_stride, float *out, int out_stride,
+                          hipStream_t st) {
+  MlpSetArgs S = s->S;
+  S.R = R;
+  auto kern = s->act == 0 ? k_mlp_set<0> : s->act == 1 ? k_mlp_set<1> : k_mlp_set<2>;
+  hipLaunchKernelGGL(kern, dim3((unsigned)(((int64_t)R + MROWS - 1) / MROWS), (unsigned)s->M), dim3(256), s->sm, st, S, x,
+                     x_stride, out, out_stride);
+  return hipGetLastError();
 }
 
 }  // namespace iqlhip

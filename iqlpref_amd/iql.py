@@ -342,14 +342,10 @@ class MLP(nn.Module):
         return y.squeeze(-1) if self._squeeze else y
 
 
-def mlp_forward_f32(weights, biases, x, *, w_in_out, hidden_act=0, out_act=0, dropout=None) -> torch.Tensor:
-    """Exact-fp32 MLP forward of ``x`` [n, in] on the GPU (iqlhip_mlp_forward).
-    ``dropout`` = (p, seed, call): nn.Dropout(p) behind every hidden activation (train mode)."""
-    lib = _lib.load()
-    dev = _lib.require_gpu(x.device)
-    lead = x.shape[:-1]
-    x2 = x.detach().reshape(-1, x.shape[-1]).to(torch.float32).contiguous()
-    n = x2.shape[0]
+def mlp_desc(weights, biases, *, w_in_out, hidden_act=0, out_act=0, dropout=None):
+    """The ``iqlhip_mlp_desc`` of an MLP given by its weight and bias tensors, and the fp32 contiguous
+    tensors its pointers refer to (to be kept alive as long as the descriptor is used).  ``dropout`` =
+    (p, seed, call) as ``mlp_forward_f32`` takes it; None: the eval-mode forward."""
     d = _lib.MlpDesc()
     d.n_layers = len(weights)
     keep = []
@@ -363,6 +359,18 @@ def mlp_forward_f32(weights, biases, x, *, w_in_out, hidden_act=0, out_act=0, dr
     d.w_in_out, d.hidden_act, d.out_act = int(w_in_out), hidden_act, out_act
     if dropout is not None:
         d.dropout_p, d.dropout_seed, d.dropout_call = dropout
+    return d, keep
+
+
+def mlp_forward_f32(weights, biases, x, *, w_in_out, hidden_act=0, out_act=0, dropout=None) -> torch.Tensor:
+    """Exact-fp32 MLP forward of ``x`` [n, in] on the GPU (iqlhip_mlp_forward).
+    ``dropout`` = (p, seed, call): nn.Dropout(p) behind every hidden activation (train mode)."""
+    lib = _lib.load()
+    dev = _lib.require_gpu(x.device)
+    lead = x.shape[:-1]
+    x2 = x.detach().reshape(-1, x.shape[-1]).to(torch.float32).contiguous()
+    n = x2.shape[0]
+    d, keep = mlp_desc(weights, biases, w_in_out=w_in_out, hidden_act=hidden_act, out_act=out_act, dropout=dropout)
     if x2.shape[1] != d.dims[0]:
         raise RuntimeError(f"input width {x2.shape[1]} does not match the first layer ({d.dims[0]})")
     n_out = d.dims[len(weights)]

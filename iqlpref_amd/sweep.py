@@ -82,10 +82,12 @@ def _flavour(spec: Mapping):
     return TrainConfig, load_config
 
 
-def sweep_axes(spec: Mapping) -> List[Tuple[str, List[Any]]]:
+def sweep_axes(spec: Mapping, known=None,
+               what: str = "TrainConfig fields nor config_path") -> List[Tuple[str, List[Any]]]:
     """The grid's parameters in file order: [(name, [values...])].  Only ``method: grid`` with
     ``{value: x}`` / ``{values: [...]}`` entries; every name must be a field of the flavour's TrainConfig
-    (``is_custom_sweep``) or ``config_path`` (all unknown names are reported together)."""
+    (``is_custom_sweep``) or ``config_path`` (all unknown names are reported together).  ``known``: another
+    set of accepted names (``posthoc.expand_eval_sweep``: the fields of its EvalConfig), ``what`` names it."""
     method = spec.get("method")
     if method != "grid":
         raise ValueError(f"sweep method {method!r}: only 'grid' is supported (random / bayes search needs the "
@@ -96,7 +98,8 @@ def sweep_axes(spec: Mapping) -> List[Tuple[str, List[Any]]]:
     params = spec.get("parameters") or {}
     if not isinstance(params, Mapping):
         raise ValueError("'parameters' must map names to {value: x} or {values: [...]}")
-    known = {f.name for f in fields(_flavour(spec)[0])} | {"config_path"}
+    if known is None:
+        known = {f.name for f in fields(_flavour(spec)[0])} | {"config_path"}
     axes, unknown = [], []
     for name, entry in params.items():
         if not isinstance(entry, Mapping) or len(entry) != 1 or next(iter(entry)) not in ("value", "values"):
@@ -114,7 +117,7 @@ def sweep_axes(spec: Mapping) -> List[Tuple[str, List[Any]]]:
             unknown.append(name)
         axes.append((name, vals))
     if unknown:
-        raise ValueError(f"unknown sweep parameters (neither TrainConfig fields nor config_path): {', '.join(unknown)}")
+        raise ValueError(f"unknown sweep parameters (neither {what}): {', '.join(unknown)}")
     return axes
 
 

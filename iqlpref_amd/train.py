@@ -17,41 +17,12 @@ import torch
 from . import _resume, _window_loop
 from . import distributed as D
 from . import prep
+from ._env_worker import NormalizedEnv as _NormalizedEnv, wrap_env  # noqa: F401 (ref:140-161; re-exported)
 from ._offline_loop import checkpoint_dirs, default_logger, tag
 from .iql import (DeterministicPolicy, EnsembleQ, GaussianPolicy, ImplicitQLearning, ReplayBuffer, TrainConfig, TwinQ,
                   ValueFunction, compute_mean_std, normalize_states, set_seed)
 from .relabel import (load_mlp_reward_model, load_pt_reward_model, modify_reward, qlearning_dataset_bnn,
                       qlearning_dataset_mr, qlearning_dataset_mr_ensemble, qlearning_dataset_pt)
-
-
-class _NormalizedEnv:
-    """What the reference builds from gym.wrappers.TransformObservation / TransformReward
-    (ref:140-161), without importing gym: observations are z-scored with the dataset
-    statistics on the way out of reset() / step(), rewards are scaled.  Everything else is the
-    wrapped environment's."""
-
-    def __init__(self, env, state_mean, state_std, reward_scale):
-        self.env = env
-        self._mean, self._std, self._scale = state_mean, state_std, reward_scale
-
-    def __getattr__(self, name):
-        return getattr(self.env, name)
-
-    def _obs(self, obs):
-        return (obs - self._mean) / self._std  # the epsilon is already part of state_std
-
-    def reset(self, **kw):
-        out = self.env.reset(**kw)
-        return (self._obs(out[0]),) + tuple(out[1:]) if isinstance(out, tuple) else self._obs(out)
-
-    def step(self, action):
-        obs, reward, *rest = self.env.step(action)
-        return (self._obs(obs), reward * self._scale if self._scale != 1.0 else reward, *rest)
-
-
-def wrap_env(env, state_mean=0.0, state_std=1.0, reward_scale: float = 1.0):
-    """ref:140-161: normalised observations (and scaled rewards) around ``env``."""
-    return _NormalizedEnv(env, state_mean, state_std, reward_scale)
 
 
 def _gym_vector_env(env_name: str, seeds: Sequence[int], state_mean, state_std):
