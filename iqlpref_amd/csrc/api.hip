@@ -13,6 +13,7 @@
 
 #include "../../include/iqlhip.h"
 #include "common.h"
+#include "host_plan.h"
 #include "iql_deep.h"
 #include "iql_step.h"
 #include "step_math.h"
@@ -21,7 +22,7 @@ namespace iqlhip {
 // the general layer-wise step (iql_deep.hip)
 struct DeepTrainer;
 bool deep_shape_ok(const iqlhip_trainer_config &, int n_hidden, const char **why);
-hipError_t deep_create(DeepTrainer **, const iqlhip_trainer_config &, int n_hidden, const iqlhip_arenas &,
+hipError_t deep_create(DeepTrainer **, const iqlhip_trainer_config &, const StepShape &, const iqlhip_arenas &,
                        const int64_t *offsets);
 void deep_destroy(DeepTrainer *);
 hipError_t deep_sync_weights(DeepTrainer *, hipStream_t);
@@ -292,18 +293,48 @@ struct Throttle {
   }
 };
 
+// Small uploads travel through a ring of N pinned host slots (a pageable source makes hipMemcpyAsync
+// host-blocking, which serialised the streams of a SeedGroup); a slot is reused only after the copy that
+// read it has completed (its event).
+template <int N>
+struct PinnedRing {
+  char *host[N] = {};
+  hipEvent_t ev[N] = {};
+  bool used[N] = {};
+  int head = 0;
+  // the next slot, free to be written: `cap` bytes, allocated on first use
+  int next(size_t cap, char **slot) {
+    if (!host[head]) {
+      HIP_TRY(hipHostMalloc((void **)&host[head], cap, hipHostMallocDefault));
+      HIP_TRY(hipEventCreateWithFlags(&ev[head], hipEventDisableTiming));
+    }
+    if (used[head]) HIP_TRY(hipEventSynchronize(ev[head]));
+    *slot = host[head];
+    return 0;
+  }
+  // the first `bytes` of that slot to `dst`, in one copy
+  int send(void *dst, size_t bytes, hipStream_t st) {
+    const int slot = head;
+    head = (slot + 1) % N;
+    HIP_TRY(hipMemcpyAsync(dst, host[slot], bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(ev[slot], st));
+    used[slot] = true;
+    return 0;
+  }
+  void destroy() {
+    for (int k = 0; k < N; ++k) {
+      if (ev[k]) (void)hipEventDestroy(ev[k]);
+      if (host[k]) (void)hipHostFree(host[k]);
+      ev[k] = nullptr, host[k] = nullptr, used[k] = false;
+    }
+  }
+};
+
 // How steps reach a stream, for one trainer (K = 1) or the K members of a group: what the device copies
 // of the tuned step's arguments hold, the cached hipGraph of `graph_unroll` steps, the throttle, the
 // per-kernel timing of the diagnostic mode and the launch counters.  Both step kinds issue through it.
 struct StepQueue {
-  // DevArgs travel through a small ring of pinned host slots, [K] each (a pageable source makes
-  // hipMemcpyAsync host-blocking, which serialised the streams of a SeedGroup); a slot is
-  // reused only after the copy that read it has completed (its event)
-  static constexpr int ARG_RING = 8;
-  DevArgs *harg[ARG_RING] = {};
-  hipEvent_t harg_ev[ARG_RING] = {};
-  bool harg_used[ARG_RING] = {};
-  int harg_head = 0;
+  PinnedRing<8> arg_ring;  // of [K] DevArgs
   DevArgs dev_args[IQLHIP_MAX_GROUP];  // what the device copies hold (see `continues`) ...
   bool dev_args_valid = false;  // ... and whether the batch of step total_it is already staged for them
   hipGraphExec_t gexec = nullptr;
@@ -321,18 +352,11 @@ struct StepQueue {
 
   // K DevArgs through one pinned slot, in one copy to `dst`
   int push(const DevArgs *want, int K, DevArgs *dst, hipStream_t st) {
-    const int slot = harg_head;
-    harg_head = (slot + 1) % ARG_RING;
-    if (!harg[slot]) {
-      HIP_TRY(hipHostMalloc((void **)&harg[slot], sizeof(DevArgs) * K, hipHostMallocDefault));
-      HIP_TRY(hipEventCreateWithFlags(&harg_ev[slot], hipEventDisableTiming));
-    }
-    if (harg_used[slot]) HIP_TRY(hipEventSynchronize(harg_ev[slot]));
-    for (int k = 0; k < K; ++k) harg[slot][k] = dev_args[k] = want[k];
-    HIP_TRY(hipMemcpyAsync(dst, harg[slot], sizeof(DevArgs) * K, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipEventRecord(harg_ev[slot], st));
-    harg_used[slot] = true;
-    return 0;
+    char *slot;
+    if (int rc = arg_ring.next(sizeof(DevArgs) * K, &slot)) return rc;
+    DevArgs *h = reinterpret_cast<DevArgs *>(slot);
+    for (int k = 0; k < K; ++k) h[k] = dev_args[k] = want[k];
+    return arg_ring.send(dst, sizeof(DevArgs) * K, st);
   }
   // the cached graph holds addresses (descriptors, arguments): whoever moves them drops it
   void drop_graph() {
@@ -411,10 +435,7 @@ struct StepQueue {
   }
   void destroy() {
     drop_graph();
-    for (int k = 0; k < ARG_RING; ++k) {
-      if (harg_ev[k]) (void)hipEventDestroy(harg_ev[k]);
-      if (harg[k]) (void)hipHostFree(harg[k]);
-    }
+    arg_ring.destroy();
     for (auto &e : ev)
       if (e) (void)hipEventDestroy(e);
     throttle.destroy();
@@ -425,17 +446,12 @@ struct StepQueue {
 //   [K] DeepArgs | [K] DeepCtr | [CAP][K] AdamCoef
 // A call is cut into chunks of at most CAP steps; ahead of each, the block, the counters (= the chunk's
 // first step) and the Adam coefficients of its steps -- computed HERE in double, as the plain launches
-// always had them -- go up in ONE copy from a ring of pinned slots (a slot is reused only after the copy
-// that read it has completed: its event).
+// always had them -- go up in ONE copy from a ring of pinned slots.
 struct DeepRing {
-  static constexpr int RING = 4;
   static constexpr int64_t CAP = 1024;
   int K = 0;
   char *dev = nullptr;
-  char *host[RING] = {};
-  hipEvent_t ev[RING] = {};
-  bool used[RING] = {};
-  int head = 0;
+  PinnedRing<4> ring;
   size_t head_bytes() const { return (size_t)K * (sizeof(DeepArgs) + sizeof(DeepCtr)); }
   size_t bytes(int64_t n) const { return head_bytes() + (size_t)n * K * sizeof(AdamCoef); }
   DeepArgs *dargs() const { return reinterpret_cast<DeepArgs *>(dev); }
@@ -447,53 +463,51 @@ struct DeepRing {
     return e != hipSuccess ? e : hipMemset(dev, 0, bytes(CAP));
   }
   void destroy() {
-    for (int k = 0; k < RING; ++k) {
-      if (ev[k]) (void)hipEventDestroy(ev[k]);
-      if (host[k]) (void)hipHostFree(host[k]);
-      ev[k] = nullptr, host[k] = nullptr;
-    }
+    ring.destroy();
     if (dev) (void)hipFree(dev);
     dev = nullptr;
   }
+};
+
+// Where a launch of the tuned step finds one trainer's descriptor, arguments, counters and update items
+struct Slots {
+  TrainerDesc *desc = nullptr;  // device copy of D (kernels read it through L2, not the kernarg segment)
+  DevArgs *args = nullptr;
+  DevCtr *ctr = nullptr;
+  UpdItem *items = nullptr;
+  int n_items = 0;
+};
+
+// What the tuned three-kernel step of one trainer works on (shapes it is built for: is_deep)
+struct TunedTrainer {
+  TrainerDesc D;
+  bool bf16 = false;
+  void *ws = nullptr;
+  // `own`: the slots of the trainer's workspace; `cur`: the ones in use -- its row of a group's contiguous
+  // arrays while the trainer is a member of one (attach / detach), else `own`
+  Slots own, cur;
+  // host copy of the update kernel's work items, per trained net: first the items of the lower half of
+  // every layer, then the upper half (n_half0 of them in the first part) -- tables are dealt from these
+  std::vector<UpdItem> net_items[MAX_TRAIN];
+  int n_half0[MAX_TRAIN] = {};
+  // a batch_size that is no multiple of 16: the kernels index idx[] and drop_keep[] with their
+  // padded row count D.B, the caller's arrays have batch_size rows a step -- copies with D.B rows a step, for
+  // one chunk of a call's steps at a time (pad_inputs); grown on demand
+  void *pad_idx = nullptr, *pad_keep = nullptr;
+  size_t pad_idx_bytes = 0, pad_keep_bytes = 0;
 };
 
 struct iqlhip_trainer {
   iqlhip_trainer_config cfg;
   iqlhip_arenas arenas;
   int device = -1;  // where the parameter arena lives
-  // shapes outside the tuned step's (n_hidden != 2 or another width): the general layer-wise step;
-  // of the members below only cfg, the learning rates, total_it, `queue` (its graph, timing events,
-  // throttle and counters; not the DevArgs ring), `group` and batch_rows are in use then
+  // one of the two step kinds: the tuned one, or (n_hidden != 2 or another width) the general layer-wise
+  // one of iql_deep.hip with the ring its arguments travel through
+  TunedTrainer *tuned = nullptr;
   DeepTrainer *deep = nullptr;
   DeepRing deep_ring;
-  TrainerDesc D;
-  bool bf16;
-  void *ws = nullptr;
-  size_t ws_bytes = 0;
-  TrainerDesc *ddesc = nullptr;  // device copy of D (kernels read it through L2, not the kernarg segment)
-  DevArgs *dargs = nullptr;
-  DevCtr *dctr = nullptr;
-  UpdItem *ditems = nullptr;
-  int n_items = 0;      // of the table `ditems` points to (the group's while the trainer is a member of one)
-  int own_n_items = 0;  // of the trainer's own table
-  // host copy of the update kernel's work items, per trained net: first the items of the lower half of
-  // every layer, then the upper half (n_half0 of them in the first part) -- tables are dealt from these
-  std::vector<UpdItem> net_items[MAX_TRAIN];
-  int n_half0[MAX_TRAIN] = {};
-  // the slots of this trainer's own workspace; ddesc / dargs / dctr / ditems point into a
-  // group's contiguous arrays while the trainer is a member of one (iqlhip_group_create)
-  TrainerDesc *own_ddesc = nullptr;
-  DevArgs *own_dargs = nullptr;
-  DevCtr *own_dctr = nullptr;
-  UpdItem *own_ditems = nullptr;
   struct iqlhip_group *group = nullptr;
-
-  float *batch_rows = nullptr;  // [B][stride] staging for iqlhip_train_batch
-  // a batch_size that is no multiple of 16 (tuned step): the kernels index idx[] and drop_keep[] with their
-  // padded row count D.B, the caller's arrays have batch_size rows a step -- copies with D.B rows a step, for
-  // one chunk of a call's steps at a time (pad_inputs); grown on demand
-  void *pad_idx = nullptr, *pad_keep = nullptr;
-  size_t pad_idx_bytes = 0, pad_keep_bytes = 0;
+  float *batch_rows = nullptr;  // [B][stride] staging for iqlhip_train_batch (tuned: a block of the workspace)
   int64_t total_it = 0;
   double lr_q, lr_v, lr_a_base;
   StepQueue queue;  // of the trainer's own calls (K = 1)
@@ -502,10 +516,13 @@ struct iqlhip_trainer {
 static_assert(MAX_CRITICS == IQLHIP_MAX_CRITICS, "iql_step.h and iqlhip.h disagree");
 static_assert(IQLHIP_N_TENSORS == 2 * DEEP_MAX_LIN * MAX_TRAIN + 1, "offset table size");
 static_assert(IQLHIP_MAX_HIDDEN + 1 == DEEP_MAX_LIN, "iql_deep.h and iqlhip.h disagree");
-// number of critics: 0 in the config means the reference's TwinQ
-static int n_critics(const iqlhip_trainer_config &c) { return c.n_critics > 0 ? c.n_critics : 2; }
-// hidden layers: 0 in the config means the reference's default (ref:458-459, 519, 538)
-static int n_hidden(const iqlhip_trainer_config &c) { return c.n_hidden > 0 ? c.n_hidden : 2; }
+// what both step kinds derive from a config: defaults resolved, net dimensions, dropout constants (host_plan.h)
+static StepShape step_shape(const iqlhip_trainer_config &c) {
+  return make_step_shape(c.state_dim, c.action_dim, c.n_critics, c.n_hidden, c.dropout_p,
+                         c.precision == IQLHIP_PREC_BF16);
+}
+static int n_critics(const iqlhip_trainer_config &c) { return step_shape(c).E; }
+static int n_hidden(const iqlhip_trainer_config &c) { return step_shape(c).NH; }
 // which step runs this shape: the tuned three-kernel one or the general layer-wise one
 static bool is_deep(const iqlhip_trainer_config &c) {
   // (tests: the general step on a shape the tuned one takes)
@@ -543,23 +560,18 @@ struct Layout {
   int64_t n_params, n_target;      // arena elements (with alignment padding)
   int64_t true_params, true_target;  // trained scalars (SURVEY 8d byte model)
 };
-static void net_dims(const iqlhip_trainer_config &c, int net, int *in, int *out) {
-  const int E = n_critics(c);
-  *in = net < E ? c.state_dim + c.action_dim : c.state_dim;
-  *out = (net == E + 1) ? c.action_dim : 1;
-}
 static Layout make_layout(const iqlhip_trainer_config &c) {
   // every tensor starts on a 128-byte line: rows of the H-wide matrices and the flat layer-1
   // strips are then streamed in whole, aligned lines
   constexpr int64_t ALIGN = 32;
   Layout L;
   int64_t o = 0, cnt = 0;
-  const int H = c.hidden_dim, NL = n_hidden(c) + 1;
-  const int E = n_critics(c), ntrain = E + 2;
+  const StepShape sh = step_shape(c);
+  const int H = c.hidden_dim, NL = sh.NH + 1;
+  const int E = sh.E, ntrain = sh.ntrain();
   for (int k = 0; k < IQLHIP_N_TENSORS; ++k) L.off[k] = -1;
   for (int n = 0; n < ntrain; ++n) {
-    int in, out;
-    net_dims(c, n, &in, &out);
+    const int in = sh.in_dim(n), out = sh.out_dim(n);
     for (int l = 0; l < NL; ++l) {
       const int64_t rows = l == NL - 1 ? out : H, cols = l == 0 ? in : H;
       const int64_t sz[2] = {rows * cols, rows};  // W_l [rows][cols], b_l [rows]
@@ -612,13 +624,6 @@ extern "C" int iqlhip_step_cost(const iqlhip_trainer_config *cfg, double *bytes,
   return 0;
 }
 
-template <typename T>
-static T *carve(char *&p, size_t n) {
-  T *r = reinterpret_cast<T *>(p);
-  p += (n * sizeof(T) + 255) / 256 * 256;
-  return r;
-}
-
 // The update kernel's item table is XCD-major: block b runs on XCD b & 7 (round-robin dispatch), so
 // slot i of the table belongs to XCD i & 7, row i >> 3.  `per_xcd` lists what each XCD works on; rows
 // are padded with idle slots (net = -1), which gather the next step's batch: they are numbered
@@ -663,7 +668,7 @@ static std::vector<UpdItem> flatten_table(const std::vector<UpdItem> (&per_xcd)[
 // 107.7k -- the rotation gives every XCD one network of every kind only for multiples of eight members;
 // smaller groups keep the one-seed table.  Dealt in order (E > 2, one seed): E = 4 at batch 1024 35.9k ->
 // 37.5k steps/s, E = 8 at batch 256 41.0k -> 42.4k.
-static void deal_items(const iqlhip_trainer *t, int member, int group_size, std::vector<UpdItem> (&per_xcd)[8]) {
+static void deal_items(const TunedTrainer *t, int member, int group_size, std::vector<UpdItem> (&per_xcd)[8]) {
   const int NT = t->D.ntrain;
   const bool group = group_size > 1;
   const bool whole = group && group_size % 8 == 0;
@@ -707,72 +712,53 @@ static void deal_items(const iqlhip_trainer *t, int member, int group_size, std:
   }
 }
 
-extern "C" int iqlhip_trainer_create(iqlhip_trainer **out, const iqlhip_trainer_config *cfg,
-                                     const iqlhip_arenas *ar) {
-  if (!out) return fail(IQLHIP_ERR_INVALID, "null out");
-  if (int e = check_cfg(cfg)) return e;
-  if (!ar || !ar->params || !ar->exp_avg || !ar->exp_avg_sq || !ar->target)
-    return fail(IQLHIP_ERR_INVALID, "null arena pointer");
-  HIP_TRY(prepare_step_kernels());
-  iqlhip_trainer *t = new (std::nothrow) iqlhip_trainer();
-  if (!t) return fail(IQLHIP_ERR_NOMEM, "host allocation failed");
-  t->cfg = *cfg;
-  t->arenas = *ar;
-  if (hipPointerAttribute_t at; hipPointerGetAttributes(&at, ar->params) == hipSuccess)
-    t->device = at.device;
-  else
-    (void)hipGetLastError();
-  t->bf16 = cfg->precision == IQLHIP_PREC_BF16;
-  t->lr_q = cfg->lr_q, t->lr_v = cfg->lr_v, t->lr_a_base = cfg->lr_actor;
-  const Layout L = make_layout(*cfg);
-  if (is_deep(*cfg)) {
-    memset(&t->D, 0, sizeof(t->D));
-    t->D.E = n_critics(*cfg);
-    const size_t rows_bytes = (size_t)cfg->batch_size * iqlhip_replay_row_stride(cfg->state_dim, cfg->action_dim) * 4;
-    hipError_t e = deep_create(&t->deep, *cfg, n_hidden(*cfg), *ar, L.off);
-    if (e == hipSuccess && (e = hipMalloc((void **)&t->batch_rows, rows_bytes)) != hipSuccess) deep_destroy(t->deep);
-    if (e == hipSuccess && (e = t->deep_ring.init(1)) != hipSuccess) {
-      deep_destroy(t->deep);
-      (void)hipFree(t->batch_rows);
-      t->deep_ring.destroy();
-    }
-    if (e != hipSuccess) {
-      delete t;
-      return fail(e == hipErrorOutOfMemory ? IQLHIP_ERR_NOMEM : IQLHIP_ERR_HIP, "general step: %s", hipGetErrorString(e));
-    }
-    *out = t;
-    return 0;
-  }
+// The pointer fields of a work item: a function of (net, layer) and the placed descriptor.
+static void item_pointers(UpdItem &it, const TrainerDesc &D, int es) {
+  if (it.net < 0) return;  // (an idle slot)
+  const TrainNet &N = D.net[it.net];
+  const int L = it.layer;
+  it.wc = N.wc[L], it.tc = N.has_target ? N.tc[L] : nullptr, it.w2ct = (L == 1) ? N.w2ct : nullptr;
+  it.w3t = (L == 2) ? N.w3t : nullptr;
+  const size_t plane = (size_t)D.H * D.BP * es;
+  it.Xsrc = (L == 0) ? D.xT : reinterpret_cast<char *>(D.hT) + (size_t)(it.net * 2 + (L - 1)) * plane;
+  it.Zsrc = (L == 0)   ? reinterpret_cast<char *>(D.dz1T) + (size_t)it.net * plane
+            : (L == 1) ? reinterpret_cast<char *>(D.dz2T) + (size_t)it.net * plane
+                       : reinterpret_cast<char *>(D.dz3T) + (size_t)it.net * D.opmax * D.BP * es;
+}
+
+static void tuned_destroy(TunedTrainer *u) {
+  if (!u) return;
+  (void)hipFree(u->ws);
+  (void)hipFree(u->pad_idx);
+  (void)hipFree(u->pad_keep);
+  delete u;
+}
+
+// The tuned step of trainer t (released with it: trainer_release).
+static int tuned_create(iqlhip_trainer *t, const StepShape &sh, const Layout &L) {
+  const iqlhip_trainer_config *cfg = &t->cfg;
+  const iqlhip_arenas *ar = &t->arenas;
+  TunedTrainer *u = t->tuned = new (std::nothrow) TunedTrainer();
+  if (!u) return fail(IQLHIP_ERR_NOMEM, "host allocation failed");
+  u->bf16 = cfg->precision == IQLHIP_PREC_BF16;
   // B: the rows every kernel works on, batch_size rounded up to whole 16-row slabs; rows [batch_size, B) are
   // padding, gathered like the others and kept out of the losses by the counted kernels (D.NB)
   const int S = cfg->state_dim, A = cfg->action_dim, H = cfg->hidden_dim, B = round_up(cfg->batch_size, 16);
-  const int es = t->bf16 ? 2 : 4, KM = t->bf16 ? 32 : 16;
-  TrainerDesc &D = t->D;
+  const int es = u->bf16 ? 2 : 4, KM = u->bf16 ? 32 : 16;
+  TrainerDesc &D = u->D;
   memset(&D, 0, sizeof(D));
   D.S = S, D.A = A, D.H = H, D.B = B, D.BP = round_up(B, 32), D.NB = cfg->batch_size;
-  const int E = n_critics(*cfg), NT = E + 2, NF = 2 * E + 3;
-  D.E = E, D.ntrain = NT, D.nfwd = NF, D.net_v = E, D.net_a = E + 1;
-  D.out_v = E, D.out_qt = E + 1, D.out_nv = 2 * E + 1, D.out_mean = 2 * E + 2;
+  const int E = sh.E, NT = sh.ntrain();
+  D.E = E, D.ntrain = NT, D.nfwd = sh.nfwd(), D.net_v = sh.net_v(), D.net_a = sh.net_a();
+  D.out_v = sh.out_v(), D.out_qt = sh.out_qt(), D.out_nv = sh.out_nv(), D.out_mean = sh.out_mean();
   D.two_over_B = 2.0f / (float)B, D.inv_E = 1.0f / (float)E;
   D.OUTW = round_up(D.out_mean + A, 4);
   D.deterministic = cfg->deterministic;
-  D.has_dropout = cfg->dropout_p > 0.f;
+  D.has_dropout = sh.has_dropout;
   D.discount = cfg->discount, D.tau = cfg->tau, D.beta = cfg->beta, D.iql_tau = cfg->iql_tau;
   D.one_m_tau = (float)(1.0 - (double)cfg->tau);
   D.polyak_convex = cfg->polyak_form == 1;
-  if (D.has_dropout) {
-    const float scale = 1.0f / (float)(1.0 - (double)cfg->dropout_p);
-    if (t->bf16) {  // noise.div_(1-p) happens in bf16 under autocast (ATen _dropout_impl)
-      uint32_t u;
-      memcpy(&u, &scale, 4);
-      u = (u + 0x7fffu + ((u >> 16) & 1u)) & 0xffff0000u;
-      memcpy(&D.drop_scale, &u, 4);
-    } else {
-      D.drop_scale = scale;
-    }
-    const double thr = (double)cfg->dropout_p * 4294967296.0;
-    D.drop_thr = thr >= 4294967295.0 ? 0xffffffffu : (uint32_t)thr;
-  }
+  D.drop_scale = sh.drop.scale, D.drop_thr = sh.drop.thr;
   D.beta1 = cfg->adam_beta1, D.beta2 = cfg->adam_beta2, D.eps = cfg->adam_eps;
   D.t_max = cfg->cosine_t_max;
   D.seed = cfg->seed;
@@ -782,83 +768,16 @@ extern "C" int iqlhip_trainer_create(iqlhip_trainer **out, const iqlhip_trainer_
   D.opmax = round_up(A, 16);
   D.xrows = round_up(S + A, 64);
   D.k1max = round_up(S + A, KM);
-  // ---- workspace ----
-  size_t total = 0;
-  auto add = [&](size_t bytes) { total += (bytes + 255) / 256 * 256; };
-  int k1pad[MAX_TRAIN], outpad[MAX_TRAIN], indim[MAX_TRAIN], outdim[MAX_TRAIN];
-  for (int n = 0; n < NT; ++n) {
-    net_dims(*cfg, n, &indim[n], &outdim[n]);
-    k1pad[n] = round_up(indim[n], KM);
-    outpad[n] = round_up(outdim[n], 16);
-    const int copies = (n < E) ? 2 : 1;  // + target copies
-    for (int c = 0; c < copies; ++c) {
-      add((size_t)H * k1pad[n] * es);
-      add((size_t)H * H * es);
-      add((size_t)outpad[n] * H * es);
-    }
-    add((size_t)H * H * es);  // w2ct
-    add((size_t)H * outpad[n] * es);  // w3t
-  }
-  add((size_t)2 * D.xrows * D.BP * es);
-  add((size_t)B * 2 * 4);
-  add((size_t)B * A * 4);
-  add((size_t)NT * 2 * H * D.BP * es);
-  add((size_t)NT * H * D.BP * es);
-  add((size_t)NT * H * D.BP * es);
-  add((size_t)NT * D.opmax * D.BP * es);
-  add((size_t)layer2_parts(H) * B * D.OUTW * 4);
-  add((size_t)NT * (B / 16) * 4);
-  add((size_t)(B / 16) * A * 4);
-  add((size_t)A * 4);
   const int stride = iqlhip_replay_row_stride(S, A);
-  add((size_t)B * stride * 4);
-  add((size_t)B * stride * 4);  // stage_rows
-  add(sizeof(DevArgs));
-  add(sizeof(DevCtr));
-  add(sizeof(TrainerDesc));
-  // update work items (see deal_items / flatten_table): per net, the lower half of every layer first
-  for (int n = 0; n < NT; ++n) {
-    std::vector<UpdItem> half[2];
-    auto put = [&](int layer, int o0, int i0) {
-      UpdItem it;
-      memset(&it, 0, sizeof(it));
-      it.net = n, it.layer = layer, it.o0 = o0, it.i0 = i0;
-      const int rows = layer == 2 ? outpad[n] : H;
-      half[(layer == 2 && rows <= 64) ? ((i0 / 32) & 1) : (o0 >= rows / 2 ? 1 : 0)].push_back(it);
-    };
-    for (int o0 = 0; o0 < H; o0 += 64)
-      for (int i0 = 0; i0 < H; i0 += 32) put(1, o0, i0);
-    for (int o0 = 0; o0 < H; o0 += strip_rows()) put(0, o0, 0);  // layer 1: strips over all in-features
-    for (int o0 = 0; o0 < outpad[n]; o0 += 64)
-      for (int i0 = 0; i0 < H; i0 += 32) put(2, o0, i0);
-    t->n_half0[n] = (int)half[0].size();
-    t->net_items[n] = half[0];
-    t->net_items[n].insert(t->net_items[n].end(), half[1].begin(), half[1].end());
-  }
-  size_t n_slots;
-  {
-    std::vector<UpdItem> per_xcd[8];
-    deal_items(t, 0, 1, per_xcd);  // (sizes only: D.ntrain is set, the pointers are filled in below)
-    size_t depth = 0;
-    n_slots = flatten_table(per_xcd, 0, &depth, (size_t)(B + 15) / 16).size();
-  }
-  t->n_items = t->own_n_items = (int)n_slots;
-  add(n_slots * sizeof(UpdItem));
-
-  if (hipMalloc(&t->ws, total) != hipSuccess) {
-    delete t;
-    return fail(IQLHIP_ERR_NOMEM, "hipMalloc of %zu workspace bytes failed", total);
-  }
-  t->ws_bytes = total;
-  if (hipMemset(t->ws, 0, total) != hipSuccess) {
-    (void)hipFree(t->ws);
-    delete t;
-    return fail(IQLHIP_ERR_HIP, "hipMemset failed");
-  }
-  char *p = reinterpret_cast<char *>(t->ws);
+  D.stage_stride = stride;
+  D.next_off = iqlhip_replay_next_offset(S, A);
+  // the idle slots of the update kernel gather the next step's batch; without them (or with
+  // IQLHIP_NO_PREFETCH, the A/B of tests/test_gpu_step.py) k_stage runs before every step
+  D.prefetch = !getenv("IQLHIP_NO_PREFETCH") ? 1 : 0;  // (every table has idle slots: flatten_table)
   for (int n = 0; n < NT; ++n) {
     TrainNet &N = D.net[n];
-    N.in_dim = indim[n], N.k1pad = k1pad[n], N.out_dim = outdim[n], N.out_pad = outpad[n];
+    N.in_dim = sh.in_dim(n), N.k1pad = round_up(N.in_dim, KM);
+    N.out_dim = sh.out_dim(n), N.out_pad = round_up(N.out_dim, 16);
     N.has_target = n < E;
     for (int k = 0; k < 3; ++k) {
       N.off_w[k] = L.off[n * 6 + 2 * k];
@@ -866,75 +785,92 @@ extern "C" int iqlhip_trainer_create(iqlhip_trainer **out, const iqlhip_trainer_
       N.toff_w[k] = N.has_target ? N.off_w[k] : -1;  // target arena = q1,q2 prefix of the layout
       N.toff_b[k] = N.has_target ? N.off_b[k] : -1;
     }
-    N.wc[0] = carve<char>(p, (size_t)H * k1pad[n] * es);
-    N.wc[1] = carve<char>(p, (size_t)H * H * es);
-    N.wc[2] = carve<char>(p, (size_t)outpad[n] * H * es);
-    if (N.has_target) {
-      N.tc[0] = carve<char>(p, (size_t)H * k1pad[n] * es);
-      N.tc[1] = carve<char>(p, (size_t)H * H * es);
-      N.tc[2] = carve<char>(p, (size_t)outpad[n] * H * es);
-    }
-    N.w2ct = carve<char>(p, (size_t)H * H * es);
-    N.w3t = carve<char>(p, (size_t)H * outpad[n] * es);
   }
-  D.xT = carve<char>(p, (size_t)2 * D.xrows * D.BP * es);
-  D.rd = carve<float>(p, (size_t)B * 2);
-  D.actf = carve<float>(p, (size_t)B * A);
-  D.hT = carve<char>(p, (size_t)NT * 2 * H * D.BP * es);
-  D.dz1T = carve<char>(p, (size_t)NT * H * D.BP * es);
-  D.dz2T = carve<char>(p, (size_t)NT * H * D.BP * es);
-  D.dz3T = carve<char>(p, (size_t)NT * D.opmax * D.BP * es);
-  D.outs = carve<float>(p, (size_t)layer2_parts(H) * B * D.OUTW);
-  D.lossp = carve<float>(p, (size_t)NT * (B / 16));
-  D.lsp = carve<float>(p, (size_t)(B / 16) * A);
-  D.ls_snap = carve<float>(p, (size_t)A);
-  t->batch_rows = carve<float>(p, (size_t)B * stride);
-  D.stage_rows = carve<float>(p, (size_t)B * stride);
-  D.stage_stride = stride;
-  D.next_off = iqlhip_replay_next_offset(S, A);
-  // the idle slots of the update kernel gather the next step's batch; without them (or with
-  // IQLHIP_NO_PREFETCH, the A/B of tests/test_gpu_step.py) k_stage runs before every step
-  D.prefetch = !getenv("IQLHIP_NO_PREFETCH") ? 1 : 0;  // (every table has idle slots: flatten_table)
-  t->own_dargs = t->dargs = carve<DevArgs>(p, 1);
-  t->own_dctr = t->dctr = carve<DevCtr>(p, 1);
-  t->own_ddesc = t->ddesc = carve<TrainerDesc>(p, 1);
-  t->own_ditems = t->ditems = carve<UpdItem>(p, n_slots);
-
-  for (int n_ = 0; n_ < NT; ++n_)
-  for (auto &it : t->net_items[n_]) {
-    const TrainNet &N = D.net[it.net];
-    const int L = it.layer;
-    it.Odim = (L == 2) ? N.out_dim : H;
-    it.Idim = (L == 0) ? N.in_dim : H;
-    it.Opad = (L == 2) ? N.out_pad : H;
-    it.Kw = (L == 0) ? N.k1pad : H;
-    it.has_target = N.has_target;
-    it.group = it.net == D.net_v ? 1 : (it.net == D.net_a ? 2 : 0);
-    it.off_w = N.off_w[L], it.off_b = N.off_b[L], it.toff_w = N.toff_w[L], it.toff_b = N.toff_b[L];
-
-    it.wc = N.wc[L], it.tc = N.has_target ? N.tc[L] : nullptr, it.w2ct = (L == 1) ? N.w2ct : nullptr;
-    it.w3t = (L == 2) ? N.w3t : nullptr;
-    const size_t plane = (size_t)H * D.BP * es;
-    it.Xsrc = (L == 0) ? D.xT : reinterpret_cast<char *>(D.hT) + (size_t)(it.net * 2 + (L - 1)) * plane;
-    it.Zsrc = (L == 0)   ? reinterpret_cast<char *>(D.dz1T) + (size_t)it.net * plane
-              : (L == 1) ? reinterpret_cast<char *>(D.dz2T) + (size_t)it.net * plane
-                         : reinterpret_cast<char *>(D.dz3T) + (size_t)it.net * D.opmax * D.BP * es;
+  // update work items (see deal_items / flatten_table): per net, the lower half of every layer first; their
+  // pointer fields wait for the workspace (item_pointers)
+  for (int n = 0; n < NT; ++n) {
+    const TrainNet &N = D.net[n];
+    std::vector<UpdItem> half[2];
+    auto put = [&](int layer, int o0, int i0) {
+      UpdItem it;
+      memset(&it, 0, sizeof(it));
+      it.net = n, it.layer = layer, it.o0 = o0, it.i0 = i0;
+      it.Odim = (layer == 2) ? N.out_dim : H;
+      it.Idim = (layer == 0) ? N.in_dim : H;
+      it.Opad = (layer == 2) ? N.out_pad : H;
+      it.Kw = (layer == 0) ? N.k1pad : H;
+      it.has_target = N.has_target;
+      it.group = n == D.net_v ? 1 : (n == D.net_a ? 2 : 0);
+      it.off_w = N.off_w[layer], it.off_b = N.off_b[layer], it.toff_w = N.toff_w[layer], it.toff_b = N.toff_b[layer];
+      half[(layer == 2 && it.Opad <= 64) ? ((i0 / 32) & 1) : (o0 >= it.Opad / 2 ? 1 : 0)].push_back(it);
+    };
+    for (int o0 = 0; o0 < H; o0 += 64)
+      for (int i0 = 0; i0 < H; i0 += 32) put(1, o0, i0);
+    for (int o0 = 0; o0 < H; o0 += strip_rows()) put(0, o0, 0);  // layer 1: strips over all in-features
+    for (int o0 = 0; o0 < N.out_pad; o0 += 64)
+      for (int i0 = 0; i0 < H; i0 += 32) put(2, o0, i0);
+    u->n_half0[n] = (int)half[0].size();
+    u->net_items[n] = half[0];
+    u->net_items[n].insert(u->net_items[n].end(), half[1].begin(), half[1].end());
   }
-  std::vector<UpdItem> items;
+  std::vector<UpdItem> items;  // the trainer's own table
   {
     std::vector<UpdItem> per_xcd[8];
-    deal_items(t, 0, 1, per_xcd);
+    deal_items(u, 0, 1, per_xcd);
     items = flatten_table(per_xcd, 0, nullptr, (size_t)(B + 15) / 16);
   }
-  if (items.size() != n_slots || hipMemcpy(t->ditems, items.data(), items.size() * sizeof(UpdItem), hipMemcpyHostToDevice) !=
-      hipSuccess) {
-    (void)hipFree(t->ws);
-    delete t;
+  // ---- workspace: the one list of its blocks, run once to measure and once to place ----
+  auto blocks = [&](WorkspacePlan p) {
+    for (int n = 0; n < NT; ++n) {
+      TrainNet &N = D.net[n];
+      N.wc[0] = p.take<char>((size_t)H * N.k1pad * es);
+      N.wc[1] = p.take<char>((size_t)H * H * es);
+      N.wc[2] = p.take<char>((size_t)N.out_pad * H * es);
+      if (N.has_target) {
+        N.tc[0] = p.take<char>((size_t)H * N.k1pad * es);
+        N.tc[1] = p.take<char>((size_t)H * H * es);
+        N.tc[2] = p.take<char>((size_t)N.out_pad * H * es);
+      }
+      N.w2ct = p.take<char>((size_t)H * H * es);
+      N.w3t = p.take<char>((size_t)H * N.out_pad * es);
+    }
+    D.xT = p.take<char>((size_t)2 * D.xrows * D.BP * es);
+    D.rd = p.take<float>((size_t)B * 2);
+    D.actf = p.take<float>((size_t)B * A);
+    D.hT = p.take<char>((size_t)NT * 2 * H * D.BP * es);
+    D.dz1T = p.take<char>((size_t)NT * H * D.BP * es);
+    D.dz2T = p.take<char>((size_t)NT * H * D.BP * es);
+    D.dz3T = p.take<char>((size_t)NT * D.opmax * D.BP * es);
+    D.outs = p.take<float>((size_t)layer2_parts(H) * B * D.OUTW);
+    D.lossp = p.take<float>((size_t)NT * (B / 16));
+    D.lsp = p.take<float>((size_t)(B / 16) * A);
+    D.ls_snap = p.take<float>((size_t)A);
+    t->batch_rows = p.take<float>((size_t)B * stride);
+    D.stage_rows = p.take<float>((size_t)B * stride);
+    u->own.args = p.take<DevArgs>(1);
+    u->own.ctr = p.take<DevCtr>(1);
+    u->own.desc = p.take<TrainerDesc>(1);
+    u->own.items = p.take<UpdItem>(items.size());
+    return p.end();
+  };
+  const size_t total = blocks(WorkspacePlan());
+  if (hipMalloc(&u->ws, total) != hipSuccess)
+    return fail(IQLHIP_ERR_NOMEM, "hipMalloc of %zu workspace bytes failed", total);
+  if (hipMemset(u->ws, 0, total) != hipSuccess) return fail(IQLHIP_ERR_HIP, "hipMemset failed");
+  blocks(WorkspacePlan(u->ws));
+  u->own.n_items = (int)items.size();
+  u->cur = u->own;
+
+  for (int n = 0; n < NT; ++n)
+    for (auto &it : u->net_items[n]) item_pointers(it, D, es);
+  for (auto &it : items) item_pointers(it, D, es);
+  if (hipMemcpy(u->own.items, items.data(), items.size() * sizeof(UpdItem), hipMemcpyHostToDevice) != hipSuccess)
     return fail(IQLHIP_ERR_HIP, "hipMemcpy of the work items failed");
-  }
 
   // ---- forward evaluations ----
-  auto mk = [&](int f, int net, bool target, int in_off, int out_col, int slot) {
+  const std::vector<EvalSpec> order = eval_order(sh, D.next_off);
+  for (int f = 0; f < (int)order.size(); ++f) {
+    const auto [net, target, in_off, out_col, slot] = order[f];
     FwdNet &F = D.fwd[f];
     const TrainNet &N = D.net[net];
     F.w1c = target ? N.tc[0] : N.wc[0];
@@ -948,36 +884,58 @@ extern "C" int iqlhip_trainer_create(iqlhip_trainer **out, const iqlhip_trainer_
     F.tanh_out = net == D.net_a;
     F.dropout = (net == D.net_a) && D.has_dropout;
     F.stage = f == 0;
-  };
-  // evaluation order: q_e, v, actor, target q_e, next_v (iql_step.h)
-  for (int e = 0; e < E; ++e) mk(e, e, false, 0, e, e);
-  mk(E, D.net_v, false, 0, D.out_v, D.net_v);
-  mk(E + 1, D.net_a, false, 0, D.out_mean, D.net_a);
-  for (int e = 0; e < E; ++e) mk(E + 2 + e, e, true, 0, D.out_qt + e, -1);
-  mk(2 * E + 2, D.net_v, false, D.next_off, D.out_nv, -1);
-
-  if (hipMemcpy(t->ddesc, &t->D, sizeof(TrainerDesc), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(t->ws);
-    delete t;
-    return fail(IQLHIP_ERR_HIP, "hipMemcpy of the descriptor failed");
   }
-  *out = t;
+  if (hipMemcpy(u->own.desc, &D, sizeof(TrainerDesc), hipMemcpyHostToDevice) != hipSuccess)
+    return fail(IQLHIP_ERR_HIP, "hipMemcpy of the descriptor failed");
+  return 0;
+}
+
+// Frees a trainer, finished or partly built (iqlhip_trainer_create's owner).
+static void trainer_release(iqlhip_trainer *t) {
+  t->queue.destroy();
+  if (!t->tuned) (void)hipFree(t->batch_rows);  // (tuned: a block of the workspace)
+  tuned_destroy(t->tuned);
+  deep_destroy(t->deep);
+  t->deep_ring.destroy();
+  delete t;
+}
+
+extern "C" int iqlhip_trainer_create(iqlhip_trainer **out, const iqlhip_trainer_config *cfg,
+                                     const iqlhip_arenas *ar) {
+  if (!out) return fail(IQLHIP_ERR_INVALID, "null out");
+  if (int e = check_cfg(cfg)) return e;
+  if (!ar || !ar->params || !ar->exp_avg || !ar->exp_avg_sq || !ar->target)
+    return fail(IQLHIP_ERR_INVALID, "null arena pointer");
+  HIP_TRY(prepare_step_kernels());
+  Owner<iqlhip_trainer, trainer_release> t(new (std::nothrow) iqlhip_trainer());
+  if (!t) return fail(IQLHIP_ERR_NOMEM, "host allocation failed");
+  t->cfg = *cfg;
+  t->arenas = *ar;
+  if (hipPointerAttribute_t at; hipPointerGetAttributes(&at, ar->params) == hipSuccess)
+    t->device = at.device;
+  else
+    (void)hipGetLastError();
+  t->lr_q = cfg->lr_q, t->lr_v = cfg->lr_v, t->lr_a_base = cfg->lr_actor;
+  const StepShape sh = step_shape(*cfg);
+  const Layout L = make_layout(*cfg);
+  if (is_deep(*cfg)) {
+    const size_t rows_bytes = (size_t)cfg->batch_size * iqlhip_replay_row_stride(cfg->state_dim, cfg->action_dim) * 4;
+    hipError_t e = deep_create(&t->deep, *cfg, sh, *ar, L.off);
+    if (e == hipSuccess) e = hipMalloc((void **)&t->batch_rows, rows_bytes);
+    if (e == hipSuccess) e = t->deep_ring.init(1);
+    if (e != hipSuccess)
+      return fail(e == hipErrorOutOfMemory ? IQLHIP_ERR_NOMEM : IQLHIP_ERR_HIP, "general step: %s", hipGetErrorString(e));
+  } else if (int rc = tuned_create(t.get(), sh, L)) {
+    return rc;
+  }
+  *out = t.release();
   return 0;
 }
 
 extern "C" int iqlhip_trainer_destroy(iqlhip_trainer *t) {
   if (!t) return 0;
   if (t->group) return fail(IQLHIP_ERR_INVALID, "trainer is a member of a group: destroy the group first");
-  t->queue.destroy();
-  if (t->deep) {
-    deep_destroy(t->deep);
-    (void)hipFree(t->batch_rows);
-    t->deep_ring.destroy();
-  }
-  if (t->ws) (void)hipFree(t->ws);
-  if (t->pad_idx) (void)hipFree(t->pad_idx);
-  if (t->pad_keep) (void)hipFree(t->pad_keep);
-  delete t;
+  trainer_release(t);
   return 0;
 }
 
@@ -993,7 +951,7 @@ extern "C" int iqlhip_trainer_sync_weights(iqlhip_trainer *t, void *stream) {
     HIP_TRY(deep_sync_weights(t->deep, (hipStream_t)stream));
     return 0;
   }
-  HIP_TRY(launch_sync_weights(t->bf16, t->ddesc, (hipStream_t)stream));
+  HIP_TRY(launch_sync_weights(t->tuned->bf16, t->tuned->cur.desc, (hipStream_t)stream));
   return 0;
 }
 
@@ -1007,7 +965,7 @@ extern "C" int iqlhip_trainer_set_step(iqlhip_trainer *t, int64_t total_it) {
   DevCtr c;
   memset(&c, 0, sizeof(c));
   c.ctr[0] = total_it, c.ctr[1] = total_it;
-  HIP_TRY(hipMemcpy(t->dctr, &c, sizeof(c), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(t->tuned->cur.ctr, &c, sizeof(c), hipMemcpyHostToDevice));
   t->queue.dev_args_valid = false;
   if (t->group) group_invalidate(t->group);
   return 0;
@@ -1130,16 +1088,12 @@ struct DeepRun {
 
 static int deep_push(const DeepRun &r, const DevArgs *a, int64_t done, int64_t n, hipStream_t st) {
   DeepRing &R = *r.ring;
-  const int K = r.K, slot = R.head;
-  R.head = (slot + 1) % DeepRing::RING;
-  if (!R.host[slot]) {
-    HIP_TRY(hipHostMalloc((void **)&R.host[slot], R.bytes(DeepRing::CAP), hipHostMallocDefault));
-    HIP_TRY(hipEventCreateWithFlags(&R.ev[slot], hipEventDisableTiming));
-  }
-  if (R.used[slot]) HIP_TRY(hipEventSynchronize(R.ev[slot]));
-  DeepArgs *ha = reinterpret_cast<DeepArgs *>(R.host[slot]);
-  DeepCtr *hc = reinterpret_cast<DeepCtr *>(R.host[slot] + (size_t)K * sizeof(DeepArgs));
-  AdamCoef *hk = reinterpret_cast<AdamCoef *>(R.host[slot] + R.head_bytes());
+  const int K = r.K;
+  char *slot;
+  if (int rc = R.ring.next(R.bytes(DeepRing::CAP), &slot)) return rc;
+  DeepArgs *ha = reinterpret_cast<DeepArgs *>(slot);
+  DeepCtr *hc = reinterpret_cast<DeepCtr *>(slot + (size_t)K * sizeof(DeepArgs));
+  AdamCoef *hk = reinterpret_cast<AdamCoef *>(slot + R.head_bytes());
   for (int k = 0; k < K; ++k) {
     const iqlhip_trainer_config &c = r.tr[k]->cfg;
     const int64_t B = c.batch_size, H = c.hidden_dim, NH = n_hidden(c);
@@ -1155,10 +1109,7 @@ static int deep_push(const DeepRun &r, const DevArgs *a, int64_t done, int64_t n
       hk[i * K + k] = make_adam_coef(c.adam_beta1, c.adam_beta2, c.adam_eps, a[k].lr_q, a[k].lr_v, a[k].lr_a_base,
                                      c.cosine_t_max, x.base_step + i + 1);
   }
-  HIP_TRY(hipMemcpyAsync(R.dev, R.host[slot], R.bytes(n), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipEventRecord(R.ev[slot], st));
-  R.used[slot] = true;
-  return 0;
+  return R.ring.send(R.dev, R.bytes(n), st);
 }
 
 static int deep_run(const DeepRun &r, const DevArgs *a, int64_t n_steps, int graph_unroll, hipStream_t st) {
@@ -1194,7 +1145,7 @@ static int check_counts(const iqlhip_trainer *t0, bool counts, const char *who) 
                 "per-step valid-row counts (a short batch) run on the tuned step only (n_hidden 2, hidden_dim 64 / "
                 "128 / 256); this %s (n_hidden %d, hidden_dim %d) runs the general layer-wise step",
                 who, n_hidden(t0->cfg), t0->cfg.hidden_dim);
-  if (counts && t0->bf16)
+  if (counts && t0->tuned->bf16)
     return fail(IQLHIP_ERR_UNSUPPORTED, "per-step valid-row counts (a short batch) are built for precision fp32 only");
   return 0;
 }
@@ -1216,10 +1167,11 @@ static int check_view(const iqlhip_replay_view &v, const iqlhip_trainer_config &
 // step is the caller's, every padding row repeats row 0 of its step (an index the caller gave: in range; a
 // mask row: never counted).  Nothing is read beyond the caller's arrays.  On-device indices and masks need
 // no copy: a padding row draws the Philox index / mask words of its own row number.
-static bool is_padded(const iqlhip_trainer *t) { return !t->deep && t->D.NB != t->D.B; }
+static bool is_padded(const iqlhip_trainer *t) { return t->tuned && t->tuned->D.NB != t->tuned->D.B; }
 static int64_t pad_chunk(const iqlhip_trainer *t, bool idx, bool keep) {
   if (!is_padded(t) || (!idx && !keep)) return INT64_MAX;
-  const size_t per_step = (idx ? (size_t)t->D.B * 8 : 0) + (keep ? (size_t)2 * t->D.B * t->D.H : 0);
+  const TrainerDesc &D = t->tuned->D;
+  const size_t per_step = (idx ? (size_t)D.B * 8 : 0) + (keep ? (size_t)2 * D.B * D.H : 0);
   const size_t budget = (size_t)32 << 20;
   return budget / per_step > 0 ? (int64_t)(budget / per_step) : 1;
 }
@@ -1233,16 +1185,17 @@ static int pad_grow(void **buf, size_t *have, size_t want) {
 }
 static int pad_inputs(iqlhip_trainer *t, DevArgs &a, hipStream_t st) {
   if (!is_padded(t)) return 0;
-  const int NB = t->D.NB, B = t->D.B, H = t->D.H;
+  TunedTrainer *u = t->tuned;
+  const int NB = u->D.NB, B = u->D.B, H = u->D.H;
   if (a.idx_mode == 1) {
-    if (int rc = pad_grow(&t->pad_idx, &t->pad_idx_bytes, (size_t)a.n_steps * B * 8)) return rc;
-    HIP_TRY(launch_pad_rows(a.idx, t->pad_idx, a.n_steps, NB, B, 8, st));
-    a.idx = reinterpret_cast<const int64_t *>(t->pad_idx);
+    if (int rc = pad_grow(&u->pad_idx, &u->pad_idx_bytes, (size_t)a.n_steps * B * 8)) return rc;
+    HIP_TRY(launch_pad_rows(a.idx, u->pad_idx, a.n_steps, NB, B, 8, st));
+    a.idx = reinterpret_cast<const int64_t *>(u->pad_idx);
   }
   if (a.drop_keep) {
-    if (int rc = pad_grow(&t->pad_keep, &t->pad_keep_bytes, (size_t)a.n_steps * 2 * B * H)) return rc;
-    HIP_TRY(launch_pad_rows(a.drop_keep, t->pad_keep, a.n_steps * 2, NB, B, H, st));
-    a.drop_keep = reinterpret_cast<const uint8_t *>(t->pad_keep);
+    if (int rc = pad_grow(&u->pad_keep, &u->pad_keep_bytes, (size_t)a.n_steps * 2 * B * H)) return rc;
+    HIP_TRY(launch_pad_rows(a.drop_keep, u->pad_keep, a.n_steps * 2, NB, B, H, st));
+    a.drop_keep = reinterpret_cast<const uint8_t *>(u->pad_keep);
   }
   return 0;
 }
@@ -1271,7 +1224,8 @@ static int run_solo(iqlhip_trainer *t, const DevArgs &a, int graph_unroll, hipSt
     return deep_run({tr, 1, &t->deep_ring, deep_desc_dev(t->deep), t->queue}, &a, a.n_steps, graph_unroll, st);
   }
   if (t->group) group_invalidate(t->group);  // this call rewrites the member's slot of the group's arguments
-  const StepTarget x = {t->bf16, t->D, t->ddesc, t->dargs, t->dctr, t->ditems, t->n_items, 1};
+  const TunedTrainer *u = t->tuned;
+  const StepTarget x = {u->bf16, u->D, u->cur.desc, u->cur.args, u->cur.ctr, u->cur.items, u->cur.n_items, 1};
   return run_tuned(t->queue, x, &a, a.n_steps, graph_unroll, counts, st);
 }
 
@@ -1329,7 +1283,7 @@ extern "C" int iqlhip_train_batch(iqlhip_trainer *t, const float *s, const float
 struct iqlhip_group {
   int K = 0;
   int n_items = 0;  // slots of every member's item table (deal_items: a whole network per XCD, rotated by member)
-  iqlhip_trainer *tr[IQLHIP_MAX_GROUP] = {};
+  iqlhip_trainer *tr[IQLHIP_MAX_GROUP] = {};  // (set by attach: none while the group is being built)
   void *mem = nullptr;  // [K] TrainerDesc | [K] DevArgs | [K] DevCtr | [K][n_items] UpdItem
   TrainerDesc *gdesc = nullptr;
   DevArgs *gargs = nullptr;
@@ -1353,28 +1307,40 @@ static bool same_shape(const iqlhip_trainer_config &a, const iqlhip_trainer_conf
          n_hidden(a) == n_hidden(b);
 }
 
-static int deep_group_create(iqlhip_group **out, iqlhip_trainer *const *trainers, int32_t n) {
-  iqlhip_group *g = new (std::nothrow) iqlhip_group();
-  if (!g) return fail(IQLHIP_ERR_NOMEM, "host allocation failed");
-  g->K = n, g->deep = true;
-  hipError_t e = hipDeviceSynchronize();  // members may have steps in flight on other streams
-  if (e == hipSuccess) e = hipMalloc(&g->mem, sizeof(DeepDesc) * n);
-  if (e == hipSuccess) {
-    g->gdeep = reinterpret_cast<DeepDesc *>(g->mem);
-    e = g->deep_ring.init(n);
-  }
-  for (int k = 0; k < n && e == hipSuccess; ++k)
-    e = hipMemcpy(g->gdeep + k, &deep_desc(trainers[k]->deep), sizeof(DeepDesc), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    g->deep_ring.destroy();
-    if (g->mem) (void)hipFree(g->mem);
-    delete g;
-    return fail(e == hipErrorOutOfMemory ? IQLHIP_ERR_NOMEM : IQLHIP_ERR_HIP, "general-step group: %s",
-                hipGetErrorString(e));
-  }
-  for (int k = 0; k < n; ++k) g->tr[k] = trainers[k], trainers[k]->group = g;
-  *out = g;
-  return 0;
+// Member k of g: the trainer steps from its row of the group's arrays from here on (a general-step member
+// keeps its own workspace and argument block, so one stepped alone between group calls needs no hand-over).
+static void attach(iqlhip_group *g, int k, iqlhip_trainer *t) {
+  g->tr[k] = t;
+  t->group = g;
+  if (g->deep) return;
+  t->tuned->cur = {g->gdesc + k, g->gargs + k, g->gctr + k, g->gitems + (size_t)k * g->n_items, g->n_items};
+  // the member's slots have moved: its next solo call must send its arguments and stage its first batch
+  // again (`continues` would otherwise trust what the OLD slot held -- after a group, whatever the last solo
+  // call OUTSIDE it sent), and its own graph holds the old descriptor addresses
+  t->queue.dev_args_valid = false;
+  t->queue.drop_graph();
+}
+// Back to its own workspace slots (with the group's current counters): usable on its own.
+static void detach(iqlhip_trainer *t) {
+  const bool deep = t->group->deep;
+  t->group = nullptr;
+  if (deep) return;
+  TunedTrainer *u = t->tuned;
+  (void)hipMemcpy(u->own.ctr, u->cur.ctr, sizeof(DevCtr), hipMemcpyDeviceToDevice);
+  u->cur = u->own;
+  t->queue.dev_args_valid = false;
+  t->queue.drop_graph();
+}
+
+// Frees a group, finished or partly built (iqlhip_group_create's owner); its members stay usable.
+static void group_release(iqlhip_group *g) {
+  (void)hipDeviceSynchronize();
+  for (int k = 0; k < g->K; ++k)
+    if (g->tr[k]) detach(g->tr[k]);
+  g->queue.destroy();
+  g->deep_ring.destroy();
+  (void)hipFree(g->mem);
+  delete g;
 }
 
 extern "C" int iqlhip_group_create(iqlhip_group **out, iqlhip_trainer *const *trainers, int32_t n) {
@@ -1388,97 +1354,73 @@ extern "C" int iqlhip_group_create(iqlhip_group **out, iqlhip_trainer *const *tr
     if (trainers[k]->group) return fail(IQLHIP_ERR_INVALID, "trainer %d already belongs to a group", k);
     for (int j = 0; j < k; ++j)
       if (trainers[j] == trainers[k]) return fail(IQLHIP_ERR_INVALID, "trainer %d listed twice", k);
-    if (!same_shape(trainers[0]->cfg, trainers[k]->cfg) || trainers[k]->n_items != trainers[0]->n_items)
+    if (!same_shape(trainers[0]->cfg, trainers[k]->cfg) ||
+        (trainers[0]->tuned && trainers[k]->tuned->own.n_items != trainers[0]->tuned->own.n_items))
       return fail(IQLHIP_ERR_INVALID, "trainer %d differs in shape from trainer 0 (dims, batch, precision, "
                   "critics, hidden layers, policy kind and dropout on/off must match)", k);
   }
-  if (trainers[0]->deep) return deep_group_create(out, trainers, n);
-  iqlhip_group *g = new (std::nothrow) iqlhip_group();
+  Owner<iqlhip_group, group_release> g(new (std::nothrow) iqlhip_group());
   if (!g) return fail(IQLHIP_ERR_NOMEM, "host allocation failed");
-  g->K = n;
-  // the members' item tables, dealt for a group launch; one size for all
-  std::vector<std::vector<UpdItem>> tables(n);
-  {
-    size_t depth = 0;
-    for (int pass = 0; pass < 2; ++pass)
-      for (int k = 0; k < n; ++k) {
-        std::vector<UpdItem> per_xcd[8];
-        deal_items(trainers[k], k, n, per_xcd);
-        size_t d = 0;
-        tables[k] = flatten_table(per_xcd, depth, &d, (size_t)(trainers[k]->D.B + 15) / 16);
-        depth = d > depth ? d : depth;
-      }
-  }
-  const int ni = (int)tables[0].size();
-  for (int k = 0; k < n; ++k)
-    if ((int)tables[k].size() != ni) {
-      delete g;
-      return fail(IQLHIP_ERR_INVALID, "item tables of the members differ in size");
+  g->K = n, g->deep = trainers[0]->deep != nullptr;
+  if (g->deep) {
+    hipError_t e = hipDeviceSynchronize();  // members may have steps in flight on other streams
+    if (e == hipSuccess) e = hipMalloc(&g->mem, sizeof(DeepDesc) * n);
+    g->gdeep = reinterpret_cast<DeepDesc *>(g->mem);
+    if (e == hipSuccess) e = g->deep_ring.init(n);
+    for (int k = 0; k < n && e == hipSuccess; ++k)
+      e = hipMemcpy(g->gdeep + k, &deep_desc(trainers[k]->deep), sizeof(DeepDesc), hipMemcpyHostToDevice);
+    if (e != hipSuccess)
+      return fail(e == hipErrorOutOfMemory ? IQLHIP_ERR_NOMEM : IQLHIP_ERR_HIP, "general-step group: %s",
+                  hipGetErrorString(e));
+  } else {
+    // the members' item tables, dealt for a group launch; one size for all
+    std::vector<std::vector<UpdItem>> tables(n);
+    {
+      size_t depth = 0;
+      for (int pass = 0; pass < 2; ++pass)
+        for (int k = 0; k < n; ++k) {
+          std::vector<UpdItem> per_xcd[8];
+          deal_items(trainers[k]->tuned, k, n, per_xcd);
+          size_t d = 0;
+          tables[k] = flatten_table(per_xcd, depth, &d, (size_t)(trainers[k]->tuned->D.B + 15) / 16);
+          depth = d > depth ? d : depth;
+        }
     }
-  g->n_items = ni;
-  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-  const size_t b_desc = up(sizeof(TrainerDesc) * n), b_args = up(sizeof(DevArgs) * n),
-               b_ctr = up(sizeof(DevCtr) * n), b_items = up(sizeof(UpdItem) * (size_t)ni * n);
-  HIP_TRY(hipDeviceSynchronize());  // members may have steps in flight on other streams
-  if (hipMalloc(&g->mem, b_desc + b_args + b_ctr + b_items) != hipSuccess) {
-    delete g;
-    return fail(IQLHIP_ERR_NOMEM, "hipMalloc of the group descriptors failed");
+    const int ni = (int)tables[0].size();
+    for (int k = 0; k < n; ++k)
+      if ((int)tables[k].size() != ni) return fail(IQLHIP_ERR_INVALID, "item tables of the members differ in size");
+    g->n_items = ni;
+    // mem = [K] TrainerDesc | [K] DevArgs | [K] DevCtr | [K][n_items] UpdItem
+    auto blocks = [&](WorkspacePlan p) {
+      g->gdesc = p.take<TrainerDesc>(n);
+      g->gargs = p.take<DevArgs>(n);
+      g->gctr = p.take<DevCtr>(n);
+      g->gitems = p.take<UpdItem>((size_t)ni * n);
+      return p.end();
+    };
+    HIP_TRY(hipDeviceSynchronize());  // members may have steps in flight on other streams
+    if (hipMalloc(&g->mem, blocks(WorkspacePlan())) != hipSuccess)
+      return fail(IQLHIP_ERR_NOMEM, "hipMalloc of the group descriptors failed");
+    blocks(WorkspacePlan(g->mem));
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < n && e == hipSuccess; ++k) {
+      const Slots &m = trainers[k]->tuned->cur;
+      e = hipMemcpy(g->gdesc + k, m.desc, sizeof(TrainerDesc), hipMemcpyDeviceToDevice);
+      if (e == hipSuccess) e = hipMemcpy(g->gargs + k, m.args, sizeof(DevArgs), hipMemcpyDeviceToDevice);
+      if (e == hipSuccess) e = hipMemcpy(g->gctr + k, m.ctr, sizeof(DevCtr), hipMemcpyDeviceToDevice);
+      if (e == hipSuccess)
+        e = hipMemcpy(g->gitems + (size_t)k * ni, tables[k].data(), sizeof(UpdItem) * ni, hipMemcpyHostToDevice);
+    }
+    if (e != hipSuccess)
+      return fail(IQLHIP_ERR_HIP, "copying the member descriptors failed: %s", hipGetErrorString(e));
   }
-  char *p = reinterpret_cast<char *>(g->mem);
-  g->gdesc = reinterpret_cast<TrainerDesc *>(p), p += b_desc;
-  g->gargs = reinterpret_cast<DevArgs *>(p), p += b_args;
-  g->gctr = reinterpret_cast<DevCtr *>(p), p += b_ctr;
-  g->gitems = reinterpret_cast<UpdItem *>(p);
-  hipError_t e = hipSuccess;
-  for (int k = 0; k < n && e == hipSuccess; ++k) {
-    iqlhip_trainer *t = trainers[k];
-    e = hipMemcpy(g->gdesc + k, t->ddesc, sizeof(TrainerDesc), hipMemcpyDeviceToDevice);
-    if (e == hipSuccess) e = hipMemcpy(g->gargs + k, t->dargs, sizeof(DevArgs), hipMemcpyDeviceToDevice);
-    if (e == hipSuccess) e = hipMemcpy(g->gctr + k, t->dctr, sizeof(DevCtr), hipMemcpyDeviceToDevice);
-    if (e == hipSuccess)
-      e = hipMemcpy(g->gitems + (size_t)k * ni, tables[k].data(), sizeof(UpdItem) * ni, hipMemcpyHostToDevice);
-  }
-  if (e != hipSuccess) {
-    (void)hipFree(g->mem);
-    delete g;
-    return fail(IQLHIP_ERR_HIP, "copying the member descriptors failed: %s", hipGetErrorString(e));
-  }
-  for (int k = 0; k < n; ++k) {
-    iqlhip_trainer *t = trainers[k];
-    g->tr[k] = t;
-    t->group = g;
-    t->ddesc = g->gdesc + k, t->dargs = g->gargs + k, t->dctr = g->gctr + k, t->ditems = g->gitems + (size_t)k * ni;
-    t->n_items = ni;
-    // the member's DevArgs slot has moved: its next solo call must send its arguments and stage
-    // its first batch again (`continues` would otherwise trust what the OLD slot held)
-    t->queue.dev_args_valid = false;
-    t->queue.drop_graph();  // the member's own graph holds the old descriptor addresses
-  }
-  *out = g;
+  for (int k = 0; k < n; ++k) attach(g.get(), k, trainers[k]);
+  *out = g.release();
   return 0;
 }
 
-// Members go back to their own workspace slots (with the group's current counters) and stay
-// usable on their own.
 extern "C" int iqlhip_group_destroy(iqlhip_group *g) {
-  if (!g) return 0;
-  (void)hipDeviceSynchronize();
-  for (int k = 0; g->deep && k < g->K; ++k) g->tr[k]->group = nullptr;
-  for (int k = 0; !g->deep && k < g->K; ++k) {
-    iqlhip_trainer *t = g->tr[k];
-    (void)hipMemcpy(t->own_dctr, t->dctr, sizeof(DevCtr), hipMemcpyDeviceToDevice);
-    t->ddesc = t->own_ddesc, t->dargs = t->own_dargs, t->dctr = t->own_dctr, t->ditems = t->own_ditems;
-    t->n_items = t->own_n_items;
-    t->group = nullptr;
-    // own_dargs holds whatever the member's last solo call OUTSIDE the group sent (all zero if
-    // there was none: rows = NULL): a solo call after the group must never continue from it
-    t->queue.dev_args_valid = false;
-    t->queue.drop_graph();
-  }
-  g->queue.destroy();
-  g->deep_ring.destroy();
-  if (g->mem) (void)hipFree(g->mem);
-  delete g;
+  if (g) group_release(g);
   return 0;
 }
 
@@ -1508,7 +1450,6 @@ extern "C" int iqlhip_group_train_steps_valid(iqlhip_group *g, const iqlhip_repl
   for (int k = 0; k < g->K; ++k)
     chunk = std::min(chunk, pad_chunk(g->tr[k], idx && idx[k], dropout_keep && dropout_keep[k]));
   const int64_t NB = t0->cfg.batch_size, keep_step = (int64_t)n_hidden(t0->cfg) * NB * t0->cfg.hidden_dim;
-  const StepTarget x = {t0->bf16, t0->D, g->gdesc, g->gargs, g->gctr, g->gitems, g->n_items, g->K};
   for (int64_t done = 0; done < n_steps;) {
     const int64_t n = std::min(chunk, n_steps - done);
     DevArgs want[IQLHIP_MAX_GROUP];
@@ -1523,7 +1464,9 @@ extern "C" int iqlhip_group_train_steps_valid(iqlhip_group *g, const iqlhip_repl
     }
     const int rc = g->deep ? deep_run({g->tr, g->K, &g->deep_ring, g->gdeep, g->queue}, want, n, graph_unroll,
                                       (hipStream_t)stream)
-                           : run_tuned(g->queue, x, want, n, graph_unroll, counts, (hipStream_t)stream);
+                           : run_tuned(g->queue, {t0->tuned->bf16, t0->tuned->D, g->gdesc, g->gargs, g->gctr, g->gitems,
+                                                  g->n_items, g->K},
+                                       want, n, graph_unroll, counts, (hipStream_t)stream);
     if (rc) return rc;
     for (int k = 0; k < g->K; ++k) g->tr[k]->total_it += n;
     done += n;
@@ -1577,27 +1520,28 @@ extern "C" int iqlhip_forward(iqlhip_trainer *t, int32_t which, const float *s, 
     HIP_TRY(deep_infer(t->deep, which, s, a, n, out, st));
     return 0;
   }
-  const int E = t->D.E;
+  const TunedTrainer *u = t->tuned;
+  const int E = u->D.E;
   FwdNet N;
   switch (which) {
     case 0:  // q_1 .. q_E -> out[n][E]
       for (int e = 0; e < E; ++e) {
-        N = t->D.fwd[e], N.out_col = e, N.train_slot = -1, N.stage = 0;
-        HIP_TRY(launch_infer(t->bf16, t->D, t->ddesc, N, s, a, n, out, E, st));
+        N = u->D.fwd[e], N.out_col = e, N.train_slot = -1, N.stage = 0;
+        HIP_TRY(launch_infer(u->bf16, u->D, u->cur.desc, N, s, a, n, out, E, st));
       }
       return 0;
     case 1:
-      N = t->D.fwd[E], N.out_col = 0, N.train_slot = -1;
-      HIP_TRY(launch_infer(t->bf16, t->D, t->ddesc, N, s, a, n, out, 1, st));
+      N = u->D.fwd[E], N.out_col = 0, N.train_slot = -1;
+      HIP_TRY(launch_infer(u->bf16, u->D, u->cur.desc, N, s, a, n, out, 1, st));
       return 0;
     case 2:  // eval-mode actor: no dropout (ref:299 actor.eval())
-      N = t->D.fwd[E + 1], N.out_col = 0, N.train_slot = -1, N.dropout = 0;
-      HIP_TRY(launch_infer(t->bf16, t->D, t->ddesc, N, s, a, n, out, t->cfg.action_dim, st));
+      N = u->D.fwd[E + 1], N.out_col = 0, N.train_slot = -1, N.dropout = 0;
+      HIP_TRY(launch_infer(u->bf16, u->D, u->cur.desc, N, s, a, n, out, t->cfg.action_dim, st));
       return 0;
     case 3:  // target critics -> out[n][E]
       for (int e = 0; e < E; ++e) {
-        N = t->D.fwd[E + 2 + e], N.out_col = e;
-        HIP_TRY(launch_infer(t->bf16, t->D, t->ddesc, N, s, a, n, out, E, st));
+        N = u->D.fwd[E + 2 + e], N.out_col = e;
+        HIP_TRY(launch_infer(u->bf16, u->D, u->cur.desc, N, s, a, n, out, E, st));
       }
       return 0;
     default:
@@ -1684,8 +1628,8 @@ extern "C" int iqlhip_mlp_set_forward(const iqlhip_mlp_set *set, const float *x,
 extern "C" int iqlhip_trainer_set_debug(iqlhip_trainer *t, void *buf) {
   if (!t) return fail(IQLHIP_ERR_INVALID, "null trainer");
   if (t->deep) return fail(IQLHIP_ERR_UNSUPPORTED, "no stamps in the general step");
-  t->D.dbg = reinterpret_cast<unsigned long long *>(buf);
-  HIP_TRY(hipMemcpy(t->ddesc, &t->D, sizeof(TrainerDesc), hipMemcpyHostToDevice));
+  t->tuned->D.dbg = reinterpret_cast<unsigned long long *>(buf);
+  HIP_TRY(hipMemcpy(t->tuned->cur.desc, &t->tuned->D, sizeof(TrainerDesc), hipMemcpyHostToDevice));
   t->queue.drop_graph();
   return 0;
 }

@@ -31,6 +31,7 @@
 
 #include "../../include/iqlhip.h"
 #include "common.h"
+#include "host_plan.h"
 #include "iql_deep.h"
 #include "step_math.h"
 
@@ -712,12 +713,7 @@ struct DeepTrainer {
   size_t lds_bytes = 0;
 };
 
-template <typename T>
-static T *carve_(char *&p, size_t n) {
-  T *r = reinterpret_cast<T *>(p);
-  p += (n * sizeof(T) + 255) / 256 * 256;
-  return r;
-}
+void deep_destroy(DeepTrainer *);
 
 bool deep_shape_ok(const iqlhip_trainer_config &c, int n_hidden, const char **why) {
   if (n_hidden < 1 || n_hidden > DEEP_MAX_LIN - 1) return *why = "n_hidden must be in 1..6", false;
@@ -725,10 +721,11 @@ bool deep_shape_ok(const iqlhip_trainer_config &c, int n_hidden, const char **wh
   return true;
 }
 
-// off: the arena layout's offsets, 2 (n_hidden + 1) per net (W0 b0 W1 b1 ...), then log_std
-hipError_t deep_create(DeepTrainer **out, const iqlhip_trainer_config &cfg, int n_hidden, const iqlhip_arenas &ar,
-                       const int64_t *off) {
-  DeepTrainer *t = new (std::nothrow) DeepTrainer();
+// sh: what api.hip derived from cfg; off: the arena layout's offsets, 2 (n_hidden + 1) per net (W0 b0 W1 b1 ...),
+// then log_std
+hipError_t deep_create(DeepTrainer **out, const iqlhip_trainer_config &cfg, const StepShape &sh,
+                       const iqlhip_arenas &ar, const int64_t *off) {
+  Owner<DeepTrainer, deep_destroy> t(new (std::nothrow) DeepTrainer());
   if (!t) return hipErrorOutOfMemory;
   t->bf16 = cfg.precision == IQLHIP_PREC_BF16;
   const int es = t->bf16 ? 2 : 4, KM = t->bf16 ? 32 : 16, EPV = t->bf16 ? 8 : 4;
@@ -736,31 +733,19 @@ hipError_t deep_create(DeepTrainer **out, const iqlhip_trainer_config &cfg, int 
   memset(&D, 0, sizeof(D));
   // B: the rows the kernels work on (whole 16-row slabs); NB = batch_size of them count
   const int S = cfg.state_dim, A = cfg.action_dim, H = cfg.hidden_dim, B = round_up(cfg.batch_size, 16);
-  const int E = cfg.n_critics > 0 ? cfg.n_critics : 2, NT = E + 2, NF = 2 * E + 3, NL = n_hidden + 1;
+  const int E = sh.E, NT = sh.ntrain(), NL = sh.NH + 1;
   D.S = S, D.A = A, D.H = H, D.Hp = round_up(H, 32), D.B = B, D.BP = round_up(B, 32), D.NL = NL;
-  D.E = E, D.ntrain = NT, D.nfwd = NF, D.net_v = E, D.net_a = E + 1;
-  D.out_v = E, D.out_qt = E + 1, D.out_nv = 2 * E + 1, D.out_mean = 2 * E + 2;
+  D.E = E, D.ntrain = NT, D.nfwd = sh.nfwd(), D.net_v = sh.net_v(), D.net_a = sh.net_a();
+  D.out_v = sh.out_v(), D.out_qt = sh.out_qt(), D.out_nv = sh.out_nv(), D.out_mean = sh.out_mean();
   D.OUTW = round_up(D.out_mean + A, 4);
   D.next_off = round_up(S + A + 2, 4);
   D.opad = round_up(A, 16);
   D.nslab = B / 16, D.NB = cfg.batch_size;
-  D.deterministic = cfg.deterministic, D.has_dropout = cfg.dropout_p > 0.f, D.polyak_convex = cfg.polyak_form == 1;
+  D.deterministic = cfg.deterministic, D.has_dropout = sh.has_dropout, D.polyak_convex = cfg.polyak_form == 1;
   D.two_over_B = 2.0f / (float)D.NB, D.inv_E = 1.0f / (float)E;
   D.discount = cfg.discount, D.tau = cfg.tau, D.beta = cfg.beta, D.iql_tau = cfg.iql_tau;
   D.one_m_tau = (float)(1.0 - (double)cfg.tau);
-  if (D.has_dropout) {
-    const float scale = 1.0f / (float)(1.0 - (double)cfg.dropout_p);
-    if (t->bf16) {  // noise.div_(1-p) happens in bf16 under autocast (ATen _dropout_impl)
-      uint32_t u;
-      memcpy(&u, &scale, 4);
-      u = (u + 0x7fffu + ((u >> 16) & 1u)) & 0xffff0000u;
-      memcpy(&D.drop_scale, &u, 4);
-    } else {
-      D.drop_scale = scale;
-    }
-    const double thr = (double)cfg.dropout_p * 4294967296.0;
-    D.drop_thr = thr >= 4294967295.0 ? 0xffffffffu : (uint32_t)thr;
-  }
+  D.drop_scale = sh.drop.scale, D.drop_thr = sh.drop.thr;
   D.seed = cfg.seed;
   D.params = ar.params, D.exp_avg = ar.exp_avg, D.exp_avg_sq = ar.exp_avg_sq, D.target = ar.target, D.grads = ar.grads;
   D.off_log_std = off[NT * 2 * NL];
@@ -769,30 +754,18 @@ hipError_t deep_create(DeepTrainer **out, const iqlhip_trainer_config &cfg, int 
   t->lds_bytes = (size_t)2 * 16 * D.lds_w * es;
   // ---- per-net geometry ----
   auto r64 = [](int x) { return (size_t)round_up(x, 64); };
-  size_t total = 0;
-  auto add = [&](size_t bytes) { total += (bytes + 255) / 256 * 256; };
   for (int n = 0; n < NT; ++n) {
     DeepNet &N = D.net[n];
-    const int in = n < E ? S + A : S, outd = n == E + 1 ? A : 1;
+    const int in = sh.in_dim(n), outd = sh.out_dim(n);
     for (int l = 0; l < NL; ++l) {
       N.K[l] = l == 0 ? in : H, N.Kpad[l] = l == 0 ? round_up(in, 32) : D.Hp;
       N.N[l] = l == NL - 1 ? outd : H, N.Npad[l] = l == NL - 1 ? round_up(outd, 16) : D.Hp;
       N.NKpad[l] = round_up(N.Npad[l], KM);
       N.off_w[l] = off[(n * NL + l) * 2], N.off_b[l] = off[(n * NL + l) * 2 + 1];
       N.toff_w[l] = n < E ? N.off_w[l] : -1, N.toff_b[l] = n < E ? N.off_b[l] : -1;
-      add((size_t)N.Npad[l] * N.Kpad[l] * es);                 // wc
-      if (l >= 1) add((size_t)N.Kpad[l] * N.NKpad[l] * es);    // wt
-      if (n < E) add((size_t)N.Npad[l] * N.Kpad[l] * es);      // tc
-      if (l >= 1) add(r64(N.Kpad[l]) * D.BP * es);             // hT[l]
-      add(r64(N.Npad[l]) * D.BP * es);                         // dzT[l]
     }
     N.has_target = n < E, N.group = n < E ? 0 : (n == E ? 1 : 2);
   }
-  add(r64(k0max) * D.BP * es);             // xT
-  add((size_t)B * 2 * 4), add((size_t)B * A * 4);
-  add((size_t)D.OUTW * D.BP * 4);
-  add((size_t)NT * D.nslab * 4), add((size_t)D.nslab * A * 4);
-  add(sizeof(DeepDesc));
   // update items.  Tile width (kd_update<.., TQ>): 64 x 64 tiles where the operand panels are the traffic (batch
   // >= 1024) or the matrices are large (width >= 768) AND such tiles still make ~150 work-groups; 64 x 16 otherwise
   // (measured with tools/general_run.py: E = 4 / batch 1024 with three hidden layers, 216 wide
@@ -816,40 +789,38 @@ hipError_t deep_create(DeepTrainer **out, const iqlhip_trainer_config &cfg, int 
     }
   items.push_back(DeepItem{-1, 0, 0, 0});
   t->n_items = (int)items.size();
-  add(items.size() * sizeof(DeepItem));
-  hipError_t e = hipMalloc(&t->ws, total);
-  if (e != hipSuccess) {
-    delete t;
-    return e;
-  }
-  if ((e = hipMemset(t->ws, 0, total)) != hipSuccess) {
-    (void)hipFree(t->ws);
-    delete t;
-    return e;
-  }
-  char *p = reinterpret_cast<char *>(t->ws);
-  void *xT = nullptr;
-  for (int n = 0; n < NT; ++n) {
-    DeepNet &N = D.net[n];
-    for (int l = 0; l < NL; ++l) {
-      N.wc[l] = carve_<char>(p, (size_t)N.Npad[l] * N.Kpad[l] * es);
-      N.wt[l] = l >= 1 ? carve_<char>(p, (size_t)N.Kpad[l] * N.NKpad[l] * es) : nullptr;
-      N.tc[l] = n < E ? carve_<char>(p, (size_t)N.Npad[l] * N.Kpad[l] * es) : nullptr;
-      N.hT[l] = l >= 1 ? carve_<char>(p, r64(N.Kpad[l]) * D.BP * es) : nullptr;
-      N.dzT[l] = carve_<char>(p, r64(N.Npad[l]) * D.BP * es);
+  // ---- workspace: the one list of its blocks, run once to measure and once to place ----
+  auto blocks = [&](WorkspacePlan p) {
+    for (int n = 0; n < NT; ++n) {
+      DeepNet &N = D.net[n];
+      for (int l = 0; l < NL; ++l) {
+        N.wc[l] = p.take<char>((size_t)N.Npad[l] * N.Kpad[l] * es);
+        N.wt[l] = l >= 1 ? p.take<char>((size_t)N.Kpad[l] * N.NKpad[l] * es) : nullptr;
+        N.tc[l] = n < E ? p.take<char>((size_t)N.Npad[l] * N.Kpad[l] * es) : nullptr;
+        N.hT[l] = l >= 1 ? p.take<char>(r64(N.Kpad[l]) * D.BP * es) : nullptr;
+        N.dzT[l] = p.take<char>(r64(N.Npad[l]) * D.BP * es);
+      }
     }
-  }
-  xT = carve_<char>(p, r64(k0max) * D.BP * es);
-  for (int n = 0; n < NT; ++n) D.net[n].hT[0] = xT;
-  D.rd = carve_<float>(p, (size_t)B * 2);
-  D.actf = carve_<float>(p, (size_t)B * A);
-  D.outs = carve_<float>(p, (size_t)D.OUTW * D.BP);
-  D.lossp = carve_<float>(p, (size_t)NT * D.nslab);
-  D.lsp = carve_<float>(p, (size_t)D.nslab * A);
-  t->dD = carve_<DeepDesc>(p, 1);
-  t->ditems = carve_<DeepItem>(p, items.size());
-  // ---- evaluations: q_e, v, actor, target q_e, next_v ----
-  auto mk = [&](int f, int net, bool target, int in_off, int out_col, int slot) {
+    void *xT = p.take<char>(r64(k0max) * D.BP * es);
+    for (int n = 0; n < NT; ++n) D.net[n].hT[0] = xT;
+    D.rd = p.take<float>((size_t)B * 2);
+    D.actf = p.take<float>((size_t)B * A);
+    D.outs = p.take<float>((size_t)D.OUTW * D.BP);
+    D.lossp = p.take<float>((size_t)NT * D.nslab);
+    D.lsp = p.take<float>((size_t)D.nslab * A);
+    t->dD = p.take<DeepDesc>(1);
+    t->ditems = p.take<DeepItem>(items.size());
+    return p.end();
+  };
+  const size_t total = blocks(WorkspacePlan());
+  hipError_t e = hipMalloc(&t->ws, total);
+  if (e == hipSuccess) e = hipMemset(t->ws, 0, total);
+  if (e != hipSuccess) return e;
+  blocks(WorkspacePlan(t->ws));
+  // ---- evaluations ----
+  const std::vector<EvalSpec> order = eval_order(sh, D.next_off);
+  for (int f = 0; f < (int)order.size(); ++f) {
+    const auto [net, target, in_off, out_col, slot] = order[f];
     DeepEval &F = D.ev[f];
     const DeepNet &N = D.net[net];
     const float *base = target ? D.target : D.params;
@@ -861,12 +832,7 @@ hipError_t deep_create(DeepTrainer **out, const iqlhip_trainer_config &cfg, int 
     F.in_off = in_off, F.in_dim = N.K[0];
     F.out_dim = N.N[NL - 1], F.out_col = out_col, F.train_slot = slot;
     F.tanh_out = net == D.net_a, F.dropout = net == D.net_a && D.has_dropout, F.stage = f == 0;
-  };
-  for (int e2 = 0; e2 < E; ++e2) mk(e2, e2, false, 0, e2, e2);
-  mk(E, D.net_v, false, 0, D.out_v, D.net_v);
-  mk(E + 1, D.net_a, false, 0, D.out_mean, D.net_a);
-  for (int e2 = 0; e2 < E; ++e2) mk(E + 2 + e2, e2, true, 0, D.out_qt + e2, -1);
-  mk(2 * E + 2, D.net_v, false, D.next_off, D.out_nv, -1);
+  }
   if ((e = hipMemcpy(t->dD, &D, sizeof(D), hipMemcpyHostToDevice)) == hipSuccess)
     e = hipMemcpy(t->ditems, items.data(), items.size() * sizeof(DeepItem), hipMemcpyHostToDevice);
   if (e == hipSuccess && t->lds_bytes > 48 * 1024) {
@@ -879,12 +845,8 @@ hipError_t deep_create(DeepTrainer **out, const iqlhip_trainer_config &cfg, int 
     for (const void *f : fns)
       if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, lb);
   }
-  if (e != hipSuccess) {
-    (void)hipFree(t->ws);
-    delete t;
-    return e;
-  }
-  *out = t;
+  if (e != hipSuccess) return e;
+  *out = t.release();
   return hipSuccess;
 }
 
@@ -924,32 +886,21 @@ hipError_t deep_step(const DeepTrainer *t, const DeepDesc *dD, const DeepArgs *d
 #define DEEP_EV(k) \
   if (ev && (e = hipEventRecord(ev[k], st)) != hipSuccess) return e;
   DEEP_EV(0);
-  if (t->bf16 && tf == 512)
-    hipLaunchKernelGGL((kd_forward<true, 512>), gf, dim3(512), t->lds_bytes, st, dD, dA, dC);
-  else if (t->bf16)
-    hipLaunchKernelGGL((kd_forward<true, 256>), gf, dim3(256), t->lds_bytes, st, dD, dA, dC);
-  else if (tf == 512)
-    hipLaunchKernelGGL((kd_forward<false, 512>), gf, dim3(512), t->lds_bytes, st, dD, dA, dC);
-  else
-    hipLaunchKernelGGL((kd_forward<false, 256>), gf, dim3(256), t->lds_bytes, st, dD, dA, dC);
+  // f(BF, V): the precision and v (one of V0, V1) as compile-time constants
+  auto pick = [&](int v, auto V0, auto V1, auto f) {
+    with_const<true, false>(t->bf16, [&](auto BF) { with_const<CV(V0), CV(V1)>(v, [&](auto V) { f(BF, V); }); });
+  };
+  pick(tf, Int<512>{}, Int<256>{}, [&](auto BF, auto T) {
+    hipLaunchKernelGGL((kd_forward<CV(BF), CV(T)>), gf, dim3(CV(T)), t->lds_bytes, st, dD, dA, dC);
+  });
   DEEP_EV(1);
-  if (t->bf16 && tb == 512)
-    hipLaunchKernelGGL((kd_backward<true, 512>), gb, dim3(512), t->lds_bytes, st, dD, dA, dC);
-  else if (t->bf16)
-    hipLaunchKernelGGL((kd_backward<true, 256>), gb, dim3(256), t->lds_bytes, st, dD, dA, dC);
-  else if (tb == 512)
-    hipLaunchKernelGGL((kd_backward<false, 512>), gb, dim3(512), t->lds_bytes, st, dD, dA, dC);
-  else
-    hipLaunchKernelGGL((kd_backward<false, 256>), gb, dim3(256), t->lds_bytes, st, dD, dA, dC);
+  pick(tb, Int<512>{}, Int<256>{}, [&](auto BF, auto T) {
+    hipLaunchKernelGGL((kd_backward<CV(BF), CV(T)>), gb, dim3(CV(T)), t->lds_bytes, st, dD, dA, dC);
+  });
   DEEP_EV(2);
-  if (t->bf16 && t->tq == 1)
-    hipLaunchKernelGGL((kd_update<true, 1>), gu, dim3(256), 0, st, dD, items, dA, dC, coefs);
-  else if (t->bf16)
-    hipLaunchKernelGGL((kd_update<true, 4>), gu, dim3(256), 0, st, dD, items, dA, dC, coefs);
-  else if (t->tq == 1)
-    hipLaunchKernelGGL((kd_update<false, 1>), gu, dim3(256), 0, st, dD, items, dA, dC, coefs);
-  else
-    hipLaunchKernelGGL((kd_update<false, 4>), gu, dim3(256), 0, st, dD, items, dA, dC, coefs);
+  pick(t->tq, Int<1>{}, Int<4>{}, [&](auto BF, auto TQ) {
+    hipLaunchKernelGGL((kd_update<CV(BF), CV(TQ)>), gu, dim3(256), 0, st, dD, items, dA, dC, coefs);
+  });
   DEEP_EV(3);
 #undef DEEP_EV
   return hipGetLastError();

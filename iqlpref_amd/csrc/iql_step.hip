@@ -37,6 +37,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "host_plan.h"
 #include "iql_step.h"
 #include "step_math.h"
 
@@ -2665,18 +2666,12 @@ int fwd_parts_per_wg(int B, int H, int n_seeds) {
   return ((int64_t)B * n_seeds >= 1024 && layer2_parts(H) % 2 == 0) ? 2 : 1;
 }
 
-#define DISPATCH_H(BF, HH, CALL)                 \
-  do {                                           \
-    if (BF) {                                    \
-      if (HH == 256) { CALL(true, 256); }        \
-      else if (HH == 128) { CALL(true, 128); }   \
-      else { CALL(true, 64); }                   \
-    } else {                                     \
-      if (HH == 256) { CALL(false, 256); }       \
-      else if (HH == 128) { CALL(false, 128); }  \
-      else { CALL(false, 64); }                  \
-    }                                            \
-  } while (0)
+// Kernel selection: f(BF, HH, ...) gets the precision and the hidden width as compile-time constants
+// (with_const)
+template <typename F>
+static void dispatch_h(bool bf16, int H, F &&f) {
+  with_const<true, false>(bf16, [&](auto BF) { with_const<256, 128, 64>(H, [&](auto HH) { f(BF, HH); }); });
+}
 
 // Launches with many rows (seed groups, batch-1024 ensembles) take the throughput kernels
 // k_forward_tp / k_backward_tp (bf16, H = 256, batch a multiple of 64).
@@ -2729,23 +2724,18 @@ hipError_t launch_forward(bool bf16, const TrainerDesc &D, const TrainerDesc *dD
   // nfwd evaluations + the spare job, each nsl slabs x (SPL / pw) part groups
   const int grid = 8 * ((D.nfwd + 1 + 7) / 8) * nsl * (layer2_parts(D.H) / pw);
   const size_t sm = fwd_smem_bytes(bf16, D.H, D.k1max, mt, pw);
-#define LAUNCH_F(BF, HH, MTV, PWV)                                                                            \
-  hipLaunchKernelGGL((k_forward<BF, HH, MTV, PWV>), dim3(grid, n_seeds), dim3(256), sm, st, dD, a, c, nsl, D.nfwd)
-#define CALL(BF, HH)                                                   \
-  do {                                                                 \
-    if constexpr (HH >= 128) {                                         \
-      if (pw == 2) {                                                   \
-        if (mt == 2) LAUNCH_F(BF, HH, 2, 2);                           \
-        else LAUNCH_F(BF, HH, 1, 2);                                   \
-        break;                                                         \
-      }                                                                \
-    }                                                                  \
-    if (mt == 2) LAUNCH_F(BF, HH, 2, 1);                               \
-    else LAUNCH_F(BF, HH, 1, 1);                                       \
-  } while (0)
-  DISPATCH_H(bf16, D.H, CALL);
-#undef CALL
-#undef LAUNCH_F
+  dispatch_h(bf16, D.H, [&](auto BF, auto HH) {
+    auto go = [&](auto PW) {
+      with_const<2, 1>(mt, [&](auto MT) {
+        hipLaunchKernelGGL((k_forward<CV(BF), CV(HH), CV(MT), CV(PW)>), dim3(grid, n_seeds), dim3(256), sm, st, dD, a,
+                           c, nsl, D.nfwd);
+      });
+    };
+    if constexpr (CV(HH) >= 128) {  // (two parts per work-group: never instantiated at H = 64)
+      if (pw == 2) return go(Int<2>{});
+    }
+    go(Int<1>{});
+  });
   return hipGetLastError();
 }
 // parts of the dZ1 columns per backward work-group: 1 for one seed at batch 256 (every part repeats
@@ -2774,37 +2764,18 @@ hipError_t launch_backward(bool bf16, const TrainerDesc &D, const TrainerDesc *d
   // GEMM operands up front below 1024 rows per launch, else behind the dZ2 phase (backward_body).
   // Measured: no difference for one seed (63.2k either way), K = 8 170.2k against 165.1k
   const bool pre = (int64_t)D.B * n_seeds < 1024;
-#define LAUNCH_B(BF, HH, PRE_, PW_)                                                                          \
-  hipLaunchKernelGGL((k_backward<BF, HH, PRE_, PW_>), dim3(grid, n_seeds), dim3(256), sm, st, dD, a, c, D.B / SLAB, \
-                     D.ntrain)
-#define CALL(BF, HH)                                                  \
-  do {                                                                \
-    if constexpr (HH >= 128) {                                        \
-      if (pw == 2) { LAUNCH_B(BF, HH, false, 2); break; }             \
-    }                                                                 \
-    if (pre) LAUNCH_B(BF, HH, true, 1);                               \
-    else LAUNCH_B(BF, HH, false, 1);                                  \
-  } while (0)
-  if (counts) {
-#define LAUNCH_V(BF, HH, PRE_, PW_)                                                                                  \
-  hipLaunchKernelGGL((k_backward<BF, HH, PRE_, PW_, true>), dim3(grid, n_seeds), dim3(256), sm, st, dD, a, c, D.B / SLAB, \
-                     D.ntrain)
-#define CALL_V(BF, HH)                                                \
-  do {                                                                \
-    if constexpr (HH >= 128) {                                        \
-      if (pw == 2) { LAUNCH_V(BF, HH, false, 2); break; }             \
-    }                                                                 \
-    if (pre) LAUNCH_V(BF, HH, true, 1);                               \
-    else LAUNCH_V(BF, HH, false, 1);                                  \
-  } while (0)
-    DISPATCH_H(bf16, D.H, CALL_V);
-#undef CALL_V
-#undef LAUNCH_V
-    return hipGetLastError();
-  }
-  DISPATCH_H(bf16, D.H, CALL);
-#undef CALL
-#undef LAUNCH_B
+  dispatch_h(bf16, D.H, [&](auto BF, auto HH) {
+    with_const<true, false>(counts, [&](auto NV) {
+      auto go = [&](auto PRE, auto PW) {
+        hipLaunchKernelGGL((k_backward<CV(BF), CV(HH), CV(PRE), CV(PW), CV(NV)>), dim3(grid, n_seeds), dim3(256), sm,
+                           st, dD, a, c, D.B / SLAB, D.ntrain);
+      };
+      if constexpr (CV(HH) >= 128) {  // (two parts per work-group: never instantiated at H = 64)
+        if (pw == 2) return go(Bool<false>{}, Int<2>{});
+      }
+      with_const<true, false>(pre, [&](auto PRE) { go(PRE, Int<1>{}); });
+    });
+  });
   return hipGetLastError();
 }
 hipError_t launch_stage(bool bf16, const TrainerDesc &D, const TrainerDesc *dD, const DevArgs *a,
@@ -2840,18 +2811,18 @@ hipError_t launch_update(bool bf16, const TrainerDesc *dD, const DevArgs *a, Dev
   }();
   const bool lat = n_seeds == 1 && n_items + 1 <= cus + 1;
   // padded: the batch has rows that do not count (D.NB < D.B); the fp32 kernels read the count as it is
-  if (bf16 && padded && !lat)
-    hipLaunchKernelGGL((k_update<true, false, true>), grid, dim3(256), 0, st, dD, a, c, items, n_items);
-  else if (bf16 && padded)
-    hipLaunchKernelGGL((k_update<true, true, true>), grid, dim3(512), 0, st, dD, a, c, items, n_items);
-  else if (bf16 && !lat)
-    hipLaunchKernelGGL((k_update<true, false>), grid, dim3(256), 0, st, dD, a, c, items, n_items);
-  else if (bf16)
-    hipLaunchKernelGGL((k_update<true, true>), grid, dim3(512), 0, st, dD, a, c, items, n_items);
-  else if (!lat)
-    hipLaunchKernelGGL((k_update<false, false>), grid, dim3(256), 0, st, dD, a, c, items, n_items);
-  else
-    hipLaunchKernelGGL((k_update<false, true>), grid, dim3(512), 0, st, dD, a, c, items, n_items);
+  with_const<true, false>(bf16, [&](auto BF) {
+    with_const<true, false>(lat, [&](auto LAT) {
+      auto go = [&](auto CNT) {
+        hipLaunchKernelGGL((k_update<CV(BF), CV(LAT), CV(CNT)>), grid, dim3(CV(LAT) ? 512 : 256), 0, st, dD, a, c,
+                           items, n_items);
+      };
+      if constexpr (CV(BF)) {  // (the counted variant: bf16 only)
+        if (padded) return go(Bool<true>{});
+      }
+      go(Bool<false>{});
+    });
+  });
   return hipGetLastError();
 }
 hipError_t launch_infer(bool bf16, const TrainerDesc &D, const TrainerDesc *dD, const FwdNet &N,
@@ -2859,10 +2830,9 @@ hipError_t launch_infer(bool bf16, const TrainerDesc &D, const TrainerDesc *dD, 
                         hipStream_t st) {
   const int grid = (int)((n + SLAB - 1) / SLAB);
   const size_t sm = infer_smem_bytes(bf16, D.H, D.k1max);
-#define CALL(BF, HH) \
-  hipLaunchKernelGGL((k_infer<BF, HH>), dim3(grid), dim3(256), sm, st, dD, N, s, a, n, out, out_stride)
-  DISPATCH_H(bf16, D.H, CALL);
-#undef CALL
+  dispatch_h(bf16, D.H, [&](auto BF, auto HH) {
+    hipLaunchKernelGGL((k_infer<CV(BF), CV(HH)>), dim3(grid), dim3(256), sm, st, dD, N, s, a, n, out, out_stride);
+  });
   return hipGetLastError();
 }
 hipError_t launch_sync_weights(bool bf16, const TrainerDesc *dD, hipStream_t st) {
