@@ -1,5 +1,10 @@
-// Host side of libiqlhip.so: the extern "C" entry points of include/iqlhip.h,
-// trainer workspace management, hipGraph capture of the step sequence.
+// The training-step driver of libiqlhip.so: the lifecycle of trainers and seed groups, their workspaces, how
+// steps reach a stream (StepQueue: pinned argument rings, hipGraph capture, padding, the throttle), the two
+// step kinds (run_tuned, deep_run) -- and the entry points that read a trainer's config or arena layout
+// (iqlhip_forward, iqlhip_explore_action*, iqlhip_arena_layout, iqlhip_step_cost), the CU-slice streams, the
+// error text, ABI version and build tag.  Every other entry point of include/iqlhip.h sits in the .hip file
+// of the kernels it launches; what one file calls in another is declared once, in iql_step.h, iql_deep.h or
+// launchers.h, which both sides include.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -13,125 +18,24 @@
 
 #include "../../include/iqlhip.h"
 #include "common.h"
+#include "errors.h"
 #include "host_plan.h"
 #include "iql_deep.h"
 #include "iql_step.h"
+#include "launchers.h"
 #include "step_math.h"
-
-namespace iqlhip {
-// the general layer-wise step (iql_deep.hip)
-struct DeepTrainer;
-bool deep_shape_ok(const iqlhip_trainer_config &, int n_hidden, const char **why);
-hipError_t deep_create(DeepTrainer **, const iqlhip_trainer_config &, const StepShape &, const iqlhip_arenas &,
-                       const int64_t *offsets);
-void deep_destroy(DeepTrainer *);
-hipError_t deep_sync_weights(DeepTrainer *, hipStream_t);
-const DeepDesc &deep_desc(const DeepTrainer *);
-const DeepDesc *deep_desc_dev(const DeepTrainer *);
-hipError_t deep_step(const DeepTrainer *, const DeepDesc *, const DeepArgs *, DeepCtr *, const AdamCoef *coefs, int K,
-                     hipStream_t, hipEvent_t *ev);
-hipError_t deep_infer(DeepTrainer *, int which, const float *s, const float *a, int64_t n, float *out, hipStream_t);
-int layer2_parts(int H);
-hipError_t launch_forward(bool, const TrainerDesc &, const TrainerDesc *, const DevArgs *, const DevCtr *,
-                          int n_seeds, hipStream_t);
-hipError_t launch_backward(bool, const TrainerDesc &, const TrainerDesc *, const DevArgs *, DevCtr *,
-                           int n_seeds, hipStream_t, bool counts = false);
-hipError_t launch_stage(bool, const TrainerDesc &, const TrainerDesc *, const DevArgs *, const DevCtr *,
-                        int n_seeds, hipStream_t);
-int strip_rows();
-int update_lds_floats();
-hipError_t launch_update(bool, const TrainerDesc *, const DevArgs *, DevCtr *, const UpdItem *, int,
-                         int n_seeds, hipStream_t, bool padded = false);
-hipError_t launch_pad_rows(const void *src, void *dst, int64_t n, int rows, int rows_padded, int row_bytes, hipStream_t);
-hipError_t launch_sync_weights(bool, const TrainerDesc *, hipStream_t);
-hipError_t prepare_step_kernels();
-
-hipError_t launch_infer(bool, const TrainerDesc &, const TrainerDesc *, const FwdNet &, const float *,
-                        const float *, int64_t, float *, int, hipStream_t);
-
-hipError_t launch_pack(float *rows, int stride, int S, int A, int64_t first, int64_t n, const float *obs,
-                       const float *act, const float *rew, const float *nxt, const float *done,
-                       hipStream_t st);
-hipError_t launch_sample(const iqlhip_replay_view &v, int batch, const int64_t *idx, uint64_t seed,
-                         uint64_t step, float *s, float *a, float *r, float *s2, float *d,
-                         int64_t *idx_out, hipStream_t st);
-hipError_t launch_mlp_f32(const iqlhip_mlp_desc &d, const float *x, int64_t n, int x_stride, float *out,
-                          int out_stride, hipStream_t st);
-hipError_t mlp_set_create(const iqlhip_mlp_desc *const *descs, int M, iqlhip_mlp_set **out, hipStream_t st);
-hipError_t mlp_set_destroy(iqlhip_mlp_set *s);
-void mlp_set_shape(const iqlhip_mlp_set *s, int *M, int *in, int *out, int *device);
-hipError_t launch_mlp_set(const iqlhip_mlp_set *s, const float *x, int R, int x_stride, float *out, int out_stride,
-                          hipStream_t st);
-hipError_t launch_cvar(const float *preds, int S, int64_t N, int n_tail, float *out, hipStream_t st);
-hipError_t launch_keep_steps(const uint8_t *term, const uint8_t *tmo, int64_t n, int64_t M, int toe,
-                             uint8_t *keep, int64_t *ep_steps, hipStream_t st);
-hipError_t launch_reward_range(const float *rew, const uint8_t *term, int64_t n, int64_t M, double *trj_lens,
-                               double *out3, hipStream_t st);
-hipError_t launch_modify_reward(float *rew, int64_t n, const double *trj_lens, int sub_first, int scale,
-                                int sub_one, double min_ret, double range, float steps, hipStream_t st);
-hipError_t launch_state_stats(const float *x, int64_t n, int S, double eps, float *mean_f, float *std_f,
-                              hipStream_t st);
-hipError_t launch_pack_norm(float *rows, int stride, int S, int A, int64_t first, int64_t n, const float *obs,
-                            const float *act, const float *rew, const float *nxt, const float *done,
-                            const float *mean, const float *sd, hipStream_t st);
-size_t pt_smem_bytes(const iqlhip_pt_weights &W, int ql);
-hipError_t launch_pt(const iqlhip_pt_weights &W, const float *obs, const float *act, int64_t n_rows,
-                     const int64_t *win_start, const int32_t *win_len, const int32_t *win_t0, int64_t n_win,
-                     int ql, float *out, hipStream_t st);
-size_t pt_general_bytes(const iqlhip_pt_model &m, int ql, int64_t nw);
-int64_t pt_general_fit(const iqlhip_pt_model &m, int ql, size_t bytes);
-int pt_general_tp(int ql);
-hipError_t launch_pt_general(const iqlhip_pt_model &m, const float *obs, const float *act, int64_t n_rows,
-                             const int64_t *win_start, const int32_t *win_len, const int32_t *win_t0,
-                             int64_t n_win, int ql, float *ws, int64_t chunk, float *out, hipStream_t st);
-hipError_t launch_block_epoch(const int64_t *perm, int64_t n_rows, int batch, int64_t t0, int64_t n_steps, int64_t *idx,
-                              int32_t *n_valid, hipStream_t st);
-hipError_t launch_block_epoch_group(const int64_t *const *perm, int64_t n_rows, int batch, int64_t t0, int64_t n_steps,
-                                    int64_t *const *idx, int32_t *n_valid, int K, hipStream_t st);
-hipError_t launch_replay_append(float *rows, int stride, int S, int A, int64_t pointer, int64_t capacity, int64_t n,
-                                const float *obs, const float *act, const float *rew, const float *nxt,
-                                const float *done, hipStream_t st);
-hipError_t launch_np_randint_growing(uint32_t *state, const int64_t *hi0, const int64_t *cap, int growth, int K,
-                                     int batch, int64_t n_steps, int64_t *const *out, hipStream_t st);
-hipError_t launch_explore_epilogue(float *act, int64_t rows, int A, const float *log_std, const float *eps,
-                                   float expl_noise, float noise_clip, float max_action, uint64_t seed, uint32_t call,
-                                   hipStream_t st);
-hipError_t launch_np_randint(uint32_t *state, const int64_t *hi, int K, int64_t total, int64_t *const *out,
-                             hipStream_t st);
-hipError_t launch_replay_append_group(float *const *rows, int stride, int S, int A, const int64_t *capacity,
-                                      const int64_t *pointer, int K, const float *stage, hipStream_t st);
-hipError_t launch_explore_group(const iqlhip_mlp_desc *actors, const float *const *log_std, int K, const float *s,
-                                int s_stride, const float *eps, float expl_noise, float noise_clip, float max_action,
-                                float *out, hipStream_t st);
-hipError_t launch_bb_step(const iqlhip_bb_sim &sim, int reset, hipStream_t st);
-size_t bb_episodes_scratch_bytes(const iqlhip_mlp_desc *const *actors, int n);
-hipError_t launch_bb_episodes(const iqlhip_bb_sim *sims, const iqlhip_mlp_desc *const *actors, int n, void *scratch,
-                              hipStream_t st);
-size_t choice_workspace_bytes(int64_t N, int n);
-int64_t choice_fit_rows(int64_t N, int n, size_t bytes);
-hipError_t launch_posterior_choice(uint32_t *state, const float *preds, int S, int64_t N, int n, int mode,
-                                   float *out, uint16_t *idx_out, uint16_t *ws, int64_t slot_rows,
-                                   hipStream_t st);
-}  // namespace iqlhip
 
 using namespace iqlhip;
 
 // ------------------------------------------------------------------ errors --
 static thread_local char g_err[512] = "";
-static int fail(int code, const char *fmt, ...) {
+int iqlhip::fail(int code, const char *fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
   va_end(ap);
   return code;
 }
-#define HIP_TRY(expr)                                                                         \
-  do {                                                                                        \
-    hipError_t e_ = (expr);                                                                   \
-    if (e_ != hipSuccess)                                                                     \
-      return fail(IQLHIP_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, \
-                  __LINE__);                                                                  \
-  } while (0)
 
 extern "C" const char *iqlhip_last_error(void) { return g_err; }
 // One capture-only stream per host thread and device, kept for the life of the process (stream
@@ -160,93 +64,6 @@ extern "C" int iqlhip_abi_version(void) { return 6; }
 #endif
 static const char g_build_tag[] = "IQLHIP_BUILD_TAG=" IQLHIP_BUILD_TAG;  // marker: build.py reads it from the file
 extern "C" const char *iqlhip_build_tag(void) { return g_build_tag + sizeof("IQLHIP_BUILD_TAG=") - 1; }
-
-// ------------------------------------------------------------------ replay --
-// Packed replay row: [ s(S) | a(A) | r | d | pad | s'(S) | pad ], s' on a 16-byte boundary
-extern "C" int32_t iqlhip_replay_next_offset(int32_t S, int32_t A) { return round_up(S + A + 2, 4); }
-extern "C" int32_t iqlhip_replay_row_stride(int32_t S, int32_t A) {
-  return round_up(iqlhip_replay_next_offset(S, A) + S, 4);
-}
-
-extern "C" int iqlhip_replay_pack(float *rows, int32_t row_stride, int32_t S, int32_t A, int64_t first_row,
-                                  int64_t n, const float *obs, const float *act, const float *rew,
-                                  const float *next_obs, const float *done, void *stream) {
-  if (!rows || !obs || !act || !rew || !next_obs || !done) return fail(IQLHIP_ERR_INVALID, "null pointer");
-  if (S <= 0 || A <= 0 || n < 0 || first_row < 0 || row_stride < iqlhip_replay_row_stride(S, A) || (row_stride & 3))
-    return fail(IQLHIP_ERR_INVALID, "bad replay geometry S=%d A=%d stride=%d", S, A, row_stride);
-  if (n == 0) return 0;
-  HIP_TRY(launch_pack(rows, row_stride, S, A, first_row, n, obs, act, rew, next_obs, done,
-                      (hipStream_t)stream));
-  return 0;
-}
-
-extern "C" int iqlhip_replay_pack_normalized(float *rows, int32_t row_stride, int32_t S, int32_t A,
-                                             int64_t first_row, int64_t n, const float *obs, const float *act,
-                                             const float *rew, const float *next_obs, const float *done,
-                                             const float *mean, const float *std, void *stream) {
-  if (!rows || !obs || !act || !rew || !next_obs || !done || !mean || !std)
-    return fail(IQLHIP_ERR_INVALID, "null pointer");
-  if (S <= 0 || A <= 0 || n < 0 || first_row < 0 || row_stride < iqlhip_replay_row_stride(S, A) || (row_stride & 3))
-    return fail(IQLHIP_ERR_INVALID, "bad replay geometry S=%d A=%d stride=%d", S, A, row_stride);
-  if (n == 0) return 0;
-  HIP_TRY(launch_pack_norm(rows, row_stride, S, A, first_row, n, obs, act, rew, next_obs, done, mean, std,
-                           (hipStream_t)stream));
-  return 0;
-}
-
-// ------------------------------------------------------- dataset preparation --
-extern "C" int iqlhip_prep_keep_mask(const uint8_t *terminals, const uint8_t *timeouts, int64_t n,
-                                     int32_t max_episode_steps, int32_t terminate_on_end, uint8_t *keep,
-                                     int64_t *ep_steps, void *stream) {
-  if (!terminals || !keep || !ep_steps) return fail(IQLHIP_ERR_INVALID, "null pointer");
-  if (n < 1) return fail(IQLHIP_ERR_INVALID, "n must be >= 1");
-  if (!timeouts && max_episode_steps < 1) return fail(IQLHIP_ERR_INVALID, "max_episode_steps must be >= 1");
-  HIP_TRY(launch_keep_steps(terminals, timeouts, n, max_episode_steps, terminate_on_end != 0, keep, ep_steps,
-                            (hipStream_t)stream));
-  return 0;
-}
-
-extern "C" int iqlhip_prep_reward_range(const float *rewards, const uint8_t *terminals, int64_t n,
-                                        int32_t max_episode_steps, double *trj_lens, double *min_ret,
-                                        double *max_ret, void *stream) {
-  if (!rewards || !terminals || !trj_lens || !min_ret || !max_ret) return fail(IQLHIP_ERR_INVALID, "null pointer");
-  if (n < 1 || max_episode_steps < 1) return fail(IQLHIP_ERR_INVALID, "n and max_episode_steps must be >= 1");
-  double out3[3];
-  HIP_TRY(launch_reward_range(rewards, terminals, n, max_episode_steps, trj_lens, out3, (hipStream_t)stream));
-  if (out3[2] == 0.0) return fail(IQLHIP_ERR_INVALID, "dataset holds no complete episode");
-  *min_ret = out3[0], *max_ret = out3[1];
-  return 0;
-}
-
-extern "C" int iqlhip_prep_modify_reward(float *rewards, int64_t n, const double *trj_lens, int32_t sub_first,
-                                         int32_t scale, int32_t sub_one, double min_ret, double max_ret,
-                                         int32_t max_episode_steps, void *stream) {
-  if (!rewards) return fail(IQLHIP_ERR_INVALID, "null pointer");
-  if (sub_first < 0 || sub_first > 2) return fail(IQLHIP_ERR_INVALID, "sub_first must be 0, 1 or 2");
-  if (sub_first == 2 && !trj_lens) return fail(IQLHIP_ERR_INVALID, "sub_first = 2 needs trj_lens");
-  if (n <= 0) return 0;
-  HIP_TRY(launch_modify_reward(rewards, n, trj_lens, sub_first, scale != 0, sub_one != 0, min_ret,
-                               max_ret - min_ret, (float)max_episode_steps, (hipStream_t)stream));
-  return 0;
-}
-
-extern "C" int iqlhip_prep_state_stats(const float *obs, int64_t n, int32_t state_dim, double eps, float *mean,
-                                       float *std, void *stream) {
-  if (!obs || !mean || !std) return fail(IQLHIP_ERR_INVALID, "null pointer");
-  if (n < 1 || state_dim < 1 || state_dim > 256) return fail(IQLHIP_ERR_UNSUPPORTED, "n >= 1, 1 <= state_dim <= 256");
-  HIP_TRY(launch_state_stats(obs, n, state_dim, eps, mean, std, (hipStream_t)stream));
-  return 0;
-}
-
-extern "C" int iqlhip_replay_sample(const iqlhip_replay_view *view, int32_t batch, const int64_t *idx,
-                                    uint64_t seed, uint64_t step, float *s, float *a, float *r, float *s2,
-                                    float *d, int64_t *idx_out, void *stream) {
-  if (!view || !view->rows || !s || !a || !r || !s2 || !d) return fail(IQLHIP_ERR_INVALID, "null pointer");
-  if (batch <= 0) return fail(IQLHIP_ERR_INVALID, "batch must be positive");
-  if (view->n_rows <= 0) return fail(IQLHIP_ERR_INVALID, "cannot sample from an empty replay buffer");
-  HIP_TRY(launch_sample(*view, batch, idx, seed, step, s, a, r, s2, d, idx_out, (hipStream_t)stream));
-  return 0;
-}
 
 // ----------------------------------------------------------------- trainer --
 static void group_invalidate(struct iqlhip_group *g);
@@ -1263,7 +1080,7 @@ extern "C" int iqlhip_train_batch(iqlhip_trainer *t, const float *s, const float
   if (!t || !s || !a || !r || !s2 || !d) return fail(IQLHIP_ERR_INVALID, "null argument");
   const int S = t->cfg.state_dim, A = t->cfg.action_dim, B = t->cfg.batch_size;
   const int stride = iqlhip_replay_row_stride(S, A);
-  HIP_TRY(launch_pack(t->batch_rows, stride, S, A, 0, B, s, a, r, s2, d, (hipStream_t)stream));
+  if (int rc = iqlhip_replay_pack(t->batch_rows, stride, S, A, 0, B, s, a, r, s2, d, stream)) return rc;
   const iqlhip_replay_view rows = {t->batch_rows, B, stride, S, A, 0};
   DevArgs args = make_args(t, rows, 1, nullptr, nullptr, dropout_keep, losses_out);
   args.idx_mode = 2;  // the rows as they lie (a padding row: clamped to the last one)
@@ -1549,81 +1366,6 @@ extern "C" int iqlhip_forward(iqlhip_trainer *t, int32_t which, const float *s, 
   }
 }
 
-extern "C" int iqlhip_mlp_forward(const iqlhip_mlp_desc *d, const float *x, int64_t n, int32_t x_stride,
-                                  float *out, int32_t out_stride, void *stream) {
-  if (!d || !x || !out) return fail(IQLHIP_ERR_INVALID, "null argument");
-  if (n <= 0) return fail(IQLHIP_ERR_INVALID, "n must be positive");
-  if (d->n_layers < 1 || d->n_layers > IQLHIP_MLP_MAX_LAYERS)
-    return fail(IQLHIP_ERR_INVALID, "n_layers must be in [1, %d]", IQLHIP_MLP_MAX_LAYERS);
-  for (int i = 0; i <= d->n_layers; ++i)
-    if (d->dims[i] <= 0 || d->dims[i] > 1024)
-      return fail(IQLHIP_ERR_UNSUPPORTED, "layer width %d outside [1, 1024]", d->dims[i]);
-  for (int i = 0; i < d->n_layers; ++i)
-    if (!d->weights[i] || !d->biases[i]) return fail(IQLHIP_ERR_INVALID, "null weight pointer");
-  for (int a : {d->hidden_act, d->out_act})
-    if (a < 0 || (a > 1 && a < 8) || a > 15) return fail(IQLHIP_ERR_INVALID, "activation code %d", a);
-  if (x_stride < d->dims[0] || out_stride < d->dims[d->n_layers])
-    return fail(IQLHIP_ERR_INVALID, "stride smaller than the row width");
-  if (!(d->dropout_p < 1.0f)) return fail(IQLHIP_ERR_INVALID, "dropout_p must be < 1");
-  if (d->dropout_p > 0.f && n > 0xffffffffLL) return fail(IQLHIP_ERR_UNSUPPORTED, "dropout: n must fit 32 bits");
-  HIP_TRY(launch_mlp_f32(*d, x, n, x_stride, out, out_stride, (hipStream_t)stream));
-  return 0;
-}
-
-extern "C" int iqlhip_mlp_set_create(const iqlhip_mlp_desc *const *descs, int32_t M, iqlhip_mlp_set **out,
-                                     void *stream) {
-  if (!descs || !out) return fail(IQLHIP_ERR_INVALID, "null argument");
-  if (M < 1 || M > IQLHIP_MLP_SET_MAX)
-    return fail(IQLHIP_ERR_INVALID, "M = %d outside [1, %d]", M, IQLHIP_MLP_SET_MAX);
-  for (int m = 0; m < M; ++m)
-    if (!descs[m]) return fail(IQLHIP_ERR_INVALID, "member %d: null descriptor", m);
-  const iqlhip_mlp_desc &d0 = *descs[0];
-  if (d0.n_layers < 1 || d0.n_layers > IQLHIP_MLP_MAX_LAYERS)
-    return fail(IQLHIP_ERR_INVALID, "n_layers must be in [1, %d]", IQLHIP_MLP_MAX_LAYERS);
-  for (int i = 0; i <= d0.n_layers; ++i) {
-    if (d0.dims[i] <= 0) return fail(IQLHIP_ERR_INVALID, "layer width %d", d0.dims[i]);
-    if (d0.dims[i] > 256)
-      return fail(IQLHIP_ERR_UNSUPPORTED, "layer width %d > 256: iqlhip_mlp_forward takes it", d0.dims[i]);
-  }
-  for (int a : {d0.hidden_act, d0.out_act})
-    if (a < 0 || (a > 1 && a < 8) || a > 15) return fail(IQLHIP_ERR_INVALID, "activation code %d", a);
-  for (int m = 0; m < M; ++m) {
-    const iqlhip_mlp_desc &d = *descs[m];
-    bool same = d.n_layers == d0.n_layers && d.w_in_out == d0.w_in_out && d.hidden_act == d0.hidden_act &&
-                d.out_act == d0.out_act;
-    for (int i = 0; same && i <= d0.n_layers; ++i) same = d.dims[i] == d0.dims[i];
-    if (!same) return fail(IQLHIP_ERR_INVALID, "member %d differs from member 0 in shape, activation or layout", m);
-    for (int i = 0; i < d.n_layers; ++i)
-      if (!d.weights[i] || !d.biases[i]) return fail(IQLHIP_ERR_INVALID, "member %d: null weight pointer", m);
-    if (d.dropout_p > 0.f)
-      return fail(IQLHIP_ERR_UNSUPPORTED, "member %d: dropout_p > 0 (the set is an eval-mode forward)", m);
-  }
-  iqlhip_mlp_set *s = nullptr;
-  HIP_TRY(mlp_set_create(descs, M, &s, (hipStream_t)stream));
-  *out = s;
-  return 0;
-}
-
-extern "C" int iqlhip_mlp_set_destroy(iqlhip_mlp_set *set) {
-  if (!set) return fail(IQLHIP_ERR_INVALID, "null set");
-  HIP_TRY(mlp_set_destroy(set));
-  return 0;
-}
-
-extern "C" int iqlhip_mlp_set_forward(const iqlhip_mlp_set *set, const float *x, int32_t R, int32_t x_stride,
-                                      float *out, int32_t out_stride, void *stream) {
-  if (!set || !x || !out) return fail(IQLHIP_ERR_INVALID, "null argument");
-  if (R < 1) return fail(IQLHIP_ERR_INVALID, "R = %d must be positive", R);
-  int M, in, width, device, current;
-  mlp_set_shape(set, &M, &in, &width, &device);
-  if (x_stride < in || out_stride < width) return fail(IQLHIP_ERR_INVALID, "stride smaller than the row width");
-  HIP_TRY(hipGetDevice(&current));  // (no launch, no wait: the set's images live on one device)
-  if (current != device)
-    return fail(IQLHIP_ERR_INVALID, "the set lives on device %d, the current device is %d", device, current);
-  HIP_TRY(launch_mlp_set(set, x, R, x_stride, out, out_stride, (hipStream_t)stream));
-  return 0;
-}
-
 // Diagnostic: attach a device buffer [3][512][8][2] u64 for IQL_STAMPS builds.
 extern "C" int iqlhip_trainer_set_debug(iqlhip_trainer *t, void *buf) {
   if (!t) return fail(IQLHIP_ERR_INVALID, "null trainer");
@@ -1634,88 +1376,7 @@ extern "C" int iqlhip_trainer_set_debug(iqlhip_trainer *t, void *buf) {
   return 0;
 }
 
-extern "C" int iqlhip_cvar_tail_mean(const float *preds, int32_t S, int64_t N, int32_t n_tail, float *out,
-                                     void *stream) {
-  if (!preds || !out) return fail(IQLHIP_ERR_INVALID, "null argument");
-  if (S < 1 || N < 1) return fail(IQLHIP_ERR_INVALID, "S and N must be positive");
-  if (n_tail < 1 || n_tail > S) return fail(IQLHIP_ERR_INVALID, "n_tail must be in [1, S]");
-  if (S > 2400) return fail(IQLHIP_ERR_UNSUPPORTED, "S = %d > 2400", S);
-  HIP_TRY(launch_cvar(preds, S, N, n_tail, out, (hipStream_t)stream));
-  return 0;
-}
-
-// ------------------------------------------------------- numpy index stream --
-extern "C" int iqlhip_np_randint(uint32_t *state, const int64_t *hi, int32_t K, int32_t batch,
-                                 int64_t n_batches, int64_t *const *out, void *stream) {
-  if (!state || !hi || !out) return fail(IQLHIP_ERR_INVALID, "null argument");
-  if (K < 1 || K > IQLHIP_MAX_GROUP) return fail(IQLHIP_ERR_INVALID, "K = %d: 1..%d streams", K, IQLHIP_MAX_GROUP);
-  if (batch < 1) return fail(IQLHIP_ERR_INVALID, "batch = %d must be >= 1", batch);
-  if (n_batches < 0) return fail(IQLHIP_ERR_INVALID, "n_batches = %lld must be >= 0", (long long)n_batches);
-  for (int k = 0; k < K; ++k) {
-    if (hi[k] < 1 || hi[k] > (int64_t(1) << 32))
-      return fail(IQLHIP_ERR_INVALID, "hi[%d] = %lld outside 1..2^32", k, (long long)hi[k]);
-    if (!out[k]) return fail(IQLHIP_ERR_INVALID, "null out[%d]", k);
-  }
-  // pos of every state: one strided copy of the K words, then the stream is synchronised
-  hipStream_t st = (hipStream_t)stream;
-  uint32_t pos[IQLHIP_MAX_GROUP];
-  HIP_TRY(hipMemcpy2DAsync(pos, sizeof(uint32_t), state + 624, 625 * sizeof(uint32_t), sizeof(uint32_t), K,
-                           hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  for (int k = 0; k < K; ++k)
-    if (pos[k] > 624) return fail(IQLHIP_ERR_INVALID, "state %d: pos = %u outside 0..624", k, pos[k]);
-  if (n_batches == 0) return 0;
-  HIP_TRY(launch_np_randint(state, hi, K, n_batches * (int64_t)batch, out, st));
-  return 0;
-}
-
-// ------------------------------------------------------- online fine-tuning --
-extern "C" int iqlhip_replay_append(float *rows, int32_t row_stride, int32_t S, int32_t A, int64_t capacity,
-                                    int64_t pointer, int64_t n, const float *obs, const float *act, const float *rew,
-                                    const float *next_obs, const float *done, void *stream) {
-  if (!rows || !obs || !act || !rew || !next_obs || !done) return fail(IQLHIP_ERR_INVALID, "null pointer");
-  if (S <= 0 || A <= 0 || row_stride < iqlhip_replay_row_stride(S, A) || (row_stride & 3))
-    return fail(IQLHIP_ERR_INVALID, "bad replay geometry S=%d A=%d stride=%d", S, A, row_stride);
-  if ((uintptr_t)rows & 15) return fail(IQLHIP_ERR_INVALID, "rows must start on a 16-byte boundary");
-  if (capacity < 1) return fail(IQLHIP_ERR_INVALID, "capacity = %lld must be >= 1", (long long)capacity);
-  if (pointer < 0 || pointer >= capacity)
-    return fail(IQLHIP_ERR_INVALID, "pointer = %lld outside 0..%lld", (long long)pointer, (long long)capacity - 1);
-  if (n < 1) return fail(IQLHIP_ERR_INVALID, "n = %lld must be >= 1", (long long)n);
-  if (n > capacity)
-    return fail(IQLHIP_ERR_INVALID, "n = %lld transitions do not fit a ring of %lld rows", (long long)n,
-                (long long)capacity);
-  HIP_TRY(launch_replay_append(rows, row_stride, S, A, pointer, capacity, n, obs, act, rew, next_obs, done,
-                               (hipStream_t)stream));
-  return 0;
-}
-
-extern "C" int iqlhip_np_randint_growing(uint32_t *state, const int64_t *hi0, const int64_t *cap, int32_t growth,
-                                         int32_t K, int32_t batch, int64_t n_steps, int64_t *const *out,
-                                         void *stream) {
-  if (!state || !hi0 || !cap || !out) return fail(IQLHIP_ERR_INVALID, "null argument");
-  if (K < 1 || K > IQLHIP_MAX_GROUP) return fail(IQLHIP_ERR_INVALID, "K = %d: 1..%d streams", K, IQLHIP_MAX_GROUP);
-  if (batch < 1) return fail(IQLHIP_ERR_INVALID, "batch = %d must be >= 1", batch);
-  if (n_steps < 0) return fail(IQLHIP_ERR_INVALID, "n_steps = %lld must be >= 0", (long long)n_steps);
-  if (growth != 0 && growth != 1) return fail(IQLHIP_ERR_INVALID, "growth = %d must be 0 or 1", growth);
-  for (int k = 0; k < K; ++k) {
-    if (hi0[k] < 1 || hi0[k] > (int64_t(1) << 32))
-      return fail(IQLHIP_ERR_INVALID, "hi0[%d] = %lld outside 1..2^32", k, (long long)hi0[k]);
-    if (cap[k] < hi0[k] || cap[k] > (int64_t(1) << 32))
-      return fail(IQLHIP_ERR_INVALID, "cap[%d] = %lld outside hi0..2^32", k, (long long)cap[k]);
-    if (!out[k]) return fail(IQLHIP_ERR_INVALID, "null out[%d]", k);
-  }
-  hipStream_t st = (hipStream_t)stream;
-  uint32_t pos[IQLHIP_MAX_GROUP];
-  HIP_TRY(hipMemcpy2DAsync(pos, sizeof(uint32_t), state + 624, 625 * sizeof(uint32_t), sizeof(uint32_t), K,
-                           hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  for (int k = 0; k < K; ++k)
-    if (pos[k] > 624) return fail(IQLHIP_ERR_INVALID, "state %d: pos = %u outside 0..624", k, pos[k]);
-  if (n_steps == 0) return 0;
-  HIP_TRY(launch_np_randint_growing(state, hi0, cap, growth, K, batch, n_steps, out, st));
-  return 0;
-}
-
+// ------------------------------------------------------ exploration action --
 // The actor of a trainer as launch_mlp_f32 takes it: the fp32 masters of the parameter arena where they lie
 // (what every step's update writes: nothing is copied, nothing can go stale), for the tuned and the general
 // step alike.  log_std: NULL for a deterministic policy.
@@ -1790,304 +1451,5 @@ extern "C" int iqlhip_explore_action_group(iqlhip_trainer *const *trainers, int3
   for (int k = 0; k < K; ++k) actors[k] = explore_actor(trainers[k], calls[k], &log_std[k]);
   HIP_TRY(launch_explore_group(actors, log_std, K, s, s_stride, eps, expl_noise, noise_clip, max_action, out,
                                (hipStream_t)stream));
-  return 0;
-}
-
-extern "C" int iqlhip_replay_append_group(float *const *rows, int32_t row_stride, int32_t S, int32_t A,
-                                          const int64_t *capacity, const int64_t *pointer, int32_t K,
-                                          const float *stage, void *stream) {
-  if (!rows || !capacity || !pointer || !stage) return fail(IQLHIP_ERR_INVALID, "null pointer");
-  if (K < 1 || K > IQLHIP_MAX_GROUP) return fail(IQLHIP_ERR_INVALID, "K = %d: 1..%d rings", K, IQLHIP_MAX_GROUP);
-  if (S <= 0 || A <= 0 || row_stride < iqlhip_replay_row_stride(S, A) || (row_stride & 3))
-    return fail(IQLHIP_ERR_INVALID, "bad replay geometry S=%d A=%d stride=%d", S, A, row_stride);
-  for (int k = 0; k < K; ++k) {
-    if (!rows[k]) return fail(IQLHIP_ERR_INVALID, "null rows[%d]", k);
-    if ((uintptr_t)rows[k] & 15) return fail(IQLHIP_ERR_INVALID, "rows[%d] must start on a 16-byte boundary", k);
-    if (capacity[k] < 1) return fail(IQLHIP_ERR_INVALID, "capacity[%d] = %lld must be >= 1", k, (long long)capacity[k]);
-    if (pointer[k] < 0 || pointer[k] >= capacity[k])
-      return fail(IQLHIP_ERR_INVALID, "pointer[%d] = %lld outside 0..%lld", k, (long long)pointer[k],
-                  (long long)capacity[k] - 1);
-    for (int j = 0; j < k; ++j)
-      if (rows[j] == rows[k]) return fail(IQLHIP_ERR_INVALID, "ring %d listed twice", k);
-  }
-  HIP_TRY(launch_replay_append_group(rows, row_stride, S, A, capacity, pointer, K, stage, (hipStream_t)stream));
-  return 0;
-}
-
-// ------------------------------------------------------- block-shuffled epochs --
-extern "C" int iqlhip_block_epoch_indices(const int64_t *perm, int64_t n_rows, int32_t batch, int64_t t0,
-                                          int64_t n_steps, int64_t *idx, int32_t *n_valid, void *stream) {
-  if (!idx || !n_valid) return fail(IQLHIP_ERR_INVALID, "null argument");
-  if (batch < 1) return fail(IQLHIP_ERR_INVALID, "batch = %d must be >= 1", batch);
-  if (n_rows < 1) return fail(IQLHIP_ERR_INVALID, "n_rows = %lld must be >= 1", (long long)n_rows);
-  if (t0 < 0 || n_steps < 0)
-    return fail(IQLHIP_ERR_INVALID, "t0 = %lld and n_steps = %lld must be >= 0", (long long)t0, (long long)n_steps);
-  if (!perm && n_rows >= batch) return fail(IQLHIP_ERR_INVALID, "null perm with %lld whole blocks", (long long)(n_rows / batch));
-  if (n_steps == 0) return 0;
-  HIP_TRY(launch_block_epoch(perm, n_rows, batch, t0, n_steps, idx, n_valid, (hipStream_t)stream));
-  return 0;
-}
-
-extern "C" int iqlhip_block_epoch_indices_group(const int64_t *const *perm, int64_t n_rows, int32_t batch, int64_t t0,
-                                                int64_t n_steps, int64_t *const *idx, int32_t *n_valid, int32_t K,
-                                                void *stream) {
-  if (!idx || !n_valid) return fail(IQLHIP_ERR_INVALID, "null argument");
-  if (K < 1 || K > IQLHIP_MAX_GROUP) return fail(IQLHIP_ERR_INVALID, "K = %d: 1..%d members", K, IQLHIP_MAX_GROUP);
-  if (batch < 1) return fail(IQLHIP_ERR_INVALID, "batch = %d must be >= 1", batch);
-  if (n_rows < 1) return fail(IQLHIP_ERR_INVALID, "n_rows = %lld must be >= 1", (long long)n_rows);
-  if (t0 < 0 || n_steps < 0)
-    return fail(IQLHIP_ERR_INVALID, "t0 = %lld and n_steps = %lld must be >= 0", (long long)t0, (long long)n_steps);
-  for (int k = 0; k < K; ++k) {
-    if (!idx[k]) return fail(IQLHIP_ERR_INVALID, "null idx[%d]", k);
-    if ((!perm || !perm[k]) && n_rows >= batch)
-      return fail(IQLHIP_ERR_INVALID, "null perm[%d] with %lld whole blocks", k, (long long)(n_rows / batch));
-  }
-  if (n_steps == 0) return 0;
-  HIP_TRY(launch_block_epoch_group(perm, n_rows, batch, t0, n_steps, idx, n_valid, K, (hipStream_t)stream));
-  return 0;
-}
-
-// ------------------------------------------------------- BB evaluation simulator --
-static int bb_sim_check(const iqlhip_bb_sim *s) {
-  if (!s) return fail(IQLHIP_ERR_INVALID, "null simulator");
-  if (!s->state || !s->drift || !s->ctl || !s->obs_hist || !s->act_hist || !s->record || !s->actor_in ||
-      !s->actor_out || !s->state_mean || !s->state_std || !s->min_actions || !s->max_actions)
-    return fail(IQLHIP_ERR_INVALID, "null pointer in the simulator");
-  if (s->n_obs < 1 || s->n_obs > 1024) return fail(IQLHIP_ERR_UNSUPPORTED, "n_obs = %d outside 1..1024", s->n_obs);
-  const int near_max = s->n_obs < 16 ? s->n_obs : 16;
-  if (s->n_near < 1 || s->n_near > near_max)
-    return fail(IQLHIP_ERR_UNSUPPORTED, "n_near = %d outside 1..%d", s->n_near, near_max);
-  if (s->action_dim != 2)
-    return fail(IQLHIP_ERR_UNSUPPORTED, "action_dim = %d: the simulator's action is (speed, heading)", s->action_dim);
-  if (s->state_dim != 2 + 3 * s->n_near + 6)
-    return fail(IQLHIP_ERR_INVALID, "state_dim = %d, an observation of %d obstacles has %d columns", s->state_dim,
-                s->n_near, 2 + 3 * s->n_near + 6);
-  if (s->max_horizon < 1) return fail(IQLHIP_ERR_INVALID, "max_horizon = %d must be >= 1", s->max_horizon);
-  if (s->actor_out_stride != 0 && s->actor_out_stride < s->action_dim)
-    return fail(IQLHIP_ERR_INVALID, "actor_out_stride = %d must be 0 or >= 2", s->actor_out_stride);
-  return 0;
-}
-
-extern "C" int iqlhip_bb_sim_reset(const iqlhip_bb_sim *sim, void *stream) {
-  if (int rc = bb_sim_check(sim)) return rc;
-  HIP_TRY(launch_bb_step(*sim, 1, (hipStream_t)stream));
-  return 0;
-}
-
-extern "C" int iqlhip_bb_sim_step(const iqlhip_bb_sim *sim, void *stream) {
-  if (int rc = bb_sim_check(sim)) return rc;
-  HIP_TRY(launch_bb_step(*sim, 0, (hipStream_t)stream));
-  return 0;
-}
-
-extern "C" int iqlhip_bb_sim_rollout(const iqlhip_bb_sim *sim, const iqlhip_mlp_desc *actor, int32_t n_steps,
-                                     void *stream) {
-  if (int rc = bb_sim_check(sim)) return rc;
-  if (!actor) return fail(IQLHIP_ERR_INVALID, "null actor");
-  if (n_steps < 1) return fail(IQLHIP_ERR_INVALID, "n_steps = %d must be >= 1", n_steps);
-  if (sim->actor_out_stride != 0)
-    return fail(IQLHIP_ERR_INVALID, "a rollout reads the forward's live output row: actor_out_stride must be 0");
-  if (actor->n_layers < 1 || actor->n_layers > IQLHIP_MLP_MAX_LAYERS)
-    return fail(IQLHIP_ERR_INVALID, "n_layers must be in [1, %d]", IQLHIP_MLP_MAX_LAYERS);
-  if (actor->dims[0] != sim->state_dim || actor->dims[actor->n_layers] != sim->action_dim)
-    return fail(IQLHIP_ERR_INVALID, "the actor maps %d -> %d, the simulator needs %d -> %d", actor->dims[0],
-                actor->dims[actor->n_layers], sim->state_dim, sim->action_dim);
-  for (int i = 0; i < n_steps; ++i) {
-    if (int rc = iqlhip_mlp_forward(actor, sim->actor_in, 1, sim->state_dim, sim->actor_out, sim->action_dim, stream))
-      return rc;
-    HIP_TRY(launch_bb_step(*sim, 0, (hipStream_t)stream));
-  }
-  return 0;
-}
-
-// The envelope of k_bb_episodes' fused forward: that of k_mlp_f32 (widths <= 256, relu / tanh hidden layers,
-// no / tanh output, no dropout), two outputs
-static int bb_actor_check(const iqlhip_mlp_desc *a, int k) {
-  if (a->n_layers < 1 || a->n_layers > IQLHIP_MLP_MAX_LAYERS)
-    return fail(IQLHIP_ERR_INVALID, "actor %d: n_layers must be in [1, %d]", k, IQLHIP_MLP_MAX_LAYERS);
-  for (int i = 0; i <= a->n_layers; ++i) {
-    if (a->dims[i] < 1) return fail(IQLHIP_ERR_INVALID, "actor %d: layer width %d", k, a->dims[i]);
-    if (a->dims[i] > 256)
-      return fail(IQLHIP_ERR_UNSUPPORTED, "actor %d: layer width %d > 256, the fused forward's limit (the launch "
-                                          "pair of iqlhip_bb_sim_rollout takes wider actors)", k, a->dims[i]);
-  }
-  for (int i = 0; i < a->n_layers; ++i)
-    if (!a->weights[i] || !a->biases[i]) return fail(IQLHIP_ERR_INVALID, "actor %d: null weight pointer", k);
-  if (a->hidden_act < 0 || a->hidden_act > 1 || a->out_act < 0 || a->out_act > 1)
-    return fail(IQLHIP_ERR_UNSUPPORTED, "actor %d: activations %d / %d, the fused forward has relu or tanh hidden "
-                                        "layers and no or a tanh output", k, a->hidden_act, a->out_act);
-  if (a->dropout_p > 0.f)
-    return fail(IQLHIP_ERR_UNSUPPORTED, "actor %d: dropout_p > 0, the fused forward is an eval-mode forward", k);
-  return 0;
-}
-
-extern "C" int iqlhip_bb_sim_episodes_scratch_bytes(const iqlhip_mlp_desc *const *actors, int32_t n, size_t *bytes) {
-  if (!actors || !bytes) return fail(IQLHIP_ERR_INVALID, "null argument");
-  if (n < 1 || n > IQLHIP_MAX_GROUP) return fail(IQLHIP_ERR_INVALID, "n = %d: 1..%d episodes", n, IQLHIP_MAX_GROUP);
-  for (int k = 0; k < n; ++k)
-    if (actors[k])
-      if (int rc = bb_actor_check(actors[k], k)) return rc;
-  *bytes = bb_episodes_scratch_bytes(actors, n);
-  return 0;
-}
-
-extern "C" int iqlhip_bb_sim_episodes(const iqlhip_bb_sim *sims, const iqlhip_mlp_desc *const *actors, int32_t n,
-                                      void *scratch, size_t scratch_bytes, void *stream) {
-  if (!sims) return fail(IQLHIP_ERR_INVALID, "null simulators");
-  if (!actors) return fail(IQLHIP_ERR_INVALID, "null actors");
-  if (!scratch) return fail(IQLHIP_ERR_INVALID, "null scratch");
-  if (n < 1 || n > IQLHIP_MAX_GROUP) return fail(IQLHIP_ERR_INVALID, "n = %d: 1..%d episodes", n, IQLHIP_MAX_GROUP);
-  if ((uintptr_t)scratch & 15) return fail(IQLHIP_ERR_INVALID, "scratch must start on a 16-byte boundary");
-  for (int k = 0; k < n; ++k) {
-    if (int rc = bb_sim_check(sims + k)) return rc;
-    const iqlhip_mlp_desc *a = actors[k];
-    if (!a) {
-      if (sims[k].actor_out_stride == 0)
-        return fail(IQLHIP_ERR_INVALID, "episode %d: null actor and no injected table", k);
-      continue;
-    }
-    if (int rc = bb_actor_check(a, k)) return rc;
-    if (a->dims[0] != sims[k].state_dim || a->dims[a->n_layers] != sims[k].action_dim)
-      return fail(IQLHIP_ERR_INVALID, "actor %d maps %d -> %d, the simulator needs %d -> %d", k, a->dims[0],
-                  a->dims[a->n_layers], sims[k].state_dim, sims[k].action_dim);
-  }
-  const size_t need = bb_episodes_scratch_bytes(actors, n);
-  if (scratch_bytes < need)
-    return fail(IQLHIP_ERR_INVALID, "scratch of %zu bytes, %d episodes need %zu (iqlhip_bb_sim_episodes_scratch_bytes)",
-                scratch_bytes, n, need);
-  HIP_TRY(launch_bb_episodes(sims, actors, n, scratch, (hipStream_t)stream));
-  return 0;
-}
-
-// ------------------------------------------------------- posterior choice --
-static int choice_check(int32_t S, int64_t N, int32_t n_samps) {
-  if (S < 2 || S > 2400) return fail(IQLHIP_ERR_INVALID, "S = %d outside 2..2400", S);
-  if (n_samps < 1 || n_samps > 1024) return fail(IQLHIP_ERR_INVALID, "n_samps = %d outside 1..1024", n_samps);
-  if (N < 1) return fail(IQLHIP_ERR_INVALID, "N = %lld must be >= 1", (long long)N);
-  return 0;
-}
-
-extern "C" int iqlhip_posterior_choice_workspace_bytes(int32_t S, int64_t N, int32_t n_samps, size_t *bytes) {
-  if (!bytes) return fail(IQLHIP_ERR_INVALID, "null argument");
-  if (int rc = choice_check(S, N, n_samps)) return rc;
-  *bytes = choice_workspace_bytes(N, n_samps);
-  return 0;
-}
-
-extern "C" int iqlhip_posterior_choice(uint32_t *state, const float *preds, int32_t S, int64_t N, int32_t n_samps,
-                                       int32_t mode, float *out, uint16_t *idx_out, void *workspace,
-                                       size_t workspace_bytes, void *stream) {
-  if (!state || !preds || !out || !workspace) return fail(IQLHIP_ERR_INVALID, "null argument");
-  if (int rc = choice_check(S, N, n_samps)) return rc;
-  if (mode != IQLHIP_CHOICE_MEAN && mode != IQLHIP_CHOICE_MEDIAN)
-    return fail(IQLHIP_ERR_INVALID, "mode %d: IQLHIP_CHOICE_MEAN or IQLHIP_CHOICE_MEDIAN", mode);
-  if (reinterpret_cast<uintptr_t>(workspace) % 16) return fail(IQLHIP_ERR_INVALID, "workspace not 16-byte aligned");
-  const int64_t slot_rows = choice_fit_rows(N, n_samps, workspace_bytes);
-  if (slot_rows < 32)
-    return fail(IQLHIP_ERR_INVALID, "workspace of %zu bytes holds no chunk (the full size is %zu)", workspace_bytes,
-                choice_workspace_bytes(N, n_samps));
-  hipStream_t st = (hipStream_t)stream;
-  uint32_t pos = 0;
-  HIP_TRY(hipMemcpyAsync(&pos, state + 624, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  if (pos > 624) return fail(IQLHIP_ERR_INVALID, "pos = %u outside 0..624", pos);
-  HIP_TRY(launch_posterior_choice(state, preds, S, N, n_samps, mode, out, idx_out, (uint16_t *)workspace, slot_rows,
-                                  st));
-  return 0;
-}
-
-extern "C" int iqlhip_pt_relabel(const iqlhip_pt_weights *w, const float *obs, const float *act,
-                                 int64_t n_rows, const int64_t *win_start, const int32_t *win_len,
-                                 const int32_t *win_t0, int64_t n_win, int32_t query_length, float *out,
-                                 void *stream) {
-  if (!w || !obs || !act || !win_start || !win_len || !out) return fail(IQLHIP_ERR_INVALID, "null argument");
-  if (n_win <= 0 || n_rows <= 0 || query_length < 1) return fail(IQLHIP_ERR_INVALID, "empty problem");
-  if (w->embd_dim != 64) return fail(IQLHIP_ERR_UNSUPPORTED, "embd_dim %d: the kernel is built for 64", w->embd_dim);
-  if (w->num_layers != 1) return fail(IQLHIP_ERR_UNSUPPORTED, "num_layers %d: only 1 is built", w->num_layers);
-  const int nh = w->num_heads;
-  if (nh < 1 || nh > 16 || (nh & (nh - 1))) return fail(IQLHIP_ERR_UNSUPPORTED, "num_heads %d", nh);
-  if (w->inter_dim < 64 || w->inter_dim > 1024 || w->inter_dim % 256)
-    return fail(IQLHIP_ERR_UNSUPPORTED, "inter_dim %d: must be a multiple of 256 up to 1024", w->inter_dim);
-  if (w->state_dim < 1 || w->action_dim < 1 || w->state_dim + w->action_dim > 192)
-    return fail(IQLHIP_ERR_UNSUPPORTED, "state/action dims");
-  if (w->n_temb < 1) return fail(IQLHIP_ERR_INVALID, "empty timestep table");
-  if (!win_t0 && query_length > w->n_temb)
-    return fail(IQLHIP_ERR_INVALID, "query_length exceeds the timestep table");
-  if (pt_smem_bytes(*w, query_length) > 160 * 1024)
-    return fail(IQLHIP_ERR_UNSUPPORTED, "query_length %d does not fit the 160 KiB LDS", query_length);
-  HIP_TRY(launch_pt(*w, obs, act, n_rows, win_start, win_len, win_t0, n_win, query_length, out,
-                    (hipStream_t)stream));
-  return 0;
-}
-
-// ---- the general PT path (pt_general.hip): host-only shape checks, then the chunked launches ----
-static constexpr size_t PT_GENERAL_BUDGET = size_t(1) << 30;  // workspace of one full chunk
-
-static int pt_general_check(const iqlhip_pt_model *m, int32_t query_length) {
-  if (!m) return fail(IQLHIP_ERR_INVALID, "null model");
-  if (m->num_layers < 1 || m->num_layers > 8)
-    return fail(IQLHIP_ERR_UNSUPPORTED, "num_layers %d: the general path takes 1..8", m->num_layers);
-  const int E = m->embd_dim, nh = m->num_heads;
-  if (E < 64 || E > 256 || E % 64)
-    return fail(IQLHIP_ERR_UNSUPPORTED, "embd_dim %d: must be a multiple of 64 up to 256", E);
-  if (nh < 1 || (nh & (nh - 1)) || E / nh < 4)
-    return fail(IQLHIP_ERR_UNSUPPORTED, "num_heads %d: must be a power of two with embd_dim / num_heads >= 4", nh);
-  if (m->inter_dim < 64 || m->inter_dim > 1024 || m->inter_dim % 64)
-    return fail(IQLHIP_ERR_UNSUPPORTED, "inter_dim %d: must be a multiple of 64 up to 1024", m->inter_dim);
-  if (m->state_dim < 1 || m->action_dim < 1 || m->state_dim + m->action_dim > 256)
-    return fail(IQLHIP_ERR_UNSUPPORTED, "state_dim %d + action_dim %d: must be <= 256", m->state_dim, m->action_dim);
-  if (query_length < 1) return fail(IQLHIP_ERR_INVALID, "query_length must be positive");
-  if (query_length > 4096) return fail(IQLHIP_ERR_UNSUPPORTED, "query_length %d > 4096", query_length);
-  if (m->n_temb < 1) return fail(IQLHIP_ERR_INVALID, "empty timestep table");
-  if (!m->blocks) return fail(IQLHIP_ERR_INVALID, "null block array");
-  const float *top[] = {m->state_wT, m->state_b, m->action_wT, m->action_b, m->temb, m->sln_w, m->sln_b,
-                        m->lnf_w, m->lnf_b, m->pref_w_last};
-  for (const float *t : top)
-    if (!t) return fail(IQLHIP_ERR_INVALID, "null weight pointer");
-  for (int l = 0; l < m->num_layers; ++l) {
-    const iqlhip_pt_block &b = m->blocks[l];
-    const float *blk[] = {b.ln0_w, b.ln0_b, b.qkv_w, b.qkv_b, b.attn_out_w, b.attn_out_b,
-                          b.ln1_w, b.ln1_b, b.mlp_in_w, b.mlp_in_b, b.mlp_out_w, b.mlp_out_b};
-    for (const float *t : blk)
-      if (!t) return fail(IQLHIP_ERR_INVALID, "null weight pointer in block %d", l);
-  }
-  return 0;
-}
-
-// windows of one full chunk: what 1 GiB holds (at least one), and few enough that the attention
-// grid (one wave per head and token row) stays far inside 2^31 work-groups
-static int64_t pt_general_cap(const iqlhip_pt_model &m, int ql) {
-  int64_t cap = pt_general_fit(m, ql, PT_GENERAL_BUDGET);
-  const int64_t grid_cap = ((int64_t)1 << 30) / ((int64_t)m.num_heads * pt_general_tp(ql));
-  cap = std::min<int64_t>(cap, std::min<int64_t>(grid_cap, 65536));
-  return std::max<int64_t>(cap, 1);
-}
-
-extern "C" int iqlhip_pt_general_workspace_bytes(const iqlhip_pt_model *m, int32_t query_length, int64_t n_win,
-                                                 size_t *bytes) {
-  if (!bytes) return fail(IQLHIP_ERR_INVALID, "null argument");
-  if (int rc = pt_general_check(m, query_length)) return rc;
-  if (n_win <= 0) return fail(IQLHIP_ERR_INVALID, "n_win must be positive");
-  *bytes = pt_general_bytes(*m, query_length, std::min(n_win, pt_general_cap(*m, query_length)));
-  return 0;
-}
-
-extern "C" int iqlhip_pt_relabel_general(const iqlhip_pt_model *m, const float *obs, const float *act,
-                                         int64_t n_rows, const int64_t *win_start, const int32_t *win_len,
-                                         const int32_t *win_t0, int64_t n_win, int32_t query_length,
-                                         void *workspace, size_t workspace_bytes, float *out, void *stream) {
-  if (int rc = pt_general_check(m, query_length)) return rc;
-  if (!obs || !act || !win_start || !win_len || !out || !workspace) return fail(IQLHIP_ERR_INVALID, "null argument");
-  if (n_win <= 0 || n_rows <= 0) return fail(IQLHIP_ERR_INVALID, "empty problem");
-  if (!win_t0 && query_length > m->n_temb)
-    return fail(IQLHIP_ERR_INVALID, "query_length exceeds the timestep table");
-  if (reinterpret_cast<uintptr_t>(workspace) % 16) return fail(IQLHIP_ERR_INVALID, "workspace not 16-byte aligned");
-  const int64_t chunk = std::min(std::min(n_win, pt_general_cap(*m, query_length)),
-                                 pt_general_fit(*m, query_length, workspace_bytes));
-  if (chunk < 1)
-    return fail(IQLHIP_ERR_INVALID, "workspace of %zu bytes holds no window (one needs %zu)", workspace_bytes,
-                pt_general_bytes(*m, query_length, 1));
-  HIP_TRY(launch_pt_general(*m, obs, act, n_rows, win_start, win_len, win_t0, n_win, query_length,
-                            static_cast<float *>(workspace), chunk, out, (hipStream_t)stream));
   return 0;
 }

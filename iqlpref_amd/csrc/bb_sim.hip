@@ -19,6 +19,8 @@
 //   * no contraction of a * b + c into an fma anywhere numpy has none (the pragma below).
 #include "../../include/iqlhip.h"
 #include "common.h"
+#include "errors.h"
+#include "launchers.h"
 
 #pragma clang fp contract(off)
 
@@ -208,7 +210,7 @@ __global__ __launch_bounds__(BB_THREADS) void k_bb_step(const iqlhip_bb_sim P, i
   bb_step_body(P, reset, t, [table](int i) { return ldg(table + i); }, sh, nullptr);
 }
 
-hipError_t launch_bb_step(const iqlhip_bb_sim &sim, int reset, hipStream_t st) {
+static hipError_t launch_bb_step(const iqlhip_bb_sim &sim, int reset, hipStream_t st) {
   hipLaunchKernelGGL(k_bb_step, dim3(1), dim3(BB_THREADS), 0, st, sim, reset);
   return hipGetLastError();
 }
@@ -350,21 +352,18 @@ __global__ __launch_bounds__(BB_THREADS) void k_bb_episodes(const BbEpisodeArgs 
   }
 }
 
-size_t mlp_image_offset(const iqlhip_mlp_desc &d, int l);
-hipError_t launch_mlp_repack(const iqlhip_mlp_desc &d, float *wf, hipStream_t st);
-
 static size_t up256(size_t x) { return (x + 255) / 256 * 256; }
 
 // scratch: the n argument blocks, then one weight image per actor that is not NULL, each on a 256-byte boundary
-size_t bb_episodes_scratch_bytes(const iqlhip_mlp_desc *const *actors, int n) {
+static size_t bb_episodes_scratch_bytes(const iqlhip_mlp_desc *const *actors, int n) {
   size_t total = up256((size_t)n * sizeof(BbEpisodeArgs));
   for (int k = 0; k < n; ++k)
     if (actors[k]) total += up256(mlp_image_offset(*actors[k], actors[k]->n_layers) * sizeof(float));
   return total;
 }
 
-hipError_t launch_bb_episodes(const iqlhip_bb_sim *sims, const iqlhip_mlp_desc *const *actors, int n, void *scratch,
-                              hipStream_t st) {
+static hipError_t launch_bb_episodes(const iqlhip_bb_sim *sims, const iqlhip_mlp_desc *const *actors, int n, void *scratch,
+                                     hipStream_t st) {
   BbEpisodeArgs host[IQLHIP_MAX_GROUP];
   char *base = static_cast<char *>(scratch);
   size_t off = up256((size_t)n * sizeof(BbEpisodeArgs));
@@ -390,3 +389,117 @@ hipError_t launch_bb_episodes(const iqlhip_bb_sim *sims, const iqlhip_mlp_desc *
 }
 
 }  // namespace iqlhip
+
+using namespace iqlhip;
+
+// ------------------------------------------------------------ entry points --
+static int bb_sim_check(const iqlhip_bb_sim *s) {
+  if (!s) return fail(IQLHIP_ERR_INVALID, "null simulator");
+  if (!s->state || !s->drift || !s->ctl || !s->obs_hist || !s->act_hist || !s->record || !s->actor_in ||
+      !s->actor_out || !s->state_mean || !s->state_std || !s->min_actions || !s->max_actions)
+    return fail(IQLHIP_ERR_INVALID, "null pointer in the simulator");
+  if (s->n_obs < 1 || s->n_obs > 1024) return fail(IQLHIP_ERR_UNSUPPORTED, "n_obs = %d outside 1..1024", s->n_obs);
+  const int near_max = s->n_obs < 16 ? s->n_obs : 16;
+  if (s->n_near < 1 || s->n_near > near_max)
+    return fail(IQLHIP_ERR_UNSUPPORTED, "n_near = %d outside 1..%d", s->n_near, near_max);
+  if (s->action_dim != 2)
+    return fail(IQLHIP_ERR_UNSUPPORTED, "action_dim = %d: the simulator's action is (speed, heading)", s->action_dim);
+  if (s->state_dim != 2 + 3 * s->n_near + 6)
+    return fail(IQLHIP_ERR_INVALID, "state_dim = %d, an observation of %d obstacles has %d columns", s->state_dim,
+                s->n_near, 2 + 3 * s->n_near + 6);
+  if (s->max_horizon < 1) return fail(IQLHIP_ERR_INVALID, "max_horizon = %d must be >= 1", s->max_horizon);
+  if (s->actor_out_stride != 0 && s->actor_out_stride < s->action_dim)
+    return fail(IQLHIP_ERR_INVALID, "actor_out_stride = %d must be 0 or >= 2", s->actor_out_stride);
+  return 0;
+}
+
+extern "C" int iqlhip_bb_sim_reset(const iqlhip_bb_sim *sim, void *stream) {
+  if (int rc = bb_sim_check(sim)) return rc;
+  HIP_TRY(launch_bb_step(*sim, 1, (hipStream_t)stream));
+  return 0;
+}
+
+extern "C" int iqlhip_bb_sim_step(const iqlhip_bb_sim *sim, void *stream) {
+  if (int rc = bb_sim_check(sim)) return rc;
+  HIP_TRY(launch_bb_step(*sim, 0, (hipStream_t)stream));
+  return 0;
+}
+
+extern "C" int iqlhip_bb_sim_rollout(const iqlhip_bb_sim *sim, const iqlhip_mlp_desc *actor, int32_t n_steps,
+                                     void *stream) {
+  if (int rc = bb_sim_check(sim)) return rc;
+  if (!actor) return fail(IQLHIP_ERR_INVALID, "null actor");
+  if (n_steps < 1) return fail(IQLHIP_ERR_INVALID, "n_steps = %d must be >= 1", n_steps);
+  if (sim->actor_out_stride != 0)
+    return fail(IQLHIP_ERR_INVALID, "a rollout reads the forward's live output row: actor_out_stride must be 0");
+  if (actor->n_layers < 1 || actor->n_layers > IQLHIP_MLP_MAX_LAYERS)
+    return fail(IQLHIP_ERR_INVALID, "n_layers must be in [1, %d]", IQLHIP_MLP_MAX_LAYERS);
+  if (actor->dims[0] != sim->state_dim || actor->dims[actor->n_layers] != sim->action_dim)
+    return fail(IQLHIP_ERR_INVALID, "the actor maps %d -> %d, the simulator needs %d -> %d", actor->dims[0],
+                actor->dims[actor->n_layers], sim->state_dim, sim->action_dim);
+  for (int i = 0; i < n_steps; ++i) {
+    if (int rc = iqlhip_mlp_forward(actor, sim->actor_in, 1, sim->state_dim, sim->actor_out, sim->action_dim, stream))
+      return rc;
+    HIP_TRY(launch_bb_step(*sim, 0, (hipStream_t)stream));
+  }
+  return 0;
+}
+
+// The envelope of k_bb_episodes' fused forward: that of k_mlp_f32 (widths <= 256, relu / tanh hidden layers,
+// no / tanh output, no dropout), two outputs
+static int bb_actor_check(const iqlhip_mlp_desc *a, int k) {
+  if (a->n_layers < 1 || a->n_layers > IQLHIP_MLP_MAX_LAYERS)
+    return fail(IQLHIP_ERR_INVALID, "actor %d: n_layers must be in [1, %d]", k, IQLHIP_MLP_MAX_LAYERS);
+  for (int i = 0; i <= a->n_layers; ++i) {
+    if (a->dims[i] < 1) return fail(IQLHIP_ERR_INVALID, "actor %d: layer width %d", k, a->dims[i]);
+    if (a->dims[i] > 256)
+      return fail(IQLHIP_ERR_UNSUPPORTED, "actor %d: layer width %d > 256, the fused forward's limit (the launch "
+                                          "pair of iqlhip_bb_sim_rollout takes wider actors)", k, a->dims[i]);
+  }
+  for (int i = 0; i < a->n_layers; ++i)
+    if (!a->weights[i] || !a->biases[i]) return fail(IQLHIP_ERR_INVALID, "actor %d: null weight pointer", k);
+  if (a->hidden_act < 0 || a->hidden_act > 1 || a->out_act < 0 || a->out_act > 1)
+    return fail(IQLHIP_ERR_UNSUPPORTED, "actor %d: activations %d / %d, the fused forward has relu or tanh hidden "
+                                        "layers and no or a tanh output", k, a->hidden_act, a->out_act);
+  if (a->dropout_p > 0.f)
+    return fail(IQLHIP_ERR_UNSUPPORTED, "actor %d: dropout_p > 0, the fused forward is an eval-mode forward", k);
+  return 0;
+}
+
+extern "C" int iqlhip_bb_sim_episodes_scratch_bytes(const iqlhip_mlp_desc *const *actors, int32_t n, size_t *bytes) {
+  if (!actors || !bytes) return fail(IQLHIP_ERR_INVALID, "null argument");
+  if (n < 1 || n > IQLHIP_MAX_GROUP) return fail(IQLHIP_ERR_INVALID, "n = %d: 1..%d episodes", n, IQLHIP_MAX_GROUP);
+  for (int k = 0; k < n; ++k)
+    if (actors[k])
+      if (int rc = bb_actor_check(actors[k], k)) return rc;
+  *bytes = bb_episodes_scratch_bytes(actors, n);
+  return 0;
+}
+
+extern "C" int iqlhip_bb_sim_episodes(const iqlhip_bb_sim *sims, const iqlhip_mlp_desc *const *actors, int32_t n,
+                                      void *scratch, size_t scratch_bytes, void *stream) {
+  if (!sims) return fail(IQLHIP_ERR_INVALID, "null simulators");
+  if (!actors) return fail(IQLHIP_ERR_INVALID, "null actors");
+  if (!scratch) return fail(IQLHIP_ERR_INVALID, "null scratch");
+  if (n < 1 || n > IQLHIP_MAX_GROUP) return fail(IQLHIP_ERR_INVALID, "n = %d: 1..%d episodes", n, IQLHIP_MAX_GROUP);
+  if ((uintptr_t)scratch & 15) return fail(IQLHIP_ERR_INVALID, "scratch must start on a 16-byte boundary");
+  for (int k = 0; k < n; ++k) {
+    if (int rc = bb_sim_check(sims + k)) return rc;
+    const iqlhip_mlp_desc *a = actors[k];
+    if (!a) {
+      if (sims[k].actor_out_stride == 0)
+        return fail(IQLHIP_ERR_INVALID, "episode %d: null actor and no injected table", k);
+      continue;
+    }
+    if (int rc = bb_actor_check(a, k)) return rc;
+    if (a->dims[0] != sims[k].state_dim || a->dims[a->n_layers] != sims[k].action_dim)
+      return fail(IQLHIP_ERR_INVALID, "actor %d maps %d -> %d, the simulator needs %d -> %d", k, a->dims[0],
+                  a->dims[a->n_layers], sims[k].state_dim, sims[k].action_dim);
+  }
+  const size_t need = bb_episodes_scratch_bytes(actors, n);
+  if (scratch_bytes < need)
+    return fail(IQLHIP_ERR_INVALID, "scratch of %zu bytes, %d episodes need %zu (iqlhip_bb_sim_episodes_scratch_bytes)",
+                scratch_bytes, n, need);
+  HIP_TRY(launch_bb_episodes(sims, actors, n, scratch, (hipStream_t)stream));
+  return 0;
+}

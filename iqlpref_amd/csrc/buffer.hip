@@ -4,6 +4,7 @@
 // [s|a|r|d|s'] read by consecutive lanes instead of five scattered reads.
 #include "../../include/iqlhip.h"
 #include "common.h"
+#include "errors.h"
 
 namespace iqlhip {
 
@@ -63,23 +64,41 @@ __global__ __launch_bounds__(256) void k_sample(const float *__restrict__ rows, 
   }
 }
 
-hipError_t launch_pack(float *rows, int stride, int S, int A, int64_t first, int64_t n, const float *obs,
-                       const float *act, const float *rew, const float *nxt, const float *done,
-                       hipStream_t st) {
-  const int64_t total = n * (int64_t)stride;
+}  // namespace iqlhip
+
+using namespace iqlhip;
+
+// Packed replay row: [ s(S) | a(A) | r | d | pad | s'(S) | pad ], s' on a 16-byte boundary
+extern "C" int32_t iqlhip_replay_next_offset(int32_t S, int32_t A) { return round_up(S + A + 2, 4); }
+extern "C" int32_t iqlhip_replay_row_stride(int32_t S, int32_t A) {
+  return round_up(iqlhip_replay_next_offset(S, A) + S, 4);
+}
+
+extern "C" int iqlhip_replay_pack(float *rows, int32_t row_stride, int32_t S, int32_t A, int64_t first_row,
+                                  int64_t n, const float *obs, const float *act, const float *rew,
+                                  const float *next_obs, const float *done, void *stream) {
+  if (!rows || !obs || !act || !rew || !next_obs || !done) return fail(IQLHIP_ERR_INVALID, "null pointer");
+  if (S <= 0 || A <= 0 || n < 0 || first_row < 0 || row_stride < iqlhip_replay_row_stride(S, A) || (row_stride & 3))
+    return fail(IQLHIP_ERR_INVALID, "bad replay geometry S=%d A=%d stride=%d", S, A, row_stride);
+  if (n == 0) return 0;
+  const int64_t total = n * (int64_t)row_stride;
   int grid = (int)((total + 255) / 256);
   if (grid > 256 * 8) grid = 256 * 8;
-  hipLaunchKernelGGL(k_pack, dim3(grid), dim3(256), 0, st, rows, stride, S, A, first, n, obs, act, rew, nxt,
-                     done);
-  return hipGetLastError();
+  hipLaunchKernelGGL(k_pack, dim3(grid), dim3(256), 0, (hipStream_t)stream, rows, row_stride, S, A, first_row, n, obs,
+                     act, rew, next_obs, done);
+  HIP_TRY(hipGetLastError());
+  return 0;
 }
 
-hipError_t launch_sample(const iqlhip_replay_view &v, int batch, const int64_t *idx, uint64_t seed,
-                         uint64_t step, float *s, float *a, float *r, float *s2, float *d,
-                         int64_t *idx_out, hipStream_t st) {
-  hipLaunchKernelGGL(k_sample, dim3((batch + 3) / 4), dim3(256), 0, st, v.rows, v.n_rows, v.row_stride,
-                     v.state_dim, v.action_dim, batch, idx, seed, step, s, a, r, s2, d, idx_out);
-  return hipGetLastError();
+extern "C" int iqlhip_replay_sample(const iqlhip_replay_view *view, int32_t batch, const int64_t *idx,
+                                    uint64_t seed, uint64_t step, float *s, float *a, float *r, float *s2,
+                                    float *d, int64_t *idx_out, void *stream) {
+  if (!view || !view->rows || !s || !a || !r || !s2 || !d) return fail(IQLHIP_ERR_INVALID, "null pointer");
+  if (batch <= 0) return fail(IQLHIP_ERR_INVALID, "batch must be positive");
+  if (view->n_rows <= 0) return fail(IQLHIP_ERR_INVALID, "cannot sample from an empty replay buffer");
+  hipLaunchKernelGGL(k_sample, dim3((batch + 3) / 4), dim3(256), 0, (hipStream_t)stream, view->rows, view->n_rows,
+                     view->row_stride, view->state_dim, view->action_dim, batch, idx, seed, step, s, a, r, s2, d,
+                     idx_out);
+  HIP_TRY(hipGetLastError());
+  return 0;
 }
-
-}  // namespace iqlhip

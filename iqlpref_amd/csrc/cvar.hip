@@ -11,6 +11,7 @@
 // segments.  LDS rows are padded so that 16-byte reads of neighbouring columns hit disjoint banks.
 #include "../../include/iqlhip.h"
 #include "common.h"
+#include "errors.h"
 
 namespace iqlhip {
 
@@ -200,7 +201,7 @@ static int cvar_row_stride(int S) {
   return sp;
 }
 
-hipError_t launch_cvar(const float *preds, int S, int64_t N, int n_tail, float *out, hipStream_t st) {
+static hipError_t launch_cvar(const float *preds, int S, int64_t N, int n_tail, float *out, hipStream_t st) {
   const int SP = cvar_row_stride(S);
   int L = 2;  // lanes per column: about one per 16 rows
   while (L < 32 && L * 16 < S) L *= 2;
@@ -230,3 +231,15 @@ hipError_t launch_cvar(const float *preds, int S, int64_t N, int n_tail, float *
 }
 
 }  // namespace iqlhip
+
+using namespace iqlhip;
+
+extern "C" int iqlhip_cvar_tail_mean(const float *preds, int32_t S, int64_t N, int32_t n_tail, float *out,
+                                     void *stream) {
+  if (!preds || !out) return fail(IQLHIP_ERR_INVALID, "null argument");
+  if (S < 1 || N < 1) return fail(IQLHIP_ERR_INVALID, "S and N must be positive");
+  if (n_tail < 1 || n_tail > S) return fail(IQLHIP_ERR_INVALID, "n_tail must be in [1, S]");
+  if (S > 2400) return fail(IQLHIP_ERR_UNSUPPORTED, "S = %d > 2400", S);
+  HIP_TRY(launch_cvar(preds, S, N, n_tail, out, (hipStream_t)stream));
+  return 0;
+}

@@ -4,6 +4,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "../../include/iqlhip.h"
+#include "host_plan.h"
 #include "iql_step.h"
 
 namespace iqlhip {
@@ -108,5 +110,20 @@ struct DeepItem {
   int32_t net, layer;  // net < 0: the misc block (losses, log_std, the step counter)
   int32_t o0, i0;      // tile origin (out-features, in-features), 64 x 64
 };
+
+// ---- the general step as the driver (api.hip) sees it (iql_deep.hip) ----
+struct DeepTrainer;
+bool deep_shape_ok(const iqlhip_trainer_config &c, int n_hidden, const char **why);
+// sh: what the driver derived from cfg; offsets: the arena layout's, 2 (n_hidden + 1) per net
+hipError_t deep_create(DeepTrainer **out, const iqlhip_trainer_config &cfg, const StepShape &sh,
+                       const iqlhip_arenas &ar, const int64_t *offsets);
+void deep_destroy(DeepTrainer *t);
+hipError_t deep_sync_weights(DeepTrainer *t, hipStream_t st);
+const DeepDesc &deep_desc(const DeepTrainer *t);
+const DeepDesc *deep_desc_dev(const DeepTrainer *t);
+hipError_t deep_step(const DeepTrainer *t, const DeepDesc *dD, const DeepArgs *dA, DeepCtr *dC, const AdamCoef *coefs,
+                     int K, hipStream_t st, hipEvent_t *ev);
+hipError_t deep_infer(DeepTrainer *t, int which, const float *s, const float *a, int64_t n, float *out,
+                      hipStream_t st);
 
 }  // namespace iqlhip

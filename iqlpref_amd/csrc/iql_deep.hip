@@ -713,15 +713,13 @@ struct DeepTrainer {
   size_t lds_bytes = 0;
 };
 
-void deep_destroy(DeepTrainer *);
-
 bool deep_shape_ok(const iqlhip_trainer_config &c, int n_hidden, const char **why) {
   if (n_hidden < 1 || n_hidden > DEEP_MAX_LIN - 1) return *why = "n_hidden must be in 1..6", false;
   if (c.hidden_dim < 1 || c.hidden_dim > DEEP_MAX_H) return *why = "hidden_dim must be in 1..1024", false;
   return true;
 }
 
-// sh: what api.hip derived from cfg; off: the arena layout's offsets, 2 (n_hidden + 1) per net (W0 b0 W1 b1 ...),
+// sh: what the driver (api.hip) derived from cfg; off: the arena layout's offsets, 2 (n_hidden + 1) per net (W0 b0 W1 b1 ...),
 // then log_std
 hipError_t deep_create(DeepTrainer **out, const iqlhip_trainer_config &cfg, const StepShape &sh,
                        const iqlhip_arenas &ar, const int64_t *off) {

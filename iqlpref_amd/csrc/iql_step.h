@@ -1,5 +1,7 @@
-// Descriptors shared by the host driver and the step kernels (iql_step.hip).
+// Descriptors shared by the host driver and the step kernels (iql_step.hip), and the launchers the driver
+// (api.hip) calls.
 #pragma once
+#include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace iqlhip {
@@ -132,5 +134,25 @@ struct UpdItem {
   void *w3t;               // layer 3 only: [H][Opad] transposed row-major copy, else null
   const void *Xsrc, *Zsrc; // fragment-major layer input and dZ^T of this (net, layer)
 };
+
+// ---- launchers (iql_step.hip; the driver is api.hip) ----
+// D: the host copy of the descriptor, dD[n_seeds] / a[n_seeds] / c[n_seeds]: the device copies a launch reads
+hipError_t prepare_step_kernels();  // once per trainer, outside any stream capture
+int layer2_parts(int H);
+int strip_rows();
+int update_lds_floats();
+hipError_t launch_forward(bool bf16, const TrainerDesc &D, const TrainerDesc *dD, const DevArgs *a, const DevCtr *c,
+                          int n_seeds, hipStream_t st);
+hipError_t launch_backward(bool bf16, const TrainerDesc &D, const TrainerDesc *dD, const DevArgs *a, DevCtr *c,
+                           int n_seeds, hipStream_t st, bool counts = false);
+hipError_t launch_stage(bool bf16, const TrainerDesc &D, const TrainerDesc *dD, const DevArgs *a, const DevCtr *c,
+                        int n_seeds, hipStream_t st);
+hipError_t launch_update(bool bf16, const TrainerDesc *dD, const DevArgs *a, DevCtr *c, const UpdItem *items,
+                         int n_items, int n_seeds, hipStream_t st, bool padded = false);
+hipError_t launch_pad_rows(const void *src, void *dst, int64_t n, int rows, int rows_padded, int row_bytes,
+                           hipStream_t st);
+hipError_t launch_sync_weights(bool bf16, const TrainerDesc *dD, hipStream_t st);
+hipError_t launch_infer(bool bf16, const TrainerDesc &D, const TrainerDesc *dD, const FwdNet &N, const float *s,
+                        const float *a, int64_t n, float *out, int out_stride, hipStream_t st);
 
 }  // namespace iqlhip

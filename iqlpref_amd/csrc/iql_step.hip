@@ -2630,19 +2630,19 @@ __global__ void k_sync_weights(const TrainerDesc *__restrict__ Dp) {
 }
 
 // ------------------------------------------------------------------------
-// launchers (host driver: api.hip)
+// launchers (declared in iql_step.h; the host driver is api.hip)
 // ------------------------------------------------------------------------
 // k_infer (unsplit 16-row slabs, mlp_slab)
-size_t infer_smem_bytes(bool bf16, int H, int k1max) {
+static size_t infer_smem_bytes(bool bf16, int H, int k1max) {
   const int es = bf16 ? 2 : 4, epv = bf16 ? 8 : 4;
   return (size_t)SLAB * (k1max + epv) * es + 2 * (size_t)SLAB * (H + epv) * es + 4 * 2 * 64 * 4 * 4;
 }
 // k_forward: xs [16 MT][k1max + EPV], h1 [16 MT][H + EPV], h2 [PW][16 MT][64 + EPV]
-size_t fwd_smem_bytes(bool bf16, int H, int k1max, int mt, int pw) {
+static size_t fwd_smem_bytes(bool bf16, int H, int k1max, int mt, int pw) {
   const int es = bf16 ? 2 : 4, epv = bf16 ? 8 : 4;
   return (size_t)16 * mt * ((k1max + epv) + (H + epv) + pw * (64 + epv)) * es;
 }
-size_t bwd_smem_bytes(bool bf16, int H) {
+static size_t bwd_smem_bytes(bool bf16, int H) {
   const int es = bf16 ? 2 : 4, epv = bf16 ? 8 : 4;
   return (size_t)SLAB * (H + epv) * es + 3 * SLAB * 32 * 4 + SLAB * 4 + SLAB * FIN_LD * 4;
 }
@@ -2652,7 +2652,7 @@ size_t bwd_smem_bytes(bool bf16, int H) {
 // batch 256: two per CU, whose phases interleave on each SIMD), two seeds and more with 32 rows; from
 // four seeds on with two layer-2 parts per work-group (K = 8: 154.8k steps/s against 150.2k with
 // 64 rows x one part, 139.7k with 32 x one).
-int fwd_row_tiles(int B, int n_seeds) {
+static int fwd_row_tiles(int B, int n_seeds) {
   const int64_t rows = (int64_t)B * n_seeds;
   // (64-row work-groups, round 3: eight seeds as ONE group 202.5k -> 205.7k steps/s, everything else
   // slower: K = 4 152.9k -> 147.1k, K = 2 103.7k -> 98.6k, two groups of eight 263.5k -> 255.4k)
@@ -2662,7 +2662,7 @@ int fwd_row_tiles(int B, int n_seeds) {
 int layer2_parts(int H) { return H >= 256 ? 4 : H / 64; }
 // parts of hidden layer 2 per forward work-group: 2 in a group launch that keeps the chip full
 // anyway (layer 1 and its epilogue are then computed twice per slab instead of four times)
-int fwd_parts_per_wg(int B, int H, int n_seeds) {
+static int fwd_parts_per_wg(int B, int H, int n_seeds) {
   return ((int64_t)B * n_seeds >= 1024 && layer2_parts(H) % 2 == 0) ? 2 : 1;
 }
 
@@ -2675,7 +2675,7 @@ static void dispatch_h(bool bf16, int H, F &&f) {
 
 // Launches with many rows (seed groups, batch-1024 ensembles) take the throughput kernels
 // k_forward_tp / k_backward_tp (bf16, H = 256, batch a multiple of 64).
-bool use_tp(bool bf16, const TrainerDesc &D, int n_seeds, bool backward) {
+static bool use_tp(bool bf16, const TrainerDesc &D, int n_seeds, bool backward) {
   // (a padded batch, NB < B, stays on the latency kernels: k_backward_tp has no counted instantiation)
   if (!bf16 || D.H != 256 || D.B % 64 != 0 || D.NB != D.B) return false;
   // The throughput kernels are one eight-wave work-group per CU, all resident at once: they win while
@@ -2702,8 +2702,7 @@ hipError_t prepare_step_kernels() {
   return hipFuncSetAttribute(reinterpret_cast<const void *>(k_forward_tp<256, true>),
                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 }
-size_t fwd_tp_smem_bytes(int H, int k1max) { return (size_t)64 * ((k1max + 8) + 2 * (H + 8)) * 2; }
-size_t bwd_smem_bytes(bool bf16, int H);
+static size_t fwd_tp_smem_bytes(int H, int k1max) { return (size_t)64 * ((k1max + 8) + 2 * (H + 8)) * 2; }
 
 hipError_t launch_forward(bool bf16, const TrainerDesc &D, const TrainerDesc *dD, const DevArgs *a,
                           const DevCtr *c, int n_seeds, hipStream_t st) {
@@ -2743,7 +2742,7 @@ hipError_t launch_forward(bool bf16, const TrainerDesc &D, const TrainerDesc *dD
 // Measured (tools/group_scan.py; steps/s with 1 / 2 parts per work-group): one seed 65.4k / 64.1k,
 // two seeds 97.4k / 102.2k, four 136.2k / 144.6k, eight 177.3k / 189.5k (k_backward 10.7 -> 8.0 us);
 // all four parts in one work-group (512 work-groups of 128 registers, spilling): 148k.
-int bwd_parts_per_wg(int B, int H, int n_seeds) {
+static int bwd_parts_per_wg(int B, int H, int n_seeds) {
   return ((int64_t)B * n_seeds >= 512 && layer2_parts(H) % 2 == 0) ? 2 : 1;
 }
 hipError_t launch_backward(bool bf16, const TrainerDesc &D, const TrainerDesc *dD, const DevArgs *a,

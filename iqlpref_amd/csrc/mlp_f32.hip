@@ -23,6 +23,8 @@
 
 #include "../../include/iqlhip.h"
 #include "common.h"
+#include "errors.h"
+#include "launchers.h"
 
 namespace iqlhip {
 
@@ -425,7 +427,7 @@ static void mlp_geometry(const iqlhip_mlp_desc &d, MlpArgs &M, int &act, size_t 
   if (act == 2 && nt_last >= 4 && d.dims[d.n_layers] > maxd) maxd = d.dims[d.n_layers];
   M.lda = round_up(maxd, 16) + 4;
   M.drop_thr = 0, M.drop_scale = 1.f, M.drop_seed = d.dropout_seed, M.drop_call = d.dropout_call;
-  if (d.dropout_p > 0.f) {  // the trainer's fp32 convention (api.hip): thr = p 2^32, scale = 1 / (1 - p)
+  if (d.dropout_p > 0.f) {  // the trainer's fp32 convention (host_plan.h dropout_consts): thr = p 2^32, scale = 1 / (1 - p)
     const double thr = (double)d.dropout_p * 4294967296.0;
     M.drop_thr = thr >= 4294967295.0 ? 0xffffffffu : (thr < 1.0 ? 1u : (uint32_t)thr);
     M.drop_scale = 1.0f / (float)(1.0 - (double)d.dropout_p);
@@ -510,8 +512,9 @@ __global__ void k_mlp_set_bias(const BiasArgs B) {
   for (int c = threadIdx.x; c < Np; c += blockDim.x) B.dst[l][c] = c < N ? B.src[l][c] : 0.f;
 }
 
-// The caller (api.hip) has checked the members: one shape, every width <= 256, no dropout, no null pointer.
-hipError_t mlp_set_create(const iqlhip_mlp_desc *const *descs, int M, iqlhip_mlp_set **out, hipStream_t st) {
+// The caller (iqlhip_mlp_set_create) has checked the members: one shape, every width <= 256, no dropout, no null
+// pointer.
+static hipError_t mlp_set_create(const iqlhip_mlp_desc *const *descs, int M, iqlhip_mlp_set **out, hipStream_t st) {
   const iqlhip_mlp_desc &d0 = *descs[0];
   const int L = d0.n_layers;
   const size_t image = mlp_image_offset(d0, L);
@@ -553,24 +556,96 @@ hipError_t mlp_set_create(const iqlhip_mlp_desc *const *descs, int M, iqlhip_mlp
   return hipSuccess;
 }
 
-hipError_t mlp_set_destroy(iqlhip_mlp_set *s) {
-  const hipError_t e = hipFree(s->mem);  // (waits for the work that still reads it)
-  delete s;
-  return e;
-}
-
-void mlp_set_shape(const iqlhip_mlp_set *s, int *M, int *in, int *out, int *device) {
-  *device = s->device, *M = s->M, *in = s->S.A.dims[0], *out = s->S.A.dims[s->S.A.n_layers];
-}
-
-hipError_t launch_mlp_set(const iqlhip_mlp_set *s, const float *x, int R, int x_stride, float *out, int out_stride,
-                          hipStream_t st) {
-  MlpSetArgs S = s->S;
-  S.R = R;
-  auto kern = s->act == 0 ? k_mlp_set<0> : s->act == 1 ? k_mlp_set<1> : k_mlp_set<2>;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(((int64_t)R + MROWS - 1) / MROWS), (unsigned)s->M), dim3(256), s->sm, st, S, x,
-                     x_stride, out, out_stride);
-  return hipGetLastError();
-}
-
 }  // namespace iqlhip
+
+using namespace iqlhip;
+
+// ------------------------------------------------------------ entry points --
+// what iqlhip_mlp_forward and iqlhip_mlp_set_create check alike in a descriptor: the layer count ...
+static int mlp_layers_check(const iqlhip_mlp_desc &d) {
+  if (d.n_layers < 1 || d.n_layers > IQLHIP_MLP_MAX_LAYERS)
+    return fail(IQLHIP_ERR_INVALID, "n_layers must be in [1, %d]", IQLHIP_MLP_MAX_LAYERS);
+  return 0;
+}
+// ... and the activation codes
+static int mlp_act_check(const iqlhip_mlp_desc &d) {
+  for (int a : {d.hidden_act, d.out_act})
+    if (a < 0 || (a > 1 && a < 8) || a > 15) return fail(IQLHIP_ERR_INVALID, "activation code %d", a);
+  return 0;
+}
+
+extern "C" int iqlhip_mlp_forward(const iqlhip_mlp_desc *d, const float *x, int64_t n, int32_t x_stride,
+                                  float *out, int32_t out_stride, void *stream) {
+  if (!d || !x || !out) return fail(IQLHIP_ERR_INVALID, "null argument");
+  if (n <= 0) return fail(IQLHIP_ERR_INVALID, "n must be positive");
+  if (int rc = mlp_layers_check(*d)) return rc;
+  for (int i = 0; i <= d->n_layers; ++i)
+    if (d->dims[i] <= 0 || d->dims[i] > 1024)
+      return fail(IQLHIP_ERR_UNSUPPORTED, "layer width %d outside [1, 1024]", d->dims[i]);
+  for (int i = 0; i < d->n_layers; ++i)
+    if (!d->weights[i] || !d->biases[i]) return fail(IQLHIP_ERR_INVALID, "null weight pointer");
+  if (int rc = mlp_act_check(*d)) return rc;
+  if (x_stride < d->dims[0] || out_stride < d->dims[d->n_layers])
+    return fail(IQLHIP_ERR_INVALID, "stride smaller than the row width");
+  if (!(d->dropout_p < 1.0f)) return fail(IQLHIP_ERR_INVALID, "dropout_p must be < 1");
+  if (d->dropout_p > 0.f && n > 0xffffffffLL) return fail(IQLHIP_ERR_UNSUPPORTED, "dropout: n must fit 32 bits");
+  HIP_TRY(launch_mlp_f32(*d, x, n, x_stride, out, out_stride, (hipStream_t)stream));
+  return 0;
+}
+
+extern "C" int iqlhip_mlp_set_create(const iqlhip_mlp_desc *const *descs, int32_t M, iqlhip_mlp_set **out,
+                                     void *stream) {
+  if (!descs || !out) return fail(IQLHIP_ERR_INVALID, "null argument");
+  if (M < 1 || M > IQLHIP_MLP_SET_MAX)
+    return fail(IQLHIP_ERR_INVALID, "M = %d outside [1, %d]", M, IQLHIP_MLP_SET_MAX);
+  for (int m = 0; m < M; ++m)
+    if (!descs[m]) return fail(IQLHIP_ERR_INVALID, "member %d: null descriptor", m);
+  const iqlhip_mlp_desc &d0 = *descs[0];
+  if (int rc = mlp_layers_check(d0)) return rc;
+  for (int i = 0; i <= d0.n_layers; ++i) {
+    if (d0.dims[i] <= 0) return fail(IQLHIP_ERR_INVALID, "layer width %d", d0.dims[i]);
+    if (d0.dims[i] > 256)
+      return fail(IQLHIP_ERR_UNSUPPORTED, "layer width %d > 256: iqlhip_mlp_forward takes it", d0.dims[i]);
+  }
+  if (int rc = mlp_act_check(d0)) return rc;
+  for (int m = 0; m < M; ++m) {
+    const iqlhip_mlp_desc &d = *descs[m];
+    bool same = d.n_layers == d0.n_layers && d.w_in_out == d0.w_in_out && d.hidden_act == d0.hidden_act &&
+                d.out_act == d0.out_act;
+    for (int i = 0; same && i <= d0.n_layers; ++i) same = d.dims[i] == d0.dims[i];
+    if (!same) return fail(IQLHIP_ERR_INVALID, "member %d differs from member 0 in shape, activation or layout", m);
+    for (int i = 0; i < d.n_layers; ++i)
+      if (!d.weights[i] || !d.biases[i]) return fail(IQLHIP_ERR_INVALID, "member %d: null weight pointer", m);
+    if (d.dropout_p > 0.f)
+      return fail(IQLHIP_ERR_UNSUPPORTED, "member %d: dropout_p > 0 (the set is an eval-mode forward)", m);
+  }
+  HIP_TRY(mlp_set_create(descs, M, out, (hipStream_t)stream));
+  return 0;
+}
+
+extern "C" int iqlhip_mlp_set_destroy(iqlhip_mlp_set *set) {
+  if (!set) return fail(IQLHIP_ERR_INVALID, "null set");
+  float *mem = set->mem;
+  delete set;
+  HIP_TRY(hipFree(mem));  // (waits for the work that still reads it)
+  return 0;
+}
+
+extern "C" int iqlhip_mlp_set_forward(const iqlhip_mlp_set *set, const float *x, int32_t R, int32_t x_stride,
+                                      float *out, int32_t out_stride, void *stream) {
+  if (!set || !x || !out) return fail(IQLHIP_ERR_INVALID, "null argument");
+  if (R < 1) return fail(IQLHIP_ERR_INVALID, "R = %d must be positive", R);
+  const int in = set->S.A.dims[0], width = set->S.A.dims[set->S.A.n_layers];
+  if (x_stride < in || out_stride < width) return fail(IQLHIP_ERR_INVALID, "stride smaller than the row width");
+  int current;
+  HIP_TRY(hipGetDevice(&current));  // (no launch, no wait: the set's images live on one device)
+  if (current != set->device)
+    return fail(IQLHIP_ERR_INVALID, "the set lives on device %d, the current device is %d", set->device, current);
+  MlpSetArgs S = set->S;
+  S.R = R;
+  auto kern = set->act == 0 ? k_mlp_set<0> : set->act == 1 ? k_mlp_set<1> : k_mlp_set<2>;
+  hipLaunchKernelGGL(kern, dim3((unsigned)(((int64_t)R + MROWS - 1) / MROWS), (unsigned)set->M), dim3(256), set->sm,
+                     (hipStream_t)stream, S, x, x_stride, out, out_stride);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}

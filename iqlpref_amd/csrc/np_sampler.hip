@@ -19,6 +19,7 @@
 // The stream itself is np_draw_stream (np_stream.h), shared with the posterior-choice draw.
 #include "../../include/iqlhip.h"
 #include "common.h"
+#include "errors.h"
 #include "np_stream.h"
 
 namespace iqlhip {
@@ -39,17 +40,6 @@ __global__ __launch_bounds__(NP_THREADS) void k_np_randint(uint32_t *__restrict_
     return;
   }
   np_draw_stream<int64_t>(state + (size_t)k * (MT_N + 1), out, rng, a.mask[k], total);
-}
-
-hipError_t launch_np_randint(uint32_t *state, const int64_t *hi, int K, int64_t total, int64_t *const *out,
-                             hipStream_t st) {
-  NpDrawArgs a = {};
-  for (int k = 0; k < K; ++k) {
-    const uint64_t rng = (uint64_t)(hi[k] - 1);
-    a.out[k] = out[k], a.rng[k] = (uint32_t)rng, a.mask[k] = np_mask_of(rng);
-  }
-  hipLaunchKernelGGL(k_np_randint, dim3(K), dim3(NP_THREADS), 0, st, state, a, total);
-  return hipGetLastError();
 }
 
 // The epoch walk of algorithms/custom_offline/iql_bb.py:208-238 (RandomBatchSampler under a BatchSampler):
@@ -104,22 +94,73 @@ __global__ __launch_bounds__(256) void k_block_epoch_group(BlockEpochGroupArgs a
   if (k == 0 && j == 0) n_valid[i] = slot < nb ? B : (int32_t)tail;
 }
 
-hipError_t launch_block_epoch(const int64_t *perm, int64_t n_rows, int batch, int64_t t0, int64_t n_steps, int64_t *idx,
-                              int32_t *n_valid, hipStream_t st) {
-  const int64_t total = n_steps * batch;
-  hipLaunchKernelGGL(k_block_epoch, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, perm, n_rows, batch, t0,
-                     n_steps, idx, n_valid);
-  return hipGetLastError();
+}  // namespace iqlhip
+
+using namespace iqlhip;
+
+// ------------------------------------------------------- numpy index stream --
+extern "C" int iqlhip_np_randint(uint32_t *state, const int64_t *hi, int32_t K, int32_t batch,
+                                 int64_t n_batches, int64_t *const *out, void *stream) {
+  if (!state || !hi || !out) return fail(IQLHIP_ERR_INVALID, "null argument");
+  if (K < 1 || K > IQLHIP_MAX_GROUP) return fail(IQLHIP_ERR_INVALID, "K = %d: 1..%d streams", K, IQLHIP_MAX_GROUP);
+  if (batch < 1) return fail(IQLHIP_ERR_INVALID, "batch = %d must be >= 1", batch);
+  if (n_batches < 0) return fail(IQLHIP_ERR_INVALID, "n_batches = %lld must be >= 0", (long long)n_batches);
+  for (int k = 0; k < K; ++k) {
+    if (hi[k] < 1 || hi[k] > (int64_t(1) << 32))
+      return fail(IQLHIP_ERR_INVALID, "hi[%d] = %lld outside 1..2^32", k, (long long)hi[k]);
+    if (!out[k]) return fail(IQLHIP_ERR_INVALID, "null out[%d]", k);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = np_check_pos(state, K, st)) return rc;
+  if (n_batches == 0) return 0;
+  NpDrawArgs a = {};
+  for (int k = 0; k < K; ++k) {
+    const uint64_t rng = (uint64_t)(hi[k] - 1);
+    a.out[k] = out[k], a.rng[k] = (uint32_t)rng, a.mask[k] = np_mask_of(rng);
+  }
+  hipLaunchKernelGGL(k_np_randint, dim3(K), dim3(NP_THREADS), 0, st, state, a, n_batches * (int64_t)batch);
+  HIP_TRY(hipGetLastError());
+  return 0;
 }
 
-hipError_t launch_block_epoch_group(const int64_t *const *perm, int64_t n_rows, int batch, int64_t t0, int64_t n_steps,
-                                    int64_t *const *idx, int32_t *n_valid, int K, hipStream_t st) {
+// ------------------------------------------------------- block-shuffled epochs --
+// what one walk and the walks of a group check alike
+static int block_epoch_check(int32_t batch, int64_t n_rows, int64_t t0, int64_t n_steps) {
+  if (batch < 1) return fail(IQLHIP_ERR_INVALID, "batch = %d must be >= 1", batch);
+  if (n_rows < 1) return fail(IQLHIP_ERR_INVALID, "n_rows = %lld must be >= 1", (long long)n_rows);
+  if (t0 < 0 || n_steps < 0)
+    return fail(IQLHIP_ERR_INVALID, "t0 = %lld and n_steps = %lld must be >= 0", (long long)t0, (long long)n_steps);
+  return 0;
+}
+
+extern "C" int iqlhip_block_epoch_indices(const int64_t *perm, int64_t n_rows, int32_t batch, int64_t t0,
+                                          int64_t n_steps, int64_t *idx, int32_t *n_valid, void *stream) {
+  if (!idx || !n_valid) return fail(IQLHIP_ERR_INVALID, "null argument");
+  if (int rc = block_epoch_check(batch, n_rows, t0, n_steps)) return rc;
+  if (!perm && n_rows >= batch) return fail(IQLHIP_ERR_INVALID, "null perm with %lld whole blocks", (long long)(n_rows / batch));
+  if (n_steps == 0) return 0;
+  hipLaunchKernelGGL(k_block_epoch, dim3((unsigned)((n_steps * batch + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     perm, n_rows, batch, t0, n_steps, idx, n_valid);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+extern "C" int iqlhip_block_epoch_indices_group(const int64_t *const *perm, int64_t n_rows, int32_t batch, int64_t t0,
+                                                int64_t n_steps, int64_t *const *idx, int32_t *n_valid, int32_t K,
+                                                void *stream) {
+  if (!idx || !n_valid) return fail(IQLHIP_ERR_INVALID, "null argument");
+  if (K < 1 || K > IQLHIP_MAX_GROUP) return fail(IQLHIP_ERR_INVALID, "K = %d: 1..%d members", K, IQLHIP_MAX_GROUP);
+  if (int rc = block_epoch_check(batch, n_rows, t0, n_steps)) return rc;
+  for (int k = 0; k < K; ++k) {
+    if (!idx[k]) return fail(IQLHIP_ERR_INVALID, "null idx[%d]", k);
+    if ((!perm || !perm[k]) && n_rows >= batch)
+      return fail(IQLHIP_ERR_INVALID, "null perm[%d] with %lld whole blocks", k, (long long)(n_rows / batch));
+  }
+  if (n_steps == 0) return 0;
   BlockEpochGroupArgs a = {};
   for (int k = 0; k < K; ++k) a.perm[k] = perm ? perm[k] : nullptr, a.idx[k] = idx[k];
-  const int64_t total = n_steps * batch;
-  hipLaunchKernelGGL(k_block_epoch_group, dim3((unsigned)((total + 255) / 256), K), dim3(256), 0, st, a, n_rows, batch,
-                     t0, n_steps, n_valid);
-  return hipGetLastError();
+  hipLaunchKernelGGL(k_block_epoch_group, dim3((unsigned)((n_steps * batch + 255) / 256), K), dim3(256), 0,
+                     (hipStream_t)stream, a, n_rows, batch, t0, n_steps, n_valid);
+  HIP_TRY(hipGetLastError());
+  return 0;
 }
-
-}  // namespace iqlhip

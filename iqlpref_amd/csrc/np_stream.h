@@ -5,6 +5,7 @@
 // np_twist / np_judge rounds, so the streams cannot drift apart.
 #pragma once
 #include "common.h"
+#include "errors.h"
 
 namespace iqlhip {
 
@@ -164,6 +165,18 @@ __host__ __device__ inline uint32_t np_mask_of(uint64_t rng) {
   uint64_t mask = rng;
   mask |= mask >> 1, mask |= mask >> 2, mask |= mask >> 4, mask |= mask >> 8, mask |= mask >> 16;
   return (uint32_t)mask;
+}
+
+// Host, ahead of a draw from K states (iqlhip_np_randint, iqlhip_np_randint_growing): pos of every state in one
+// strided copy of the K words, then the stream is synchronised; each must lie in 0..624.
+inline int np_check_pos(const uint32_t *state, int K, hipStream_t st) {
+  uint32_t pos[IQLHIP_MAX_GROUP];
+  HIP_TRY(hipMemcpy2DAsync(pos, sizeof(uint32_t), state + 624, 625 * sizeof(uint32_t), sizeof(uint32_t), K,
+                           hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  for (int k = 0; k < K; ++k)
+    if (pos[k] > 624) return fail(IQLHIP_ERR_INVALID, "state %d: pos = %u outside 0..624", k, pos[k]);
+  return 0;
 }
 
 }  // namespace iqlhip

@@ -10,6 +10,8 @@
 //   k_explore_group       one actor forward + epilogue per work-group, bit for bit the solo pair's row.
 #include "../../include/iqlhip.h"
 #include "common.h"
+#include "errors.h"
+#include "launchers.h"
 #include "np_stream.h"
 
 namespace iqlhip {
@@ -48,18 +50,6 @@ __global__ __launch_bounds__(256) void k_replay_append(float *__restrict__ rows,
     const int64_t row = (pointer + i) % capacity;
     *reinterpret_cast<float4 *>(rows + row * stride + c0) = make_float4(v[0], v[1], v[2], v[3]);
   }
-}
-
-hipError_t launch_replay_append(float *rows, int stride, int S, int A, int64_t pointer, int64_t capacity, int64_t n,
-                                const float *obs, const float *act, const float *rew, const float *nxt,
-                                const float *done, hipStream_t st) {
-  const int64_t total = n * (int64_t)(stride >> 2);
-  int64_t blocks = (total + 255) / 256;
-  if (blocks > 256 * 8) blocks = 256 * 8;  // (the kernel strides over the rest)
-  const int grid = (int)blocks;
-  hipLaunchKernelGGL(k_replay_append, dim3(grid), dim3(256), 0, st, rows, stride, S, A, pointer, capacity, n, obs, act,
-                     rew, nxt, done);
-  return hipGetLastError();
 }
 
 // ------------------------------------------------------------ growing draw --
@@ -130,14 +120,6 @@ __global__ __launch_bounds__(NP_THREADS) void k_np_randint_growing(uint32_t *__r
   }
   if (t == 0) st[MT_N] = (uint32_t)pos;
   np_lane_store(L, st);
-}
-
-hipError_t launch_np_randint_growing(uint32_t *state, const int64_t *hi0, const int64_t *cap, int growth, int K,
-                                     int batch, int64_t n_steps, int64_t *const *out, hipStream_t st) {
-  NpGrowArgs a = {};
-  for (int k = 0; k < K; ++k) a.out[k] = out[k], a.hi0[k] = hi0[k], a.cap[k] = cap[k];
-  hipLaunchKernelGGL(k_np_randint_growing, dim3(K), dim3(NP_THREADS), 0, st, state, a, growth, batch, n_steps);
-  return hipGetLastError();
 }
 
 // ------------------------------------------------------ exploration action --
@@ -221,14 +203,6 @@ __global__ __launch_bounds__(64) void k_replay_append_group(AppendGroupArgs a, i
     }
     stg16(dst + c0, make_float4(v[0], v[1], v[2], v[3]));
   }
-}
-
-hipError_t launch_replay_append_group(float *const *rows, int stride, int S, int A, const int64_t *capacity,
-                                      const int64_t *pointer, int K, const float *stage, hipStream_t st) {
-  AppendGroupArgs a = {};
-  for (int k = 0; k < K; ++k) a.rows[k] = rows[k], a.row[k] = pointer[k] % capacity[k];
-  hipLaunchKernelGGL(k_replay_append_group, dim3(K), dim3(64), 0, st, a, stride, S, A, stage);
-  return hipGetLastError();
 }
 
 // iqlhip_explore_action for one state row of each of K actors in ONE launch: work-group k runs member k's
@@ -472,3 +446,82 @@ hipError_t launch_explore_group(const iqlhip_mlp_desc *actors, const float *cons
 }
 
 }  // namespace iqlhip
+
+using namespace iqlhip;
+
+// ------------------------------------------------------------ entry points --
+// what the append into one ring and into the rings of a group check alike: the packed row
+static int replay_geometry_check(int32_t row_stride, int32_t S, int32_t A) {
+  if (S <= 0 || A <= 0 || row_stride < iqlhip_replay_row_stride(S, A) || (row_stride & 3))
+    return fail(IQLHIP_ERR_INVALID, "bad replay geometry S=%d A=%d stride=%d", S, A, row_stride);
+  return 0;
+}
+
+extern "C" int iqlhip_replay_append(float *rows, int32_t row_stride, int32_t S, int32_t A, int64_t capacity,
+                                    int64_t pointer, int64_t n, const float *obs, const float *act, const float *rew,
+                                    const float *next_obs, const float *done, void *stream) {
+  if (!rows || !obs || !act || !rew || !next_obs || !done) return fail(IQLHIP_ERR_INVALID, "null pointer");
+  if (int rc = replay_geometry_check(row_stride, S, A)) return rc;
+  if ((uintptr_t)rows & 15) return fail(IQLHIP_ERR_INVALID, "rows must start on a 16-byte boundary");
+  if (capacity < 1) return fail(IQLHIP_ERR_INVALID, "capacity = %lld must be >= 1", (long long)capacity);
+  if (pointer < 0 || pointer >= capacity)
+    return fail(IQLHIP_ERR_INVALID, "pointer = %lld outside 0..%lld", (long long)pointer, (long long)capacity - 1);
+  if (n < 1) return fail(IQLHIP_ERR_INVALID, "n = %lld must be >= 1", (long long)n);
+  if (n > capacity)
+    return fail(IQLHIP_ERR_INVALID, "n = %lld transitions do not fit a ring of %lld rows", (long long)n,
+                (long long)capacity);
+  int64_t blocks = (n * (int64_t)(row_stride >> 2) + 255) / 256;
+  if (blocks > 256 * 8) blocks = 256 * 8;  // (the kernel strides over the rest)
+  hipLaunchKernelGGL(k_replay_append, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, rows, row_stride, S, A,
+                     pointer, capacity, n, obs, act, rew, next_obs, done);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+extern "C" int iqlhip_replay_append_group(float *const *rows, int32_t row_stride, int32_t S, int32_t A,
+                                          const int64_t *capacity, const int64_t *pointer, int32_t K,
+                                          const float *stage, void *stream) {
+  if (!rows || !capacity || !pointer || !stage) return fail(IQLHIP_ERR_INVALID, "null pointer");
+  if (K < 1 || K > IQLHIP_MAX_GROUP) return fail(IQLHIP_ERR_INVALID, "K = %d: 1..%d rings", K, IQLHIP_MAX_GROUP);
+  if (int rc = replay_geometry_check(row_stride, S, A)) return rc;
+  for (int k = 0; k < K; ++k) {
+    if (!rows[k]) return fail(IQLHIP_ERR_INVALID, "null rows[%d]", k);
+    if ((uintptr_t)rows[k] & 15) return fail(IQLHIP_ERR_INVALID, "rows[%d] must start on a 16-byte boundary", k);
+    if (capacity[k] < 1) return fail(IQLHIP_ERR_INVALID, "capacity[%d] = %lld must be >= 1", k, (long long)capacity[k]);
+    if (pointer[k] < 0 || pointer[k] >= capacity[k])
+      return fail(IQLHIP_ERR_INVALID, "pointer[%d] = %lld outside 0..%lld", k, (long long)pointer[k],
+                  (long long)capacity[k] - 1);
+    for (int j = 0; j < k; ++j)
+      if (rows[j] == rows[k]) return fail(IQLHIP_ERR_INVALID, "ring %d listed twice", k);
+  }
+  AppendGroupArgs a = {};
+  for (int k = 0; k < K; ++k) a.rows[k] = rows[k], a.row[k] = pointer[k] % capacity[k];
+  hipLaunchKernelGGL(k_replay_append_group, dim3(K), dim3(64), 0, (hipStream_t)stream, a, row_stride, S, A, stage);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+extern "C" int iqlhip_np_randint_growing(uint32_t *state, const int64_t *hi0, const int64_t *cap, int32_t growth,
+                                         int32_t K, int32_t batch, int64_t n_steps, int64_t *const *out,
+                                         void *stream) {
+  if (!state || !hi0 || !cap || !out) return fail(IQLHIP_ERR_INVALID, "null argument");
+  if (K < 1 || K > IQLHIP_MAX_GROUP) return fail(IQLHIP_ERR_INVALID, "K = %d: 1..%d streams", K, IQLHIP_MAX_GROUP);
+  if (batch < 1) return fail(IQLHIP_ERR_INVALID, "batch = %d must be >= 1", batch);
+  if (n_steps < 0) return fail(IQLHIP_ERR_INVALID, "n_steps = %lld must be >= 0", (long long)n_steps);
+  if (growth != 0 && growth != 1) return fail(IQLHIP_ERR_INVALID, "growth = %d must be 0 or 1", growth);
+  for (int k = 0; k < K; ++k) {
+    if (hi0[k] < 1 || hi0[k] > (int64_t(1) << 32))
+      return fail(IQLHIP_ERR_INVALID, "hi0[%d] = %lld outside 1..2^32", k, (long long)hi0[k]);
+    if (cap[k] < hi0[k] || cap[k] > (int64_t(1) << 32))
+      return fail(IQLHIP_ERR_INVALID, "cap[%d] = %lld outside hi0..2^32", k, (long long)cap[k]);
+    if (!out[k]) return fail(IQLHIP_ERR_INVALID, "null out[%d]", k);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = np_check_pos(state, K, st)) return rc;
+  if (n_steps == 0) return 0;
+  NpGrowArgs a = {};
+  for (int k = 0; k < K; ++k) a.out[k] = out[k], a.hi0[k] = hi0[k], a.cap[k] = cap[k];
+  hipLaunchKernelGGL(k_np_randint_growing, dim3(K), dim3(NP_THREADS), 0, st, state, a, growth, batch, n_steps);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}

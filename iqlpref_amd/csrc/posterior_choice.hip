@@ -21,6 +21,7 @@
 // chunks is all that does not hide behind the serial draw.
 #include "../../include/iqlhip.h"
 #include "common.h"
+#include "errors.h"
 #include "np_stream.h"
 
 namespace iqlhip {
@@ -119,18 +120,18 @@ __global__ __launch_bounds__(CH_THREADS) void k_choice_reduce(const float *__res
 }
 
 // rows of one index slot for this (n, N), before the workspace's own limit
-int64_t choice_slot_rows(int64_t N, int n) {
+static int64_t choice_slot_rows(int64_t N, int n) {
   const int64_t full = (CH_VALUES / n) / CH_ROW_ALIGN * CH_ROW_ALIGN;  // n <= 1024: >= 1024 rows
   const int64_t all = (N + CH_ROW_ALIGN - 1) / CH_ROW_ALIGN * CH_ROW_ALIGN;
   return full < all ? full : all;
 }
 
-size_t choice_workspace_bytes(int64_t N, int n) {
+static size_t choice_workspace_bytes(int64_t N, int n) {
   return (size_t)CH_RING * (size_t)choice_slot_rows(N, n) * (size_t)n * sizeof(uint16_t);
 }
 
 // rows per slot that a workspace of `bytes` allows (0: it holds no tile)
-int64_t choice_fit_rows(int64_t N, int n, size_t bytes) {
+static int64_t choice_fit_rows(int64_t N, int n, size_t bytes) {
   int64_t rows = (int64_t)(bytes / CH_RING / ((size_t)n * sizeof(uint16_t))) / CH_ROW_ALIGN * CH_ROW_ALIGN;
   const int64_t want = choice_slot_rows(N, n);
   return rows < want ? rows : want;
@@ -183,9 +184,9 @@ static hipError_t launch_reduce(const float *preds, const uint16_t *idx, int S, 
 // slot_rows: rows per ring slot (a multiple of CH_ROW_ALIGN, >= CH_ROW_ALIGN), ws: CH_RING slots of
 // slot_rows * n uint16.  `st` is the caller's stream: the reduces run on it, the draws on the draw
 // stream between two events, and st waits for the last draw, so the state is final for st's later work.
-hipError_t launch_posterior_choice(uint32_t *state, const float *preds, int S, int64_t N, int n, int mode,
-                                   float *out, uint16_t *idx_out, uint16_t *ws, int64_t slot_rows,
-                                   hipStream_t st) {
+static hipError_t launch_posterior_choice(uint32_t *state, const float *preds, int S, int64_t N, int n, int mode,
+                                          float *out, uint16_t *idx_out, uint16_t *ws, int64_t slot_rows,
+                                          hipStream_t st) {
   ChoiceLane *L;
   hipError_t e = choice_lane(&L);
   if (e != hipSuccess) return e;
@@ -235,3 +236,42 @@ hipError_t launch_posterior_choice(uint32_t *state, const float *preds, int S, i
 }
 
 }  // namespace iqlhip
+
+using namespace iqlhip;
+
+// ------------------------------------------------------------ entry points --
+static int choice_check(int32_t S, int64_t N, int32_t n_samps) {
+  if (S < 2 || S > 2400) return fail(IQLHIP_ERR_INVALID, "S = %d outside 2..2400", S);
+  if (n_samps < 1 || n_samps > 1024) return fail(IQLHIP_ERR_INVALID, "n_samps = %d outside 1..1024", n_samps);
+  if (N < 1) return fail(IQLHIP_ERR_INVALID, "N = %lld must be >= 1", (long long)N);
+  return 0;
+}
+
+extern "C" int iqlhip_posterior_choice_workspace_bytes(int32_t S, int64_t N, int32_t n_samps, size_t *bytes) {
+  if (!bytes) return fail(IQLHIP_ERR_INVALID, "null argument");
+  if (int rc = choice_check(S, N, n_samps)) return rc;
+  *bytes = choice_workspace_bytes(N, n_samps);
+  return 0;
+}
+
+extern "C" int iqlhip_posterior_choice(uint32_t *state, const float *preds, int32_t S, int64_t N, int32_t n_samps,
+                                       int32_t mode, float *out, uint16_t *idx_out, void *workspace,
+                                       size_t workspace_bytes, void *stream) {
+  if (!state || !preds || !out || !workspace) return fail(IQLHIP_ERR_INVALID, "null argument");
+  if (int rc = choice_check(S, N, n_samps)) return rc;
+  if (mode != IQLHIP_CHOICE_MEAN && mode != IQLHIP_CHOICE_MEDIAN)
+    return fail(IQLHIP_ERR_INVALID, "mode %d: IQLHIP_CHOICE_MEAN or IQLHIP_CHOICE_MEDIAN", mode);
+  if (reinterpret_cast<uintptr_t>(workspace) % 16) return fail(IQLHIP_ERR_INVALID, "workspace not 16-byte aligned");
+  const int64_t slot_rows = choice_fit_rows(N, n_samps, workspace_bytes);
+  if (slot_rows < 32)
+    return fail(IQLHIP_ERR_INVALID, "workspace of %zu bytes holds no chunk (the full size is %zu)", workspace_bytes,
+                choice_workspace_bytes(N, n_samps));
+  hipStream_t st = (hipStream_t)stream;
+  uint32_t pos = 0;
+  HIP_TRY(hipMemcpyAsync(&pos, state + 624, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (pos > 624) return fail(IQLHIP_ERR_INVALID, "pos = %u outside 0..624", pos);
+  HIP_TRY(launch_posterior_choice(state, preds, S, N, n_samps, mode, out, idx_out, (uint16_t *)workspace, slot_rows,
+                                  st));
+  return 0;
+}

@@ -30,6 +30,7 @@
 // Cross-lane sums are DPP / v_permlane*_swap (common.h lane_sum), never ds_bpermute.
 #include "../../include/iqlhip.h"
 #include "common.h"
+#include "errors.h"
 
 namespace iqlhip {
 
@@ -481,16 +482,16 @@ __global__ __launch_bounds__(64 * PT_WAVES, 4) void k_pt_relabel(const iqlhip_pt
   }
 }
 
-size_t pt_smem_bytes(const iqlhip_pt_weights &W, int ql) {
+static size_t pt_smem_bytes(const iqlhip_pt_weights &W, int ql) {
   (void)ql;  // keys and values are never stored: the footprint does not depend on the window length
   const size_t ks = (size_t)round_up(W.state_dim, 16) + round_up(W.action_dim, 16);
   return (ks * E + 8 * 4 * 64 * 4 + 8 * E + 6 * E + 2 * PT_WAVES * CB + PT_SLOTS * E + 2 * PT_SLOTS * VLD +
           PT_SLOTS * (W.inter_dim + 4)) * 4 + 64;
 }
 
-hipError_t launch_pt(const iqlhip_pt_weights &W, const float *obs, const float *act, int64_t n_rows,
-                     const int64_t *win_start, const int32_t *win_len, const int32_t *win_t0, int64_t n_win,
-                     int ql, float *out, hipStream_t st) {
+static hipError_t launch_pt(const iqlhip_pt_weights &W, const float *obs, const float *act, int64_t n_rows,
+                            const int64_t *win_start, const int32_t *win_len, const int32_t *win_t0, int64_t n_win,
+                            int ql, float *out, hipStream_t st) {
   const size_t sm = pt_smem_bytes(W, ql);
   int dev = 0, cus = 256;
   (void)hipGetDevice(&dev);
@@ -509,3 +510,29 @@ hipError_t launch_pt(const iqlhip_pt_weights &W, const float *obs, const float *
 }
 
 }  // namespace iqlhip
+
+using namespace iqlhip;
+
+extern "C" int iqlhip_pt_relabel(const iqlhip_pt_weights *w, const float *obs, const float *act,
+                                 int64_t n_rows, const int64_t *win_start, const int32_t *win_len,
+                                 const int32_t *win_t0, int64_t n_win, int32_t query_length, float *out,
+                                 void *stream) {
+  if (!w || !obs || !act || !win_start || !win_len || !out) return fail(IQLHIP_ERR_INVALID, "null argument");
+  if (n_win <= 0 || n_rows <= 0 || query_length < 1) return fail(IQLHIP_ERR_INVALID, "empty problem");
+  if (w->embd_dim != 64) return fail(IQLHIP_ERR_UNSUPPORTED, "embd_dim %d: the kernel is built for 64", w->embd_dim);
+  if (w->num_layers != 1) return fail(IQLHIP_ERR_UNSUPPORTED, "num_layers %d: only 1 is built", w->num_layers);
+  const int nh = w->num_heads;
+  if (nh < 1 || nh > 16 || (nh & (nh - 1))) return fail(IQLHIP_ERR_UNSUPPORTED, "num_heads %d", nh);
+  if (w->inter_dim < 64 || w->inter_dim > 1024 || w->inter_dim % 256)
+    return fail(IQLHIP_ERR_UNSUPPORTED, "inter_dim %d: must be a multiple of 256 up to 1024", w->inter_dim);
+  if (w->state_dim < 1 || w->action_dim < 1 || w->state_dim + w->action_dim > 192)
+    return fail(IQLHIP_ERR_UNSUPPORTED, "state/action dims");
+  if (w->n_temb < 1) return fail(IQLHIP_ERR_INVALID, "empty timestep table");
+  if (!win_t0 && query_length > w->n_temb)
+    return fail(IQLHIP_ERR_INVALID, "query_length exceeds the timestep table");
+  if (pt_smem_bytes(*w, query_length) > 160 * 1024)
+    return fail(IQLHIP_ERR_UNSUPPORTED, "query_length %d does not fit the 160 KiB LDS", query_length);
+  HIP_TRY(launch_pt(*w, obs, act, n_rows, win_start, win_len, win_t0, n_win, query_length, out,
+                    (hipStream_t)stream));
+  return 0;
+}

@@ -25,8 +25,11 @@
 // rows and up to 256 output columns (four 16-column tiles per wave, two 16-row tiles each: eight
 // independent accumulators), A staged in LDS in 256-deep chunks, B straight from the torch-layout
 // weights (16 bytes per lane, L2 resident).
+#include <algorithm>
+
 #include "../../include/iqlhip.h"
 #include "common.h"
+#include "errors.h"
 
 namespace iqlhip {
 namespace ptg {
@@ -365,24 +368,24 @@ static void lin(const Lin &p, const Chunk &c, int64_t rows, int tokens, hipStrea
 
 }  // namespace ptg
 
-int pt_general_tp(int ql) { return round_up(2 * ql, ptg::RT); }
+static int pt_general_tp(int ql) { return round_up(2 * ql, ptg::RT); }
 
-size_t pt_general_bytes(const iqlhip_pt_model &m, int ql, int64_t nw) {
+static size_t pt_general_bytes(const iqlhip_pt_model &m, int ql, int64_t nw) {
   const int64_t tail_rows = (nw + ptg::RT - 1) / ptg::RT * ptg::RT;
   return (size_t)(nw * ptg::tok_floats(m, pt_general_tp(ql)) + tail_rows * ptg::tail_floats(m)) * 4;
 }
 
 // windows a workspace of `bytes` holds (0: not even one)
-int64_t pt_general_fit(const iqlhip_pt_model &m, int ql, size_t bytes) {
+static int64_t pt_general_fit(const iqlhip_pt_model &m, int ql, size_t bytes) {
   const int64_t per = ptg::tok_floats(m, pt_general_tp(ql)) + ptg::tail_floats(m);
   const int64_t pad = (ptg::RT - 1) * ptg::tail_floats(m);
   const int64_t fl = (int64_t)(bytes / 4);
   return fl <= pad ? 0 : (fl - pad) / per;
 }
 
-hipError_t launch_pt_general(const iqlhip_pt_model &m, const float *obs, const float *act, int64_t n_rows,
-                             const int64_t *win_start, const int32_t *win_len, const int32_t *win_t0,
-                             int64_t n_win, int ql, float *ws, int64_t chunk, float *out, hipStream_t st) {
+static hipError_t launch_pt_general(const iqlhip_pt_model &m, const float *obs, const float *act, int64_t n_rows,
+                                    const int64_t *win_start, const int32_t *win_len, const int32_t *win_t0,
+                                    int64_t n_win, int ql, float *ws, int64_t chunk, float *out, hipStream_t st) {
   using namespace ptg;
   const int E = m.embd_dim, I = m.inter_dim, NH = m.num_heads, tp = pt_general_tp(ql);
   const int mx = I > E ? I : E;
@@ -448,3 +451,77 @@ hipError_t launch_pt_general(const iqlhip_pt_model &m, const float *obs, const f
 }
 
 }  // namespace iqlhip
+
+using namespace iqlhip;
+
+// ---- entry points: host-only shape checks, then the chunked launches ----
+static constexpr size_t PT_GENERAL_BUDGET = size_t(1) << 30;  // workspace of one full chunk
+
+static int pt_general_check(const iqlhip_pt_model *m, int32_t query_length) {
+  if (!m) return fail(IQLHIP_ERR_INVALID, "null model");
+  if (m->num_layers < 1 || m->num_layers > 8)
+    return fail(IQLHIP_ERR_UNSUPPORTED, "num_layers %d: the general path takes 1..8", m->num_layers);
+  const int E = m->embd_dim, nh = m->num_heads;
+  if (E < 64 || E > 256 || E % 64)
+    return fail(IQLHIP_ERR_UNSUPPORTED, "embd_dim %d: must be a multiple of 64 up to 256", E);
+  if (nh < 1 || (nh & (nh - 1)) || E / nh < 4)
+    return fail(IQLHIP_ERR_UNSUPPORTED, "num_heads %d: must be a power of two with embd_dim / num_heads >= 4", nh);
+  if (m->inter_dim < 64 || m->inter_dim > 1024 || m->inter_dim % 64)
+    return fail(IQLHIP_ERR_UNSUPPORTED, "inter_dim %d: must be a multiple of 64 up to 1024", m->inter_dim);
+  if (m->state_dim < 1 || m->action_dim < 1 || m->state_dim + m->action_dim > 256)
+    return fail(IQLHIP_ERR_UNSUPPORTED, "state_dim %d + action_dim %d: must be <= 256", m->state_dim, m->action_dim);
+  if (query_length < 1) return fail(IQLHIP_ERR_INVALID, "query_length must be positive");
+  if (query_length > 4096) return fail(IQLHIP_ERR_UNSUPPORTED, "query_length %d > 4096", query_length);
+  if (m->n_temb < 1) return fail(IQLHIP_ERR_INVALID, "empty timestep table");
+  if (!m->blocks) return fail(IQLHIP_ERR_INVALID, "null block array");
+  const float *top[] = {m->state_wT, m->state_b, m->action_wT, m->action_b, m->temb, m->sln_w, m->sln_b,
+                        m->lnf_w, m->lnf_b, m->pref_w_last};
+  for (const float *t : top)
+    if (!t) return fail(IQLHIP_ERR_INVALID, "null weight pointer");
+  for (int l = 0; l < m->num_layers; ++l) {
+    const iqlhip_pt_block &b = m->blocks[l];
+    const float *blk[] = {b.ln0_w, b.ln0_b, b.qkv_w, b.qkv_b, b.attn_out_w, b.attn_out_b,
+                          b.ln1_w, b.ln1_b, b.mlp_in_w, b.mlp_in_b, b.mlp_out_w, b.mlp_out_b};
+    for (const float *t : blk)
+      if (!t) return fail(IQLHIP_ERR_INVALID, "null weight pointer in block %d", l);
+  }
+  return 0;
+}
+
+// windows of one full chunk: what 1 GiB holds (at least one), and few enough that the attention
+// grid (one wave per head and token row) stays far inside 2^31 work-groups
+static int64_t pt_general_cap(const iqlhip_pt_model &m, int ql) {
+  int64_t cap = pt_general_fit(m, ql, PT_GENERAL_BUDGET);
+  const int64_t grid_cap = ((int64_t)1 << 30) / ((int64_t)m.num_heads * pt_general_tp(ql));
+  cap = std::min<int64_t>(cap, std::min<int64_t>(grid_cap, 65536));
+  return std::max<int64_t>(cap, 1);
+}
+
+extern "C" int iqlhip_pt_general_workspace_bytes(const iqlhip_pt_model *m, int32_t query_length, int64_t n_win,
+                                                 size_t *bytes) {
+  if (!bytes) return fail(IQLHIP_ERR_INVALID, "null argument");
+  if (int rc = pt_general_check(m, query_length)) return rc;
+  if (n_win <= 0) return fail(IQLHIP_ERR_INVALID, "n_win must be positive");
+  *bytes = pt_general_bytes(*m, query_length, std::min(n_win, pt_general_cap(*m, query_length)));
+  return 0;
+}
+
+extern "C" int iqlhip_pt_relabel_general(const iqlhip_pt_model *m, const float *obs, const float *act,
+                                         int64_t n_rows, const int64_t *win_start, const int32_t *win_len,
+                                         const int32_t *win_t0, int64_t n_win, int32_t query_length,
+                                         void *workspace, size_t workspace_bytes, float *out, void *stream) {
+  if (int rc = pt_general_check(m, query_length)) return rc;
+  if (!obs || !act || !win_start || !win_len || !out || !workspace) return fail(IQLHIP_ERR_INVALID, "null argument");
+  if (n_win <= 0 || n_rows <= 0) return fail(IQLHIP_ERR_INVALID, "empty problem");
+  if (!win_t0 && query_length > m->n_temb)
+    return fail(IQLHIP_ERR_INVALID, "query_length exceeds the timestep table");
+  if (reinterpret_cast<uintptr_t>(workspace) % 16) return fail(IQLHIP_ERR_INVALID, "workspace not 16-byte aligned");
+  const int64_t chunk = std::min(std::min(n_win, pt_general_cap(*m, query_length)),
+                                 pt_general_fit(*m, query_length, workspace_bytes));
+  if (chunk < 1)
+    return fail(IQLHIP_ERR_INVALID, "workspace of %zu bytes holds no window (one needs %zu)", workspace_bytes,
+                pt_general_bytes(*m, query_length, 1));
+  HIP_TRY(launch_pt_general(*m, obs, act, n_rows, win_start, win_len, win_t0, n_win, query_length,
+                            static_cast<float *>(workspace), chunk, out, (hipStream_t)stream));
+  return 0;
+}

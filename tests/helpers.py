@@ -512,3 +512,81 @@ def pt_clamp_windows(starts, lens, t0, n_rows, n_temb, QL):
     starts = np.clip(np.asarray(starts, np.int64), 0, n_rows - lens)
     t0 = np.clip(np.asarray(t0, np.int64), 0, n_temb - lens)
     return starts.astype(np.int64), lens.astype(np.int32), t0.astype(np.int32)
+
+
+# ---- include/iqlhip.h as data: what tests/test_abi_host.py compares the ctypes binding with ----
+class CType:
+    """A C type as a declaration spells it, ``const`` dropped: ``base`` (a scalar, ``void``, ``char`` or a struct
+    name), ``ptr`` levels of ``*`` and ``array``, the length of a ``[n]`` suffix or None."""
+
+    def __init__(self, base, ptr=0, array=None):
+        self.base, self.ptr, self.array = base, ptr, array
+
+    def __repr__(self):
+        return self.base + " " * bool(self.ptr) + "*" * self.ptr + (f"[{self.array}]" if self.array is not None else "")
+
+
+def _c_int_expr(expr, macros):
+    """An integer macro body: integers, earlier macros, + - * / and parentheses."""
+    import re
+    expr = re.sub(r"[A-Za-z_]\w*", lambda m: str(macros[m.group(0)]), expr)
+    assert re.fullmatch(r"[\d\s()+\-*/]+", expr), expr
+    return int(eval(expr.replace("/", "//"), {"__builtins__": {}}))
+
+
+def _c_declarators(decl, macros):
+    """A field or parameter declaration ``const float *a, *b[N]`` -> [("a", CType), ("b", CType)]; every
+    declarator carries a name (the header names all its parameters)."""
+    import re
+    first, *more = [d.strip() for d in decl.split(",")]
+    words = re.findall(r"[A-Za-z_]\w*", re.sub(r"\[.*?\]", "", first))
+    words = [w for w in words if w != "const"]
+    base, out = " ".join(words[:-1]), []
+    for d in [first] + more:
+        m = re.fullmatch(r"(.*?)([A-Za-z_]\w*)\s*(?:\[(.*?)\])?", d, re.S)
+        assert m, d
+        out.append((m.group(2), CType(base, m.group(1).count("*"),
+                                      _c_int_expr(m.group(3), macros) if m.group(3) is not None else None)))
+    return out
+
+
+def parse_c_header(text):
+    """The declarations of a C header in the plain style of include/iqlhip.h (no function pointers, no nested
+    structs, no bit fields): {"macros": {name: int}, "enums": {name: int}, "structs": {name: [(field, CType)]},
+    "opaque": {names of ``typedef struct x x;``}, "functions": {name: (CType, [(param, CType)])}}."""
+    import re
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    macros = {}
+    for name, body in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(\w+)[ \t]+(\S[^\n]*)$", text, flags=re.M):
+        macros[name] = _c_int_expr(body, macros)
+    text = re.sub(r"^[ \t]*#[^\n]*$", " ", text, flags=re.M)
+    text = re.sub(r'extern\s+"C"\s*\{', " ", text)
+    enums = {}
+    for body in re.findall(r"typedef\s+enum\s*\{(.*?)\}\s*\w+\s*;", text, flags=re.S):
+        for name, value in re.findall(r"(\w+)\s*=\s*([^,}]+)", body):
+            enums[name] = _c_int_expr(value, macros)
+    text = re.sub(r"typedef\s+enum\s*\{.*?\}\s*\w+\s*;", " ", text, flags=re.S)
+    structs = {}
+    for body, name in re.findall(r"typedef\s+struct\s*\{(.*?)\}\s*(\w+)\s*;", text, flags=re.S):
+        assert "{" not in body, name
+        structs[name] = [f for decl in body.split(";") if decl.strip() for f in _c_declarators(decl.strip(), macros)]
+    text = re.sub(r"typedef\s+struct\s*\{.*?\}\s*\w+\s*;", " ", text, flags=re.S)
+    opaque = set()
+    for tag, name in re.findall(r"typedef\s+struct\s+(\w+)\s+(\w+)\s*;", text):
+        assert tag == name, (tag, name)
+        opaque.add(name)
+    text = re.sub(r"typedef\s+struct\s+\w+\s+\w+\s*;", " ", text)
+    functions = {}
+    for stmt in text.split(";"):
+        stmt = stmt.strip().lstrip("}").strip()  # (the brace that closes extern "C")
+        if not stmt:
+            continue
+        m = re.fullmatch(r"(.*?)\b(\w+)\s*\((.*)\)", stmt, re.S)
+        assert m and "(" not in m.group(3), "not a prototype: " + stmt
+        ret, name, params = m.group(1), m.group(2), m.group(3).strip()
+        words = [w for w in re.findall(r"[A-Za-z_]\w*", ret) if w != "const"]
+        assert name not in functions, name
+        functions[name] = (CType(" ".join(words), ret.count("*")),
+                           [] if params == "void" else [_c_declarators(p, macros)[0] for p in params.split(",")])
+    return {"macros": macros, "enums": enums, "structs": structs, "opaque": opaque, "functions": functions}
