@@ -508,6 +508,8 @@ __device__ __forceinline__ void deep_misc(const DeepDesc &D, const DeepArgs &G, 
 // 10.2 -> 5.4 us at one) -- and 64 x 64 tiles from batch 1024 on, where the operand panels (batch x 2 bytes per
 // row) are the traffic (E = 4 at batch 1024: 26.7 us against 32.3), and from 768 units on (H = 1024: 43.8 us
 // against 46.6), provided such tiles still make ~150 work-groups (deep_create).
+// Tests: tests/test_gpu_general_step_envelope.py enters both orientations (hidden widths 1 .. 1023 that are no
+// multiple of 4: dZ^T X on every layer; 4 .. 1024: transposed) at both tile widths (DEEP_TQ = 4 by width and by batch).
 template <bool BF16, int DEEP_TQ>
 __global__ __launch_bounds__(256) void kd_update(const DeepDesc *__restrict__ Dp, const DeepItem *__restrict__ items,
                                                  const DeepArgs *__restrict__ Gp, DeepCtr *__restrict__ Cp,

@@ -23,11 +23,11 @@ def make_nets(hyper, nets, device=DEV):
     return q.to(device), v.to(device), actor.to(device)
 
 
-def make_trainer(hyper, nets, mode, device=DEV, **kw):
+def make_trainer(hyper, nets, mode, device=DEV, lr=3e-4, **kw):
     q, v, actor = make_nets(hyper, nets, device)
-    vo = torch.optim.Adam(v.parameters(), lr=3e-4)
-    qo = torch.optim.Adam(q.parameters(), lr=3e-4)
-    ao = torch.optim.Adam(actor.parameters(), lr=3e-4)
+    vo = torch.optim.Adam(v.parameters(), lr=lr)
+    qo = torch.optim.Adam(q.parameters(), lr=lr)
+    ao = torch.optim.Adam(actor.parameters(), lr=lr)
     tr = ia.ImplicitQLearning(
         max_action=1.0, actor=actor, actor_optimizer=ao, q_network=q, q_optimizer=qo,
         v_network=v, v_optimizer=vo, iql_tau=hyper["iql_tau"], beta=hyper["beta"],

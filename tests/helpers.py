@@ -338,6 +338,57 @@ def bf16_ulp(x):
     return np.ldexp(1.0, e - 1 - 7)
 
 
+FWD_TOL = 2e-5  # the project's rtol = atol for fp32 forwards of up to four Linear layers, width <= 256
+
+
+def forward_reference(params, mode, s, a):
+    """which -> (reference [n, width] in fp64, |second CPU forward - reference| per element) of the four
+    forwards "q" | "v" | "actor" | "q_target" on ``params`` = (qf, vf, actor, q_target) parameter dicts.
+    fp32: mlp_forward_ref in fp64, the second forward the same in fp32 numpy; bf16: the oracle's autocast
+    restatement, the second forward mlp_forward_bf16_f64."""
+    qf, vf, actor, qt = params
+    sa = np.concatenate([s, a], axis=1)
+    out = {}
+    if mode == "fp32":
+        def pair(p, prefix, x, out_act):
+            ws, bs = net_layers(p, prefix)
+            want = mlp_forward_ref(ws, bs, x, 0, out_act)
+            return want, np.abs(mlp_forward_ref(ws, bs, x, 0, out_act, dtype=np.float32).astype(np.float64) - want)
+        for which, q in (("q", qf), ("q_target", qt)):
+            cols = [pair(q, f"q{e + 1}.net.", sa, 0) for e in range(orc.n_critics(q))]
+            out[which] = tuple(np.concatenate(c, axis=1) for c in zip(*cols))
+        out["v"] = pair(vf, "v.net.", s, 0)
+        out["actor"] = pair(actor, "net.net.", s, 1)
+        return out
+    for which, q in (("q", qf), ("q_target", qt)):
+        want = np.stack(orc.critics_all(q, s, a, "bf16")[0], axis=1).astype(np.float64)
+        other = np.concatenate([mlp_forward_bf16_f64(sa, q, f"q{e + 1}.net.") for e in range(orc.n_critics(q))], axis=1)
+        out[which] = (want, np.abs(other - want))
+    want = orc.value_forward(vf, s, "bf16")[0][:, None].astype(np.float64)
+    out["v"] = (want, np.abs(mlp_forward_bf16_f64(s, vf, "v.net.") - want))
+    want = orc.policy_forward(actor, s, "bf16")[0].astype(np.float64)
+    out["actor"] = (want, np.abs(mlp_forward_bf16_f64(s, actor, "net.net.", "tanh") - want))
+    return out
+
+
+def forward_judge(mode, got, want, gap, n_lin, width):
+    """(within the bounds of tests/test_gpu_forward_envelope.py's docstring?, the figures as text)."""
+    assert got.shape == want.shape and got.dtype == np.float32
+    err = np.abs(got.astype(np.float64) - want)
+    if mode == "fp32":
+        if n_lin <= 4 and width <= 256:
+            bound, lim = f"rtol = atol = {FWD_TOL:.0e}", FWD_TOL + FWD_TOL * np.abs(want)
+        else:
+            atol = max(4 * float(gap.max()), FWD_TOL)
+            bound, lim = f"atol {atol:.2e}", atol
+        return bool(np.all(err <= lim)), f"max |err| {err.max():.3e} ({bound}; fp32 numpy vs fp64: gap {gap.max():.3e})"
+    max_b = max(4 * float(gap.max()), 2 * float(bf16_ulp(np.abs(want).max())))
+    med_b = max(4 * float(np.median(gap)), 0.25 * float(bf16_ulp(np.median(np.abs(want)))))
+    ok = err.max() <= max_b and np.median(err) <= med_b
+    return bool(ok), (f"max |err| {err.max():.3e} (bound {max_b:.3e}), median {np.median(err):.3e} (bound {med_b:.3e}), "
+                      f"bit-identical {np.mean(err == 0):.3f}; the CPU pair: max gap {gap.max():.3e}, median {np.median(gap):.3e}")
+
+
 # ---------------------------------------------------------------------------------------------
 # Preference-transformer relabel (tests/test_gpu_relabel.py, test_gpu_pt_general.py,
 # test_gpu_pt_envelope.py): windows, their oracle values, the two bounds, and the cases of the
@@ -512,6 +563,392 @@ def pt_clamp_windows(starts, lens, t0, n_rows, n_temb, QL):
     starts = np.clip(np.asarray(starts, np.int64), 0, n_rows - lens)
     t0 = np.clip(np.asarray(t0, np.int64), 0, n_temb - lens)
     return starts.astype(np.int64), lens.astype(np.int32), t0.astype(np.int32)
+
+
+# ---------------------------------------------------------------------------------------------
+# Envelope tests of the general layer-wise training step (csrc/iql_deep.hip: kd_backward / kd_update;
+# tests/test_gpu_general_step_envelope.py and, on the host, tests/test_general_step_envelope_host.py).
+# Every step is judged at the parameters the GPU held BEFORE it: the references below take a state
+# (qf, vf, actor, q_target) and one batch, and return that single step's losses and gradients.
+# ---------------------------------------------------------------------------------------------
+GS_LR = 1e-2          # one sign-like Adam step moves every weight by several bf16 ulps (largest ulp ~1e-3 at fan-in 17)
+GS_ROWS = 200
+GS_STEPS = 2          # step 1 on kd_sync's copies, step 2 on the copies kd_update wrote
+GS_MARGIN = 1e-5      # the project's kink threshold (_shape_case)
+GS_GRAD_TOL = 5e-5    # fp32 gradients, of the largest reference entry (_shape_case)
+GS_BF16_FLOOR = 2e-2  # bf16 gradients: the project's 2e-2 of the largest entry (_shape_case)
+GS_LOSS_RTOL = {"fp32": 3e-5, "bf16": 6e-3}
+GS_HYPER = dict(iql_tau=0.8, beta=3.0, max_steps=1000, discount=0.99, tau=0.005)
+GS_ADAM = dict(beta1=0.9, beta2=0.999, eps=1e-8)  # torch.optim.Adam's defaults
+
+# id -> (S, A, n_hidden, H, B, E, deterministic, dropout, offset biases, numpy seed, tq, orientation of the hidden
+# and output layers).  seed: the first that gs_pick_seed accepts (the reference's own two steps keep every net
+# 2e-5 from a kink and its bf16 restatements agree within the test's bounds; B >= 1024 cannot avoid a kink, any seed).  tq / orientation: what the case is meant to reach, checked
+# against gs_update_plan, the rule of deep_create restated.
+GS_CASES = {
+    # hidden width not a multiple of 4: dW = dZ^T X on hidden and output layers
+    "1x1": (12, 5, 1, 1, 16, 2, False, None, False, 0, 1, "dzT_x"),
+    "2x3_det": (11, 5, 2, 3, 16, 2, True, None, False, 0, 1, "dzT_x"),
+    "3x17_b17": (12, 5, 3, 17, 17, 2, False, None, False, 1, 1, "dzT_x"),
+    "6x33_det": (11, 5, 6, 33, 16, 2, True, None, False, 10, 1, "dzT_x"),
+    "2x65_b32_e3": (17, 6, 2, 65, 32, 3, False, None, False, 0, 1, "dzT_x"),
+    "3x129": (17, 6, 3, 129, 16, 2, False, None, False, 10, 1, "dzT_x"),
+    "2x257_det": (17, 6, 2, 257, 16, 2, True, None, False, 15, 1, "dzT_x"),
+    "1x1023_offset": (17, 6, 1, 1023, 16, 2, False, None, True, 1, 1, "dzT_x"),
+    "2x765_offset": (17, 6, 2, 765, 16, 2, False, None, True, 2, 4, "dzT_x"),
+    # multiples of 4 at the boundaries: dW^T = X^T dZ
+    "2x4": (17, 6, 2, 4, 16, 2, False, None, False, 0, 1, "xT_dz"),
+    "3x36_det": (17, 6, 3, 36, 16, 2, True, None, False, 4, 1, "xT_dz"),
+    "2x68_b48": (17, 6, 2, 68, 48, 2, False, None, False, 3, 1, "xT_dz"),
+    "2x768_offset": (17, 6, 2, 768, 16, 2, False, None, True, 0, 4, "xT_dz"),
+    "6x1024_offset": (17, 6, 6, 1024, 16, 2, False, None, True, 28, 4, "xT_dz"),
+    # tq = 4 reached by batch size, and just under the rule
+    "2x129_b1024_e8": (12, 5, 2, 129, 1024, 8, False, None, False, 0, 4, "dzT_x"),
+    "2x192_b1024_e8": (12, 5, 2, 192, 1024, 8, False, None, False, 0, 4, "xT_dz"),
+    "2x129_b1024_e7": (12, 5, 2, 129, 1024, 7, False, None, False, 0, 1, "dzT_x"),
+    # input and output widths at an odd hidden width
+    "s15a17_2x21": (15, 17, 2, 21, 16, 2, False, None, False, 0, 1, "dzT_x"),
+    "s96a32_1x7_det": (96, 32, 1, 7, 16, 2, True, None, False, 0, 1, "dzT_x"),
+    "s1a1_2x5": (1, 1, 2, 5, 16, 2, False, None, False, 0, 1, "dzT_x"),
+    # dropout at an odd width
+    "3x33_b17_dropout": (12, 5, 3, 33, 17, 2, False, 0.25, False, 1, 1, "dzT_x"),
+}
+GS_DAMAGE_CASES = ("3x17_b17", "2x768_offset")  # where the host test shows what the bounds reject
+
+
+def _round_up(x, m):
+    return (x + m - 1) // m * m
+
+
+def gs_update_plan(S, A, NH, H, B, E):
+    """(tq, orientation of the layers with H in-features, the count ``wide``) kd_update runs at, restated from deep_create
+    (csrc/iql_deep.hip): 64 x 64 tiles (tq = 4) when (BP >= 1024 or Hp >= 768) and the 64 x 64 tiles of all
+    trained tensors number >= 150, else 64 x 16 (tq = 1); a layer whose in-feature count is a multiple of 4
+    is computed transposed (dW^T = X^T dZ, "xT_dz"), any other as dW = dZ^T X ("dzT_x")."""
+    BP, Hp = _round_up(_round_up(B, 16), 32), _round_up(H, 32)
+    wide = 0
+    for n_in, n_out in [(S + A, 1)] * E + [(S, 1), (S, A)]:
+        dims = [n_in] + [H] * NH + [n_out]
+        wide += sum(-(-dims[l + 1] // 64) * -(-dims[l] // 64) for l in range(NH + 1))
+    return (4 if (BP >= 1024 or Hp >= 768) and wide >= 150 else 1), ("xT_dz" if H % 4 == 0 else "dzT_x"), wide
+
+
+def gs_inputs(case, seed=None):
+    """(hyper, (qf, vf, actor), data, indices [GS_STEPS, B]) of a case: forward_nets' weights from the case's
+    numpy seed, _shape_case's data on GS_ROWS rows.  Offset cases: hidden-layer biases + 3 (unit index % 4 != 3)
+    or - 3: most of their units are on or off for the whole batch (3 to 15 % of V's see both signs at step 1), which
+    keeps wide layers' thousands of pre-activations away from the kink -- they test tile geometry, the per-sample
+    relu' masks are the small cases' part."""
+    S, A, NH, H, B, E, det, drop, offset, case_seed = GS_CASES[case][:10]
+    rng = np.random.default_rng([case_seed if seed is None else seed, S, A, NH, H, B, E])
+    nets = forward_nets(rng, S, A, H, NH, E, det, drop)
+    if offset:
+        shift = np.where(np.arange(H) % 4 != 3, 3.0, -3.0).astype(np.float32)
+        for net, prefixes in zip(nets, ([f"q{e + 1}.net." for e in range(E)], ["v.net."], ["net.net."])):
+            for prefix in prefixes:
+                for _, bk in orc.linear_keys(net, prefix)[:-1]:
+                    net[bk] = (net[bk] + shift).astype(np.float32)
+    N = GS_ROWS
+    data = {"observations": rng.standard_normal((N, S)).astype(np.float32),
+            "actions": rng.uniform(-1, 1, (N, A)).astype(np.float32),
+            "rewards": rng.standard_normal(N).astype(np.float32),
+            "next_observations": rng.standard_normal((N, S)).astype(np.float32),
+            "terminals": (rng.uniform(size=N) < 0.05).astype(np.float32)}
+    idx = rng.integers(0, N, (GS_STEPS, B)).astype(np.int64)
+    hyper = dict(GS_HYPER, s_dim=S, a_dim=A, hidden=H, n_hidden=NH, n_critics=E, deterministic=det, dropout=drop,
+                 n_rows=N, batch=B)
+    return hyper, nets, data, idx
+
+
+def gs_oracle_at(hyper, state, mode, total_it, acc=np.float32):
+    """An IQLOracle holding ``state`` = (qf, vf, actor, q_target) after ``total_it`` steps."""
+    qf, vf, actor, qt = state
+    o = orc.IQLOracle(qf, vf, actor, iql_tau=hyper["iql_tau"], beta=hyper["beta"], max_steps=hyper["max_steps"],
+                      discount=hyper["discount"], tau=hyper["tau"], lr=GS_LR, mode=mode, dropout=hyper["dropout"], acc=acc)
+    o.q_target = {k: np.array(v, dtype=np.float32) for k, v in qt.items()}
+    o.total_it = total_it
+    return o
+
+
+def gs_f64_step(hyper, state, batch, keeps=None):
+    """float64 autograd of the three IQL losses (ref:581-637) at ``state``, on plain torch tensors:
+    target_q = min_e q_target, detached; next_v detached; exp_adv detached and clamped at 100; the Gaussian
+    term -Normal(mean, exp(clamp(log_std))).log_prob(a).sum(-1).  Two tensors are held as the fp32 numbers the
+    step stores: the tanh output, which its backward reads (ATen's tanh_backward: g (1 - out^2)), and the detached
+    weight exp_adv.  Where they saturate or underflow -- the wide offset cases at step 2: |pre-tanh| > 16,
+    exp(beta adv) below 1e-45 -- the fp32 FORMAT decides that a gradient is exactly zero, not a summation order,
+    and a reference that ignored it would call that zero wrong; anywhere else the rounding moves the result by
+    1e-7 of itself.  Returns (losses, grads, margin) in the oracle's layout: margin[group] = the smallest hidden |pre-activation| of the group's trained forwards,
+    for V also min |adv| (IQLOracle.last_margin)."""
+    import torch
+    t64 = lambda x: torch.from_numpy(np.asarray(x, dtype=np.float64))
+    as_f32 = lambda x: x.float().double()
+
+    class TanhStoredF32(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x):
+            out = as_f32(torch.tanh(x))
+            ctx.save_for_backward(out)
+            return out
+
+        @staticmethod
+        def backward(ctx, g):
+            out, = ctx.saved_tensors
+            return g * (1.0 - out * out)
+
+    qf, vf, actor, qt = ({k: t64(v) for k, v in d.items()} for d in state)
+    for d in (qf, vf, actor):
+        for v in d.values():
+            v.requires_grad_(True)
+    s, a, r, s2, d = [t64(x) for x in batch]
+    r, d = r.reshape(-1), d.reshape(-1)
+    scale = None if keeps is None else float(np.float32(1.0) / np.float32(1.0 - hyper["dropout"]))
+
+    def mlp(x, p, prefix, keeps=None):
+        keys, margin = orc.linear_keys(p, prefix), np.inf
+        for l, (wk, bk) in enumerate(keys):
+            x = x @ p[wk].T + p[bk]
+            if l < len(keys) - 1:
+                margin = min(margin, float(x.detach().abs().min()))
+                x = torch.relu(x)
+                if keeps is not None:
+                    x = x * (t64(keeps[l]) * scale)
+        return x, margin
+
+    E = orc.n_critics(qf)
+    with torch.no_grad():
+        next_v = mlp(s2, vf, "v.net.")[0][:, 0]
+        target_q = torch.stack([mlp(torch.cat([s, a], 1), qt, f"q{e + 1}.net.")[0][:, 0] for e in range(E)]).min(0).values
+    v, m_v = mlp(s, vf, "v.net.")
+    adv = target_q - v[:, 0]
+    value_loss = ((hyper["iql_tau"] - (adv < 0).double()).abs() * adv ** 2).mean()
+    targets = r + (1.0 - d) * hyper["discount"] * next_v
+    qs = [mlp(torch.cat([s, a], 1), qf, f"q{e + 1}.net.") for e in range(E)]
+    q_loss = sum(((q[:, 0] - targets) ** 2).mean() for q, _ in qs) / E
+    exp_adv = as_f32(torch.exp(hyper["beta"] * adv.detach()).clamp(max=orc.EXP_ADV_MAX))
+    out, m_a = mlp(s, actor, "net.net.", keeps)
+    mean = TanhStoredF32.apply(out)
+    if "log_std" in actor:
+        std = torch.exp(actor["log_std"].clamp(orc.LOG_STD_MIN, orc.LOG_STD_MAX))
+        bc = -torch.distributions.Normal(mean, std).log_prob(a).sum(-1)
+    else:
+        bc = ((mean - a) ** 2).sum(1)
+    policy_loss = (exp_adv * bc).mean()
+    (value_loss + q_loss + policy_loss).backward()  # (three disjoint parameter sets: one backward)
+    grads = {g: {k: t.grad.numpy() for k, t in p.items()} for g, p in (("q", qf), ("v", vf), ("actor", actor))}
+    margin = {"v": min(m_v, float(adv.detach().abs().min())), "q": min(m for _, m in qs), "actor": m_a}
+    return {"value_loss": value_loss.item(), "q_loss": q_loss.item(), "actor_loss": policy_loss.item()}, grads, margin
+
+
+def gs_reference_step(hyper, state, mode, batch, total_it, keeps=None):
+    """The reference of ONE step at ``state``: {"losses": the oracle's in ``mode``, "grads": group -> name ->
+    array, "gap": the same layout or None, "margin": group -> float}.
+    fp32: gradients and margins from gs_f64_step.  bf16: the oracle in "bf16" mode; gap = what the same
+    restatement with every sum in fp64 (acc=float64) differs by, elementwise."""
+    o = gs_oracle_at(hyper, state, mode, total_it)
+    losses = o.train(batch, keeps)
+    if mode == "fp32":
+        _, grads, margin = gs_f64_step(hyper, state, batch, keeps)
+        return {"losses": losses, "grads": grads, "gap": None, "margin": margin, "oracle_grads": o.last_grads}
+    o64 = gs_oracle_at(hyper, state, mode, total_it, acc=np.float64)
+    o64.train(batch, keeps)
+    gap = {g: {k: np.abs(o64.last_grads[g][k].astype(np.float64) - w) for k, w in d.items()} for g, d in o.last_grads.items()}
+    return {"losses": losses, "grads": o.last_grads, "gap": gap, "margin": o.last_margin}
+
+
+def gs_loose_bound(mode, B):
+    """The project's bound for a net within GS_MARGIN of a kink (_shape_case): a few samples' share."""
+    return max(4.0 / B, GS_BF16_FLOOR if mode == "bf16" else 0.0)
+
+
+def gs_judge_grad(mode, got, want, gap=None, loose=None):
+    """One gradient tensor against its reference: (ok, figures as text, max |err| / max |reference|, share of
+    bit-identical entries).  A reference that is identically zero must be met exactly.  Errors are relative to
+    the largest reference entry.
+      fp32  max |err| <= GS_GRAD_TOL
+      bf16  max |err| <= max(4 x max gap, GS_BF16_FLOOR), median |err| <= max(4 x median gap, a quarter bf16 ulp
+            at the median |reference|)
+      loose (a float: the net is within GS_MARGIN of a kink in this step) max |err| <= loose, nothing else."""
+    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
+    assert got.shape == want.shape, (got.shape, want.shape)
+    err, top = np.abs(got - want), float(np.abs(want).max())
+    same = float(np.mean(err == 0))
+    if top == 0.0:
+        return bool(err.max() == 0.0), f"zero reference, max |got| {err.max():.3e}", float(err.max() != 0), same
+    rel = float(err.max()) / top
+    if loose is not None:
+        return rel <= loose, f"max {rel:.3e} of the largest entry (LOOSE bound {loose:.2e})", rel, same
+    if mode == "fp32":
+        return rel <= GS_GRAD_TOL, f"max {rel:.3e} of the largest entry (bound {GS_GRAD_TOL:.0e})", rel, same
+    max_b = max(4 * float(gap.max()), GS_BF16_FLOOR * top)
+    med_b = max(4 * float(np.median(gap)), 0.25 * float(bf16_ulp(np.median(np.abs(want)))))
+    ok = err.max() <= max_b and np.median(err) <= med_b
+    return bool(ok), (f"max {rel:.3e} of the largest entry (bound {max_b / top:.3e}), median |err| {np.median(err):.3e} "
+                      f"(bound {med_b:.3e}), bit-identical {same:.4f}; max gap {gap.max() / top:.3e}"), rel, same
+
+
+def gs_judge_grads(mode, got, ref, B, groups=("q", "v", "actor")):
+    """Every tensor of ``got`` (group -> name -> array) against ``ref`` (gs_reference_step): (failures as text,
+    report lines, groups judged under the loose bound, largest relative error under the tight bounds, share of
+    bit-identical entries over all tensors but the fp32 log_std)."""
+    bad, lines, loose_groups, worst, n_same, n_all = [], [], [], 0.0, 0.0, 0
+    for g in groups:
+        loose = gs_loose_bound(mode, B) if ref["margin"][g] < GS_MARGIN else None
+        if loose is not None:
+            loose_groups.append(g)
+        assert got[g].keys() == ref["grads"][g].keys()
+        for k, want in ref["grads"][g].items():
+            ok, text, rel, same = gs_judge_grad(mode, got[g][k], want, None if ref["gap"] is None else ref["gap"][g][k], loose)
+            lines.append(f"grad {g}/{k} (margin {ref['margin'][g]:.1e}): {text}")
+            if loose is None:
+                worst = max(worst, rel)
+            if k != "log_std":
+                n_same, n_all = n_same + same * want.size, n_all + want.size
+            if not ok:
+                bad.append(lines[-1])
+    return bad, lines, loose_groups, worst, n_same / n_all
+
+
+def gs_adam_coef(step, lr, lr_actor_base, t_max):
+    """make_adam_coef (csrc/step_math.h) for the step whose 1-based count is ``step``: the coefficients are
+    formed in double and rounded to float; returned as the floats' values in float64.  neg_step: q, v, actor
+    (the actor's lr on the cosine schedule after step - 1 scheduler steps)."""
+    b1, b2, eps = GS_ADAM["beta1"], GS_ADAM["beta2"], GS_ADAM["eps"]
+    bc1, bc2 = 1.0 - b1 ** step, 1.0 - b2 ** step
+    lr_a = lr_actor_base * (1.0 + np.cos(np.pi * (step - 1) / t_max)) * 0.5
+    f = lambda x: float(np.float32(x))
+    return dict(one_m_b1=f(1.0 - b1), b2=f(b2), one_m_b2=f(1.0 - b2), bc2_sqrt=f(np.sqrt(bc2)), eps=f(eps),
+                neg_step={"q": f(-(lr / bc1)), "v": f(-(lr / bc1)), "actor": f(-(lr_a / bc1))})
+
+
+def ulp32(x):
+    """Spacing of float32 at |x| (normal numbers; the smallest normal's below)."""
+    _, e = np.frexp(np.maximum(np.abs(np.asarray(x, dtype=np.float64)), 2.0 ** -126))
+    return np.ldexp(1.0, e - 1 - 23)
+
+
+def gs_judge_update(coef, group, p0, m0, v0, g, p1, m1, v1, lr, t0=None, t1=None, tau=None):
+    """Adam and Polyak of one tensor from the GPU's own numbers, in float64 (adam_apply / polyak of
+    csrc/step_math.h):  m = m0 + (g - m0)(1 - b1);  v = b2 v0 + (1 - b2) g g;  p = p0 - step m / (sqrt(v) /
+    sqrt(bc2) + eps);  t = t0 + tau (p1 - t0) on the GPU's new p.  The two lerps are ATen's form, one fused
+    multiply-add over the fp32-ROUNDED difference: the reference takes that difference as the fp32 number it is
+    and does the rest in float64, so what is left to the kernel is the last rounding -- also where the two terms
+    cancel (m0 = -g / 9, t0 = -tau p1: a few entries of a million), where half an ulp of the difference is many
+    ulps of the result.  Bounds (derived, not fitted):
+      moments    1e-6 relative, floor 1e-37 (g g underflows).
+      parameter  1 ulp32(p) + 1e-5 lr: adam_apply is about six fp32 operations on float-rounded coefficients,
+                 in bf16 mode with the hardware's 1-ulp sqrt / rcp (3e-7 of the step): ~1e-6 of an update <= lr.
+      target     2 ulp32(t).
+    Returns (failures, {"m": largest error / tolerance unit, ...}: moments in units of 1e-6 relative, the
+    parameter's distance from p_ref in ulp32 and what of it exceeds one ulp32 in units of lr, the target in ulp32)."""
+    f = lambda x: np.asarray(x, dtype=np.float64)
+    p0, m0, v0, g, p1, m1, v1 = map(f, (p0, m0, v0, g, p1, m1, v1))
+    f32_diff = lambda a, b: (a.astype(np.float32) - b.astype(np.float32)).astype(np.float64)  # (a, b hold fp32 values)
+    m = m0 + f32_diff(g, m0) * coef["one_m_b1"]
+    v = coef["b2"] * v0 + (coef["one_m_b2"] * g) * g
+    p = p0 + coef["neg_step"][group] * (m / (np.sqrt(v) / coef["bc2_sqrt"] + coef["eps"]))
+    bad, fig = [], {}
+    fig["m"] = float((np.maximum(np.abs(m1 - m) - 1e-37, 0) / np.maximum(np.abs(m), 1e-300)).max() / 1e-6)
+    fig["v"] = float((np.maximum(np.abs(v1 - v) - 1e-37, 0) / np.maximum(v, 1e-300)).max() / 1e-6)
+    dp = np.abs(p1 - p)
+    fig["p_ulp"], fig["p_lr"] = float((dp / ulp32(p)).max()), float(np.maximum(dp - ulp32(p), 0).max() / lr)
+    if fig["m"] > 1.0:
+        bad.append(f"exp_avg off by {fig['m']:.3g} x 1e-6")
+    if fig["v"] > 1.0:
+        bad.append(f"exp_avg_sq off by {fig['v']:.3g} x 1e-6")
+    if np.any(dp > ulp32(p) + 1e-5 * lr):
+        bad.append(f"parameter off by {fig['p_ulp']:.3g} ulp32 / {fig['p_lr']:.3g} lr at the worst entry")
+    if t0 is not None:
+        t = f(t0) + tau * f32_diff(p1, f(t0))
+        fig["t_ulp"] = float((np.abs(f(t1) - t) / ulp32(t)).max())
+        if fig["t_ulp"] > 2.0:
+            bad.append(f"target off by {fig['t_ulp']:.3g} ulp32")
+    return bad, fig
+
+
+def gs_trajectory_margins(case, mode, seed=None):
+    """The oracle's OWN two steps (lr = GS_LR) on a case: [{group: margin} per step]."""
+    hyper, nets, data, idx = gs_inputs(case, seed)
+    o = gs_oracle_at(hyper, nets + (nets[0],), mode, 0)
+    out = []
+    for t in range(GS_STEPS):
+        o.train(orc.gather_batch(data, idx[t]), gs_keep_masks(hyper, t))
+        out.append(dict(o.last_margin))
+    return out
+
+
+GS_SEED = 7  # the trainers' Philox key (dropout masks)
+
+
+def gs_keep_masks(hyper, t):
+    """The Philox keep masks of step t (0-based) as the device draws them, or None without dropout."""
+    if not hyper["dropout"]:
+        return None
+    from oracle import philox
+    B = hyper["batch"]  # (a Philox block covers 4 rows of one unit whatever the batch: whole blocks, then the real rows)
+    return [philox.dropout_keep(GS_SEED, t, philox.dropout_stream(l), _round_up(B, 4), hyper["hidden"], hyper["dropout"])[:B]
+            for l in range(hyper["n_hidden"])]
+
+
+class gs_chunked_sums:
+    """Inside the block the oracle forms every matrix product in fp32 over ``chunk`` terms at a time, the partial
+    products added in order: the shape of an MFMA accumulation chain -- a third correct restatement of the step."""
+
+    def __init__(self, chunk):
+        self.chunk = chunk
+
+    def _mm(self, a, b, acc):
+        (M, K), N, c = a.shape, b.shape[1], self.chunk
+        nk = -(-K // c)
+        a3, b3 = np.zeros((M, nk * c), np.float32), np.zeros((nk * c, N), np.float32)  # (zero padding adds exact zeros)
+        a3[:, :K], b3[:K] = a, b
+        parts = a3.reshape(M, nk, c).transpose(1, 0, 2) @ b3.reshape(nk, c, N)  # [nk, M, N]: the chunks' products
+        out = parts[0]
+        for k in range(1, nk):
+            out = out + parts[k]
+        return out
+
+    def __enter__(self):
+        self.real, orc._mm = orc._mm, self._mm
+
+    def __exit__(self, *exc):
+        orc._mm = self.real
+
+
+def gs_restatements_disagree(case, seed=None, chunks=(8, 32)):
+    """In bf16 a rounding tie that falls the other way under another summation order moves a pre-activation by an
+    ulp of ITS size, which in a deep, wide net flips relu' of units far further from zero than GS_MARGIN.  So the
+    reference is asked to agree with itself first: along the oracle's own two steps, the oracle with chunked fp32
+    sums (gs_chunked_sums; no GPU in it) is judged against the reference exactly as the GPU is.  Returns the
+    tensors beyond the bounds -- a seed where correct restatements already differ by more cannot tell a wrong
+    kernel from a right one."""
+    hyper, nets, data, idx = gs_inputs(case, seed)
+    o, bad = gs_oracle_at(hyper, nets + (nets[0],), "bf16", 0), []
+    for t in range(GS_STEPS):
+        state = tuple({k: v.copy() for k, v in d.items()} for d in (o.qf, o.vf, o.actor, o.q_target))
+        batch, keeps = orc.gather_batch(data, idx[t]), gs_keep_masks(hyper, t)
+        ref = gs_reference_step(hyper, state, "bf16", batch, t, keeps)
+        for chunk in chunks:
+            third = gs_oracle_at(hyper, state, "bf16", t)
+            with gs_chunked_sums(chunk):
+                third.train(batch, keeps)
+            bad += [f"step {t + 1}, sums of {chunk}: {b}" for b in gs_judge_grads("bf16", third.last_grads, ref, hyper["batch"])[0]]
+        o.train(batch, keeps)
+    return bad
+
+
+def gs_pick_seed(case, tries=64):
+    """The first numpy seed at which the reference ALONE (a) keeps every net 2 x GS_MARGIN from a kink at both
+    steps in both modes (twice the threshold: the GPU's parameters after step 1 differ from the oracle's by
+    rounding) and (b) agrees with its own restatements in bf16 (gs_restatements_disagree).  GS_CASES records what
+    this returns; cases at B >= 1024 cannot avoid a kink and keep seed 0."""
+    if GS_CASES[case][4] >= 1024:
+        return 0
+    for seed in range(tries):
+        if all(min(m.values()) >= 2 * GS_MARGIN for mode in ("fp32", "bf16") for m in gs_trajectory_margins(case, mode, seed)) \
+                and not gs_restatements_disagree(case, seed):
+            return seed
+    raise AssertionError(f"{case}: no seed below {tries} keeps the reference away from the kinks")
 
 
 # ---- include/iqlhip.h as data: what tests/test_abi_host.py compares the ctypes binding with ----

@@ -26,11 +26,9 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import iql_oracle as orc
 from tests import helpers
 
 pytestmark = pytest.mark.gpu
-TOL = 2e-5      # the project's rtol = atol for fp32 forwards of up to four Linear layers, width <= 256
 N_ROWS = 100    # six full 16-row slabs and one of four rows
 B = 16          # the smallest batch a trainer takes: a forward does not depend on it
 MODES = ("fp32", "bf16")
@@ -75,49 +73,11 @@ def _forward_all(tr, ts, ta):
 
 
 def _reference(gh, tr, mode, s, a):
-    """which -> (reference [n, width] in fp64, |second CPU forward - reference| per element), on the
-    trainer's CURRENT parameters (the modules' and q_target's state_dicts)."""
-    qf, vf, actor, qt = (gh.module_params(m) for m in (tr.qf, tr.vf, tr.actor, tr.q_target))
-    sa = np.concatenate([s, a], axis=1)
-    out = {}
-    if mode == "fp32":
-        def pair(params, prefix, x, out_act):
-            ws, bs = helpers.net_layers(params, prefix)
-            want = helpers.mlp_forward_ref(ws, bs, x, 0, out_act)
-            return want, np.abs(helpers.mlp_forward_ref(ws, bs, x, 0, out_act, dtype=np.float32).astype(np.float64) - want)
-        for which, q in (("q", qf), ("q_target", qt)):
-            cols = [pair(q, f"q{e + 1}.net.", sa, 0) for e in range(orc.n_critics(q))]
-            out[which] = tuple(np.concatenate(c, axis=1) for c in zip(*cols))
-        out["v"] = pair(vf, "v.net.", s, 0)
-        out["actor"] = pair(actor, "net.net.", s, 1)
-        return out
-    for which, q in (("q", qf), ("q_target", qt)):
-        want = np.stack(orc.critics_all(q, s, a, "bf16")[0], axis=1).astype(np.float64)
-        other = np.concatenate([helpers.mlp_forward_bf16_f64(sa, q, f"q{e + 1}.net.") for e in range(orc.n_critics(q))], axis=1)
-        out[which] = (want, np.abs(other - want))
-    want = orc.value_forward(vf, s, "bf16")[0][:, None].astype(np.float64)
-    out["v"] = (want, np.abs(helpers.mlp_forward_bf16_f64(s, vf, "v.net.") - want))
-    want = orc.policy_forward(actor, s, "bf16")[0].astype(np.float64)
-    out["actor"] = (want, np.abs(helpers.mlp_forward_bf16_f64(s, actor, "net.net.", "tanh") - want))
-    return out
+    """helpers.forward_reference on the trainer's CURRENT parameters (the modules' and q_target's state_dicts)."""
+    return helpers.forward_reference(tuple(gh.module_params(m) for m in (tr.qf, tr.vf, tr.actor, tr.q_target)), mode, s, a)
 
 
-def _judge(mode, got, want, gap, n_lin, width):
-    """(within the bounds of the module docstring?, the figures as text)."""
-    assert got.shape == want.shape and got.dtype == np.float32
-    err = np.abs(got.astype(np.float64) - want)
-    if mode == "fp32":
-        if n_lin <= 4 and width <= 256:
-            bound, lim = f"rtol = atol = {TOL:.0e}", TOL + TOL * np.abs(want)
-        else:
-            atol = max(4 * float(gap.max()), TOL)
-            bound, lim = f"atol {atol:.2e}", atol
-        return bool(np.all(err <= lim)), f"max |err| {err.max():.3e} ({bound}; fp32 numpy vs fp64: gap {gap.max():.3e})"
-    max_b = max(4 * float(gap.max()), 2 * float(helpers.bf16_ulp(np.abs(want).max())))
-    med_b = max(4 * float(np.median(gap)), 0.25 * float(helpers.bf16_ulp(np.median(np.abs(want)))))
-    ok = err.max() <= max_b and np.median(err) <= med_b
-    return bool(ok), (f"max |err| {err.max():.3e} (bound {max_b:.3e}), median {np.median(err):.3e} (bound {med_b:.3e}), "
-                      f"bit-identical {np.mean(err == 0):.3f}; the CPU pair: max gap {gap.max():.3e}, median {np.median(gap):.3e}")
+_judge = helpers.forward_judge  # (the bounds of the module docstring)
 
 
 def _check(mode, got, ref, n_lin, width, label, rows=None):
