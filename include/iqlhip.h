@@ -748,6 +748,60 @@ int iqlhip_trainer_set_timing(iqlhip_trainer *t, int32_t enable);
  * the cost of an empty event pair (measured in the same pass) subtracted.    */
 int iqlhip_trainer_get_timing(iqlhip_trainer *t, double avg_ms[3], int64_t *n_launches);
 
+/* ------------------------------------------------------------------------ */
+/* Any-percent behaviour cloning (algorithms/minari/any_percent_bc.py,        */
+/* "bcref"; csrc/bc_step.hip): ONE network, Actor [S,256] ReLU [256,256] ReLU  */
+/* [256,A] Tanh times max_action (bcref:195-209), F.mse_loss(pi, action)       */
+/* (bcref:235-236), plain Adam (bcref:330).  Two launches per step.            */
+/* Envelope (anything else: IQLHIP_ERR_UNSUPPORTED before any HIP call):       */
+/* precision fp32, hidden_dim 256, n_hidden 0 or 2, state_dim <= 128,          */
+/* action_dim <= 32, no dropout, any batch_size >= 1 (padded to whole 16-row   */
+/* slabs inside, the mean counts the batch_size x action_dim real elements),   */
+/* 1..IQLHIP_MAX_GROUP members per group.                                      */
+/* Of iqlhip_trainer_config these fields are read: state_dim, action_dim,      */
+/* hidden_dim, n_hidden, batch_size, precision, dropout_p, lr_actor (the Adam  */
+/* lr, no schedule), adam_beta1, adam_beta2, adam_eps.  Of iqlhip_arenas:      */
+/* params, exp_avg, exp_avg_sq, grads (optional); target is ignored.           */
+/* ------------------------------------------------------------------------ */
+/* Element offsets of W_1[256][S] b_1[256] W_2[256][256] b_2[256] W_3[A][256] b_3[A] (torch
+ * [out][in] row-major, packed in this order) in the arenas, and their length.               */
+int iqlhip_bc_arena_layout(const iqlhip_trainer_config *cfg, int64_t offsets[6], int64_t *n_params);
+
+typedef struct iqlhip_bc iqlhip_bc;
+/* Borrows the arenas for the trainer's lifetime; allocates its workspace (the padded copy of
+ * every weight matrix that the forward reads, the transposed copies of W_2 and W_3 that the
+ * backward reads, the feature-major activation and dz planes) on the current device and builds
+ * the copies from the masters.  Synchronises the default stream once.                        */
+int iqlhip_bc_create(iqlhip_bc **out, const iqlhip_trainer_config *cfg, float max_action,
+                     const iqlhip_arenas *arenas);
+int iqlhip_bc_destroy(iqlhip_bc *t);
+/* Rebuild the copies from the masters (after the arenas were written from outside).          */
+int iqlhip_bc_sync_weights(iqlhip_bc *t, void *stream);
+/* Optimiser steps taken so far = Adam `step` (the bias corrections of the next step).        */
+int iqlhip_bc_set_step(iqlhip_bc *t, int64_t total_it);
+int iqlhip_bc_set_lr(iqlhip_bc *t, double lr);
+/* bcref:339-341 n_steps times: gather rows idx[i][0..batch) of the view (its s and a columns),
+ * forward, mse loss, backward, Adam.  idx: device int64[n_steps][batch], required (the index
+ * stream is the caller's: numpy's, custom_offline.NumpyIndexStream); values outside the view
+ * are clamped into it.  losses_out: NULL or device fp32[n_steps] (actor_loss of each step).
+ * Plain launches on `stream`; at most ~2048 steps are left queued ahead of the device.       */
+int iqlhip_bc_train_steps(iqlhip_bc *t, const iqlhip_replay_view *view, int64_t n_steps,
+                          const int64_t *idx, float *losses_out, void *stream);
+/* One of the copies the kernels read, device to device into dst (tests): which = 0 W_1 copy
+ * [256][S padded to 16], 1 W_2 copy [256][256], 2 W_3 copy [A padded to 16][256], 3 W_2
+ * transposed [256][256], 4 W_3 transposed [256][A padded to 16].  Padding is zero.           */
+int iqlhip_bc_copy_out(iqlhip_bc *t, int32_t which, float *dst, void *stream);
+
+/* K trainers of one shape (dims, batch size, max_action) stepped by the same two launches per
+ * step, the member as a launch coordinate.  Each member is bit-identical to stepping it alone.
+ * views[k], idx[k], losses_out[k] belong to member k (losses_out NULL as a whole or per member).
+ * Destroy the group before its members.                                                      */
+typedef struct iqlhip_bc_group iqlhip_bc_group;
+int iqlhip_bc_group_create(iqlhip_bc_group **out, iqlhip_bc *const *members, int32_t n);
+int iqlhip_bc_group_destroy(iqlhip_bc_group *g);
+int iqlhip_bc_group_train_steps(iqlhip_bc_group *g, const iqlhip_replay_view *views, int64_t n_steps,
+                                const int64_t *const *idx, float *const *losses_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -182,6 +182,18 @@ SYMBOLS = {
                                    C.POINTER(C.c_double)]),
     "iqlhip_trainer_set_timing": (C.c_int, [P, C.c_int32]),
     "iqlhip_trainer_get_timing": (C.c_int, [P, C.POINTER(C.c_double * 3), C.POINTER(C.c_int64)]),
+    # behaviour cloning (csrc/bc_step.hip)
+    "iqlhip_bc_arena_layout": (C.c_int, [C.POINTER(TrainerConfig), C.POINTER(C.c_int64 * 6), C.POINTER(C.c_int64)]),
+    "iqlhip_bc_create": (C.c_int, [C.POINTER(P), C.POINTER(TrainerConfig), C.c_float, C.POINTER(Arenas)]),
+    "iqlhip_bc_destroy": (C.c_int, [P]),
+    "iqlhip_bc_sync_weights": (C.c_int, [P, P]),
+    "iqlhip_bc_set_step": (C.c_int, [P, C.c_int64]),
+    "iqlhip_bc_set_lr": (C.c_int, [P, C.c_double]),
+    "iqlhip_bc_train_steps": (C.c_int, [P, C.POINTER(ReplayView), C.c_int64, P, P, P]),
+    "iqlhip_bc_copy_out": (C.c_int, [P, C.c_int32, P, P]),
+    "iqlhip_bc_group_create": (C.c_int, [C.POINTER(P), C.POINTER(P), C.c_int32]),
+    "iqlhip_bc_group_destroy": (C.c_int, [P]),
+    "iqlhip_bc_group_train_steps": (C.c_int, [P, C.POINTER(ReplayView), C.c_int64, C.POINTER(P), C.POINTER(P), P]),
 }
 
 _lib = None

@@ -22,6 +22,7 @@ from . import _resume
 
 Logger = Callable[[Dict[str, float], int], None]
 PerMember = Union[int, Sequence[int]]  # one value for all members of a loop, or one per member
+LOSS_NAMES = ("value_loss", "q_loss", "actor_loss")  # the columns of an IQL step's loss tensor
 
 
 def checkpoint_dirs(config, seeds: Sequence[int], resume: bool = False) -> List[Optional[str]]:
@@ -118,7 +119,8 @@ def run(trainers: Sequence, seeds: Sequence[int], make_group: Callable, total: P
         chunk: int, logger: Logger, ckpt_dirs: Sequence[Optional[str]], steps: Callable, evaluate: Callable,
         normalized: Union[None, Callable, Sequence[Optional[Callable]]] = None, best_by_return: bool = False, *,
         tagged: Optional[Callable] = None, resume: bool = False, sampler_state: Optional[Callable] = None,
-        set_sampler_state: Optional[Callable] = None) -> None:
+        set_sampler_state: Optional[Callable] = None, loss_names: Sequence[str] = LOSS_NAMES,
+        best_model: bool = True) -> None:
     """``total`` steps in chunks of at most ``chunk`` that end on the evaluation boundaries (every ``every``
     steps); the losses of a chunk come back to the host once, after the next chunk has been queued.
 
@@ -131,6 +133,11 @@ def run(trainers: Sequence, seeds: Sequence[int], make_group: Callable, total: P
     strictly greatest normalized score, or mean return without one or with ``best_by_return``.  One
     ``logger(record, step)`` call per step and member for the losses, then per evaluation record;
     ``tagged(record, k)`` makes the record the logger gets (default: ``tag(seeds)``).
+
+    ``loss_names``: the names of the columns of the loss tensors (default: the three losses of an IQL step;
+    ``minari_bc`` logs one ``actor_loss``).  ``best_model=False``: no best-model bookkeeping -- no
+    ``best_model.pt``, no ``best_score_so_far`` / ``best_step_so_far`` records (``minari_bc``: the reference's
+    loop there has none); the default leaves every record as it was.
 
     ``total`` / ``every`` may be one entry per member (a sweep's runs): all members start at step 0, a chunk
     ends on the next evaluation boundary or end of ANY active member, and a member whose ``total`` is reached
@@ -169,8 +176,8 @@ def run(trainers: Sequence, seeds: Sequence[int], make_group: Callable, total: P
         t0, members, losses = pending
         pending = None
         for k, arr in zip(members, (l.cpu().numpy() for l in losses)):
-            for i, (v, q, a) in enumerate(arr.tolist()):
-                logger(tagged({"value_loss": v, "q_loss": q, "actor_loss": a}, k), t0 + i)
+            for i, row in enumerate(arr.tolist()):
+                logger(tagged(dict(zip(loss_names, row)), k), t0 + i)
 
     t = 0
     finished = set()
@@ -219,12 +226,13 @@ def run(trainers: Sequence, seeds: Sequence[int], make_group: Callable, total: P
                     except ValueError:
                         pass
                 score = norm[k] if norm[k] is not None and not best_by_return else mean_eval
-                if score > best_score[k]:
+                if best_model and score > best_score[k]:
                     best_score[k], best_step[k] = score, step
                     if ckpt_dirs[k] is not None:
                         torch.save(trainer.state_dict(), os.path.join(ckpt_dirs[k], "best_model.pt"))
-                log({"best_score_so_far": best_score[k]})
-                log({"best_step_so_far": best_step[k]})
+                if best_model:
+                    log({"best_score_so_far": best_score[k]})
+                    log({"best_step_so_far": best_step[k]})
                 if ckpt_dirs[k] is not None:
                     torch.save(trainer.state_dict(), os.path.join(ckpt_dirs[k], f"checkpoint_{step}.pt"))
             left = [k for k in active if t < totals[k]]

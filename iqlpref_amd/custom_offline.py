@@ -551,11 +551,11 @@ def _reward_model_missing(where: str, config, advice: str, readers: str):
         f"{where}: iqlpref_amd has no Orbax checkpoint reader ({readers}); pass reward_model= {advice}{npz}")
 
 
-def _minari():
+def _minari(where: str = "custom_offline.train"):
     try:
         import minari
     except ImportError:
-        raise ImportError("custom_offline.train: dataset=None loads the Minari dataset config.dataset_id, but "
+        raise ImportError(f"{where}: dataset=None loads the Minari dataset config.dataset_id, but "
                           "minari is not installed; pass dataset= (iterable of episodes) and eval_env=") from None
     return minari
 
@@ -669,12 +669,13 @@ def train(config: TrainConfig, dataset=None, reward_model=None, eval_env=None, *
 
 def _train(config, dataset, eval_env, relabel: Optional[Callable], best_by_return: bool, *, logger=None,
            normalized_score=None, seeds_per_gpu: int = 1, sampler: str = "device", device=None, chunk: int = 2000,
-           model_file: Optional[str] = None, resume: bool = False):
+           model_file: Optional[str] = None, resume: bool = False, where: str = "custom_offline.train"):
     """``train()`` with the two things a flavour chooses: ``relabel(dataset)`` builds the transition dict
     (None: there is no reward model to build it with, which is reported after the other argument checks --
     unless ``model_file`` names a ``save_reward_params`` file, read once the dims and the device are known),
     and ``best_by_return`` keeps the best model by the mean evaluation return even when a normalized score is
-    logged (``custom_offline_br``)."""
+    logged (``custom_offline_br``).  A flavour without a reward model (``minari_iql``: the dataset's own
+    rewards) always hands in a ``relabel``.  ``where``: the caller's name in the messages."""
     if sampler not in ("host", "device"):
         raise ValueError("sampler must be 'host' or 'device'")
     K = int(seeds_per_gpu)
@@ -686,16 +687,16 @@ def _train(config, dataset, eval_env, relabel: Optional[Callable], best_by_retur
         device = D.local_device() or "cuda:0"
     minari = None
     if dataset is None:
-        minari = _minari()
+        minari = _minari(where)
         dataset = minari.load_dataset(config.dataset_id)
     if eval_env is None:
         if not hasattr(dataset, "recover_environment"):
-            raise ValueError("custom_offline.train: pass eval_env= (the dataset cannot recover_environment())")
+            raise ValueError(f"{where}: pass eval_env= (the dataset cannot recover_environment())")
         eval_env = dataset.recover_environment()
     if normalized_score is None:
         normalized_score = _minari_score(minari)
     if relabel is None and model_file is None:
-        _reward_model_missing("custom_offline.train", config,
+        _reward_model_missing(where, config,
                               "a QMLP or RewardPT holding its parameters (load_flax_params)", "load_QMLP / load_PT")
     state_dim = eval_env.observation_space.shape[0]
     action_dim = eval_env.action_space.shape[0]
