@@ -154,6 +154,35 @@ int iqlhip_prep_modify_reward(float *rewards, int64_t n, const double *trj_lens,
 int iqlhip_prep_state_stats(const float *obs, int64_t n, int32_t state_dim, double eps, float *mean,
                             float *std, void *stream);
 
+/* algorithms/offline/any_percent_bc.py:206-239 keep_best_trajectories, the part that walks every row.
+ * A trajectory ends at a row whose terminal is set or when it has max_len rows (iqlhip_prep_reward_range's
+ * rule); a trailing run that reaches neither is no trajectory.  For the complete trajectories, in dataset
+ * order: starts[t] = first row, lengths[t] = rows, returns[t] = the discounted return (device arrays of n
+ * entries each: max_len = 1 makes every row a trajectory; entries from the count on are not written);
+ * *n_traj (HOST) = their count.  returns[t] = sum over k of fp32(scale[k] * rewards[starts[t] + k]), products
+ * and sums each rounded to fp32, in row order from 0 -- what numpy 2 computes for
+ * `cur_return += reward_scale * reward` on float32 rewards when scale[k] = fp32(the Python float after k
+ * multiplications by the discount): bit-identical to the reference's returns.  scale: device fp32
+ * [min(max_len, n)] (a trajectory has at most n rows: entry k is read only by a trajectory with a row k).
+ * Synchronises `stream` (the count comes back).  Refused before any launch: a null pointer, n < 1,
+ * max_len < 1 (IQLHIP_ERR_INVALID), max_len > 2^20 (IQLHIP_ERR_UNSUPPORTED).  IQLHIP_ERR_INVALID when no
+ * trajectory is complete: nothing has been written to starts / lengths / returns / *n_traj then.           */
+int iqlhip_prep_trajectory_returns(const float *rewards, const uint8_t *terminals, int64_t n,
+                                   int32_t max_len, const float *scale, int64_t *starts, int64_t *lengths,
+                                   float *returns, int64_t *n_traj, void *stream);
+/* The same function's `dataset[k][order]` (:231-239) for one array: src [n][width] fp32; chosen [m] = numbers of
+ * trajectories (indices into starts / lengths of the call above, n_traj of them), in the order they are to
+ * lie in dst; dst_offsets [m] = the exclusive prefix sum of their lengths; dst [total_rows][width] with
+ * total_rows = the sum of their lengths.  Whole trajectories are copied, in 16-byte pieces where both ends lie
+ * on 16-byte boundaries and in floats otherwise; rows of no chosen trajectory are not read.  An entry of
+ * chosen outside [0, n_traj), or whose rows would not fit src or dst, is skipped on the device.  All arrays are
+ * device arrays; no host wait.  Refused before the launch (IQLHIP_ERR_INVALID): a null pointer, n < 1,
+ * width < 1, n_traj outside 1..n, m outside 1..n_traj, total_rows outside m..n.                              */
+int iqlhip_prep_gather_trajectories(const float *src, int64_t n, int32_t width, const int64_t *starts,
+                                    const int64_t *lengths, int64_t n_traj, const int64_t *chosen,
+                                    const int64_t *dst_offsets, int64_t m, int64_t total_rows, float *dst,
+                                    void *stream);
+
 /* ref:211-221 sample.  idx == NULL: indices are drawn on device,
  * idx[b] = philox4x32_10(key=seed, ctr=(b, step, stream 0)).x % n_rows
  * (oracle/philox.py); otherwise idx is a device int64[batch] that is used as

@@ -119,6 +119,9 @@ SYMBOLS = {
     "iqlhip_prep_modify_reward": (C.c_int, [P, C.c_int64, P, C.c_int32, C.c_int32, C.c_int32, C.c_double,
                                             C.c_double, C.c_int32, P]),
     "iqlhip_prep_state_stats": (C.c_int, [P, C.c_int64, C.c_int32, C.c_double, P, P, P]),
+    "iqlhip_prep_trajectory_returns": (C.c_int, [P, P, C.c_int64, C.c_int32, P, P, P, P, C.POINTER(C.c_int64), P]),
+    "iqlhip_prep_gather_trajectories": (C.c_int, [P, C.c_int64, C.c_int32, P, P, C.c_int64, P, P, C.c_int64,
+                                                  C.c_int64, P, P]),
     "iqlhip_replay_sample": (C.c_int, [C.POINTER(ReplayView), C.c_int32, P, C.c_uint64,
                                        C.c_uint64, P, P, P, P, P, P, P]),
     "iqlhip_arena_layout": (C.c_int, [C.POINTER(TrainerConfig), C.POINTER(C.c_int64 * N_TENSORS),

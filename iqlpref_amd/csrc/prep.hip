@@ -20,6 +20,7 @@
 namespace iqlhip {
 
 constexpr int CHUNK = 1024;  // elements per work-group of the scan (256 threads x 4)
+constexpr int TRAJ_MAX_LEN = 1 << 20;  // iqlhip_prep_trajectory_returns: the longest trajectory cut (rows of `scale`)
 
 // ---- flags -----------------------------------------------------------------
 // Counter reset AFTER transition i (ref:708-716 with a timeouts array):
@@ -199,6 +200,145 @@ __global__ void k_episode_walk(const float *__restrict__ rew, const uint8_t *__r
   }
 }
 
+// ---- any-percent selection (algorithms/offline/any_percent_bc.py:206-239 keep_best_trajectories) ----
+// A trajectory ends at a terminal or at M rows, the rule of k_episode_walk above: with `last` = index of the
+// last terminal before i, row i starts one iff (i - last - 1) % M == 0.  Its number in dataset order is the
+// count of starts before it (only the trailing run can be incomplete, and nothing follows that one): an
+// exclusive sum of the start flags -- per-chunk counts, one block that scans the chunk table, and the in-chunk
+// scan fused into the walk.  The walker of a start adds float32(scale[k] * r) in float32 in row order, each
+// product and each sum rounded on its own: numpy's `cur_return += reward_scale * reward` on float32 rewards.
+// c + fp32(s * r): what __fadd_rn(c, __fmul_rn(s, r)) says.  HIP defines those two as plain `+` and `*`, which
+// the compiler's default contraction fuses into one fma across the inlined calls; the pragma keeps the product's
+// own rounding (by hand: k_traj_walk's code has v_mul_f32 / v_add_f32 here and no fma).
+__device__ __forceinline__ float add_rounded_product(float c, float s, float r) {
+#pragma clang fp contract(off)
+  const float p = s * r;
+  return c + p;
+}
+
+__device__ __forceinline__ bool traj_start(const int64_t *last, int64_t i, int64_t M) {
+  return (i - last[i] - 1) % M == 0;
+}
+
+__global__ __launch_bounds__(256) void k_start_count(const int64_t *__restrict__ last, int64_t n, int64_t M,
+                                                     int64_t *__restrict__ chunk_starts) {
+  __shared__ int red[4];
+  const int64_t base = (int64_t)blockIdx.x * CHUNK + threadIdx.x * 4;
+  int c = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if (base + k < n && traj_start(last, base + k, M)) ++c;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) chunk_starts[blockIdx.x] = (int64_t)red[0] + red[1] + red[2] + red[3];
+}
+
+// one block: chunk_starts[b] := sum of the entries before b
+__global__ __launch_bounds__(256) void k_chunk_offsets(int64_t *__restrict__ chunk_starts, int nchunk) {
+  __shared__ long long wave_sum[4];
+  __shared__ long long carry_s;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (tid == 0) carry_s = 0;
+  __syncthreads();
+  for (int b0 = 0; b0 < nchunk; b0 += 256) {
+    const int b = b0 + tid;
+    const long long v = b < nchunk ? chunk_starts[b] : 0;
+    long long inc = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const long long o = __shfl_up(inc, off);
+      if (lane >= off) inc += o;
+    }
+    if (lane == 63) wave_sum[wave] = inc;
+    __syncthreads();
+    long long before = carry_s;
+    for (int w = 0; w < wave; ++w) before += wave_sum[w];
+    if (b < nchunk) chunk_starts[b] = before + inc - v;
+    __syncthreads();
+    if (tid == 255) carry_s = before + inc;
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(256) void k_traj_walk(const float *__restrict__ rew, const uint8_t *__restrict__ term,
+                                                   int64_t n, int64_t M, const float *__restrict__ scale,
+                                                   const int64_t *__restrict__ last,
+                                                   const int64_t *__restrict__ chunk_off, int64_t *__restrict__ starts,
+                                                   int64_t *__restrict__ lengths, float *__restrict__ returns,
+                                                   int64_t *__restrict__ n_traj) {
+  __shared__ int wave_sum[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t base = (int64_t)blockIdx.x * CHUNK + tid * 4;
+  bool f[4];
+  int cnt = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    f[k] = base + k < n && traj_start(last, base + k, M);
+    cnt += f[k] ? 1 : 0;
+  }
+  int inc = cnt;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const int o = __shfl_up(inc, off);
+    if (lane >= off) inc += o;
+  }
+  if (lane == 63) wave_sum[wave] = inc;
+  __syncthreads();
+  int64_t rank = chunk_off[blockIdx.x] + (inc - cnt);
+  for (int w = 0; w < wave; ++w) rank += wave_sum[w];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    if (!f[k]) continue;
+    const int64_t i = base + k;
+    float c = 0.f;
+    int64_t j = i, len = 0;
+    bool complete = false;
+    while (j < n) {
+      c = add_rounded_product(c, scale[len], rew[j]);
+      ++len;
+      const bool d = term[j] != 0;
+      ++j;
+      if (d || len == M) {
+        complete = true;
+        break;
+      }
+    }
+    if (complete) starts[rank] = i, lengths[rank] = len, returns[rank] = c;
+    if (j == n) *n_traj = complete ? rank + 1 : rank;  // the one walker that reaches the end of the data
+    ++rank;
+  }
+}
+
+// dst rows [dst_off[j], dst_off[j] + lengths[c]) := src rows [starts[c], ...), c = chosen[j]: one block column per
+// chosen trajectory, gridDim.y blocks share its len * width contiguous floats.  float4 pieces when both ends are
+// on 16-byte boundaries, floats otherwise and for the tail.  An entry that does not fit (c outside [0, n_traj), rows
+// outside src or dst) is skipped: nothing is read or written for it.
+__global__ __launch_bounds__(256) void k_gather_traj(const float *__restrict__ src, int64_t n, int width,
+                                                     const int64_t *__restrict__ starts,
+                                                     const int64_t *__restrict__ lengths, int64_t n_traj,
+                                                     const int64_t *__restrict__ chosen,
+                                                     const int64_t *__restrict__ dst_off, int64_t total_rows,
+                                                     float *__restrict__ dst) {
+  const int64_t c = chosen[blockIdx.x];
+  if (c < 0 || c >= n_traj) return;
+  const int64_t s = starts[c], len = lengths[c], o = dst_off[blockIdx.x];
+  if (s < 0 || len < 1 || len > n - s || o < 0 || len > total_rows - o) return;
+  const float *from = src + s * width;
+  float *to = dst + o * width;
+  const int64_t count = len * width;
+  const int64_t t0 = (int64_t)blockIdx.y * 256 + threadIdx.x, stride = (int64_t)gridDim.y * 256;
+  if ((((uintptr_t)from | (uintptr_t)to) & 15) == 0) {
+    const int64_t n4 = count >> 2;
+    for (int64_t q = t0; q < n4; q += stride)
+      reinterpret_cast<float4 *>(to)[q] = reinterpret_cast<const float4 *>(from)[q];
+    for (int64_t e = (n4 << 2) + t0; e < count; e += stride) to[e] = from[e];
+  } else {
+    for (int64_t e = t0; e < count; e += stride) to[e] = from[e];
+  }
+}
+
 // ---- reward normalisation (ref:363-401), numpy's in-place float32 semantics --------
 //   rewards op= python scalar  -> the scalar is rounded to float32, the op runs in float32
 //   rewards -= float64 array   -> the op runs in float64, the result is rounded to float32
@@ -364,6 +504,36 @@ static hipError_t launch_reward_range(const float *rew, const uint8_t *term, int
   return hipSuccess;
 }
 
+// *n_traj_host = number of complete trajectories; starts / lengths / returns are written for those only
+static hipError_t launch_trajectory_returns(const float *rew, const uint8_t *term, int64_t n, int64_t M,
+                                            const float *scale, int64_t *starts, int64_t *lengths, float *returns,
+                                            int64_t *n_traj_host, hipStream_t st) {
+  const int nchunk = (int)((n + CHUNK - 1) / CHUNK);
+  int64_t *last = nullptr, *table = nullptr;  // table: [nchunk] start counts -> offsets, [nchunk] = the count
+  hipError_t e = hipMallocAsync((void **)&last, sizeof(int64_t) * n, st);
+  if (e != hipSuccess) return e;
+  e = hipMallocAsync((void **)&table, sizeof(int64_t) * ((size_t)nchunk + 1), st);
+  if (e != hipSuccess) {
+    (void)hipFreeAsync(last, st);
+    return e;
+  }
+  e = last_flag_scan<1>(term, nullptr, n, 0, last, st);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_start_count, dim3(nchunk), dim3(256), 0, st, last, n, M, table);
+    hipLaunchKernelGGL(k_chunk_offsets, dim3(1), dim3(256), 0, st, table, nchunk);
+    hipLaunchKernelGGL(k_traj_walk, dim3(nchunk), dim3(256), 0, st, rew, term, n, M, scale, last, table, starts,
+                       lengths, returns, table + nchunk);
+    e = hipGetLastError();
+  }
+  int64_t h = 0;
+  if (e == hipSuccess) e = hipMemcpyAsync(&h, table + nchunk, sizeof(h), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  (void)hipFreeAsync(last, st);
+  (void)hipFreeAsync(table, st);
+  if (e == hipSuccess) *n_traj_host = h;
+  return e;
+}
+
 static hipError_t launch_state_stats(const float *x, int64_t n, int S, double eps, float *mean_f, float *std_f,
                                      hipStream_t st) {
   const int nblk = (int)((n + STAT_ROWS - 1) / STAT_ROWS);
@@ -449,6 +619,40 @@ extern "C" int iqlhip_replay_pack_normalized(float *rows, int32_t row_stride, in
   if (grid > 256 * 8) grid = 256 * 8;
   hipLaunchKernelGGL(k_pack_norm, dim3(grid), dim3(256), 0, (hipStream_t)stream, rows, row_stride, S, A, first_row, n,
                      obs, act, rew, next_obs, done, mean, std);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+extern "C" int iqlhip_prep_trajectory_returns(const float *rewards, const uint8_t *terminals, int64_t n,
+                                              int32_t max_len, const float *scale, int64_t *starts,
+                                              int64_t *lengths, float *returns, int64_t *n_traj, void *stream) {
+  if (!rewards || !terminals || !scale || !starts || !lengths || !returns || !n_traj)
+    return fail(IQLHIP_ERR_INVALID, "null pointer");
+  if (n < 1 || max_len < 1) return fail(IQLHIP_ERR_INVALID, "n and max_len must be >= 1");
+  if (max_len > TRAJ_MAX_LEN)
+    return fail(IQLHIP_ERR_UNSUPPORTED, "max_len %d is beyond %d", max_len, TRAJ_MAX_LEN);
+  int64_t count = 0;
+  HIP_TRY(launch_trajectory_returns(rewards, terminals, n, max_len, scale, starts, lengths, returns, &count,
+                                    (hipStream_t)stream));
+  if (count == 0) return fail(IQLHIP_ERR_INVALID, "dataset holds no complete trajectory");
+  *n_traj = count;
+  return 0;
+}
+
+extern "C" int iqlhip_prep_gather_trajectories(const float *src, int64_t n, int32_t width, const int64_t *starts,
+                                               const int64_t *lengths, int64_t n_traj, const int64_t *chosen,
+                                               const int64_t *dst_offsets, int64_t m, int64_t total_rows, float *dst,
+                                               void *stream) {
+  if (!src || !starts || !lengths || !chosen || !dst_offsets || !dst) return fail(IQLHIP_ERR_INVALID, "null pointer");
+  if (n < 1 || width < 1 || n_traj < 1 || n_traj > n)
+    return fail(IQLHIP_ERR_INVALID, "n >= 1, width >= 1, 1 <= n_traj <= n");
+  if (m < 1 || m > n_traj || m > 0x7fffffff || total_rows < m || total_rows > n)
+    return fail(IQLHIP_ERR_INVALID, "1 <= m <= n_traj, m <= total_rows <= n");
+  // blocks per trajectory: about 4096 floats each at the mean trajectory length, 1 .. 16
+  int64_t split = (total_rows / m) * width / 4096;
+  split = split < 1 ? 1 : (split > 16 ? 16 : split);
+  hipLaunchKernelGGL(k_gather_traj, dim3((unsigned)m, (unsigned)split), dim3(256), 0, (hipStream_t)stream, src, n,
+                     (int)width, starts, lengths, n_traj, chosen, dst_offsets, total_rows, dst);
   HIP_TRY(hipGetLastError());
   return 0;
 }
