@@ -634,7 +634,12 @@ static int tuned_create(iqlhip_trainer *t, const StepShape &sh, const Layout &L)
   {
     std::vector<UpdItem> per_xcd[8];
     deal_items(u, 0, 1, per_xcd);
-    items = flatten_table(per_xcd, 0, nullptr, (size_t)(B + 15) / 16);
+    // A lone trainer with dropout: its idle slots also draw the next step's masks (draw_keep_plane), B H / 2
+    // Philox calls that are pure multiplier time -- on 16 slots at B = H = 256 they were the launch's longest
+    // work-groups (k_update 5.6 -> 7.2 us traced).  32 slots keep a TwinQ table (224 tiles) on one work-group
+    // per CU.  Group tables stay as they are: the chip is full there and the draws are throughput.
+    const size_t rows16 = (size_t)(B + 15) / 16;
+    items = flatten_table(per_xcd, 0, nullptr, D.has_dropout && rows16 < 32 ? 32 : rows16);
   }
   // ---- workspace: the one list of its blocks, run once to measure and once to place ----
   auto blocks = [&](WorkspacePlan p) {
@@ -662,6 +667,8 @@ static int tuned_create(iqlhip_trainer *t, const StepShape &sh, const Layout &L)
     D.lossp = p.take<float>((size_t)NT * (B / 16));
     D.lsp = p.take<float>((size_t)(B / 16) * A);
     D.ls_snap = p.take<float>((size_t)A);
+    // one plane: its only reader is k_forward, its writers (k_stage, k_update's idle slots) run between two forwards
+    D.keepb = D.has_dropout ? p.take<uint8_t>((size_t)2 * (B / 4) * H) : nullptr;
     t->batch_rows = p.take<float>((size_t)B * stride);
     D.stage_rows = p.take<float>((size_t)B * stride);
     u->own.args = p.take<DevArgs>(1);

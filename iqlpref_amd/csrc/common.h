@@ -207,6 +207,24 @@ __device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint3
   }
   return Philox4{c0, c1, c2, c3};
 }
+// The same function with each round's two 32 x 32 -> 64-bit products written as such: one v_mad_u64_u32 per
+// product where the form above compiles to a v_mul_hi_u32 and a v_mul_lo_u32 (all quarter rate): half the
+// multiplier passes, for callers whose cost IS the multiplies (the dropout mask plane, iql_step.hip).  The
+// other callers keep the form their kernels were tuned with.
+__device__ __forceinline__ Philox4 philox4x32_10_wide(uint32_t c0, uint32_t c1, uint32_t c2,
+                                                      uint32_t c3, uint32_t k0, uint32_t k1) {
+#pragma unroll
+  for (int i = 0; i < 10; ++i) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+    c0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
+    c1 = (uint32_t)p1;
+    c2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+    c3 = (uint32_t)p0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  return Philox4{c0, c1, c2, c3};
+}
 constexpr uint32_t STREAM_INDEX = 0, STREAM_DROPOUT1 = 1, STREAM_DROPOUT2 = 2, STREAM_MLP_DROPOUT = 3;
 
 __device__ __forceinline__ int64_t philox_index(uint64_t seed, uint64_t step, uint32_t row,

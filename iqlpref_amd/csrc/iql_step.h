@@ -78,6 +78,9 @@ struct TrainerDesc {
   float *lossp;   // [ntrain][nslab]   per-slab loss partial sums
   float *lsp;     // [nslab][A]   per-slab d(loss)/d(std) partial sums
   float *ls_snap; // [A] log_std as of the start of the step (written by k_forward's spare block)
+  uint8_t *keepb; // [2][B/4][H] the dropout masks of the step about to run, drawn with its batch (k_stage /
+                  // k_update): bit i of byte (layer, rb, unit) = keep row 4 rb + i of that hidden unit.  Null
+                  // without dropout.
   // arenas
   float *params, *exp_avg, *exp_avg_sq, *target, *grads;
   int64_t off_log_std;

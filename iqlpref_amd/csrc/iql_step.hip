@@ -5,14 +5,16 @@
 //               k_update, else gathered from the packed replay rows), 3 Linear layers on
 //               MFMA (activations staged in LDS, weights streamed from L2 straight into B
 //               fragments), hidden activations of the trained nets stored feature-major for
-//               the backward GEMMs.  A spare job writes the step's Adam coefficients.
+//               the backward GEMMs.  A spare job writes the step's Adam coefficients.  The actor's
+//               dropout masks are bytes of a plane drawn with the batch (draw_keep_plane), loaded
+//               with the biases; trainers without dropout run instantiations with no mask code.
 //   k_backward  (E+2) trained nets x B/16 slabs x 2 halves of W2^T: loss terms (expectile,
 //               TD, AWR), d(out), dZ2 (VALU outer product), dZ1 (MFMA), all stored
 //               feature-major; per-slab loss partial sums.
 //   k_update    weight-gradient GEMMs (K = batch) fused with Adam, the compute-precision
 //               weight copies and the Polyak target update: 64x32 tiles for the H-wide
 //               layers, 16-row strips with a flat state stream for layer 1; idle slots of
-//               the XCD-major item table prefetch the next step's batch.
+//               the XCD-major item table prefetch the next step's batch and draw its dropout masks.
 //
 // Every kernel is a latency chain (one 16-row slab / one tile per work-group, 100-260
 // work-groups on 256 CUs).  Rules the code follows, each measured:
@@ -217,6 +219,23 @@ __device__ __forceinline__ void dropout_keep4(const TrainerDesc &D, const DevArg
     keep[1] = ph.y >= D.drop_thr;
     keep[2] = ph.z >= D.drop_thr;
     keep[3] = ph.w >= D.drop_thr;
+  }
+}
+
+// The same four keep flags in k_forward / k_forward_tp: the bits of the byte `kb` that the kernel loaded
+// from the mask plane up front (D.keepb: drawn with the batch, draw_keep_plane), or, in a call with
+// injected masks (inj = A.drop_keep, [n][2][B][H] bytes), four guarded loads as before -- the only path
+// on which a forward reads the step counter.
+__device__ __forceinline__ void keep4_fwd(const TrainerDesc &D, const DevArgs &A, const uint8_t *inj,
+                                          const DevCtr *Cp, uint32_t kb, int layer, int rowblk, int col,
+                                          bool keep[4]) {
+  if (inj) {
+    const uint8_t *m = inj + (((size_t)(Cp->ctr[0] - A.base_step) * 2 + layer) * D.B + (size_t)rowblk * 4) * D.H + col;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) keep[i] = ldg(m + (size_t)i * D.H) != 0;
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) keep[i] = ((kb >> i) & 1u) != 0;
   }
 }
 
@@ -436,12 +455,36 @@ __device__ __forceinline__ void stage_rows16(const TrainerDesc &D, const DevArgs
   }
 }
 
+// The actor's dropout masks of step `step` go wherever its batch is staged, into the plane D.keepb
+// [2][B/4][H]: they depend on (seed, step, layer, row block, unit) and on no data, so they are drawn once,
+// off the forward's latency chain, which then reads a byte where it ran ten Philox rounds (and layer 1's
+// mask once, not once per part work-group).  One Philox call = the keep bits of rows 4 rb .. 4 rb + 3 of
+// one unit = one byte; the 2 (B/4) H calls are split evenly over the `nparts` staging work-groups of
+// `nthr` threads.  Nothing is drawn for a call with injected masks (the forward reads those).
+__device__ __forceinline__ void draw_keep_plane(const TrainerDesc &D, const DevArgs &A, int64_t step, int part,
+                                                int nparts, int tid, int nthr) {
+  if (!D.has_dropout || A.drop_keep) return;
+  const int per_layer = (D.B >> 2) * D.H;
+  const uint32_t thr = D.drop_thr;
+  for (int e = part * nthr + tid; e < 2 * per_layer; e += nparts * nthr) {
+    const int layer = e >= per_layer ? 1 : 0;
+    const Philox4 ph = philox4x32_10_wide((uint32_t)(e - layer * per_layer), (uint32_t)step,
+                                          (uint32_t)((uint64_t)step >> 32),
+                                          layer == 0 ? STREAM_DROPOUT1 : STREAM_DROPOUT2,
+                                          (uint32_t)D.seed, (uint32_t)(D.seed >> 32));
+    const uint32_t bits = (ph.x >= thr ? 1u : 0u) | (ph.y >= thr ? 2u : 0u) | (ph.z >= thr ? 4u : 0u) |
+                          (ph.w >= thr ? 8u : 0u);
+    stg(D.keepb + e, (uint8_t)bits);
+  }
+}
+
 template <bool BF16>
 __global__ __launch_bounds__(256) void k_stage(const TrainerDesc *__restrict__ Dp,
                                                const DevArgs *__restrict__ Ap,
                                                const DevCtr *__restrict__ Cp) {
   Dp += blockIdx.y, Ap += blockIdx.y, Cp += blockIdx.y;
   stage_rows16<BF16>(*Dp, *Ap, Cp->ctr[0], blockIdx.x * 16, gridDim.x * 16, threadIdx.x);
+  draw_keep_plane(*Dp, *Ap, Cp->ctr[0], blockIdx.x, gridDim.x, threadIdx.x, 256);
 }
 
 // A padded batch (batch_size no multiple of 16; api.hip, pad_inputs): n blocks of `rows` rows of w8 x 8 bytes
@@ -487,7 +530,7 @@ struct FCfg {
   static_assert(HQ == 64, "one 16-column tile per wave and part");
 };
 
-template <bool BF16, int H, int MT, int PW>
+template <bool BF16, int H, int MT, int PW, bool DROP>
 __global__ __launch_bounds__(256, 3) void k_forward(const TrainerDesc *__restrict__ Dp,
                                                  const DevArgs *__restrict__ Ap,
                                                  const DevCtr *__restrict__ Cp, const int nsl_,
@@ -536,7 +579,10 @@ __global__ __launch_bounds__(256, 3) void k_forward(const TrainerDesc *__restric
   const unsigned sstride = (unsigned)D.stage_stride;
   float *const g_outs = D.outs;
   void *const g_hT = D.hT;
-  const int64_t step = Cp->ctr[0];  // dropout masks only
+  // DROP = the trainer's has_dropout (the host picks): without it no mask code at all
+  const uint8_t *const keepb = DROP ? D.keepb : nullptr;
+  const uint8_t *const inj = DROP ? Ap->drop_keep : nullptr;  // injected masks (tests): read in the epilogues
+  if constexpr (DROP) pin_s(inj), pin_s(D.drop_scale);
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // scalar: wave-uniform branches stay scalar
@@ -579,6 +625,20 @@ __global__ __launch_bounds__(256, 3) void k_forward(const TrainerDesc *__restric
   float bias2[PW];
 #pragma unroll
   for (int j = 0; j < PW; ++j) bias2[j] = ldg(N.b2 + 16 * (tile2 + 4 * j) + r);
+  // the keep bytes of this lane's layer-1 and layer-2 tiles (D.keepb, draw_keep_plane), with the biases:
+  // clamped and unconditional, whatever the network -- a guarded load in an epilogue is a memory round trip
+  uint32_t kb1[MT][TPW] = {}, kb2[PW][MT] = {};
+  if constexpr (DROP) {
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+      const int rb_ = ((slab * ROWS + 16 * m) >> 2) + q;
+      const uint8_t *kr = keepb + (size_t)(rb_ < (B >> 2) ? rb_ : (B >> 2) - 1) * H + r;
+#pragma unroll
+      for (int jj = 0; jj < TPW; ++jj) kb1[m][jj] = ldg(kr + 16 * (wave * TPW + jj));
+#pragma unroll
+      for (int j = 0; j < PW; ++j) kb2[j][m] = ldg(kr + (size_t)(B >> 2) * H + 16 * (tile2 + 4 * j));
+    }
+  }
 #pragma unroll
   for (int jt = 0; jt < 2; ++jt)  // clamped (used for col < out_dim)
     bias3[jt] = ldg(N.b3 + (16 * jt + r < N.out_dim ? 16 * jt + r : N.out_dim - 1));
@@ -641,6 +701,19 @@ __global__ __launch_bounds__(256, 3) void k_forward(const TrainerDesc *__restric
       }
     }
   }
+  // (the keep bytes arrived with the biases, ahead of every weight fragment: four bits each, one register
+  // per layer from here on instead of one per tile)
+  uint32_t kp1 = 0, kp2 = 0;
+  if constexpr (DROP) {
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+#pragma unroll
+      for (int jj = 0; jj < TPW; ++jj) kp1 |= kb1[m][jj] << (4 * (m * TPW + jj));
+#pragma unroll
+      for (int j = 0; j < PW; ++j) kp2 |= kb2[j][m] << (4 * (j * MT + m));
+    }
+    asm volatile("" : "+v"(kp1), "+v"(kp2));  // (packed HERE: not one register per tile across the products)
+  }
   __syncthreads();
   STAMP(0, 2);
 
@@ -665,8 +738,8 @@ __global__ __launch_bounds__(256, 3) void k_forward(const TrainerDesc *__restric
     __builtin_amdgcn_sched_barrier(0);
     load_w2();
     __builtin_amdgcn_sched_barrier(0);
-    bool lean = false;
-    if constexpr (BF16) lean = !N.dropout;  // (wave-uniform) see relu_bias_bf16x4
+    // (wave-uniform; a constant without dropout) see relu_bias_bf16x4
+    const bool lean = BF16 && (!DROP || !N.dropout);
 #pragma unroll
     for (int jj = 0; jj < TPW; ++jj) {
       const int tile = wave * TPW + jj;
@@ -704,11 +777,13 @@ __global__ __launch_bounds__(256, 3) void k_forward(const TrainerDesc *__restric
         float v[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) v[i] = fmaxf(P::round(acc[m][jj][i] + bias), 0.f);
-        if (N.dropout) {
-          bool keep[4];
-          dropout_keep4(D, *Ap, step, 0, (row0 >> 2) + q, col, keep);
+        if constexpr (DROP) {
+          if (N.dropout) {
+            bool keep[4];
+            keep4_fwd(D, *Ap, inj, Cp, kp1 >> (4 * (m * TPW + jj)), 0, (row0 >> 2) + q, col, keep);
 #pragma unroll
-          for (int i = 0; i < 4; ++i) v[i] = keep[i] ? P::round(v[i] * D.drop_scale) : 0.f;
+            for (int i = 0; i < 4; ++i) v[i] = keep[i] ? P::round(v[i] * D.drop_scale) : 0.f;
+          }
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) h1[(16 * m + 4 * q + i) * HP + col] = P::from_f32(v[i]);
@@ -740,8 +815,7 @@ __global__ __launch_bounds__(256, 3) void k_forward(const TrainerDesc *__restric
     __builtin_amdgcn_sched_barrier(0);
     load_w3();
     __builtin_amdgcn_sched_barrier(0);
-    bool lean = false;
-    if constexpr (BF16) lean = !N.dropout;
+    const bool lean = BF16 && (!DROP || !N.dropout);
 #pragma unroll
     for (int j = 0; j < PW; ++j) {
       const int col = 16 * (tile2 + 4 * j) + r;
@@ -778,11 +852,13 @@ __global__ __launch_bounds__(256, 3) void k_forward(const TrainerDesc *__restric
         float v[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) v[i] = fmaxf(P::round(acc[j][m][i] + bias), 0.f);
-        if (N.dropout) {
-          bool keep[4];
-          dropout_keep4(D, *Ap, step, 1, (row0 >> 2) + q, col, keep);
+        if constexpr (DROP) {
+          if (N.dropout) {
+            bool keep[4];
+            keep4_fwd(D, *Ap, inj, Cp, kp2 >> (4 * (j * MT + m)), 1, (row0 >> 2) + q, col, keep);
 #pragma unroll
-          for (int i = 0; i < 4; ++i) v[i] = keep[i] ? P::round(v[i] * D.drop_scale) : 0.f;
+            for (int i = 0; i < 4; ++i) v[i] = keep[i] ? P::round(v[i] * D.drop_scale) : 0.f;
+          }
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) h2j[(16 * m + 4 * q + i) * HQP + 16 * wave + r] = P::from_f32(v[i]);
@@ -890,7 +966,9 @@ __global__ __launch_bounds__(512, 1) void k_forward_tp(const TrainerDesc *__rest
   const unsigned sstride = (unsigned)D.stage_stride;
   float *const g_outs = D.outs;
   void *const g_hT = D.hT;
-  const int64_t step = Cp->ctr[0];  // dropout masks only
+  const uint8_t *const keepb = DROP ? D.keepb : nullptr;
+  const uint8_t *const inj = DROP ? Ap->drop_keep : nullptr;  // injected masks (tests): read in the epilogues
+  if constexpr (DROP) pin_s(inj), pin_s(D.drop_scale);
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -929,6 +1007,20 @@ __global__ __launch_bounds__(512, 1) void k_forward_tp(const TrainerDesc *__rest
 #pragma unroll
   for (int jt = 0; jt < 2; ++jt)
     bias3[jt] = ldg(N.b3 + (16 * jt + r < N.out_dim ? 16 * jt + r : N.out_dim - 1));
+  // the keep bytes of this lane's tiles of both hidden layers (D.keepb, draw_keep_plane): unconditional,
+  // with the biases (B is a multiple of 64: every row block exists)
+  uint32_t kb1[MT][TPW] = {}, kb2[TPW][MT] = {};
+  if constexpr (DROP) {
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+      const uint8_t *kr = keepb + (size_t)(((slab * ROWS + 16 * m) >> 2) + q) * H + 16 * tile0 + r;
+#pragma unroll
+      for (int jj = 0; jj < TPW; ++jj) {
+        kb1[m][jj] = ldg(kr + 16 * jj);
+        kb2[jj][m] = ldg(kr + (size_t)(B >> 2) * H + 16 * jj);
+      }
+    }
+  }
   uint4 w1[C::NK1][TPW], w2[TPW][NK2], w3[NK3][2];
   {
     const T *W1w = reinterpret_cast<const T *>(N.w1c) + (size_t)tile0 * nk1 * 64 * P::EPV;
@@ -975,11 +1067,20 @@ __global__ __launch_bounds__(512, 1) void k_forward_tp(const TrainerDesc *__rest
       *reinterpret_cast<uint2 *>(xs + rr * K1P + c) = u;
     }
   }
+  uint32_t kp1 = 0, kp2 = 0;  // the keep bytes, four bits each: one register per layer
+  if constexpr (DROP) {
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+      for (int jj = 0; jj < TPW; ++jj)
+        kp1 |= kb1[m][jj] << (4 * (m * TPW + jj)), kp2 |= kb2[jj][m] << (4 * (jj * MT + m));
+    asm volatile("" : "+v"(kp1), "+v"(kp2));  // (packed HERE: not one register per tile across the products)
+  }
   __syncthreads();
   STAMP(0, 2);
 
   // DROP = false: the lean bf16 epilogues only (relu_bias_bf16x4); the instantiation with dropout
-  // carries the Philox masks.  The host picks by the trainer's has_dropout; a network without dropout
+  // applies the masks (kb1 / kb2).  The host picks by the trainer's has_dropout; a network without dropout
   // inside a DROP launch (every net but the actor) takes the general path with an all-ones mask.
   const bool store_h = N.train_slot >= 0;  // (wave-uniform) B is a multiple of 64: no row guards
   // ---- hidden layer 1 ----
@@ -1030,7 +1131,7 @@ __global__ __launch_bounds__(512, 1) void k_forward_tp(const TrainerDesc *__rest
         for (int i = 0; i < 4; ++i) v[i] = fmaxf(P::round(acc[m][jj][i] + bias), 0.f);
         if (N.dropout) {
           bool keep[4];
-          dropout_keep4(D, *Ap, step, 0, (row0 >> 2) + q, col, keep);
+          keep4_fwd(D, *Ap, inj, Cp, kp1 >> (4 * (m * TPW + jj)), 0, (row0 >> 2) + q, col, keep);
 #pragma unroll
           for (int i = 0; i < 4; ++i) v[i] = keep[i] ? P::round(v[i] * D.drop_scale) : 0.f;
         }
@@ -1091,7 +1192,7 @@ __global__ __launch_bounds__(512, 1) void k_forward_tp(const TrainerDesc *__rest
         for (int i = 0; i < 4; ++i) v[i] = fmaxf(P::round(acc[jj][m][i] + bias), 0.f);
         if (N.dropout) {
           bool keep[4];
-          dropout_keep4(D, *Ap, step, 1, (row0 >> 2) + q, col, keep);
+          keep4_fwd(D, *Ap, inj, Cp, kp2 >> (4 * (jj * MT + m)), 1, (row0 >> 2) + q, col, keep);
 #pragma unroll
           for (int i = 0; i < 4; ++i) v[i] = keep[i] ? P::round(v[i] * D.drop_scale) : 0.f;
         }
@@ -1980,8 +2081,17 @@ __device__ __forceinline__ void update_body(const TrainerDesc *__restrict__ Dp,
     // padding slot of the XCD-major item table: gather the NEXT step's replay rows while the
     // tiles work (random HBM rows + TLB misses leave the next k_forward's critical path); possible
     // iff that step's indices are known
-    if (D.prefetch && (A.idx_mode == 0 || (A.idx_mode == 1 && t1 - A.base_step < A.n_steps)))
+    if (D.prefetch && (A.idx_mode == 0 || (A.idx_mode == 1 && t1 - A.base_step < A.n_steps))) {
       stage_rows16<BF16>(D, A, t1, it.o0 * (UT / 16), it.i0 * (UT / 16), tid);
+      // ... and that step's dropout masks: on the slots that have no rows to gather, where there are any (a
+      // lone dropout trainer's table has 32 slots, api.hip).  The pen rows take the eight gathering slots
+      // 2.5 us; with a share of the draws behind them they ended with the launch's last tiles (stamps:
+      // 3.8 of 3.9 us) and k_update's traced time rose by 0.7 us.
+      const int ng = (D.B + UT / 16 - 1) / (UT / 16);  // slots with rows
+      const int nd = it.i0 > ng ? ng : 0;              // ... do not draw, if others can
+      if (it.o0 >= nd) draw_keep_plane(D, A, t1, it.o0 - nd, it.i0 - nd, tid, UT);
+    }
+    STAMP(2, 4);
     return;
   }
   const int L = it.layer;
@@ -2726,8 +2836,10 @@ hipError_t launch_forward(bool bf16, const TrainerDesc &D, const TrainerDesc *dD
   dispatch_h(bf16, D.H, [&](auto BF, auto HH) {
     auto go = [&](auto PW) {
       with_const<2, 1>(mt, [&](auto MT) {
-        hipLaunchKernelGGL((k_forward<CV(BF), CV(HH), CV(MT), CV(PW)>), dim3(grid, n_seeds), dim3(256), sm, st, dD, a,
-                           c, nsl, D.nfwd);
+        with_const<false, true>(D.has_dropout != 0, [&](auto DROP) {
+          hipLaunchKernelGGL((k_forward<CV(BF), CV(HH), CV(MT), CV(PW), CV(DROP)>), dim3(grid, n_seeds), dim3(256), sm,
+                             st, dD, a, c, nsl, D.nfwd);
+        });
       });
     };
     if constexpr (CV(HH) >= 128) {  // (two parts per work-group: never instantiated at H = 64)

@@ -20,14 +20,21 @@ lib = _lib.load()
 lib.iqlhip_trainer_set_debug.restype = C.c_int
 lib.iqlhip_trainer_set_debug.argtypes = [C.c_void_p, C.c_void_p]
 dev = "cuda:0"
-data = bench.synth_dataset(1, 200_000)
-buf = ia.ReplayBuffer(bench.S_DIM, bench.A_DIM, 200_000, dev)
-buf.load_d4rl_dataset(data)
+# STAMP_PEN=1: BASELINE configs[2] (pen shapes, actor dropout 0.1, 5,000 rows) instead of the antmaze shapes
+_kw = {}
+if os.environ.get("STAMP_PEN"):
+    _S, _A = bench.PEN["dims"]
+    buf = ia.ReplayBuffer(_S, _A, bench.PEN["n_rows"], dev)
+    buf.load_d4rl_dataset(bench.synth_dataset_dims(1, bench.PEN["n_rows"], _S, _A))
+    _kw = dict(dims=bench.PEN["dims"], dropout=bench.PEN["dropout"], hyper=bench.PEN["hyper"])
+else:
+    buf = ia.ReplayBuffer(bench.S_DIM, bench.A_DIM, 200_000, dev)
+    buf.load_d4rl_dataset(bench.synth_dataset(1, 200_000))
 prec = sys.argv[1] if len(sys.argv) > 1 and not sys.argv[1].startswith("-") else "bf16"
 # STAMP_E / STAMP_B: critics and batch of the stamped configuration (default: the headline's 2 / 256)
 _E, _B = int(os.environ.get("STAMP_E", "2")), int(os.environ.get("STAMP_B", str(bench.BATCH)))
 bench.BATCH = _B
-tr = bench.build_trainer(ia, torch, dev, 1, prec, n_critics=_E)
+tr = bench.build_trainer(ia, torch, dev, 1, prec, n_critics=_E, **_kw)
 # STAMP_GROUP=K: the stamped trainer is member 0 of a seed group of K (one launch sequence,
 # gridDim.y = K): the timeline of ITS work-groups inside the group launches
 _K = int(os.environ.get("STAMP_GROUP", "1"))
@@ -37,7 +44,7 @@ dbg_all = [dbg]
 if _K > 1:
     # the group copies its members' descriptors when it is created: attach the buffers first
     # (every member gets its own: STAMP_ALL=1 prints when each member's work-groups ran)
-    members = [tr] + [bench.build_trainer(ia, torch, dev, 1 + i, prec, n_critics=_E) for i in range(1, _K)]
+    members = [tr] + [bench.build_trainer(ia, torch, dev, 1 + i, prec, n_critics=_E, **_kw) for i in range(1, _K)]
     dbg_all = [dbg] + [torch.zeros_like(dbg) for _ in range(1, _K)]
     for t_, d_ in zip(members, dbg_all):
         t_._ensure_handle(bench.BATCH)
@@ -74,7 +81,7 @@ if _K > 1 and os.environ.get("STAMP_ALL"):
         for mi, w in enumerate(allw):
             ww = w[k][w[k][:, 0] > 0]
             dur = (ww.max(axis=1) - ww[:, 0]) * 10
-            busy = dur > 200  # (idle / padding work-groups write only their start stamp)
+            busy = dur > 200  # (padding work-groups with nothing to stage end at once)
             st = (ww[:, 0] - t0) * 10
             print(f"   member {mi}: {len(ww):4d} blocks  start {st.min():6.0f} .. {st.max():6.0f}  "
                   f"end max {(ww.max() - t0) * 10:6.0f}  duration med {np.median(dur[busy]):6.0f} max {dur.max():6.0f}")
