@@ -1,6 +1,7 @@
 """The chunked train / evaluate / checkpoint loop of the custom-offline flavours (``custom_offline.train`` and
 ``train_runs``, ``custom_offline_br``, ``custom_offline_bb``), once, and the setup every ``train()`` shares: the
-checkpoint directories, the default logger and the ``seed`` tag of K > 1 records.  The offline flavour (``train``,
+``sampler`` check, the seeds of a rank, the checkpoint directories, the default logger and the ``seed`` tag of
+K > 1 records.  The offline flavour (``train``,
 ``sweep.train_runs``) takes that setup from here and runs ``_window_loop``: window means instead of every step's
 losses, a metric exchange instead of a best model.
 
@@ -19,10 +20,26 @@ import numpy as np
 import torch
 
 from . import _resume
+from . import distributed as D
+from ._lib import MAX_GROUP
 
 Logger = Callable[[Dict[str, float], int], None]
 PerMember = Union[int, Sequence[int]]  # one value for all members of a loop, or one per member
 LOSS_NAMES = ("value_loss", "q_loss", "actor_loss")  # the columns of an IQL step's loss tensor
+
+
+def check_sampler(sampler: str) -> None:
+    if sampler not in ("host", "device"):
+        raise ValueError("sampler must be 'host' or 'device'")
+
+
+def group_seeds(train_seed: int, seeds_per_gpu: int) -> List[int]:
+    """The seeds of the K runs of this rank: ``rank_seed(train_seed, K) + k``.  ValueError for a K no group holds."""
+    K = int(seeds_per_gpu)
+    if not 1 <= K <= MAX_GROUP:
+        raise ValueError(f"seeds_per_gpu must be in 1..{MAX_GROUP}")
+    first = D.rank_seed(train_seed, K)
+    return [first + k for k in range(K)]
 
 
 def checkpoint_dirs(config, seeds: Sequence[int], resume: bool = False) -> List[Optional[str]]:

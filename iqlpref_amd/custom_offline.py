@@ -42,7 +42,7 @@ import ctypes as C
 import json
 import uuid
 import os
-from dataclasses import dataclass, fields
+from dataclasses import dataclass
 from typing import Any, Callable, Dict, Iterable, List, Mapping, Optional, Sequence, Tuple
 
 import numpy as np
@@ -55,7 +55,7 @@ from ._lib import check, ptr
 from .iql import DeterministicPolicy, GaussianPolicy, TwinQ, ValueFunction, compute_mean_std, normalize_states, set_seed
 from .iql import ImplicitQLearning as _OfflineIQL
 from .iql import ReplayBuffer as _OfflineReplayBuffer
-from .iql import _coerce, mlp_forward_f32
+from .iql import load_config_for, mlp_forward_f32
 from .multi import stepper
 from .relabel import RewardPT
 
@@ -98,22 +98,8 @@ class TrainConfig:
 
 
 def load_config(config_path: Optional[str] = None, **overrides) -> TrainConfig:
-    """The pyrallis ``--config_path`` behaviour (cref:597) with ``iql.load_config``'s rules: YAML keys =
-    field names, unknown keys raise, values are coerced to the field's declared type; ``overrides`` beat
-    the file."""
-    import yaml
-    raw: Dict[str, Any] = {}
-    if config_path:
-        with open(config_path) as f:
-            raw.update(yaml.safe_load(f) or {})
-    raw.update(overrides)
-    known = {f.name: f for f in fields(TrainConfig)}
-    kwargs = {}
-    for k, v in raw.items():
-        if k not in known:
-            raise ValueError(f"unknown custom_offline.TrainConfig field {k!r}")
-        kwargs[k] = _coerce(v, known[k].type)
-    return TrainConfig(**kwargs)
+    """The pyrallis ``--config_path`` behaviour (cref:597) with ``iql.load_config``'s rules."""
+    return load_config_for(TrainConfig, "custom_offline.TrainConfig", config_path, **overrides)
 
 
 # --------------------------------------------------------------------------- #
@@ -593,7 +579,7 @@ def _build_trainer(config, seed: int, state_dim: int, action_dim: int, limits: S
 def _prepare(config, qdataset: Dict[str, np.ndarray], eval_env, state_dim: int, action_dim: int, device):
     """cref:631-653: the relabelled transitions (rewritten in place) -> the device buffer and the evaluation
     environment that normalises its observations with the same mean / std."""
-    if config.normalize_reward:
+    if getattr(config, "normalize_reward", False):  # (``minari_bc``'s config has no such field)
         modify_reward(qdataset, config.dataset_id)
     if config.normalize_state:
         state_mean, state_std = compute_mean_std(qdataset["observations"], eps=1e-3)
@@ -606,6 +592,31 @@ def _prepare(config, qdataset: Dict[str, np.ndarray], eval_env, state_dim: int, 
     replay_buffer = ReplayBuffer(state_dim, action_dim, config.buffer_size, device)
     replay_buffer.load_dataset(qdataset)
     return replay_buffer, eval_env
+
+
+def _minari_setup(where: str, config, dataset, eval_env, normalized_score):
+    """The Minari arguments of a ``train()`` with their defaults filled in: ``(dataset, eval_env, normalized_score,
+    state_dim, action_dim, max_action)``.  ``where``: the caller's name in the messages."""
+    minari = None
+    if dataset is None:
+        minari = _minari(where)
+        dataset = minari.load_dataset(config.dataset_id)
+    if eval_env is None:
+        if not hasattr(dataset, "recover_environment"):
+            raise ValueError(f"{where}: pass eval_env= (the dataset cannot recover_environment())")
+        eval_env = dataset.recover_environment()
+    if normalized_score is None:
+        normalized_score = _minari_score(minari)
+    return (dataset, eval_env, normalized_score, eval_env.observation_space.shape[0], eval_env.action_space.shape[0],
+            float(eval_env.action_space.high[0]))
+
+
+def _index_sources(seeds: Sequence[int], sampler: str, device):
+    """Where the members' indices come from: ``(gens, stream)`` -- one ``np.random.RandomState(seed)`` per seed
+    (one seed alone: None, numpy's global generator, which ``set_seed`` has seeded) and the ``NumpyIndexStream``
+    that draws from them on the device (None: ``sampler="host"``)."""
+    gens = [None] if len(seeds) == 1 else [np.random.RandomState(s) for s in seeds]
+    return gens, NumpyIndexStream(device) if sampler == "device" else None
 
 
 def _steps(stream, trainers, bufs, gens, B: int):
@@ -676,45 +687,30 @@ def _train(config, dataset, eval_env, relabel: Optional[Callable], best_by_retur
     and ``best_by_return`` keeps the best model by the mean evaluation return even when a normalized score is
     logged (``custom_offline_br``).  A flavour without a reward model (``minari_iql``: the dataset's own
     rewards) always hands in a ``relabel``.  ``where``: the caller's name in the messages."""
-    if sampler not in ("host", "device"):
-        raise ValueError("sampler must be 'host' or 'device'")
-    K = int(seeds_per_gpu)
-    if not 1 <= K <= _lib.MAX_GROUP:
-        raise ValueError(f"seeds_per_gpu must be in 1..{_lib.MAX_GROUP}")
+    _offline_loop.check_sampler(sampler)
+    seeds = _offline_loop.group_seeds(config.train_seed, seeds_per_gpu)
+    K = len(seeds)
     if resume:
         _resume.check_config(config)
     if device is None:
         device = D.local_device() or "cuda:0"
-    minari = None
-    if dataset is None:
-        minari = _minari(where)
-        dataset = minari.load_dataset(config.dataset_id)
-    if eval_env is None:
-        if not hasattr(dataset, "recover_environment"):
-            raise ValueError(f"{where}: pass eval_env= (the dataset cannot recover_environment())")
-        eval_env = dataset.recover_environment()
-    if normalized_score is None:
-        normalized_score = _minari_score(minari)
+    dataset, eval_env, normalized_score, state_dim, action_dim, max_action = _minari_setup(
+        where, config, dataset, eval_env, normalized_score)
     if relabel is None and model_file is None:
         _reward_model_missing(where, config,
                               "a QMLP or RewardPT holding its parameters (load_flax_params)", "load_QMLP / load_PT")
-    state_dim = eval_env.observation_space.shape[0]
-    action_dim = eval_env.action_space.shape[0]
-    max_action = float(eval_env.action_space.high[0])
     if relabel is None:
         file_model = load_reward_model(model_file, state_dim, action_dim, device)
         relabel = lambda ds: qlearning_dataset(ds, file_model, config.query_length)
 
     replay_buffer, eval_env = _prepare(config, relabel(dataset), eval_env, state_dim, action_dim, device)
 
-    seeds = [D.rank_seed(config.train_seed, K) + k for k in range(K)]
     ckpt_dirs = _offline_loop.checkpoint_dirs(config, seeds, resume=resume)
 
     # ---- seeds and nets (cref:659-689) ----
     set_seed(seeds[0])  # np, random, torch, PYTHONHASHSEED
-    gens = [None] if K == 1 else [np.random.RandomState(s) for s in seeds]  # None: numpy's global generator
     trainers = [_build_trainer(config, s, state_dim, action_dim, (max_action,), device) for s in seeds]
-    stream = NumpyIndexStream(device) if sampler == "device" else None
+    gens, stream = _index_sources(seeds, sampler, device)
     if logger is None:
         logger = _offline_loop.default_logger(config, K)
 
@@ -863,8 +859,7 @@ def train_runs(configs: Sequence[TrainConfig], dataset=None, reward_models=None,
     from . import sweep as SW
     configs = list(configs)
     run_ids, mine = SW.start_runs(configs, runs_per_gpu, run_ids, resume)
-    if sampler not in ("host", "device"):
-        raise ValueError("sampler must be 'host' or 'device'")
+    _offline_loop.check_sampler(sampler)
     sources = _model_sources(configs, reward_models)
     if not mine:
         return []

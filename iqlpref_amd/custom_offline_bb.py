@@ -866,13 +866,7 @@ def bb_run_eval_fused_group(actors, num_episodes, r_model, move_stats, state_mea
 # --------------------------------------------------------------------------- #
 # train (bref:870-1027)
 # --------------------------------------------------------------------------- #
-def group_seeds(train_seed: int, seeds_per_gpu: int) -> List[int]:
-    """The seeds of the K runs of this rank: ``rank_seed(train_seed, K) + k``."""
-    K = int(seeds_per_gpu)
-    if not 1 <= K <= _lib.MAX_GROUP:
-        raise ValueError(f"seeds_per_gpu must be in 1..{_lib.MAX_GROUP}")
-    first = D.rank_seed(train_seed, K)
-    return [first + k for k in range(K)]
+group_seeds = _offline_loop.group_seeds
 
 
 def train(config: TrainConfig, dataset=None, reward_model=None, move_stats=None, *,

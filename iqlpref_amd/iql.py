@@ -22,7 +22,7 @@ import torch.nn as nn
 from torch.distributions import Normal
 from torch.optim.lr_scheduler import CosineAnnealingLR
 
-from . import _lib
+from . import _arena, _lib
 from ._lib import PREC_BF16, PREC_FP32, check, ptr, stream_ptr
 
 TensorBatch = List[torch.Tensor]
@@ -88,11 +88,12 @@ class TrainConfig:
             self.reward_model_path = f"{self.reward_model_root}_{self.seed}"
 
 
-def load_config(config_path: Optional[str] = None, **overrides) -> TrainConfig:
-    """The pyrallis ``--config_path`` behaviour (ref:1393): YAML keys = field names.
+def load_config_for(cls, label: str, config_path: Optional[str] = None, **overrides):
+    """The pyrallis ``--config_path`` behaviour (ref:1393) for the config dataclass ``cls``: YAML keys = field
+    names, ``overrides`` beat the file.
 
-    Unknown keys raise, values are coerced to the field's declared type (the
-    reference YAMLs write ``3e-4`` and ``false`` for int fields)."""
+    Unknown keys raise (``label`` names the class in the message), values are coerced to the field's declared
+    type (the reference YAMLs write ``3e-4`` and ``false`` for int fields)."""
     import yaml
 
     raw: Dict[str, Any] = {}
@@ -100,13 +101,18 @@ def load_config(config_path: Optional[str] = None, **overrides) -> TrainConfig:
         with open(config_path) as f:
             raw.update(yaml.safe_load(f) or {})
     raw.update(overrides)
-    known = {f.name: f for f in fields(TrainConfig)}
+    known = {f.name: f for f in fields(cls)}
     kwargs = {}
     for k, v in raw.items():
         if k not in known:
-            raise ValueError(f"unknown TrainConfig field {k!r}")
+            raise ValueError(f"unknown {label} field {k!r}")
         kwargs[k] = _coerce(v, known[k].type)
-    return TrainConfig(**kwargs)
+    return cls(**kwargs)
+
+
+def load_config(config_path: Optional[str] = None, **overrides) -> TrainConfig:
+    """ref:1393 for this module's ``TrainConfig`` (``load_config_for``)."""
+    return load_config_for(TrainConfig, "TrainConfig", config_path, **overrides)
 
 
 def _coerce(v, typ):
@@ -495,7 +501,7 @@ def _linears(mlp: MLP, what: str) -> List[nn.Linear]:
     return lin
 
 
-class ImplicitQLearning:
+class ImplicitQLearning(_arena.ArenaTrainer):
     """ref:546-688.  Extra keyword-only arguments (not in the reference):
 
     precision  "bf16" (default; the reference's ``torch.amp.autocast(bfloat16)``
@@ -506,6 +512,7 @@ class ImplicitQLearning:
     polyak_form 0: ``tp.lerp_(sp, tau)`` (ref:127-129); 1: ``(1 - tau) tp + tau sp``
                (algorithms/custom_offline/iql.py:85-87; iqlpref_amd.custom_offline sets it).
     """
+    _ENTRY = "iqlhip_trainer"
 
     def __init__(self, max_action: float, actor: nn.Module, actor_optimizer: torch.optim.Optimizer,
                  q_network: nn.Module, q_optimizer: torch.optim.Optimizer, v_network: nn.Module,
@@ -524,6 +531,7 @@ class ImplicitQLearning:
         self.v_optimizer = v_optimizer
         self.q_optimizer = q_optimizer
         self.actor_optimizer = actor_optimizer
+        self._optimizers = (q_optimizer, v_optimizer, actor_optimizer)
         self.actor_lr_schedule = CosineAnnealingLR(self.actor_optimizer, max_steps)
         self.iql_tau = iql_tau
         self.beta = beta
@@ -537,9 +545,6 @@ class ImplicitQLearning:
         self._seed = int(torch.initial_seed() if seed is None else seed) & 0xFFFFFFFFFFFFFFFF
         self._keep_grads = keep_grads
         self._polyak_form = int(polyak_form)
-        self._handle = None
-        self._handle_batch = None
-        self._group_owner = None  # the SeedGroup whose device-side group holds this trainer
         # steps per hipGraph of train_steps when the caller names none; 0 = plain kernel launches from
         # the library's C loop.  Measured (round 3, one seed): plain launches 66.7k steps/s, graphs of 50
         # steps 66.0k, graphs of 8 steps 63.6k -- every graph launch costs ~5 us of device time that
@@ -578,11 +583,8 @@ class ImplicitQLearning:
     # -- arenas ------------------------------------------------------------- #
     def _cfg(self, batch_size: int) -> _lib.TrainerConfig:
         g = lambda opt, k: opt.param_groups[0][k]
-        for opt in (self.q_optimizer, self.v_optimizer, self.actor_optimizer):
-            if not isinstance(opt, torch.optim.Adam) or g(opt, "weight_decay") != 0 or g(opt, "amsgrad") \
-                    or g(opt, "maximize"):
-                raise NotImplementedError("optimisers must be plain torch.optim.Adam "
-                                          "(no weight decay / amsgrad / maximize)")
+        _arena.check_plain_adam(self._optimizers, "optimisers must be plain torch.optim.Adam "
+                                "(no weight decay / amsgrad / maximize)")
         b1, b2 = g(self.q_optimizer, "betas")
         for opt in (self.v_optimizer, self.actor_optimizer):
             if tuple(g(opt, "betas")) != (b1, b2) or g(opt, "eps") != g(self.q_optimizer, "eps"):
@@ -631,78 +633,23 @@ class ImplicitQLearning:
         tensors = self._tensor_list()
         offsets = [o for o in self._offsets if o >= 0]
         assert len(tensors) == len(offsets)
-        self._views = []
-        with torch.no_grad():
-            for p, o in zip(tensors, offsets):
-                view = self._params[o:o + p.numel()].view(p.shape)
-                view.copy_(p.data)
-                p.data = view  # same Parameter object: the optimisers keep their references
-                self._views.append((p, o))
-                if self._grads is not None:
-                    p.grad = self._grads[o:o + p.numel()].view(p.shape)
+        self._views = _arena.bind_parameters(self._params, tensors, offsets, self._grads)
 
     def _bind_target(self):
         """q_target parameters become views of the target arena (ref:565)."""
-        tl = []
-        for mlp in self.q_target.critics():
-            for l in mlp.linears():
-                tl += [l.weight, l.bias]
-        with torch.no_grad():
-            for p, o in zip(tl, self._offsets[:2 * (self._n_hidden + 1) * self._n_critics]):
-                view = self._target[o:o + p.numel()].view(p.shape)
-                view.copy_(p.data)
-                p.data = view
+        tl = [t for mlp in self.q_target.critics() for l in mlp.linears() for t in (l.weight, l.bias)]
+        _arena.bind_parameters(self._target, tl, self._offsets[:len(tl)])
 
-    def _bind_optimizer_state(self, rebuild: bool = False):
-        """Adam moments live in the arenas; expose them through optimizer.state so
-        ``optimizer.state_dict()`` stays what torch.optim.Adam would write.  The views are made
-        once (and again after ``load_state_dict``, which replaces the state tensors); afterwards a
-        call only moves the step counters."""
-        steps = getattr(self, "_step_tensors", None)
-        if steps is None or rebuild:
-            steps = []
-            for p, o in self._views:
-                for opt in (self.q_optimizer, self.v_optimizer, self.actor_optimizer):
-                    if any(p is q for q in opt.param_groups[0]["params"]):
-                        st = opt.state[p]
-                        st["step"] = torch.tensor(float(self.total_it))
-                        st["exp_avg"] = self._exp_avg[o:o + p.numel()].view(p.shape)
-                        st["exp_avg_sq"] = self._exp_avg_sq[o:o + p.numel()].view(p.shape)
-                        steps.append(st["step"])
-            self._step_tensors = steps
-            return
-        t = float(self.total_it)
-        for st in steps:
-            st.fill_(t)
-
-    def _ensure_handle(self, batch_size: int):
-        if self._handle is not None and self._handle_batch == batch_size:
-            return
-        self._destroy_handle()
+    def _create_handle(self, batch_size: int):
         cfg = self._cfg(batch_size)
         ar = _lib.Arenas(ptr(self._params), ptr(self._exp_avg), ptr(self._exp_avg_sq),
                          ptr(self._target), ptr(self._grads))
         h = C.c_void_p()
         with torch.cuda.device(self._dev):
             check(self._lib.iqlhip_trainer_create(C.byref(h), C.byref(cfg), C.byref(ar)))
-            self._handle, self._handle_batch = h, batch_size
             check(self._lib.iqlhip_trainer_set_step(h, self.total_it))
             check(self._lib.iqlhip_trainer_sync_weights(h, stream_ptr()))
-
-    def _destroy_handle(self):
-        if getattr(self, "_handle", None) is not None:
-            owner = getattr(self, "_group_owner", None)
-            if owner is not None:  # the device-side group refers to this handle: dissolve it first
-                owner._drop_group()
-            torch.cuda.synchronize(self._dev)
-            self._lib.iqlhip_trainer_destroy(self._handle)
-            self._handle = None
-
-    def __del__(self):
-        try:
-            self._destroy_handle()
-        except Exception:
-            pass
+        return h
 
     def step_kind(self, batch_size: int) -> str:
         """"tuned" (the three-kernel step of csrc/iql_step.hip: n_hidden = 2, hidden_dim 64 / 128 / 256) or
@@ -711,13 +658,6 @@ class ImplicitQLearning:
         kind = C.c_int32()
         check(self._lib.iqlhip_trainer_step_kind(self._handle, C.byref(kind)))
         return "general" if kind.value else "tuned"
-
-    def sync_weights(self):
-        """Call after writing parameters from outside (the compute-precision copies
-        the kernels read are rebuilt from the fp32 masters)."""
-        if self._handle is not None:
-            with torch.cuda.device(self._dev):
-                check(self._lib.iqlhip_trainer_sync_weights(self._handle, stream_ptr()))
 
     def _after_steps(self, n: int):
         self.total_it += n
@@ -795,10 +735,7 @@ class ImplicitQLearning:
         self._refresh_lrs()
         losses = (torch.empty((n_steps, 3), dtype=torch.float32, device=self._dev)
                   if return_losses else None)
-        if indices is not None:
-            if indices.dtype != torch.int64 or tuple(indices.shape) != (n_steps, batch_size):
-                raise ValueError("indices must be int64 [n_steps, batch_size]")
-            indices = indices.contiguous()
+        indices = _arena.check_indices(indices, n_steps, batch_size, False, "indices must be int64 [n_steps, batch_size]")
         if dropout_keep is not None:
             dropout_keep = self._check_keep(dropout_keep, n_steps, batch_size)
         v = replay_buffer.view()
@@ -851,22 +788,11 @@ class ImplicitQLearning:
         self.actor_optimizer.load_state_dict(state_dict["actor_optimizer"])
         self.actor_lr_schedule.load_state_dict(state_dict["actor_lr_schedule"])
         self.total_it = state_dict["total_it"]
-        # optimizer.load_state_dict made fresh moment tensors: move them into the arenas
-        # (a checkpoint taken before the first step has no moments: they are zero, not stale)
+        self._adopt_optimizer_state()  # (optimizer.load_state_dict made fresh moment tensors)
         with torch.no_grad():
-            self._exp_avg.zero_()
-            self._exp_avg_sq.zero_()
-            for p, o in self._views:
-                for opt in (self.q_optimizer, self.v_optimizer, self.actor_optimizer):
-                    st = opt.state.get(p)
-                    if st and "exp_avg" in st:
-                        self._exp_avg[o:o + p.numel()].copy_(st["exp_avg"].reshape(-1))
-                        self._exp_avg_sq[o:o + p.numel()].copy_(st["exp_avg_sq"].reshape(-1))
             self._target.copy_(self._params[:self._n_target])  # ref:679 deepcopy(qf)
         self._bind_optimizer_state(rebuild=True)
-        if self._handle is not None:
-            with torch.cuda.device(self._dev):
-                check(self._lib.iqlhip_trainer_set_step(self._handle, self.total_it))
+        self._send_step()
         self.sync_weights()
 
     # -- exact resumption ---------------------------------------------------- #
@@ -915,9 +841,7 @@ class ImplicitQLearning:
         if int(state["total_it"]) != self.total_it:
             self.total_it = int(state["total_it"])
             self._after_steps(0)  # schedule, learning rate and Adam step counters at this step
-            if self._handle is not None:
-                with torch.cuda.device(self._dev):
-                    check(self._lib.iqlhip_trainer_set_step(self._handle, self.total_it))
+            self._send_step()
         mods = self._dropout_modules()
         if set(mods) != set(state["dropout"]):
             raise ValueError(f"resume state has dropout modules {sorted(state['dropout'])}, the trainer "

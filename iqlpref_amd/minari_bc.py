@@ -27,12 +27,14 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib, _offline_loop
+from . import _arena, _lib, _offline_loop
 from . import custom_offline as _co
 from . import distributed as D
 from ._lib import check, ptr, stream_ptr
 from .custom_offline import ReplayBuffer, evaluate  # noqa: F401  (bcref:133-192, 256-275)
-from .iql import compute_mean_std, mlp_forward_f32, normalize_states, set_seed
+from .iql import mlp_forward_f32, set_seed
+from .multi import DeviceGroup, _per_member
+from .multi import stepper as _multi_stepper
 
 HIDDEN = 256  # bcref:199-203
 TensorBatch = List[torch.Tensor]
@@ -139,28 +141,28 @@ class Actor(nn.Module):
         return self(state).cpu().data.numpy().flatten()
 
 
-class BC:
+class BC(_arena.ArenaTrainer):
     """bcref:217-253 on ``iqlhip_bc_*``.  The actor's parameters, gradients (``keep_grads``) and Adam moments live
-    in arenas the library borrows; the parameters stay the same ``nn.Parameter`` objects and
+    in arenas the library borrows (``_arena``); the parameters stay the same ``nn.Parameter`` objects and
     ``actor_optimizer.state_dict()`` stays what ``torch.optim.Adam`` writes."""
+    _ENTRY = "iqlhip_bc"
 
     def __init__(self, max_action: float, actor: nn.Module, actor_optimizer: torch.optim.Optimizer,
                  device: str = "cpu", *, keep_grads: bool = False):
         self._lib = _lib.load()
         self._dev = _lib.require_gpu(device)
         self.actor, self.actor_optimizer = actor, actor_optimizer
+        self._optimizers = (actor_optimizer,)
         self.max_action, self.device = max_action, device
         self.total_it = 0
-        self._handle = self._handle_batch = None
         self._keep_grads = keep_grads
         lin = actor.linears() if isinstance(actor, Actor) else None
         if lin is None or len(lin) != 3:
             raise TypeError("actor must be an iqlpref_amd.minari_bc.Actor")
         self._state_dim, self._action_dim = lin[0].in_features, lin[2].out_features
         widths = (lin[0].out_features, lin[1].in_features, lin[1].out_features, lin[2].in_features)
-        g = actor_optimizer.param_groups[0]
-        if not isinstance(actor_optimizer, torch.optim.Adam) or g["weight_decay"] != 0 or g["amsgrad"] or g["maximize"]:
-            raise NotImplementedError("the optimiser must be plain torch.optim.Adam (no weight decay / amsgrad / maximize)")
+        _arena.check_plain_adam(self._optimizers,
+                                "the optimiser must be plain torch.optim.Adam (no weight decay / amsgrad / maximize)")
         self._hidden = widths[0] if len(set(widths)) == 1 else -1
         for p in actor.parameters():
             if p.device.type != "cuda":
@@ -185,56 +187,17 @@ class BC:
         self._params, self._exp_avg, self._exp_avg_sq = z(), z(), z()
         self._grads = z() if self._keep_grads else None
         tensors = [t for l in self.actor.linears() for t in (l.weight, l.bias)]
-        self._views = list(zip(tensors, [int(o) for o in offs]))
-        with torch.no_grad():
-            for p, o in self._views:
-                view = self._params[o:o + p.numel()].view(p.shape)
-                view.copy_(p.data)
-                p.data = view  # same Parameter object: the optimiser keeps its references
-                if self._grads is not None:
-                    p.grad = self._grads[o:o + p.numel()].view(p.shape)
+        self._views = _arena.bind_parameters(self._params, tensors, offs, self._grads)
 
-    def _bind_optimizer_state(self):
-        """The Adam moments are views of the arenas, the step counters this trainer's count."""
-        for p, o in self._views:
-            st = self.actor_optimizer.state[p]
-            st["step"] = torch.tensor(float(self.total_it))
-            st["exp_avg"] = self._exp_avg[o:o + p.numel()].view(p.shape)
-            st["exp_avg_sq"] = self._exp_avg_sq[o:o + p.numel()].view(p.shape)
-
-    def _ensure_handle(self, batch_size: int):
-        if self._handle is not None and self._handle_batch == batch_size:
-            return
-        self._destroy_handle()
+    def _create_handle(self, batch_size: int):
         cfg = self._cfg(batch_size)
         ar = _lib.Arenas(ptr(self._params), ptr(self._exp_avg), ptr(self._exp_avg_sq), None, ptr(self._grads))
         h = C.c_void_p()
         with torch.cuda.device(self._dev):
             torch.cuda.synchronize(self._dev)  # (the copies are built from the masters on the default stream)
             check(self._lib.iqlhip_bc_create(C.byref(h), C.byref(cfg), float(self.max_action), C.byref(ar)))
-        self._handle, self._handle_batch = h, batch_size
         check(self._lib.iqlhip_bc_set_step(h, self.total_it))
-
-    def _destroy_handle(self):
-        if getattr(self, "_handle", None) is not None:
-            owner = getattr(self, "_group_owner", None)
-            if owner is not None:  # the device-side group refers to this handle: dissolve it first
-                owner.close()
-            torch.cuda.synchronize(self._dev)
-            self._lib.iqlhip_bc_destroy(self._handle)
-            self._handle = None
-
-    def __del__(self):
-        try:
-            self._destroy_handle()
-        except Exception:
-            pass
-
-    def sync_weights(self):
-        """Call after writing parameters from outside: the copies the kernels read are rebuilt from the masters."""
-        if self._handle is not None:
-            with torch.cuda.device(self._dev):
-                check(self._lib.iqlhip_bc_sync_weights(self._handle, stream_ptr()))
+        return h
 
     def weight_copies(self) -> Dict[str, torch.Tensor]:
         """The copies the kernels read, as they stand (tests): the padded forward copies ``w1`` [256, S16],
@@ -251,8 +214,7 @@ class BC:
                 check(self._lib.iqlhip_bc_copy_out(self._handle, i, ptr(out[name]), stream_ptr()))
         return out
 
-    def _prepare_steps(self, batch_size: int):
-        self._ensure_handle(batch_size)
+    def _refresh_lrs(self):
         lr = float(self.actor_optimizer.param_groups[0]["lr"])
         if lr != getattr(self, "_lr_sent", None):
             check(self._lib.iqlhip_bc_set_lr(self._handle, lr))
@@ -264,15 +226,24 @@ class BC:
 
     # -- the step ----------------------------------------------------------- #
     def train_steps(self, replay_buffer: ReplayBuffer, n_steps: int, batch_size: int, *,
-                    indices: torch.Tensor, return_losses: bool = True):
+                    indices: torch.Tensor, dropout_keep=None, return_losses: bool = True,
+                    graph_unroll: Optional[int] = None, n_valid=None):
         """bcref:339-341 ``n_steps`` times without host syncs: rows ``indices[i]`` (int64 device tensor
         [n_steps, batch_size]) of the buffer, forward, mse loss, backward, Adam.  Returns the float32 device tensor
-        [n_steps, 1] of the steps' ``actor_loss`` when ``return_losses``."""
+        [n_steps, 1] of the steps' ``actor_loss`` when ``return_losses``.
+
+        The other keywords are those of ``ImplicitQLearning.train_steps``, so that ``multi.Solo`` steps either
+        family: ``dropout_keep`` and ``n_valid`` must be None (the BC step has no dropout and pads its own batch),
+        ``graph_unroll`` is accepted and unused (the step issues plain launches)."""
+        if dropout_keep is not None or n_valid is not None:
+            raise NotImplementedError("the BC step has no dropout and pads its own batch: dropout_keep and n_valid "
+                                      "must be None")
         return self._steps_on_view(replay_buffer.view(), n_steps, batch_size, indices, return_losses)
 
     def _steps_on_view(self, view: _lib.ReplayView, n_steps: int, batch_size: int, indices, return_losses: bool):
-        self._prepare_steps(batch_size)
-        indices = _check_indices(indices, n_steps, batch_size)
+        self._ensure_handle(batch_size)
+        self._refresh_lrs()
+        indices = _arena.check_indices(indices, n_steps, batch_size, True)
         losses = torch.empty((n_steps, 1), dtype=torch.float32, device=self._dev) if return_losses else None
         with torch.cuda.device(self._dev):
             check(self._lib.iqlhip_bc_train_steps(self._handle, C.byref(view), n_steps, ptr(indices), ptr(losses),
@@ -298,29 +269,20 @@ class BC:
     def state_dict(self) -> Dict[str, Any]:
         if self._handle is not None:  # (without a handle no step was ever queued)
             torch.cuda.synchronize(self._dev)
+        # (fresh views: whatever was done to the optimiser's state from outside, the checkpoint holds the arenas')
         if self.total_it > 0:  # (before the first step the optimiser holds no state, as bcref's)
-            self._bind_optimizer_state()
+            self._bind_optimizer_state(rebuild=True)
         return {"actor": self.actor.state_dict(), "actor_optimizer": self.actor_optimizer.state_dict()}
 
     def load_state_dict(self, state_dict: Dict[str, Any]):
         torch.cuda.synchronize(self._dev)
         self.actor.load_state_dict(state_dict["actor"])  # copies into the arena views
         self.actor_optimizer.load_state_dict(state_dict["actor_optimizer"])
-        # optimizer.load_state_dict made fresh moment tensors: move them into the arenas
-        self.total_it = 0
-        with torch.no_grad():
-            self._exp_avg.zero_()
-            self._exp_avg_sq.zero_()
-            for p, o in self._views:
-                st = self.actor_optimizer.state.get(p)
-                if st and "exp_avg" in st:
-                    self._exp_avg[o:o + p.numel()].copy_(st["exp_avg"].reshape(-1))
-                    self._exp_avg_sq[o:o + p.numel()].copy_(st["exp_avg_sq"].reshape(-1))
-                    self.total_it = int(float(st["step"]))
+        # (optimizer.load_state_dict made fresh moment tensors; the count is the optimiser's, bcref keeps no other)
+        self.total_it = self._adopt_optimizer_state() or 0
         if self.total_it > 0:
-            self._bind_optimizer_state()
-        if self._handle is not None:
-            check(self._lib.iqlhip_bc_set_step(self._handle, self.total_it))
+            self._bind_optimizer_state(rebuild=True)
+        self._send_step()
         self.sync_weights()
 
 
@@ -334,17 +296,10 @@ def check_envelope(state_dim: int, action_dim: int, batch_size: int = 16) -> Non
     check(_lib.load().iqlhip_bc_arena_layout(C.byref(c), C.byref(offs), C.byref(n)))
 
 
-def _check_indices(indices: torch.Tensor, n_steps: int, batch_size: int) -> torch.Tensor:
-    if indices is None or indices.dtype != torch.int64 or tuple(indices.shape) != (n_steps, batch_size) or \
-            indices.device.type != "cuda":
-        raise ValueError("indices must be an int64 device tensor [n_steps, batch_size]")
-    return indices.contiguous()
-
-
-class BCGroup:
+class BCGroup(DeviceGroup):
     """K ``BC`` trainers of one shape stepped by the same two launches per step (``iqlhip_bc_group_*``): the part
     of ``multi.SeedGroup``'s surface ``_offline_loop.run`` uses.  Every member is bit-identical to stepping it
-    alone.  One trainer needs no group: ``stepper`` hands back a ``BCSolo``."""
+    alone.  One trainer needs no group: ``stepper`` hands back a ``multi.Solo``."""
 
     def __init__(self, trainers: Sequence[BC]):
         if not 1 <= len(trainers) <= _lib.MAX_GROUP:
@@ -353,35 +308,29 @@ class BCGroup:
             raise ValueError("the members of a group are distinct trainers on one device")
         self.trainers = list(trainers)
         self._lib, self._dev = trainers[0]._lib, trainers[0]._dev
-        self._group = self._key = None
 
     def __len__(self):
         return len(self.trainers)
 
-    def _ensure_group(self, batch_size: int):
-        for t in self.trainers:
-            t._prepare_steps(batch_size)
-        key = tuple(t._handle.value for t in self.trainers)
-        if self._group is not None and key == self._key:
-            return
-        self.close()
-        hs = (C.c_void_p * len(key))(*key)
+    def _create_group(self, batch_size: int, handles, n: int):
         g = C.c_void_p()
-        check(self._lib.iqlhip_bc_group_create(C.byref(g), hs, len(key)))
-        self._group, self._key = g, key
-        for t in self.trainers:
-            t._group_owner = self
+        check(self._lib.iqlhip_bc_group_create(C.byref(g), handles, n))
+        return g
+
+    def _destroy_group(self, group):
+        torch.cuda.synchronize(self._dev)
+        self._lib.iqlhip_bc_group_destroy(group)
 
     def train_steps(self, replay, n_steps: int, batch_size: int, *, indices: Sequence[torch.Tensor],
                     return_losses: bool = False):
         """``BC.train_steps`` for every member: ``replay`` is one buffer for all or one per member, ``indices``
         one tensor per member.  Returns the list of [n_steps, 1] loss tensors when ``return_losses``."""
         K = len(self.trainers)
-        bufs = list(replay) if isinstance(replay, (list, tuple)) else [replay] * K
-        if len(bufs) != K or len(indices) != K:
-            raise ValueError("one buffer and one index tensor per member")
+        bufs, idx, _, _ = _per_member(K, replay, indices, None, None)
         self._ensure_group(batch_size)
-        idx = [_check_indices(i, n_steps, batch_size) for i in indices]
+        for t in self.trainers:
+            t._refresh_lrs()
+        idx = [_arena.check_indices(i, n_steps, batch_size, True) for i in idx]
         losses = [torch.empty((n_steps, 1), dtype=torch.float32, device=self._dev) for _ in range(K)] \
             if return_losses else None
         views = (_lib.ReplayView * K)(*[b.view() for b in bufs])
@@ -393,48 +342,10 @@ class BCGroup:
             t._after_steps(n_steps)
         return losses
 
-    def synchronize(self):
-        torch.cuda.current_stream(self._dev).synchronize()
-
-    def close(self):
-        if getattr(self, "_group", None) is not None:
-            torch.cuda.synchronize(self._dev)
-            self._lib.iqlhip_bc_group_destroy(self._group)
-            self._group = None
-            for t in self.trainers:
-                t._group_owner = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class BCSolo:
-    """One trainer behind ``BCGroup``'s surface: nothing is added on the device."""
-
-    def __init__(self, trainer: BC):
-        self.trainers = [trainer]
-
-    def __len__(self):
-        return 1
-
-    def train_steps(self, replay, n_steps: int, batch_size: int, *, indices, return_losses: bool = False):
-        buf = replay[0] if isinstance(replay, (list, tuple)) else replay
-        losses = self.trainers[0].train_steps(buf, n_steps, batch_size, indices=indices[0], return_losses=return_losses)
-        return [losses] if return_losses else None
-
-    def synchronize(self):
-        torch.cuda.current_stream(self.trainers[0]._dev).synchronize()
-
-    def close(self):
-        pass
-
 
 def stepper(trainers: Sequence[BC]):
-    """What steps these trainers together: ``BCSolo`` for one, ``BCGroup`` for more."""
-    return BCSolo(trainers[0]) if len(trainers) == 1 else BCGroup(trainers)
+    """What steps these trainers together: ``multi.Solo`` for one, ``BCGroup`` for more."""
+    return _multi_stepper(trainers, group=BCGroup)
 
 
 # --------------------------------------------------------------------------- #
@@ -465,47 +376,23 @@ def train(config: TrainConfig, dataset=None, eval_env=None, *,
     under ``seed_<seed>/`` and a ``seed`` entry in its records; all K share the buffer and step as one
     ``BCGroup`` on the indices of one K-stream draw.  Every seed is bit-identical to the run it is alone.
     Returns the trainer (K = 1) or the list of K trainers."""
-    if sampler not in ("host", "device"):
-        raise ValueError("sampler must be 'host' or 'device'")
-    K = int(seeds_per_gpu)
-    if not 1 <= K <= _lib.MAX_GROUP:
-        raise ValueError(f"seeds_per_gpu must be in 1..{_lib.MAX_GROUP}")
+    _offline_loop.check_sampler(sampler)
+    seeds = _offline_loop.group_seeds(config.train_seed, seeds_per_gpu)
+    K = len(seeds)
     if device is None:
         device = D.local_device() or "cuda:0"
-    minari = None
-    if dataset is None:
-        minari = _co._minari("minari_bc.train")
-        dataset = minari.load_dataset(config.dataset_id)
-    if eval_env is None:
-        if not hasattr(dataset, "recover_environment"):
-            raise ValueError("minari_bc.train: pass eval_env= (the dataset cannot recover_environment())")
-        eval_env = dataset.recover_environment()
-    if normalized_score is None:
-        normalized_score = _co._minari_score(minari)
-    state_dim = eval_env.observation_space.shape[0]
-    action_dim = eval_env.action_space.shape[0]
-    max_action = float(eval_env.action_space.high[0])
+    dataset, eval_env, normalized_score, state_dim, action_dim, max_action = _co._minari_setup(
+        "minari_bc.train", config, dataset, eval_env, normalized_score)
 
     check_envelope(state_dim, action_dim)  # (before the buffer is packed: nothing is launched for a refused shape)
 
     qdataset = qlearning_dataset(dataset, best_trajectories_ids(dataset, config.top_fraction, config.gamma))
-    if config.normalize_state:
-        state_mean, state_std = compute_mean_std(qdataset["observations"], eps=1e-3)
-    else:
-        state_mean, state_std = 0, 1
-    qdataset["observations"] = normalize_states(qdataset["observations"], state_mean, state_std)
-    qdataset["next_observations"] = normalize_states(qdataset["next_observations"], state_mean, state_std)
-    from .train import _NormalizedEnv
-    eval_env = _NormalizedEnv(eval_env, state_mean, state_std, 1.0)  # bcref wrap_env, reward_scale 1
-    replay_buffer = ReplayBuffer(state_dim, action_dim, config.buffer_size, device)
-    replay_buffer.load_dataset(qdataset)
+    replay_buffer, eval_env = _co._prepare(config, qdataset, eval_env, state_dim, action_dim, device)  # bcref:300-312
 
-    seeds = [D.rank_seed(config.train_seed, K) + k for k in range(K)]
     ckpt_dirs = _offline_loop.checkpoint_dirs(config, seeds)
     set_seed(seeds[0])  # np, random, torch, PYTHONHASHSEED (bcref:327)
-    gens = [None] if K == 1 else [np.random.RandomState(s) for s in seeds]  # None: numpy's global generator
     trainers = [_build_trainer(s, state_dim, action_dim, max_action, device) for s in seeds]
-    stream = _co.NumpyIndexStream(device) if sampler == "device" else None
+    gens, stream = _co._index_sources(seeds, sampler, device)
     if logger is None:
         logger = _offline_loop.default_logger(config, K)
 

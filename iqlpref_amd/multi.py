@@ -34,6 +34,7 @@ from typing import List, Optional, Sequence, Union
 import torch
 
 from . import _lib
+from ._arena import check_indices
 from ._lib import check, ptr, stream_ptr
 from .iql import ImplicitQLearning, ReplayBuffer
 
@@ -105,7 +106,53 @@ def _per_member(K: int, replay, indices, dropout_keep, n_valid):
     return bufs, idx, keep, valid
 
 
-class SeedGroup:
+class DeviceGroup:
+    """A native group over the handles of member trainers (``_arena.ArenaTrainer``), built from the members' handle
+    values and keyed on that tuple: a member whose handle was rebuilt (another batch size) dissolves the group
+    through ``_group_owner`` first, and the next step builds a new one.  A subclass sets ``trainers``, ``_lib`` and
+    ``_dev`` and supplies ``_create_group`` / ``_destroy_group``."""
+    _group = _key = None
+    trainers: Sequence = ()
+
+    def _create_group(self, batch_size: int, handles, n: int) -> C.c_void_p:
+        raise NotImplementedError
+
+    def _destroy_group(self, group) -> None:
+        raise NotImplementedError
+
+    def _ensure_group(self, batch_size: int):
+        for t in self.trainers:
+            t._ensure_handle(batch_size)
+        key = tuple(t._handle.value for t in self.trainers)
+        if self._group is not None and key == self._key:
+            return
+        self._drop_group()
+        self._group, self._key = self._create_group(batch_size, (C.c_void_p * len(key))(*key), len(key)), key
+        for t in self.trainers:
+            t._group_owner = self
+
+    def _drop_group(self):
+        if self._group is not None:
+            self._destroy_group(self._group)
+            self._group = None
+            for t in self.trainers:
+                t._group_owner = None
+
+    def close(self):
+        """Dissolve the device-side group; the trainers stay usable on their own."""
+        self._drop_group()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def synchronize(self):
+        torch.cuda.current_stream(self._dev).synchronize()
+
+
+class SeedGroup(DeviceGroup):
     def __init__(self, trainers: Sequence[ImplicitQLearning], chunk: int = 2000, mode: Optional[str] = None,
                  n_streams: int = 2):
         if not trainers:
@@ -136,8 +183,6 @@ class SeedGroup:
         self._lib = _lib.load()
         self._streams = [torch.cuda.Stream(device=self._dev) for _ in self.trainers] if mode == "streams" else []
         self._chunk = int(chunk)
-        self._group = None
-        self._group_batch = None
         self._children: List["SeedGroup"] = []
         self._child_slices: List[slice] = []
         if mode == "split":
@@ -169,32 +214,18 @@ class SeedGroup:
                              "on the tuned step (use mode='group' or 'split')")
 
     # -- group handle --------------------------------------------------------- #
-    def _ensure_group(self, batch_size: int):
-        if self._group is not None and self._group_batch == batch_size and \
-                all(t._handle is not None and t._handle_batch == batch_size for t in self.trainers):
-            return
-        self._drop_group()
-        for t in self.trainers:
-            t._ensure_handle(batch_size)
+    def _create_group(self, batch_size: int, handles, n: int):
         if self.mode == "general":
             self._check_general(self.trainers, batch_size)
-        arr = (C.c_void_p * len(self.trainers))(*[t._handle.value for t in self.trainers])
         g = C.c_void_p()
         with torch.cuda.device(self._dev):
-            check(self._lib.iqlhip_group_create(C.byref(g), arr, len(self.trainers)))
-        self._group, self._group_batch = g, batch_size
-        for t in self.trainers:
-            t._group_owner = self
+            check(self._lib.iqlhip_group_create(C.byref(g), handles, n))
+        return g
 
-    def _drop_group(self):
-        if getattr(self, "_group", None) is not None:
-            self._lib.iqlhip_group_destroy(self._group)
-            self._group = None
-            for t in self.trainers:
-                t._group_owner = None
+    def _destroy_group(self, group):
+        self._lib.iqlhip_group_destroy(group)  # (waits for the device itself)
 
     def close(self):
-        """Dissolve the device-side group; the trainers stay usable on their own."""
         for ch in getattr(self, "_children", []):
             ch.close()
         self._drop_group()
@@ -202,12 +233,6 @@ class SeedGroup:
             for st in self._streams:
                 st.synchronize()
             self._streams = []  # (the slice streams themselves are shared and stay, see _slice_streams)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # -- stepping ------------------------------------------------------------- #
     def train_steps(self, replay: Union[ReplayBuffer, Sequence[ReplayBuffer]], n_steps: int, batch_size: int, *,
@@ -233,11 +258,7 @@ class SeedGroup:
         if self.mode == "split":
             return self._train_split(bufs, n_steps, batch_size, idx, keep, return_losses, graph_unroll, valid)
         self._ensure_group(batch_size)
-        for i, t in enumerate(idx):
-            if t is not None:
-                if t.dtype != torch.int64 or tuple(t.shape) != (n_steps, batch_size):
-                    raise ValueError("indices must be int64 [n_steps, batch_size]")
-                idx[i] = t.contiguous()
+        idx = [check_indices(t, n_steps, batch_size, False, "indices must be int64 [n_steps, batch_size]") for t in idx]
         keep = [None if k is None else t._check_keep(k, n_steps, batch_size) for t, k in zip(self.trainers, keep)]
         losses = [torch.empty((n_steps, 3), dtype=torch.float32, device=self._dev) for _ in range(K)] \
             if return_losses else None
@@ -362,7 +383,7 @@ class SeedGroup:
     def synchronize(self):
         for st in self._streams:
             st.synchronize()
-        torch.cuda.current_stream(self._dev).synchronize()
+        super().synchronize()
 
 
 class Solo:
@@ -370,11 +391,12 @@ class Solo:
     seed and K seeds with the same calls.  Nothing is added on the device: no group is created, the trainer
     is never owned, there is no stream of its own, and ``train_steps`` is one ``trainer.train_steps`` call with
     ``SeedGroup.train_steps``' argument conventions and ValueErrors (every per-member list holds one entry;
-    ``graph_unroll`` None leaves the unroll to the trainer) that returns ``[losses]`` or None."""
+    ``graph_unroll`` None leaves the unroll to the trainer) that returns ``[losses]`` or None.  Every trainer
+    family whose ``train_steps`` takes these keywords is served: ``ImplicitQLearning`` and ``minari_bc.BC``."""
     mode = "solo"
 
-    def __init__(self, trainer: ImplicitQLearning):
-        self.trainers: List[ImplicitQLearning] = [trainer]
+    def __init__(self, trainer):
+        self.trainers = [trainer]
 
     def __len__(self):
         return 1
@@ -393,6 +415,9 @@ class Solo:
         pass
 
 
-def stepper(trainers: Sequence[ImplicitQLearning], mode: Optional[str] = None, **kw) -> Union[Solo, SeedGroup]:
-    """What steps these trainers together: ``Solo`` for one, ``SeedGroup(trainers, mode=mode, **kw)`` for more."""
-    return Solo(trainers[0]) if len(trainers) == 1 else SeedGroup(trainers, mode=mode, **kw)
+def stepper(trainers: Sequence, mode: Optional[str] = None, *, group=None, **kw):
+    """What steps these trainers together: ``Solo`` for one; for more ``SeedGroup(trainers, mode=mode, **kw)``, or
+    ``group(trainers, **kw)`` for a family with a group class of its own (``minari_bc.BCGroup``)."""
+    if len(trainers) == 1:
+        return Solo(trainers[0])
+    return SeedGroup(trainers, mode=mode, **kw) if group is None else group(trainers, **kw)

@@ -42,7 +42,7 @@ Two quirks of dbc's ``train()`` are kept on purpose:
 import ctypes as C
 import os
 import uuid
-from dataclasses import dataclass, fields
+from dataclasses import dataclass
 from pathlib import Path
 from typing import Any, Callable, Dict, List, Optional, Tuple
 
@@ -54,7 +54,7 @@ from . import _lib, _offline_loop, minari_bc
 from . import custom_offline as _co
 from . import distributed as D
 from ._lib import check, ptr, stream_ptr
-from .iql import _coerce, compute_mean_std, normalize_states, set_seed  # noqa: F401  (dbc:68-75, 162-172)
+from .iql import load_config_for, compute_mean_std, normalize_states, set_seed  # noqa: F401  (dbc:68-75, 162-172)
 from .minari_bc import Actor, check_envelope, stepper  # (dbc:242-263 is minari_bc.Actor)
 from .train import wrap_env  # noqa: F401  (dbc:78-97)
 
@@ -91,21 +91,8 @@ class TrainConfig:
 
 
 def load_config(config_path: Optional[str] = None, **overrides) -> TrainConfig:
-    """The pyrallis ``--config_path`` behaviour (dbc:313) with ``iql.load_config``'s rules: YAML keys = field
-    names, unknown keys raise, values are coerced to the field's declared type; ``overrides`` beat the file."""
-    import yaml
-    raw: Dict[str, Any] = {}
-    if config_path:
-        with open(config_path) as f:
-            raw.update(yaml.safe_load(f) or {})
-    raw.update(overrides)
-    known = {f.name: f for f in fields(TrainConfig)}
-    kwargs = {}
-    for k, v in raw.items():
-        if k not in known:
-            raise ValueError(f"unknown offline_bc.TrainConfig field {k!r}")
-        kwargs[k] = _coerce(v, known[k].type)
-    return TrainConfig(**kwargs)
+    """The pyrallis ``--config_path`` behaviour (dbc:313) with ``iql.load_config``'s rules."""
+    return load_config_for(TrainConfig, "offline_bc.TrainConfig", config_path, **overrides)
 
 
 # --------------------------------------------------------------------------- #
@@ -398,11 +385,9 @@ def train(config: TrainConfig, dataset=None, env=None, *,
     checkpoints under ``seed_<seed>/`` and a ``seed`` entry in its records; all K share the buffer and step as one
     ``BCGroup``.  Every seed is bit-identical to the run it is alone.  ``load_model`` is for one seed.
     Returns the trainer (K = 1) or the list of K trainers."""
-    if sampler not in ("host", "device"):
-        raise ValueError("sampler must be 'host' or 'device'")
-    K = int(seeds_per_gpu)
-    if not 1 <= K <= _lib.MAX_GROUP:
-        raise ValueError(f"seeds_per_gpu must be in 1..{_lib.MAX_GROUP}")
+    _offline_loop.check_sampler(sampler)
+    seeds = _offline_loop.group_seeds(config.seed, seeds_per_gpu)
+    K = len(seeds)
     if K > 1 and config.load_model != "":
         raise ValueError("load_model continues one run: seeds_per_gpu must be 1")
     if device is None:
@@ -423,18 +408,16 @@ def train(config: TrainConfig, dataset=None, env=None, *,
     replay_buffer, state_mean, state_std = _load_selected(config, dataset, state_dim, action_dim, device)
     env = wrap_env(env, state_mean=state_mean, state_std=state_std)
 
-    seeds = [D.rank_seed(config.seed, K) + k for k in range(K)]
     ckpt_dirs = _offline_loop.checkpoint_dirs(config, seeds)
     max_action = float(env.action_space.high[0])
     set_seed(seeds[0], env)  # dbc:353-354
-    gens = [None] if K == 1 else [np.random.RandomState(s) for s in seeds]  # None: numpy's global generator
     print("---------------------------------------")
     print(f"Training BC, Env: {config.env}, Seed: {seeds[0] if K == 1 else seeds}")
     print("---------------------------------------")
     trainers = [_build_trainer(s, state_dim, action_dim, max_action, config.discount, device) for s in seeds]
     if config.load_model != "":
         trainers[0].load_state_dict(torch.load(Path(config.load_model)))
-    stream = _co.NumpyIndexStream(device) if sampler == "device" else None
+    gens, stream = _co._index_sources(seeds, sampler, device)
     if logger is None:
         logger = _offline_loop.default_logger(config, K)
 

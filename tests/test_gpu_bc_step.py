@@ -26,6 +26,10 @@ restatement alone); with no such pair nothing is added.  Every figure is printed
 An MI355X gave, as the largest error / bound over the five cases and three steps: loss 0.75, gradients 0.81
 (net.4.bias of the one-row case; 0.65 elsewhere), new parameters 0.25, exp_avg 0.25, exp_avg_sq 0.94; every copy
 equal to the new parameters bit for bit; at most 4 pairs of a step near a kink (3e-5 of them), no inf or nan.
+
+Below the step cases: the life of handles and groups (a ``BCGroup`` whose members change batch size, are closed,
+deleted and stepped on alone, bit for bit against twins stepped alone), and the refusal of host ``indices`` by both
+trainer families and ``SeedGroup`` before anything is launched.
 """
 import numpy as np
 import pytest
@@ -184,3 +188,137 @@ def test_outside_the_envelope_is_refused_before_any_launch():
         assert lib.iqlhip_bc_create(C.byref(h), C.byref(cfg), 1.0, C.byref(ar)) == _lib.ERR_UNSUPPORTED, field
     cfg = ok._cfg(0)
     assert lib.iqlhip_bc_arena_layout(C.byref(cfg), C.byref(offs), C.byref(n)) == _lib.ERR_INVALID
+
+
+# --------------------------------------------------------------------------- #
+# the lifecycle of handles and groups
+# --------------------------------------------------------------------------- #
+def _lifecycle_inputs():
+    """Two members of the shape of case ``s3_a1_b1`` (S 3, A 1): member 0 starts at the case's parameters, member 1
+    at torch's initialisation under another seed.  Batch 1 steps on the case's own rows and indices; batch 17 on
+    the rows and indices of case ``s17_a6_b17`` cut to the first 3 state columns and the first action column (its
+    indices name unpoisoned rows only), member 1 on the same rows in reverse order."""
+    S, A, B1, max_action, params, d1, i1, _ = mc.bc_case_inputs("s3_a1_b1")
+    _, _, B17, _, _, d17, i17, _ = mc.bc_case_inputs("s17_a6_b17")
+    cut = {k: np.ascontiguousarray(v[:, :S] if "observations" in k else v[:, :A] if k == "actions" else v)
+           for k, v in d17.items()}
+    torch.manual_seed(7)
+    other = {"net." + k: v.detach().numpy().copy()
+             for k, v in torch.nn.Sequential(torch.nn.Linear(S, mc.H), torch.nn.ReLU(), torch.nn.Linear(mc.H, mc.H),
+                                             torch.nn.ReLU(), torch.nn.Linear(mc.H, A)).state_dict().items()}
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+    idx1, idx17 = up(i1[:, :B1]), up(i17[:, :B17])
+    return S, A, max_action, (params, other), (d1, cut), ((B1, [idx1, idx1]), (B17, [idx17, up(i17[:, :B17][:, ::-1])]))
+
+
+def _same(a, b, where=""):
+    """Equal key for key; tensors bit for bit."""
+    if isinstance(a, dict):
+        assert isinstance(b, dict) and list(a) == list(b), where
+        for k in a:
+            _same(a[k], b[k], f"{where}/{k}")
+    elif isinstance(a, (list, tuple)):
+        assert len(a) == len(b), where
+        for i, (x, y) in enumerate(zip(a, b)):
+            _same(x, y, f"{where}/{i}")
+    elif torch.is_tensor(a):
+        assert torch.is_tensor(b) and a.dtype == b.dtype and torch.equal(a.cpu(), b.cpu()), where
+    else:
+        assert a == b, where
+
+
+def _same_trainer(got, want, where):
+    torch.cuda.synchronize()
+    assert got.total_it == want.total_it, where
+    for (k, p), q in zip(got.actor.named_parameters(), want.actor.parameters()):
+        assert torch.equal(p, q), f"{where}: {k}"
+    assert torch.equal(got._exp_avg, want._exp_avg) and torch.equal(got._exp_avg_sq, want._exp_avg_sq), where
+    _same(got.state_dict(), want.state_dict(), where)
+
+
+def test_group_lifecycle_matches_members_stepped_alone():
+    """Two ``BC`` trainers as a ``BCGroup``: three steps at batch 1, three at batch 17 -- every member handle is
+    rebuilt there, so the group is dissolved through its owner and built again -- against twins stepped alone
+    through the same calls: losses, parameters, moments and ``state_dict()`` bit for bit.  Then the group is
+    closed, one member is deleted while the other lives, and the survivor steps on alone like its twin."""
+    import gc
+    from iqlpref_amd import custom_offline as co, minari_bc
+    S, A, max_action, params, datas, calls = _lifecycle_inputs()
+
+    def build():
+        out = []
+        for p in params:
+            actor = minari_bc.Actor(S, A, max_action)
+            actor.load_state_dict({k: torch.from_numpy(v) for k, v in p.items()})
+            actor = actor.to(DEV)
+            out.append(minari_bc.BC(max_action, actor, torch.optim.Adam(actor.parameters(), lr=mc.LR), DEV))
+        return out
+
+    bufs = []
+    for d in datas:
+        bufs.append(co.ReplayBuffer(S, A, len(d["observations"]), DEV))
+        bufs[-1].load_dataset(d)
+    members, twins = build(), build()
+    group = minari_bc.BCGroup(members)
+    handles = []
+    for buf, (B, idx) in zip(bufs, calls):
+        got = group.train_steps(buf, mc.STEPS, B, indices=idx, return_losses=True)
+        want = [t.train_steps(buf, mc.STEPS, B, indices=i) for t, i in zip(twins, idx)]
+        for k, (g, w) in enumerate(zip(got, want)):
+            assert g.shape == (mc.STEPS, 1) and torch.equal(g, w), f"batch {B} member {k}"
+            assert bool(torch.isfinite(g).all())
+        assert all(t._group_owner is group and t._handle_batch == B for t in members)
+        handles.append(group._group.value)
+        for k, (m, t) in enumerate(zip(members, twins)):
+            _same_trainer(m, t, f"batch {B} member {k}")
+    assert all(t.total_it == 2 * mc.STEPS for t in members) and None not in handles
+    assert not torch.equal(members[0]._params, members[1]._params)
+
+    group.close()
+    assert all(t._group_owner is None and t._handle is not None for t in members)
+    survivor = members[1]
+    del group, members
+    gc.collect()
+    (B, idx), buf = calls[1], bufs[1]
+    got = survivor.train_steps(buf, 1, B, indices=idx[1][:1])
+    want = twins[1].train_steps(buf, 1, B, indices=idx[1][:1])
+    assert torch.equal(got, want)
+    _same_trainer(survivor, twins[1], "the survivor")
+
+
+@pytest.mark.parametrize("who", ["bc", "iql", "seed_group"])
+def test_host_indices_are_refused_before_any_launch(who):
+    """An ``indices`` tensor on the host is a ValueError of ``BC.train_steps``, ``ImplicitQLearning.train_steps``
+    and ``SeedGroup.train_steps`` alike: nothing is launched and no step is counted."""
+    if who == "bc":
+        tr, buf, (S, A, B, _, _, idx) = _trainer("s17_a6_b17", keep_grads=False)
+        good = torch.from_numpy(idx[:1, :B]).to(DEV)
+        tr.train_steps(buf, 1, B, indices=good)
+        before = tr._params.clone()
+        with pytest.raises(ValueError, match="indices"):
+            tr.train_steps(buf, 1, B, indices=good.cpu())
+        torch.cuda.synchronize()
+        assert tr.total_it == 1 and torch.equal(tr._params, before)
+        return
+    import iqlpref_amd as ia
+    from tests import gpu_helpers, helpers
+    d, hyper, data, nets = helpers.load_traj("traj_antmaze", "fp32")
+    B = hyper["batch"]
+    buf = gpu_helpers.make_buffer(hyper, data)
+    good = torch.from_numpy(d["indices"][:1]).to(DEV)
+    trs = [gpu_helpers.make_trainer(hyper, nets, "fp32", seed=s) for s in ((1,) if who == "iql" else (1, 2))]
+    if who == "iql":
+        stepped, step = trs[0], lambda i: trs[0].train_steps(buf, 1, B, indices=i)
+    else:
+        stepped = ia.SeedGroup(trs, mode="group")
+        step = lambda i: stepped.train_steps(buf, 1, B, indices=[i, good])
+    step(good)
+    counts = [x.launch_counts() for x in [stepped] + trs]
+    before = [t._params.clone() for t in trs]
+    with pytest.raises(ValueError, match="indices"):
+        step(good.cpu())
+    torch.cuda.synchronize()
+    assert [x.launch_counts() for x in [stepped] + trs] == counts
+    assert all(t.total_it == 1 and torch.equal(t._params, p) for t, p in zip(trs, before))
+    if who == "seed_group":
+        stepped.close()
