@@ -831,6 +831,79 @@ int iqlhip_bc_group_destroy(iqlhip_bc_group *g);
 int iqlhip_bc_group_train_steps(iqlhip_bc_group *g, const iqlhip_replay_view *views, int64_t n_steps,
                                 const int64_t *const *idx, float *const *losses_out, void *stream);
 
+/* ------------------------------------------------------------------------ */
+/* Offline AWAC (algorithms/offline/awac.py, "awac"; csrc/awac_step.hip): an   */
+/* actor Linear(S,H) ReLU Linear(H,H) ReLU Linear(H,H) ReLU Linear(H,A) with a */
+/* _log_std[A] parameter, two critics of the same shape on (s | a) ending in   */
+/* Linear(H,1), their two Polyak targets (awac:134-215); update() as           */
+/* awac:301-310: critics (MSE against r + gamma (1 - d) min Q_target(s', a'),  */
+/* a' sampled from the live actor), then the actor (mean of                    */
+/* -min(exp((q - v) / lambda), exp_adv_max) log_prob(a | s) at the critics     */
+/* just updated), then the targets.  Plain Adam, four launches per step.       */
+/* Envelope (anything else: IQLHIP_ERR_UNSUPPORTED before any HIP call):       */
+/* precision fp32, n_hidden 3, hidden_dim a multiple of 16 in 16..256,         */
+/* state_dim <= 128, action_dim <= 32, no dropout, batch_size 1..65536 (padded */
+/* to whole 16-row slabs inside, the means count the batch_size real rows),    */
+/* 1..IQLHIP_MAX_GROUP members per group.                                      */
+/* Of iqlhip_trainer_config these fields are read: state_dim, action_dim,      */
+/* hidden_dim, n_hidden, batch_size, precision, dropout_p, discount (gamma),   */
+/* beta (awac_lambda),      lr_q (critic 1), lr_v (critic 2), lr_actor,        */
+/* adam_beta1, adam_beta2, adam_eps (one set for the three optimisers), seed   */
+/* (the Philox key of the action noise).  Of iqlhip_arenas: all five (grads    */
+/* optional).                                                                  */
+/* ------------------------------------------------------------------------ */
+/* Element offsets in the parameter arena, every tensor on a 128-byte line, torch [out][in]
+ * row-major: actor W_1 b_1 .. W_4 b_4, _log_std, critic 1 W_1 b_1 .. W_4 b_4, critic 2 the same
+ * (25 offsets), and the arena lengths.  The target arena holds the two critics' part of the
+ * layout: a target tensor sits at its critic's offset minus offsets[9] (critic 1's W_1).       */
+int iqlhip_awac_arena_layout(const iqlhip_trainer_config *cfg, int64_t offsets[25], int64_t *n_params,
+                             int64_t *n_target);
+
+typedef struct iqlhip_awac iqlhip_awac;
+/* Borrows the arenas for the trainer's lifetime; allocates its workspace (padded forward copies
+ * of every weight matrix of the five networks, transposed copies of layers 2..4 of the three
+ * trained ones, the feature-major activation and dz planes, the last step's eps) on the current
+ * device and builds the copies from the masters.  Synchronises the default stream once.
+ * tau: the Polyak coefficient in double -- awac:215 multiplies by float32(1 - tau) and float32(tau)
+ * of the Python double, and 1 - cfg->tau (already fp32) can be one ulp away from the former; cfg->tau
+ * is not read.                                                                                 */
+int iqlhip_awac_create(iqlhip_awac **out, const iqlhip_trainer_config *cfg, double tau, float exp_adv_max,
+                       const iqlhip_arenas *arenas);
+int iqlhip_awac_destroy(iqlhip_awac *t);
+/* Rebuild the copies from the masters and targets (after the arenas were written from outside). */
+int iqlhip_awac_sync_weights(iqlhip_awac *t, void *stream);
+/* Updates taken so far = Adam `step` of the three optimisers and the step of the noise streams. */
+int iqlhip_awac_set_step(iqlhip_awac *t, int64_t total_it);
+int iqlhip_awac_set_lr(iqlhip_awac *t, double lr_actor, double lr_critic_1, double lr_critic_2);
+/* awac:301-310 n_steps times on rows idx[i][0..batch) of the view.  idx: device int64
+ * [n_steps][batch], required (the index stream is the caller's); values outside the view are
+ * clamped into it.  eps: device fp32 [n_steps][2][batch][action_dim] -- [i][0] the standard
+ * normals of a' (awac:269), [i][1] those of pi (awac:250) -- or NULL: drawn from the Philox key
+ * `seed`, Box-Muller on block (row * 8 + column / 4, step lo, step hi, stream 5 | 6), words
+ * (x, y) and (z, w) one pair each: u1 = (x + 1) 2^-32, u2 = y 2^-32 -> sqrt(-2 ln u1)
+ * (cos, sin)(2 pi u2) in double; step = the update's zero-based count.  losses_out: NULL or
+ * device fp32 [n_steps][2] (critic_loss, actor_loss).  Plain launches on `stream`; at most
+ * ~1024 steps are left queued ahead of the device.                                            */
+int iqlhip_awac_train_steps(iqlhip_awac *t, const iqlhip_replay_view *view, int64_t n_steps,
+                            const int64_t *idx, const float *eps, float *losses_out, void *stream);
+/* Device to device into dst (tests, replays): which = 0 the eps of the last step
+ * [2][batch][action_dim]; 1 + 7 net + c, net = 0 actor, 1 critic 1, 2 critic 2, 3 target 1,
+ * 4 target 2: c = 0..3 the forward copy of Linear c + 1 [out padded to 16][in padded to 16],
+ * c = 4..6 the transposed copy of Linear c - 2 [in padded][out padded] (trained nets only; a
+ * critic's single output is padded to 16).  Padding is zero.                                  */
+int iqlhip_awac_copy_out(iqlhip_awac *t, int32_t which, float *dst, void *stream);
+
+/* K trainers of one shape (dims, width, batch size, gamma, tau, lambda, exp_adv_max) stepped by
+ * the same four launches per step, the member as a launch coordinate.  Each member is
+ * bit-identical to stepping it alone.  views[k], idx[k], eps[k], losses_out[k] belong to member k
+ * (eps and losses_out NULL as a whole or per member).  Destroy the group before its members.  */
+typedef struct iqlhip_awac_group iqlhip_awac_group;
+int iqlhip_awac_group_create(iqlhip_awac_group **out, iqlhip_awac *const *members, int32_t n);
+int iqlhip_awac_group_destroy(iqlhip_awac_group *g);
+int iqlhip_awac_group_train_steps(iqlhip_awac_group *g, const iqlhip_replay_view *views, int64_t n_steps,
+                                  const int64_t *const *idx, const float *const *eps, float *const *losses_out,
+                                  void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -197,6 +197,20 @@ SYMBOLS = {
     "iqlhip_bc_group_create": (C.c_int, [C.POINTER(P), C.POINTER(P), C.c_int32]),
     "iqlhip_bc_group_destroy": (C.c_int, [P]),
     "iqlhip_bc_group_train_steps": (C.c_int, [P, C.POINTER(ReplayView), C.c_int64, C.POINTER(P), C.POINTER(P), P]),
+    # offline AWAC (csrc/awac_step.hip)
+    "iqlhip_awac_arena_layout": (C.c_int, [C.POINTER(TrainerConfig), C.POINTER(C.c_int64 * 25), C.POINTER(C.c_int64),
+                                           C.POINTER(C.c_int64)]),
+    "iqlhip_awac_create": (C.c_int, [C.POINTER(P), C.POINTER(TrainerConfig), C.c_double, C.c_float, C.POINTER(Arenas)]),
+    "iqlhip_awac_destroy": (C.c_int, [P]),
+    "iqlhip_awac_sync_weights": (C.c_int, [P, P]),
+    "iqlhip_awac_set_step": (C.c_int, [P, C.c_int64]),
+    "iqlhip_awac_set_lr": (C.c_int, [P, C.c_double, C.c_double, C.c_double]),
+    "iqlhip_awac_train_steps": (C.c_int, [P, C.POINTER(ReplayView), C.c_int64, P, P, P, P]),
+    "iqlhip_awac_copy_out": (C.c_int, [P, C.c_int32, P, P]),
+    "iqlhip_awac_group_create": (C.c_int, [C.POINTER(P), C.POINTER(P), C.c_int32]),
+    "iqlhip_awac_group_destroy": (C.c_int, [P]),
+    "iqlhip_awac_group_train_steps": (C.c_int, [P, C.POINTER(ReplayView), C.c_int64, C.POINTER(P), C.POINTER(P),
+                                                C.POINTER(P), P]),
 }
 
 _lib = None

@@ -1,0 +1,919 @@
+// Offline AWAC (algorithms/offline/awac.py, "awac"): the training step of an actor and two critics with two
+// Polyak targets, every network Linear(in, H) ReLU Linear(H, H) ReLU Linear(H, H) ReLU Linear(H, out)
+// (awac:134-210), fp32 throughout (the reference has no autocast): exact fp32 MFMA (v_mfma_f32_16x16x4_f32).
+// One update (awac:301-310) is four launches -- an Adam step needs the whole batch's gradient, and the actor
+// loss reads the critics that the step has just updated:
+//
+//   k_awac_critic_fwd_bwd  one work-group of sixteen waves per 16-row slab and member: gathers the slab's rows,
+//                          runs the actor at s' and draws (or reads) eps_1: a' = clamp(mu + sigma eps_1, -1, 1);
+//                          both target critics at (s', a'): y = r + gamma (1 - d) min; both critics at (s, a)
+//                          with the activations held in LDS, the two MSE heads (awac:280-282: a sum, not a
+//                          half-sum) and the backward down to dz1.  Leaves x, h1..h3, dz1..dz4 feature-major
+//                          ([feature][batch row]) and the slab's two sums of squared errors.
+//   k_awac_critic_update   one wave per 16x16 tile of a weight matrix (dW = dz^T x activation, the batch as the
+//                          K dimension) or per 16 bias entries of both critics: Adam on the fp32 masters, the
+//                          padded forward copy and the transposed copy, and the target update (awac:213-215:
+//                          two rounded products and a sum) with the targets' forward copy.  Nothing reads the
+//                          targets before the next step and the critics do not change again within the step.
+//   k_awac_actor_fwd_bwd   per slab and member: the actor at s with the activations kept, eps_2:
+//                          pi = clamp(mu + sigma eps_2, -1, 1); the new critics at (s, pi) and (s, a):
+//                          w = min(exp((q - v) / lambda), exp_adv_max); the head of
+//                          mean(-w sum_A log N(a; mu, sigma)) (d mu, per-slab d sigma sums) and the backward.
+//   k_awac_actor_update    Adam on the actor's tiles and on _log_std (exp and clamp backward: the clamp passes
+//                          the gradient inside [-20, 2] only), and both logged losses, summed in slab order.
+//
+// A batch of any size is padded to whole 16-row slabs: padding rows gather nothing, their head gradients are
+// zero and so is everything behind them; the means divide by the B real rows.  The members of a group are the
+// y coordinate of every launch; a member's arguments are its own entry of the by-value argument block and its
+// arithmetic does not depend on who else is launched with it.
+//
+// eps: [n_steps][2][B][A] as given, or (null) standard normals from the trainer's Philox key by Box-Muller as
+// online.hip draws them: block (row * 8 + column / 4, step lo, step hi, STREAM_AWAC_NEXT | STREAM_AWAC_PI), words
+// (x, y) and (z, w) each one pair, evaluated in double.  Either way the eps of the last step stay in the
+// workspace (iqlhip_awac_copy_out).
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <new>
+
+#include "../../include/iqlhip.h"
+#include "common.h"
+#include "errors.h"
+#include "host_plan.h"
+#include "step_math.h"
+
+namespace iqlhip {
+
+constexpr uint32_t STREAM_AWAC_NEXT = 5, STREAM_AWAC_PI = 6;  // (0-3 common.h, 4 online.hip, 8.. drop_stream)
+constexpr int AW_MAX_H = 256, AW_MAX_S = 128, AW_MAX_A = 32;
+constexpr int AW_LS = AW_MAX_H + 4;             // floats; rows stay 16-byte aligned, 4 r mod 32 banks apart
+constexpr int AW_XS = AW_MAX_S + AW_MAX_A + 4;  // of a [s | a] row
+constexpr int AW_DS = AW_MAX_A + 4;             // of a head-gradient row
+constexpr int AW_WAVES = 16, AW_THREADS = AW_WAVES * WAVE;
+constexpr int AW_ACTOR = 0, AW_C1 = 1, AW_C2 = 2, AW_T1 = 3, AW_T2 = 4, AW_NETS = 5;
+constexpr int AW_COPIES = 7;  // per net: forward copies of the four layers, transposed copies of layers 2..4
+
+// One network: Linear l has OUT_l x IN_l real entries, its forward copy is [OP_l][KP_l] and (trained nets,
+// l >= 1) its transposed copy [KP_l][OP_l]; OP_l = KP_(l+1).  Element offsets: o_* in the parameter arena
+// (targets: the target arena), everything else in the member's workspace.
+struct AwNet {
+  int o_w[4], o_b[4];
+  int c_w[4], t_w[3];
+  int pl_h[3], pl_dz[4];  // planes [H][BP] x 3; [H][BP] x 3 and [OP][BP]
+  int K1, K1P, OUT, OP;
+};
+
+struct AwShape {
+  int S, A, B, H;
+  int SP, AP, BP, XP;  // padded to 16; XP: S + A
+  int row_stride, next_off;
+  int o_log_std;
+  int pl_x;                      // [XP][BP] (s | a), feature-major
+  int o_eps;                     // [2][B][A]
+  int o_qpart, o_apart, o_lsp;   // doubles [BP/16][2], [BP/16]; floats [BP/16][AP]
+  float gamma, tau, one_m_tau, lambda, exp_adv_max, two_over_B, fB;
+  AwNet net[AW_NETS];
+};
+
+__host__ __device__ inline int aw_out(const AwShape &s, int n, int l) { return l < 3 ? s.H : s.net[n].OUT; }
+__host__ __device__ inline int aw_op(const AwShape &s, int n, int l) { return l < 3 ? s.H : s.net[n].OP; }
+__host__ __device__ inline int aw_in(const AwShape &s, int n, int l) { return l == 0 ? s.net[n].K1 : s.H; }
+__host__ __device__ inline int aw_kp(const AwShape &s, int n, int l) { return l == 0 ? s.net[n].K1P : s.H; }
+
+struct AwMember {
+  float *P, *M, *V, *G, *T;  // arenas (G may be null)
+  float *ws;
+  const float *rows;    // replay rows of this call
+  const int64_t *idx;   // [n_steps][B] of this call
+  const float *eps;     // [n_steps][2][B][A] of this call, or null
+  float *loss;          // [n_steps][2] of this call, or null
+  int64_t n_rows;
+  uint64_t seed;
+  int64_t step0;        // total_it of the call's first step (the noise streams)
+  AdamCoef coef;        // of the step being launched: neg_step = critic 1, critic 2, actor
+};
+
+struct AwArgs {
+  AwShape s;
+  int64_t step;  // of this call
+  AwMember m[IQLHIP_MAX_GROUP];
+};
+static_assert(sizeof(AwArgs) <= 4096, "the argument block travels by value");
+
+// ---------------------------------------------------------------------------------------------------
+// pieces of a slab's walk
+// ---------------------------------------------------------------------------------------------------
+// One Linear layer of the slab, forward or backward: tile t (features 16 t .. 16 t + 16) of out[16][OP] =
+// act[16][K] x Wm^T, Wm row-major [OP][K]; the tiles go round the sixteen waves.
+// Exact fp32 MFMA (common.h, Prec<false>) on four accumulators, one per component of the 16-byte fragments, added
+// pairwise at the end: four independent chains a quarter as long as one -- a quarter of the latency between
+// dependent MFMAs, and the rounding error of a four-way pairwise sum instead of a sequential one.
+__device__ __forceinline__ void aw_mma(const uint4 &a, const uint4 &b, f32x4 (&acc)[4]) {
+  const float4 af = __builtin_bit_cast(float4, a), bf = __builtin_bit_cast(float4, b);
+  acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(af.x, bf.x, acc[0], 0, 0, 0);
+  acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(af.y, bf.y, acc[1], 0, 0, 0);
+  acc[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(af.z, bf.z, acc[2], 0, 0, 0);
+  acc[3] = __builtin_amdgcn_mfma_f32_16x16x4f32(af.w, bf.w, acc[3], 0, 0, 0);
+}
+__device__ __forceinline__ f32x4 aw_acc(const f32x4 (&acc)[4]) { return (acc[0] + acc[1]) + (acc[2] + acc[3]); }
+
+template <class Epilogue>
+__device__ __forceinline__ void aw_layer(const float *act, int act_stride, const float *Wm, int K, int n_tiles,
+                                         int wave, int lane, Epilogue &&ep) {
+  const int r = lane & 15, q = lane >> 4;
+  for (int t = wave; t < n_tiles; t += AW_WAVES) {
+    const int f = 16 * t + r;
+    f32x4 acc[4] = {};
+    for (int ks = 0; ks < K / 16; ++ks) {
+      const uint4 a = *reinterpret_cast<const uint4 *>(act + r * act_stride + ks * 16 + 4 * q);
+      const uint4 b = ldg16(Wm + (size_t)f * K + ks * 16 + 4 * q);
+      aw_mma(a, b, acc);
+    }
+    ep(f, 4 * q, aw_acc(acc));  // (feature, first of 4 rows, values)
+  }
+}
+
+// A standard normal of (row, column) of the step: Box-Muller in double on one Philox block per four columns.
+__device__ __forceinline__ float aw_normal(uint64_t seed, int64_t step, int row, int c, uint32_t stream) {
+  const Philox4 r = philox4x32_10((uint32_t)row * 8u + (uint32_t)(c >> 2), (uint32_t)step, (uint32_t)((uint64_t)step >> 32),
+                                  stream, (uint32_t)seed, (uint32_t)(seed >> 32));
+  const uint32_t ua = (c & 2) ? r.z : r.x, ub = (c & 2) ? r.w : r.y;
+  const double u1 = ((double)ua + 1.0) * (1.0 / 4294967296.0), u2 = (double)ub * (1.0 / 4294967296.0);
+  // (sinpi / cospi: the angle 2 pi u2 without the large-argument reduction of sin / cos, which costs registers)
+  const double rad = sqrt(-2.0 * log(u1)), turn = 2.0 * u2;
+  return (float)(rad * ((c & 1) ? sinpi(turn) : cospi(turn)));
+}
+
+// exp(clamp(_log_std, -20, 2)) (awac:163-164), correctly rounded
+__device__ __forceinline__ float aw_std(float ls) { return (float)exp((double)fminf(fmaxf(ls, -20.f), 2.f)); }
+
+// awac:174-175: rsample = mean + eps * std (a product and a sum, each rounded), clamped to [-1, 1]
+__device__ __forceinline__ float aw_sample(float mean, float sd, float eps) {
+#pragma clang fp contract(off)
+  return fminf(fmaxf(mean + eps * sd, -1.f), 1.f);
+}
+
+// awac:275: r + gamma * (1 - d) * q_next in the tensor expression's order
+__device__ __forceinline__ float aw_target(float r, float d, float gamma, float qn) {
+#pragma clang fp contract(off)
+  return r + (gamma * (1.f - d)) * qn;
+}
+
+// awac:215: (1 - tau) * t + tau * p, two rounded products and a sum
+__device__ __forceinline__ float aw_polyak(float one_m_tau, float tau, float t, float p) {
+#pragma clang fp contract(off)
+  return (one_m_tau * t) + (tau * p);
+}
+
+// The three hidden layers of one network over the slab without kept activations: in [16][K1P] -> Ha -> Hb -> Ha.
+// Ends behind a barrier.
+__device__ __forceinline__ void aw_hidden(const AwShape &s, const AwMember &m, int n, const float *arena, const float *in,
+                                          float *Ha, float *Hb, int wave, int lane) {
+  const AwNet &N = s.net[n];
+  const int ht = s.H / 16;
+  const auto relu_to = [&](float *dst, int ob) {
+    return [&, dst, ob](int f, int row, f32x4 z) {
+      const float b = ldg(arena + ob + f);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) dst[(row + e) * AW_LS + f] = fmaxf(z[e] + b, 0.f);
+    };
+  };
+  aw_layer(in, AW_XS, m.ws + N.c_w[0], N.K1P, ht, wave, lane, relu_to(Ha, N.o_b[0]));
+  __syncthreads();
+  aw_layer(Ha, AW_LS, m.ws + N.c_w[1], s.H, ht, wave, lane, relu_to(Hb, N.o_b[1]));
+  __syncthreads();
+  aw_layer(Hb, AW_LS, m.ws + N.c_w[2], s.H, ht, wave, lane, relu_to(Ha, N.o_b[2]));
+  __syncthreads();
+}
+
+// A critic's value of the slab's rows, q[16] = h3 W4^T + b4: one tile, its column 0.  Ends behind a barrier.
+__device__ __forceinline__ void aw_q(const AwShape &s, const AwMember &m, int n, const float *arena, const float *h3,
+                                     float *q, int wave, int lane) {
+  const AwNet &N = s.net[n];
+  aw_layer(h3, AW_LS, m.ws + N.c_w[3], s.H, 1, wave, lane, [&](int f, int row, f32x4 z) {
+    if (f != 0) return;
+    const float b = ldg(arena + N.o_b[3]);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) q[row + e] = z[e] + b;
+  });
+  __syncthreads();
+}
+
+// The three hidden layers of a trained network with the activations kept in H0, H1, H2 and as planes.  Ends
+// behind a barrier; the caller runs the last layer.
+__device__ __forceinline__ void aw_hidden_kept(const AwShape &s, const AwMember &m, int n, const float *in, int in_stride,
+                                               float *H0, float *H1, float *H2, int r0, int wave, int lane) {
+  const AwNet &N = s.net[n];
+  const int ht = s.H / 16;
+  const auto keep = [&](float *dst, int ob, int plane) {
+    return [&, dst, ob, plane](int f, int row, f32x4 z) {
+      const float b = ldg(m.P + ob + f);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) z[e] = fmaxf(z[e] + b, 0.f), dst[(row + e) * AW_LS + f] = z[e];
+      stg16(m.ws + plane + (size_t)f * s.BP + r0 + row, make_float4(z[0], z[1], z[2], z[3]));
+    };
+  };
+  aw_layer(in, in_stride, m.ws + N.c_w[0], N.K1P, ht, wave, lane, keep(H0, N.o_b[0], N.pl_h[0]));
+  __syncthreads();
+  aw_layer(H0, AW_LS, m.ws + N.c_w[1], s.H, ht, wave, lane, keep(H1, N.o_b[1], N.pl_h[1]));
+  __syncthreads();
+  aw_layer(H1, AW_LS, m.ws + N.c_w[2], s.H, ht, wave, lane, keep(H2, N.o_b[2], N.pl_h[2]));
+  __syncthreads();
+}
+
+// The backward of a trained network from the head gradient DZ4 [16][OP] (in LDS, its plane already written):
+// dz3 = (dz4 W4) [h3 > 0] replaces h3 in H2, dz2 = (dz3 W3) [h2 > 0] replaces h2 in H1, dz1 = (dz2 W2) [h1 > 0]
+// goes to its plane only.  Ends behind a barrier.
+__device__ __forceinline__ void aw_backward(const AwShape &s, const AwMember &m, int n, const float *DZ4, float *H0,
+                                            float *H1, float *H2, int r0, int wave, int lane) {
+  const AwNet &N = s.net[n];
+  const int ht = s.H / 16;
+  const auto masked = [&](float *h, int plane, bool keep) {
+    return [&, h, plane, keep](int f, int row, f32x4 g) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        g[e] = h[(row + e) * AW_LS + f] > 0.f ? g[e] : 0.f;
+        if (keep) h[(row + e) * AW_LS + f] = g[e];
+      }
+      stg16(m.ws + plane + (size_t)f * s.BP + r0 + row, make_float4(g[0], g[1], g[2], g[3]));
+    };
+  };
+  aw_layer(DZ4, AW_DS, m.ws + N.t_w[2], N.OP, ht, wave, lane, masked(H2, N.pl_dz[2], true));
+  __syncthreads();
+  aw_layer(H2, AW_LS, m.ws + N.t_w[1], s.H, ht, wave, lane, masked(H1, N.pl_dz[1], true));
+  __syncthreads();
+  aw_layer(H1, AW_LS, m.ws + N.t_w[0], s.H, ht, wave, lane, masked(H0, N.pl_dz[0], false));
+  __syncthreads();
+}
+
+// The slab's rows (awac:120-126): padding rows have no index and read nothing.  X[16][AW_XS] = (s | a | 0),
+// X2 = (s' | 0) or (s | 0) (`next`), rd = reward and done (or null).  Ends behind a barrier.
+__device__ __forceinline__ void aw_gather(const AwShape &s, const AwMember &m, int64_t step, int r0, bool next, float *X,
+                                          float *X2, float *rd, int64_t *ridx, int tid) {
+  if (tid < 16) {
+    int64_t i = -1;
+    if (r0 + tid < s.B) {
+      i = ldg(m.idx + step * s.B + r0 + tid);
+      i = i < 0 ? 0 : (i >= m.n_rows ? m.n_rows - 1 : i);  // (an index outside the buffer must not leave it)
+    }
+    ridx[tid] = i;
+  }
+  __syncthreads();
+  for (int i = tid; i < 16 * s.XP; i += AW_THREADS) {
+    const int r = i / s.XP, c = i - r * s.XP;
+    const int64_t row = ridx[r];
+    const bool real = row >= 0;
+    X[r * AW_XS + c] = (real && c < s.S + s.A) ? ldg(m.rows + row * s.row_stride + c) : 0.f;
+    X2[r * AW_XS + c] = (real && c < s.S) ? ldg(m.rows + row * s.row_stride + (next ? s.next_off : 0) + c) : 0.f;
+  }
+  if (rd && tid < 32) {
+    const int64_t row = ridx[tid & 15];
+    rd[tid] = row >= 0 ? ldg(m.rows + row * s.row_stride + s.S + s.A + (tid >> 4)) : 0.f;
+  }
+  __syncthreads();
+}
+
+// The slab's standard normals of draw `which` (0: a', 1: pi), one thread per (row, column): read or drawn, kept
+// in the workspace and in EPS[16][AW_DS].  Padding rows draw and read nothing.  No barrier of its own.
+__device__ __forceinline__ void aw_noise(const AwShape &s, const AwMember &m, int64_t step, int which, float *EPS, int r0,
+                                         int tid) {
+  for (int i = tid; i < 16 * s.A; i += AW_THREADS) {
+    const int r = i / s.A, j = i - r * s.A, gr = r0 + r;
+    float ep = 0.f;
+    if (gr < s.B) {
+      ep = m.eps ? ldg(m.eps + ((size_t)(step * 2 + which) * s.B + gr) * s.A + j)
+                 : aw_normal(m.seed, m.step0 + step, gr, j, which ? STREAM_AWAC_PI : STREAM_AWAC_NEXT);
+      stg(m.ws + s.o_eps + ((size_t)which * s.B + gr) * s.A + j, ep);
+    }
+    EPS[r * AW_DS + j] = ep;
+  }
+}
+
+// The last layer of the actor over the slab: mu = H2 W4^T + b4 (kept in MU, or not: null) and the clamped sample
+// written behind the state columns of X2 (the critics' input).  MUD: mu without the rounding of the bias add, for
+// the logged loss.  Ends behind a barrier.
+__device__ __forceinline__ void aw_actor_sample(const AwShape &s, const AwMember &m, const float *H2, float *X2, float *MU,
+                                                double *MUD, const float *EPS, int r0, int wave, int lane) {
+  const AwNet &N = s.net[AW_ACTOR];
+  aw_layer(H2, AW_LS, m.ws + N.c_w[3], s.H, s.AP / 16, wave, lane, [&](int j, int row, f32x4 z) {
+    if (j >= s.A) return;
+    const float b = ldg(m.P + N.o_b[3] + j);
+    const float sd = aw_std(ldg(m.P + s.o_log_std + j));
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float mu = z[e] + b;
+      if (MU) MU[(row + e) * AW_DS + j] = mu, MUD[(row + e) * AW_DS + j] = (double)z[e] + (double)b;
+      if (r0 + row + e < s.B) X2[(row + e) * AW_XS + s.S + j] = aw_sample(mu, sd, EPS[(row + e) * AW_DS + j]);
+    }
+  });
+  __syncthreads();
+}
+
+// ---------------------------------------------------------------------------------------------------
+// launch 1: the critics' forward, heads and backward
+// ---------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(AW_THREADS) void k_awac_critic_fwd_bwd(const AwArgs args) {
+  const AwShape &s = args.s;
+  const AwMember &m = args.m[blockIdx.y];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int r0 = blockIdx.x * 16;
+  __shared__ __attribute__((aligned(16))) float Xs[16 * AW_XS], Xn[16 * AW_XS];
+  __shared__ __attribute__((aligned(16))) float H0[16 * AW_LS], H1[16 * AW_LS], H2[16 * AW_LS];
+  __shared__ __attribute__((aligned(16))) float DZ4[16 * AW_DS], EPS[16 * AW_DS];
+  __shared__ int64_t ridx[16];
+  __shared__ float rd[32], qt[2][16];
+  __shared__ double sq[16];
+
+  aw_gather(s, m, args.step, r0, true, Xs, Xn, rd, ridx, tid);
+  for (int i = tid; i < 16 * s.XP; i += AW_THREADS) {  // x = (s | a), feature-major, for dW1 of all three nets
+    const int c = i >> 4, r = i & 15;
+    stg(m.ws + s.pl_x + (size_t)c * s.BP + r0 + r, Xs[r * AW_XS + c]);
+  }
+  for (int i = tid; i < 16 * AW_DS; i += AW_THREADS) DZ4[i] = 0.f;  // (a critic's head writes column 0 only)
+
+  // ---- a' = clamp(mu(s') + sigma eps_1, -1, 1) from the actor as it stands (awac:268-269) ----
+  aw_noise(s, m, args.step, 0, EPS, r0, tid);
+  aw_hidden(s, m, AW_ACTOR, m.P, Xn, H0, H1, wave, lane);
+  aw_actor_sample(s, m, H0, Xn, nullptr, nullptr, EPS, r0, wave, lane);
+
+  // ---- q_next = min of both targets at (s', a') (awac:271-274) ----
+  for (int t = 0; t < 2; ++t) {
+    aw_hidden(s, m, AW_T1 + t, m.T, Xn, H0, H1, wave, lane);
+    aw_q(s, m, AW_T1 + t, m.T, H0, qt[t], wave, lane);
+  }
+
+  // ---- both critics at (s, a), the MSE heads (awac:277-282), the backward ----
+  for (int c = 0; c < 2; ++c) {
+    const int n = AW_C1 + c;
+    const AwNet &N = s.net[n];
+    aw_hidden_kept(s, m, n, Xs, AW_XS, H0, H1, H2, r0, wave, lane);
+    aw_layer(H2, AW_LS, m.ws + N.c_w[3], s.H, 1, wave, lane, [&](int f, int row, f32x4 z) {
+      const float b = f == 0 ? ldg(m.P + N.o_b[3]) : 0.f;
+      f32x4 dz = {};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int r = row + e;
+        if (f == 0 && r0 + r < s.B) {
+          const float qn = fminf(qt[0][r], qt[1][r]);
+          const float diff = (z[e] + b) - aw_target(rd[r], rd[16 + r], s.gamma, qn);
+          dz[e] = s.two_over_B * diff;  // mse_loss backward: (2 / B) (q - y)
+          // (the logged loss from the same fp32 values without the roundings of q + b, y and q - y)
+          const double dd = ((double)z[e] + (double)b) -
+                            ((double)rd[r] + ((double)s.gamma * (1.0 - (double)rd[16 + r])) * (double)qn);
+          sq[r] = dd * dd;
+        } else if (f == 0) {
+          sq[r] = 0.0;
+        }
+        if (f == 0) DZ4[r * AW_DS] = dz[e];
+      }
+      stg16(m.ws + N.pl_dz[3] + (size_t)f * s.BP + r0 + row, make_float4(dz[0], dz[1], dz[2], dz[3]));
+    });
+    __syncthreads();
+    if (tid == 0) {  // in double and in one fixed order: the logged loss is the correctly rounded mean
+      double t = 0.0;
+      for (int i = 0; i < 16; ++i) t += sq[i];
+      stg(reinterpret_cast<double *>(m.ws + s.o_qpart) + 2 * blockIdx.x + c, t);
+    }
+    aw_backward(s, m, n, DZ4, H0, H1, H2, r0, wave, lane);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// launch 3: the actor's forward, head and backward
+// ---------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(AW_THREADS) void k_awac_actor_fwd_bwd(const AwArgs args) {
+  const AwShape &s = args.s;
+  const AwMember &m = args.m[blockIdx.y];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int r0 = blockIdx.x * 16;
+  __shared__ __attribute__((aligned(16))) float Xs[16 * AW_XS], Xp[16 * AW_XS];
+  __shared__ __attribute__((aligned(16))) float H0[16 * AW_LS], H1[16 * AW_LS], H2[16 * AW_LS];
+  __shared__ __attribute__((aligned(16))) float E0[16 * AW_LS], E1[16 * AW_LS];
+  __shared__ __attribute__((aligned(16))) float DZ4[16 * AW_DS], MU[16 * AW_DS], GS[16 * AW_DS], EPS[16 * AW_DS];
+  __shared__ int64_t ridx[16];
+  __shared__ float qv[4][16], SD[AW_MAX_A];
+  __shared__ double LSD[AW_MAX_A], SDD[AW_MAX_A], MUD[16 * AW_DS];
+  __shared__ double nll[16];
+  const AwNet &N = s.net[AW_ACTOR];
+
+  aw_gather(s, m, args.step, r0, false, Xs, Xp, nullptr, ridx, tid);
+  for (int i = tid; i < 16 * AW_DS; i += AW_THREADS) DZ4[i] = 0.f, MU[i] = 0.f;
+  if (tid < s.A) {  // sigma_j and log sigma_j, once per slab (Normal.log_prob takes the log of the scale)
+    SD[tid] = aw_std(ldg(m.P + s.o_log_std + tid));
+    LSD[tid] = (double)fminf(fmaxf(ldg(m.P + s.o_log_std + tid), -20.f), 2.f);
+    SDD[tid] = exp(LSD[tid]);
+  }
+
+  // ---- the actor at s, activations kept; pi = clamp(mu + sigma eps_2, -1, 1) (awac:250) ----
+  aw_noise(s, m, args.step, 1, EPS, r0, tid);
+  aw_hidden_kept(s, m, AW_ACTOR, Xp, AW_XS, H0, H1, H2, r0, wave, lane);
+  aw_actor_sample(s, m, H2, Xp, MU, MUD, EPS, r0, wave, lane);
+
+  // ---- v = min Q_i(s, pi), q = min Q_i(s, a) at the critics just updated (awac:251-257) ----
+  for (int c = 0; c < 4; ++c) {
+    aw_hidden(s, m, AW_C1 + (c & 1), m.P, c < 2 ? Xp : Xs, E0, E1, wave, lane);
+    aw_q(s, m, AW_C1 + (c & 1), m.P, E0, qv[c], wave, lane);
+  }
+
+  // ---- w = min(exp((q - v) / lambda), exp_adv_max) (awac:258-261); the head of mean(-w log_prob) ----
+  if (tid < 16) {
+    const int r = tid;
+    const bool real = r0 + r < s.B;
+    const float qmin = fminf(qv[2][r], qv[3][r]), vmin = fminf(qv[0][r], qv[1][r]);
+    const float w = real ? fminf((float)exp((double)((qmin - vmin) / s.lambda)), s.exp_adv_max) : 0.f;
+    const float gbc = w / s.fB;
+    // (the logged loss from the same fp32 values, its own arithmetic in double: log sigma is the clamped _log_std)
+    const double wd = fmin(exp(((double)qmin - (double)vmin) / (double)s.lambda), (double)s.exp_adv_max);
+    double lp = 0.0;  // -log_prob of the row: Normal.log_prob term by term, summed over the actions
+    for (int j = 0; j < s.A; ++j) {
+      const float sd = SD[j], var = sd * sd;
+      const float zg = Xs[r * AW_XS + s.S + j] - MU[r * AW_DS + j];
+      const double zd = (double)Xs[r * AW_XS + s.S + j] - MUD[r * AW_DS + j], sdd = SDD[j];
+      lp += (zd * zd) / (2.0 * sdd * sdd) + LSD[j] + 0.91893853320467274178;
+      const float dmu = real ? -gbc * (zg / var) : 0.f;
+      DZ4[r * AW_DS + j] = dmu;
+      GS[r * AW_DS + j] = real ? gbc * (-(zg * zg) / (var * sd) + 1.f / sd) : 0.f;
+      stg(m.ws + N.pl_dz[3] + (size_t)j * s.BP + r0 + r, dmu);
+    }
+    for (int j = s.A; j < s.AP; ++j) stg(m.ws + N.pl_dz[3] + (size_t)j * s.BP + r0 + r, 0.f);
+    nll[r] = real ? wd * lp : 0.0;
+  }
+  __syncthreads();
+  if (tid < s.AP) {  // the slab's d loss / d sigma_j, rows in order
+    float g = 0.f;
+    if (tid < s.A)
+      for (int r = 0; r < 16; ++r) g += GS[r * AW_DS + tid];
+    stg(m.ws + s.o_lsp + (size_t)blockIdx.x * s.AP + tid, g);
+  }
+  if (tid == 64) {
+    double t = 0.0;
+    for (int i = 0; i < 16; ++i) t += nll[i];
+    stg(reinterpret_cast<double *>(m.ws + s.o_apart) + blockIdx.x, t);
+  }
+  aw_backward(s, m, AW_ACTOR, DZ4, H0, H1, H2, r0, wave, lane);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// launches 2 and 4: dW per tile, Adam, the refreshed copies, the targets, the logged losses
+// ---------------------------------------------------------------------------------------------------
+// The waves of one network, in order: the 16x16 tiles of W1..W4, then 16 bias entries each of b1..b4.
+__host__ __device__ inline int aw_net_waves(const AwShape &s, int n) {
+  int t = 0;
+  for (int l = 0; l < 4; ++l) t += (aw_op(s, n, l) / 16) * (aw_kp(s, n, l) / 16) + aw_op(s, n, l) / 16;
+  return t;
+}
+
+// step_math.h's adam_apply<false> (torch's _single_tensor_adam) with the second moment b2 v + (1 - b2) g g formed in
+// double from the same fp32 constants and rounded once: torch's mul_ and addcmul_ round four times, and on a
+// one-entry tensor (a critic's last bias) nothing averages that out.
+__device__ __forceinline__ void aw_adam(float &p, float &m, float &v, float g, const AdamCoef &c, float neg_step) {
+#pragma clang fp contract(off)
+  m = __builtin_fmaf(g - m, c.one_m_b1, m);
+  v = (float)((double)c.b2 * (double)v + ((double)c.one_m_b2 * (double)g) * (double)g);
+  const float denom = sqrtf(v) / c.bc2_sqrt + c.eps;
+  p = __builtin_fmaf(neg_step, m / denom, p);
+}
+
+// One weight tile of Linear l of net n: rows jt (output features), columns kt (input features).  tn >= 0: the
+// target net that follows this one.
+__device__ __forceinline__ void aw_weight_tile(const AwShape &s, const AwMember &m, int n, int l, int tn, int jt, int kt,
+                                               float neg_step, int lane) {
+  const AwNet &N = s.net[n];
+  const int OUT = aw_out(s, n, l), IN = aw_in(s, n, l), OP = aw_op(s, n, l), KP = aw_kp(s, n, l);
+  const int r = lane & 15, q = lane >> 4;
+  f32x4 accs[4] = {};
+  const float *ap = m.ws + N.pl_dz[l] + (size_t)(16 * jt + r) * s.BP + 4 * q;
+  const float *bp = m.ws + (l == 0 ? s.pl_x : N.pl_h[l - 1]) + (size_t)(16 * kt + r) * s.BP + 4 * q;
+  for (int ks = 0; ks < s.BP / 16; ++ks) aw_mma(ldg16(ap + ks * 16), ldg16(bp + ks * 16), accs);
+  const f32x4 acc = aw_acc(accs);
+  const int k = 16 * kt + r;  // C layout: column = lane & 15, rows 4 q + e
+  float *fwd = m.ws + N.c_w[l], *tfwd = tn >= 0 ? m.ws + s.net[tn].c_w[l] : nullptr;
+  float pv[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int j = 16 * jt + 4 * q + e;
+    float tv = 0.f;
+    pv[e] = 0.f;
+    if (j < OUT && k < IN) {
+      const size_t o = (size_t)N.o_w[l] + (size_t)j * IN + k;
+      float p = ldg(m.P + o), mm = ldg(m.M + o), vv = ldg(m.V + o);
+      aw_adam(p, mm, vv, acc[e], m.coef, neg_step);
+      stg(m.P + o, p), stg(m.M + o, mm), stg(m.V + o, vv);
+      if (m.G) stg(m.G + o, acc[e]);
+      pv[e] = p;
+      if (tn >= 0) {
+        const size_t to = (size_t)s.net[tn].o_w[l] + (size_t)j * IN + k;
+        tv = aw_polyak(s.one_m_tau, s.tau, ldg(m.T + to), p);
+        stg(m.T + to, tv);
+      }
+    }
+    stg(fwd + (size_t)j * KP + k, pv[e]);
+    if (tfwd) stg(tfwd + (size_t)j * KP + k, tv);
+  }
+  if (l > 0) stg16(m.ws + N.t_w[l - 1] + (size_t)k * OP + 16 * jt + 4 * q, make_float4(pv[0], pv[1], pv[2], pv[3]));
+}
+
+// 16 bias entries: db[f] = sum over the batch rows of dz[f][.]
+__device__ __forceinline__ void aw_bias_tile(const AwShape &s, const AwMember &m, int n, int l, int tn, int bt,
+                                             float neg_step, int lane) {
+  const AwNet &N = s.net[n];
+  const int r = lane & 15, q = lane >> 4, f = 16 * bt + r;
+  const float *dz = m.ws + N.pl_dz[l];
+  double gd = 0.0;  // (in double: the rows' terms cancel, and a one-entry bias has no other entries to hide behind)
+  for (int ks = 0; ks < s.BP / 16; ++ks) {
+    const float4 v = __builtin_bit_cast(float4, ldg16(dz + (size_t)f * s.BP + ks * 16 + 4 * q));
+    gd += ((double)v.x + (double)v.y) + ((double)v.z + (double)v.w);
+  }
+  gd += __shfl_xor(gd, 16);
+  gd += __shfl_xor(gd, 32);
+  const float g = (float)gd;
+  if (q == 0 && f < aw_out(s, n, l)) {
+    const size_t o = (size_t)N.o_b[l] + f;
+    float p = ldg(m.P + o), mm = ldg(m.M + o), vv = ldg(m.V + o);
+    aw_adam(p, mm, vv, g, m.coef, neg_step);
+    stg(m.P + o, p), stg(m.M + o, mm), stg(m.V + o, vv);
+    if (m.G) stg(m.G + o, g);
+    if (tn >= 0) {
+      const size_t to = (size_t)s.net[tn].o_b[l] + f;
+      stg(m.T + to, aw_polyak(s.one_m_tau, s.tau, ldg(m.T + to), p));
+    }
+  }
+}
+
+// Wave w of net n's update (w < aw_net_waves).
+__device__ __forceinline__ void aw_update_wave(const AwShape &s, const AwMember &m, int n, int tn, int w, float neg_step,
+                                               int lane) {
+  for (int l = 0; l < 4; ++l) {
+    const int nk = aw_kp(s, n, l) / 16, cnt = (aw_op(s, n, l) / 16) * nk;
+    if (w < cnt) return aw_weight_tile(s, m, n, l, tn, w / nk, w % nk, neg_step, lane);
+    w -= cnt;
+  }
+  for (int l = 0; l < 4; ++l) {
+    const int cnt = aw_op(s, n, l) / 16;
+    if (w < cnt) return aw_bias_tile(s, m, n, l, tn, w, neg_step, lane);
+    w -= cnt;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_awac_critic_update(const AwArgs args) {
+  const AwShape &s = args.s;
+  const AwMember &m = args.m[blockIdx.y];
+  const int lane = threadIdx.x & 63;
+  int w = blockIdx.x * 4 + (threadIdx.x >> 6);  // wave-uniform
+  const int per = aw_net_waves(s, AW_C1);
+  if (w >= 2 * per) return;
+  const int c = w >= per ? 1 : 0;
+  aw_update_wave(s, m, AW_C1 + c, AW_T1 + c, w - c * per, m.coef.neg_step[c], lane);
+}
+
+__global__ __launch_bounds__(256) void k_awac_actor_update(const AwArgs args) {
+  const AwShape &s = args.s;
+  const AwMember &m = args.m[blockIdx.y];
+  const int lane = threadIdx.x & 63;
+  const int w = blockIdx.x * 4 + (threadIdx.x >> 6);  // wave-uniform
+  const int per = aw_net_waves(s, AW_ACTOR);
+  if (w > per) return;
+  if (w < per) return aw_update_wave(s, m, AW_ACTOR, -1, w, m.coef.neg_step[2], lane);
+  const int ns = s.BP / 16;
+  if (lane < s.A) {  // _log_std: sigma = exp(clamp(ls, -20, 2)); the slab sums in slab order
+    double gs = 0.0;
+    for (int i = 0; i < ns; ++i) gs += (double)ldg(m.ws + s.o_lsp + (size_t)i * s.AP + lane);
+    const size_t o = (size_t)s.o_log_std + lane;
+    float p = ldg(m.P + o), mm = ldg(m.M + o), vv = ldg(m.V + o);
+    const float g = (p >= -20.f && p <= 2.f) ? (float)gs * aw_std(p) : 0.f;
+    aw_adam(p, mm, vv, g, m.coef, m.coef.neg_step[2]);
+    stg(m.P + o, p), stg(m.M + o, mm), stg(m.V + o, vv);
+    if (m.G) stg(m.G + o, g);
+  }
+  if (lane == 63 && m.loss) {  // awac:282, 264: mse + mse; the mean of -w log_prob
+    const double *qp = reinterpret_cast<const double *>(m.ws + s.o_qpart);
+    const double *apart = reinterpret_cast<const double *>(m.ws + s.o_apart);
+    double s1 = 0.0, s2 = 0.0, sa = 0.0;
+    for (int i = 0; i < ns; ++i) s1 += ldg(qp + 2 * i), s2 += ldg(qp + 2 * i + 1), sa += ldg(apart + i);
+    stg(m.loss + 2 * args.step, (float)(s1 / (double)s.B) + (float)(s2 / (double)s.B));
+    stg(m.loss + 2 * args.step + 1, (float)(sa / (double)s.B));
+  }
+}
+
+// The copies from the fp32 masters (creation, load_state_dict): blockIdx.y = net * 7 + copy, one thread per
+// element of the padded copy.
+__global__ void k_awac_sync(const AwShape s, const float *P, const float *T, float *ws) {
+  const int n = blockIdx.y / AW_COPIES, kind = blockIdx.y % AW_COPIES;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const AwNet &N = s.net[n];
+  const float *src = n >= AW_T1 ? T : P;
+  const bool tr = kind >= 4;
+  if (tr && n >= AW_T1) return;
+  const int l = tr ? kind - 3 : kind;
+  const int OUT = aw_out(s, n, l), IN = aw_in(s, n, l), OP = aw_op(s, n, l), KP = aw_kp(s, n, l);
+  if (i >= OP * KP) return;
+  const int j = tr ? i % OP : i / KP, k = tr ? i / OP : i % KP;
+  const float v = (j < OUT && k < IN) ? ldg(src + N.o_w[l] + (size_t)j * IN + k) : 0.f;
+  stg(ws + (tr ? N.t_w[l - 1] : N.c_w[l]) + i, v);
+}
+
+}  // namespace iqlhip
+
+using namespace iqlhip;
+
+// ---------------------------------------------------------------------------------------------------
+// entry points (include/iqlhip.h)
+// ---------------------------------------------------------------------------------------------------
+struct iqlhip_awac {
+  AwShape s{};
+  float *P = nullptr, *M = nullptr, *V = nullptr, *G = nullptr, *T = nullptr;
+  float *ws = nullptr;
+  size_t bytes = 0;
+  double lr[3] = {0, 0, 0};  // critic 1, critic 2, actor
+  double beta1 = 0, beta2 = 0, eps = 0;
+  uint64_t seed = 0;
+  int64_t total_it = 0;
+  hipEvent_t ev = nullptr;  // bounds what one call leaves queued
+  bool ev_used = false;
+};
+
+struct iqlhip_awac_group {
+  int n = 0;
+  iqlhip_awac *member[IQLHIP_MAX_GROUP] = {};
+  hipEvent_t ev = nullptr;
+  bool ev_used = false;
+};
+
+// The envelope, checked before any HIP call.
+static int awac_check(const iqlhip_trainer_config *c) {
+  if (!c) return fail(IQLHIP_ERR_INVALID, "null config");
+  if (c->precision != IQLHIP_PREC_FP32)
+    return fail(IQLHIP_ERR_UNSUPPORTED, "AWAC runs at precision fp32 only (the reference has no autocast)");
+  if (c->n_hidden != 3) return fail(IQLHIP_ERR_UNSUPPORTED, "AWAC trains networks of three hidden layers (n_hidden %d)", c->n_hidden);
+  if (c->hidden_dim < 16 || c->hidden_dim > AW_MAX_H || c->hidden_dim % 16)
+    return fail(IQLHIP_ERR_UNSUPPORTED, "hidden_dim %d is not a multiple of 16 in 16..%d", c->hidden_dim, AW_MAX_H);
+  if (c->state_dim < 1 || c->action_dim < 1 || c->batch_size < 1)
+    return fail(IQLHIP_ERR_INVALID, "state_dim, action_dim and batch_size must be positive");
+  if (c->state_dim > AW_MAX_S || c->action_dim > AW_MAX_A)
+    return fail(IQLHIP_ERR_UNSUPPORTED, "state_dim %d > %d or action_dim %d > %d", c->state_dim, AW_MAX_S, c->action_dim,
+                AW_MAX_A);
+  // (the workspace is addressed with 32-bit element offsets: ~20 planes of hidden_dim x batch_size floats)
+  if ((int64_t)c->batch_size > (1 << 16)) return fail(IQLHIP_ERR_UNSUPPORTED, "batch_size %d > 2^16", c->batch_size);
+  if (c->dropout_p > 0.f) return fail(IQLHIP_ERR_UNSUPPORTED, "the AWAC networks have no dropout");
+  return 0;
+}
+
+// Arena offsets: every tensor starts on a 128-byte line.
+static AwShape awac_arena_shape(const iqlhip_trainer_config *c, int64_t *n_params, int64_t *n_target) {
+  AwShape s{};
+  s.S = c->state_dim, s.A = c->action_dim, s.B = c->batch_size, s.H = c->hidden_dim;
+  s.SP = round_up(s.S, 16), s.AP = round_up(s.A, 16), s.BP = round_up(s.B, 16), s.XP = round_up(s.S + s.A, 16);
+  s.row_stride = iqlhip_replay_row_stride(s.S, s.A), s.next_off = iqlhip_replay_next_offset(s.S, s.A);
+  for (int n = 0; n < AW_NETS; ++n) {
+    AwNet &N = s.net[n];
+    const bool actor = n == AW_ACTOR;
+    N.K1 = actor ? s.S : s.S + s.A, N.K1P = actor ? s.SP : s.XP, N.OUT = actor ? s.A : 1, N.OP = actor ? s.AP : 16;
+  }
+  int64_t off = 0;
+  const auto take = [&](int64_t n) {
+    const int64_t o = off;
+    off += (n + 31) / 32 * 32;
+    return (int)o;
+  };
+  const auto lay = [&](int n) {
+    for (int l = 0; l < 4; ++l) {
+      s.net[n].o_w[l] = take((int64_t)aw_out(s, n, l) * aw_in(s, n, l));
+      s.net[n].o_b[l] = take(aw_out(s, n, l));
+    }
+  };
+  lay(AW_ACTOR);
+  s.o_log_std = take(s.A);
+  const int64_t critics = off;
+  lay(AW_C1), lay(AW_C2);
+  if (n_params) *n_params = off;
+  if (n_target) *n_target = off - critics;
+  for (int t = 0; t < 2; ++t)
+    for (int l = 0; l < 4; ++l) {
+      s.net[AW_T1 + t].o_w[l] = s.net[AW_C1 + t].o_w[l] - (int)critics;
+      s.net[AW_T1 + t].o_b[l] = s.net[AW_C1 + t].o_b[l] - (int)critics;
+    }
+  return s;
+}
+
+// The workspace of one trainer (element offsets, floats).  Everything is zero at creation; padding is only
+// ever rewritten with zeros.
+static size_t awac_plan(AwShape &s) {
+  size_t off = 0;
+  const auto take = [&](size_t n) {
+    const size_t o = off;
+    off += (n + 63) / 64 * 64;  // 256-byte blocks
+    return (int)o;
+  };
+  for (int n = 0; n < AW_NETS; ++n) {
+    AwNet &N = s.net[n];
+    for (int l = 0; l < 4; ++l) N.c_w[l] = take((size_t)aw_op(s, n, l) * aw_kp(s, n, l));
+    if (n >= AW_T1) continue;
+    for (int l = 1; l < 4; ++l) N.t_w[l - 1] = take((size_t)aw_kp(s, n, l) * aw_op(s, n, l));
+    for (int l = 0; l < 3; ++l) N.pl_h[l] = take((size_t)s.H * s.BP);
+    for (int l = 0; l < 4; ++l) N.pl_dz[l] = take((size_t)aw_op(s, n, l) * s.BP);
+  }
+  s.pl_x = take((size_t)s.XP * s.BP);
+  s.o_eps = take((size_t)2 * s.B * s.A);
+  s.o_qpart = take((size_t)4 * (s.BP / 16));  // doubles [BP / 16][2]
+  s.o_apart = take((size_t)2 * (s.BP / 16));  // doubles [BP / 16]
+  s.o_lsp = take((size_t)(s.BP / 16) * s.AP);
+  return off * sizeof(float);
+}
+
+extern "C" int iqlhip_awac_arena_layout(const iqlhip_trainer_config *cfg, int64_t offsets[25], int64_t *n_params,
+                                        int64_t *n_target) {
+  if (!offsets || !n_params || !n_target) return fail(IQLHIP_ERR_INVALID, "null argument");
+  if (int rc = awac_check(cfg)) return rc;
+  const AwShape s = awac_arena_shape(cfg, n_params, n_target);
+  int i = 0;
+  for (int n = AW_ACTOR; n <= AW_C2; ++n) {
+    for (int l = 0; l < 4; ++l) offsets[i++] = s.net[n].o_w[l], offsets[i++] = s.net[n].o_b[l];
+    if (n == AW_ACTOR) offsets[i++] = s.o_log_std;
+  }
+  return 0;
+}
+
+static int awac_sync(iqlhip_awac *t, hipStream_t st) {
+  const int n = AW_MAX_H * (t->s.XP > t->s.H ? t->s.XP : t->s.H);
+  hipLaunchKernelGGL(k_awac_sync, dim3((n + 255) / 256, AW_NETS * AW_COPIES), dim3(256), 0, st, t->s, (const float *)t->P,
+                     (const float *)t->T, t->ws);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+extern "C" int iqlhip_awac_destroy(iqlhip_awac *t) {
+  if (!t) return 0;
+  if (t->ws) {
+    (void)hipDeviceSynchronize();
+    (void)hipFree(t->ws);
+  }
+  if (t->ev) (void)hipEventDestroy(t->ev);
+  delete t;
+  return 0;
+}
+
+extern "C" int iqlhip_awac_create(iqlhip_awac **out, const iqlhip_trainer_config *cfg, double tau, float exp_adv_max,
+                                  const iqlhip_arenas *arenas) {
+  if (!out || !arenas) return fail(IQLHIP_ERR_INVALID, "null argument");
+  if (int rc = awac_check(cfg)) return rc;
+  if (!arenas->params || !arenas->exp_avg || !arenas->exp_avg_sq || !arenas->target) return fail(IQLHIP_ERR_INVALID, "null arena");
+  if (!(cfg->beta > 0.f) || !(exp_adv_max > 0.f)) return fail(IQLHIP_ERR_INVALID, "awac_lambda and exp_adv_max must be positive");
+  if (!(tau >= 0.0 && tau <= 1.0)) return fail(IQLHIP_ERR_INVALID, "tau must lie in [0, 1]");
+  iqlhip_awac *t = new (std::nothrow) iqlhip_awac;
+  if (!t) return fail(IQLHIP_ERR_NOMEM, "out of host memory");
+  t->s = awac_arena_shape(cfg, nullptr, nullptr);
+  AwShape &s = t->s;
+  // awac:215: the Python doubles tau and 1 - tau, each rounded to fp32 once (cfg->tau is already fp32: 1 - it is another number)
+  s.gamma = cfg->discount, s.tau = (float)tau, s.one_m_tau = (float)(1.0 - tau);
+  s.lambda = cfg->beta, s.exp_adv_max = exp_adv_max;
+  s.two_over_B = (float)(2.0 / (double)s.B), s.fB = (float)s.B;
+  t->P = arenas->params, t->M = arenas->exp_avg, t->V = arenas->exp_avg_sq, t->G = arenas->grads, t->T = arenas->target;
+  t->lr[0] = cfg->lr_q, t->lr[1] = cfg->lr_v, t->lr[2] = cfg->lr_actor;
+  t->beta1 = cfg->adam_beta1, t->beta2 = cfg->adam_beta2, t->eps = cfg->adam_eps, t->seed = cfg->seed;
+  t->bytes = awac_plan(s);
+  void *mem = nullptr;
+  if (hipMalloc(&mem, t->bytes) != hipSuccess) {
+    iqlhip_awac_destroy(t);
+    return fail(IQLHIP_ERR_NOMEM, "hipMalloc of %zu workspace bytes failed", t->bytes);
+  }
+  t->ws = static_cast<float *>(mem);
+  int rc = 0;
+  if (hipMemset(t->ws, 0, t->bytes) != hipSuccess) rc = fail(IQLHIP_ERR_HIP, "hipMemset of the workspace failed");
+  if (!rc) rc = awac_sync(t, nullptr);
+  if (!rc && hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(IQLHIP_ERR_HIP, "building the weight copies failed");
+  if (rc) {
+    iqlhip_awac_destroy(t);
+    return rc;
+  }
+  *out = t;
+  return 0;
+}
+
+extern "C" int iqlhip_awac_sync_weights(iqlhip_awac *t, void *stream) {
+  if (!t) return fail(IQLHIP_ERR_INVALID, "null trainer");
+  return awac_sync(t, (hipStream_t)stream);
+}
+
+extern "C" int iqlhip_awac_set_step(iqlhip_awac *t, int64_t total_it) {
+  if (!t || total_it < 0) return fail(IQLHIP_ERR_INVALID, "null trainer or negative step");
+  t->total_it = total_it;
+  return 0;
+}
+
+extern "C" int iqlhip_awac_set_lr(iqlhip_awac *t, double lr_actor, double lr_critic_1, double lr_critic_2) {
+  if (!t || !(lr_actor >= 0) || !(lr_critic_1 >= 0) || !(lr_critic_2 >= 0))
+    return fail(IQLHIP_ERR_INVALID, "null trainer or negative lr");
+  t->lr[0] = lr_critic_1, t->lr[1] = lr_critic_2, t->lr[2] = lr_actor;
+  return 0;
+}
+
+extern "C" int iqlhip_awac_copy_out(iqlhip_awac *t, int32_t which, float *dst, void *stream) {
+  if (!t || !dst) return fail(IQLHIP_ERR_INVALID, "null argument");
+  const AwShape &s = t->s;
+  const float *src = nullptr;
+  size_t n = 0;
+  if (which == 0) {
+    src = t->ws + s.o_eps, n = (size_t)2 * s.B * s.A;
+  } else if (which >= 1 && which <= AW_NETS * AW_COPIES) {
+    const int net = (which - 1) / AW_COPIES, kind = (which - 1) % AW_COPIES, l = kind >= 4 ? kind - 3 : kind;
+    if (kind >= 4 && net >= AW_T1) return fail(IQLHIP_ERR_INVALID, "the targets have no transposed copies");
+    src = t->ws + (kind >= 4 ? s.net[net].t_w[l - 1] : s.net[net].c_w[l]);
+    n = (size_t)aw_op(s, net, l) * aw_kp(s, net, l);
+  } else {
+    return fail(IQLHIP_ERR_INVALID, "which must be in 0..%d", AW_NETS * AW_COPIES);
+  }
+  HIP_TRY(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return 0;
+}
+
+// n_steps steps of the members m[0..n): four launches per step for all of them.
+static int awac_run(iqlhip_awac *const *mem, int n, hipEvent_t *ev, bool *ev_used, const iqlhip_replay_view *views,
+                    int64_t n_steps, const int64_t *const *idx, const float *const *eps, float *const *losses,
+                    hipStream_t st) {
+  if (!views || !idx) return fail(IQLHIP_ERR_INVALID, "null views or indices");
+  if (n_steps < 0) return fail(IQLHIP_ERR_INVALID, "n_steps must be >= 0");
+  AwArgs a{};
+  a.s = mem[0]->s;
+  for (int k = 0; k < n; ++k) {
+    const iqlhip_awac *t = mem[k];
+    const iqlhip_replay_view &v = views[k];
+    if (!idx[k]) return fail(IQLHIP_ERR_INVALID, "member %d: AWAC takes its indices from the caller", k);
+    if (!v.rows || v.n_rows < 1) return fail(IQLHIP_ERR_INVALID, "member %d: empty replay view", k);
+    if (v.state_dim != t->s.S || v.action_dim != t->s.A || v.row_stride != t->s.row_stride)
+      return fail(IQLHIP_ERR_INVALID, "member %d: the replay view does not have the trainer's dims", k);
+    AwMember &m = a.m[k];
+    m.P = t->P, m.M = t->M, m.V = t->V, m.G = t->G, m.T = t->T, m.ws = t->ws;
+    m.rows = v.rows, m.n_rows = v.n_rows, m.idx = idx[k], m.eps = eps ? eps[k] : nullptr;
+    m.loss = losses ? losses[k] : nullptr, m.seed = t->seed, m.step0 = t->total_it;
+  }
+  const int slabs = a.s.BP / 16;
+  const dim3 g1(slabs, n), g2((2 * aw_net_waves(a.s, AW_C1) + 3) / 4, n), g4((aw_net_waves(a.s, AW_ACTOR) + 1 + 3) / 4, n);
+  for (int64_t i = 0; i < n_steps; ++i) {
+    a.step = i;
+    for (int k = 0; k < n; ++k) {
+      const iqlhip_awac *t = mem[k];
+      a.m[k].coef = make_adam_coef(t->beta1, t->beta2, t->eps, t->lr[0], t->lr[1], 0.0, 1, t->total_it + i + 1);
+      a.m[k].coef.neg_step[2] =
+          make_adam_coef(t->beta1, t->beta2, t->eps, t->lr[2], 0.0, 0.0, 1, t->total_it + i + 1).neg_step[0];
+    }
+    hipLaunchKernelGGL(k_awac_critic_fwd_bwd, g1, dim3(AW_THREADS), 0, st, a);
+    hipLaunchKernelGGL(k_awac_critic_update, g2, dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_awac_actor_fwd_bwd, g1, dim3(AW_THREADS), 0, st, a);
+    hipLaunchKernelGGL(k_awac_actor_update, g4, dim3(256), 0, st, a);
+    if ((i & 511) == 511) {  // at most ~2 x 512 steps are ever queued ahead of the device
+      HIP_TRY(hipGetLastError());
+      if (!*ev) HIP_TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+      if (*ev_used) HIP_TRY(hipEventSynchronize(*ev));
+      HIP_TRY(hipEventRecord(*ev, st));
+      *ev_used = true;
+    }
+  }
+  HIP_TRY(hipGetLastError());
+  for (int k = 0; k < n; ++k) mem[k]->total_it += n_steps;
+  return 0;
+}
+
+extern "C" int iqlhip_awac_group_create(iqlhip_awac_group **out, iqlhip_awac *const *members, int32_t n) {
+  if (!out || !members) return fail(IQLHIP_ERR_INVALID, "null argument");
+  if (n < 1 || n > IQLHIP_MAX_GROUP) return fail(IQLHIP_ERR_UNSUPPORTED, "a group has 1..%d members (got %d)", IQLHIP_MAX_GROUP, n);
+  for (int k = 0; k < n; ++k) {
+    if (!members[k]) return fail(IQLHIP_ERR_INVALID, "member %d is null", k);
+    const AwShape &a = members[0]->s, &b = members[k]->s;
+    if (a.S != b.S || a.A != b.A || a.B != b.B || a.H != b.H || a.gamma != b.gamma || a.tau != b.tau || a.lambda != b.lambda ||
+        a.exp_adv_max != b.exp_adv_max)
+      return fail(IQLHIP_ERR_INVALID, "member %d: the members of a group share dims, width, batch size, gamma, tau, "
+                                      "awac_lambda and exp_adv_max", k);
+    for (int j = 0; j < k; ++j)
+      if (members[j] == members[k]) return fail(IQLHIP_ERR_INVALID, "member %d appears twice", k);
+  }
+  iqlhip_awac_group *g = new (std::nothrow) iqlhip_awac_group;
+  if (!g) return fail(IQLHIP_ERR_NOMEM, "out of host memory");
+  g->n = n;
+  for (int k = 0; k < n; ++k) g->member[k] = members[k];
+  *out = g;
+  return 0;
+}
+
+extern "C" int iqlhip_awac_group_destroy(iqlhip_awac_group *g) {
+  if (!g) return 0;
+  if (g->ev) {
+    (void)hipEventSynchronize(g->ev);
+    (void)hipEventDestroy(g->ev);
+  }
+  delete g;
+  return 0;
+}
+
+extern "C" int iqlhip_awac_group_train_steps(iqlhip_awac_group *g, const iqlhip_replay_view *views, int64_t n_steps,
+                                             const int64_t *const *idx, const float *const *eps, float *const *losses_out,
+                                             void *stream) {
+  if (!g) return fail(IQLHIP_ERR_INVALID, "null group");
+  return awac_run(g->member, g->n, &g->ev, &g->ev_used, views, n_steps, idx, eps, losses_out, (hipStream_t)stream);
+}
+
+extern "C" int iqlhip_awac_train_steps(iqlhip_awac *t, const iqlhip_replay_view *view, int64_t n_steps, const int64_t *idx,
+                                       const float *eps, float *losses_out, void *stream) {
+  if (!t) return fail(IQLHIP_ERR_INVALID, "null trainer");
+  return awac_run(&t, 1, &t->ev, &t->ev_used, view, n_steps, &idx, eps ? &eps : nullptr,
+                  losses_out ? &losses_out : nullptr, (hipStream_t)stream);
+}
