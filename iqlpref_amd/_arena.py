@@ -1,13 +1,14 @@
-"""What an arena-backed trainer is, once (``iql.ImplicitQLearning``, ``minari_bc.BC``): parameters, gradients and
-Adam moments are views of flat fp32 arenas that the library borrows, behind ``nn.Parameter`` objects and
-``optimizer.state`` entries that stay what torch expects, and one native handle per batch size that lives and dies
-by one set of rules.  The free functions are pure torch: no library, any device.
+"""What an arena-backed trainer is, once (``iql.ImplicitQLearning``, ``minari_bc.BC``,
+``awac.AdvantageWeightedActorCritic``): parameters, gradients and Adam moments are views of flat fp32 arenas that the
+library borrows, behind ``nn.Parameter`` objects and ``optimizer.state`` entries that stay what torch expects, and one
+native handle per batch size that lives and dies by one set of rules.  The free functions are pure torch: no library,
+any device.
 """
 from typing import List, Optional, Sequence, Tuple
 
 import torch
 
-from ._lib import check, stream_ptr
+from ._lib import ReplayView, check, ptr, stream_ptr
 
 Views = List[Tuple[torch.nn.Parameter, int]]
 INDICES = "indices must be an int64 device tensor [n_steps, batch_size]"
@@ -161,3 +162,29 @@ class ArenaTrainer:
         if self._handle is not None:
             with torch.cuda.device(self._dev):
                 check(self._entry("sync_weights")(self._handle, stream_ptr()))
+
+    # -- steps ---------------------------------------------------------------- #
+    def _after_steps(self, n: int):
+        """``n`` steps were queued: the count and the optimisers' step counters follow.  (A family with host-side
+        schedules overrides this.)"""
+        self.total_it += n
+        self._bind_optimizer_state()
+
+    def _batch_as_rows(self, message: str, state, action, reward=None, done=None, next_state=None):
+        """An explicit batch laid out as replay rows of its own (include/iqlhip.h: s | a | r | d ... s'; a trainer
+        that reads only s and a passes only those; needs ``_state_dim`` / ``_action_dim``).  Returns (the view over
+        the rows, the indices [1, n] that step them once in order, the rows: keep them until the step is queued).
+        RuntimeError(message) when the shapes are not the networks'."""
+        n, S, A = state.shape[0], self._state_dim, self._action_dim
+        if tuple(state.shape) != (n, S) or tuple(action.shape) != (n, A) or \
+                (next_state is not None and tuple(next_state.shape) != (n, S)):
+            raise RuntimeError(message)
+        stride = self._lib.iqlhip_replay_row_stride(S, A)
+        rows = torch.zeros((n, stride), dtype=torch.float32, device=self._dev)
+        rows[:, :S], rows[:, S:S + A] = state, action
+        if next_state is not None:
+            nxt = self._lib.iqlhip_replay_next_offset(S, A)
+            rows[:, nxt:nxt + S] = next_state
+            rows[:, S + A], rows[:, S + A + 1] = reward.reshape(n), done.reshape(n)
+        view = ReplayView(ptr(rows), n, stride, S, A, 0)
+        return view, torch.arange(n, dtype=torch.int64, device=self._dev)[None], rows

@@ -41,7 +41,7 @@ from . import custom_offline as _co
 from . import distributed as D
 from ._lib import check, ptr, stream_ptr
 from .iql import load_config_for, compute_mean_std, normalize_states, set_seed, mlp_forward_f32  # noqa: F401
-from .multi import DeviceGroup, _per_member
+from .multi import ArenaGroup
 from .train import wrap_env  # noqa: F401  (awac:348-357)
 
 TensorBatch = List[torch.Tensor]
@@ -314,10 +314,6 @@ class AdvantageWeightedActorCritic(_arena.ArenaTrainer):
             check(self._lib.iqlhip_awac_set_lr(self._handle, *lrs))
             self._lr_sent = lrs
 
-    def _after_steps(self, n: int):
-        self.total_it += n
-        self._bind_optimizer_state()
-
     def _check_eps(self, eps, n_steps: int, batch_size: int) -> Optional[torch.Tensor]:
         if eps is None:
             return None
@@ -351,16 +347,8 @@ class AdvantageWeightedActorCritic(_arena.ArenaTrainer):
         """awac:301-310 on an explicit batch [s, a, r, s', d]: the rows are laid out as replay rows of their own and
         stepped once in order.  ``eps``: [2, batch_size, action_dim] or None."""
         s, a, r, s2, d = [t.detach().to(device=self._dev, dtype=torch.float32) for t in batch]
-        n, S, A = s.shape[0], self._state_dim, self._action_dim
-        if tuple(s.shape) != (n, S) or tuple(a.shape) != (n, A) or tuple(s2.shape) != (n, S):
-            raise RuntimeError("batch shapes do not match the networks")
-        stride, nxt = self._lib.iqlhip_replay_row_stride(S, A), self._lib.iqlhip_replay_next_offset(S, A)
-        rows = torch.zeros((n, stride), dtype=torch.float32, device=self._dev)
-        rows[:, :S], rows[:, S:S + A], rows[:, nxt:nxt + S] = s, a, s2
-        rows[:, S + A], rows[:, S + A + 1] = r.reshape(n), d.reshape(n)
-        view = _lib.ReplayView(ptr(rows), n, stride, S, A, 0)
-        idx = torch.arange(n, dtype=torch.int64, device=self._dev)[None]
-        losses = self._steps_on_view(view, 1, n, idx, None if eps is None else eps[None], True).cpu()
+        view, idx, _rows = self._batch_as_rows("batch shapes do not match the networks", s, a, r, d, s2)
+        losses = self._steps_on_view(view, 1, s.shape[0], idx, None if eps is None else eps[None], True).cpu()
         return {"critic_loss": losses[0, 0].item(), "actor_loss": losses[0, 1].item()}
 
     # -- checkpoints (awac:312-322) ------------------------------------------ #
@@ -379,30 +367,11 @@ class AdvantageWeightedActorCritic(_arena.ArenaTrainer):
         self.sync_weights()
 
 
-class AWACGroup(DeviceGroup):
+class AWACGroup(ArenaGroup):
     """1..16 ``AdvantageWeightedActorCritic`` trainers of one shape stepped by the same four launches per step
     (``iqlhip_awac_group_*``): the part of ``multi.SeedGroup``'s surface ``_offline_loop.run`` uses, plus ``eps``.
     Every member is bit-identical to stepping it alone."""
-
-    def __init__(self, trainers: Sequence[AdvantageWeightedActorCritic]):
-        if not 1 <= len(trainers) <= _lib.MAX_GROUP:
-            raise NotImplementedError(f"a group has 1..{_lib.MAX_GROUP} members")
-        if len({id(t) for t in trainers}) != len(trainers) or len({t._dev for t in trainers}) != 1:
-            raise ValueError("the members of a group are distinct trainers on one device")
-        self.trainers = list(trainers)
-        self._lib, self._dev = trainers[0]._lib, trainers[0]._dev
-
-    def __len__(self):
-        return len(self.trainers)
-
-    def _create_group(self, batch_size: int, handles, n: int):
-        g = C.c_void_p()
-        check(self._lib.iqlhip_awac_group_create(C.byref(g), handles, n))
-        return g
-
-    def _destroy_group(self, group):
-        torch.cuda.synchronize(self._dev)
-        self._lib.iqlhip_awac_group_destroy(group)
+    _ENTRY, _LOSSES = "iqlhip_awac", 2
 
     def train_steps(self, replay, n_steps: int, batch_size: int, *, indices: Sequence[torch.Tensor],
                     eps: Optional[Sequence[Optional[torch.Tensor]]] = None, return_losses: bool = False):
@@ -410,26 +379,11 @@ class AWACGroup(DeviceGroup):
         per member, ``indices`` one tensor per member, ``eps`` None or one entry (a tensor or None) per member.
         Returns the list of [n_steps, 2] loss tensors when ``return_losses``."""
         K = len(self.trainers)
-        bufs, idx, _, _ = _per_member(K, replay, indices, None, None)
         eps = [None] * K if eps is None else list(eps)
         if len(eps) != K:
             raise ValueError("eps: one entry per trainer")
-        idx = [_arena.check_indices(i, n_steps, batch_size, True) for i in idx]
-        eps = [t._check_eps(e, n_steps, batch_size) for t, e in zip(self.trainers, eps)]
-        self._ensure_group(batch_size)
-        for t in self.trainers:
-            t._refresh_lrs()
-        losses = [torch.empty((n_steps, 2), dtype=torch.float32, device=self._dev) for _ in range(K)] \
-            if return_losses else None
-        views = (_lib.ReplayView * K)(*[b.view() for b in bufs])
-        parr = lambda ts: (C.c_void_p * K)(*[None if t is None else t.data_ptr() for t in ts])
-        with torch.cuda.device(self._dev):
-            check(self._lib.iqlhip_awac_group_train_steps(
-                self._group, views, n_steps, parr(idx), parr(eps) if any(e is not None for e in eps) else None,
-                parr(losses) if return_losses else None, stream_ptr()))
-        for t in self.trainers:
-            t._after_steps(n_steps)
-        return losses
+        check_eps = lambda: [t._check_eps(e, n_steps, batch_size) for t, e in zip(self.trainers, eps)]
+        return self._group_steps(replay, n_steps, batch_size, indices, return_losses, extra=(check_eps,))
 
 
 def stepper(trainers: Sequence[AdvantageWeightedActorCritic]) -> AWACGroup:

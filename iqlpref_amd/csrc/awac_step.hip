@@ -31,6 +31,9 @@
 // online.hip draws them: block (row * 8 + column / 4, step lo, step hi, STREAM_AWAC_NEXT | STREAM_AWAC_PI), words
 // (x, y) and (z, w) each one pair, evaluated in double.  Either way the eps of the last step stay in the
 // workspace (iqlhip_awac_copy_out).
+//
+// The slab walk, the tile updates and the host side are slab_step.h's, with this family's policies: four MFMA
+// chains per tile added pairwise (FourChains), the bias gradient summed in double (SumDouble), aw_adam below.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -40,6 +43,7 @@
 #include "common.h"
 #include "errors.h"
 #include "host_plan.h"
+#include "slab_step.h"
 #include "step_math.h"
 
 namespace iqlhip {
@@ -103,35 +107,8 @@ static_assert(sizeof(AwArgs) <= 4096, "the argument block travels by value");
 // ---------------------------------------------------------------------------------------------------
 // pieces of a slab's walk
 // ---------------------------------------------------------------------------------------------------
-// One Linear layer of the slab, forward or backward: tile t (features 16 t .. 16 t + 16) of out[16][OP] =
-// act[16][K] x Wm^T, Wm row-major [OP][K]; the tiles go round the sixteen waves.
-// Exact fp32 MFMA (common.h, Prec<false>) on four accumulators, one per component of the 16-byte fragments, added
-// pairwise at the end: four independent chains a quarter as long as one -- a quarter of the latency between
-// dependent MFMAs, and the rounding error of a four-way pairwise sum instead of a sequential one.
-__device__ __forceinline__ void aw_mma(const uint4 &a, const uint4 &b, f32x4 (&acc)[4]) {
-  const float4 af = __builtin_bit_cast(float4, a), bf = __builtin_bit_cast(float4, b);
-  acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(af.x, bf.x, acc[0], 0, 0, 0);
-  acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(af.y, bf.y, acc[1], 0, 0, 0);
-  acc[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(af.z, bf.z, acc[2], 0, 0, 0);
-  acc[3] = __builtin_amdgcn_mfma_f32_16x16x4f32(af.w, bf.w, acc[3], 0, 0, 0);
-}
-__device__ __forceinline__ f32x4 aw_acc(const f32x4 (&acc)[4]) { return (acc[0] + acc[1]) + (acc[2] + acc[3]); }
-
-template <class Epilogue>
-__device__ __forceinline__ void aw_layer(const float *act, int act_stride, const float *Wm, int K, int n_tiles,
-                                         int wave, int lane, Epilogue &&ep) {
-  const int r = lane & 15, q = lane >> 4;
-  for (int t = wave; t < n_tiles; t += AW_WAVES) {
-    const int f = 16 * t + r;
-    f32x4 acc[4] = {};
-    for (int ks = 0; ks < K / 16; ++ks) {
-      const uint4 a = *reinterpret_cast<const uint4 *>(act + r * act_stride + ks * 16 + 4 * q);
-      const uint4 b = ldg16(Wm + (size_t)f * K + ks * 16 + 4 * q);
-      aw_mma(a, b, acc);
-    }
-    ep(f, 4 * q, aw_acc(acc));  // (feature, first of 4 rows, values)
-  }
-}
+// A Linear layer of the slab is slab_layer<FourChains, AW_WAVES>: its n_tiles tiles of 16 features go round the
+// sixteen waves (hidden layers: H / 16 of them; a critic's head: one; the actor's head: AP / 16).
 
 // A standard normal of (row, column) of the step: Box-Muller in double on one Philox block per four columns.
 __device__ __forceinline__ float aw_normal(uint64_t seed, int64_t step, int row, int c, uint32_t stream) {
@@ -178,11 +155,11 @@ __device__ __forceinline__ void aw_hidden(const AwShape &s, const AwMember &m, i
       for (int e = 0; e < 4; ++e) dst[(row + e) * AW_LS + f] = fmaxf(z[e] + b, 0.f);
     };
   };
-  aw_layer(in, AW_XS, m.ws + N.c_w[0], N.K1P, ht, wave, lane, relu_to(Ha, N.o_b[0]));
+  slab_layer<FourChains, AW_WAVES>(in, AW_XS, m.ws + N.c_w[0], N.K1P, ht, wave, lane, relu_to(Ha, N.o_b[0]));
   __syncthreads();
-  aw_layer(Ha, AW_LS, m.ws + N.c_w[1], s.H, ht, wave, lane, relu_to(Hb, N.o_b[1]));
+  slab_layer<FourChains, AW_WAVES>(Ha, AW_LS, m.ws + N.c_w[1], s.H, ht, wave, lane, relu_to(Hb, N.o_b[1]));
   __syncthreads();
-  aw_layer(Hb, AW_LS, m.ws + N.c_w[2], s.H, ht, wave, lane, relu_to(Ha, N.o_b[2]));
+  slab_layer<FourChains, AW_WAVES>(Hb, AW_LS, m.ws + N.c_w[2], s.H, ht, wave, lane, relu_to(Ha, N.o_b[2]));
   __syncthreads();
 }
 
@@ -190,7 +167,7 @@ __device__ __forceinline__ void aw_hidden(const AwShape &s, const AwMember &m, i
 __device__ __forceinline__ void aw_q(const AwShape &s, const AwMember &m, int n, const float *arena, const float *h3,
                                      float *q, int wave, int lane) {
   const AwNet &N = s.net[n];
-  aw_layer(h3, AW_LS, m.ws + N.c_w[3], s.H, 1, wave, lane, [&](int f, int row, f32x4 z) {
+  slab_layer<FourChains, AW_WAVES>(h3, AW_LS, m.ws + N.c_w[3], s.H, 1, wave, lane, [&](int f, int row, f32x4 z) {
     if (f != 0) return;
     const float b = ldg(arena + N.o_b[3]);
 #pragma unroll
@@ -210,14 +187,14 @@ __device__ __forceinline__ void aw_hidden_kept(const AwShape &s, const AwMember 
       const float b = ldg(m.P + ob + f);
 #pragma unroll
       for (int e = 0; e < 4; ++e) z[e] = fmaxf(z[e] + b, 0.f), dst[(row + e) * AW_LS + f] = z[e];
-      stg16(m.ws + plane + (size_t)f * s.BP + r0 + row, make_float4(z[0], z[1], z[2], z[3]));
+      slab_plane4(m.ws + plane, s.BP, f, r0 + row, z);
     };
   };
-  aw_layer(in, in_stride, m.ws + N.c_w[0], N.K1P, ht, wave, lane, keep(H0, N.o_b[0], N.pl_h[0]));
+  slab_layer<FourChains, AW_WAVES>(in, in_stride, m.ws + N.c_w[0], N.K1P, ht, wave, lane, keep(H0, N.o_b[0], N.pl_h[0]));
   __syncthreads();
-  aw_layer(H0, AW_LS, m.ws + N.c_w[1], s.H, ht, wave, lane, keep(H1, N.o_b[1], N.pl_h[1]));
+  slab_layer<FourChains, AW_WAVES>(H0, AW_LS, m.ws + N.c_w[1], s.H, ht, wave, lane, keep(H1, N.o_b[1], N.pl_h[1]));
   __syncthreads();
-  aw_layer(H1, AW_LS, m.ws + N.c_w[2], s.H, ht, wave, lane, keep(H2, N.o_b[2], N.pl_h[2]));
+  slab_layer<FourChains, AW_WAVES>(H1, AW_LS, m.ws + N.c_w[2], s.H, ht, wave, lane, keep(H2, N.o_b[2], N.pl_h[2]));
   __syncthreads();
 }
 
@@ -235,14 +212,14 @@ __device__ __forceinline__ void aw_backward(const AwShape &s, const AwMember &m,
         g[e] = h[(row + e) * AW_LS + f] > 0.f ? g[e] : 0.f;
         if (keep) h[(row + e) * AW_LS + f] = g[e];
       }
-      stg16(m.ws + plane + (size_t)f * s.BP + r0 + row, make_float4(g[0], g[1], g[2], g[3]));
+      slab_plane4(m.ws + plane, s.BP, f, r0 + row, g);
     };
   };
-  aw_layer(DZ4, AW_DS, m.ws + N.t_w[2], N.OP, ht, wave, lane, masked(H2, N.pl_dz[2], true));
+  slab_layer<FourChains, AW_WAVES>(DZ4, AW_DS, m.ws + N.t_w[2], N.OP, ht, wave, lane, masked(H2, N.pl_dz[2], true));
   __syncthreads();
-  aw_layer(H2, AW_LS, m.ws + N.t_w[1], s.H, ht, wave, lane, masked(H1, N.pl_dz[1], true));
+  slab_layer<FourChains, AW_WAVES>(H2, AW_LS, m.ws + N.t_w[1], s.H, ht, wave, lane, masked(H1, N.pl_dz[1], true));
   __syncthreads();
-  aw_layer(H1, AW_LS, m.ws + N.t_w[0], s.H, ht, wave, lane, masked(H0, N.pl_dz[0], false));
+  slab_layer<FourChains, AW_WAVES>(H1, AW_LS, m.ws + N.t_w[0], s.H, ht, wave, lane, masked(H0, N.pl_dz[0], false));
   __syncthreads();
 }
 
@@ -250,14 +227,7 @@ __device__ __forceinline__ void aw_backward(const AwShape &s, const AwMember &m,
 // X2 = (s' | 0) or (s | 0) (`next`), rd = reward and done (or null).  Ends behind a barrier.
 __device__ __forceinline__ void aw_gather(const AwShape &s, const AwMember &m, int64_t step, int r0, bool next, float *X,
                                           float *X2, float *rd, int64_t *ridx, int tid) {
-  if (tid < 16) {
-    int64_t i = -1;
-    if (r0 + tid < s.B) {
-      i = ldg(m.idx + step * s.B + r0 + tid);
-      i = i < 0 ? 0 : (i >= m.n_rows ? m.n_rows - 1 : i);  // (an index outside the buffer must not leave it)
-    }
-    ridx[tid] = i;
-  }
+  slab_row_indices(m.idx, step, s.B, r0, m.n_rows, ridx, tid);
   __syncthreads();
   for (int i = tid; i < 16 * s.XP; i += AW_THREADS) {
     const int r = i / s.XP, c = i - r * s.XP;
@@ -295,7 +265,7 @@ __device__ __forceinline__ void aw_noise(const AwShape &s, const AwMember &m, in
 __device__ __forceinline__ void aw_actor_sample(const AwShape &s, const AwMember &m, const float *H2, float *X2, float *MU,
                                                 double *MUD, const float *EPS, int r0, int wave, int lane) {
   const AwNet &N = s.net[AW_ACTOR];
-  aw_layer(H2, AW_LS, m.ws + N.c_w[3], s.H, s.AP / 16, wave, lane, [&](int j, int row, f32x4 z) {
+  slab_layer<FourChains, AW_WAVES>(H2, AW_LS, m.ws + N.c_w[3], s.H, s.AP / 16, wave, lane, [&](int j, int row, f32x4 z) {
     if (j >= s.A) return;
     const float b = ldg(m.P + N.o_b[3] + j);
     const float sd = aw_std(ldg(m.P + s.o_log_std + j));
@@ -347,7 +317,7 @@ __global__ __launch_bounds__(AW_THREADS) void k_awac_critic_fwd_bwd(const AwArgs
     const int n = AW_C1 + c;
     const AwNet &N = s.net[n];
     aw_hidden_kept(s, m, n, Xs, AW_XS, H0, H1, H2, r0, wave, lane);
-    aw_layer(H2, AW_LS, m.ws + N.c_w[3], s.H, 1, wave, lane, [&](int f, int row, f32x4 z) {
+    slab_layer<FourChains, AW_WAVES>(H2, AW_LS, m.ws + N.c_w[3], s.H, 1, wave, lane, [&](int f, int row, f32x4 z) {
       const float b = f == 0 ? ldg(m.P + N.o_b[3]) : 0.f;
       f32x4 dz = {};
 #pragma unroll
@@ -366,7 +336,7 @@ __global__ __launch_bounds__(AW_THREADS) void k_awac_critic_fwd_bwd(const AwArgs
         }
         if (f == 0) DZ4[r * AW_DS] = dz[e];
       }
-      stg16(m.ws + N.pl_dz[3] + (size_t)f * s.BP + r0 + row, make_float4(dz[0], dz[1], dz[2], dz[3]));
+      slab_plane4(m.ws + N.pl_dz[3], s.BP, f, r0 + row, dz);
     });
     __syncthreads();
     if (tid == 0) {  // in double and in one fixed order: the logged loss is the correctly rounded mean
@@ -474,83 +444,36 @@ __device__ __forceinline__ void aw_adam(float &p, float &m, float &v, float g, c
   p = __builtin_fmaf(neg_step, m / denom, p);
 }
 
-// One weight tile of Linear l of net n: rows jt (output features), columns kt (input features).  tn >= 0: the
-// target net that follows this one.
-__device__ __forceinline__ void aw_weight_tile(const AwShape &s, const AwMember &m, int n, int l, int tn, int jt, int kt,
-                                               float neg_step, int lane) {
-  const AwNet &N = s.net[n];
-  const int OUT = aw_out(s, n, l), IN = aw_in(s, n, l), OP = aw_op(s, n, l), KP = aw_kp(s, n, l);
-  const int r = lane & 15, q = lane >> 4;
-  f32x4 accs[4] = {};
-  const float *ap = m.ws + N.pl_dz[l] + (size_t)(16 * jt + r) * s.BP + 4 * q;
-  const float *bp = m.ws + (l == 0 ? s.pl_x : N.pl_h[l - 1]) + (size_t)(16 * kt + r) * s.BP + 4 * q;
-  for (int ks = 0; ks < s.BP / 16; ++ks) aw_mma(ldg16(ap + ks * 16), ldg16(bp + ks * 16), accs);
-  const f32x4 acc = aw_acc(accs);
-  const int k = 16 * kt + r;  // C layout: column = lane & 15, rows 4 q + e
-  float *fwd = m.ws + N.c_w[l], *tfwd = tn >= 0 ? m.ws + s.net[tn].c_w[l] : nullptr;
-  float pv[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const int j = 16 * jt + 4 * q + e;
-    float tv = 0.f;
-    pv[e] = 0.f;
-    if (j < OUT && k < IN) {
-      const size_t o = (size_t)N.o_w[l] + (size_t)j * IN + k;
-      float p = ldg(m.P + o), mm = ldg(m.M + o), vv = ldg(m.V + o);
-      aw_adam(p, mm, vv, acc[e], m.coef, neg_step);
-      stg(m.P + o, p), stg(m.M + o, mm), stg(m.V + o, vv);
-      if (m.G) stg(m.G + o, acc[e]);
-      pv[e] = p;
-      if (tn >= 0) {
-        const size_t to = (size_t)s.net[tn].o_w[l] + (size_t)j * IN + k;
-        tv = aw_polyak(s.one_m_tau, s.tau, ldg(m.T + to), p);
-        stg(m.T + to, tv);
-      }
+// Wave w of net n's update (w < aw_net_waves): a weight tile or 16 bias entries of Linear l.  TARGET: the target
+// net of critic n follows it -- (1 - tau) t + tau p into the target arena and into the target's forward copy.
+template <bool TARGET>
+__device__ __forceinline__ void aw_update_wave(const AwShape &s, const AwMember &m, int n, int w, float neg_step, int lane) {
+  const AwNet &N = s.net[n], &TN = s.net[TARGET ? n + (AW_T1 - AW_C1) : n];
+  const auto adam = [&](float &p, float &mm, float &vv, float g) { aw_adam(p, mm, vv, g, m.coef, neg_step); };
+  const auto tile = [&](int l, int off) {
+    return SlabTile{m.P, m.M, m.V, m.G, (size_t)off, aw_out(s, n, l), aw_in(s, n, l), aw_op(s, n, l), aw_kp(s, n, l), s.BP,
+                    m.ws + N.pl_dz[l], m.ws + (l == 0 ? s.pl_x : N.pl_h[l - 1]), m.ws + N.c_w[l],
+                    l > 0 ? m.ws + N.t_w[l - 1] : nullptr, TARGET ? m.ws + TN.c_w[l] : nullptr};
+  };
+  const auto target = [&](int off) {  // of the tensor at `off` of the target arena
+    if constexpr (TARGET) {
+      return [&m, &s, off](size_t rel, float p) {
+        const float tv = aw_polyak(s.one_m_tau, s.tau, ldg(m.T + off + rel), p);
+        stg(m.T + off + rel, tv);
+        return tv;
+      };
+    } else {
+      return SlabNoTarget{};
     }
-    stg(fwd + (size_t)j * KP + k, pv[e]);
-    if (tfwd) stg(tfwd + (size_t)j * KP + k, tv);
-  }
-  if (l > 0) stg16(m.ws + N.t_w[l - 1] + (size_t)k * OP + 16 * jt + 4 * q, make_float4(pv[0], pv[1], pv[2], pv[3]));
-}
-
-// 16 bias entries: db[f] = sum over the batch rows of dz[f][.]
-__device__ __forceinline__ void aw_bias_tile(const AwShape &s, const AwMember &m, int n, int l, int tn, int bt,
-                                             float neg_step, int lane) {
-  const AwNet &N = s.net[n];
-  const int r = lane & 15, q = lane >> 4, f = 16 * bt + r;
-  const float *dz = m.ws + N.pl_dz[l];
-  double gd = 0.0;  // (in double: the rows' terms cancel, and a one-entry bias has no other entries to hide behind)
-  for (int ks = 0; ks < s.BP / 16; ++ks) {
-    const float4 v = __builtin_bit_cast(float4, ldg16(dz + (size_t)f * s.BP + ks * 16 + 4 * q));
-    gd += ((double)v.x + (double)v.y) + ((double)v.z + (double)v.w);
-  }
-  gd += __shfl_xor(gd, 16);
-  gd += __shfl_xor(gd, 32);
-  const float g = (float)gd;
-  if (q == 0 && f < aw_out(s, n, l)) {
-    const size_t o = (size_t)N.o_b[l] + f;
-    float p = ldg(m.P + o), mm = ldg(m.M + o), vv = ldg(m.V + o);
-    aw_adam(p, mm, vv, g, m.coef, neg_step);
-    stg(m.P + o, p), stg(m.M + o, mm), stg(m.V + o, vv);
-    if (m.G) stg(m.G + o, g);
-    if (tn >= 0) {
-      const size_t to = (size_t)s.net[tn].o_b[l] + f;
-      stg(m.T + to, aw_polyak(s.one_m_tau, s.tau, ldg(m.T + to), p));
-    }
-  }
-}
-
-// Wave w of net n's update (w < aw_net_waves).
-__device__ __forceinline__ void aw_update_wave(const AwShape &s, const AwMember &m, int n, int tn, int w, float neg_step,
-                                               int lane) {
+  };
   for (int l = 0; l < 4; ++l) {
     const int nk = aw_kp(s, n, l) / 16, cnt = (aw_op(s, n, l) / 16) * nk;
-    if (w < cnt) return aw_weight_tile(s, m, n, l, tn, w / nk, w % nk, neg_step, lane);
+    if (w < cnt) return slab_weight_tile<FourChains>(tile(l, N.o_w[l]), w / nk, w % nk, lane, adam, target(TN.o_w[l]));
     w -= cnt;
   }
   for (int l = 0; l < 4; ++l) {
     const int cnt = aw_op(s, n, l) / 16;
-    if (w < cnt) return aw_bias_tile(s, m, n, l, tn, w, neg_step, lane);
+    if (w < cnt) return slab_bias_tile<SumDouble>(tile(l, N.o_b[l]), w, lane, adam, target(TN.o_b[l]));
     w -= cnt;
   }
 }
@@ -563,7 +486,7 @@ __global__ __launch_bounds__(256) void k_awac_critic_update(const AwArgs args) {
   const int per = aw_net_waves(s, AW_C1);
   if (w >= 2 * per) return;
   const int c = w >= per ? 1 : 0;
-  aw_update_wave(s, m, AW_C1 + c, AW_T1 + c, w - c * per, m.coef.neg_step[c], lane);
+  aw_update_wave<true>(s, m, AW_C1 + c, w - c * per, m.coef.neg_step[c], lane);
 }
 
 __global__ __launch_bounds__(256) void k_awac_actor_update(const AwArgs args) {
@@ -573,7 +496,7 @@ __global__ __launch_bounds__(256) void k_awac_actor_update(const AwArgs args) {
   const int w = blockIdx.x * 4 + (threadIdx.x >> 6);  // wave-uniform
   const int per = aw_net_waves(s, AW_ACTOR);
   if (w > per) return;
-  if (w < per) return aw_update_wave(s, m, AW_ACTOR, -1, w, m.coef.neg_step[2], lane);
+  if (w < per) return aw_update_wave<false>(s, m, AW_ACTOR, w, m.coef.neg_step[2], lane);
   const int ns = s.BP / 16;
   if (lane < s.A) {  // _log_std: sigma = exp(clamp(ls, -20, 2)); the slab sums in slab order
     double gs = 0.0;
@@ -607,9 +530,7 @@ __global__ void k_awac_sync(const AwShape s, const float *P, const float *T, flo
   const int l = tr ? kind - 3 : kind;
   const int OUT = aw_out(s, n, l), IN = aw_in(s, n, l), OP = aw_op(s, n, l), KP = aw_kp(s, n, l);
   if (i >= OP * KP) return;
-  const int j = tr ? i % OP : i / KP, k = tr ? i / OP : i % KP;
-  const float v = (j < OUT && k < IN) ? ldg(src + N.o_w[l] + (size_t)j * IN + k) : 0.f;
-  stg(ws + (tr ? N.t_w[l - 1] : N.c_w[l]) + i, v);
+  slab_padded_copy(ws + (tr ? N.t_w[l - 1] : N.c_w[l]), src + N.o_w[l], OUT, IN, OP, KP, tr, i);
 }
 
 }  // namespace iqlhip
@@ -619,25 +540,17 @@ using namespace iqlhip;
 // ---------------------------------------------------------------------------------------------------
 // entry points (include/iqlhip.h)
 // ---------------------------------------------------------------------------------------------------
-struct iqlhip_awac {
+struct iqlhip_awac : SlabTrainer {
+  static constexpr int QUEUE_STEPS = 512;  // at most ~2 x 512 steps are ever queued ahead of the device
   AwShape s{};
-  float *P = nullptr, *M = nullptr, *V = nullptr, *G = nullptr, *T = nullptr;
-  float *ws = nullptr;
-  size_t bytes = 0;
+  float *T = nullptr;        // the target arena
   double lr[3] = {0, 0, 0};  // critic 1, critic 2, actor
-  double beta1 = 0, beta2 = 0, eps = 0;
   uint64_t seed = 0;
-  int64_t total_it = 0;
-  hipEvent_t ev = nullptr;  // bounds what one call leaves queued
-  bool ev_used = false;
+  iqlhip_awac() : SlabTrainer(QUEUE_STEPS) {}
+  float *ws() const { return static_cast<float *>(mem); }
 };
 
-struct iqlhip_awac_group {
-  int n = 0;
-  iqlhip_awac *member[IQLHIP_MAX_GROUP] = {};
-  hipEvent_t ev = nullptr;
-  bool ev_used = false;
-};
+struct iqlhip_awac_group : SlabGroup<iqlhip_awac> {};
 
 // The envelope, checked before any HIP call.
 static int awac_check(const iqlhip_trainer_config *c) {
@@ -696,7 +609,8 @@ static AwShape awac_arena_shape(const iqlhip_trainer_config *c, int64_t *n_param
 }
 
 // The workspace of one trainer (element offsets, floats).  Everything is zero at creation; padding is only
-// ever rewritten with zeros.
+// ever rewritten with zeros.  (Offsets into one allocation, not pointers as bc_step.hip's BcWorkspace holds: the
+// members' arguments travel by value, and 16 members' pointers to some sixty pieces would not fit the 4 KB block.)
 static size_t awac_plan(AwShape &s) {
   size_t off = 0;
   const auto take = [&](size_t n) {
@@ -736,21 +650,12 @@ extern "C" int iqlhip_awac_arena_layout(const iqlhip_trainer_config *cfg, int64_
 static int awac_sync(iqlhip_awac *t, hipStream_t st) {
   const int n = AW_MAX_H * (t->s.XP > t->s.H ? t->s.XP : t->s.H);
   hipLaunchKernelGGL(k_awac_sync, dim3((n + 255) / 256, AW_NETS * AW_COPIES), dim3(256), 0, st, t->s, (const float *)t->P,
-                     (const float *)t->T, t->ws);
+                     (const float *)t->T, t->ws());
   HIP_TRY(hipGetLastError());
   return 0;
 }
 
-extern "C" int iqlhip_awac_destroy(iqlhip_awac *t) {
-  if (!t) return 0;
-  if (t->ws) {
-    (void)hipDeviceSynchronize();
-    (void)hipFree(t->ws);
-  }
-  if (t->ev) (void)hipEventDestroy(t->ev);
-  delete t;
-  return 0;
-}
+extern "C" int iqlhip_awac_destroy(iqlhip_awac *t) { return slab_destroy(t); }
 
 extern "C" int iqlhip_awac_create(iqlhip_awac **out, const iqlhip_trainer_config *cfg, double tau, float exp_adv_max,
                                   const iqlhip_arenas *arenas) {
@@ -771,22 +676,7 @@ extern "C" int iqlhip_awac_create(iqlhip_awac **out, const iqlhip_trainer_config
   t->lr[0] = cfg->lr_q, t->lr[1] = cfg->lr_v, t->lr[2] = cfg->lr_actor;
   t->beta1 = cfg->adam_beta1, t->beta2 = cfg->adam_beta2, t->eps = cfg->adam_eps, t->seed = cfg->seed;
   t->bytes = awac_plan(s);
-  void *mem = nullptr;
-  if (hipMalloc(&mem, t->bytes) != hipSuccess) {
-    iqlhip_awac_destroy(t);
-    return fail(IQLHIP_ERR_NOMEM, "hipMalloc of %zu workspace bytes failed", t->bytes);
-  }
-  t->ws = static_cast<float *>(mem);
-  int rc = 0;
-  if (hipMemset(t->ws, 0, t->bytes) != hipSuccess) rc = fail(IQLHIP_ERR_HIP, "hipMemset of the workspace failed");
-  if (!rc) rc = awac_sync(t, nullptr);
-  if (!rc && hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(IQLHIP_ERR_HIP, "building the weight copies failed");
-  if (rc) {
-    iqlhip_awac_destroy(t);
-    return rc;
-  }
-  *out = t;
-  return 0;
+  return slab_finish_create(out, t, [](iqlhip_awac *t) { return awac_sync(t, nullptr); });
 }
 
 extern "C" int iqlhip_awac_sync_weights(iqlhip_awac *t, void *stream) {
@@ -794,11 +684,7 @@ extern "C" int iqlhip_awac_sync_weights(iqlhip_awac *t, void *stream) {
   return awac_sync(t, (hipStream_t)stream);
 }
 
-extern "C" int iqlhip_awac_set_step(iqlhip_awac *t, int64_t total_it) {
-  if (!t || total_it < 0) return fail(IQLHIP_ERR_INVALID, "null trainer or negative step");
-  t->total_it = total_it;
-  return 0;
-}
+extern "C" int iqlhip_awac_set_step(iqlhip_awac *t, int64_t total_it) { return slab_set_step(t, total_it); }
 
 extern "C" int iqlhip_awac_set_lr(iqlhip_awac *t, double lr_actor, double lr_critic_1, double lr_critic_2) {
   if (!t || !(lr_actor >= 0) || !(lr_critic_1 >= 0) || !(lr_critic_2 >= 0))
@@ -813,11 +699,11 @@ extern "C" int iqlhip_awac_copy_out(iqlhip_awac *t, int32_t which, float *dst, v
   const float *src = nullptr;
   size_t n = 0;
   if (which == 0) {
-    src = t->ws + s.o_eps, n = (size_t)2 * s.B * s.A;
+    src = t->ws() + s.o_eps, n = (size_t)2 * s.B * s.A;
   } else if (which >= 1 && which <= AW_NETS * AW_COPIES) {
     const int net = (which - 1) / AW_COPIES, kind = (which - 1) % AW_COPIES, l = kind >= 4 ? kind - 3 : kind;
     if (kind >= 4 && net >= AW_T1) return fail(IQLHIP_ERR_INVALID, "the targets have no transposed copies");
-    src = t->ws + (kind >= 4 ? s.net[net].t_w[l - 1] : s.net[net].c_w[l]);
+    src = t->ws() + (kind >= 4 ? s.net[net].t_w[l - 1] : s.net[net].c_w[l]);
     n = (size_t)aw_op(s, net, l) * aw_kp(s, net, l);
   } else {
     return fail(IQLHIP_ERR_INVALID, "which must be in 0..%d", AW_NETS * AW_COPIES);
@@ -827,28 +713,21 @@ extern "C" int iqlhip_awac_copy_out(iqlhip_awac *t, int32_t which, float *dst, v
 }
 
 // n_steps steps of the members m[0..n): four launches per step for all of them.
-static int awac_run(iqlhip_awac *const *mem, int n, hipEvent_t *ev, bool *ev_used, const iqlhip_replay_view *views,
-                    int64_t n_steps, const int64_t *const *idx, const float *const *eps, float *const *losses,
-                    hipStream_t st) {
-  if (!views || !idx) return fail(IQLHIP_ERR_INVALID, "null views or indices");
-  if (n_steps < 0) return fail(IQLHIP_ERR_INVALID, "n_steps must be >= 0");
+static int awac_run(iqlhip_awac *const *mem, int n, SlabQueueBound &bound, const iqlhip_replay_view *views, int64_t n_steps,
+                    const int64_t *const *idx, const float *const *eps, float *const *losses, hipStream_t st) {
+  if (int rc = slab_check_call(mem, n, views, idx, n_steps, "AWAC")) return rc;
   AwArgs a{};
   a.s = mem[0]->s;
   for (int k = 0; k < n; ++k) {
     const iqlhip_awac *t = mem[k];
-    const iqlhip_replay_view &v = views[k];
-    if (!idx[k]) return fail(IQLHIP_ERR_INVALID, "member %d: AWAC takes its indices from the caller", k);
-    if (!v.rows || v.n_rows < 1) return fail(IQLHIP_ERR_INVALID, "member %d: empty replay view", k);
-    if (v.state_dim != t->s.S || v.action_dim != t->s.A || v.row_stride != t->s.row_stride)
-      return fail(IQLHIP_ERR_INVALID, "member %d: the replay view does not have the trainer's dims", k);
     AwMember &m = a.m[k];
-    m.P = t->P, m.M = t->M, m.V = t->V, m.G = t->G, m.T = t->T, m.ws = t->ws;
-    m.rows = v.rows, m.n_rows = v.n_rows, m.idx = idx[k], m.eps = eps ? eps[k] : nullptr;
+    m.P = t->P, m.M = t->M, m.V = t->V, m.G = t->G, m.T = t->T, m.ws = t->ws();
+    m.rows = views[k].rows, m.n_rows = views[k].n_rows, m.idx = idx[k], m.eps = eps ? eps[k] : nullptr;
     m.loss = losses ? losses[k] : nullptr, m.seed = t->seed, m.step0 = t->total_it;
   }
   const int slabs = a.s.BP / 16;
   const dim3 g1(slabs, n), g2((2 * aw_net_waves(a.s, AW_C1) + 3) / 4, n), g4((aw_net_waves(a.s, AW_ACTOR) + 1 + 3) / 4, n);
-  for (int64_t i = 0; i < n_steps; ++i) {
+  return slab_run(mem, n, bound, n_steps, st, [&](int64_t i) {
     a.step = i;
     for (int k = 0; k < n; ++k) {
       const iqlhip_awac *t = mem[k];
@@ -860,60 +739,31 @@ static int awac_run(iqlhip_awac *const *mem, int n, hipEvent_t *ev, bool *ev_use
     hipLaunchKernelGGL(k_awac_critic_update, g2, dim3(256), 0, st, a);
     hipLaunchKernelGGL(k_awac_actor_fwd_bwd, g1, dim3(AW_THREADS), 0, st, a);
     hipLaunchKernelGGL(k_awac_actor_update, g4, dim3(256), 0, st, a);
-    if ((i & 511) == 511) {  // at most ~2 x 512 steps are ever queued ahead of the device
-      HIP_TRY(hipGetLastError());
-      if (!*ev) HIP_TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming));
-      if (*ev_used) HIP_TRY(hipEventSynchronize(*ev));
-      HIP_TRY(hipEventRecord(*ev, st));
-      *ev_used = true;
-    }
-  }
-  HIP_TRY(hipGetLastError());
-  for (int k = 0; k < n; ++k) mem[k]->total_it += n_steps;
-  return 0;
+  });
 }
 
 extern "C" int iqlhip_awac_group_create(iqlhip_awac_group **out, iqlhip_awac *const *members, int32_t n) {
-  if (!out || !members) return fail(IQLHIP_ERR_INVALID, "null argument");
-  if (n < 1 || n > IQLHIP_MAX_GROUP) return fail(IQLHIP_ERR_UNSUPPORTED, "a group has 1..%d members (got %d)", IQLHIP_MAX_GROUP, n);
-  for (int k = 0; k < n; ++k) {
-    if (!members[k]) return fail(IQLHIP_ERR_INVALID, "member %d is null", k);
-    const AwShape &a = members[0]->s, &b = members[k]->s;
-    if (a.S != b.S || a.A != b.A || a.B != b.B || a.H != b.H || a.gamma != b.gamma || a.tau != b.tau || a.lambda != b.lambda ||
-        a.exp_adv_max != b.exp_adv_max)
-      return fail(IQLHIP_ERR_INVALID, "member %d: the members of a group share dims, width, batch size, gamma, tau, "
-                                      "awac_lambda and exp_adv_max", k);
-    for (int j = 0; j < k; ++j)
-      if (members[j] == members[k]) return fail(IQLHIP_ERR_INVALID, "member %d appears twice", k);
-  }
-  iqlhip_awac_group *g = new (std::nothrow) iqlhip_awac_group;
-  if (!g) return fail(IQLHIP_ERR_NOMEM, "out of host memory");
-  g->n = n;
-  for (int k = 0; k < n; ++k) g->member[k] = members[k];
-  *out = g;
-  return 0;
+  return slab_group_create(
+      out, members, n,
+      [](const AwShape &a, const AwShape &b) {
+        return a.S == b.S && a.A == b.A && a.B == b.B && a.H == b.H && a.gamma == b.gamma && a.tau == b.tau &&
+               a.lambda == b.lambda && a.exp_adv_max == b.exp_adv_max;
+      },
+      "dims, width, batch size, gamma, tau, awac_lambda and exp_adv_max");
 }
 
-extern "C" int iqlhip_awac_group_destroy(iqlhip_awac_group *g) {
-  if (!g) return 0;
-  if (g->ev) {
-    (void)hipEventSynchronize(g->ev);
-    (void)hipEventDestroy(g->ev);
-  }
-  delete g;
-  return 0;
-}
+extern "C" int iqlhip_awac_group_destroy(iqlhip_awac_group *g) { return slab_group_destroy(g); }
 
 extern "C" int iqlhip_awac_group_train_steps(iqlhip_awac_group *g, const iqlhip_replay_view *views, int64_t n_steps,
                                              const int64_t *const *idx, const float *const *eps, float *const *losses_out,
                                              void *stream) {
   if (!g) return fail(IQLHIP_ERR_INVALID, "null group");
-  return awac_run(g->member, g->n, &g->ev, &g->ev_used, views, n_steps, idx, eps, losses_out, (hipStream_t)stream);
+  return awac_run(g->member, g->n, g->bound, views, n_steps, idx, eps, losses_out, (hipStream_t)stream);
 }
 
 extern "C" int iqlhip_awac_train_steps(iqlhip_awac *t, const iqlhip_replay_view *view, int64_t n_steps, const int64_t *idx,
                                        const float *eps, float *losses_out, void *stream) {
   if (!t) return fail(IQLHIP_ERR_INVALID, "null trainer");
-  return awac_run(&t, 1, &t->ev, &t->ev_used, view, n_steps, &idx, eps ? &eps : nullptr,
-                  losses_out ? &losses_out : nullptr, (hipStream_t)stream);
+  return awac_run(&t, 1, t->bound, view, n_steps, &idx, eps ? &eps : nullptr, losses_out ? &losses_out : nullptr,
+                  (hipStream_t)stream);
 }

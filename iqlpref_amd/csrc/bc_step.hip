@@ -19,6 +19,9 @@
 // their dz3 is zero and so is everything behind it, and the mean divides by the B x A real elements.
 // The members of a group are the y coordinate of both launches; each member's arguments are its own entry
 // of the by-value argument block, its arithmetic does not depend on who else is launched with it.
+//
+// The slab walk, the tile updates and the host side are slab_step.h's, with this family's policies: one MFMA
+// chain per tile (OneChain), the bias gradient summed in float (SumFloat), step_math.h's adam_apply<false>.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -28,6 +31,7 @@
 #include "common.h"
 #include "errors.h"
 #include "host_plan.h"
+#include "slab_step.h"
 #include "step_math.h"
 
 namespace iqlhip {
@@ -91,26 +95,6 @@ struct BcArgs {
 // ---------------------------------------------------------------------------------------------------
 // forward / loss head / backward of one 16-row slab
 // ---------------------------------------------------------------------------------------------------
-// One Linear layer of the slab, forward or backward: out[16][16 w .. 16 w + 16) of wave w =
-// act[16][K] x Wm^T, Wm row-major [256][K] (row = output feature, 16-byte pieces along K).  (Four waves
-// with four tiles each measured 22.6k steps/s at the pen shape: a slab is a chain of 256 dependent MFMAs per
-// wave and wide layer; sixteen waves cut the chain to 64.)
-template <class Epilogue>
-__device__ __forceinline__ void bc_slab_layer(const float *act, int act_stride, const float *Wm, int K, int wave,
-                                              int lane, Epilogue &&ep) {
-  using P = Prec<false>;
-  const int r = lane & 15, q = lane >> 4;
-  const int f = 16 * wave + r;
-  f32x4 acc = {};
-#pragma unroll 4
-  for (int ks = 0; ks < K / 16; ++ks) {
-    const uint4 a = *reinterpret_cast<const uint4 *>(act + r * act_stride + ks * 16 + 4 * q);
-    const uint4 b = ldg16(Wm + (size_t)f * K + ks * 16 + 4 * q);
-    P::mma(a, b, acc);
-  }
-  ep(f, 4 * q, acc);  // (feature, first of 4 rows, values)
-}
-
 __global__ __launch_bounds__(BC_THREADS) void k_bc_fwd_bwd(const BcArgs args) {
   const BcShape &s = args.s;
   const BcMember &m = args.m[blockIdx.y];
@@ -126,14 +110,7 @@ __global__ __launch_bounds__(BC_THREADS) void k_bc_fwd_bwd(const BcArgs args) {
   const int XS = s.SP + 4, AS = s.AP + 4;
 
   // ---- gather (bcref:180-187): padding rows have no index and read nothing ----
-  if (tid < 16) {
-    int64_t i = -1;
-    if (r0 + tid < s.B) {
-      i = ldg(m.idx + args.step * s.B + r0 + tid);
-      i = i < 0 ? 0 : (i >= m.n_rows ? m.n_rows - 1 : i);  // (an index outside the buffer must not leave it)
-    }
-    ridx[tid] = i;
-  }
+  slab_row_indices(m.idx, args.step, s.B, r0, m.n_rows, ridx, tid);
   __syncthreads();
   for (int i = tid; i < 16 * s.SP; i += BC_THREADS) {
     const int r = i / s.SP, c = i - r * s.SP;
@@ -151,18 +128,22 @@ __global__ __launch_bounds__(BC_THREADS) void k_bc_fwd_bwd(const BcArgs args) {
     stg(m.ws.xT + (size_t)c * s.BP + r0 + r, Xs[r * XS + c]);
   }
 
-  const auto plane4 = [&](float *plane, int f, int row, const f32x4 &v) {
-    stg16(plane + (size_t)f * s.BP + r0 + row, make_float4(v[0], v[1], v[2], v[3]));
+  const auto plane4 = [&](float *plane, int f, int row, const f32x4 &v) { slab_plane4(plane, s.BP, f, r0 + row, v); };
+  // One 256-wide Linear layer of the slab, forward or backward: one 16-feature tile per wave, so slab_layer's tile
+  // loop is one pass.  (Four waves with four tiles each measured 22.6k steps/s at the pen shape: a slab is a chain
+  // of 256 dependent MFMAs per wave and wide layer; sixteen waves cut the chain to 64.)
+  const auto wide_layer = [&](const float *act, int act_stride, const float *Wm, int K, auto &&ep) {
+    slab_layer<OneChain, BC_WAVES>(act, act_stride, Wm, K, BC_WAVES, wave, lane, ep);
   };
   // ---- layer 1, layer 2: h = relu(x W^T + b) ----
-  bc_slab_layer(Xs, XS, m.ws.w1c, s.SP, wave, lane, [&](int f, int row, f32x4 z) {
+  wide_layer(Xs, XS, m.ws.w1c, s.SP, [&](int f, int row, f32x4 z) {
     const float b = ldg(m.P + s.o_b1 + f);
 #pragma unroll
     for (int e = 0; e < 4; ++e) z[e] = fmaxf(z[e] + b, 0.f), H1s[(row + e) * LS + f] = z[e];
     plane4(m.ws.h1T, f, row, z);
   });
   __syncthreads();
-  bc_slab_layer(H1s, LS, m.ws.w2c, BC_H, wave, lane, [&](int f, int row, f32x4 z) {
+  wide_layer(H1s, LS, m.ws.w2c, BC_H, [&](int f, int row, f32x4 z) {
     const float b = ldg(m.P + s.o_b2 + f);
 #pragma unroll
     for (int e = 0; e < 4; ++e) z[e] = fmaxf(z[e] + b, 0.f), H2s[(row + e) * LS + f] = z[e];
@@ -173,6 +154,7 @@ __global__ __launch_bounds__(BC_THREADS) void k_bc_fwd_bwd(const BcArgs args) {
   // ---- layer 3 and the loss head: pi = max_action tanh(z3), loss = mean (pi - a)^2 ----
   // (one 16-feature tile per wave, AP / 16 <= 2 of them; the other waves wait at the barrier)
   static_assert(BC_WAVES * 16 == BC_H, "one tile of a hidden layer per wave");
+  // (its own k-loop: through slab_layer's unrolled walk the kernel takes 96 VGPRs instead of 54)
   if (wave < s.AP / 16) {
     using P = Prec<false>;
     const int r = lane & 15, q = lane >> 4, j = 16 * wave + r;
@@ -208,13 +190,13 @@ __global__ __launch_bounds__(BC_THREADS) void k_bc_fwd_bwd(const BcArgs args) {
   }
 
   // ---- backward: dz2 = (dz3 W3) [h2 > 0], dz1 = (dz2 W2) [h1 > 0] (the transposed copies) ----
-  bc_slab_layer(DZ3s, AS, m.ws.w3t, s.AP, wave, lane, [&](int f, int row, f32x4 g) {
+  wide_layer(DZ3s, AS, m.ws.w3t, s.AP, [&](int f, int row, f32x4 g) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) g[e] = H2s[(row + e) * LS + f] > 0.f ? g[e] : 0.f, DZ2s[(row + e) * LS + f] = g[e];
     plane4(m.ws.dz2T, f, row, g);
   });
   __syncthreads();
-  bc_slab_layer(DZ2s, LS, m.ws.w2t, BC_H, wave, lane, [&](int f, int row, f32x4 g) {
+  wide_layer(DZ2s, LS, m.ws.w2t, BC_H, [&](int f, int row, f32x4 g) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) g[e] = H1s[(row + e) * LS + f] > 0.f ? g[e] : 0.f;
     plane4(m.ws.dz1T, f, row, g);
@@ -234,56 +216,6 @@ __host__ __device__ inline BcTiles bc_tiles(const BcShape &s) {
   return {16 * 16, 16 * (s.SP / 16), (s.AP / 16) * 16, 16, 16, s.AP / 16};
 }
 
-// One weight tile: rows jt (output features), columns kt (input features) of W[OUT][IN]; dz [..][BP] and
-// act [..][BP] feature-major; fwd [OUT padded][KP] and (optional) tr [IN padded][OP] the copies.
-__device__ __forceinline__ void bc_weight_tile(const BcShape &s, const BcMember &m, int off, int OUT, int IN,
-                                               const float *dz, const float *act, float *fwd, int KP, float *tr,
-                                               int OP, int jt, int kt, int lane) {
-  using P = Prec<false>;
-  const int r = lane & 15, q = lane >> 4;
-  f32x4 acc = {};
-  const float *ap = dz + (size_t)(16 * jt + r) * s.BP + 4 * q;
-  const float *bp = act + (size_t)(16 * kt + r) * s.BP + 4 * q;
-  for (int ks = 0; ks < s.BP / 16; ++ks) P::mma(ldg16(ap + ks * 16), ldg16(bp + ks * 16), acc);
-  const int k = 16 * kt + r;  // C layout: column = lane & 15, rows 4 q + e
-  float pv[4];
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const int j = 16 * jt + 4 * q + e;
-    pv[e] = 0.f;
-    if (j < OUT && k < IN) {
-      const size_t o = (size_t)off + (size_t)j * IN + k;
-      float p = ldg(m.P + o), mm = ldg(m.M + o), vv = ldg(m.V + o);
-      adam_apply<false>(p, mm, vv, acc[e], m.coef, m.coef.neg_step[0]);
-      stg(m.P + o, p), stg(m.M + o, mm), stg(m.V + o, vv);
-      if (m.G) stg(m.G + o, acc[e]);
-      pv[e] = p;
-    }
-    stg(fwd + (size_t)j * KP + k, pv[e]);
-  }
-  if (tr) stg16(tr + (size_t)k * OP + 16 * jt + 4 * q, make_float4(pv[0], pv[1], pv[2], pv[3]));
-}
-
-// 16 bias entries: db[f] = sum over the batch rows of dz[f][.]
-__device__ __forceinline__ void bc_bias_tile(const BcShape &s, const BcMember &m, int off, int OUT, const float *dz,
-                                             int bt, int lane) {
-  const int r = lane & 15, q = lane >> 4, f = 16 * bt + r;
-  float g = 0.f;
-  for (int ks = 0; ks < s.BP / 16; ++ks) {
-    const float4 v = __builtin_bit_cast(float4, ldg16(dz + (size_t)f * s.BP + ks * 16 + 4 * q));
-    g += (v.x + v.y) + (v.z + v.w);
-  }
-  g = xor16_sum(g);
-  g = xor32_sum(g);
-  if (q == 0 && f < OUT) {
-    const size_t o = (size_t)off + f;
-    float p = ldg(m.P + o), mm = ldg(m.M + o), vv = ldg(m.V + o);
-    adam_apply<false>(p, mm, vv, g, m.coef, m.coef.neg_step[0]);
-    stg(m.P + o, p), stg(m.M + o, mm), stg(m.V + o, vv);
-    if (m.G) stg(m.G + o, g);
-  }
-}
-
 __global__ __launch_bounds__(256) void k_bc_update(const BcArgs args) {
   const BcShape &s = args.s;
   const BcMember &m = args.m[blockIdx.y];
@@ -292,20 +224,29 @@ __global__ __launch_bounds__(256) void k_bc_update(const BcArgs args) {
   const BcTiles t = bc_tiles(s);
   if (w >= t.total()) return;
   const BcWorkspace &ws = m.ws;
-  if (w < t.w2) return bc_weight_tile(s, m, s.o_w2, BC_H, BC_H, ws.dz2T, ws.h1T, ws.w2c, BC_H, ws.w2t, BC_H, w >> 4, w & 15, lane);
+  const auto adam = [&](float &p, float &mm, float &vv, float g) { adam_apply<false>(p, mm, vv, g, m.coef, m.coef.neg_step[0]); };
+  // Linear W[OUT][IN] (or its bias) at `off`: dz and act the planes, fwd [..][KP] and tr [..][OP] the copies
+  const auto tile = [&](int off, int OUT, int IN, const float *dz, const float *act, float *fwd, int KP, float *tr, int OP) {
+    return SlabTile{m.P, m.M, m.V, m.G, (size_t)off, OUT, IN, OP, KP, s.BP, dz, act, fwd, tr, nullptr};
+  };
+  const auto weight = [&](const SlabTile &tl, int jt, int kt) { slab_weight_tile<OneChain>(tl, jt, kt, lane, adam, SlabNoTarget{}); };
+  const auto bias = [&](int off, int OUT, const float *dz, int bt) {
+    slab_bias_tile<SumFloat>(tile(off, OUT, 0, dz, nullptr, nullptr, 0, nullptr, 0), bt, lane, adam, SlabNoTarget{});
+  };
+  if (w < t.w2) return weight(tile(s.o_w2, BC_H, BC_H, ws.dz2T, ws.h1T, ws.w2c, BC_H, ws.w2t, BC_H), w >> 4, w & 15);
   w -= t.w2;
   if (w < t.w1) {
     const int nk = s.SP / 16;
-    return bc_weight_tile(s, m, s.o_w1, BC_H, s.S, ws.dz1T, ws.xT, ws.w1c, s.SP, nullptr, 0, w / nk, w % nk, lane);
+    return weight(tile(s.o_w1, BC_H, s.S, ws.dz1T, ws.xT, ws.w1c, s.SP, nullptr, 0), w / nk, w % nk);
   }
   w -= t.w1;
-  if (w < t.w3) return bc_weight_tile(s, m, s.o_w3, s.A, BC_H, ws.dz3T, ws.h2T, ws.w3c, BC_H, ws.w3t, s.AP, w >> 4, w & 15, lane);
+  if (w < t.w3) return weight(tile(s.o_w3, s.A, BC_H, ws.dz3T, ws.h2T, ws.w3c, BC_H, ws.w3t, s.AP), w >> 4, w & 15);
   w -= t.w3;
-  if (w < t.b1) return bc_bias_tile(s, m, s.o_b1, BC_H, ws.dz1T, w, lane);
+  if (w < t.b1) return bias(s.o_b1, BC_H, ws.dz1T, w);
   w -= t.b1;
-  if (w < t.b2) return bc_bias_tile(s, m, s.o_b2, BC_H, ws.dz2T, w, lane);
+  if (w < t.b2) return bias(s.o_b2, BC_H, ws.dz2T, w);
   w -= t.b2;
-  if (w < t.b3) return bc_bias_tile(s, m, s.o_b3, s.A, ws.dz3T, w, lane);
+  if (w < t.b3) return bias(s.o_b3, s.A, ws.dz3T, w);
   if (lane == 0 && m.loss) {  // actor_loss (bcref:236-237): the slab sums in slab order, over n
     double sum = 0.0;
     for (int i = 0; i < s.BP / 16; ++i) sum += ldg(ws.partial + i);
@@ -316,15 +257,14 @@ __global__ __launch_bounds__(256) void k_bc_update(const BcArgs args) {
 // The copies from the fp32 masters (creation, load_state_dict): one thread per element of a padded copy.
 __global__ void k_bc_sync(const BcShape s, const float *P, const BcWorkspace ws) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const auto at = [&](int off, int OUT, int IN, int j, int k) { return (j < OUT && k < IN) ? ldg(P + off + (size_t)j * IN + k) : 0.f; };
-  if (i < BC_H * s.SP) stg(ws.w1c + i, at(s.o_w1, BC_H, s.S, i / s.SP, i % s.SP));
+  if (i < BC_H * s.SP) slab_padded_copy(ws.w1c, P + s.o_w1, BC_H, s.S, BC_H, s.SP, false, i);
   if (i < BC_H * BC_H) {
-    stg(ws.w2c + i, at(s.o_w2, BC_H, BC_H, i / BC_H, i % BC_H));
-    stg(ws.w2t + i, at(s.o_w2, BC_H, BC_H, i % BC_H, i / BC_H));
+    slab_padded_copy(ws.w2c, P + s.o_w2, BC_H, BC_H, BC_H, BC_H, false, i);
+    slab_padded_copy(ws.w2t, P + s.o_w2, BC_H, BC_H, BC_H, BC_H, true, i);
   }
   if (i < s.AP * BC_H) {
-    stg(ws.w3c + i, at(s.o_w3, s.A, BC_H, i / BC_H, i % BC_H));
-    stg(ws.w3t + i, at(s.o_w3, s.A, BC_H, i % s.AP, i / s.AP));
+    slab_padded_copy(ws.w3c, P + s.o_w3, s.A, BC_H, s.AP, BC_H, false, i);
+    slab_padded_copy(ws.w3t, P + s.o_w3, s.A, BC_H, s.AP, BC_H, true, i);
   }
 }
 
@@ -335,24 +275,15 @@ using namespace iqlhip;
 // ---------------------------------------------------------------------------------------------------
 // entry points (include/iqlhip.h)
 // ---------------------------------------------------------------------------------------------------
-struct iqlhip_bc {
+struct iqlhip_bc : SlabTrainer {
+  static constexpr int QUEUE_STEPS = 1024;  // at most ~2 x 1024 steps are ever queued ahead of the device
   BcShape s{};
   BcWorkspace ws{};
-  float *P = nullptr, *M = nullptr, *V = nullptr, *G = nullptr;
-  void *mem = nullptr;
-  size_t bytes = 0;
-  double lr = 0, beta1 = 0, beta2 = 0, eps = 0;
-  int64_t total_it = 0;
-  hipEvent_t ev = nullptr;  // bounds what one call leaves queued
-  bool ev_used = false;
+  double lr = 0;
+  iqlhip_bc() : SlabTrainer(QUEUE_STEPS) {}
 };
 
-struct iqlhip_bc_group {
-  int n = 0;
-  iqlhip_bc *member[IQLHIP_MAX_GROUP] = {};
-  hipEvent_t ev = nullptr;  // bounds what one call leaves queued
-  bool ev_used = false;
-};
+struct iqlhip_bc_group : SlabGroup<iqlhip_bc> {};
 
 // The envelope, checked before any HIP call.
 static int bc_check(const iqlhip_trainer_config *c) {
@@ -401,16 +332,7 @@ static int bc_sync(iqlhip_bc *t, hipStream_t st) {
   return 0;
 }
 
-extern "C" int iqlhip_bc_destroy(iqlhip_bc *t) {
-  if (!t) return 0;
-  if (t->mem) {
-    (void)hipDeviceSynchronize();
-    (void)hipFree(t->mem);
-  }
-  if (t->ev) (void)hipEventDestroy(t->ev);
-  delete t;
-  return 0;
-}
+extern "C" int iqlhip_bc_destroy(iqlhip_bc *t) { return slab_destroy(t); }
 
 extern "C" int iqlhip_bc_create(iqlhip_bc **out, const iqlhip_trainer_config *cfg, float max_action,
                                 const iqlhip_arenas *arenas) {
@@ -426,23 +348,11 @@ extern "C" int iqlhip_bc_create(iqlhip_bc **out, const iqlhip_trainer_config *cf
   WorkspacePlan measure;
   BcWorkspace none;
   t->bytes = bc_plan(measure, t->s, none);
-  if (hipMalloc(&t->mem, t->bytes) != hipSuccess) {
-    t->mem = nullptr;
-    iqlhip_bc_destroy(t);
-    return fail(IQLHIP_ERR_NOMEM, "hipMalloc of %zu workspace bytes failed", t->bytes);
-  }
-  WorkspacePlan place(t->mem);
-  bc_plan(place, t->s, t->ws);
-  int rc = 0;
-  if (hipMemset(t->mem, 0, t->bytes) != hipSuccess) rc = fail(IQLHIP_ERR_HIP, "hipMemset of the workspace failed");
-  if (!rc) rc = bc_sync(t, nullptr);
-  if (!rc && hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(IQLHIP_ERR_HIP, "building the weight copies failed");
-  if (rc) {
-    iqlhip_bc_destroy(t);
-    return rc;
-  }
-  *out = t;
-  return 0;
+  return slab_finish_create(out, t, [](iqlhip_bc *t) {
+    WorkspacePlan place(t->mem);
+    bc_plan(place, t->s, t->ws);
+    return bc_sync(t, nullptr);
+  });
 }
 
 extern "C" int iqlhip_bc_sync_weights(iqlhip_bc *t, void *stream) {
@@ -450,11 +360,7 @@ extern "C" int iqlhip_bc_sync_weights(iqlhip_bc *t, void *stream) {
   return bc_sync(t, (hipStream_t)stream);
 }
 
-extern "C" int iqlhip_bc_set_step(iqlhip_bc *t, int64_t total_it) {
-  if (!t || total_it < 0) return fail(IQLHIP_ERR_INVALID, "null trainer or negative step");
-  t->total_it = total_it;
-  return 0;
-}
+extern "C" int iqlhip_bc_set_step(iqlhip_bc *t, int64_t total_it) { return slab_set_step(t, total_it); }
 
 extern "C" int iqlhip_bc_set_lr(iqlhip_bc *t, double lr) {
   if (!t || !(lr >= 0)) return fail(IQLHIP_ERR_INVALID, "null trainer or negative lr");
@@ -474,82 +380,46 @@ extern "C" int iqlhip_bc_copy_out(iqlhip_bc *t, int32_t which, float *dst, void 
 }
 
 // n_steps steps of the members m[0..n): two launches per step for all of them.
-static int bc_run(iqlhip_bc *const *mem, int n, hipEvent_t *ev, bool *ev_used, const iqlhip_replay_view *views,
-                  int64_t n_steps, const int64_t *const *idx, float *const *losses, hipStream_t st) {
-  if (!views || !idx) return fail(IQLHIP_ERR_INVALID, "null views or indices");
-  if (n_steps < 0) return fail(IQLHIP_ERR_INVALID, "n_steps must be >= 0");
+static int bc_run(iqlhip_bc *const *mem, int n, SlabQueueBound &bound, const iqlhip_replay_view *views, int64_t n_steps,
+                  const int64_t *const *idx, float *const *losses, hipStream_t st) {
+  if (int rc = slab_check_call(mem, n, views, idx, n_steps, "behaviour cloning")) return rc;
   BcArgs a{};
   a.s = mem[0]->s;
   for (int k = 0; k < n; ++k) {
     const iqlhip_bc *t = mem[k];
-    const iqlhip_replay_view &v = views[k];
-    if (!idx[k]) return fail(IQLHIP_ERR_INVALID, "member %d: behaviour cloning takes its indices from the caller", k);
-    if (!v.rows || v.n_rows < 1) return fail(IQLHIP_ERR_INVALID, "member %d: empty replay view", k);
-    if (v.state_dim != t->s.S || v.action_dim != t->s.A || v.row_stride != t->s.row_stride)
-      return fail(IQLHIP_ERR_INVALID, "member %d: the replay view does not have the trainer's dims", k);
     BcMember &m = a.m[k];
     m.P = t->P, m.M = t->M, m.V = t->V, m.G = t->G, m.ws = t->ws;
-    m.rows = v.rows, m.n_rows = v.n_rows, m.idx = idx[k], m.loss = losses ? losses[k] : nullptr;
+    m.rows = views[k].rows, m.n_rows = views[k].n_rows, m.idx = idx[k], m.loss = losses ? losses[k] : nullptr;
   }
   const BcTiles tiles = bc_tiles(a.s);
   const dim3 g1(a.s.BP / 16, n), g2((tiles.total() + 3) / 4, n);
-  for (int64_t i = 0; i < n_steps; ++i) {
+  return slab_run(mem, n, bound, n_steps, st, [&](int64_t i) {
     a.step = i;
     for (int k = 0; k < n; ++k)
       a.m[k].coef = make_adam_coef(mem[k]->beta1, mem[k]->beta2, mem[k]->eps, mem[k]->lr, mem[k]->lr, mem[k]->lr, 1,
                                    mem[k]->total_it + i + 1);
     hipLaunchKernelGGL(k_bc_fwd_bwd, g1, dim3(BC_THREADS), 0, st, a);
     hipLaunchKernelGGL(k_bc_update, g2, dim3(256), 0, st, a);
-    if ((i & 1023) == 1023) {  // at most ~2 x 1024 steps are ever queued ahead of the device
-      HIP_TRY(hipGetLastError());
-      if (!*ev) HIP_TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming));
-      if (*ev_used) HIP_TRY(hipEventSynchronize(*ev));
-      HIP_TRY(hipEventRecord(*ev, st));
-      *ev_used = true;
-    }
-  }
-  HIP_TRY(hipGetLastError());
-  for (int k = 0; k < n; ++k) mem[k]->total_it += n_steps;
-  return 0;
+  });
 }
 
 extern "C" int iqlhip_bc_group_create(iqlhip_bc_group **out, iqlhip_bc *const *members, int32_t n) {
-  if (!out || !members) return fail(IQLHIP_ERR_INVALID, "null argument");
-  if (n < 1 || n > IQLHIP_MAX_GROUP) return fail(IQLHIP_ERR_UNSUPPORTED, "a group has 1..%d members (got %d)", IQLHIP_MAX_GROUP, n);
-  for (int k = 0; k < n; ++k) {
-    if (!members[k]) return fail(IQLHIP_ERR_INVALID, "member %d is null", k);
-    const BcShape &a = members[0]->s, &b = members[k]->s;
-    if (a.S != b.S || a.A != b.A || a.B != b.B || a.max_action != b.max_action)
-      return fail(IQLHIP_ERR_INVALID, "member %d: the members of a group share dims, batch size and max_action", k);
-    for (int j = 0; j < k; ++j)
-      if (members[j] == members[k]) return fail(IQLHIP_ERR_INVALID, "member %d appears twice", k);
-  }
-  iqlhip_bc_group *g = new (std::nothrow) iqlhip_bc_group;
-  if (!g) return fail(IQLHIP_ERR_NOMEM, "out of host memory");
-  g->n = n;
-  for (int k = 0; k < n; ++k) g->member[k] = members[k];
-  *out = g;
-  return 0;
+  return slab_group_create(
+      out, members, n,
+      [](const BcShape &a, const BcShape &b) { return a.S == b.S && a.A == b.A && a.B == b.B && a.max_action == b.max_action; },
+      "dims, batch size and max_action");
 }
 
-extern "C" int iqlhip_bc_group_destroy(iqlhip_bc_group *g) {
-  if (!g) return 0;
-  if (g->ev) {
-    (void)hipEventSynchronize(g->ev);
-    (void)hipEventDestroy(g->ev);
-  }
-  delete g;
-  return 0;
-}
+extern "C" int iqlhip_bc_group_destroy(iqlhip_bc_group *g) { return slab_group_destroy(g); }
 
 extern "C" int iqlhip_bc_group_train_steps(iqlhip_bc_group *g, const iqlhip_replay_view *views, int64_t n_steps,
                                            const int64_t *const *idx, float *const *losses_out, void *stream) {
   if (!g) return fail(IQLHIP_ERR_INVALID, "null group");
-  return bc_run(g->member, g->n, &g->ev, &g->ev_used, views, n_steps, idx, losses_out, (hipStream_t)stream);
+  return bc_run(g->member, g->n, g->bound, views, n_steps, idx, losses_out, (hipStream_t)stream);
 }
 
 extern "C" int iqlhip_bc_train_steps(iqlhip_bc *t, const iqlhip_replay_view *view, int64_t n_steps, const int64_t *idx,
                                      float *losses_out, void *stream) {
   if (!t) return fail(IQLHIP_ERR_INVALID, "null trainer");
-  return bc_run(&t, 1, &t->ev, &t->ev_used, view, n_steps, &idx, losses_out ? &losses_out : nullptr, (hipStream_t)stream);
+  return bc_run(&t, 1, t->bound, view, n_steps, &idx, losses_out ? &losses_out : nullptr, (hipStream_t)stream);
 }

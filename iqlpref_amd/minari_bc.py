@@ -33,7 +33,7 @@ from . import distributed as D
 from ._lib import check, ptr, stream_ptr
 from .custom_offline import ReplayBuffer, evaluate  # noqa: F401  (bcref:133-192, 256-275)
 from .iql import mlp_forward_f32, set_seed
-from .multi import DeviceGroup, _per_member
+from .multi import ArenaGroup
 from .multi import stepper as _multi_stepper
 
 HIDDEN = 256  # bcref:199-203
@@ -220,10 +220,6 @@ class BC(_arena.ArenaTrainer):
             check(self._lib.iqlhip_bc_set_lr(self._handle, lr))
             self._lr_sent = lr
 
-    def _after_steps(self, n: int):
-        self.total_it += n
-        self._bind_optimizer_state()
-
     # -- the step ----------------------------------------------------------- #
     def train_steps(self, replay_buffer: ReplayBuffer, n_steps: int, batch_size: int, *,
                     indices: torch.Tensor, dropout_keep=None, return_losses: bool = True,
@@ -255,15 +251,8 @@ class BC(_arena.ArenaTrainer):
         """bcref:230-243 on an explicit batch [s, a, ...]: the rows are laid out as replay rows of their own and
         stepped once in order."""
         state, action = [t.detach().to(device=self._dev, dtype=torch.float32) for t in batch[:2]]
-        n, S, A = state.shape[0], self._state_dim, self._action_dim
-        if tuple(state.shape) != (n, S) or tuple(action.shape) != (n, A):
-            raise RuntimeError("batch shapes do not match the actor")
-        stride = self._lib.iqlhip_replay_row_stride(S, A)
-        rows = torch.zeros((n, stride), dtype=torch.float32, device=self._dev)
-        rows[:, :S], rows[:, S:S + A] = state, action
-        view = _lib.ReplayView(ptr(rows), n, stride, S, A, 0)
-        idx = torch.arange(n, dtype=torch.int64, device=self._dev)[None]
-        return {"actor_loss": self._steps_on_view(view, 1, n, idx, True).item()}
+        view, idx, _rows = self._batch_as_rows("batch shapes do not match the actor", state, action)
+        return {"actor_loss": self._steps_on_view(view, 1, state.shape[0], idx, True).item()}
 
     # -- checkpoints (bcref:245-253) ----------------------------------------- #
     def state_dict(self) -> Dict[str, Any]:
@@ -296,51 +285,17 @@ def check_envelope(state_dim: int, action_dim: int, batch_size: int = 16) -> Non
     check(_lib.load().iqlhip_bc_arena_layout(C.byref(c), C.byref(offs), C.byref(n)))
 
 
-class BCGroup(DeviceGroup):
+class BCGroup(ArenaGroup):
     """K ``BC`` trainers of one shape stepped by the same two launches per step (``iqlhip_bc_group_*``): the part
     of ``multi.SeedGroup``'s surface ``_offline_loop.run`` uses.  Every member is bit-identical to stepping it
     alone.  One trainer needs no group: ``stepper`` hands back a ``multi.Solo``."""
-
-    def __init__(self, trainers: Sequence[BC]):
-        if not 1 <= len(trainers) <= _lib.MAX_GROUP:
-            raise NotImplementedError(f"a group has 1..{_lib.MAX_GROUP} members")
-        if len({id(t) for t in trainers}) != len(trainers) or len({t._dev for t in trainers}) != 1:
-            raise ValueError("the members of a group are distinct trainers on one device")
-        self.trainers = list(trainers)
-        self._lib, self._dev = trainers[0]._lib, trainers[0]._dev
-
-    def __len__(self):
-        return len(self.trainers)
-
-    def _create_group(self, batch_size: int, handles, n: int):
-        g = C.c_void_p()
-        check(self._lib.iqlhip_bc_group_create(C.byref(g), handles, n))
-        return g
-
-    def _destroy_group(self, group):
-        torch.cuda.synchronize(self._dev)
-        self._lib.iqlhip_bc_group_destroy(group)
+    _ENTRY, _LOSSES = "iqlhip_bc", 1
 
     def train_steps(self, replay, n_steps: int, batch_size: int, *, indices: Sequence[torch.Tensor],
                     return_losses: bool = False):
         """``BC.train_steps`` for every member: ``replay`` is one buffer for all or one per member, ``indices``
         one tensor per member.  Returns the list of [n_steps, 1] loss tensors when ``return_losses``."""
-        K = len(self.trainers)
-        bufs, idx, _, _ = _per_member(K, replay, indices, None, None)
-        self._ensure_group(batch_size)
-        for t in self.trainers:
-            t._refresh_lrs()
-        idx = [_arena.check_indices(i, n_steps, batch_size, True) for i in idx]
-        losses = [torch.empty((n_steps, 1), dtype=torch.float32, device=self._dev) for _ in range(K)] \
-            if return_losses else None
-        views = (_lib.ReplayView * K)(*[b.view() for b in bufs])
-        idx_p = (C.c_void_p * K)(*[i.data_ptr() for i in idx])
-        loss_p = (C.c_void_p * K)(*[l.data_ptr() for l in losses]) if return_losses else None
-        with torch.cuda.device(self._dev):
-            check(self._lib.iqlhip_bc_group_train_steps(self._group, views, n_steps, idx_p, loss_p, stream_ptr()))
-        for t in self.trainers:
-            t._after_steps(n_steps)
-        return losses
+        return self._group_steps(replay, n_steps, batch_size, indices, return_losses)
 
 
 def stepper(trainers: Sequence[BC]):

@@ -152,6 +152,61 @@ class DeviceGroup:
         torch.cuda.current_stream(self._dev).synchronize()
 
 
+class ArenaGroup(DeviceGroup):
+    """The group of a family whose native group steps K trainers of one shape by injected indices
+    (``minari_bc.BCGroup``, ``awac.AWACGroup``).  A subclass names the family's entry points (``_ENTRY``:
+    ``<_ENTRY>_group_create`` / ``_destroy`` / ``_train_steps``) and the width of a step's loss record (``_LOSSES``)."""
+    _ENTRY, _LOSSES = "", 1
+
+    def __init__(self, trainers: Sequence):
+        if not 1 <= len(trainers) <= _lib.MAX_GROUP:
+            raise NotImplementedError(f"a group has 1..{_lib.MAX_GROUP} members")
+        if len({id(t) for t in trainers}) != len(trainers) or len({t._dev for t in trainers}) != 1:
+            raise ValueError("the members of a group are distinct trainers on one device")
+        self.trainers = list(trainers)
+        self._lib, self._dev = trainers[0]._lib, trainers[0]._dev
+
+    def __len__(self):
+        return len(self.trainers)
+
+    def _group_entry(self, name: str):
+        return getattr(self._lib, f"{self._ENTRY}_group_{name}")
+
+    def _create_group(self, batch_size: int, handles, n: int):
+        g = C.c_void_p()
+        check(self._group_entry("create")(C.byref(g), handles, n))
+        return g
+
+    def _destroy_group(self, group):
+        torch.cuda.synchronize(self._dev)
+        self._group_entry("destroy")(group)
+
+    def _group_steps(self, replay, n_steps: int, batch_size: int, indices, return_losses: bool, extra=()):
+        """The family's ``train_steps`` for every member: ``replay`` one buffer for all or one per member,
+        ``indices`` one tensor per member.  ``extra``: callables that check and hand back one more per-member list
+        of optional device tensors each, passed on between the indices and the losses (all None: a null array);
+        they run after the indices are checked and before anything is created.  Returns the list of [n_steps,
+        _LOSSES] loss tensors when ``return_losses``."""
+        K = len(self.trainers)
+        bufs, idx, _, _ = _per_member(K, replay, indices, None, None)
+        idx = [check_indices(i, n_steps, batch_size, True) for i in idx]
+        more = [e() for e in extra]
+        self._ensure_group(batch_size)
+        for t in self.trainers:
+            t._refresh_lrs()
+        losses = [torch.empty((n_steps, self._LOSSES), dtype=torch.float32, device=self._dev) for _ in range(K)] \
+            if return_losses else None
+        views = (_lib.ReplayView * K)(*[b.view() for b in bufs])
+        parr = lambda ts: None if ts is None or all(t is None for t in ts) else \
+            (C.c_void_p * K)(*[None if t is None else t.data_ptr() for t in ts])
+        with torch.cuda.device(self._dev):
+            check(self._group_entry("train_steps")(self._group, views, n_steps, parr(idx), *map(parr, more), parr(losses),
+                                                   stream_ptr()))
+        for t in self.trainers:
+            t._after_steps(n_steps)
+        return losses
+
+
 class SeedGroup(DeviceGroup):
     def __init__(self, trainers: Sequence[ImplicitQLearning], chunk: int = 2000, mode: Optional[str] = None,
                  n_streams: int = 2):
