@@ -1,16 +1,18 @@
-"""The chunked train / evaluate / checkpoint loop of the custom-offline flavours (``custom_offline.train`` and
-``train_runs``, ``custom_offline_br``, ``custom_offline_bb``), once, and the setup every ``train()`` shares: the
-``sampler`` check, the seeds of a rank, the checkpoint directories, the default logger and the ``seed`` tag of
-K > 1 records.  The offline flavour (``train``,
-``sweep.train_runs``) takes that setup from here and runs ``_window_loop``: window means instead of every step's
-losses, a metric exchange instead of a best model.
+"""The chunked train / evaluate / checkpoint loop of every offline ``train()`` but the window loop's
+(``custom_offline.train`` and ``train_runs``, ``custom_offline_br``, ``custom_offline_bb``, ``minari_iql``,
+``minari_bc``, ``offline_bc``, ``awac``), once, and the setup every ``train()`` shares: the ``sampler`` check, the
+seeds of a rank, the checkpoint directories, the default logger and the ``seed`` tag of K > 1 records.  The
+offline flavour (``train``, ``sweep.train_runs``) takes that setup from here and runs ``_window_loop``: window
+means instead of every step's losses, a metric exchange instead of a best model.
 
-``run`` knows no trainer class, buffer or sampler: a flavour hands in how a group is built, how a chunk of steps
-is queued and how one seed is evaluated.  Its members are the K seeds of one config (one step count and
+``run`` knows no trainer class, buffer or sampler, and no record name: a flavour hands in how a group is built,
+how a chunk of steps is queued, how one seed is evaluated and a ``Records`` that logs what the flavour logs
+(``EvalRecords``, ``BestModelRecords``, or its own).  Its members are the K seeds of one config (one step count and
 evaluation period for all) or the runs of a sweep's launch batch (``custom_offline.train_runs``: one of each per
 member).  ``Members`` is the group lifecycle of both loops: built over the members that start, rebuilt when one
 leaves, closed at the end.  Nothing here touches the GPU or loads the library.
 """
+import contextlib
 import os
 import uuid
 from dataclasses import asdict
@@ -132,29 +134,81 @@ class Members:
             group.close()
 
 
+class Records:
+    """What a flavour logs under ``run``.  ``loss_names``: the columns of the loss tensors.  ``step_offset`` is
+    added to the zero-based step of every record, losses and evaluations alike, never to a file name.
+    ``evaluated`` logs member k's evaluation through ``log(record)``, bound by ``run`` to the member's tag and to
+    ``step + step_offset``.  For ``resume``, ``state(k)`` / ``load_state(k, state)``: member k's ``"loop"`` entry."""
+    loss_names: Sequence[str] = LOSS_NAMES
+    step_offset = 0
+
+    def evaluated(self, k: int, trainer, step: int, returns: np.ndarray, log: Callable) -> None:
+        raise NotImplementedError
+
+
+class EvalRecords(Records):
+    """``evaluation_return``, then ``normalized_score``: the mean of ``normalized(returns)`` (one callable, or one
+    per member) x 100.  A ``ValueError`` from it logs nothing and keeps ``norm[k]``.  ``minari_bc``'s recorder."""
+
+    def __init__(self, normalized=None, loss_names: Sequence[str] = LOSS_NAMES):
+        self.normalized, self.loss_names = normalized, loss_names
+        self.norm: Dict[int, Optional[float]] = {}
+
+    def evaluated(self, k, trainer, step, returns, log):
+        log({"evaluation_return": returns.mean()})
+        normalized = self.normalized[k] if isinstance(self.normalized, (list, tuple)) else self.normalized
+        if normalized is not None:
+            with contextlib.suppress(ValueError):
+                self.norm[k] = np.asarray(normalized(returns)).mean() * 100
+                log({"normalized_score": self.norm[k]})
+
+
+class BestModelRecords(EvalRecords):
+    """``EvalRecords`` plus the best model of every member -- that of the strictly greatest kept normalized score,
+    or mean return without one or with ``best_by_return`` --, saved as ``best_model.pt`` into ``ckpt_dirs[k]``
+    (None: nowhere) ahead of ``best_score_so_far`` and ``best_step_so_far``.  The custom-offline flavours' recorder."""
+
+    def __init__(self, ckpt_dirs: Sequence[Optional[str]], normalized=None, best_by_return: bool = False):
+        super().__init__(normalized)
+        self.ckpt_dirs, self.best_by_return = ckpt_dirs, best_by_return
+        self.best_score, self.best_step = [-np.inf] * len(ckpt_dirs), [0] * len(ckpt_dirs)
+
+    def evaluated(self, k, trainer, step, returns, log):
+        super().evaluated(k, trainer, step, returns, log)
+        norm = self.norm.get(k)
+        score = norm if norm is not None and not self.best_by_return else returns.mean()
+        if score > self.best_score[k]:
+            self.best_score[k], self.best_step[k] = score, step
+            if self.ckpt_dirs[k] is not None:
+                torch.save(trainer.state_dict(), os.path.join(self.ckpt_dirs[k], "best_model.pt"))
+        log({"best_score_so_far": self.best_score[k]})
+        log({"best_step_so_far": self.best_step[k]})
+
+    def state(self, k):
+        norm = self.norm.get(k)
+        return {"best_score": float(self.best_score[k]), "best_step": int(self.best_step[k]),
+                "norm": None if norm is None else float(norm)}
+
+    def load_state(self, k, state):
+        self.best_score[k], self.best_step[k], self.norm[k] = state["best_score"], state["best_step"], state["norm"]
+
+
 def run(trainers: Sequence, seeds: Sequence[int], make_group: Callable, total: PerMember, every: PerMember,
         chunk: int, logger: Logger, ckpt_dirs: Sequence[Optional[str]], steps: Callable, evaluate: Callable,
-        normalized: Union[None, Callable, Sequence[Optional[Callable]]] = None, best_by_return: bool = False, *,
-        tagged: Optional[Callable] = None, resume: bool = False, sampler_state: Optional[Callable] = None,
-        set_sampler_state: Optional[Callable] = None, loss_names: Sequence[str] = LOSS_NAMES,
-        best_model: bool = True) -> None:
+        records: Records, *, tagged: Optional[Callable] = None, resume: bool = False,
+        sampler_state: Optional[Callable] = None, set_sampler_state: Optional[Callable] = None) -> None:
     """``total`` steps in chunks of at most ``chunk`` that end on the evaluation boundaries (every ``every``
     steps); the losses of a chunk come back to the host once, after the next chunk has been queued.
 
     ``make_group(active)`` builds what steps the members that start together (``multi.stepper``; None: nothing to
     synchronize or close); ``steps(group, active, t, n)`` queues steps t .. t + n - 1 and returns the loss tensors
-    [n, 3] of the active members in member order; the group is synchronized before an evaluation (``Members``).
-    ``evaluate(k, trainer, step)`` gives the returns of member k.  ``normalized(returns)``: the normalized
-    scores, logged x 100 (one callable, or one per member); a ``ValueError`` from it keeps what the member had
-    (at first the raw mean return), and a value once obtained stays.  The best model is the one of the
-    strictly greatest normalized score, or mean return without one or with ``best_by_return``.  One
-    ``logger(record, step)`` call per step and member for the losses, then per evaluation record;
-    ``tagged(record, k)`` makes the record the logger gets (default: ``tag(seeds)``).
+    [n, len(records.loss_names)] of the active members in member order; the group is synchronized before an
+    evaluation (``Members``).  ``evaluate(k, trainer, step)`` gives the returns of member k.
 
-    ``loss_names``: the names of the columns of the loss tensors (default: the three losses of an IQL step;
-    ``minari_bc`` logs one ``actor_loss``).  ``best_model=False``: no best-model bookkeeping -- no
-    ``best_model.pt``, no ``best_score_so_far`` / ``best_step_so_far`` records (``minari_bc``: the reference's
-    loop there has none); the default leaves every record as it was.
+    The loop schedules, ``records`` (a ``Records``) names and logs: one ``logger(record, step)`` call per step and
+    member for the losses; at a boundary, per due member in member order, ``evaluate``, ``records.evaluated`` --
+    that flavour's evaluation records and best model, if it keeps one -- and ``checkpoint_{step}.pt``.
+    ``tagged(record, k)`` makes the record the logger gets (default: ``tag(seeds)``).
 
     ``total`` / ``every`` may be one entry per member (a sweep's runs): all members start at step 0, a chunk
     ends on the next evaluation boundary or end of ANY active member, and a member whose ``total`` is reached
@@ -166,24 +220,22 @@ def run(trainers: Sequence, seeds: Sequence[int], make_group: Callable, total: P
     files of all due members -- every member active in the chunk, due or not, writes one file of a resume
     generation (``_resume``) at the common step: its ``trainer.resume_state()``, ``sampler_state(k)`` (what
     its index sampler needs to stand where it stands now; ``steps`` draws exactly the steps it queues, so
-    nothing is drawn ahead of the boundary), its best score and step, its kept normalized score and whether
-    it has finished.  No loss record is pending then.  And the loop starts from the newest complete
-    generation (``_resume.latest``) instead of step 0: every member is restored with
-    ``trainer.load_resume_state`` and ``set_sampler_state(k, state)``, files of later, incomplete
-    generations are removed, finished members are neither trained nor evaluated again, and ``make_group`` is
-    first called after the restore, with the members that go on.  Without any generation the run starts at step
-    0; members that hold generations of different steps and none in common were not interrupted together:
-    ValueError, and their files stay (``_resume.restore``).  Without ``resume`` nothing of this happens and no
-    such file is written."""
+    nothing is drawn ahead of the boundary), ``records.state(k)`` (its best score and step, its kept normalized
+    score) and whether it has finished.  No loss record is pending then.  And the loop starts from the newest
+    complete generation (``_resume.latest``) instead of step 0: every member is restored with
+    ``trainer.load_resume_state``, ``set_sampler_state(k, state)`` and ``records.load_state(k, state)``, files of
+    later, incomplete generations are removed, finished members are neither trained nor evaluated again, and
+    ``make_group`` is first called after the restore, with the members that go on.  Without any generation the
+    run starts at step 0; members that hold generations of different steps and none in common were not
+    interrupted together: ValueError, and their files stay (``_resume.restore``).  Without ``resume`` nothing of
+    this happens and no such file is written."""
     K = len(trainers)
     totals, everys = spread(total, K), spread(every, K)
-    norms = list(normalized) if isinstance(normalized, (list, tuple)) else [normalized] * K
-    if not len(totals) == len(everys) == len(norms) == K:
-        raise ValueError("total / every / normalized: one entry per member")
+    if not len(totals) == len(everys) == K:
+        raise ValueError("total / every: one entry per member")
     if tagged is None:
         tagged = tag(seeds)
-    best_score, best_step = [-np.inf] * K, [0] * K
-    norm = [None] * K
+    loss_names, offset = records.loss_names, int(records.step_offset)
     pending = None  # (first step, members, their device losses) of the chunk whose records are still to be logged
 
     def flush():
@@ -193,8 +245,8 @@ def run(trainers: Sequence, seeds: Sequence[int], make_group: Callable, total: P
         t0, members, losses = pending
         pending = None
         for k, arr in zip(members, (l.cpu().numpy() for l in losses)):
-            for i, row in enumerate(arr.tolist()):
-                logger(tagged(dict(zip(loss_names, row)), k), t0 + i)
+            for i, row in enumerate(arr.tolist(), t0 + offset):
+                logger(tagged(dict(zip(loss_names, row)), k), i)
 
     t = 0
     finished = set()
@@ -205,7 +257,7 @@ def run(trainers: Sequence, seeds: Sequence[int], make_group: Callable, total: P
             trainers[k].load_resume_state(p["trainer"])
             if set_sampler_state is not None:
                 set_sampler_state(k, p["sampler"])
-            best_score[k], best_step[k], norm[k] = p["loop"]["best_score"], p["loop"]["best_step"], p["loop"]["norm"]
+            records.load_state(k, p["loop"])
             if p["finished"]:
                 finished.add(k)
 
@@ -213,8 +265,7 @@ def run(trainers: Sequence, seeds: Sequence[int], make_group: Callable, total: P
         flush()
         payloads = {k: {"finished": t >= totals[k], "trainer": trainers[k].resume_state(),
                         "sampler": None if sampler_state is None else sampler_state(k),
-                        "loop": {"best_score": float(best_score[k]), "best_step": int(best_step[k]),
-                                 "norm": None if norm[k] is None else float(norm[k])}} for k in members}
+                        "loop": records.state(k)} for k in members}
         _resume.commit(ckpt_dirs, t, payloads, kept)
 
     with Members(make_group, [k for k in range(K) if t < totals[k] and k not in finished]) as live:
@@ -231,27 +282,10 @@ def run(trainers: Sequence, seeds: Sequence[int], make_group: Callable, total: P
                 live.synchronize()
             step = t - 1
             for k in due:
-                trainer = trainers[k]
-                log = lambda d: logger(tagged(d, k), step)
-                eval_scores = evaluate(k, trainer, step)
-                mean_eval = eval_scores.mean()
-                log({"evaluation_return": mean_eval})
-                if norms[k] is not None:
-                    try:
-                        norm[k] = np.asarray(norms[k](eval_scores)).mean() * 100
-                        log({"normalized_score": norm[k]})
-                    except ValueError:
-                        pass
-                score = norm[k] if norm[k] is not None and not best_by_return else mean_eval
-                if best_model and score > best_score[k]:
-                    best_score[k], best_step[k] = score, step
-                    if ckpt_dirs[k] is not None:
-                        torch.save(trainer.state_dict(), os.path.join(ckpt_dirs[k], "best_model.pt"))
-                if best_model:
-                    log({"best_score_so_far": best_score[k]})
-                    log({"best_step_so_far": best_step[k]})
+                returns = evaluate(k, trainers[k], step)
+                records.evaluated(k, trainers[k], step, returns, lambda d: logger(tagged(d, k), step + offset))
                 if ckpt_dirs[k] is not None:
-                    torch.save(trainer.state_dict(), os.path.join(ckpt_dirs[k], f"checkpoint_{step}.pt"))
+                    torch.save(trainers[k].state_dict(), os.path.join(ckpt_dirs[k], f"checkpoint_{step}.pt"))
             left = [k for k in active if t < totals[k]]
             if resume and live.commit_due(due, left):
                 commit(active)

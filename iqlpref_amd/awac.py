@@ -36,9 +36,9 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _arena, _lib, _offline_loop
+from . import _arena, _d4rl, _lib, _offline_loop
 from . import custom_offline as _co
-from . import distributed as D
+from ._d4rl import eval_actor  # noqa: F401  (awac:360-377: on the unclamped mean, ``Actor.act`` in eval mode)
 from ._lib import check, ptr, stream_ptr
 from .iql import load_config_for, compute_mean_std, normalize_states, set_seed, mlp_forward_f32  # noqa: F401
 from .multi import ArenaGroup
@@ -392,29 +392,8 @@ def stepper(trainers: Sequence[AdvantageWeightedActorCritic]) -> AWACGroup:
 
 
 # --------------------------------------------------------------------------- #
-# dataset and evaluation helpers (awac:360-401)
+# dataset helpers (awac:380-401; the evaluation, awac:360-377, is ``_d4rl.eval_actor``)
 # --------------------------------------------------------------------------- #
-@torch.no_grad()
-def eval_actor(env, actor: Actor, device: str, n_episodes: int, seed: int) -> np.ndarray:
-    """awac:360-377: ``env.seed(seed)`` once, then ``n_episodes`` chained episodes of a gym < 0.26 environment on
-    the unclamped mean (``actor.eval()``).  The actor is handed back in train mode."""
-    env.seed(seed)
-    actor.eval()
-    episode_rewards = []
-    try:
-        for _ in range(n_episodes):
-            state, done = env.reset(), False
-            episode_reward = 0.0
-            while not done:
-                action = actor.act(state, device)
-                state, reward, done, _ = env.step(action)
-                episode_reward += reward
-            episode_rewards.append(episode_reward)
-    finally:
-        actor.train()
-    return np.asarray(episode_rewards)
-
-
 def return_reward_range(dataset, max_episode_steps):
     """awac:380-392."""
     returns, lengths = [], []
@@ -482,6 +461,20 @@ def _noise_source(noise, K: int, B: int, A: int, device) -> Optional[Callable]:
     return source
 
 
+class _Records(_offline_loop.Records):
+    """awac:487-492: ``eval_score``, the mean return, and -- where the environment has ``get_normalized_score`` --
+    ``d4rl_normalized_score``, the mean of the episodes' scores x 100."""
+    loss_names = LOSS_NAMES
+
+    def __init__(self, env):
+        self.env = env
+
+    def evaluated(self, k, trainer, step, returns, log):
+        log({"eval_score": returns.mean()})
+        if hasattr(self.env, "get_normalized_score"):
+            log({"d4rl_normalized_score": (self.env.get_normalized_score(returns) * 100.0).mean()})
+
+
 def _steps(stream, trainers, buf, gens, B: int, source):
     """The ``steps(group, active, t, n)`` of ``_offline_loop.run``: ``custom_offline._steps`` plus the noise."""
     def steps(group, act, t, n):
@@ -516,19 +509,12 @@ def train(config: TrainConfig, dataset=None, env=None, *,
     _offline_loop.check_sampler(sampler)
     seeds = _offline_loop.group_seeds(config.seed, seeds_per_gpu)
     K = len(seeds)
-    if device is None:
-        device = D.local_device() or ("cuda:0" if config.device == "cuda" else config.device)
-    if env is None:
-        import gym
-        if dataset is None:
-            import d4rl  # noqa: F401  (registers the environments)
-        env = gym.make(config.env_name)
+    device = _d4rl.default_device(config, device)
+    env = _d4rl.default_env(config.env_name, env, dataset)
     set_seed(seeds[0], env, deterministic_torch=config.deterministic_torch)  # awac:418
     state_dim = env.observation_space.shape[0]
     action_dim = env.action_space.shape[0]
-    if dataset is None:
-        import d4rl
-        dataset = d4rl.qlearning_dataset(env)
+    dataset = _d4rl.default_dataset(env, dataset)
 
     # (before anything is uploaded: nothing is launched for a refused shape)
     check_envelope(state_dim, action_dim, config.hidden_dim, config.batch_size)
@@ -549,45 +535,18 @@ def train(config: TrainConfig, dataset=None, env=None, *,
     if logger is None:
         logger = _offline_loop.default_logger(config, K)
 
-    scores: Dict[int, np.ndarray] = {}
-
-    def evaluate(k, trainer, step):
-        scores[k] = eval_actor(env, trainer._actor, device, config.n_test_episodes, config.test_seed)
-        return scores[k]
-
-    tagged = _offline_loop.tag(seeds)
-
-    def tag_and_rename(record, k):
-        """awac:487-492 names: the mean return is ``eval_score``; the normalized score is computed as awac does."""
-        if "evaluation_return" in record:
-            record = {"eval_score": record["evaluation_return"]}
-        return dict(tagged(record, k), _member=k) if "eval_score" in record else tagged(record, k)
-
-    def log(record, t):
-        k = record.pop("_member", None)
-        logger(record, t)
-        if k is not None and hasattr(env, "get_normalized_score"):
-            normalized_eval_scores = env.get_normalized_score(scores[k]) * 100.0
-            logger(tagged({"d4rl_normalized_score": normalized_eval_scores.mean()}, k), t)
-
     _offline_loop.run(
         trainers, seeds, lambda active: stepper([trainers[k] for k in active]), int(config.num_train_ops),
-        int(config.eval_frequency), chunk, log, ckpt_dirs,
-        _steps(stream, trainers, replay_buffer, gens, config.batch_size, source), evaluate=evaluate, normalized=None,
-        tagged=tag_and_rename, loss_names=LOSS_NAMES, best_model=False)
+        int(config.eval_frequency), chunk, logger, ckpt_dirs,
+        _steps(stream, trainers, replay_buffer, gens, config.batch_size, source),
+        lambda k, trainer, step: eval_actor(env, trainer._actor, device, config.n_test_episodes, config.test_seed),
+        _Records(env))
     return trainers if K > 1 else trainers[0]
 
 
 def main(argv=None):
     """``python -m iqlpref_amd.awac --config_path file.yaml --field value ...`` (awac:415 pyrallis.wrap)."""
-    import argparse
-    from .train import parse_overrides
-    ap = argparse.ArgumentParser(prog="python -m iqlpref_amd.awac")
-    ap.add_argument("--config_path", default=None)
-    ap.add_argument("--seeds_per_gpu", type=int, default=int(os.environ.get("AGENTS_PER_GPU", "1")),
-                    help="independent seeds trained side by side on each GPU")
-    args, rest = ap.parse_known_args(argv)
-    train(load_config(args.config_path, **parse_overrides(rest)), seeds_per_gpu=args.seeds_per_gpu)
+    _d4rl.cli("iqlpref_amd.awac", load_config, train, argv)
 
 
 if __name__ == "__main__":

@@ -714,13 +714,13 @@ def _train(config, dataset, eval_env, relabel: Optional[Callable], best_by_retur
     if logger is None:
         logger = _offline_loop.default_logger(config, K)
 
+    normalized = None if normalized_score is None else (lambda scores: normalized_score(dataset, scores))
     _offline_loop.run(
         trainers, seeds, lambda active: stepper(trainers), int(config.update_steps), int(config.eval_every), chunk,
         logger, ckpt_dirs, _steps(stream, trainers, [replay_buffer] * K, gens, config.batch_size),
-        evaluate=lambda k, trainer, step: evaluate(eval_env, trainer.actor, config.eval_episodes, config.eval_seed,
-                                                   device),
-        normalized=None if normalized_score is None else (lambda scores: normalized_score(dataset, scores)),
-        best_by_return=best_by_return, resume=resume, sampler_state=lambda k: generator_state(gens[k]),
+        lambda k, trainer, step: evaluate(eval_env, trainer.actor, config.eval_episodes, config.eval_seed, device),
+        _offline_loop.BestModelRecords(ckpt_dirs, normalized, best_by_return), resume=resume,
+        sampler_state=lambda k: generator_state(gens[k]),
         set_sampler_state=lambda k, st: set_generator_state(gens[k], st))
     return trainers if K > 1 else trainers[0]
 
@@ -810,7 +810,7 @@ def train_runs(configs: Sequence[TrainConfig], dataset=None, reward_models=None,
                run_ids: Optional[Sequence[int]] = None, resume: bool = False) -> List[ImplicitQLearning]:
     """Train every config exactly as ``train(config, ...)`` would train it alone -- the same logged records
     (each with a ``run`` entry besides), evaluations (own actor, ``eval_seed``, ``eval_episodes``, the
-    best-model rule of ``_offline_loop.run``), files under the run's own ``checkpoints_path``
+    best-model rule of ``_offline_loop.BestModelRecords``), files under the run's own ``checkpoints_path``
     (``config.yaml``, ``checkpoint_{step}.pt``, ``best_model.pt``) and final parameters, target, Adam
     moments and actor learning rate, bit for bit -- with the runs packed into seed groups.
 
@@ -920,15 +920,16 @@ def train_runs(configs: Sequence[TrainConfig], dataset=None, reward_models=None,
             trainers[i] = _build_trainer(cfg, cfg.train_seed, *dims[cfg.dataset_id], (high,), device)
         trs = [trainers[i] for i in batch]
         gens = [np.random.RandomState(cfg.train_seed) for cfg in cfgs]
+        normalized = [None if normalized_score is None else
+                      (lambda scores, ds=datasets[cfg.dataset_id]: normalized_score(ds, scores)) for cfg in cfgs]
         # member k has its own buffer, bound, generator, step count and evaluation period (one alone: a ``Solo``)
         _offline_loop.run(
             trs, [cfg.train_seed for cfg in cfgs], lambda act: stepper([trs[k] for k in act]),
             [int(cfg.update_steps) for cfg in cfgs], [int(cfg.eval_every) for cfg in cfgs], chunk, logger, ckpt_dirs,
             _steps(stream, trs, bufs, gens, int(cfgs[0].batch_size)),
-            evaluate=lambda k, trainer, step: evaluate(batch_envs[k], trainer.actor, cfgs[k].eval_episodes,
-                                                       cfgs[k].eval_seed, device),
-            normalized=[None if normalized_score is None else
-                        (lambda scores, ds=datasets[cfg.dataset_id]: normalized_score(ds, scores)) for cfg in cfgs],
+            lambda k, trainer, step: evaluate(batch_envs[k], trainer.actor, cfgs[k].eval_episodes, cfgs[k].eval_seed,
+                                              device),
+            _offline_loop.BestModelRecords(ckpt_dirs, normalized),
             tagged=lambda rec, k: dict(rec, run=run_ids[batch[k]]), resume=resume,
             sampler_state=lambda k: generator_state(gens[k]),
             set_sampler_state=lambda k, st: set_generator_state(gens[k], st))

@@ -968,5 +968,6 @@ def train(config: TrainConfig, dataset=None, reward_model=None, move_stats=None,
         return run_eval(actor=trainer.actor, seed=config.eval_seed + step, **kw)
 
     _offline_loop.run(trainers, seeds, lambda active: stepper(trainers), int(config.update_steps),
-                      int(config.eval_every), chunk, logger, ckpt_dirs, steps, evaluate)
+                      int(config.eval_every), chunk, logger, ckpt_dirs, steps, evaluate,
+                      _offline_loop.BestModelRecords(ckpt_dirs))
     return trainers if K > 1 else trainers[0]

@@ -34,7 +34,7 @@ from typing import Callable, Dict, Optional, Sequence, Tuple, Union
 import numpy as np
 import torch
 
-from . import _lib, _offline_loop
+from . import _d4rl, _lib, _offline_loop
 from . import distributed as D
 from ._lib import check, ptr, stream_ptr
 from .custom_offline import NP_STATE_WORDS, NumpyIndexStream, pack_np_state, unpack_np_state
@@ -518,8 +518,7 @@ def train(config: TrainConfig, env=None, eval_env=None, dataset: Optional[Dict[s
     if not 1 <= K <= _lib.MAX_GROUP:
         raise ValueError(f"seeds_per_gpu must be in 1..{_lib.MAX_GROUP}")
     env, eval_env = _member_envs(env, K, "env"), _member_envs(eval_env, K, "eval_env")
-    if device is None:
-        device = D.local_device() or ("cuda:0" if config.device == "cuda" else config.device)
+    device = _d4rl.default_device(config, device)
     if env is None or eval_env is None or dataset is None:
         gym, d4rl = _gym_and_d4rl()
         env = (lambda k: gym.make(config.env)) if env is None else env

@@ -351,11 +351,10 @@ def train(config: TrainConfig, dataset=None, eval_env=None, *,
     if logger is None:
         logger = _offline_loop.default_logger(config, K)
 
+    normalized = None if normalized_score is None else (lambda scores: normalized_score(dataset, scores))
     _offline_loop.run(
         trainers, seeds, lambda active: stepper(trainers), int(config.update_steps), int(config.eval_every), chunk,
         logger, ckpt_dirs, _co._steps(stream, trainers, [replay_buffer] * K, gens, config.batch_size),
-        evaluate=lambda k, trainer, step: evaluate(eval_env, trainer.actor, config.eval_episodes, config.eval_seed,
-                                                   device),
-        normalized=None if normalized_score is None else (lambda scores: normalized_score(dataset, scores)),
-        loss_names=("actor_loss",), best_model=False)
+        lambda k, trainer, step: evaluate(eval_env, trainer.actor, config.eval_episodes, config.eval_seed, device),
+        _offline_loop.EvalRecords(normalized, ("actor_loss",)))
     return trainers if K > 1 else trainers[0]

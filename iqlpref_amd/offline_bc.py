@@ -50,9 +50,9 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib, _offline_loop, minari_bc
+from . import _d4rl, _lib, _offline_loop, minari_bc
 from . import custom_offline as _co
-from . import distributed as D
+from ._d4rl import eval_actor  # noqa: F401  (dbc:186-203: greedy actions from ``actor.act``)
 from ._lib import check, ptr, stream_ptr
 from .iql import load_config_for, compute_mean_std, normalize_states, set_seed  # noqa: F401  (dbc:68-75, 162-172)
 from .minari_bc import Actor, check_envelope, stepper  # (dbc:242-263 is minari_bc.Actor)
@@ -261,7 +261,7 @@ def select_best_trajectories(observations, actions, next_observations, rewards, 
 
 
 # --------------------------------------------------------------------------- #
-# buffer, trainer, evaluation (dbc:100-159, 186-203, 266-310)
+# buffer, trainer (dbc:100-159, 266-310; the evaluation, dbc:186-203, is ``_d4rl.eval_actor``)
 # --------------------------------------------------------------------------- #
 class ReplayBuffer(_co.ReplayBuffer):
     """dbc:100-159 on the packed device rows: ``load_d4rl_dataset`` (its two ``ValueError``s, dbc:129-136),
@@ -287,28 +287,6 @@ class BC(minari_bc.BC):
         minari_bc.BC.load_state_dict(self, state_dict)  # (total_it := the optimiser's step count)
         if int(state_dict["total_it"]) != self.total_it:
             raise ValueError(f"total_it {state_dict['total_it']} is not the optimiser's step count {self.total_it}")
-
-
-@torch.no_grad()
-def eval_actor(env, actor: nn.Module, device: str, n_episodes: int, seed: int) -> np.ndarray:
-    """dbc:186-203: ``env.seed(seed)`` once, then ``n_episodes`` chained episodes of a gym < 0.26 environment
-    (``reset() -> obs``, ``step() -> (obs, reward, done, info)``), greedy actions from ``actor.act``, returns
-    accumulated from the Python float 0.0.  The actor is handed back in train mode."""
-    env.seed(seed)
-    actor.eval()
-    episode_rewards = []
-    try:
-        for _ in range(n_episodes):
-            state, done = env.reset(), False
-            episode_reward = 0.0
-            while not done:
-                action = actor.act(state, device)
-                state, reward, done, _ = env.step(action)
-                episode_reward += reward
-            episode_rewards.append(episode_reward)
-    finally:
-        actor.train()
-    return np.asarray(episode_rewards)
 
 
 # --------------------------------------------------------------------------- #
@@ -352,17 +330,16 @@ def _load_selected(config: TrainConfig, dataset: Dict[str, np.ndarray], state_di
     return replay_buffer, state_mean, state_std
 
 
-def _reference_records(logger, first_it: int):
-    """``_offline_loop.run`` logs the zero-based step ``t``; dbc logs at ``step=trainer.total_it`` (dbc:386, 413-416),
-    one-based and continuing a loaded model's count, has no raw-return record, and calls the score
-    ``d4rl_normalized_score``."""
-    def log(record, t):
-        if "evaluation_return" in record:
-            return
-        if "normalized_score" in record:
-            record = {("d4rl_normalized_score" if k == "normalized_score" else k): v for k, v in record.items()}
-        logger(record, first_it + t + 1)
-    return log
+class _Records(_offline_loop.Records):
+    """dbc:386, 413-416: every record at ``step=trainer.total_it``, one-based and continuing a loaded model's count
+    (``first_it``); an evaluation logs ``d4rl_normalized_score``, the score of the mean return x 100, nothing else."""
+    loss_names = ("actor_loss",)
+
+    def __init__(self, env, first_it: int):
+        self.env, self.step_offset = env, first_it + 1
+
+    def evaluated(self, k, trainer, step, returns, log):
+        log({"d4rl_normalized_score": np.asarray(self.env.get_normalized_score(returns.mean())).mean() * 100})
 
 
 def train(config: TrainConfig, dataset=None, env=None, *,
@@ -390,16 +367,9 @@ def train(config: TrainConfig, dataset=None, env=None, *,
     K = len(seeds)
     if K > 1 and config.load_model != "":
         raise ValueError("load_model continues one run: seeds_per_gpu must be 1")
-    if device is None:
-        device = D.local_device() or ("cuda:0" if config.device == "cuda" else config.device)
-    if env is None:
-        import gym
-        if dataset is None:
-            import d4rl  # noqa: F401  (registers the environments)
-        env = gym.make(config.env)
-    if dataset is None:
-        import d4rl
-        dataset = d4rl.qlearning_dataset(env)
+    device = _d4rl.default_device(config, device)
+    env = _d4rl.default_env(config.env, env, dataset)
+    dataset = _d4rl.default_dataset(env, dataset)
     state_dim = env.observation_space.shape[0]
     action_dim = env.action_space.shape[0]
 
@@ -423,24 +393,15 @@ def train(config: TrainConfig, dataset=None, env=None, *,
 
     _offline_loop.run(
         trainers, seeds, lambda active: stepper(trainers), int(config.max_timesteps), int(config.eval_freq), chunk,
-        _reference_records(logger, trainers[0].total_it), ckpt_dirs,
-        _co._steps(stream, trainers, [replay_buffer] * K, gens, config.batch_size),
-        evaluate=lambda k, trainer, step: eval_actor(env, trainer.actor, device, config.n_episodes, seeds[k]),
-        normalized=lambda scores: env.get_normalized_score(scores.mean()),
-        loss_names=("actor_loss",), best_model=False)
+        logger, ckpt_dirs, _co._steps(stream, trainers, [replay_buffer] * K, gens, config.batch_size),
+        lambda k, trainer, step: eval_actor(env, trainer.actor, device, config.n_episodes, seeds[k]),
+        _Records(env, trainers[0].total_it))
     return trainers if K > 1 else trainers[0]
 
 
 def main(argv=None):
     """``python -m iqlpref_amd.offline_bc --config_path file.yaml --field value ...`` (dbc:313 pyrallis.wrap)."""
-    import argparse
-    from .train import parse_overrides
-    ap = argparse.ArgumentParser(prog="python -m iqlpref_amd.offline_bc")
-    ap.add_argument("--config_path", default=None)
-    ap.add_argument("--seeds_per_gpu", type=int, default=int(os.environ.get("AGENTS_PER_GPU", "1")),
-                    help="independent seeds trained side by side on each GPU")
-    args, rest = ap.parse_known_args(argv)
-    train(load_config(args.config_path, **parse_overrides(rest)), seeds_per_gpu=args.seeds_per_gpu)
+    _d4rl.cli("iqlpref_amd.offline_bc", load_config, train, argv)
 
 
 if __name__ == "__main__":

@@ -323,7 +323,7 @@ class _Stepper:
         pass
 
 
-def _stub_train(monkeypatch, tmp_path, noise="device", **config_kw):
+def _stub_train(monkeypatch, tmp_path, noise="device", seeds_per_gpu=1, **config_kw):
     _Buffer.made.clear(), _Stepper.seen.clear()
     monkeypatch.setattr(awac, "ReplayBuffer", _Buffer)
     monkeypatch.setattr(awac, "_build_trainer", lambda *a, **k: _Trainer())
@@ -333,7 +333,7 @@ def _stub_train(monkeypatch, tmp_path, noise="device", **config_kw):
     records = []
     dataset = obe.make_dataset(11)
     out = awac.train(config, dataset, obe.OfflineBCEnv(), logger=lambda d, step: records.append((step, dict(d))),
-                     sampler="host", noise=noise, device="cpu", chunk=2)
+                     sampler="host", noise=noise, device="cpu", chunk=2, seeds_per_gpu=seeds_per_gpu)
     return config, records, out, dataset
 
 
@@ -361,6 +361,29 @@ def test_train_bookkeeping_on_a_stub_stepper(monkeypatch, tmp_path):
     np.testing.assert_array_equal(_Buffer.made[0].data["rewards"], raw["rewards"])
     assert dataset["observations"] is not None and np.array_equal(dataset["observations"], _Buffer.made[0].data["observations"])
     assert all(e is None for e in _Stepper.seen)  # noise="device": nothing injected
+
+
+def test_group_records_carry_their_seed_and_no_other_key(monkeypatch, tmp_path):
+    """K = 2: what reaches the logger is a loss record or one of awac's two evaluation records, each under the
+    seed of its member -- nothing the loop and the flavour pass between them leaks into a record."""
+    config, records, trainers, _ = _stub_train(monkeypatch, tmp_path, seeds_per_gpu=2)
+    seeds = [config.seed, config.seed + 1]
+    assert len(trainers) == 2 and sorted(os.listdir(config.checkpoints_path)) == ["config.yaml", "seed_6", "seed_7"]
+    allowed = set(awac.LOSS_NAMES) | {"eval_score", "d4rl_normalized_score", "seed"}
+    assert all(set(d) <= allowed and d["seed"] in seeds for s, d in records)
+    for seed in seeds:
+        mine = [(s, [k for k in d if k != "seed"]) for s, d in records if d["seed"] == seed]
+        assert [s for s, k in mine if k == ["critic_loss", "actor_loss"]] == list(range(7))
+        assert [(s, k) for s, k in mine if len(k) == 1] == [(2, ["eval_score"]), (2, ["d4rl_normalized_score"]),
+                                                            (5, ["eval_score"]), (5, ["d4rl_normalized_score"])]
+    # evaluations in member order, each member's two records together
+    evals = [(s, d["seed"], next(k for k in d if k != "seed")) for s, d in records if "critic_loss" not in d]
+    assert evals == [(t, seed, name) for t in (2, 5) for seed in seeds for name in ("eval_score", "d4rl_normalized_score")]
+    env = awac.wrap_env(obe.OfflineBCEnv(), 0.0, 1.0)
+    scores = awac.eval_actor(env, _Actor(), "cpu", 2, config.test_seed)
+    assert all(d["eval_score"] == scores.mean() for s, d in records if "eval_score" in d)
+    want = (env.get_normalized_score(scores) * 100.0).mean()
+    assert all(d["d4rl_normalized_score"] == want for s, d in records if "d4rl_normalized_score" in d)
 
 
 def test_train_hands_recorded_noise_to_the_steps(monkeypatch, tmp_path):

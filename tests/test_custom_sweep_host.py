@@ -242,7 +242,7 @@ def _loop(totals, everys, chunk):
     _offline_loop.run([object()] * K, list(range(K)), make_group, totals, everys, chunk,
                       lambda d, s: records.append((d, s)), [None] * K, steps,
                       lambda k, tr, step: calls.append(("eval", k, step)) or np.asarray([1.0 * k]),
-                      tagged=lambda rec, k: dict(rec, run=k))
+                      _offline_loop.BestModelRecords([None] * K), tagged=lambda rec, k: dict(rec, run=k))
     return calls, records
 
 

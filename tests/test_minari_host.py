@@ -166,27 +166,29 @@ class _FakeTrainer:
         return {"n": self.saved}
 
 
-def _loop(tmp_path, **kw):
+_half = lambda scores: 0.5 * scores
+
+
+def _loop(tmp_path, recorder):
     records = []
     trainer = _FakeTrainer()
     os.makedirs(tmp_path)
-    width = len(kw.get("loss_names", _offline_loop.LOSS_NAMES))
+    width = len(recorder.loss_names)
     steps = lambda group, active, t, n: [torch.arange(t, t + n, dtype=torch.float32)[:, None].repeat(1, width)]
     _offline_loop.run([trainer], [0], lambda active: None, 6, 3, 4, lambda d, step: records.append((step, dict(d))),
-                      [str(tmp_path)], steps, evaluate=lambda k, tr, step: np.asarray([1.0 + step, 3.0 + step]),
-                      normalized=lambda scores: 0.5 * scores, **kw)
+                      [str(tmp_path)], steps, lambda k, tr, step: np.asarray([1.0 + step, 3.0 + step]), recorder)
     return records, sorted(os.listdir(tmp_path))
 
 
 def test_loop_without_best_model_bookkeeping(tmp_path):
-    """``best_model=False`` with one loss column: bcref's records and files, nothing else; the defaults keep the
-    records and files of every other caller."""
-    rec, files = _loop(tmp_path / "bc", loss_names=("actor_loss",), best_model=False)
+    """``EvalRecords`` with one loss column: bcref's records and files, nothing else; ``BestModelRecords`` keeps
+    the records and files of every other caller."""
+    rec, files = _loop(tmp_path / "bc", _offline_loop.EvalRecords(_half, ("actor_loss",)))
     assert files == ["checkpoint_2.pt", "checkpoint_5.pt"]
     want = [(i, {"actor_loss": float(i)}) for i in range(3)] + [(2, {"evaluation_return": 4.0}), (2, {"normalized_score": 200.0})]
     want += [(i, {"actor_loss": float(i)}) for i in range(3, 6)] + [(5, {"evaluation_return": 7.0}), (5, {"normalized_score": 350.0})]
     assert rec == want
-    rec, files = _loop(tmp_path / "iql")
+    rec, files = _loop(tmp_path / "iql", _offline_loop.BestModelRecords([str(tmp_path / "iql")], _half))
     assert files == ["best_model.pt", "checkpoint_2.pt", "checkpoint_5.pt"]
     assert rec[0] == (0, {"value_loss": 0.0, "q_loss": 0.0, "actor_loss": 0.0})
     assert [list(d)[0] for s, d in rec if s == 2][1:] == ["evaluation_return", "normalized_score", "best_score_so_far",

@@ -272,7 +272,7 @@ class _Stepper:
         pass
 
 
-def _stub_train(monkeypatch, tmp_path, **config_kw):
+def _stub_train(monkeypatch, tmp_path, seeds_per_gpu=1, **config_kw):
     _Buffer.made.clear()
     monkeypatch.setattr(offline_bc, "ReplayBuffer", _Buffer)
     monkeypatch.setattr(offline_bc, "_build_trainer", lambda *a, **k: _Trainer())
@@ -282,7 +282,7 @@ def _stub_train(monkeypatch, tmp_path, **config_kw):
     records = []
     dataset = obe.make_dataset(11, np.float64)  # (float64 rewards: the host restatement, no device)
     out = offline_bc.train(config, dataset, obe.OfflineBCEnv(), logger=lambda d, step: records.append((step, dict(d))),
-                           sampler="host", device="cpu", chunk=2)
+                           sampler="host", device="cpu", chunk=2, seeds_per_gpu=seeds_per_gpu)
     return config, records, out, dataset
 
 
@@ -315,6 +315,25 @@ def test_train_bookkeeping_on_stub_steppers(monkeypatch, tmp_path):
     assert len(cut7["rewards"]) != len(ref["rewards"])
 
 
+def test_group_records_carry_their_seed_and_no_other_key(monkeypatch, tmp_path):
+    """K = 2: what reaches the logger is an ``actor_loss`` or a ``d4rl_normalized_score`` record under the seed of
+    its member, the score that of the member's own evaluation seed."""
+    config, records, trainers, _ = _stub_train(monkeypatch, tmp_path, seeds_per_gpu=2)
+    seeds = [config.seed, config.seed + 1]
+    assert len(trainers) == 2 and sorted(os.listdir(config.checkpoints_path)) == ["config.yaml", "seed_0", "seed_1"]
+    assert all(set(d) <= {"actor_loss", "d4rl_normalized_score", "seed"} and d["seed"] in seeds for s, d in records)
+    env = offline_bc.wrap_env(obe.OfflineBCEnv(), 0.0, 1.0)
+    wants = []
+    for seed in seeds:
+        mine = [(s, d) for s, d in records if d["seed"] == seed]
+        assert [s for s, d in mine if "actor_loss" in d] == list(range(1, 8))
+        want = env.get_normalized_score(offline_bc.eval_actor(env, _Actor(), "cpu", 2, seed).mean()) * 100.0
+        assert [(s, d["d4rl_normalized_score"]) for s, d in mine if "actor_loss" not in d] == [(3, want), (6, want)]
+        wants.append(want)
+    assert wants[0] != wants[1]  # (the evaluation seed is the member's: a record under the wrong seed would show)
+    assert [(s, d["seed"]) for s, d in records if "actor_loss" not in d] == [(3, 0), (3, 1), (6, 0), (6, 1)]
+
+
 def test_train_continues_a_loaded_models_count(monkeypatch, tmp_path):
     path = tmp_path / "model.pt"
     torch.save({"total_it": 40}, path)
@@ -342,6 +361,13 @@ def test_eval_actor_seeds_once_and_chains_episodes():
     assert seeds == [5, 5] and a.shape == (3,) and a.dtype == np.float64
     np.testing.assert_array_equal(a, b)  # seeded again: the same three chained episodes
     assert len(set(a.tolist())) == 3     # (chained: not one episode three times)
+
+
+def test_awacs_eval_actor_is_the_same_object(monkeypatch):
+    from iqlpref_amd import _d4rl, awac
+    assert awac.eval_actor is _d4rl.eval_actor and offline_bc.eval_actor is _d4rl.eval_actor
+    monkeypatch.setattr(offline_bc, "eval_actor", awac.eval_actor)  # (the test above, through awac's name)
+    test_eval_actor_seeds_once_and_chains_episodes()
 
 
 # --------------------------------------------------------------------------- #

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from iqlpref_amd import _offline_loop as ol
+from iqlpref_amd import _resume
 
 LOSS_KEYS = ("value_loss", "q_loss", "actor_loss")
 
@@ -26,6 +27,12 @@ class Trainer:
     def state_dict(self):
         return {"w": torch.tensor([float(self.k), float(self.done)])}
 
+    def resume_state(self):
+        return {"done": self.done}
+
+    def load_resume_state(self, state):
+        self.done = state["done"]
+
 
 class Failure(Exception):
     pass
@@ -42,11 +49,13 @@ class Group:
         self.events.append(("close",))
 
 
-def drive(K, returns, path=None, total=12, normalized=None, best_by_return=False, fail_at=None):
+def drive(K, returns, path=None, total=12, normalized=None, best_by_return=False, fail_at=None, records=None,
+          resume=False):
     """Run the loop (every=6, chunk=4) over fakes; ``returns[b]`` is the mean return of every seed at
     boundary b.  -> (events, trainers, seeds, ckpt_dirs); events are ("group", active) of every ``make_group``
     call (which gives None for K = 1), ("steps", t, n), ("sync",), ("close",), ("eval", k, step) and
-    ("log", record, step) in the order they happened.  ``fail_at``: the evaluation at that step raises."""
+    ("log", record, step) in the order they happened.  ``fail_at``: the evaluation at that step raises.
+    ``records(ckpt_dirs)``: the recorder, instead of ``BestModelRecords``."""
     events = []
     seeds = [40 + k for k in range(K)]
     trainers = [Trainer(k) for k in range(K)]
@@ -77,7 +86,8 @@ def drive(K, returns, path=None, total=12, normalized=None, best_by_return=False
     ckpt_dirs = ol.checkpoint_dirs(Config(checkpoints_path=None if path is None else str(path)), seeds)
     ol.run(trainers, seeds, make_group, total, 6, 4,
            lambda rec, step: events.append(("log", dict(rec), step)), ckpt_dirs, steps, evaluate,
-           normalized=normalized, best_by_return=best_by_return)
+           ol.BestModelRecords(ckpt_dirs, normalized, best_by_return) if records is None else records(ckpt_dirs),
+           resume=resume)
     return events, trainers, seeds, ckpt_dirs
 
 
@@ -271,6 +281,53 @@ def test_total_that_is_no_multiple_of_every(K):
     # the last chunk's losses are flushed at the end
     assert events[-4 * K:] == loss_records(K, seeds, 6, 4)
     assert len([e for e in events if e[0] == "log" and "value_loss" in e[1]]) == 10 * K
+
+
+@pytest.mark.parametrize("K", [1, 3])
+def test_step_offset_moves_every_record_and_no_file_name(K, tmp_path):
+    class Shifted(ol.BestModelRecords):
+        step_offset = 7
+
+    plain, *_ = drive(K, (2.0, 1.0), tmp_path / "plain")
+    events, _, _, dirs = drive(K, (2.0, 1.0), tmp_path / "shifted", records=Shifted)
+    assert any(e[0] == "log" and "value_loss" in e[1] for e in plain) and any("evaluation_return" in e[1] for e in plain
+                                                                               if e[0] == "log")
+    assert events == [("log", e[1], e[2] + 7) if e[0] == "log" else e for e in plain]
+    # what a record says stays zero-based (best_step_so_far), and so do the files
+    assert {e[1]["best_step_so_far"] for e in events if e[0] == "log" and "best_step_so_far" in e[1]} == {5}
+    for d in dirs:
+        assert sorted(f for f in os.listdir(d) if f.endswith(".pt")) == ["best_model.pt", "checkpoint_11.pt",
+                                                                         "checkpoint_5.pt"]
+
+
+def test_resume_generation_loop_entry_is_best_score_best_step_norm(tmp_path):
+    # seed 0 never gets a normalized score, seed 1 gets 0.5 at step 5 (the calls: 0 and 1 at step 5, then at 11)
+    err = ValueError("no reference score")
+    _, _, _, dirs = drive(2, (3.0, 1.0), tmp_path, normalized=scripted([err, 0.5, err, err]), resume=True)
+    step, payloads = _resume.latest(dirs)
+    assert step == 12 and sorted(payloads) == [0, 1]
+    loops = [payloads[k]["loop"] for k in (0, 1)]
+    assert loops == [{"best_score": 3.0, "best_step": 5, "norm": None}, {"best_score": 50.0, "best_step": 5, "norm": 50.0}]
+    for loop in loops:
+        assert sorted(loop) == ["best_score", "best_step", "norm"]
+        assert type(loop["best_score"]) is float and type(loop["best_step"]) is int
+        assert loop["norm"] is None or type(loop["norm"]) is float
+
+
+def test_a_generation_of_the_parent_format_restores_into_best_model_records(tmp_path):
+    """The payload below is written by hand in the format of the commit before the recorders (``run`` built the
+    ``"loop"`` entry itself there): ``BestModelRecords`` must take it as its own."""
+    _resume.write(str(tmp_path), 6, {"finished": False, "trainer": {"done": 6}, "sampler": None,
+                                     "loop": {"best_score": 40.0, "best_step": 5, "norm": 40.0}})
+    # the evaluation at step 11 returns 90 and gets no normalized score: the kept 40 still counts, and 40 is not
+    # beaten -- without the restored norm the raw 90 would be the best, without the restored best 40 would be new
+    events, trainers, _, _ = drive(1, (None, 90.0), tmp_path, normalized=scripted([ValueError("no reference score")]),
+                                   resume=True)
+    assert [e for e in events if e[0] == "steps"] == [("steps", 6, 4), ("steps", 10, 2)] and trainers[0].done == 12
+    assert evaluation_logs(events) == [(("evaluation_return", 90.0), 11), (("best_score_so_far", 40.0), 11),
+                                       (("best_step_so_far", 5), 11)]
+    assert "best_model.pt" not in os.listdir(tmp_path)
+    assert _resume.latest([str(tmp_path)])[1][0]["loop"] == {"best_score": 40.0, "best_step": 5, "norm": 40.0}
 
 
 def test_tag_and_print_logger(capsys, monkeypatch):

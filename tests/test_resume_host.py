@@ -89,7 +89,7 @@ class World:
 
         ol.run(self.trainers, self.seeds, self.make_group, self.totals, self.everys, chunk,
                lambda rec, step: self.records.append((dict(rec), step)), self.dirs, self.steps, evaluate,
-               normalized=lambda scores: scores / 8.0, resume=resume,
+               ol.BestModelRecords(self.dirs, lambda scores: scores / 8.0), resume=resume,
                sampler_state=lambda k: {"draws": self.draws[k]},
                set_sampler_state=lambda k, st: self.draws.__setitem__(k, st["draws"]))
         return self
