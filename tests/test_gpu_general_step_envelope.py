@@ -53,20 +53,14 @@ Every test prints its figures (IQLTEST lines with -s, IQL_TEST_DIAG=<file>).  An
              target within 0.50 ulp32 -- the last rounding alone;
   copies     fp32 max |err| 4.6e-5 (6 x 1024, outputs ~1e5); bf16: 87 of 88 output arrays bit-identical, the other in 0.975.
   The two dropout runs (Philox / injected masks) were bit-identical in losses, gradients and parameters."""
-import os
-
-import numpy as np
 import pytest
 import torch
 
-from oracle import iql_oracle as orc
-from tests import helpers
+from tests import helpers, step_envelope
 
 pytestmark = pytest.mark.gpu
 MODES = ("fp32", "bf16")
-N_FWD = 20
-GROUPS = ("q", "v", "actor")
-LOOSE = {"checks": 0, "uses": []}  # step-2 (case, mode, net) checks at B < 1024, and those that took the loose bound
+LOOSE = step_envelope.new_tally()  # step-2 (case, mode, net) checks at B < 1024, and those that took the loose bound
 
 
 @pytest.fixture(scope="module")
@@ -77,107 +71,21 @@ def gh():
 
 
 def _say(line):
-    print("IQLTEST general-step " + line)
-    path = os.environ.get("IQL_TEST_DIAG")
-    if path:
-        with open(path, "a") as f:
-            f.write("general-step " + line + "\n")
+    step_envelope.say("general-step", line)
 
 
-def _mods(tr):
-    return (("q", tr.qf, tr.q_optimizer), ("v", tr.vf, tr.v_optimizer), ("actor", tr.actor, tr.actor_optimizer))
-
-
-def _state(gh, tr):
-    torch.cuda.synchronize()
-    return tuple(gh.module_params(m) for m in (tr.qf, tr.vf, tr.actor, tr.q_target))
-
-
-def _moments(tr):
-    """group -> name -> (exp_avg, exp_avg_sq) through optimizer.state; zeros before the first step (no state yet)."""
-    out = {}
-    for g, mod, opt in _mods(tr):
-        out[g] = {}
-        for name, p in mod.named_parameters():
-            st = opt.state.get(p) or {}
-            out[g][name] = tuple(st[k].detach().cpu().numpy().copy() if k in st else np.zeros(tuple(p.shape), np.float32)
-                                 for k in ("exp_avg", "exp_avg_sq"))
-    return out
-
-
-def _grads(tr):
-    return {g: {name: p.grad.detach().cpu().numpy().copy() for name, p in mod.named_parameters()} for g, mod, _ in _mods(tr)}
+def _plan(row, mode):
+    """The tile width and orientation the case records are what deep_create's rule, restated, gives."""
+    S, A, NH, H, B, E = row[:6]
+    tq, orient = row[10:12]
+    assert helpers.gs_update_plan(S, A, NH, H, B, E)[:2] == (tq, orient)
+    return f"tq {tq}, hidden/output layers {orient}"
 
 
 def _run(gh, case, mode, inject_masks=False):
-    """Two judged steps of a case; returns what each step left (losses, gradients, state) for bitwise comparisons."""
-    S, A, NH, H, B, E, det, drop, offset, seed, tq, orient = helpers.GS_CASES[case]
-    assert helpers.gs_update_plan(S, A, NH, H, B, E)[:2] == (tq, orient)
-    hyper, nets, data, idx = helpers.gs_inputs(case)
-    tr = gh.make_trainer(hyper, nets, mode, lr=helpers.GS_LR, seed=helpers.GS_SEED, keep_grads=True)
-    assert tr.step_kind(B) == "general"
-    label = f"{case} {mode}" + (" injected masks" if inject_masks else "")
-    _say(f"{label}: tq {tq}, hidden/output layers {orient}, S{S} A{A} {NH}x{H} B{B} E{E}")
-    buf = gh.make_buffer(hyper, data)
-    idx_t = torch.from_numpy(idx).to(gh.DEV)
-    tau = float(np.float32(hyper["tau"]))
-    left, failures = [], []
-    for t in range(helpers.GS_STEPS):
-        before, mom0 = _state(gh, tr), _moments(tr)
-        keeps, kw = helpers.gs_keep_masks(hyper, t), {}
-        if inject_masks:
-            kw["dropout_keep"] = torch.from_numpy(np.stack(keeps)[None].astype(np.uint8)).to(gh.DEV)
-        losses = tr.train_steps(buf, 1, B, indices=idx_t[t:t + 1], graph_unroll=0, **kw).cpu().numpy()[0]
-        after, mom1, grads = _state(gh, tr), _moments(tr), _grads(tr)
-        assert tr.total_it == t + 1
-        left.append((losses, grads, after))
-        ref = helpers.gs_reference_step(hyper, before, mode, orc.gather_batch(data, idx[t]), t, keeps)
-        # 1. losses
-        want = np.array([ref["losses"][k] for k in ("value_loss", "q_loss", "actor_loss")])
-        rel = np.abs(losses - want) / np.where(want == 0, 1.0, np.abs(want))  # (a zero reference: the absolute error)
-        _say(f"{label} step {t + 1}: losses {losses.tolist()} against {want.tolist()}: "
-             f"max rel {rel.max():.2e} (rtol {helpers.GS_LOSS_RTOL[mode]:.0e})")
-        if not np.allclose(losses, want, rtol=helpers.GS_LOSS_RTOL[mode], atol=0):
-            failures.append(f"step {t + 1}: losses {losses.tolist()} against {want.tolist()}")
-        # 2. gradients
-        bad, lines, loose, worst, same = helpers.gs_judge_grads(mode, grads, ref, B)
-        for line in lines:
-            _say(f"{label} step {t + 1} {line}")
-        margins = ", ".join("%s %.1e" % (g, ref["margin"][g]) for g in GROUPS)
-        _say(f"{label} step {t + 1}: largest gradient error {worst:.2e} of the largest entry, bit-identical entries {same:.4f}, "
-             f"loose bound for {loose or 'no net'} (margins {margins})")
-        failures += [f"step {t + 1}: {b}" for b in bad]
-        if B < 1024:
-            if t == 0:
-                assert not loose, f"{label}: step 1 within {helpers.GS_MARGIN} of a kink ({ref['margin']}): pick another seed"
-            else:
-                LOOSE["checks"] += len(GROUPS)
-                LOOSE["uses"] += [(case, mode, g) for g in loose]
-        # 3. the update, from the GPU's own numbers
-        coef = helpers.gs_adam_coef(t + 1, helpers.GS_LR, helpers.GS_LR, hyper["max_steps"])
-        top = {}
-        for gi, g in enumerate(GROUPS):
-            for name in grads[g]:
-                tgt = dict(t0=before[3][name], t1=after[3][name], tau=tau) if g == "q" else {}
-                ub, fig = helpers.gs_judge_update(coef, g, before[gi][name], *mom0[g][name], grads[g][name], after[gi][name],
-                                                  *mom1[g][name], lr=helpers.GS_LR, **tgt)
-                failures += [f"step {t + 1} update {g}/{name}: {b}" for b in ub]
-                for k, v in fig.items():
-                    top[k] = max(top.get(k, 0.0), v)
-        _say(f"{label} step {t + 1} update: exp_avg {top['m']:.3f}e-6, exp_avg_sq {top['v']:.3f}e-6 (bound 1e-6 relative), parameter "
-             f"{top['p_ulp']:.2f} ulp32, beyond one ulp32 {top['p_lr']:.2e} lr (bound 1 ulp32 + 1e-5 lr), target {top['t_ulp']:.2f} ulp32 (bound 2)")
-    # 4. the compute and target copies the second update wrote
-    s, a = data["observations"][:N_FWD], data["actions"][:N_FWD]
-    ts, ta = (torch.from_numpy(np.ascontiguousarray(x)).to(gh.DEV) for x in (s, a))
-    fref = helpers.forward_reference(after, mode, s, a)
-    for which in ("q", "v", "actor", "q_target"):
-        got = tr.forward(which, ts, ta if which in ("q", "q_target") else None).cpu().numpy()
-        ok, text = helpers.forward_judge(mode, got, *fref[which], NH + 1, max(H, S + A))
-        _say(f"{label} forward {which} after step {helpers.GS_STEPS}: {text}")
-        if not ok:
-            failures.append(f"forward {which}: {text}")
-    assert not failures, f"{label}:\n  " + "\n  ".join(failures)
-    return left
+    """Two judged steps of a case (step_envelope.run): what each step left, for bitwise comparisons."""
+    return step_envelope.run(gh, helpers.GS_CASES, case, mode, tag="general-step", step_kind="general", plan=_plan,
+                             tally=LOOSE, inject_masks=inject_masks)
 
 
 @pytest.mark.parametrize("mode", MODES)
@@ -192,15 +100,7 @@ def test_dropout_at_an_odd_width(gh, mode):
     oracle/philox.py), once with the same masks injected through dropout_keep=.  Both runs are judged as every
     case is, and their losses, gradients and parameters are bit-identical to each other."""
     case = "3x33_b17_dropout"
-    own, injected = _run(gh, case, mode), _run(gh, case, mode, inject_masks=True)
-    for t, ((l0, g0, s0), (l1, g1, s1)) in enumerate(zip(own, injected)):
-        np.testing.assert_array_equal(l0.view(np.uint32), l1.view(np.uint32), err_msg=f"step {t + 1} losses")
-        for g in GROUPS:
-            for k in g0[g]:
-                np.testing.assert_array_equal(g0[g][k].view(np.uint32), g1[g][k].view(np.uint32), err_msg=f"step {t + 1} grad {g}/{k}")
-        for a, b in zip(s0, s1):
-            for k in a:
-                np.testing.assert_array_equal(a[k].view(np.uint32), b[k].view(np.uint32), err_msg=f"step {t + 1} {k}")
+    step_envelope.assert_runs_bit_identical(_run(gh, case, mode), _run(gh, case, mode, inject_masks=True))
 
 
 def test_loose_bound_stays_within_its_cap():
