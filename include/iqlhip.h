@@ -904,6 +904,79 @@ int iqlhip_awac_group_train_steps(iqlhip_awac_group *g, const iqlhip_replay_view
                                   const int64_t *const *idx, const float *const *eps, float *const *losses_out,
                                   void *stream);
 
+/* ------------------------------------------------------------------------ */
+/* Offline TD3+BC (algorithms/offline/td3_bc.py, "tdbc"; csrc/td3_bc_step.hip): */
+/* an actor Linear(S,H) ReLU Linear(H,H) ReLU Linear(H,A) Tanh times           */
+/* max_action, two critics Linear(S+A,H) ReLU Linear(H,H) ReLU Linear(H,1), a  */
+/* Polyak target of each of the three (tdbc:244-282); train() as tdbc:324-380: */
+/* the critics every step (MSE against r + (1 - d) discount min Q_target(s',   */
+/* a'), a' the target actor plus clipped noise), and when total_it %           */
+/* policy_freq == 0 the actor (-lmbda mean Q1(s, pi) + mse(pi, a), lmbda =     */
+/* alpha / mean|Q1(s, pi)| at the critic 1 just updated) and the three         */
+/* targets.  Plain Adam; two launches per step, five on an actor step.         */
+/* Envelope (anything else: IQLHIP_ERR_UNSUPPORTED before any HIP call):       */
+/* precision fp32, n_hidden 2, hidden_dim a multiple of 16 in 16..256,         */
+/* state_dim <= 128, action_dim <= 32, no dropout, batch_size 1..65536 (padded */
+/* to whole 16-row slabs inside, the means count the batch_size real rows),    */
+/* policy_freq >= 1, 1..IQLHIP_MAX_GROUP members per group.                    */
+/* Of iqlhip_trainer_config these fields are read: state_dim, action_dim,      */
+/* hidden_dim, n_hidden, batch_size, precision, dropout_p, discount, lr_q      */
+/* (critic 1), lr_v (critic 2), lr_actor, adam_beta1, adam_beta2, adam_eps     */
+/* (one set for the three optimisers), seed (the Philox key of the noise).     */
+/* Of iqlhip_arenas: all five (grads optional).                                */
+/* ------------------------------------------------------------------------ */
+/* Element offsets in the parameter arena, every tensor on a 128-byte line, torch [out][in]
+ * row-major: actor W_1 b_1 .. W_3 b_3, critic 1 the same, critic 2 the same (18 offsets), and the
+ * arena length.  The target arena has the same length and layout: a target tensor sits at the
+ * offset of the tensor it follows.                                                              */
+int iqlhip_td3bc_arena_layout(const iqlhip_trainer_config *cfg, int64_t offsets[18], int64_t *n_params);
+
+typedef struct iqlhip_td3bc iqlhip_td3bc;
+/* Borrows the arenas for the trainer's lifetime; allocates its workspace (padded forward copies
+ * of every weight matrix of the six networks, transposed copies of Linear 2 and 3 of the three
+ * trained ones and of critic 1's Linear 1, the feature-major activation and dz planes, the last
+ * step's eps) on the current device and builds the copies from the masters.  Synchronises the
+ * default stream once.  tau in double, as iqlhip_awac_create takes it (cfg->tau is not read).
+ * policy_noise and noise_clip arrive already multiplied by max_action (tdbc:473-474).          */
+int iqlhip_td3bc_create(iqlhip_td3bc **out, const iqlhip_trainer_config *cfg, double tau, float policy_noise,
+                        float noise_clip, float max_action, float alpha, int64_t policy_freq,
+                        const iqlhip_arenas *arenas);
+int iqlhip_td3bc_destroy(iqlhip_td3bc *t);
+/* Rebuild the copies from the masters and targets (after the arenas were written from outside). */
+int iqlhip_td3bc_sync_weights(iqlhip_td3bc *t, void *stream);
+/* total_it: train() calls so far = Adam `step` of the two critic optimisers, the step of the noise
+ * stream, and what decides the actor steps; actor_it: Adam `step` of the actor's optimiser (its
+ * own count: total_it / policy_freq for a fresh trainer).                                      */
+int iqlhip_td3bc_set_step(iqlhip_td3bc *t, int64_t total_it, int64_t actor_it);
+int iqlhip_td3bc_set_lr(iqlhip_td3bc *t, double lr_actor, double lr_critic_1, double lr_critic_2);
+/* tdbc:324-380 n_steps times on rows idx[i][0..batch) of the view.  idx: device int64
+ * [n_steps][batch], required; values outside the view are clamped into it.  eps: device fp32
+ * [n_steps][batch][action_dim], the standard normals of tdbc:333, or NULL: drawn from the Philox
+ * key `seed` as iqlhip_awac_train_steps draws them, on stream 7.  losses_out: NULL or device fp32
+ * [n_steps][2] (critic_loss, actor_loss; actor_loss is 0 on a step without an actor update).
+ * Plain launches on `stream`; at most ~1024 steps are left queued ahead of the device.         */
+int iqlhip_td3bc_train_steps(iqlhip_td3bc *t, const iqlhip_replay_view *view, int64_t n_steps,
+                             const int64_t *idx, const float *eps, float *losses_out, void *stream);
+/* Device to device into dst (tests, replays): which = 0 the eps of the last step
+ * [batch][action_dim]; 1 + 6 net + c, net = 0 actor, 1 critic 1, 2 critic 2, 3 actor target,
+ * 4 target 1, 5 target 2: c = 0..2 the forward copy of Linear c + 1 [out padded to 16][in padded
+ * to 16], c = 3..5 the transposed copy of Linear c - 2 [in padded][out padded] (Linear 2 and 3 of
+ * the trained nets, Linear 1 of critic 1 only).  Padding is zero.                              */
+int iqlhip_td3bc_copy_out(iqlhip_td3bc *t, int32_t which, float *dst, void *stream);
+
+/* K trainers of one shape (dims, width, batch size) stepped by the same launches, the member as
+ * a launch coordinate; every hyperparameter, policy_freq and the step counts are the member's
+ * own, and the actor launches are issued on a step on which any member's actor steps.  Each
+ * member is bit-identical to stepping it alone.  views[k], idx[k], eps[k], losses_out[k] belong
+ * to member k (eps and losses_out NULL as a whole or per member).  Destroy the group before its
+ * members.                                                                                    */
+typedef struct iqlhip_td3bc_group iqlhip_td3bc_group;
+int iqlhip_td3bc_group_create(iqlhip_td3bc_group **out, iqlhip_td3bc *const *members, int32_t n);
+int iqlhip_td3bc_group_destroy(iqlhip_td3bc_group *g);
+int iqlhip_td3bc_group_train_steps(iqlhip_td3bc_group *g, const iqlhip_replay_view *views, int64_t n_steps,
+                                   const int64_t *const *idx, const float *const *eps, float *const *losses_out,
+                                   void *stream);
+
 #ifdef __cplusplus
 }
 #endif

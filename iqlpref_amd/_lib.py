@@ -211,6 +211,20 @@ SYMBOLS = {
     "iqlhip_awac_group_destroy": (C.c_int, [P]),
     "iqlhip_awac_group_train_steps": (C.c_int, [P, C.POINTER(ReplayView), C.c_int64, C.POINTER(P), C.POINTER(P),
                                                 C.POINTER(P), P]),
+    # offline TD3+BC (csrc/td3_bc_step.hip)
+    "iqlhip_td3bc_arena_layout": (C.c_int, [C.POINTER(TrainerConfig), C.POINTER(C.c_int64 * 18), C.POINTER(C.c_int64)]),
+    "iqlhip_td3bc_create": (C.c_int, [C.POINTER(P), C.POINTER(TrainerConfig), C.c_double, C.c_float, C.c_float, C.c_float,
+                                      C.c_float, C.c_int64, C.POINTER(Arenas)]),
+    "iqlhip_td3bc_destroy": (C.c_int, [P]),
+    "iqlhip_td3bc_sync_weights": (C.c_int, [P, P]),
+    "iqlhip_td3bc_set_step": (C.c_int, [P, C.c_int64, C.c_int64]),
+    "iqlhip_td3bc_set_lr": (C.c_int, [P, C.c_double, C.c_double, C.c_double]),
+    "iqlhip_td3bc_train_steps": (C.c_int, [P, C.POINTER(ReplayView), C.c_int64, P, P, P, P]),
+    "iqlhip_td3bc_copy_out": (C.c_int, [P, C.c_int32, P, P]),
+    "iqlhip_td3bc_group_create": (C.c_int, [C.POINTER(P), C.POINTER(P), C.c_int32]),
+    "iqlhip_td3bc_group_destroy": (C.c_int, [P]),
+    "iqlhip_td3bc_group_train_steps": (C.c_int, [P, C.POINTER(ReplayView), C.c_int64, C.POINTER(P), C.POINTER(P),
+                                                 C.POINTER(P), P]),
 }
 
 _lib = None

@@ -1,6 +1,6 @@
 """The chunked train / evaluate / checkpoint loop of every offline ``train()`` but the window loop's
 (``custom_offline.train`` and ``train_runs``, ``custom_offline_br``, ``custom_offline_bb``, ``minari_iql``,
-``minari_bc``, ``offline_bc``, ``awac``), once, and the setup every ``train()`` shares: the ``sampler`` check, the
+``minari_bc``, ``offline_bc``, ``awac``, ``td3_bc``), once, and the setup every ``train()`` shares: the ``sampler`` check, the
 seeds of a rank, the checkpoint directories, the default logger and the ``seed`` tag of K > 1 records.  The
 offline flavour (``train``, ``sweep.train_runs``) takes that setup from here and runs ``_window_loop``: window
 means instead of every step's losses, a metric exchange instead of a best model.
@@ -142,6 +142,11 @@ class Records:
     loss_names: Sequence[str] = LOSS_NAMES
     step_offset = 0
 
+    def loss_record(self, k: int, row: Sequence[float], step: int) -> Dict[str, float]:
+        """The loss record of member k at the zero-based ``step`` from its row of the loss tensor (a flavour whose
+        steps do not all log every column overrides this; it is logged at ``step + step_offset``)."""
+        return dict(zip(self.loss_names, row))
+
     def evaluated(self, k: int, trainer, step: int, returns: np.ndarray, log: Callable) -> None:
         raise NotImplementedError
 
@@ -235,7 +240,7 @@ def run(trainers: Sequence, seeds: Sequence[int], make_group: Callable, total: P
         raise ValueError("total / every: one entry per member")
     if tagged is None:
         tagged = tag(seeds)
-    loss_names, offset = records.loss_names, int(records.step_offset)
+    offset = int(records.step_offset)
     pending = None  # (first step, members, their device losses) of the chunk whose records are still to be logged
 
     def flush():
@@ -245,8 +250,8 @@ def run(trainers: Sequence, seeds: Sequence[int], make_group: Callable, total: P
         t0, members, losses = pending
         pending = None
         for k, arr in zip(members, (l.cpu().numpy() for l in losses)):
-            for i, row in enumerate(arr.tolist(), t0 + offset):
-                logger(tagged(dict(zip(loss_names, row)), k), i)
+            for i, row in enumerate(arr.tolist(), t0):
+                logger(tagged(records.loss_record(k, row, i), k), i + offset)
 
     t = 0
     finished = set()

@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 HEADER = os.path.join(HERE, "..", "include", "iqlhip.h")
 SOURCES = ["api.hip", "iql_step.hip", "iql_deep.hip", "buffer.hip", "mlp_f32.hip", "cvar.hip", "pt.hip", "pt_general.hip", "prep.hip", "np_sampler.hip", "posterior_choice.hip",
-           "online.hip", "bb_sim.hip", "bc_step.hip", "awac_step.hip"]
+           "online.hip", "bb_sim.hip", "bc_step.hip", "awac_step.hip", "td3_bc_step.hip"]
 LIB = os.path.join(HERE, "libiqlhip.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-value",
          # kernarg preload: the first 16 kernarg dwords (the descriptor pointers) arrive in SGPRs

@@ -33,7 +33,7 @@
 // workspace (iqlhip_awac_copy_out).
 //
 // The slab walk, the tile updates and the host side are slab_step.h's, with this family's policies: four MFMA
-// chains per tile added pairwise (FourChains), the bias gradient summed in double (SumDouble), aw_adam below.
+// chains per tile added pairwise (FourChains), the bias gradient summed in double (SumDouble), step_math.h's adam_apply_v64.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -79,11 +79,6 @@ struct AwShape {
   AwNet net[AW_NETS];
 };
 
-__host__ __device__ inline int aw_out(const AwShape &s, int n, int l) { return l < 3 ? s.H : s.net[n].OUT; }
-__host__ __device__ inline int aw_op(const AwShape &s, int n, int l) { return l < 3 ? s.H : s.net[n].OP; }
-__host__ __device__ inline int aw_in(const AwShape &s, int n, int l) { return l == 0 ? s.net[n].K1 : s.H; }
-__host__ __device__ inline int aw_kp(const AwShape &s, int n, int l) { return l == 0 ? s.net[n].K1P : s.H; }
-
 struct AwMember {
   float *P, *M, *V, *G, *T;  // arenas (G may be null)
   float *ws;
@@ -110,17 +105,6 @@ static_assert(sizeof(AwArgs) <= 4096, "the argument block travels by value");
 // A Linear layer of the slab is slab_layer<FourChains, AW_WAVES>: its n_tiles tiles of 16 features go round the
 // sixteen waves (hidden layers: H / 16 of them; a critic's head: one; the actor's head: AP / 16).
 
-// A standard normal of (row, column) of the step: Box-Muller in double on one Philox block per four columns.
-__device__ __forceinline__ float aw_normal(uint64_t seed, int64_t step, int row, int c, uint32_t stream) {
-  const Philox4 r = philox4x32_10((uint32_t)row * 8u + (uint32_t)(c >> 2), (uint32_t)step, (uint32_t)((uint64_t)step >> 32),
-                                  stream, (uint32_t)seed, (uint32_t)(seed >> 32));
-  const uint32_t ua = (c & 2) ? r.z : r.x, ub = (c & 2) ? r.w : r.y;
-  const double u1 = ((double)ua + 1.0) * (1.0 / 4294967296.0), u2 = (double)ub * (1.0 / 4294967296.0);
-  // (sinpi / cospi: the angle 2 pi u2 without the large-argument reduction of sin / cos, which costs registers)
-  const double rad = sqrt(-2.0 * log(u1)), turn = 2.0 * u2;
-  return (float)(rad * ((c & 1) ? sinpi(turn) : cospi(turn)));
-}
-
 // exp(clamp(_log_std, -20, 2)) (awac:163-164), correctly rounded
 __device__ __forceinline__ float aw_std(float ls) { return (float)exp((double)fminf(fmaxf(ls, -20.f), 2.f)); }
 
@@ -130,133 +114,45 @@ __device__ __forceinline__ float aw_sample(float mean, float sd, float eps) {
   return fminf(fmaxf(mean + eps * sd, -1.f), 1.f);
 }
 
-// awac:275: r + gamma * (1 - d) * q_next in the tensor expression's order
-__device__ __forceinline__ float aw_target(float r, float d, float gamma, float qn) {
-#pragma clang fp contract(off)
-  return r + (gamma * (1.f - d)) * qn;
-}
-
-// awac:215: (1 - tau) * t + tau * p, two rounded products and a sum
-__device__ __forceinline__ float aw_polyak(float one_m_tau, float tau, float t, float p) {
-#pragma clang fp contract(off)
-  return (one_m_tau * t) + (tau * p);
-}
-
-// The three hidden layers of one network over the slab without kept activations: in [16][K1P] -> Ha -> Hb -> Ha.
-// Ends behind a barrier.
+// The walk's pieces are slab_step.h's at this family's sizes: three hidden layers, LDS rows of AW_LS / AW_XS / AW_DS.
+// aw_hidden: a network without kept activations, in -> Ha -> Hb -> Ha.
 __device__ __forceinline__ void aw_hidden(const AwShape &s, const AwMember &m, int n, const float *arena, const float *in,
                                           float *Ha, float *Hb, int wave, int lane) {
   const AwNet &N = s.net[n];
-  const int ht = s.H / 16;
-  const auto relu_to = [&](float *dst, int ob) {
-    return [&, dst, ob](int f, int row, f32x4 z) {
-      const float b = ldg(arena + ob + f);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) dst[(row + e) * AW_LS + f] = fmaxf(z[e] + b, 0.f);
-    };
-  };
-  slab_layer<FourChains, AW_WAVES>(in, AW_XS, m.ws + N.c_w[0], N.K1P, ht, wave, lane, relu_to(Ha, N.o_b[0]));
-  __syncthreads();
-  slab_layer<FourChains, AW_WAVES>(Ha, AW_LS, m.ws + N.c_w[1], s.H, ht, wave, lane, relu_to(Hb, N.o_b[1]));
-  __syncthreads();
-  slab_layer<FourChains, AW_WAVES>(Hb, AW_LS, m.ws + N.c_w[2], s.H, ht, wave, lane, relu_to(Ha, N.o_b[2]));
-  __syncthreads();
+  float *const bufs[3] = {Ha, Hb, Ha};
+  slab_hidden<3, AW_LS, AW_WAVES, FourChains>(in, AW_XS, m.ws, N.c_w, N.K1P, s.H, arena, N.o_b, bufs, nullptr, N.pl_h, s.BP, 0,
+                                             wave, lane);
 }
-
-// A critic's value of the slab's rows, q[16] = h3 W4^T + b4: one tile, its column 0.  Ends behind a barrier.
 __device__ __forceinline__ void aw_q(const AwShape &s, const AwMember &m, int n, const float *arena, const float *h3,
                                      float *q, int wave, int lane) {
-  const AwNet &N = s.net[n];
-  slab_layer<FourChains, AW_WAVES>(h3, AW_LS, m.ws + N.c_w[3], s.H, 1, wave, lane, [&](int f, int row, f32x4 z) {
-    if (f != 0) return;
-    const float b = ldg(arena + N.o_b[3]);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) q[row + e] = z[e] + b;
-  });
-  __syncthreads();
+  slab_q<AW_LS, AW_WAVES, FourChains>(h3, m.ws + s.net[n].c_w[3], s.H, arena + s.net[n].o_b[3], q, wave, lane);
 }
-
-// The three hidden layers of a trained network with the activations kept in H0, H1, H2 and as planes.  Ends
-// behind a barrier; the caller runs the last layer.
+// a trained network with the activations kept in H0, H1, H2 and as planes; the caller runs the last layer
 __device__ __forceinline__ void aw_hidden_kept(const AwShape &s, const AwMember &m, int n, const float *in, int in_stride,
                                                float *H0, float *H1, float *H2, int r0, int wave, int lane) {
   const AwNet &N = s.net[n];
-  const int ht = s.H / 16;
-  const auto keep = [&](float *dst, int ob, int plane) {
-    return [&, dst, ob, plane](int f, int row, f32x4 z) {
-      const float b = ldg(m.P + ob + f);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) z[e] = fmaxf(z[e] + b, 0.f), dst[(row + e) * AW_LS + f] = z[e];
-      slab_plane4(m.ws + plane, s.BP, f, r0 + row, z);
-    };
-  };
-  slab_layer<FourChains, AW_WAVES>(in, in_stride, m.ws + N.c_w[0], N.K1P, ht, wave, lane, keep(H0, N.o_b[0], N.pl_h[0]));
-  __syncthreads();
-  slab_layer<FourChains, AW_WAVES>(H0, AW_LS, m.ws + N.c_w[1], s.H, ht, wave, lane, keep(H1, N.o_b[1], N.pl_h[1]));
-  __syncthreads();
-  slab_layer<FourChains, AW_WAVES>(H1, AW_LS, m.ws + N.c_w[2], s.H, ht, wave, lane, keep(H2, N.o_b[2], N.pl_h[2]));
-  __syncthreads();
+  float *const bufs[3] = {H0, H1, H2};
+  slab_hidden<3, AW_LS, AW_WAVES, FourChains>(in, in_stride, m.ws, N.c_w, N.K1P, s.H, m.P, N.o_b, bufs, m.ws, N.pl_h, s.BP, r0,
+                                             wave, lane);
 }
-
-// The backward of a trained network from the head gradient DZ4 [16][OP] (in LDS, its plane already written):
-// dz3 = (dz4 W4) [h3 > 0] replaces h3 in H2, dz2 = (dz3 W3) [h2 > 0] replaces h2 in H1, dz1 = (dz2 W2) [h1 > 0]
-// goes to its plane only.  Ends behind a barrier.
+// its backward from the head gradient DZ4 (its plane already written): dz1 goes to its plane only
 __device__ __forceinline__ void aw_backward(const AwShape &s, const AwMember &m, int n, const float *DZ4, float *H0,
                                             float *H1, float *H2, int r0, int wave, int lane) {
   const AwNet &N = s.net[n];
-  const int ht = s.H / 16;
-  const auto masked = [&](float *h, int plane, bool keep) {
-    return [&, h, plane, keep](int f, int row, f32x4 g) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        g[e] = h[(row + e) * AW_LS + f] > 0.f ? g[e] : 0.f;
-        if (keep) h[(row + e) * AW_LS + f] = g[e];
-      }
-      slab_plane4(m.ws + plane, s.BP, f, r0 + row, g);
-    };
-  };
-  slab_layer<FourChains, AW_WAVES>(DZ4, AW_DS, m.ws + N.t_w[2], N.OP, ht, wave, lane, masked(H2, N.pl_dz[2], true));
-  __syncthreads();
-  slab_layer<FourChains, AW_WAVES>(H2, AW_LS, m.ws + N.t_w[1], s.H, ht, wave, lane, masked(H1, N.pl_dz[1], true));
-  __syncthreads();
-  slab_layer<FourChains, AW_WAVES>(H1, AW_LS, m.ws + N.t_w[0], s.H, ht, wave, lane, masked(H0, N.pl_dz[0], false));
-  __syncthreads();
+  float *const bufs[3] = {H0, H1, H2};
+  slab_backward<3, AW_LS, AW_DS, AW_WAVES, FourChains>(DZ4, N.OP, m.ws, N.t_w, s.H, bufs, false, m.ws, N.pl_dz, s.BP, r0, wave,
+                                                      lane);
 }
-
-// The slab's rows (awac:120-126): padding rows have no index and read nothing.  X[16][AW_XS] = (s | a | 0),
-// X2 = (s' | 0) or (s | 0) (`next`), rd = reward and done (or null).  Ends behind a barrier.
 __device__ __forceinline__ void aw_gather(const AwShape &s, const AwMember &m, int64_t step, int r0, bool next, float *X,
                                           float *X2, float *rd, int64_t *ridx, int tid) {
-  slab_row_indices(m.idx, step, s.B, r0, m.n_rows, ridx, tid);
-  __syncthreads();
-  for (int i = tid; i < 16 * s.XP; i += AW_THREADS) {
-    const int r = i / s.XP, c = i - r * s.XP;
-    const int64_t row = ridx[r];
-    const bool real = row >= 0;
-    X[r * AW_XS + c] = (real && c < s.S + s.A) ? ldg(m.rows + row * s.row_stride + c) : 0.f;
-    X2[r * AW_XS + c] = (real && c < s.S) ? ldg(m.rows + row * s.row_stride + (next ? s.next_off : 0) + c) : 0.f;
-  }
-  if (rd && tid < 32) {
-    const int64_t row = ridx[tid & 15];
-    rd[tid] = row >= 0 ? ldg(m.rows + row * s.row_stride + s.S + s.A + (tid >> 4)) : 0.f;
-  }
-  __syncthreads();
+  slab_gather<AW_XS, AW_THREADS>(s, m.idx, m.rows, m.n_rows, step, r0, next, X, X2, rd, ridx, tid);
 }
-
-// The slab's standard normals of draw `which` (0: a', 1: pi), one thread per (row, column): read or drawn, kept
-// in the workspace and in EPS[16][AW_DS].  Padding rows draw and read nothing.  No barrier of its own.
+// draw `which` (0: a', 1: pi) of the step
 __device__ __forceinline__ void aw_noise(const AwShape &s, const AwMember &m, int64_t step, int which, float *EPS, int r0,
                                          int tid) {
-  for (int i = tid; i < 16 * s.A; i += AW_THREADS) {
-    const int r = i / s.A, j = i - r * s.A, gr = r0 + r;
-    float ep = 0.f;
-    if (gr < s.B) {
-      ep = m.eps ? ldg(m.eps + ((size_t)(step * 2 + which) * s.B + gr) * s.A + j)
-                 : aw_normal(m.seed, m.step0 + step, gr, j, which ? STREAM_AWAC_PI : STREAM_AWAC_NEXT);
-      stg(m.ws + s.o_eps + ((size_t)which * s.B + gr) * s.A + j, ep);
-    }
-    EPS[r * AW_DS + j] = ep;
-  }
+  const size_t draw = (size_t)s.B * s.A;
+  slab_noise<AW_DS, AW_THREADS>(m.eps ? m.eps + (size_t)(step * 2 + which) * draw : nullptr, m.ws + s.o_eps + which * draw,
+                                m.seed, m.step0 + step, which ? STREAM_AWAC_PI : STREAM_AWAC_NEXT, s.B, s.A, EPS, r0, tid);
 }
 
 // The last layer of the actor over the slab: mu = H2 W4^T + b4 (kept in MU, or not: null) and the clamped sample
@@ -325,7 +221,7 @@ __global__ __launch_bounds__(AW_THREADS) void k_awac_critic_fwd_bwd(const AwArgs
         const int r = row + e;
         if (f == 0 && r0 + r < s.B) {
           const float qn = fminf(qt[0][r], qt[1][r]);
-          const float diff = (z[e] + b) - aw_target(rd[r], rd[16 + r], s.gamma, qn);
+          const float diff = (z[e] + b) - slab_td_target(rd[r], rd[16 + r], s.gamma, qn);
           dz[e] = s.two_over_B * diff;  // mse_loss backward: (2 / B) (q - y)
           // (the logged loss from the same fp32 values without the roundings of q + b, y and q - y)
           const double dd = ((double)z[e] + (double)b) -
@@ -426,39 +322,22 @@ __global__ __launch_bounds__(AW_THREADS) void k_awac_actor_fwd_bwd(const AwArgs 
 // ---------------------------------------------------------------------------------------------------
 // launches 2 and 4: dW per tile, Adam, the refreshed copies, the targets, the logged losses
 // ---------------------------------------------------------------------------------------------------
-// The waves of one network, in order: the 16x16 tiles of W1..W4, then 16 bias entries each of b1..b4.
-__host__ __device__ inline int aw_net_waves(const AwShape &s, int n) {
-  int t = 0;
-  for (int l = 0; l < 4; ++l) t += (aw_op(s, n, l) / 16) * (aw_kp(s, n, l) / 16) + aw_op(s, n, l) / 16;
-  return t;
-}
-
-// step_math.h's adam_apply<false> (torch's _single_tensor_adam) with the second moment b2 v + (1 - b2) g g formed in
-// double from the same fp32 constants and rounded once: torch's mul_ and addcmul_ round four times, and on a
-// one-entry tensor (a critic's last bias) nothing averages that out.
-__device__ __forceinline__ void aw_adam(float &p, float &m, float &v, float g, const AdamCoef &c, float neg_step) {
-#pragma clang fp contract(off)
-  m = __builtin_fmaf(g - m, c.one_m_b1, m);
-  v = (float)((double)c.b2 * (double)v + ((double)c.one_m_b2 * (double)g) * (double)g);
-  const float denom = sqrtf(v) / c.bc2_sqrt + c.eps;
-  p = __builtin_fmaf(neg_step, m / denom, p);
-}
-
-// Wave w of net n's update (w < aw_net_waves): a weight tile or 16 bias entries of Linear l.  TARGET: the target
+// Wave w of net n's update (w < slab_net_waves<4>): a weight tile or 16 bias entries of Linear l.  TARGET: the target
 // net of critic n follows it -- (1 - tau) t + tau p into the target arena and into the target's forward copy.
 template <bool TARGET>
 __device__ __forceinline__ void aw_update_wave(const AwShape &s, const AwMember &m, int n, int w, float neg_step, int lane) {
   const AwNet &N = s.net[n], &TN = s.net[TARGET ? n + (AW_T1 - AW_C1) : n];
-  const auto adam = [&](float &p, float &mm, float &vv, float g) { aw_adam(p, mm, vv, g, m.coef, neg_step); };
-  const auto tile = [&](int l, int off) {
-    return SlabTile{m.P, m.M, m.V, m.G, (size_t)off, aw_out(s, n, l), aw_in(s, n, l), aw_op(s, n, l), aw_kp(s, n, l), s.BP,
-                    m.ws + N.pl_dz[l], m.ws + (l == 0 ? s.pl_x : N.pl_h[l - 1]), m.ws + N.c_w[l],
-                    l > 0 ? m.ws + N.t_w[l - 1] : nullptr, TARGET ? m.ws + TN.c_w[l] : nullptr};
+  const auto adam = [&](float &p, float &mm, float &vv, float g) { adam_apply_v64(p, mm, vv, g, m.coef, neg_step); };
+  const auto tile = [&](int l, bool bias) {
+    return SlabTile{m.P, m.M, m.V, m.G, (size_t)(bias ? N.o_b[l] : N.o_w[l]), slab_out<4>(s, n, l), slab_in(s, n, l),
+                    slab_op<4>(s, n, l), slab_kp(s, n, l), s.BP, m.ws + N.pl_dz[l], m.ws + (l == 0 ? s.pl_x : N.pl_h[l - 1]),
+                    m.ws + N.c_w[l], l > 0 ? m.ws + N.t_w[l - 1] : nullptr, TARGET ? m.ws + TN.c_w[l] : nullptr};
   };
-  const auto target = [&](int off) {  // of the tensor at `off` of the target arena
+  const auto target = [&](int l, bool bias) {  // of that tensor of the target arena
     if constexpr (TARGET) {
+      const int off = bias ? TN.o_b[l] : TN.o_w[l];
       return [&m, &s, off](size_t rel, float p) {
-        const float tv = aw_polyak(s.one_m_tau, s.tau, ldg(m.T + off + rel), p);
+        const float tv = slab_polyak(s.one_m_tau, s.tau, ldg(m.T + off + rel), p);
         stg(m.T + off + rel, tv);
         return tv;
       };
@@ -466,16 +345,7 @@ __device__ __forceinline__ void aw_update_wave(const AwShape &s, const AwMember 
       return SlabNoTarget{};
     }
   };
-  for (int l = 0; l < 4; ++l) {
-    const int nk = aw_kp(s, n, l) / 16, cnt = (aw_op(s, n, l) / 16) * nk;
-    if (w < cnt) return slab_weight_tile<FourChains>(tile(l, N.o_w[l]), w / nk, w % nk, lane, adam, target(TN.o_w[l]));
-    w -= cnt;
-  }
-  for (int l = 0; l < 4; ++l) {
-    const int cnt = aw_op(s, n, l) / 16;
-    if (w < cnt) return slab_bias_tile<SumDouble>(tile(l, N.o_b[l]), w, lane, adam, target(TN.o_b[l]));
-    w -= cnt;
-  }
+  slab_update_wave<4, FourChains, SumDouble>(s, n, w, lane, tile, adam, target);
 }
 
 __global__ __launch_bounds__(256) void k_awac_critic_update(const AwArgs args) {
@@ -483,7 +353,7 @@ __global__ __launch_bounds__(256) void k_awac_critic_update(const AwArgs args) {
   const AwMember &m = args.m[blockIdx.y];
   const int lane = threadIdx.x & 63;
   int w = blockIdx.x * 4 + (threadIdx.x >> 6);  // wave-uniform
-  const int per = aw_net_waves(s, AW_C1);
+  const int per = slab_net_waves<4>(s, AW_C1);
   if (w >= 2 * per) return;
   const int c = w >= per ? 1 : 0;
   aw_update_wave<true>(s, m, AW_C1 + c, w - c * per, m.coef.neg_step[c], lane);
@@ -494,7 +364,7 @@ __global__ __launch_bounds__(256) void k_awac_actor_update(const AwArgs args) {
   const AwMember &m = args.m[blockIdx.y];
   const int lane = threadIdx.x & 63;
   const int w = blockIdx.x * 4 + (threadIdx.x >> 6);  // wave-uniform
-  const int per = aw_net_waves(s, AW_ACTOR);
+  const int per = slab_net_waves<4>(s, AW_ACTOR);
   if (w > per) return;
   if (w < per) return aw_update_wave<false>(s, m, AW_ACTOR, w, m.coef.neg_step[2], lane);
   const int ns = s.BP / 16;
@@ -504,7 +374,7 @@ __global__ __launch_bounds__(256) void k_awac_actor_update(const AwArgs args) {
     const size_t o = (size_t)s.o_log_std + lane;
     float p = ldg(m.P + o), mm = ldg(m.M + o), vv = ldg(m.V + o);
     const float g = (p >= -20.f && p <= 2.f) ? (float)gs * aw_std(p) : 0.f;
-    aw_adam(p, mm, vv, g, m.coef, m.coef.neg_step[2]);
+    adam_apply_v64(p, mm, vv, g, m.coef, m.coef.neg_step[2]);
     stg(m.P + o, p), stg(m.M + o, mm), stg(m.V + o, vv);
     if (m.G) stg(m.G + o, g);
   }
@@ -528,7 +398,7 @@ __global__ void k_awac_sync(const AwShape s, const float *P, const float *T, flo
   const bool tr = kind >= 4;
   if (tr && n >= AW_T1) return;
   const int l = tr ? kind - 3 : kind;
-  const int OUT = aw_out(s, n, l), IN = aw_in(s, n, l), OP = aw_op(s, n, l), KP = aw_kp(s, n, l);
+  const int OUT = slab_out<4>(s, n, l), IN = slab_in(s, n, l), OP = slab_op<4>(s, n, l), KP = slab_kp(s, n, l);
   if (i >= OP * KP) return;
   slab_padded_copy(ws + (tr ? N.t_w[l - 1] : N.c_w[l]), src + N.o_w[l], OUT, IN, OP, KP, tr, i);
 }
@@ -590,8 +460,8 @@ static AwShape awac_arena_shape(const iqlhip_trainer_config *c, int64_t *n_param
   };
   const auto lay = [&](int n) {
     for (int l = 0; l < 4; ++l) {
-      s.net[n].o_w[l] = take((int64_t)aw_out(s, n, l) * aw_in(s, n, l));
-      s.net[n].o_b[l] = take(aw_out(s, n, l));
+      s.net[n].o_w[l] = take((int64_t)slab_out<4>(s, n, l) * slab_in(s, n, l));
+      s.net[n].o_b[l] = take(slab_out<4>(s, n, l));
     }
   };
   lay(AW_ACTOR);
@@ -620,11 +490,11 @@ static size_t awac_plan(AwShape &s) {
   };
   for (int n = 0; n < AW_NETS; ++n) {
     AwNet &N = s.net[n];
-    for (int l = 0; l < 4; ++l) N.c_w[l] = take((size_t)aw_op(s, n, l) * aw_kp(s, n, l));
+    for (int l = 0; l < 4; ++l) N.c_w[l] = take((size_t)slab_op<4>(s, n, l) * slab_kp(s, n, l));
     if (n >= AW_T1) continue;
-    for (int l = 1; l < 4; ++l) N.t_w[l - 1] = take((size_t)aw_kp(s, n, l) * aw_op(s, n, l));
+    for (int l = 1; l < 4; ++l) N.t_w[l - 1] = take((size_t)slab_kp(s, n, l) * slab_op<4>(s, n, l));
     for (int l = 0; l < 3; ++l) N.pl_h[l] = take((size_t)s.H * s.BP);
-    for (int l = 0; l < 4; ++l) N.pl_dz[l] = take((size_t)aw_op(s, n, l) * s.BP);
+    for (int l = 0; l < 4; ++l) N.pl_dz[l] = take((size_t)slab_op<4>(s, n, l) * s.BP);
   }
   s.pl_x = take((size_t)s.XP * s.BP);
   s.o_eps = take((size_t)2 * s.B * s.A);
@@ -704,7 +574,7 @@ extern "C" int iqlhip_awac_copy_out(iqlhip_awac *t, int32_t which, float *dst, v
     const int net = (which - 1) / AW_COPIES, kind = (which - 1) % AW_COPIES, l = kind >= 4 ? kind - 3 : kind;
     if (kind >= 4 && net >= AW_T1) return fail(IQLHIP_ERR_INVALID, "the targets have no transposed copies");
     src = t->ws() + (kind >= 4 ? s.net[net].t_w[l - 1] : s.net[net].c_w[l]);
-    n = (size_t)aw_op(s, net, l) * aw_kp(s, net, l);
+    n = (size_t)slab_op<4>(s, net, l) * slab_kp(s, net, l);
   } else {
     return fail(IQLHIP_ERR_INVALID, "which must be in 0..%d", AW_NETS * AW_COPIES);
   }
@@ -726,7 +596,7 @@ static int awac_run(iqlhip_awac *const *mem, int n, SlabQueueBound &bound, const
     m.loss = losses ? losses[k] : nullptr, m.seed = t->seed, m.step0 = t->total_it;
   }
   const int slabs = a.s.BP / 16;
-  const dim3 g1(slabs, n), g2((2 * aw_net_waves(a.s, AW_C1) + 3) / 4, n), g4((aw_net_waves(a.s, AW_ACTOR) + 1 + 3) / 4, n);
+  const dim3 g1(slabs, n), g2((2 * slab_net_waves<4>(a.s, AW_C1) + 3) / 4, n), g4((slab_net_waves<4>(a.s, AW_ACTOR) + 1 + 3) / 4, n);
   return slab_run(mem, n, bound, n_steps, st, [&](int64_t i) {
     a.step = i;
     for (int k = 0; k < n; ++k) {

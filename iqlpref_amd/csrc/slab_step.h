@@ -1,5 +1,5 @@
-// The slab-step core: what the behaviour-cloning step (bc_step.hip) and the AWAC step (awac_step.hip) are both
-// made of.  A training step of this kind is
+// The slab-step core: what the behaviour-cloning step (bc_step.hip), the AWAC step (awac_step.hip) and the TD3+BC
+// step (td3_bc_step.hip) are made of.  A training step of this kind is
 //
 //   a slab launch    one work-group of WAVES waves walks a 16-row slab of the batch through its layers with the
 //                    activations in LDS (slab_layer), and leaves x, h and dz feature-major ([feature][batch row],
@@ -12,11 +12,15 @@
 // Group members are gridDim.y of a by-value argument block; the host side is one trainer core (SlabTrainer), one
 // group (SlabGroup), one bound on queued work (SlabQueueBound) and one step loop (slab_run).
 //
-// The two families differ on purpose in three pieces of arithmetic; each is a compile-time policy here, never a
-// merged formula ("The slab-step core"):
-//   MFMA accumulation        OneChain (BC)           | FourChains (AWAC: four chains added pairwise)
-//   bias-gradient batch sum  SumFloat (BC)           | SumDouble (AWAC)
-//   Adam                     the `adam` callable: adam_apply<false> (BC) | second moment in double (AWAC)
+// The families differ on purpose in three pieces of arithmetic; each is a compile-time policy here, never a merged
+// formula ("The slab-step core"):
+//                            BC                  | AWAC                          | TD3+BC
+//   MFMA accumulation        OneChain            | FourChains (added pairwise)   | FourChains
+//   bias-gradient batch sum  SumFloat            | SumDouble                     | SumDouble
+//   Adam (the `adam` call)   adam_apply<false>   | adam_apply_v64 on the fp32    | adam_apply_v64 on the doubles beta2
+//                                                | b2, 1 - b2 of AdamCoef        | and 1 - beta2: a third policy
+// The actor-critic families (AWAC, TD3+BC) also share their walk: the gather, the noise, the hidden layers, a critic's
+// head, the backward and the update's wave order, generic over depth and LDS strides (below).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -100,6 +104,152 @@ __device__ __forceinline__ void slab_layer(const float *act, int act_stride, con
     }
     ep(f, 4 * q, acc.sum());
   }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// device: the walk of the actor-critic families (AWAC: L = 4 Linears per network; TD3+BC: L = 3)
+// ---------------------------------------------------------------------------------------------------
+// Their shapes (AwShape, TdShape) spell these fields alike: S, A, B, H, XP, BP, row_stride, next_off and per network
+// net[n].{K1, K1P, OUT, OP}.  Linear l of network n has OUT x IN real entries, padded to OP x KP.
+template <int L, class Shape>
+__host__ __device__ inline int slab_out(const Shape &s, int n, int l) { return l < L - 1 ? s.H : s.net[n].OUT; }
+template <int L, class Shape>
+__host__ __device__ inline int slab_op(const Shape &s, int n, int l) { return l < L - 1 ? s.H : s.net[n].OP; }
+template <class Shape>
+__host__ __device__ inline int slab_in(const Shape &s, int n, int l) { return l == 0 ? s.net[n].K1 : s.H; }
+template <class Shape>
+__host__ __device__ inline int slab_kp(const Shape &s, int n, int l) { return l == 0 ? s.net[n].K1P : s.H; }
+
+// The waves of one network's update, in order: the 16x16 tiles of W1..WL, then 16 bias entries each of b1..bL.
+template <int L, class Shape>
+__host__ __device__ inline int slab_net_waves(const Shape &s, int n) {
+  int t = 0;
+  for (int l = 0; l < L; ++l) t += (slab_op<L>(s, n, l) / 16) * (slab_kp(s, n, l) / 16) + slab_op<L>(s, n, l) / 16;
+  return t;
+}
+
+// The slab's rows: padding rows have no index and read nothing.  X[16][XS] = (s | a | 0) (or null), X2 = (s' | 0) or
+// (s | 0) (`next`; or null), rd = reward and done (or null).  Ends behind a barrier.
+template <int XS, int THREADS, class Shape>
+__device__ __forceinline__ void slab_gather(const Shape &s, const int64_t *idx, const float *rows, int64_t n_rows,
+                                            int64_t step, int r0, bool next, float *X, float *X2, float *rd, int64_t *ridx,
+                                            int tid) {
+  slab_row_indices(idx, step, s.B, r0, n_rows, ridx, tid);
+  __syncthreads();
+  for (int i = tid; i < 16 * s.XP; i += THREADS) {
+    const int r = i / s.XP, c = i - r * s.XP;
+    const int64_t row = ridx[r];
+    const bool real = row >= 0;
+    if (X) X[r * XS + c] = (real && c < s.S + s.A) ? ldg(rows + row * s.row_stride + c) : 0.f;
+    if (X2) X2[r * XS + c] = (real && c < s.S) ? ldg(rows + row * s.row_stride + (next ? s.next_off : 0) + c) : 0.f;
+  }
+  if (rd && tid < 32) {
+    const int64_t row = ridx[tid & 15];
+    rd[tid] = row >= 0 ? ldg(rows + row * s.row_stride + s.S + s.A + (tid >> 4)) : 0.f;
+  }
+  __syncthreads();
+}
+
+// The NH hidden layers (Linear + ReLU) of one network over the slab: in [16][K1P] -> bufs[0] -> .. -> bufs[NH - 1]
+// (LDS, [16][LS]; entries may repeat where nothing is kept), weights from the forward copies ws + c_w[l], biases from
+// arena + o_b[l].  planes (or null): layer l is also kept feature-major at planes + pl_h[l].  Ends behind a barrier.
+template <int NH, int LS, int WAVES, class Acc>
+__device__ __forceinline__ void slab_hidden(const float *in, int in_stride, const float *ws, const int *c_w, int K1P, int H,
+                                            const float *arena, const int *o_b, float *const (&bufs)[NH], float *planes,
+                                            const int *pl_h, int BP, int r0, int wave, int lane) {
+#pragma unroll
+  for (int l = 0; l < NH; ++l) {
+    float *dst = bufs[l];
+    slab_layer<Acc, WAVES>(l == 0 ? in : bufs[l - 1], l == 0 ? in_stride : LS, ws + c_w[l], l == 0 ? K1P : H, H / 16, wave, lane,
+                           [&](int f, int row, f32x4 z) {
+                             const float b = ldg(arena + o_b[l] + f);
+#pragma unroll
+                             for (int e = 0; e < 4; ++e) z[e] = fmaxf(z[e] + b, 0.f), dst[(row + e) * LS + f] = z[e];
+                             if (planes) slab_plane4(planes + pl_h[l], BP, f, r0 + row, z);
+                           });
+    __syncthreads();
+  }
+}
+
+// A critic's value of the slab's rows, q[16] = h Wc^T + b: one tile, its column 0.  Ends behind a barrier.
+template <int LS, int WAVES, class Acc>
+__device__ __forceinline__ void slab_q(const float *h, const float *Wc, int H, const float *bias, float *q, int wave, int lane) {
+  slab_layer<Acc, WAVES>(h, LS, Wc, H, 1, wave, lane, [&](int f, int row, f32x4 z) {
+    if (f != 0) return;
+    const float b = ldg(bias);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) q[row + e] = z[e] + b;
+  });
+  __syncthreads();
+}
+
+// The backward of a trained network from the head gradient DZ [16][DS] (LDS, OP columns): hidden layer l = NH - 1 .. 0
+// takes dz_l = (dz_(l+1) W_(l+1)) [h_l > 0] through the transposed copy ws + t_w[l] of the Linear behind it; it
+// replaces h_l in bufs[l] (layer 0 only when `keep_first`) and, with planes, goes to planes + pl_dz[l].  Ends behind
+// a barrier.
+template <int NH, int LS, int DS, int WAVES, class Acc>
+__device__ __forceinline__ void slab_backward(const float *DZ, int OP, const float *ws, const int *t_w, int H,
+                                              float *const (&bufs)[NH], bool keep_first, float *planes, const int *pl_dz,
+                                              int BP, int r0, int wave, int lane) {
+#pragma unroll
+  for (int l = NH - 1; l >= 0; --l) {
+    float *h = bufs[l];
+    const bool keep = l > 0 || keep_first;
+    slab_layer<Acc, WAVES>(l == NH - 1 ? DZ : bufs[l + 1], l == NH - 1 ? DS : LS, ws + t_w[l], l == NH - 1 ? OP : H, H / 16, wave,
+                           lane, [&](int f, int row, f32x4 g) {
+#pragma unroll
+                             for (int e = 0; e < 4; ++e) {
+                               g[e] = h[(row + e) * LS + f] > 0.f ? g[e] : 0.f;
+                               if (keep) h[(row + e) * LS + f] = g[e];
+                             }
+                             if (planes) slab_plane4(planes + pl_dz[l], BP, f, r0 + row, g);
+                           });
+    __syncthreads();
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// device: arithmetic the actor-critic families (AWAC, TD3+BC) spell the same way
+// ---------------------------------------------------------------------------------------------------
+// A standard normal of (row, column) of the step: Box-Muller in double on one Philox block per four columns.
+__device__ __forceinline__ float slab_normal(uint64_t seed, int64_t step, int row, int c, uint32_t stream) {
+  const Philox4 r = philox4x32_10((uint32_t)row * 8u + (uint32_t)(c >> 2), (uint32_t)step, (uint32_t)((uint64_t)step >> 32),
+                                  stream, (uint32_t)seed, (uint32_t)(seed >> 32));
+  const uint32_t ua = (c & 2) ? r.z : r.x, ub = (c & 2) ? r.w : r.y;
+  const double u1 = ((double)ua + 1.0) * (1.0 / 4294967296.0), u2 = (double)ub * (1.0 / 4294967296.0);
+  // (sinpi / cospi: the angle 2 pi u2 without the large-argument reduction of sin / cos, which costs registers)
+  const double rad = sqrt(-2.0 * log(u1)), turn = 2.0 * u2;
+  return (float)(rad * ((c & 1) ? sinpi(turn) : cospi(turn)));
+}
+
+// The slab's standard normals of one draw, one thread per (row, column): read from eps ([B][A] of this draw) or
+// (null) drawn by slab_normal, kept at `kept` ([B][A], the workspace) and in EPS[16][DS].  Padding rows draw and read
+// nothing.  No barrier of its own.
+template <int DS, int THREADS>
+__device__ __forceinline__ void slab_noise(const float *eps, float *kept, uint64_t seed, int64_t step, uint32_t stream, int B,
+                                           int A, float *EPS, int r0, int tid) {
+  for (int i = tid; i < 16 * A; i += THREADS) {
+    const int r = i / A, j = i - r * A, gr = r0 + r;
+    float ep = 0.f;
+    if (gr < B) {
+      ep = eps ? ldg(eps + (size_t)gr * A + j) : slab_normal(seed, step, gr, j, stream);
+      stg(kept + (size_t)gr * A + j, ep);
+    }
+    EPS[r * DS + j] = ep;
+  }
+}
+
+// awac:275, tdbc:345: r + gamma * (1 - d) * q_next in the tensor expression's order (the product of the two
+// factors first, in either order)
+__device__ __forceinline__ float slab_td_target(float r, float d, float gamma, float qn) {
+#pragma clang fp contract(off)
+  return r + (gamma * (1.f - d)) * qn;
+}
+
+// awac:215, tdbc:79: (1 - tau) * t + tau * p, two rounded products and a sum
+__device__ __forceinline__ float slab_polyak(float one_m_tau, float tau, float t, float p) {
+#pragma clang fp contract(off)
+  return (one_m_tau * t) + (tau * p);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -191,6 +341,23 @@ __device__ __forceinline__ void slab_bias_tile(const SlabTile &t, int bt, int la
   if (q == 0 && f < t.OUT) {
     const float p = slab_adam_entry(t, t.off + f, g, adam);
     if constexpr (!std::is_same_v<std::decay_t<Target>, SlabNoTarget>) target((size_t)f, p);
+  }
+}
+
+// Wave w of network n's update (w < slab_net_waves<L>): a weight tile or 16 bias entries of Linear l.  tile(l, bias)
+// gives the SlabTile of Linear l (off: its weight, or its bias), target(l, bias) the `target` of that tensor.
+template <int L, class Acc, class Sum, class Shape, class Tile, class Adam, class Target>
+__device__ __forceinline__ void slab_update_wave(const Shape &s, int n, int w, int lane, Tile &&tile, Adam &&adam,
+                                                 Target &&target) {
+  for (int l = 0; l < L; ++l) {
+    const int nk = slab_kp(s, n, l) / 16, cnt = (slab_op<L>(s, n, l) / 16) * nk;
+    if (w < cnt) return slab_weight_tile<Acc>(tile(l, false), w / nk, w % nk, lane, adam, target(l, false));
+    w -= cnt;
+  }
+  for (int l = 0; l < L; ++l) {
+    const int cnt = slab_op<L>(s, n, l) / 16;
+    if (w < cnt) return slab_bias_tile<Sum>(tile(l, true), w, lane, adam, target(l, true));
+    w -= cnt;
   }
 }
 

@@ -116,6 +116,23 @@ __device__ __forceinline__ void adam_apply(float &p, float &m, float &v, float g
   }
 }
 
+// adam_apply<false> (torch's _single_tensor_adam) with the second moment b2 v + (1 - b2) g g formed in double and
+// rounded once: torch's mul_ and addcmul_ round four times, and on a one-entry tensor (a critic's last bias) nothing
+// averages that out.  The Adam of the fp32 actor-critic steps.  b2 / one_m_b2: the two constants of that sum -- AWAC
+// widens the fp32 ones of AdamCoef (the overload below); TD3+BC hands in the doubles beta2 and 1 - beta2 themselves:
+// float32(1 - 0.999) alone is 4.7e-8 off in relative terms, 0.4 to 0.8 of an fp32 spacing of v before v is rounded.
+__device__ __forceinline__ void adam_apply_v64(float &p, float &m, float &v, float g, const AdamCoef &c, float neg_step,
+                                               double b2, double one_m_b2) {
+#pragma clang fp contract(off)
+  m = __builtin_fmaf(g - m, c.one_m_b1, m);
+  v = (float)(b2 * (double)v + (one_m_b2 * (double)g) * (double)g);
+  const float denom = sqrtf(v) / c.bc2_sqrt + c.eps;
+  p = __builtin_fmaf(neg_step, m / denom, p);
+}
+__device__ __forceinline__ void adam_apply_v64(float &p, float &m, float &v, float g, const AdamCoef &c, float neg_step) {
+  adam_apply_v64(p, m, v, g, c, neg_step, (double)c.b2, (double)c.one_m_b2);
+}
+
 // beta^t by binary exponentiation (t <= 2^31): a few ulp, ~60 double multiplies
 __host__ __device__ inline double ipow(double b, int64_t t) {
   double r = 1.0;
